@@ -15,8 +15,10 @@ A "step" is one full forward of SynthesizerTrn.infer (text encoder -> stochastic
 length regulator -> flow -> decoder) over one synthetic batch whose inputs are already resident in HBM.
 Durations are pinned to 3 frames/token so the work is fixed, but the duration predictor IS
 executed (its logw is simply not used), so every row of §8a is inside the timed region.  The timed region
-is repeated in blocks of --steps steps until it spans at least --min-seconds; ms_per_step is the median
-block.  Each rank is an independent replica (no collective on the data path) and `value`
+is exactly --steps steps and ms_per_step is its length / --steps (--min-seconds S repeats such blocks until
+they span S seconds and takes the median block).  --dump-outputs DIR writes what the timed path returned in
+its last step as DIR/<name>.npy (write_outputs); the inputs are seeded, so two builds compare output for
+output.  Each rank is an independent replica (no collective on the data path) and `value`
 is the whole-job aggregate.  Next to this device-resident figure the default line carries "host_api": the
 drop-in path a vosk-tts user calls (ids on the host -> int16 PCM on the host, free-running durations, a
 fresh seed per request; what vosk_tts/synth.py:122-131 brackets).  Weights are seeded synthetic tensors of the ru-0.9-multi-shaped
@@ -66,6 +68,28 @@ def settle_gc():
     collector STAYS ENABLED during the timed steps: it only has the steps' own garbage to look at."""
     gc.collect()
     gc.freeze()
+
+
+DUMP_LIMIT_BYTES = 64_000_000
+
+
+def write_outputs(out_dir, arrays, limit=DUMP_LIMIT_BYTES):
+    """--dump-outputs: one DIR/<name>.npy per array, float32 arrays as they are and every other dtype as float64 (integers are
+    exact up to 2**53).  Where the arrays hold more than `limit` bytes in all, each one is cut to a fixed, seeded sample of its
+    share: flattened, the same ascending element indices on every run, so that two builds still compare element for element."""
+    os.makedirs(out_dir, exist_ok=True)
+    arrs = {}
+    for name, a in arrays.items():
+        a = np.asarray(a)
+        arrs[name] = a if a.dtype == np.float32 else a.astype(np.float64)
+    budget = limit - 4096 * len(arrs)  # (room for the .npy headers)
+    total = sum(a.nbytes for a in arrs.values())
+    for name, a in arrs.items():
+        if total > budget:
+            n = int(a.size * (budget / total))
+            idx = np.sort(np.random.default_rng(0).choice(a.size, n, replace=False))
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(out_dir, name + ".npy"), a)
 
 
 def make_workload(name, rng, rank=0, world=1):
@@ -200,6 +224,8 @@ def bench_multistream(args, torch, rank, world, local_rank, dist, as_object=Fals
         t = torch.tensor([elapsed], dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
+    if getattr(args, "dump_outputs", None) and not as_object and rank == 0:
+        write_outputs(args.dump_outputs, {"audio": audio[0], "out_lengths": audio[1]} if batched else {"audio": audio})
     if batched:
         audio, olen = audio
         S_ = int(olen.sum())
@@ -642,11 +668,16 @@ def main():
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-seconds", type=float, default=10.0, help="budget for the CPU-oracle baseline leg")
     ap.add_argument("--no-graph", action="store_true", help="eager launches instead of hipGraph replay")
-    ap.add_argument("--min-seconds", type=float, default=0.5, help="the timed region repeats blocks of --steps steps until it spans this long")
+    ap.add_argument("--min-seconds", type=float, default=0.0,
+                    help="0 (default): the timed region is exactly --steps steps; S > 0: blocks of --steps steps repeat until they span S seconds, "
+                         "ms_per_step from the median block")
     ap.add_argument("--precision", default="f32", choices=["f32", "bf16x3"],
                     help="bf16x3: model created with hparams.conv_precision = 1 (split-bf16 decoder ResBlock convs at batch size)")
     ap.add_argument("--no-host-api", action="store_true", help="skip the host-to-host drop-in path leg of the default run")
     ap.add_argument("--no-extras", action="store_true", help="skip the streaming (c5) and concurrency legs of the default run")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the timed path returned in its last step as DIR/<name>.npy (rank 0; float32 / float64, "
+                         "at most 64 MB in all, a fixed seeded sample beyond that)")
     ap.add_argument("--dry-run", action="store_true", help="no GPU work: exercise launch, barrier and aggregation only (CPU test of the multi-process path)")
     args = ap.parse_args()
 
@@ -696,7 +727,7 @@ def main():
     lib = VitsLib()
     model = lib.create(blob, local_rank)
 
-    def measure(wname, steps, warmup, min_seconds, model=model):
+    def measure(wname, steps, warmup, min_seconds, model=model, dump=False):
         rng = np.random.default_rng(1234)
         ids, lengths, dur = make_workload(wname, rng, rank, world)
         B, Tx = ids.shape
@@ -709,7 +740,7 @@ def main():
         d_len = torch.from_numpy(lengths).to(dev)
         d_sid = torch.full((B,), 2, dtype=torch.int64, device=dev)
         d_dur = torch.from_numpy(dur).to(dev)
-        d_audio = torch.empty((B, S), dtype=torch.float32, device=dev)
+        d_audio = torch.zeros((B, S), dtype=torch.float32, device=dev)  # (zeros: padding the engine leaves alone is the same in every dump)
         sess = VitsDeviceSession(model, B, Tx, Ty)
         sess.set_options(use_graph=not args.no_graph, profile=False)
         sess.set_sdp_always(True)  # durations pinned for fixed work, duration predictor still executed (rows a6-a9)
@@ -758,6 +789,7 @@ def main():
             blocks.append(timed_block())
         elapsed = float(np.median(blocks))
         timed_region_s = float(sum(blocks))
+        outputs = {"audio": d_audio.cpu().numpy()} if dump else None  # the last timed step's result, before the profiled forwards below
         graph_nodes = sess.graph_nodes()
         # did the single-utterance persistent programs run?  (one owner per device -- a token inside the process, a lock file across
         # processes: a second process on the device silently takes the launch path, ~1.5 x slower at c2 -- so the line says which it was)
@@ -937,14 +969,17 @@ def main():
         return dict(B=B, Tx=Tx, Ty=Ty, lengths=lengths, ids=ids, dur=dur, valid_samples=valid_samples, job_samples=job_samples,
                     ms_per_step=ms_per_step, value=value, rtf=rtf, roofline=roofline, scales=scales,
                     timed_region_s=timed_region_s, blocks=len(blocks), launches=graph_nodes or sum(v[0] for v in rep.values()) // nprof,
-                    rank_ms=rank_ms, finite_checked=finite_checked, persistent_per_step=persistent_per_step, rank_persist=rank_persist)
+                    rank_ms=rank_ms, finite_checked=finite_checked, persistent_per_step=persistent_per_step, rank_persist=rank_persist,
+                    outputs=outputs)
 
-    R = measure(args.workload, args.steps, args.warmup, args.min_seconds)
+    R = measure(args.workload, args.steps, args.warmup, args.min_seconds, dump=bool(args.dump_outputs))
+    if args.dump_outputs and rank == 0:
+        write_outputs(args.dump_outputs, R["outputs"])
     B, Tx, Ty, lengths, ids, dur = R["B"], R["Tx"], R["Ty"], R["lengths"], R["ids"], R["dur"]
     valid_samples, ms_per_step, value, rtf, roofline, scales = R["valid_samples"], R["ms_per_step"], R["value"], R["rtf"], R["roofline"], R["scales"]
     batch32 = None
     if args.workload == "c2" and not args.no_batch32:
-        R3 = measure("c3", max(3, min(args.steps, 10)), 2, min(args.min_seconds, 0.5))
+        R3 = measure("c3", max(3, min(args.steps, 10)), 2, 0.5)
         batch32 = {"value": round(R3["value"], 1), "unit": "samples/s", "ms_per_step": round(R3["ms_per_step"], 4),
                    "x_realtime": round(1.0 / R3["rtf"], 1), "batch": R3["B"], "T_x": R3["Tx"], "T_y": R3["Ty"],
                    "samples_per_step_per_gpu": R3["valid_samples"],
@@ -960,7 +995,7 @@ def main():
         hp3 = W.default_hparams()
         hp3.conv_precision = 1
         model3 = lib.create(W.synthetic_blob(hp3, 1234), local_rank)
-        R4 = measure("c3", max(3, min(args.steps, 10)), 2, min(args.min_seconds, 0.5), model=model3)
+        R4 = measure("c3", max(3, min(args.steps, 10)), 2, 0.5, model=model3)
         batch32_bf16x3 = {"value": round(R4["value"], 1), "unit": "samples/s", "ms_per_step": round(R4["ms_per_step"], 4), "dtype": "bf16x3",
                           "x_realtime": round(1.0 / R4["rtf"], 1), "batch": R4["B"], "T_x": R4["Tx"], "T_y": R4["Ty"],
                           "workload": "c3 as batch32, ResBlock, encoder / flow STORE and WaveNet gate convs split-bf16 (hi*hi + hi*lo + lo*hi, fp32 accumulate), the rest fp32",

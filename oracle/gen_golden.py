@@ -222,7 +222,31 @@ def main():
     answers = [g2p.convert(w) for w in words]
     np.savez_compressed(os.path.join(OUT, "g2p.npz"), words=np.array(words), phonemes=np.array(answers))
     print("  g2p.npz")
+    mas_random()
+
+
+def mas_random():
+    """mas_random: the compiled core's paths on tests/conftest.py:random_mas_cases(91) and (92) (the scores are regenerated from
+    the seed by the tests; their sha256 is stored so that a change of the case list cannot go unnoticed)
+        python oracle/gen_golden.py mas_random      # this fixture alone"""
+    import hashlib
+
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    from conftest import random_mas_cases
+
+    mas = refimport.build_reference_mas()
+    arrs = {}
+    for seed in (91, 92):
+        for i, (v, t_ys, t_xs) in enumerate(random_mas_cases(seed)):
+            paths = np.zeros(v.shape, np.int32)
+            mas.maximum_path_c(paths, v.copy(), t_ys, t_xs)
+            arrs[f"s{seed}_{i}_paths"] = paths.astype(np.int8)
+            arrs[f"s{seed}_{i}_values_sha256"] = np.array(hashlib.sha256(v.tobytes()).hexdigest())
+    save("mas_random", **arrs)
 
 
 if __name__ == "__main__":
-    main()
+    if sys.argv[1:] == ["mas_random"]:
+        mas_random()
+    else:
+        main()

@@ -3,7 +3,7 @@
 `torch.onnx.export` (TorchScript exporter) needs the `onnx` package only in its last step, to splice onnxscript
 functions into the serialized model; the reference graphs have none, so that step is bypassed.  Everything else is
 the real exporter: initializer naming, de-duplication, constant folding - exactly what vosk_tts_amd/onnx_import.py must
-undo.  Used by tests/test_onnx_import.py (skipped where /root/reference is absent).
+undo.  Used by oracle/check_onnx_exports.py.
 """
 import io
 import warnings

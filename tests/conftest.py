@@ -124,3 +124,16 @@ def random_mas_cases(seed):
         t_xs[0], t_ys[0] = Tx, Ty
         cases.append((v, t_ys, t_xs))
     return cases
+
+
+def reference_mas_cases(seed):
+    """[(values, t_ys, t_xs, paths)]: random_mas_cases(seed) with the paths the reference's compiled Cython core gives for them
+    (tests/golden/mas_random.npz, oracle/gen_golden.py mas_random; seeds 91 and 92)"""
+    import hashlib
+
+    g = golden("mas_random")
+    out = []
+    for i, (v, t_ys, t_xs) in enumerate(random_mas_cases(seed)):
+        assert hashlib.sha256(v.tobytes()).hexdigest() == str(g[f"s{seed}_{i}_values_sha256"]), f"random_mas_cases({seed}) changed: regenerate the fixture"
+        out.append((v, t_ys, t_xs, g[f"s{seed}_{i}_paths"].astype(np.int32)))
+    return out

@@ -905,15 +905,17 @@ def test_monotonic_alignment_search(hip_lib, oracle_lib):
 
     with pytest.raises(VitsError):
         hip_lib.mas_maximum_path(values, t_ys + 5000, t_xs)
-    # and directly against the reference's compiled core where it is present (oracle/_ref stays in the build container: .gpurunignore)
-    from conftest import load_reference_mas, random_mas_cases
+    # and against the reference's compiled core on random ragged batches (its paths: tests/golden/mas_random.npz; the core itself
+    # as well where build() compiled it into oracle/_ref/mas)
+    from conftest import load_reference_mas, reference_mas_cases
 
     ref = load_reference_mas()
-    if ref is not None:
-        for v, ty, tx in random_mas_cases(92):
-            want_ref = np.zeros(v.shape, np.int32)
-            ref.maximum_path_c(want_ref, v.copy(), ty, tx)
-            assert np.array_equal(hip_lib.mas_maximum_path(v, ty, tx), want_ref), v.shape
+    for v, ty, tx, want_ref in reference_mas_cases(92):
+        assert np.array_equal(hip_lib.mas_maximum_path(v, ty, tx), want_ref), v.shape
+        if ref is not None:
+            live = np.zeros(v.shape, np.int32)
+            ref.maximum_path_c(live, v.copy(), ty, tx)
+            assert np.array_equal(live, want_ref), v.shape
 
 
 def test_long_form_properties_at_c5_size(hip_default):

@@ -143,6 +143,25 @@ def test_bench_reads_rocprofv3_kernel_stats(tmp_path):
     assert bench.rocprof_avg_us(str(tmp_path / "absent.csv"), "x") is None
 
 
+def test_bench_write_outputs(tmp_path):
+    """bench.py --dump-outputs: whole arrays while they fit (float32 kept, integers as exact float64); over the byte limit a
+    seeded sample of every array that is the same on every run and stays under the limit"""
+    import bench
+
+    audio = np.random.default_rng(3).standard_normal((4, 1000)).astype(np.float32)
+    lens = np.array([1000, 700, 3, 0], np.int64)
+    bench.write_outputs(str(tmp_path / "a"), {"audio": audio, "out_lengths": lens})
+    a, l = np.load(tmp_path / "a" / "audio.npy"), np.load(tmp_path / "a" / "out_lengths.npy")
+    assert a.dtype == np.float32 and np.array_equal(a, audio)
+    assert l.dtype == np.float64 and np.array_equal(l, lens)
+    for d in ("b", "c"):
+        bench.write_outputs(str(tmp_path / d), {"audio": audio, "out_lengths": lens}, limit=12000)
+    files = [tmp_path / "b" / "audio.npy", tmp_path / "b" / "out_lengths.npy"]
+    assert sum(os.path.getsize(f) for f in files) <= 12000
+    b, c = np.load(files[0]), np.load(tmp_path / "c" / "audio.npy")
+    assert 0 < b.size < audio.size and np.array_equal(b, c) and np.isin(b, audio).all()
+
+
 @pytest.mark.parametrize("launcher", ["self", "torchrun"])
 def test_bench_multi_rank_entry_point_dry_run(launcher):
     """`python bench.py --gpus 2 ...` must work PLAINLY (it starts its own ranks) and under the driver's

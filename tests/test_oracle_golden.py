@@ -138,17 +138,20 @@ def test_monotonic_alignment_search(oracle_lib):
 
 
 def test_monotonic_alignment_search_vs_the_compiled_reference(oracle_lib):
-    """oracle/_ref/mas: the reference's own core.pyx compiled from /root/reference (build()); the restatement must agree bit
-    for bit on random ragged batches, including what it does to `values` (the reference accumulates in place; ours does not)"""
-    from conftest import load_reference_mas, random_mas_cases
+    """The reference's own core.pyx, compiled: the restatement must agree bit for bit on random ragged batches, and leave
+    `values` alone (the reference accumulates in place; ours does not).  The core's paths are stored in
+    tests/golden/mas_random.npz; where build() compiled the core into oracle/_ref/mas it is also called directly."""
+    from conftest import load_reference_mas, reference_mas_cases
 
     ref = load_reference_mas()
-    if ref is None:
-        pytest.skip("oracle/_ref/mas not built (no /root/reference at build time)")
-    for v, t_ys, t_xs in random_mas_cases(91):
-        want = np.zeros(v.shape, np.int32)
-        ref.maximum_path_c(want, v.copy(), t_ys, t_xs)
+    for v, t_ys, t_xs, want in reference_mas_cases(91):
+        v0 = v.copy()
         assert np.array_equal(oracle_lib.mas_maximum_path(v, t_ys, t_xs), want), v.shape
+        assert np.array_equal(v, v0)
+        if ref is not None:
+            live = np.zeros(v.shape, np.int32)
+            ref.maximum_path_c(live, v.copy(), t_ys, t_xs)
+            assert np.array_equal(live, want), v.shape
 
 
 def test_constants(oracle_lib, oracle_default):
