@@ -75,7 +75,11 @@ typedef struct vits_hparams {
   int32_t flow_wn_layers;    /* models.py:1617  4 */
   int32_t flow_kernel_size;  /* models.py:1615  5 (WN conv and pre-transformer FFN kernel) */
   int32_t flow_dilation_rate;/* models.py:1616  1 */
-  int32_t dec_type;          /* 0 = Multiband_iSTFT_Generator (models.py:974), 1 = Generator (models.py:845) */
+  int32_t dec_type;          /* 0 = Multiband_iSTFT_Generator (models.py:974), 1 = Generator (models.py:845),
+                                2 = Multistream_iSTFT_Generator (models.py:1066): the type-0 tail with a biased subband_conv_post and the
+                                    learned multistream_conv_post.weight [1, subbands, pqmf_taps + 1] as synthesis filter (pqmf_taps even),
+                                3 = iSTFT_Generator (models.py:901): conv_post into istft_n_fft + 2 rows and one iSTFT (subbands must be 1).
+                                Any other value: vits_create returns VITS_ERR_UNSUPPORTED */
   int32_t dec_initial_channel;/* json:67 512 */
   int32_t n_ups;             /* len(json:66) 2 */
   int32_t up_rates[VITS_MAX_UPS];   /* json:66 [4,4] */
@@ -87,7 +91,7 @@ typedef struct vits_hparams {
   int32_t subbands;          /* json:53 4 */
   int32_t istft_n_fft;       /* json:54 16 */
   int32_t istft_hop;         /* json:55 4 */
-  int32_t pqmf_taps;         /* pqmf.py:53 62 */
+  int32_t pqmf_taps;         /* pqmf.py:53 62; dec_type 2: the learned synthesis filter's length - 1 */
   float   pqmf_cutoff;       /* pqmf.py:53 0.15 */
   float   pqmf_beta;         /* pqmf.py:53 9.0 */
   float   dp_tail_bound;     /* modules.py:347 5.0 */
@@ -278,7 +282,8 @@ int vits_stage_regulate(vits_model* m, const float* logw, const int32_t* forced_
 int vits_stage_flow(vits_model* m, const float* z_p, const int64_t* y_lengths, int32_t B, int32_t T_y,
                     const int64_t* sid, float* z);
 /* a15-a21: dec((z*y_mask), g) (models.py:1016-1054 / 872-891, :1703).  z [B,inter,T_y] already masked.
- * audio [B, T_y*hop_length]; audio_mb [B,subbands,T_y*hop/subbands] may be NULL.  sid is used only by the
+ * audio [B, T_y*hop_length]; audio_mb [B,subbands,T_y*hop/subbands] may be NULL (written for dec_type 0 and 2: the sub-band
+ * signal before the x subbands zero-stuffing of the synthesis stage).  sid is used only by the
  * plain Generator variant (dec_type 1: x = conv_pre(x) + cond(g), models.py:873-875) and may be NULL. */
 int vits_stage_decoder(vits_model* m, const float* z, int32_t B, int32_t T_y, const int64_t* sid, float* audio, float* audio_mb);
 

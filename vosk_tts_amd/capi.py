@@ -402,7 +402,7 @@ class VitsModel:
         hop = self.hp.hop_length
         audio = np.empty((B, T * hop), np.float32)
         mb = None
-        if want_mb and self.hp.dec_type == 0:
+        if want_mb and self.hp.dec_type in (0, 2):  # type 2: the sub-band signal before zero-stuffing, as for type 0
             mb = np.empty((B, self.hp.subbands, T * hop // self.hp.subbands), np.float32)
         self.lib.check(self.lib._fn("stage_decoder")(self._h, _p(z, c_f32p), B, T, _p(sid, c_i64p), _p(audio, c_f32p), _p(mb, c_f32p)))
         return audio, mb

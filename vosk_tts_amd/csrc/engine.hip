@@ -152,6 +152,11 @@ int vits_create(const void* blob, size_t bytes, int device, vits_model** out) {
     if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device) == hipSuccess) m->n_cu = cus > 256 ? 256 : cus;
   }
   if (m->hp.abi_version != VITS_ABI_VERSION) { delete m; return fail(VITS_ERR_BLOB, "abi version mismatch"); }
+  if (m->hp.dec_type < 0 || m->hp.dec_type > 3) {
+    const int t = m->hp.dec_type;
+    delete m;
+    return fail(VITS_ERR_UNSUPPORTED, "dec_type %d: 0 = multi-band iSTFT, 1 = HiFi-GAN Generator, 2 = multi-stream iSTFT, 3 = single-band iSTFT", t);
+  }
   m->blob = p; m->blob_bytes = bytes;
   memcpy(&m->n_entries, p + 12 + hb, 4);
   m->entries = reinterpret_cast<const vits_blob_entry*>(p + 16 + hb);
@@ -221,11 +226,11 @@ double vits_algorithmic_flops(const vits_model* m, int32_t B, int32_t Tx, int32_
     C /= 2;
     for (int j = 0; j < hp->n_resk; ++j) dec += rate * hp->n_resd * 2 * (2 * C * C * hp->res_kernels[j]);
   }
-  if (hp->dec_type == 0) {
+  if (hp->dec_type == 0 || hp->dec_type == 2 || hp->dec_type == 3) {
     double P = hp->subbands * (hp->istft_n_fft + 2);
     dec += rate * 2 * C * P * 7;
     dec += rate * hp->subbands * 2 * (hp->istft_n_fft + 2) * hp->istft_n_fft;
-    dec += rate * hp->subbands * hp->istft_hop * 2 * (hp->pqmf_taps + 1);
+    if (hp->dec_type != 3) dec += rate * hp->subbands * hp->istft_hop * 2 * (hp->pqmf_taps + 1);  // synthesis FIR
   } else {
     dec += rate * 2 * C * 7;
   }
@@ -344,7 +349,7 @@ int vits_stage_decoder(vits_model* m, const float* z, int32_t B, int32_t Ty, con
   if (!d_audio) return fail(VITS_ERR_NOMEM, "device alloc failed");
   run_decoder(s, s->zA, false, B, Ty, d_audio, S, nullptr);
   HIP_TRY(hipMemcpyAsync(audio, d_audio, sizeof(float) * (size_t)B * S, hipMemcpyDeviceToHost, s->stream));
-  if (audio_mb && hp.dec_type == 0)
+  if (audio_mb && (hp.dec_type == 0 || hp.dec_type == 2))  // the sub-band signal before zero-stuffing (type 2's y_mb_hat is S x it on every S-th sample)
     HIP_TRY(hipMemcpyAsync(audio_mb, s->dec_bufs[16], sizeof(float) * (size_t)B * S, hipMemcpyDeviceToHost, s->stream));
   return check_err(s);
 }
@@ -590,7 +595,11 @@ int vits_debug_decoder_needs(const vits_hparams* hp, int32_t* out, int32_t cap) 
   if (!hp || !out || hp->n_ups < 0 || hp->n_ups > VITS_MAX_UPS || hp->n_resd < 0 || hp->n_resd > VITS_MAX_RESD || hp->n_resk < 0 || hp->n_resk > VITS_MAX_RESK)
     return -fail(VITS_ERR_ARG, "decoder_needs: bad arguments");
   for (int i = 0; i < hp->n_ups; ++i) if (hp->up_rates[i] < 1) return -fail(VITS_ERR_ARG, "decoder_needs: bad up_rates");
-  if (hp->dec_type == 0 && (hp->istft_hop < 1 || hp->subbands < 1)) return -fail(VITS_ERR_ARG, "decoder_needs: bad tail geometry");
+  if (hp->dec_type < 0 || hp->dec_type > 3) return -fail(VITS_ERR_ARG, "decoder_needs: dec_type %d unsupported", hp->dec_type);
+  if ((hp->dec_type == 0 || hp->dec_type == 2 || hp->dec_type == 3) && (hp->istft_hop < 1 || hp->subbands < 1 || hp->istft_n_fft < 1))
+    return -fail(VITS_ERR_ARG, "decoder_needs: bad tail geometry");
+  if ((hp->dec_type == 0 || hp->dec_type == 2) && hp->pqmf_taps < 0) return -fail(VITS_ERR_ARG, "decoder_needs: bad synthesis filter length");
+  if (hp->dec_type == 3 && hp->subbands != 1) return -fail(VITS_ERR_ARG, "decoder_needs: single-band decoder with subbands != 1");
   const DecNeeds N = decoder_needs(*hp, true);
   std::vector<int32_t> v = {N.pre_out + 3, N.pre_out, N.post_out, N.tail_cols};
   for (int i = 0; i < hp->n_ups; ++i) {

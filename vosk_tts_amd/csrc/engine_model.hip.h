@@ -83,7 +83,8 @@ struct vits_model {
   ConvW conv_pre, conv_post;
   std::vector<UpW> ups;
   std::vector<ResBlockW> rb;
-  float *istft_basis = nullptr, *pqmf = nullptr;
+  float *istft_basis = nullptr, *pqmf = nullptr;  // pqmf: [S][taps+1] synthesis filter (dec_type 0: PQMF design, 2: learned)
+  size_t tail_lds = 0;  // dynamic LDS of the fused decoder tail (istft_tail_kernel), checked against the device limit at load
   bool use_g = false;
   float* zeros = nullptr;  // 4096 zeros: the "unused" parameter pointers of persistent-kernel steps (persist.hip.h)
   int* ps_dbg = nullptr;   // device words read / written by persist_kernel: [0] poll-round limit (0 = default), [1] completed persistent launches
@@ -316,9 +317,12 @@ static int load_decoder(vits_model* m) {
       if (u <= 0 || Ku < u) return fail(VITS_ERR_BLOB, "decoder stage %d: upsample rate %d / kernel %d invalid", i, u, Ku);
       rate *= u;
     }
-    if (hp.dec_type == 0) {
-      if (hp.subbands <= 0 || hp.istft_hop <= 0 || hp.istft_n_fft <= 0 || hp.istft_n_fft % hp.istft_hop || hp.pqmf_taps <= 0)
+    if (hp.dec_type == 0 || hp.dec_type == 2 || hp.dec_type == 3) {
+      if (hp.subbands <= 0 || hp.istft_hop <= 0 || hp.istft_n_fft <= 0 || hp.istft_n_fft % hp.istft_hop || (hp.dec_type != 3 && hp.pqmf_taps <= 0))
         return fail(VITS_ERR_BLOB, "iSTFT / PQMF parameters invalid (subbands %d, n_fft %d, hop %d, taps %d)", hp.subbands, hp.istft_n_fft, hp.istft_hop, hp.pqmf_taps);
+      if (hp.dec_type == 2 && hp.pqmf_taps % 2)
+        return fail(VITS_ERR_BLOB, "multi-stream synthesis filter of %d taps: the length must be odd", hp.pqmf_taps + 1);
+      if (hp.dec_type == 3 && hp.subbands != 1) return fail(VITS_ERR_BLOB, "single-band iSTFT decoder with subbands %d (must be 1)", hp.subbands);
       rate *= (long long)hp.istft_hop * hp.subbands;
     }
     if (hp.hop_length <= 0 || rate != hp.hop_length)
@@ -343,7 +347,8 @@ static int load_decoder(vits_model* m) {
       rf += worst / rate;
     }
     rf += 4.0 / rate;  // conv_post k = 7 (+ reflection pad)
-    if (hp.dec_type == 0) rf += ((double)hp.istft_n_fft / hp.istft_hop + (hp.pqmf_taps / 2.0) / hp.subbands / hp.istft_hop) / rate;
+    if (hp.dec_type == 0 || hp.dec_type == 2) rf += ((double)hp.istft_n_fft / hp.istft_hop + (hp.pqmf_taps / 2.0) / hp.subbands / hp.istft_hop) / rate;
+    if (hp.dec_type == 3) rf += ((double)hp.istft_n_fft / hp.istft_hop) / rate;  // iSTFT only, no synthesis filter
     m->rag_halo = (int)ceil(rf) + 2;
     if (m->rag_halo < 32) m->rag_halo = 32;
     if (m->rag_halo > 4096) return fail(VITS_ERR_UNSUPPORTED, "decoder receptive field of %d frames is not supported", m->rag_halo);
@@ -394,9 +399,22 @@ static int load_decoder(vits_model* m) {
     }
   }
   if (m->missing) return VITS_ERR_BLOB;
-  if (hp.dec_type == 0) {
+  if (hp.dec_type == 0 || hp.dec_type == 2 || hp.dec_type == 3) {
     const int S = hp.subbands, N = hp.istft_n_fft, hop = hp.istft_hop, cut = N / 2 + 1;
-    m->conv_post = conv_from(m, "dec.subband_conv_post", S * (N + 2), C, 7, false, false);
+    // the fused tail keeps the frames' spectra, the basis (and for 0 / 2 the sub-band samples and the filter) in LDS
+    {
+      int lds_max = 0;
+      if (hipDeviceGetAttribute(&lds_max, hipDeviceAttributeMaxSharedMemoryPerBlock, m->device) != hipSuccess || lds_max <= 0) lds_max = 65536;
+      if (lds_max > 65536) lds_max = 65536;  // (beyond 64 KiB a dynamic allocation needs a per-kernel attribute: not used)
+      m->tail_lds = tail_lds_bytes(hp.dec_type != 3, S, N, hop, hp.pqmf_taps);
+      if (m->tail_lds > (size_t)lds_max)
+        return fail(VITS_ERR_UNSUPPORTED, "decoder tail geometry (subbands %d, n_fft %d, hop %d, taps %d) needs %zu bytes of LDS > %d", S, N, hop,
+                    hp.pqmf_taps, m->tail_lds, lds_max);
+    }
+    if (hp.dec_type == 3)  // iSTFT_Generator.conv_post: n_fft + 2 rows, no bias (models.py:932)
+      m->conv_post = conv_from(m, "dec.conv_post", N + 2, C, 7, false, false);
+    else  // Multistream_iSTFT_Generator's subband_conv_post has a bias (models.py:1095), the multi-band one has none (:1003)
+      m->conv_post = conv_from(m, "dec.subband_conv_post", S * (N + 2), C, 7, hp.dec_type == 2, false);
     // OnnxSTFT inverse basis (stft.py:191-214): pinv(scale*[Re F;Im F]).T * hann == irfft synthesis rows / scale
     std::vector<float> basis((size_t)2 * cut * N);
     const double PI_D = 3.14159265358979323846, scale = (double)N / hop;
@@ -409,8 +427,15 @@ static int load_decoder(vits_model* m) {
       }
     }
     m->istft_basis = upload(m, basis.data(), basis.size());
-    // PQMF synthesis filter (pqmf.py:15-43,64-75)
+    if (hp.dec_type == 3) return m->missing ? VITS_ERR_BLOB : VITS_OK;
     const int taps = hp.pqmf_taps, Lf = taps + 1;
+    if (hp.dec_type == 2) {  // learned synthesis filter multistream_conv_post.weight [1, S, taps + 1] (models.py:1107) == [S][Lf]
+      const float* w = tget(m, 3, 1, S, Lf, "dec.multistream_conv_post.weight");
+      if (m->missing) return VITS_ERR_BLOB;
+      m->pqmf = upload(m, w, (size_t)S * Lf);
+      return m->missing ? VITS_ERR_BLOB : VITS_OK;
+    }
+    // PQMF synthesis filter (pqmf.py:15-43,64-75)
     std::vector<double> hpz(Lf);
     for (int n = 0; n < Lf; ++n) {
       const double xx = n - 0.5 * taps;

@@ -277,11 +277,12 @@ static void plan(vits_session* s, int B, int Tx, int Ty) {
   }
   // two alternating sets of 7 stage buffers (stage i reads set (i-1)&1's res-chain, writes set i&1)
   for (int k = 0; k < 14; ++k) s->dec_bufs.push_back(bump<float>(s, B * stage_max));
-  if (hp.dec_type == 0) {
+  if (hp.dec_type == 0 || hp.dec_type == 2 || hp.dec_type == 3) {
+    // post-conv output [B, S*(N+2), t+1]; the sub-band signal [B, S, t*hop] (types 0 and 2: the single-band decoder writes audio directly)
     size_t P = (size_t)hp.subbands * (hp.istft_n_fft + 2);
     size_t t = T; for (int i = 0; i < hp.n_ups; ++i) t *= hp.up_rates[i];
     s->dec_bufs.push_back(bump<float>(s, B * P * (t + 1)));
-    s->dec_bufs.push_back(bump<float>(s, B * hp.subbands * t * hp.istft_hop));
+    s->dec_bufs.push_back(bump<float>(s, hp.dec_type == 3 ? 64 : B * hp.subbands * t * hp.istft_hop));
   } else {
     size_t t = T; for (int i = 0; i < hp.n_ups; ++i) t *= hp.up_rates[i];
     s->dec_bufs.push_back(bump<float>(s, B * t));

@@ -416,9 +416,12 @@ static DecNeeds decoder_needs(const vits_hparams& hp, bool continuation) {
   DecNeeds N;
   if (!continuation) return N;  // halo 0: every item is decoded as if alone (zeros beyond its own end at every stage)
   int need;  // columns the NEXT consumer wants beyond len * rate, at the current rate
-  if (hp.dec_type == 0) {
+  if (hp.dec_type == 0 || hp.dec_type == 2) {
     // iSTFT frame f feeds sub-band samples [f hop, f hop + n_fft); PQMF synthesis reaches (taps / 2) / subbands sub-band samples ahead
+    // (dec_type 2: the same geometry with the learned filter's taps)
     need = (hp.istft_n_fft + hp.istft_hop - 1) / hp.istft_hop + ((hp.pqmf_taps / 2 + hp.subbands - 1) / hp.subbands + hp.istft_hop - 1) / hp.istft_hop + 2;
+  } else if (hp.dec_type == 3) {
+    need = (hp.istft_n_fft + hp.istft_hop - 1) / hp.istft_hop + 2;  // the iSTFT's reach only: no synthesis filter
   } else {
     need = 0;
   }
@@ -534,12 +537,13 @@ static void run_decoder(vits_session* s, const float* z, bool mask_in, int B, in
   }
   float* post = s->dec_bufs[15];
   float* mb = d_mb ? d_mb : s->dec_bufs[16];
-  if (hp.dec_type == 0) {
-    // leaky_relu(0.01) -> ReflectionPad1d((1,0)) -> subband_conv_post (models.py:1038-1040)
+  if (hp.dec_type == 0 || hp.dec_type == 2 || hp.dec_type == 3) {
+    // leaky_relu(0.01) -> ReflectionPad1d((1,0)) -> subband_conv_post (models.py:1038-1040; dec_type 2 with its bias, :1095-1097;
+    // dec_type 3: conv_post into n_fft + 2 rows, :943-945)
     const int Tp = T + 1, Pc = m->conv_post.M;
     memset(&P, 0, sizeof P);
     P.n_groups = 1;
-    P.g[0].x = in1; P.g[0].x2 = in2; P.g[0].x3 = in3; P.g[0].w = m->conv_post.w; P.g[0].y = post;
+    P.g[0].x = in1; P.g[0].x2 = in2; P.g[0].x3 = in3; P.g[0].w = m->conv_post.w; P.g[0].bias = m->conv_post.bias; P.g[0].y = post;
     P.g[0].K = 7; P.g[0].dil = 1; P.g[0].pad_l = 4; P.g[0].n_sg = m->conv_post.n_sg;
     P.B = B; P.Cin = C; P.x_ch_sign = 1; P.x_bstride = (long long)C * T; P.Tin = T; P.Tin_stride = T;
     P.M = m->conv_post.Mpad; P.Cout = Pc; P.Tout = Tp; P.Tout_stride = Tp; P.y_bstride = (long long)Pc * Tp;
@@ -548,17 +552,25 @@ static void run_decoder(vits_session* s, const float* z, bool mask_in, int B, in
     P.rag_out_cap_add = 1;  // T + 1 output columns
     launch_conv(s, P, EPI_STORE, "dec.conv_post");
     const int S = hp.subbands, N = hp.istft_n_fft, hop = hp.istft_hop, Tm = T * hop;
-    if (g_tail_impl == 0) {  // one launch: exp/sin, iSTFT and PQMF through LDS
-      ProfScope ps(s, "istft_pqmf", 0, "istft_pqmf_kernel");
+    if (hp.dec_type == 3) {  // single band: the iSTFT samples are the waveform
+      if (g_tail_impl == 0) {  // one launch: exp/sin and iSTFT through LDS, straight to audio
+        ProfScope ps(s, "istft", 0, "istft_tail_kernel<false>");
+        TailParams tp{post, m->istft_basis, nullptr, nullptr, d_audio, 1, N, hop, Tp, Tm, 0, audio_bstride, rag_tail, hop};
+        hipLaunchKernelGGL(istft_tail_kernel<false>, dim3(cdiv(Tm, TAIL_SB), B), dim3(256), m->tail_lds, s->stream, tp);
+      } else {
+        ProfScope ps(s, "istft", 0, "istft_kernel");
+        hipLaunchKernelGGL(istft_kernel, dim3(cdiv(Tm, 256), 1, B), dim3(256), 0, s->stream, post, m->istft_basis, d_audio, 1, N, hop, Tp, Tm,
+                           audio_bstride, rag_tail, hop, 1);
+      }
+    } else if (g_tail_impl == 0) {  // one launch: exp/sin, iSTFT and PQMF (dec_type 2: the learned filter) through LDS
+      ProfScope ps(s, "istft_pqmf", 0, "istft_tail_kernel<true>");
       TailParams tp{post, m->istft_basis, m->pqmf, mb, d_audio, S, N, hop, Tp, Tm, hp.pqmf_taps, audio_bstride, rag_tail, hop};  // (rag_tail: conv_post columns that exist)
-      const int HM = (hp.pqmf_taps / 2 + S - 1) / S + 1, nsub = TAIL_MB + 2 * HM, FR = (nsub + N) / hop + 2;
-      const size_t lds = ((size_t)2 * S * (N / 2 + 1) * FR + (size_t)S * nsub + (size_t)(N + 2) * N + (size_t)S * (hp.pqmf_taps + 1)) * sizeof(float);
-      hipLaunchKernelGGL(istft_pqmf_kernel, dim3(cdiv(Tm, TAIL_MB), B), dim3(256), lds, s->stream, tp);
+      hipLaunchKernelGGL(istft_tail_kernel<true>, dim3(cdiv(Tm, TAIL_MB), B), dim3(256), m->tail_lds, s->stream, tp);
     } else {
       {
         ProfScope ps(s, "istft", 0, "istft_kernel");
         hipLaunchKernelGGL(istft_kernel, dim3(cdiv(Tm, 256), S, B), dim3(256), 0, s->stream, post, m->istft_basis, mb, S, N, hop, Tp, Tm,
-                           rag_tail, hop);
+                           (long long)S * Tm, rag_tail, hop, 0);
       }
       {
         ProfScope ps(s, "pqmf", 0, "pqmf_synthesis_kernel");

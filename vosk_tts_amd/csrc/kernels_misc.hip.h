@@ -964,12 +964,16 @@ __global__ void pcm16_kernel(const float* audio, long long a_bstride, int16_t* o
 // spec = exp(x[:, :, :cut]); phase = pi*sin(x[:, :, cut:]) (models.py:1043-1044);
 // OnnxSTFT.inverse (stft.py:246-262): conv_transpose1d with the windowed pinv-DFT basis, stride hop,
 // * n_fft/hop, trim n_fft/2 both sides.  One thread per sub-band output sample.
-// post: [B, S*(N+2), Tp]; mb: [B, S, Tm], Tm = (Tp-1)*hop.  basis: [N+2][N].
+// post: [B, S*(N+2), Tp]; mb: [B, S, Tm] with batch stride mb_bstride, Tm = (Tp-1)*hop.  basis: [N+2][N].
+// zero_pad: samples beyond a ragged item's end are written as zeros (the single-band decoder writes the waveform itself here).
 __global__ void istft_kernel(const float* post, const float* basis, float* mb, int S, int N, int hop, int Tp, int Tm,
-                             const int* rag, int rag_mul) {
+                             long long mb_bstride, const int* rag, int rag_mul, int zero_pad) {
   const int n = blockIdx.x * blockDim.x + threadIdx.x, s = blockIdx.y, b = blockIdx.z;
   if (n >= Tm) return;
-  if (rag && n >= rag[b] * rag_mul) return;  // ragged batch: beyond this item's length + halo
+  if (rag && n >= rag[b] * rag_mul) {  // ragged batch: beyond this item's length + halo
+    if (zero_pad) mb[(long long)b * mb_bstride + (long long)s * Tm + n] = 0.f;
+    return;
+  }
   const int cut = N / 2 + 1, C = S * (N + 2);
   const int np = n + N / 2;
   int t_hi = np / hop;
@@ -992,7 +996,7 @@ __global__ void istft_kernel(const float* post, const float* basis, float* mb, i
       a += mag * cs * basis[k * N + j] + mag * sn * basis[(cut + k) * N + j];
     }
   }
-  mb[((long long)b * S + s) * Tm + n] = a * ((float)N / (float)hop);
+  mb[(long long)b * mb_bstride + (long long)s * Tm + n] = a * ((float)N / (float)hop);
 }
 
 // PQMF.synthesis (pqmf.py:105-116) in polyphase form: zero-stuffing by S with gain S, pad taps/2,
@@ -1024,21 +1028,33 @@ __global__ void pqmf_synthesis_kernel(const float* mb, const float* filt, float*
 //   2. the sub-band samples [m0 - HM, m0 + TAIL_MB + HM) by the same windowed-basis sum as istft_kernel -> LDS (and -> mb),
 //   3. the polyphase PQMF FIR over LDS -> audio.
 // Same operand order as the separate kernels, so results agree to rounding of the re-used products.
+// kSynth = true: the multi-band (dec_type 0, PQMF filter) and multi-stream (dec_type 2, learned filter) decoders.
+// kSynth = false: the single-band iSTFT decoder (dec_type 3, S = 1): no synthesis stage, a block owns TAIL_SB output samples
+// and step 2 writes them straight to audio (no sub-band / filter arrays in LDS, no halo).
 #define TAIL_MB 64
+#define TAIL_SB 256
 struct TailParams {
   const float* post; const float* basis; const float* filt; float* mb; float* audio;
   int S, N, hop, Tp, Tm, taps;
   long long audio_bstride;
   const int* rag; int rag_mul;  // item b is valid for rag[b]*rag_mul sub-band samples (ragged batches), null = dense
 };
-__global__ void __launch_bounds__(256) istft_pqmf_kernel(const TailParams P) {
+// dynamic LDS of istft_tail_kernel<kSynth> in bytes (the same sizes as the kernel's carve-up below)
+__host__ __device__ inline size_t tail_lds_bytes(bool synth, int S, int N, int hop, int taps) {
+  const int HM = synth ? (taps / 2 + S - 1) / S + 1 : 0, nsub = (synth ? TAIL_MB : TAIL_SB) + 2 * HM, FR = (nsub + N) / hop + 2;
+  return ((size_t)2 * S * (N / 2 + 1) * FR + (synth ? (size_t)S * nsub : 0) + (size_t)(N + 2) * N + (synth ? (size_t)S * (taps + 1) : 0)) *
+         sizeof(float);
+}
+template <bool kSynth>
+__global__ void __launch_bounds__(256) istft_tail_kernel(const TailParams P) {
   extern __shared__ float sm[];
   kernarg_warm<sizeof(TailParams)>();
-  const int tid = threadIdx.x, b = blockIdx.y, m0 = blockIdx.x * TAIL_MB;
-  const int S = P.S, N = P.N, hop = P.hop, Tp = P.Tp, Tm = P.Tm;
+  constexpr int MB = kSynth ? TAIL_MB : TAIL_SB;
+  const int tid = threadIdx.x, b = blockIdx.y, m0 = blockIdx.x * MB;
+  const int S = kSynth ? P.S : 1, N = P.N, hop = P.hop, Tp = P.Tp, Tm = P.Tm;
   const int cut = N / 2 + 1, C = S * (N + 2), L = P.taps + 1, padl = P.taps / 2;
-  const int HM = (padl + S - 1) / S + 1;
-  const int n_lo = m0 - HM, nsub = TAIL_MB + 2 * HM;
+  const int HM = kSynth ? (padl + S - 1) / S + 1 : 0;
+  const int n_lo = m0 - HM, nsub = MB + 2 * HM;
   const int FR = (nsub + N) / hop + 2;
   const int n_valid = P.rag ? (P.rag[b] * P.rag_mul < Tm ? P.rag[b] * P.rag_mul : Tm) : Tm;  // sub-band samples that exist
   int f_hi_lim = Tp - 1;
@@ -1050,11 +1066,12 @@ __global__ void __launch_bounds__(256) istft_pqmf_kernel(const TailParams P) {
   const int nfr = f_hi - f_lo + 1;
   float* re = sm;                       // [S*cut][FR]
   float* im = re + S * cut * FR;
-  float* sub = im + S * cut * FR;       // [S][nsub]
-  float* bas = sub + S * nsub;          // [(N+2)][N]   windowed inverse basis
-  float* flt = bas + (N + 2) * N;       // [S][L]       PQMF synthesis filters
+  float* sub = im + S * cut * FR;       // [S][nsub]   (kSynth only)
+  float* bas = sub + (kSynth ? S * nsub : 0);  // [(N+2)][N]   windowed inverse basis
+  float* flt = bas + (N + 2) * N;       // [S][L]       synthesis filters (kSynth only)
   for (int i = tid; i < (N + 2) * N; i += 256) bas[i] = P.basis[i];
-  for (int i = tid; i < S * L; i += 256) flt[i] = P.filt[i];
+  if (kSynth)
+    for (int i = tid; i < S * L; i += 256) flt[i] = P.filt[i];
   for (int i = tid; i < S * cut * nfr; i += 256) {
     const int fr = i % nfr, sk = i / nfr, s = sk / cut, k = sk - s * cut;
     const float* pb = P.post + ((long long)b * C + (long long)s * (N + 2)) * Tp + f_lo + fr;
@@ -1082,10 +1099,12 @@ __global__ void __launch_bounds__(256) istft_pqmf_kernel(const TailParams P) {
         for (int k = 0; k < cut; ++k) a += rp[k * FR] * bas[k * N + j] + ip[k * FR] * bas[(cut + k) * N + j];
       }
       a *= (float)N / (float)hop;
-      if (P.mb && q >= HM && q < HM + TAIL_MB) P.mb[((long long)b * S + s) * Tm + n] = a;
+      if (kSynth && P.mb && q >= HM && q < HM + TAIL_MB) P.mb[((long long)b * S + s) * Tm + n] = a;
     }
-    sub[i] = a;
+    if (kSynth) sub[i] = a;
+    else if (n < Tm) P.audio[(long long)b * P.audio_bstride + n] = a;  // (zeros beyond a ragged item's valid samples)
   }
+  if (!kSynth) return;
   __syncthreads();
   const int To = Tm * S;
   for (int r = 0; r * 256 < TAIL_MB * S; ++r) {

@@ -285,6 +285,13 @@ def infer_hparams(t):
             raise KeyError(name)
         return t[name]
 
+    # decoder / duration-predictor variants the reference can build but the engine does not: named, not reported as missing tensors
+    if any(k.startswith("dec.resblocks.") and ".convs." in k for k in t):
+        raise NotImplementedError("decoder with ResBlock2 (resblock '2', modules.py:232: dec.resblocks.*.convs.*) is not supported; "
+                                  "only ResBlock1 decoders are")
+    if any(k.startswith(("dp.conv_1.", "dp.norm_1.")) for k in t) and not any(k.startswith("dp.flows.") for k in t):
+        raise NotImplementedError("deterministic DurationPredictor (use_sdp false, models.py:104-139: dp.conv_1 / dp.norm_1 without "
+                                  "dp.flows) is not supported; only the stochastic duration predictor is")
     try:
         emb = need("enc_p.emb.weight")
         hp = W.default_hparams(n_vocab=emb.shape[0])
@@ -322,10 +329,22 @@ def infer_hparams(t):
         for j in range(hp.n_resk):
             hp.res_kernels[j] = t[f"dec.resblocks.{j}.convs1.0.weight"].shape[2]
         hp.n_resd = sum(1 for k in t if k.startswith("dec.resblocks.0.convs1.") and k.endswith(".weight"))
-        if "dec.subband_conv_post.weight" in t:
+        if "dec.multistream_conv_post.weight" in t:
+            # Multistream_iSTFT_Generator (models.py:1066-1163): same subband_conv_post as the multi-band decoder (plus a bias),
+            # and a learned [1, S, L] synthesis filter in place of the PQMF one -- its shape gives S and the filter length
+            hp.dec_type = 2
+            ms = t["dec.multistream_conv_post.weight"]
+            hp.subbands, hp.pqmf_taps = int(ms.shape[1]), int(ms.shape[2]) - 1
+            hp.istft_n_fft = t["dec.subband_conv_post.weight"].shape[0] // hp.subbands - 2
+        elif "dec.subband_conv_post.weight" in t:
             hp.dec_type = 0
             post = t["dec.subband_conv_post.weight"].shape[0]
             hp.istft_n_fft = post // hp.subbands - 2
+        elif "dec.conv_post.weight" in t and t["dec.conv_post.weight"].shape[0] > 1:
+            # iSTFT_Generator (models.py:901-971): conv_post into n_fft + 2 rows, one iSTFT, no sub-bands
+            hp.dec_type = 3
+            hp.istft_n_fft = int(t["dec.conv_post.weight"].shape[0]) - 2
+            hp.subbands = 1
         elif "dec.conv_post.weight" in t:
             hp.dec_type = 1
         else:
@@ -384,7 +403,7 @@ def import_onnx(path_or_bytes, config=None):  # noqa: C901
             dl = g.attrs.get(f"/dec/resblocks.{j}/convs1.{d}/Conv", {}).get("dilations")
             if dl:
                 hp.res_dilations[j][d] = int(dl[0])
-    if hp.dec_type == 0:
+    if hp.dec_type in (0, 2, 3):
         for nm, at in g.attrs.items():
             if nm.startswith("/dec/") and "stft" in nm.lower() and nm.endswith("ConvTranspose") and at.get("strides"):
                 hp.istft_hop = int(at["strides"][0])
@@ -395,9 +414,11 @@ def import_onnx(path_or_bytes, config=None):  # noqa: C901
             hp.res_dilations[j][d] = int(v)
     for key, field in (("gen_istft_hop_size", "istft_hop"), ("subbands", "subbands"), ("sampling_rate", "sampling_rate"),
                        ("hop_length", "hop_length")):
+        if key == "subbands" and hp.dec_type in (2, 3):
+            continue  # the synthesis filter's shape (2) or the single band (3) decides; a training config carries "subbands" either way
         if key in config:
             setattr(hp, field, int(config[key]))
-    rate = int(np.prod([hp.up_rates[i] for i in range(hp.n_ups)])) * (hp.istft_hop * hp.subbands if hp.dec_type == 0 else 1)
+    rate = int(np.prod([hp.up_rates[i] for i in range(hp.n_ups)])) * (hp.istft_hop * hp.subbands if hp.dec_type in (0, 2, 3) else 1)
     if "hop_length" not in config:
         hp.hop_length = rate  # samples per frame are a property of the decoder, not an independent setting
     W.validate_hparams(hp)

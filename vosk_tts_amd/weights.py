@@ -168,6 +168,40 @@ def plain_hparams(n_vocab=20):
     return hp
 
 
+def multistream_hparams(n_vocab=62):
+    """Default-size graph with the `Multistream_iSTFT_Generator` decoder (models.py:1066-1163, config flag ms_istft_vits):
+    the multi-band trunk and geometry, a biased subband_conv_post and a learned 63-tap synthesis filter
+    (multistream_conv_post) in place of the fixed PQMF filter."""
+    hp = default_hparams(n_vocab)
+    hp.dec_type = 2
+    return hp
+
+
+def tiny_multistream_hparams(n_vocab=20):
+    hp = tiny_hparams(n_vocab)
+    hp.dec_type = 2
+    return hp
+
+
+def istft_hparams(n_vocab=62):
+    """Default-size graph with the single-band `iSTFT_Generator` decoder (models.py:901-971, config flag istft_vits):
+    conv_post into n_fft + 2 rows, one iSTFT, no sub-bands.  Upsampling [8,8] with n_fft 16 / hop 4 is the original
+    iSTFT-VITS geometry that gives 256 samples per frame."""
+    hp = default_hparams(n_vocab)
+    hp.dec_type = 3
+    hp.up_rates[0], hp.up_rates[1] = 8, 8
+    hp.subbands = 1
+    return hp
+
+
+def tiny_istft_hparams(n_vocab=20):
+    hp = istft_hparams(n_vocab)
+    t = tiny_hparams(n_vocab)
+    for f in ("hidden_channels", "inter_channels", "filter_channels", "n_layers", "gin_channels", "n_speakers", "dec_initial_channel"):
+        setattr(hp, f, getattr(t, f))
+    return hp
+
+
 def hifigan_v1_vocoder_hparams():
     """Vocoder-only blob (n_vocab = 0): the HiFi-GAN V1 generator bundled with StableTTS
     (training/stabletts/matcha/hifigan/models.py:148-199, config.py v1) that the multistream export wraps as
@@ -265,6 +299,12 @@ def tensor_specs(hp):
                 conv(f"{rb}.convs2.{d}", ch, ch, k, gain=0.7)
     if hp.dec_type == 0:
         conv("dec.subband_conv_post", hp.subbands * (hp.istft_n_fft + 2), ch, 7, bias=False, gain=0.5)
+    elif hp.dec_type == 2:
+        # Multistream_iSTFT_Generator: the post conv has a bias (models.py:1095), the synthesis filter is learned (:1107)
+        conv("dec.subband_conv_post", hp.subbands * (hp.istft_n_fft + 2), ch, 7, bias=True, gain=0.5)
+        specs.append(("dec.multistream_conv_post.weight", (1, hp.subbands, hp.pqmf_taps + 1), "w", hp.pqmf_taps + 1, 1.0))
+    elif hp.dec_type == 3:
+        conv("dec.conv_post", hp.istft_n_fft + 2, ch, 7, bias=False, gain=0.5)  # iSTFT_Generator (models.py:932), no cond
     else:
         # VITS' Generator: no conv_post bias (models.py:866); StableTTS' HiFi-GAN: bias (hifigan/models.py:176)
         conv("dec.conv_post", 1, ch, 7, bias=not acoustic, gain=0.5)
@@ -370,9 +410,16 @@ def validate_hparams(hp):
         if u <= 0 or k < u:
             raise ValueError(f"decoder stage {i}: upsample rate {u} / kernel {k} invalid")
         rate *= u
-    if hp.dec_type == 0:
+    if hp.dec_type not in (0, 1, 2, 3):
+        raise ValueError(f"dec_type {hp.dec_type}: 0 = multi-band iSTFT, 1 = HiFi-GAN Generator, 2 = multi-stream iSTFT, "
+                         "3 = single-band iSTFT")
+    if hp.dec_type in (0, 2, 3):
         if hp.subbands <= 0 or hp.istft_hop <= 0 or hp.istft_n_fft <= 0 or hp.istft_n_fft % hp.istft_hop:
             raise ValueError("iSTFT / PQMF parameters invalid")
+        if hp.dec_type == 2 and (hp.pqmf_taps <= 0 or hp.pqmf_taps % 2):
+            raise ValueError(f"multi-stream synthesis filter of {hp.pqmf_taps + 1} taps: the length must be odd")
+        if hp.dec_type == 3 and hp.subbands != 1:
+            raise ValueError(f"single-band iSTFT decoder with subbands {hp.subbands}: must be 1")
         rate *= hp.istft_hop * hp.subbands
     if hp.conv_precision not in (0, 1):
         raise ValueError(f"conv_precision {hp.conv_precision}: 0 = fp32, 1 = split-bf16 decoder ResBlock convs")
