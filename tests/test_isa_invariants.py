@@ -33,8 +33,8 @@ def isa(tmp_path_factory):
     return kernels
 
 
-def test_big_tile_kernels_keep_three_workgroups_per_cu_without_spills(isa):
-    for name in ("conv_mfma_kernel<2, 2, 2, 2, 0>", "conv_bf3_kernel<2, 0, 2>", "conv_bf3_kernel<1, 0, 2>"):
+def test_big_tile_and_split_bf16_kernels_keep_three_workgroups_per_cu_without_spills(isa):
+    for name in ("conv_mfma_kernel<2, 2, 2, 2, 0>", "conv_bf3_kernel<2, 0>", "conv_bf3_kernel<1, 0>"):
         k = isa[name]
         assert k["scratch"] == 0 and k["occupancy"] >= 3, (name, k["vgprs"], k["scratch"], k["occupancy"])
     # 256-thread workgroups, 3 per CU = 3 waves per SIMD: at most 512 / 3 registers

@@ -59,15 +59,7 @@ template <int V> struct bf3_int { static constexpr int value = V; };
 // immediate offsets.  The weight stream is read one step past its end (add_bf3_packing pads the array).
 // MI = 32-row blocks per wave: 2 -> 128 x 128 tiles, 1 -> 64 x 128 tiles (64-channel stages).  EPI: EPI_STORE, or EPI_GATE with MI == 2
 // (a wave's two row blocks are the [tanh 32 | sigmoid 32] pre-activations of the same 32 channels, commons.py:100-107)
-// PC (producer / consumer split): the workgroup has 6 waves.  Waves 4 and 5 only stage -- each owns 8 of a chunk's 16 channels
-// (one 16-byte half of every staged column), loads them two chunks ahead, splits and stores them; waves 0..3 only stream weights,
-// read LDS and issue MFMAs.  vmcnt retires in order: in the 4-wave form every weight wait that follows the activation loads of
-// chunk c + 2 also waits for those (an HBM round trip once per chunk, measured as 26 % of the ResBlock launches' time with the
-// staging compiled out, profiles/r3_bf3_ab.txt); here the consumers' counter only ever holds weight fragments.
-// NS = weight-fragment slots: 2 (a step is requested one tap ahead) or 3 (two taps ahead, slot = (phase + tap) mod 3 with the chunk
-// body instantiated per phase; the activation loads are then requested ONE chunk ahead straight into the single staging register
-// set, at the top of the chunk, where the weight fragments of the chunk's first two taps are already older than them).
-template <int MI, int EPI, bool PC = false, int NS = 2>
+template <int MI, int EPI>
 static __device__ __forceinline__ void conv_bf3_body(const ConvParams& P, const ConvGroup& G, float* lds, int mt, int nt, int b) {
   constexpr int N_T = 128, M_T = 64 * MI;
   constexpr int JT = (N_T + CONV_MAX_HALO + 63) / 64;
@@ -90,69 +82,12 @@ static __device__ __forceinline__ void conv_bf3_body(const ConvParams& P, const 
   if (P.skip_len && n0 >= P.len[b]) return;
 
   const int piece_bytes = ROW * (BF3_PITCH * 2);  // one piece (hi or lo) of one chunk buffer
-  if constexpr (PC) {
-    if (wave >= 4) {
-      // ---- producer wave pw: positions 8 pw .. 8 pw + 7 of every staged column = channels (2 pw + (i >> 2)) + 4 (i & 3), i = 0..7
-      const int pw = wave - 4;
-      float stg[8][JT], stn[8][JT];
-      const float* xb = G.x + (long long)b * P.x_bstride;
-      // leaky ReLU of the scaled input as max(s x, (s slope) x): in_scale >= 0 and 0 <= in_slope <= 1 (launcher: bf3_ok), one compare
-      // and one select less per element than conv_act_in
-      const float in_scale = P.in_scale, in_ss = P.in_scale * P.in_slope;
-      const int t_base = n0 - G.pad_l;
-      CONV_STAGE_COLS(JT)
-      unsigned tob[JT];
-#pragma unroll
-      for (int j = 0; j < JT; ++j) tob[j] = (unsigned)toff[j] * 4u;
-      const __amdgpu_buffer_rsrc_t rx = bt_rsrc(xb);
-      auto load_chunk = [&](int c, float (&dst)[8][JT]) {
-#pragma unroll
-        for (int i = 0; i < 8; ++i) {
-          const unsigned ro = (unsigned)((long long)(c * CONV_CI_T + 2 * pw + (i >> 2) + 4 * (i & 3)) * P.Tin_stride * 4);
-#pragma unroll
-          for (int j = 0; j < JT; ++j) dst[i][j] = bt_ld(rx, tob[j], ro);
-        }
-      };
-      auto store_chunk = [&](int buf) {
-        char* dst = reinterpret_cast<char*>(lds) + buf * (2 * piece_bytes) + 16 * pw;
-#pragma unroll
-        for (int j = 0; j < JT; ++j) {
-          const int col = lane + 64 * j;
-          bf16x8 hi, lo;
-#pragma unroll
-          for (int i = 0; i < 8; ++i) {
-            const float v = tok[j] ? fmaxf(stg[i][j] * in_scale, stg[i][j] * in_ss) : 0.f;  // select: stale padding may hold NaN
-            hi[i] = (__bf16)v;
-            lo[i] = (__bf16)(v - (float)hi[i]);
-          }
-          if (j < JT - 1 || col < ROW) {
-            *reinterpret_cast<bf16x8*>(dst + col * (BF3_PITCH * 2)) = hi;
-            *reinterpret_cast<bf16x8*>(dst + piece_bytes + col * (BF3_PITCH * 2)) = lo;
-          }
-        }
-      };
-      load_chunk(0, stg);
-      store_chunk(0);
-      if (nchunks > 1) load_chunk(1, stg);
-      __syncthreads();
-#pragma unroll 1
-      for (int c = 0; c < nchunks; ++c) {
-        if (c + 2 < nchunks) load_chunk(c + 2, stn);
-        if (c + 1 < nchunks) store_chunk((c + 1) & 1);  // (waits for the loads of chunk c + 1 only: the newer ones stay in flight)
-        __syncthreads();
-#pragma unroll
-        for (int i = 0; i < 8; ++i)
-#pragma unroll
-          for (int j = 0; j < JT; ++j) stg[i][j] = stn[i][j];
-      }
-      return;
-    }
-  }
-
   // ---- staging: wave w owns chunk rows w, w+4, w+8, w+12 (coalesced along time); lanes stride over columns
   float stg[4][JT], stn[4][JT];  // staged values of chunk c + 1 (loaded one chunk earlier) and in-flight loads of chunk c + 2
   const float* xb = G.x + (long long)b * P.x_bstride;
-  const float in_scale = P.in_scale, in_ss = P.in_scale * P.in_slope;  // (see the producer path)
+  // leaky ReLU of the scaled input as max(s x, (s slope) x): in_scale >= 0 and 0 <= in_slope <= 1 (launcher: bf3_ok), one compare
+  // and one select less per element than conv_act_in
+  const float in_scale = P.in_scale, in_ss = P.in_scale * P.in_slope;
   const int t_base = n0 - G.pad_l;
   CONV_STAGE_COLS(JT)
   unsigned tob[JT];  // byte offsets of the staging columns (buffer addressing: descriptor + scalar row offset + tob, conv_mfma.hip.h bt_ld)
@@ -208,29 +143,25 @@ static __device__ __forceinline__ void conv_bf3_body(const ConvParams& P, const 
   const unsigned lane16 = (unsigned)lane * 16u;
   auto wload = [&](__amdgpu_buffer_rsrc_t r, unsigned off) { return __builtin_bit_cast(bf16x8, __builtin_amdgcn_raw_buffer_load_b128(r, lane16, off, 0)); };
 
-  if constexpr (!PC) {
-    load_chunk(0, stg);
-    store_chunk(0);
-    if (nchunks > 1) load_chunk(1, stg);
-  }
+  load_chunk(0, stg);
+  store_chunk(0);
+  if (nchunks > 1) load_chunk(1, stg);
   __syncthreads();
 
-  bf16x8 a[NS][MI][2];  // [slot][mi][piece]
+  bf16x8 a[2][MI][2];  // [slot][mi][piece]
 #pragma unroll
-  for (int sl = 0; sl < NS - 1; ++sl)
-#pragma unroll
-    for (int mi = 0; mi < MI; ++mi) {
-      a[sl][mi][0] = wload(wq[mi], sl * 2048);
-      a[sl][mi][1] = wload(wq[mi], sl * 2048 + 1024);
-    }
-  unsigned ws = (NS - 1) * 2048;  // byte offset of the next step to fetch (2 KB per step and m-block; the packing is padded by two steps for the last prefetches)
+  for (int mi = 0; mi < MI; ++mi) {
+    a[0][mi][0] = wload(wq[mi], 0);
+    a[0][mi][1] = wload(wq[mi], 1024);
+  }
+  unsigned ws = 2048;  // byte offset of the next step to fetch (2 KB per step and m-block; the packing is padded by two steps for the last prefetches)
   // one tap: prefetch the next step into the other slot, read this tap's B fragments, 12 MFMAs
   auto tap = [&](auto slot_, const char* lk0, const char* lk1) {
     constexpr int S = decltype(slot_)::value;
 #pragma unroll
     for (int mi = 0; mi < MI; ++mi) {
-      a[(S + NS - 1) % NS][mi][0] = wload(wq[mi], ws);
-      a[(S + NS - 1) % NS][mi][1] = wload(wq[mi], ws + 1024);
+      a[S ^ 1][mi][0] = wload(wq[mi], ws);
+      a[S ^ 1][mi][1] = wload(wq[mi], ws + 1024);
     }
     ws += 2048;
     bf16x8 bh[2], bl[2];
@@ -255,48 +186,6 @@ static __device__ __forceinline__ void conv_bf3_body(const ConvParams& P, const 
       for (int ni = 0; ni < 2; ++ni) acc[mi][ni] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[S][mi][0], bh[ni], acc[mi][ni], 0, 0, 0);
     __builtin_amdgcn_sched_barrier(0);
   };
-  if constexpr (NS == 3) {
-    static_assert(!PC, "three weight slots: 4-wave form only");
-    const int dstep = dil * (BF3_PITCH * 2);
-    const int kmod = K % 3;
-#pragma unroll 1
-    for (int c = 0; c < nchunks; ++c) {
-      // slot = tap mod 3 inside a chunk (static names); a chunk whose tap count is not a multiple of 3 ends with its successor's
-      // first two steps in slots (K mod 3) and (K mod 3) + 1: rotated back to slots 0 and 1 below (32 moves per chunk, 7- and 11-tap
-      // groups only)
-      const char* lk0 = reinterpret_cast<const char*>(lds) + (c & 1) * (2 * piece_bytes) + (wn * 64 + l31 + tap_base) * (BF3_PITCH * 2) + 16 * h;
-      const char* lk1 = lk0 + piece_bytes;
-      tap(bf3_int<0>{}, lk0, lk1);
-      lk0 += dstep; lk1 += dstep;
-      int kk = 1;
-#pragma unroll 1
-      for (; kk + 2 < K; kk += 3) {
-        tap(bf3_int<1>{}, lk0, lk1);
-        tap(bf3_int<2>{}, lk0 + dstep, lk1 + dstep);
-        tap(bf3_int<0>{}, lk0 + 2 * dstep, lk1 + 2 * dstep);
-        lk0 += 3 * dstep; lk1 += 3 * dstep;
-      }
-      if (kk < K) {
-        tap(bf3_int<1>{}, lk0, lk1);
-        if (kk + 1 < K) tap(bf3_int<2>{}, lk0 + dstep, lk1 + dstep);
-      }
-      if (kmod == 1) {
-#pragma unroll
-        for (int mi = 0; mi < MI; ++mi)
-#pragma unroll
-          for (int pc = 0; pc < 2; ++pc) { a[0][mi][pc] = a[1][mi][pc]; a[1][mi][pc] = a[2][mi][pc]; }
-      } else if (kmod == 2) {
-#pragma unroll
-        for (int mi = 0; mi < MI; ++mi)
-#pragma unroll
-          for (int pc = 0; pc < 2; ++pc) { a[1][mi][pc] = a[0][mi][pc]; a[0][mi][pc] = a[2][mi][pc]; }
-      }
-      if (c + 1 < nchunks) store_chunk((c + 1) & 1);
-      __syncthreads();
-      if (c + 2 < nchunks) load_chunk(c + 2, stg);  // one chunk ahead, into the registers the store just freed
-      __builtin_amdgcn_sched_barrier(0);
-    }
-  } else
 #pragma unroll 1
   for (int c = 0; c < nchunks; ++c) {
     const int dstep = dil * (BF3_PITCH * 2);
@@ -306,7 +195,7 @@ static __device__ __forceinline__ void conv_bf3_body(const ConvParams& P, const 
     // activation loads waits for those too (conv_mfma.hip.h, same rule).  They are requested TWO chunks ahead: a chunk's taps
     // take 1.2 k (3 taps) .. 4.2 k (11 taps) MFMA cycles per wave, less than an HBM round trip under load.
     tap(bf3_int<0>{}, lk0, lk1);
-    if constexpr (!PC) { if (c + 2 < nchunks) load_chunk(c + 2, stn); }
+    if (c + 2 < nchunks) load_chunk(c + 2, stn);
     __builtin_amdgcn_sched_barrier(0);
     lk0 += dstep;
     lk1 += dstep;
@@ -326,14 +215,12 @@ static __device__ __forceinline__ void conv_bf3_body(const ConvParams& P, const 
 #pragma unroll
         for (int pc = 0; pc < 2; ++pc) a[0][mi][pc] = a[1][mi][pc];
     }
-    if constexpr (!PC) { if (c + 1 < nchunks) store_chunk((c + 1) & 1); }
+    if (c + 1 < nchunks) store_chunk((c + 1) & 1);
     __syncthreads();
-    if constexpr (!PC) {
 #pragma unroll
-      for (int rr = 0; rr < 4; ++rr)
+    for (int rr = 0; rr < 4; ++rr)
 #pragma unroll
-        for (int j = 0; j < JT; ++j) stg[rr][j] = stn[rr][j];
-    }
+      for (int j = 0; j < JT; ++j) stg[rr][j] = stn[rr][j];
   }
 
   // ---- epilogue (shared with the fp32 kernels).  C/D layout of the 32x32 MFMA: col = lane&31, row = (e&3) + 8*(e>>2) + 4*(lane>>5)
@@ -369,18 +256,6 @@ static __device__ __forceinline__ void conv_bf3_body(const ConvParams& P, const 
 }
 
 template <int MI, int EPI>
-__global__ void __launch_bounds__(384, 2) conv_bf3pc_kernel(const ConvParams P) {
-  extern __shared__ float lds[];
-  kernarg_warm<sizeof(ConvParams)>();
-  int mt, grp, nt, b;
-  if (!conv_decode_block(P, mt, grp, nt, b)) return;
-  mt = __builtin_amdgcn_readfirstlane(mt); grp = __builtin_amdgcn_readfirstlane(grp);
-  nt = __builtin_amdgcn_readfirstlane(nt); b = __builtin_amdgcn_readfirstlane(b);
-  const ConvGroup& G = P.g[grp];
-  conv_bf3_body<MI, EPI, true>(P, G, lds, mt, nt, b);
-}
-
-template <int MI, int EPI, int NS = 2>
 __global__ void __launch_bounds__(256, 3) conv_bf3_kernel(const ConvParams P) {
   extern __shared__ float lds[];
   kernarg_warm<sizeof(ConvParams)>();
@@ -389,5 +264,5 @@ __global__ void __launch_bounds__(256, 3) conv_bf3_kernel(const ConvParams P) {
   mt = __builtin_amdgcn_readfirstlane(mt); grp = __builtin_amdgcn_readfirstlane(grp);  // block-uniform (see conv_mfma_kernel)
   nt = __builtin_amdgcn_readfirstlane(nt); b = __builtin_amdgcn_readfirstlane(b);
   const ConvGroup& G = P.g[grp];
-  conv_bf3_body<MI, EPI, false, NS>(P, G, lds, mt, nt, b);
+  conv_bf3_body<MI, EPI>(P, G, lds, mt, nt, b);
 }

@@ -100,8 +100,7 @@ struct ConvParams {
   int first;          // EPI_RESSKIP: first layer (store skip instead of accumulate)
   int last;           // EPI_RESSKIP: last layer (M == H, everything is skip; apply mask)
   int ntiles_m, ntiles_n;
-  // 11: CU-mate order of a grouped single-utterance launch (conv_decode_block); 12: plain order without the per-XCD pairing of
-  // M-tiles (A/B: VITS_PAIR_MTILES=0); 0: the plain orders
+  // 11: CU-mate order of a grouped single-utterance launch (conv_decode_block); 0: the plain orders
   int xcd_mode;
   // DDSConv prologue of the small-tile kernel (conv_small.hip.h, PRO == 1): the B operand of this 1x1 conv is computed from
   // the previous layer's raw tensors instead of being read:
@@ -193,12 +192,11 @@ __device__ __forceinline__ int conv_pair_mtiles(int ntiles_m, int L = blockIdx.x
   const int base = L / run * run, r = L - base, x = r & 7, w = r >> 3;  // w-th workgroup of XCD x inside this run
   return base + x * ntiles_m + w;
 }
-// (Lb / nblk: the block id and grid size to decode for -- the launch's own by default; a persistent kernel that walks VIRTUAL blocks
-//  passes its own, conv_sk.hip.h)
-__device__ __forceinline__ bool conv_decode_block(const ConvParams& P, int& mt, int& grp, int& nt, int& b, int Lb = blockIdx.x, int nblk_ = gridDim.x) {
+__device__ __forceinline__ bool conv_decode_block(const ConvParams& P, int& mt, int& grp, int& nt, int& b) {
+  const int Lb = blockIdx.x;
   if (P.tile_start) {
     // plain dispatch order (no XCD-contiguous remap: working tiles must be spread over all XCDs), M-tiles paired per XCD
-    int id = P.xcd_mode == 12 ? Lb : conv_pair_mtiles(P.ntiles_m, Lb, nblk_);
+    int id = conv_pair_mtiles(P.ntiles_m);
     mt = id % P.ntiles_m; id /= P.ntiles_m;
     const int total = P.tile_start[P.B];
     int q;
@@ -236,14 +234,14 @@ __device__ __forceinline__ bool conv_decode_block(const ConvParams& P, int& mt, 
   {
     // bijective XCD remap: block L runs on XCD L%8; give each XCD a contiguous range of logical ids so
     // tiles sharing an activation window share an L2
-    const int nblk = nblk_, L = Lb;
+    const int nblk = gridDim.x, L = Lb;
     const int q = nblk >> 3, r = nblk & 7, xcd = L & 7, within = L >> 3;
     id = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + within;
   }
   if (P.n_groups > 1) {
     // grouped launch (k = 11/7/3 ResBlocks, sorted heaviest first by the launcher): plain dispatch order
     // with the group outermost, so the long blocks start first and the launch tail is made of short ones
-    id = (P.B > 1 && P.xcd_mode != 12) ? conv_pair_mtiles(P.ntiles_m, Lb, nblk_) : Lb;  // (one utterance: an XCD keeps its M-tile's weight rows, profiles/r3_xcd_map.txt)
+    id = P.B > 1 ? conv_pair_mtiles(P.ntiles_m) : Lb;  // (one utterance: an XCD keeps its M-tile's weight rows, profiles/r3_xcd_map.txt)
     mt = id % P.ntiles_m; id /= P.ntiles_m;
     nt = id % P.ntiles_n; id /= P.ntiles_n;
     b = id % P.B;

@@ -34,8 +34,8 @@
 // (profiles/r5_conv_sp.txt).  Pitch 20: the 16 lanes of a ds_read_b128 group land on 16 distinct 4-bank groups (20 i mod 64).
 #define SP_PITCH 20
 
-// One 64 x 64 tile's contraction over the stages [s_begin, s_end) of 64 channels (the whole tile: 0 .. C_in / 64; stream-K segments,
-// conv_sk.hip.h: any sub-range) -> the two accumulators of this wave.  false: the tile lies in an item's padding (block-uniform).
+// One 64 x 64 tile's contraction over the stages [s_begin, s_end) of 64 channels (conv_sp_kernel: the whole tile, 0 .. C_in / 64)
+// -> the two accumulators of this wave.  false: the tile lies in an item's padding (block-uniform).
 template <int JT>
 __device__ __forceinline__ bool conv_sp_tile(const ConvParams& P, const ConvGroup& G, float* lds, int mt, int nt, int b, int s_begin, int s_end,
                                              f32x16 (&acc)[2]) {

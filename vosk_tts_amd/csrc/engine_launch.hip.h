@@ -34,8 +34,6 @@ static void persist_launch(vits_session* s, vits_session::PersistProg& pp, const
   c.solo = s->solo ? 1 : 0; c.dv = s->dv; c.item_seeds = s->item_seeds; c.trace = nullptr;
   c.dbg = m->ps_dbg;
   c.forced = d_forced; c.length_scale = length_scale; c.noise_scale = noise_scale; c.noise_prior = nullptr; c.noise_stride = 0;
-  static const int tune = getenv("VITS_PS_TUNE") ? atoi(getenv("VITS_PS_TUNE")) : PS_TUNE_DEFAULT;  // experiment switches (persist.hip.h)
-  c.tune = tune;
   static const char* trace_path = getenv("VITS_PS_TRACE");  // tools/ps_trace.py: per-worker, per-step cycle stamps of an EAGER forward
   static const char* trace_name = getenv("VITS_PS_TRACE_PROG");  // which program ("dp.persist" by default)
   hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
@@ -75,8 +73,6 @@ static const int* tile_table(vits_session* s, const int* len, int mul, int add, 
 }
 
 static void attach_tile_table(vits_session* s, ConvParams& P, int N_T) {
-  static const bool pair = !(getenv("VITS_PAIR_MTILES") && atoi(getenv("VITS_PAIR_MTILES")) == 0);
-  if (!pair && !P.xcd_mode) P.xcd_mode = 12;
   P.tile_start = nullptr;
   if (!s || !s->arena || s->B == 1) return;  // a single utterance in a padded bucket: the few dead tiles exit early instead
   if (P.rag) P.tile_start = tile_table(s, P.rag, P.rag_out_mul, P.rag_tab_add > P.rag_out_add ? P.rag_tab_add : P.rag_out_add, P.Tout, N_T, 1, P.rag_out_cap_add);  // (tiles the map lists beyond this launch's own limit exit at once)  // (the decoder's rag array carries its cap in rag[B])
@@ -269,19 +265,6 @@ static void launch_c16_dds(vits_session* s, ConvParams& P, const char* name, dou
 
 // ---- wave-pipelined kernel for the single-utterance decoder's ResBlock convs (conv_small.hip.h conv_wp_kernel)
 static thread_local int g_wp_mode = 0;  // 0 = heuristic, 1 = never, 2 = whenever eligible (tests)
-// split-bf16 kernels: VITS_BF3_PC=1 runs the producer / consumer workgroups (6 waves, conv_bf3.hip.h) instead of the 4-wave form.
-// MEASURED (profiles/r3_bf3_ab.txt): 25 % slower -- two 6-wave workgroups per CU leave two MFMA waves per SIMD instead of three, which
-// costs more than taking the staging out of their instruction streams gains.  Kept for A/B runs, off by default.
-static bool bf3_pc() {
-  static const bool on = getenv("VITS_BF3_PC") && atoi(getenv("VITS_BF3_PC")) == 1;
-  return on;
-}
-// weight-fragment slots of conv_bf3_kernel<2, STORE>: 2; VITS_BF3_SLOTS=3 runs the variant with two taps of prefetch lead and the
-// activation loads one chunk ahead (MEASURED 8 % slower, profiles/r3_bf3_ab.txt; A/B knob)
-static int bf3_slots() {
-  static const int n = getenv("VITS_BF3_SLOTS") ? atoi(getenv("VITS_BF3_SLOTS")) : 2;
-  return n == 3 ? 3 : 2;
-}
 static thread_local int g_no_bf3 = 0;   // test hook: 1 = a conv_precision == 1 model runs its fp32 kernels (A/B of the split-bf16 variant)
 static bool conv_wp_ok(const ConvParams& P, int epi, int halo, bool small) {
   static const int env_mode = getenv("VITS_CONV_WP") ? atoi(getenv("VITS_CONV_WP")) : 0;
@@ -306,26 +289,17 @@ static void launch_conv_wp(vits_session* s, ConvParams& P, ProfScope& ps) {
   {
     // a grouped launch whose workgroups are all resident at once (two per CU): choose the CU mates (conv_decode_block, mode 11).
     // Measured on the C = 256 stage of c2 (profiles/r3_blocktrace_c2.txt): makespan 26.9 -> 23.0 us.  Launches of several rounds keep
-    // the heaviest-first order (the same mapping made the 900-workgroup C = 128 launch 14 % slower).  VITS_WP_ORDER=0: off (A/B).
+    // the heaviest-first order (the same mapping made the 900-workgroup C = 128 launch 14 % slower).
     // (Tried before that, measured in profiles/r3_xcd_map.txt, removed: giving every XCD one group's input and a range of its weight
     // rows or columns -- fabric traffic -35..44 %, launches 13-15 % slower.)
-    static const int order = getenv("VITS_WP_ORDER") ? atoi(getenv("VITS_WP_ORDER")) : 1;
     const int per_xcd = cdiv(P.ntiles_m * P.ntiles_n, 8);
-    if (order && P.B == 1 && P.n_groups == 3 && P.g[0].K >= P.g[1].K && P.g[1].K >= P.g[2].K && 3 * per_xcd <= 64 &&
+    if (P.B == 1 && P.n_groups == 3 && P.g[0].K >= P.g[1].K && P.g[1].K >= P.g[2].K && 3 * per_xcd <= 64 &&
         per_xcd <= 32) {
       P.xcd_mode = 11;
       owned = 8 * 3 * per_xcd;
     }
   }
   const dim3 grid(owned ? owned : P.ntiles_m * P.ntiles_n * P.B * P.n_groups);
-  // A/B (round 5, VITS_WP_NW4=1): four waves per workgroup where a contraction has only 8 chunks (the C = 128 decoder stage: one chunk per
-  // wave and an 8-way reduction with 8 waves).  Measured: see profiles/r5_wp_nw4.txt
-  static const bool nw4 = getenv("VITS_WP_NW4") && atoi(getenv("VITS_WP_NW4")) != 0;
-  if (nw4 && P.Cin / CONV_CI_T <= 8 && !owned) {
-    ps.set_kernel("conv_wp_kernel<4>");
-    hipLaunchKernelGGL(conv_wp_kernel<4>, grid, dim3(4 * 64), (size_t)4 * CONV_CI_T * WP_PITCH * sizeof(float), s->stream, P);
-    return;
-  }
   ps.set_kernel("conv_wp_kernel<8>");
   hipLaunchKernelGGL(conv_wp_kernel<NW>, grid, dim3(NW * 64), lds, s->stream, P);
 }
@@ -333,15 +307,10 @@ static void launch_conv_wp(vits_session* s, ConvParams& P, ProfScope& ps) {
 // Column counts (B x T) up to which the 16-column-tile kernels run.  Round 4, measured on single utterances of 300 - 1000 tokens and on
 // batches of 8 / 16 short requests (profiles/r4_c16_threshold.txt): beyond ~256 columns the K-split / wave-pipelined kernels win the
 // plain convolutions (although the LayerNorm is then a launch of its own), the gate conv to ~512, the fused DDSConv layer to ~800.
-// VITS_C16_COLS overrides both, VITS_C16_DDS_COLS the second.
 static long c16_cols_conv(int epi) {  // (the WaveNet gate conv -- 5 taps, 2H rows, tanh * sigmoid epilogue -- crosses over at ~500 columns)
-  static const long v = getenv("VITS_C16_COLS") ? atol(getenv("VITS_C16_COLS")) : 0;
-  return v ? v : (epi == EPI_GATE ? 512 : 256);
+  return epi == EPI_GATE ? 512 : 256;
 }
-static long c16_cols_dds() {
-  static const long v = getenv("VITS_C16_DDS_COLS") ? atol(getenv("VITS_C16_DDS_COLS")) : (getenv("VITS_C16_COLS") ? atol(getenv("VITS_C16_COLS")) : 800);
-  return v;
-}
+static constexpr long C16_COLS_DDS = 800;
 // would launch_conv route this launch to the small-tile kernel?  (callers that fold a LayerNorm into the consumer's staging
 // must know before they drop the LayerNorm launch: only that kernel has the prologue)
 static bool conv_takes_c16(const ConvParams& P, int epi) {
@@ -356,12 +325,9 @@ static bool conv_takes_c16(const ConvParams& P, int epi) {
 }
 
 // ---- software-pipelined 64 x 64 kernel (conv_sp.hip.h): stands in for conv_mfma_kernel<2,2,1,1,*> on launches that leave a CU with
-// few workgroups.  VITS_SP: 0 = never, 1 = by size (default), 2 = whenever eligible (A/B, tests); VITS_SP_MAXBLK: largest grid it takes.
+// few workgroups (grids of up to 2048 workgroups).  vits_debug_conv_sp: 0 = never, 1 = by size (default), 2 = whenever eligible (tests).
 static thread_local int g_sp_mode = -1;
-static int sp_mode() {
-  static const int env = getenv("VITS_SP") ? atoi(getenv("VITS_SP")) : 1;
-  return g_sp_mode >= 0 ? g_sp_mode : env;
-}
+static int sp_mode() { return g_sp_mode >= 0 ? g_sp_mode : 1; }
 static bool conv_sp_ok(const ConvParams& P, int epi, int halo) {
   if (sp_mode() == 0 || epi == EPI_GATE) return false;
   if (P.Cin % SP_STAGE_CH || P.ups_u || P.reflect || P.x_split || P.ln_g || P.dds_y2 || P.ln_stat_out || 64 + halo > 128 || P.Tin < 2) return false;
@@ -385,62 +351,10 @@ static void launch_sp(vits_session* s, ConvParams& P, int halo) {
   if (P.row_len <= 64) hipLaunchKernelGGL((conv_sp_kernel<EPI, 1>), dim3(nblk), dim3(256), lds, s->stream, P);
   else hipLaunchKernelGGL((conv_sp_kernel<EPI, 2>), dim3(nblk), dim3(256), lds, s->stream, P);
 }
-// stream-K schedule of the same tile (conv_sk.hip.h; prototype, VITS_SK): G persistent workgroups, equal-cost contiguous ranges
-static bool sk_takes(vits_session* s, const ConvParams& P, int epi, int halo) {
-  return sk_mode() && epi == EPI_STORE && s && s->sk_ws && s->sk_ctl && conv_sp_ok(P, epi, halo);
-}
-static void launch_sk(vits_session* s, ConvParams& P, int halo) {
-  attach_tile_table(s, P, 64);
-  P.ntiles_m = cdiv(P.M, 64);
-  P.ntiles_n = cdiv(P.Tout, 64);
-  P.row_len = 64 + halo;
-  const long nblk = (long)P.ntiles_m * P.ntiles_n * P.B * P.n_groups;
-  static const int gmax = getenv("VITS_SK_G") ? atoi(getenv("VITS_SK_G")) : 0;
-  long G = gmax > 0 ? gmax : 2L * s->m->n_cu;  // two workgroups per CU are co-resident at every halo (73 KB of LDS at the widest)
-  if (G > SK_SLOTS) G = SK_SLOTS;
-  if (G > nblk) G = nblk;
-  const size_t lds = (size_t)2 * 4 * P.row_len * SP_PITCH * sizeof(float);
-  if (lds > 64 * 1024) {
-    static std::atomic<unsigned long long> done1{0}, done2{0};
-    if (P.row_len <= 64) { if (big_lds_needed(done1)) hipFuncSetAttribute((const void*)conv_sk_kernel<1>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); }
-    else if (big_lds_needed(done2)) hipFuncSetAttribute((const void*)conv_sk_kernel<2>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-  }
-  const SkArgs A{s->sk_ctl, s->sk_ws, 1 << 22};
-  if (P.row_len <= 64) hipLaunchKernelGGL((conv_sk_kernel<1>), dim3((unsigned)G), dim3(256), lds, s->stream, P, A);
-  else hipLaunchKernelGGL((conv_sk_kernel<2>), dim3((unsigned)G), dim3(256), lds, s->stream, P, A);
-}
 // the 64 x 64 tile of a launch that was routed to conv_mfma_kernel<2,2,1,1,EPI>: the pipelined kernel when the grid is small
 static bool sp_takes(const ConvParams& P, int epi, int halo) {
-  static const long max_blk = getenv("VITS_SP_MAXBLK") ? atol(getenv("VITS_SP_MAXBLK")) : 2048;
   const long nblk = (long)cdiv(P.M, 64) * cdiv(P.Tout, 64) * P.B * P.n_groups;
-  return conv_sp_ok(P, epi, halo) && (sp_mode() == 2 || nblk <= max_blk);
-}
-
-// ---- independent-wave 64 x 64 tiles (conv_w1.hip.h): stands in for conv_mfma_kernel<2,2,2,2,STORE> (the ResBlock convs of a batch).
-// MEASURED (profiles/r6_w1_ab.txt): parity green, 1.3 % SLOWER than the four-wave kernel on c3 / c4 (20.40 -> 20.66 ms, 127.3 -> 129.1):
-// the chunk barrier is not what the 128 x 128 kernel loses -- an independent-wave form with no barrier at all lands on the same plateau
-// (and moves 2.6 x the activation bytes through L2).  Kept as an A/B (like the producer / consumer split-bf16 kernel): VITS_W1=1 takes
-// the launches the 128 x 128 kernel would; default off.
-static int w1_mode() {
-  static const int env = getenv("VITS_W1") ? atoi(getenv("VITS_W1")) : 0;
-  return env;
-}
-static bool conv_w1_ok(const ConvParams& P, int epi, int halo) {
-  if (w1_mode() == 0 || epi != EPI_STORE) return false;
-  if (P.M % 64 || P.Cin % CONV_CI_T || P.ups_u || P.reflect || P.x_split || P.ln_g || P.dds_y2 || P.ln_stat_out || 64 + halo > W1_PITCH || P.Tin < 2) return false;
-  for (int g = 0; g < P.n_groups; ++g)
-    if (P.g[g].x2 || P.g[g].x3) return false;
-  return true;
-}
-static void launch_w1(vits_session* s, ConvParams& P, int halo) {
-  attach_tile_table(s, P, 64);
-  P.ntiles_m = cdiv(P.M, 64);
-  P.ntiles_n = cdiv(P.Tout, 64);
-  P.row_len = 64 + halo;
-  const int nblk = P.ntiles_m * P.ntiles_n * P.B * P.n_groups;
-  const size_t lds = (size_t)CONV_CI_T * W1_PITCH * sizeof(float);
-  if (P.row_len <= 64) hipLaunchKernelGGL((conv_w1_kernel<EPI_STORE, 1>), dim3(nblk), dim3(64), lds, s->stream, P);
-  else hipLaunchKernelGGL((conv_w1_kernel<EPI_STORE, 2>), dim3(nblk), dim3(64), lds, s->stream, P);
+  return conv_sp_ok(P, epi, halo) && (sp_mode() == 2 || nblk <= 2048);
 }
 
 // dispatch on epilogue + problem size.  halo = max over groups of (K-1)*dil (or the polyphase spread).
@@ -546,17 +460,14 @@ static void launch_conv(vits_session* s, ConvParams& P, int epi, const char* nam
       P.ntiles_n = cdiv(P.Tout, 128);
       P.row_len = 128 + halo;
       const size_t lds = (size_t)2 * 2 * P.row_len * (BF3_PITCH * 2);
-      if (bf3_pc()) hipLaunchKernelGGL((conv_bf3pc_kernel<2, EPI_GATE>), dim3(P.ntiles_m * P.ntiles_n * P.B), dim3(384), lds, s->stream, P);
-      else hipLaunchKernelGGL((conv_bf3_kernel<2, EPI_GATE>), dim3(P.ntiles_m * P.ntiles_n * P.B), dim3(256), lds, s->stream, P);
+      hipLaunchKernelGGL((conv_bf3_kernel<2, EPI_GATE>), dim3(P.ntiles_m * P.ntiles_n * P.B), dim3(256), lds, s->stream, P);
     } else {  // (128 x 128 tiles for the gate conv: 2.30 against 1.77 ms per c3 forward, round 4, profiles/r4_c3_tile_ab.txt)
       // Round 6: a grid of 1 - 3 four-wave workgroups per CU (all resident at once) lasts as long as the CU with the most of them; the
-      // same wave tiles in TWO-wave workgroups of 128 x 32 halve the quantum (c3: 580 tiles -> 1160).  VITS_GATE2W: 0 = never,
-      // 1 = by grid size (default), 2 = whenever the window fits (A/B)
-      static const int g2w = getenv("VITS_GATE2W") ? atoi(getenv("VITS_GATE2W")) : 1;
+      // same wave tiles in TWO-wave workgroups of 128 x 32 halve the quantum (c3: 580 tiles -> 1160)
       const long nblk64 = (long)cdiv(P.M, 128) * cdiv(P.Tout, 64) * P.B;
       // (only where the four-wave grid is 2 - 6 workgroups per CU: a 6000-frame single utterance -- 282 four-wave workgroups, about one
       //  per CU -- is 3 % SLOWER on two-wave tiles, profiles/r6_gate2w_ab.txt)
-      if (g_force_tile == 0 && g2w && 32 + halo <= 64 && (g2w == 2 || (nblk64 >= 512 && nblk64 <= 1536))) {
+      if (g_force_tile == 0 && 32 + halo <= 64 && nblk64 >= 512 && nblk64 <= 1536) {
         ps.set_kernel("conv_mfma_kernel<2,1,2,1,GATE>"); launch_cfg<2, 1, 2, 1, EPI_GATE>(s, P, halo);
       } else {
         ps.set_kernel("conv_mfma_kernel<2,2,2,1,GATE>"); launch_cfg<2, 2, 2, 1, EPI_GATE>(s, P, halo);
@@ -606,11 +517,7 @@ static void launch_conv(vits_session* s, ConvParams& P, int epi, const char* nam
     P.row_len = 128 + halo;
     const size_t lds = (size_t)2 * 2 * P.row_len * (BF3_PITCH * 2);
     const dim3 grid(P.ntiles_m * P.ntiles_n * P.B * P.n_groups);
-    if (bf3_pc()) {
-      if (mi == 2) hipLaunchKernelGGL((conv_bf3pc_kernel<2, EPI_STORE>), grid, dim3(384), lds, s->stream, P);
-      else hipLaunchKernelGGL((conv_bf3pc_kernel<1, EPI_STORE>), grid, dim3(384), lds, s->stream, P);
-    } else if (mi == 2 && bf3_slots() == 3) hipLaunchKernelGGL((conv_bf3_kernel<2, EPI_STORE, 3>), grid, dim3(256), lds, s->stream, P);
-    else if (mi == 2) hipLaunchKernelGGL((conv_bf3_kernel<2, EPI_STORE>), grid, dim3(256), lds, s->stream, P);
+    if (mi == 2) hipLaunchKernelGGL((conv_bf3_kernel<2, EPI_STORE>), grid, dim3(256), lds, s->stream, P);
     else hipLaunchKernelGGL((conv_bf3_kernel<1, EPI_STORE>), grid, dim3(256), lds, s->stream, P);
   };
   // 64-row outputs at batch size: 64 x 128 tiles (twice the columns per weight fragment of the 64 x 64 tile)
@@ -623,14 +530,12 @@ static void launch_conv(vits_session* s, ConvParams& P, int epi, const char* nam
   static const long big_min = getenv("VITS_BIG_BLOCKS") ? atol(getenv("VITS_BIG_BLOCKS")) : 512;
   if (m_fits && big_blocks >= big_min) {
     if (bf3_ok()) { bf3_go(2); return; }
-    if (g_force_tile == 0 && conv_w1_ok(P, epi, halo)) { ps.set_kernel("conv_w1_kernel<STORE>"); launch_w1(s, P, halo); return; }
     ps.set_kernel("conv_mfma_kernel<2,2,2,2,STORE>"); launch_cfg<2, 2, 2, 2, EPI_STORE>(s, P, halo); return;
   }
   // 64-row multiples at batch size (encoder / flow STORE convs: 192, 576, 768 rows) of a conv_precision == 1 model
   if (P.M % 64 == 0 && (long)cdiv(P.M, 64) * cdiv(P.Tout, 128) * P.B * P.n_groups >= 256 && bf3_ok()) { bf3_go(1); return; }
   // (64 x 128 fp32 tiles for these convs were measured on the c3 batch in round 4: 2.21 - 2.42 ms against 2.17 ms per forward for the
   //  64 x 64 tiles -- profiles/r4_c3_tile_ab.txt; not a tile-shape problem)
-  if (g_force_tile == 0 && sk_takes(s, P, epi, halo) && (sk_mode() == 2 || sp_takes(P, epi, halo))) { ps.set_kernel("conv_sk_kernel<STORE>"); launch_sk(s, P, halo); return; }
   if (g_force_tile == 0 && sp_takes(P, epi, halo)) { ps.set_kernel("conv_sp_kernel<STORE>"); launch_sp<EPI_STORE>(s, P, halo); return; }
   ps.set_kernel("conv_mfma_kernel<2,2,1,1,STORE>");
   launch_cfg<2, 2, 1, 1, EPI_STORE>(s, P, halo);
@@ -669,10 +574,9 @@ static void launch_attention_raw(vits_session* s, const float* qkv, const float*
   struct { const float* ek; const float* ev; } L{ek, ev};
   // 16-query tiles (more, smaller workgroups) while the 32-query MFMA kernel's grid would not fill the chip: measured round 4
   // (profiles/r4_c16_threshold.txt) single utterances of 200 - 600 tokens (T_y 600 - 1800) -15..-35 % attention time against the old rule
-  // (T <= 512), the 32-item batch c3 -6 % (its 200-token text side now runs the MFMA kernel).  VITS_ATT16_MAXT=<T> restores a pure T rule.
-  static const int t16_max = getenv("VITS_ATT16_MAXT") ? atoi(getenv("VITS_ATT16_MAXT")) : 0;
+  // (T <= 512), the 32-item batch c3 -6 % (its 200-token text side now runs the MFMA kernel).
   const bool small_grid = (long)cdiv(T, 32) * nh * B < 256;
-  const bool use16 = g_attn_impl == 3 || (g_attn_impl == 0 && (t16_max ? T <= t16_max : (T <= 64 || (small_grid && T <= 4096))));
+  const bool use16 = g_attn_impl == 3 || (g_attn_impl == 0 && (T <= 64 || (small_grid && T <= 4096)));
   ProfScope ps(s, "attention", 4.0 * (double)B * H * T * T,
                use16 ? "relpos_attention16_kernel" : (g_attn_impl == 1 ? "relpos_attention_kernel" : "relpos_attention_mfma_kernel"));
   if (use16) {  // short sequences: 16-query tiles, more and smaller workgroups

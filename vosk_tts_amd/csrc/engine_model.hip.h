@@ -142,18 +142,11 @@ static size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 // mappings, a layer's tensors adjacent, ~470 fewer allocations per model.  (Measured: no effect on the forward's time, so
 // address translation of the small per-tensor allocations was not what bounds the short-utterance kernels.)
 static void* weight_alloc(vits_model* m, size_t bytes) {
-  static const bool no_slab = getenv("VITS_NO_SLAB") != nullptr;  // A/B switch for tools/
   bytes = align_up(bytes ? bytes : 4, 256);
   // every allocation is followed by >= 64 KB of mapped memory: the weight streams are prefetched past their end by design (one or
   // two steps in the conv kernels, whose packings are padded for it); the slack makes an overrun of any of them a read of mapped
   // memory instead of a fault
   constexpr size_t guard = (size_t)64 << 10;
-  if (no_slab) {
-    void* d = nullptr;
-    if (hipMalloc(&d, bytes + guard) != hipSuccess) return nullptr;
-    m->allocs.push_back(d);
-    return d;
-  }
   if (m->slab_used + bytes + guard > m->slab_bytes) {
     size_t want = m->blob_bytes + m->blob_bytes / 4 + ((size_t)8 << 20);  // first slab: the whole model with packing slack
     if (!m->allocs.empty()) want = (size_t)32 << 20;

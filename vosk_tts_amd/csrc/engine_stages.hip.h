@@ -13,8 +13,7 @@
 struct PendingLN { const float* raw = nullptr; const float* g = nullptr; const float* b = nullptr; const float* stat = nullptr; int nmb = 0; };
 
 static bool enc_fold_ok(vits_session* s, const EncoderW& E, int B, int T) {
-  static const bool no_fold = getenv("VITS_NO_LN_FOLD") != nullptr;  // A/B switch for tools/ and tests
-  if (no_fold || E.layers.empty() || !s->xb || !s->y1b) return false;
+  if (E.layers.empty() || !s->xb || !s->y1b) return false;
   const EncLayerW& L = E.layers[0];
   static const float dummy = 0.f;
   ConvParams P = conv_params(L.qkv, s->x, s->qkv, B, T, 1, 0);
@@ -186,11 +185,10 @@ static float* run_dds(vits_session* s, const DDSW& W, float* h, int B, int T) {
   const vits_hparams& hp = s->m->hp;
   const int D = hp.dp_filter_channels, K = hp.dp_kernel_size;
   int dil = 1;
-  static const bool no_fuse = getenv("VITS_NO_DDS_FUSION") != nullptr;  // A/B switch for tools/ and tests
   // Single utterances / small batches only: there the three launches per layer are pure latency.  Every workgroup
   // of the fused kernel streams the whole D x D matrix and does its mat-vec on the VALU, so beyond ~one workgroup
   // per CU (B*T/8 > 256) the MFMA conv path below wins.
-  if (D <= 256 && D % 64 == 0 && (long)B * T <= 2048 && !no_fuse) {  // dds_layer_kernel, ping-pong between h and s->dy
+  if (D <= 256 && D % 64 == 0 && (long)B * T <= 2048) {  // dds_layer_kernel, ping-pong between h and s->dy
     float* src = h; float* dst = s->dy;
     for (size_t i = 0; i < W.pw.size(); ++i) {
       ProfScope ps(s, "dp.dds_layer", 2.0 * B * T * ((double)D * D + (double)D * K), "dds_layer_kernel");
@@ -228,14 +226,12 @@ static void run_dds_proj(vits_session* s, const DDSW& W, float* h, const ConvW& 
                          const DdsPre* pre = nullptr) {
   const vits_hparams& hp = s->m->hp;
   const int D = hp.dp_filter_channels, K = hp.dp_kernel_size;
-  static const bool no_c16 = getenv("VITS_NO_DDS_C16") != nullptr;  // A/B switch for tools/ and tests
-  const long c16_cols = c16_cols_dds();
   {
     ConvParams P = conv_params(proj, h, out, B, T, 1, 0);
     P.len = s->len_x;
     int max_dil = 1;
     for (size_t i = 1; i < W.pw.size(); ++i) max_dil *= K;
-    if (!no_c16 && (g_force_tile == 0 || g_force_tile == 3) && (long)B * T <= c16_cols && c16_dds_ok(P, K) && max_dil <= 9 && W.pw.size() >= 1 &&
+    if ((g_force_tile == 0 || g_force_tile == 3) && (long)B * T <= C16_COLS_DDS && c16_dds_ok(P, K) && max_dil <= 9 && W.pw.size() >= 1 &&
         W.pw[0].w16) {
       const int n = (int)W.pw.size();
       float* X[2] = {s->dy, s->dq1};
@@ -449,7 +445,6 @@ static DecNeeds decoder_needs(const vits_hparams& hp, bool continuation) {
 // rag_halo > 0 (with ragged): the reference's padded-batch continuation -- every valid sample equals the dense padded run (the per-layer
 // limits above; the value only has to be >= the receptive field and is otherwise unused); 0 decodes every item as if it were alone
 // (zeros beyond its own end at every stage), which is what a batch of independent utterances wants (solo batches, the StableTTS path).
-// VITS_RAG_UNIFORM=1: the round-4 form (len + rag_halo frames at every layer), the A/B reference.
 static void run_decoder(vits_session* s, const float* z, bool mask_in, int B, int Ty, float* d_audio, long long audio_bstride,
                         float* d_mb, bool ragged = false, int rag_halo = -1) {
   vits_model* m = s->m;
@@ -459,13 +454,11 @@ static void run_decoder(vits_session* s, const float* z, bool mask_in, int B, in
   const int* rag = nullptr;
   const int* rag_tail = nullptr;
   int rate = 1;  // columns per frame at the current stage
-  static const bool no_ragged_env = getenv("VITS_NO_RAGGED") != nullptr;
-  static const bool uniform = getenv("VITS_RAG_UNIFORM") && atoi(getenv("VITS_RAG_UNIFORM")) != 0;
   int final_rate = 1;
   for (int i = 0; i < hp.n_ups; ++i) final_rate *= hp.up_rates[i];
-  const bool layered = rag_halo > 0 && !uniform;
+  const bool layered = rag_halo > 0;
   const DecNeeds ND = decoder_needs(hp, layered);
-  if (ragged && (B > 1 || s->rag_b1) && !no_ragged_env) {
+  if (ragged && (B > 1 || s->rag_b1)) {
     // uniform form: rag = len + halo, the tail may read (len + halo) * rate columns; layered form: rag = len, every launch adds its own need
     hipLaunchKernelGGL(ragged_len_kernel, dim3(cdiv(B + 1, 64)), dim3(64), 0, s->stream, s->len_y, s->len_rag, s->len_tail, B, Ty,
                        layered ? 0 : rag_halo, final_rate, layered ? ND.tail_cols : rag_halo * final_rate);
@@ -651,8 +644,7 @@ static void set_lengths(vits_session* s, const int64_t* d_len64, int* d_len32, i
 
 static void forward_device(vits_session* s, const int64_t* d_ids, const int64_t* d_len, int B, int Tx, const float* scales,
                            const int64_t* d_sid, const int32_t* d_forced, int Ty, uint64_t seed, float* d_audio, int64_t cap) {
-  static const bool no_ragged = getenv("VITS_NO_RAGGED") != nullptr;  // A/B switch for tools/
-  s->ragged = B > 1 && !no_ragged;
+  s->ragged = B > 1;
   s->tile_keys.clear();
   run_cond(s, d_sid, B, d_len, s->len_x, Tx);
   const bool with_sdp = !d_forced || s->sdp_always;  // (logw unused when durations are pinned)

@@ -214,8 +214,7 @@ __global__ void __launch_bounds__(256) layernorm_c_kernel(const LNParams P) {
 }
 
 static void launch_layernorm(hipStream_t st, const LNParams& P, int B) {
-  static const int small_blocks = getenv("VITS_LN_SMALL") ? atoi(getenv("VITS_LN_SMALL")) : 64;  // A/B: 0 = never the 4-lane form
-  if ((long)((P.T + LN_TL - 1) / LN_TL) * B < small_blocks && P.C <= 12 * 64) {  // few columns: 4 time lanes x 64 channel groups, 4 x the blocks
+  if ((long)((P.T + LN_TL - 1) / LN_TL) * B < 64 && P.C <= 12 * 64) {  // few columns: 4 time lanes x 64 channel groups, 4 x the blocks
     const dim3 g4((P.T + 3) / 4, B);
     if (P.C <= 6 * 64) hipLaunchKernelGGL((layernorm_c_kernel<6, 4>), g4, dim3(256), 0, st, P);
     else hipLaunchKernelGGL((layernorm_c_kernel<12, 4>), g4, dim3(256), 0, st, P);

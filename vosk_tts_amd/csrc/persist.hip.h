@@ -57,8 +57,6 @@ typedef unsigned long long ll_t;  // {float value (bits 0..31), u32 epoch (bits 
 #define PS_DKP 128       // attention: head-dimension slots per row of threads (d_k <= 128)
 #define PS_MKT 12        // key tiles the attention merge polls per round (3 cells each)
 #define PS_SPIN_LIMIT (1 << 18)
-#define PS_TUNE_TOUCH 1   // PCall.tune bits
-#define PS_TUNE_DEFAULT 0
 #define PS_ERR_TIMEOUT 8  // bit in the session error word
 
 struct PersistCtl {
@@ -86,8 +84,7 @@ enum {
 // PK_MM    a1 = Cs | K << 16 ; a2 = cell pitch of the operand * channel direction (signed; plain operands: +-1); a3 = t0 (first window column)
 //          p0 operand (cells: (column 0, LOWEST channel of the slice); plain: the row of the slice's first channel),
 //          p1 yout tile (cell (n0, first row)), p2 yplain (first row, column n0), p3 res tile, p4 z, p5 zout
-//          p9 = weight fragments of this worker's NEXT matrix item (first row block; 0: none)
-//          b0 = n_u | nblk << 7 | next item's (n_u << 11 | nblk << 18 | KB between its row blocks << 22);
+//          b0 = n_u | nblk << 7;
 //          b1 = floats between consecutive row blocks of the weights; b2 = ypitch; b3 = rows left (Cout - first row);
 //          b4 = pT; b5 = rpitch; b6 = n0 | z_row << 16 | ea_row << 20; b7 = gate_H
 // PK_DDS   a1 = C | dil << 16; a2 = t; p0 xin, p1 y2, p2 z row, p3 xout, p4 bout
@@ -136,7 +133,6 @@ struct PCall {                          // per-call values (by value: a captured
   float length_scale, noise_scale;      // PK_DUR / PK_EXPAND (overridden by dv)
   const float* noise_prior;             // PK_EXPAND: injected prior noise [I][noise_stride] or null (Philox stream 2)
   long long noise_stride;
-  int tune;                             // experiment switches (VITS_PS_TUNE; default PS_TUNE_DEFAULT): bit 0 = pull the next matrix step's weights into L2 ahead of time
   int* dbg;                             // device words of the model: [0] poll rounds before a worker gives up (0 = PS_SPIN_LIMIT; tests shrink it to
                                         // force the fallback -- read at run time, so captured graphs follow the hook), [1] completed persistent launches
 };
@@ -310,29 +306,6 @@ __device__ __forceinline__ void ps_prefetch(const ps_i4& r, int tid, int wave, i
   ps_load_weights(PR_P(const float, r, 6), PR_B(r, 0) & 0x7f, wave, lane, pre.a);
 }
 
-// LDS-DMA load of one dword per lane into a scratch slot of the LDS: a load WITHOUT a register destination.  Used to pull lines into
-// this XCD's L2 ahead of time.  The compiler does not see it (inline asm): it is absent from its s_waitcnt bookkeeping, which is
-// what is wanted here -- nothing ever waits for it -- and harmless for the loads the compiler does count (vmcnt retires in order:
-// a counted wait can only wait longer, never shorter).  M0 holds the LDS destination and is restored (cdna_hip_programming.md 5.7).
-__device__ __forceinline__ void ps_glds_dword(const PS_G char* g, unsigned lds_dst) {
-  unsigned keep;
-  asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dword %1, off\n\ts_mov_b32 m0, %0" : "=&s"(keep) : "v"(g), "s"(lds_dst) : "memory");
-}
-// the weight fragments wave `wave` will stream in a later matrix step (units u = wave + 8 i of nblk row blocks, 1 KiB each): one dword
-// per 64 bytes, four units per instruction
-__device__ __forceinline__ void ps_touch_weights(const PS_G char* w, int n_u, int nblk, unsigned stride_bytes, int wave, int lane, unsigned lds_dst) {
-  const unsigned lo = (unsigned)(lane & 15) * 64u;
-  for (int blk = 0; blk < nblk; ++blk) {
-#pragma unroll
-    for (int h = 0; h < 2; ++h) {
-      int u = wave + PS_WAVES * (h * 4 + (lane >> 4));
-      u = u < n_u ? u : n_u - 1;  // (beyond the last unit: a line that is fetched anyway)
-      ps_glds_dword(w + ((unsigned)u * 1024u + lo), lds_dst);
-    }
-    w += stride_bytes;
-  }
-}
-
 // Placed where a poll has just completed: the record of step s + 1 (requested at the top of this step, older than every poll load) is
 // certainly there -- touching it HERE makes the compiler account for its wait at a point where it costs nothing.  Without this the
 // hand-over rv = rvB at the loop's back edge is the first use, and because loads and stores share the in-order vmcnt counter the
@@ -358,7 +331,6 @@ __global__ void __launch_bounds__(PS_THREADS) persist_kernel(const PProgram* __r
   __shared__ float hb[32 * 16];            // ConvFlow.proj output of the tile (spline parameters)
   __shared__ float xs[3 * PS_MAXC];        // column steps: x_in at t - d, t, t + d
   __shared__ float red[4 * 16];            // block reductions (one 16-float scratch per call site)
-  __shared__ float dma_sink[64];           // destination of the L2 pre-touch loads (never read)
   __shared__ __attribute__((aligned(16))) float att_r[PS_WAVES * 256];  // attention blocks: partial q E_k^T tiles of the 8 waves
   __shared__ float att_p[16 * 17];         // attention blocks: probabilities [query][key], pitch 17 (conflict-free MFMA A reads)
   const int tid0 = threadIdx.x;
@@ -1086,16 +1058,6 @@ __global__ void __launch_bounds__(PS_THREADS) persist_kernel(const PProgram* __r
           rsd0 = ll_val(qr);
         }
         PS_STAMP(1); PS_REC_READY();
-        // The poll has completed: this CU's memory queue is empty and ~4 k cycles of LDS and matrix work follow.  The moment to pull
-        // the weights of this worker's NEXT matrix item towards it (into the XCD's L2; the workers of the other column tiles that
-        // stream the same fragments sit on the same XCD, persist_plan.hip.h).  Measured neutral to slightly negative at c2 (round 4,
-        // profiles/r4_persist_ab.txt): off by default, kept as a switch (VITS_PS_TUNE bit 0).
-        if (call.tune & PS_TUNE_TOUCH) {
-          const int nx = PR_B(rv, 0) >> 11;
-          if (nx & 0x7f)
-            ps_touch_weights(PR_P(const char, rv, 9), nx & 0x7f, (nx >> 7) & 0xf, (unsigned)((nx >> 11) & 0x1ff) << 10, wave, lane,
-                             __builtin_amdgcn_readfirstlane((unsigned)(size_t)dma_sink));
-        }
         if (cok) {
           float* tp = tile + c * PS_TP + jh;
 #pragma unroll

@@ -342,13 +342,12 @@ static void persist_resolve(vits_session* s, const std::vector<PStep>& steps, in
   // in dispatch order (worker = item) they sit on ntn different XCDs -- block b runs on XCD b % 8 (MI355X_MICROARCH.md; a
   // placement for speed only, nothing depends on it) -- and every XCD's L2 fetches every fragment of the step from the fabric
   // (round 3 PMC: 200 MB per launch against 26 MB of weights).  Placement by weight group: group q -> XCD q % 8, its tiles on
-  // consecutive workers of that XCD; groups beyond 8 * floor(P / 8 / ntn) fill the workers left over.  VITS_PS_XCD=0: dispatch order.
-  static const bool xcd_place = !(getenv("VITS_PS_XCD") && atoi(getenv("VITS_PS_XCD")) == 0);
+  // consecutive workers of that XCD; groups beyond 8 * floor(P / 8 / ntn) fill the workers left over.
   std::vector<int> rank_of, used;
   auto place = [&](int Q) {
     const int items = Q * ntn;
     rank_of.assign(items, -1);
-    if (!xcd_place || P % 8 || P / 8 < ntn) { for (int i = 0; i < items; ++i) rank_of[i] = i; return; }
+    if (P % 8 || P / 8 < ntn) { for (int i = 0; i < items; ++i) rank_of[i] = i; return; }
     used.assign(P, 0);
     const int per = P / 8, cap = per / ntn;
     for (int q = 0; q < Q && q < 8 * cap; ++q)
@@ -416,7 +415,7 @@ static void persist_resolve(vits_session* s, const std::vector<PStep>& steps, in
         r.p[6] = U(st.w16 + ((size_t)mb0 * st.ks + slice) * n_u * 256);
         r.p[7] = U(st.bias + (st.bias == m->zeros ? 0 : row0));
         r.p[8] = U(st.cond + (st.cond == m->zeros ? 0 : row0));
-        r.b[0] = n_u | (nblk << 7);  // (+ the next matrix item of this worker: chained below)
+        r.b[0] = n_u | (nblk << 7);
         r.b[1] = st.ks * n_u * 256;
         r.b[2] = st.ypitch;
         r.b[3] = gate ? 2 * st.gate_H : st.Cout - row0;
@@ -491,22 +490,6 @@ static void persist_resolve(vits_session* s, const std::vector<PStep>& steps, in
       }
     }
     if ((int)(recs.size() / P) > PS_MAX_STEPS) { bad = true; return; }
-  }
-  // chain: every matrix record says where the same worker's NEXT matrix item streams its weights from (the kernel pulls them into L2
-  // while it computes this one)
-  const int nst = (int)(recs.size() / P);
-  for (int w = 0; w < P; ++w) {
-    unsigned long long nw = 0;
-    int nx = 0;
-    for (int si = nst - 1; si >= 0; --si) {
-      PRec& r = recs[(size_t)si * P + w];
-      if ((r.kf & 0xff) != PK_MM) continue;
-      const int n_u = r.b[0] & 0x7f, nblk = (r.b[0] >> 7) & 0xf, kb = r.b[1] / 256;  // b1 = floats between row blocks = ks * n_u KiB
-      r.p[9] = nw;
-      r.b[0] |= nx << 11;
-      nw = r.p[6];
-      nx = (kb < 512 && n_u < 128) ? (n_u | (nblk << 7) | (kb << 11)) : 0;
-    }
   }
 }
 

@@ -1291,9 +1291,8 @@ static void bert_forward(bert_model* m, vits_session* s, const int64_t* d_ids, c
     launch_layernorm(s->stream, P, 1);
   }
   // (round 5) sentence-sized calls: the 3072 -> 768 matrix of the FFN is the one launch of a layer that ran on 24 CUs (21 us of a 75 us
-  // layer, profiles/r5_bert_ffn2.txt); VITS_BERT_KSLICE=0: the single launch (A/B)
-  static const bool kslice_env = !(getenv("VITS_BERT_KSLICE") && atoi(getenv("VITS_BERT_KSLICE")) == 0);
-  const bool ffn2_slices = kslice_env && g_force_tile == 0 && T <= 64 && T >= 4 && hp.intermediate % (3 * CONV_CI_T) == 0 && hp.intermediate / 3 >= 8 * CONV_CI_T &&
+  // layer, profiles/r5_bert_ffn2.txt)
+  const bool ffn2_slices = g_force_tile == 0 && T <= 64 && T >= 4 && hp.intermediate % (3 * CONV_CI_T) == 0 && hp.intermediate / 3 >= 8 * CONV_CI_T &&
                            H % 32 == 0 && !m->layers.empty() && m->layers[0].c2.K == 1;
   for (const BertLayerW& L : m->layers) {
     ConvParams P = conv_params(L.qkv, x, qkv, 1, T, 1, 0);
