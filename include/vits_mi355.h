@@ -105,7 +105,17 @@ typedef struct vits_hparams {
                                 run on the bf16 matrix core with every operand split into two bf16 pieces (hi*hi + hi*lo + lo*hi,
                                 fp32 accumulation; csrc/conv_bf3.hip.h) -- BASELINE configs[2]'s reduced-precision variant in the
                                 form that keeps fp32-class accuracy (~4e-6 per conv) */
-  int32_t reserved[6];
+  int32_t flow_type;         /* coupling layers of the flow (ResidualCouplingTransformersBlock, models.py:630-762):
+                                0 = ResidualCouplingTransformersLayer2 ("pre_conv2", models.py:329-396; vosk's config): a one-layer
+                                    pre-transformer on hidden_channels after `pre`, relative positions (window_size, n_heads above),
+                                1 = ResidualCouplingTransformersLayer ("pre_conv", models.py:399-483; the upstream VITS2 default): a two-layer
+                                    attentions.Encoder on the inter_channels/2 channels of x0 BEFORE `pre`, 2 heads, FFN kernel 3, filter
+                                    inter_channels/2, no relative positions (window_size=None); its head dim inter_channels/4 must be a
+                                    multiple of 16 in [16, 96].  post_transformer is never run and not in the blob,
+                                2 = modules.ResidualCouplingLayer (the VITS-1 coupling, modules.py:298-345; use_transformer_flows false):
+                                    pre, WN, post, no transformer.
+                                Any other value: vits_create returns VITS_ERR_UNSUPPORTED.  (Blobs written before the field existed hold 0.) */
+  int32_t reserved[5];
 } vits_hparams;
 
 /*

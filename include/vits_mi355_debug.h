@@ -70,6 +70,13 @@ void vits_debug_no_bf16x3(int on);
 void vits_debug_tail_impl(int impl);
 /* Test hook: fill every newly laid-out workspace with NaN bit patterns (stale-padding detector). */
 void vits_debug_poison_workspace(int on);
+/* Test hook: the attention of the pre_conv flow's pre-transformer (window_size=None: masked multi-head softmax attention with no
+ * relative-position terms, plain_attention_kernel / plain_attention16_kernel) on caller host buffers.  qkv float [B, 3C, T] holds
+ * q, k, v rows as the fused q/k/v conv writes them, out float [B, C, T]; keys >= lengths[b] carry no weight and query columns
+ * >= lengths[b] are written as 0.  C / n_heads must be a multiple of 16 in [16, 96].  The tile variant is the engine's choice by
+ * grid size, or the one vits_debug_attention_impl forces (2: 32-query tiles, 3: 16-query tiles). */
+int vits_debug_plain_attention(int device, const float* qkv, const int64_t* lengths, int32_t B, int32_t C, int32_t T,
+                               int32_t n_heads, float* out);
 
 /* Shader clock under load (round 6): launches `n` one-wave workgroups on a stream of the library's own that sit on the device for
  * `duration_us` and compare the shader-clock counter (s_memtime) with the constant 100 MHz wall clock (s_memrealtime); ghz[i] = the clock

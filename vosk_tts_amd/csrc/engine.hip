@@ -632,6 +632,39 @@ int vits_debug_clock_probe(int device, int32_t duration_us, double* ghz, int32_t
 }
 void vits_debug_no_bf16x3(int on) { g_no_bf3 = on; }
 void vits_debug_poison_workspace(int on) { g_poison = on; }
+// The attention of the pre_conv flow's pre-transformer (no relative positions, plain_attention*_kernel) on caller buffers: qkv [B, 3C, T]
+// (q | k | v rows, as the fused q/k/v conv writes them), out [B, C, T].  Tile variant as the engine picks it, or forced by
+// vits_debug_attention_impl (2: 32-query, 3: 16-query).
+int vits_debug_plain_attention(int device, const float* qkv, const int64_t* lengths, int32_t B, int32_t C, int32_t T, int32_t n_heads,
+                               float* out) {
+  if (!qkv || !lengths || !out || B <= 0 || B > 65535 || T <= 0 || C <= 0 || n_heads <= 0 || n_heads > 64 || C % n_heads)
+    return fail(VITS_ERR_ARG, "plain attention: bad arguments");
+  if (!plain_attention_dk_ok(C / n_heads)) return fail(VITS_ERR_UNSUPPORTED, "plain attention: head dim %d not built", C / n_heads);
+  std::vector<int> len32(B);
+  for (int b = 0; b < B; ++b) {
+    if (lengths[b] < 0 || lengths[b] > T) return fail(VITS_ERR_ARG, "plain attention: length out of range");
+    len32[b] = (int)lengths[b];
+  }
+  HIP_TRY(hipSetDevice(device));
+  const size_t nq = (size_t)B * 3 * C * T, no = (size_t)B * C * T;
+  float *d_qkv = nullptr, *d_out = nullptr;
+  int* d_len = nullptr;
+  hipError_t e = hipMalloc((void**)&d_qkv, nq * sizeof(float));
+  if (e == hipSuccess) e = hipMalloc((void**)&d_out, no * sizeof(float));
+  if (e == hipSuccess) e = hipMalloc((void**)&d_len, B * sizeof(int));
+  if (e == hipSuccess) e = hipMemcpy(d_qkv, qkv, nq * sizeof(float), hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = hipMemcpy(d_len, len32.data(), B * sizeof(int), hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = hipMemset(d_out, 0xff, no * sizeof(float));  // NaN: an output the kernel does not write shows
+  if (e == hipSuccess) {
+    launch_plain_attention_on(nullptr, d_qkv, d_len, d_out, B, C, T, n_heads);
+    e = hipGetLastError();
+  }
+  if (e == hipSuccess) e = hipDeviceSynchronize();
+  if (e == hipSuccess) e = hipMemcpy(out, d_out, no * sizeof(float), hipMemcpyDeviceToHost);
+  hipFree(d_qkv); hipFree(d_out); hipFree(d_len);
+  if (e != hipSuccess) return fail(VITS_ERR_DEVICE, "plain attention: %s", hipGetErrorString(e));
+  return VITS_OK;
+}
 
 int vits_session_sync(vits_session* s) {
   if (!s) return fail(VITS_ERR_ARG, "null session");

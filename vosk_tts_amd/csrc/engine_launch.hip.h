@@ -611,7 +611,48 @@ static void launch_attention_raw(vits_session* s, const float* qkv, const float*
   else hipLaunchKernelGGL((relpos_attention_kernel<32>), grid, dim3(256), 0, s->stream, qkv, L.ek, L.ev, len, out, H, T, W);
 }
 
-static void launch_attention(vits_session* s, const float* qkv, const EncLayerW& L, const int* len, float* out, int B, int H, int T) {
-  launch_attention_raw(s, qkv, L.ek, L.ev, len, out, B, H, T, s->m->hp.n_heads, s->m->hp.window_size);
+// Attention with no relative-position terms (window_size=None: the pre-transformer of the `pre_conv` flow) on plain_attention*_kernel
+// (kernels_misc.hip.h), the tile variant picked by the rule above; g_attn_impl 2 / 3 force the 32- / 16-query kernel (1, the VALU
+// cross-check, has no plain form: the 32-query kernel runs).  Returns false for a head dim the kernels are not built for.
+static bool plain_attention_use16(int B, int T, int nh) {
+  const bool small_grid = (long)cdiv(T, 32) * nh * B < 256;
+  return g_attn_impl == 3 || (g_attn_impl == 0 && (T <= 64 || (small_grid && T <= 4096)));
+}
+static bool launch_plain_attention_on(hipStream_t st, const float* qkv, const int* len, float* out, int B, int H, int T, int nh) {
+  if (nh <= 0 || H % nh || !plain_attention_dk_ok(H / nh)) return false;
+  const int dk = H / nh;
+  if (plain_attention_use16(B, T, nh)) {
+    dim3 grid(cdiv(T, 16), nh, B);
+    const bool w8 = T > 64;
+    const int wreg = 16 * (dk + 4), nv = (dk / 16) * 4 + 2;
+    const size_t lds = (size_t)(w8 ? 8 : 4) * (wreg > nv * 64 ? wreg : nv * 64) * sizeof(float);
+#define PATT16_GO(DK_)                                                                                                             \
+  case DK_:                                                                                                                        \
+    if (w8) hipLaunchKernelGGL((plain_attention16_kernel<DK_, 8>), grid, dim3(512), lds, st, qkv, len, out, H, T);               \
+    else hipLaunchKernelGGL((plain_attention16_kernel<DK_, 4>), grid, dim3(256), lds, st, qkv, len, out, H, T);                  \
+    break;
+    switch (dk) { PATT16_GO(16) PATT16_GO(32) PATT16_GO(48) PATT16_GO(64) PATT16_GO(80) PATT16_GO(96) }
+#undef PATT16_GO
+    return true;
+  }
+  dim3 grid(cdiv(T, 32), nh, B);
+  const int nd = (dk + 31) / 32, wreg = nd * 32 * 33, nv = nd * 16 + 2;
+  const size_t lds = (size_t)4 * (wreg > nv * 64 ? wreg : nv * 64) * sizeof(float);
+#define PATT_GO(DK_) \
+  case DK_: hipLaunchKernelGGL((plain_attention_kernel<DK_>), grid, dim3(256), lds, st, qkv, len, out, H, T); break;
+  switch (dk) { PATT_GO(16) PATT_GO(32) PATT_GO(48) PATT_GO(64) PATT_GO(80) PATT_GO(96) }
+#undef PATT_GO
+  return true;
+}
+
+// one attention layer of encoder E: its own head count, relative-position window (W < 0: none) and width
+static void launch_attention(vits_session* s, const float* qkv, const EncoderW& E, const EncLayerW& L, const int* len, float* out, int B, int T) {
+  if (E.W >= 0) {
+    launch_attention_raw(s, qkv, L.ek, L.ev, len, out, B, E.H, T, E.nh, E.W);
+    return;
+  }
+  ProfScope ps(s, "attention", 4.0 * (double)B * E.H * T * T,
+               plain_attention_use16(B, T, E.nh) ? "plain_attention16_kernel" : "plain_attention_kernel");
+  launch_plain_attention_on(s->stream, qkv, len, out, B, E.H, T, E.nh);  // (head dim checked at load)
 }
 

@@ -17,6 +17,7 @@ struct EncLayerW {
 struct EncoderW {
   std::vector<EncLayerW> layers;
   int H = 0, F = 0, K = 0;
+  int nh = 0, W = 0;  // attention heads and relative-position window; W < 0: window_size=None (no emb_rel_k / emb_rel_v)
 };
 struct DDSW {
   std::vector<float*> sw, sb, g1, b1, g2, b2;
@@ -219,10 +220,10 @@ static ConvW conv_from(vits_model* m, const char* name, int Cout, int Cin, int K
   return c;
 }
 
-static void load_encoder(vits_model* m, EncoderW& E, const char* pfx, int n_layers, int H, int F, int K) {
+static void load_encoder(vits_model* m, EncoderW& E, const char* pfx, int n_layers, int H, int F, int K, int nh, int W) {
   const vits_hparams& hp = m->hp;
-  const int dk = H / hp.n_heads, NW = 2 * hp.window_size + 1;
-  E.H = H; E.F = F; E.K = K;
+  const int dk = H / nh, NW = 2 * W + 1;
+  E.H = H; E.F = F; E.K = K; E.nh = nh; E.W = W;
   E.layers.resize(n_layers);
   char nm[200];
   for (int i = 0; i < n_layers && !m->missing; ++i) {
@@ -246,8 +247,10 @@ static void load_encoder(vits_model* m, EncoderW& E, const char* pfx, int n_laye
     if (bf3) add_bf3_packing(m, L.qkv, qkv_src);
     snprintf(nm, sizeof nm, "%s.attn_layers.%d.conv_o", pfx, i);
     L.o = conv_from(m, nm, H, H, 1, true, true, bf3);
-    L.ek = upload(m, tget(m, 3, 1, NW, dk, "%s.attn_layers.%d.emb_rel_k", pfx, i), (size_t)NW * dk);
-    L.ev = upload(m, tget(m, 3, 1, NW, dk, "%s.attn_layers.%d.emb_rel_v", pfx, i), (size_t)NW * dk);
+    if (W >= 0) {
+      L.ek = upload(m, tget(m, 3, 1, NW, dk, "%s.attn_layers.%d.emb_rel_k", pfx, i), (size_t)NW * dk);
+      L.ev = upload(m, tget(m, 3, 1, NW, dk, "%s.attn_layers.%d.emb_rel_v", pfx, i), (size_t)NW * dk);
+    }
     snprintf(nm, sizeof nm, "%s.ffn_layers.%d.conv_1", pfx, i);
     L.f1 = conv_from(m, nm, F, H, K, true, true, bf3);
     snprintf(nm, sizeof nm, "%s.ffn_layers.%d.conv_2", pfx, i);
@@ -469,10 +472,14 @@ static int load_model(vits_model* m) {
   if (hp.dp_num_bins > 15 || hp.n_ups > VITS_MAX_UPS || hp.n_resk > 3 || hp.n_resd > VITS_MAX_RESD || hp.n_ups < 1)
     return fail(VITS_ERR_UNSUPPORTED, "hparams out of range");
   if (hp.flow_dilation_rate != 1) return fail(VITS_ERR_UNSUPPORTED, "flow dilation_rate != 1");
+  if (hp.flow_type < 0 || hp.flow_type > 2)
+    return fail(VITS_ERR_UNSUPPORTED, "flow_type %d (0 = pre_conv2, 1 = pre_conv, 2 = plain ResidualCouplingLayer)", hp.flow_type);
+  if (hp.flow_type == 1 && (I % 4 || !plain_attention_dk_ok(I / 4)))  // pre_conv: 2 heads on I/2 channels
+    return fail(VITS_ERR_UNSUPPORTED, "pre_conv flow: head dim inter_channels/4 = %d is not a multiple of 16 in [16, 96]", I / 4);
   m->use_g = G > 0 && hp.n_speakers > 1;
 
   m->emb = upload(m, tget(m, 2, hp.n_vocab, H, -1, "enc_p.emb.weight"), (size_t)hp.n_vocab * H);
-  load_encoder(m, m->enc_p, "enc_p.encoder", hp.n_layers, H, F, hp.kernel_size);
+  load_encoder(m, m->enc_p, "enc_p.encoder", hp.n_layers, H, F, hp.kernel_size, hp.n_heads, hp.window_size);
   m->enc_proj = conv_from(m, "enc_p.proj", 2 * I, H, 1, true);
   if (hp.bert_dim < 0 || hp.bert_dim % CONV_CI_T) return fail(VITS_ERR_UNSUPPORTED, "bert_dim %d must be a multiple of %d", hp.bert_dim, CONV_CI_T);
   if (hp.conv_precision != 0 && hp.conv_precision != 1) return fail(VITS_ERR_UNSUPPORTED, "conv_precision %d (0 = fp32, 1 = split-bf16 decoder convs)", hp.conv_precision);
@@ -527,7 +534,10 @@ static int load_model(vits_model* m) {
     snprintf(nm, sizeof nm, "flow.flows.%d.pre", 2 * f);
     c.pre = conv_from(m, nm, H, I / 2, 1, true);
     snprintf(nm, sizeof nm, "flow.flows.%d.pre_transformer", 2 * f);
-    load_encoder(m, c.enc, nm, 1, H, H, K5);
+    // pre_conv2 (models.py:353-360): 1 layer on H channels, the text encoder's heads and window.  pre_conv (models.py:417-425):
+    // 2 layers on the I/2 channels of x0, 2 heads, FFN kernel 3 with filter I/2, window_size=None.  plain: no pre-transformer.
+    if (hp.flow_type == 0) load_encoder(m, c.enc, nm, 1, H, H, K5, hp.n_heads, hp.window_size);
+    else if (hp.flow_type == 1) load_encoder(m, c.enc, nm, 2, I / 2, I / 2, 3, 2, -1);
     for (int i = 0; i < L && !m->missing; ++i) {
       // in_layer rows permuted to [tanh 32 | sigmoid 32] per 32 channels for the fused gate epilogue
       const float* w = tget(m, 3, 2 * H, H, K5, "flow.flows.%d.enc.in_layers.%d.weight", 2 * f, i);

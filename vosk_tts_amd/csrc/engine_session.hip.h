@@ -213,6 +213,8 @@ static void plan(vits_session* s, int B, int Tx, int Ty) {
   const size_t H = hp.hidden_channels, I = hp.inter_channels, F = hp.filter_channels, D = hp.dp_filter_channels;
   const size_t Fm = F > H ? F : H;
   const size_t Tm = (size_t)(Tx > Ty ? Tx : Ty);
+  // width of the encoder-shaped scratch: the pre_conv flow's pre-transformer runs on I/2 channels (engine_stages.hip.h run_flow)
+  const size_t He = hp.flow_type == 1 && I / 2 > H ? I / 2 : H;
   s->arena_used = 0;
   s->B = B; s->Tx = Tx; s->Ty = Ty;
   s->len_x = bump<int>(s, B); s->len_y = bump<int>(s, B); s->len_rag = bump<int>(s, B + 1); s->len_tail = bump<int>(s, B);
@@ -221,14 +223,14 @@ static void plan(vits_session* s, int B, int Tx, int Ty) {
   s->condv = bump<float>(s, (size_t)B * (s->m->cond_rows + 1));
   s->tile_tabs = bump<int>(s, (size_t)32 * (B + 1));
   // encoder-shaped scratch is shared by the text encoder (T_x) and the flow pre-transformers (T_y)
-  s->x = bump<float>(s, B * H * Tm);
-  s->qkv = bump<float>(s, B * 3 * H * Tm);
-  s->att = bump<float>(s, B * H * Tm);
-  s->y1 = bump<float>(s, B * H * Tm);
-  s->xb = bump<float>(s, B * H * Tm);
-  s->y1b = bump<float>(s, B * H * Tm);
+  s->x = bump<float>(s, B * He * Tm);
+  s->qkv = bump<float>(s, B * 3 * He * Tm);
+  s->att = bump<float>(s, B * He * Tm);
+  s->y1 = bump<float>(s, B * He * Tm);
+  s->xb = bump<float>(s, B * He * Tm);
+  s->y1b = bump<float>(s, B * He * Tm);
   s->lnst = bump<float>(s, (size_t)B * 16 * Tm * 2);
-  s->ffh = bump<float>(s, B * Fm * Tm);
+  s->ffh = bump<float>(s, B * (Fm > He ? Fm : He) * Tm);
   s->stats = bump<float>(s, B * 2 * I * Tx);
   s->dh = bump<float>(s, B * D * Tx); s->dy = bump<float>(s, B * D * Tx); s->dy2 = bump<float>(s, B * D * Tx);
   s->dc = bump<float>(s, B * D * Tx); s->dfh = bump<float>(s, B * D * Tx);
@@ -253,9 +255,9 @@ static void plan(vits_session* s, int B, int Tx, int Ty) {
     s->ps_x_zp = p;
   }
   s->zA = bump<float>(s, B * I * Ty); s->zB = bump<float>(s, B * I * Ty);
-  s->fh = bump<float>(s, B * H * Ty); s->fx = bump<float>(s, B * H * Ty);
+  s->fh = bump<float>(s, B * He * Ty); s->fx = bump<float>(s, B * H * Ty);
   s->facts = bump<float>(s, B * H * Ty * (size_t)(hp.flow_wn_layers > 0 ? hp.flow_wn_layers : 1));  // gate outputs of all WN layers, stacked
-  s->fskip = bump<float>(s, B * H * Ty);
+  s->fskip = bump<float>(s, B * He * Ty);
   // decoder: conv_pre out, then per stage: ups out + 3 tmp + 3 res-chain (models.py:1026-1036)
   s->dec_bufs.clear();
   size_t C = hp.dec_initial_channel, T = Ty;

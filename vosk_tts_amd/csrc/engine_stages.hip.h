@@ -59,7 +59,7 @@ static void run_encoder(vits_session* s, const EncoderW& E, float* x, const int*
     }
     mark_masked(s, P, len);
     launch_conv(s, P, EPI_STORE, "enc.qkv");
-    launch_attention(s, s->qkv, L, len, s->att, B, H, T);
+    launch_attention(s, s->qkv, E, L, len, s->att, B, T);
     P = conv_params(L.o, s->att, s->y1, B, T, 1, 0);  // y1 = x + conv_o(att)
     P.g[0].res = x;
     if (pstat) { P.ln_stat_out = s->lnst; P.ln_nmb = H / 16; }
@@ -341,15 +341,26 @@ static float* run_flow(vits_session* s, int B, int Ty) {
   float* v = s->zB;
   for (int f = hp.flow_n_flows - 1; f >= 0; --f) {
     const CouplingW& C = m->flow[f];
-    // h = pre(x0) * mask, x0[c] = u[I-1-c]  (models.py:375-376 after Flip)
-    ConvParams P = conv_params(C.pre, u, s->fh, B, Ty, 1, 0);
-    P.x_ch_off = I - 1; P.x_ch_sign = -1; P.x_bstride = (long long)I * Ty;
-    P.out_mask = 1; P.len = s->len_y;
-    mark_masked(s, P, s->len_y);
-    P.g[0].y2 = s->x;  // second copy: the pre-transformer updates its input in place, fh stays the residual base
-    launch_conv(s, P, EPI_STORE, "flow.pre");
-    // h = h + pre_transformer(h * mask)  (models.py:377)
-    run_encoder(s, C.enc, s->x, s->len_y, B, Ty, -1, -1, s->fh, s->fx);
+    ConvParams P;
+    if (hp.flow_type == 1) {
+      // pre_conv (models.py:460-462): x0_ = pre_transformer(x0 * mask) + x0 ; h = pre(x0_) * mask, x0[c] = u[I-1-c]
+      hipLaunchKernelGGL(flow_x0_kernel, dim3(cdiv(Ty, 256), half, B), dim3(256), 0, s->stream, u, s->x, s->fh, s->len_y, I, half, Ty);
+      run_encoder(s, C.enc, s->x, s->len_y, B, Ty, -1, -1, s->fh, s->fskip);
+      P = conv_params(C.pre, s->fskip, s->fx, B, Ty, 1, 0);
+      P.out_mask = 1; P.len = s->len_y;
+      mark_masked(s, P, s->len_y);
+      launch_conv(s, P, EPI_STORE, "flow.pre");
+    } else {
+      // h = pre(x0) * mask, x0[c] = u[I-1-c]  (models.py:375-376 after Flip; modules.py:334-335)
+      P = conv_params(C.pre, u, hp.flow_type == 0 ? s->fh : s->fx, B, Ty, 1, 0);
+      P.x_ch_off = I - 1; P.x_ch_sign = -1; P.x_bstride = (long long)I * Ty;
+      P.out_mask = 1; P.len = s->len_y;
+      mark_masked(s, P, s->len_y);
+      if (hp.flow_type == 0) P.g[0].y2 = s->x;  // second copy: the pre-transformer updates its input in place, fh stays the residual base
+      launch_conv(s, P, EPI_STORE, "flow.pre");
+      // h = h + pre_transformer(h * mask)  (models.py:377)
+      if (hp.flow_type == 0) run_encoder(s, C.enc, s->x, s->len_y, B, Ty, -1, -1, s->fh, s->fx);
+    }
     // WN (modules.py:148-176): fx is the running x.  Folded form (default): the gate outputs of all layers are kept, stacked
     // [L*H, T]; res_skip layer i < L-1 only updates x (its residual half); one [I/2 x L*H] conv = post o (sum of skip halves)
     // feeds the coupling tail.  Unfolded form (vits_debug_wn_fold(0)): res/skip epilogue per layer + post, as the reference runs it.

@@ -1510,6 +1510,302 @@ __global__ void __launch_bounds__(NW * 64) relpos_attention16_kernel(const float
   }
 }
 
+// ----------------------------------------------------------------------------- attention without relative positions
+// MultiHeadAttention.attention with window_size=None (attentions.py:165-196): scores = (q / sqrt(d_k)) k^T, keys >= len masked,
+// softmax, p v.  The pre-transformer of the `pre_conv` flow (models.py:417-425) runs it over T_y frames at head dim
+// inter_channels / 4 (48 at the default size), 8 layers per forward.  Two tilings of the same flash-style online softmax (O(T)
+// memory), fp32 operands on the fp32 matrix cores; query rows >= len are written as 0 ("masked rows" in DESIGN.md).
+//
+// plain_attention_kernel<DK>: 32 queries per workgroup, the "swapped" v_mfma_f32_32x32x2_f32 formulation of
+// relpos_attention_mfma_kernel with the relative-position work removed and any DK that is a multiple of 16: S^T = K Q^T takes
+// DK / 2 k-steps; O^T = V P^T is produced in 32-row d tiles, so a DK that is not a multiple of 32 (48, 80) pads its last tile with
+// zero V rows (48: 2 tiles for 1.5 of work, 56 MFMAs per key tile instead of 48).  4 waves split the key tiles and merge (m, l, O).
+// x0 of a `pre_conv` / plain coupling layer after the folded Flip: x[b][c][t] = u[b][I-1-c][t] on valid frames, 0 beyond len[b], written
+// to x (the pre-transformer's in-place input) and x2 (its residual base)
+__global__ void flow_x0_kernel(const float* u, float* x, float* x2, const int* len, int I, int C, int T) {
+  const int t = blockIdx.x * 256 + threadIdx.x, c = blockIdx.y, b = blockIdx.z;
+  if (t >= T) return;
+  const float v = t < len[b] ? u[((long long)b * I + (I - 1 - c)) * T + t] : 0.f;
+  const long long o = ((long long)b * C + c) * T + t;
+  x[o] = v;
+  x2[o] = v;
+}
+
+// head dims both kernels are instantiated for (engine_launch.hip.h launch_plain_attention_on)
+static inline bool plain_attention_dk_ok(int dk) { return dk % 16 == 0 && dk >= 16 && dk <= 96; }
+template <int DK>
+__global__ void __launch_bounds__(256, 2) plain_attention_kernel(const float* qkv, const int* len, float* out, int H, int T) {
+  static_assert(DK % 16 == 0 && DK >= 16 && DK <= 96, "head dim");
+  constexpr int NS = DK / 2, ND = (DK + 31) / 32, VS = 33;
+  constexpr int WREG = ND * 32 * VS;  // per-wave LDS: V tile [ND * 32 d rows][33]
+  extern __shared__ float lds[];
+  const int lane = threadIdx.x & 63, h = lane >> 5, l31 = lane & 31;
+  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int hd = blockIdx.y, b = blockIdx.z, i0 = blockIdx.x * 32;
+  const int L = len[b] < T ? len[b] : T;
+  const int i = i0 + l31;
+  float* ob = out + ((long long)b * H + (long long)hd * DK) * T;
+  if (i0 >= L) {  // whole query tile is padding: zeros
+    if (i < T)
+      for (int d = (threadIdx.x >> 5); d < DK; d += 8) ob[(long long)d * T + i] = 0.f;
+    return;
+  }
+  const bool active = i < L;
+  const int ic = active ? i : L - 1;
+  const float* qb = qkv + ((long long)b * 3 * H + (long long)hd * DK) * T;
+  const float* kb = qb + (long long)H * T;
+  const float* vb = kb + (long long)H * T;
+  float* vt = lds + wave * WREG;
+  const float scale = 1.0f / sqrtf((float)DK);
+  if (DK % 32) {  // padding rows of the last d tile: zero once, never written by the tile loop
+    for (int x = lane; x < (ND * 32 - DK) * VS; x += 64) vt[DK * VS + x] = 0.f;
+  }
+
+  // B operand of every QK^T step: Q^T[d = 2s + h][query], pre-scaled
+  float qf[NS];
+#pragma unroll
+  for (int s = 0; s < NS; ++s) qf[s] = qb[(long long)(2 * s + h) * T + ic] * scale;
+
+  f32x16 O[ND];
+#pragma unroll
+  for (int dt = 0; dt < ND; ++dt)
+#pragma unroll
+    for (int e = 0; e < 16; ++e) O[dt][e] = 0.f;
+  float m = -3.0e38f, l = 0.f;
+
+  const int ntiles = (L + 31) >> 5;
+  float kf[NS];
+  auto load_k = [&](int jt_) {
+    const int j = jt_ * 32 + l31;
+    const int jc = j < L ? j : L - 1;
+    const float* kp = kb + (long long)h * T + jc;
+#pragma unroll
+    for (int s = 0; s < NS; ++s) kf[s] = kp[(long long)(2 * s) * T];
+  };
+  if (wave < ntiles) load_k(wave);
+  for (int jt = wave; jt < ntiles; jt += 4) {
+    const int j0 = jt * 32;
+    // V tile loads issued now (keys beyond L become 0), parked in LDS once QK^T has been issued
+    float vst[NS];
+    const bool vok = j0 + l31 < L;
+    {
+      const int jc = vok ? j0 + l31 : L - 1;
+      const float* vp = vb + (long long)h * T + jc;
+#pragma unroll
+      for (int s = 0; s < NS; ++s) vst[s] = vp[(long long)(2 * s) * T];
+    }
+    f32x16 S;
+#pragma unroll
+    for (int e = 0; e < 16; ++e) S[e] = 0.f;
+#pragma unroll
+    for (int s = 0; s < NS; ++s) S = __builtin_amdgcn_mfma_f32_32x32x2f32(kf[s], qf[s], S, 0, 0, 0);
+#pragma unroll
+    for (int s = 0; s < NS; ++s) vt[(2 * s + h) * VS + l31] = vok ? vst[s] : 0.f;
+    if (jt + 4 < ntiles) load_k(jt + 4);
+    // key mask, tile max (lane l31 holds 16 of the 32 scores of its query; the other 16 are in lane l31 + 32)
+    float mx = -3.0e38f;
+#pragma unroll
+    for (int e = 0; e < 16; ++e) {
+      const int key = j0 + (e & 3) + 8 * (e >> 2) + 4 * h;
+      const float sv = key < L ? S[e] : -3.0e38f;
+      S[e] = sv;
+      mx = fmaxf(mx, sv);
+    }
+    mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
+    const float mn = fmaxf(m, mx);
+    const float alpha = __expf(m - mn);
+    float psum = 0.f;
+#pragma unroll
+    for (int e = 0; e < 16; ++e) {
+      const int key = j0 + (e & 3) + 8 * (e >> 2) + 4 * h;
+      const float pe = key < L ? __expf(S[e] - mn) : 0.f;
+      S[e] = pe;  // S now holds P^T
+      psum += pe;
+    }
+    l = l * alpha + psum;
+    m = mn;
+#pragma unroll
+    for (int dt = 0; dt < ND; ++dt)
+#pragma unroll
+      for (int e = 0; e < 16; ++e) O[dt][e] *= alpha;
+    // O^T += V P^T  (k-step s <-> keys kappa(s,0), kappa(s,1): the B fragment is S[s])
+#pragma unroll
+    for (int dt = 0; dt < ND; ++dt) {
+      const float* vrow = vt + (dt * 32 + l31) * VS + 4 * h;
+#pragma unroll
+      for (int s = 0; s < 16; ++s) O[dt] = __builtin_amdgcn_mfma_f32_32x32x2f32(vrow[(s & 3) + 8 * (s >> 2)], S[s], O[dt], 0, 0, 0);
+    }
+  }
+
+  // merge the 4 waves' partial (m, l, O) through LDS; wave w finishes values idx == w (mod 4)
+  __syncthreads();
+  constexpr int NV = ND * 16 + 2;
+  float* comb = lds;  // [wave][NV][64]
+  {
+    float* c = comb + (wave * NV) * 64 + lane;
+    c[0] = m;
+    c[64] = l;
+#pragma unroll
+    for (int dt = 0; dt < ND; ++dt)
+#pragma unroll
+      for (int e = 0; e < 16; ++e) c[(2 + dt * 16 + e) * 64] = O[dt][e];
+  }
+  __syncthreads();
+  float mw[4], sc[4];
+  float ms = -3.0e38f;
+#pragma unroll
+  for (int w = 0; w < 4; ++w) { mw[w] = comb[(w * NV) * 64 + lane]; ms = fmaxf(ms, mw[w]); }
+  float lt = 0.f;
+#pragma unroll
+  for (int w = 0; w < 4; ++w) { sc[w] = __expf(mw[w] - ms); lt += comb[(w * NV + 1) * 64 + lane] * sc[w]; }
+  lt += __shfl_xor(lt, 32, 64);
+  const float inv = lt > 0.f ? 1.0f / lt : 0.f;
+#pragma unroll
+  for (int k = 0; k < ND * 4; ++k) {
+    const int idx = 4 * k + wave;  // dt*16 + e
+    const int dt = idx >> 4, e = idx & 15;
+    const int d = dt * 32 + (e & 3) + 8 * (e >> 2) + 4 * h;
+    if (d >= DK) continue;  // padding rows of the last d tile
+    float a = 0.f;
+#pragma unroll
+    for (int w = 0; w < 4; ++w) a += comb[(w * NV + 2 + idx) * 64 + lane] * sc[w];
+    if (i < T) ob[(long long)d * T + i] = active ? a * inv : 0.f;
+  }
+}
+
+// plain_attention16_kernel<DK, NW>: the small-grid form for short sequences and single utterances (the tiling of
+// relpos_attention16_kernel without its relative-position work): 16 queries per workgroup on v_mfma_f32_16x16x4_f32, NW waves
+// split the key tiles of 16, d in exact 16-row tiles (no padding at any DK).
+template <int DK, int NW>
+__global__ void __launch_bounds__(NW * 64) plain_attention16_kernel(const float* qkv, const int* len, float* out, int H, int T) {
+  static_assert(DK % 16 == 0 && DK >= 16 && DK <= 96, "head dim");
+  constexpr int NS = DK / 4, ND = DK / 16, DS = DK + 4;
+  constexpr int WREG = 16 * DS;  // per-wave LDS: V tile [16 keys][DS]
+  extern __shared__ float lds[];
+  const int lane = threadIdx.x & 63, g = lane >> 4, l15 = lane & 15;
+  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int hd = blockIdx.y, b = blockIdx.z, i0 = blockIdx.x * 16;
+  const int len_raw = len[b];
+  const int i = i0 + l15;
+  const int ic = i < T ? i : T - 1;
+  const float* qb = qkv + ((long long)b * 3 * H + (long long)hd * DK) * T;
+  const float* kb = qb + (long long)H * T;
+  const float* vb = kb + (long long)H * T;
+  float* ob = out + ((long long)b * H + (long long)hd * DK) * T;
+  float* vt = lds + wave * WREG;
+  const float scale = 1.0f / sqrtf((float)DK);
+
+  // Q^T[d = 4s + g][query] and this wave's first K tile are requested before len[b] is needed (addresses depend on T only)
+  float qf[NS], kf[NS];
+#pragma unroll
+  for (int s = 0; s < NS; ++s) qf[s] = qb[(long long)(4 * s + g) * T + ic];
+  auto load_k = [&](int jt_) {
+    const int j = jt_ * 16 + l15;
+    const int jc = j < T ? j : T - 1;
+    const float* kp = kb + (long long)g * T + jc;
+#pragma unroll
+    for (int s = 0; s < NS; ++s) kf[s] = kp[(long long)(4 * s) * T];
+  };
+  load_k(wave);
+  __builtin_amdgcn_sched_barrier(0);
+  const int L = len_raw < T ? len_raw : T;
+  if (i0 >= L) {  // whole query tile is padding: zeros
+    if (i < T)
+      for (int d = (threadIdx.x >> 4); d < DK; d += NW * 4) ob[(long long)d * T + i] = 0.f;
+    return;
+  }
+  const bool active = i < L;
+#pragma unroll
+  for (int s = 0; s < NS; ++s) qf[s] *= scale;
+  f32x4 O[ND];
+#pragma unroll
+  for (int db = 0; db < ND; ++db) O[db] = (f32x4){0.f, 0.f, 0.f, 0.f};
+  float m = -3.0e38f, l = 0.f;  // l: this lane's partial row sum (its 4 keys per tile); the 4 lane groups add up at the end
+  const int ntiles = (L + 15) >> 4;
+  for (int jt = wave; jt < ntiles; jt += NW) {
+    const int j0 = jt * 16;
+    // V tile: lane (key = l15, d = 4s + g); keys beyond L are written as 0 (select: stale memory may hold NaN)
+    float vst[NS];
+    const bool vok = j0 + l15 < L;
+    {
+      const int jc = j0 + l15 < T ? j0 + l15 : T - 1;
+      const float* vp = vb + (long long)g * T + jc;
+#pragma unroll
+      for (int s = 0; s < NS; ++s) vst[s] = vp[(long long)(4 * s) * T];
+    }
+    f32x4 S = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int s = 0; s < NS; ++s) S = __builtin_amdgcn_mfma_f32_16x16x4f32(kf[s], qf[s], S, 0, 0, 0);
+#pragma unroll
+    for (int s = 0; s < NS; ++s) vt[l15 * DS + 4 * s + g] = vok ? vst[s] : 0.f;
+    if (jt + NW < ntiles) load_k(jt + NW);
+    float mx = -3.0e38f;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      const int key = j0 + 4 * g + e;
+      const float sv = key < L ? S[e] : -3.0e38f;
+      S[e] = sv;
+      mx = fmaxf(mx, sv);
+    }
+    mx = fmaxf(mx, __shfl_xor(mx, 16, 64));
+    mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
+    const float mn = fmaxf(m, mx);
+    const float alpha = __expf(m - mn);
+    float psum = 0.f;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      const int key = j0 + 4 * g + e;
+      const float pe = key < L ? __expf(S[e] - mn) : 0.f;
+      S[e] = pe;  // S now holds P^T
+      psum += pe;
+    }
+    l = l * alpha + psum;
+    m = mn;
+#pragma unroll
+    for (int db = 0; db < ND; ++db)
+#pragma unroll
+      for (int e = 0; e < 4; ++e) O[db][e] *= alpha;
+    // O^T += V P^T: k-step r <-> keys {4g + r}: B fragment == S[r]; A = V[d = 16 db + l15][key 4g + r]
+#pragma unroll
+    for (int db = 0; db < ND; ++db)
+#pragma unroll
+      for (int r = 0; r < 4; ++r)
+        O[db] = __builtin_amdgcn_mfma_f32_16x16x4f32(vt[(4 * g + r) * DS + db * 16 + l15], S[r], O[db], 0, 0, 0);
+  }
+  // merge the waves' partial (m, l, O) through LDS; wave w finishes output registers idx == w (mod NW)
+  __syncthreads();
+  constexpr int NV = ND * 4 + 2;
+  float* comb = lds;  // [wave][NV][64]
+  {
+    float* c = comb + (wave * NV) * 64 + lane;
+    c[0] = m;
+    c[64] = l;
+#pragma unroll
+    for (int db = 0; db < ND; ++db)
+#pragma unroll
+      for (int e = 0; e < 4; ++e) c[(2 + db * 4 + e) * 64] = O[db][e];
+  }
+  __syncthreads();
+  float sc[NW];
+  float ms = -3.0e38f;
+#pragma unroll
+  for (int w = 0; w < NW; ++w) { sc[w] = comb[(w * NV) * 64 + lane]; ms = fmaxf(ms, sc[w]); }
+  float lt = 0.f;
+#pragma unroll
+  for (int w = 0; w < NW; ++w) { sc[w] = __expf(sc[w] - ms); lt += comb[(w * NV + 1) * 64 + lane] * sc[w]; }
+  lt += __shfl_xor(lt, 16, 64);
+  lt += __shfl_xor(lt, 32, 64);
+  const float inv = lt > 0.f ? 1.0f / lt : 0.f;
+  for (int idx = wave; idx < ND * 4; idx += NW) {
+    const int db = idx >> 2, e = idx & 3;
+    float a = 0.f;
+#pragma unroll
+    for (int w = 0; w < NW; ++w) a += comb[(w * NV + 2 + idx) * 64 + lane] * sc[w];
+    const int d = db * 16 + 4 * g + e;
+    if (i < T) ob[(long long)d * T + i] = active ? a * inv : 0.f;
+  }
+}
+
 // ---- shader clock under load (vits_debug_clock_probe, include/vits_mi355_debug.h): one wave per workgroup sleeps on its CU for
 // `ticks` of the constant 100 MHz clock and reports shader-clock cycles per wall nanosecond over that interval.  s_memtime counts the
 // shader clock of the CU's XCD whether or not this wave is issuing, so the figure is the clock the kernels running NEXT to the probe

@@ -278,6 +278,46 @@ def read_initializers(path_or_bytes):
 # ---------------------------------------------------------------------------------------------------
 
 
+# ResidualCouplingTransformersBlock (models.py:630-762) builds one of these coupling-layer families; the engine serves the first three
+# (hparams.flow_type).  The mono_layer_* and fft flows cannot be exported by the reference's onnx_export.py (their
+# remove_weight_norm call fails on a layer that has none), so a graph of theirs is named, not guessed at.
+FLOW_TYPES = {"pre_conv2": 0, "pre_conv": 1, "plain": 2}
+
+
+def flow_kind_from_config(model_cfg):
+    """The coupling-layer family SynthesizerTrn builds for a config's "model" section: the selection of models.py:653-747 with the
+    defaults of models.py:1560-1561.  "mono_layer_post_residual" is an OUTER elif (:715): with use_transformer_flows false it wins,
+    any other type falls through to the plain VITS-1 coupling layers; with use_transformer_flows true an unknown type builds no flow
+    at all ("none")."""
+    use = bool(model_cfg.get("use_transformer_flows", False))
+    kind = model_cfg.get("transformer_flow_type", "mono_layer_post_residual")
+    if use:
+        return kind if kind in ("pre_conv", "pre_conv2", "fft", "mono_layer_inter_residual") else "none"
+    return "mono_layer_post_residual" if kind == "mono_layer_post_residual" else "plain"
+
+
+def _infer_flow_type(t, inter_channels):
+    """flow_type from the flow's tensors: flows.0.pre_transformer present or not, its width and whether it has relative positions."""
+    if any(k.startswith("flow.flows.0.enc.self_attn_layers.") for k in t):
+        raise NotImplementedError("flow type 'fft' (FFTransformerCouplingLayer, models.py:486-542: flow.flows.*.enc.self_attn_layers) is not "
+                                  "supported; pre_conv2, pre_conv and the plain ResidualCouplingLayer flows are")
+    if any(k.startswith("flow.flows.2.pre_transformer.") for k in t) and "flow.flows.2.pre.weight" not in t:
+        raise NotImplementedError("flow type 'mono_layer_*' (MonoTransformerFlowLayer, models.py:545-627, at flow.flows.2, 5, ...) is not "
+                                  "supported; pre_conv2, pre_conv and the plain ResidualCouplingLayer flows are")
+    q = t.get("flow.flows.0.pre_transformer.attn_layers.0.conv_q.weight")
+    if q is None:
+        if any(k.startswith("flow.flows.0.pre_transformer.") for k in t):
+            raise KeyError("flow.flows.0.pre_transformer.attn_layers.0.conv_q.weight")
+        return FLOW_TYPES["plain"]
+    rel = "flow.flows.0.pre_transformer.attn_layers.0.emb_rel_k" in t
+    if rel:
+        return FLOW_TYPES["pre_conv2"]
+    if q.shape[0] == inter_channels // 2:
+        return FLOW_TYPES["pre_conv"]
+    raise NotImplementedError(f"flow pre-transformer of width {q.shape[0]} without relative positions (inter_channels {inter_channels}): "
+                              "neither pre_conv2 nor pre_conv")
+
+
 def infer_hparams(t):
     """Hyper-parameters from tensor shapes (training/vits2/models.py:1503-1630 constructor wiring)."""
     def need(name):
@@ -319,6 +359,7 @@ def infer_hparams(t):
         hp.flow_n_flows = len(fl)
         hp.flow_wn_layers = sum(1 for k in t if k.startswith("flow.flows.0.enc.in_layers.") and k.endswith(".weight"))
         hp.flow_kernel_size = need("flow.flows.0.enc.in_layers.0.weight").shape[2]
+        hp.flow_type = _infer_flow_type(t, hp.inter_channels)
         hp.dec_initial_channel = need("dec.conv_pre.weight").shape[0]
         ups = sorted({int(k.split(".")[2]) for k in t if k.startswith("dec.ups.") and k.endswith(".weight")})
         hp.n_ups = len(ups)
@@ -361,7 +402,8 @@ def import_onnx(path_or_bytes, config=None):  # noqa: C901
 
     `config`: optional dict with the values that shapes cannot reveal — "upsample_rates",
     "resblock_dilation_sizes", "gen_istft_hop_size", "subbands", "sampling_rate", "hop_length"
-    (keys of training/vits2/configs/*.json "model"/"data")."""
+    (keys of training/vits2/configs/*.json "model"/"data").  "use_transformer_flows" / "transformer_flow_type", when
+    present, must select the flow the tensors show (flow_kind_from_config); a contradiction raises ValueError."""
     g = OnnxGraph(path_or_bytes)
     t = g.tensors()
     hp = infer_hparams(t)
@@ -418,6 +460,13 @@ def import_onnx(path_or_bytes, config=None):  # noqa: C901
             continue  # the synthesis filter's shape (2) or the single band (3) decides; a training config carries "subbands" either way
         if key in config:
             setattr(hp, field, int(config[key]))
+    if "use_transformer_flows" in config or "transformer_flow_type" in config:
+        kind = flow_kind_from_config(config)
+        if FLOW_TYPES.get(kind) != hp.flow_type:
+            have = next(k for k, v in FLOW_TYPES.items() if v == hp.flow_type)
+            raise ValueError(f"config selects the {kind!r} flow (use_transformer_flows {config.get('use_transformer_flows', False)}, "
+                             f"transformer_flow_type {config.get('transformer_flow_type', 'mono_layer_post_residual')!r}) but the graph's "
+                             f"flow tensors are those of {have!r}")
     rate = int(np.prod([hp.up_rates[i] for i in range(hp.n_ups)])) * (hp.istft_hop * hp.subbands if hp.dec_type in (0, 2, 3) else 1)
     if "hop_length" not in config:
         hp.hop_length = rate  # samples per frame are a property of the decoder, not an independent setting

@@ -69,7 +69,8 @@ class HParams(ctypes.Structure):
         ("hop_length", ctypes.c_int32),
         ("bert_dim", ctypes.c_int32),
         ("conv_precision", ctypes.c_int32),  # 0 fp32 (default), 1 split-bf16 decoder ResBlock convs at batch size ("bf16x3")
-        ("reserved", ctypes.c_int32 * 6),
+        ("flow_type", ctypes.c_int32),  # 0 pre_conv2 (default), 1 pre_conv, 2 plain ResidualCouplingLayer (include/vits_mi355.h)
+        ("reserved", ctypes.c_int32 * 5),
     ]
 
     def total_upsample(self):
@@ -202,6 +203,36 @@ def tiny_istft_hparams(n_vocab=20):
     return hp
 
 
+PRE_CONV_HEAD_DIMS = (16, 32, 48, 64, 80, 96)  # head dims the plain (no relative position) attention kernels are built for
+
+
+def pre_conv_hparams(n_vocab=62):
+    """Default-size graph with the `pre_conv` flow (flow_type 1, ResidualCouplingTransformersLayer, models.py:399-483): the
+    upstream VITS2 default.  Its pre-transformer runs at inter_channels/2 = 96 channels, 2 heads of 48."""
+    hp = default_hparams(n_vocab)
+    hp.flow_type = 1
+    return hp
+
+
+def tiny_pre_conv_hparams(n_vocab=20):
+    hp = tiny_hparams(n_vocab)
+    hp.flow_type = 1
+    return hp
+
+
+def plain_flow_hparams(n_vocab=62):
+    """Default-size graph with the VITS-1 coupling layers (flow_type 2, modules.ResidualCouplingLayer, modules.py:298-345)."""
+    hp = default_hparams(n_vocab)
+    hp.flow_type = 2
+    return hp
+
+
+def tiny_plain_flow_hparams(n_vocab=20):
+    hp = tiny_hparams(n_vocab)
+    hp.flow_type = 2
+    return hp
+
+
 def hifigan_v1_vocoder_hparams():
     """Vocoder-only blob (n_vocab = 0): the HiFi-GAN V1 generator bundled with StableTTS
     (training/stabletts/matcha/hifigan/models.py:148-199, config.py v1) that the multistream export wraps as
@@ -243,20 +274,21 @@ def tensor_specs(hp):
         specs.append((name + ".gamma", (c,), "gamma", 0, 1.0))
         specs.append((name + ".beta", (c,), "beta", 0, 1.0))
 
-    def encoder(prefix, n_layers, filt, k):
+    def encoder(prefix, n_layers, filt, k, C=H, rel=True):
         for i in range(n_layers):
             a = f"{prefix}.attn_layers.{i}"
-            specs.append((a + ".emb_rel_k", (1, W, dk), "rel", dk, 1.0))
-            specs.append((a + ".emb_rel_v", (1, W, dk), "rel", dk, 1.0))
+            if rel:
+                specs.append((a + ".emb_rel_k", (1, W, dk), "rel", dk, 1.0))
+                specs.append((a + ".emb_rel_v", (1, W, dk), "rel", dk, 1.0))
             for n in ("conv_q", "conv_k", "conv_v", "conv_o"):
-                conv(f"{a}.{n}", H, H, 1)
+                conv(f"{a}.{n}", C, C, 1)
         for i in range(n_layers):
-            ln(f"{prefix}.norm_layers_1.{i}", H)
+            ln(f"{prefix}.norm_layers_1.{i}", C)
         for i in range(n_layers):
-            conv(f"{prefix}.ffn_layers.{i}.conv_1", filt, H, k)
-            conv(f"{prefix}.ffn_layers.{i}.conv_2", H, filt, k)
+            conv(f"{prefix}.ffn_layers.{i}.conv_1", filt, C, k)
+            conv(f"{prefix}.ffn_layers.{i}.conv_2", C, filt, k)
         for i in range(n_layers):
-            ln(f"{prefix}.norm_layers_2.{i}", H)
+            ln(f"{prefix}.norm_layers_2.{i}", C)
 
     def ddsconv(prefix, c, k, n):
         for i in range(n):
@@ -313,11 +345,16 @@ def tensor_specs(hp):
     if not acoustic:
         return specs
 
-    # flow (models.py:329-396, 630-762); only even indices carry weights
+    # flow (models.py:329-483, 630-762, modules.py:298-345); only even indices carry weights.  flow_type 1 (pre_conv): the
+    # pre-transformer is a 2-layer, 2-head Encoder on the I/2 channels of x0 with FFN kernel 3 and no relative positions
+    # (models.py:417-425); its post_transformer (:436-444) is never run and not part of the export.  flow_type 2: no transformer.
     for f in range(hp.flow_n_flows):
         p = f"flow.flows.{2 * f}"
+        if hp.flow_type == 1:
+            encoder(p + ".pre_transformer", 2, I // 2, 3, C=I // 2, rel=False)
         conv(p + ".pre", H, I // 2, 1)
-        encoder(p + ".pre_transformer", 1, H, hp.flow_kernel_size)
+        if hp.flow_type == 0:
+            encoder(p + ".pre_transformer", 1, H, hp.flow_kernel_size)
         for i in range(hp.flow_wn_layers):
             conv(f"{p}.enc.in_layers.{i}", 2 * H, H, hp.flow_kernel_size)
         for i in range(hp.flow_wn_layers):
@@ -421,6 +458,10 @@ def validate_hparams(hp):
         if hp.dec_type == 3 and hp.subbands != 1:
             raise ValueError(f"single-band iSTFT decoder with subbands {hp.subbands}: must be 1")
         rate *= hp.istft_hop * hp.subbands
+    if hp.flow_type not in (0, 1, 2):
+        raise ValueError(f"flow_type {hp.flow_type}: 0 = pre_conv2, 1 = pre_conv, 2 = plain ResidualCouplingLayer")
+    if hp.flow_type == 1 and hp.n_vocab > 0 and not (hp.inter_channels % 4 == 0 and (hp.inter_channels // 4) in PRE_CONV_HEAD_DIMS):
+        raise ValueError(f"pre_conv flow with inter_channels {hp.inter_channels}: head dim inter_channels/4 must be one of {PRE_CONV_HEAD_DIMS}")
     if hp.conv_precision not in (0, 1):
         raise ValueError(f"conv_precision {hp.conv_precision}: 0 = fp32, 1 = split-bf16 decoder ResBlock convs")
     if rate != hp.hop_length:
