@@ -66,9 +66,12 @@ typedef struct vits_hparams {
   int32_t gin_channels;      /* json:72  256 */
   int32_t n_speakers;        /* json:37  200 */
   int32_t enc_cond_layer;    /* attentions.py:38  2 (speaker add before this layer); -1 = no speaker-conditioned encoder */
-  int32_t dp_filter_channels;/* models.py:1625  256 */
-  int32_t dp_kernel_size;    /* models.py:1625  3 */
-  int32_t dp_n_flows;        /* models.py:1625  4 */
+  int32_t dp_filter_channels;/* models.py:1625  256  (deterministic predictor: conv_1's output width, a multiple of 32 up to 384) */
+  int32_t dp_kernel_size;    /* models.py:1625  3    (deterministic predictor: the kernel of conv_1 and conv_2, odd) */
+  int32_t dp_n_flows;        /* models.py:1625  4.  0 = the deterministic DurationPredictor (use_sdp false, models.py:104-139,
+                                1626-1627): conv_1 / norm_1 / conv_2 / norm_2 / proj, with dp_num_bins and dp_dds_layers 0.  The
+                                reference hard-codes 4 flows for the stochastic predictor, so no stochastic voice has 0: blobs
+                                written before this reading keep their meaning. */
   int32_t dp_num_bins;       /* modules.py:347  10 */
   int32_t dp_dds_layers;     /* models.py:38  3 */
   int32_t flow_n_flows;      /* models.py:636  4 */
@@ -277,7 +280,10 @@ int vits_session_profile_report(vits_session* s, char* buf, size_t cap);
 int vits_stage_text_encoder(vits_model* m, const int64_t* ids, const int64_t* lengths, int32_t B, int32_t T_x,
                             const int64_t* sid, float* x, float* m_p, float* logs_p);
 /* a6: StochasticDurationPredictor.forward(reverse=True) (models.py:56-63,93-101).
- * x [B,hidden,T_x] (encoder output), noise [B,2,T_x] (unit normal), out logw [B,T_x] */
+ * x [B,hidden,T_x] (encoder output), noise [B,2,T_x] (unit normal), out logw [B,T_x].
+ * A voice with the deterministic DurationPredictor (hparams.dp_n_flows == 0, models.py:104-139) computes its logw from x alone:
+ * noise (which may then be NULL) and noise_scale_w are accepted and ignored, as are vits_synth_opts.noise_dp and scales[2] of
+ * vits_synthesize*.  The prior sample's Philox stream does not depend on the predictor: same seed, same eps. */
 int vits_stage_duration(vits_model* m, const float* x, const int64_t* lengths, int32_t B, int32_t T_x,
                         const int64_t* sid, const float* noise, float noise_scale_w, float* logw);
 /* a10+a11: length regulator + prior sample (models.py:1689-1700).

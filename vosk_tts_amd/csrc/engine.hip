@@ -210,7 +210,10 @@ double vits_algorithmic_flops(const vits_model* m, int32_t B, int32_t Tx, int32_
   double enc_layer = 2 * (4 * H * H) + 2 * (2 * H * F * hp->kernel_size) + 2 * 2 * NW * H;
   double tok = hp->n_layers * enc_layer + 2 * H * 2 * I;
   double dds = hp->dp_dds_layers * (2 * D * hp->dp_kernel_size + 2 * D * D);
-  tok += 2 * H * D + 2 * D * D + dds + (hp->dp_n_flows - 1) * (2 * D + dds + 2 * D * (3 * hp->dp_num_bins - 1));
+  if (hp->dp_n_flows == 0)  // deterministic DurationPredictor: conv_1, conv_2, proj
+    tok += 2 * D * H * hp->dp_kernel_size + 2 * D * D * hp->dp_kernel_size + 2 * D;
+  else
+    tok += 2 * H * D + 2 * D * D + dds + (hp->dp_n_flows - 1) * (2 * D + dds + 2 * D * (3 * hp->dp_num_bins - 1));
   double tok_quad = hp->n_layers * 4 * H;
   double K5 = hp->flow_kernel_size;
   double fl = 2 * (I / 2) * H + (2 * (4 * H * H) + 2 * (2 * H * H * K5) + 2 * 2 * NW * H);
@@ -263,7 +266,7 @@ int vits_stage_text_encoder(vits_model* m, const int64_t* ids, const int64_t* le
 int vits_stage_duration(vits_model* m, const float* x, const int64_t* lengths, int32_t B, int32_t Tx, const int64_t* sid,
                         const float* noise, float noise_scale_w, float* logw) {
   if (m && !m->acoustic) return fail(VITS_ERR_UNSUPPORTED, "vocoder-only model: only the decoder stage is available");
-  if (!m || !x || !lengths || !noise || !logw || B <= 0 || Tx <= 0) return fail(VITS_ERR_ARG, "bad argument");
+  if (!m || !x || !lengths || (!noise && !m->dp_det) || !logw || B <= 0 || Tx <= 0) return fail(VITS_ERR_ARG, "bad argument");
   HostStage hs(m);
   TRY(begin_stage(hs, B, Tx, 1, PERSIST_SDP));
   vits_session* s = hs.s;
@@ -271,8 +274,8 @@ int vits_stage_duration(vits_model* m, const float* x, const int64_t* lengths, i
   float* d_x = hs.to_dev(x, (size_t)B * H * Tx);
   int64_t* d_len = hs.to_dev(lengths, B);
   int64_t* d_sid = hs.to_dev(sid, B);
-  float* d_noise = hs.to_dev(noise, (size_t)B * 2 * Tx);
-  if (!d_x || !d_len || !d_noise) return fail(VITS_ERR_NOMEM, "device alloc failed");
+  float* d_noise = m->dp_det ? nullptr : hs.to_dev(noise, (size_t)B * 2 * Tx);  // (the deterministic predictor draws no noise)
+  if (!d_x || !d_len || (!d_noise && !m->dp_det)) return fail(VITS_ERR_NOMEM, "device alloc failed");
   set_lengths(s, d_len, s->len_x, B, Tx);
   run_cond(s, d_sid, B);
   run_duration(s, d_x, d_noise, noise_scale_w, 0, B, Tx);

@@ -78,6 +78,11 @@ struct vits_model {
   ConvW dp_pre, dp_proj;
   DDSW dp_dds;
   std::vector<ConvFlowW> cf;  // index k -> dp.flows.(2k+1), k = 1..n-1 (k = 0 unused)
+  // deterministic DurationPredictor (hparams.dp_n_flows == 0, models.py:104-139): conv_1 / conv_2 on the conv kernels, norm_1, and
+  // norm_2 + proj in dp_det_tail_kernel (proj weight [D] and bias [1] as plain vectors)
+  bool dp_det = false;
+  ConvW dp_c1, dp_c2;
+  float *dp_n1g = nullptr, *dp_n1b = nullptr, *dp_n2g = nullptr, *dp_n2b = nullptr, *dp_pw = nullptr, *dp_pb = nullptr;
   float *ea_m = nullptr, *ea_logs = nullptr;
   float ea_m_h[2] = {0, 0}, ea_logs_h[2] = {0, 0};
   std::vector<CouplingW> flow;
@@ -471,6 +476,17 @@ static int load_model(vits_model* m) {
   if (H > LN_MAXV * LN_CG || D > LN_MAXV * LN_CG) return fail(VITS_ERR_UNSUPPORTED, "LayerNorm width > %d", LN_MAXV * LN_CG);
   if (hp.dp_num_bins > 15 || hp.n_ups > VITS_MAX_UPS || hp.n_resk > 3 || hp.n_resd > VITS_MAX_RESD || hp.n_ups < 1)
     return fail(VITS_ERR_UNSUPPORTED, "hparams out of range");
+  if (hp.dp_n_flows < 0) return fail(VITS_ERR_UNSUPPORTED, "dp_n_flows %d", hp.dp_n_flows);
+  m->dp_det = hp.dp_n_flows == 0;
+  if (m->dp_det) {  // deterministic DurationPredictor: conv_1 [D, H, K], conv_2 [D, D, K] ('same' padding), norm_2 + proj in one tail kernel
+    if (hp.dp_dds_layers || hp.dp_num_bins)
+      return fail(VITS_ERR_UNSUPPORTED, "deterministic duration predictor (dp_n_flows 0) with dp_dds_layers %d / dp_num_bins %d (both must be 0)",
+                  hp.dp_dds_layers, hp.dp_num_bins);
+    if (hp.dp_kernel_size <= 0 || hp.dp_kernel_size % 2 == 0 || hp.dp_kernel_size - 1 > CONV_MAX_HALO)
+      return fail(VITS_ERR_UNSUPPORTED, "deterministic duration predictor kernel %d (must be odd, at most %d)", hp.dp_kernel_size, CONV_MAX_HALO + 1);
+    if (D % CONV_CI_T || D > DPT_CG * DPT_MAXV)
+      return fail(VITS_ERR_UNSUPPORTED, "deterministic duration predictor of %d filter channels (a multiple of %d up to %d)", D, CONV_CI_T, DPT_CG * DPT_MAXV);
+  }
   if (hp.flow_dilation_rate != 1) return fail(VITS_ERR_UNSUPPORTED, "flow dilation_rate != 1");
   if (hp.flow_type < 0 || hp.flow_type > 2)
     return fail(VITS_ERR_UNSUPPORTED, "flow_type %d (0 = pre_conv2, 1 = pre_conv, 2 = plain ResidualCouplingLayer)", hp.flow_type);
@@ -500,30 +516,46 @@ static int load_model(vits_model* m) {
     if (hp.enc_cond_layer >= 0)
       m->cond_enc_off = add_cond(tget(m, 2, H, G, -1, "enc_p.encoder.spk_emb_linear.weight"),
                                  tget(m, 1, H, -1, -1, "enc_p.encoder.spk_emb_linear.bias"), H);
-    m->cond_dp_off = add_cond(tget(m, 3, D, G, 1, "dp.cond.weight"), tget(m, 1, D, -1, -1, "dp.cond.bias"), D);
+    if (m->dp_det)  // DurationPredictor.cond: Conv1d(gin, hidden, 1), added to the predictor's input (models.py:120-121, 127-128)
+      m->cond_dp_off = add_cond(tget(m, 3, H, G, 1, "dp.cond.weight"), tget(m, 1, H, -1, -1, "dp.cond.bias"), H);
+    else
+      m->cond_dp_off = add_cond(tget(m, 3, D, G, 1, "dp.cond.weight"), tget(m, 1, D, -1, -1, "dp.cond.bias"), D);
   }
 
-  // ---- duration predictor (reverse path)
-  m->dp_pre = conv_from(m, "dp.pre", D, H, 1, true);
-  m->dp_proj = conv_from(m, "dp.proj", D, D, 1, true);
-  load_dds(m, m->dp_dds, "dp.convs", D, hp.dp_kernel_size, hp.dp_dds_layers);
-  m->cf.resize(hp.dp_n_flows);
   char nm[200];
-  const int P = 3 * hp.dp_num_bins - 1;
-  for (int k = 1; k < hp.dp_n_flows && !m->missing; ++k) {
-    ConvFlowW& c = m->cf[k];
-    c.pre_w = upload(m, tget(m, 3, D, 1, 1, "dp.flows.%d.pre.weight", 2 * k + 1), D);
-    c.pre_b = upload(m, tget(m, 1, D, -1, -1, "dp.flows.%d.pre.bias", 2 * k + 1), D);
-    snprintf(nm, sizeof nm, "dp.flows.%d.convs", 2 * k + 1);
-    load_dds(m, c.dds, nm, D, hp.dp_kernel_size, hp.dp_dds_layers);
-    snprintf(nm, sizeof nm, "dp.flows.%d.proj", 2 * k + 1);
-    c.proj = conv_from(m, nm, P, D, 1, true);
-  }
-  {
-    const float* em = tget(m, 2, 2, 1, -1, "dp.flows.0.m");
-    const float* el = tget(m, 2, 2, 1, -1, "dp.flows.0.logs");
+  if (m->dp_det) {
+    const int K = hp.dp_kernel_size;
+    m->dp_c1 = conv_from(m, "dp.conv_1", D, H, K, true);
+    m->dp_c2 = conv_from(m, "dp.conv_2", D, D, K, true);
+    m->dp_n1g = upload(m, tget(m, 1, D, -1, -1, "dp.norm_1.gamma"), D);
+    m->dp_n1b = upload(m, tget(m, 1, D, -1, -1, "dp.norm_1.beta"), D);
+    m->dp_n2g = upload(m, tget(m, 1, D, -1, -1, "dp.norm_2.gamma"), D);
+    m->dp_n2b = upload(m, tget(m, 1, D, -1, -1, "dp.norm_2.beta"), D);
+    m->dp_pw = upload(m, tget(m, 3, 1, D, 1, "dp.proj.weight"), D);
+    m->dp_pb = upload(m, tget(m, 1, 1, -1, -1, "dp.proj.bias"), 1);
     if (m->missing) return VITS_ERR_BLOB;
-    m->ea_m = upload(m, em, 2); m->ea_logs = upload(m, el, 2);
+  } else {
+    // ---- duration predictor (reverse path)
+    m->dp_pre = conv_from(m, "dp.pre", D, H, 1, true);
+    m->dp_proj = conv_from(m, "dp.proj", D, D, 1, true);
+    load_dds(m, m->dp_dds, "dp.convs", D, hp.dp_kernel_size, hp.dp_dds_layers);
+    m->cf.resize(hp.dp_n_flows);
+    const int P = 3 * hp.dp_num_bins - 1;
+    for (int k = 1; k < hp.dp_n_flows && !m->missing; ++k) {
+      ConvFlowW& c = m->cf[k];
+      c.pre_w = upload(m, tget(m, 3, D, 1, 1, "dp.flows.%d.pre.weight", 2 * k + 1), D);
+      c.pre_b = upload(m, tget(m, 1, D, -1, -1, "dp.flows.%d.pre.bias", 2 * k + 1), D);
+      snprintf(nm, sizeof nm, "dp.flows.%d.convs", 2 * k + 1);
+      load_dds(m, c.dds, nm, D, hp.dp_kernel_size, hp.dp_dds_layers);
+      snprintf(nm, sizeof nm, "dp.flows.%d.proj", 2 * k + 1);
+      c.proj = conv_from(m, nm, P, D, 1, true);
+    }
+    {
+      const float* em = tget(m, 2, 2, 1, -1, "dp.flows.0.m");
+      const float* el = tget(m, 2, 2, 1, -1, "dp.flows.0.logs");
+      if (m->missing) return VITS_ERR_BLOB;
+      m->ea_m = upload(m, em, 2); m->ea_logs = upload(m, el, 2);
+    }
   }
 
   // ---- flow

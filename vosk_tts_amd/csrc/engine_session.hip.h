@@ -232,7 +232,8 @@ static void plan(vits_session* s, int B, int Tx, int Ty) {
   s->lnst = bump<float>(s, (size_t)B * 16 * Tm * 2);
   s->ffh = bump<float>(s, B * (Fm > He ? Fm : He) * Tm);
   s->stats = bump<float>(s, B * 2 * I * Tx);
-  s->dh = bump<float>(s, B * D * Tx); s->dy = bump<float>(s, B * D * Tx); s->dy2 = bump<float>(s, B * D * Tx);
+  // (dh: the deterministic predictor's x + cond(g) copy has H rows)
+  s->dh = bump<float>(s, B * (s->m->dp_det && H > D ? H : D) * Tx); s->dy = bump<float>(s, B * D * Tx); s->dy2 = bump<float>(s, B * D * Tx);
   s->dc = bump<float>(s, B * D * Tx); s->dfh = bump<float>(s, B * D * Tx);
   s->dq1 = bump<float>(s, B * D * Tx); s->dq2 = bump<float>(s, B * D * Tx);
   s->dz = bump<float>(s, (size_t)B * 2 * Tx); s->dpr = bump<float>(s, (size_t)B * 32 * Tx); s->logw = bump<float>(s, (size_t)B * Tx);

@@ -49,7 +49,7 @@ static void run_encoder(vits_session* s, const EncoderW& E, float* x, const int*
     const EncLayerW& L = E.layers[i];
     const bool cond_here = i == cond_layer && cond_off >= 0;
     if (cond_here && !prev.raw)
-      hipLaunchKernelGGL(add_vec_mask_kernel, dim3(cdiv(T, 64), H, B), dim3(64), 0, s->stream, x, s->condv, m->cond_rows,
+      hipLaunchKernelGGL(add_vec_mask_kernel, dim3(cdiv(T, 64), H, B), dim3(64), 0, s->stream, x, x, s->condv, m->cond_rows,
                          cond_off, len, H, T);
     ConvParams P = conv_params(L.qkv, prev.raw ? prev.raw : x, s->qkv, B, T, 1, 0);
     if (prev.raw) {
@@ -272,13 +272,55 @@ static void run_dds_proj(vits_session* s, const DDSW& W, float* h, const ConvW& 
   launch_conv(s, P, EPI_STORE, proj_name);
 }
 
+// ---- a6, deterministic DurationPredictor.forward (models.py:123-139; hparams.dp_n_flows == 0) -> s->logw.  x is not modified (stage-level
+// callers pass their own).  Launches: [x + cond(g) into a scratch copy], conv_1 + ReLU, [norm_1 where it cannot be folded into conv_2's
+// staging], conv_2 + ReLU, then norm_2 + proj in dp_det_tail_kernel.
+static void run_duration_det(vits_session* s, const float* x, int B, int Tx) {
+  vits_model* m = s->m;
+  const vits_hparams& hp = m->hp;
+  const int H = hp.hidden_channels, D = hp.dp_filter_channels, K = hp.dp_kernel_size;
+  const float* xin = x;
+  if (m->use_g) {  // x = x + cond(g), masked (conv_1 reads x * mask either way)
+    ProfScope ps(s, "dp.cond_add", (double)B * H * Tx, "add_vec_mask_kernel");
+    hipLaunchKernelGGL(add_vec_mask_kernel, dim3(cdiv(Tx, 64), H, B), dim3(64), 0, s->stream, s->dh, x, s->condv, m->cond_rows,
+                       m->cond_dp_off, s->len_x, H, Tx);
+    xin = s->dh;
+  }
+  // x = norm_1(relu(conv_1(x * mask)))
+  ConvParams P = conv_params(m->dp_c1, xin, s->dy, B, Tx, 1, (K - 1) / 2);
+  P.in_mask = 1; P.len = s->len_x; P.relu = 1;
+  mark_masked(s, P, s->len_x);
+  launch_conv(s, P, EPI_STORE, "dp.conv_1");
+  // h = relu(conv_2(x * mask)): norm_1 on load when the small-tile kernel takes the launch (the text encoder FFN's fold)
+  static const float dummy = 0.f;
+  P = conv_params(m->dp_c2, s->dy, s->dc, B, Tx, 1, (K - 1) / 2);
+  P.in_mask = 1; P.len = s->len_x; P.relu = 1;
+  P.ln_g = &dummy;
+  if (conv_takes_c16(P, EPI_STORE)) {
+    P.ln_g = m->dp_n1g; P.ln_b = m->dp_n1b;
+  } else {
+    P.ln_g = nullptr;
+    launch_ln(s, s->dy, nullptr, nullptr, s->dy2, m->dp_n1g, m->dp_n1b, s->len_x, B, D, Tx, 0, 0);
+    P.g[0].x = s->dy2;
+  }
+  mark_masked(s, P, s->len_x);
+  launch_conv(s, P, EPI_STORE, "dp.conv_2");
+  // logw = proj(norm_2(h) * mask) * mask
+  ProfScope ps(s, "dp.tail", (double)B * Tx * 8.0 * D, "dp_det_tail_kernel");
+  hipLaunchKernelGGL(dp_det_tail_kernel, dim3(cdiv(Tx, DPT_COLS), B), dim3(256), 0, s->stream, s->dc, m->dp_n2g, m->dp_n2b, m->dp_pw,
+                     m->dp_pb, s->len_x, s->logw, D, Tx);
+  s->ea_pending = false;
+}
+
 // ---- a6: StochasticDurationPredictor.forward(reverse=True) (models.py:56-63,93-101) -> s->logw
 // defer_ea: the caller runs run_durations next on this session; the final ElementwiseAffine (logw from z) is then folded into
 // durations_kernel instead of being its own launch (stage-level callers need logw itself and keep the launch)
+// A deterministic-predictor voice ignores d_noise, nsw and seed (the predictor draws no noise) and writes logw itself.
 static void run_duration(vits_session* s, const float* x, const float* d_noise, float nsw, uint64_t seed, int B, int Tx, bool defer_ea = false) {
   vits_model* m = s->m;
   const vits_hparams& hp = m->hp;
   const int D = hp.dp_filter_channels;
+  if (m->dp_det) return run_duration_det(s, x, B, Tx);
   if ((persist_mask() & PERSIST_SDP) && s->ps_sdp.ok && B == 1 && Tx == s->Tx) {  // one persistent kernel instead of ~21 launches (persist.hip.h)
     // the program reads the text-encoder output from the session's own buffer (stage-level callers bring theirs)
     if (x != s->x) hipMemcpyAsync(s->x, x, sizeof(float) * (size_t)hp.hidden_channels * Tx, hipMemcpyDeviceToDevice, s->stream);

@@ -85,12 +85,77 @@ __global__ void cond_gemv_kernel(const float* W, const float* bias, const float*
   if (lane == 0) out[(long long)b * rows + row] = a + bias[row];
 }
 
-// x = (x + v[b][c]) * mask   (attentions.py:55-56)
-__global__ void add_vec_mask_kernel(float* x, const float* v, int v_stride, int v_off, const int* len, int C, int T) {
+// y = (x + v[b][c]) * mask   (attentions.py:55-56; DurationPredictor, models.py:127-128).  y == x: in place
+__global__ void add_vec_mask_kernel(float* y, const float* x, const float* v, int v_stride, int v_off, const int* len, int C, int T) {
   const int t = blockIdx.x * blockDim.x + threadIdx.x, c = blockIdx.y, b = blockIdx.z;
   if (t >= T) return;
   const long long o = ((long long)b * C + c) * T + t;
-  x[o] = t < len[b] ? x[o] + v[(long long)b * v_stride + v_off + c] : 0.f;
+  y[o] = t < len[b] ? x[o] + v[(long long)b * v_stride + v_off + c] : 0.f;
+}
+
+// ----------------------------------------------------------------------------- deterministic duration predictor tail
+// DurationPredictor (models.py:133-139) after conv_2 + ReLU:  logw = proj(LN_2(h) * mask) * mask, proj = Conv1d(D, 1, 1).
+// A per-column LayerNorm and a D-long dot product: on the conv kernels it would fill one row of every 16- or 32-row matrix tile
+// and need a LayerNorm pass of its own.  Block = 256 threads = 32 columns x 8 channel groups: lanes run along t (coalesced rows),
+// every thread keeps its D/8 channel values in registers; the groups combine through LDS.  fp32, two-pass like F.layer_norm
+// (mean, then the centred squares), eps 1e-5.  Columns at or beyond len[b] are written as 0 and their h is never read (a
+// tile-skipping producer leaves stale data there).
+#define DPT_COLS 32
+#define DPT_CG 8
+#define DPT_MAXV 48  // D <= 384
+__global__ __launch_bounds__(256) void dp_det_tail_kernel(const float* __restrict__ h, const float* __restrict__ gamma,
+                                                          const float* __restrict__ beta, const float* __restrict__ pw,
+                                                          const float* __restrict__ pb, const int* __restrict__ len,
+                                                          float* __restrict__ logw, int D, int T) {
+  __shared__ float red[DPT_CG][DPT_COLS];
+  const int tx = threadIdx.x % DPT_COLS, cg = threadIdx.x / DPT_COLS, b = blockIdx.y;
+  const int t = blockIdx.x * DPT_COLS + tx;
+  const bool ok = t < T && t < len[b];
+  const int nv = D / DPT_CG;
+  const float* hb = h + (long long)b * D * T + t;
+  float v[DPT_MAXV];
+  float acc = 0.f;
+#pragma unroll
+  for (int i = 0; i < DPT_MAXV; ++i) {
+    v[i] = 0.f;
+    if (i < nv && ok) v[i] = hb[(long long)(cg + DPT_CG * i) * T];
+    acc += v[i];
+  }
+  red[cg][tx] = acc;
+  __syncthreads();
+  float sum = 0.f;
+#pragma unroll
+  for (int k = 0; k < DPT_CG; ++k) sum += red[k][tx];
+  const float mean = sum / (float)D;
+  __syncthreads();
+  acc = 0.f;
+#pragma unroll
+  for (int i = 0; i < DPT_MAXV; ++i) {
+    const float d = v[i] - mean;
+    acc += i < nv ? d * d : 0.f;
+  }
+  red[cg][tx] = acc;
+  __syncthreads();
+  float q = 0.f;
+#pragma unroll
+  for (int k = 0; k < DPT_CG; ++k) q += red[k][tx];
+  const float rstd = 1.0f / sqrtf(q / (float)D + 1e-5f);
+  __syncthreads();
+  acc = 0.f;
+#pragma unroll
+  for (int i = 0; i < DPT_MAXV; ++i) {
+    if (i < nv) {
+      const int c = cg + DPT_CG * i;
+      acc += ((v[i] - mean) * rstd * gamma[c] + beta[c]) * pw[c];
+    }
+  }
+  red[cg][tx] = acc;
+  __syncthreads();
+  if (cg != 0 || t >= T) return;
+  float y = 0.f;
+#pragma unroll
+  for (int k = 0; k < DPT_CG; ++k) y += red[k][tx];
+  logw[(long long)b * T + t] = ok ? y + pb[0] : 0.f;
 }
 
 // ----------------------------------------------------------------------------- LayerNorm over C

@@ -44,6 +44,7 @@ static bool persist_common_ok(const vits_model* m, int B, int T) {
 // ---- stochastic duration predictor
 static bool persist_sdp_eligible(const vits_model* m, int B, int Tx) {
   const vits_hparams& hp = m->hp;
+  if (m->dp_det) return false;  // deterministic DurationPredictor: the launch path (run_duration_det) only
   if (!persist_common_ok(m, B, Tx)) return false;
   const int D = hp.dp_filter_channels, H = hp.hidden_channels;
   if (D % 32 || D > PS_MAXC || H % 16 || H > PS_MAXC || hp.dp_kernel_size != 3) return false;

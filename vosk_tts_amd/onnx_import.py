@@ -318,6 +318,30 @@ def _infer_flow_type(t, inter_channels):
                               "neither pre_conv2 nor pre_conv")
 
 
+# The deterministic DurationPredictor (use_sdp false, models.py:104-139) is told apart from the stochastic one by its conv_1 / norm_1 /
+# conv_2 / norm_2 tensors; its proj and cond reuse stochastic-predictor names with other shapes, so the family is decided first.
+DET_DP_TENSORS = ("dp.conv_1.weight", "dp.conv_1.bias", "dp.norm_1.gamma", "dp.norm_1.beta", "dp.conv_2.weight", "dp.conv_2.bias",
+                  "dp.norm_2.gamma", "dp.norm_2.beta", "dp.proj.weight", "dp.proj.bias")
+_SDP_PREFIXES = ("dp.flows.", "dp.pre.", "dp.convs.")
+
+
+def _deterministic_dp(t):
+    """True for a complete deterministic duration predictor, False for no dp.conv_* / dp.norm_* at all (the stochastic predictor, or
+    a graph without one: its missing dp.pre.weight is reported later).  A mixed or incomplete set is refused by name."""
+    det = sorted(k for k in t if k.startswith(("dp.conv_1.", "dp.norm_1.", "dp.conv_2.", "dp.norm_2.")))
+    if not det:
+        return False
+    sdp = sorted(k for k in t if k.startswith(_SDP_PREFIXES))
+    if sdp:
+        raise NotImplementedError(f"duration predictor tensors of both families: deterministic DurationPredictor ({det[0]}, ...) and "
+                                  f"StochasticDurationPredictor ({sdp[0]}, ...); a graph has one or the other")
+    missing = [k for k in DET_DP_TENSORS if k not in t]
+    if missing:
+        raise NotImplementedError(f"deterministic DurationPredictor (use_sdp false, models.py:104-139) is incomplete: initializer "
+                                  f"{missing[0]!r} not found")
+    return True
+
+
 def infer_hparams(t):
     """Hyper-parameters from tensor shapes (training/vits2/models.py:1503-1630 constructor wiring)."""
     def need(name):
@@ -329,9 +353,7 @@ def infer_hparams(t):
     if any(k.startswith("dec.resblocks.") and ".convs." in k for k in t):
         raise NotImplementedError("decoder with ResBlock2 (resblock '2', modules.py:232: dec.resblocks.*.convs.*) is not supported; "
                                   "only ResBlock1 decoders are")
-    if any(k.startswith(("dp.conv_1.", "dp.norm_1.")) for k in t) and not any(k.startswith("dp.flows.") for k in t):
-        raise NotImplementedError("deterministic DurationPredictor (use_sdp false, models.py:104-139: dp.conv_1 / dp.norm_1 without "
-                                  "dp.flows) is not supported; only the stochastic duration predictor is")
+    deterministic = _deterministic_dp(t)
     try:
         emb = need("enc_p.emb.weight")
         hp = W.default_hparams(n_vocab=emb.shape[0])
@@ -349,12 +371,17 @@ def infer_hparams(t):
             hp.n_speakers, hp.gin_channels = 0, 0
         # the Linear's weight is folded into an anonymous transposed MatMul constant by the exporter; its bias keeps the name
         hp.enc_cond_layer = 2 if ("enc_p.encoder.spk_emb_linear.bias" in t or "enc_p.encoder.spk_emb_linear.weight" in t) else -1
-        hp.dp_filter_channels = need("dp.pre.weight").shape[0]
-        hp.dp_kernel_size = need("dp.convs.convs_sep.0.weight").shape[2]
-        hp.dp_dds_layers = sum(1 for k in t if k.startswith("dp.convs.convs_sep.") and k.endswith(".weight"))
-        cf = sorted({int(k.split(".")[2]) for k in t if k.startswith("dp.flows.") and k.endswith(".proj.weight")})
-        hp.dp_n_flows = (max(cf) + 1) // 2 if cf else 4
-        hp.dp_num_bins = (need(f"dp.flows.{max(cf)}.proj.weight").shape[0] + 1) // 3
+        if deterministic:  # dp_n_flows 0 (weights.HParams): conv_1 [D, H, K] gives the filter channels and the kernel
+            c1 = t["dp.conv_1.weight"]
+            hp.dp_filter_channels, hp.dp_kernel_size = int(c1.shape[0]), int(c1.shape[2])
+            hp.dp_n_flows = hp.dp_num_bins = hp.dp_dds_layers = 0
+        else:
+            hp.dp_filter_channels = need("dp.pre.weight").shape[0]
+            hp.dp_kernel_size = need("dp.convs.convs_sep.0.weight").shape[2]
+            hp.dp_dds_layers = sum(1 for k in t if k.startswith("dp.convs.convs_sep.") and k.endswith(".weight"))
+            cf = sorted({int(k.split(".")[2]) for k in t if k.startswith("dp.flows.") and k.endswith(".proj.weight")})
+            hp.dp_n_flows = (max(cf) + 1) // 2 if cf else 4
+            hp.dp_num_bins = (need(f"dp.flows.{max(cf)}.proj.weight").shape[0] + 1) // 3
         fl = sorted({int(k.split(".")[2]) for k in t if k.startswith("flow.flows.") and k.endswith(".pre.weight")})
         hp.flow_n_flows = len(fl)
         hp.flow_wn_layers = sum(1 for k in t if k.startswith("flow.flows.0.enc.in_layers.") and k.endswith(".weight"))
@@ -403,7 +430,8 @@ def import_onnx(path_or_bytes, config=None):  # noqa: C901
     `config`: optional dict with the values that shapes cannot reveal — "upsample_rates",
     "resblock_dilation_sizes", "gen_istft_hop_size", "subbands", "sampling_rate", "hop_length"
     (keys of training/vits2/configs/*.json "model"/"data").  "use_transformer_flows" / "transformer_flow_type", when
-    present, must select the flow the tensors show (flow_kind_from_config); a contradiction raises ValueError."""
+    present, must select the flow the tensors show (flow_kind_from_config), and "use_sdp" the duration predictor; a contradiction
+    raises ValueError."""
     g = OnnxGraph(path_or_bytes)
     t = g.tensors()
     hp = infer_hparams(t)
@@ -467,6 +495,10 @@ def import_onnx(path_or_bytes, config=None):  # noqa: C901
             raise ValueError(f"config selects the {kind!r} flow (use_transformer_flows {config.get('use_transformer_flows', False)}, "
                              f"transformer_flow_type {config.get('transformer_flow_type', 'mono_layer_post_residual')!r}) but the graph's "
                              f"flow tensors are those of {have!r}")
+    if "use_sdp" in config and bool(config["use_sdp"]) != (hp.dp_n_flows != 0):
+        have = "stochastic" if hp.dp_n_flows else "deterministic"
+        raise ValueError(f"config selects the {'stochastic' if config['use_sdp'] else 'deterministic'} duration predictor (use_sdp "
+                         f"{config['use_sdp']}) but the graph's dp tensors are those of the {have} one")
     rate = int(np.prod([hp.up_rates[i] for i in range(hp.n_ups)])) * (hp.istft_hop * hp.subbands if hp.dec_type in (0, 2, 3) else 1)
     if "hop_length" not in config:
         hp.hop_length = rate  # samples per frame are a property of the decoder, not an independent setting

@@ -42,7 +42,7 @@ class HParams(ctypes.Structure):
         ("enc_cond_layer", ctypes.c_int32),
         ("dp_filter_channels", ctypes.c_int32),
         ("dp_kernel_size", ctypes.c_int32),
-        ("dp_n_flows", ctypes.c_int32),
+        ("dp_n_flows", ctypes.c_int32),  # 0: the deterministic DurationPredictor (use_sdp false, include/vits_mi355.h)
         ("dp_num_bins", ctypes.c_int32),
         ("dp_dds_layers", ctypes.c_int32),
         ("flow_n_flows", ctypes.c_int32),
@@ -233,6 +233,26 @@ def tiny_plain_flow_hparams(n_vocab=20):
     return hp
 
 
+def deterministic_dp_hparams(n_vocab=62):
+    """Default-size graph with the deterministic `DurationPredictor` (use_sdp false, models.py:104-139, 1624-1627):
+    conv_1 / norm_1 / conv_2 / norm_2 / proj at dp_filter_channels 256, kernel 3.  dp_n_flows == 0 selects it: the reference
+    hard-codes 4 flows for the stochastic predictor (models.py:1625), so a stochastic voice never has 0."""
+    hp = default_hparams(n_vocab)
+    hp.dp_n_flows = 0
+    hp.dp_num_bins = 0
+    hp.dp_dds_layers = 0
+    return hp
+
+
+def tiny_deterministic_dp_hparams(n_vocab=20):
+    """The tiny graph (with speaker conditioning: dp.cond) with the deterministic duration predictor."""
+    hp = tiny_hparams(n_vocab)
+    hp.dp_n_flows = 0
+    hp.dp_num_bins = 0
+    hp.dp_dds_layers = 0
+    return hp
+
+
 def hifigan_v1_vocoder_hparams():
     """Vocoder-only blob (n_vocab = 0): the HiFi-GAN V1 generator bundled with StableTTS
     (training/stabletts/matcha/hifigan/models.py:148-199, config.py v1) that the multistream export wraps as
@@ -364,9 +384,22 @@ def tensor_specs(hp):
             conv(p + ".enc.cond_layer", 2 * H * hp.flow_wn_layers, G, 1)
         conv(p + ".post", I // 2, H, 1, gain=0.5)
 
+    D = hp.dp_filter_channels
+    if hp.dp_n_flows == 0:
+        # deterministic DurationPredictor (models.py:104-139): dp.proj and dp.cond share their names with stochastic-predictor tensors
+        # of other shapes.  proj's gain keeps the synthetic logw spread small; its bias is set in synthetic_from_specs.
+        conv("dp.conv_1", D, H, hp.dp_kernel_size)
+        ln("dp.norm_1", D)
+        conv("dp.conv_2", D, D, hp.dp_kernel_size)
+        ln("dp.norm_2", D)
+        conv("dp.proj", 1, D, 1, gain=0.3)
+        if G > 0:
+            conv("dp.cond", H, G, 1)
+        if hp.n_speakers > 1:
+            specs.append(("emb_g.weight", (hp.n_speakers, G), "emb1", G, 1.0))
+        return specs
     # stochastic duration predictor, reverse path only (models.py:23-63,93-101):
     # flows[0] ElementwiseAffine, flows[2k+1] ConvFlow for k>=1 (flows[1] is skipped, :94-95)
-    D = hp.dp_filter_channels
     specs.append(("dp.flows.0.m", (2, 1), "small", 0, 1.0))
     specs.append(("dp.flows.0.logs", (2, 1), "small", 0, 1.0))
     for k in range(1, hp.dp_n_flows):
@@ -412,6 +445,8 @@ def synthetic_from_specs(specs, seed=1234, heavy_sigma=0.0):
                 t = t * g.reshape((-1,) + (1,) * (len(shape) - 1))
         elif kind == "b":
             t = u * 0.05
+            if name == "dp.proj.bias" and shape == (1,):
+                t = t + 0.9  # deterministic predictor: logw about 0.9 - 1.4 +- 0.3 on encoder outputs, i.e. 2 - 6 frames per token
         elif kind == "gamma":
             t = 1.0 + 0.1 * u
         elif kind == "beta":
@@ -462,6 +497,15 @@ def validate_hparams(hp):
         raise ValueError(f"flow_type {hp.flow_type}: 0 = pre_conv2, 1 = pre_conv, 2 = plain ResidualCouplingLayer")
     if hp.flow_type == 1 and hp.n_vocab > 0 and not (hp.inter_channels % 4 == 0 and (hp.inter_channels // 4) in PRE_CONV_HEAD_DIMS):
         raise ValueError(f"pre_conv flow with inter_channels {hp.inter_channels}: head dim inter_channels/4 must be one of {PRE_CONV_HEAD_DIMS}")
+    if hp.n_vocab > 0 and hp.dp_n_flows == 0:  # deterministic duration predictor (use_sdp false)
+        if hp.dp_dds_layers or hp.dp_num_bins:
+            raise ValueError(f"deterministic duration predictor (dp_n_flows 0) with dp_dds_layers {hp.dp_dds_layers} / dp_num_bins "
+                             f"{hp.dp_num_bins}: both must be 0")
+        if hp.dp_kernel_size <= 0 or hp.dp_kernel_size % 2 == 0:
+            raise ValueError(f"deterministic duration predictor kernel {hp.dp_kernel_size}: must be odd")
+        if hp.dp_filter_channels <= 0 or hp.dp_filter_channels % 32 or hp.dp_filter_channels > 384:
+            raise ValueError(f"deterministic duration predictor of {hp.dp_filter_channels} filter channels: the conv kernels take a "
+                             "multiple of 32 up to 384")
     if hp.conv_precision not in (0, 1):
         raise ValueError(f"conv_precision {hp.conv_precision}: 0 = fp32, 1 = split-bf16 decoder ResBlock convs")
     if rate != hp.hop_length:
