@@ -77,6 +77,14 @@ void vits_debug_poison_workspace(int on);
  * grid size, or the one vits_debug_attention_impl forces (2: 32-query tiles, 3: 16-query tiles). */
 int vits_debug_plain_attention(int device, const float* qkv, const int64_t* lengths, int32_t B, int32_t C, int32_t T,
                                int32_t n_heads, float* out);
+/* Test hook: the relative-position attention (attentions.py:165-260: relpos_attention_kernel, relpos_attention_mfma_kernel,
+ * relpos_attention16_kernel) on caller host buffers.  qkv float [B, 3C, T] as the fused q/k/v conv writes it, out float [B, C, T].
+ * ek / ev: the shared relative-position tables [2 window + 1][C / n_heads] (heads_share=True), or both null for plain scaled-dot-product
+ * attention (the StableTTS / BERT form); exactly one null is VITS_ERR_ARG.  C / n_heads must be 32, 64 or 96 and, with tables, window
+ * in [0, 4] (else VITS_ERR_UNSUPPORTED).  Keys >= lengths[b] carry no weight; query columns >= lengths[b] are written as 0.  The
+ * kernel is the engine's choice, or the one vits_debug_attention_impl forces (1: scalar, 2: 32-query tiles, 3: 16-query tiles). */
+int vits_debug_relpos_attention(int device, const float* qkv, const float* ek, const float* ev, const int64_t* lengths, int32_t B,
+                                int32_t C, int32_t T, int32_t n_heads, int32_t window, float* out);
 
 /* Shader clock under load (round 6): launches `n` one-wave workgroups on a stream of the library's own that sit on the device for
  * `duration_us` and compare the shader-clock counter (s_memtime) with the constant 100 MHz wall clock (s_memrealtime); ghz[i] = the clock

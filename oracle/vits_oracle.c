@@ -191,9 +191,9 @@ static void mul_mask(float* x, int B, int C, int T, const int64_t* len) {
 /* MultiHeadAttention.forward + attention (attentions.py:155-213) with the
  * relative-position terms (attentions.py:216-260) in band form (SURVEY.md A1,
  * verified bit-exact against the pad/reshape skew).  x [B,H,T] -> y [B,H,T]. */
-static void mha(vits_model* m, const char* pfx, const float* x, int B, int H, int T, const int64_t* len, float* y) {
+static void mha(vits_model* m, const char* pfx, const float* x, int B, int H, int nh, int T, const int64_t* len, float* y) {
   const vits_hparams* hp = &m->hp;
-  int nh = hp->n_heads, dk = H / nh, W = hp->window_size, NW = 2 * W + 1;
+  int dk = H / nh, W = hp->window_size, NW = 2 * W + 1;
   const float* wq = tget(m, 3, H, H, 1, "%s.conv_q.weight", pfx);
   const float* bq = tget(m, 1, H, -1, -1, "%s.conv_q.bias", pfx);
   const float* wk = tget(m, 3, H, H, 1, "%s.conv_k.weight", pfx);
@@ -274,9 +274,9 @@ static void ffn(vits_model* m, const char* pfx, const float* x, int B, int H, in
   free(xm); free(h);
 }
 
-/* attentions.Encoder.forward (attentions.py:48-65).  x in/out [B,H,T].
+/* attentions.Encoder.forward (attentions.py:48-65).  x in/out [B,H,T], nh heads.
  * g [B,G] or NULL (speaker add before layer cond_layer, attentions.py:52-56). */
-static void encoder(vits_model* m, const char* pfx, float* x, int B, int H, int F, int K, int n_layers, int T,
+static void encoder(vits_model* m, const char* pfx, float* x, int B, int H, int nh, int F, int K, int n_layers, int T,
                     const int64_t* len, const float* g, int G, int cond_layer) {
   size_t n = (size_t)B * H * T;
   float* y = falloc(n);
@@ -297,7 +297,7 @@ static void encoder(vits_model* m, const char* pfx, float* x, int B, int H, int 
       mul_mask(x, B, H, T, len);
     }
     snprintf(sub, sizeof sub, "%s.attn_layers.%d", pfx, i);
-    mha(m, sub, x, B, H, T, len, y);
+    mha(m, sub, x, B, H, nh, T, len, y);
     for (size_t e = 0; e < n; ++e) x[e] += y[e];
     layer_norm_c(x, B, H, T, tget(m, 1, H, -1, -1, "%s.norm_layers_1.%d.gamma", pfx, i),
                  tget(m, 1, H, -1, -1, "%s.norm_layers_1.%d.beta", pfx, i));
@@ -372,7 +372,7 @@ static int text_encoder_impl(vits_model* m, const int64_t* ids, const int64_t* l
   int rc = speaker_g(m, sid, B, g);
   if (rc) { free(g); return rc; }
   int use_g = hp->enc_cond_layer >= 0 && G > 0 && hp->n_speakers > 1;
-  encoder(m, "enc_p.encoder", x, B, H, hp->filter_channels, hp->kernel_size, hp->n_layers, T, lengths,
+  encoder(m, "enc_p.encoder", x, B, H, hp->n_heads, hp->filter_channels, hp->kernel_size, hp->n_layers, T, lengths,
           use_g ? g : NULL, G, hp->enc_cond_layer);
   free(g);
   const float* pw = tget(m, 3, 2 * I, H, 1, "enc_p.proj.weight");
@@ -716,7 +716,8 @@ static void coupling_reverse(vits_model* m, const char* pfx, float* x, int B, in
   memcpy(e, h, sizeof(float) * n);
   char sub[200];
   snprintf(sub, sizeof sub, "%s.pre_transformer", pfx);
-  encoder(m, sub, e, B, H, H, hp->flow_kernel_size, 1, T, len, NULL, 0, -1);
+  /* models.py:352-360: 2 heads whatever n_heads is (only the text encoder takes it, models.py:307-314) */
+  encoder(m, sub, e, B, H, 2, H, hp->flow_kernel_size, 1, T, len, NULL, 0, -1);
   for (size_t i = 0; i < n; ++i) h[i] += e[i]; /* models.py:377 */
   snprintf(sub, sizeof sub, "%s.enc", pfx);
   wn(m, sub, h, B, H, T, len, (G > 0 && hp->n_speakers > 1) ? g : NULL, G, e);

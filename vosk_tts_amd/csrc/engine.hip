@@ -669,6 +669,47 @@ int vits_debug_plain_attention(int device, const float* qkv, const int64_t* leng
   return VITS_OK;
 }
 
+// The relative-position attention (attentions.py:165-260; relpos_attention*_kernel) on caller buffers: qkv [B, 3C, T], shared tables
+// ek / ev [2W + 1][C / n_heads] or both null (plain scaled-dot-product attention, the StableTTS / BERT form), out [B, C, T].  Kernel as
+// the engine picks it, or forced by vits_debug_attention_impl (1: scalar, 2: 32-query, 3: 16-query).
+int vits_debug_relpos_attention(int device, const float* qkv, const float* ek, const float* ev, const int64_t* lengths, int32_t B,
+                                int32_t C, int32_t T, int32_t n_heads, int32_t window, float* out) {
+  if (!qkv || !lengths || !out || B <= 0 || B > 65535 || T <= 0 || C <= 0 || n_heads <= 0 || n_heads > 64 || C % n_heads || (!ek != !ev))
+    return fail(VITS_ERR_ARG, "relpos attention: bad arguments");
+  const int dk = C / n_heads;
+  if (dk != 32 && dk != 64 && dk != 96) return fail(VITS_ERR_UNSUPPORTED, "relpos attention: head dim %d not built", dk);
+  if (ek && (window < 0 || window > 4)) return fail(VITS_ERR_UNSUPPORTED, "relpos attention: window %d not in [0, 4]", window);
+  const int W = ek ? window : 4;  // (the engine's own argument for table-less calls, stts.hip.h)
+  std::vector<int> len32(B);
+  for (int b = 0; b < B; ++b) {
+    if (lengths[b] < 0 || lengths[b] > T) return fail(VITS_ERR_ARG, "relpos attention: length out of range");
+    len32[b] = (int)lengths[b];
+  }
+  HIP_TRY(hipSetDevice(device));
+  const size_t nq = (size_t)B * 3 * C * T, no = (size_t)B * C * T, ne = ek ? (size_t)(2 * W + 1) * dk : 0;
+  float *d_qkv = nullptr, *d_out = nullptr, *d_ek = nullptr, *d_ev = nullptr;
+  int* d_len = nullptr;
+  hipError_t e = hipMalloc((void**)&d_qkv, nq * sizeof(float));
+  if (e == hipSuccess) e = hipMalloc((void**)&d_out, no * sizeof(float));
+  if (e == hipSuccess) e = hipMalloc((void**)&d_len, B * sizeof(int));
+  if (e == hipSuccess && ne) e = hipMalloc((void**)&d_ek, ne * sizeof(float));
+  if (e == hipSuccess && ne) e = hipMalloc((void**)&d_ev, ne * sizeof(float));
+  if (e == hipSuccess) e = hipMemcpy(d_qkv, qkv, nq * sizeof(float), hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = hipMemcpy(d_len, len32.data(), B * sizeof(int), hipMemcpyHostToDevice);
+  if (e == hipSuccess && ne) e = hipMemcpy(d_ek, ek, ne * sizeof(float), hipMemcpyHostToDevice);
+  if (e == hipSuccess && ne) e = hipMemcpy(d_ev, ev, ne * sizeof(float), hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = hipMemset(d_out, 0xff, no * sizeof(float));  // NaN: an output the kernel does not write shows
+  if (e == hipSuccess) {
+    launch_relpos_attention_on(nullptr, d_qkv, d_ek, d_ev, d_len, d_out, B, C, T, n_heads, W);
+    e = hipGetLastError();
+  }
+  if (e == hipSuccess) e = hipDeviceSynchronize();
+  if (e == hipSuccess) e = hipMemcpy(out, d_out, no * sizeof(float), hipMemcpyDeviceToHost);
+  hipFree(d_qkv); hipFree(d_out); hipFree(d_len); hipFree(d_ek); hipFree(d_ev);
+  if (e != hipSuccess) return fail(VITS_ERR_DEVICE, "relpos attention: %s", hipGetErrorString(e));
+  return VITS_OK;
+}
+
 int vits_session_sync(vits_session* s) {
   if (!s) return fail(VITS_ERR_ARG, "null session");
   return check_err(s);

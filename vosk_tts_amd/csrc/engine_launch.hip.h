@@ -567,19 +567,24 @@ static void launch_ln(vits_session* s, const float* a, const float* b, const flo
   launch_layernorm(s->stream, P, B);
 }
 
-// ek / ev: relative-position tables [2W+1][dk] or null (plain scaled-dot-product attention: StableTTS DiT blocks, BERT)
-static void launch_attention_raw(vits_session* s, const float* qkv, const float* ek, const float* ev, const int* len, float* out, int B,
-                                 int H, int T, int nh, int W) {
+// ek / ev: relative-position tables [2W+1][dk] or null (plain scaled-dot-product attention: StableTTS DiT blocks, BERT).
+// 16-query tiles (more, smaller workgroups) while the 32-query MFMA kernel's grid would not fill the chip: measured round 4
+// (profiles/r4_c16_threshold.txt) single utterances of 200 - 600 tokens (T_y 600 - 1800) -15..-35 % attention time against the old rule
+// (T <= 512), the 32-item batch c3 -6 % (its 200-token text side now runs the MFMA kernel).
+static bool relpos_attention_use16(int B, int T, int nh) {
+  const bool small_grid = (long)cdiv(T, 32) * nh * B < 256;
+  return g_attn_impl == 3 || (g_attn_impl == 0 && (T <= 64 || (small_grid && T <= 4096)));
+}
+static const char* relpos_attention_kernel_name(int B, int T, int nh) {
+  return relpos_attention_use16(B, T, nh) ? "relpos_attention16_kernel"
+                                          : (g_attn_impl == 1 ? "relpos_attention_kernel" : "relpos_attention_mfma_kernel");
+}
+// the kernel choice and launch on stream st (head dim 32 / 64 / 96 and W <= 4: checked at load, or by vits_debug_relpos_attention)
+static void launch_relpos_attention_on(hipStream_t st, const float* qkv, const float* ek, const float* ev, const int* len, float* out, int B,
+                                       int H, int T, int nh, int W) {
   const int dk = H / nh;
   struct { const float* ek; const float* ev; } L{ek, ev};
-  // 16-query tiles (more, smaller workgroups) while the 32-query MFMA kernel's grid would not fill the chip: measured round 4
-  // (profiles/r4_c16_threshold.txt) single utterances of 200 - 600 tokens (T_y 600 - 1800) -15..-35 % attention time against the old rule
-  // (T <= 512), the 32-item batch c3 -6 % (its 200-token text side now runs the MFMA kernel).
-  const bool small_grid = (long)cdiv(T, 32) * nh * B < 256;
-  const bool use16 = g_attn_impl == 3 || (g_attn_impl == 0 && (T <= 64 || (small_grid && T <= 4096)));
-  ProfScope ps(s, "attention", 4.0 * (double)B * H * T * T,
-               use16 ? "relpos_attention16_kernel" : (g_attn_impl == 1 ? "relpos_attention_kernel" : "relpos_attention_mfma_kernel"));
-  if (use16) {  // short sequences: 16-query tiles, more and smaller workgroups
+  if (relpos_attention_use16(B, T, nh)) {  // short sequences: 16-query tiles, more and smaller workgroups
     dim3 grid(cdiv(T, 16), nh, B);
     const bool w8 = T > 64;
     const int nwv = w8 ? 8 : 4;
@@ -587,8 +592,8 @@ static void launch_attention_raw(vits_session* s, const float* qkv, const float*
     const size_t lds = (size_t)nwv * (wreg > nv * 64 ? wreg : nv * 64) * sizeof(float);
 #define ATT16_GO(DK_)                                                                                                                  \
   do {                                                                                                                                 \
-    if (w8) hipLaunchKernelGGL((relpos_attention16_kernel<DK_, 8>), grid, dim3(512), lds, s->stream, qkv, L.ek, L.ev, len, out, H, T, W); \
-    else hipLaunchKernelGGL((relpos_attention16_kernel<DK_, 4>), grid, dim3(256), lds, s->stream, qkv, L.ek, L.ev, len, out, H, T, W);   \
+    if (w8) hipLaunchKernelGGL((relpos_attention16_kernel<DK_, 8>), grid, dim3(512), lds, st, qkv, L.ek, L.ev, len, out, H, T, W);        \
+    else hipLaunchKernelGGL((relpos_attention16_kernel<DK_, 4>), grid, dim3(256), lds, st, qkv, L.ek, L.ev, len, out, H, T, W);          \
   } while (0)
     if (dk == 96) ATT16_GO(96);
     else if (dk == 64) ATT16_GO(64);
@@ -600,15 +605,20 @@ static void launch_attention_raw(vits_session* s, const float* qkv, const float*
     dim3 grid(cdiv(T, 32), nh, B);
     const int wreg = dk * 33 + 10 * 32 + 9 * 32;
     const size_t lds = (size_t)4 * wreg * sizeof(float);
-    if (dk == 96) hipLaunchKernelGGL((relpos_attention_mfma_kernel<96>), grid, dim3(256), lds, s->stream, qkv, L.ek, L.ev, len, out, H, T, W);
-    else if (dk == 64) hipLaunchKernelGGL((relpos_attention_mfma_kernel<64>), grid, dim3(256), lds, s->stream, qkv, L.ek, L.ev, len, out, H, T, W);
-    else hipLaunchKernelGGL((relpos_attention_mfma_kernel<32>), grid, dim3(256), lds, s->stream, qkv, L.ek, L.ev, len, out, H, T, W);
+    if (dk == 96) hipLaunchKernelGGL((relpos_attention_mfma_kernel<96>), grid, dim3(256), lds, st, qkv, L.ek, L.ev, len, out, H, T, W);
+    else if (dk == 64) hipLaunchKernelGGL((relpos_attention_mfma_kernel<64>), grid, dim3(256), lds, st, qkv, L.ek, L.ev, len, out, H, T, W);
+    else hipLaunchKernelGGL((relpos_attention_mfma_kernel<32>), grid, dim3(256), lds, st, qkv, L.ek, L.ev, len, out, H, T, W);
     return;
   }
   dim3 grid(cdiv(T, ATT_TQ), nh, B);
-  if (dk == 96) hipLaunchKernelGGL((relpos_attention_kernel<96>), grid, dim3(256), 0, s->stream, qkv, L.ek, L.ev, len, out, H, T, W);
-  else if (dk == 64) hipLaunchKernelGGL((relpos_attention_kernel<64>), grid, dim3(256), 0, s->stream, qkv, L.ek, L.ev, len, out, H, T, W);
-  else hipLaunchKernelGGL((relpos_attention_kernel<32>), grid, dim3(256), 0, s->stream, qkv, L.ek, L.ev, len, out, H, T, W);
+  if (dk == 96) hipLaunchKernelGGL((relpos_attention_kernel<96>), grid, dim3(256), 0, st, qkv, L.ek, L.ev, len, out, H, T, W);
+  else if (dk == 64) hipLaunchKernelGGL((relpos_attention_kernel<64>), grid, dim3(256), 0, st, qkv, L.ek, L.ev, len, out, H, T, W);
+  else hipLaunchKernelGGL((relpos_attention_kernel<32>), grid, dim3(256), 0, st, qkv, L.ek, L.ev, len, out, H, T, W);
+}
+static void launch_attention_raw(vits_session* s, const float* qkv, const float* ek, const float* ev, const int* len, float* out, int B,
+                                 int H, int T, int nh, int W) {
+  ProfScope ps(s, "attention", 4.0 * (double)B * H * T * T, relpos_attention_kernel_name(B, T, nh));
+  launch_relpos_attention_on(s->stream, qkv, ek, ev, len, out, B, H, T, nh, W);
 }
 
 // Attention with no relative-position terms (window_size=None: the pre-transformer of the `pre_conv` flow) on plain_attention*_kernel

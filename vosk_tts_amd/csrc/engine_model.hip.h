@@ -490,6 +490,8 @@ static int load_model(vits_model* m) {
   if (hp.flow_dilation_rate != 1) return fail(VITS_ERR_UNSUPPORTED, "flow dilation_rate != 1");
   if (hp.flow_type < 0 || hp.flow_type > 2)
     return fail(VITS_ERR_UNSUPPORTED, "flow_type %d (0 = pre_conv2, 1 = pre_conv, 2 = plain ResidualCouplingLayer)", hp.flow_type);
+  if (hp.flow_type == 0 && H / 2 != 32 && H / 2 != 64 && H / 2 != 96)  // pre_conv2: 2 heads on H channels
+    return fail(VITS_ERR_UNSUPPORTED, "pre_conv2 flow: head dim hidden/2 = %d not in {32,64,96}", H / 2);
   if (hp.flow_type == 1 && (I % 4 || !plain_attention_dk_ok(I / 4)))  // pre_conv: 2 heads on I/2 channels
     return fail(VITS_ERR_UNSUPPORTED, "pre_conv flow: head dim inter_channels/4 = %d is not a multiple of 16 in [16, 96]", I / 4);
   m->use_g = G > 0 && hp.n_speakers > 1;
@@ -566,9 +568,10 @@ static int load_model(vits_model* m) {
     snprintf(nm, sizeof nm, "flow.flows.%d.pre", 2 * f);
     c.pre = conv_from(m, nm, H, I / 2, 1, true);
     snprintf(nm, sizeof nm, "flow.flows.%d.pre_transformer", 2 * f);
-    // pre_conv2 (models.py:353-360): 1 layer on H channels, the text encoder's heads and window.  pre_conv (models.py:417-425):
-    // 2 layers on the I/2 channels of x0, 2 heads, FFN kernel 3 with filter I/2, window_size=None.  plain: no pre-transformer.
-    if (hp.flow_type == 0) load_encoder(m, c.enc, nm, 1, H, H, K5, hp.n_heads, hp.window_size);
+    // pre_conv2 (models.py:352-360): 1 layer on H channels, 2 heads whatever n_heads is (only the text encoder takes it), the Encoder's
+    // default window like the text encoder's.  pre_conv (models.py:417-425): 2 layers on the I/2 channels of x0, 2 heads, FFN kernel 3
+    // with filter I/2, window_size=None.  plain: no pre-transformer.
+    if (hp.flow_type == 0) load_encoder(m, c.enc, nm, 1, H, H, K5, 2, hp.window_size);
     else if (hp.flow_type == 1) load_encoder(m, c.enc, nm, 2, I / 2, I / 2, 3, 2, -1);
     for (int i = 0; i < L && !m->missing; ++i) {
       // in_layer rows permuted to [tanh 32 | sigmoid 32] per 32 channels for the fused gate epilogue

@@ -491,6 +491,7 @@ __global__ void __launch_bounds__(256) relpos_attention_kernel(const float* qkv,
   const int tid = threadIdx.x, kl = tid & (ATT_KL - 1), qi = tid >> 4;
   const int hd = blockIdx.y, b = blockIdx.z;
   const int i = blockIdx.x * ATT_TQ + qi;
+  if (ek == nullptr) W = -1;  // no tables (StableTTS DiT blocks, BERT): no band, neither table is read
   const int L = len[b] < T ? len[b] : T;
   const float* qb = qkv + ((long long)b * 3 * H + (long long)hd * DK) * T;
   const float* kb = qb + (long long)H * T;

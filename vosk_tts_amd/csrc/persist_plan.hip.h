@@ -20,11 +20,13 @@ static int persist_slice(int Cin, int K) {
 }
 static bool persist_conv_ok(const ConvW& W) { return W.w16 && persist_slice(W.Cin, W.K) > 0; }
 
+// (each encoder with its own heads and window: the pre_conv2 flow's pre-transformer has 2 heads whatever n_heads is).  W >= 1: the
+// program's attention blocks take W == 0 as "no tables" (persist_encoder_layer), so a window-0 encoder stays on the launch path.
 static bool persist_encoder_ok(const vits_model* m, const EncoderW& E) {
-  const vits_hparams& hp = m->hp;
-  if (E.layers.empty() || E.H % 16 || E.H > PS_MAXC || hp.n_heads < 1 || hp.n_heads > 4 || E.H % hp.n_heads) return false;
-  const int dk = E.H / hp.n_heads;
-  if (dk > PS_DKP || dk % 16 || hp.window_size < 0 || hp.window_size > 4 || (2 * hp.window_size + 1) * dk > 1024) return false;  // (dk % 16: the PV tiles of the MFMA attention blocks)
+  (void)m;
+  if (E.layers.empty() || E.H % 16 || E.H > PS_MAXC || E.nh < 1 || E.nh > 4 || E.H % E.nh) return false;
+  const int dk = E.H / E.nh;
+  if (dk > PS_DKP || dk % 16 || E.W < 1 || E.W > 4 || (2 * E.W + 1) * dk > 1024) return false;  // (dk % 16: the PV tiles of the MFMA attention blocks)
   for (const EncLayerW& L : E.layers)
     if (!persist_conv_ok(L.qkv) || !persist_conv_ok(L.o) || !persist_conv_ok(L.f1) || !persist_conv_ok(L.f2) || L.qkv.K != 1 || L.o.K != 1) return false;
   return true;
@@ -70,7 +72,7 @@ static size_t persist_sdp_cells(const vits_model* m, int B, int Tx) {
 
 // ---- one attentions.Encoder layer: qkv, attention partials, merged attention, y1, x1, FFN hidden, FFN partials, output
 static size_t persist_enc_layer_cells(const vits_model* m, const EncoderW& E, size_t Tp) {
-  const size_t H = E.H, F = E.F, nh = m->hp.n_heads, dk = H / nh, ntn = Tp / 16;
+  const size_t H = E.H, F = E.F, nh = E.nh, dk = H / nh, ntn = Tp / 16;
   const size_t ks2 = E.layers[0].f2.Cin / persist_slice(E.layers[0].f2.Cin, E.layers[0].f2.K);
   return Tp * (3 * H + ntn * nh * (dk + 2) + H + H + H + F + ks2 * H + H);
 }
@@ -279,7 +281,7 @@ struct PBuild {
 static const ll_t* persist_encoder_layer(PBuild& b, const EncLayerW& L, const EncoderW& E, const ll_t* x, const float* vec_next, const ll_t* base,
                                          float* xplain) {
   vits_model* m = b.m;
-  const int H = E.H, F = E.F, nh = m->hp.n_heads, dk = H / nh, W = m->hp.window_size, Tp = b.Tp, ntn = b.ntn;
+  const int H = E.H, F = E.F, nh = E.nh, dk = H / nh, W = E.W, Tp = b.Tp, ntn = b.ntn;
   // q | k | v
   PStep st = b.mm(L.qkv, x, H);
   st.yout = b.take_rows(3 * H);

@@ -503,6 +503,12 @@ def import_onnx(path_or_bytes, config=None):  # noqa: C901
     if "hop_length" not in config:
         hp.hop_length = rate  # samples per frame are a property of the decoder, not an independent setting
     W.validate_hparams(hp)
+    if hp.flow_type == 0:  # pre_conv2: the pre-transformer has 2 heads whatever n_heads is (models.py:352-360), the text encoder's window
+        want = (1, 2 * hp.window_size + 1, hp.hidden_channels // W.FLOW_N_HEADS)
+        for name in sorted(k for k in t if k.startswith("flow.flows.") and k.endswith((".emb_rel_k", ".emb_rel_v"))):
+            if tuple(t[name].shape) != want:
+                raise ValueError(f"{name}: shape {tuple(t[name].shape)}, expected {want} (the pre_conv2 flow's pre-transformer has "
+                                 f"{W.FLOW_N_HEADS} heads of hidden/{W.FLOW_N_HEADS} and the text encoder's window {hp.window_size})")
     tensors, missing, bad = {}, [], []
     for name, shape, _kind, _fan, _gain in W.tensor_specs(hp):
         a = t.get(name)

@@ -203,6 +203,29 @@ def tiny_istft_hparams(n_vocab=20):
     return hp
 
 
+# The pre_conv2 flow's pre-transformer is attentions.Encoder(hidden, hidden, n_heads=2, ...) whatever the config's n_heads is
+# (models.py:352-360; only the text encoder takes n_heads, models.py:307-314); both use the Encoder's default window.
+FLOW_N_HEADS = 2
+
+
+def heads3_hparams(n_vocab=62):
+    """Default-size graph with 3 attention heads: the text encoder runs at head dim 64, the pre_conv2 flow keeps 2 heads of 96."""
+    hp = default_hparams(n_vocab)
+    hp.n_heads = 3
+    return hp
+
+
+def heads4_hparams(n_vocab=62):
+    """hidden 128 with 4 attention heads (the most the persistent programs take): the text encoder runs 4 heads of 32, the pre_conv2
+    flow 2 heads of 64."""
+    hp = default_hparams(n_vocab)
+    hp.hidden_channels = 128
+    hp.inter_channels = 128
+    hp.filter_channels = 512
+    hp.n_heads = 4
+    return hp
+
+
 PRE_CONV_HEAD_DIMS = (16, 32, 48, 64, 80, 96)  # head dims the plain (no relative position) attention kernels are built for
 
 
@@ -280,8 +303,6 @@ def tensor_specs(hp):
     path.  kind selects the synthetic init."""
     H, I, F = hp.hidden_channels, hp.inter_channels, hp.filter_channels
     G = hp.gin_channels
-    nh = hp.n_heads
-    dk = H // nh
     W = 2 * hp.window_size + 1
     specs = []
 
@@ -294,7 +315,8 @@ def tensor_specs(hp):
         specs.append((name + ".gamma", (c,), "gamma", 0, 1.0))
         specs.append((name + ".beta", (c,), "beta", 0, 1.0))
 
-    def encoder(prefix, n_layers, filt, k, C=H, rel=True):
+    def encoder(prefix, n_layers, filt, k, C=H, rel=True, nh=hp.n_heads):
+        dk = C // nh
         for i in range(n_layers):
             a = f"{prefix}.attn_layers.{i}"
             if rel:
@@ -373,8 +395,8 @@ def tensor_specs(hp):
         if hp.flow_type == 1:
             encoder(p + ".pre_transformer", 2, I // 2, 3, C=I // 2, rel=False)
         conv(p + ".pre", H, I // 2, 1)
-        if hp.flow_type == 0:
-            encoder(p + ".pre_transformer", 1, H, hp.flow_kernel_size)
+        if hp.flow_type == 0:  # pre_conv2 (models.py:352-360): 2 heads whatever n_heads is, the Encoder's default window
+            encoder(p + ".pre_transformer", 1, H, hp.flow_kernel_size, nh=FLOW_N_HEADS)
         for i in range(hp.flow_wn_layers):
             conv(f"{p}.enc.in_layers.{i}", 2 * H, H, hp.flow_kernel_size)
         for i in range(hp.flow_wn_layers):
