@@ -61,6 +61,15 @@ void vits_debug_conv_wp(int mode);
  * iSTFT / PQMF tail reads, then per upsampling stage: the polyphase launch's limit (input positions), c1 limits [n_resd], c2 limits
  * [n_resd].  Returns the number of values (at most `cap` are written), or a negative error. */
 int vits_debug_decoder_needs(const vits_hparams* hp, int32_t* out, int32_t cap);
+/* Test hook, host arithmetic only: the halo in frames vits_create derives for these hparams (ragged batches decoded as a padded
+ * continuation, streaming windows): at least the decoder's one-sided receptive field, at least 32.  Negative on bad arguments. */
+int vits_debug_rag_halo(const vits_hparams* hp);
+/* Test hooks: vits_debug_launch_log(1) clears the process-wide launch counters and starts counting every kernel launch of the eager
+ * paths under (operation, kernel instantiation) -- the names of vits_session_profile_report; (0) stops.  vits_debug_launch_count returns
+ * the launches counted so far whose operation equals `op` (e.g. "dec.ups") and whose kernel name starts with `kernel_prefix` (e.g.
+ * "conv_mfma_kernel<2,2,2,2"): lets a test assert which kernel a launch took, not only what it computed. */
+void vits_debug_launch_log(int on);
+int vits_debug_launch_count(const char* op, const char* kernel_prefix);
 /* Test hook: software-pipelined 64 x 64 conv kernel (conv_sp_kernel, csrc/conv_sp.hip.h): -1 = default (by grid size),
  * 0 = never, 1 = by grid size, 2 = wherever a launch is eligible for it. */
 void vits_debug_conv_sp(int mode);

@@ -184,6 +184,21 @@ class VitsLib:
             k += 1 + 2 * nd
         return out
 
+    def rag_halo(self, hp):
+        """vits_debug_rag_halo (host arithmetic, no device): the ragged / streaming halo in frames vits_create derives for `hp`"""
+        n = self._fn("debug_rag_halo")(ctypes.byref(hp))
+        if n < 0:
+            raise VitsError(-n, self._fn("last_error")().decode(errors="replace"))
+        return int(n)
+
+    def launch_log(self, on):
+        """vits_debug_launch_log: start (clearing the counters) or stop counting eager launches by (operation, kernel)"""
+        self._fn("debug_launch_log")(int(on))
+
+    def launch_count(self, op, kernel_prefix):
+        """vits_debug_launch_count: launches of operation `op` counted so far whose kernel name starts with `kernel_prefix`"""
+        return int(self._fn("debug_launch_count")(op.encode(), kernel_prefix.encode()))
+
     def mas_maximum_path(self, values, t_ys, t_xs, device=0):
         """monotonic_align.maximum_path_c (core.pyx:35-42): values float32 [B,T_y,T_x] -> paths int32 [B,T_y,T_x]."""
         values = _f32(values)

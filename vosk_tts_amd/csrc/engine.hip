@@ -589,6 +589,27 @@ int vits_debug_persist_runs(vits_model* m) {
   return v[1];
 }
 void vits_debug_conv_wp(int mode) { g_wp_mode = mode; }
+void vits_debug_launch_log(int on) {
+  std::lock_guard<std::mutex> g(g_launch_log_mu);
+  if (on) g_launch_counts.clear();
+  g_launch_log.store(on ? 1 : 0);
+}
+int vits_debug_launch_count(const char* op, const char* kernel_prefix) {
+  if (!op || !kernel_prefix) return -1;
+  const std::string key = std::string(op) + "|" + kernel_prefix;
+  std::lock_guard<std::mutex> g(g_launch_log_mu);
+  int n = 0;
+  for (const auto& kv : g_launch_counts)
+    if (kv.first.compare(0, key.size(), key) == 0) n += kv.second;
+  return n;
+}
+int vits_debug_rag_halo(const vits_hparams* hp) {
+  if (!hp || hp->n_ups < 1 || hp->n_ups > VITS_MAX_UPS || hp->n_resk < 1 || hp->n_resk > VITS_MAX_RESK || hp->n_resd < 1 || hp->n_resd > VITS_MAX_RESD)
+    return -fail(VITS_ERR_ARG, "rag_halo: bad arguments");
+  for (int i = 0; i < hp->n_ups; ++i) if (hp->up_rates[i] < 1) return -fail(VITS_ERR_ARG, "rag_halo: bad up_rates");
+  if (hp->dec_type != 1 && (hp->istft_hop < 1 || hp->subbands < 1)) return -fail(VITS_ERR_ARG, "rag_halo: bad tail geometry");
+  return decoder_rag_halo(*hp);
+}
 // Host arithmetic only (no device): the per-layer limits decoder_needs derives for a padded-batch continuation.  Layout: [0] frames of z
 // read beyond an item's end (conv_pre's output limit + its 3 taps to the right), [1] pre_out, [2] post_out, [3] tail_cols, then per
 // upsampling stage: ups_q, c1_out[0..n_resd), c2_out[0..n_resd).  Returns the number of values (written up to cap).

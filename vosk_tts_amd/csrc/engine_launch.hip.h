@@ -3,22 +3,32 @@
 // planner / launch selection / stages / host paths can be read on their own.
 #pragma once
 // ------------------------------------------------------------------------------------ launch helpers
+// Test hook (vits_debug_launch_log / vits_debug_launch_count): while on, every ProfScope counts its launch under "op|kernel", process-wide,
+// so a test can assert WHICH kernel a launch took and not only what it computed.  Off (default): one relaxed load per launch.
+static std::atomic<int> g_launch_log{0};
+static std::mutex g_launch_log_mu;
+static std::map<std::string, int> g_launch_counts;
 struct ProfScope {
-  vits_session* s; bool on;
-  ProfScope(vits_session* s_, const char* name, double flops, const char* kernel = "-") : s(s_), on(s_->profile) {
+  vits_session* s; bool on; bool log; const char* op; std::string lk;
+  ProfScope(vits_session* s_, const char* name, double flops, const char* kernel = "-")
+      : s(s_), on(s_->profile), log(g_launch_log.load(std::memory_order_relaxed) != 0), op(name) {
+    if (log) lk = kernel;
     if (!on) return;
     ProfRec r; r.name = name; r.kernel = kernel; r.flops = flops;
     hipEventCreate(&r.e0); hipEventCreate(&r.e1);
     hipEventRecord(r.e0, s->stream);
     s->prof.push_back(r);
   }
-  void set_kernel(const char* k) { if (on) s->prof.back().kernel = k; }
+  void set_kernel(const char* k) { if (on) s->prof.back().kernel = k; if (log) lk = k; }
+  static void append_arg(std::string& k, int v) { if (!k.empty() && k.back() == '>') { k.pop_back(); k += "," + std::to_string(v) + ">"; } }
   void add_template_arg(int v) {  // "name<a,b>" -> "name<a,b,v>"
-    if (!on) return;
-    std::string& k = s->prof.back().kernel;
-    if (!k.empty() && k.back() == '>') { k.pop_back(); k += "," + std::to_string(v) + ">"; }
+    if (log) append_arg(lk, v);
+    if (on) append_arg(s->prof.back().kernel, v);
   }
-  ~ProfScope() { if (on) hipEventRecord(s->prof.back().e1, s->stream); }
+  ~ProfScope() {
+    if (on) hipEventRecord(s->prof.back().e1, s->stream);
+    if (log) { std::lock_guard<std::mutex> g(g_launch_log_mu); ++g_launch_counts[std::string(op) + "|" + lk]; }
+  }
 };
 
 

@@ -302,6 +302,29 @@ static double bessel_i0(double x) {
   return s;
 }
 
+// One-sided receptive field of the decoder in frames (24.9 for the default config), rounded up with 2 frames of slack and
+// at least 32: ragged batches and streaming windows reproduce the dense result only if the halo they keep is at least this wide.
+static int decoder_rag_halo(const vits_hparams& hp) {
+  double rf = 3.0, rate = 1.0;  // conv_pre k = 7
+  for (int i = 0; i < hp.n_ups; ++i) {
+    const int u = hp.up_rates[i], Ku = hp.up_kernels[i];
+    rf += (double)((Ku + u - 1) / u / 2 + 1) / rate;
+    rate *= u;
+    double worst = 0;
+    for (int j = 0; j < hp.n_resk; ++j) {
+      double span = 0;
+      for (int d = 0; d < hp.n_resd; ++d) span += (hp.res_kernels[j] - 1) * hp.res_dilations[j][d] / 2.0 + (hp.res_kernels[j] - 1) / 2.0;
+      if (span > worst) worst = span;
+    }
+    rf += worst / rate;
+  }
+  rf += 4.0 / rate;  // conv_post k = 7 (+ reflection pad)
+  if (hp.dec_type == 0 || hp.dec_type == 2) rf += ((double)hp.istft_n_fft / hp.istft_hop + (hp.pqmf_taps / 2.0) / hp.subbands / hp.istft_hop) / rate;
+  if (hp.dec_type == 3) rf += ((double)hp.istft_n_fft / hp.istft_hop) / rate;  // iSTFT only, no synthesis filter
+  const int halo = (int)ceil(rf) + 2;
+  return halo < 32 ? 32 : halo;
+}
+
 // ---- decoder weights (Multiband_iSTFT_Generator models.py:975-1054 / Generator :845-898)
 static int load_decoder(vits_model* m) {
   const vits_hparams& hp = m->hp;
@@ -329,37 +352,18 @@ static int load_decoder(vits_model* m) {
     if (hp.hop_length <= 0 || rate != hp.hop_length)
       return fail(VITS_ERR_BLOB, "decoder produces %lld samples per frame but hop_length is %d", rate, hp.hop_length);
     for (int j = 0; j < hp.n_resk; ++j)
-      if (hp.res_kernels[j] <= 0 || hp.res_kernels[j] % 2 == 0) return fail(VITS_ERR_BLOB, "resblock kernel %d invalid", hp.res_kernels[j]);
+      if (hp.res_kernels[j] <= 0 || hp.res_kernels[j] % 2 == 0) return fail(VITS_ERR_BLOB, "resblock kernel %d invalid (must be odd)", hp.res_kernels[j]);
   }
-  {
-    // One-sided receptive field of the decoder in frames (24.9 for the default config): ragged batches and
-    // streaming windows reproduce the dense result only if the halo they keep is at least this wide.
-    double rf = 3.0, rate = 1.0;  // conv_pre k = 7
-    for (int i = 0; i < hp.n_ups; ++i) {
-      const int u = hp.up_rates[i], Ku = hp.up_kernels[i];
-      rf += (double)((Ku + u - 1) / u / 2 + 1) / rate;
-      rate *= u;
-      double worst = 0;
-      for (int j = 0; j < hp.n_resk; ++j) {
-        double span = 0;
-        for (int d = 0; d < hp.n_resd; ++d) span += (hp.res_kernels[j] - 1) * hp.res_dilations[j][d] / 2.0 + (hp.res_kernels[j] - 1) / 2.0;
-        if (span > worst) worst = span;
-      }
-      rf += worst / rate;
-    }
-    rf += 4.0 / rate;  // conv_post k = 7 (+ reflection pad)
-    if (hp.dec_type == 0 || hp.dec_type == 2) rf += ((double)hp.istft_n_fft / hp.istft_hop + (hp.pqmf_taps / 2.0) / hp.subbands / hp.istft_hop) / rate;
-    if (hp.dec_type == 3) rf += ((double)hp.istft_n_fft / hp.istft_hop) / rate;  // iSTFT only, no synthesis filter
-    m->rag_halo = (int)ceil(rf) + 2;
-    if (m->rag_halo < 32) m->rag_halo = 32;
-    if (m->rag_halo > 4096) return fail(VITS_ERR_UNSUPPORTED, "decoder receptive field of %d frames is not supported", m->rag_halo);
-  }
+  m->rag_halo = decoder_rag_halo(hp);
+  if (m->rag_halo > 4096) return fail(VITS_ERR_UNSUPPORTED, "decoder receptive field of %d frames is not supported", m->rag_halo);
   m->ups.resize(hp.n_ups);
   m->rb.resize((size_t)hp.n_ups * hp.n_resk);
   for (int i = 0; i < hp.n_ups && !m->missing; ++i) {
     UpW& U = m->ups[i];
     const int u = hp.up_rates[i], Ku = hp.up_kernels[i], Co = C / 2, p = (Ku - u) / 2;
-    if (u > 8 || Ku % u || (Ku - u) % 2 || C % 64) return fail(VITS_ERR_UNSUPPORTED, "upsample rate/kernel unsupported");
+    if (u > 8 || Ku % u || (Ku - u) % 2)
+      return fail(VITS_ERR_UNSUPPORTED, "decoder stage %d: upsample rate %d / kernel %d unsupported (rate <= 8, kernel a multiple of the rate, kernel - rate even)", i, u, Ku);
+    if (C % 64) return fail(VITS_ERR_UNSUPPORTED, "decoder stage %d: %d input channels (must be a multiple of 64)", i, C);
     const float* w = tget(m, 3, C, Co, Ku, "dec.ups.%d.weight", i);  // [Cin, Cout, K]
     const float* b = tget(m, 1, Co, -1, -1, "dec.ups.%d.bias", i);
     if (m->missing) break;
@@ -390,7 +394,8 @@ static int load_decoder(vits_model* m) {
       R.K = hp.res_kernels[j];
       for (int d = 0; d < hp.n_resd; ++d) {
         R.dil[d] = hp.res_dilations[j][d];
-        if ((R.K - 1) * R.dil[d] > CONV_MAX_HALO) return fail(VITS_ERR_UNSUPPORTED, "resblock receptive field too wide");
+        if (R.dil[d] <= 0 || (R.K - 1) * R.dil[d] > CONV_MAX_HALO)
+          return fail(VITS_ERR_UNSUPPORTED, "resblock kernel %d with dilation %d: a halo of %d columns (1 .. %d are served)", R.K, R.dil[d], (R.K - 1) * R.dil[d], CONV_MAX_HALO);
         snprintf(nm, sizeof nm, "dec.resblocks.%d.convs1.%d", i * hp.n_resk + j, d);
         const bool bf3 = hp.conv_precision == 1 && C % 64 == 0;  // split-bf16 variant of the batch-size kernel (128- or 64-row tiles)
         R.c1[d] = conv_from(m, nm, C, C, R.K, true, false, bf3);
@@ -456,6 +461,13 @@ static int load_decoder(vits_model* m) {
   return m->missing ? VITS_ERR_BLOB : VITS_OK;
 }
 
+static int check_decoder_counts(const vits_hparams& hp) {
+  if (hp.n_ups < 1 || hp.n_ups > VITS_MAX_UPS || hp.n_resk < 1 || hp.n_resk > 3 || hp.n_resd < 1 || hp.n_resd > VITS_MAX_RESD)
+    return fail(VITS_ERR_UNSUPPORTED, "decoder with n_ups %d / n_resk %d / n_resd %d: 1-%d upsampling stages, 1-3 ResBlock chains and 1-%d dilations are served",
+                hp.n_ups, hp.n_resk, hp.n_resd, VITS_MAX_UPS, VITS_MAX_RESD);
+  return VITS_OK;
+}
+
 static int load_model(vits_model* m) {
   const vits_hparams& hp = m->hp;
   const int H = hp.hidden_channels, I = hp.inter_channels, F = hp.filter_channels, G = hp.gin_channels;
@@ -465,7 +477,7 @@ static int load_model(vits_model* m) {
   m->acoustic = hp.n_vocab > 0;
   if (!m->acoustic) {
     if (I % CONV_CI_T) return fail(VITS_ERR_UNSUPPORTED, "decoder input channels must be a multiple of %d", CONV_CI_T);
-    if (hp.n_ups > VITS_MAX_UPS || hp.n_resk > 3 || hp.n_resd > VITS_MAX_RESD || hp.n_ups < 1) return fail(VITS_ERR_UNSUPPORTED, "hparams out of range");
+    if (int rc = check_decoder_counts(hp)) return rc;
     return load_decoder(m);
   }
   if (hp.n_heads <= 0 || H % hp.n_heads) return fail(VITS_ERR_UNSUPPORTED, "hidden %% n_heads != 0");
@@ -474,8 +486,8 @@ static int load_model(vits_model* m) {
   if (hp.window_size > 4 || hp.window_size < 0) return fail(VITS_ERR_UNSUPPORTED, "window_size > 4");
   if (H % 32 || I % 32 || (I / 2) % 16 || D % 32) return fail(VITS_ERR_UNSUPPORTED, "channel counts must be multiples of 32");
   if (H > LN_MAXV * LN_CG || D > LN_MAXV * LN_CG) return fail(VITS_ERR_UNSUPPORTED, "LayerNorm width > %d", LN_MAXV * LN_CG);
-  if (hp.dp_num_bins > 15 || hp.n_ups > VITS_MAX_UPS || hp.n_resk > 3 || hp.n_resd > VITS_MAX_RESD || hp.n_ups < 1)
-    return fail(VITS_ERR_UNSUPPORTED, "hparams out of range");
+  if (hp.dp_num_bins > 15) return fail(VITS_ERR_UNSUPPORTED, "dp_num_bins %d > 15", hp.dp_num_bins);
+  if (int rc = check_decoder_counts(hp)) return rc;
   if (hp.dp_n_flows < 0) return fail(VITS_ERR_UNSUPPORTED, "dp_n_flows %d", hp.dp_n_flows);
   m->dp_det = hp.dp_n_flows == 0;
   if (m->dp_det) {  // deterministic DurationPredictor: conv_1 [D, H, K], conv_2 [D, D, K] ('same' padding), norm_2 + proj in one tail kernel

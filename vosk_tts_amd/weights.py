@@ -294,6 +294,52 @@ def hifigan_v1_vocoder_hparams():
     return hp
 
 
+def decoder_hparams(dec_type, ups, res_kernels, res_dilations, tail=None, dec_initial_channel=128, inter_channels=64, n_vocab=0,
+                    gin_channels=0, n_speakers=0, conv_precision=0):
+    """One decoder geometry as an hparams struct.  ups: ((u, Ku), ...); res_kernels: (k, ...); res_dilations: one list for every
+    chain, (d, ...), or one list per chain, ((d, ...), ...); tail: (subbands, n_fft, hop, taps) for dec_type 0 / 2, (n_fft, hop) for
+    dec_type 3, None for the plain Generator.  hop_length is set to the product.  n_vocab 0 (default): a vocoder-only blob (decoder
+    tensors only, no speaker conditioning); n_vocab > 0: the tiny voice (tiny_hparams) around this decoder, gin_channels /
+    n_speakers as given (0 keeps the tiny voice's)."""
+    hp = tiny_hparams(n_vocab) if n_vocab > 0 else default_hparams(0)
+    if n_vocab > 0:
+        if gin_channels:
+            hp.gin_channels = gin_channels
+        if n_speakers:
+            hp.n_speakers = n_speakers
+    else:
+        hp.n_vocab, hp.n_speakers, hp.gin_channels = 0, 0, 0
+    hp.inter_channels = inter_channels
+    if n_vocab > 0:
+        hp.hidden_channels = inter_channels  # the tiny voice keeps hidden == inter
+    hp.dec_type = dec_type
+    hp.dec_initial_channel = dec_initial_channel
+    hp.conv_precision = conv_precision
+    hp.n_ups = len(ups)
+    for i in range(MAX_UPS):
+        hp.up_rates[i], hp.up_kernels[i] = ups[i] if i < len(ups) else (0, 0)
+    per_chain = res_dilations if isinstance(res_dilations[0], (tuple, list)) else [res_dilations] * len(res_kernels)
+    if len(per_chain) != len(res_kernels) or len({len(d) for d in per_chain}) != 1:
+        raise ValueError("res_dilations: one list per ResBlock chain, all of one length")
+    hp.n_resk, hp.n_resd = len(res_kernels), len(per_chain[0])
+    for j in range(MAX_RESK):
+        hp.res_kernels[j] = res_kernels[j] if j < hp.n_resk else 0
+        for d in range(MAX_RESD):
+            hp.res_dilations[j][d] = per_chain[j][d] if j < hp.n_resk and d < hp.n_resd else 0
+    rate = 1
+    for u, _ in ups:
+        rate *= u
+    if dec_type in (0, 2):
+        hp.subbands, hp.istft_n_fft, hp.istft_hop, hp.pqmf_taps = tail
+        rate *= hp.istft_hop * hp.subbands
+    elif dec_type == 3:
+        hp.istft_n_fft, hp.istft_hop = tail
+        hp.subbands = 1
+        rate *= hp.istft_hop
+    hp.hop_length = rate
+    return hp
+
+
 # --------------------------------------------------------------------------- #
 # tensor inventory
 # --------------------------------------------------------------------------- #
@@ -493,17 +539,46 @@ def synthetic_from_specs(specs, seed=1234, heavy_sigma=0.0):
 # blob I/O
 # --------------------------------------------------------------------------- #
 
+CONV_MAX_HALO = 64  # (kernel - 1) * dilation of a ResBlock conv (csrc/conv_mfma.hip.h)
+
+
+def tail_lds_bytes(synth, S, N, hop, taps):
+    """LDS of the fused decoder tail for one geometry: the mirror of tail_lds_bytes in csrc/kernels_misc.hip.h"""
+    HM = (taps // 2 + S - 1) // S + 1 if synth else 0
+    nsub = (64 if synth else 256) + 2 * HM
+    FR = (nsub + N) // hop + 2
+    return 4 * (2 * S * (N // 2 + 1) * FR + (S * nsub if synth else 0) + (N + 2) * N + (S * (taps + 1) if synth else 0))
+
+
 def validate_hparams(hp):
     """The checks vits_create makes before it divides by a rate or sizes a buffer from hop_length (engine.hip load_decoder):
     the decoder writes T_y * prod(up_rates) [* istft_hop * subbands] samples per item into buffers of T_y * hop_length."""
     if not isinstance(hp, HParams):
         return
     rate = 1
+    if not 1 <= hp.n_ups <= MAX_UPS or not 1 <= hp.n_resk <= 3 or not 1 <= hp.n_resd <= MAX_RESD:
+        raise ValueError(f"decoder with n_ups {hp.n_ups} / n_resk {hp.n_resk} / n_resd {hp.n_resd}: 1-{MAX_UPS} upsampling stages, 1-3 ResBlock "
+                         f"chains and 1-{MAX_RESD} dilations are served")
+    ch = hp.dec_initial_channel
     for i in range(hp.n_ups):
         u, k = hp.up_rates[i], hp.up_kernels[i]
         if u <= 0 or k < u:
             raise ValueError(f"decoder stage {i}: upsample rate {u} / kernel {k} invalid")
+        if u > 8 or k % u or (k - u) % 2:
+            raise ValueError(f"decoder stage {i}: upsample rate {u} / kernel {k} unsupported (rate <= 8, kernel a multiple of the rate, "
+                             "kernel - rate even)")
+        if ch <= 0 or ch % 64:
+            raise ValueError(f"decoder stage {i}: {ch} input channels (must be a multiple of 64)")
+        ch //= 2
         rate *= u
+    for j in range(hp.n_resk):
+        k = hp.res_kernels[j]
+        if k <= 0 or k % 2 == 0:
+            raise ValueError(f"resblock kernel {k} invalid (must be odd)")
+        for d in range(hp.n_resd):
+            if hp.res_dilations[j][d] <= 0 or (k - 1) * hp.res_dilations[j][d] > CONV_MAX_HALO:
+                raise ValueError(f"resblock kernel {k} with dilation {hp.res_dilations[j][d]}: a halo of {(k - 1) * hp.res_dilations[j][d]} "
+                                 f"columns (1 .. {CONV_MAX_HALO} are served)")
     if hp.dec_type not in (0, 1, 2, 3):
         raise ValueError(f"dec_type {hp.dec_type}: 0 = multi-band iSTFT, 1 = HiFi-GAN Generator, 2 = multi-stream iSTFT, "
                          "3 = single-band iSTFT")
@@ -514,6 +589,10 @@ def validate_hparams(hp):
             raise ValueError(f"multi-stream synthesis filter of {hp.pqmf_taps + 1} taps: the length must be odd")
         if hp.dec_type == 3 and hp.subbands != 1:
             raise ValueError(f"single-band iSTFT decoder with subbands {hp.subbands}: must be 1")
+        lds = tail_lds_bytes(hp.dec_type != 3, hp.subbands, hp.istft_n_fft, hp.istft_hop, hp.pqmf_taps)
+        if lds > 65536:
+            raise ValueError(f"decoder tail geometry (subbands {hp.subbands}, n_fft {hp.istft_n_fft}, hop {hp.istft_hop}, taps {hp.pqmf_taps}) "
+                             f"needs {lds} bytes of LDS > 65536")
         rate *= hp.istft_hop * hp.subbands
     if hp.flow_type not in (0, 1, 2):
         raise ValueError(f"flow_type {hp.flow_type}: 0 = pre_conv2, 1 = pre_conv, 2 = plain ResidualCouplingLayer")
@@ -535,8 +614,10 @@ def validate_hparams(hp):
                          "gen_istft_hop_size / subbands / hop_length are inconsistent")
 
 
-def pack_blob(hp, tensors, magic=MAGIC):
-    validate_hparams(hp)
+def pack_blob(hp, tensors, magic=MAGIC, validate=True):
+    """validate=False: pack whatever the struct says (tests hand the library hparams it has to refuse itself)"""
+    if validate:
+        validate_hparams(hp)
     names = list(tensors.keys())
     n = len(names)
     head = magic + struct.pack("<I", ctypes.sizeof(type(hp))) + bytes(hp) + struct.pack("<I", n)
