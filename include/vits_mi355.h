@@ -117,6 +117,14 @@ typedef struct vits_hparams {
                                     multiple of 16 in [16, 96].  post_transformer is never run and not in the blob,
                                 2 = modules.ResidualCouplingLayer (the VITS-1 coupling, modules.py:298-345; use_transformer_flows false):
                                     pre, WN, post, no transformer.
+                                3 = reserved for FFTransformerCouplingLayer ("fft", models.py:486-542), which is not served,
+                                4 = "mono_layer_inter_residual" (models.py:696-714): per flow a ResidualCouplingLayer as in 2 at flow.flows.{3f},
+                                    a Flip, and a MonoTransformerFlowLayer (models.py:545-627) at flow.flows.{3f+2}: the 2-layer, 2-head
+                                    attentions.Encoder of type 1 on the inter_channels/2 channels of x0 (the same head-dim rule), then
+                                    post = Conv1d(inter_channels/2, inter_channels/2, 1); no speaker conditioning.  h = encoder(x0) + x0,
+                                5 = "mono_layer_post_residual" (models.py:715-734; what SynthesizerTrn builds when a config names no flow):
+                                    the tensors of 4; in reverse the mono layer halves x0 before the encoder, adds nothing back, and halves
+                                    x1 - m as well.
                                 Any other value: vits_create returns VITS_ERR_UNSUPPORTED.  (Blobs written before the field existed hold 0.) */
   int32_t reserved[5];
 } vits_hparams;

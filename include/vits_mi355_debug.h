@@ -86,6 +86,13 @@ void vits_debug_poison_workspace(int on);
  * grid size, or the one vits_debug_attention_impl forces (2: 32-query tiles, 3: 16-query tiles). */
 int vits_debug_plain_attention(int device, const float* qkv, const int64_t* lengths, int32_t B, int32_t C, int32_t T,
                                int32_t n_heads, float* out);
+/* Test hook: the tail of a MonoTransformerFlowLayer in reverse (mono_layer_* flows, flow_type 4 / 5; mono_couple_kernel) on caller host
+ * buffers.  h float [B, C, T] is the pre-transformer's output, u float [B, 2C, T] the layer's input z, W float [C, C] and b float [C]
+ * the layer's `post` conv; z float [B, 2C, T] receives rows [0, C) = u * s and rows [C, 2C) = (u - (W h + b)) * s on columns
+ * < lengths[b], exactly 0 beyond; s = 1 for mode 0 (inter_residual), 1/2 for mode 1 (post_residual).  C must be a multiple of 32
+ * in [32, 192]. */
+int vits_debug_mono_couple(int device, const float* h, const float* u, const float* W, const float* b, const int64_t* lengths,
+                           int32_t B, int32_t C, int32_t T, int32_t mode, float* z);
 /* Test hook: the relative-position attention (attentions.py:165-260: relpos_attention_kernel, relpos_attention_mfma_kernel,
  * relpos_attention16_kernel) on caller host buffers.  qkv float [B, 3C, T] as the fused q/k/v conv writes it, out float [B, C, T].
  * ek / ev: the shared relative-position tables [2 window + 1][C / n_heads] (heads_share=True), or both null for plain scaled-dot-product

@@ -730,6 +730,43 @@ int vits_debug_relpos_attention(int device, const float* qkv, const float* ek, c
   if (e != hipSuccess) return fail(VITS_ERR_DEVICE, "relpos attention: %s", hipGetErrorString(e));
   return VITS_OK;
 }
+// The tail of a MonoTransformerFlowLayer (mono_couple_kernel) on caller buffers: h [B, C, T], u and z [B, 2C, T], W [C, C], b [C].
+int vits_debug_mono_couple(int device, const float* h, const float* u, const float* W, const float* b, const int64_t* lengths, int32_t B,
+                           int32_t C, int32_t T, int32_t mode, float* z) {
+  if (!h || !u || !W || !b || !lengths || !z || B <= 0 || B > 65535 || T <= 0 || C <= 0 || (mode != 0 && mode != 1))
+    return fail(VITS_ERR_ARG, "mono couple: bad arguments");
+  if (!mono_couple_c_ok(C)) return fail(VITS_ERR_UNSUPPORTED, "mono couple: width %d not built (a multiple of 32 in [32, 192])", C);
+  std::vector<int> len32(B);
+  for (int i = 0; i < B; ++i) {
+    if (lengths[i] < 0 || lengths[i] > T) return fail(VITS_ERR_ARG, "mono couple: length out of range");
+    len32[i] = (int)lengths[i];
+  }
+  HIP_TRY(hipSetDevice(device));
+  const size_t nh = (size_t)B * C * T, nz = 2 * nh;
+  float *d_h = nullptr, *d_u = nullptr, *d_W = nullptr, *d_b = nullptr, *d_z = nullptr;
+  int* d_len = nullptr;
+  hipError_t e = hipMalloc((void**)&d_h, nh * sizeof(float));
+  if (e == hipSuccess) e = hipMalloc((void**)&d_u, nz * sizeof(float));
+  if (e == hipSuccess) e = hipMalloc((void**)&d_z, nz * sizeof(float));
+  if (e == hipSuccess) e = hipMalloc((void**)&d_W, (size_t)C * C * sizeof(float));
+  if (e == hipSuccess) e = hipMalloc((void**)&d_b, C * sizeof(float));
+  if (e == hipSuccess) e = hipMalloc((void**)&d_len, B * sizeof(int));
+  if (e == hipSuccess) e = hipMemcpy(d_h, h, nh * sizeof(float), hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = hipMemcpy(d_u, u, nz * sizeof(float), hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = hipMemcpy(d_W, W, (size_t)C * C * sizeof(float), hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = hipMemcpy(d_b, b, C * sizeof(float), hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = hipMemcpy(d_len, len32.data(), B * sizeof(int), hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = hipMemset(d_z, 0xff, nz * sizeof(float));  // NaN: an output the kernel does not write shows
+  if (e == hipSuccess) {
+    launch_mono_couple_on(nullptr, d_h, d_u, d_W, d_b, d_len, d_z, B, C, T, mode);
+    e = hipGetLastError();
+  }
+  if (e == hipSuccess) e = hipDeviceSynchronize();
+  if (e == hipSuccess) e = hipMemcpy(z, d_z, nz * sizeof(float), hipMemcpyDeviceToHost);
+  hipFree(d_h); hipFree(d_u); hipFree(d_z); hipFree(d_W); hipFree(d_b); hipFree(d_len);
+  if (e != hipSuccess) return fail(VITS_ERR_DEVICE, "mono couple: %s", hipGetErrorString(e));
+  return VITS_OK;
+}
 
 int vits_session_sync(vits_session* s) {
   if (!s) return fail(VITS_ERR_ARG, "null session");

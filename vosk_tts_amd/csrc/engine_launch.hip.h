@@ -665,6 +665,19 @@ static bool launch_plain_attention_on(hipStream_t st, const float* qkv, const in
   return true;
 }
 
+// The tail of a MonoTransformerFlowLayer (mono_couple_kernel, kernels_misc.hip.h): z = cat(x0 * s, (x1 - (W h + b)) * s * mask) from
+// h [B, C, T] and u [B, 2C, T]; mode 0: s = 1 (inter_residual), 1: s = 1/2 (post_residual).  Returns false for a width it is not built for.
+static bool launch_mono_couple_on(hipStream_t st, const float* h, const float* u, const float* W, const float* bias, const int* len, float* z,
+                                  int B, int C, int T, int mode) {
+  if (!mono_couple_c_ok(C)) return false;
+  dim3 grid(cdiv(T, 32), B);
+#define MONO_GO(N_) \
+  case N_: hipLaunchKernelGGL((mono_couple_kernel<N_>), grid, dim3(256), 0, st, h, u, W, bias, len, z, T, mode); break;
+  switch (C / 32) { MONO_GO(1) MONO_GO(2) MONO_GO(3) MONO_GO(4) MONO_GO(5) MONO_GO(6) }
+#undef MONO_GO
+  return true;
+}
+
 // one attention layer of encoder E: its own head count, relative-position window (W < 0: none) and width
 static void launch_attention(vits_session* s, const float* qkv, const EncoderW& E, const EncLayerW& L, const int* len, float* out, int B, int T) {
   if (E.W >= 0) {

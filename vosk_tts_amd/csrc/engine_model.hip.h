@@ -43,6 +43,12 @@ struct CouplingW {
   ConvW skip_post;
   int cond_off = 0;
 };
+// MonoTransformerFlowLayer (models.py:545-627; flow_type 4 / 5): the pre_conv Encoder geometry on the I/2 channels of x0, then
+// post = Conv1d(I/2, I/2, 1) in mono_couple_kernel (weight [I/2][I/2] and bias in their original order)
+struct MonoW {
+  EncoderW enc;
+  float *post_w = nullptr, *post_b = nullptr;
+};
 struct ResBlockW {
   ConvW c1[VITS_MAX_RESD], c2[VITS_MAX_RESD];
   int K = 0;
@@ -86,6 +92,7 @@ struct vits_model {
   float *ea_m = nullptr, *ea_logs = nullptr;
   float ea_m_h[2] = {0, 0}, ea_logs_h[2] = {0, 0};
   std::vector<CouplingW> flow;
+  std::vector<MonoW> mono;  // flow_type 4 / 5: mono[f] is flow.flows.{3f+2}, run BEFORE flow[f] in reverse
   ConvW conv_pre, conv_post;
   std::vector<UpW> ups;
   std::vector<ResBlockW> rb;
@@ -500,12 +507,16 @@ static int load_model(vits_model* m) {
       return fail(VITS_ERR_UNSUPPORTED, "deterministic duration predictor of %d filter channels (a multiple of %d up to %d)", D, CONV_CI_T, DPT_CG * DPT_MAXV);
   }
   if (hp.flow_dilation_rate != 1) return fail(VITS_ERR_UNSUPPORTED, "flow dilation_rate != 1");
-  if (hp.flow_type < 0 || hp.flow_type > 2)
-    return fail(VITS_ERR_UNSUPPORTED, "flow_type %d (0 = pre_conv2, 1 = pre_conv, 2 = plain ResidualCouplingLayer)", hp.flow_type);
+  const bool mono = hp.flow_type == 4 || hp.flow_type == 5;
+  if (hp.flow_type < 0 || (hp.flow_type > 2 && !mono))
+    return fail(VITS_ERR_UNSUPPORTED, "flow_type %d (0 = pre_conv2, 1 = pre_conv, 2 = plain ResidualCouplingLayer, 4 = mono_layer_inter_residual, "
+                "5 = mono_layer_post_residual; 3 is reserved for the fft flow, which is not served)", hp.flow_type);
   if (hp.flow_type == 0 && H / 2 != 32 && H / 2 != 64 && H / 2 != 96)  // pre_conv2: 2 heads on H channels
     return fail(VITS_ERR_UNSUPPORTED, "pre_conv2 flow: head dim hidden/2 = %d not in {32,64,96}", H / 2);
   if (hp.flow_type == 1 && (I % 4 || !plain_attention_dk_ok(I / 4)))  // pre_conv: 2 heads on I/2 channels
     return fail(VITS_ERR_UNSUPPORTED, "pre_conv flow: head dim inter_channels/4 = %d is not a multiple of 16 in [16, 96]", I / 4);
+  if (mono && (I % 4 || !plain_attention_dk_ok(I / 4)))  // MonoTransformerFlowLayer: 2 heads on I/2 channels
+    return fail(VITS_ERR_UNSUPPORTED, "mono_layer flow: head dim inter_channels/4 = %g is not a multiple of 16 in [16, 96]", I / 4.0);
   m->use_g = G > 0 && hp.n_speakers > 1;
 
   m->emb = upload(m, tget(m, 2, hp.n_vocab, H, -1, "enc_p.emb.weight"), (size_t)hp.n_vocab * H);
@@ -574,21 +585,25 @@ static int load_model(vits_model* m) {
 
   // ---- flow
   m->flow.resize(hp.flow_n_flows);
+  if (mono) m->mono.resize(hp.flow_n_flows);
   const int K5 = hp.flow_kernel_size, L = hp.flow_wn_layers;
   for (int f = 0; f < hp.flow_n_flows && !m->missing; ++f) {
     CouplingW& c = m->flow[f];
-    snprintf(nm, sizeof nm, "flow.flows.%d.pre", 2 * f);
+    // index of the coupling layer in flow.flows: [layer, Flip] per flow, or [ResidualCouplingLayer, Flip, MonoTransformerFlowLayer]
+    // (models.py:696-734)
+    const int fi = (mono ? 3 : 2) * f;
+    snprintf(nm, sizeof nm, "flow.flows.%d.pre", fi);
     c.pre = conv_from(m, nm, H, I / 2, 1, true);
-    snprintf(nm, sizeof nm, "flow.flows.%d.pre_transformer", 2 * f);
+    snprintf(nm, sizeof nm, "flow.flows.%d.pre_transformer", fi);
     // pre_conv2 (models.py:352-360): 1 layer on H channels, 2 heads whatever n_heads is (only the text encoder takes it), the Encoder's
     // default window like the text encoder's.  pre_conv (models.py:417-425): 2 layers on the I/2 channels of x0, 2 heads, FFN kernel 3
-    // with filter I/2, window_size=None.  plain: no pre-transformer.
+    // with filter I/2, window_size=None.  plain, and the coupling layer of a mono_layer_* flow: no pre-transformer.
     if (hp.flow_type == 0) load_encoder(m, c.enc, nm, 1, H, H, K5, 2, hp.window_size);
     else if (hp.flow_type == 1) load_encoder(m, c.enc, nm, 2, I / 2, I / 2, 3, 2, -1);
     for (int i = 0; i < L && !m->missing; ++i) {
       // in_layer rows permuted to [tanh 32 | sigmoid 32] per 32 channels for the fused gate epilogue
-      const float* w = tget(m, 3, 2 * H, H, K5, "flow.flows.%d.enc.in_layers.%d.weight", 2 * f, i);
-      const float* b = tget(m, 1, 2 * H, -1, -1, "flow.flows.%d.enc.in_layers.%d.bias", 2 * f, i);
+      const float* w = tget(m, 3, 2 * H, H, K5, "flow.flows.%d.enc.in_layers.%d.weight", fi, i);
+      const float* b = tget(m, 1, 2 * H, -1, -1, "flow.flows.%d.enc.in_layers.%d.bias", fi, i);
       if (m->missing) break;
       auto gate_src = [&](int r, int ci, int kk) {
         const int j = r / 64, q = r % 64;
@@ -601,13 +616,13 @@ static int load_model(vits_model* m) {
         return w[((size_t)orig * H + ci) * K5 + kk];
       }));
       if (hp.conv_precision == 1 && (2 * H) % 128 == 0) add_bf3_packing(m, c.in_layers.back(), gate_src);
-      snprintf(nm, sizeof nm, "flow.flows.%d.enc.res_skip_layers.%d", 2 * f, i);
+      snprintf(nm, sizeof nm, "flow.flows.%d.enc.res_skip_layers.%d", fi, i);
       c.rs_layers.push_back(conv_from(m, nm, i < L - 1 ? 2 * H : H, H, 1, true));
     }
     if (m->use_g)
-      c.cond_off = add_cond(tget(m, 3, 2 * H * L, G, 1, "flow.flows.%d.enc.cond_layer.weight", 2 * f),
-                            tget(m, 1, 2 * H * L, -1, -1, "flow.flows.%d.enc.cond_layer.bias", 2 * f), 2 * H * L);
-    snprintf(nm, sizeof nm, "flow.flows.%d.post", 2 * f);
+      c.cond_off = add_cond(tget(m, 3, 2 * H * L, G, 1, "flow.flows.%d.enc.cond_layer.weight", fi),
+                            tget(m, 1, 2 * H * L, -1, -1, "flow.flows.%d.enc.cond_layer.bias", fi), 2 * H * L);
+    snprintf(nm, sizeof nm, "flow.flows.%d.post", fi);
     c.post = conv_from(m, nm, I / 2, H, 1, true);
     if (!m->missing) {
       const float* pw = tget(m, 3, I / 2, H, 1, "%s.weight", nm);
@@ -615,8 +630,8 @@ static int load_model(vits_model* m) {
       std::vector<const float*> rw(L), rb(L);
       for (int i = 0; i < L; ++i) {
         const int rows = i < L - 1 ? 2 * H : H;
-        rw[i] = tget(m, 3, rows, H, 1, "flow.flows.%d.enc.res_skip_layers.%d.weight", 2 * f, i);
-        rb[i] = tget(m, 1, rows, -1, -1, "flow.flows.%d.enc.res_skip_layers.%d.bias", 2 * f, i);
+        rw[i] = tget(m, 3, rows, H, 1, "flow.flows.%d.enc.res_skip_layers.%d.weight", fi, i);
+        rb[i] = tget(m, 1, rows, -1, -1, "flow.flows.%d.enc.res_skip_layers.%d.bias", fi, i);
       }
       if (!m->missing) {
         for (int i = 0; i < L - 1; ++i) {  // residual half: rows [0, H)
@@ -644,6 +659,14 @@ static int load_model(vits_model* m) {
         for (int o = 0; o < half; ++o) bff[o] = (float)bf[o];
         c.skip_post = make_conv(m, half, L * H, 1, bff.data(), [&](int r, int ci, int) { return (float)Wf[(size_t)r * L * H + ci]; });
       }
+    }
+    if (mono && !m->missing) {
+      MonoW& mo = m->mono[f];
+      const int half = I / 2;
+      snprintf(nm, sizeof nm, "flow.flows.%d.pre_transformer", fi + 2);
+      load_encoder(m, mo.enc, nm, 2, half, half, 3, 2, -1);
+      mo.post_w = upload(m, tget(m, 3, half, half, 1, "flow.flows.%d.post.weight", fi + 2), (size_t)half * half);
+      mo.post_b = upload(m, tget(m, 1, half, -1, -1, "flow.flows.%d.post.bias", fi + 2), half);
     }
   }
   if (m->use_g && hp.dec_type == 1)  // Generator.cond (models.py:869-870, 873-875)

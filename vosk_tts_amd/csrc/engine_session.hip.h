@@ -214,7 +214,8 @@ static void plan(vits_session* s, int B, int Tx, int Ty) {
   const size_t Fm = F > H ? F : H;
   const size_t Tm = (size_t)(Tx > Ty ? Tx : Ty);
   // width of the encoder-shaped scratch: the pre_conv flow's pre-transformer runs on I/2 channels (engine_stages.hip.h run_flow)
-  const size_t He = hp.flow_type == 1 && I / 2 > H ? I / 2 : H;
+  // (and the mono_layer_* flows' MonoTransformerFlowLayer, flow_type 4 / 5, has the same encoder)
+  const size_t He = (hp.flow_type == 1 || hp.flow_type == 4 || hp.flow_type == 5) && I / 2 > H ? I / 2 : H;
   s->arena_used = 0;
   s->B = B; s->Tx = Tx; s->Ty = Ty;
   s->len_x = bump<int>(s, B); s->len_y = bump<int>(s, B); s->len_rag = bump<int>(s, B + 1); s->len_tail = bump<int>(s, B);

@@ -371,6 +371,11 @@ static void run_expand(vits_session* s, const float* d_noise, long long noise_st
 // ---- a12-a14: ResidualCouplingTransformersBlock.forward(reverse=True) (models.py:750-757).
 // z in s->zA; result pointer returned (zA or zB).  Each Flip is folded into the next layer's
 // channel-reversed read (pre conv) and the EPI_COUPLE write.
+// Channel layout: zA / zB always hold z in the reference's own channel order.  A coupling layer reads its input through the Flip that
+// precedes it in reverse (x0[c] = u[I-1-c], x1[c] = u[half-1-c]) and EPI_COUPLE writes cat(x0, x1') unreversed.  In a mono_layer_*
+// flow (flow_type 4 / 5; [ResidualCouplingLayer, Flip, MonoTransformerFlowLayer] per flow, models.py:696-734) reverse runs Mono_f,
+// Flip, RCL_f: the mono layer follows the previous flow's coupling layer with NO Flip between them, so it reads u and writes its
+// result unreversed (x0 = rows [0, half)), and the one Flip of the flow is the reversed read the coupling layer does anyway.
 static float* run_flow(vits_session* s, int B, int Ty) {
   vits_model* m = s->m;
   const vits_hparams& hp = m->hp;
@@ -381,9 +386,26 @@ static float* run_flow(vits_session* s, int B, int Ty) {
   }
   float* u = s->zA;
   float* v = s->zB;
+  const bool mono = hp.flow_type == 4 || hp.flow_type == 5;
   for (int f = hp.flow_n_flows - 1; f >= 0; --f) {
     const CouplingW& C = m->flow[f];
     ConvParams P;
+    if (mono) {
+      // MonoTransformerFlowLayer reverse, mean_only (models.py:595-627), x0 = u[0:half], x1 = u[half:I]:
+      //   inter_residual (4): h = pre_transformer(x0 * mask) + x0 ;     z = cat(x0,     (x1 - post(h) * mask) * mask)
+      //   post_residual  (5): h = pre_transformer(x0 / 2)  (masks it) ; z = cat(x0 / 2, (x1 - post(h) * mask) / 2 * mask)
+      // 3 + the encoder's launches: x0 staging, the 2-layer encoder, mono_couple_kernel (post + coupling + both halves of z).
+      const MonoW& Mo = m->mono[f];
+      const bool post_res = hp.flow_type == 5;
+      hipLaunchKernelGGL(mono_x0_kernel, dim3(cdiv(Ty, 256), half, B), dim3(256), 0, s->stream, u, s->x, s->fh, s->len_y, I, half, Ty,
+                         post_res ? 0.5f : 1.0f);
+      run_encoder(s, Mo.enc, s->x, s->len_y, B, Ty, -1, -1, post_res ? nullptr : s->fh, s->fskip);
+      {
+        ProfScope ps(s, "flow.mono_couple", 2.0 * B * half * half * Ty, "mono_couple_kernel");
+        launch_mono_couple_on(s->stream, s->fskip, u, Mo.post_w, Mo.post_b, s->len_y, v, B, half, Ty, post_res ? 1 : 0);
+      }
+      float* t = u; u = v; v = t;
+    }
     if (hp.flow_type == 1) {
       // pre_conv (models.py:460-462): x0_ = pre_transformer(x0 * mask) + x0 ; h = pre(x0_) * mask, x0[c] = u[I-1-c]
       hipLaunchKernelGGL(flow_x0_kernel, dim3(cdiv(Ty, 256), half, B), dim3(256), 0, s->stream, u, s->x, s->fh, s->len_y, I, half, Ty);

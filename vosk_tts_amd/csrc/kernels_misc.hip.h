@@ -1872,6 +1872,105 @@ __global__ void __launch_bounds__(NW * 64) plain_attention16_kernel(const float*
   }
 }
 
+// ----------------------------------------------------------------------------- MonoTransformerFlowLayer (mono_layer_* flows)
+// x0 of a MonoTransformerFlowLayer (models.py:545-627; flow_type 4 / 5): the layer follows the previous coupling layer with no Flip
+// in between, so x0 is rows [0, C) of u as they lie; x = x2 = x0 * scale on valid frames, 0 beyond len[b] (x: the pre-transformer's
+// in-place input, x2: its residual base).  scale 1 for inter_residual, 1/2 for post_residual (x0 / 2, models.py:597).
+__global__ void mono_x0_kernel(const float* u, float* x, float* x2, const int* len, int I, int C, int T, float scale) {
+  const int t = blockIdx.x * 256 + threadIdx.x, c = blockIdx.y, b = blockIdx.z;
+  if (t >= T) return;
+  const float v = t < len[b] ? u[((long long)b * I + c) * T + t] * scale : 0.f;
+  const long long o = ((long long)b * C + c) * T + t;
+  x[o] = v;
+  x2[o] = v;
+}
+
+// The tail of a MonoTransformerFlowLayer in reverse with mean_only (models.py:600-607, 613-627) as ONE launch: the 1x1 conv
+// m = W h + b over the C = inter_channels / 2 rows of the pre-transformer's output h, the mask, the coupling and both halves of the
+// new z (in place of a conv launch into a scratch buffer plus an elementwise pass over z):
+//   z[C + r] = (u[C + r] - m[r]) * s   on columns < len[b], exactly 0 beyond
+//   z[r]     =  u[r] * s               (x0 passed on, unmasked as in the reference)
+// s = 1 (mode 0, inter_residual) or 1/2 (mode 1, post_residual: 1 + exp(-logs) = 2 with logs = 0, and x0 / 2).
+// h [B, C, T], u / z [B, 2C, T], W [C][C] row-major (the Conv1d weight as stored), C = 32 * NRT with NRT 1..6.
+// A workgroup owns 32 columns of one item; wave (wr, wc) computes rows [wr * C/2, (wr + 1) * C/2) of columns 16 wc .. 16 wc + 15 on
+// v_mfma_f32_16x16x4_f32 (A = W[row][k] from LDS, B = h[k][col] straight from global: a lane reads 16 consecutive columns of a row
+// with its 15 neighbours, every element once per wave).  W is streamed through LDS in chunks of 32 k: [C][36] floats (stride 36:
+// the A fragment's 64 lanes read 16 rows x 4 k with two lanes per bank, the minimum; <= 27 KiB), the next chunk of W and of h is in
+// flight in registers while the current one is multiplied.  Columns are independent (kernel size 1), so what h holds beyond len[b]
+// never reaches a value that is kept; a tile wholly beyond len[b] skips the product.
+#define MONO_KC 32
+#define MONO_WS 36
+template <int NRT>
+__global__ void __launch_bounds__(256) mono_couple_kernel(const float* __restrict__ h, const float* __restrict__ u, const float* __restrict__ W,
+                                                           const float* __restrict__ bias, const int* __restrict__ len, float* __restrict__ z,
+                                                           int T, int mode) {
+  constexpr int C = 32 * NRT, NKC = C / MONO_KC;
+  __shared__ __attribute__((aligned(16))) float wl[C * MONO_WS];
+  const int lane = threadIdx.x & 63, g = lane >> 4, l15 = lane & 15;
+  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int wr = wave >> 1, wc = wave & 1;
+  const int b = blockIdx.y, c0 = blockIdx.x * 32;
+  const int L = len[b] < T ? len[b] : T;
+  const int col = c0 + wc * 16 + l15;
+  const int colc = col < T ? col : T - 1;
+  const float sc = mode ? 0.5f : 1.0f;
+  const float* ub = u + (long long)b * 2 * C * T;
+  float* zb = z + (long long)b * 2 * C * T;
+  const int row0 = wr * (C / 2);
+
+  f32x4 acc[NRT];
+#pragma unroll
+  for (int rt = 0; rt < NRT; ++rt) acc[rt] = (f32x4){0.f, 0.f, 0.f, 0.f};
+
+  if (c0 < L) {  // (uniform over the workgroup: the barriers below are reached by all of it or by none)
+    const float* hb = h + (long long)b * C * T + colc;
+    f32x4 wreg[NRT];  // this thread's share of a W chunk: row (i * 256 + tid) / 8, k quad (i * 256 + tid) % 8
+    float hreg[MONO_KC / 4];
+    auto load_chunk = [&](int kc) {
+#pragma unroll
+      for (int i = 0; i < NRT; ++i) {
+        const int idx = i * 256 + threadIdx.x;
+        wreg[i] = *reinterpret_cast<const f32x4*>(W + (long long)(idx >> 3) * C + kc * MONO_KC + (idx & 7) * 4);
+      }
+#pragma unroll
+      for (int s = 0; s < MONO_KC / 4; ++s) hreg[s] = hb[(long long)(kc * MONO_KC + 4 * s + g) * T];
+    };
+    load_chunk(0);
+    for (int kc = 0; kc < NKC; ++kc) {
+      if (kc) __syncthreads();  // every wave is done with the previous chunk
+#pragma unroll
+      for (int i = 0; i < NRT; ++i) {
+        const int idx = i * 256 + threadIdx.x;
+        *reinterpret_cast<f32x4*>(&wl[(idx >> 3) * MONO_WS + (idx & 7) * 4]) = wreg[i];
+      }
+      float hcur[MONO_KC / 4];
+#pragma unroll
+      for (int s = 0; s < MONO_KC / 4; ++s) hcur[s] = hreg[s];
+      __syncthreads();
+      if (kc + 1 < NKC) load_chunk(kc + 1);
+#pragma unroll
+      for (int s = 0; s < MONO_KC / 4; ++s)
+#pragma unroll
+        for (int rt = 0; rt < NRT; ++rt)
+          acc[rt] = __builtin_amdgcn_mfma_f32_16x16x4f32(wl[(row0 + rt * 16 + l15) * MONO_WS + 4 * s + g], hcur[s], acc[rt], 0, 0, 0);
+    }
+  }
+  if (col >= T) return;
+  const bool valid = col < L;
+#pragma unroll
+  for (int rt = 0; rt < NRT; ++rt)
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      const int r = row0 + rt * 16 + 4 * g + e;  // accumulator register e of lane (g, l15): row 4 g + e, column l15
+      const float x0 = ub[(long long)r * T + col];
+      const float x1 = ub[(long long)(C + r) * T + col];
+      zb[(long long)r * T + col] = x0 * sc;
+      zb[(long long)(C + r) * T + col] = valid ? (x1 - (acc[rt][e] + bias[r])) * sc : 0.f;
+    }
+}
+// widths the kernel is instantiated for (engine_launch.hip.h launch_mono_couple_on): C = inter_channels / 2 = 2 heads of 16 .. 96
+static inline bool mono_couple_c_ok(int C) { return C % 32 == 0 && C >= 32 && C <= 192; }
+
 // ---- shader clock under load (vits_debug_clock_probe, include/vits_mi355_debug.h): one wave per workgroup sleeps on its CU for
 // `ticks` of the constant 100 MHz clock and reports shader-clock cycles per wall nanosecond over that interval.  s_memtime counts the
 // shader clock of the CU's XCD whether or not this wave is issuing, so the figure is the clock the kernels running NEXT to the probe

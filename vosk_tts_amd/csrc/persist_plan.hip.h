@@ -95,7 +95,7 @@ static size_t persist_enc_cells(const vits_model* m, int B, int Tx) {
 // ---- flow (ResidualCouplingTransformersBlock reverse, folded WaveNet tail)
 static bool persist_flow_eligible(const vits_model* m, int B, int Ty) {
   const vits_hparams& hp = m->hp;
-  if (hp.flow_type != 0) return false;  // pre_conv (1) and plain (2) coupling layers: the launch path (run_flow) only
+  if (hp.flow_type != 0) return false;  // pre_conv (1), plain (2) and mono_layer_* (4, 5) flows: the launch path (run_flow) only
   if (!persist_common_ok(m, B, Ty) || hp.flow_n_flows < 1) return false;
   const int I = hp.inter_channels, H = hp.hidden_channels, L = hp.flow_wn_layers;
   if (I % 32 || I > PS_MAXC || L < 1 || L > 4 || H % 16 || H > PS_MAXC || (I / 2) % 16) return false;

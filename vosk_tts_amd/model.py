@@ -89,7 +89,9 @@ class Model:
                     raise NotImplementedError("model.onnx has no embedded vocoder: a mel-only export cannot produce audio")
                 self.onnx = SttsSession(S.pack_blob(hp, tensors), W.pack_blob(*voc), device=device)
             else:
-                hp, tensors = oi.import_onnx(str(model_path / "model.onnx"), cfg)
+                # (no training config in the directory: None, so that a mono_layer_* graph, whose kind only the config names, is
+                # refused with the keys it needs instead of being guessed at)
+                hp, tensors = oi.import_onnx(str(model_path / "model.onnx"), cfg or None)
                 blob = W.pack_blob(hp, tensors)
         else:
             raise FileNotFoundError(f"neither {blob_path} nor model.onnx found in {model_path}")

@@ -278,10 +278,15 @@ def read_initializers(path_or_bytes):
 # ---------------------------------------------------------------------------------------------------
 
 
-# ResidualCouplingTransformersBlock (models.py:630-762) builds one of these coupling-layer families; the engine serves the first three
-# (hparams.flow_type).  The mono_layer_* and fft flows cannot be exported by the reference's onnx_export.py (their
-# remove_weight_norm call fails on a layer that has none), so a graph of theirs is named, not guessed at.
-FLOW_TYPES = {"pre_conv2": 0, "pre_conv": 1, "plain": 2}
+# ResidualCouplingTransformersBlock (models.py:630-762) builds one of five coupling-layer families; the engine serves all but `fft`
+# (hparams.flow_type; 3 is reserved for it).  The two mono_layer_* flows hold [ResidualCouplingLayer, Flip, MonoTransformerFlowLayer]
+# per flow (weights at flow.flows.{3f} and {3f+2}); their reverse runs, for f = n_flows-1 .. 0: Mono_f, Flip, RCL_f -- one Flip per
+# flow, between the mono layer and the coupling layer.  They have the same tensors, so only the training config tells them apart
+# (flow_kind_from_config).  Neither they, the plain flow nor fft can be exported by the reference's onnx_export.py as written (its
+# remove_weight_norm call fails on a layer that has none); an export that removes the weight norm of each WN directly imports.  On
+# the engine a mono layer costs the pre_conv pre-transformer's launches plus two: its x0 staging and mono_couple_kernel.
+FLOW_TYPES = {"pre_conv2": 0, "pre_conv": 1, "plain": 2, "mono_layer_inter_residual": 4, "mono_layer_post_residual": 5}
+_MONO = "mono_layer_*"  # what the tensors alone show of flow_type 4 / 5
 
 
 def flow_kind_from_config(model_cfg):
@@ -296,14 +301,47 @@ def flow_kind_from_config(model_cfg):
     return "mono_layer_post_residual" if kind == "mono_layer_post_residual" else "plain"
 
 
+def _mono_layer_tensors(idx, half):
+    """name -> shape of the MonoTransformerFlowLayer at flow.flows.{idx} (models.py:545-627)."""
+    p = f"flow.flows.{idx}"
+    out = {}
+    for i in range(2):
+        for n in ("conv_q", "conv_k", "conv_v", "conv_o"):
+            out[f"{p}.pre_transformer.attn_layers.{i}.{n}.weight"] = (half, half, 1)
+            out[f"{p}.pre_transformer.attn_layers.{i}.{n}.bias"] = (half,)
+        for n in ("norm_layers_1", "norm_layers_2"):
+            out[f"{p}.pre_transformer.{n}.{i}.gamma"] = (half,)
+            out[f"{p}.pre_transformer.{n}.{i}.beta"] = (half,)
+        for n in ("conv_1", "conv_2"):
+            out[f"{p}.pre_transformer.ffn_layers.{i}.{n}.weight"] = (half, half, 3)
+            out[f"{p}.pre_transformer.ffn_layers.{i}.{n}.bias"] = (half,)
+    out[f"{p}.post.weight"] = (half, half, 1)
+    out[f"{p}.post.bias"] = (half,)
+    return out
+
+
 def _infer_flow_type(t, inter_channels):
-    """flow_type from the flow's tensors: flows.0.pre_transformer present or not, its width and whether it has relative positions."""
+    """flow_type from the flow's tensors: flows.0.pre_transformer present or not, its width and whether it has relative positions;
+    a mono_layer_* graph (mono layers at flows.2, 5, ...) gives None: its two kinds have the same tensors (import_onnx decides)."""
     if any(k.startswith("flow.flows.0.enc.self_attn_layers.") for k in t):
         raise NotImplementedError("flow type 'fft' (FFTransformerCouplingLayer, models.py:486-542: flow.flows.*.enc.self_attn_layers) is not "
-                                  "supported; pre_conv2, pre_conv and the plain ResidualCouplingLayer flows are")
+                                  "supported; pre_conv2, pre_conv, the plain ResidualCouplingLayer and the mono_layer_* flows are")
     if any(k.startswith("flow.flows.2.pre_transformer.") for k in t) and "flow.flows.2.pre.weight" not in t:
-        raise NotImplementedError("flow type 'mono_layer_*' (MonoTransformerFlowLayer, models.py:545-627, at flow.flows.2, 5, ...) is not "
-                                  "supported; pre_conv2, pre_conv and the plain ResidualCouplingLayer flows are")
+        # coupling layers at 0, 3, ...: every one is followed by a complete mono layer of width inter_channels / 2
+        half = inter_channels // 2
+        rcl = sorted({int(k.split(".")[2]) for k in t if k.startswith("flow.flows.") and k.endswith(".pre.weight")})
+        if rcl != [3 * f for f in range(len(rcl))]:
+            raise NotImplementedError(f"flow type 'mono_layer_*' (MonoTransformerFlowLayer, models.py:545-627): coupling layers at flow.flows "
+                                      f"{rcl}, expected 0, 3, 6, ...")
+        for f in rcl:
+            for name, shape in _mono_layer_tensors(f + 2, half).items():
+                if name not in t:
+                    raise NotImplementedError(f"flow type 'mono_layer_*' (MonoTransformerFlowLayer, models.py:545-627, at flow.flows.2, 5, "
+                                              f"...) is incomplete: initializer {name!r} not found")
+                if tuple(t[name].shape) != shape:
+                    raise NotImplementedError(f"flow type 'mono_layer_*': {name} has shape {tuple(t[name].shape)}, expected {shape} "
+                                              f"(the mono layer runs on inter_channels/2 = {half} channels)")
+        return None
     q = t.get("flow.flows.0.pre_transformer.attn_layers.0.conv_q.weight")
     if q is None:
         if any(k.startswith("flow.flows.0.pre_transformer.") for k in t):
@@ -343,7 +381,8 @@ def _deterministic_dp(t):
 
 
 def infer_hparams(t):
-    """Hyper-parameters from tensor shapes (training/vits2/models.py:1503-1630 constructor wiring)."""
+    """Hyper-parameters from tensor shapes (training/vits2/models.py:1503-1630 constructor wiring).  flow_type is None for a
+    mono_layer_* graph (-1 in the struct): the tensors do not tell its two kinds apart."""
     def need(name):
         if name not in t:
             raise KeyError(name)
@@ -383,10 +422,11 @@ def infer_hparams(t):
             hp.dp_n_flows = (max(cf) + 1) // 2 if cf else 4
             hp.dp_num_bins = (need(f"dp.flows.{max(cf)}.proj.weight").shape[0] + 1) // 3
         fl = sorted({int(k.split(".")[2]) for k in t if k.startswith("flow.flows.") and k.endswith(".pre.weight")})
-        hp.flow_n_flows = len(fl)
+        hp.flow_n_flows = len(fl)  # the coupling layers (every family has one `pre` per flow), whatever else sits between them
         hp.flow_wn_layers = sum(1 for k in t if k.startswith("flow.flows.0.enc.in_layers.") and k.endswith(".weight"))
         hp.flow_kernel_size = need("flow.flows.0.enc.in_layers.0.weight").shape[2]
-        hp.flow_type = _infer_flow_type(t, hp.inter_channels)
+        flow_type = _infer_flow_type(t, hp.inter_channels)
+        hp.flow_type = -1 if flow_type is None else flow_type  # -1: mono_layer_*, import_onnx takes the kind from the config
         hp.dec_initial_channel = need("dec.conv_pre.weight").shape[0]
         ups = sorted({int(k.split(".")[2]) for k in t if k.startswith("dec.ups.") and k.endswith(".weight")})
         hp.n_ups = len(ups)
@@ -431,10 +471,12 @@ def import_onnx(path_or_bytes, config=None):  # noqa: C901
     "resblock_dilation_sizes", "gen_istft_hop_size", "subbands", "sampling_rate", "hop_length"
     (keys of training/vits2/configs/*.json "model"/"data").  "use_transformer_flows" / "transformer_flow_type", when
     present, must select the flow the tensors show (flow_kind_from_config), and "use_sdp" the duration predictor; a contradiction
-    raises ValueError."""
+    raises ValueError.  A mono_layer_* graph needs a config: its two kinds have the same tensors (absent keys select
+    mono_layer_post_residual, as in the reference; config=None raises ValueError)."""
     g = OnnxGraph(path_or_bytes)
     t = g.tensors()
     hp = infer_hparams(t)
+    no_config = config is None
     config = config or {}
     # BERT-conditioned flavours (vosk_tts/synth.py:88-99): their text encoder is not in the reference tree, so the extra tensors are
     # found by name and shape -- a [hidden, D(, 1)] weight with "bert" in its name and a [hidden] bias next to it -- and mapped onto
@@ -488,7 +530,18 @@ def import_onnx(path_or_bytes, config=None):  # noqa: C901
             continue  # the synthesis filter's shape (2) or the single band (3) decides; a training config carries "subbands" either way
         if key in config:
             setattr(hp, field, int(config[key]))
-    if "use_transformer_flows" in config or "transformer_flow_type" in config:
+    if hp.flow_type < 0:  # mono_layer_*: inter_residual and post_residual have the same tensors, the training config names the one
+        if no_config:
+            raise ValueError("the graph's flow tensors are those of a mono_layer_* flow, whose two kinds (mono_layer_inter_residual, "
+                             "mono_layer_post_residual) have the same tensors: pass the training config's \"use_transformer_flows\" / "
+                             "\"transformer_flow_type\" (a config without them selects mono_layer_post_residual, as in the reference)")
+        kind = flow_kind_from_config(config)
+        if not kind.startswith("mono_layer_"):
+            raise ValueError(f"config selects the {kind!r} flow (use_transformer_flows {config.get('use_transformer_flows', False)}, "
+                             f"transformer_flow_type {config.get('transformer_flow_type', 'mono_layer_post_residual')!r}) but the graph's "
+                             f"flow tensors are those of {_MONO!r}")
+        hp.flow_type = FLOW_TYPES[kind]
+    elif "use_transformer_flows" in config or "transformer_flow_type" in config:
         kind = flow_kind_from_config(config)
         if FLOW_TYPES.get(kind) != hp.flow_type:
             have = next(k for k, v in FLOW_TYPES.items() if v == hp.flow_type)

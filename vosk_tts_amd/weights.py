@@ -69,7 +69,9 @@ class HParams(ctypes.Structure):
         ("hop_length", ctypes.c_int32),
         ("bert_dim", ctypes.c_int32),
         ("conv_precision", ctypes.c_int32),  # 0 fp32 (default), 1 split-bf16 decoder ResBlock convs at batch size ("bf16x3")
-        ("flow_type", ctypes.c_int32),  # 0 pre_conv2 (default), 1 pre_conv, 2 plain ResidualCouplingLayer (include/vits_mi355.h)
+        # 0 pre_conv2 (default), 1 pre_conv, 2 plain ResidualCouplingLayer, 3 reserved (fft, refused), 4 mono_layer_inter_residual,
+        # 5 mono_layer_post_residual (include/vits_mi355.h)
+        ("flow_type", ctypes.c_int32),
         ("reserved", ctypes.c_int32 * 5),
     ]
 
@@ -256,6 +258,39 @@ def tiny_plain_flow_hparams(n_vocab=20):
     return hp
 
 
+MONO_FLOW_TYPES = (4, 5)  # mono_layer_inter_residual, mono_layer_post_residual (3 is reserved for the fft flow)
+
+
+def mono_inter_hparams(n_vocab=62):
+    """Default-size graph with the `mono_layer_inter_residual` flow (flow_type 4, models.py:696-714): per flow a plain
+    ResidualCouplingLayer at flow.flows.{3f}, a Flip, and a MonoTransformerFlowLayer (models.py:545-627) at flow.flows.{3f+2} whose
+    2-layer, 2-head pre-transformer runs on the inter_channels/2 = 96 channels of x0 (head dim 48) and adds x0 back before `post`."""
+    hp = default_hparams(n_vocab)
+    hp.flow_type = 4
+    return hp
+
+
+def tiny_mono_inter_hparams(n_vocab=20):
+    hp = tiny_hparams(n_vocab)
+    hp.flow_type = 4
+    return hp
+
+
+def mono_post_hparams(n_vocab=62):
+    """Default-size graph with the `mono_layer_post_residual` flow (flow_type 5, models.py:715-734): what SynthesizerTrn builds
+    when a config says nothing about flows.  The tensors of flow_type 4; the mono layer halves both halves of z instead of adding
+    x0 to the pre-transformer's output (residual_connection=True, models.py:595-608)."""
+    hp = default_hparams(n_vocab)
+    hp.flow_type = 5
+    return hp
+
+
+def tiny_mono_post_hparams(n_vocab=20):
+    hp = tiny_hparams(n_vocab)
+    hp.flow_type = 5
+    return hp
+
+
 def deterministic_dp_hparams(n_vocab=62):
     """Default-size graph with the deterministic `DurationPredictor` (use_sdp false, models.py:104-139, 1624-1627):
     conv_1 / norm_1 / conv_2 / norm_2 / proj at dp_filter_channels 256, kernel 3.  dp_n_flows == 0 selects it: the reference
@@ -436,8 +471,12 @@ def tensor_specs(hp):
     # flow (models.py:329-483, 630-762, modules.py:298-345); only even indices carry weights.  flow_type 1 (pre_conv): the
     # pre-transformer is a 2-layer, 2-head Encoder on the I/2 channels of x0 with FFN kernel 3 and no relative positions
     # (models.py:417-425); its post_transformer (:436-444) is never run and not part of the export.  flow_type 2: no transformer.
+    # flow_type 4 / 5 (mono_layer_*, models.py:696-734): [ResidualCouplingLayer, Flip, MonoTransformerFlowLayer] per flow, so the plain
+    # coupling layer sits at index 3f and the mono layer (models.py:545-627: the pre_conv Encoder geometry, then post = Conv1d(I/2, I/2, 1),
+    # mean_only, no speaker conditioning) at 3f + 2.  The reference zero-initialises that post; the synthetic one is not zero.
+    mono = hp.flow_type in MONO_FLOW_TYPES
     for f in range(hp.flow_n_flows):
-        p = f"flow.flows.{2 * f}"
+        p = f"flow.flows.{(3 if mono else 2) * f}"
         if hp.flow_type == 1:
             encoder(p + ".pre_transformer", 2, I // 2, 3, C=I // 2, rel=False)
         conv(p + ".pre", H, I // 2, 1)
@@ -451,6 +490,10 @@ def tensor_specs(hp):
         if G > 0:
             conv(p + ".enc.cond_layer", 2 * H * hp.flow_wn_layers, G, 1)
         conv(p + ".post", I // 2, H, 1, gain=0.5)
+        if mono:
+            p = f"flow.flows.{3 * f + 2}"
+            encoder(p + ".pre_transformer", 2, I // 2, 3, C=I // 2, rel=False, nh=2)
+            conv(p + ".post", I // 2, I // 2, 1, gain=0.5)
 
     D = hp.dp_filter_channels
     if hp.dp_n_flows == 0:
@@ -594,10 +637,14 @@ def validate_hparams(hp):
             raise ValueError(f"decoder tail geometry (subbands {hp.subbands}, n_fft {hp.istft_n_fft}, hop {hp.istft_hop}, taps {hp.pqmf_taps}) "
                              f"needs {lds} bytes of LDS > 65536")
         rate *= hp.istft_hop * hp.subbands
-    if hp.flow_type not in (0, 1, 2):
-        raise ValueError(f"flow_type {hp.flow_type}: 0 = pre_conv2, 1 = pre_conv, 2 = plain ResidualCouplingLayer")
+    if hp.flow_type not in (0, 1, 2) + MONO_FLOW_TYPES:
+        raise ValueError(f"flow_type {hp.flow_type}: 0 = pre_conv2, 1 = pre_conv, 2 = plain ResidualCouplingLayer, "
+                         "4 = mono_layer_inter_residual, 5 = mono_layer_post_residual (3 is reserved for the fft flow, which is not served)")
     if hp.flow_type == 1 and hp.n_vocab > 0 and not (hp.inter_channels % 4 == 0 and (hp.inter_channels // 4) in PRE_CONV_HEAD_DIMS):
         raise ValueError(f"pre_conv flow with inter_channels {hp.inter_channels}: head dim inter_channels/4 must be one of {PRE_CONV_HEAD_DIMS}")
+    if hp.flow_type in MONO_FLOW_TYPES and hp.n_vocab > 0 and not (hp.inter_channels % 4 == 0 and (hp.inter_channels // 4) in PRE_CONV_HEAD_DIMS):
+        raise ValueError(f"mono_layer flow with inter_channels {hp.inter_channels}: head dim inter_channels/4 = {hp.inter_channels / 4:g} "
+                         f"must be one of {PRE_CONV_HEAD_DIMS}")
     if hp.n_vocab > 0 and hp.dp_n_flows == 0:  # deterministic duration predictor (use_sdp false)
         if hp.dp_dds_layers or hp.dp_num_bins:
             raise ValueError(f"deterministic duration predictor (dp_n_flows 0) with dp_dds_layers {hp.dp_dds_layers} / dp_num_bins "
