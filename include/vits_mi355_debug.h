@@ -70,6 +70,9 @@ int vits_debug_rag_halo(const vits_hparams* hp);
  * "conv_mfma_kernel<2,2,2,2"): lets a test assert which kernel a launch took, not only what it computed. */
 void vits_debug_launch_log(int on);
 int vits_debug_launch_count(const char* op, const char* kernel_prefix);
+/* Test hook: every "op|kernel count" line of the launch log, sorted by key, into buf (NUL-terminated; lines that do not fit are
+ * dropped).  Returns the number of lines written, negative on bad arguments. */
+int vits_debug_launch_dump(char* buf, size_t cap);
 /* Test hook: software-pipelined 64 x 64 conv kernel (conv_sp_kernel, csrc/conv_sp.hip.h): -1 = default (by grid size),
  * 0 = never, 1 = by grid size, 2 = wherever a launch is eligible for it. */
 void vits_debug_conv_sp(int mode);

@@ -95,7 +95,7 @@ def test_dense_on_every_kernel(hip_lib, row):
         model.close()
 
 
-BIG_TILE = "conv_mfma_kernel<2,2,2,2"  # the 128 x 128 fp32 tile (engine_launch.hip.h)
+BIG_TILE = "conv_mfma_kernel<2,2,2,2"  # the 128 x 128 fp32 tile (plan_conv, engine_convplan.hip.h)
 # (row, B, T_y, upsampler launches that must take the 128 x 128 tile).  A polyphase launch has M = u * C_out rows and T input positions as
 # columns; the dispatch takes the big tile when C_out % 128 == 0 and cdiv(M, 128) * cdiv(T, 128) * B >= 512.  Sized from that rule so that
 # the "tile inside one phase" indexing (tap_base = ups_shift[m0 / C_out]) runs at rates 5, 6, 3, 7 and 8, several taps and one tap per phase:
@@ -240,7 +240,7 @@ def test_streaming_chunks_below_and_above_the_reach(hip_lib, name):
 
 # ------------------------------------------------------------------------------------------------ split-bf16 ResBlock convs
 # (row, B, T_y, polyphase launches that must take the split-bf16 kernel).  The kernel is taken by tile count as well as by channels
-# (engine_launch.hip.h: 512 tiles of 128 x 128, or 256 of 64 x 128 for other multiples of 64 rows), and a polyphase launch only when
+# (engine_convplan.hip.h: 512 tiles of 128 x 128, or 256 of 64 x 128 for other multiples of 64 rows), and a polyphase launch only when
 # C_out % 128 == 0 and its input is one tensor (stage 0, or a later stage of a one-chain decoder), so sizes follow the rows:
 # rates 4, 6, 5, 7, 8, 2 at the first stage; is_3stage_d4's (2,2) first stage is too small at this size (ResBlocks only).
 BF3_ROWS = (("mb_default", 16, 400, 1), ("ms_u6_u5", 16, 400, 1), ("is_u5_u6", 16, 400, 1), ("ms_u7_2x8", 24, 400, 1), ("hg_v1", 8, 120, 1),

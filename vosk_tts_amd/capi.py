@@ -199,6 +199,12 @@ class VitsLib:
         """vits_debug_launch_count: launches of operation `op` counted so far whose kernel name starts with `kernel_prefix`"""
         return int(self._fn("debug_launch_count")(op.encode(), kernel_prefix.encode()))
 
+    def launch_dump(self):
+        """vits_debug_launch_dump: the whole launch log as {"op|kernel": count}"""
+        buf = ctypes.create_string_buffer(1 << 16)
+        self._fn("debug_launch_dump")(buf, ctypes.c_size_t(len(buf)))
+        return {k: int(n) for k, n in (line.rsplit(" ", 1) for line in buf.value.decode().splitlines())}
+
     def mas_maximum_path(self, values, t_ys, t_xs, device=0):
         """monotonic_align.maximum_path_c (core.pyx:35-42): values float32 [B,T_y,T_x] -> paths int32 [B,T_y,T_x]."""
         values = _f32(values)

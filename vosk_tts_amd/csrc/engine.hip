@@ -63,8 +63,7 @@ static inline int cdiv(int a, int b) { return (a + b - 1) / b; }
 // another server thread is running.  (They were process-wide statics; the engine runs every call on the caller's thread.)  The
 // persistent-program switches below stay process-wide on purpose: they describe a per-device resource, and they are atomics.
 // Declarations: include/vits_mi355_debug.h (not part of the installed ABI).
-// 0 = size heuristic, 1 = force the big-tile kernel, 2 = force the K-split kernel (tests only)
-static thread_local int g_force_tile = 0;
+// (the conv kernel-selection hooks: ConvSelect, engine_convplan.hip.h)
 // 0 = fp32-MFMA flash attention (default), 1 = the VALU kernel (kept as an independent cross-check in tests)
 static thread_local int g_attn_impl = 0;
 // tests: fill every freshly planned workspace with NaN so stale padding can never hide as zeros
@@ -118,6 +117,8 @@ static int persist_cfg() {
 
 #include "engine_model.hip.h"
 #include "engine_session.hip.h"
+#include "engine_convplan.hip.h"
+#include "engine_convdbg.hip.h"
 #include "engine_launch.hip.h"
 #include "engine_stages.hip.h"
 
@@ -408,7 +409,6 @@ static int acoustic_host(HostStage& hs, const int64_t* ids, const int64_t* lengt
   if (opts && opts->max_frames > 0 && Ty > opts->max_frames) return fail(VITS_ERR_ARG, "T_y %lld exceeds max_frames %d", (long long)Ty, opts->max_frames);
   if (Ty > (1 << 24)) return fail(VITS_ERR_ARG, "T_y unreasonably large");
   // grow the workspace for T_y: encoder outputs live in the arena, so keep them across the re-plan
-  const int H = hp.hidden_channels;
   float* keep_stats = hs.dev_alloc<float>((size_t)B * 2 * I * Tx);
   int* keep_cum = hs.dev_alloc<int>((size_t)B * Tx);
   if (!keep_stats || !keep_cum) return fail(VITS_ERR_NOMEM, "device alloc failed");
@@ -425,7 +425,6 @@ static int acoustic_host(HostStage& hs, const int64_t* ids, const int64_t* lengt
   HIP_TRY(hipMemcpyAsync(s->len_y, ylen32.data(), sizeof(int) * B, hipMemcpyHostToDevice, s->stream));
   set_lengths(s, d_len, s->len_x, B, Tx);
   run_cond(s, d_sid, B);
-  (void)H;
   float* d_npr = nullptr;
   long long nstride = Ty;
   if (opts && opts->noise_prior) {
@@ -535,9 +534,9 @@ int vits_session_last_ms(vits_session* s, float* ms) {
   return check_err(s);
 }
 
-void vits_debug_force_tile(int mode) { g_force_tile = mode; }
+void vits_debug_force_tile(int mode) { conv_select().force_tile = mode; }
 void vits_debug_attention_impl(int impl) { g_attn_impl = impl; }
-void vits_debug_ks_waves(int nw) { g_ks_waves = nw; }
+void vits_debug_ks_waves(int nw) { conv_select().ks_waves = nw; }
 void vits_debug_tail_impl(int impl) { g_tail_impl = impl; }
 void vits_debug_wn_fold(int on) { g_wn_fold = on; }
 void vits_debug_ln_stats(int on) { g_ln_stats = on; }
@@ -588,7 +587,7 @@ int vits_debug_persist_runs(vits_model* m) {
   if (hipMemcpy(v, m->ps_dbg, sizeof v, hipMemcpyDeviceToHost) != hipSuccess) return -1;
   return v[1];
 }
-void vits_debug_conv_wp(int mode) { g_wp_mode = mode; }
+void vits_debug_conv_wp(int mode) { conv_select().wp_mode = mode; }
 void vits_debug_launch_log(int on) {
   std::lock_guard<std::mutex> g(g_launch_log_mu);
   if (on) g_launch_counts.clear();
@@ -602,6 +601,19 @@ int vits_debug_launch_count(const char* op, const char* kernel_prefix) {
   for (const auto& kv : g_launch_counts)
     if (kv.first.compare(0, key.size(), key) == 0) n += kv.second;
   return n;
+}
+int vits_debug_launch_dump(char* buf, size_t cap) {
+  if (!buf || !cap) return -1;
+  std::lock_guard<std::mutex> g(g_launch_log_mu);
+  size_t off = 0;
+  int lines = 0;
+  buf[0] = 0;
+  for (const auto& kv : g_launch_counts) {  // (std::map: sorted by key)
+    const int n = snprintf(buf + off, cap - off, "%s %d\n", kv.first.c_str(), kv.second);
+    if (n < 0 || (size_t)n >= cap - off) { buf[off] = 0; break; }
+    off += n; ++lines;
+  }
+  return lines;
 }
 int vits_debug_rag_halo(const vits_hparams* hp) {
   if (!hp || hp->n_ups < 1 || hp->n_ups > VITS_MAX_UPS || hp->n_resk < 1 || hp->n_resk > VITS_MAX_RESK || hp->n_resd < 1 || hp->n_resd > VITS_MAX_RESD)
@@ -632,7 +644,7 @@ int vits_debug_decoder_needs(const vits_hparams* hp, int32_t* out, int32_t cap) 
   for (int i = 0; i < (int)v.size() && i < cap; ++i) out[i] = v[i];
   return (int)v.size();
 }
-void vits_debug_conv_sp(int mode) { g_sp_mode = mode; }
+void vits_debug_conv_sp(int mode) { conv_select().sp_mode = mode; }
 int vits_debug_clock_probe(int device, int32_t duration_us, double* ghz, int32_t n) {
   if (!ghz || n < 1 || n > 1024 || duration_us < 1 || duration_us > 2000000 || device < 0 || device >= 64) return fail(VITS_ERR_ARG, "clock probe: bad arguments");
   HIP_TRY(hipSetDevice(device));
@@ -654,7 +666,7 @@ int vits_debug_clock_probe(int device, int32_t duration_us, double* ghz, int32_t
   if (e != hipSuccess) return fail(VITS_ERR_DEVICE, "clock probe failed: %s", hipGetErrorString(e));
   return n;
 }
-void vits_debug_no_bf16x3(int on) { g_no_bf3 = on; }
+void vits_debug_no_bf16x3(int on) { conv_select().no_bf3 = on; }
 void vits_debug_poison_workspace(int on) { g_poison = on; }
 // The attention of the pre_conv flow's pre-transformer (no relative positions, plain_attention*_kernel) on caller buffers: qkv [B, 3C, T]
 // (q | k | v rows, as the fused q/k/v conv writes them), out [B, C, T].  Tile variant as the engine picks it, or forced by
@@ -835,58 +847,18 @@ int vits_op_conv1d(int device, const float* x, const float* w, const float* bias
     hipMemcpy(dx, x, sizeof(float) * (size_t)B * Cin * T, hipMemcpyHostToDevice);
     ConvParams P = conv_params(W, dx, dy, B, T, dil, (K - 1) * dil / 2);
     P.in_slope = slope;
-    const char* dbg_env = getenv("VITS_CONV_DBG");
-    long long* d_dbg = nullptr;
-    constexpr size_t dbg_n = 128 + 4 * 4000;  // phase stamps + block trace (timing build)
-    if (dbg_env) { hipMalloc((void**)&d_dbg, dbg_n * sizeof(long long)); hipMemset(d_dbg, 0, dbg_n * sizeof(long long)); P.dbg = d_dbg; }
-    const int reps = dbg_env ? atoi(dbg_env) : 1;
-    hipEvent_t e0, e1, ea; hipEventCreate(&e0); hipEventCreate(&e1); hipEventCreate(&ea);
-    for (int r = 0; r < reps; ++r) {
-      if (r == 1 || reps == 1) hipEventRecord(ea, 0);  // all launches after the first (steady state, operands cache-warm)
-      if (r == reps - 1) hipEventRecord(e0, 0);
+    ConvOpDbg dbg(P);
+    for (int r = 0; r < dbg.reps; ++r) {
+      dbg.before_launch(r);
       launch_conv(&s, P, EPI_STORE, "op.conv1d");
     }
-    hipEventRecord(e1, 0);
+    dbg.after_launches();
     hipError_t e = hipDeviceSynchronize();
     if (e != hipSuccess) rc = fail(VITS_ERR_DEVICE, "conv kernel failed: %s", hipGetErrorString(e));
-    else hipMemcpy(y, dy, sizeof(float) * (size_t)B * Cout * T, hipMemcpyDeviceToHost);
-    if (dbg_env && rc == VITS_OK) {
-      long long h[128]; float ms = 0, msa = 0;
-      hipMemcpy(h, d_dbg, sizeof h, hipMemcpyDeviceToHost);
-      hipEventElapsedTime(&ms, e0, e1);
-      hipEventElapsedTime(&msa, ea, e1);
-      fprintf(stderr, "[conv dbg] B=%d Cin=%d Cout=%d T=%d K=%d dil=%d: last launch %.2f us (event), %.2f us/launch over the last %d back-to-back launches = %.1f TFLOP/s; block 0 cycles since kernel start:\n",
-              B, Cin, Cout, T, K, dil, ms * 1e3, msa * 1e3 / (reps > 1 ? reps - 1 : 1), reps > 1 ? reps - 1 : 1,
-              2.0 * B * Cin * Cout * (double)T * K / (msa * 1e-3 / (reps > 1 ? reps - 1 : 1)) / 1e12);
-      const long blocks64 = (long)cdiv(W.Mpad, 64) * cdiv(T, 64) * B;
-      {
-        int nb = -1, nb2 = -1, nb3 = -1;
-        hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, conv_mfma_kernel<2, 2, 2, 2, EPI_STORE>, 256, 2 * CONV_CI_T * (128 + 64) * 4);
-        hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb2, conv_mfma_kernel<2, 2, 1, 1, EPI_STORE>, 256, 2 * CONV_CI_T * (64 + 64) * 4);
-        hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb3, conv_mfma_ks_kernel<1, 1, EPI_STORE, 1, 4>, 256, 16384);
-        hipFuncAttributes fa; hipFuncGetAttributes(&fa, (const void*)conv_mfma_kernel<2, 2, 2, 2, EPI_STORE>);
-        fprintf(stderr, "   occupancy API (blocks/CU): T128 %d  T64 %d  ks %d ; T128 numRegs %d sharedStatic %zu localMem %zu maxDynShared %d\n", nb, nb2, nb3, fa.numRegs,
-                fa.sharedSizeBytes, fa.localSizeBytes, fa.maxDynamicSharedSizeBytes);
-      }
-      if (blocks64 >= 512) {
-        for (int w = 0; w < 4; ++w)
-          fprintf(stderr, "   [big-tile] wave %d: prologue %lld  taps %lld  store+barrier %lld  mainloop_end %lld  end %lld  (MFMA floor %lld)\n", w, h[w * 8], h[w * 8 + 1],
-                  h[w * 8 + 2], h[w * 8 + 3], h[w * 8 + 4], (long long)(Cin / 2) * K * 4 * 64);
-      } else
-      for (int w = 0; w < 16; ++w)  // stamps relative to wave 0's start; HW_ID: simd = bits 5:4, cu = bits 11:8, se = bits 15:13
-        if (h[w * 8]) fprintf(stderr, "   wave %2d simd %lld cu %lld: start %+lld | +%lld  +%lld  +%lld  +%lld  +%lld  +%lld\n", w, (h[w * 8 + 7] >> 4) & 3, (h[w * 8 + 7] >> 8) & 15,
-                h[w * 8] - h[0], h[w * 8 + 1] - h[w * 8], h[w * 8 + 2] - h[w * 8], h[w * 8 + 3] - h[w * 8], h[w * 8 + 4] - h[w * 8], h[w * 8 + 5] - h[w * 8], h[w * 8 + 6] - h[w * 8]);
+    else {
+      hipMemcpy(y, dy, sizeof(float) * (size_t)B * Cout * T, hipMemcpyDeviceToHost);
+      dbg.report(B, Cin, Cout, W.Mpad, T, K, dil);
     }
-    if (d_dbg && rc == VITS_OK && getenv("VITS_CONV_BT")) {  // block trace of the LAST launch (timing build): "blk id start end hw xcc", 10 ns units
-      std::vector<long long> t(4 * 4000);
-      hipMemcpy(t.data(), d_dbg + 128, t.size() * sizeof(long long), hipMemcpyDeviceToHost);
-      long long t0 = 0;
-      for (int i = 0; i < 4000; ++i) if (t[4 * i] && (!t0 || t[4 * i] < t0)) t0 = t[4 * i];
-      for (int i = 0; i < 4000; ++i)
-        if (t[4 * i]) fprintf(stderr, "blk %d %lld %lld %lld %lld\n", i, t[4 * i] - t0, t[4 * i + 1] ? t[4 * i + 1] - t0 : -1, t[4 * i + 2], t[4 * i + 3]);
-    }
-    if (d_dbg) hipFree(d_dbg);
-    hipEventDestroy(e0); hipEventDestroy(e1); hipEventDestroy(ea);
   }
   if (dx) hipFree(dx);
   if (dy) hipFree(dy);

@@ -15,34 +15,24 @@ struct PendingLN { const float* raw = nullptr; const float* g = nullptr; const f
 static bool enc_fold_ok(vits_session* s, const EncoderW& E, int B, int T) {
   if (E.layers.empty() || !s->xb || !s->y1b) return false;
   const EncLayerW& L = E.layers[0];
-  static const float dummy = 0.f;
-  ConvParams P = conv_params(L.qkv, s->x, s->qkv, B, T, 1, 0);
-  P.ln_g = &dummy;
-  if (!conv_takes_c16(P, EPI_STORE)) return false;
-  P = conv_params(L.f1, s->x, s->ffh, B, T, 1, (E.K - 1) / 2);
-  P.ln_g = &dummy;
-  if (!conv_takes_c16(P, EPI_STORE)) return false;
-  return true;
+  return conv_takes_ln_prologue(conv_params(L.qkv, s->x, s->qkv, B, T, 1, 0)) &&
+         conv_takes_ln_prologue(conv_params(L.f1, s->x, s->ffh, B, T, 1, (E.K - 1) / 2));
 }
 
 static void run_encoder(vits_session* s, const EncoderW& E, float* x, const int* len, int B, int T, int cond_layer,
                         int cond_off, const float* final_base, float* final_out, PendingLN* pend = nullptr) {
   vits_model* m = s->m;
-  const int H = E.H, F = E.F, K = E.K;
+  const int H = E.H, K = E.K;
   const int n = (int)E.layers.size();
   const bool fold = enc_fold_ok(s, E, B, T);
   // statistics of the folded LayerNorms come from the producing conv's epilogue (conv16 PRO == 3) instead of being redone by every
   // workgroup of the consumer: test hook vits_debug_ln_stats
   bool pstat = fold && g_ln_stats && s->lnst && H % 16 == 0 && H / 16 <= 16;
   if (pstat) {  // the producers (conv_o, FFN conv_2) must run on the small-tile kernel too: only its epilogue writes the statistics
-    float dummy_stat = 0.f;
     const EncLayerW& L0 = E.layers[0];
-    ConvParams Pp = conv_params(L0.o, s->att, s->y1, B, T, 1, 0);
-    Pp.ln_stat_out = &dummy_stat;
-    pstat = conv_takes_c16(Pp, EPI_STORE);
-    Pp = conv_params(L0.f2, s->ffh, s->y1, B, T, 1, (K - 1) / 2);
-    Pp.ln_stat_out = &dummy_stat; Pp.in_mask = 1; Pp.out_mask = 1; Pp.len = len;
-    pstat = pstat && conv_takes_c16(Pp, EPI_STORE);
+    ConvParams Pp = conv_params(L0.f2, s->ffh, s->y1, B, T, 1, (K - 1) / 2);
+    Pp.in_mask = 1; Pp.out_mask = 1; Pp.len = len;
+    pstat = conv_writes_ln_stats(conv_params(L0.o, s->att, s->y1, B, T, 1, 0)) && conv_writes_ln_stats(Pp);
   }
   PendingLN prev;  // norm_layers_2 of the previous layer, not yet applied (fold only)
   for (int i = 0; i < n; ++i) {
@@ -87,7 +77,6 @@ static void run_encoder(vits_session* s, const EncoderW& E, float* x, const int*
     launch_ln(s, y2, nullptr, lastl ? final_base : nullptr, (lastl && final_out) ? final_out : x, L.g2, L.b2, len, B, H,
               T, 0, lastl ? 1 : 0);
   }
-  (void)F;
 }
 
 // A bounded poll of a persistent program ran out (its workgroups were not all co-resident: another process on the device, a
@@ -166,10 +155,9 @@ static void run_text_encoder(vits_session* s, const int64_t* d_ids, int B, int T
   // the encoder's last LayerNorm is folded into proj's staging when both run on the small-tile kernel
   PendingLN pend;
   {
-    static const float dummy = 0.f;
     ConvParams Pt = conv_params(m->enc_proj, s->x, s->stats, B, Tx, 1, 0);
-    Pt.ln_g = &dummy; Pt.in_mask = 1; Pt.out_mask = 1; Pt.len = s->len_x;
-    const bool can = conv_takes_c16(Pt, EPI_STORE);
+    Pt.in_mask = 1; Pt.out_mask = 1; Pt.len = s->len_x;
+    const bool can = conv_takes_ln_prologue(Pt);
     run_encoder(s, m->enc_p, s->x, s->len_x, B, Tx, m->use_g ? hp.enc_cond_layer : -1, m->cond_enc_off, nullptr, nullptr, can ? &pend : nullptr);
   }
   ConvParams P = conv_params(m->enc_proj, pend.raw ? pend.raw : s->x, s->stats, B, Tx, 1, 0);
@@ -231,8 +219,7 @@ static void run_dds_proj(vits_session* s, const DDSW& W, float* h, const ConvW& 
     P.len = s->len_x;
     int max_dil = 1;
     for (size_t i = 1; i < W.pw.size(); ++i) max_dil *= K;
-    if ((g_force_tile == 0 || g_force_tile == 3) && (long)B * T <= C16_COLS_DDS && c16_dds_ok(P, K) && max_dil <= 9 && W.pw.size() >= 1 &&
-        W.pw[0].w16) {
+    if (c16_dds_ok(P, K, conv_select()) && max_dil <= 9 && W.pw.size() >= 1 && W.pw[0].w16) {
       const int n = (int)W.pw.size();
       float* X[2] = {s->dy, s->dq1};
       float* Y[2] = {s->dy2, s->dq2};
@@ -262,8 +249,7 @@ static void run_dds_proj(vits_session* s, const DDSW& W, float* h, const ConvW& 
     }
   }
   if (pre) {
-    const int D2 = hp.dp_filter_channels;
-    hipLaunchKernelGGL(convflow_pre_kernel, dim3(cdiv(T, 64), D2, B), dim3(64), 0, s->stream, pre->z, pre->row, pre->pw, pre->pb, pre->cond, h, D2, T);
+    hipLaunchKernelGGL(convflow_pre_kernel, dim3(cdiv(T, 64), D, B), dim3(64), 0, s->stream, pre->z, pre->row, pre->pw, pre->pb, pre->cond, h, D, T);
   }
   const float* hd = run_dds(s, W, h, B, T);
   ConvParams P = conv_params(proj, hd, out, B, T, 1, 0);
@@ -292,14 +278,11 @@ static void run_duration_det(vits_session* s, const float* x, int B, int Tx) {
   mark_masked(s, P, s->len_x);
   launch_conv(s, P, EPI_STORE, "dp.conv_1");
   // h = relu(conv_2(x * mask)): norm_1 on load when the small-tile kernel takes the launch (the text encoder FFN's fold)
-  static const float dummy = 0.f;
   P = conv_params(m->dp_c2, s->dy, s->dc, B, Tx, 1, (K - 1) / 2);
   P.in_mask = 1; P.len = s->len_x; P.relu = 1;
-  P.ln_g = &dummy;
-  if (conv_takes_c16(P, EPI_STORE)) {
+  if (conv_takes_ln_prologue(P)) {
     P.ln_g = m->dp_n1g; P.ln_b = m->dp_n1b;
   } else {
-    P.ln_g = nullptr;
     launch_ln(s, s->dy, nullptr, nullptr, s->dy2, m->dp_n1g, m->dp_n1b, s->len_x, B, D, Tx, 0, 0);
     P.g[0].x = s->dy2;
   }
@@ -335,8 +318,6 @@ static void run_duration(vits_session* s, const float* x, const float* d_noise, 
   run_dds_proj(s, m->dp_dds, s->dh, m->dp_proj, s->dc, "dp.proj", B, Tx);
   hipLaunchKernelGGL(dp_init_z_kernel, dim3(cdiv(Tx, 64), 2, B), dim3(64), 0, s->stream, s->dz, d_noise, nsw, seed, Tx, s->solo ? 1 : 0, s->dv, s->item_seeds);
   int swap = 0;
-  const float cst = (float)log(exp(1.0 - 1e-3) - 1.0);
-  (void)cst;
   for (int k = hp.dp_n_flows - 1; k >= 1; --k) {
     swap ^= 1;  // Flip (modules.py:270-277) is a row relabel on the 2-channel z
     const ConvFlowW& c = m->cf[k];

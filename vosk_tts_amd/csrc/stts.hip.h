@@ -1292,7 +1292,7 @@ static void bert_forward(bert_model* m, vits_session* s, const int64_t* d_ids, c
   }
   // (round 5) sentence-sized calls: the 3072 -> 768 matrix of the FFN is the one launch of a layer that ran on 24 CUs (21 us of a 75 us
   // layer, profiles/r5_bert_ffn2.txt)
-  const bool ffn2_slices = g_force_tile == 0 && T <= 64 && T >= 4 && hp.intermediate % (3 * CONV_CI_T) == 0 && hp.intermediate / 3 >= 8 * CONV_CI_T &&
+  const bool ffn2_slices = conv_select().force_tile == 0 && T <= 64 && T >= 4 && hp.intermediate % (3 * CONV_CI_T) == 0 && hp.intermediate / 3 >= 8 * CONV_CI_T &&
                            H % 32 == 0 && !m->layers.empty() && m->layers[0].c2.K == 1;
   for (const BertLayerW& L : m->layers) {
     ConvParams P = conv_params(L.qkv, x, qkv, 1, T, 1, 0);
@@ -1319,7 +1319,8 @@ static void bert_forward(bert_model* m, vits_session* s, const int64_t* d_ids, c
         P.g[j].y = qkv + (size_t)j * H * T;
       }
       ProfScope ps(s, "bert.ffn2", 2.0 * H * hp.intermediate * (double)T);
-      launch_conv_wp(s, P, ps);
+      name_plan(ps, plan_wp());
+      launch_conv_wp(s, P, plan_wp());
     } else {
       launch_conv(s, P, EPI_STORE, "bert.ffn2");
     }
