@@ -247,3 +247,43 @@ def test_ragged_limit_covers_the_measured_reach(row):
     halo = VitsLib().rag_halo(row_hparams(row))
     print(f"{row[0]}: rag_halo {halo}")
     assert halo >= max(left, right)
+
+
+# ------------------------------------------------------------------------------------------------ the recorded host arithmetic
+def _recorded():
+    import json
+
+    from vosk_tts_amd import weights as W
+
+    doc = json.load(open(os.path.join(GOLDEN, "decoder_geom.json")))
+    hps = {r[0]: row_hparams(r) for r in GRID}
+    hps.update(default=W.default_hparams(), multistream=W.multistream_hparams(), istft=W.istft_hparams(), plain=W.plain_hparams())
+    return doc, hps, {e[0]: refused_hparams(e) for e in REFUSED}
+
+
+def _hooks(lib, hp):
+    from vosk_tts_amd.capi import VitsError
+
+    out = {}
+    for key, fn in (("rag_halo", lib.rag_halo), ("needs", lib.decoder_needs)):
+        try:
+            out[key] = fn(hp)
+        except VitsError as e:
+            out[key] = {"error": e.code}
+    return out
+
+
+def test_host_arithmetic_equals_the_recording():
+    """rag_halo and the whole decoder_needs vector of all 43 grid rows, the default / multistream / single-band / plain-Generator
+    hparams and the nine refused geometries equal tests/golden/decoder_geom.json, recorded (tools/gen_golden_decoder_geom.py) from
+    the library as it stood before the decoder's shape moved into DecGeom.  Equality, no tolerance: these are integers."""
+    from vosk_tts_amd.capi import VitsLib
+
+    doc, hps, refused = _recorded()
+    lib = VitsLib()
+    assert sorted(doc["rows"]) == sorted(hps) and len(hps) == N_GRID + 4
+    assert sorted(doc["refused"]) == sorted(refused) and len(refused) == N_REFUSED
+    for name, hp in hps.items():
+        assert _hooks(lib, hp) == doc["rows"][name], name
+    for name, hp in refused.items():
+        assert _hooks(lib, hp) == doc["refused"][name], name

@@ -12,11 +12,13 @@ Tolerance: STAGE_TOL = 1e-4 on the assert_close scale for every row (fp32 kernel
 Observed on the MI355X (printed per row with -s): WORST below.
 """
 import functools
+import json
+import os
 
 import numpy as np
 import pytest
 
-from conftest import assert_close
+from conftest import GOLDEN, assert_close
 from decoder_grid import GRID, N_GRID, N_REFUSED, REFUSED, measured_field, refused_hparams, row_hparams, row_id
 from decoder_ref import decoder_ref
 
@@ -32,6 +34,10 @@ WORST = {0: "1.54e-06 (mb_default)", 1: "1.37e-06 (hg_v1)", 2: "1.30e-06 (ms_4st
 # float64 2.3e-06 .. 9.2e-06 (ms_u6_u5).  No row came near the cap, and no engine bug was found at any geometry of the grid.
 
 assert len(GRID) == N_GRID == 43 and len(REFUSED) == N_REFUSED == 9
+# recorded from the library before the decoder's shape moved into DecGeom (tools/gen_golden_decoder_geom.py --device): per row
+# vits_algorithmic_flops(1, 1, 0) / (1, 0, 1), per refused geometry vits_create's code and message
+RECORDED = json.load(open(os.path.join(GOLDEN, "decoder_geom.json")))
+assert sorted(RECORDED["flops"]) == sorted(ROWS) and sorted(RECORDED["refusals"]) == sorted(e[0] for e in REFUSED)
 
 # (hook, value, restore): every conv kernel the decoder can be forced onto, and the separately written tail kernels
 FORCED = [("force_tile", 1, 0), ("force_tile", 2, 0), ("force_tile", 3, 0), ("conv_sp", 2, -1), ("conv_wp", 2, 0), ("tail_impl", 1, 0)]
@@ -73,6 +79,7 @@ def test_dense_on_every_kernel(hip_lib, row):
     sid = np.array([1, 3], np.int64) if row[8] else None
     worst = 0.0
     try:
+        assert [model.algorithmic_flops(1, 1, 0), model.algorithmic_flops(1, 0, 1)] == RECORDED["flops"][name]  # exact: integer-valued doubles
         for Ty in T_YS[GRID.index(row) % 3]:
             z = rng.standard_normal((2, hp.inter_channels, Ty)).astype(np.float32)
             ref = decoder_ref(hp, tens, z, sid=sid)
@@ -292,3 +299,4 @@ def test_loader_refuses(hip_lib, entry):
         hip_lib.create(blob, 0)
     assert ei.value.code == codes[entry[3]], str(ei.value)
     assert re.search(entry[4], str(ei.value)), str(ei.value)
+    assert {"code": ei.value.code, "message": str(ei.value)} == RECORDED["refusals"][entry[0]]

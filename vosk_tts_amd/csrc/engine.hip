@@ -221,21 +221,18 @@ double vits_algorithmic_flops(const vits_model* m, int32_t B, int32_t Tx, int32_
   for (int i = 0; i < hp->flow_wn_layers; ++i) fl += 2 * H * 2 * H * K5 + 2 * H * (i < hp->flow_wn_layers - 1 ? 2 * H : H);
   fl += 2 * H * (I / 2);
   double frame = hp->flow_n_flows * fl, frame_quad = hp->flow_n_flows * 4 * H;
-  double C = hp->dec_initial_channel, rate = 1, dec = 2 * I * C * 7;
-  for (int i = 0; i < hp->n_ups; ++i) {
-    dec += rate * 2 * C * (C / 2) * hp->up_kernels[i];
-    rate *= hp->up_rates[i];
-    C /= 2;
+  const DecGeom& G = m->geom;
+  double C = hp->dec_initial_channel, dec = 2 * I * C * 7;
+  for (int i = 0; i < G.n_ups; ++i) {
+    const double rate = G.st[i].rate_out;
+    C = G.st[i].cout;
+    dec += G.st[i].rate_in * 2.0 * G.st[i].cin * C * hp->up_kernels[i];
     for (int j = 0; j < hp->n_resk; ++j) dec += rate * hp->n_resd * 2 * (2 * C * C * hp->res_kernels[j]);
   }
-  if (hp->dec_type == 0 || hp->dec_type == 2 || hp->dec_type == 3) {
-    double P = hp->subbands * (hp->istft_n_fft + 2);
-    dec += rate * 2 * C * P * 7;
-    dec += rate * hp->subbands * 2 * (hp->istft_n_fft + 2) * hp->istft_n_fft;
-    if (hp->dec_type != 3) dec += rate * hp->subbands * hp->istft_hop * 2 * (hp->pqmf_taps + 1);  // synthesis FIR
-  } else {
-    dec += rate * 2 * C * 7;
-  }
+  const double rate = G.final_rate;
+  dec += rate * 2 * C * G.post_rows * 7;
+  if (G.reflect) dec += rate * hp->subbands * 2 * (hp->istft_n_fft + 2) * hp->istft_n_fft;  // iSTFT
+  if (G.has_mb) dec += rate * hp->subbands * hp->istft_hop * 2 * (hp->pqmf_taps + 1);       // synthesis FIR
   frame += dec;
   return (double)B * ((double)Tx * (tok + tok_quad * Tx) + (double)Ty * (frame + frame_quad * Ty));
 }
@@ -349,10 +346,10 @@ int vits_stage_decoder(vits_model* m, const float* z, int32_t B, int32_t Ty, con
   if (m->cond_dec_off >= 0) { int64_t* d_sid = hs.to_dev(sid, B); run_cond(s, d_sid, B); }
   float* d_audio = hs.dev_alloc<float>((size_t)B * S);
   if (!d_audio) return fail(VITS_ERR_NOMEM, "device alloc failed");
-  run_decoder(s, s->zA, false, B, Ty, d_audio, S, nullptr);
+  run_decoder(s, s->zA, false, B, Ty, d_audio, S);
   HIP_TRY(hipMemcpyAsync(audio, d_audio, sizeof(float) * (size_t)B * S, hipMemcpyDeviceToHost, s->stream));
-  if (audio_mb && (hp.dec_type == 0 || hp.dec_type == 2))  // the sub-band signal before zero-stuffing (type 2's y_mb_hat is S x it on every S-th sample)
-    HIP_TRY(hipMemcpyAsync(audio_mb, s->dec_bufs[16], sizeof(float) * (size_t)B * S, hipMemcpyDeviceToHost, s->stream));
+  if (audio_mb && m->geom.has_mb)  // the sub-band signal before zero-stuffing (type 2's y_mb_hat is S x it on every S-th sample)
+    HIP_TRY(hipMemcpyAsync(audio_mb, s->dec.mb, sizeof(float) * (size_t)B * S, hipMemcpyDeviceToHost, s->stream));
   return check_err(s);
 }
 
@@ -620,9 +617,9 @@ int vits_debug_rag_halo(const vits_hparams* hp) {
     return -fail(VITS_ERR_ARG, "rag_halo: bad arguments");
   for (int i = 0; i < hp->n_ups; ++i) if (hp->up_rates[i] < 1) return -fail(VITS_ERR_ARG, "rag_halo: bad up_rates");
   if (hp->dec_type != 1 && (hp->istft_hop < 1 || hp->subbands < 1)) return -fail(VITS_ERR_ARG, "rag_halo: bad tail geometry");
-  return decoder_rag_halo(*hp);
+  return dec_geom(*hp).rag_halo;
 }
-// Host arithmetic only (no device): the per-layer limits decoder_needs derives for a padded-batch continuation.  Layout: [0] frames of z
+// Host arithmetic only (no device): the per-layer limits dec_geom derives for a padded-batch continuation.  Layout: [0] frames of z
 // read beyond an item's end (conv_pre's output limit + its 3 taps to the right), [1] pre_out, [2] post_out, [3] tail_cols, then per
 // upsampling stage: ups_q, c1_out[0..n_resd), c2_out[0..n_resd).  Returns the number of values (written up to cap).
 int vits_debug_decoder_needs(const vits_hparams* hp, int32_t* out, int32_t cap) {
@@ -634,7 +631,7 @@ int vits_debug_decoder_needs(const vits_hparams* hp, int32_t* out, int32_t cap) 
     return -fail(VITS_ERR_ARG, "decoder_needs: bad tail geometry");
   if ((hp->dec_type == 0 || hp->dec_type == 2) && hp->pqmf_taps < 0) return -fail(VITS_ERR_ARG, "decoder_needs: bad synthesis filter length");
   if (hp->dec_type == 3 && hp->subbands != 1) return -fail(VITS_ERR_ARG, "decoder_needs: single-band decoder with subbands != 1");
-  const DecNeeds N = decoder_needs(*hp, true);
+  const DecNeeds N = dec_geom(*hp).needs;
   std::vector<int32_t> v = {N.pre_out + 3, N.pre_out, N.post_out, N.tail_cols};
   for (int i = 0; i < hp->n_ups; ++i) {
     v.push_back(N.ups_q[i]);

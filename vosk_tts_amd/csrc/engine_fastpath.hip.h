@@ -231,7 +231,7 @@ static int phase2_launch(vits_session* F, vits_session* Bk, bool solo, bool pcm)
     }
     // a lone utterance decodes as the exact-size run does (zeros beyond its end); batches keep the reference's padded-batch
     // continuation over the halo unless the caller asked for independent items
-    run_decoder(Bk, z, true, B, TyB, Bk->out_d, stride, nullptr, true, (solo || B == 1) ? 0 : F->m->rag_halo);
+    run_decoder(Bk, z, true, B, TyB, Bk->out_d, stride, true, !(solo || B == 1));
     if (pcm) {
       hipLaunchKernelGGL(pcm16_kernel, dim3(cdiv((int)stride, 256), B), dim3(256), 0, F->stream, Bk->out_d, stride, Bk->pcm_d, stride, stride, 1.f, Bk->dv);
       hipMemcpyAsync(Bk->out_h, Bk->pcm_d, Bk->out_elems * sizeof(int16_t), hipMemcpyDeviceToHost, F->stream);
@@ -373,7 +373,7 @@ static int synth_eager(vits_model* m, const int64_t* ids, const int64_t* lengths
   const int64_t S = Ty * hp.hop_length;
   float* d_audio = hs.dev_alloc<float>((size_t)B * S);
   if (!d_audio) return fail(VITS_ERR_NOMEM, "device alloc failed");
-  run_decoder(s, z, true, B, (int)Ty, d_audio, S, nullptr, true, s->solo ? 0 : m->rag_halo);
+  run_decoder(s, z, true, B, (int)Ty, d_audio, S, true, !s->solo);
   const size_t esz = pcm ? sizeof(int16_t) : sizeof(float);
   const void* d_src = d_audio;
   if (pcm) {

@@ -59,6 +59,101 @@ struct UpW {
   int u = 0, Ku = 0, cout = 0, taps = 0, pad_l = 0, halo = 0;
   int shift[8] = {0};
 };
+// What each decoder layer still has to produce BEYOND an item's end in a ragged batch, in columns of its own output (round 5).  The
+// decoder has no masks: in the reference's padded batch an item's activations continue into the padding, and a valid sample depends on
+// that continuation over the receptive field that is left between a layer and the waveform -- 25 frames at conv_pre, 5 columns after
+// the last ResBlock.  Rounds 1-4 computed len + 32 frames at EVERY layer (10 % of the decoder's work at 330-frame items); now every
+// launch carries its own limit: out = what the layers behind it need, in = what its producer made.  Walked backwards from the tail.
+// All zero: every item is decoded as if alone (zeros beyond its own end at every stage).
+struct DecNeeds {
+  int pre_out = 0, post_out = 0, tail_cols = 0;
+  int ups_q[VITS_MAX_UPS] = {0};            // polyphase launch: input positions q beyond len * rate_in
+  int c1_out[VITS_MAX_UPS][VITS_MAX_RESD] = {{0}}, c2_out[VITS_MAX_UPS][VITS_MAX_RESD] = {{0}};
+};
+// The decoder's shape, decided once from the hparams (dec_geom) and read by everything that sizes, launches or counts the decoder.
+struct DecGeom {
+  struct Stage {
+    int cin = 0, cout = 0;          // channels before / after the upsampler (the ResBlocks keep cout)
+    int u = 0, taps = 0;            // rate and polyphase taps per phase, ceil(Ku / u)
+    int rate_in = 1, rate_out = 1;  // columns per frame before / after the stage
+  } st[VITS_MAX_UPS];
+  int n_ups = 0;
+  // tail: conv_post [post_rows, T * final_rate (+ 1 with the reflection column)], then iSTFT [+ synthesis filter] or tanh
+  int post_rows = 1, post_pad = 3;
+  bool reflect = false;   // ReflectionPad1d((1, 0)) in front of conv_post: T + 1 output columns
+  bool has_mb = false;    // a sub-band signal [S, T * final_rate * hop] exists between iSTFT and synthesis filter
+  int final_rate = 1;     // conv_post columns per frame
+  long long samples_per_frame = 1;
+  // ragged limits that follow from the shape alone
+  DecNeeds needs;         // of the reference's padded-batch continuation
+  int rag_halo = 32;      // frames decoded beyond an item's end in streaming windows: >= the one-sided receptive field
+};
+// Pure host arithmetic (no device, no model).  hp has passed load_decoder's validity checks or a debug hook's argument checks: counts
+// within the VITS_MAX_* bounds, rates >= 1, and hop / subbands >= 1 where the tail divides by them.
+static DecGeom dec_geom(const vits_hparams& hp) {
+  DecGeom G;
+  const bool istft = hp.dec_type == 0 || hp.dec_type == 2 || hp.dec_type == 3, filt = hp.dec_type == 0 || hp.dec_type == 2;
+  G.n_ups = hp.n_ups;
+  // rf: one-sided receptive field in frames (24.9 for the default config)
+  double rf = 3.0;  // conv_pre k = 7
+  double span = 0;  // widest ResBlock chain of a stage, in its columns
+  for (int j = 0; j < hp.n_resk; ++j) {
+    double sp = 0;
+    for (int d = 0; d < hp.n_resd; ++d) sp += (hp.res_kernels[j] - 1) * hp.res_dilations[j][d] / 2.0 + (hp.res_kernels[j] - 1) / 2.0;
+    if (sp > span) span = sp;
+  }
+  long long rate = 1;
+  int C = hp.dec_initial_channel;
+  for (int i = 0; i < hp.n_ups; ++i) {
+    DecGeom::Stage& S = G.st[i];
+    S.u = hp.up_rates[i]; S.taps = (hp.up_kernels[i] + S.u - 1) / S.u;
+    S.cin = C; S.cout = C / 2;  // every stage halves the channels (models.py:860 / 993)
+    S.rate_in = (int)rate;
+    rf += (double)(S.taps / 2 + 1) / (double)rate;
+    rate *= S.u;
+    S.rate_out = (int)rate;
+    rf += span / (double)rate;
+    C = S.cout;
+  }
+  G.final_rate = (int)rate;
+  G.samples_per_frame = istft ? rate * hp.istft_hop * hp.subbands : rate;
+  G.reflect = istft; G.post_pad = istft ? 4 : 3;
+  G.post_rows = istft ? hp.subbands * (hp.istft_n_fft + 2) : 1;
+  G.has_mb = filt;
+  rf += 4.0 / (double)rate;  // conv_post k = 7 (+ reflection pad)
+  if (filt) rf += ((double)hp.istft_n_fft / hp.istft_hop + (hp.pqmf_taps / 2.0) / hp.subbands / hp.istft_hop) / (double)rate;
+  if (hp.dec_type == 3) rf += ((double)hp.istft_n_fft / hp.istft_hop) / (double)rate;  // iSTFT only, no synthesis filter
+  // rounded up with 2 frames of slack and at least 32: ragged batches and streaming windows reproduce the dense result only if the
+  // halo they keep is at least this wide
+  G.rag_halo = std::max((int)ceil(rf) + 2, 32);
+
+  DecNeeds& N = G.needs;
+  int need = 0;  // columns the NEXT consumer wants beyond len * rate, at the current rate
+  // iSTFT frame f feeds sub-band samples [f hop, f hop + n_fft); PQMF synthesis reaches (taps / 2) / subbands sub-band samples ahead
+  // (dec_type 2: the same geometry with the learned filter's taps; 3: the iSTFT's reach only)
+  if (istft) need = (hp.istft_n_fft + hp.istft_hop - 1) / hp.istft_hop + 2;
+  if (filt) need += ((hp.pqmf_taps / 2 + hp.subbands - 1) / hp.subbands + hp.istft_hop - 1) / hp.istft_hop;
+  N.tail_cols = need;              // the tail reads conv_post columns 0 .. len * rate + need INCLUSIVE ...
+  N.post_out = need + 1;           // ... so conv_post makes need + 1 of them beyond len * rate (it has T + 1 columns: the reflection pad)
+  need += 4;                       // conv_post, 7 taps (pad 4 with the reflection column, 3 without)
+  for (int i = hp.n_ups - 1; i >= 0; --i) {
+    for (int d = hp.n_resd - 1; d >= 0; --d) {
+      int h2 = 0, h1 = 0;
+      for (int j = 0; j < hp.n_resk; ++j) {
+        const int k = hp.res_kernels[j];
+        h2 = std::max(h2, (k - 1) / 2);
+        h1 = std::max(h1, (k - 1) * hp.res_dilations[j][d] / 2);
+      }
+      N.c2_out[i][d] = need; need += h2;
+      N.c1_out[i][d] = need; need += h1;
+    }
+    const int u = G.st[i].u;
+    N.ups_q[i] = (need + u - 1) / u + 1;       // output column c = u q + phase
+    need = N.ups_q[i] + G.st[i].taps / 2 + 2;  // input positions a polyphase output reads: q -+ taps / 2 (+ slack for the phase shifts)
+  }
+  N.pre_out = need;
+  return G;
+}
 
 struct vits_session;
 
@@ -104,7 +199,8 @@ struct vits_model {
   std::mutex pack_mu;      // packed per-thread parameter vectors of persistent steps, keyed by their sources (persist_plan.hip.h)
   std::map<std::vector<long long>, const float*> packs;
   int n_cu = 0;       // compute units of the device = workgroups of a persistent kernel (persist.hip.h)
-  int rag_halo = 32;  // frames decoded beyond an item's end in ragged batches / streaming windows: >= the decoder's receptive field
+  DecGeom geom;       // the decoder's shape (load_decoder)
+  int rag_halo = 32;  // geom.rag_halo: frames decoded beyond an item's end in streaming windows, >= the decoder's receptive field
 
   std::mutex pool_mu;
   std::vector<vits_session*> pool;
@@ -309,29 +405,6 @@ static double bessel_i0(double x) {
   return s;
 }
 
-// One-sided receptive field of the decoder in frames (24.9 for the default config), rounded up with 2 frames of slack and
-// at least 32: ragged batches and streaming windows reproduce the dense result only if the halo they keep is at least this wide.
-static int decoder_rag_halo(const vits_hparams& hp) {
-  double rf = 3.0, rate = 1.0;  // conv_pre k = 7
-  for (int i = 0; i < hp.n_ups; ++i) {
-    const int u = hp.up_rates[i], Ku = hp.up_kernels[i];
-    rf += (double)((Ku + u - 1) / u / 2 + 1) / rate;
-    rate *= u;
-    double worst = 0;
-    for (int j = 0; j < hp.n_resk; ++j) {
-      double span = 0;
-      for (int d = 0; d < hp.n_resd; ++d) span += (hp.res_kernels[j] - 1) * hp.res_dilations[j][d] / 2.0 + (hp.res_kernels[j] - 1) / 2.0;
-      if (span > worst) worst = span;
-    }
-    rf += worst / rate;
-  }
-  rf += 4.0 / rate;  // conv_post k = 7 (+ reflection pad)
-  if (hp.dec_type == 0 || hp.dec_type == 2) rf += ((double)hp.istft_n_fft / hp.istft_hop + (hp.pqmf_taps / 2.0) / hp.subbands / hp.istft_hop) / rate;
-  if (hp.dec_type == 3) rf += ((double)hp.istft_n_fft / hp.istft_hop) / rate;  // iSTFT only, no synthesis filter
-  const int halo = (int)ceil(rf) + 2;
-  return halo < 32 ? 32 : halo;
-}
-
 // ---- decoder weights (Multiband_iSTFT_Generator models.py:975-1054 / Generator :845-898)
 static int load_decoder(vits_model* m) {
   const vits_hparams& hp = m->hp;
@@ -341,40 +414,36 @@ static int load_decoder(vits_model* m) {
   m->conv_pre = conv_from(m, "dec.conv_pre", C, I, 7, true, false, hp.conv_precision == 1 && C % 128 == 0);
   // Geometry checks before anything divides by a rate or sizes a buffer from hop_length: the decoder writes
   // T_y * prod(up_rates) [* istft_hop * subbands] samples per item while every output buffer is T_y * hop_length.
-  {
-    long long rate = 1;
-    for (int i = 0; i < hp.n_ups; ++i) {
-      const int u = hp.up_rates[i], Ku = hp.up_kernels[i];
-      if (u <= 0 || Ku < u) return fail(VITS_ERR_BLOB, "decoder stage %d: upsample rate %d / kernel %d invalid", i, u, Ku);
-      rate *= u;
-    }
-    if (hp.dec_type == 0 || hp.dec_type == 2 || hp.dec_type == 3) {
-      if (hp.subbands <= 0 || hp.istft_hop <= 0 || hp.istft_n_fft <= 0 || hp.istft_n_fft % hp.istft_hop || (hp.dec_type != 3 && hp.pqmf_taps <= 0))
-        return fail(VITS_ERR_BLOB, "iSTFT / PQMF parameters invalid (subbands %d, n_fft %d, hop %d, taps %d)", hp.subbands, hp.istft_n_fft, hp.istft_hop, hp.pqmf_taps);
-      if (hp.dec_type == 2 && hp.pqmf_taps % 2)
-        return fail(VITS_ERR_BLOB, "multi-stream synthesis filter of %d taps: the length must be odd", hp.pqmf_taps + 1);
-      if (hp.dec_type == 3 && hp.subbands != 1) return fail(VITS_ERR_BLOB, "single-band iSTFT decoder with subbands %d (must be 1)", hp.subbands);
-      rate *= (long long)hp.istft_hop * hp.subbands;
-    }
-    if (hp.hop_length <= 0 || rate != hp.hop_length)
-      return fail(VITS_ERR_BLOB, "decoder produces %lld samples per frame but hop_length is %d", rate, hp.hop_length);
-    for (int j = 0; j < hp.n_resk; ++j)
-      if (hp.res_kernels[j] <= 0 || hp.res_kernels[j] % 2 == 0) return fail(VITS_ERR_BLOB, "resblock kernel %d invalid (must be odd)", hp.res_kernels[j]);
+  for (int i = 0; i < hp.n_ups; ++i) {
+    const int u = hp.up_rates[i], Ku = hp.up_kernels[i];
+    if (u <= 0 || Ku < u) return fail(VITS_ERR_BLOB, "decoder stage %d: upsample rate %d / kernel %d invalid", i, u, Ku);
   }
-  m->rag_halo = decoder_rag_halo(hp);
+  if (hp.dec_type == 0 || hp.dec_type == 2 || hp.dec_type == 3) {
+    if (hp.subbands <= 0 || hp.istft_hop <= 0 || hp.istft_n_fft <= 0 || hp.istft_n_fft % hp.istft_hop || (hp.dec_type != 3 && hp.pqmf_taps <= 0))
+      return fail(VITS_ERR_BLOB, "iSTFT / PQMF parameters invalid (subbands %d, n_fft %d, hop %d, taps %d)", hp.subbands, hp.istft_n_fft, hp.istft_hop, hp.pqmf_taps);
+    if (hp.dec_type == 2 && hp.pqmf_taps % 2)
+      return fail(VITS_ERR_BLOB, "multi-stream synthesis filter of %d taps: the length must be odd", hp.pqmf_taps + 1);
+    if (hp.dec_type == 3 && hp.subbands != 1) return fail(VITS_ERR_BLOB, "single-band iSTFT decoder with subbands %d (must be 1)", hp.subbands);
+  }
+  const DecGeom& G = m->geom = dec_geom(hp);
+  if (hp.hop_length <= 0 || G.samples_per_frame != hp.hop_length)
+    return fail(VITS_ERR_BLOB, "decoder produces %lld samples per frame but hop_length is %d", G.samples_per_frame, hp.hop_length);
+  for (int j = 0; j < hp.n_resk; ++j)
+    if (hp.res_kernels[j] <= 0 || hp.res_kernels[j] % 2 == 0) return fail(VITS_ERR_BLOB, "resblock kernel %d invalid (must be odd)", hp.res_kernels[j]);
+  m->rag_halo = G.rag_halo;
   if (m->rag_halo > 4096) return fail(VITS_ERR_UNSUPPORTED, "decoder receptive field of %d frames is not supported", m->rag_halo);
   m->ups.resize(hp.n_ups);
   m->rb.resize((size_t)hp.n_ups * hp.n_resk);
   for (int i = 0; i < hp.n_ups && !m->missing; ++i) {
     UpW& U = m->ups[i];
-    const int u = hp.up_rates[i], Ku = hp.up_kernels[i], Co = C / 2, p = (Ku - u) / 2;
+    const int u = G.st[i].u, Ku = hp.up_kernels[i], Co = G.st[i].cout, p = (Ku - u) / 2;
     if (u > 8 || Ku % u || (Ku - u) % 2)
       return fail(VITS_ERR_UNSUPPORTED, "decoder stage %d: upsample rate %d / kernel %d unsupported (rate <= 8, kernel a multiple of the rate, kernel - rate even)", i, u, Ku);
     if (C % 64) return fail(VITS_ERR_UNSUPPORTED, "decoder stage %d: %d input channels (must be a multiple of 64)", i, C);
     const float* w = tget(m, 3, C, Co, Ku, "dec.ups.%d.weight", i);  // [Cin, Cout, K]
     const float* b = tget(m, 1, Co, -1, -1, "dec.ups.%d.bias", i);
     if (m->missing) break;
-    U.u = u; U.Ku = Ku; U.cout = Co; U.taps = Ku / u;
+    U.u = u; U.Ku = Ku; U.cout = Co; U.taps = G.st[i].taps;
     // out[u*q + r] = sum_{delta} x[q + delta] * W[.., r + p - u*delta]; delta in [dmin(r), dmin(r)+taps-1]
     int dmin[8], dmin_all = 1 << 30, dmax_all = -(1 << 30);
     for (int r = 0; r < u; ++r) {

@@ -46,7 +46,13 @@ struct vits_session {
   float *dh = nullptr, *dy = nullptr, *dy2 = nullptr, *dc = nullptr, *dz = nullptr, *dpr = nullptr, *logw = nullptr, *dfh = nullptr;
   float *dq1 = nullptr, *dq2 = nullptr;  // second x / y pair of the per-layer DDSConv launches (ping-pong with dy / dy2)
   float *zA = nullptr, *zB = nullptr, *fh = nullptr, *fx = nullptr, *facts = nullptr, *fskip = nullptr;
-  std::vector<float*> dec_bufs;
+  struct DecBufs {  // decoder (run_decoder): stage i works in the set of parity i & 1
+    float* pre = nullptr;                 // conv_pre out
+    float* ups[2] = {nullptr, nullptr};   // upsampler out
+    float* xt[2][3] = {{nullptr}};        // per ResBlock chain: c1 out
+    float* x[2][3] = {{nullptr}};         // per ResBlock chain: the residual stream
+    float *post = nullptr, *mb = nullptr; // conv_post out; the sub-band signal (64 floats where the decoder has none)
+  } dec;
   // persistent step programs of a single utterance (persist.hip.h / persist_plan.hip.h): text encoder and duration predictor
   // (laid out for T_x) and flow (T_y).  LL-cell exchange buffers live inside the arena and are zeroed at every re-plan; the
   // programs are rebuilt at every re-plan; the epoch / completion block survives re-plans (epochs only ever grow).
@@ -261,27 +267,20 @@ static void plan(vits_session* s, int B, int Tx, int Ty) {
   s->facts = bump<float>(s, B * H * Ty * (size_t)(hp.flow_wn_layers > 0 ? hp.flow_wn_layers : 1));  // gate outputs of all WN layers, stacked
   s->fskip = bump<float>(s, B * He * Ty);
   // decoder: conv_pre out, then per stage: ups out + 3 tmp + 3 res-chain (models.py:1026-1036)
-  s->dec_bufs.clear();
-  size_t C = hp.dec_initial_channel, T = Ty;
-  s->dec_bufs.push_back(bump<float>(s, B * C * T));
+  const DecGeom& G = s->m->geom;
+  const size_t T = Ty, Tf = T * G.final_rate;
+  s->dec.pre = bump<float>(s, (size_t)B * hp.dec_initial_channel * T);
   size_t stage_max = 0;
-  {
-    size_t c = C, t = T;
-    for (int i = 0; i < hp.n_ups; ++i) { c /= 2; t *= hp.up_rates[i]; if (c * t > stage_max) stage_max = c * t; }
-  }
+  for (int i = 0; i < G.n_ups; ++i) stage_max = std::max(stage_max, G.st[i].cout * T * G.st[i].rate_out);
   // two alternating sets of 7 stage buffers (stage i reads set (i-1)&1's res-chain, writes set i&1)
-  for (int k = 0; k < 14; ++k) s->dec_bufs.push_back(bump<float>(s, B * stage_max));
-  if (hp.dec_type == 0 || hp.dec_type == 2 || hp.dec_type == 3) {
-    // post-conv output [B, S*(N+2), t+1]; the sub-band signal [B, S, t*hop] (types 0 and 2: the single-band decoder writes audio directly)
-    size_t P = (size_t)hp.subbands * (hp.istft_n_fft + 2);
-    size_t t = T; for (int i = 0; i < hp.n_ups; ++i) t *= hp.up_rates[i];
-    s->dec_bufs.push_back(bump<float>(s, B * P * (t + 1)));
-    s->dec_bufs.push_back(bump<float>(s, hp.dec_type == 3 ? 64 : B * hp.subbands * t * hp.istft_hop));
-  } else {
-    size_t t = T; for (int i = 0; i < hp.n_ups; ++i) t *= hp.up_rates[i];
-    s->dec_bufs.push_back(bump<float>(s, B * t));
-    s->dec_bufs.push_back(bump<float>(s, 64));
+  for (int p = 0; p < 2; ++p) {
+    s->dec.ups[p] = bump<float>(s, B * stage_max);
+    for (float*& b : s->dec.xt[p]) b = bump<float>(s, B * stage_max);
+    for (float*& b : s->dec.x[p]) b = bump<float>(s, B * stage_max);
   }
+  // post-conv output [B, post_rows, t (+ 1)]; the sub-band signal [B, S, t*hop] (types 0 and 2: the others write audio directly)
+  s->dec.post = bump<float>(s, (size_t)B * G.post_rows * (Tf + G.reflect));
+  s->dec.mb = bump<float>(s, G.has_mb ? B * hp.subbands * Tf * hp.istft_hop : 64);
 }
 
 static void drop_graphs(vits_session* s) {
@@ -301,12 +300,8 @@ static int session_reserve(vits_session* s, int B, int Tx, int Ty) {
     for (int c : {hp.dec_initial_channel, 2 * hp.hidden_channels, 2 * hp.inter_channels, hp.dp_filter_channels, hp.bert_dim})
       if (c > widest) widest = c;
     long long worst = (long long)widest * (Ty > Tx ? Ty : Tx);
-    long long rate = 1;
-    for (int i = 0; i < hp.n_ups && i < VITS_MAX_UPS; ++i) {
-      rate *= hp.up_rates[i];
-      const long long e = (long long)(hp.dec_initial_channel >> (i + 1)) * Ty * rate;
-      if (e > worst) worst = e;
-    }
+    const DecGeom& G = s->m->geom;
+    for (int i = 0; i < G.n_ups; ++i) worst = std::max(worst, (long long)G.st[i].cout * Ty * G.st[i].rate_out);
     if (worst * 4 >= (1LL << 31)) return fail(VITS_ERR_ARG, "T_y = %d frames: a per-item decoder tensor would exceed 2 GiB", Ty);
   }
   drop_graphs(s);

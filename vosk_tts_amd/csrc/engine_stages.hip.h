@@ -454,190 +454,127 @@ static float* run_flow(vits_session* s, int B, int Ty) {
 static void set_rag(ConvParams& P, const int* rag, int in_mul, int in_add, int out_mul, int out_add) {
   P.rag = rag; P.rag_in_mul = in_mul; P.rag_in_add = in_add; P.rag_out_mul = out_mul; P.rag_out_add = out_add; P.rag_out_cap_add = 0; P.rag_tab_add = 0;
 }
-// What each decoder layer still has to produce BEYOND an item's end in a ragged batch, in columns of its own output (round 5).  The
-// decoder has no masks: in the reference's padded batch an item's activations continue into the padding, and a valid sample depends on
-// that continuation over the receptive field that is left between a layer and the waveform -- 25 frames at conv_pre, 5 columns after
-// the last ResBlock.  Rounds 1-4 computed len + 32 frames at EVERY layer (10 % of the decoder's work at 330-frame items); now every
-// launch carries its own limit: out = what the layers behind it need, in = what its producer made.  Walked backwards from the tail.
-struct DecNeeds {
-  int pre_out = 0, post_out = 0, tail_cols = 0;
-  int ups_q[8] = {0};                       // polyphase launch: input positions q beyond len * rate_in
-  int c1_out[8][VITS_MAX_RESD] = {{0}}, c2_out[8][VITS_MAX_RESD] = {{0}};
-};
-static DecNeeds decoder_needs(const vits_hparams& hp, bool continuation) {
-  DecNeeds N;
-  if (!continuation) return N;  // halo 0: every item is decoded as if alone (zeros beyond its own end at every stage)
-  int need;  // columns the NEXT consumer wants beyond len * rate, at the current rate
-  if (hp.dec_type == 0 || hp.dec_type == 2) {
-    // iSTFT frame f feeds sub-band samples [f hop, f hop + n_fft); PQMF synthesis reaches (taps / 2) / subbands sub-band samples ahead
-    // (dec_type 2: the same geometry with the learned filter's taps)
-    need = (hp.istft_n_fft + hp.istft_hop - 1) / hp.istft_hop + ((hp.pqmf_taps / 2 + hp.subbands - 1) / hp.subbands + hp.istft_hop - 1) / hp.istft_hop + 2;
-  } else if (hp.dec_type == 3) {
-    need = (hp.istft_n_fft + hp.istft_hop - 1) / hp.istft_hop + 2;  // the iSTFT's reach only: no synthesis filter
-  } else {
-    need = 0;
+// A decoder conv that reads the MRF sum: in[0..2] (null = absent) are added at staging, scaled by in_scale, through leaky_relu(slope).
+// U: the polyphase form of a transposed conv -- output "columns" are the Tout = Tin input positions q, stored at u q + phase.
+static ConvParams dec_sum_conv(const ConvW& W, const float* const in[3], float in_scale, float slope, float* y, int B, int Cin, int Cout,
+                               int Tin, int Tout, int pad_l, int taps, const UpW* U = nullptr, bool reflect = false) {
+  ConvParams P = conv_params(W, in[0], y, B, Tin, 1, pad_l);
+  P.g[0].x2 = in[1]; P.g[0].x3 = in[2]; P.g[0].K = taps;
+  P.Cin = Cin; P.x_bstride = (long long)Cin * Tin;
+  P.Cout = Cout; P.Tout = Tout; P.Tout_stride = U ? Tout * U->u : Tout; P.y_bstride = (long long)(U ? U->cout : Cout) * P.Tout_stride;
+  P.in_slope = slope; P.in_scale = in_scale; P.reflect = reflect;
+  if (U) {
+    P.ups_u = U->u; P.ups_cout = U->cout;
+    for (int r = 0; r < U->u; ++r) P.ups_shift[r] = U->shift[r];
   }
-  N.tail_cols = need;              // the tail reads conv_post columns 0 .. len * rate + need INCLUSIVE ...
-  N.post_out = need + 1;           // ... so conv_post makes need + 1 of them beyond len * rate (it has T + 1 columns: the reflection pad)
-  need += 4;                       // conv_post, 7 taps (pad 4 with the reflection column, 3 without)
-  for (int i = hp.n_ups - 1; i >= 0; --i) {
-    for (int d = hp.n_resd - 1; d >= 0; --d) {
-      int h2 = 0, h1 = 0;
-      for (int j = 0; j < hp.n_resk; ++j) {
-        const int k = hp.res_kernels[j];
-        h2 = std::max(h2, (k - 1) / 2);
-        h1 = std::max(h1, (k - 1) * hp.res_dilations[j][d] / 2);
-      }
-      N.c2_out[i][d] = need; need += h2;
-      N.c1_out[i][d] = need; need += h1;
-    }
-    const int u = hp.up_rates[i], taps = (hp.up_kernels[i] + u - 1) / u;
-    N.ups_q[i] = (need + u - 1) / u + 1;  // output column c = u q + phase
-    need = N.ups_q[i] + taps / 2 + 2;      // input positions a polyphase output reads: q -+ taps / 2 (+ slack for the phase shifts)
-  }
-  N.pre_out = need;
-  return N;
+  return P;
 }
-// rag_halo > 0 (with ragged): the reference's padded-batch continuation -- every valid sample equals the dense padded run (the per-layer
-// limits above; the value only has to be >= the receptive field and is otherwise unused); 0 decodes every item as if it were alone
-// (zeros beyond its own end at every stage), which is what a batch of independent utterances wants (solo batches, the StableTTS path).
+// cont (with ragged): the reference's padded-batch continuation -- every valid sample equals the dense padded run (the per-layer limits
+// of DecGeom::needs); off, every item is decoded as if it were alone (zeros beyond its own end at every stage), which is what a batch
+// of independent utterances wants (solo batches, the StableTTS path).
 static void run_decoder(vits_session* s, const float* z, bool mask_in, int B, int Ty, float* d_audio, long long audio_bstride,
-                        float* d_mb, bool ragged = false, int rag_halo = -1) {
+                        bool ragged = false, bool cont = true) {
   vits_model* m = s->m;
-  if (rag_halo < 0) rag_halo = m->rag_halo;  // default: the reference's padded-batch continuation over the receptive field
   const vits_hparams& hp = m->hp;
-  int C = hp.dec_initial_channel, T = Ty;
+  const DecGeom& G = m->geom;
+  vits_session::DecBufs& W = s->dec;
+  static const DecNeeds alone;
+  const DecNeeds& ND = cont ? G.needs : alone;
   const int* rag = nullptr;
   const int* rag_tail = nullptr;
-  int rate = 1;  // columns per frame at the current stage
-  int final_rate = 1;
-  for (int i = 0; i < hp.n_ups; ++i) final_rate *= hp.up_rates[i];
-  const bool layered = rag_halo > 0;
-  const DecNeeds ND = decoder_needs(hp, layered);
   if (ragged && (B > 1 || s->rag_b1)) {
-    // uniform form: rag = len + halo, the tail may read (len + halo) * rate columns; layered form: rag = len, every launch adds its own need
+    // rag = len: every launch adds its own need; the tail may read len * final_rate + tail_cols columns
     hipLaunchKernelGGL(ragged_len_kernel, dim3(cdiv(B + 1, 64)), dim3(64), 0, s->stream, s->len_y, s->len_rag, s->len_tail, B, Ty,
-                       layered ? 0 : rag_halo, final_rate, layered ? ND.tail_cols : rag_halo * final_rate);
+                       0, G.final_rate, ND.tail_cols);
     rag = s->len_rag;
     rag_tail = s->len_tail;
   }
-  float* cur = s->dec_bufs[0];
-  ConvParams P = conv_params(m->conv_pre, z, cur, B, Ty, 1, 3);
+  ConvParams P = conv_params(m->conv_pre, z, W.pre, B, Ty, 1, 3);
   if (mask_in) { P.in_mask = 1; P.len = s->len_y; }  // (z * y_mask) models.py:1703
   if (m->cond_dec_off >= 0) { P.bias_b = s->condv; P.bias_b_stride = m->cond_rows; P.bias_b_off = m->cond_dec_off; }  // + cond(g)
   set_rag(P, rag, 1, 0, 1, ND.pre_out);
   launch_conv(s, P, EPI_STORE, "dec.conv_pre");
   int prod_add = ND.pre_out;  // columns (at the current rate) the tensor about to be consumed has beyond len * rate
-  const float* in1 = cur; const float* in2 = nullptr; const float* in3 = nullptr;
+  const float* in[3] = {W.pre, nullptr, nullptr};
   float in_scale = 1.f;
-  for (int i = 0; i < hp.n_ups; ++i) {
+  const int nk = hp.n_resk;
+  auto group = [](ConvGroup& g, const ConvW& w, const float* x, float* y, const float* res, int K, int dil) {
+    g.x = x; g.w = w.w; g.wb = w.wb; g.bias = w.bias; g.y = y; g.res = res;
+    g.K = K; g.dil = dil; g.pad_l = (K - 1) * dil / 2; g.n_sg = w.n_sg;
+  };
+  for (int i = 0; i < G.n_ups; ++i) {
+    const DecGeom::Stage& S = G.st[i];
     const UpW& U = m->ups[i];
-    float** set = &s->dec_bufs[1 + 7 * (i & 1)];
-    float* y = set[0];
-    const int Co = U.cout, To = T * U.u;
+    const int p = i & 1, Ti = Ty * S.rate_in, T = Ty * S.rate_out;
+    // two alternating sets of stage buffers: stage i reads set (i - 1) & 1's residual chains, writes set i & 1
+    float* y = W.ups[p];
+    float* const* xt = W.xt[p];
+    float* const* x = W.x[p];
     // x = leaky_relu(x, 0.1); x = ups[i](x)  (models.py:1027-1028), polyphase
-    memset(&P, 0, sizeof P);
-    P.n_groups = 1;
-    P.g[0].x = in1; P.g[0].x2 = in2; P.g[0].x3 = in3; P.g[0].w = U.w.w; P.g[0].wb = U.w.wb; P.g[0].bias = U.w.bias; P.g[0].y = y;
-    P.g[0].K = U.taps; P.g[0].dil = 1; P.g[0].pad_l = U.pad_l; P.g[0].n_sg = U.w.n_sg;
-    P.B = B; P.Cin = C; P.x_ch_sign = 1; P.x_bstride = (long long)C * T; P.Tin = T; P.Tin_stride = T;
-    P.M = U.w.Mpad; P.Cout = U.w.M; P.Tout = T; P.Tout_stride = To; P.y_bstride = (long long)Co * To;
-    P.in_slope = 0.1f; P.in_scale = in_scale;
-    P.ups_u = U.u; P.ups_cout = Co;
-    for (int r = 0; r < U.u; ++r) P.ups_shift[r] = U.shift[r];
-    set_rag(P, rag, rate, prod_add, rate, ND.ups_q[i]);  // polyphase: output "columns" are input positions q
+    P = dec_sum_conv(U.w, in, in_scale, 0.1f, y, B, S.cin, U.w.M, Ti, Ti, U.pad_l, U.taps, &U);
+    set_rag(P, rag, S.rate_in, prod_add, S.rate_in, ND.ups_q[i]);  // polyphase: output "columns" are input positions q
     launch_conv(s, P, EPI_STORE, "dec.ups", U.halo);
-    C = Co; T = To; rate *= U.u;
-    prod_add = ND.ups_q[i] * U.u;
+    prod_add = ND.ups_q[i] * S.u;
     // MRF: 3 ResBlock1 chains in grouped launches (modules.py:210-223)
-    const int nk = hp.n_resk;
     // (Round 4 experiment, removed: the three chains as three branches of the captured graph -- one stream each, forked and joined
     //  with events -- so that a chain's per-launch fixed cost runs under the other chains' matrix work: c2 0.856 -> 0.921 ms, 19 -> 43
     //  graph nodes; the cross-queue dependencies cost more than the overlap returns.  profiles/r4_decoder_split.txt)
     for (int d = 0; d < hp.n_resd; ++d) {
-      memset(&P, 0, sizeof P);
-      P.n_groups = nk;
-      for (int j = 0; j < nk; ++j) {  // xt = c1(leaky_relu(x))
-        const ResBlockW& R = m->rb[(size_t)i * nk + j];
-        P.g[j].x = d == 0 ? y : set[4 + j];
-        P.g[j].w = R.c1[d].w; P.g[j].wb = R.c1[d].wb; P.g[j].bias = R.c1[d].bias; P.g[j].y = set[1 + j];
-        P.g[j].K = R.K; P.g[j].dil = R.dil[d]; P.g[j].pad_l = (R.K - 1) * R.dil[d] / 2; P.g[j].n_sg = R.c1[d].n_sg;
-      }
-      P.B = B; P.Cin = C; P.x_ch_sign = 1; P.x_bstride = (long long)C * T; P.Tin = T; P.Tin_stride = T;
-      P.M = m->rb[(size_t)i * nk].c1[d].Mpad; P.Cout = C; P.Tout = T; P.Tout_stride = T; P.y_bstride = (long long)C * T;
-      P.in_slope = 0.1f; P.in_scale = 1.f;
-      set_rag(P, rag, rate, prod_add, rate, ND.c1_out[i][d]);
+      const ResBlockW* R = &m->rb[(size_t)i * nk];
+      P = conv_params(R[0].c1[d], nullptr, nullptr, B, T, 1, 0);
+      P.n_groups = nk; P.in_slope = 0.1f;
+      for (int j = 0; j < nk; ++j) group(P.g[j], R[j].c1[d], d == 0 ? y : x[j], xt[j], nullptr, R[j].K, R[j].dil[d]);  // xt = c1(leaky_relu(x))
+      set_rag(P, rag, S.rate_out, prod_add, S.rate_out, ND.c1_out[i][d]);
       P.rag_tab_add = ND.c1_out[i][0];  // one compact tile map for the six launches of the stage (its widest limit)
       launch_conv(s, P, EPI_STORE, "dec.res_c1");
-      for (int j = 0; j < nk; ++j) {  // x = c2(leaky_relu(xt)) + x
-        const ResBlockW& R = m->rb[(size_t)i * nk + j];
-        P.g[j].x = set[1 + j];
-        P.g[j].w = R.c2[d].w; P.g[j].wb = R.c2[d].wb; P.g[j].bias = R.c2[d].bias; P.g[j].y = set[4 + j];
-        P.g[j].res = d == 0 ? y : set[4 + j];
-        P.g[j].K = R.K; P.g[j].dil = 1; P.g[j].pad_l = (R.K - 1) / 2; P.g[j].n_sg = R.c2[d].n_sg;
-      }
-      set_rag(P, rag, rate, ND.c1_out[i][d], rate, ND.c2_out[i][d]);
+      for (int j = 0; j < nk; ++j) group(P.g[j], R[j].c2[d], xt[j], x[j], d == 0 ? y : x[j], R[j].K, 1);  // x = c2(leaky_relu(xt)) + x
+      set_rag(P, rag, S.rate_out, ND.c1_out[i][d], S.rate_out, ND.c2_out[i][d]);
       P.rag_tab_add = ND.c1_out[i][0];
       launch_conv(s, P, EPI_STORE, "dec.res_c2");
       prod_add = ND.c2_out[i][d];
     }
-    in1 = set[4]; in2 = nk > 1 ? set[5] : nullptr; in3 = nk > 2 ? set[6] : nullptr;
+    in[0] = x[0]; in[1] = nk > 1 ? x[1] : nullptr; in[2] = nk > 2 ? x[2] : nullptr;
     in_scale = 1.0f / (float)nk;  // x = xs / num_kernels (models.py:1036), folded into the next staging
   }
-  float* post = s->dec_bufs[15];
-  float* mb = d_mb ? d_mb : s->dec_bufs[16];
-  if (hp.dec_type == 0 || hp.dec_type == 2 || hp.dec_type == 3) {
-    // leaky_relu(0.01) -> ReflectionPad1d((1,0)) -> subband_conv_post (models.py:1038-1040; dec_type 2 with its bias, :1095-1097;
-    // dec_type 3: conv_post into n_fft + 2 rows, :943-945)
-    const int Tp = T + 1, Pc = m->conv_post.M;
-    memset(&P, 0, sizeof P);
-    P.n_groups = 1;
-    P.g[0].x = in1; P.g[0].x2 = in2; P.g[0].x3 = in3; P.g[0].w = m->conv_post.w; P.g[0].bias = m->conv_post.bias; P.g[0].y = post;
-    P.g[0].K = 7; P.g[0].dil = 1; P.g[0].pad_l = 4; P.g[0].n_sg = m->conv_post.n_sg;
-    P.B = B; P.Cin = C; P.x_ch_sign = 1; P.x_bstride = (long long)C * T; P.Tin = T; P.Tin_stride = T;
-    P.M = m->conv_post.Mpad; P.Cout = Pc; P.Tout = Tp; P.Tout_stride = Tp; P.y_bstride = (long long)Pc * Tp;
-    P.in_slope = 0.01f; P.in_scale = in_scale; P.reflect = 1;
-    set_rag(P, rag, rate, prod_add, rate, layered ? ND.post_out : 1);
-    P.rag_out_cap_add = 1;  // T + 1 output columns
-    launch_conv(s, P, EPI_STORE, "dec.conv_post");
-    const int S = hp.subbands, N = hp.istft_n_fft, hop = hp.istft_hop, Tm = T * hop;
-    if (hp.dec_type == 3) {  // single band: the iSTFT samples are the waveform
-      if (g_tail_impl == 0) {  // one launch: exp/sin and iSTFT through LDS, straight to audio
-        ProfScope ps(s, "istft", 0, "istft_tail_kernel<false>");
-        TailParams tp{post, m->istft_basis, nullptr, nullptr, d_audio, 1, N, hop, Tp, Tm, 0, audio_bstride, rag_tail, hop};
-        hipLaunchKernelGGL(istft_tail_kernel<false>, dim3(cdiv(Tm, TAIL_SB), B), dim3(256), m->tail_lds, s->stream, tp);
-      } else {
-        ProfScope ps(s, "istft", 0, "istft_kernel");
-        hipLaunchKernelGGL(istft_kernel, dim3(cdiv(Tm, 256), 1, B), dim3(256), 0, s->stream, post, m->istft_basis, d_audio, 1, N, hop, Tp, Tm,
-                           audio_bstride, rag_tail, hop, 1);
-      }
-    } else if (g_tail_impl == 0) {  // one launch: exp/sin, iSTFT and PQMF (dec_type 2: the learned filter) through LDS
-      ProfScope ps(s, "istft_pqmf", 0, "istft_tail_kernel<true>");
-      TailParams tp{post, m->istft_basis, m->pqmf, mb, d_audio, S, N, hop, Tp, Tm, hp.pqmf_taps, audio_bstride, rag_tail, hop};  // (rag_tail: conv_post columns that exist)
-      hipLaunchKernelGGL(istft_tail_kernel<true>, dim3(cdiv(Tm, TAIL_MB), B), dim3(256), m->tail_lds, s->stream, tp);
-    } else {
-      {
-        ProfScope ps(s, "istft", 0, "istft_kernel");
-        hipLaunchKernelGGL(istft_kernel, dim3(cdiv(Tm, 256), S, B), dim3(256), 0, s->stream, post, m->istft_basis, mb, S, N, hop, Tp, Tm,
-                           (long long)S * Tm, rag_tail, hop, 0);
-      }
-      {
-        ProfScope ps(s, "pqmf", 0, "pqmf_synthesis_kernel");
-        hipLaunchKernelGGL(pqmf_synthesis_kernel, dim3(cdiv(Tm * S, 256), B), dim3(256), 0, s->stream, mb, m->pqmf, d_audio, S,
-                           hp.pqmf_taps, Tm, audio_bstride, rag_tail, hop * S);
-      }
-    }
-  } else {
-    memset(&P, 0, sizeof P);
-    P.n_groups = 1;
-    P.g[0].x = in1; P.g[0].x2 = in2; P.g[0].x3 = in3; P.g[0].w = m->conv_post.w; P.g[0].bias = m->conv_post.bias; P.g[0].y = post;
-    P.g[0].K = 7; P.g[0].dil = 1; P.g[0].pad_l = 3; P.g[0].n_sg = m->conv_post.n_sg;
-    P.B = B; P.Cin = C; P.x_ch_sign = 1; P.x_bstride = (long long)C * T; P.Tin = T; P.Tin_stride = T;
-    P.M = m->conv_post.Mpad; P.Cout = 1; P.Tout = T; P.Tout_stride = T; P.y_bstride = T;
-    P.in_slope = 0.01f; P.in_scale = in_scale;
-    set_rag(P, rag, rate, prod_add, rate, layered ? ND.post_out : 0);
-    launch_conv(s, P, EPI_STORE, "dec.conv_post");
+  // leaky_relu(0.01) [-> ReflectionPad1d((1,0))] -> conv_post: subband_conv_post (models.py:1038-1040; dec_type 2 with its bias, :1095-1097),
+  // dec_type 3 into n_fft + 2 rows (:943-945), the plain Generator into one row (:889-891)
+  const int T = Ty * G.final_rate, Tp = T + G.reflect, C = G.st[G.n_ups - 1].cout;
+  float* post = W.post;
+  P = dec_sum_conv(m->conv_post, in, in_scale, 0.01f, post, B, C, G.post_rows, T, Tp, G.post_pad, 7, nullptr, G.reflect);
+  set_rag(P, rag, G.final_rate, prod_add, G.final_rate, cont ? ND.post_out : (int)G.reflect);  // (alone: only the reflection column)
+  P.rag_out_cap_add = G.reflect;  // T + 1 output columns
+  launch_conv(s, P, EPI_STORE, "dec.conv_post");
+  if (!G.reflect) {  // the plain Generator: tanh
     hipLaunchKernelGGL(tanh_copy_kernel, dim3(cdiv(T, 256), B), dim3(256), 0, s->stream, post, d_audio, T, (long long)T, audio_bstride, rag_tail, 1);
+    return;
+  }
+  float* mb = W.mb;
+  const int S = hp.subbands, N = hp.istft_n_fft, hop = hp.istft_hop, Tm = T * hop;
+  if (!G.has_mb) {  // single band: the iSTFT samples are the waveform
+    if (g_tail_impl == 0) {  // one launch: exp/sin and iSTFT through LDS, straight to audio
+      ProfScope ps(s, "istft", 0, "istft_tail_kernel<false>");
+      TailParams tp{post, m->istft_basis, nullptr, nullptr, d_audio, 1, N, hop, Tp, Tm, 0, audio_bstride, rag_tail, hop};
+      hipLaunchKernelGGL(istft_tail_kernel<false>, dim3(cdiv(Tm, TAIL_SB), B), dim3(256), m->tail_lds, s->stream, tp);
+    } else {
+      ProfScope ps(s, "istft", 0, "istft_kernel");
+      hipLaunchKernelGGL(istft_kernel, dim3(cdiv(Tm, 256), 1, B), dim3(256), 0, s->stream, post, m->istft_basis, d_audio, 1, N, hop, Tp, Tm,
+                         audio_bstride, rag_tail, hop, 1);
+    }
+  } else if (g_tail_impl == 0) {  // one launch: exp/sin, iSTFT and PQMF (dec_type 2: the learned filter) through LDS
+    ProfScope ps(s, "istft_pqmf", 0, "istft_tail_kernel<true>");
+    TailParams tp{post, m->istft_basis, m->pqmf, mb, d_audio, S, N, hop, Tp, Tm, hp.pqmf_taps, audio_bstride, rag_tail, hop};  // (rag_tail: conv_post columns that exist)
+    hipLaunchKernelGGL(istft_tail_kernel<true>, dim3(cdiv(Tm, TAIL_MB), B), dim3(256), m->tail_lds, s->stream, tp);
+  } else {
+    {
+      ProfScope ps(s, "istft", 0, "istft_kernel");
+      hipLaunchKernelGGL(istft_kernel, dim3(cdiv(Tm, 256), S, B), dim3(256), 0, s->stream, post, m->istft_basis, mb, S, N, hop, Tp, Tm,
+                         (long long)S * Tm, rag_tail, hop, 0);
+    }
+    {
+      ProfScope ps(s, "pqmf", 0, "pqmf_synthesis_kernel");
+      hipLaunchKernelGGL(pqmf_synthesis_kernel, dim3(cdiv(Tm * S, 256), B), dim3(256), 0, s->stream, mb, m->pqmf, d_audio, S,
+                         hp.pqmf_taps, Tm, audio_bstride, rag_tail, hop * S);
+    }
   }
 }
 
@@ -717,7 +654,7 @@ static void forward_device(vits_session* s, const int64_t* d_ids, const int64_t*
     run_expand(s, nullptr, Ty, scales[0], seed, s->zA, B, Tx, Ty);
     z = run_flow(s, B, Ty);
   }
-  run_decoder(s, z, true, B, Ty, d_audio, cap, nullptr, true);
+  run_decoder(s, z, true, B, Ty, d_audio, cap, true);
   s->ragged = false;
 }
 

@@ -43,7 +43,7 @@ static int stream_launch(vits_stream* st, int lo, int slot) {
   w.start = start;
   hipLaunchKernelGGL(window_copy_kernel, dim3(cdiv(width, 256), I), dim3(256), 0, s->stream, st->z, (long long)st->Ty, start, width, st->d_win);
   const long long S = (long long)width * st->m->hp.hop_length;
-  run_decoder(s, st->d_win, false, 1, width, w.aud, S, nullptr);
+  run_decoder(s, st->d_win, false, 1, width, w.aud, S);
   if (st->clamp) hipLaunchKernelGGL(clamp_kernel, dim3(cdiv((int)S, 256)), dim3(256), 0, s->stream, w.aud, S);
   HIP_TRY(hipEventRecord(w.done, s->stream));
   return VITS_OK;

@@ -811,7 +811,7 @@ static int stts_phase2(stts_model* m, SttsFront* F, SttsBack* Bk, bool audio) {
       sv->tile_keys.clear();
       sv->ragged = true; sv->rag_b1 = true;
       hipMemcpyAsync(sv->len_y, d_len, sizeof(int), hipMemcpyDeviceToDevice, st);
-      run_decoder(sv, Bk->d_mel, false, 1, TB, Bk->d_audio, (long long)Bk->audio_elems, nullptr, true, 0);
+      run_decoder(sv, Bk->d_mel, false, 1, TB, Bk->d_audio, (long long)Bk->audio_elems, true, false);
       sv->ragged = false; sv->rag_b1 = false;
       sv->stream = own;
       hipLaunchKernelGGL(clamp_kernel, dim3(cdiv((int)Bk->audio_elems, 256)), dim3(256), 0, st, Bk->d_audio, (long long)Bk->audio_elems);
@@ -1010,7 +1010,7 @@ int stts_synthesize(stts_model* m, const int64_t* ids, int32_t Tx, const float* 
       // consumed in stream order, no host synchronisation between the two halves
       hipStream_t own = sv->stream;
       sv->stream = s->stream;
-      run_decoder(sv, d_mel, false, 1, (int)ylen, d_audio, S, nullptr);
+      run_decoder(sv, d_mel, false, 1, (int)ylen, d_audio, S);
       sv->stream = own;
       hipLaunchKernelGGL(clamp_kernel, dim3(cdiv((int)S, 256)), dim3(256), 0, s->stream, d_audio, (long long)S);
       hipMemcpyAsync(h_audio, d_audio, sizeof(float) * (size_t)S, hipMemcpyDeviceToHost, s->stream);
@@ -1133,7 +1133,7 @@ int stts_synthesize_batch(stts_model* m, const int64_t* ids, const int64_t* leng
     sv->tile_keys.clear();
     sv->ragged = B > 1;
     hipMemcpyAsync(sv->len_y, d_len, sizeof(int) * B, hipMemcpyDeviceToDevice, s->stream);
-    run_decoder(sv, d_mel, false, B, Tm, d_audio, S, nullptr, true, 0);
+    run_decoder(sv, d_mel, false, B, Tm, d_audio, S, true, false);
     sv->ragged = false;
     sv->stream = own;
     hipLaunchKernelGGL(clamp_kernel, dim3(cdiv((int)(B * S), 256)), dim3(256), 0, s->stream, d_audio, (long long)B * S);
