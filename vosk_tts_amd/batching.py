@@ -59,6 +59,13 @@ def scatter_results(n_requests, shards, shard_outputs):
     return out
 
 
+# Smallest part of a shard whose front end runs as one batched BERT call (Synth.front_batch).  profiles/bert_batch_bench.txt
+# (tools/bert_batch_bench.py, rubert-base geometry, sentences of 9 - 40 tokens): one sentence is a tie (0.83 ms either way: the solo
+# call replays a captured graph, the batched one launches eagerly), from two sentences on the batched call wins (1.5x at 2, 2.0x at 4,
+# 2.9x at 8, 4.0x at 16, 3.5x at 32 against as many solo calls), so a part of one request keeps the per-request front end.
+BATCHED_FRONT_MIN = 2
+
+
 class MultiDeviceSynth:
     """Batched multi-utterance synthesis over N device replicas in ONE process (BASELINE north_star: "Batched multi-utterance
     synthesis shards across the 8 GPUs of one node as embarrassingly-parallel data replicas"; SURVEY.md 8e: "one host thread
@@ -76,7 +83,7 @@ class MultiDeviceSynth:
         pcm = mds.synth_batch(["...", "..."], speaker_ids=2)        # list of int16 arrays, request order
     """
 
-    def __init__(self, model_path=None, devices=None, model_name=None, lang=None, max_batch=32):
+    def __init__(self, model_path=None, devices=None, model_name=None, lang=None, max_batch=32, batched_front=True):
         from .model import Model
         from .synth import Synth
 
@@ -89,6 +96,10 @@ class MultiDeviceSynth:
             raise ValueError("no devices")
         self.devices = list(devices)
         self.max_batch = int(max_batch)
+        # BERT-conditioned families: front end of a whole part in one Synth.front_batch call (one padded BERT forward, the phoneme
+        # feed gathered on the device) where the voice's BERT session has the batched entry points; False keeps the per-request
+        # front end (get_word_bert per text)
+        self.batched_front = bool(batched_front)
         self.models = [Model(model_path=model_path, model_name=model_name, lang=lang, device=d) for d in self.devices]
         # the three voice families of vosk_tts/synth.py:64-103 behind the same door:
         #   "vits"        plain VITS (g2p_noembed -> token ids)                              -> vits_synthesize_pcm16, solo batch
@@ -168,10 +179,39 @@ class MultiDeviceSynth:
                 self._seed += n
         return scales, scale, sids, list(seeds)
 
-    def _run_shard_bert(self, r, texts, idx, sids, scales, scale, seeds):
+    def _front_is_batched(self, r, n):
+        """whether a part of n requests on replica r takes Synth.front_batch"""
+        enc = getattr(self.models[r], "bert_onnx", None)
+        return self.batched_front and n >= BATCHED_FRONT_MIN and (self.models[r].tokenizer is None or getattr(enc, "has_batch", False))
+
+    def _run_parts(self, r, idx, run_part, per_request):
+        """`idx` (sorted by descending estimated length by plan_shards) in parts of <= max_batch: run_part(part) for every part that
+        takes front_batch, per_request(rest) once for the requests of all the others -> results in the order of idx"""
+        out, rest = {}, []
+        for k in range(0, len(idx), self.max_batch):
+            part = idx[k:k + self.max_batch]
+            if self._front_is_batched(r, len(part)):
+                out.update(zip(part, run_part(part)))
+            else:
+                rest.extend(part)
+        if rest:
+            out.update(zip(rest, per_request(rest)))
+        return [out[i] for i in idx]
+
+    def _run_shard_bert(self, r, texts, idx, sids, scales, scale, seeds, per_request=False):
         """BERT-conditioned VITS requests `idx` on replica r: get_word_bert + g2p / g2p_noblank per request (synth.py:88-99), then padded
         solo batches with a padded `bert` feed [B, 768, T]"""
         synth, sess = self.synths[r], self.models[r].onnx
+        if not per_request:
+            def run_part(part):
+                f = synth.front_batch([texts[i] for i in part], [sids[i] for i in part])
+                feed = {"input": f["input"], "input_lengths": f["input_lengths"], "scales": scales, "sid": f["sid"], "bert": f["bert"],
+                        "phone_duration_extra": None, "vits.solo": True, "vits.item_seeds": np.array([seeds[i] for i in part], np.uint64)}
+                with self._replica_locks[r]:
+                    pcm, lengths = sess.run_pcm16(feed, scale, return_lengths=True)
+                return [pcm[b, :int(lengths[b])].copy() for b in range(len(part))]
+
+            return self._run_parts(r, idx, run_part, lambda rest: self._run_shard_bert(r, texts, rest, sids, scales, scale, seeds, per_request=True))
         fe = synth.g2p_noblank if synth.model.config.get("no_blank", 0) != 0 else synth.g2p
         fronts = []
         for i in idx:
@@ -197,10 +237,19 @@ class MultiDeviceSynth:
                 out[k] = pcm[b, :int(lengths[b])].copy()
         return out
 
-    def _run_shard_multistream(self, r, texts, idx, sids, scales, scale, seeds):
+    def _run_shard_multistream(self, r, texts, idx, sids, scales, scale, seeds, per_request=False):
         """multistream (StableTTS / Matcha) requests `idx` on replica r: the five-stream front end of Synth._feed per request
         (synth.py:64-87), then stts_synthesize_batch with per-request seeds; float -> int16 as Synth.audio_float_to_int16"""
         synth, sess = self.synths[r], self.models[r].onnx
+        if not per_request:
+            def run_part(part):
+                f = synth.front_batch([texts[i] for i in part], [sids[i] for i in part])
+                with self._replica_locks[r]:
+                    audio, ol = sess._model.synthesize_batch(f["input"], f["input_lengths"], scales, f["sid"], f["bert"], f["phone_duration_extra"],
+                                                             seed=0, item_seeds=np.array([seeds[i] for i in part], np.uint64))
+                return [synth.audio_float_to_int16(audio[b, :int(ol[b])] * scale) for b in range(len(part))]
+
+            return self._run_parts(r, idx, run_part, lambda rest: self._run_shard_multistream(r, texts, rest, sids, scales, scale, seeds, per_request=True))
         fronts = []
         for i in idx:
             feed, _ = synth._feed(texts[i], sids[i], None, None, None, None)

@@ -208,6 +208,11 @@ class BertEncoder:
         f("destroy").restype = None
         f("get_hparams").argtypes = [vp, ctypes.POINTER(BertHParams)]
         f("encode").argtypes = [vp, c_i64p, c_i64p, ctypes.c_int32, c_f32p]
+        # include/stts_bert_batch.h: padded batches, an extension of the product library (the CPU oracle encodes one sentence)
+        self.has_batch = hasattr(vlib.lib, self.prefix + "encode_batch") and hasattr(vlib.lib, self.prefix + "feed_batch")
+        if self.has_batch:
+            f("encode_batch").argtypes = [vp, c_i64p, c_i64p, c_i32p, ctypes.c_int32, ctypes.c_int32, c_f32p]
+            f("feed_batch").argtypes = [vp, c_i64p, c_i64p, c_i32p, ctypes.c_int32, ctypes.c_int32, c_i32p, ctypes.c_int32, c_f32p]
         self._err = getattr(vlib.lib, "stts_last_error" if vlib.prefix == "vits_" else "sttsref_last_error")
         self._err.restype = ctypes.c_char_p
         self._h = vp()
@@ -228,6 +233,77 @@ class BertEncoder:
         ty = None if token_type_ids is None else _i64(token_type_ids).reshape(-1)
         out = np.empty((ids.shape[0], self.hp.hidden), np.float32)
         self._check(self._fn("encode")(self._h, _p(ids, c_i64p), None if ty is None else _p(ty, c_i64p), ids.shape[0], _p(out, c_f32p)))
+        return out
+
+    def _pad_ids(self, id_lists, token_type_ids):
+        """-> ids int64 [B, T], types int64 [B, T] or None, lengths int32 [B] (padding entries are never read by the library)"""
+        if not self.has_batch:
+            raise NotImplementedError("this library has no batched BERT entry points (include/stts_bert_batch.h)")
+        seqs = [_i64(a).reshape(-1) for a in id_lists]
+        if not seqs:
+            raise ValueError("empty batch")
+        lens = np.array([a.shape[0] for a in seqs], np.int32)
+        B, T = len(seqs), max(int(lens.max()), 1)
+        ids = np.zeros((B, T), np.int64)
+        for b, a in enumerate(seqs):
+            ids[b, :lens[b]] = a
+        ty = None
+        if token_type_ids is not None:
+            if len(token_type_ids) != B:
+                raise ValueError("token_type_ids must hold one array per sentence")
+            ty = np.zeros((B, T), np.int64)
+            for b, a in enumerate(token_type_ids):
+                a = _i64(a).reshape(-1)
+                if a.shape[0] != lens[b]:
+                    raise ValueError(f"token_type_ids[{b}] has {a.shape[0]} entries for {lens[b]} tokens")
+                ty[b, :lens[b]] = a
+        return ids, ty, lens
+
+    def encode_batch(self, id_lists, token_type_ids=None):
+        """stts_bert_encode_batch: B sentences of any lengths in ONE padded forward -> list of float32 [T_b, hidden], item b what
+        encode(id_lists[b]) returns (to rounding: the batch takes other conv / attention tiles than a lone sentence)."""
+        ids, ty, lens = self._pad_ids(id_lists, token_type_ids)
+        out = self.encode_batch_padded(ids, ty, lens)
+        return [out[b, :lens[b]].copy() for b in range(len(lens))]
+
+    def encode_batch_padded(self, ids, token_type_ids, lengths):
+        """the call itself on padded arrays: ids / token_type_ids [B, T] (types may be None), lengths [B] -> float32 [B, T, hidden],
+        rows beyond lengths[b] zero"""
+        ids = _i64(ids); lens = _i32(lengths)
+        ty = None if token_type_ids is None else _i64(token_type_ids)
+        if ids.ndim != 2 or lens.shape != (ids.shape[0],) or (ty is not None and ty.shape != ids.shape):
+            raise ValueError("ids / token_type_ids must be [B, T], lengths [B]")
+        B, T = ids.shape
+        out = np.empty((B, T, self.hp.hidden), np.float32)
+        self._check(self._fn("encode_batch")(self._h, _p(ids, c_i64p), _p(ty, c_i64p), _p(lens, c_i32p), B, T, _p(out, c_f32p)))
+        return out
+
+    def feed_batch(self, id_lists, row_lists, T_x=None, token_type_ids=None):
+        """stts_bert_feed_batch: the same forward and, still on the device, the phoneme feed of the acoustic models:
+        -> float32 [B, hidden, T_x] with out[b, :, t] = hidden state of token row_lists[b][t] of sentence b; a negative row and
+        every column beyond len(row_lists[b]) is zero.  T_x defaults to the longest row list."""
+        ids, ty, lens = self._pad_ids(id_lists, token_type_ids)
+        if len(row_lists) != len(lens):
+            raise ValueError("one row list per sentence")
+        rl = [_i32(r).reshape(-1) for r in row_lists]
+        longest = max(r.shape[0] for r in rl)
+        T_x = max(longest, 1) if T_x is None else int(T_x)
+        if T_x < longest:
+            raise ValueError(f"T_x = {T_x} is shorter than the longest row list ({longest})")
+        rows = np.full((len(rl), T_x), -1, np.int32)
+        for b, r in enumerate(rl):
+            rows[b, :r.shape[0]] = r
+        return self.feed_batch_padded(ids, ty, lens, rows)
+
+    def feed_batch_padded(self, ids, token_type_ids, lengths, rows):
+        ids = _i64(ids); lens = _i32(lengths); rows = _i32(rows)
+        ty = None if token_type_ids is None else _i64(token_type_ids)
+        if ids.ndim != 2 or rows.ndim != 2 or rows.shape[0] != ids.shape[0] or lens.shape != (ids.shape[0],) or (ty is not None and ty.shape != ids.shape):
+            raise ValueError("ids / token_type_ids must be [B, T], lengths [B], rows [B, T_x]")
+        B, T = ids.shape
+        out = np.empty((B, self.hp.hidden, rows.shape[1]), np.float32)
+        self._check(self._fn("feed_batch")(self._h, _p(ids, c_i64p), _p(ty, c_i64p), _p(lens, c_i32p), B, T, _p(rows, c_i32p), rows.shape[1],
+                                           _p(out, c_f32p)))
         return out
 
     def run(self, output_names, feed):

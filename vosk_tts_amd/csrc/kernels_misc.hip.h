@@ -1393,6 +1393,36 @@ __global__ void transpose_ct_kernel(const float* x, float* y, int C, int T) {  /
   const int c = blockIdx.x * blockDim.x + threadIdx.x, t = blockIdx.y;
   if (c < C) y[(long long)t * C + c] = x[(long long)c * T + t];
 }
+// Padded batch of sentences (stts_bert_encode_batch / stts_bert_feed_batch): ids / types [B][T], x [B][H][T], positions count from 0 in
+// every item.  Columns at or beyond len[b] take the [PAD] token's embedding (id 0, type 0) WITHOUT reading ids / types there, as the
+// bucket columns of the solo graph path do: nothing valid reads them (every op of the encoder is column-local except attention, which
+// masks keys at the length).
+__global__ void bert_embed_batch_kernel(const int64_t* ids, const int64_t* types, const int* len, const float* we, const float* pe, const float* te,
+                                        float* x, int H, int T, int vocab, int type_vocab, int* err) {
+  const int t = blockIdx.x * blockDim.x + threadIdx.x, c = blockIdx.y, b = blockIdx.z;
+  if (t >= T) return;
+  long long id = 0, ty = 0;
+  if (t < len[b]) {
+    id = ids[(long long)b * T + t];
+    ty = types ? types[(long long)b * T + t] : 0;
+    if (id < 0 || id >= vocab || ty < 0 || ty >= type_vocab) { atomicOr(err, 1); id = 0; ty = 0; }
+  }
+  x[((long long)b * H + c) * T + t] = we[id * H + c] + pe[(long long)t * H + c] + te[ty * H + c];
+}
+// The phoneme feed of the acoustic models straight from the encoder's channel-major activations: y[b][c][t] = x[b][c][rows[b][t]],
+// a negative row = a zero column.  x [B][C][T], y [B][C][Tx], rows [B][Tx] (< T: checked by the host).  A wave owns 64 consecutive t of
+// one channel row: its loads stay inside that row's T floats (a few cache lines), its stores are contiguous.  Block 64 x 4 channels.
+__global__ void bert_gather_cols_kernel(const float* x, const int* rows, float* y, int C, int T, int Tx) {
+  const int t = blockIdx.x * 64 + threadIdx.x, c = blockIdx.y * 4 + threadIdx.y, b = blockIdx.z;
+  if (t >= Tx || c >= C) return;
+  const int r = rows[(long long)b * Tx + t];
+  y[((long long)b * C + c) * Tx + t] = (r >= 0 && r < T) ? x[((long long)b * C + c) * T + r] : 0.f;
+}
+// [B][C][T] -> [B][T][C], rows at or beyond len[b] written as 0
+__global__ void transpose_ct_batch_kernel(const float* x, const int* len, float* y, int C, int T) {
+  const int c = blockIdx.x * blockDim.x + threadIdx.x, t = blockIdx.y, b = blockIdx.z;
+  if (c < C) y[((long long)b * T + t) * C + c] = t < len[b] ? x[((long long)b * C + c) * T + t] : 0.f;
+}
 
 // ----------------------------------------------------------------------------- attention, few-column form
 // Same math as relpos_attention_mfma_kernel (attentions.py:165-260, exact banded relative positions) for SHORT sequences

@@ -4,6 +4,7 @@
 // applied to q/k beforehand), the adaLN / FiLM / Euler glue on the small kernels at the end of kernels_misc.hip.h.
 // Reference citations are relative to /root/reference/training/stabletts/matcha/.
 #include "../../include/stts_mi355.h"
+#include "../../include/stts_bert_batch.h"
 
 struct DitW {  // DiTConVBlock (models/components/diffusion_transformer.py:82-118)
   ConvW qkv, o, c1, c2;
@@ -1279,31 +1280,38 @@ int stts_bert_get_hparams(const bert_model* m, bert_hparams* out) {
   return VITS_OK;
 }
 
-// the encoder's launches on session s: ids / types int64 [T] and len int32 on the device -> ot [T][H]
-static void bert_forward(bert_model* m, vits_session* s, const int64_t* d_ids, const int64_t* d_ty, const int* d_len, int T, float* x, float* y, float* att,
-                         float* qkv, float* ff, float* ot) {
+// the encoder's launches on session s: ids / types int64 [B][T] and len int32 [B] on the device -> final hidden states x [B][H][T]
+// (channel-major), and for one sentence (ot != null) ot [T][H].  padded = false is the single-sentence form (B = 1, every column a token
+// the caller supplied: a whole sentence, or a bucket the caller filled with [PAD]); padded = true reads ids / types below len[b] only.
+static void bert_forward(bert_model* m, vits_session* s, const int64_t* d_ids, const int64_t* d_ty, const int* d_len, int B, int T, bool padded,
+                         float* x, float* y, float* att, float* qkv, float* ff, float* ot) {
   const bert_hparams& hp = m->hp;
   const int H = hp.hidden, nh = hp.n_heads;
-  hipLaunchKernelGGL(bert_embed_kernel, dim3(cdiv(T, 64), H), dim3(64), 0, s->stream, d_ids, d_ty, m->we, m->pe, m->te, y, H, T,
-                     hp.vocab_size, hp.type_vocab, s->d_err);
+  if (padded)
+    hipLaunchKernelGGL(bert_embed_batch_kernel, dim3(cdiv(T, 64), H, B), dim3(64), 0, s->stream, d_ids, d_ty, d_len, m->we, m->pe, m->te, y, H, T,
+                       hp.vocab_size, hp.type_vocab, s->d_err);
+  else
+    hipLaunchKernelGGL(bert_embed_kernel, dim3(cdiv(T, 64), H), dim3(64), 0, s->stream, d_ids, d_ty, m->we, m->pe, m->te, y, H, T,
+                       hp.vocab_size, hp.type_vocab, s->d_err);
   {
     LNParams P{y, nullptr, nullptr, x, m->eg, m->eb, nullptr, H, T, 0, 0, 0, 0, hp.ln_eps, nullptr, nullptr};
-    launch_layernorm(s->stream, P, 1);
+    launch_layernorm(s->stream, P, B);
   }
   // (round 5) sentence-sized calls: the 3072 -> 768 matrix of the FFN is the one launch of a layer that ran on 24 CUs (21 us of a 75 us
   // layer, profiles/r5_bert_ffn2.txt)
-  const bool ffn2_slices = conv_select().force_tile == 0 && T <= 64 && T >= 4 && hp.intermediate % (3 * CONV_CI_T) == 0 && hp.intermediate / 3 >= 8 * CONV_CI_T &&
+  // the sliced launch describes ONE item (its groups' x_bstride is a slice, not the tensor): batches take launch_conv
+  const bool ffn2_slices = B == 1 && conv_select().force_tile == 0 && T <= 64 && T >= 4 && hp.intermediate % (3 * CONV_CI_T) == 0 && hp.intermediate / 3 >= 8 * CONV_CI_T &&
                            H % 32 == 0 && !m->layers.empty() && m->layers[0].c2.K == 1;
   for (const BertLayerW& L : m->layers) {
-    ConvParams P = conv_params(L.qkv, x, qkv, 1, T, 1, 0);
+    ConvParams P = conv_params(L.qkv, x, qkv, B, T, 1, 0);
     launch_conv(s, P, EPI_STORE, "bert.qkv");
-    launch_attention_raw(s, qkv, nullptr, nullptr, d_len, att, 1, H, T, nh, 4);
-    P = conv_params(L.o, att, y, 1, T, 1, 0);
+    launch_attention_raw(s, qkv, nullptr, nullptr, d_len, att, B, H, T, nh, 4);
+    P = conv_params(L.o, att, y, B, T, 1, 0);
     launch_conv(s, P, EPI_STORE, "bert.o");
-    { LNParams Q{y, x, nullptr, x, L.g1, L.b1, nullptr, H, T, 0, 0, 0, 0, hp.ln_eps, nullptr, nullptr}; launch_layernorm(s->stream, Q, 1); }  // LayerNorm(dense(ctx) + x)
-    P = conv_params(L.c1, x, ff, 1, T, 1, 0); P.relu = 3;
+    { LNParams Q{y, x, nullptr, x, L.g1, L.b1, nullptr, H, T, 0, 0, 0, 0, hp.ln_eps, nullptr, nullptr}; launch_layernorm(s->stream, Q, B); }  // LayerNorm(dense(ctx) + x)
+    P = conv_params(L.c1, x, ff, B, T, 1, 0); P.relu = 3;
     launch_conv(s, P, EPI_STORE, "bert.ffn1");
-    P = conv_params(L.c2, ff, y, 1, T, 1, 0);
+    P = conv_params(L.c2, ff, y, B, T, 1, 0);
     if (ffn2_slices) {
       // K-sliced: three contiguous thirds of the 3072 input channels as the three groups of ONE conv_wp launch (72 workgroups of 8 waves,
       // each streaming 128 KB of weights) instead of the K-split kernel's 24 workgroups x 384 KB; the partial tensors land in the qkv
@@ -1326,10 +1334,10 @@ static void bert_forward(bert_model* m, vits_session* s, const int64_t* d_ids, c
     }
     {
       LNParams Q{ffn2_slices ? qkv : y, x, nullptr, x, L.g2, L.b2, nullptr, H, T, 0, 0, 0, 0, hp.ln_eps, nullptr, nullptr, ffn2_slices ? 3 : 0, (long long)H * T};
-      launch_layernorm(s->stream, Q, 1);
+      launch_layernorm(s->stream, Q, B);
     }
   }
-  hipLaunchKernelGGL(transpose_ct_kernel, dim3(cdiv(H, 256), T), dim3(256), 0, s->stream, x, ot, H, T);
+  if (ot) hipLaunchKernelGGL(transpose_ct_kernel, dim3(cdiv(H, 256), T), dim3(256), 0, s->stream, x, ot, H, T);
 }
 
 // graph-replayed form: returns 1 when it served the call, 0 when the caller should take the eager form (bucket busy in another
@@ -1378,7 +1386,7 @@ static int bert_encode_graph(bert_model* m, const int64_t* ids, const int64_t* t
     CaptureGuard cg(s->stream);
     hipMemcpyAsync(c->io_d, c->io_h, (size_t)2 * Tb * sizeof(int64_t) + 64, hipMemcpyHostToDevice, s->stream);
     const int64_t* d_ids = reinterpret_cast<const int64_t*>(c->io_d);
-    bert_forward(m, s, d_ids, d_ids + Tb, reinterpret_cast<const int*>(d_ids + 2 * Tb), Tb, x, y, att, qkv, ff, c->ot);
+    bert_forward(m, s, d_ids, d_ids + Tb, reinterpret_cast<const int*>(d_ids + 2 * Tb), 1, Tb, false, x, y, att, qkv, ff, c->ot);
     hipMemcpyAsync(c->out_h, c->ot, sizeof(float) * (size_t)Tb * H, hipMemcpyDeviceToHost, s->stream);
     if (capture_end(s, &c->g, &cg) != VITS_OK) { c->g = nullptr; return 0; }
   }
@@ -1415,9 +1423,78 @@ int stts_bert_encode(bert_model* m, const int64_t* ids, const int64_t* types, in
   if (types) HIP_TRY(hipMemcpyAsync(d_ty, types, sizeof(int64_t) * T, hipMemcpyHostToDevice, s->stream));
   const int tl = T;
   HIP_TRY(hipMemcpyAsync(d_len, &tl, sizeof(int), hipMemcpyHostToDevice, s->stream));
-  bert_forward(m, s, (const int64_t*)d_ids, (const int64_t*)d_ty, d_len, T, x, y, att, qkv, ff, ot);
+  bert_forward(m, s, (const int64_t*)d_ids, (const int64_t*)d_ty, d_len, 1, T, false, x, y, att, qkv, ff, ot);
   HIP_TRY(hipMemcpyAsync(out, ot, sizeof(float) * (size_t)T * H, hipMemcpyDeviceToHost, s->stream));
   return check_err(s);
+}
+
+}  // extern "C"
+
+// ---- padded batches of sentences (include/stts_bert_batch.h) ----
+// One eager forward over [B][H][T] on a pooled session: rows == null -> out [B][T][H] (stts_bert_encode_batch), else the gather
+// out [B][H][T_x] (stts_bert_feed_batch).  Everything is checked on the host before the first launch; a call whose workspace would pass
+// BERT_BATCH_WS_BYTES runs as consecutive sub-batches of whole items (items never interact, so the split changes nothing).
+static const size_t BERT_BATCH_WS_BYTES = (size_t)256 << 20;
+static int bert_batch_run(bert_model* m, const int64_t* ids, const int64_t* types, const int32_t* lengths, int B, int T, const int32_t* rows, int Tx,
+                          float* out) {
+  const bool feed = rows != nullptr;
+  if (!m || !ids || !lengths || !out) return fail(VITS_ERR_ARG, "null argument");
+  if (B <= 0 || T <= 0) return fail(VITS_ERR_ARG, "B = %d and T = %d must be positive", B, T);
+  if (feed && Tx <= 0) return fail(VITS_ERR_ARG, "T_x = %d must be positive", Tx);
+  const bert_hparams& hp = m->hp;
+  if (T > hp.max_position) return fail(VITS_ERR_ARG, "T = %d tokens exceed max_position %d", T, hp.max_position);
+  for (int b = 0; b < B; ++b)
+    if (lengths[b] < 1 || lengths[b] > T) return fail(VITS_ERR_ARG, "lengths[%d] = %d outside [1, T = %d]", b, lengths[b], T);
+  if (feed)
+    for (int b = 0; b < B; ++b)
+      for (int t = 0; t < Tx; ++t)
+        if (rows[(size_t)b * Tx + t] >= lengths[b])
+          return fail(VITS_ERR_ARG, "rows[%d, %d] = %d is not below lengths[%d] = %d", b, t, rows[(size_t)b * Tx + t], b, lengths[b]);
+  const int H = hp.hidden, F = hp.intermediate;
+  HIP_TRY(hipSetDevice(m->base.device));
+  // per item: x, y, att [H][T], qkv [3H][T], ff [F][T], the output tensor, ids + types int64 [T], rows int32 [T_x], len
+  const size_t n_out = feed ? (size_t)H * Tx : (size_t)H * T;
+  const size_t item_bytes = sizeof(float) * ((size_t)T * (6 * H + F) + n_out) + 2 * sizeof(int64_t) * T + sizeof(int32_t) * (feed ? Tx : 0) + sizeof(int32_t);
+  size_t nb_max = BERT_BATCH_WS_BYTES / item_bytes;
+  if (nb_max < 1) nb_max = 1;
+  if (nb_max > 65535) nb_max = 65535;  // grid z
+  const int NB = B < (int)nb_max ? B : (int)nb_max;
+  vits_session* s = nullptr;
+  TRY(pool_acquire(&m->base, &s));
+  struct Rel { vits_model* b; vits_session* s; ~Rel() { hipStreamSynchronize(s->stream); pool_release(b, s); } } rel{&m->base, s};
+  TRY(stts_arena(s, (size_t)NB * item_bytes + 64 * 1024));
+  float* x = bump<float>(s, (size_t)NB * H * T); float* y = bump<float>(s, (size_t)NB * H * T); float* att = bump<float>(s, (size_t)NB * H * T);
+  float* qkv = bump<float>(s, (size_t)NB * 3 * H * T); float* ff = bump<float>(s, (size_t)NB * F * T); float* o = bump<float>(s, (size_t)NB * n_out);
+  int64_t* d_ids = bump<int64_t>(s, (size_t)NB * T);
+  int64_t* d_ty = types ? bump<int64_t>(s, (size_t)NB * T) : nullptr;
+  int* d_len = bump<int>(s, NB);
+  int* d_rows = feed ? bump<int>(s, (size_t)NB * Tx) : nullptr;
+  for (int b0 = 0; b0 < B; b0 += NB) {
+    const int nb = B - b0 < NB ? B - b0 : NB;
+    HIP_TRY(hipMemcpyAsync(d_ids, ids + (size_t)b0 * T, sizeof(int64_t) * (size_t)nb * T, hipMemcpyHostToDevice, s->stream));
+    if (types) HIP_TRY(hipMemcpyAsync(d_ty, types + (size_t)b0 * T, sizeof(int64_t) * (size_t)nb * T, hipMemcpyHostToDevice, s->stream));
+    HIP_TRY(hipMemcpyAsync(d_len, lengths + b0, sizeof(int32_t) * nb, hipMemcpyHostToDevice, s->stream));
+    if (feed) HIP_TRY(hipMemcpyAsync(d_rows, rows + (size_t)b0 * Tx, sizeof(int32_t) * (size_t)nb * Tx, hipMemcpyHostToDevice, s->stream));
+    bert_forward(m, s, d_ids, d_ty, d_len, nb, T, true, x, y, att, qkv, ff, nullptr);
+    if (feed) hipLaunchKernelGGL(bert_gather_cols_kernel, dim3(cdiv(Tx, 64), cdiv(H, 4), nb), dim3(64, 4), 0, s->stream, x, d_rows, o, H, T, Tx);
+    else hipLaunchKernelGGL(transpose_ct_batch_kernel, dim3(cdiv(H, 256), T, nb), dim3(256), 0, s->stream, x, d_len, o, H, T);
+    HIP_TRY(hipMemcpyAsync(out + (size_t)b0 * n_out, o, sizeof(float) * (size_t)nb * n_out, hipMemcpyDeviceToHost, s->stream));
+    TRY(check_err(s));  // (synchronises: the next sub-batch reuses the workspace)
+  }
+  return VITS_OK;
+}
+
+extern "C" {
+
+int stts_bert_encode_batch(bert_model* m, const int64_t* input_ids, const int64_t* token_type_ids, const int32_t* lengths, int32_t B, int32_t T,
+                           float* out) {
+  return bert_batch_run(m, input_ids, token_type_ids, lengths, B, T, nullptr, 0, out);
+}
+
+int stts_bert_feed_batch(bert_model* m, const int64_t* input_ids, const int64_t* token_type_ids, const int32_t* lengths, int32_t B, int32_t T,
+                         const int32_t* rows, int32_t T_x, float* out) {
+  if (!rows) return fail(VITS_ERR_ARG, "null argument");
+  return bert_batch_run(m, input_ids, token_type_ids, lengths, B, T, rows, T_x, out);
 }
 
 }  // extern "C"

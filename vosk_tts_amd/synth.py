@@ -102,6 +102,85 @@ class Synth:
                                                "token_type_ids": [tokens.type_ids]})[0]
         return bert[word_bert_rows(tokens.tokens, nopunc)]
 
+    def _front_rows(self, text):
+        """One text through the front end that _feed would pick, with the BERT vectors replaced by their indices: -> (ids int64 [T] or
+        [5, T], token ids + type ids of the sentence for BERT or None, rows int32 [T] = the BERT token whose hidden state phoneme t
+        takes (-1: none), phone_duration_extra float32 [T] or None).  The front ends are called as they are, with
+        embeddings = np.arange(number of word rows) -- an array, so that -1 for '$' still means the last row -- and what they return is
+        composed with word_bert_rows to token indices."""
+        from .multistream import word_bert_rows
+
+        model_type = self.model.config.get("model_type") or ""
+        have_bert = self.model.tokenizer is not None
+
+        def encode(t, nopunc):
+            tokens = self.model.tokenizer.encode(t.replace("+", "").replace("_", ""))
+            return tokens, np.asarray(word_bert_rows(tokens.tokens, nopunc), np.int32)
+
+        pde = None
+        if model_type.startswith("multistream"):
+            from .multistream import g2p_multistream
+
+            idmap = self.model.config["phoneme_id_map"]
+            tokens = None
+            if model_type == "multistream_v3" and have_bert:
+                tokens, word_rows = encode(text.lower(), True)
+                stream_ids, per_symbol, extra = g2p_multistream(text, self.model.dic, idmap, np.arange(len(word_rows)), pause_marks=True)
+                pde = np.array(extra, dtype=np.float32)
+            elif model_type in ("multistream_v1", "multistream_v2") and have_bert:
+                tokens, word_rows = encode(text, True)
+                stream_ids, per_symbol = g2p_multistream(text, self.model.dic, idmap, np.arange(len(word_rows)),
+                                                         word_pos=model_type == "multistream_v2")
+            elif model_type == "multistream_v2":
+                stream_ids, _ = g2p_multistream(text, self.model.dic, idmap, None, word_pos=True)
+            else:
+                raise NotImplementedError(f"{model_type} needs bert/ (vocab.txt + model.bertw) next to the model")
+            ids = np.transpose(np.array(stream_ids, dtype=np.int64))  # [5, T]
+            rows = np.full(ids.shape[1], -1, np.int32) if tokens is None else word_rows[np.asarray(per_symbol, np.int64)]
+        elif have_bert:
+            tokens, word_rows = encode(text, False)
+            fe = self.g2p_noblank if self.model.config.get("no_blank", 0) != 0 else self.g2p
+            phoneme_ids, emb = fe(text, np.arange(len(word_rows)))
+            ids = np.array(phoneme_ids, dtype=np.int64)
+            rows = word_rows[np.asarray(emb, np.int64)]
+        else:
+            raise NotImplementedError("front_batch is the front end of BERT-conditioned and multistream voices")
+        tok = None if tokens is None else (np.asarray(tokens.ids, np.int64), np.asarray(tokens.type_ids, np.int64))
+        return ids, tok, rows, pde
+
+    def front_batch(self, texts, speaker_ids=0):
+        """The front end of _feed for a list of texts as ONE padded set, with one batched BERT call (BertEncoder.feed_batch: all
+        sentences in one padded forward, the per-phoneme feed gathered on the device) instead of an encoder call, a row selection, a
+        fan-out and a transpose per text.  Covers _feed's BERT-conditioned branches: g2p, g2p_noblank, multistream_v1 / v2 / v3
+        (a tokenizer-less v2 gets a zero feed and makes no BERT call).
+        -> {"input": int64 [B, T] ([B, 5, T] multistream), "input_lengths": int64 [B], "bert": float32 [B, 768, T],
+            "phone_duration_extra": float32 [B, T] or None, "sid": int64 [B]}; item b, cut at its length, is _feed's feed of texts[b]."""
+        n = len(texts)
+        if n == 0:
+            raise ValueError("empty batch")
+        sids = [speaker_ids] * n if np.isscalar(speaker_ids) or speaker_ids is None else list(speaker_ids)
+        if len(sids) != n:
+            raise ValueError("one speaker id per text")
+        fronts = [self._front_rows(self.normalize(t)) for t in texts]
+        lens = np.array([f[0].shape[-1] for f in fronts], np.int64)
+        T = int(lens.max())
+        ids = np.zeros((n,) + fronts[0][0].shape[:-1] + (T,), np.int64)
+        any_pde = any(f[3] is not None for f in fronts)
+        pde = np.zeros((n, T), np.float32) if any_pde else None
+        for b, (i, _, _, p) in enumerate(fronts):
+            ids[b, ..., :lens[b]] = i
+            if p is not None:
+                pde[b, :lens[b]] = p
+        if fronts[0][1] is None:  # tokenizer-less multistream_v2 (the branch depends on the voice, not on the text): zero vectors
+            bert = np.zeros((n, 768, T), np.float32)
+        else:
+            enc = self.model.bert_onnx
+            if not getattr(enc, "has_batch", False):
+                raise NotImplementedError("the BERT session of this voice has no batched entry point (BertEncoder.has_batch)")
+            bert = enc.feed_batch([f[1][0] for f in fronts], [f[2] for f in fronts], T_x=T, token_type_ids=[f[1][1] for f in fronts])
+        return {"input": ids, "input_lengths": lens, "bert": bert, "phone_duration_extra": pde,
+                "sid": np.array([0 if v is None else int(v) for v in sids], np.int64)}
+
     def synth_audio(self, text, speaker_id=0, noise_level=None, speech_rate=None, duration_noise_level=None, scale=None):
         args, scale = self._feed(text, speaker_id, noise_level, speech_rate, duration_noise_level, scale)
 
