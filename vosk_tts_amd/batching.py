@@ -128,7 +128,7 @@ class MultiDeviceSynth:
             if getattr(m, "bert_onnx", None) is not None and hasattr(m.bert_onnx, "close"):
                 m.bert_onnx.close()
 
-    def _run_shard(self, r, token_lists, idx, sids, scales, scale, seeds):
+    def _run_shard(self, r, token_lists, idx, sids, scales, scale, seeds, sample_rate=None):
         """the requests `idx` on replica r, in batches of <= max_batch (already sorted by descending length) -> list of int16 arrays"""
         out = []
         sess = self.models[r].onnx
@@ -139,17 +139,19 @@ class MultiDeviceSynth:
                     "bert": None, "phone_duration_extra": None, "vits.solo": True,
                     "vits.item_seeds": np.array([seeds[i] for i in part], np.uint64)}
             with self._replica_locks[r]:  # concurrent synth_batch() calls do not interleave on one replica
-                pcm, lengths = sess.run_pcm16(feed, scale, return_lengths=True)  # lengths of THIS call (not the shared attribute)
+                pcm, lengths = sess.run_pcm16(feed, scale, return_lengths=True, sample_rate=sample_rate)  # lengths of THIS call (not the shared attribute)
             out.extend(pcm[j, :int(lengths[j])].copy() for j in range(len(part)))
         return out
 
-    def synth_batch(self, texts, speaker_ids=0, noise_level=None, speech_rate=None, duration_noise_level=None, scale=None, seeds=None):
+    def synth_batch(self, texts, speaker_ids=0, noise_level=None, speech_rate=None, duration_noise_level=None, scale=None, seeds=None,
+                    sample_rate=None):
         """texts: list of str -> list of int16 PCM arrays (22.05 kHz), one per request, in request order.  `seeds`: optional
-        per-request noise seeds (default: a running counter), `speaker_ids`: one id or one per request."""
+        per-request noise seeds (default: a running counter), `speaker_ids`: one id or one per request.  `sample_rate`: output rate
+        in Hz for the whole batch (default: the voice's own; include/vits_resample.h)."""
         s0 = self.synths[0]
         if self.family == "vits":
             token_lists = [s0.g2p_noembed(s0.normalize(t)) for t in texts]
-            return self.synth_tokens(token_lists, speaker_ids, noise_level, speech_rate, duration_noise_level, scale, seeds)
+            return self.synth_tokens(token_lists, speaker_ids, noise_level, speech_rate, duration_noise_level, scale, seeds, sample_rate)
         # BERT-conditioned families: the front end needs the replica's BERT encoder, so it runs on the replica that gets the request;
         # requests are sharded by a cheap length estimate (phoneme count, no BERT needed)
         n = len(texts)
@@ -160,7 +162,8 @@ class MultiDeviceSynth:
         est = [len(s0.phonemize(t.replace("_", " "))) for t in texts]
         shards = plan_shards(est, len(self.devices))
         run = self._run_shard_bert if self.family == "vits_bert" else self._run_shard_multistream
-        futs = [self._pool.submit(run, r, texts, idx, sids, scales, scale, seeds) if idx else None for r, idx in enumerate(shards)]
+        futs = [self._pool.submit(run, r, texts, idx, sids, scales, scale, seeds, sample_rate=sample_rate) if idx else None
+                for r, idx in enumerate(shards)]
         return scatter_results(n, [idx for idx in shards if idx], [f.result() for f in futs if f is not None])
 
     def _call_params(self, n, speaker_ids, noise_level, speech_rate, duration_noise_level, scale, seeds):
@@ -198,7 +201,7 @@ class MultiDeviceSynth:
             out.update(zip(rest, per_request(rest)))
         return [out[i] for i in idx]
 
-    def _run_shard_bert(self, r, texts, idx, sids, scales, scale, seeds, per_request=False):
+    def _run_shard_bert(self, r, texts, idx, sids, scales, scale, seeds, per_request=False, sample_rate=None):
         """BERT-conditioned VITS requests `idx` on replica r: get_word_bert + g2p / g2p_noblank per request (synth.py:88-99), then padded
         solo batches with a padded `bert` feed [B, 768, T]"""
         synth, sess = self.synths[r], self.models[r].onnx
@@ -208,10 +211,11 @@ class MultiDeviceSynth:
                 feed = {"input": f["input"], "input_lengths": f["input_lengths"], "scales": scales, "sid": f["sid"], "bert": f["bert"],
                         "phone_duration_extra": None, "vits.solo": True, "vits.item_seeds": np.array([seeds[i] for i in part], np.uint64)}
                 with self._replica_locks[r]:
-                    pcm, lengths = sess.run_pcm16(feed, scale, return_lengths=True)
+                    pcm, lengths = sess.run_pcm16(feed, scale, return_lengths=True, sample_rate=sample_rate)
                 return [pcm[b, :int(lengths[b])].copy() for b in range(len(part))]
 
-            return self._run_parts(r, idx, run_part, lambda rest: self._run_shard_bert(r, texts, rest, sids, scales, scale, seeds, per_request=True))
+            return self._run_parts(r, idx, run_part, lambda rest: self._run_shard_bert(r, texts, rest, sids, scales, scale, seeds, per_request=True,
+                                                                                      sample_rate=sample_rate))
         fe = synth.g2p_noblank if synth.model.config.get("no_blank", 0) != 0 else synth.g2p
         fronts = []
         for i in idx:
@@ -232,12 +236,12 @@ class MultiDeviceSynth:
                     "bert": bert, "phone_duration_extra": None, "vits.solo": True,
                     "vits.item_seeds": np.array([seeds[idx[k]] for k in part], np.uint64)}
             with self._replica_locks[r]:
-                pcm, lengths = sess.run_pcm16(feed, scale, return_lengths=True)
+                pcm, lengths = sess.run_pcm16(feed, scale, return_lengths=True, sample_rate=sample_rate)
             for b, k in enumerate(part):
                 out[k] = pcm[b, :int(lengths[b])].copy()
         return out
 
-    def _run_shard_multistream(self, r, texts, idx, sids, scales, scale, seeds, per_request=False):
+    def _run_shard_multistream(self, r, texts, idx, sids, scales, scale, seeds, per_request=False, sample_rate=None):
         """multistream (StableTTS / Matcha) requests `idx` on replica r: the five-stream front end of Synth._feed per request
         (synth.py:64-87), then stts_synthesize_batch with per-request seeds; float -> int16 as Synth.audio_float_to_int16"""
         synth, sess = self.synths[r], self.models[r].onnx
@@ -247,9 +251,11 @@ class MultiDeviceSynth:
                 with self._replica_locks[r]:
                     audio, ol = sess._model.synthesize_batch(f["input"], f["input_lengths"], scales, f["sid"], f["bert"], f["phone_duration_extra"],
                                                              seed=0, item_seeds=np.array([seeds[i] for i in part], np.uint64))
+                    audio, ol = sess.resample(audio, ol, sample_rate)
                 return [synth.audio_float_to_int16(audio[b, :int(ol[b])] * scale) for b in range(len(part))]
 
-            return self._run_parts(r, idx, run_part, lambda rest: self._run_shard_multistream(r, texts, rest, sids, scales, scale, seeds, per_request=True))
+            return self._run_parts(r, idx, run_part, lambda rest: self._run_shard_multistream(r, texts, rest, sids, scales, scale, seeds, per_request=True,
+                                                                                             sample_rate=sample_rate))
         fronts = []
         for i in idx:
             feed, _ = synth._feed(texts[i], sids[i], None, None, None, None)
@@ -273,11 +279,13 @@ class MultiDeviceSynth:
             with self._replica_locks[r]:
                 audio, ol = sess._model.synthesize_batch(ids, lens, scales, np.array([sids[idx[k]] for k in part], np.int64), bert, pde,
                                                          seed=0, item_seeds=np.array([seeds[idx[k]] for k in part], np.uint64))
+                audio, ol = sess.resample(audio, ol, sample_rate)
             for b, k in enumerate(part):
                 out[k] = synth.audio_float_to_int16(audio[b, :int(ol[b])] * scale)
         return out
 
-    def synth_tokens(self, token_lists, speaker_ids=0, noise_level=None, speech_rate=None, duration_noise_level=None, scale=None, seeds=None):
+    def synth_tokens(self, token_lists, speaker_ids=0, noise_level=None, speech_rate=None, duration_noise_level=None, scale=None, seeds=None,
+                     sample_rate=None):
         """synth_batch() behind the front end: token id lists in, int16 PCM arrays out (request order)."""
         n = len(token_lists)
         if n == 0:
@@ -286,6 +294,6 @@ class MultiDeviceSynth:
             raise NotImplementedError("synth_tokens takes plain VITS token ids; BERT-conditioned and multistream voices need the text (synth_batch)")
         scales, scale, sids, seeds = self._call_params(n, speaker_ids, noise_level, speech_rate, duration_noise_level, scale, seeds)
         shards = plan_shards([len(t) for t in token_lists], len(self.devices))
-        futs = [self._pool.submit(self._run_shard, r, token_lists, idx, sids, scales, scale, seeds) if idx else None
+        futs = [self._pool.submit(self._run_shard, r, token_lists, idx, sids, scales, scale, seeds, sample_rate) if idx else None
                 for r, idx in enumerate(shards)]
         return scatter_results(n, [idx for idx in shards if idx], [f.result() for f in futs if f is not None])

@@ -112,6 +112,7 @@ class VitsLib:
         f("mas_maximum_path").argtypes = [ctypes.c_int, c_f32p, c_i32p, c_i32p, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,
                                           c_i32p]
         self.is_device = bool(f("is_device_backend")())
+        self.has_resample = False
         if self.is_device:
             c_i16p = ctypes.POINTER(ctypes.c_int16)
             f("synthesize_pcm16").argtypes = [ctypes.c_void_p, c_i64p, c_i64p, ctypes.c_int32, ctypes.c_int32, c_f32p, c_i64p,
@@ -137,6 +138,23 @@ class VitsLib:
             f("stream_close").argtypes = [ctypes.c_void_p]
             f("stream_close").restype = None
             f("persist_state").argtypes = [ctypes.c_void_p, ctypes.POINTER(PersistInfo)]
+            # include/vits_resample.h: an extension of the product library (the oracle has no counterpart), declared where it exists
+            self.has_resample = self.has("resample_plan")
+            if self.has_resample:
+                f("resample_plan").argtypes = [ctypes.c_int32, ctypes.c_int32, c_i32p, c_i32p, c_i32p, c_i32p]
+                f("resample_table").argtypes = [ctypes.c_int32, ctypes.c_int32, c_f32p, ctypes.c_int64]
+                f("op_resample").argtypes = [ctypes.c_int, c_f32p, c_i64p, ctypes.c_int32, ctypes.c_int64, ctypes.c_int32, ctypes.c_int32,
+                                             c_f32p]
+                f("synthesize_rate").argtypes = [ctypes.c_void_p, c_i64p, c_i64p, ctypes.c_int32, ctypes.c_int32, c_f32p, c_i64p,
+                                                 ctypes.POINTER(SynthOpts), ctypes.c_int32, ctypes.POINTER(c_f32p), c_i64p, c_i64p]
+                f("synthesize_pcm16_rate").argtypes = [ctypes.c_void_p, c_i64p, c_i64p, ctypes.c_int32, ctypes.c_int32, c_f32p, c_i64p,
+                                                       ctypes.POINTER(SynthOpts), ctypes.c_float, ctypes.c_int32,
+                                                       ctypes.POINTER(c_i16p), c_i64p, c_i64p]
+                f("stream_open_rate").argtypes = [ctypes.c_void_p, c_i64p, ctypes.c_int32, c_f32p, ctypes.c_int64,
+                                                  ctypes.POINTER(SynthOpts), ctypes.c_int32, ctypes.c_int32,
+                                                  ctypes.POINTER(ctypes.c_void_p), c_i64p]
+                f("stream_open_latent_rate").argtypes = [ctypes.c_void_p, c_f32p, ctypes.c_int32, ctypes.c_int32, ctypes.c_uint32,
+                                                         ctypes.c_int32, ctypes.POINTER(ctypes.c_void_p), c_i64p]
             if self.has("debug_clock_probe"):
                 f("debug_clock_probe").argtypes = [ctypes.c_int, ctypes.c_int32, ctypes.POINTER(ctypes.c_double), ctypes.c_int32]
 
@@ -204,6 +222,46 @@ class VitsLib:
         buf = ctypes.create_string_buffer(1 << 16)
         self._fn("debug_launch_dump")(buf, ctypes.c_size_t(len(buf)))
         return {k: int(n) for k, n in (line.rsplit(" ", 1) for line in buf.value.decode().splitlines())}
+
+    # ---- output sample rate (include/vits_resample.h) -----------------------
+    def _need_resample(self):
+        if not self.has_resample:
+            raise VitsError(4, "this backend has no resampler (include/vits_resample.h): only the voice's own sample rate")
+
+    def resample_plan(self, rate_in, rate_out):
+        """vits_resample_plan (host only): dict(L, M, taps, half) of rate_in -> rate_out; VitsError(4) names a refused pair"""
+        self._need_resample()
+        v = [ctypes.c_int32() for _ in range(4)]
+        self.check(self._fn("resample_plan")(int(rate_in), int(rate_out), *[ctypes.byref(c) for c in v]))
+        return dict(L=v[0].value, M=v[1].value, taps=v[2].value, half=v[3].value)
+
+    def resample_table(self, rate_in, rate_out):
+        """vits_resample_table (host only): the fp32 phase table [L, taps]"""
+        P = self.resample_plan(rate_in, rate_out)
+        tab = np.empty((P["L"], P["taps"]), np.float32)
+        self.check(self._fn("resample_table")(int(rate_in), int(rate_out), _p(tab, c_f32p), tab.size))
+        return tab
+
+    def out_samples(self, n, rate_in, rate_out):
+        """ceil(n * L / M): samples at rate_out of n samples at rate_in (rate_out 0 / None / rate_in: n)"""
+        if not rate_out or rate_out == rate_in:
+            return int(n)
+        P = self.resample_plan(rate_in, rate_out)
+        return -(-int(n) * P["L"] // P["M"])
+
+    def op_resample(self, x, lengths, rate_in, rate_out, device=0):
+        """vits_op_resample: x float32 [B, N], lengths [B] -> y float32 [B, ceil(N*L/M)]; item b from x[b, :lengths[b]] only"""
+        self._need_resample()
+        x = _f32(x)
+        if x.ndim != 2:
+            raise ValueError("x must be [B, N]")
+        B, N = x.shape
+        lengths = _i64(lengths).reshape(-1)
+        if lengths.shape != (B,):
+            raise ValueError("lengths must be [B]")
+        y = np.empty((B, self.out_samples(N, rate_in, rate_out)), np.float32)
+        self.check(self._fn("op_resample")(device, _p(x, c_f32p), _p(lengths, c_i64p), B, N, int(rate_in), int(rate_out), _p(y, c_f32p)))
+        return y
 
     def mas_maximum_path(self, values, t_ys, t_xs, device=0):
         """monotonic_align.maximum_path_c (core.pyx:35-42): values float32 [B,T_y,T_x] -> paths int32 [B,T_y,T_x]."""
@@ -285,10 +343,20 @@ class VitsModel:
         return opts, keep
 
     # ---- the hot path -----------------------------------------------------
+    def _rate(self, sample_rate):
+        """None / 0 / the voice's own rate -> 0 (the entry points without a rate); anything else needs the resampler"""
+        rate = int(sample_rate or 0)
+        if rate == self.hp.sampling_rate:
+            rate = 0
+        if rate:
+            self.lib._need_resample()
+        return rate
+
     def synthesize(self, ids, lengths, scales, sid, noise_dp=None, noise_prior=None, forced_durations=None, seed=0,
-                   max_frames=0, solo=False, item_seeds=None, bert=None):
+                   max_frames=0, solo=False, item_seeds=None, bert=None, sample_rate=None):
         """One .run(): returns (audio float32 [B,S], out_lengths int64 [B]).  solo=True (VITS_FLAG_SOLO_BATCH): every
-        item equals its own single-utterance call with seed + b instead of the reference's padded-batch result."""
+        item equals its own single-utterance call with seed + b instead of the reference's padded-batch result.
+        sample_rate: output rate in Hz (vits_synthesize_rate; S and out_lengths are then in output samples)."""
         ids = _i64(ids)
         B, Tx = ids.shape
         lengths = _i64(lengths)
@@ -300,9 +368,15 @@ class VitsModel:
         out = c_f32p()
         ns = ctypes.c_int64()
         olen = np.zeros(B, dtype=np.int64)
-        self.lib.check(self.lib._fn("synthesize")(self._h, _p(ids, c_i64p), _p(lengths, c_i64p), B, Tx, _p(scales, c_f32p),
-                                                  _p(sid, c_i64p), ctypes.byref(opts), ctypes.byref(out),
-                                                  ctypes.byref(ns), _p(olen, c_i64p)))
+        rate = self._rate(sample_rate)
+        if rate:
+            self.lib.check(self.lib._fn("synthesize_rate")(self._h, _p(ids, c_i64p), _p(lengths, c_i64p), B, Tx, _p(scales, c_f32p),
+                                                           _p(sid, c_i64p), ctypes.byref(opts), rate, ctypes.byref(out),
+                                                           ctypes.byref(ns), _p(olen, c_i64p)))
+        else:
+            self.lib.check(self.lib._fn("synthesize")(self._h, _p(ids, c_i64p), _p(lengths, c_i64p), B, Tx, _p(scales, c_f32p),
+                                                      _p(sid, c_i64p), ctypes.byref(opts), ctypes.byref(out),
+                                                      ctypes.byref(ns), _p(olen, c_i64p)))
         try:
             audio = np.ctypeslib.as_array(out, shape=(B, ns.value)).copy()
         finally:
@@ -310,9 +384,10 @@ class VitsModel:
         return audio, olen
 
     def synthesize_pcm16(self, ids, lengths, scales, sid, pcm_scale=1.0, noise_dp=None, noise_prior=None, forced_durations=None,
-                         seed=0, max_frames=0, solo=False, item_seeds=None, bert=None):
+                         seed=0, max_frames=0, solo=False, item_seeds=None, bert=None, sample_rate=None):
         """synthesize() with Synth.synth_audio's `* scale` and audio_float_to_int16 (vosk_tts/synth.py:127-130) done on the
-        device: returns (pcm int16 [B,S], out_lengths int64 [B])."""
+        device: returns (pcm int16 [B,S], out_lengths int64 [B]).  sample_rate: as for synthesize (vits_synthesize_pcm16_rate:
+        the resampler does the conversion in its epilogue)."""
         ids = _i64(ids)
         B, Tx = ids.shape
         lengths = _i64(lengths); sid = _i64(sid); scales = _f32(scales)
@@ -322,18 +397,28 @@ class VitsModel:
         out = ctypes.POINTER(ctypes.c_int16)()
         ns = ctypes.c_int64()
         olen = np.zeros(B, dtype=np.int64)
-        self.lib.check(self.lib._fn("synthesize_pcm16")(self._h, _p(ids, c_i64p), _p(lengths, c_i64p), B, Tx, _p(scales, c_f32p),
-                                                        _p(sid, c_i64p), ctypes.byref(opts), float(pcm_scale), ctypes.byref(out),
-                                                        ctypes.byref(ns), _p(olen, c_i64p)))
+        rate = self._rate(sample_rate)
+        if rate:
+            self.lib.check(self.lib._fn("synthesize_pcm16_rate")(self._h, _p(ids, c_i64p), _p(lengths, c_i64p), B, Tx,
+                                                                 _p(scales, c_f32p), _p(sid, c_i64p), ctypes.byref(opts),
+                                                                 float(pcm_scale), rate, ctypes.byref(out), ctypes.byref(ns),
+                                                                 _p(olen, c_i64p)))
+        else:
+            self.lib.check(self.lib._fn("synthesize_pcm16")(self._h, _p(ids, c_i64p), _p(lengths, c_i64p), B, Tx, _p(scales, c_f32p),
+                                                            _p(sid, c_i64p), ctypes.byref(opts), float(pcm_scale), ctypes.byref(out),
+                                                            ctypes.byref(ns), _p(olen, c_i64p)))
         try:
             pcm = np.ctypeslib.as_array(out, shape=(B, ns.value)).copy()
         finally:
             self.lib._fn("free_pcm16")(out)
         return pcm, olen
 
-    def stream(self, ids, scales, sid, chunk_frames=64, noise_dp=None, noise_prior=None, forced_durations=None, seed=0, bert=None):
+    def stream(self, ids, scales, sid, chunk_frames=64, noise_dp=None, noise_prior=None, forced_durations=None, seed=0, bert=None,
+               sample_rate=None):
         """Streaming synthesis of ONE utterance (vits_stream_*): a generator of float32 chunks of
-        chunk_frames*hop_length samples (the last one shorter); their concatenation equals synthesize()."""
+        chunk_frames*hop_length samples (the last one shorter); their concatenation equals synthesize().
+        sample_rate: output rate in Hz (vits_stream_open_rate): the chunk that covers input samples [a, b) holds the outputs
+        ceil(a*L/M) <= n < ceil(b*L/M), so chunk sizes vary by one sample."""
         if not self.lib.has("stream_open"):
             raise VitsError(-1, "this backend has no streaming entry points")
         ids = _i64(ids).reshape(1, -1)
@@ -343,26 +428,39 @@ class VitsModel:
         L = self.lib
         st = ctypes.c_void_p()
         total = ctypes.c_int64()
-        L.check(L._fn("stream_open")(self._h, _p(ids, c_i64p), Tx, _p(scales, c_f32p), int(sid), ctypes.byref(opts),
-                                     int(chunk_frames), ctypes.byref(st), ctypes.byref(total)))
-        return self._drain(st, chunk_frames)
+        rate = self._rate(sample_rate)
+        if rate:
+            L.check(L._fn("stream_open_rate")(self._h, _p(ids, c_i64p), Tx, _p(scales, c_f32p), int(sid), ctypes.byref(opts),
+                                              int(chunk_frames), rate, ctypes.byref(st), ctypes.byref(total)))
+        else:
+            L.check(L._fn("stream_open")(self._h, _p(ids, c_i64p), Tx, _p(scales, c_f32p), int(sid), ctypes.byref(opts),
+                                         int(chunk_frames), ctypes.byref(st), ctypes.byref(total)))
+        return self._drain(st, chunk_frames, rate)
 
-    def stream_latent(self, z, chunk_frames=64, clamp=False):
-        """Streams the decoder over a latent the caller holds (vits_stream_open_latent): z float32 [inter_channels, T_y]."""
+    def stream_latent(self, z, chunk_frames=64, clamp=False, sample_rate=None):
+        """Streams the decoder over a latent the caller holds (vits_stream_open_latent): z float32 [inter_channels, T_y].
+        sample_rate: as for stream (vits_stream_open_latent_rate)."""
         z = _f32(z)
         if z.ndim != 2 or z.shape[0] != self.hp.inter_channels:
             raise ValueError("z must be [inter_channels, T_y]")
         L = self.lib
         st = ctypes.c_void_p()
         total = ctypes.c_int64()
-        L.check(L._fn("stream_open_latent")(self._h, _p(z, c_f32p), z.shape[1], int(chunk_frames), 1 if clamp else 0,
-                                            ctypes.byref(st), ctypes.byref(total)))
-        return self._drain(st, chunk_frames)
+        rate = self._rate(sample_rate)
+        if rate:
+            L.check(L._fn("stream_open_latent_rate")(self._h, _p(z, c_f32p), z.shape[1], int(chunk_frames), 1 if clamp else 0, rate,
+                                                     ctypes.byref(st), ctypes.byref(total)))
+        else:
+            L.check(L._fn("stream_open_latent")(self._h, _p(z, c_f32p), z.shape[1], int(chunk_frames), 1 if clamp else 0,
+                                                ctypes.byref(st), ctypes.byref(total)))
+        return self._drain(st, chunk_frames, rate)
 
-    def _drain(self, st, chunk_frames):
+    def _drain(self, st, chunk_frames, rate=0):
         """generator over an open vits_stream; closes it when exhausted or dropped"""
         L = self.lib
         cap = int(chunk_frames) * self.hp.hop_length
+        if rate:  # chunk sizes vary by one sample around chunk * hop * L / M
+            cap = L.out_samples(cap, self.hp.sampling_rate, rate) + 1
         n = ctypes.c_int64()
         try:
             while True:

@@ -11,7 +11,8 @@ import argparse
 import logging
 import sys
 
-# (flags, argparse keyword arguments) — one row per option of the reference CLI
+# (flags, argparse keyword arguments) — one row per option of the reference CLI, plus --sample-rate (tts_service.proto's
+# output_audio_spec.raw_audio.sample_rate_hertz; the reference script has no such flag)
 _OPTIONS = (
     (("-m", "--model"), dict(type=str, metavar="DIR", help="directory holding model.vitsw, dictionary and config.json")),
     (("-n", "--model-name"), dict(type=str, metavar="NAME", help="pick a locally installed model by its directory name")),
@@ -22,6 +23,7 @@ _OPTIONS = (
     (("-o", "--output"), dict(type=str, default="out.wav", metavar="WAV", help="where to write the audio")),
     (("--list-models",), dict(action="store_true", help="print the models found in the local search path and exit")),
     (("--list-languages",), dict(action="store_true", help="print the language codes of the local models and exit")),
+    (("--sample-rate",), dict(type=int, default=None, metavar="HZ", help="output sample rate (default: the voice's own, 22050)")),
     (("--log-level",), dict(default="INFO", metavar="LEVEL", help="python logging level (INFO shows the RTF line)")),
 )
 
@@ -47,7 +49,7 @@ def run(opts):
     from .synth import Synth
 
     voice = model_mod.Model(opts.model, opts.model_name, opts.lang)
-    Synth(voice).synth(opts.input, opts.output, opts.speaker, speech_rate=opts.speech_rate)
+    Synth(voice).synth(opts.input, opts.output, opts.speaker, speech_rate=opts.speech_rate, sample_rate=opts.sample_rate)
     return 0
 
 

@@ -121,6 +121,7 @@ static int persist_cfg() {
 #include "engine_convdbg.hip.h"
 #include "engine_launch.hip.h"
 #include "engine_stages.hip.h"
+#include "resample.hip.h"
 
 // ------------------------------------------------------------------------------------ C ABI
 extern "C" {

@@ -33,6 +33,7 @@ static size_t fast_cache_cap() {
 
 static size_t session_device_bytes(const vits_session* s) {
   size_t n = s->arena_bytes + s->io_bytes + s->out_elems * (sizeof(float) + sizeof(int16_t));
+  for (auto& kv : s->rates) n += (size_t)s->B * kv.second.n_cap * sizeof(float);
   for (auto& kv : s->backs) n += session_device_bytes(kv.second);
   return n;
 }
@@ -153,6 +154,37 @@ static int back_get(vits_session* F, int TyB, vits_session** out) {
   return VITS_OK;
 }
 
+// output buffers and graphs of back session Bk at the rate of `T` (created on first use; at most 4 rates stay cached per back)
+static int back_rate_get(vits_session* F, vits_session* Bk, const ResampleTab& T, vits_session::RateOut** out) {
+  auto drop = [&](std::map<int, vits_session::RateOut>::iterator it) {
+    hipStreamSynchronize(F->stream);
+    for (hipGraphExec_t g : it->second.g2) if (g) hipGraphExecDestroy(g);
+    if (it->second.y_d) hipFree(it->second.y_d);
+    if (it->second.y_h) hipHostFree(it->second.y_h);
+    Bk->rates.erase(it);
+  };
+  auto it = Bk->rates.find(T.P.rate_out);
+  if (it == Bk->rates.end()) {
+    if (Bk->rates.size() >= 4) {
+      auto lru = Bk->rates.begin();
+      for (auto jt = Bk->rates.begin(); jt != Bk->rates.end(); ++jt) if (jt->second.last_use < lru->second.last_use) lru = jt;
+      drop(lru);
+    }
+    it = Bk->rates.emplace(T.P.rate_out, vits_session::RateOut()).first;
+    vits_session::RateOut& R = it->second;
+    R.n_cap = T.P.n_out((long long)Bk->Ty * F->m->hp.hop_length);
+    const size_t bytes = (size_t)F->B * R.n_cap * sizeof(float);
+    if (hipMalloc(&R.y_d, bytes) != hipSuccess || hipHostMalloc((void**)&R.y_h, bytes) != hipSuccess) {
+      drop(it);
+      (void)hipGetLastError();
+      return fail(VITS_ERR_NOMEM, "fast-path output buffers at %d Hz (%zu bytes)", T.P.rate_out, bytes);
+    }
+  }
+  it->second.last_use = ++F->last_use;
+  *out = &it->second;
+  return VITS_OK;
+}
+
 // A capture that does not reach capture_end (an early return between Begin and End) must not leave the stream in capture mode:
 // every later call on the session would fail.  The guard ends and discards it.
 struct CaptureGuard {
@@ -213,9 +245,11 @@ static int phase1_launch(vits_session* F, bool forced, bool solo) {
   return VITS_OK;
 }
 
-static int phase2_launch(vits_session* F, vits_session* Bk, bool solo, bool pcm) {
+// R / T: the output rate's buffers and table (both null: the native rate)
+static int phase2_launch(vits_session* F, vits_session* Bk, bool solo, bool pcm, vits_session::RateOut* R = nullptr, const ResampleTab* T = nullptr) {
   const int gi = (persist_mask() ? 4 : 0) + (solo ? 2 : 0) + (pcm ? 1 : 0);
-  if (!Bk->g2[gi]) {
+  hipGraphExec_t* g2 = R ? R->g2 : Bk->g2;
+  if (!g2[gi]) {
     const int B = F->B, TxB = F->Tx, TyB = Bk->Ty;
     const long long stride = (long long)TyB * F->m->hp.hop_length;
     HIP_TRY(hipStreamBeginCapture(F->stream, hipStreamCaptureModeThreadLocal));
@@ -232,17 +266,26 @@ static int phase2_launch(vits_session* F, vits_session* Bk, bool solo, bool pcm)
     // a lone utterance decodes as the exact-size run does (zeros beyond its end); batches keep the reference's padded-batch
     // continuation over the halo unless the caller asked for independent items
     run_decoder(Bk, z, true, B, TyB, Bk->out_d, stride, true, !(solo || B == 1));
-    if (pcm) {
-      hipLaunchKernelGGL(pcm16_kernel, dim3(cdiv((int)stride, 256), B), dim3(256), 0, F->stream, Bk->out_d, stride, Bk->pcm_d, stride, stride, 1.f, Bk->dv);
+    if (R) {  // the resampler reads each item's own [0, len) of the decoder's output; at int16 it stands where pcm16_kernel stands
+      ProfScope ps(Bk, "out.resample", 2.0 * B * R->n_cap * T->P.taps, pcm ? "resample_kernel<int16>" : "resample_kernel<float>");
+      const int hop = F->m->hp.hop_length;
+      if (pcm) resample_launch<int16_t>(F->stream, *T, Bk->out_d, stride, 0, stride, Bk->len_y, hop, B, static_cast<int16_t*>(R->y_d), R->n_cap, 0, R->n_cap, 1.f, Bk->dv);
+      else resample_launch<float>(F->stream, *T, Bk->out_d, stride, 0, stride, Bk->len_y, hop, B, static_cast<float*>(R->y_d), R->n_cap, 0, R->n_cap, 1.f, nullptr);
+      hipMemcpyAsync(R->y_h, R->y_d, (size_t)B * R->n_cap * (pcm ? sizeof(int16_t) : sizeof(float)), hipMemcpyDeviceToHost, F->stream);
+    } else if (pcm) {
+      {
+        ProfScope ps(Bk, "out.pcm16", 0, "pcm16_kernel");
+        hipLaunchKernelGGL(pcm16_kernel, dim3(cdiv((int)stride, 256), B), dim3(256), 0, F->stream, Bk->out_d, stride, Bk->pcm_d, stride, stride, 1.f, Bk->dv);
+      }
       hipMemcpyAsync(Bk->out_h, Bk->pcm_d, Bk->out_elems * sizeof(int16_t), hipMemcpyDeviceToHost, F->stream);
     } else {
       hipMemcpyAsync(Bk->out_h, Bk->out_d, Bk->out_elems * sizeof(float), hipMemcpyDeviceToHost, F->stream);
     }
     hipMemcpyAsync(Bk->h_err, Bk->d_err, sizeof(int), hipMemcpyDeviceToHost, F->stream);  // (the flow program's error bits)
     Bk->ragged = false; Bk->solo = false;
-    TRY(capture_end(F, &Bk->g2[gi], &cg));
+    TRY(capture_end(F, &g2[gi], &cg));
   }
-  HIP_TRY(hipGraphLaunch(Bk->g2[gi], F->stream));
+  HIP_TRY(hipGraphLaunch(g2[gi], F->stream));
   return VITS_OK;
 }
 
@@ -255,10 +298,12 @@ static int device_error_word(int e) {
 }
 
 static int synth_fast(vits_model* m, const int64_t* ids, const int64_t* lengths, int32_t B, int32_t Tx, const float* scales,
-                      const int64_t* sid, const vits_synth_opts* opts, bool pcm, float pcm_scale, void** out, int64_t* out_samples,
+                      const int64_t* sid, const vits_synth_opts* opts, bool pcm, float pcm_scale, int rate, void** out, int64_t* out_samples,
                       int64_t* out_lengths) {
   const vits_hparams& hp = m->hp;
   HIP_TRY(hipSetDevice(m->device));
+  const ResampleTab* T = nullptr;  // (uploaded on the first call at this rate, before any capture)
+  if (rate) TRY(resample_get(m->device, hp.sampling_rate, rate, &T));
   const int TxB = (Tx + 7) / 8 * 8;
   const bool forced = opts && opts->forced_durations, solo = opts && (opts->flags & VITS_FLAG_SOLO_BATCH);
   // (declared before the session guard: the call's last stream synchronisation happens before this scope ends)
@@ -335,8 +380,12 @@ static int synth_fast(vits_model* m, const int64_t* ids, const int64_t* lengths,
     }
     if (rc != VITS_OK) return rc;
   }
-  TRY(phase2_launch(F, Bk, solo, pcm));
-  const int64_t S = Ty * hp.hop_length, stride = (int64_t)TyB * hp.hop_length;
+  vits_session::RateOut* R = nullptr;
+  if (T) TRY(back_rate_get(F, Bk, *T, &R));
+  TRY(phase2_launch(F, Bk, solo, pcm, R, T));
+  // (sizes in output samples)
+  const int64_t S = T ? T->P.n_out(Ty * hp.hop_length) : Ty * hp.hop_length, stride = R ? R->n_cap : (int64_t)TyB * hp.hop_length;
+  const char* src_h = R ? R->y_h : Bk->out_h;
   const size_t esz = pcm ? sizeof(int16_t) : sizeof(float);
   char* h_out = static_cast<char*>(malloc(esz * (size_t)B * S));
   if (!h_out) { hipStreamSynchronize(F->stream); return fail(VITS_ERR_NOMEM, "host alloc failed"); }
@@ -350,17 +399,19 @@ static int synth_fast(vits_model* m, const int64_t* ids, const int64_t* lengths,
     free(h_out);
     return device_error_word(e2);
   }
-  for (int b = 0; b < B; ++b) memcpy(h_out + esz * (size_t)b * S, Bk->out_h + esz * (size_t)b * stride, esz * (size_t)S);
+  for (int b = 0; b < B; ++b) memcpy(h_out + esz * (size_t)b * S, src_h + esz * (size_t)b * stride, esz * (size_t)S);
   *out = h_out;
   *out_samples = S;
-  if (out_lengths) for (int b = 0; b < B; ++b) out_lengths[b] = F->h_ylen[b] * hp.hop_length;
+  if (out_lengths) for (int b = 0; b < B; ++b) out_lengths[b] = T ? T->P.n_out(F->h_ylen[b] * hp.hop_length) : F->h_ylen[b] * hp.hop_length;
   return VITS_OK;
 }
 
 static int synth_eager(vits_model* m, const int64_t* ids, const int64_t* lengths, int32_t B, int32_t Tx, const float* scales,
-                       const int64_t* sid, const vits_synth_opts* opts, bool pcm, float pcm_scale, void** out, int64_t* out_samples,
+                       const int64_t* sid, const vits_synth_opts* opts, bool pcm, float pcm_scale, int rate, void** out, int64_t* out_samples,
                        int64_t* out_lengths) {
   const vits_hparams& hp = m->hp;
+  const ResampleTab* T = nullptr;
+  if (rate) TRY(resample_get(m->device, hp.sampling_rate, rate, &T));
   HostStage hs(m);
   std::vector<int64_t> ylen;
   int64_t Ty = 0;
@@ -376,30 +427,41 @@ static int synth_eager(vits_model* m, const int64_t* ids, const int64_t* lengths
   run_decoder(s, z, true, B, (int)Ty, d_audio, S, true, !s->solo);
   const size_t esz = pcm ? sizeof(int16_t) : sizeof(float);
   const void* d_src = d_audio;
-  if (pcm) {
+  const int64_t So = T ? T->P.n_out(S) : S;  // samples per item as returned
+  if (T) {  // item b from its own [0, len) of d_audio; at int16 in place of pcm16_kernel
+    void* d_y = hs.raw_alloc(esz * (size_t)B * So);
+    if (!d_y) return fail(VITS_ERR_NOMEM, "device alloc failed");
+    ProfScope ps(s, "out.resample", 2.0 * B * So * T->P.taps, pcm ? "resample_kernel<int16>" : "resample_kernel<float>");
+    if (pcm) resample_launch<int16_t>(s->stream, *T, d_audio, S, 0, S, s->len_y, hp.hop_length, B, static_cast<int16_t*>(d_y), So, 0, So, pcm_scale, nullptr);
+    else resample_launch<float>(s->stream, *T, d_audio, S, 0, S, s->len_y, hp.hop_length, B, static_cast<float*>(d_y), So, 0, So, 1.f, nullptr);
+    d_src = d_y;
+  } else if (pcm) {
     int16_t* d_pcm = hs.dev_alloc<int16_t>((size_t)B * S);
     if (!d_pcm) return fail(VITS_ERR_NOMEM, "device alloc failed");
+    ProfScope ps(s, "out.pcm16", 0, "pcm16_kernel");
     hipLaunchKernelGGL(pcm16_kernel, dim3(cdiv((int)S, 256), B), dim3(256), 0, s->stream, d_audio, (long long)S, d_pcm, (long long)S, (long long)S, pcm_scale,
                        (const SynthDev*)nullptr);
     d_src = d_pcm;
   }
-  void* h_out = malloc(esz * (size_t)B * S);
+  void* h_out = malloc(esz * (size_t)B * So);
   if (!h_out) return fail(VITS_ERR_NOMEM, "host alloc failed");
-  hipError_t e = hipMemcpyAsync(h_out, d_src, esz * (size_t)B * S, hipMemcpyDeviceToHost, s->stream);
+  hipError_t e = hipMemcpyAsync(h_out, d_src, esz * (size_t)B * So, hipMemcpyDeviceToHost, s->stream);
   int rc = e == hipSuccess ? check_err(s) : fail(VITS_ERR_DEVICE, "D2H failed: %s", hipGetErrorString(e));
   if (rc != VITS_OK) { free(h_out); return rc; }
   *out = h_out;
-  *out_samples = S;
-  if (out_lengths) for (int b = 0; b < B; ++b) out_lengths[b] = ylen[b] * hp.hop_length;
+  *out_samples = So;
+  if (out_lengths) for (int b = 0; b < B; ++b) out_lengths[b] = T ? T->P.n_out(ylen[b] * hp.hop_length) : ylen[b] * hp.hop_length;
   return VITS_OK;
 }
 
 static int synth_dispatch(vits_model* m, const int64_t* ids, const int64_t* lengths, int32_t B, int32_t Tx, const float* scales,
-                          const int64_t* sid, const vits_synth_opts* opts, bool pcm, float pcm_scale, void** out, int64_t* out_samples,
-                          int64_t* out_lengths) {
+                          const int64_t* sid, const vits_synth_opts* opts, bool pcm, float pcm_scale, int32_t sample_rate, void** out,
+                          int64_t* out_samples, int64_t* out_lengths) {
   if (!m || !ids || !lengths || !scales || !out || !out_samples || B <= 0 || Tx <= 0) return fail(VITS_ERR_ARG, "bad argument");
   if (!m->acoustic) return fail(VITS_ERR_UNSUPPORTED, "vocoder-only model: only the decoder stage is available");
   for (int b = 0; b < B; ++b) if (lengths[b] < 0 || lengths[b] > Tx) return fail(VITS_ERR_ARG, "length out of range");
+  int rate = 0;  // 0: the native rate, on the path as it was
+  TRY(resample_rate_arg(m, sample_rate, &rate));
   static const bool env_off = getenv("VITS_NO_FASTPATH") != nullptr;
   if (m->hp.bert_dim > 0 && (!opts || !opts->bert)) return fail(VITS_ERR_ARG, "this voice is BERT-conditioned: the bert feed [B,%d,T_x] is required", m->hp.bert_dim);
   if (m->hp.bert_dim == 0 && opts && opts->bert) return fail(VITS_ERR_ARG, "the bert feed was given but this voice has no BERT projection (hparams.bert_dim == 0)");
@@ -412,21 +474,35 @@ static int synth_dispatch(vits_model* m, const int64_t* ids, const int64_t* leng
   for (int attempt = 0;; ++attempt) {
     tl_ps_timed_out = false;
     const int rc = (g_fast_path && !env_off && !injected)
-                       ? synth_fast(m, ids, lengths, B, Tx, scales, sid, opts, pcm, pcm_scale, out, out_samples, out_lengths)
-                       : synth_eager(m, ids, lengths, B, Tx, scales, sid, opts, pcm, pcm_scale, out, out_samples, out_lengths);
+                       ? synth_fast(m, ids, lengths, B, Tx, scales, sid, opts, pcm, pcm_scale, rate, out, out_samples, out_lengths)
+                       : synth_eager(m, ids, lengths, B, Tx, scales, sid, opts, pcm, pcm_scale, rate, out, out_samples, out_lengths);
     if (rc == VITS_OK || !tl_ps_timed_out || attempt) return rc;  // a persistent program timed out: once more, on launches
   }
 }
 
 int vits_synthesize(vits_model* m, const int64_t* ids, const int64_t* lengths, int32_t B, int32_t Tx, const float* scales,
                     const int64_t* sid, const vits_synth_opts* opts, float** out_audio, int64_t* out_samples, int64_t* out_lengths) {
-  return synth_dispatch(m, ids, lengths, B, Tx, scales, sid, opts, false, 1.f, reinterpret_cast<void**>(out_audio), out_samples, out_lengths);
+  return synth_dispatch(m, ids, lengths, B, Tx, scales, sid, opts, false, 1.f, 0, reinterpret_cast<void**>(out_audio), out_samples, out_lengths);
+}
+
+int vits_synthesize_rate(vits_model* m, const int64_t* ids, const int64_t* lengths, int32_t B, int32_t Tx, const float* scales,
+                         const int64_t* sid, const vits_synth_opts* opts, int32_t sample_rate, float** out_audio, int64_t* out_samples,
+                         int64_t* out_lengths) {
+  if (sample_rate < 0) return fail(VITS_ERR_UNSUPPORTED, "sample_rate %d: must be positive, or 0 for the voice's own rate", sample_rate);
+  return synth_dispatch(m, ids, lengths, B, Tx, scales, sid, opts, false, 1.f, sample_rate, reinterpret_cast<void**>(out_audio), out_samples, out_lengths);
 }
 
 int vits_synthesize_pcm16(vits_model* m, const int64_t* ids, const int64_t* lengths, int32_t B, int32_t Tx, const float* scales,
                           const int64_t* sid, const vits_synth_opts* opts, float pcm_scale, int16_t** out_pcm, int64_t* out_samples,
                           int64_t* out_lengths) {
-  return synth_dispatch(m, ids, lengths, B, Tx, scales, sid, opts, true, pcm_scale, reinterpret_cast<void**>(out_pcm), out_samples, out_lengths);
+  return synth_dispatch(m, ids, lengths, B, Tx, scales, sid, opts, true, pcm_scale, 0, reinterpret_cast<void**>(out_pcm), out_samples, out_lengths);
+}
+
+int vits_synthesize_pcm16_rate(vits_model* m, const int64_t* ids, const int64_t* lengths, int32_t B, int32_t Tx, const float* scales,
+                               const int64_t* sid, const vits_synth_opts* opts, float pcm_scale, int32_t sample_rate, int16_t** out_pcm,
+                               int64_t* out_samples, int64_t* out_lengths) {
+  if (sample_rate < 0) return fail(VITS_ERR_UNSUPPORTED, "sample_rate %d: must be positive, or 0 for the voice's own rate", sample_rate);
+  return synth_dispatch(m, ids, lengths, B, Tx, scales, sid, opts, true, pcm_scale, sample_rate, reinterpret_cast<void**>(out_pcm), out_samples, out_lengths);
 }
 
 void vits_free_pcm16(int16_t* p) { free(p); }

@@ -106,6 +106,16 @@ struct vits_session {
   char* out_h = nullptr;           // back: pinned host copy of whichever output the call asked for
   size_t out_elems = 0;
   hipGraphExec_t g2[8] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};  // [persist*4 + solo*2 + pcm]
+  // back: phase 2 at another output rate (include/vits_resample.h).  The rate changes a launch and the size of the output, so it is part
+  // of the graph key: one entry per rate, with its own graphs and its own output buffers [B, ceil(T_y bucket * hop * L / M)].
+  struct RateOut {
+    hipGraphExec_t g2[8] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};  // as g2 above
+    void* y_d = nullptr;   // device: float or int16 (sized for float)
+    char* y_h = nullptr;   // pinned host copy
+    long long n_cap = 0;   // outputs per item
+    uint64_t last_use = 0;
+  };
+  std::map<int, RateOut> rates;
   uint64_t last_use = 0;
   size_t cache_bytes = 0;          // device bytes this session pins while cached (front: incl. its backs)
 };
@@ -351,6 +361,12 @@ static void session_free(vits_session* s) {
   drop_graphs(s);
   for (auto& kv : s->backs) session_free(kv.second);
   s->backs.clear();
+  for (auto& kv : s->rates) {
+    for (hipGraphExec_t g : kv.second.g2) if (g) hipGraphExecDestroy(g);
+    if (kv.second.y_d) hipFree(kv.second.y_d);
+    if (kv.second.y_h) hipHostFree(kv.second.y_h);
+  }
+  s->rates.clear();
   for (int i = 0; i < 8; ++i) { if (s->g1[i]) hipGraphExecDestroy(s->g1[i]); if (s->g2[i]) hipGraphExecDestroy(s->g2[i]); }
   if (s->io_h) hipHostFree(s->io_h);
   if (s->io_d) hipFree(s->io_d);

@@ -19,11 +19,16 @@ struct vits_stream {
   // per slot: a single 192-frame decode is latency-bound (0.6 ms per chunk) and pays the 2 x 32-frame halo per 128 frames, a
   // wide window pays it once per kmax chunks and runs the one-shot's kernels.  Two audio slots: while the chunks of one window
   // are copied out on the session's copy stream, the next window is decoded into the other slot on the compute stream.
-  struct Win { int lo = -1, hi = -1, start = -1; float* aud = nullptr; hipEvent_t done = nullptr; };
+  struct Win { int lo = -1, hi = -1, start = -1, width = 0; float* aud = nullptr; hipEvent_t done = nullptr; };
   Win win[2];
   int kmax = 8, WK = 0;
   bool clamp = false;               // audio clamped to [-1, 1] (the StableTTS export, onnx/export.py:28-31)
   float *d_win = nullptr, *h_pin = nullptr;
+  // another output rate (include/vits_resample.h): every emitted chunk is resampled from its window's audio slot into d_rs on the copy
+  // stream, then copied out.  The windows carry ceil(half_width_in / hop) more halo frames, so the filter reads exactly decoded samples.
+  const ResampleTab* rs = nullptr;
+  float* d_rs = nullptr;
+  long long rs_cap = 0;             // outputs one chunk can have: ceil(chunk * hop * L / M) + 1
   hipEvent_t ev = nullptr;
   int find(int lo) const { for (int i = 0; i < 2; ++i) if (lo >= win[i].lo && lo < win[i].hi) return i; return -1; }
 };
@@ -41,6 +46,7 @@ static int stream_launch(vits_stream* st, int lo, int slot) {
   w.lo = lo;
   w.hi = wide ? lo + st->kmax * st->chunk : lo + st->chunk;
   w.start = start;
+  w.width = width;
   hipLaunchKernelGGL(window_copy_kernel, dim3(cdiv(width, 256), I), dim3(256), 0, s->stream, st->z, (long long)st->Ty, start, width, st->d_win);
   const long long S = (long long)width * st->m->hp.hop_length;
   run_decoder(s, st->d_win, false, 1, width, w.aud, S);
@@ -69,6 +75,14 @@ static int stream_start(vits_stream* st, const float* z, int Ty, int chunk_frame
   st->z = z;
   st->Ty = (int)Ty;
   st->halo = m->rag_halo;
+  size_t pin_elems = (size_t)chunk_frames * hp.hop_length;
+  if (st->rs) {
+    st->halo += cdiv(st->rs->P.half, hp.hop_length);
+    st->rs_cap = st->rs->P.n_out((long long)chunk_frames * hp.hop_length) + 1;
+    pin_elems = (size_t)st->rs_cap;
+    st->d_rs = st->hs->dev_alloc<float>((size_t)st->rs_cap);
+    if (!st->d_rs) { vits_stream_close(st); return fail(VITS_ERR_NOMEM, "stream buffers"); }
+  }
   st->chunk = chunk_frames;
   st->W = chunk_frames + 2 * st->halo;
   if (st->W > st->Ty) st->W = st->Ty;
@@ -82,7 +96,7 @@ static int stream_start(vits_stream* st, const float* z, int Ty, int chunk_frame
   }
   if (!st->d_win || !st->win[0].aud || !st->win[1].aud ||
       hipEventCreateWithFlags(&st->win[0].done, hipEventDisableTiming) != hipSuccess ||
-      hipEventCreateWithFlags(&st->win[1].done, hipEventDisableTiming) != hipSuccess || hipHostMalloc((void**)&st->h_pin, sizeof(float) * (size_t)chunk_frames * hp.hop_length) != hipSuccess ||
+      hipEventCreateWithFlags(&st->win[1].done, hipEventDisableTiming) != hipSuccess || hipHostMalloc((void**)&st->h_pin, sizeof(float) * pin_elems) != hipSuccess ||
       hipEventCreateWithFlags(&st->ev, hipEventDisableTiming) != hipSuccess) {
     vits_stream_close(st);
     return fail(VITS_ERR_NOMEM, "stream buffers");
@@ -92,18 +106,37 @@ static int stream_start(vits_stream* st, const float* z, int Ty, int chunk_frame
   st->hs->pscope.release();
   rc = stream_launch(st, 0, 0);  // first chunk is already decoding when the caller asks for it
   if (rc != VITS_OK) { vits_stream_close(st); return rc; }
-  if (total_samples) *total_samples = (int64_t)Ty * hp.hop_length;
+  if (total_samples) *total_samples = st->rs ? st->rs->P.n_out((long long)Ty * hp.hop_length) : (int64_t)Ty * hp.hop_length;
   *out = st;
   return VITS_OK;
 }
 
 
+// the table of a stream at `sample_rate` (null: the native rate)
+static int stream_rate(vits_model* m, int32_t sample_rate, const ResampleTab** T) {
+  *T = nullptr;
+  if (sample_rate < 0) return fail(VITS_ERR_UNSUPPORTED, "sample_rate %d: must be positive, or 0 for the voice's own rate", sample_rate);
+  int rate = 0;
+  TRY(resample_rate_arg(m, sample_rate, &rate));
+  if (!rate) return VITS_OK;
+  HIP_TRY(hipSetDevice(m->device));
+  return resample_get(m->device, m->hp.sampling_rate, rate, T);
+}
+
 int vits_stream_open(vits_model* m, const int64_t* ids, int32_t Tx, const float* scales, int64_t sid, const vits_synth_opts* opts,
                      int32_t chunk_frames, vits_stream** out, int64_t* total_samples) {
+  return vits_stream_open_rate(m, ids, Tx, scales, sid, opts, chunk_frames, 0, out, total_samples);
+}
+
+int vits_stream_open_rate(vits_model* m, const int64_t* ids, int32_t Tx, const float* scales, int64_t sid, const vits_synth_opts* opts,
+                          int32_t chunk_frames, int32_t sample_rate, vits_stream** out, int64_t* total_samples) {
   if (!m || !ids || !scales || !out || Tx <= 0 || chunk_frames <= 0) return fail(VITS_ERR_ARG, "bad argument");
+  const ResampleTab* T = nullptr;
+  TRY(stream_rate(m, sample_rate, &T));
   for (int attempt = 0;; ++attempt) {
     vits_stream* st = new vits_stream();
     st->m = m;
+    st->rs = T;
     st->hs = new HostStage(m);
     std::vector<int64_t> ylen;
     int64_t Ty = 0, len = Tx;
@@ -120,10 +153,18 @@ int vits_stream_open(vits_model* m, const int64_t* ids, int32_t Tx, const float*
 // two-model voice (StableTTS mel -> vocoder, vosk_tts/synth.py:113-126) or a z produced elsewhere.  flags bit 0: clamp to [-1, 1].
 int vits_stream_open_latent(vits_model* m, const float* z, int32_t Ty, int32_t chunk_frames, uint32_t flags, vits_stream** out,
                             int64_t* total_samples) {
+  return vits_stream_open_latent_rate(m, z, Ty, chunk_frames, flags, 0, out, total_samples);
+}
+
+int vits_stream_open_latent_rate(vits_model* m, const float* z, int32_t Ty, int32_t chunk_frames, uint32_t flags, int32_t sample_rate,
+                                 vits_stream** out, int64_t* total_samples) {
   if (!m || !z || !out || Ty <= 0 || chunk_frames <= 0) return fail(VITS_ERR_ARG, "bad argument");
   if (Ty > (1 << 18)) return fail(VITS_ERR_ARG, "T_y unreasonably large");
+  const ResampleTab* T = nullptr;
+  TRY(stream_rate(m, sample_rate, &T));
   vits_stream* st = new vits_stream();
   st->m = m;
+  st->rs = T;
   st->hs = new HostStage(m);
   st->clamp = (flags & 1u) != 0;
   int rc = begin_stage(*st->hs, 1, 1, Ty, 0);
@@ -141,13 +182,22 @@ int vits_stream_next(vits_stream* st, float* audio, int64_t capacity, int64_t* n
   vits_session* s = st->hs->s;
   const int hop = st->m->hp.hop_length;
   const int lo = st->pos, hi = lo + st->chunk < st->Ty ? lo + st->chunk : st->Ty;
-  const int64_t n = (int64_t)(hi - lo) * hop;
+  // at another rate the chunk that covers input samples [a, b) is the outputs ceil(a L / M) <= n < ceil(b L / M)
+  const int64_t n_first = st->rs ? st->rs->P.n_out((long long)lo * hop) : 0;
+  const int64_t n = st->rs ? st->rs->P.n_out((long long)hi * hop) - n_first : (int64_t)(hi - lo) * hop;
   if (capacity < n) return fail(VITS_ERR_ARG, "chunk capacity %lld < %lld samples", (long long)capacity, (long long)n);
   int slot = st->find(lo);
   if (slot < 0) { slot = 0; TRY(stream_launch(st, lo, slot)); }  // only the first call: later windows are decoded ahead
   const vits_stream::Win& w = st->win[slot];
   HIP_TRY(hipStreamWaitEvent(s->copy_stream, w.done, 0));
-  HIP_TRY(hipMemcpyAsync(st->h_pin, w.aud + (size_t)(lo - w.start) * hop, sizeof(float) * n, hipMemcpyDeviceToHost, s->copy_stream));
+  if (st->rs) {
+    // the window's slot holds input samples [w.start * hop, (w.start + width) * hop); beyond the utterance's end the filter sees zeros
+    resample_launch<float>(s->copy_stream, *st->rs, w.aud, 0, (long long)w.start * hop, (long long)w.width * hop, nullptr, (long long)st->Ty * hop, 1, st->d_rs, 0,
+                           n_first, n, 1.f, nullptr);
+    HIP_TRY(hipMemcpyAsync(st->h_pin, st->d_rs, sizeof(float) * n, hipMemcpyDeviceToHost, s->copy_stream));
+  } else {
+    HIP_TRY(hipMemcpyAsync(st->h_pin, w.aud + (size_t)(lo - w.start) * hop, sizeof(float) * n, hipMemcpyDeviceToHost, s->copy_stream));
+  }
   HIP_TRY(hipEventRecord(st->ev, s->copy_stream));
   st->pos = hi;
   // decode ahead into the other slot: every chunk of the window it held was handed over (and waited for) before this call

@@ -41,7 +41,7 @@ class RequestCoalescer:
     Natural batching: a request that finds fewer than `max_inflight` engine calls running runs at once (the first of them on the
     persistent single-utterance path; nothing added to a lone client's latency).  Requests that arrive while `max_inflight` calls are in
     flight queue up; when one of those calls returns, its thread hands the queue's compatible requests (same scales / output kind /
-    conversion scale, at most `max_batch`) to the first waiter, which runs them as ONE padded VITS_FLAG_SOLO_BATCH call with per-request
+    conversion scale / output sample rate, at most `max_batch`) to the first waiter, which runs them as ONE padded VITS_FLAG_SOLO_BATCH call with per-request
     item seeds -- every item of a solo batch is its own single-utterance synthesis (own Philox streams, zeros beyond its own end), so
     what a request gets does not depend on what it was batched with -- and scatters the results.
 
@@ -225,7 +225,7 @@ BACK_SESSIONS_PER_FRONT = 6
 _GRAPH_INPUTS = ("input", "input_lengths", "scales", "sid")
 _OPTIONAL_NONE = ("bert", "phone_duration_extra")
 # extension feeds (not part of the ONNX graph) used by parity tests
-_EXT = ("vits.noise_dp", "vits.noise_prior", "vits.forced_durations", "vits.seed", "vits.solo", "vits.item_seeds")
+_EXT = ("vits.noise_dp", "vits.noise_prior", "vits.forced_durations", "vits.seed", "vits.solo", "vits.item_seeds", "vits.sample_rate")
 
 
 class _Arg:
@@ -290,14 +290,14 @@ class VitsSession:
 
     def _run_solo_batch(self, key, reqs):
         """reqs: [(ids [1,T] int64, sid, seed)] -> per request (audio-or-pcm [1,S_b], lengths [1]); one request: the plain call"""
-        kind, scales, scale = key
+        kind, scales, scale, rate = key  # (rate: output sample rate in Hz, 0 = the voice's own; part of the key, so a batch has one)
         scales = np.array(scales, np.float32)
         if len(reqs) == 1:
             ids, sid, seed = reqs[0]
             lens = np.array([ids.shape[1]], np.int64)
             if kind == "pcm":
-                return [self._model.synthesize_pcm16(ids, lens, scales, np.array([sid], np.int64), pcm_scale=scale, seed=seed)]
-            return [self._model.synthesize(ids, lens, scales, np.array([sid], np.int64), seed=seed)]
+                return [self._model.synthesize_pcm16(ids, lens, scales, np.array([sid], np.int64), pcm_scale=scale, seed=seed, sample_rate=rate)]
+            return [self._model.synthesize(ids, lens, scales, np.array([sid], np.int64), seed=seed, sample_rate=rate)]
         # batch sizes come in powers of two (filled up with one-token dummies, whose padding tiles the ragged solo batch never
         # computes): every (batch size, length bucket) is a workspace and two captured graphs inside the engine, and a thread pool
         # produces every batch size between 1 and its own size
@@ -313,9 +313,10 @@ class VitsSession:
         sids = np.array([r[1] for r in reqs], np.int64)
         seeds = np.array([r[2] for r in reqs], np.uint64)
         if kind == "pcm":
-            out, ol = self._model.synthesize_pcm16(batch, lens, scales, sids, pcm_scale=scale, seed=int(seeds[0]), solo=True, item_seeds=seeds)
+            out, ol = self._model.synthesize_pcm16(batch, lens, scales, sids, pcm_scale=scale, seed=int(seeds[0]), solo=True, item_seeds=seeds,
+                                                   sample_rate=rate)
         else:
-            out, ol = self._model.synthesize(batch, lens, scales, sids, seed=int(seeds[0]), solo=True, item_seeds=seeds)
+            out, ol = self._model.synthesize(batch, lens, scales, sids, seed=int(seeds[0]), solo=True, item_seeds=seeds, sample_rate=rate)
         return [(out[b:b + 1, :int(ol[b])].copy(), ol[b:b + 1].copy()) for b in range(n_real)]
 
     # -- onnxruntime.InferenceSession surface used by the reference ------------------------
@@ -363,12 +364,22 @@ class VitsSession:
                 seed = next(self._seed)
         return feed, ids, sid, int(seed)
 
+    def _rate(self, sample_rate):
+        """output sample rate of a request -> 0 for None / 0 / the voice's own rate (those take the calls without a rate)"""
+        rate = int(sample_rate or 0)
+        if rate < 0:
+            raise ValueError(f"sample_rate {rate}: must be positive, or None for the voice's own {self.hp.sampling_rate} Hz")
+        return 0 if rate == self.hp.sampling_rate else rate
+
     def run(self, output_names, input_feed, run_options=None):
+        """Extension feed "vits.sample_rate" (next to "vits.seed"): output rate in Hz; the time axis of the output is then in output
+        samples (include/vits_resample.h)."""
         feed, ids, sid, seed = self._validated(output_names, input_feed)
         self._watch()
+        rate = self._rate(feed.get("vits.sample_rate"))
         n = self._coalescable(feed, ids)
         if n:
-            key = ("f32", tuple(float(v) for v in np.asarray(feed["scales"], np.float32).reshape(-1)), 1.0)
+            key = ("f32", tuple(float(v) for v in np.asarray(feed["scales"], np.float32).reshape(-1)), 1.0, rate)
             audio, lengths = self.coalescer.submit(key, np.ascontiguousarray(ids[:, :n], np.int64), int(sid[0]), int(seed))
             self.last_lengths = lengths
             return [audio[:, None, None, :]]
@@ -376,20 +387,23 @@ class VitsSession:
             ids, np.asarray(feed["input_lengths"]).reshape(-1), np.asarray(feed["scales"], np.float32).reshape(-1), sid,
             noise_dp=feed.get("vits.noise_dp"), noise_prior=feed.get("vits.noise_prior"),
             forced_durations=feed.get("vits.forced_durations"), seed=int(seed), solo=bool(feed.get("vits.solo", False)),
-            item_seeds=feed.get("vits.item_seeds"), bert=feed.get("bert"))
+            item_seeds=feed.get("vits.item_seeds"), bert=feed.get("bert"), sample_rate=rate)
         self.last_lengths = lengths
         return [audio[:, None, None, :]]
 
-    def run_pcm16(self, input_feed, scale=1.0, return_lengths=False):
+    def run_pcm16(self, input_feed, scale=1.0, return_lengths=False, sample_rate=None):
         """run() followed by `audio.squeeze() * scale` and Synth.audio_float_to_int16 (vosk_tts/synth.py:127-130), with the
         conversion done on the device (vits_synthesize_pcm16): returns int16 [B, S] -- bit-identical to converting run()'s
         float output with numpy, half the bytes over PCIe.  return_lengths: also return the per-item sample counts
-        (concurrent callers must take them from the call, not from the shared `last_lengths` attribute)."""
+        (concurrent callers must take them from the call, not from the shared `last_lengths` attribute).
+        sample_rate: output rate in Hz (default: the feed's "vits.sample_rate", else the voice's own): the resampler converts in its
+        epilogue, so the call launches as many kernels as at the voice's rate and copies rate_out / rate_in as many bytes."""
         feed, ids, sid, seed = self._validated(None, input_feed)
         self._watch()
+        rate = self._rate(sample_rate if sample_rate is not None else feed.get("vits.sample_rate"))
         n = self._coalescable(feed, ids)
         if n:
-            key = ("pcm", tuple(float(v) for v in np.asarray(feed["scales"], np.float32).reshape(-1)), float(scale))
+            key = ("pcm", tuple(float(v) for v in np.asarray(feed["scales"], np.float32).reshape(-1)), float(scale), rate)
             pcm, lengths = self.coalescer.submit(key, np.ascontiguousarray(ids[:, :n], np.int64), int(sid[0]), int(seed))
             self.last_lengths = lengths
             return (pcm, lengths) if return_lengths else pcm
@@ -397,15 +411,17 @@ class VitsSession:
             ids, np.asarray(feed["input_lengths"]).reshape(-1), np.asarray(feed["scales"], np.float32).reshape(-1), sid,
             pcm_scale=float(scale), noise_dp=feed.get("vits.noise_dp"), noise_prior=feed.get("vits.noise_prior"),
             forced_durations=feed.get("vits.forced_durations"), seed=int(seed), solo=bool(feed.get("vits.solo", False)),
-            item_seeds=feed.get("vits.item_seeds"), bert=feed.get("bert"))
+            item_seeds=feed.get("vits.item_seeds"), bert=feed.get("bert"), sample_rate=rate)
         self.last_lengths = lengths
         return (pcm, lengths) if return_lengths else pcm
 
-    def run_stream(self, output_names, input_feed, chunk_frames=64):
+    def run_stream(self, output_names, input_feed, chunk_frames=64, sample_rate=None):
         """Streaming form of run() for ONE utterance (extension; the reference's transport is already
         `stream AudioChunk`, server/tts_service.proto:46-54): yields float32 [n] chunks of chunk_frames*256
-        samples whose concatenation equals run(...)[0].squeeze() for the same feed (same "vits.seed")."""
+        samples whose concatenation equals run(...)[0].squeeze() for the same feed (same "vits.seed").
+        sample_rate (default: the feed's "vits.sample_rate"): output rate in Hz; chunk sizes then vary by one sample."""
         feed, ids, sid, seed = self._validated(output_names, input_feed)
+        rate = self._rate(sample_rate if sample_rate is not None else feed.get("vits.sample_rate"))
         if ids.shape[0] != 1:
             raise ValueError("run_stream takes one utterance")
         n = int(np.asarray(feed["input_lengths"]).reshape(-1)[0])
@@ -416,7 +432,7 @@ class VitsSession:
             ids[:, :n], np.asarray(feed["scales"], np.float32).reshape(-1), int(sid[0]), chunk_frames=chunk_frames,
             noise_dp=None if nd is None else np.asarray(nd)[:, :, :n], noise_prior=feed.get("vits.noise_prior"),
             forced_durations=None if fd is None else np.asarray(fd)[:, :n], seed=seed,
-            bert=None if bert is None else np.ascontiguousarray(np.asarray(bert, np.float32)[:, :, :n]))
+            bert=None if bert is None else np.ascontiguousarray(np.asarray(bert, np.float32)[:, :, :n]), sample_rate=rate)
 
     def warmup(self, max_tokens=128, frames_per_token=(2.0, 5.0), speaker_id=0, freeze_gc=False, typical_frames_per_token=3.0,
                stream_chunk_frames=None):

@@ -13,7 +13,7 @@ from .capi import VitsLib
 from .capi_stts import SttsModel
 
 _INPUTS = ("input", "input_lengths", "scales", "sid", "bert", "phone_duration_extra")
-_EXT = ("vits.noise", "vits.seed", "vits.n_timesteps")
+_EXT = ("vits.noise", "vits.seed", "vits.n_timesteps", "vits.sample_rate")
 
 
 class SttsSession:
@@ -57,20 +57,46 @@ class SttsSession:
                 seed = next(self._seed)
         return feed, ids[0], np.asarray(feed["scales"], np.float32).reshape(-1), sid, bert, pde, int(seed)
 
+    def _rate(self, sample_rate):
+        """output sample rate of a request -> 0 for None / 0 / the vocoder's own rate"""
+        rate = int(sample_rate or 0)
+        if rate < 0:
+            raise ValueError(f"sample_rate {rate}: must be positive, or None for the voice's own {self._vocoder.hp.sampling_rate} Hz")
+        return 0 if rate == self._vocoder.hp.sampling_rate else rate
+
+    def resample(self, audio, lengths, sample_rate):
+        """audio float32 [B, S] with per-item sample counts -> (audio, lengths) at `sample_rate` (vits_op_resample on the host
+        buffer, every item from its own samples only); None / the vocoder's own rate: unchanged"""
+        rate = self._rate(sample_rate)
+        if not rate:
+            return audio, lengths
+        native = self._vocoder.hp.sampling_rate
+        lengths = np.asarray(lengths, np.int64).reshape(-1)
+        out = self._lib.op_resample(audio, lengths, native, rate, device=self._vocoder.device)
+        return out, np.array([self._lib.out_samples(n, native, rate) for n in lengths], np.int64)
+
     def run(self, output_names, input_feed, run_options=None):
+        """Extension feed "vits.sample_rate": output rate in Hz (the finished waveform is resampled, include/vits_resample.h)."""
         feed, ids, scales, sid, bert, pde, seed = self._parse(output_names, input_feed)
         audio, _ = self._model.synthesize(ids, scales, sid, bert, pde, noise=feed.get("vits.noise"), seed=seed,
                                           n_timesteps=int(feed.get("vits.n_timesteps", 0)), want_mel=False)
+        if self._rate(feed.get("vits.sample_rate")):
+            audio = self.resample(audio[None, :], [audio.shape[0]], feed["vits.sample_rate"])[0][0]
         outs = {"wav": audio[None, :], "wav_lengths": np.array([audio.shape[0]], np.int64)}
         return [outs[n] for n in (output_names or ["wav", "wav_lengths"])]
 
-    def run_stream(self, output_names, input_feed, chunk_frames=64):
+    def run_stream(self, output_names, input_feed, chunk_frames=64, sample_rate=None):
         """Streaming form of run() (extension; the reference's transport is already `stream AudioChunk`,
         server/tts_service.proto:46-54): yields float32 [n] chunks of chunk_frames * hop samples whose concatenation equals
         run(...)[0].squeeze() for the same feed (same "vits.seed").  The acoustic model runs once, the vocoder is streamed."""
         feed, ids, scales, sid, bert, pde, seed = self._parse(output_names, input_feed)
         if "vits.noise" in feed:
             raise NotImplementedError("run_stream draws the CFM noise on the device (vits.seed)")
+        rate = self._rate(sample_rate if sample_rate is not None else feed.get("vits.sample_rate"))
+        if rate:  # the acoustic model's mel, then the vocoder streamed at the rate asked for (vits_stream_open_latent_rate; clamped like the export)
+            _, mel = self._model.synthesize(ids, scales, sid, bert, pde, seed=seed, n_timesteps=int(feed.get("vits.n_timesteps", 0)),
+                                            want_audio=False, want_mel=True)
+            return self._vocoder.stream_latent(mel, chunk_frames=chunk_frames, clamp=True, sample_rate=rate)
         return self._model.stream(ids, scales, sid, bert, pde, seed=seed, n_timesteps=int(feed.get("vits.n_timesteps", 0)),
                                   chunk_frames=chunk_frames)
 

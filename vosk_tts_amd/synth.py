@@ -181,8 +181,20 @@ class Synth:
         return {"input": ids, "input_lengths": lens, "bert": bert, "phone_duration_extra": pde,
                 "sid": np.array([0 if v is None else int(v) for v in sids], np.int64)}
 
-    def synth_audio(self, text, speaker_id=0, noise_level=None, speech_rate=None, duration_noise_level=None, scale=None):
+    def native_rate(self):
+        """the voice's own sample rate (the session's hparams; 22050 for sessions that do not say)"""
+        sess = self.model.onnx
+        hp = getattr(getattr(sess, "_vocoder", None), "hp", None) or getattr(sess, "hp", None)
+        return int(getattr(hp, "sampling_rate", 0) or 22050)
+
+    def synth_audio(self, text, speaker_id=0, noise_level=None, speech_rate=None, duration_noise_level=None, scale=None, sample_rate=None):
+        """sample_rate: output rate in Hz (extension; default None = the voice's own rate, the reference's behaviour): the feed gets
+        "vits.sample_rate" and the engine resamples on the device."""
         args, scale = self._feed(text, speaker_id, noise_level, speech_rate, duration_noise_level, scale)
+        rate = self.native_rate()
+        if sample_rate and int(sample_rate) != rate:
+            rate = int(sample_rate)
+            args["vits.sample_rate"] = rate
 
         start_time = time.perf_counter()
         run_pcm16 = getattr(self.model.onnx, "run_pcm16", None)
@@ -197,29 +209,31 @@ class Synth:
             audio = self.audio_float_to_int16(audio)
         end_time = time.perf_counter()
 
-        audio_duration_sec = audio.shape[-1] / 22050
+        audio_duration_sec = audio.shape[-1] / rate
         infer_sec = end_time - start_time
         real_time_factor = infer_sec / audio_duration_sec if audio_duration_sec > 0 else 0.0
         logging.info("Real-time factor: %0.2f (infer=%0.2f sec, audio=%0.2f sec)" % (real_time_factor, infer_sec, audio_duration_sec))
         return audio
 
     def synth_stream(self, text, speaker_id=0, noise_level=None, speech_rate=None, duration_noise_level=None, scale=None,
-                     chunk_frames=64):
+                     chunk_frames=64, sample_rate=None):
         """Generator of int16 PCM chunks (chunk_frames*256 samples each, ~0.74 s at the default): what a streaming
         `SynthesizeStream` handler would put into successive AudioChunk messages (tts_service.proto:46-54) instead
         of the single whole-utterance chunk of tts_server.py:54.  Same conversion as synth_audio per chunk."""
         args, scale = self._feed(text, speaker_id, noise_level, speech_rate, duration_noise_level, scale)
         if not hasattr(self.model.onnx, "run_stream"):
             raise NotImplementedError("this session type has no run_stream (VitsSession: vits_stream_open, SttsSession: stts_stream_open)")
+        if sample_rate and int(sample_rate) != self.native_rate():
+            args["vits.sample_rate"] = int(sample_rate)
         for chunk in self.model.onnx.run_stream(None, args, chunk_frames=chunk_frames):
             yield self.audio_float_to_int16(chunk * scale)
 
-    def synth(self, text, oname, speaker_id=0, noise_level=None, speech_rate=None, duration_noise_level=None, scale=None):
-        audio = self.synth_audio(text, speaker_id, noise_level, speech_rate, duration_noise_level, scale)
+    def synth(self, text, oname, speaker_id=0, noise_level=None, speech_rate=None, duration_noise_level=None, scale=None, sample_rate=None):
+        audio = self.synth_audio(text, speaker_id, noise_level, speech_rate, duration_noise_level, scale, sample_rate)
         with wave.open(oname, "w") as f:
             f.setnchannels(1)
             f.setsampwidth(2)
-            f.setframerate(22050)
+            f.setframerate(int(sample_rate) if sample_rate else self.native_rate())
             f.writeframes(audio.tobytes())
 
     def _phonemes_and_words(self, text):
