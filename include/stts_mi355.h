@@ -61,6 +61,8 @@ typedef struct stts_synth_opts {
                                * item (otherwise seed + b), so that what a request gets does not depend on what it was batched with
                                * (MultiDeviceSynth).  The field was appended after the first release of this struct: a caller built
                                * against the shorter struct never sets the flag, so the library never reads past what it passed */
+  float denoiser_strength;        /* only read when flags & STTS_FLAG_DENOISE (include/vits_denoise.h, which defines the flag): the */
+  int32_t denoiser_filter_length; /* vocoder-bias denoiser behind the clamp; 0 = 1024.  Appended by the same rule as item_seeds */
 } stts_synth_opts;
 #define STTS_FLAG_ITEM_SEEDS 1
 

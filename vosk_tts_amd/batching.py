@@ -144,11 +144,16 @@ class MultiDeviceSynth:
         return out
 
     def synth_batch(self, texts, speaker_ids=0, noise_level=None, speech_rate=None, duration_noise_level=None, scale=None, seeds=None,
-                    sample_rate=None):
+                    sample_rate=None, denoiser_strength=None):
         """texts: list of str -> list of int16 PCM arrays (22.05 kHz), one per request, in request order.  `seeds`: optional
         per-request noise seeds (default: a running counter), `speaker_ids`: one id or one per request.  `sample_rate`: output rate
-        in Hz for the whole batch (default: the voice's own; include/vits_resample.h)."""
+        in Hz for the whole batch (default: the voice's own; include/vits_resample.h).  `denoiser_strength`: the vocoder-bias
+        denoiser of a multistream voice for the whole batch (default: the voice's inference.denoiser_strength, else off; as
+        Synth.synth_audio, a VITS-family voice raises ValueError), every item denoised from its own length before any resampling."""
         s0 = self.synths[0]
+        dn = {}
+        s0._denoiser(dn, denoiser_strength)
+        denoiser_strength = dn.get("vits.denoiser_strength")
         if self.family == "vits":
             token_lists = [s0.g2p_noembed(s0.normalize(t)) for t in texts]
             return self.synth_tokens(token_lists, speaker_ids, noise_level, speech_rate, duration_noise_level, scale, seeds, sample_rate)
@@ -162,7 +167,8 @@ class MultiDeviceSynth:
         est = [len(s0.phonemize(t.replace("_", " "))) for t in texts]
         shards = plan_shards(est, len(self.devices))
         run = self._run_shard_bert if self.family == "vits_bert" else self._run_shard_multistream
-        futs = [self._pool.submit(run, r, texts, idx, sids, scales, scale, seeds, sample_rate=sample_rate) if idx else None
+        kw = {"denoiser_strength": denoiser_strength} if self.family == "multistream" else {}
+        futs = [self._pool.submit(run, r, texts, idx, sids, scales, scale, seeds, sample_rate=sample_rate, **kw) if idx else None
                 for r, idx in enumerate(shards)]
         return scatter_results(n, [idx for idx in shards if idx], [f.result() for f in futs if f is not None])
 
@@ -241,21 +247,23 @@ class MultiDeviceSynth:
                 out[k] = pcm[b, :int(lengths[b])].copy()
         return out
 
-    def _run_shard_multistream(self, r, texts, idx, sids, scales, scale, seeds, per_request=False, sample_rate=None):
+    def _run_shard_multistream(self, r, texts, idx, sids, scales, scale, seeds, per_request=False, sample_rate=None, denoiser_strength=None):
         """multistream (StableTTS / Matcha) requests `idx` on replica r: the five-stream front end of Synth._feed per request
-        (synth.py:64-87), then stts_synthesize_batch with per-request seeds; float -> int16 as Synth.audio_float_to_int16"""
+        (synth.py:64-87), then stts_synthesize_batch with per-request seeds (and the denoiser, where a strength is given);
+        float -> int16 as Synth.audio_float_to_int16"""
         synth, sess = self.synths[r], self.models[r].onnx
         if not per_request:
             def run_part(part):
                 f = synth.front_batch([texts[i] for i in part], [sids[i] for i in part])
                 with self._replica_locks[r]:
                     audio, ol = sess._model.synthesize_batch(f["input"], f["input_lengths"], scales, f["sid"], f["bert"], f["phone_duration_extra"],
-                                                             seed=0, item_seeds=np.array([seeds[i] for i in part], np.uint64))
+                                                             seed=0, item_seeds=np.array([seeds[i] for i in part], np.uint64),
+                                                             denoiser_strength=denoiser_strength)
                     audio, ol = sess.resample(audio, ol, sample_rate)
                 return [synth.audio_float_to_int16(audio[b, :int(ol[b])] * scale) for b in range(len(part))]
 
             return self._run_parts(r, idx, run_part, lambda rest: self._run_shard_multistream(r, texts, rest, sids, scales, scale, seeds, per_request=True,
-                                                                                             sample_rate=sample_rate))
+                                                                                             sample_rate=sample_rate, denoiser_strength=denoiser_strength))
         fronts = []
         for i in idx:
             feed, _ = synth._feed(texts[i], sids[i], None, None, None, None)
@@ -278,7 +286,8 @@ class MultiDeviceSynth:
                     pde[b, :lens[b]] = fronts[k][2]
             with self._replica_locks[r]:
                 audio, ol = sess._model.synthesize_batch(ids, lens, scales, np.array([sids[idx[k]] for k in part], np.int64), bert, pde,
-                                                         seed=0, item_seeds=np.array([seeds[idx[k]] for k in part], np.uint64))
+                                                         seed=0, item_seeds=np.array([seeds[idx[k]] for k in part], np.uint64),
+                                                         denoiser_strength=denoiser_strength)
                 audio, ol = sess.resample(audio, ol, sample_rate)
             for b, k in enumerate(part):
                 out[k] = synth.audio_float_to_int16(audio[b, :int(ol[b])] * scale)

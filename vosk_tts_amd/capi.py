@@ -113,6 +113,7 @@ class VitsLib:
                                           c_i32p]
         self.is_device = bool(f("is_device_backend")())
         self.has_resample = False
+        self.has_denoise = False
         if self.is_device:
             c_i16p = ctypes.POINTER(ctypes.c_int16)
             f("synthesize_pcm16").argtypes = [ctypes.c_void_p, c_i64p, c_i64p, ctypes.c_int32, ctypes.c_int32, c_f32p, c_i64p,
@@ -155,6 +156,14 @@ class VitsLib:
                                                   ctypes.POINTER(ctypes.c_void_p), c_i64p]
                 f("stream_open_latent_rate").argtypes = [ctypes.c_void_p, c_f32p, ctypes.c_int32, ctypes.c_int32, ctypes.c_uint32,
                                                          ctypes.c_int32, ctypes.POINTER(ctypes.c_void_p), c_i64p]
+            # include/vits_denoise.h: the vocoder-bias denoiser, an extension of the product library like the resampler
+            self.has_denoise = self.has("op_denoise")
+            if self.has_denoise:
+                f("denoise_bias").argtypes = [ctypes.c_void_p, ctypes.c_int32, c_f32p, ctypes.c_int64]
+                f("op_denoise").argtypes = [ctypes.c_int, c_f32p, c_i64p, ctypes.c_int32, ctypes.c_int64, c_f32p, ctypes.c_int32, ctypes.c_float,
+                                            c_f32p]
+                f("stream_open_latent_denoise").argtypes = [ctypes.c_void_p, c_f32p, ctypes.c_int32, ctypes.c_int32, ctypes.c_uint32,
+                                                            ctypes.c_float, ctypes.c_int32, ctypes.POINTER(ctypes.c_void_p), c_i64p]
             if self.has("debug_clock_probe"):
                 f("debug_clock_probe").argtypes = [ctypes.c_int, ctypes.c_int32, ctypes.POINTER(ctypes.c_double), ctypes.c_int32]
 
@@ -261,6 +270,31 @@ class VitsLib:
             raise ValueError("lengths must be [B]")
         y = np.empty((B, self.out_samples(N, rate_in, rate_out)), np.float32)
         self.check(self._fn("op_resample")(device, _p(x, c_f32p), _p(lengths, c_i64p), B, N, int(rate_in), int(rate_out), _p(y, c_f32p)))
+        return y
+
+    # ---- vocoder-bias denoiser (include/vits_denoise.h) ---------------------
+    def _need_denoise(self):
+        if not self.has_denoise:
+            raise VitsError(4, "this backend has no denoiser (include/vits_denoise.h)")
+
+    def op_denoise(self, x, lengths, bias, strength, filter_length=1024, device=0):
+        """vits_op_denoise: x float32 [B, N], lengths [B], bias [filter_length / 2 + 1] -> y float32 [B, hop * (N // hop)], hop =
+        filter_length / 4; item b from x[b, :lengths[b]] only, zero at and beyond hop * (lengths[b] // hop)"""
+        self._need_denoise()
+        x = _f32(x)
+        if x.ndim != 2:
+            raise ValueError("x must be [B, N]")
+        B, N = x.shape
+        lengths = _i64(lengths).reshape(-1)
+        if lengths.shape != (B,):
+            raise ValueError("lengths must be [B]")
+        n = int(filter_length)
+        bias = _f32(bias).reshape(-1)
+        if 0 < n <= 4096 and bias.shape[0] != n // 2 + 1:  # (a filter length the library refuses is refused there, by name)
+            raise ValueError(f"bias must hold filter_length / 2 + 1 = {n // 2 + 1} values")
+        hop = max(n // 4, 1)
+        y = np.empty((B, hop * (N // hop)), np.float32)
+        self.check(self._fn("op_denoise")(device, _p(x, c_f32p), _p(lengths, c_i64p), B, N, _p(bias, c_f32p), n, float(strength), _p(y, c_f32p)))
         return y
 
     def mas_maximum_path(self, values, t_ys, t_xs, device=0):
@@ -437,9 +471,19 @@ class VitsModel:
                                          int(chunk_frames), ctypes.byref(st), ctypes.byref(total)))
         return self._drain(st, chunk_frames, rate)
 
-    def stream_latent(self, z, chunk_frames=64, clamp=False, sample_rate=None):
+    def denoise_bias(self, filter_length=1024):
+        """vits_denoise_bias: float32 [filter_length / 2 + 1], the magnitudes of frame 0 of this vocoder's output for an all-zero
+        input (computed once per filter length and cached in the model)"""
+        self.lib._need_denoise()
+        n = int(filter_length) or 1024
+        bias = np.empty(max(n // 2 + 1, 1), np.float32)
+        self.lib.check(self.lib._fn("denoise_bias")(self._h, int(filter_length), _p(bias, c_f32p), bias.shape[0]))
+        return bias
+
+    def stream_latent(self, z, chunk_frames=64, clamp=False, sample_rate=None, denoiser_strength=None, denoiser_filter_length=0):
         """Streams the decoder over a latent the caller holds (vits_stream_open_latent): z float32 [inter_channels, T_y].
-        sample_rate: as for stream (vits_stream_open_latent_rate)."""
+        sample_rate: as for stream (vits_stream_open_latent_rate).  denoiser_strength (None = off): every chunk goes through the
+        vocoder-bias denoiser (vits_stream_open_latent_denoise), chunk sizes unchanged; not together with another sample rate."""
         z = _f32(z)
         if z.ndim != 2 or z.shape[0] != self.hp.inter_channels:
             raise ValueError("z must be [inter_channels, T_y]")
@@ -447,6 +491,14 @@ class VitsModel:
         st = ctypes.c_void_p()
         total = ctypes.c_int64()
         rate = self._rate(sample_rate)
+        if denoiser_strength is not None:
+            L._need_denoise()
+            if rate:
+                raise VitsError(4, f"a stream with a denoiser (strength {denoiser_strength}) at sample_rate {rate} Hz is not supported: "
+                                   f"only the voice's own {self.hp.sampling_rate} Hz")
+            L.check(L._fn("stream_open_latent_denoise")(self._h, _p(z, c_f32p), z.shape[1], int(chunk_frames), 1 if clamp else 0,
+                                                        float(denoiser_strength), int(denoiser_filter_length), ctypes.byref(st), ctypes.byref(total)))
+            return self._drain(st, chunk_frames, 0)
         if rate:
             L.check(L._fn("stream_open_latent_rate")(self._h, _p(z, c_f32p), z.shape[1], int(chunk_frames), 1 if clamp else 0, rate,
                                                      ctypes.byref(st), ctypes.byref(total)))

@@ -10,11 +10,13 @@ from .weights_stts import SttsHParams
 
 
 STTS_FLAG_ITEM_SEEDS = 1  # include/stts_mi355.h
+STTS_FLAG_DENOISE = 2     # include/vits_denoise.h
 
 
 class SttsOpts(ctypes.Structure):
     _fields_ = [("noise", c_f32p), ("noise_stride", ctypes.c_int64), ("seed", ctypes.c_uint64),
-                ("n_timesteps", ctypes.c_int32), ("flags", ctypes.c_int32), ("item_seeds", ctypes.POINTER(ctypes.c_uint64))]
+                ("n_timesteps", ctypes.c_int32), ("flags", ctypes.c_int32), ("item_seeds", ctypes.POINTER(ctypes.c_uint64)),
+                ("denoiser_strength", ctypes.c_float), ("denoiser_filter_length", ctypes.c_int32)]
 
 
 class SttsModel:
@@ -69,10 +71,22 @@ class SttsModel:
         except Exception:
             pass
 
+    def _denoise(self, opts, denoiser_strength, denoiser_filter_length):
+        """STTS_FLAG_DENOISE and its two fields (include/vits_denoise.h); None = off.  Only the device library has the denoiser: the CPU
+        oracle would ignore the flag, which is refused here instead"""
+        if denoiser_strength is None:
+            return
+        if not getattr(self.vlib, "has_denoise", False):
+            raise VitsError(4, "this backend has no denoiser (include/vits_denoise.h)")
+        opts.flags |= STTS_FLAG_DENOISE
+        opts.denoiser_strength = float(denoiser_strength)
+        opts.denoiser_filter_length = int(denoiser_filter_length or 0)
+
     # ---- hot path ----------------------------------------------------------------------------
     def synthesize(self, ids, scales, sid, bert=None, phone_duration_extra=None, noise=None, seed=0, n_timesteps=0,
-                   want_audio=True, want_mel=True):
-        """One utterance.  ids int64 [5,T]; returns (audio float32 [S] or None, mel float32 [n_feats,T_y] or None)."""
+                   want_audio=True, want_mel=True, denoiser_strength=None, denoiser_filter_length=0):
+        """One utterance.  ids int64 [5,T]; returns (audio float32 [S] or None, mel float32 [n_feats,T_y] or None).
+        denoiser_strength (None = off) / denoiser_filter_length (0 = 1024): the vocoder-bias denoiser behind the clamp."""
         ids = _i64(ids)
         if ids.ndim != 2 or ids.shape[0] != 5:
             raise ValueError("ids must be [5, T]")
@@ -88,6 +102,7 @@ class SttsModel:
             opts.noise_stride = a.shape[1]
         opts.seed = seed
         opts.n_timesteps = n_timesteps
+        self._denoise(opts, denoiser_strength, denoiser_filter_length)
         b = None if bert is None else _f32(bert)
         if b is not None and b.shape != (self.hp.bert_dim, T):
             raise ValueError("bert must be [768, T]")
@@ -108,7 +123,8 @@ class SttsModel:
             melo = np.ctypeslib.as_array(mel, shape=(self.hp.n_feats, nf.value)).copy(); free(mel)
         return audio, melo
 
-    def stream(self, ids, scales, sid, bert=None, phone_duration_extra=None, seed=0, n_timesteps=0, chunk_frames=64):
+    def stream(self, ids, scales, sid, bert=None, phone_duration_extra=None, seed=0, n_timesteps=0, chunk_frames=64,
+               denoiser_strength=None, denoiser_filter_length=0):
         """Streaming form of synthesize() (stts_stream_open): a generator of float32 chunks of chunk_frames*hop samples whose
         concatenation equals synthesize()'s audio for the same arguments."""
         if self._vocoder is None:
@@ -119,6 +135,7 @@ class SttsModel:
         T = ids.shape[1]
         scales = _f32(scales)
         opts = SttsOpts(); opts.seed = seed; opts.n_timesteps = n_timesteps
+        self._denoise(opts, denoiser_strength, denoiser_filter_length)
         b = None if bert is None else _f32(bert)
         if b is not None and b.shape != (self.hp.bert_dim, T):
             raise ValueError("bert must be [768, T]")
@@ -132,7 +149,8 @@ class SttsModel:
                                            ctypes.byref(st), ctypes.byref(total)))
         return self._vocoder._drain(st, chunk_frames)
 
-    def synthesize_batch(self, ids, lengths, scales, sid, bert=None, phone_duration_extra=None, seed=0, n_timesteps=0, item_seeds=None):
+    def synthesize_batch(self, ids, lengths, scales, sid, bert=None, phone_duration_extra=None, seed=0, n_timesteps=0, item_seeds=None,
+                         denoiser_strength=None, denoiser_filter_length=0):
         """B independent utterances in one pass (stts_synthesize_batch): ids [B,5,T], lengths [B], sid [B];
         returns (audio float32 [B,S] zero-padded, out_lengths int64 [B] in samples).  Item b equals
         synthesize(ids[b][:, :lengths[b]], ..., seed=item_seeds[b]) (seed + b without item seeds)."""
@@ -141,6 +159,7 @@ class SttsModel:
         b = None if bert is None else _f32(bert)
         p = None if phone_duration_extra is None else _f32(phone_duration_extra)
         opts = SttsOpts(); opts.seed = seed; opts.n_timesteps = n_timesteps
+        self._denoise(opts, denoiser_strength, denoiser_filter_length)
         if item_seeds is not None:
             sd = np.ascontiguousarray(item_seeds, dtype=np.uint64)
             if sd.shape != (B,):

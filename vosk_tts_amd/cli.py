@@ -12,7 +12,8 @@ import logging
 import sys
 
 # (flags, argparse keyword arguments) — one row per option of the reference CLI, plus --sample-rate (tts_service.proto's
-# output_audio_spec.raw_audio.sample_rate_hertz; the reference script has no such flag)
+# output_audio_spec.raw_audio.sample_rate_hertz; the reference script has no such flag) and --denoiser-strength (the
+# --denoiser_strength of the StableTTS script, training/stabletts/matcha/cli.py:253-256)
 _OPTIONS = (
     (("-m", "--model"), dict(type=str, metavar="DIR", help="directory holding model.vitsw, dictionary and config.json")),
     (("-n", "--model-name"), dict(type=str, metavar="NAME", help="pick a locally installed model by its directory name")),
@@ -24,6 +25,9 @@ _OPTIONS = (
     (("--list-models",), dict(action="store_true", help="print the models found in the local search path and exit")),
     (("--list-languages",), dict(action="store_true", help="print the language codes of the local models and exit")),
     (("--sample-rate",), dict(type=int, default=None, metavar="HZ", help="output sample rate (default: the voice's own, 22050)")),
+    (("--denoiser-strength",), dict(type=float, default=None, metavar="S",
+                                    help="vocoder-bias denoiser of a multistream voice (the StableTTS script's default is 0.00025; default here: "
+                                         "the voice's inference.denoiser_strength, else off)")),
     (("--log-level",), dict(default="INFO", metavar="LEVEL", help="python logging level (INFO shows the RTF line)")),
 )
 
@@ -49,7 +53,8 @@ def run(opts):
     from .synth import Synth
 
     voice = model_mod.Model(opts.model, opts.model_name, opts.lang)
-    Synth(voice).synth(opts.input, opts.output, opts.speaker, speech_rate=opts.speech_rate, sample_rate=opts.sample_rate)
+    Synth(voice).synth(opts.input, opts.output, opts.speaker, speech_rate=opts.speech_rate, sample_rate=opts.sample_rate,
+                       denoiser_strength=opts.denoiser_strength)
     return 0
 
 

@@ -122,6 +122,7 @@ static int persist_cfg() {
 #include "engine_launch.hip.h"
 #include "engine_stages.hip.h"
 #include "resample.hip.h"
+#include "denoise.hip.h"
 
 // ------------------------------------------------------------------------------------ C ABI
 extern "C" {

@@ -201,6 +201,8 @@ struct vits_model {
   int n_cu = 0;       // compute units of the device = workgroups of a persistent kernel (persist.hip.h)
   DecGeom geom;       // the decoder's shape (load_decoder)
   int rag_halo = 32;  // geom.rag_halo: frames decoded beyond an item's end in streaming windows, >= the decoder's receptive field
+  std::mutex dn_mu;   // the vocoder-bias denoiser's bias by filter_length (denoise.hip.h): host copy and device copy (in allocs)
+  std::map<int, std::pair<std::vector<float>, float*>> dn_bias;
 
   std::mutex pool_mu;
   std::vector<vits_session*> pool;

@@ -29,6 +29,13 @@ struct vits_stream {
   const ResampleTab* rs = nullptr;
   float* d_rs = nullptr;
   long long rs_cap = 0;             // outputs one chunk can have: ceil(chunk * hop * L / M) + 1
+  // the vocoder-bias denoiser (include/vits_denoise.h): every emitted chunk is denoised from its window's audio slot into d_dn on the
+  // copy stream (two launches), then copied out.  The windows carry ceil(filter_length / hop) more halo frames.
+  const DenoiseTab* dn = nullptr;
+  const float* dn_bias = nullptr;
+  float dn_strength = 0.f;
+  float *d_dn = nullptr, *d_dn_scr = nullptr;
+  size_t dn_scr_elems = 0;
   hipEvent_t ev = nullptr;
   int find(int lo) const { for (int i = 0; i < 2; ++i) if (lo >= win[i].lo && lo < win[i].hi) return i; return -1; }
 };
@@ -82,6 +89,14 @@ static int stream_start(vits_stream* st, const float* z, int Ty, int chunk_frame
     pin_elems = (size_t)st->rs_cap;
     st->d_rs = st->hs->dev_alloc<float>((size_t)st->rs_cap);
     if (!st->d_rs) { vits_stream_close(st); return fail(VITS_ERR_NOMEM, "stream buffers"); }
+  }
+  if (st->dn && (long long)Ty * hp.hop_length < st->dn->n / 2 + 1) st->dn = nullptr;  // too short for the reflection: streamed undenoised
+  if (st->dn) {
+    st->halo += cdiv(st->dn->n, hp.hop_length);
+    st->dn_scr_elems = denoise_scratch_elems(st->dn->n, (long long)chunk_frames * hp.hop_length);
+    st->d_dn = st->hs->dev_alloc<float>(pin_elems);
+    st->d_dn_scr = st->hs->dev_alloc<float>(st->dn_scr_elems);
+    if (!st->d_dn || !st->d_dn_scr) { vits_stream_close(st); return fail(VITS_ERR_NOMEM, "stream buffers"); }
   }
   st->chunk = chunk_frames;
   st->W = chunk_frames + 2 * st->halo;
@@ -156,15 +171,16 @@ int vits_stream_open_latent(vits_model* m, const float* z, int32_t Ty, int32_t c
   return vits_stream_open_latent_rate(m, z, Ty, chunk_frames, flags, 0, out, total_samples);
 }
 
-int vits_stream_open_latent_rate(vits_model* m, const float* z, int32_t Ty, int32_t chunk_frames, uint32_t flags, int32_t sample_rate,
-                                 vits_stream** out, int64_t* total_samples) {
-  if (!m || !z || !out || Ty <= 0 || chunk_frames <= 0) return fail(VITS_ERR_ARG, "bad argument");
-  if (Ty > (1 << 18)) return fail(VITS_ERR_ARG, "T_y unreasonably large");
-  const ResampleTab* T = nullptr;
-  TRY(stream_rate(m, sample_rate, &T));
+// the latent opens' common body: a stream over the device copy of z, with the resampler's table (null: native rate) or the denoiser's
+// tables and bias (dn null: none) behind every chunk
+static int stream_open_latent(vits_model* m, const float* z, int32_t Ty, int32_t chunk_frames, uint32_t flags, const ResampleTab* rs,
+                              const DenoiseTab* dn, const float* dn_bias, float dn_strength, vits_stream** out, int64_t* total_samples) {
   vits_stream* st = new vits_stream();
   st->m = m;
-  st->rs = T;
+  st->rs = rs;
+  st->dn = dn;
+  st->dn_bias = dn_bias;
+  st->dn_strength = dn_strength;
   st->hs = new HostStage(m);
   st->clamp = (flags & 1u) != 0;
   int rc = begin_stage(*st->hs, 1, 1, Ty, 0);
@@ -172,6 +188,25 @@ int vits_stream_open_latent_rate(vits_model* m, const float* z, int32_t Ty, int3
   const float* d_z = st->hs->to_dev(z, (size_t)m->hp.inter_channels * Ty);
   if (!d_z) { vits_stream_close(st); return fail(VITS_ERR_NOMEM, "device alloc failed"); }
   return stream_start(st, d_z, Ty, chunk_frames, out, total_samples);
+}
+
+int vits_stream_open_latent_rate(vits_model* m, const float* z, int32_t Ty, int32_t chunk_frames, uint32_t flags, int32_t sample_rate,
+                                 vits_stream** out, int64_t* total_samples) {
+  if (!m || !z || !out || Ty <= 0 || chunk_frames <= 0) return fail(VITS_ERR_ARG, "bad argument");
+  if (Ty > (1 << 18)) return fail(VITS_ERR_ARG, "T_y unreasonably large");
+  const ResampleTab* T = nullptr;
+  TRY(stream_rate(m, sample_rate, &T));
+  return stream_open_latent(m, z, Ty, chunk_frames, flags, T, nullptr, nullptr, 0.f, out, total_samples);
+}
+
+int vits_stream_open_latent_denoise(vits_model* m, const float* z, int32_t Ty, int32_t chunk_frames, uint32_t flags, float strength,
+                                    int32_t filter_length, vits_stream** out, int64_t* total_samples) {
+  if (!m || !z || !out || Ty <= 0 || chunk_frames <= 0) return fail(VITS_ERR_ARG, "bad argument");
+  if (Ty > (1 << 18)) return fail(VITS_ERR_ARG, "T_y unreasonably large");
+  const DenoiseTab* T = nullptr;
+  const float* d_bias = nullptr;
+  TRY(denoise_prepare(m, strength, filter_length, &T, &d_bias));
+  return stream_open_latent(m, z, Ty, chunk_frames, flags, nullptr, T, d_bias, strength, out, total_samples);
 }
 
 int vits_stream_next(vits_stream* st, float* audio, int64_t capacity, int64_t* n_samples) {
@@ -195,6 +230,11 @@ int vits_stream_next(vits_stream* st, float* audio, int64_t capacity, int64_t* n
     resample_launch<float>(s->copy_stream, *st->rs, w.aud, 0, (long long)w.start * hop, (long long)w.width * hop, nullptr, (long long)st->Ty * hop, 1, st->d_rs, 0,
                            n_first, n, 1.f, nullptr);
     HIP_TRY(hipMemcpyAsync(st->h_pin, st->d_rs, sizeof(float) * n, hipMemcpyDeviceToHost, s->copy_stream));
+  } else if (st->dn) {
+    // outputs [lo * hop, hi * hop) of the utterance's transform: its frames read the slot, which holds samples [w.start * hop, ...)
+    denoise_launch(s->copy_stream, *st->dn, w.aud, 0, (long long)w.start * hop, (long long)w.width * hop, nullptr, (long long)st->Ty * hop, 1, st->dn_bias,
+                   st->dn_strength, st->d_dn_scr, (long long)st->dn_scr_elems, st->d_dn, 0, (long long)lo * hop, n);
+    HIP_TRY(hipMemcpyAsync(st->h_pin, st->d_dn, sizeof(float) * n, hipMemcpyDeviceToHost, s->copy_stream));
   } else {
     HIP_TRY(hipMemcpyAsync(st->h_pin, w.aud + (size_t)(lo - w.start) * hop, sizeof(float) * n, hipMemcpyDeviceToHost, s->copy_stream));
   }

@@ -5,6 +5,7 @@
 // Reference citations are relative to /root/reference/training/stabletts/matcha/.
 #include "../../include/stts_mi355.h"
 #include "../../include/stts_bert_batch.h"
+#include "../../include/vits_denoise.h"
 
 struct DitW {  // DiTConVBlock (models/components/diffusion_transformer.py:82-118)
   ConvW qkv, o, c1, c2;
@@ -602,6 +603,8 @@ struct SttsBack {
   float* out_h = nullptr;      // pinned: audio [TB * hop] | mel [NF * TB]
   size_t audio_elems = 0;
   hipGraphExec_t g[2] = {nullptr, nullptr};  // [with vocoder]
+  float* d_dn = nullptr;       // denoised audio [audio_elems] | frames scratch: allocated by the first request that sets STTS_FLAG_DENOISE
+  size_t dn_scr_elems = 0;
   uint64_t last_use = 0;
 };
 struct SttsFront {
@@ -620,6 +623,7 @@ static void stts_back_free(SttsBack* b) {
   if (!b) return;
   for (int i = 0; i < 2; ++i) if (b->g[i]) hipGraphExecDestroy(b->g[i]);
   if (b->buf) hipFree(b->buf);
+  if (b->d_dn) hipFree(b->d_dn);
   if (b->out_h) hipHostFree(b->out_h);
   if (b->sv) session_free(b->sv);
   if (b->s) { b->s->stream = nullptr; session_free(b->s); }
@@ -825,12 +829,30 @@ static int stts_phase2(stts_model* m, SttsFront* F, SttsBack* Bk, bool audio) {
   return VITS_OK;
 }
 
+// STTS_FLAG_DENOISE of a call (include/vits_denoise.h): the two appended fields are read only under the flag
+struct SttsDenoise {
+  const DenoiseTab* T = nullptr;  // null: off
+  const float* bias = nullptr;
+  float strength = 0.f;
+};
+static int stts_denoise_arg(stts_model* m, const stts_synth_opts* opts, SttsDenoise* d) {
+  *d = SttsDenoise();
+  if (!opts || !(opts->flags & STTS_FLAG_DENOISE)) return VITS_OK;
+  if (!m->vocoder) return fail(VITS_ERR_ARG, "no vocoder attached");
+  d->strength = opts->denoiser_strength;
+  return denoise_prepare(m->vocoder, opts->denoiser_strength, opts->denoiser_filter_length, &d->T, &d->bias);
+}
+
 static int stts_synth_fast(stts_model* m, const int64_t* ids, int32_t Tx, const float* scales, int64_t sid, const float* bert, const float* pde,
                            const stts_synth_opts* opts, float** out_audio, int64_t* out_samples, float** out_mel, int64_t* out_frames) {
   const stts_hparams& hp = m->hp;
   const int NF = hp.n_feats;
   const int n = (opts && opts->n_timesteps > 0) ? opts->n_timesteps : hp.n_timesteps;
   HIP_TRY(hipSetDevice(m->base.device));
+  // the denoiser's arguments first: a refusal costs nothing, and the one-time tables and bias (allocations, a decode, a device-wide
+  // synchronise) are made before this request has anything queued
+  SttsDenoise dn;
+  if (out_audio) TRY(stts_denoise_arg(m, opts, &dn));
   const int TxB = (Tx + 7) / 8 * 8;
   SttsFront* F = nullptr;
   {
@@ -902,6 +924,21 @@ static int stts_synth_fast(stts_model* m, const int64_t* ids, int32_t Tx, const 
   const bool audio = out_audio != nullptr;
   TRY(stts_phase2(m, F, Bk, audio));
   const int64_t S = audio ? (int64_t)ylen * m->vocoder->hp.hop_length : 0;
+  if (dn.T && S >= dn.T->n / 2 + 1) {
+    // behind the captured graph, on its stream: strength and filter length are per call, and the graph's own copy of the plain audio into
+    // out_h is overwritten in stream order (an utterance too short for the reflection keeps it)
+    if (!Bk->d_dn) {
+      Bk->dn_scr_elems = denoise_scratch_elems(VITS_DENOISE_MAX_FILTER, (long long)Bk->audio_elems);  // (the largest over the filter lengths)
+      if (hipMalloc((void**)&Bk->d_dn, sizeof(float) * (Bk->audio_elems + Bk->dn_scr_elems)) != hipSuccess) {
+        Bk->d_dn = nullptr;
+        hipStreamSynchronize(st);
+        return fail(VITS_ERR_NOMEM, "denoise buffers of frame bucket %d", TB);
+      }
+    }
+    denoise_launch(st, *dn.T, Bk->d_audio, 0, 0, (long long)Bk->audio_elems, nullptr, S, 1, dn.bias, dn.strength, Bk->d_dn + Bk->audio_elems,
+                   (long long)Bk->dn_scr_elems, Bk->d_dn, 0, 0, S);
+    hipMemcpyAsync(Bk->out_h, Bk->d_dn, sizeof(float) * (size_t)S, hipMemcpyDeviceToHost, st);
+  }
   float* h_audio = audio ? static_cast<float*>(malloc(sizeof(float) * (size_t)(S ? S : 1))) : nullptr;
   float* h_mel = out_mel ? static_cast<float*>(malloc(sizeof(float) * (size_t)NF * (ylen ? ylen : 1))) : nullptr;
   if ((audio && !h_audio) || (out_mel && !h_mel)) { hipStreamSynchronize(st); free(h_audio); free(h_mel); return fail(VITS_ERR_NOMEM, "host alloc failed"); }
@@ -932,6 +969,8 @@ int stts_synthesize(stts_model* m, const int64_t* ids, int32_t Tx, const float* 
     if (g_fast_path && !env_off && !(opts && opts->noise))
       return stts_synth_fast(m, ids, Tx, scales, sid, bert, pde, opts, out_audio, out_samples, out_mel, out_frames);
   }
+  SttsDenoise dn;
+  if (out_audio) TRY(stts_denoise_arg(m, opts, &dn));
   const stts_hparams& hp = m->hp;
   const int NF = hp.n_feats, CC = hp.enc_hidden, G = hp.spk_emb_dim, H = hp.dec_hidden;
   const float temperature = scales[0], length_scale = scales[1];
@@ -1014,8 +1053,17 @@ int stts_synthesize(stts_model* m, const int64_t* ids, int32_t Tx, const float* 
       run_decoder(sv, d_mel, false, 1, (int)ylen, d_audio, S);
       sv->stream = own;
       hipLaunchKernelGGL(clamp_kernel, dim3(cdiv((int)S, 256)), dim3(256), 0, s->stream, d_audio, (long long)S);
-      hipMemcpyAsync(h_audio, d_audio, sizeof(float) * (size_t)S, hipMemcpyDeviceToHost, s->stream);
-      rc = check_err(s);
+      const float* d_src = d_audio;
+      if (dn.T && S >= dn.T->n / 2 + 1) {  // (shorter: returned undenoised, include/vits_denoise.h)
+        const size_t sc = denoise_scratch_elems(dn.T->n, S);
+        float* d_dn = call.dev<float>((size_t)S);
+        float* d_scr = call.dev<float>(sc);
+        if (!d_dn || !d_scr) { hipStreamSynchronize(s->stream); rc = fail(VITS_ERR_NOMEM, "alloc failed"); }
+        else denoise_launch(s->stream, *dn.T, d_audio, 0, 0, S, nullptr, S, 1, dn.bias, dn.strength, d_scr, (long long)sc, d_dn, 0, 0, S);
+        d_src = d_dn;
+      }
+      if (rc == VITS_OK) hipMemcpyAsync(h_audio, d_src, sizeof(float) * (size_t)S, hipMemcpyDeviceToHost, s->stream);
+      if (rc == VITS_OK) rc = check_err(s);
     }
     if (sv) pool_release(v, sv);
   } else {
@@ -1036,8 +1084,11 @@ int stts_stream_open(stts_model* m, const int64_t* ids, int32_t Tx, const float*
   int64_t frames = 0;
   TRY(stts_synthesize(m, ids, Tx, scales, sid, bert, pde, opts, nullptr, nullptr, &mel, &frames));
   // the mel crosses the host once (80 x T_y floats): the acoustic context that produced it is cached and reused by other calls
-  int rc = frames > 0 ? vits_stream_open_latent(m->vocoder, mel, (int32_t)frames, chunk_frames, 1u, out, total_samples)
-                      : fail(VITS_ERR_ARG, "empty utterance");
+  int rc = VITS_OK;
+  if (frames <= 0) rc = fail(VITS_ERR_ARG, "empty utterance");
+  else if (opts && (opts->flags & STTS_FLAG_DENOISE))
+    rc = vits_stream_open_latent_denoise(m->vocoder, mel, (int32_t)frames, chunk_frames, 1u, opts->denoiser_strength, opts->denoiser_filter_length, out, total_samples);
+  else rc = vits_stream_open_latent(m->vocoder, mel, (int32_t)frames, chunk_frames, 1u, out, total_samples);
   free(mel);
   return rc;
 }
@@ -1050,6 +1101,8 @@ int stts_synthesize_batch(stts_model* m, const int64_t* ids, const int64_t* leng
   if (opts && opts->noise) return fail(VITS_ERR_ARG, "injected noise is a single-utterance option");
   for (int b = 0; b < B; ++b) if (lengths[b] <= 0 || lengths[b] > Tx) return fail(VITS_ERR_ARG, "length out of range");
   TRY(stts_check_sid(m, sid, B));
+  SttsDenoise dn;
+  TRY(stts_denoise_arg(m, opts, &dn));
   const stts_hparams& hp = m->hp;
   const int NF = hp.n_feats, CC = hp.enc_hidden, G = hp.spk_emb_dim, H = hp.dec_hidden;
   const float temperature = scales[0], length_scale = scales[1];
@@ -1138,8 +1191,17 @@ int stts_synthesize_batch(stts_model* m, const int64_t* ids, const int64_t* leng
     sv->ragged = false;
     sv->stream = own;
     hipLaunchKernelGGL(clamp_kernel, dim3(cdiv((int)(B * S), 256)), dim3(256), 0, s->stream, d_audio, (long long)B * S);
-    hipMemcpyAsync(h_audio, d_audio, sizeof(float) * (size_t)B * S, hipMemcpyDeviceToHost, s->stream);
-    rc = check_err(s);
+    const float* d_src = d_audio;
+    if (dn.T) {  // every item from its own length (frames * hop_length), as if alone; an item too short for the reflection is copied
+      const size_t sc = denoise_scratch_elems(dn.T->n, S);
+      float* d_dn = call.dev<float>((size_t)B * S);
+      float* d_scr = call.dev<float>((size_t)B * sc);
+      if (!d_dn || !d_scr) { hipStreamSynchronize(s->stream); rc = fail(VITS_ERR_NOMEM, "alloc failed"); }  // (the decoder is still queued on buffers of this call)
+      else denoise_launch(s->stream, *dn.T, d_audio, S, 0, S, d_len, v->hp.hop_length, B, dn.bias, dn.strength, d_scr, (long long)sc, d_dn, S, 0, S);
+      d_src = d_dn;
+    }
+    if (rc == VITS_OK) hipMemcpyAsync(h_audio, d_src, sizeof(float) * (size_t)B * S, hipMemcpyDeviceToHost, s->stream);
+    if (rc == VITS_OK) rc = check_err(s);
   }
   if (sv) pool_release(v, sv);
   if (rc != VITS_OK) { free(h_audio); return rc; }

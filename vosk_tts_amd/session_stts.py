@@ -13,7 +13,7 @@ from .capi import VitsLib
 from .capi_stts import SttsModel
 
 _INPUTS = ("input", "input_lengths", "scales", "sid", "bert", "phone_duration_extra")
-_EXT = ("vits.noise", "vits.seed", "vits.n_timesteps", "vits.sample_rate")
+_EXT = ("vits.noise", "vits.seed", "vits.n_timesteps", "vits.sample_rate", "vits.denoiser_strength", "vits.denoiser_filter_length")
 
 
 class SttsSession:
@@ -57,6 +57,24 @@ class SttsSession:
                 seed = next(self._seed)
         return feed, ids[0], np.asarray(feed["scales"], np.float32).reshape(-1), sid, bert, pde, int(seed)
 
+    @staticmethod
+    def _denoiser(feed):
+        """the extension feeds "vits.denoiser_strength" (absent / None = off) and "vits.denoiser_filter_length" (absent / 0 = 1024) ->
+        keyword arguments of the SttsModel calls; values the library would refuse are refused here, by name, before any work"""
+        strength = feed.get("vits.denoiser_strength")
+        n = feed.get("vits.denoiser_filter_length")
+        if strength is None:
+            if n is not None:
+                raise ValueError("vits.denoiser_filter_length needs vits.denoiser_strength")
+            return {}
+        strength = float(np.asarray(strength).reshape(-1)[0])
+        if not strength >= 0:
+            raise ValueError(f"vits.denoiser_strength {strength}: must be >= 0")
+        n = int(np.asarray(n).reshape(-1)[0]) if n is not None else 0
+        if n and (n < 64 or n > 1024 or n & (n - 1)):
+            raise ValueError(f"vits.denoiser_filter_length {n}: must be a power of two in [64, 1024] (0 = 1024)")
+        return {"denoiser_strength": strength, "denoiser_filter_length": n}
+
     def _rate(self, sample_rate):
         """output sample rate of a request -> 0 for None / 0 / the vocoder's own rate"""
         rate = int(sample_rate or 0)
@@ -76,10 +94,12 @@ class SttsSession:
         return out, np.array([self._lib.out_samples(n, native, rate) for n in lengths], np.int64)
 
     def run(self, output_names, input_feed, run_options=None):
-        """Extension feed "vits.sample_rate": output rate in Hz (the finished waveform is resampled, include/vits_resample.h)."""
+        """Extension feeds: "vits.sample_rate", output rate in Hz (the finished waveform is resampled, include/vits_resample.h);
+        "vits.denoiser_strength" / "vits.denoiser_filter_length", the vocoder-bias denoiser behind the clamp (include/vits_denoise.h),
+        applied at the vocoder's own rate, before any resampling."""
         feed, ids, scales, sid, bert, pde, seed = self._parse(output_names, input_feed)
         audio, _ = self._model.synthesize(ids, scales, sid, bert, pde, noise=feed.get("vits.noise"), seed=seed,
-                                          n_timesteps=int(feed.get("vits.n_timesteps", 0)), want_mel=False)
+                                          n_timesteps=int(feed.get("vits.n_timesteps", 0)), want_mel=False, **self._denoiser(feed))
         if self._rate(feed.get("vits.sample_rate")):
             audio = self.resample(audio[None, :], [audio.shape[0]], feed["vits.sample_rate"])[0][0]
         outs = {"wav": audio[None, :], "wav_lengths": np.array([audio.shape[0]], np.int64)}
@@ -93,12 +113,44 @@ class SttsSession:
         if "vits.noise" in feed:
             raise NotImplementedError("run_stream draws the CFM noise on the device (vits.seed)")
         rate = self._rate(sample_rate if sample_rate is not None else feed.get("vits.sample_rate"))
+        dn = self._denoiser(feed)
+        if rate and dn:
+            from .capi import VitsError
+
+            raise VitsError(4, f"a stream with a denoiser (strength {dn['denoiser_strength']}) at sample_rate {rate} Hz is not supported: "
+                               f"only the voice's own {self._vocoder.hp.sampling_rate} Hz")
         if rate:  # the acoustic model's mel, then the vocoder streamed at the rate asked for (vits_stream_open_latent_rate; clamped like the export)
             _, mel = self._model.synthesize(ids, scales, sid, bert, pde, seed=seed, n_timesteps=int(feed.get("vits.n_timesteps", 0)),
                                             want_audio=False, want_mel=True)
             return self._vocoder.stream_latent(mel, chunk_frames=chunk_frames, clamp=True, sample_rate=rate)
         return self._model.stream(ids, scales, sid, bert, pde, seed=seed, n_timesteps=int(feed.get("vits.n_timesteps", 0)),
-                                  chunk_frames=chunk_frames)
+                                  chunk_frames=chunk_frames, **dn)
+
+    def run_batch(self, input_feed):
+        """The batch door as a feed (stts_synthesize_batch; MultiDeviceSynth calls the model's synthesize_batch with the same
+        keywords): "input" int64 [B, 5, T], "input_lengths" [B], "scales" [3],
+        "sid" [B], "bert" [B, 768, T] or None, "phone_duration_extra" [B, T] or None, "vits.item_seeds" [B] (or "vits.seed"), and the
+        extension feeds of run() -> (audio float32 [B, S] zero beyond each item, lengths int64 [B] in output samples).  Every item is
+        denoised from its own length, then resampled from its own samples."""
+        feed = {k: v for k, v in input_feed.items() if v is not None}
+        for k in feed:
+            if k not in _INPUTS and k not in _EXT and k != "vits.item_seeds":
+                raise ValueError(f"Invalid input name: {k}")
+        if "vits.noise" in feed:
+            raise NotImplementedError("injected noise is a single-utterance option")
+        for k in ("input", "input_lengths", "scales"):
+            if k not in feed:
+                raise ValueError(f"Required input {k} is missing")
+        dn = self._denoiser(feed)
+        rate = self._rate(feed.get("vits.sample_rate"))
+        ids = np.asarray(feed["input"])
+        if ids.ndim != 3 or ids.shape[1] != 5:
+            raise ValueError("input must be int64 [B, 5, T]")
+        sid = np.asarray(feed.get("sid", np.zeros(ids.shape[0])), np.int64).reshape(-1)
+        audio, ol = self._model.synthesize_batch(ids, feed["input_lengths"], np.asarray(feed["scales"], np.float32).reshape(-1), sid,
+                                                 feed.get("bert"), feed.get("phone_duration_extra"), seed=int(feed.get("vits.seed", 0)),
+                                                 n_timesteps=int(feed.get("vits.n_timesteps", 0)), item_seeds=feed.get("vits.item_seeds"), **dn)
+        return self.resample(audio, ol, rate) if rate else (audio, ol)
 
     def close(self):
         self._model.close()

@@ -187,10 +187,25 @@ class Synth:
         hp = getattr(getattr(sess, "_vocoder", None), "hp", None) or getattr(sess, "hp", None)
         return int(getattr(hp, "sampling_rate", 0) or 22050)
 
-    def synth_audio(self, text, speaker_id=0, noise_level=None, speech_rate=None, duration_noise_level=None, scale=None, sample_rate=None):
+    def _denoiser(self, args, denoiser_strength):
+        """The vocoder-bias denoiser of the multistream (StableTTS / Matcha) voices (matcha/cli.py:105-108,253-256): `denoiser_strength`,
+        or the config key inference.denoiser_strength, goes into the feed as "vits.denoiser_strength"; None and no config key = off.
+        A VITS-family voice has no separate vocoder stage to put it behind (its decoder runs inside the fused forward): ValueError."""
+        if denoiser_strength is None:
+            denoiser_strength = self.model.config.get("inference", {}).get("denoiser_strength")
+        if denoiser_strength is None:
+            return
+        if not (self.model.config.get("model_type") or "").startswith("multistream"):
+            raise ValueError(f"denoiser_strength {denoiser_strength}: the denoiser belongs to the multistream (StableTTS / Matcha) voices; "
+                             "this is a VITS-family voice")
+        args["vits.denoiser_strength"] = float(denoiser_strength)
+
+    def synth_audio(self, text, speaker_id=0, noise_level=None, speech_rate=None, duration_noise_level=None, scale=None, sample_rate=None,
+                    denoiser_strength=None):
         """sample_rate: output rate in Hz (extension; default None = the voice's own rate, the reference's behaviour): the feed gets
-        "vits.sample_rate" and the engine resamples on the device."""
+        "vits.sample_rate" and the engine resamples on the device.  denoiser_strength: see _denoiser."""
         args, scale = self._feed(text, speaker_id, noise_level, speech_rate, duration_noise_level, scale)
+        self._denoiser(args, denoiser_strength)
         rate = self.native_rate()
         if sample_rate and int(sample_rate) != rate:
             rate = int(sample_rate)
@@ -216,11 +231,12 @@ class Synth:
         return audio
 
     def synth_stream(self, text, speaker_id=0, noise_level=None, speech_rate=None, duration_noise_level=None, scale=None,
-                     chunk_frames=64, sample_rate=None):
+                     chunk_frames=64, sample_rate=None, denoiser_strength=None):
         """Generator of int16 PCM chunks (chunk_frames*256 samples each, ~0.74 s at the default): what a streaming
         `SynthesizeStream` handler would put into successive AudioChunk messages (tts_service.proto:46-54) instead
         of the single whole-utterance chunk of tts_server.py:54.  Same conversion as synth_audio per chunk."""
         args, scale = self._feed(text, speaker_id, noise_level, speech_rate, duration_noise_level, scale)
+        self._denoiser(args, denoiser_strength)
         if not hasattr(self.model.onnx, "run_stream"):
             raise NotImplementedError("this session type has no run_stream (VitsSession: vits_stream_open, SttsSession: stts_stream_open)")
         if sample_rate and int(sample_rate) != self.native_rate():
@@ -228,8 +244,9 @@ class Synth:
         for chunk in self.model.onnx.run_stream(None, args, chunk_frames=chunk_frames):
             yield self.audio_float_to_int16(chunk * scale)
 
-    def synth(self, text, oname, speaker_id=0, noise_level=None, speech_rate=None, duration_noise_level=None, scale=None, sample_rate=None):
-        audio = self.synth_audio(text, speaker_id, noise_level, speech_rate, duration_noise_level, scale, sample_rate)
+    def synth(self, text, oname, speaker_id=0, noise_level=None, speech_rate=None, duration_noise_level=None, scale=None, sample_rate=None,
+              denoiser_strength=None):
+        audio = self.synth_audio(text, speaker_id, noise_level, speech_rate, duration_noise_level, scale, sample_rate, denoiser_strength)
         with wave.open(oname, "w") as f:
             f.setnchannels(1)
             f.setsampwidth(2)
