@@ -41,6 +41,11 @@ struct CouplingW {
   // rsx[i] (i < L-1) keeps only the residual half of res_skip layer i.
   std::vector<ConvW> rsx;
   ConvW skip_post;
+  // The pre-transformer's q | k | v composed with `pre` (flow_type 0): pre and qkv are 1x1 convs with only the mask between them, so
+  //   qkv(pre(x0) * mask) = (W_qkv W_pre) x0 + (W_qkv b_pre + b_qkv)   on every valid column
+  // -- a [3H x I/2] conv that reads the previous coupling output directly.  The persistent flow program runs it in `pre`'s place on the
+  // chain of dependent steps (persist_plan.hip.h seg_flow); small-tile packing only.
+  ConvW qkv_pre;
   int cond_off = 0;
 };
 // MonoTransformerFlowLayer (models.py:545-627; flow_type 4 / 5): the pre_conv Encoder geometry on the I/2 channels of x0, then
@@ -308,6 +313,19 @@ static ConvW make_conv2(vits_model* m, int M, int Cin, int K, const float* bias,
 template <typename F>
 static ConvW make_conv(vits_model* m, int M, int Cin, int K, const float* bias, F src, bool small16 = true) {
   return make_conv2(m, M, Cin, K, bias, src, small16, src);
+}
+// A conv that only the persistent programs run (composed from the model's own at load): the small-tile packing and the bias
+template <typename F>
+static ConvW make_conv16(vits_model* m, int M, int Cin, int K, const float* bias, F src) {
+  ConvW c;
+  c.M = M; c.Mpad = cdiv(M, 32) * 32; c.Cin = Cin; c.K = K;
+  if (Cin % CONV_CI_T != 0) return c;
+  const int Mp16 = cdiv(M, 16) * 16;
+  std::vector<float> packed((size_t)Mp16 * Cin * K, 0.f);
+  pack_conv_weights16(packed.data(), Mp16, Cin, K, [&](int row, int ci, int kk) -> float { return row < M ? src(row, ci, kk) : 0.f; });
+  c.w16 = upload(m, packed.data(), packed.size());
+  c.bias = bias ? upload(m, bias, M) : nullptr;
+  return c;
 }
 
 // nn.Conv1d weight [Cout, Cin, K] (+ optional bias)
@@ -729,6 +747,35 @@ static int load_model(vits_model* m) {
         std::vector<float> bff(half);
         for (int o = 0; o < half; ++o) bff[o] = (float)bf[o];
         c.skip_post = make_conv(m, half, L * H, 1, bff.data(), [&](int r, int ci, int) { return (float)Wf[(size_t)r * L * H + ci]; });
+      }
+    }
+    if (hp.flow_type == 0 && !m->missing && (I / 2) % CONV_CI_T == 0) {
+      // qkv_pre = qkv o pre, product and bias in double, rounded once (CouplingW)
+      const int half = I / 2;
+      const float* pw = tget(m, 3, H, half, 1, "flow.flows.%d.pre.weight", fi);
+      const float* pb = tget(m, 1, H, -1, -1, "flow.flows.%d.pre.bias", fi);
+      const float *aw[3], *ab[3];
+      const char* qkvn[3] = {"q", "k", "v"};
+      for (int j = 0; j < 3; ++j) {
+        aw[j] = tget(m, 3, H, H, 1, "flow.flows.%d.pre_transformer.attn_layers.0.conv_%s.weight", fi, qkvn[j]);
+        ab[j] = tget(m, 1, H, -1, -1, "flow.flows.%d.pre_transformer.attn_layers.0.conv_%s.bias", fi, qkvn[j]);
+      }
+      if (!m->missing) {
+        std::vector<double> Wc((size_t)3 * H * half, 0.0);
+        std::vector<float> bc(3 * H);
+        for (int r = 0; r < 3 * H; ++r) {
+          const float* wr = aw[r / H] + (size_t)(r % H) * H;
+          double bacc = ab[r / H][r % H];
+          double* dst = &Wc[(size_t)r * half];
+          for (int k = 0; k < H; ++k) {
+            const double wk = wr[k];
+            bacc += wk * pb[k];
+            const float* pr = pw + (size_t)k * half;
+            for (int ci = 0; ci < half; ++ci) dst[ci] += wk * pr[ci];
+          }
+          bc[r] = (float)bacc;
+        }
+        c.qkv_pre = make_conv16(m, 3 * H, half, 1, bc.data(), [&](int r, int ci, int) { return (float)Wc[(size_t)r * half + ci]; });
       }
     }
     if (mono && !m->missing) {

@@ -122,6 +122,8 @@ enum { PS_EPI_STORE = 0, PS_EPI_SPLINE = 1, PS_EPI_GATE = 2 };
 struct PStep {
   int kind;
   int Tp;                  // padded column count of the segment the step belongs to (set by PBuild::push)
+  int join;                // PK_MM after a PK_MM: independent of the previous step -- its records go into that step's slot, on the workers
+                           // the slot leaves idle (persist_resolve; two steps where the items of both do not fit the workers)
   // ---- PK_MM: y[Cout x 16-column tile] (+)= W[Cout x ks*Cin*K] * window(B)
   int Cin;                 // contraction channels of ONE K-slice (multiple of 16, <= PS_MAXC)
   int cin_pitch;           // channel pitch of the operand cells
@@ -268,6 +270,22 @@ struct PBuild {
     st.G = cdiv(st.n_mb, st.mbg);
     while (ntn * st.G * st.ks > m->n_cu && st.mbg < st.n_mb) { ++st.mbg; st.G = cdiv(st.n_mb, st.mbg); }
   }
+  // Two matrix steps that are to share a slot (PStep::join): coarser row-block groups until the items of both fit the workers.  The
+  // step with less work per worker gives way first, so the slot is as long as its longer item.  false: they do not fit (groups as they were)
+  bool fit_pair(PStep& a, PStep& c) const {
+    const PStep a0 = a, c0 = c;
+    auto work = [](const PStep& st) { return st.mbg * (st.Cin / 16) * st.K; };
+    auto coarser = [](PStep& st) {
+      if (st.epi == PS_EPI_SPLINE || st.mbg >= st.n_mb || st.mbg >= 15) return false;
+      ++st.mbg; st.G = cdiv(st.n_mb, st.mbg);
+      return true;
+    };
+    while (ntn * (a.G * a.ks + c.G * c.ks) > m->n_cu) {
+      const bool c_first = work(c) <= work(a);
+      if (!coarser(c_first ? c : a) && !coarser(c_first ? a : c)) { a = a0; c = c0; return false; }
+    }
+    return true;
+  }
   void col_par(PStep& st, int C, const float* p0, const float* p1, const float* p2, const float* vec) {
     st.C = C; st.plen = C;
     st.par[0] = p0 ? p0 : m->zeros; st.par[1] = p1 ? p1 : m->zeros; st.par[2] = p2 ? p2 : m->zeros;
@@ -278,14 +296,17 @@ struct PBuild {
 // One attentions.Encoder layer (attentions.py:48-65) on x cells [Tp][H] -> new x cells.
 //   vec_next: per-item vector added to the OUTPUT (the speaker embedding that the reference adds before the next layer), or null
 //   base: cells added after the last LayerNorm (flow: h + pre_transformer(h)), or null;  xplain: also write the output as plain floats
+//   qkv_st: the q | k | v step where it does not read x (flow: composed with `pre`, CouplingW::qkv_pre);  joined: the step that
+//   produces x then, off the chain in the q | k | v slot (x is not read before conv_o's residual)
 static const ll_t* persist_encoder_layer(PBuild& b, const EncLayerW& L, const EncoderW& E, const ll_t* x, const float* vec_next, const ll_t* base,
-                                         float* xplain) {
+                                         float* xplain, const PStep* qkv_st = nullptr, const PStep* joined = nullptr) {
   vits_model* m = b.m;
   const int H = E.H, F = E.F, nh = E.nh, dk = H / nh, W = E.W, Tp = b.Tp, ntn = b.ntn;
   // q | k | v
-  PStep st = b.mm(L.qkv, x, H);
+  PStep st = qkv_st ? *qkv_st : b.mm(L.qkv, x, H);
   st.yout = b.take_rows(3 * H);
   const ll_t* qkv = b.push(st).yout;
+  if (joined) b.push(*joined);
   // attention blocks -> partial (O, m, l) per (key tile, column, head)
   st = b.blank(PK_ATT);
   st.nh = nh; st.dk = dk; st.W = W; st.qkv = qkv;
@@ -367,6 +388,44 @@ static void persist_resolve(vits_session* s, const std::vector<PStep>& steps, in
       used[nx] = 1;
     }
   };
+  auto mm_items = [&](const PStep& st) { return (st.Tp / 16) * st.G * st.ks; };
+  // records of one matrix step into slot R; its (row-block group, K-slice) q is group q0 + q of the slot's placement
+  auto emit_mm = [&](const PStep& st, PRec* R, int q0) -> bool {
+    const int items = ntn * st.G * st.ks;
+    const int n_u = st.Cin / 16 * st.K;
+    const bool gate = st.epi == PS_EPI_GATE;
+    if (n_u > 127 || st.mbg > 15) return false;  // (field widths of record dword b0)
+    for (int item = 0; item < items; ++item) {
+      const int j = item % ntn, q = item / ntn, g = q % st.G, slice = q / st.G;
+      const int n0 = j * 16, mb0 = g * st.mbg, nblk = std::min(st.mbg, st.n_mb - mb0);
+      PRec& r = R[rank_of[(q0 + q) * ntn + j]];
+      r.kf = PK_MM | (st.relu ? PF_RELU : 0) | (st.in_mask ? PF_INMASK : 0) | (st.out_mask ? PF_OUTMASK : 0) | (gate ? PF_GATE : 0) |
+             (st.epi == PS_EPI_SPLINE ? PF_SPLINE : 0) | ((st.zinit && g == 0 && slice == 0) ? PF_ZINIT : 0) | (st.last ? PF_LAST : 0) |
+             (st.bin_plain ? PF_PLAIN_IN : 0);
+      r.a1 = st.Cin | (st.K << 16);
+      r.a2 = st.bin_plain ? st.c_sign : st.cin_pitch * st.c_sign;
+      r.a3 = n0 - st.pad;
+      const int ch0 = st.c_off + st.c_sign * slice * st.Cin;
+      if (st.bin_plain) r.p[0] = U(st.bin_plain + (size_t)ch0 * st.plain_T);
+      else r.p[0] = U(st.bin + (st.c_sign > 0 ? ch0 : ch0 - (st.Cin - 1)));
+      const int row0 = gate ? mb0 * 8 : mb0 * 16;
+      r.p[1] = st.yout ? U(st.yout + ((size_t)slice * Tp + n0) * st.ypitch + st.y_off + row0) : 0;
+      r.p[2] = st.yplain ? U(st.yplain + (size_t)row0 * st.plain_T + n0) : 0;
+      r.p[3] = st.res ? U(st.res + (size_t)n0 * st.rpitch + row0) : 0;
+      r.p[4] = U(st.z); r.p[5] = U(st.zout);
+      r.p[6] = U(st.w16 + ((size_t)mb0 * st.ks + slice) * n_u * 256);
+      r.p[7] = U(st.bias + (st.bias == m->zeros ? 0 : row0));
+      r.p[8] = U(st.cond + (st.cond == m->zeros ? 0 : row0));
+      r.b[0] = n_u | (nblk << 7);
+      r.b[1] = st.ks * n_u * 256;
+      r.b[2] = st.ypitch;
+      r.b[3] = gate ? 2 * st.gate_H : st.Cout - row0;
+      r.b[4] = st.plain_T; r.b[5] = st.rpitch;
+      r.b[6] = n0 | (st.z_row << 16) | (st.ea_row << 20);
+      r.b[7] = st.gate_H;
+    }
+    return true;
+  };
   for (size_t si = 0; si < steps.size(); ++si) {
     const PStep& st = steps[si];
     Tp = st.Tp; ntn = Tp / 16;
@@ -391,42 +450,14 @@ static void persist_resolve(vits_session* s, const std::vector<PStep>& steps, in
         r.b[4] = st.plain_T;
       }
     } else if (st.kind == PK_MM) {
-      const int items = ntn * st.G * st.ks;
-      if (items > P) { bad = true; return; }
+      // a joined step (PStep::join) shares this slot when the items of both fit the workers; place() places the union
+      const PStep* nx = si + 1 < steps.size() ? &steps[si + 1] : nullptr;
+      if (nx && !(nx->kind == PK_MM && nx->join && nx->Tp == st.Tp && (int)si + 1 != seg_pstep && mm_items(st) + mm_items(*nx) <= P)) nx = nullptr;
+      if (mm_items(st) > P) { bad = true; return; }
       PRec* R = new_step();
-      const int n_u = st.Cin / 16 * st.K;
-      const bool gate = st.epi == PS_EPI_GATE;
-      if (n_u > 127 || st.mbg > 15) { bad = true; return; }  // (field widths of record dword b0)
-      place(st.G * st.ks);
-      for (int item = 0; item < items; ++item) {
-        const int j = item % ntn, q = item / ntn, g = q % st.G, slice = q / st.G;
-        const int n0 = j * 16, mb0 = g * st.mbg, nblk = std::min(st.mbg, st.n_mb - mb0);
-        PRec& r = R[rank_of[q * ntn + j]];
-        r.kf = PK_MM | (st.relu ? PF_RELU : 0) | (st.in_mask ? PF_INMASK : 0) | (st.out_mask ? PF_OUTMASK : 0) | (gate ? PF_GATE : 0) |
-               (st.epi == PS_EPI_SPLINE ? PF_SPLINE : 0) | ((st.zinit && g == 0 && slice == 0) ? PF_ZINIT : 0) | (st.last ? PF_LAST : 0) |
-               (st.bin_plain ? PF_PLAIN_IN : 0);
-        r.a1 = st.Cin | (st.K << 16);
-        r.a2 = st.bin_plain ? st.c_sign : st.cin_pitch * st.c_sign;
-        r.a3 = n0 - st.pad;
-        const int ch0 = st.c_off + st.c_sign * slice * st.Cin;
-        if (st.bin_plain) r.p[0] = U(st.bin_plain + (size_t)ch0 * st.plain_T);
-        else r.p[0] = U(st.bin + (st.c_sign > 0 ? ch0 : ch0 - (st.Cin - 1)));
-        const int row0 = gate ? mb0 * 8 : mb0 * 16;
-        r.p[1] = st.yout ? U(st.yout + ((size_t)slice * Tp + n0) * st.ypitch + st.y_off + row0) : 0;
-        r.p[2] = st.yplain ? U(st.yplain + (size_t)row0 * st.plain_T + n0) : 0;
-        r.p[3] = st.res ? U(st.res + (size_t)n0 * st.rpitch + row0) : 0;
-        r.p[4] = U(st.z); r.p[5] = U(st.zout);
-        r.p[6] = U(st.w16 + ((size_t)mb0 * st.ks + slice) * n_u * 256);
-        r.p[7] = U(st.bias + (st.bias == m->zeros ? 0 : row0));
-        r.p[8] = U(st.cond + (st.cond == m->zeros ? 0 : row0));
-        r.b[0] = n_u | (nblk << 7);
-        r.b[1] = st.ks * n_u * 256;
-        r.b[2] = st.ypitch;
-        r.b[3] = gate ? 2 * st.gate_H : st.Cout - row0;
-        r.b[4] = st.plain_T; r.b[5] = st.rpitch;
-        r.b[6] = n0 | (st.z_row << 16) | (st.ea_row << 20);
-        r.b[7] = st.gate_H;
-      }
+      place(st.G * st.ks + (nx ? nx->G * nx->ks : 0));
+      if (!emit_mm(st, R, 0) || (nx && !emit_mm(*nx, R, st.G * st.ks))) { bad = true; return; }
+      if (nx) ++si;
     } else if (st.kind == PK_ATT) {
       const int items = st.nh * ntn * ntn;
       const int add[8] = {0, 512, 0, 512, 0, 0, 0, 0};
@@ -603,6 +634,8 @@ static void seg_sdp(vits_session* s, PBuild& b, const ll_t* x_cells) {
   if (m->use_g && m->cond_dp_off >= 0) st.cond = s->condv + m->cond_dp_off;
   st.zinit = 1;
   st.yout = b.take_rows(D); st.zout = b.take_rows(2);
+  // (one launch with the text encoder: its last step, enc_proj, reads the same cells and neither needs the other -- one slot)
+  if (x_cells && !steps.empty() && steps.back().kind == PK_MM && steps.back().Tp == b.Tp) { st.join = 1; b.fit_pair(steps.back(), st); }
   const size_t first = steps.size();
   const ll_t* x = b.push(st).yout;
   const ll_t* z = steps[first].zout;
@@ -668,9 +701,20 @@ static void seg_flow(vits_session* s, PBuild& b, const ll_t* zp_cells) {
     if (!u) st.bin_plain = s->zA;
     st.out_mask = 1;
     st.yout = b.take_rows(H);
-    const ll_t* fh = b.push(st).yout;
-    // h = h + pre_transformer(h * mask)  (models.py:377)
-    const ll_t* fx = persist_encoder_layer(b, C.enc.layers[0], C.enc, fh, nullptr, fh, nullptr);
+    // h = h + pre_transformer(h * mask)  (models.py:377).  The first reader of h on the chain is q | k | v: composed with `pre`
+    // (CouplingW::qkv_pre) it reads x0 itself, and `pre` runs beside it -- one dependent step less per coupling layer.  (On columns
+    // >= len the composed bias differs from qkv(0): attention skips those keys and every later step zeroes those columns.)
+    const ll_t* fx;
+    if (C.qkv_pre.w16 && persist_slice(C.qkv_pre.Cin, 1) == C.qkv_pre.Cin) {
+      PStep q = b.mm(C.qkv_pre, u, I, I - 1, -1);
+      if (!u) q.bin_plain = s->zA;
+      st.join = 1;
+      b.fit_pair(q, st);
+      fx = persist_encoder_layer(b, C.enc.layers[0], C.enc, st.yout, nullptr, st.yout, nullptr, &q, &st);
+    } else {
+      const ll_t* fh = b.push(st).yout;
+      fx = persist_encoder_layer(b, C.enc.layers[0], C.enc, fh, nullptr, fh, nullptr);
+    }
     // WN (modules.py:148-176), folded tail: gate outputs of all layers stacked [Tp][L*H]; res_skip layer i < L-1 only updates x
     ll_t* acts = b.take_rows((size_t)L * H);
     for (int i = 0; i < L; ++i) {
