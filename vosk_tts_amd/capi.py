@@ -114,6 +114,7 @@ class VitsLib:
         self.is_device = bool(f("is_device_backend")())
         self.has_resample = False
         self.has_denoise = False
+        self.has_marks = False
         if self.is_device:
             c_i16p = ctypes.POINTER(ctypes.c_int16)
             f("synthesize_pcm16").argtypes = [ctypes.c_void_p, c_i64p, c_i64p, ctypes.c_int32, ctypes.c_int32, c_f32p, c_i64p,
@@ -164,6 +165,15 @@ class VitsLib:
                                             c_f32p]
                 f("stream_open_latent_denoise").argtypes = [ctypes.c_void_p, c_f32p, ctypes.c_int32, ctypes.c_int32, ctypes.c_uint32,
                                                             ctypes.c_float, ctypes.c_int32, ctypes.POINTER(ctypes.c_void_p), c_i64p]
+            # include/vits_marks.h: speech marks, an extension of the product library like the two above
+            self.has_marks = self.has("synthesize_marks")
+            if self.has_marks:
+                f("synthesize_marks").argtypes = [ctypes.c_void_p, c_i64p, c_i64p, ctypes.c_int32, ctypes.c_int32, c_f32p, c_i64p,
+                                                  ctypes.POINTER(SynthOpts), ctypes.c_int32, ctypes.POINTER(c_f32p), c_i64p, c_i64p, c_i64p]
+                f("synthesize_pcm16_marks").argtypes = [ctypes.c_void_p, c_i64p, c_i64p, ctypes.c_int32, ctypes.c_int32, c_f32p, c_i64p,
+                                                        ctypes.POINTER(SynthOpts), ctypes.c_float, ctypes.c_int32,
+                                                        ctypes.POINTER(c_i16p), c_i64p, c_i64p, c_i64p]
+                f("stream_marks").argtypes = [ctypes.c_void_p, c_i64p, ctypes.c_int32, c_i32p]
             if self.has("debug_clock_probe"):
                 f("debug_clock_probe").argtypes = [ctypes.c_int, ctypes.c_int32, ctypes.POINTER(ctypes.c_double), ctypes.c_int32]
 
@@ -186,6 +196,20 @@ class VitsLib:
 
     def create(self, blob, device=0):
         return VitsModel(self, blob, device)
+
+    def _need_marks(self):
+        if not self.has_marks:
+            raise VitsError(4, "this backend has no speech marks (include/vits_marks.h): the CPU oracle returns audio only")
+
+    def stream_marks(self, st):
+        """vits_stream_marks of an open stream handle -> int64 [T_x] (empty for a latent stream)"""
+        self._need_marks()
+        n = ctypes.c_int32()
+        self.check(self._fn("stream_marks")(st, None, 0, ctypes.byref(n)))  # (NULL, capacity 0: the count only)
+        ends = np.zeros(n.value, np.int64)
+        if n.value:
+            self.check(self._fn("stream_marks")(st, _p(ends, c_i64p), n.value, ctypes.byref(n)))
+        return ends
 
     def clock_probe(self, device=0, duration_us=20000, n=64):
         """vits_debug_clock_probe (include/vits_mi355_debug.h): shader clock in GHz seen by `n` one-wave workgroups that sit on the device
@@ -387,8 +411,9 @@ class VitsModel:
         return rate
 
     def synthesize(self, ids, lengths, scales, sid, noise_dp=None, noise_prior=None, forced_durations=None, seed=0,
-                   max_frames=0, solo=False, item_seeds=None, bert=None, sample_rate=None):
-        """One .run(): returns (audio float32 [B,S], out_lengths int64 [B]).  solo=True (VITS_FLAG_SOLO_BATCH): every
+                   max_frames=0, solo=False, item_seeds=None, bert=None, sample_rate=None, marks=False):
+        """One .run(): returns (audio float32 [B,S], out_lengths int64 [B]); with marks=True (vits_synthesize_marks) a third value,
+        token_ends int64 [B,T_x] in output samples (include/vits_marks.h).  solo=True (VITS_FLAG_SOLO_BATCH): every
         item equals its own single-utterance call with seed + b instead of the reference's padded-batch result.
         sample_rate: output rate in Hz (vits_synthesize_rate; S and out_lengths are then in output samples)."""
         ids = _i64(ids)
@@ -403,7 +428,14 @@ class VitsModel:
         ns = ctypes.c_int64()
         olen = np.zeros(B, dtype=np.int64)
         rate = self._rate(sample_rate)
-        if rate:
+        ends = None
+        if marks:
+            self.lib._need_marks()
+            ends = np.zeros((B, Tx), np.int64)
+            self.lib.check(self.lib._fn("synthesize_marks")(self._h, _p(ids, c_i64p), _p(lengths, c_i64p), B, Tx, _p(scales, c_f32p),
+                                                            _p(sid, c_i64p), ctypes.byref(opts), rate, ctypes.byref(out),
+                                                            ctypes.byref(ns), _p(olen, c_i64p), _p(ends, c_i64p)))
+        elif rate:
             self.lib.check(self.lib._fn("synthesize_rate")(self._h, _p(ids, c_i64p), _p(lengths, c_i64p), B, Tx, _p(scales, c_f32p),
                                                            _p(sid, c_i64p), ctypes.byref(opts), rate, ctypes.byref(out),
                                                            ctypes.byref(ns), _p(olen, c_i64p)))
@@ -415,10 +447,10 @@ class VitsModel:
             audio = np.ctypeslib.as_array(out, shape=(B, ns.value)).copy()
         finally:
             self.lib._fn("free_output")(out)
-        return audio, olen
+        return (audio, olen, ends) if marks else (audio, olen)
 
     def synthesize_pcm16(self, ids, lengths, scales, sid, pcm_scale=1.0, noise_dp=None, noise_prior=None, forced_durations=None,
-                         seed=0, max_frames=0, solo=False, item_seeds=None, bert=None, sample_rate=None):
+                         seed=0, max_frames=0, solo=False, item_seeds=None, bert=None, sample_rate=None, marks=False):
         """synthesize() with Synth.synth_audio's `* scale` and audio_float_to_int16 (vosk_tts/synth.py:127-130) done on the
         device: returns (pcm int16 [B,S], out_lengths int64 [B]).  sample_rate: as for synthesize (vits_synthesize_pcm16_rate:
         the resampler does the conversion in its epilogue)."""
@@ -432,7 +464,15 @@ class VitsModel:
         ns = ctypes.c_int64()
         olen = np.zeros(B, dtype=np.int64)
         rate = self._rate(sample_rate)
-        if rate:
+        ends = None
+        if marks:  # (vits_synthesize_pcm16_marks: token_ends int64 [B,T_x] as a third value)
+            self.lib._need_marks()
+            ends = np.zeros((B, Tx), np.int64)
+            self.lib.check(self.lib._fn("synthesize_pcm16_marks")(self._h, _p(ids, c_i64p), _p(lengths, c_i64p), B, Tx,
+                                                                  _p(scales, c_f32p), _p(sid, c_i64p), ctypes.byref(opts),
+                                                                  float(pcm_scale), rate, ctypes.byref(out), ctypes.byref(ns),
+                                                                  _p(olen, c_i64p), _p(ends, c_i64p)))
+        elif rate:
             self.lib.check(self.lib._fn("synthesize_pcm16_rate")(self._h, _p(ids, c_i64p), _p(lengths, c_i64p), B, Tx,
                                                                  _p(scales, c_f32p), _p(sid, c_i64p), ctypes.byref(opts),
                                                                  float(pcm_scale), rate, ctypes.byref(out), ctypes.byref(ns),
@@ -445,14 +485,18 @@ class VitsModel:
             pcm = np.ctypeslib.as_array(out, shape=(B, ns.value)).copy()
         finally:
             self.lib._fn("free_pcm16")(out)
-        return pcm, olen
+        return (pcm, olen, ends) if marks else (pcm, olen)
 
     def stream(self, ids, scales, sid, chunk_frames=64, noise_dp=None, noise_prior=None, forced_durations=None, seed=0, bert=None,
-               sample_rate=None):
+               sample_rate=None, on_marks=None):
         """Streaming synthesis of ONE utterance (vits_stream_*): a generator of float32 chunks of
         chunk_frames*hop_length samples (the last one shorter); their concatenation equals synthesize().
         sample_rate: output rate in Hz (vits_stream_open_rate): the chunk that covers input samples [a, b) holds the outputs
-        ceil(a*L/M) <= n < ceil(b*L/M), so chunk sizes vary by one sample."""
+        ceil(a*L/M) <= n < ceil(b*L/M), so chunk sizes vary by one sample.
+        on_marks: called once with token_ends int64 [T_x] (vits_stream_marks, the stream's own output samples) as soon as the
+        stream is open, before the first chunk."""
+        if on_marks is not None:
+            self.lib._need_marks()
         if not self.lib.has("stream_open"):
             raise VitsError(-1, "this backend has no streaming entry points")
         ids = _i64(ids).reshape(1, -1)
@@ -469,6 +513,13 @@ class VitsModel:
         else:
             L.check(L._fn("stream_open")(self._h, _p(ids, c_i64p), Tx, _p(scales, c_f32p), int(sid), ctypes.byref(opts),
                                          int(chunk_frames), ctypes.byref(st), ctypes.byref(total)))
+        if on_marks is not None:
+            try:
+                ends = L.stream_marks(st)
+            except Exception:
+                L._fn("stream_close")(st)
+                raise
+            on_marks(ends)
         return self._drain(st, chunk_frames, rate)
 
     def denoise_bias(self, filter_length=1024):

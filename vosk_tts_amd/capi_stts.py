@@ -40,6 +40,13 @@ class SttsModel:
         if hasattr(L, self.prefix + "stream_open"):
             f("stream_open").argtypes = [vp, c_i64p, ctypes.c_int32, c_f32p, ctypes.c_int64, c_f32p, c_f32p, ctypes.POINTER(SttsOpts),
                                          ctypes.c_int32, ctypes.POINTER(vp), c_i64p]
+        # include/vits_marks.h: speech marks, declared where the symbols exist (the CPU oracle has none)
+        self.has_marks = hasattr(L, self.prefix + "synthesize_marks")
+        if self.has_marks:
+            f("synthesize_marks").argtypes = [vp, c_i64p, ctypes.c_int32, c_f32p, ctypes.c_int64, c_f32p, c_f32p, ctypes.POINTER(SttsOpts),
+                                              ctypes.c_int32, ctypes.POINTER(c_f32p), c_i64p, ctypes.POINTER(c_f32p), c_i64p, c_i64p]
+            f("synthesize_batch_marks").argtypes = [vp, c_i64p, c_i64p, ctypes.c_int32, ctypes.c_int32, c_f32p, c_i64p, c_f32p, c_f32p,
+                                                    ctypes.POINTER(SttsOpts), ctypes.c_int32, ctypes.POINTER(c_f32p), c_i64p, c_i64p, c_i64p]
         f("stage_encoder").argtypes = [vp, c_i64p, c_i64p, ctypes.c_int32, ctypes.c_int32, c_i64p, c_f32p, c_f32p, c_f32p]
         f("stage_durations").argtypes = [vp, c_f32p, ctypes.c_int32, ctypes.c_int32, ctypes.c_float, c_f32p, c_i32p, c_i64p]
         f("stage_estimator").argtypes = [vp, c_f32p, c_f32p, c_i64p, ctypes.c_int32, ctypes.c_int32, ctypes.c_float, c_f32p, c_f32p]
@@ -82,11 +89,21 @@ class SttsModel:
         opts.denoiser_strength = float(denoiser_strength)
         opts.denoiser_filter_length = int(denoiser_filter_length or 0)
 
+    def _need_marks(self):
+        if not self.has_marks:
+            raise VitsError(4, "this backend has no speech marks (include/vits_marks.h): the CPU oracle returns audio only")
+
     # ---- hot path ----------------------------------------------------------------------------
     def synthesize(self, ids, scales, sid, bert=None, phone_duration_extra=None, noise=None, seed=0, n_timesteps=0,
-                   want_audio=True, want_mel=True, denoiser_strength=None, denoiser_filter_length=0):
+                   want_audio=True, want_mel=True, denoiser_strength=None, denoiser_filter_length=0, marks=False, sample_rate=None):
         """One utterance.  ids int64 [5,T]; returns (audio float32 [S] or None, mel float32 [n_feats,T_y] or None).
-        denoiser_strength (None = off) / denoiser_filter_length (0 = 1024): the vocoder-bias denoiser behind the clamp."""
+        denoiser_strength (None = off) / denoiser_filter_length (0 = 1024): the vocoder-bias denoiser behind the clamp.
+        marks=True (stts_synthesize_marks): a third value, token_ends int64 [T]; audio and marks are then at `sample_rate`
+        (None / 0 = the voice's own)."""
+        if marks:
+            self._need_marks()
+        elif sample_rate:
+            raise ValueError("sample_rate is an argument of the marks call (SttsSession.resample serves the call without marks)")
         ids = _i64(ids)
         if ids.ndim != 2 or ids.shape[0] != 5:
             raise ValueError("ids must be [5, T]")
@@ -111,22 +128,30 @@ class SttsModel:
             raise ValueError("phone_duration_extra must be [T]")
         au, mel = c_f32p(), c_f32p()
         ns, nf = ctypes.c_int64(), ctypes.c_int64()
-        self.check(self._fn("synthesize")(
-            self._h, _p(ids, c_i64p), T, _p(scales, c_f32p), int(sid), None if b is None else _p(b, c_f32p),
-            None if p is None else _p(p, c_f32p), ctypes.byref(opts), ctypes.byref(au) if want_audio else None,
-            ctypes.byref(ns) if want_audio else None, ctypes.byref(mel) if want_mel else None, ctypes.byref(nf) if want_mel else None))
+        ends = np.zeros(T, np.int64) if marks else None
+        tail = (ctypes.byref(au) if want_audio else None, ctypes.byref(ns) if want_audio else None,
+                ctypes.byref(mel) if want_mel else None, ctypes.byref(nf) if want_mel else None)
+        head = (self._h, _p(ids, c_i64p), T, _p(scales, c_f32p), int(sid), None if b is None else _p(b, c_f32p),
+                None if p is None else _p(p, c_f32p), ctypes.byref(opts))
+        if marks:
+            self.check(self._fn("synthesize_marks")(*head, int(sample_rate or 0), *tail, _p(ends, c_i64p)))
+        else:
+            self.check(self._fn("synthesize")(*head, *tail))
         free = self.vlib._fn("free_output")
         audio = melo = None
         if want_audio:
             audio = np.ctypeslib.as_array(au, shape=(ns.value,)).copy(); free(au)
         if want_mel:
             melo = np.ctypeslib.as_array(mel, shape=(self.hp.n_feats, nf.value)).copy(); free(mel)
-        return audio, melo
+        return (audio, melo, ends) if marks else (audio, melo)
 
     def stream(self, ids, scales, sid, bert=None, phone_duration_extra=None, seed=0, n_timesteps=0, chunk_frames=64,
-               denoiser_strength=None, denoiser_filter_length=0):
+               denoiser_strength=None, denoiser_filter_length=0, on_marks=None):
         """Streaming form of synthesize() (stts_stream_open): a generator of float32 chunks of chunk_frames*hop samples whose
-        concatenation equals synthesize()'s audio for the same arguments."""
+        concatenation equals synthesize()'s audio for the same arguments.  on_marks: called once with token_ends int64 [T]
+        (vits_stream_marks) as soon as the stream is open."""
+        if on_marks is not None:
+            self._need_marks()
         if self._vocoder is None:
             raise ValueError("no vocoder attached")
         ids = _i64(ids)
@@ -147,13 +172,25 @@ class SttsModel:
         self.check(self._fn("stream_open")(self._h, _p(ids, c_i64p), T, _p(scales, c_f32p), int(sid), None if b is None else _p(b, c_f32p),
                                            None if p is None else _p(p, c_f32p), ctypes.byref(opts), int(chunk_frames),
                                            ctypes.byref(st), ctypes.byref(total)))
+        if on_marks is not None:
+            try:
+                ends = self.vlib.stream_marks(st)
+            except Exception:
+                self.vlib._fn("stream_close")(st)
+                raise
+            on_marks(ends)
         return self._vocoder._drain(st, chunk_frames)
 
     def synthesize_batch(self, ids, lengths, scales, sid, bert=None, phone_duration_extra=None, seed=0, n_timesteps=0, item_seeds=None,
-                         denoiser_strength=None, denoiser_filter_length=0):
+                         denoiser_strength=None, denoiser_filter_length=0, marks=False, sample_rate=None):
         """B independent utterances in one pass (stts_synthesize_batch): ids [B,5,T], lengths [B], sid [B];
         returns (audio float32 [B,S] zero-padded, out_lengths int64 [B] in samples).  Item b equals
-        synthesize(ids[b][:, :lengths[b]], ..., seed=item_seeds[b]) (seed + b without item seeds)."""
+        synthesize(ids[b][:, :lengths[b]], ..., seed=item_seeds[b]) (seed + b without item seeds).  marks=True
+        (stts_synthesize_batch_marks): a third value, token_ends int64 [B,T]; everything is then at `sample_rate`."""
+        if marks:
+            self._need_marks()
+        elif sample_rate:
+            raise ValueError("sample_rate is an argument of the marks call (SttsSession.resample serves the call without marks)")
         ids = _i64(ids); lengths = _i64(lengths); sid = _i64(sid); scales = _f32(scales)
         B, five, T = ids.shape
         b = None if bert is None else _f32(bert)
@@ -167,12 +204,17 @@ class SttsModel:
             opts.item_seeds = sd.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64))
             opts.flags |= STTS_FLAG_ITEM_SEEDS  # (the trailing field is only read under this flag: include/stts_mi355.h)
         au = c_f32p(); ns = ctypes.c_int64(); ol = np.zeros(B, np.int64)
-        self.check(self._fn("synthesize_batch")(self._h, _p(ids, c_i64p), _p(lengths, c_i64p), B, T, _p(scales, c_f32p), _p(sid, c_i64p),
-                                                None if b is None else _p(b, c_f32p), None if p is None else _p(p, c_f32p),
-                                                ctypes.byref(opts), ctypes.byref(au), ctypes.byref(ns), _p(ol, c_i64p)))
+        head = (self._h, _p(ids, c_i64p), _p(lengths, c_i64p), B, T, _p(scales, c_f32p), _p(sid, c_i64p),
+                None if b is None else _p(b, c_f32p), None if p is None else _p(p, c_f32p), ctypes.byref(opts))
+        ends = np.zeros((B, T), np.int64) if marks else None
+        if marks:
+            self.check(self._fn("synthesize_batch_marks")(*head, int(sample_rate or 0), ctypes.byref(au), ctypes.byref(ns), _p(ol, c_i64p),
+                                                          _p(ends, c_i64p)))
+        else:
+            self.check(self._fn("synthesize_batch")(*head, ctypes.byref(au), ctypes.byref(ns), _p(ol, c_i64p)))
         audio = np.ctypeslib.as_array(au, shape=(B, ns.value)).copy()
         self.vlib._fn("free_output")(au)
-        return audio, ol
+        return (audio, ol, ends) if marks else (audio, ol)
 
     # ---- stages --------------------------------------------------------------------------------
     def encoder(self, ids, lengths, sid, bert=None):

@@ -28,6 +28,8 @@ _OPTIONS = (
     (("--denoiser-strength",), dict(type=float, default=None, metavar="S",
                                     help="vocoder-bias denoiser of a multistream voice (the StableTTS script's default is 0.00025; default here: "
                                          "the voice's inference.denoiser_strength, else off)")),
+    (("--marks",), dict(type=str, default=None, metavar="FILE",
+                        help="also write the speech marks as JSON: rate, phonemes and words with their offsets in samples and seconds")),
     (("--log-level",), dict(default="INFO", metavar="LEVEL", help="python logging level (INFO shows the RTF line)")),
 )
 
@@ -53,8 +55,11 @@ def run(opts):
     from .synth import Synth
 
     voice = model_mod.Model(opts.model, opts.model_name, opts.lang)
-    Synth(voice).synth(opts.input, opts.output, opts.speaker, speech_rate=opts.speech_rate, sample_rate=opts.sample_rate,
-                       denoiser_strength=opts.denoiser_strength)
+    marks = Synth(voice).synth(opts.input, opts.output, opts.speaker, speech_rate=opts.speech_rate, sample_rate=opts.sample_rate,
+                               denoiser_strength=opts.denoiser_strength, marks=bool(opts.marks))
+    if opts.marks:
+        with open(opts.marks, "w", encoding="utf-8") as f:
+            f.write(marks.to_json(indent=1) + "\n")
     return 0
 
 

@@ -123,6 +123,7 @@ static int persist_cfg() {
 #include "engine_stages.hip.h"
 #include "resample.hip.h"
 #include "denoise.hip.h"
+#include "marks.hip.h"
 
 // ------------------------------------------------------------------------------------ C ABI
 extern "C" {
@@ -359,7 +360,8 @@ int vits_stage_decoder(vits_model* m, const float* z, int32_t B, int32_t Ty, con
 // Everything up to and including the flow (models.py:1680-1701) for host inputs: leaves z [B,inter,T_y] in the
 // session workspace (masked by the decoder's first staging), the per-item frame counts in ylen.
 static int acoustic_host(HostStage& hs, const int64_t* ids, const int64_t* lengths, int32_t B, int32_t Tx, const float* scales,
-                         const int64_t* sid, const vits_synth_opts* opts, std::vector<int64_t>& ylen, int64_t& Ty_out, float*& z_out) {
+                         const int64_t* sid, const vits_synth_opts* opts, std::vector<int64_t>& ylen, int64_t& Ty_out, float*& z_out,
+                         std::vector<int>* cum_out = nullptr) {  // cum_out: the cumulative frame counts [B, Tx] on the host (speech marks)
   if (!hs.m->acoustic) return fail(VITS_ERR_UNSUPPORTED, "vocoder-only model: only the decoder stage is available");
   vits_model* m = hs.m;
   const vits_hparams& hp = m->hp;
@@ -402,6 +404,10 @@ static int acoustic_host(HostStage& hs, const int64_t* ids, const int64_t* lengt
   // the one host round trip of the free-running path: T_y sizes everything downstream
   ylen.assign(B, 0);
   HIP_TRY(hipMemcpyAsync(ylen.data(), s->ylen64, sizeof(int64_t) * B, hipMemcpyDeviceToHost, s->stream));
+  if (cum_out) {
+    cum_out->assign((size_t)B * Tx, 0);
+    HIP_TRY(hipMemcpyAsync(cum_out->data(), s->cum, sizeof(int) * (size_t)B * Tx, hipMemcpyDeviceToHost, s->stream));
+  }
   TRY(check_err(s));
   int64_t Ty = 1;
   for (int b = 0; b < B; ++b) if (ylen[b] > Ty) Ty = ylen[b];

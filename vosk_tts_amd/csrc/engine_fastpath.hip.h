@@ -33,6 +33,7 @@ static size_t fast_cache_cap() {
 
 static size_t session_device_bytes(const vits_session* s) {
   size_t n = s->arena_bytes + s->io_bytes + s->out_elems * (sizeof(float) + sizeof(int16_t));
+  if (s->marks_d) n += sizeof(long long) * (size_t)s->B * s->Tx;
   for (auto& kv : s->rates) n += (size_t)s->B * kv.second.n_cap * sizeof(float);
   for (auto& kv : s->backs) n += session_device_bytes(kv.second);
   return n;
@@ -211,8 +212,10 @@ static int capture_end(vits_session* s, hipGraphExec_t* out, CaptureGuard* guard
   return VITS_OK;
 }
 
-static int phase1_launch(vits_session* F, bool forced, bool solo) {
-  const int gi = (persist_mask() ? 4 : 0) + (forced ? 2 : 0) + (solo ? 1 : 0);
+// marks: the variants that also turn cum into token ends (marks.hip.h) and copy them to F->marks_h, in front of the h_ylen copy -- the
+// host reads them after the one synchronisation the call performs anyway.  L / M of the call ride in the per-call block.
+static int phase1_launch(vits_session* F, bool forced, bool solo, bool marks = false) {
+  const int gi = (marks ? 8 : 0) + (persist_mask() ? 4 : 0) + (forced ? 2 : 0) + (solo ? 1 : 0);
   if (!F->g1[gi]) {
     const int B = F->B, TxB = F->Tx;
     HIP_TRY(hipStreamBeginCapture(F->stream, hipStreamCaptureModeThreadLocal));
@@ -235,6 +238,10 @@ static int phase1_launch(vits_session* F, bool forced, bool solo) {
       run_text_encoder(F, d_ids, B, TxB, F->io_bert ? reinterpret_cast<const float*>(F->io_d + F->io_bert) : nullptr);
       if (!forced) run_duration(F, F->x, nullptr, 0.f, 0, B, TxB, true);
       run_durations(F, forced ? d_forced : nullptr, 1.f, B, TxB, 0);
+    }
+    if (marks) {
+      token_ends_launch(F, F->cum, F->len_x, B, TxB, F->m->hp.hop_length, 1, 1, F->dv, F->marks_d);
+      hipMemcpyAsync(F->marks_h, F->marks_d, sizeof(int64_t) * (size_t)B * TxB, hipMemcpyDeviceToHost, F->stream);
     }
     hipMemcpyAsync(F->h_ylen, F->ylen64, sizeof(int64_t) * B, hipMemcpyDeviceToHost, F->stream);
     hipMemcpyAsync(F->h_ylen + B, F->d_err, sizeof(int), hipMemcpyDeviceToHost, F->stream);
@@ -299,7 +306,7 @@ static int device_error_word(int e) {
 
 static int synth_fast(vits_model* m, const int64_t* ids, const int64_t* lengths, int32_t B, int32_t Tx, const float* scales,
                       const int64_t* sid, const vits_synth_opts* opts, bool pcm, float pcm_scale, int rate, void** out, int64_t* out_samples,
-                      int64_t* out_lengths) {
+                      int64_t* out_lengths, int64_t* token_ends) {
   const vits_hparams& hp = m->hp;
   HIP_TRY(hipSetDevice(m->device));
   const ResampleTab* T = nullptr;  // (uploaded on the first call at this rate, before any capture)
@@ -316,8 +323,18 @@ static int synth_fast(vits_model* m, const int64_t* ids, const int64_t* lengths,
     if (rc != VITS_OK) return rc;
   }
   struct Rel { vits_model* m; vits_session* s; ~Rel() { front_release(m, s); } } rel{m, F};
+  if (token_ends && !F->marks_d) {  // the first marks request of this bucket (before any capture)
+    const size_t bytes = sizeof(int64_t) * (size_t)B * TxB;
+    if (hipMalloc((void**)&F->marks_d, bytes) != hipSuccess || hipHostMalloc((void**)&F->marks_h, bytes) != hipSuccess) {
+      if (F->marks_d) hipFree(F->marks_d);
+      F->marks_d = nullptr; F->marks_h = nullptr;
+      (void)hipGetLastError();
+      return fail(VITS_ERR_NOMEM, "speech-mark buffers (%zu bytes)", bytes);
+    }
+  }
   // ---- inputs -> pinned block
   SynthDev* hv = reinterpret_cast<SynthDev*>(F->io_h);
+  hv->rate_L = T ? T->P.L : 1; hv->rate_M = T ? T->P.M : 1;
   hv->scales[0] = scales[0]; hv->scales[1] = scales[1]; hv->scales[2] = scales[2];
   hv->pcm_scale = pcm_scale;
   hv->seed = opts ? opts->seed : 0;
@@ -346,7 +363,7 @@ static int synth_fast(vits_model* m, const int64_t* ids, const int64_t* lengths,
     }
   }
   // ---- phase 1 and the one host round trip
-  TRY(phase1_launch(F, forced, solo));
+  TRY(phase1_launch(F, forced, solo, token_ends != nullptr));
   HIP_TRY(hipStreamSynchronize(F->stream));
   {
     int e = 0;
@@ -403,20 +420,24 @@ static int synth_fast(vits_model* m, const int64_t* ids, const int64_t* lengths,
   *out = h_out;
   *out_samples = S;
   if (out_lengths) for (int b = 0; b < B; ++b) out_lengths[b] = T ? T->P.n_out(F->h_ylen[b] * hp.hop_length) : F->h_ylen[b] * hp.hop_length;
+  if (token_ends) for (int b = 0; b < B; ++b) memcpy(token_ends + (size_t)b * Tx, F->marks_h + (size_t)b * TxB, sizeof(int64_t) * Tx);  // (bucket columns dropped)
   return VITS_OK;
 }
 
 static int synth_eager(vits_model* m, const int64_t* ids, const int64_t* lengths, int32_t B, int32_t Tx, const float* scales,
                        const int64_t* sid, const vits_synth_opts* opts, bool pcm, float pcm_scale, int rate, void** out, int64_t* out_samples,
-                       int64_t* out_lengths) {
+                       int64_t* out_lengths, int64_t* token_ends) {
   const vits_hparams& hp = m->hp;
   const ResampleTab* T = nullptr;
   if (rate) TRY(resample_get(m->device, hp.sampling_rate, rate, &T));
   HostStage hs(m);
   std::vector<int64_t> ylen;
+  std::vector<int> cum;  // (marks: copied out next to ylen, in acoustic_host's own round trip)
   int64_t Ty = 0;
   float* z = nullptr;
-  TRY(acoustic_host(hs, ids, lengths, B, Tx, scales, sid, opts, ylen, Ty, z));
+  TRY(acoustic_host(hs, ids, lengths, B, Tx, scales, sid, opts, ylen, Ty, z, token_ends ? &cum : nullptr));
+  if (token_ends)
+    for (int b = 0; b < B; ++b) marks_fill_host(cum.data() + (size_t)b * Tx, lengths[b], Tx, hp.hop_length, T ? T->P.L : 1, T ? T->P.M : 1, token_ends + (size_t)b * Tx);
   vits_session* s = hs.s;
   s->ragged = B > 1;
   s->solo = opts && (opts->flags & VITS_FLAG_SOLO_BATCH);
@@ -456,7 +477,7 @@ static int synth_eager(vits_model* m, const int64_t* ids, const int64_t* lengths
 
 static int synth_dispatch(vits_model* m, const int64_t* ids, const int64_t* lengths, int32_t B, int32_t Tx, const float* scales,
                           const int64_t* sid, const vits_synth_opts* opts, bool pcm, float pcm_scale, int32_t sample_rate, void** out,
-                          int64_t* out_samples, int64_t* out_lengths) {
+                          int64_t* out_samples, int64_t* out_lengths, int64_t* token_ends = nullptr) {
   if (!m || !ids || !lengths || !scales || !out || !out_samples || B <= 0 || Tx <= 0) return fail(VITS_ERR_ARG, "bad argument");
   if (!m->acoustic) return fail(VITS_ERR_UNSUPPORTED, "vocoder-only model: only the decoder stage is available");
   for (int b = 0; b < B; ++b) if (lengths[b] < 0 || lengths[b] > Tx) return fail(VITS_ERR_ARG, "length out of range");
@@ -474,8 +495,8 @@ static int synth_dispatch(vits_model* m, const int64_t* ids, const int64_t* leng
   for (int attempt = 0;; ++attempt) {
     tl_ps_timed_out = false;
     const int rc = (g_fast_path && !env_off && !injected)
-                       ? synth_fast(m, ids, lengths, B, Tx, scales, sid, opts, pcm, pcm_scale, rate, out, out_samples, out_lengths)
-                       : synth_eager(m, ids, lengths, B, Tx, scales, sid, opts, pcm, pcm_scale, rate, out, out_samples, out_lengths);
+                       ? synth_fast(m, ids, lengths, B, Tx, scales, sid, opts, pcm, pcm_scale, rate, out, out_samples, out_lengths, token_ends)
+                       : synth_eager(m, ids, lengths, B, Tx, scales, sid, opts, pcm, pcm_scale, rate, out, out_samples, out_lengths, token_ends);
     if (rc == VITS_OK || !tl_ps_timed_out || attempt) return rc;  // a persistent program timed out: once more, on launches
   }
 }
@@ -503,6 +524,25 @@ int vits_synthesize_pcm16_rate(vits_model* m, const int64_t* ids, const int64_t*
                                int64_t* out_samples, int64_t* out_lengths) {
   if (sample_rate < 0) return fail(VITS_ERR_UNSUPPORTED, "sample_rate %d: must be positive, or 0 for the voice's own rate", sample_rate);
   return synth_dispatch(m, ids, lengths, B, Tx, scales, sid, opts, true, pcm_scale, sample_rate, reinterpret_cast<void**>(out_pcm), out_samples, out_lengths);
+}
+
+// ---- include/vits_marks.h
+int vits_synthesize_marks(vits_model* m, const int64_t* ids, const int64_t* lengths, int32_t B, int32_t Tx, const float* scales,
+                          const int64_t* sid, const vits_synth_opts* opts, int32_t sample_rate, float** out_audio, int64_t* out_samples,
+                          int64_t* out_lengths, int64_t* token_ends) {
+  if (!token_ends) return fail(VITS_ERR_ARG, "token_ends must not be NULL (vits_synthesize_rate is the call without marks)");
+  if (sample_rate < 0) return fail(VITS_ERR_UNSUPPORTED, "sample_rate %d: must be positive, or 0 for the voice's own rate", sample_rate);
+  return synth_dispatch(m, ids, lengths, B, Tx, scales, sid, opts, false, 1.f, sample_rate, reinterpret_cast<void**>(out_audio), out_samples, out_lengths,
+                        token_ends);
+}
+
+int vits_synthesize_pcm16_marks(vits_model* m, const int64_t* ids, const int64_t* lengths, int32_t B, int32_t Tx, const float* scales,
+                                const int64_t* sid, const vits_synth_opts* opts, float pcm_scale, int32_t sample_rate, int16_t** out_pcm,
+                                int64_t* out_samples, int64_t* out_lengths, int64_t* token_ends) {
+  if (!token_ends) return fail(VITS_ERR_ARG, "token_ends must not be NULL (vits_synthesize_pcm16_rate is the call without marks)");
+  if (sample_rate < 0) return fail(VITS_ERR_UNSUPPORTED, "sample_rate %d: must be positive, or 0 for the voice's own rate", sample_rate);
+  return synth_dispatch(m, ids, lengths, B, Tx, scales, sid, opts, true, pcm_scale, sample_rate, reinterpret_cast<void**>(out_pcm), out_samples, out_lengths,
+                        token_ends);
 }
 
 void vits_free_pcm16(int16_t* p) { free(p); }

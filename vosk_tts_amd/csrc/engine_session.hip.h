@@ -98,7 +98,11 @@ struct vits_session {
   char *io_h = nullptr, *io_d = nullptr;  // per-call inputs: pinned host mirror and device copy (SynthDev | lengths | sid | ids | forced)
   size_t io_bytes = 0, io_len = 0, io_sid = 0, io_ids = 0, io_forced = 0, io_seeds = 0, io_bert = 0;  // io_bert: float [B, bert_dim, TxB] (BERT-conditioned voices), 0 = none
   int64_t* h_ylen = nullptr;       // pinned [B] + one int error word behind it
-  hipGraphExec_t g1[8] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};  // [persist*4 + forced*2 + solo]
+  hipGraphExec_t g1[16] = {};      // [marks*8 + persist*4 + forced*2 + solo]; a call without marks only ever touches 0..7
+  // speech marks (include/vits_marks.h), front: token ends int64 [B, T_x bucket] on the device and their pinned copy, allocated by the
+  // first request that asks for marks; the marks variants of g1 write and copy them in front of the h_ylen copy
+  long long* marks_d = nullptr;
+  int64_t* marks_h = nullptr;
   std::map<int, vits_session*> backs;
   vits_session* front = nullptr;
   float* out_d = nullptr;          // back: fp32 audio [B, T_y bucket * hop] on the device
@@ -367,7 +371,10 @@ static void session_free(vits_session* s) {
     if (kv.second.y_h) hipHostFree(kv.second.y_h);
   }
   s->rates.clear();
-  for (int i = 0; i < 8; ++i) { if (s->g1[i]) hipGraphExecDestroy(s->g1[i]); if (s->g2[i]) hipGraphExecDestroy(s->g2[i]); }
+  for (hipGraphExec_t g : s->g1) if (g) hipGraphExecDestroy(g);
+  for (hipGraphExec_t g : s->g2) if (g) hipGraphExecDestroy(g);
+  if (s->marks_d) hipFree(s->marks_d);
+  if (s->marks_h) hipHostFree(s->marks_h);
   if (s->io_h) hipHostFree(s->io_h);
   if (s->io_d) hipFree(s->io_d);
   if (s->h_ylen) hipHostFree(s->h_ylen);

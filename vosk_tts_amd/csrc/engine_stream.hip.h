@@ -37,6 +37,7 @@ struct vits_stream {
   float *d_dn = nullptr, *d_dn_scr = nullptr;
   size_t dn_scr_elems = 0;
   hipEvent_t ev = nullptr;
+  std::vector<int64_t> marks;       // token ends in output samples (include/vits_marks.h); empty: a latent stream, which has no tokens
   int find(int lo) const { for (int i = 0; i < 2; ++i) if (lo >= win[i].lo && lo < win[i].hi) return i; return -1; }
 };
 
@@ -154,11 +155,16 @@ int vits_stream_open_rate(vits_model* m, const int64_t* ids, int32_t Tx, const f
     st->rs = T;
     st->hs = new HostStage(m);
     std::vector<int64_t> ylen;
+    std::vector<int> cum;
     int64_t Ty = 0, len = Tx;
     float* z = nullptr;
     tl_ps_timed_out = false;
-    const int rc = acoustic_host(*st->hs, ids, &len, 1, Tx, scales, &sid, opts, ylen, Ty, z);
-    if (rc == VITS_OK) return stream_start(st, z, (int)Ty, chunk_frames, out, total_samples);
+    const int rc = acoustic_host(*st->hs, ids, &len, 1, Tx, scales, &sid, opts, ylen, Ty, z, &cum);
+    if (rc == VITS_OK) {
+      st->marks.resize(Tx);
+      marks_fill_host(cum.data(), Tx, Tx, m->hp.hop_length, T ? T->P.L : 1, T ? T->P.M : 1, st->marks.data());
+      return stream_start(st, z, (int)Ty, chunk_frames, out, total_samples);
+    }
     vits_stream_close(st);
     if (!tl_ps_timed_out || attempt) return rc;  // a persistent program timed out: once more, on launches
   }
@@ -207,6 +213,15 @@ int vits_stream_open_latent_denoise(vits_model* m, const float* z, int32_t Ty, i
   const float* d_bias = nullptr;
   TRY(denoise_prepare(m, strength, filter_length, &T, &d_bias));
   return stream_open_latent(m, z, Ty, chunk_frames, flags, nullptr, T, d_bias, strength, out, total_samples);
+}
+
+int vits_stream_marks(vits_stream* st, int64_t* token_ends, int32_t cap, int32_t* n_tokens) {
+  if (!st || !n_tokens || cap < 0 || (!token_ends && cap > 0)) return fail(VITS_ERR_ARG, "bad argument");
+  *n_tokens = (int32_t)st->marks.size();
+  if (st->marks.empty() || (!token_ends && cap == 0)) return VITS_OK;  // (NULL with capacity 0 asks for the count only)
+  if (cap < *n_tokens) return fail(VITS_ERR_ARG, "token_ends capacity %d < %d tokens", cap, *n_tokens);
+  memcpy(token_ends, st->marks.data(), sizeof(int64_t) * st->marks.size());
+  return VITS_OK;
 }
 
 int vits_stream_next(vits_stream* st, float* audio, int64_t capacity, int64_t* n_samples) {

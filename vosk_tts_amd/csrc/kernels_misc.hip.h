@@ -36,6 +36,7 @@ struct SynthDev {
   float scales[3];            // [noise_scale, length_scale, noise_scale_w]  (onnx_export.py:62-64)
   float pcm_scale;            // Synth.synth_audio's `scale` (vosk_tts/synth.py:128) for the int16 output
   unsigned long long seed;    // Philox seed
+  int rate_L, rate_M;         // output rate / native rate in lowest terms (1 / 1 at the native rate): read by token_ends_kernel only
 };
 
 __device__ __forceinline__ float gelu_erf(float v) { return 0.5f * v * (1.0f + erff(v * 0.70710678118654752440f)); }

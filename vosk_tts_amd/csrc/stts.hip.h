@@ -843,8 +843,32 @@ static int stts_denoise_arg(stts_model* m, const stts_synth_opts* opts, SttsDeno
   return denoise_prepare(m->vocoder, opts->denoiser_strength, opts->denoiser_filter_length, &d->T, &d->bias);
 }
 
+// Speech marks of a call (include/vits_marks.h): where the token ends go and the output rate's L / M.  The durations are on the host in
+// every multistream path, so the marks are filled there (marks_fill_host) and nothing is launched for them.
+struct SttsMarks {
+  int64_t* token_ends = nullptr;  // [B, T_x]
+  long long L = 1, M = 1;
+};
+static int stts_hop(const stts_model* m) { return m->vocoder ? m->vocoder->hp.hop_length : m->hp.hop_length; }
+// the marks argument of an entry point: rate 0 / the voice's own = native time axis; another rate only fixes L / M (host arithmetic)
+static int stts_marks_arg(const stts_model* m, int64_t* token_ends, int32_t sample_rate, SttsMarks* mk, int* rate_out) {
+  if (!token_ends) return fail(VITS_ERR_ARG, "token_ends must not be NULL (the call without marks has no such argument)");
+  if (sample_rate < 0) return fail(VITS_ERR_UNSUPPORTED, "sample_rate %d: must be positive, or 0 for the voice's own rate", sample_rate);
+  const int native = m->vocoder ? m->vocoder->hp.sampling_rate : m->hp.sampling_rate;
+  mk->token_ends = token_ends;
+  *rate_out = 0;
+  if (sample_rate && sample_rate != native) {
+    ResamplePlan P;
+    TRY(resample_plan(native, sample_rate, &P));
+    mk->L = P.L; mk->M = P.M;
+    *rate_out = sample_rate;
+  }
+  return VITS_OK;
+}
+
 static int stts_synth_fast(stts_model* m, const int64_t* ids, int32_t Tx, const float* scales, int64_t sid, const float* bert, const float* pde,
-                           const stts_synth_opts* opts, float** out_audio, int64_t* out_samples, float** out_mel, int64_t* out_frames) {
+                           const stts_synth_opts* opts, float** out_audio, int64_t* out_samples, float** out_mel, int64_t* out_frames,
+                           const SttsMarks* mk) {
   const stts_hparams& hp = m->hp;
   const int NF = hp.n_feats;
   const int n = (opts && opts->n_timesteps > 0) ? opts->n_timesteps : hp.n_timesteps;
@@ -900,6 +924,7 @@ static int stts_synth_fast(stts_model* m, const int64_t* ids, int32_t Tx, const 
   int ylen = 0;
   for (int j = 0; j < TxB; ++j) { if (j < Tx) ylen += dur[j]; h_cum[j] = ylen; }  // only the utterance's own tokens count
   if (ylen > (1 << 18)) return fail(VITS_ERR_ARG, "T_y unreasonably large");  // (also keeps every per-item [C <= 2048, T] tensor below the 2 GiB the conv kernels' 32-bit offsets address)
+  if (mk) marks_fill_host(h_cum, Tx, Tx, stts_hop(m), mk->L, mk->M, mk->token_ends);
   const int T4 = (ylen + 3) / 4 * 4;  // fix_len_compatibility (utils/model.py:14-20): where the exact-size run's tensors end
   const int TB = (T4 + 31) / 32 * 32;
   SttsDev* hv = reinterpret_cast<SttsDev*>(F->io_h + F->o_dev);
@@ -957,17 +982,16 @@ static int stts_synth_fast(stts_model* m, const int64_t* ids, int32_t Tx, const 
   return VITS_OK;
 }
 
-extern "C" {
-
-int stts_synthesize(stts_model* m, const int64_t* ids, int32_t Tx, const float* scales, int64_t sid, const float* bert, const float* pde,
-                    const stts_synth_opts* opts, float** out_audio, int64_t* out_samples, float** out_mel, int64_t* out_frames) {
+static int stts_synthesize_impl(stts_model* m, const int64_t* ids, int32_t Tx, const float* scales, int64_t sid, const float* bert, const float* pde,
+                               const stts_synth_opts* opts, float** out_audio, int64_t* out_samples, float** out_mel, int64_t* out_frames,
+                               const SttsMarks* mk) {
   if (!m || !ids || !scales || Tx <= 0 || (out_audio && !out_samples) || (out_mel && !out_frames)) return fail(VITS_ERR_ARG, "bad argument");
   if (out_audio && !m->vocoder) return fail(VITS_ERR_ARG, "no vocoder attached");
   TRY(stts_check_sid(m, &sid, 1));
   {
     static const bool env_off = getenv("VITS_NO_FASTPATH") != nullptr;
     if (g_fast_path && !env_off && !(opts && opts->noise))
-      return stts_synth_fast(m, ids, Tx, scales, sid, bert, pde, opts, out_audio, out_samples, out_mel, out_frames);
+      return stts_synth_fast(m, ids, Tx, scales, sid, bert, pde, opts, out_audio, out_samples, out_mel, out_frames, mk);
   }
   SttsDenoise dn;
   if (out_audio) TRY(stts_denoise_arg(m, opts, &dn));
@@ -998,6 +1022,7 @@ int stts_synthesize(stts_model* m, const int64_t* ids, int32_t Tx, const float* 
   const int T = (int)((ylen + 3) / 4 * 4);  // fix_len_compatibility (utils/model.py:14-20)
   std::vector<int> cum(Tx);
   for (int j = 0, a = 0; j < Tx; ++j) { a += dur[j]; cum[j] = a; }
+  if (mk) marks_fill_host(cum.data(), Tx, Tx, stts_hop(m), mk->L, mk->M, mk->token_ends);
   // ---- flow-matching decoder
   TRY(stts_arena(s, stts_est_bytes(hp, nb, T, n)));
   int* d_cum = call.up(cum.data(), Tx);
@@ -1076,13 +1101,55 @@ int stts_synthesize(stts_model* m, const int64_t* ids, int32_t Tx, const float* 
   return VITS_OK;
 }
 
+// a call's audio [B, S] (library-owned, items of lengths[b] samples) replaced by its copy at `rate` (vits_op_resample: the finished
+// waveform crosses the host once more, as it does for every multistream request at another rate)
+static int stts_resample_out(stts_model* m, int rate, int B, float** audio, int64_t* S, int64_t* lengths) {
+  ResamplePlan P;
+  TRY(resample_plan(m->vocoder->hp.sampling_rate, rate, &P));
+  const int64_t So = P.n_out(*S);
+  float* y = static_cast<float*>(malloc(sizeof(float) * (size_t)B * (So ? So : 1)));
+  if (!y) return fail(VITS_ERR_NOMEM, "host alloc failed");
+  const int rc = *S > 0 ? vits_op_resample(m->base.device, *audio, lengths, B, *S, m->vocoder->hp.sampling_rate, rate, y) : VITS_OK;
+  if (rc != VITS_OK) { free(y); return rc; }
+  free(*audio);
+  *audio = y; *S = So;
+  for (int b = 0; b < B; ++b) lengths[b] = P.n_out(lengths[b]);
+  return VITS_OK;
+}
+
+extern "C" {
+
+int stts_synthesize(stts_model* m, const int64_t* ids, int32_t Tx, const float* scales, int64_t sid, const float* bert, const float* pde,
+                    const stts_synth_opts* opts, float** out_audio, int64_t* out_samples, float** out_mel, int64_t* out_frames) {
+  return stts_synthesize_impl(m, ids, Tx, scales, sid, bert, pde, opts, out_audio, out_samples, out_mel, out_frames, nullptr);
+}
+
+int stts_synthesize_marks(stts_model* m, const int64_t* ids, int32_t Tx, const float* scales, int64_t sid, const float* bert, const float* pde,
+                          const stts_synth_opts* opts, int32_t sample_rate, float** out_audio, int64_t* out_samples, float** out_mel,
+                          int64_t* out_frames, int64_t* token_ends) {
+  if (!m) return fail(VITS_ERR_ARG, "bad argument");
+  SttsMarks mk;
+  int rate = 0;
+  TRY(stts_marks_arg(m, token_ends, sample_rate, &mk, &rate));
+  TRY(stts_synthesize_impl(m, ids, Tx, scales, sid, bert, pde, opts, out_audio, out_samples, out_mel, out_frames, &mk));
+  if (rate && out_audio) {
+    int64_t len = *out_samples;
+    const int rc = stts_resample_out(m, rate, 1, out_audio, out_samples, &len);
+    if (rc != VITS_OK) { free(*out_audio); *out_audio = nullptr; if (out_mel) { free(*out_mel); *out_mel = nullptr; } return rc; }
+  }
+  return VITS_OK;
+}
+
 int stts_stream_open(stts_model* m, const int64_t* ids, int32_t Tx, const float* scales, int64_t sid, const float* bert, const float* pde,
                      const stts_synth_opts* opts, int32_t chunk_frames, vits_stream** out, int64_t* total_samples) {
   if (!m || !out || chunk_frames <= 0) return fail(VITS_ERR_ARG, "bad argument");
   if (!m->vocoder) return fail(VITS_ERR_ARG, "no vocoder attached");
   float* mel = nullptr;
   int64_t frames = 0;
-  TRY(stts_synthesize(m, ids, Tx, scales, sid, bert, pde, opts, nullptr, nullptr, &mel, &frames));
+  std::vector<int64_t> ends(Tx > 0 ? Tx : 0);  // recorded for vits_stream_marks (native rate: this open has no other)
+  SttsMarks mk;
+  mk.token_ends = ends.data();
+  TRY(stts_synthesize_impl(m, ids, Tx, scales, sid, bert, pde, opts, nullptr, nullptr, &mel, &frames, Tx > 0 ? &mk : nullptr));
   // the mel crosses the host once (80 x T_y floats): the acoustic context that produced it is cached and reused by other calls
   int rc = VITS_OK;
   if (frames <= 0) rc = fail(VITS_ERR_ARG, "empty utterance");
@@ -1090,12 +1157,13 @@ int stts_stream_open(stts_model* m, const int64_t* ids, int32_t Tx, const float*
     rc = vits_stream_open_latent_denoise(m->vocoder, mel, (int32_t)frames, chunk_frames, 1u, opts->denoiser_strength, opts->denoiser_filter_length, out, total_samples);
   else rc = vits_stream_open_latent(m->vocoder, mel, (int32_t)frames, chunk_frames, 1u, out, total_samples);
   free(mel);
+  if (rc == VITS_OK) (*out)->marks = std::move(ends);
   return rc;
 }
 
-int stts_synthesize_batch(stts_model* m, const int64_t* ids, const int64_t* lengths, int32_t B, int32_t Tx, const float* scales,
-                          const int64_t* sid, const float* bert, const float* pde, const stts_synth_opts* opts, float** out_audio,
-                          int64_t* out_samples, int64_t* out_lengths) {
+static int stts_synthesize_batch_impl(stts_model* m, const int64_t* ids, const int64_t* lengths, int32_t B, int32_t Tx, const float* scales,
+                                     const int64_t* sid, const float* bert, const float* pde, const stts_synth_opts* opts, float** out_audio,
+                                     int64_t* out_samples, int64_t* out_lengths, const SttsMarks* mk) {
   if (!m || !ids || !lengths || !scales || !out_audio || !out_samples || !out_lengths || B <= 0 || Tx <= 0) return fail(VITS_ERR_ARG, "bad argument");
   if (!m->vocoder) return fail(VITS_ERR_ARG, "no vocoder attached");
   if (opts && opts->noise) return fail(VITS_ERR_ARG, "injected noise is a single-utterance option");
@@ -1138,6 +1206,7 @@ int stts_synthesize_batch(stts_model* m, const int64_t* ids, const int64_t* leng
     l2[b] = l2[B + b] = a; lT[b] = lT[B + b] = Tb;
     if (Tb > T) T = Tb;
     if (a > Tm) Tm = a;
+    if (mk) marks_fill_host(cum.data() + (size_t)b * Tx, lengths[b], Tx, stts_hop(m), mk->L, mk->M, mk->token_ends + (size_t)b * Tx);
   }
   // ---- flow matching over all items (and their CFG twins) at once
   TRY(stts_arena(s, stts_est_bytes(hp, nb, T, n)));
@@ -1208,6 +1277,27 @@ int stts_synthesize_batch(stts_model* m, const int64_t* ids, const int64_t* leng
   *out_audio = h_audio;
   *out_samples = S;
   for (int b = 0; b < B; ++b) out_lengths[b] = ylen[b] * v->hp.hop_length;
+  return VITS_OK;
+}
+
+int stts_synthesize_batch(stts_model* m, const int64_t* ids, const int64_t* lengths, int32_t B, int32_t Tx, const float* scales,
+                          const int64_t* sid, const float* bert, const float* pde, const stts_synth_opts* opts, float** out_audio,
+                          int64_t* out_samples, int64_t* out_lengths) {
+  return stts_synthesize_batch_impl(m, ids, lengths, B, Tx, scales, sid, bert, pde, opts, out_audio, out_samples, out_lengths, nullptr);
+}
+
+int stts_synthesize_batch_marks(stts_model* m, const int64_t* ids, const int64_t* lengths, int32_t B, int32_t Tx, const float* scales,
+                                const int64_t* sid, const float* bert, const float* pde, const stts_synth_opts* opts, int32_t sample_rate,
+                                float** out_audio, int64_t* out_samples, int64_t* out_lengths, int64_t* token_ends) {
+  if (!m) return fail(VITS_ERR_ARG, "bad argument");
+  SttsMarks mk;
+  int rate = 0;
+  TRY(stts_marks_arg(m, token_ends, sample_rate, &mk, &rate));
+  TRY(stts_synthesize_batch_impl(m, ids, lengths, B, Tx, scales, sid, bert, pde, opts, out_audio, out_samples, out_lengths, &mk));
+  if (rate) {
+    const int rc = stts_resample_out(m, rate, B, out_audio, out_samples, out_lengths);
+    if (rc != VITS_OK) { free(*out_audio); *out_audio = nullptr; return rc; }
+  }
   return VITS_OK;
 }
 

@@ -26,8 +26,9 @@ def word_positions(phones):
     return [p + ("_B" if i == 0 else "_E" if i == len(phones) - 1 else "_I") for i, p in enumerate(phones)]
 
 
-def _symbols(text, dic, word_pos, tokens=_TOKENS):
-    """[(symbol, punctuation list, in_quote, word index)] in reading order, '^' first, ' ' + '$' last"""
+def _symbols(text, dic, word_pos, tokens=_TOKENS, word_texts=None):
+    """[(symbol, punctuation list, in_quote, word index)] in reading order, '^' first, ' ' + '$' last.
+    word_texts (optional dict): filled with {word index: the word as written, lower-cased}"""
     out = [("^", [], 0, 0)]
     quote, pending, widx = 0, [], 1
     for tok in tokens.split(text.replace(" -", "- ").lower()):
@@ -47,6 +48,8 @@ def _symbols(text, dic, word_pos, tokens=_TOKENS):
             if word_pos:
                 phones = word_positions(phones)
             out.extend((p, [], quote, widx) for p in phones)
+            if word_texts is not None:
+                word_texts[widx] = tok
             pending = []
             widx += 1
     out.append((" ", pending, quote, widx))
@@ -54,11 +57,15 @@ def _symbols(text, dic, word_pos, tokens=_TOKENS):
     return out
 
 
-def g2p_multistream(text, dic, phoneme_id_map, bert_embeddings=None, word_pos=False, pause_marks=False):
+def g2p_multistream(text, dic, phoneme_id_map, bert_embeddings=None, word_pos=False, pause_marks=False, return_words=False):
     """-> (ids: list of 5-tuples, one per symbol; bert: list of per-symbol vectors or [])
+    return_words=True appends one more value, for speech marks (vosk_tts_amd/marks.py): (symbols, bert_word_index per symbol,
+    {word index: the word's text}) -- a word is the run of symbols other than ' ', '^', '$' that share one index.
     pause_marks=True is g2p_multistream_scales (multistream_v3, synth.py:360-456): '_' is a punctuation token, word
     positions are always on, and a third list carries 20.0 for symbols whose boundary holds a '_' (else 0.0)."""
-    syms = _symbols(text, dic, word_pos or pause_marks, _TOKENS_V3 if pause_marks else _TOKENS)
+    word_texts = {} if return_words else None
+    syms = _symbols(text, dic, word_pos or pause_marks, _TOKENS_V3 if pause_marks else _TOKENS, word_texts)
+    words = (([s[0] for s in syms], [s[3] for s in syms], word_texts),) if return_words else ()
     last, last_sentence = " ", " "
     ids, bert = [None] * len(syms), []
     for k in range(len(syms) - 1, -1, -1):  # the two "last ..." streams accumulate from the END of the utterance
@@ -74,8 +81,8 @@ def g2p_multistream(text, dic, phoneme_id_map, bert_embeddings=None, word_pos=Fa
     if bert_embeddings is not None:
         bert = [bert_embeddings[widx] for (_, _, _, widx) in syms]
     if pause_marks:
-        return ids, bert, [PAUSE_FRAMES if "_" in puncs else 0.0 for (_, puncs, _, _) in syms]
-    return ids, bert
+        return (ids, bert, [PAUSE_FRAMES if "_" in puncs else 0.0 for (_, puncs, _, _) in syms]) + words
+    return (ids, bert) + words
 
 
 _BERT_PUNCT = re.compile(r"[-,.?!;:\"]")

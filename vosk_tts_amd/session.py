@@ -225,7 +225,7 @@ BACK_SESSIONS_PER_FRONT = 6
 _GRAPH_INPUTS = ("input", "input_lengths", "scales", "sid")
 _OPTIONAL_NONE = ("bert", "phone_duration_extra")
 # extension feeds (not part of the ONNX graph) used by parity tests
-_EXT = ("vits.noise_dp", "vits.noise_prior", "vits.forced_durations", "vits.seed", "vits.solo", "vits.item_seeds", "vits.sample_rate")
+_EXT = ("vits.noise_dp", "vits.noise_prior", "vits.forced_durations", "vits.seed", "vits.solo", "vits.item_seeds", "vits.sample_rate", "vits.marks")
 
 
 class _Arg:
@@ -290,14 +290,17 @@ class VitsSession:
 
     def _run_solo_batch(self, key, reqs):
         """reqs: [(ids [1,T] int64, sid, seed)] -> per request (audio-or-pcm [1,S_b], lengths [1]); one request: the plain call"""
-        kind, scales, scale, rate = key  # (rate: output sample rate in Hz, 0 = the voice's own; part of the key, so a batch has one)
+        # (rate: output sample rate in Hz, 0 = the voice's own; marks: the requests want their token ends, include/vits_marks.h.  Both are
+        #  part of the key, so a batch has one rate and either every request of it gets a third value or none does)
+        kind, scales, scale, rate, marks = key
         scales = np.array(scales, np.float32)
         if len(reqs) == 1:
             ids, sid, seed = reqs[0]
             lens = np.array([ids.shape[1]], np.int64)
             if kind == "pcm":
-                return [self._model.synthesize_pcm16(ids, lens, scales, np.array([sid], np.int64), pcm_scale=scale, seed=seed, sample_rate=rate)]
-            return [self._model.synthesize(ids, lens, scales, np.array([sid], np.int64), seed=seed, sample_rate=rate)]
+                return [self._model.synthesize_pcm16(ids, lens, scales, np.array([sid], np.int64), pcm_scale=scale, seed=seed, sample_rate=rate,
+                                                     marks=marks)]
+            return [self._model.synthesize(ids, lens, scales, np.array([sid], np.int64), seed=seed, sample_rate=rate, marks=marks)]
         # batch sizes come in powers of two (filled up with one-token dummies, whose padding tiles the ragged solo batch never
         # computes): every (batch size, length bucket) is a workspace and two captured graphs inside the engine, and a thread pool
         # produces every batch size between 1 and its own size
@@ -313,10 +316,13 @@ class VitsSession:
         sids = np.array([r[1] for r in reqs], np.int64)
         seeds = np.array([r[2] for r in reqs], np.uint64)
         if kind == "pcm":
-            out, ol = self._model.synthesize_pcm16(batch, lens, scales, sids, pcm_scale=scale, seed=int(seeds[0]), solo=True, item_seeds=seeds,
-                                                   sample_rate=rate)
+            res = self._model.synthesize_pcm16(batch, lens, scales, sids, pcm_scale=scale, seed=int(seeds[0]), solo=True, item_seeds=seeds,
+                                               sample_rate=rate, marks=marks)
         else:
-            out, ol = self._model.synthesize(batch, lens, scales, sids, seed=int(seeds[0]), solo=True, item_seeds=seeds, sample_rate=rate)
+            res = self._model.synthesize(batch, lens, scales, sids, seed=int(seeds[0]), solo=True, item_seeds=seeds, sample_rate=rate, marks=marks)
+        out, ol = res[0], res[1]
+        if marks:  # each request its own tokens' ends
+            return [(out[b:b + 1, :int(ol[b])].copy(), ol[b:b + 1].copy(), res[2][b:b + 1, :int(lens[b])].copy()) for b in range(n_real)]
         return [(out[b:b + 1, :int(ol[b])].copy(), ol[b:b + 1].copy()) for b in range(n_real)]
 
     # -- onnxruntime.InferenceSession surface used by the reference ------------------------
@@ -373,23 +379,42 @@ class VitsSession:
 
     def run(self, output_names, input_feed, run_options=None):
         """Extension feed "vits.sample_rate" (next to "vits.seed"): output rate in Hz; the time axis of the output is then in output
-        samples (include/vits_resample.h)."""
+        samples (include/vits_resample.h).  Extension feed "vits.marks": True -- the result list gets a second entry, token_ends int64
+        [B, T_x] in output samples (include/vits_marks.h)."""
         feed, ids, sid, seed = self._validated(output_names, input_feed)
         self._watch()
         rate = self._rate(feed.get("vits.sample_rate"))
+        marks = self._marks(feed)
         n = self._coalescable(feed, ids)
         if n:
-            key = ("f32", tuple(float(v) for v in np.asarray(feed["scales"], np.float32).reshape(-1)), 1.0, rate)
-            audio, lengths = self.coalescer.submit(key, np.ascontiguousarray(ids[:, :n], np.int64), int(sid[0]), int(seed))
-            self.last_lengths = lengths
-            return [audio[:, None, None, :]]
-        audio, lengths = self._model.synthesize(
+            key = ("f32", tuple(float(v) for v in np.asarray(feed["scales"], np.float32).reshape(-1)), 1.0, rate, marks)
+            res = self.coalescer.submit(key, np.ascontiguousarray(ids[:, :n], np.int64), int(sid[0]), int(seed))
+            self.last_lengths = res[1]
+            if marks:  # (the request's own tokens; columns beyond its length repeat the last end, as the C ABI pads them)
+                return [res[0][:, None, None, :], self._pad_ends(res[2], ids.shape[1])]
+            return [res[0][:, None, None, :]]
+        res = self._model.synthesize(
             ids, np.asarray(feed["input_lengths"]).reshape(-1), np.asarray(feed["scales"], np.float32).reshape(-1), sid,
             noise_dp=feed.get("vits.noise_dp"), noise_prior=feed.get("vits.noise_prior"),
             forced_durations=feed.get("vits.forced_durations"), seed=int(seed), solo=bool(feed.get("vits.solo", False)),
-            item_seeds=feed.get("vits.item_seeds"), bert=feed.get("bert"), sample_rate=rate)
-        self.last_lengths = lengths
-        return [audio[:, None, None, :]]
+            item_seeds=feed.get("vits.item_seeds"), bert=feed.get("bert"), sample_rate=rate, marks=marks)
+        self.last_lengths = res[1]
+        return [res[0][:, None, None, :], res[2]] if marks else [res[0][:, None, None, :]]
+
+    def _marks(self, feed):
+        """the "vits.marks" feed of a request -> bool; the CPU oracle has no marks, and says so"""
+        marks = bool(feed.get("vits.marks", False))
+        if marks:
+            self._lib._need_marks()
+        return marks
+
+    @staticmethod
+    def _pad_ends(ends, T):
+        """token ends [1, n] of a request cut at its length -> [1, T], padded by the rule of include/vits_marks.h"""
+        n = ends.shape[1]
+        if n >= T:
+            return ends
+        return np.concatenate([ends, np.repeat(ends[:, -1:] if n else np.zeros((1, 1), np.int64), T - n, axis=1)], axis=1)
 
     def run_pcm16(self, input_feed, scale=1.0, return_lengths=False, sample_rate=None):
         """run() followed by `audio.squeeze() * scale` and Synth.audio_float_to_int16 (vosk_tts/synth.py:127-130), with the
@@ -397,26 +422,37 @@ class VitsSession:
         float output with numpy, half the bytes over PCIe.  return_lengths: also return the per-item sample counts
         (concurrent callers must take them from the call, not from the shared `last_lengths` attribute).
         sample_rate: output rate in Hz (default: the feed's "vits.sample_rate", else the voice's own): the resampler converts in its
-        epilogue, so the call launches as many kernels as at the voice's rate and copies rate_out / rate_in as many bytes."""
+        epilogue, so the call launches as many kernels as at the voice's rate and copies rate_out / rate_in as many bytes.
+        With the feed "vits.marks": True the result is a tuple that ends with token_ends int64 [B, T_x]: (pcm, token_ends), or
+        (pcm, lengths, token_ends) with return_lengths."""
         feed, ids, sid, seed = self._validated(None, input_feed)
         self._watch()
         rate = self._rate(sample_rate if sample_rate is not None else feed.get("vits.sample_rate"))
+        marks = self._marks(feed)
         n = self._coalescable(feed, ids)
         if n:
-            key = ("pcm", tuple(float(v) for v in np.asarray(feed["scales"], np.float32).reshape(-1)), float(scale), rate)
-            pcm, lengths = self.coalescer.submit(key, np.ascontiguousarray(ids[:, :n], np.int64), int(sid[0]), int(seed))
+            key = ("pcm", tuple(float(v) for v in np.asarray(feed["scales"], np.float32).reshape(-1)), float(scale), rate, marks)
+            res = self.coalescer.submit(key, np.ascontiguousarray(ids[:, :n], np.int64), int(sid[0]), int(seed))
+            pcm, lengths = res[0], res[1]
             self.last_lengths = lengths
+            if marks:
+                ends = self._pad_ends(res[2], ids.shape[1])
+                return (pcm, lengths, ends) if return_lengths else (pcm, ends)
             return (pcm, lengths) if return_lengths else pcm
-        pcm, lengths = self._model.synthesize_pcm16(
+        res = self._model.synthesize_pcm16(
             ids, np.asarray(feed["input_lengths"]).reshape(-1), np.asarray(feed["scales"], np.float32).reshape(-1), sid,
             pcm_scale=float(scale), noise_dp=feed.get("vits.noise_dp"), noise_prior=feed.get("vits.noise_prior"),
             forced_durations=feed.get("vits.forced_durations"), seed=int(seed), solo=bool(feed.get("vits.solo", False)),
-            item_seeds=feed.get("vits.item_seeds"), bert=feed.get("bert"), sample_rate=rate)
+            item_seeds=feed.get("vits.item_seeds"), bert=feed.get("bert"), sample_rate=rate, marks=marks)
+        pcm, lengths = res[0], res[1]
         self.last_lengths = lengths
+        if marks:
+            return (pcm, lengths, res[2]) if return_lengths else (pcm, res[2])
         return (pcm, lengths) if return_lengths else pcm
 
-    def run_stream(self, output_names, input_feed, chunk_frames=64, sample_rate=None):
-        """Streaming form of run() for ONE utterance (extension; the reference's transport is already
+    def run_stream(self, output_names, input_feed, chunk_frames=64, sample_rate=None, on_marks=None):
+        """on_marks: called once with token_ends int64 [T_x] in the stream's output samples before the first chunk (vits_stream_marks).
+        Streaming form of run() for ONE utterance (extension; the reference's transport is already
         `stream AudioChunk`, server/tts_service.proto:46-54): yields float32 [n] chunks of chunk_frames*256
         samples whose concatenation equals run(...)[0].squeeze() for the same feed (same "vits.seed").
         sample_rate (default: the feed's "vits.sample_rate"): output rate in Hz; chunk sizes then vary by one sample."""
@@ -432,7 +468,8 @@ class VitsSession:
             ids[:, :n], np.asarray(feed["scales"], np.float32).reshape(-1), int(sid[0]), chunk_frames=chunk_frames,
             noise_dp=None if nd is None else np.asarray(nd)[:, :, :n], noise_prior=feed.get("vits.noise_prior"),
             forced_durations=None if fd is None else np.asarray(fd)[:, :n], seed=seed,
-            bert=None if bert is None else np.ascontiguousarray(np.asarray(bert, np.float32)[:, :, :n]), sample_rate=rate)
+            bert=None if bert is None else np.ascontiguousarray(np.asarray(bert, np.float32)[:, :, :n]), sample_rate=rate,
+            on_marks=on_marks)
 
     def warmup(self, max_tokens=128, frames_per_token=(2.0, 5.0), speaker_id=0, freeze_gc=False, typical_frames_per_token=3.0,
                stream_chunk_frames=None):

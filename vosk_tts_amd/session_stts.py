@@ -13,7 +13,8 @@ from .capi import VitsLib
 from .capi_stts import SttsModel
 
 _INPUTS = ("input", "input_lengths", "scales", "sid", "bert", "phone_duration_extra")
-_EXT = ("vits.noise", "vits.seed", "vits.n_timesteps", "vits.sample_rate", "vits.denoiser_strength", "vits.denoiser_filter_length")
+_EXT = ("vits.noise", "vits.seed", "vits.n_timesteps", "vits.sample_rate", "vits.denoiser_strength", "vits.denoiser_filter_length",
+        "vits.marks")
 
 
 class SttsSession:
@@ -96,8 +97,15 @@ class SttsSession:
     def run(self, output_names, input_feed, run_options=None):
         """Extension feeds: "vits.sample_rate", output rate in Hz (the finished waveform is resampled, include/vits_resample.h);
         "vits.denoiser_strength" / "vits.denoiser_filter_length", the vocoder-bias denoiser behind the clamp (include/vits_denoise.h),
-        applied at the vocoder's own rate, before any resampling."""
+        applied at the vocoder's own rate, before any resampling; "vits.marks": True appends token_ends int64 [1, T] in output samples
+        to the result list (include/vits_marks.h; stts_synthesize_marks takes the rate itself)."""
         feed, ids, scales, sid, bert, pde, seed = self._parse(output_names, input_feed)
+        if feed.get("vits.marks"):
+            audio, _, ends = self._model.synthesize(ids, scales, sid, bert, pde, noise=feed.get("vits.noise"), seed=seed,
+                                                    n_timesteps=int(feed.get("vits.n_timesteps", 0)), want_mel=False, marks=True,
+                                                    sample_rate=self._rate(feed.get("vits.sample_rate")), **self._denoiser(feed))
+            outs = {"wav": audio[None, :], "wav_lengths": np.array([audio.shape[0]], np.int64)}
+            return [outs[n] for n in (output_names or ["wav", "wav_lengths"])] + [ends[None, :]]
         audio, _ = self._model.synthesize(ids, scales, sid, bert, pde, noise=feed.get("vits.noise"), seed=seed,
                                           n_timesteps=int(feed.get("vits.n_timesteps", 0)), want_mel=False, **self._denoiser(feed))
         if self._rate(feed.get("vits.sample_rate")):
@@ -105,8 +113,9 @@ class SttsSession:
         outs = {"wav": audio[None, :], "wav_lengths": np.array([audio.shape[0]], np.int64)}
         return [outs[n] for n in (output_names or ["wav", "wav_lengths"])]
 
-    def run_stream(self, output_names, input_feed, chunk_frames=64, sample_rate=None):
-        """Streaming form of run() (extension; the reference's transport is already `stream AudioChunk`,
+    def run_stream(self, output_names, input_feed, chunk_frames=64, sample_rate=None, on_marks=None):
+        """on_marks: called once with token_ends int64 [T] in the stream's output samples, before the first chunk.
+        Streaming form of run() (extension; the reference's transport is already `stream AudioChunk`,
         server/tts_service.proto:46-54): yields float32 [n] chunks of chunk_frames * hop samples whose concatenation equals
         run(...)[0].squeeze() for the same feed (same "vits.seed").  The acoustic model runs once, the vocoder is streamed."""
         feed, ids, scales, sid, bert, pde, seed = self._parse(output_names, input_feed)
@@ -120,18 +129,22 @@ class SttsSession:
             raise VitsError(4, f"a stream with a denoiser (strength {dn['denoiser_strength']}) at sample_rate {rate} Hz is not supported: "
                                f"only the voice's own {self._vocoder.hp.sampling_rate} Hz")
         if rate:  # the acoustic model's mel, then the vocoder streamed at the rate asked for (vits_stream_open_latent_rate; clamped like the export)
-            _, mel = self._model.synthesize(ids, scales, sid, bert, pde, seed=seed, n_timesteps=int(feed.get("vits.n_timesteps", 0)),
-                                            want_audio=False, want_mel=True)
+            res = self._model.synthesize(ids, scales, sid, bert, pde, seed=seed, n_timesteps=int(feed.get("vits.n_timesteps", 0)),
+                                         want_audio=False, want_mel=True, marks=on_marks is not None, sample_rate=rate if on_marks else None)
+            mel = res[1]
+            if on_marks is not None:
+                on_marks(res[2])
             return self._vocoder.stream_latent(mel, chunk_frames=chunk_frames, clamp=True, sample_rate=rate)
         return self._model.stream(ids, scales, sid, bert, pde, seed=seed, n_timesteps=int(feed.get("vits.n_timesteps", 0)),
-                                  chunk_frames=chunk_frames, **dn)
+                                  chunk_frames=chunk_frames, on_marks=on_marks, **dn)
 
     def run_batch(self, input_feed):
         """The batch door as a feed (stts_synthesize_batch; MultiDeviceSynth calls the model's synthesize_batch with the same
         keywords): "input" int64 [B, 5, T], "input_lengths" [B], "scales" [3],
         "sid" [B], "bert" [B, 768, T] or None, "phone_duration_extra" [B, T] or None, "vits.item_seeds" [B] (or "vits.seed"), and the
         extension feeds of run() -> (audio float32 [B, S] zero beyond each item, lengths int64 [B] in output samples).  Every item is
-        denoised from its own length, then resampled from its own samples."""
+        denoised from its own length, then resampled from its own samples.  "vits.marks": True -> a third value, token_ends int64
+        [B, T] in output samples (stts_synthesize_batch_marks)."""
         feed = {k: v for k, v in input_feed.items() if v is not None}
         for k in feed:
             if k not in _INPUTS and k not in _EXT and k != "vits.item_seeds":
@@ -147,6 +160,11 @@ class SttsSession:
         if ids.ndim != 3 or ids.shape[1] != 5:
             raise ValueError("input must be int64 [B, 5, T]")
         sid = np.asarray(feed.get("sid", np.zeros(ids.shape[0])), np.int64).reshape(-1)
+        if feed.get("vits.marks"):
+            return self._model.synthesize_batch(ids, feed["input_lengths"], np.asarray(feed["scales"], np.float32).reshape(-1), sid,
+                                                feed.get("bert"), feed.get("phone_duration_extra"), seed=int(feed.get("vits.seed", 0)),
+                                                n_timesteps=int(feed.get("vits.n_timesteps", 0)), item_seeds=feed.get("vits.item_seeds"),
+                                                marks=True, sample_rate=rate, **dn)
         audio, ol = self._model.synthesize_batch(ids, feed["input_lengths"], np.asarray(feed["scales"], np.float32).reshape(-1), sid,
                                                  feed.get("bert"), feed.get("phone_duration_extra"), seed=int(feed.get("vits.seed", 0)),
                                                  n_timesteps=int(feed.get("vits.n_timesteps", 0)), item_seeds=feed.get("vits.item_seeds"), **dn)

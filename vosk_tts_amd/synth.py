@@ -200,25 +200,65 @@ class Synth:
                              "this is a VITS-family voice")
         args["vits.denoiser_strength"] = float(denoiser_strength)
 
+    def marks_layout(self, text):
+        """The token layout of `text` under the front end _feed picks, for speech marks (vosk_tts_amd/marks.py):
+        -> (symbols, ids per symbol, blank layout?, word_of per symbol, word_texts).  Needs the voice's config and dictionary only."""
+        from . import marks as M
+
+        text = self.normalize(text)
+        model_type = self.model.config.get("model_type") or ""
+        have_bert = self.model.tokenizer is not None
+        if model_type.startswith("multistream"):
+            from .multistream import g2p_multistream
+
+            v3 = model_type == "multistream_v3" and have_bert
+            res = g2p_multistream(text, self.model.dic, self.model.config["phoneme_id_map"], None, word_pos=model_type == "multistream_v2",
+                                  pause_marks=v3, return_words=True)
+            symbols, word_of, word_texts = M.multistream_layout(*res[-1])
+            return symbols, [1] * len(symbols), False, word_of, word_texts
+        symbols, word_of, word_texts = M.vits_layout(
+            text, lambda w: (self.model.dic[w] if w in self.model.dic else convert(w)).split())
+        if have_bert:
+            return symbols, [1] * len(symbols), self.model.config.get("no_blank", 0) == 0, word_of, word_texts
+        id_map = self.model.config["phoneme_id_map"]
+        return symbols, [len(id_map[p]) if isinstance(id_map[p], list) else 1 for p in symbols], True, word_of, word_texts
+
+    def _marks(self, text, token_ends, rate):
+        from .marks import build_marks
+
+        symbols, counts, blank, word_of, word_texts = self.marks_layout(text)
+        return build_marks(rate, np.asarray(token_ends).reshape(-1), symbols, counts, blank, word_of, word_texts)
+
     def synth_audio(self, text, speaker_id=0, noise_level=None, speech_rate=None, duration_noise_level=None, scale=None, sample_rate=None,
-                    denoiser_strength=None):
+                    denoiser_strength=None, marks=False):
         """sample_rate: output rate in Hz (extension; default None = the voice's own rate, the reference's behaviour): the feed gets
-        "vits.sample_rate" and the engine resamples on the device.  denoiser_strength: see _denoiser."""
+        "vits.sample_rate" and the engine resamples on the device.  denoiser_strength: see _denoiser.
+        marks=True (extension): returns (audio, marks) -- marks.SpeechMarks with rate, token_ends, phonemes [(symbol, start, end)] and
+        words [(text, start, end)] in samples of the returned audio, and seconds(); the default returns the array alone."""
         args, scale = self._feed(text, speaker_id, noise_level, speech_rate, duration_noise_level, scale)
         self._denoiser(args, denoiser_strength)
         rate = self.native_rate()
         if sample_rate and int(sample_rate) != rate:
             rate = int(sample_rate)
             args["vits.sample_rate"] = rate
+        if marks:
+            args["vits.marks"] = True
 
         start_time = time.perf_counter()
         run_pcm16 = getattr(self.model.onnx, "run_pcm16", None)
+        ends = None
         if run_pcm16 is not None:
             # same three steps as below (squeeze, * scale, audio_float_to_int16) fused behind the boundary: the device
             # converts and only int16 crosses PCIe (vits_synthesize_pcm16)
-            audio = run_pcm16(args, scale).squeeze()
+            audio = run_pcm16(args, scale)
+            if marks:
+                audio, ends = audio
+            audio = audio.squeeze()
         else:
-            audio = self.model.onnx.run(None, args)[0]
+            audio = self.model.onnx.run(None, args)
+            if marks:
+                ends = audio[-1]
+            audio = audio[0]
             audio = audio.squeeze()
             audio = audio * scale
             audio = self.audio_float_to_int16(audio)
@@ -228,30 +268,43 @@ class Synth:
         infer_sec = end_time - start_time
         real_time_factor = infer_sec / audio_duration_sec if audio_duration_sec > 0 else 0.0
         logging.info("Real-time factor: %0.2f (infer=%0.2f sec, audio=%0.2f sec)" % (real_time_factor, infer_sec, audio_duration_sec))
+        if marks:
+            return audio, self._marks(text, ends, rate)
         return audio
 
     def synth_stream(self, text, speaker_id=0, noise_level=None, speech_rate=None, duration_noise_level=None, scale=None,
-                     chunk_frames=64, sample_rate=None, denoiser_strength=None):
+                     chunk_frames=64, sample_rate=None, denoiser_strength=None, on_marks=None):
         """Generator of int16 PCM chunks (chunk_frames*256 samples each, ~0.74 s at the default): what a streaming
         `SynthesizeStream` handler would put into successive AudioChunk messages (tts_service.proto:46-54) instead
-        of the single whole-utterance chunk of tts_server.py:54.  Same conversion as synth_audio per chunk."""
+        of the single whole-utterance chunk of tts_server.py:54.  Same conversion as synth_audio per chunk.
+        on_marks: a callable that receives the utterance's marks.SpeechMarks once, before the first chunk is yielded."""
         args, scale = self._feed(text, speaker_id, noise_level, speech_rate, duration_noise_level, scale)
         self._denoiser(args, denoiser_strength)
         if not hasattr(self.model.onnx, "run_stream"):
             raise NotImplementedError("this session type has no run_stream (VitsSession: vits_stream_open, SttsSession: stts_stream_open)")
-        if sample_rate and int(sample_rate) != self.native_rate():
-            args["vits.sample_rate"] = int(sample_rate)
-        for chunk in self.model.onnx.run_stream(None, args, chunk_frames=chunk_frames):
+        rate = self.native_rate()
+        if sample_rate and int(sample_rate) != rate:
+            rate = int(sample_rate)
+            args["vits.sample_rate"] = rate
+        kw = {}
+        if on_marks is not None:
+            kw["on_marks"] = lambda ends: on_marks(self._marks(text, ends, rate))
+        for chunk in self.model.onnx.run_stream(None, args, chunk_frames=chunk_frames, **kw):
             yield self.audio_float_to_int16(chunk * scale)
 
     def synth(self, text, oname, speaker_id=0, noise_level=None, speech_rate=None, duration_noise_level=None, scale=None, sample_rate=None,
-              denoiser_strength=None):
-        audio = self.synth_audio(text, speaker_id, noise_level, speech_rate, duration_noise_level, scale, sample_rate, denoiser_strength)
+              denoiser_strength=None, marks=False):
+        """marks=True: the utterance's marks.SpeechMarks are returned (the default returns None, as the reference does)"""
+        audio = self.synth_audio(text, speaker_id, noise_level, speech_rate, duration_noise_level, scale, sample_rate, denoiser_strength, marks=marks)
+        sm = None
+        if marks:
+            audio, sm = audio
         with wave.open(oname, "w") as f:
             f.setnchannels(1)
             f.setsampwidth(2)
             f.setframerate(int(sample_rate) if sample_rate else self.native_rate())
             f.writeframes(audio.tobytes())
+        return sm
 
     def _phonemes_and_words(self, text):
         """One pass over the split text: the phoneme string ('^' ... '$', punctuation kept, dictionary or rule G2P per word) and,
