@@ -183,6 +183,11 @@ typedef struct vits_synth_opts {
   const float*   bert;             /* [B, bert_dim, T_x] or NULL: the "bert" feed of the BERT-conditioned flavours (synth.py:113-120);
                                       required when hparams.bert_dim > 0.  The shipped graphs' text encoder is not in the reference tree
                                       (SURVEY.md 8f rank 2); the wiring implemented is a 1x1 projection added to the scaled embedding. */
+  int32_t loudness_mode;      /* the five fields below are only read when flags & VITS_FLAG_LOUDNESS (include/vits_loudness.h, which defines */
+  float loudness_target;      /* the flag and the normalisation): VITS_LOUDNESS_LUFS / _PEAK, the LUFS or peak target, the LUFS mode's */
+  float loudness_ceiling;     /* cap on gain * peak (0 = none); out_loudness / out_gain: [B] or NULL, the measured integrated loudness */
+  float* out_loudness;        /* of the un-normalised item (-INFINITY for silence) and the gain applied.  Appended by the same rule */
+  float* out_gain;            /* as item_seeds */
 } vits_synth_opts;
 
 #define VITS_FLAG_NONE 0

@@ -141,9 +141,10 @@ class MultiDeviceSynth:
         a = pcm[:int(n)].copy()
         return a if ends is None else (a, ends[:int(n_tokens)].copy())
 
-    def _run_shard(self, r, token_lists, idx, sids, scales, scale, seeds, sample_rate=None, marks=False):
+    def _run_shard(self, r, token_lists, idx, sids, scales, scale, seeds, sample_rate=None, marks=False, loud=None):
         """the requests `idx` on replica r, in batches of <= max_batch (already sorted by descending length) -> list of int16 arrays
-        (marks: of (int16 array, token ends))"""
+        (marks: of (int16 array, token ends)).  loud: the loudness feeds of the batch ("vits.loudness" / "vits.peak" / "vits.peak_ceiling",
+        include/vits_loudness.h), merged into every feed; the engine normalises per item"""
         out = []
         sess = self.models[r].onnx
         for k in range(0, len(idx), self.max_batch):
@@ -151,21 +152,25 @@ class MultiDeviceSynth:
             ids, lens = pad_batch(token_lists, part)
             feed = {"input": ids, "input_lengths": lens, "scales": scales, "sid": np.array([sids[i] for i in part], np.int64),
                     "bert": None, "phone_duration_extra": None, "vits.solo": True,
-                    "vits.item_seeds": np.array([seeds[i] for i in part], np.uint64)}
+                    "vits.item_seeds": np.array([seeds[i] for i in part], np.uint64), **(loud or {})}
             with self._replica_locks[r]:  # concurrent synth_batch() calls do not interleave on one replica
                 pcm, lengths, ends = self._pcm16_marks(sess, feed, scale, sample_rate, marks)  # lengths of THIS call (not the shared attribute)
             out.extend(self._item(pcm[j], lengths[j], None if ends is None else ends[j], lens[j]) for j in range(len(part)))
         return out
 
     def synth_batch(self, texts, speaker_ids=0, noise_level=None, speech_rate=None, duration_noise_level=None, scale=None, seeds=None,
-                    sample_rate=None, denoiser_strength=None, marks=False):
+                    sample_rate=None, denoiser_strength=None, marks=False, loudness=None, peak=None, peak_ceiling=None):
         """texts: list of str -> list of int16 PCM arrays (22.05 kHz), one per request, in request order.  marks=True: a list of
         (audio, marks.SpeechMarks) per request instead (as Synth.synth_audio(..., marks=True)), through every shard path.  `seeds`: optional
         per-request noise seeds (default: a running counter), `speaker_ids`: one id or one per request.  `sample_rate`: output rate
         in Hz for the whole batch (default: the voice's own; include/vits_resample.h).  `denoiser_strength`: the vocoder-bias
         denoiser of a multistream voice for the whole batch (default: the voice's inference.denoiser_strength, else off; as
-        Synth.synth_audio, a VITS-family voice raises ValueError), every item denoised from its own length before any resampling."""
+        Synth.synth_audio, a VITS-family voice raises ValueError), every item denoised from its own length before any resampling.
+        `loudness` / `peak` / `peak_ceiling`: a LUFS or a peak target for every request of the batch (defaults and rules of
+        Synth.synth_audio): each request is measured and normalised on its own, so it equals its single call with the same seed."""
         s0 = self.synths[0]
+        loud = {}
+        s0._loudness(loud, loudness, peak, peak_ceiling)
         dn = {}
         s0._denoiser(dn, denoiser_strength)
         denoiser_strength = dn.get("vits.denoiser_strength")
@@ -174,7 +179,7 @@ class MultiDeviceSynth:
         if self.family == "vits":
             token_lists = [s0.g2p_noembed(s0.normalize(t)) for t in texts]
             return with_marks(self.synth_tokens(token_lists, speaker_ids, noise_level, speech_rate, duration_noise_level, scale, seeds, sample_rate,
-                                                marks=marks))
+                                                marks=marks, loud=loud))
         # BERT-conditioned families: the front end needs the replica's BERT encoder, so it runs on the replica that gets the request;
         # requests are sharded by a cheap length estimate (phoneme count, no BERT needed)
         n = len(texts)
@@ -186,7 +191,7 @@ class MultiDeviceSynth:
         shards = plan_shards(est, len(self.devices))
         run = self._run_shard_bert if self.family == "vits_bert" else self._run_shard_multistream
         kw = {"denoiser_strength": denoiser_strength} if self.family == "multistream" else {}
-        futs = [self._pool.submit(run, r, texts, idx, sids, scales, scale, seeds, sample_rate=sample_rate, marks=marks, **kw) if idx else None
+        futs = [self._pool.submit(run, r, texts, idx, sids, scales, scale, seeds, sample_rate=sample_rate, marks=marks, loud=loud, **kw) if idx else None
                 for r, idx in enumerate(shards)]
         return with_marks(scatter_results(n, [idx for idx in shards if idx], [f.result() for f in futs if f is not None]))
 
@@ -225,7 +230,7 @@ class MultiDeviceSynth:
             out.update(zip(rest, per_request(rest)))
         return [out[i] for i in idx]
 
-    def _run_shard_bert(self, r, texts, idx, sids, scales, scale, seeds, per_request=False, sample_rate=None, marks=False):
+    def _run_shard_bert(self, r, texts, idx, sids, scales, scale, seeds, per_request=False, sample_rate=None, marks=False, loud=None):
         """BERT-conditioned VITS requests `idx` on replica r: get_word_bert + g2p / g2p_noblank per request (synth.py:88-99), then padded
         solo batches with a padded `bert` feed [B, 768, T]"""
         synth, sess = self.synths[r], self.models[r].onnx
@@ -233,13 +238,14 @@ class MultiDeviceSynth:
             def run_part(part):
                 f = synth.front_batch([texts[i] for i in part], [sids[i] for i in part])
                 feed = {"input": f["input"], "input_lengths": f["input_lengths"], "scales": scales, "sid": f["sid"], "bert": f["bert"],
-                        "phone_duration_extra": None, "vits.solo": True, "vits.item_seeds": np.array([seeds[i] for i in part], np.uint64)}
+                        "phone_duration_extra": None, "vits.solo": True, "vits.item_seeds": np.array([seeds[i] for i in part], np.uint64),
+                        **(loud or {})}
                 with self._replica_locks[r]:
                     pcm, lengths, ends = self._pcm16_marks(sess, feed, scale, sample_rate, marks)
                 return [self._item(pcm[b], lengths[b], None if ends is None else ends[b], f["input_lengths"][b]) for b in range(len(part))]
 
             return self._run_parts(r, idx, run_part, lambda rest: self._run_shard_bert(r, texts, rest, sids, scales, scale, seeds, per_request=True,
-                                                                                      sample_rate=sample_rate, marks=marks))
+                                                                                      sample_rate=sample_rate, marks=marks, loud=loud))
         fe = synth.g2p_noblank if synth.model.config.get("no_blank", 0) != 0 else synth.g2p
         fronts = []
         for i in idx:
@@ -258,23 +264,28 @@ class MultiDeviceSynth:
                 bert[b, :, :lens[b]] = fronts[k][1]
             feed = {"input": ids, "input_lengths": lens, "scales": scales, "sid": np.array([sids[idx[k]] for k in part], np.int64),
                     "bert": bert, "phone_duration_extra": None, "vits.solo": True,
-                    "vits.item_seeds": np.array([seeds[idx[k]] for k in part], np.uint64)}
+                    "vits.item_seeds": np.array([seeds[idx[k]] for k in part], np.uint64), **(loud or {})}
             with self._replica_locks[r]:
                 pcm, lengths, ends = self._pcm16_marks(sess, feed, scale, sample_rate, marks)
             for b, k in enumerate(part):
                 out[k] = self._item(pcm[b], lengths[b], None if ends is None else ends[b], lens[b])
         return out
 
-    def _stts_batch(self, sess, args, kw, sample_rate, marks):
+    def _stts_batch(self, sess, args, kw, sample_rate, marks, loud=None):
         """stts_synthesize_batch of one padded part -> (audio, lengths, token_ends or None) at `sample_rate`; with marks the call takes
-        the rate itself (stts_synthesize_batch_marks)"""
+        the rate itself (stts_synthesize_batch_marks).  loud: the loudness feeds; every item is normalised last, behind the resampler"""
+        spec = sess._loudness(loud or {})
         if marks:
-            return sess._model.synthesize_batch(*args, marks=True, sample_rate=sess._rate(sample_rate), **kw)
-        audio, ol = sess._model.synthesize_batch(*args, **kw)
-        return sess.resample(audio, ol, sample_rate) + (None,)
+            return sess._model.synthesize_batch(*args, marks=True, sample_rate=sess._rate(sample_rate), loudness=spec, **kw)
+        rate = sess._rate(sample_rate)
+        audio, ol = sess._model.synthesize_batch(*args, loudness=None if rate else spec, **kw)
+        if not rate:
+            return audio, ol, None
+        audio, ol = sess.resample(audio, ol, rate)
+        return sess.normalize(audio, ol, rate, spec), ol, None
 
     def _run_shard_multistream(self, r, texts, idx, sids, scales, scale, seeds, per_request=False, sample_rate=None, denoiser_strength=None,
-                               marks=False):
+                               marks=False, loud=None):
         """multistream (StableTTS / Matcha) requests `idx` on replica r: the five-stream front end of Synth._feed per request
         (synth.py:64-87), then stts_synthesize_batch with per-request seeds (and the denoiser, where a strength is given);
         float -> int16 as Synth.audio_float_to_int16"""
@@ -285,13 +296,13 @@ class MultiDeviceSynth:
                 with self._replica_locks[r]:
                     audio, ol, ends = self._stts_batch(
                         sess, (f["input"], f["input_lengths"], scales, f["sid"], f["bert"], f["phone_duration_extra"]),
-                        dict(seed=0, item_seeds=np.array([seeds[i] for i in part], np.uint64), denoiser_strength=denoiser_strength), sample_rate, marks)
+                        dict(seed=0, item_seeds=np.array([seeds[i] for i in part], np.uint64), denoiser_strength=denoiser_strength), sample_rate, marks, loud)
                 pcm = [synth.audio_float_to_int16(audio[b, :int(ol[b])] * scale) for b in range(len(part))]
                 return pcm if ends is None else [(pcm[b], ends[b, :int(f["input_lengths"][b])].copy()) for b in range(len(part))]
 
             return self._run_parts(r, idx, run_part, lambda rest: self._run_shard_multistream(r, texts, rest, sids, scales, scale, seeds, per_request=True,
                                                                                              sample_rate=sample_rate, denoiser_strength=denoiser_strength,
-                                                                                             marks=marks))
+                                                                                             marks=marks, loud=loud))
         fronts = []
         for i in idx:
             feed, _ = synth._feed(texts[i], sids[i], None, None, None, None)
@@ -315,7 +326,7 @@ class MultiDeviceSynth:
             with self._replica_locks[r]:
                 audio, ol, ends = self._stts_batch(
                     sess, (ids, lens, scales, np.array([sids[idx[k]] for k in part], np.int64), bert, pde),
-                    dict(seed=0, item_seeds=np.array([seeds[idx[k]] for k in part], np.uint64), denoiser_strength=denoiser_strength), sample_rate, marks)
+                    dict(seed=0, item_seeds=np.array([seeds[idx[k]] for k in part], np.uint64), denoiser_strength=denoiser_strength), sample_rate, marks, loud)
             for b, k in enumerate(part):
                 out[k] = synth.audio_float_to_int16(audio[b, :int(ol[b])] * scale)
                 if ends is not None:
@@ -323,9 +334,9 @@ class MultiDeviceSynth:
         return out
 
     def synth_tokens(self, token_lists, speaker_ids=0, noise_level=None, speech_rate=None, duration_noise_level=None, scale=None, seeds=None,
-                     sample_rate=None, marks=False):
+                     sample_rate=None, marks=False, loud=None):
         """synth_batch() behind the front end: token id lists in, int16 PCM arrays out (request order).  marks=True: (PCM, token ends
-        int64 [len(tokens)] in output samples) per request."""
+        int64 [len(tokens)] in output samples) per request.  loud: the loudness feeds of the batch (Synth._loudness)."""
         n = len(token_lists)
         if n == 0:
             return []
@@ -333,6 +344,6 @@ class MultiDeviceSynth:
             raise NotImplementedError("synth_tokens takes plain VITS token ids; BERT-conditioned and multistream voices need the text (synth_batch)")
         scales, scale, sids, seeds = self._call_params(n, speaker_ids, noise_level, speech_rate, duration_noise_level, scale, seeds)
         shards = plan_shards([len(t) for t in token_lists], len(self.devices))
-        futs = [self._pool.submit(self._run_shard, r, token_lists, idx, sids, scales, scale, seeds, sample_rate, marks) if idx else None
+        futs = [self._pool.submit(self._run_shard, r, token_lists, idx, sids, scales, scale, seeds, sample_rate, marks, loud) if idx else None
                 for r, idx in enumerate(shards)]
         return scatter_results(n, [idx for idx in shards if idx], [f.result() for f in futs if f is not None])

@@ -34,7 +34,58 @@ class SynthOpts(ctypes.Structure):
         ("flags", ctypes.c_int32),
         ("item_seeds", ctypes.POINTER(ctypes.c_uint64)),
         ("bert", c_f32p),
+        # include/vits_loudness.h: read only under VITS_FLAG_LOUDNESS
+        ("loudness_mode", ctypes.c_int32),
+        ("loudness_target", ctypes.c_float),
+        ("loudness_ceiling", ctypes.c_float),
+        ("out_loudness", c_f32p),
+        ("out_gain", c_f32p),
     ]
+
+
+# include/vits_loudness.h
+FLAG_LOUDNESS = 2       # VITS_FLAG_LOUDNESS
+LOUDNESS_LUFS = 1       # VITS_LOUDNESS_LUFS
+LOUDNESS_PEAK = 2       # VITS_LOUDNESS_PEAK
+LOUDNESS_MIN_RATE = 4000
+
+
+def loudness_spec(loudness=None, peak=None, peak_ceiling=None):
+    """The normalisation a call asks for -> None (none) or (mode, target, ceiling) as vits_synth_opts carries it.  loudness: a LUFS
+    target (BS.1770 integrated loudness) with peak_ceiling as the cap on the resulting peak (default 1.0: an int16 result never clips
+    harder than it did; 0 = no cap); peak: a max-|sample| target.  Both at once is a ValueError, as is a value out of range (the
+    library refuses the same values, VITS_ERR_ARG: here they are refused before any device work)."""
+    if loudness is not None and peak is not None:
+        raise ValueError(f"loudness={loudness} and peak={peak}: a request is normalised to a LUFS target or to a peak target, not both")
+    if loudness is not None:
+        t, c = float(loudness), 1.0 if peak_ceiling is None else float(peak_ceiling)
+        if not -70.0 <= t <= 0.0:
+            raise ValueError(f"loudness target {t} LUFS outside [-70, 0]")
+        if not 0.0 <= c < float("inf"):
+            raise ValueError(f"peak_ceiling {c} must be >= 0 (0 = none)")
+        return (LOUDNESS_LUFS, t, c)
+    if peak is not None:
+        t = float(peak)
+        if not 0.0 < t <= 1.0:
+            raise ValueError(f"peak target {t} outside (0, 1]")
+        return (LOUDNESS_PEAK, t, 0.0)
+    return None
+
+
+def set_loudness(opts, keep, spec, B, flag, out=None):
+    """Fills the loudness fields of a SynthOpts / SttsOpts and sets `flag`; the [B] result arrays are kept alive in `keep` and, when
+    `out` is a dict, published there as out["loudness"] (LUFS of the un-normalised item, -inf for silence) and out["gain"]."""
+    if spec is None:
+        return
+    mode, target, ceiling = spec
+    loud = np.full(B, np.nan, np.float32)
+    gain = np.full(B, np.nan, np.float32)
+    keep += [loud, gain]
+    opts.flags |= flag
+    opts.loudness_mode, opts.loudness_target, opts.loudness_ceiling = int(mode), float(target), float(ceiling)
+    opts.out_loudness, opts.out_gain = _p(loud, c_f32p), _p(gain, c_f32p)
+    if out is not None:
+        out["loudness"], out["gain"] = loud, gain
 
 
 class PersistInfo(ctypes.Structure):
@@ -115,6 +166,7 @@ class VitsLib:
         self.has_resample = False
         self.has_denoise = False
         self.has_marks = False
+        self.has_loudness = False
         if self.is_device:
             c_i16p = ctypes.POINTER(ctypes.c_int16)
             f("synthesize_pcm16").argtypes = [ctypes.c_void_p, c_i64p, c_i64p, ctypes.c_int32, ctypes.c_int32, c_f32p, c_i64p,
@@ -174,6 +226,13 @@ class VitsLib:
                                                         ctypes.POINTER(SynthOpts), ctypes.c_float, ctypes.c_int32,
                                                         ctypes.POINTER(c_i16p), c_i64p, c_i64p, c_i64p]
                 f("stream_marks").argtypes = [ctypes.c_void_p, c_i64p, ctypes.c_int32, c_i32p]
+            # include/vits_loudness.h: loudness normalisation, an extension of the product library like the three above
+            self.has_loudness = self.has("op_loudness")
+            if self.has_loudness:
+                f("loudness_plan").argtypes = [ctypes.c_int32, ctypes.POINTER(ctypes.c_double), c_i32p]
+                f("op_loudness").argtypes = [ctypes.c_int, c_f32p, c_i64p, ctypes.c_int32, ctypes.c_int64, ctypes.c_int32, c_f32p, c_f32p]
+                f("op_loudness_normalize").argtypes = [ctypes.c_int, c_f32p, c_i64p, ctypes.c_int32, ctypes.c_int64, ctypes.c_int32,
+                                                       ctypes.c_int32, ctypes.c_float, ctypes.c_float, c_f32p, c_f32p, c_f32p]
             if self.has("debug_clock_probe"):
                 f("debug_clock_probe").argtypes = [ctypes.c_int, ctypes.c_int32, ctypes.POINTER(ctypes.c_double), ctypes.c_int32]
 
@@ -321,6 +380,49 @@ class VitsLib:
         self.check(self._fn("op_denoise")(device, _p(x, c_f32p), _p(lengths, c_i64p), B, N, _p(bias, c_f32p), n, float(strength), _p(y, c_f32p)))
         return y
 
+    # ---- loudness normalisation (include/vits_loudness.h) --------------------
+    def _need_loudness(self):
+        if not self.has_loudness:
+            raise VitsError(4, "this backend has no loudness normalisation (include/vits_loudness.h)")
+
+    def loudness_plan(self, rate):
+        """vits_loudness_plan (host only): (sos float64 [2, 6] = rows of b0 b1 b2 1 a1 a2, hop); VitsError(4) names a refused rate"""
+        self._need_loudness()
+        sos = np.zeros((2, 6), np.float64)
+        hop = ctypes.c_int32()
+        self.check(self._fn("loudness_plan")(int(rate), sos.ctypes.data_as(ctypes.POINTER(ctypes.c_double)), ctypes.byref(hop)))
+        return sos, hop.value
+
+    def _loud_args(self, x, lengths):
+        x = _f32(x)
+        if x.ndim != 2:
+            raise ValueError("x must be [B, N]")
+        lengths = _i64(lengths).reshape(-1)
+        if lengths.shape != (x.shape[0],):
+            raise ValueError("lengths must be [B]")
+        return x, lengths
+
+    def op_loudness(self, x, lengths, rate, device=0):
+        """vits_op_loudness: x float32 [B, N], lengths [B] -> (loudness float32 [B] in LUFS, -inf for silence; peak float32 [B]);
+        item b from x[b, :lengths[b]] only"""
+        self._need_loudness()
+        x, lengths = self._loud_args(x, lengths)
+        B, N = x.shape
+        loud, peak = np.empty(B, np.float32), np.empty(B, np.float32)
+        self.check(self._fn("op_loudness")(device, _p(x, c_f32p), _p(lengths, c_i64p), B, N, int(rate), _p(loud, c_f32p), _p(peak, c_f32p)))
+        return loud, peak
+
+    def op_loudness_normalize(self, x, lengths, rate, mode, target, ceiling=0.0, device=0):
+        """vits_op_loudness_normalize -> (y float32 [B, N] = gain[b] * x[b], zero at and beyond lengths[b]; loudness [B]; gain [B])"""
+        self._need_loudness()
+        x, lengths = self._loud_args(x, lengths)
+        B, N = x.shape
+        y = np.empty((B, N), np.float32)
+        loud, gain = np.empty(B, np.float32), np.empty(B, np.float32)
+        self.check(self._fn("op_loudness_normalize")(device, _p(x, c_f32p), _p(lengths, c_i64p), B, N, int(rate), int(mode), float(target),
+                                                     float(ceiling), _p(y, c_f32p), _p(loud, c_f32p), _p(gain, c_f32p)))
+        return y, loud, gain
+
     def mas_maximum_path(self, values, t_ys, t_xs, device=0):
         """monotonic_align.maximum_path_c (core.pyx:35-42): values float32 [B,T_y,T_x] -> paths int32 [B,T_y,T_x]."""
         values = _f32(values)
@@ -366,9 +468,12 @@ class VitsModel:
         except Exception:
             pass
 
-    def _opts(self, B, Tx, noise_dp, noise_prior, forced_durations, seed, max_frames, solo=False, item_seeds=None, bert=None):
+    def _opts(self, B, Tx, noise_dp, noise_prior, forced_durations, seed, max_frames, solo=False, item_seeds=None, bert=None,
+              loudness=None, loudness_out=None):
         opts = SynthOpts()
         keep = []
+        if loudness is not None:
+            self.lib._need_loudness()
         if bert is not None:
             a = _f32(bert); keep.append(a)
             if a.shape != (B, self.hp.bert_dim, Tx):
@@ -398,6 +503,7 @@ class VitsModel:
         opts.seed = seed
         opts.max_frames = max_frames
         opts.flags = 1 if solo else 0  # VITS_FLAG_SOLO_BATCH
+        set_loudness(opts, keep, loudness, B, FLAG_LOUDNESS, loudness_out)
         return opts, keep
 
     # ---- the hot path -----------------------------------------------------
@@ -411,11 +517,13 @@ class VitsModel:
         return rate
 
     def synthesize(self, ids, lengths, scales, sid, noise_dp=None, noise_prior=None, forced_durations=None, seed=0,
-                   max_frames=0, solo=False, item_seeds=None, bert=None, sample_rate=None, marks=False):
+                   max_frames=0, solo=False, item_seeds=None, bert=None, sample_rate=None, marks=False, loudness=None, loudness_out=None):
         """One .run(): returns (audio float32 [B,S], out_lengths int64 [B]); with marks=True (vits_synthesize_marks) a third value,
         token_ends int64 [B,T_x] in output samples (include/vits_marks.h).  solo=True (VITS_FLAG_SOLO_BATCH): every
         item equals its own single-utterance call with seed + b instead of the reference's padded-batch result.
-        sample_rate: output rate in Hz (vits_synthesize_rate; S and out_lengths are then in output samples)."""
+        sample_rate: output rate in Hz (vits_synthesize_rate; S and out_lengths are then in output samples).
+        loudness: a loudness_spec() (VITS_FLAG_LOUDNESS, include/vits_loudness.h): every item normalised on the device, last in the
+        chain; loudness_out: a dict that receives "loudness" (LUFS of each un-normalised item) and "gain" float32 [B]."""
         ids = _i64(ids)
         B, Tx = ids.shape
         lengths = _i64(lengths)
@@ -423,7 +531,7 @@ class VitsModel:
         scales = _f32(scales)
         if lengths.shape != (B,) or sid.shape != (B,) or scales.shape != (3,):
             raise ValueError("bad feed shapes")
-        opts, keep = self._opts(B, Tx, noise_dp, noise_prior, forced_durations, seed, max_frames, solo, item_seeds, bert)
+        opts, keep = self._opts(B, Tx, noise_dp, noise_prior, forced_durations, seed, max_frames, solo, item_seeds, bert, loudness, loudness_out)
         out = c_f32p()
         ns = ctypes.c_int64()
         olen = np.zeros(B, dtype=np.int64)
@@ -450,16 +558,18 @@ class VitsModel:
         return (audio, olen, ends) if marks else (audio, olen)
 
     def synthesize_pcm16(self, ids, lengths, scales, sid, pcm_scale=1.0, noise_dp=None, noise_prior=None, forced_durations=None,
-                         seed=0, max_frames=0, solo=False, item_seeds=None, bert=None, sample_rate=None, marks=False):
+                         seed=0, max_frames=0, solo=False, item_seeds=None, bert=None, sample_rate=None, marks=False, loudness=None,
+                         loudness_out=None):
         """synthesize() with Synth.synth_audio's `* scale` and audio_float_to_int16 (vosk_tts/synth.py:127-130) done on the
         device: returns (pcm int16 [B,S], out_lengths int64 [B]).  sample_rate: as for synthesize (vits_synthesize_pcm16_rate:
-        the resampler does the conversion in its epilogue)."""
+        the resampler does the conversion in its epilogue).  loudness / loudness_out: as for synthesize (pcm_scale multiplies the
+        normalised audio, as before)."""
         ids = _i64(ids)
         B, Tx = ids.shape
         lengths = _i64(lengths); sid = _i64(sid); scales = _f32(scales)
         if lengths.shape != (B,) or sid.shape != (B,) or scales.shape != (3,):
             raise ValueError("bad feed shapes")
-        opts, keep = self._opts(B, Tx, noise_dp, noise_prior, forced_durations, seed, max_frames, solo, item_seeds, bert)
+        opts, keep = self._opts(B, Tx, noise_dp, noise_prior, forced_durations, seed, max_frames, solo, item_seeds, bert, loudness, loudness_out)
         out = ctypes.POINTER(ctypes.c_int16)()
         ns = ctypes.c_int64()
         olen = np.zeros(B, dtype=np.int64)
@@ -488,13 +598,16 @@ class VitsModel:
         return (pcm, olen, ends) if marks else (pcm, olen)
 
     def stream(self, ids, scales, sid, chunk_frames=64, noise_dp=None, noise_prior=None, forced_durations=None, seed=0, bert=None,
-               sample_rate=None, on_marks=None):
+               sample_rate=None, on_marks=None, loudness=None):
         """Streaming synthesis of ONE utterance (vits_stream_*): a generator of float32 chunks of
         chunk_frames*hop_length samples (the last one shorter); their concatenation equals synthesize().
         sample_rate: output rate in Hz (vits_stream_open_rate): the chunk that covers input samples [a, b) holds the outputs
         ceil(a*L/M) <= n < ceil(b*L/M), so chunk sizes vary by one sample.
         on_marks: called once with token_ends int64 [T_x] (vits_stream_marks, the stream's own output samples) as soon as the
         stream is open, before the first chunk."""
+        if loudness is not None:  # (vits_stream_open* refuse VITS_FLAG_LOUDNESS the same way; here before any device work)
+            raise VitsError(4, "a stream cannot be loudness-normalised: an integrated-loudness or peak target needs the whole utterance "
+                               "before the first chunk")
         if on_marks is not None:
             self.lib._need_marks()
         if not self.lib.has("stream_open"):

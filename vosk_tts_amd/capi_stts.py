@@ -5,7 +5,7 @@ import ctypes
 
 import numpy as np
 
-from .capi import VitsError, VitsLib, _f32, _i32, _i64, _p, c_f32p, c_i32p, c_i64p
+from .capi import VitsError, VitsLib, _f32, _i32, _i64, _p, c_f32p, c_i32p, c_i64p, set_loudness
 from .weights_stts import SttsHParams
 
 
@@ -17,6 +17,17 @@ class SttsOpts(ctypes.Structure):
     _fields_ = [("noise", c_f32p), ("noise_stride", ctypes.c_int64), ("seed", ctypes.c_uint64),
                 ("n_timesteps", ctypes.c_int32), ("flags", ctypes.c_int32), ("item_seeds", ctypes.POINTER(ctypes.c_uint64)),
                 ("denoiser_strength", ctypes.c_float), ("denoiser_filter_length", ctypes.c_int32)]
+
+
+class SttsLoudnessOpts(SttsOpts):
+    """mirror of `struct stts_synth_opts_loudness` (include/vits_loudness.h): SttsOpts followed by the five loudness fields, which the
+    library reads only under STTS_FLAG_LOUDNESS; passed where a POINTER(SttsOpts) is declared"""
+
+    _fields_ = [("loudness_mode", ctypes.c_int32), ("loudness_target", ctypes.c_float), ("loudness_ceiling", ctypes.c_float),
+                ("out_loudness", c_f32p), ("out_gain", c_f32p)]
+
+
+STTS_FLAG_LOUDNESS = 4    # include/vits_loudness.h
 
 
 class SttsModel:
@@ -89,17 +100,29 @@ class SttsModel:
         opts.denoiser_strength = float(denoiser_strength)
         opts.denoiser_filter_length = int(denoiser_filter_length or 0)
 
+    def _loudness(self, opts, keep, spec, B, out):
+        """STTS_FLAG_LOUDNESS and its fields (include/vits_loudness.h; spec = capi.loudness_spec(), None = off).  Only the device library
+        normalises: the CPU oracle would ignore the flag, which is refused here instead.  `opts` must then be a SttsLoudnessOpts"""
+        if spec is None:
+            return
+        assert isinstance(opts, SttsLoudnessOpts)
+        if not getattr(self.vlib, "has_loudness", False):
+            raise VitsError(4, "this backend has no loudness normalisation (include/vits_loudness.h)")
+        set_loudness(opts, keep, spec, B, STTS_FLAG_LOUDNESS, out)
+
     def _need_marks(self):
         if not self.has_marks:
             raise VitsError(4, "this backend has no speech marks (include/vits_marks.h): the CPU oracle returns audio only")
 
     # ---- hot path ----------------------------------------------------------------------------
     def synthesize(self, ids, scales, sid, bert=None, phone_duration_extra=None, noise=None, seed=0, n_timesteps=0,
-                   want_audio=True, want_mel=True, denoiser_strength=None, denoiser_filter_length=0, marks=False, sample_rate=None):
+                   want_audio=True, want_mel=True, denoiser_strength=None, denoiser_filter_length=0, marks=False, sample_rate=None,
+                   loudness=None, loudness_out=None):
         """One utterance.  ids int64 [5,T]; returns (audio float32 [S] or None, mel float32 [n_feats,T_y] or None).
         denoiser_strength (None = off) / denoiser_filter_length (0 = 1024): the vocoder-bias denoiser behind the clamp.
         marks=True (stts_synthesize_marks): a third value, token_ends int64 [T]; audio and marks are then at `sample_rate`
-        (None / 0 = the voice's own)."""
+        (None / 0 = the voice's own).  loudness: a capi.loudness_spec() (STTS_FLAG_LOUDNESS): the audio normalised last in the chain
+        (after the denoiser and, in the marks call, the resampler); loudness_out: a dict that receives "loudness" and "gain" [1]."""
         if marks:
             self._need_marks()
         elif sample_rate:
@@ -110,7 +133,7 @@ class SttsModel:
         T = ids.shape[1]
         scales = _f32(scales)
         keep = []
-        opts = SttsOpts()
+        opts = SttsOpts() if loudness is None else SttsLoudnessOpts()
         if noise is not None:
             a = _f32(noise); keep.append(a)
             if a.ndim != 2 or a.shape[0] != self.hp.n_feats:
@@ -120,6 +143,8 @@ class SttsModel:
         opts.seed = seed
         opts.n_timesteps = n_timesteps
         self._denoise(opts, denoiser_strength, denoiser_filter_length)
+        if want_audio:
+            self._loudness(opts, keep, loudness, 1, loudness_out)
         b = None if bert is None else _f32(bert)
         if b is not None and b.shape != (self.hp.bert_dim, T):
             raise ValueError("bert must be [768, T]")
@@ -146,10 +171,14 @@ class SttsModel:
         return (audio, melo, ends) if marks else (audio, melo)
 
     def stream(self, ids, scales, sid, bert=None, phone_duration_extra=None, seed=0, n_timesteps=0, chunk_frames=64,
-               denoiser_strength=None, denoiser_filter_length=0, on_marks=None):
+               denoiser_strength=None, denoiser_filter_length=0, on_marks=None, loudness=None):
         """Streaming form of synthesize() (stts_stream_open): a generator of float32 chunks of chunk_frames*hop samples whose
         concatenation equals synthesize()'s audio for the same arguments.  on_marks: called once with token_ends int64 [T]
-        (vits_stream_marks) as soon as the stream is open."""
+        (vits_stream_marks) as soon as the stream is open.  loudness: refused (stts_stream_open refuses STTS_FLAG_LOUDNESS the same
+        way; here before any device work)."""
+        if loudness is not None:
+            raise VitsError(4, "a stream cannot be loudness-normalised: an integrated-loudness or peak target needs the whole utterance "
+                               "before the first chunk")
         if on_marks is not None:
             self._need_marks()
         if self._vocoder is None:
@@ -182,7 +211,7 @@ class SttsModel:
         return self._vocoder._drain(st, chunk_frames)
 
     def synthesize_batch(self, ids, lengths, scales, sid, bert=None, phone_duration_extra=None, seed=0, n_timesteps=0, item_seeds=None,
-                         denoiser_strength=None, denoiser_filter_length=0, marks=False, sample_rate=None):
+                         denoiser_strength=None, denoiser_filter_length=0, marks=False, sample_rate=None, loudness=None, loudness_out=None):
         """B independent utterances in one pass (stts_synthesize_batch): ids [B,5,T], lengths [B], sid [B];
         returns (audio float32 [B,S] zero-padded, out_lengths int64 [B] in samples).  Item b equals
         synthesize(ids[b][:, :lengths[b]], ..., seed=item_seeds[b]) (seed + b without item seeds).  marks=True
@@ -195,8 +224,11 @@ class SttsModel:
         B, five, T = ids.shape
         b = None if bert is None else _f32(bert)
         p = None if phone_duration_extra is None else _f32(phone_duration_extra)
-        opts = SttsOpts(); opts.seed = seed; opts.n_timesteps = n_timesteps
+        opts = SttsOpts() if loudness is None else SttsLoudnessOpts()
+        opts.seed = seed; opts.n_timesteps = n_timesteps
         self._denoise(opts, denoiser_strength, denoiser_filter_length)
+        keep = []
+        self._loudness(opts, keep, loudness, B, loudness_out)  # (per-item gains; loudness_out as for synthesize, [B])
         if item_seeds is not None:
             sd = np.ascontiguousarray(item_seeds, dtype=np.uint64)
             if sd.shape != (B,):

@@ -28,6 +28,11 @@ _OPTIONS = (
     (("--denoiser-strength",), dict(type=float, default=None, metavar="S",
                                     help="vocoder-bias denoiser of a multistream voice (the StableTTS script's default is 0.00025; default here: "
                                          "the voice's inference.denoiser_strength, else off)")),
+    (("--loudness",), dict(type=float, default=None, metavar="LUFS",
+                           help="normalise the audio to this ITU-R BS.1770 integrated loudness, e.g. -19 (default: the voice's "
+                                "inference.loudness, else off)")),
+    (("--peak",), dict(type=float, default=None, metavar="P",
+                       help="normalise the audio to this peak in (0, 1] instead (not together with --loudness)")),
     (("--marks",), dict(type=str, default=None, metavar="FILE",
                         help="also write the speech marks as JSON: rate, phonemes and words with their offsets in samples and seconds")),
     (("--log-level",), dict(default="INFO", metavar="LEVEL", help="python logging level (INFO shows the RTF line)")),
@@ -56,7 +61,7 @@ def run(opts):
 
     voice = model_mod.Model(opts.model, opts.model_name, opts.lang)
     marks = Synth(voice).synth(opts.input, opts.output, opts.speaker, speech_rate=opts.speech_rate, sample_rate=opts.sample_rate,
-                               denoiser_strength=opts.denoiser_strength, marks=bool(opts.marks))
+                               denoiser_strength=opts.denoiser_strength, marks=bool(opts.marks), loudness=opts.loudness, peak=opts.peak)
     if opts.marks:
         with open(opts.marks, "w", encoding="utf-8") as f:
             f.write(marks.to_json(indent=1) + "\n")

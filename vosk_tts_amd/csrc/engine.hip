@@ -123,6 +123,7 @@ static int persist_cfg() {
 #include "engine_stages.hip.h"
 #include "resample.hip.h"
 #include "denoise.hip.h"
+#include "loudness.hip.h"
 #include "marks.hip.h"
 
 // ------------------------------------------------------------------------------------ C ABI

@@ -34,7 +34,8 @@ static size_t fast_cache_cap() {
 static size_t session_device_bytes(const vits_session* s) {
   size_t n = s->arena_bytes + s->io_bytes + s->out_elems * (sizeof(float) + sizeof(int16_t));
   if (s->marks_d) n += sizeof(long long) * (size_t)s->B * s->Tx;
-  for (auto& kv : s->rates) n += (size_t)s->B * kv.second.n_cap * sizeof(float);
+  for (auto& kv : s->rates) n += (size_t)s->B * kv.second.n_cap * sizeof(float) + loud_ws_bytes(kv.second.lw);
+  n += loud_ws_bytes(s->lw);
   for (auto& kv : s->backs) n += session_device_bytes(kv.second);
   return n;
 }
@@ -162,6 +163,7 @@ static int back_rate_get(vits_session* F, vits_session* Bk, const ResampleTab& T
     for (hipGraphExec_t g : it->second.g2) if (g) hipGraphExecDestroy(g);
     if (it->second.y_d) hipFree(it->second.y_d);
     if (it->second.y_h) hipHostFree(it->second.y_h);
+    loud_ws_delete(it->second.lw);
     Bk->rates.erase(it);
   };
   auto it = Bk->rates.find(T.P.rate_out);
@@ -306,7 +308,7 @@ static int device_error_word(int e) {
 
 static int synth_fast(vits_model* m, const int64_t* ids, const int64_t* lengths, int32_t B, int32_t Tx, const float* scales,
                       const int64_t* sid, const vits_synth_opts* opts, bool pcm, float pcm_scale, int rate, void** out, int64_t* out_samples,
-                      int64_t* out_lengths, int64_t* token_ends) {
+                      int64_t* out_lengths, int64_t* token_ends, const LoudReq& lq) {
   const vits_hparams& hp = m->hp;
   HIP_TRY(hipSetDevice(m->device));
   const ResampleTab* T = nullptr;  // (uploaded on the first call at this rate, before any capture)
@@ -399,10 +401,27 @@ static int synth_fast(vits_model* m, const int64_t* ids, const int64_t* lengths,
   }
   vits_session::RateOut* R = nullptr;
   if (T) TRY(back_rate_get(F, Bk, *T, &R));
-  TRY(phase2_launch(F, Bk, solo, pcm, R, T));
   // (sizes in output samples)
   const int64_t S = T ? T->P.n_out(Ty * hp.hop_length) : Ty * hp.hop_length, stride = R ? R->n_cap : (int64_t)TyB * hp.hop_length;
   const char* src_h = R ? R->y_h : Bk->out_h;
+  if (lq.on) {
+    // include/vits_loudness.h: the float form of the graph as it is, then the measurement and the gain behind it on the same stream,
+    // from the finished waveform on the device (the graph's own copy of the un-normalised float audio to the host is not used)
+    LoudWs** pw = R ? &R->lw : &Bk->lw;
+    TRY(loud_ws_ensure(pw, B, stride));  // (the first flagged request of this context allocates, before anything is launched)
+    const LoudWs& W = **pw;
+    TRY(phase2_launch(F, Bk, solo, false, R, T));
+    const float* x_d = R ? static_cast<const float*>(R->y_d) : Bk->out_d;
+    const int rL = T ? T->P.L : 1, rM = T ? T->P.M : 1;
+    loud_measure_launch(F->stream, lq.P, lq.prm, W.S, x_d, stride, stride, Bk->len_y, hp.hop_length, rL, rM, B, Bk);
+    if (pcm) loud_apply_launch<int16_t>(F->stream, W.S, x_d, stride, stride, Bk->len_y, hp.hop_length, rL, rM, B, static_cast<int16_t*>(W.y_d()), stride, stride, pcm_scale, Bk);
+    else loud_apply_launch<float>(F->stream, W.S, x_d, stride, stride, Bk->len_y, hp.hop_length, rL, rM, B, static_cast<float*>(W.y_d()), stride, stride, 1.f, Bk);
+    hipMemcpyAsync(W.y_h(), W.y_d(), (size_t)B * stride * (pcm ? sizeof(int16_t) : sizeof(float)), hipMemcpyDeviceToHost, F->stream);
+    hipMemcpyAsync(W.res_h(), W.S.res, sizeof(float) * 4 * (size_t)B, hipMemcpyDeviceToHost, F->stream);
+    src_h = W.y_h();
+  } else {
+    TRY(phase2_launch(F, Bk, solo, pcm, R, T));
+  }
   const size_t esz = pcm ? sizeof(int16_t) : sizeof(float);
   char* h_out = static_cast<char*>(malloc(esz * (size_t)B * S));
   if (!h_out) { hipStreamSynchronize(F->stream); return fail(VITS_ERR_NOMEM, "host alloc failed"); }
@@ -417,6 +436,7 @@ static int synth_fast(vits_model* m, const int64_t* ids, const int64_t* lengths,
     return device_error_word(e2);
   }
   for (int b = 0; b < B; ++b) memcpy(h_out + esz * (size_t)b * S, src_h + esz * (size_t)b * stride, esz * (size_t)S);
+  if (lq.on) loud_req_results(lq, (R ? R->lw : Bk->lw)->res_h(), B);
   *out = h_out;
   *out_samples = S;
   if (out_lengths) for (int b = 0; b < B; ++b) out_lengths[b] = T ? T->P.n_out(F->h_ylen[b] * hp.hop_length) : F->h_ylen[b] * hp.hop_length;
@@ -426,7 +446,7 @@ static int synth_fast(vits_model* m, const int64_t* ids, const int64_t* lengths,
 
 static int synth_eager(vits_model* m, const int64_t* ids, const int64_t* lengths, int32_t B, int32_t Tx, const float* scales,
                        const int64_t* sid, const vits_synth_opts* opts, bool pcm, float pcm_scale, int rate, void** out, int64_t* out_samples,
-                       int64_t* out_lengths, int64_t* token_ends) {
+                       int64_t* out_lengths, int64_t* token_ends, const LoudReq& lq) {
   const vits_hparams& hp = m->hp;
   const ResampleTab* T = nullptr;
   if (rate) TRY(resample_get(m->device, hp.sampling_rate, rate, &T));
@@ -449,7 +469,29 @@ static int synth_eager(vits_model* m, const int64_t* ids, const int64_t* lengths
   const size_t esz = pcm ? sizeof(int16_t) : sizeof(float);
   const void* d_src = d_audio;
   const int64_t So = T ? T->P.n_out(S) : S;  // samples per item as returned
-  if (T) {  // item b from its own [0, len) of d_audio; at int16 in place of pcm16_kernel
+  std::vector<float> loud_res;
+  if (lq.on) {  // include/vits_loudness.h: the float waveform at the rate it is returned at, measured, then the gain (and the conversion)
+    const float* x_d = d_audio;
+    if (T) {
+      float* d_y = hs.dev_alloc<float>((size_t)B * So);
+      if (!d_y) return fail(VITS_ERR_NOMEM, "device alloc failed");
+      ProfScope ps(s, "out.resample", 2.0 * B * So * T->P.taps, "resample_kernel<float>");
+      resample_launch<float>(s->stream, *T, d_audio, S, 0, S, s->len_y, hp.hop_length, B, d_y, So, 0, So, 1.f, nullptr);
+      x_d = d_y;
+    }
+    char* d_scr = static_cast<char*>(hs.raw_alloc(loud_scratch_bytes(B, So)));
+    void* d_n = hs.raw_alloc(esz * (size_t)B * So);
+    if (!d_scr || !d_n) return fail(VITS_ERR_NOMEM, "device alloc failed");
+    LoudScratch LS;
+    loud_scratch_layout(B, So, d_scr, &LS);
+    const int rL = T ? T->P.L : 1, rM = T ? T->P.M : 1;
+    loud_measure_launch(s->stream, lq.P, lq.prm, LS, x_d, So, So, s->len_y, hp.hop_length, rL, rM, B, s);
+    if (pcm) loud_apply_launch<int16_t>(s->stream, LS, x_d, So, So, s->len_y, hp.hop_length, rL, rM, B, static_cast<int16_t*>(d_n), So, So, pcm_scale, s);
+    else loud_apply_launch<float>(s->stream, LS, x_d, So, So, s->len_y, hp.hop_length, rL, rM, B, static_cast<float*>(d_n), So, So, 1.f, s);
+    loud_res.resize((size_t)B * 4);
+    hipMemcpyAsync(loud_res.data(), LS.res, sizeof(float) * loud_res.size(), hipMemcpyDeviceToHost, s->stream);
+    d_src = d_n;
+  } else if (T) {  // item b from its own [0, len) of d_audio; at int16 in place of pcm16_kernel
     void* d_y = hs.raw_alloc(esz * (size_t)B * So);
     if (!d_y) return fail(VITS_ERR_NOMEM, "device alloc failed");
     ProfScope ps(s, "out.resample", 2.0 * B * So * T->P.taps, pcm ? "resample_kernel<int16>" : "resample_kernel<float>");
@@ -469,6 +511,7 @@ static int synth_eager(vits_model* m, const int64_t* ids, const int64_t* lengths
   hipError_t e = hipMemcpyAsync(h_out, d_src, esz * (size_t)B * So, hipMemcpyDeviceToHost, s->stream);
   int rc = e == hipSuccess ? check_err(s) : fail(VITS_ERR_DEVICE, "D2H failed: %s", hipGetErrorString(e));
   if (rc != VITS_OK) { free(h_out); return rc; }
+  if (lq.on) loud_req_results(lq, loud_res.data(), B);
   *out = h_out;
   *out_samples = So;
   if (out_lengths) for (int b = 0; b < B; ++b) out_lengths[b] = T ? T->P.n_out(ylen[b] * hp.hop_length) : ylen[b] * hp.hop_length;
@@ -483,6 +526,10 @@ static int synth_dispatch(vits_model* m, const int64_t* ids, const int64_t* leng
   for (int b = 0; b < B; ++b) if (lengths[b] < 0 || lengths[b] > Tx) return fail(VITS_ERR_ARG, "length out of range");
   int rate = 0;  // 0: the native rate, on the path as it was
   TRY(resample_rate_arg(m, sample_rate, &rate));
+  LoudReq lq;  // (the five fields are read only under the flag)
+  if (opts && (opts->flags & VITS_FLAG_LOUDNESS))
+    TRY(loud_req(true, opts->loudness_mode, opts->loudness_target, opts->loudness_ceiling, opts->out_loudness, opts->out_gain,
+                 rate ? rate : m->hp.sampling_rate, &lq));
   static const bool env_off = getenv("VITS_NO_FASTPATH") != nullptr;
   if (m->hp.bert_dim > 0 && (!opts || !opts->bert)) return fail(VITS_ERR_ARG, "this voice is BERT-conditioned: the bert feed [B,%d,T_x] is required", m->hp.bert_dim);
   if (m->hp.bert_dim == 0 && opts && opts->bert) return fail(VITS_ERR_ARG, "the bert feed was given but this voice has no BERT projection (hparams.bert_dim == 0)");
@@ -495,8 +542,8 @@ static int synth_dispatch(vits_model* m, const int64_t* ids, const int64_t* leng
   for (int attempt = 0;; ++attempt) {
     tl_ps_timed_out = false;
     const int rc = (g_fast_path && !env_off && !injected)
-                       ? synth_fast(m, ids, lengths, B, Tx, scales, sid, opts, pcm, pcm_scale, rate, out, out_samples, out_lengths, token_ends)
-                       : synth_eager(m, ids, lengths, B, Tx, scales, sid, opts, pcm, pcm_scale, rate, out, out_samples, out_lengths, token_ends);
+                       ? synth_fast(m, ids, lengths, B, Tx, scales, sid, opts, pcm, pcm_scale, rate, out, out_samples, out_lengths, token_ends, lq)
+                       : synth_eager(m, ids, lengths, B, Tx, scales, sid, opts, pcm, pcm_scale, rate, out, out_samples, out_lengths, token_ends, lq);
     if (rc == VITS_OK || !tl_ps_timed_out || attempt) return rc;  // a persistent program timed out: once more, on launches
   }
 }

@@ -8,6 +8,8 @@
 // the gRPC server's worker threads (server/tts_server.py:39-40,57) never share buffers.
 struct ProfRec { std::string name; std::string kernel; hipEvent_t e0, e1; double flops; };
 
+struct LoudWs;                         // loudness.hip.h: the buffers of a context's normalised calls (include/vits_loudness.h)
+static void loud_ws_delete(LoudWs* w);
 struct vits_session {
   vits_model* m = nullptr;
   hipStream_t stream = nullptr;
@@ -118,8 +120,10 @@ struct vits_session {
     char* y_h = nullptr;   // pinned host copy
     long long n_cap = 0;   // outputs per item
     uint64_t last_use = 0;
+    LoudWs* lw = nullptr;  // as vits_session::lw below
   };
   std::map<int, RateOut> rates;
+  LoudWs* lw = nullptr;            // back: scratch and output buffers of the calls with VITS_FLAG_LOUDNESS, allocated by the first of them
   uint64_t last_use = 0;
   size_t cache_bytes = 0;          // device bytes this session pins while cached (front: incl. its backs)
 };
@@ -369,8 +373,10 @@ static void session_free(vits_session* s) {
     for (hipGraphExec_t g : kv.second.g2) if (g) hipGraphExecDestroy(g);
     if (kv.second.y_d) hipFree(kv.second.y_d);
     if (kv.second.y_h) hipHostFree(kv.second.y_h);
+    loud_ws_delete(kv.second.lw);
   }
   s->rates.clear();
+  loud_ws_delete(s->lw);
   for (hipGraphExec_t g : s->g1) if (g) hipGraphExecDestroy(g);
   for (hipGraphExec_t g : s->g2) if (g) hipGraphExecDestroy(g);
   if (s->marks_d) hipFree(s->marks_d);

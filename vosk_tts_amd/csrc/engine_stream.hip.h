@@ -147,6 +147,8 @@ int vits_stream_open(vits_model* m, const int64_t* ids, int32_t Tx, const float*
 int vits_stream_open_rate(vits_model* m, const int64_t* ids, int32_t Tx, const float* scales, int64_t sid, const vits_synth_opts* opts,
                           int32_t chunk_frames, int32_t sample_rate, vits_stream** out, int64_t* total_samples) {
   if (!m || !ids || !scales || !out || Tx <= 0 || chunk_frames <= 0) return fail(VITS_ERR_ARG, "bad argument");
+  if (opts && (opts->flags & VITS_FLAG_LOUDNESS))
+    return fail(VITS_ERR_UNSUPPORTED, "VITS_FLAG_LOUDNESS on a stream: an integrated-loudness or peak target needs the whole utterance before the first chunk");
   const ResampleTab* T = nullptr;
   TRY(stream_rate(m, sample_rate, &T));
   for (int attempt = 0;; ++attempt) {

@@ -1117,11 +1117,46 @@ static int stts_resample_out(stts_model* m, int rate, int B, float** audio, int6
   return VITS_OK;
 }
 
+// STTS_FLAG_LOUDNESS of a call (include/vits_loudness.h): under the flag `opts` is the `base` of a stts_synth_opts_loudness, whose five
+// fields are read only then.  `rate` is the rate the call returns (0: the vocoder's own).  Checked before anything is synthesised: a
+// refusal costs nothing.
+static int stts_loud_arg(const stts_model* m, const stts_synth_opts* opts, int rate, LoudReq* q) {
+  q->on = false;
+  if (!opts || !(opts->flags & STTS_FLAG_LOUDNESS)) return VITS_OK;
+  if (!m->vocoder) return fail(VITS_ERR_ARG, "no vocoder attached");
+  static_assert(offsetof(stts_synth_opts_loudness, base) == 0, "the extended options begin with the plain ones");
+  const stts_synth_opts_loudness* lo = reinterpret_cast<const stts_synth_opts_loudness*>(opts);
+  return loud_req(true, lo->loudness_mode, lo->loudness_target, lo->loudness_ceiling, lo->out_loudness, lo->out_gain,
+                  rate ? rate : m->vocoder->hp.sampling_rate, q);
+}
+// a call's audio [B, S] (library-owned, items of lengths[b] samples) normalised in place: last in the order decode, clamp, denoise,
+// resample, normalise, on the finished waveform (the kernels of vits_op_loudness_normalize; like stts_resample_out, it crosses the host
+// once more)
+static int stts_loud_out(stts_model* m, const LoudReq& q, int B, float* audio, int64_t S, const int64_t* lengths) {
+  if (!q.on) return VITS_OK;
+  std::vector<float> loud(B, -INFINITY), gain(B, 1.f);
+  if (S > 0) TRY(loud_op(m->base.device, audio, lengths, B, S, q.P.rate, q.prm, audio, loud.data(), nullptr, gain.data()));
+  for (int b = 0; b < B; ++b) {
+    if (q.out_loudness) q.out_loudness[b] = loud[b];
+    if (q.out_gain) q.out_gain[b] = gain[b];
+  }
+  return VITS_OK;
+}
+
 extern "C" {
 
 int stts_synthesize(stts_model* m, const int64_t* ids, int32_t Tx, const float* scales, int64_t sid, const float* bert, const float* pde,
                     const stts_synth_opts* opts, float** out_audio, int64_t* out_samples, float** out_mel, int64_t* out_frames) {
-  return stts_synthesize_impl(m, ids, Tx, scales, sid, bert, pde, opts, out_audio, out_samples, out_mel, out_frames, nullptr);
+  if (!m) return fail(VITS_ERR_ARG, "bad argument");
+  LoudReq lq;
+  if (out_audio) TRY(stts_loud_arg(m, opts, 0, &lq));
+  TRY(stts_synthesize_impl(m, ids, Tx, scales, sid, bert, pde, opts, out_audio, out_samples, out_mel, out_frames, nullptr));
+  if (lq.on) {
+    const int64_t len = *out_samples;
+    const int rc = stts_loud_out(m, lq, 1, *out_audio, len, &len);
+    if (rc != VITS_OK) { free(*out_audio); *out_audio = nullptr; if (out_mel) { free(*out_mel); *out_mel = nullptr; } return rc; }
+  }
+  return VITS_OK;
 }
 
 int stts_synthesize_marks(stts_model* m, const int64_t* ids, int32_t Tx, const float* scales, int64_t sid, const float* bert, const float* pde,
@@ -1131,10 +1166,13 @@ int stts_synthesize_marks(stts_model* m, const int64_t* ids, int32_t Tx, const f
   SttsMarks mk;
   int rate = 0;
   TRY(stts_marks_arg(m, token_ends, sample_rate, &mk, &rate));
+  LoudReq lq;
+  if (out_audio) TRY(stts_loud_arg(m, opts, rate, &lq));
   TRY(stts_synthesize_impl(m, ids, Tx, scales, sid, bert, pde, opts, out_audio, out_samples, out_mel, out_frames, &mk));
-  if (rate && out_audio) {
+  if (out_audio) {
     int64_t len = *out_samples;
-    const int rc = stts_resample_out(m, rate, 1, out_audio, out_samples, &len);
+    int rc = rate ? stts_resample_out(m, rate, 1, out_audio, out_samples, &len) : VITS_OK;
+    if (rc == VITS_OK) rc = stts_loud_out(m, lq, 1, *out_audio, *out_samples, &len);
     if (rc != VITS_OK) { free(*out_audio); *out_audio = nullptr; if (out_mel) { free(*out_mel); *out_mel = nullptr; } return rc; }
   }
   return VITS_OK;
@@ -1144,6 +1182,8 @@ int stts_stream_open(stts_model* m, const int64_t* ids, int32_t Tx, const float*
                      const stts_synth_opts* opts, int32_t chunk_frames, vits_stream** out, int64_t* total_samples) {
   if (!m || !out || chunk_frames <= 0) return fail(VITS_ERR_ARG, "bad argument");
   if (!m->vocoder) return fail(VITS_ERR_ARG, "no vocoder attached");
+  if (opts && (opts->flags & STTS_FLAG_LOUDNESS))
+    return fail(VITS_ERR_UNSUPPORTED, "STTS_FLAG_LOUDNESS on a stream: an integrated-loudness or peak target needs the whole utterance before the first chunk");
   float* mel = nullptr;
   int64_t frames = 0;
   std::vector<int64_t> ends(Tx > 0 ? Tx : 0);  // recorded for vits_stream_marks (native rate: this open has no other)
@@ -1283,7 +1323,13 @@ static int stts_synthesize_batch_impl(stts_model* m, const int64_t* ids, const i
 int stts_synthesize_batch(stts_model* m, const int64_t* ids, const int64_t* lengths, int32_t B, int32_t Tx, const float* scales,
                           const int64_t* sid, const float* bert, const float* pde, const stts_synth_opts* opts, float** out_audio,
                           int64_t* out_samples, int64_t* out_lengths) {
-  return stts_synthesize_batch_impl(m, ids, lengths, B, Tx, scales, sid, bert, pde, opts, out_audio, out_samples, out_lengths, nullptr);
+  if (!m) return fail(VITS_ERR_ARG, "bad argument");
+  LoudReq lq;
+  TRY(stts_loud_arg(m, opts, 0, &lq));
+  TRY(stts_synthesize_batch_impl(m, ids, lengths, B, Tx, scales, sid, bert, pde, opts, out_audio, out_samples, out_lengths, nullptr));
+  const int rc = stts_loud_out(m, lq, B, *out_audio, *out_samples, out_lengths);
+  if (rc != VITS_OK) { free(*out_audio); *out_audio = nullptr; }
+  return rc;
 }
 
 int stts_synthesize_batch_marks(stts_model* m, const int64_t* ids, const int64_t* lengths, int32_t B, int32_t Tx, const float* scales,
@@ -1293,12 +1339,13 @@ int stts_synthesize_batch_marks(stts_model* m, const int64_t* ids, const int64_t
   SttsMarks mk;
   int rate = 0;
   TRY(stts_marks_arg(m, token_ends, sample_rate, &mk, &rate));
+  LoudReq lq;
+  TRY(stts_loud_arg(m, opts, rate, &lq));
   TRY(stts_synthesize_batch_impl(m, ids, lengths, B, Tx, scales, sid, bert, pde, opts, out_audio, out_samples, out_lengths, &mk));
-  if (rate) {
-    const int rc = stts_resample_out(m, rate, B, out_audio, out_samples, out_lengths);
-    if (rc != VITS_OK) { free(*out_audio); *out_audio = nullptr; return rc; }
-  }
-  return VITS_OK;
+  int rc = rate ? stts_resample_out(m, rate, B, out_audio, out_samples, out_lengths) : VITS_OK;
+  if (rc == VITS_OK) rc = stts_loud_out(m, lq, B, *out_audio, *out_samples, out_lengths);
+  if (rc != VITS_OK) { free(*out_audio); *out_audio = nullptr; }
+  return rc;
 }
 
 }  // extern "C"

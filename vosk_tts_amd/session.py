@@ -18,7 +18,7 @@ import threading
 
 import numpy as np
 
-from .capi import VitsLib
+from .capi import VitsLib, loudness_spec
 
 log = logging.getLogger(__name__)
 
@@ -225,7 +225,8 @@ BACK_SESSIONS_PER_FRONT = 6
 _GRAPH_INPUTS = ("input", "input_lengths", "scales", "sid")
 _OPTIONAL_NONE = ("bert", "phone_duration_extra")
 # extension feeds (not part of the ONNX graph) used by parity tests
-_EXT = ("vits.noise_dp", "vits.noise_prior", "vits.forced_durations", "vits.seed", "vits.solo", "vits.item_seeds", "vits.sample_rate", "vits.marks")
+_EXT = ("vits.noise_dp", "vits.noise_prior", "vits.forced_durations", "vits.seed", "vits.solo", "vits.item_seeds", "vits.sample_rate", "vits.marks",
+        "vits.loudness", "vits.peak", "vits.peak_ceiling")
 
 
 class _Arg:
@@ -292,15 +293,17 @@ class VitsSession:
         """reqs: [(ids [1,T] int64, sid, seed)] -> per request (audio-or-pcm [1,S_b], lengths [1]); one request: the plain call"""
         # (rate: output sample rate in Hz, 0 = the voice's own; marks: the requests want their token ends, include/vits_marks.h.  Both are
         #  part of the key, so a batch has one rate and either every request of it gets a third value or none does)
-        kind, scales, scale, rate, marks = key
+        # loud: the normalisation of the batch (capi.loudness_spec(), None = none; include/vits_loudness.h): part of the key like the rate, and
+        # measured and applied per item, so a request's result does not depend on what it was batched with
+        kind, scales, scale, rate, marks, loud = key
         scales = np.array(scales, np.float32)
         if len(reqs) == 1:
             ids, sid, seed = reqs[0]
             lens = np.array([ids.shape[1]], np.int64)
             if kind == "pcm":
                 return [self._model.synthesize_pcm16(ids, lens, scales, np.array([sid], np.int64), pcm_scale=scale, seed=seed, sample_rate=rate,
-                                                     marks=marks)]
-            return [self._model.synthesize(ids, lens, scales, np.array([sid], np.int64), seed=seed, sample_rate=rate, marks=marks)]
+                                                     marks=marks, loudness=loud)]
+            return [self._model.synthesize(ids, lens, scales, np.array([sid], np.int64), seed=seed, sample_rate=rate, marks=marks, loudness=loud)]
         # batch sizes come in powers of two (filled up with one-token dummies, whose padding tiles the ragged solo batch never
         # computes): every (batch size, length bucket) is a workspace and two captured graphs inside the engine, and a thread pool
         # produces every batch size between 1 and its own size
@@ -317,9 +320,10 @@ class VitsSession:
         seeds = np.array([r[2] for r in reqs], np.uint64)
         if kind == "pcm":
             res = self._model.synthesize_pcm16(batch, lens, scales, sids, pcm_scale=scale, seed=int(seeds[0]), solo=True, item_seeds=seeds,
-                                               sample_rate=rate, marks=marks)
+                                               sample_rate=rate, marks=marks, loudness=loud)
         else:
-            res = self._model.synthesize(batch, lens, scales, sids, seed=int(seeds[0]), solo=True, item_seeds=seeds, sample_rate=rate, marks=marks)
+            res = self._model.synthesize(batch, lens, scales, sids, seed=int(seeds[0]), solo=True, item_seeds=seeds, sample_rate=rate, marks=marks,
+                                         loudness=loud)
         out, ol = res[0], res[1]
         if marks:  # each request its own tokens' ends
             return [(out[b:b + 1, :int(ol[b])].copy(), ol[b:b + 1].copy(), res[2][b:b + 1, :int(lens[b])].copy()) for b in range(n_real)]
@@ -377,17 +381,27 @@ class VitsSession:
             raise ValueError(f"sample_rate {rate}: must be positive, or None for the voice's own {self.hp.sampling_rate} Hz")
         return 0 if rate == self.hp.sampling_rate else rate
 
+    def _loudness(self, feed):
+        """the extension feeds "vits.loudness" (LUFS target), "vits.peak" (peak target) and "vits.peak_ceiling" of a request ->
+        capi.loudness_spec() (None = none); both targets at once and values out of range are ValueError, before any device work"""
+        spec = loudness_spec(feed.get("vits.loudness"), feed.get("vits.peak"), feed.get("vits.peak_ceiling"))
+        if spec is not None:
+            self._lib._need_loudness()
+        return spec
+
     def run(self, output_names, input_feed, run_options=None):
         """Extension feed "vits.sample_rate" (next to "vits.seed"): output rate in Hz; the time axis of the output is then in output
         samples (include/vits_resample.h).  Extension feed "vits.marks": True -- the result list gets a second entry, token_ends int64
-        [B, T_x] in output samples (include/vits_marks.h)."""
+        [B, T_x] in output samples (include/vits_marks.h).  Extension feeds "vits.loudness" / "vits.peak" / "vits.peak_ceiling": every
+        item normalised to a LUFS or a peak target on the device, last in the chain (include/vits_loudness.h)."""
         feed, ids, sid, seed = self._validated(output_names, input_feed)
         self._watch()
         rate = self._rate(feed.get("vits.sample_rate"))
         marks = self._marks(feed)
+        loud = self._loudness(feed)
         n = self._coalescable(feed, ids)
         if n:
-            key = ("f32", tuple(float(v) for v in np.asarray(feed["scales"], np.float32).reshape(-1)), 1.0, rate, marks)
+            key = ("f32", tuple(float(v) for v in np.asarray(feed["scales"], np.float32).reshape(-1)), 1.0, rate, marks, loud)
             res = self.coalescer.submit(key, np.ascontiguousarray(ids[:, :n], np.int64), int(sid[0]), int(seed))
             self.last_lengths = res[1]
             if marks:  # (the request's own tokens; columns beyond its length repeat the last end, as the C ABI pads them)
@@ -397,7 +411,7 @@ class VitsSession:
             ids, np.asarray(feed["input_lengths"]).reshape(-1), np.asarray(feed["scales"], np.float32).reshape(-1), sid,
             noise_dp=feed.get("vits.noise_dp"), noise_prior=feed.get("vits.noise_prior"),
             forced_durations=feed.get("vits.forced_durations"), seed=int(seed), solo=bool(feed.get("vits.solo", False)),
-            item_seeds=feed.get("vits.item_seeds"), bert=feed.get("bert"), sample_rate=rate, marks=marks)
+            item_seeds=feed.get("vits.item_seeds"), bert=feed.get("bert"), sample_rate=rate, marks=marks, loudness=loud)
         self.last_lengths = res[1]
         return [res[0][:, None, None, :], res[2]] if marks else [res[0][:, None, None, :]]
 
@@ -424,14 +438,15 @@ class VitsSession:
         sample_rate: output rate in Hz (default: the feed's "vits.sample_rate", else the voice's own): the resampler converts in its
         epilogue, so the call launches as many kernels as at the voice's rate and copies rate_out / rate_in as many bytes.
         With the feed "vits.marks": True the result is a tuple that ends with token_ends int64 [B, T_x]: (pcm, token_ends), or
-        (pcm, lengths, token_ends) with return_lengths."""
+        (pcm, lengths, token_ends) with return_lengths.  The loudness feeds: as for run(); `scale` multiplies the normalised audio."""
         feed, ids, sid, seed = self._validated(None, input_feed)
         self._watch()
         rate = self._rate(sample_rate if sample_rate is not None else feed.get("vits.sample_rate"))
         marks = self._marks(feed)
+        loud = self._loudness(feed)
         n = self._coalescable(feed, ids)
         if n:
-            key = ("pcm", tuple(float(v) for v in np.asarray(feed["scales"], np.float32).reshape(-1)), float(scale), rate, marks)
+            key = ("pcm", tuple(float(v) for v in np.asarray(feed["scales"], np.float32).reshape(-1)), float(scale), rate, marks, loud)
             res = self.coalescer.submit(key, np.ascontiguousarray(ids[:, :n], np.int64), int(sid[0]), int(seed))
             pcm, lengths = res[0], res[1]
             self.last_lengths = lengths
@@ -443,7 +458,7 @@ class VitsSession:
             ids, np.asarray(feed["input_lengths"]).reshape(-1), np.asarray(feed["scales"], np.float32).reshape(-1), sid,
             pcm_scale=float(scale), noise_dp=feed.get("vits.noise_dp"), noise_prior=feed.get("vits.noise_prior"),
             forced_durations=feed.get("vits.forced_durations"), seed=int(seed), solo=bool(feed.get("vits.solo", False)),
-            item_seeds=feed.get("vits.item_seeds"), bert=feed.get("bert"), sample_rate=rate, marks=marks)
+            item_seeds=feed.get("vits.item_seeds"), bert=feed.get("bert"), sample_rate=rate, marks=marks, loudness=loud)
         pcm, lengths = res[0], res[1]
         self.last_lengths = lengths
         if marks:
@@ -457,6 +472,9 @@ class VitsSession:
         samples whose concatenation equals run(...)[0].squeeze() for the same feed (same "vits.seed").
         sample_rate (default: the feed's "vits.sample_rate"): output rate in Hz; chunk sizes then vary by one sample."""
         feed, ids, sid, seed = self._validated(output_names, input_feed)
+        if self._loudness(feed) is not None:
+            raise ValueError("a stream cannot be loudness-normalised: an integrated-loudness or peak target needs the whole utterance before "
+                             "the first chunk (run() / run_pcm16() take the loudness feeds)")
         rate = self._rate(sample_rate if sample_rate is not None else feed.get("vits.sample_rate"))
         if ids.shape[0] != 1:
             raise ValueError("run_stream takes one utterance")

@@ -9,12 +9,12 @@ import threading
 
 import numpy as np
 
-from .capi import VitsLib
+from .capi import VitsLib, loudness_spec
 from .capi_stts import SttsModel
 
 _INPUTS = ("input", "input_lengths", "scales", "sid", "bert", "phone_duration_extra")
 _EXT = ("vits.noise", "vits.seed", "vits.n_timesteps", "vits.sample_rate", "vits.denoiser_strength", "vits.denoiser_filter_length",
-        "vits.marks")
+        "vits.marks", "vits.loudness", "vits.peak", "vits.peak_ceiling")
 
 
 class SttsSession:
@@ -94,22 +94,45 @@ class SttsSession:
         out = self._lib.op_resample(audio, lengths, native, rate, device=self._vocoder.device)
         return out, np.array([self._lib.out_samples(n, native, rate) for n in lengths], np.int64)
 
+    def _loudness(self, feed):
+        """the extension feeds "vits.loudness" (LUFS target), "vits.peak" (peak target), "vits.peak_ceiling" -> capi.loudness_spec()
+        (None = none); both targets at once and values out of range are ValueError, before any device work"""
+        spec = loudness_spec(feed.get("vits.loudness"), feed.get("vits.peak"), feed.get("vits.peak_ceiling"))
+        if spec is not None:
+            self._lib._need_loudness()
+        return spec
+
+    def normalize(self, audio, lengths, sample_rate, spec):
+        """audio float32 [B, S] at `sample_rate` Hz (None / 0 = the vocoder's own) with per-item sample counts -> the audio normalised
+        per item by `spec` (vits_op_loudness_normalize on the host buffer); None: unchanged.  What run() / run_batch() do behind
+        resample(): the order is decode, clamp, denoise, resample, normalise"""
+        if spec is None or audio.shape[-1] == 0:
+            return audio
+        rate = int(sample_rate or 0) or self._vocoder.hp.sampling_rate
+        return self._lib.op_loudness_normalize(audio, lengths, rate, *spec, device=self._vocoder.device)[0]
+
     def run(self, output_names, input_feed, run_options=None):
         """Extension feeds: "vits.sample_rate", output rate in Hz (the finished waveform is resampled, include/vits_resample.h);
         "vits.denoiser_strength" / "vits.denoiser_filter_length", the vocoder-bias denoiser behind the clamp (include/vits_denoise.h),
         applied at the vocoder's own rate, before any resampling; "vits.marks": True appends token_ends int64 [1, T] in output samples
-        to the result list (include/vits_marks.h; stts_synthesize_marks takes the rate itself)."""
+        to the result list (include/vits_marks.h; stts_synthesize_marks takes the rate itself); "vits.loudness" / "vits.peak" /
+        "vits.peak_ceiling": the audio normalised to a LUFS or a peak target, last in the chain -- at another rate the resampled audio
+        is what is measured (include/vits_loudness.h)."""
         feed, ids, scales, sid, bert, pde, seed = self._parse(output_names, input_feed)
+        loud = self._loudness(feed)
         if feed.get("vits.marks"):
             audio, _, ends = self._model.synthesize(ids, scales, sid, bert, pde, noise=feed.get("vits.noise"), seed=seed,
                                                     n_timesteps=int(feed.get("vits.n_timesteps", 0)), want_mel=False, marks=True,
-                                                    sample_rate=self._rate(feed.get("vits.sample_rate")), **self._denoiser(feed))
+                                                    sample_rate=self._rate(feed.get("vits.sample_rate")), loudness=loud, **self._denoiser(feed))
             outs = {"wav": audio[None, :], "wav_lengths": np.array([audio.shape[0]], np.int64)}
             return [outs[n] for n in (output_names or ["wav", "wav_lengths"])] + [ends[None, :]]
+        rate = self._rate(feed.get("vits.sample_rate"))
         audio, _ = self._model.synthesize(ids, scales, sid, bert, pde, noise=feed.get("vits.noise"), seed=seed,
-                                          n_timesteps=int(feed.get("vits.n_timesteps", 0)), want_mel=False, **self._denoiser(feed))
-        if self._rate(feed.get("vits.sample_rate")):
-            audio = self.resample(audio[None, :], [audio.shape[0]], feed["vits.sample_rate"])[0][0]
+                                          n_timesteps=int(feed.get("vits.n_timesteps", 0)), want_mel=False,
+                                          loudness=None if rate else loud, **self._denoiser(feed))
+        if rate:  # (the library normalises last, and this resampling happens behind it: the normalisation follows it here)
+            audio = self.resample(audio[None, :], [audio.shape[0]], rate)[0][0]
+            audio = self.normalize(audio[None, :], [audio.shape[0]], rate, loud)[0]
         outs = {"wav": audio[None, :], "wav_lengths": np.array([audio.shape[0]], np.int64)}
         return [outs[n] for n in (output_names or ["wav", "wav_lengths"])]
 
@@ -121,6 +144,9 @@ class SttsSession:
         feed, ids, scales, sid, bert, pde, seed = self._parse(output_names, input_feed)
         if "vits.noise" in feed:
             raise NotImplementedError("run_stream draws the CFM noise on the device (vits.seed)")
+        if self._loudness(feed) is not None:
+            raise ValueError("a stream cannot be loudness-normalised: an integrated-loudness or peak target needs the whole utterance before "
+                             "the first chunk (run() takes the loudness feeds)")
         rate = self._rate(sample_rate if sample_rate is not None else feed.get("vits.sample_rate"))
         dn = self._denoiser(feed)
         if rate and dn:
@@ -155,6 +181,7 @@ class SttsSession:
             if k not in feed:
                 raise ValueError(f"Required input {k} is missing")
         dn = self._denoiser(feed)
+        loud = self._loudness(feed)  # (per-item gains, last in the chain like run())
         rate = self._rate(feed.get("vits.sample_rate"))
         ids = np.asarray(feed["input"])
         if ids.ndim != 3 or ids.shape[1] != 5:
@@ -164,11 +191,15 @@ class SttsSession:
             return self._model.synthesize_batch(ids, feed["input_lengths"], np.asarray(feed["scales"], np.float32).reshape(-1), sid,
                                                 feed.get("bert"), feed.get("phone_duration_extra"), seed=int(feed.get("vits.seed", 0)),
                                                 n_timesteps=int(feed.get("vits.n_timesteps", 0)), item_seeds=feed.get("vits.item_seeds"),
-                                                marks=True, sample_rate=rate, **dn)
+                                                marks=True, sample_rate=rate, loudness=loud, **dn)
         audio, ol = self._model.synthesize_batch(ids, feed["input_lengths"], np.asarray(feed["scales"], np.float32).reshape(-1), sid,
                                                  feed.get("bert"), feed.get("phone_duration_extra"), seed=int(feed.get("vits.seed", 0)),
-                                                 n_timesteps=int(feed.get("vits.n_timesteps", 0)), item_seeds=feed.get("vits.item_seeds"), **dn)
-        return self.resample(audio, ol, rate) if rate else (audio, ol)
+                                                 n_timesteps=int(feed.get("vits.n_timesteps", 0)), item_seeds=feed.get("vits.item_seeds"),
+                                                 loudness=None if rate else loud, **dn)
+        if not rate:
+            return audio, ol
+        audio, ol = self.resample(audio, ol, rate)
+        return self.normalize(audio, ol, rate, loud), ol
 
     def close(self):
         self._model.close()

@@ -200,6 +200,47 @@ class Synth:
                              "this is a VITS-family voice")
         args["vits.denoiser_strength"] = float(denoiser_strength)
 
+    def _loudness(self, args, loudness, peak, peak_ceiling):
+        """Loudness normalisation of the request (include/vits_loudness.h): `loudness`, a LUFS target (ITU-R BS.1770 integrated loudness),
+        or `peak`, a max-|sample| target in (0, 1], each defaulting to the config keys inference.loudness / inference.peak; peak_ceiling
+        (inference.peak_ceiling, else 1.0; 0 = none) caps the peak a LUFS target may produce.  They go into the feed as "vits.loudness" /
+        "vits.peak" / "vits.peak_ceiling"; none given and no config key = off, the reference's behaviour.  An argument overrides the
+        config as a whole (peak=0.9 on a voice whose config names a loudness is a peak request); both arguments at once is ValueError.
+        The engine measures and applies the gain on the device, last in the chain; `scale` multiplies afterwards, as before."""
+        from .capi import loudness_spec
+
+        inf = self.model.config.get("inference", {})
+        if loudness is None and peak is None:
+            loudness, peak = inf.get("loudness"), inf.get("peak")
+        if peak_ceiling is None:
+            peak_ceiling = inf.get("peak_ceiling")
+        if loudness_spec(loudness, peak, peak_ceiling) is None:  # (raises on both at once and on values out of range)
+            return False
+        if loudness is not None:
+            args["vits.loudness"] = float(loudness)
+            if peak_ceiling is not None:
+                args["vits.peak_ceiling"] = float(peak_ceiling)
+        else:
+            args["vits.peak"] = float(peak)
+        return True
+
+    def measure_loudness(self, audio, rate=None):
+        """(lufs, peak) of one utterance: BS.1770 integrated loudness (-inf for silence) and max |sample| in full-scale units, measured
+        by the engine's own kernels (vits_op_loudness).  audio: int16 PCM (scaled by 1 / 32767, the conversion's own factor) or float;
+        rate: its sample rate in Hz (default: the voice's own)."""
+        a = np.asarray(audio)
+        x = a.astype(np.float32) / np.float32(32767.0) if a.dtype == np.int16 else a.astype(np.float32)
+        x = x.reshape(1, -1)
+        sess = self.model.onnx
+        lib = getattr(sess, "_lib", None)
+        if lib is None or not getattr(lib, "has_loudness", False):
+            raise NotImplementedError("this session type has no loudness measurement (include/vits_loudness.h)")
+        if x.shape[1] == 0:
+            return float("-inf"), 0.0
+        dev = getattr(getattr(sess, "_vocoder", None) or getattr(sess, "_model", None), "device", 0)
+        loud, pk = lib.op_loudness(x, [x.shape[1]], int(rate or self.native_rate()), device=dev)
+        return float(loud[0]), float(pk[0])
+
     def marks_layout(self, text):
         """The token layout of `text` under the front end _feed picks, for speech marks (vosk_tts_amd/marks.py):
         -> (symbols, ids per symbol, blank layout?, word_of per symbol, word_texts).  Needs the voice's config and dictionary only."""
@@ -230,13 +271,15 @@ class Synth:
         return build_marks(rate, np.asarray(token_ends).reshape(-1), symbols, counts, blank, word_of, word_texts)
 
     def synth_audio(self, text, speaker_id=0, noise_level=None, speech_rate=None, duration_noise_level=None, scale=None, sample_rate=None,
-                    denoiser_strength=None, marks=False):
+                    denoiser_strength=None, marks=False, loudness=None, peak=None, peak_ceiling=None):
         """sample_rate: output rate in Hz (extension; default None = the voice's own rate, the reference's behaviour): the feed gets
         "vits.sample_rate" and the engine resamples on the device.  denoiser_strength: see _denoiser.
+        loudness / peak / peak_ceiling (extension): a LUFS or a peak target for the returned audio, see _loudness.
         marks=True (extension): returns (audio, marks) -- marks.SpeechMarks with rate, token_ends, phonemes [(symbol, start, end)] and
         words [(text, start, end)] in samples of the returned audio, and seconds(); the default returns the array alone."""
         args, scale = self._feed(text, speaker_id, noise_level, speech_rate, duration_noise_level, scale)
         self._denoiser(args, denoiser_strength)
+        self._loudness(args, loudness, peak, peak_ceiling)
         rate = self.native_rate()
         if sample_rate and int(sample_rate) != rate:
             rate = int(sample_rate)
@@ -273,11 +316,16 @@ class Synth:
         return audio
 
     def synth_stream(self, text, speaker_id=0, noise_level=None, speech_rate=None, duration_noise_level=None, scale=None,
-                     chunk_frames=64, sample_rate=None, denoiser_strength=None, on_marks=None):
+                     chunk_frames=64, sample_rate=None, denoiser_strength=None, on_marks=None, loudness=None, peak=None, peak_ceiling=None):
         """Generator of int16 PCM chunks (chunk_frames*256 samples each, ~0.74 s at the default): what a streaming
         `SynthesizeStream` handler would put into successive AudioChunk messages (tts_service.proto:46-54) instead
         of the single whole-utterance chunk of tts_server.py:54.  Same conversion as synth_audio per chunk.
-        on_marks: a callable that receives the utterance's marks.SpeechMarks once, before the first chunk is yielded."""
+        on_marks: a callable that receives the utterance's marks.SpeechMarks once, before the first chunk is yielded.
+        loudness / peak: ValueError -- an integrated-loudness or peak target needs the whole utterance before the first chunk (a voice
+        whose config names inference.loudness / inference.peak streams un-normalised)."""
+        if loudness is not None or peak is not None:
+            raise ValueError("synth_stream cannot normalise loudness: an integrated-loudness or peak target needs the whole utterance "
+                             "before the first chunk (synth_audio takes loudness= / peak=)")
         args, scale = self._feed(text, speaker_id, noise_level, speech_rate, duration_noise_level, scale)
         self._denoiser(args, denoiser_strength)
         if not hasattr(self.model.onnx, "run_stream"):
@@ -293,9 +341,10 @@ class Synth:
             yield self.audio_float_to_int16(chunk * scale)
 
     def synth(self, text, oname, speaker_id=0, noise_level=None, speech_rate=None, duration_noise_level=None, scale=None, sample_rate=None,
-              denoiser_strength=None, marks=False):
+              denoiser_strength=None, marks=False, loudness=None, peak=None, peak_ceiling=None):
         """marks=True: the utterance's marks.SpeechMarks are returned (the default returns None, as the reference does)"""
-        audio = self.synth_audio(text, speaker_id, noise_level, speech_rate, duration_noise_level, scale, sample_rate, denoiser_strength, marks=marks)
+        audio = self.synth_audio(text, speaker_id, noise_level, speech_rate, duration_noise_level, scale, sample_rate, denoiser_strength, marks=marks,
+                                 loudness=loudness, peak=peak, peak_ceiling=peak_ceiling)
         sm = None
         if marks:
             audio, sm = audio
