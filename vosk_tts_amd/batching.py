@@ -159,7 +159,7 @@ class MultiDeviceSynth:
         return out
 
     def synth_batch(self, texts, speaker_ids=0, noise_level=None, speech_rate=None, duration_noise_level=None, scale=None, seeds=None,
-                    sample_rate=None, denoiser_strength=None, marks=False, loudness=None, peak=None, peak_ceiling=None):
+                    sample_rate=None, denoiser_strength=None, marks=False, loudness=None, peak=None, peak_ceiling=None, pitch=None):
         """texts: list of str -> list of int16 PCM arrays (22.05 kHz), one per request, in request order.  marks=True: a list of
         (audio, marks.SpeechMarks) per request instead (as Synth.synth_audio(..., marks=True)), through every shard path.  `seeds`: optional
         per-request noise seeds (default: a running counter), `speaker_ids`: one id or one per request.  `sample_rate`: output rate
@@ -171,6 +171,7 @@ class MultiDeviceSynth:
         s0 = self.synths[0]
         loud = {}
         s0._loudness(loud, loudness, peak, peak_ceiling)
+        s0._pitch(loud, pitch)  # ("vits.pitch": one shift for the whole batch, travelling with the loudness feeds; include/vits_pitch.h)
         dn = {}
         s0._denoiser(dn, denoiser_strength)
         denoiser_strength = dn.get("vits.denoiser_strength")
@@ -275,6 +276,7 @@ class MultiDeviceSynth:
         """stts_synthesize_batch of one padded part -> (audio, lengths, token_ends or None) at `sample_rate`; with marks the call takes
         the rate itself (stts_synthesize_batch_marks).  loud: the loudness feeds; every item is normalised last, behind the resampler"""
         spec = sess._loudness(loud or {})
+        kw = dict(kw, **sess._pitch(loud or {}))
         if marks:
             return sess._model.synthesize_batch(*args, marks=True, sample_rate=sess._rate(sample_rate), loudness=spec, **kw)
         rate = sess._rate(sample_rate)

@@ -88,6 +88,39 @@ def set_loudness(opts, keep, spec, B, flag, out=None):
         out["loudness"], out["gain"] = loud, gain
 
 
+# include/vits_pitch.h
+FLAG_PITCH = 4          # VITS_FLAG_PITCH
+PITCH_FRAME = 1024      # VITS_PITCH_FRAME
+PITCH_MAX_SEMITONES = 12.0
+
+
+class SynthPitchOpts(SynthOpts):
+    """mirror of `struct vits_synth_opts_pitch` (include/vits_pitch.h): SynthOpts followed by pitch_semitones, which the library reads
+    only under VITS_FLAG_PITCH; passed where a POINTER(SynthOpts) is declared"""
+
+    _fields_ = [("pitch_semitones", ctypes.c_float)]
+
+
+def pitch_ratio(semitones):
+    """(P, Q) of a shift as include/vits_pitch.h defines it; ValueError names a value out of range (NaN included), as the library's
+    VITS_ERR_ARG does: here it is refused before any device work"""
+    import math
+    s = float(semitones)
+    if not abs(s) <= PITCH_MAX_SEMITONES:
+        raise ValueError(f"pitch {s} semitones outside [-{PITCH_MAX_SEMITONES:g}, {PITCH_MAX_SEMITONES:g}]")
+    p0 = int(math.floor(1000.0 * 2.0 ** (s / 12.0) + 0.5))
+    g = math.gcd(p0, 1000)
+    return p0 // g, 1000 // g
+
+
+def pitch_spec(pitch=None):
+    """The shift a call asks for -> None (none, or one that reduces to P = Q) or the semitones as a float"""
+    if pitch is None:
+        return None
+    P, Q = pitch_ratio(pitch)
+    return None if P == Q else float(pitch)
+
+
 class PersistInfo(ctypes.Structure):
     """mirror of `struct vits_persist_info` (vits_persist_state)"""
 
@@ -167,6 +200,7 @@ class VitsLib:
         self.has_denoise = False
         self.has_marks = False
         self.has_loudness = False
+        self.has_pitch = False
         if self.is_device:
             c_i16p = ctypes.POINTER(ctypes.c_int16)
             f("synthesize_pcm16").argtypes = [ctypes.c_void_p, c_i64p, c_i64p, ctypes.c_int32, ctypes.c_int32, c_f32p, c_i64p,
@@ -233,6 +267,12 @@ class VitsLib:
                 f("op_loudness").argtypes = [ctypes.c_int, c_f32p, c_i64p, ctypes.c_int32, ctypes.c_int64, ctypes.c_int32, c_f32p, c_f32p]
                 f("op_loudness_normalize").argtypes = [ctypes.c_int, c_f32p, c_i64p, ctypes.c_int32, ctypes.c_int64, ctypes.c_int32,
                                                        ctypes.c_int32, ctypes.c_float, ctypes.c_float, c_f32p, c_f32p, c_f32p]
+            # include/vits_pitch.h: pitch-shifted output, an extension of the product library like the four above
+            self.has_pitch = self.has("op_pitch_shift")
+            if self.has_pitch:
+                f("pitch_plan").argtypes = [ctypes.c_float, c_i32p, c_i32p]
+                for name in ("op_pitch_shift", "op_pitch_stretch"):
+                    f(name).argtypes = [ctypes.c_int, c_f32p, c_i64p, ctypes.c_int32, ctypes.c_int64, ctypes.c_float, c_f32p]
             if self.has("debug_clock_probe"):
                 f("debug_clock_probe").argtypes = [ctypes.c_int, ctypes.c_int32, ctypes.POINTER(ctypes.c_double), ctypes.c_int32]
 
@@ -423,6 +463,37 @@ class VitsLib:
                                                      float(ceiling), _p(y, c_f32p), _p(loud, c_f32p), _p(gain, c_f32p)))
         return y, loud, gain
 
+    # ---- pitch-shifted output (include/vits_pitch.h) ---------------------------
+    def _need_pitch(self):
+        if not self.has_pitch:
+            raise VitsError(4, "this backend has no pitch shifter (include/vits_pitch.h)")
+
+    def pitch_plan(self, semitones):
+        """vits_pitch_plan (host only): (P, Q) of a shift; VitsError(1) names a refused value"""
+        self._need_pitch()
+        P, Q = ctypes.c_int32(), ctypes.c_int32()
+        self.check(self._fn("pitch_plan")(float(semitones), ctypes.byref(P), ctypes.byref(Q)))
+        return P.value, Q.value
+
+    def op_pitch_shift(self, x, lengths, semitones, device=0):
+        """vits_op_pitch_shift: x float32 [B, N], lengths [B] -> y float32 [B, N]; item b from x[b, :lengths[b]] only, zero beyond"""
+        self._need_pitch()
+        x, lengths = self._loud_args(x, lengths)
+        B, N = x.shape
+        y = np.empty((B, N), np.float32)
+        self.check(self._fn("op_pitch_shift")(device, _p(x, c_f32p), _p(lengths, c_i64p), B, N, float(semitones), _p(y, c_f32p)))
+        return y
+
+    def op_pitch_stretch(self, x, lengths, semitones, device=0):
+        """vits_op_pitch_stretch: the vocoder's output before the resampler, float32 [B, 256 * (ceil((N // 256 + 2) * P / Q) - 1)]"""
+        self._need_pitch()
+        x, lengths = self._loud_args(x, lengths)
+        B, N = x.shape
+        P, Q = self.pitch_plan(semitones)
+        y = np.empty((B, 256 * (-(-(N // 256 + 2) * P // Q) - 1)), np.float32)
+        self.check(self._fn("op_pitch_stretch")(device, _p(x, c_f32p), _p(lengths, c_i64p), B, N, float(semitones), _p(y, c_f32p)))
+        return y
+
     def mas_maximum_path(self, values, t_ys, t_xs, device=0):
         """monotonic_align.maximum_path_c (core.pyx:35-42): values float32 [B,T_y,T_x] -> paths int32 [B,T_y,T_x]."""
         values = _f32(values)
@@ -469,9 +540,12 @@ class VitsModel:
             pass
 
     def _opts(self, B, Tx, noise_dp, noise_prior, forced_durations, seed, max_frames, solo=False, item_seeds=None, bert=None,
-              loudness=None, loudness_out=None):
-        opts = SynthOpts()
+              loudness=None, loudness_out=None, pitch=None):
+        pitch = pitch_spec(pitch)  # (None, or a shift that does not reduce to P = Q)
+        opts = SynthOpts() if pitch is None else SynthPitchOpts()
         keep = []
+        if pitch is not None:
+            self.lib._need_pitch()
         if loudness is not None:
             self.lib._need_loudness()
         if bert is not None:
@@ -504,6 +578,9 @@ class VitsModel:
         opts.max_frames = max_frames
         opts.flags = 1 if solo else 0  # VITS_FLAG_SOLO_BATCH
         set_loudness(opts, keep, loudness, B, FLAG_LOUDNESS, loudness_out)
+        if pitch is not None:
+            opts.flags |= FLAG_PITCH
+            opts.pitch_semitones = pitch
         return opts, keep
 
     # ---- the hot path -----------------------------------------------------
@@ -517,8 +594,11 @@ class VitsModel:
         return rate
 
     def synthesize(self, ids, lengths, scales, sid, noise_dp=None, noise_prior=None, forced_durations=None, seed=0,
-                   max_frames=0, solo=False, item_seeds=None, bert=None, sample_rate=None, marks=False, loudness=None, loudness_out=None):
-        """One .run(): returns (audio float32 [B,S], out_lengths int64 [B]); with marks=True (vits_synthesize_marks) a third value,
+                   max_frames=0, solo=False, item_seeds=None, bert=None, sample_rate=None, marks=False, loudness=None, loudness_out=None,
+                   pitch=None):
+        """pitch: semitones in [-12, 12] (VITS_FLAG_PITCH, include/vits_pitch.h): every item shifted on the device behind the decoder,
+        before the resampler; lengths and marks do not change.
+        One .run(): returns (audio float32 [B,S], out_lengths int64 [B]); with marks=True (vits_synthesize_marks) a third value,
         token_ends int64 [B,T_x] in output samples (include/vits_marks.h).  solo=True (VITS_FLAG_SOLO_BATCH): every
         item equals its own single-utterance call with seed + b instead of the reference's padded-batch result.
         sample_rate: output rate in Hz (vits_synthesize_rate; S and out_lengths are then in output samples).
@@ -531,7 +611,8 @@ class VitsModel:
         scales = _f32(scales)
         if lengths.shape != (B,) or sid.shape != (B,) or scales.shape != (3,):
             raise ValueError("bad feed shapes")
-        opts, keep = self._opts(B, Tx, noise_dp, noise_prior, forced_durations, seed, max_frames, solo, item_seeds, bert, loudness, loudness_out)
+        opts, keep = self._opts(B, Tx, noise_dp, noise_prior, forced_durations, seed, max_frames, solo, item_seeds, bert, loudness, loudness_out,
+                                pitch)
         out = c_f32p()
         ns = ctypes.c_int64()
         olen = np.zeros(B, dtype=np.int64)
@@ -559,8 +640,9 @@ class VitsModel:
 
     def synthesize_pcm16(self, ids, lengths, scales, sid, pcm_scale=1.0, noise_dp=None, noise_prior=None, forced_durations=None,
                          seed=0, max_frames=0, solo=False, item_seeds=None, bert=None, sample_rate=None, marks=False, loudness=None,
-                         loudness_out=None):
-        """synthesize() with Synth.synth_audio's `* scale` and audio_float_to_int16 (vosk_tts/synth.py:127-130) done on the
+                         loudness_out=None, pitch=None):
+        """pitch: as for synthesize.
+        synthesize() with Synth.synth_audio's `* scale` and audio_float_to_int16 (vosk_tts/synth.py:127-130) done on the
         device: returns (pcm int16 [B,S], out_lengths int64 [B]).  sample_rate: as for synthesize (vits_synthesize_pcm16_rate:
         the resampler does the conversion in its epilogue).  loudness / loudness_out: as for synthesize (pcm_scale multiplies the
         normalised audio, as before)."""
@@ -569,7 +651,8 @@ class VitsModel:
         lengths = _i64(lengths); sid = _i64(sid); scales = _f32(scales)
         if lengths.shape != (B,) or sid.shape != (B,) or scales.shape != (3,):
             raise ValueError("bad feed shapes")
-        opts, keep = self._opts(B, Tx, noise_dp, noise_prior, forced_durations, seed, max_frames, solo, item_seeds, bert, loudness, loudness_out)
+        opts, keep = self._opts(B, Tx, noise_dp, noise_prior, forced_durations, seed, max_frames, solo, item_seeds, bert, loudness, loudness_out,
+                                pitch)
         out = ctypes.POINTER(ctypes.c_int16)()
         ns = ctypes.c_int64()
         olen = np.zeros(B, dtype=np.int64)
@@ -598,8 +681,9 @@ class VitsModel:
         return (pcm, olen, ends) if marks else (pcm, olen)
 
     def stream(self, ids, scales, sid, chunk_frames=64, noise_dp=None, noise_prior=None, forced_durations=None, seed=0, bert=None,
-               sample_rate=None, on_marks=None, loudness=None):
-        """Streaming synthesis of ONE utterance (vits_stream_*): a generator of float32 chunks of
+               sample_rate=None, on_marks=None, loudness=None, pitch=None):
+        """pitch: refused (vits_stream_open* refuse VITS_FLAG_PITCH the same way; here before any device work).
+        Streaming synthesis of ONE utterance (vits_stream_*): a generator of float32 chunks of
         chunk_frames*hop_length samples (the last one shorter); their concatenation equals synthesize().
         sample_rate: output rate in Hz (vits_stream_open_rate): the chunk that covers input samples [a, b) holds the outputs
         ceil(a*L/M) <= n < ceil(b*L/M), so chunk sizes vary by one sample.
@@ -608,6 +692,8 @@ class VitsModel:
         if loudness is not None:  # (vits_stream_open* refuse VITS_FLAG_LOUDNESS the same way; here before any device work)
             raise VitsError(4, "a stream cannot be loudness-normalised: an integrated-loudness or peak target needs the whole utterance "
                                "before the first chunk")
+        if pitch_spec(pitch) is not None:
+            raise VitsError(4, "a stream cannot be pitch-shifted: the phase recursion needs the frames before a chunk")
         if on_marks is not None:
             self.lib._need_marks()
         if not self.lib.has("stream_open"):

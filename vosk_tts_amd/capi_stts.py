@@ -5,7 +5,7 @@ import ctypes
 
 import numpy as np
 
-from .capi import VitsError, VitsLib, _f32, _i32, _i64, _p, c_f32p, c_i32p, c_i64p, set_loudness
+from .capi import VitsError, VitsLib, _f32, _i32, _i64, _p, c_f32p, c_i32p, c_i64p, pitch_spec, set_loudness
 from .weights_stts import SttsHParams
 
 
@@ -28,6 +28,14 @@ class SttsLoudnessOpts(SttsOpts):
 
 
 STTS_FLAG_LOUDNESS = 4    # include/vits_loudness.h
+STTS_FLAG_PITCH = 8       # include/vits_pitch.h
+
+
+class SttsPitchOpts(SttsLoudnessOpts):
+    """mirror of `struct stts_synth_opts_pitch` (include/vits_pitch.h): SttsLoudnessOpts followed by pitch_semitones, which the library
+    reads only under STTS_FLAG_PITCH (the loudness fields inside still only under their own flag)"""
+
+    _fields_ = [("pitch_semitones", ctypes.c_float)]
 
 
 class SttsModel:
@@ -105,10 +113,21 @@ class SttsModel:
         normalises: the CPU oracle would ignore the flag, which is refused here instead.  `opts` must then be a SttsLoudnessOpts"""
         if spec is None:
             return
-        assert isinstance(opts, SttsLoudnessOpts)
+        assert isinstance(opts, SttsLoudnessOpts)  # (SttsPitchOpts is one)
         if not getattr(self.vlib, "has_loudness", False):
             raise VitsError(4, "this backend has no loudness normalisation (include/vits_loudness.h)")
         set_loudness(opts, keep, spec, B, STTS_FLAG_LOUDNESS, out)
+
+    def _opts_for(self, loudness, pitch):
+        """the options struct a call needs: the plain one, the one with the loudness fields, or the one with the pitch behind those"""
+        if pitch_spec(pitch) is not None:
+            if not getattr(self.vlib, "has_pitch", False):
+                raise VitsError(4, "this backend has no pitch shifter (include/vits_pitch.h)")
+            opts = SttsPitchOpts()
+            opts.flags |= STTS_FLAG_PITCH
+            opts.pitch_semitones = float(pitch)
+            return opts
+        return SttsOpts() if loudness is None else SttsLoudnessOpts()
 
     def _need_marks(self):
         if not self.has_marks:
@@ -117,8 +136,10 @@ class SttsModel:
     # ---- hot path ----------------------------------------------------------------------------
     def synthesize(self, ids, scales, sid, bert=None, phone_duration_extra=None, noise=None, seed=0, n_timesteps=0,
                    want_audio=True, want_mel=True, denoiser_strength=None, denoiser_filter_length=0, marks=False, sample_rate=None,
-                   loudness=None, loudness_out=None):
-        """One utterance.  ids int64 [5,T]; returns (audio float32 [S] or None, mel float32 [n_feats,T_y] or None).
+                   loudness=None, loudness_out=None, pitch=None):
+        """pitch: semitones in [-12, 12] (STTS_FLAG_PITCH, include/vits_pitch.h): the audio shifted behind the denoiser, before any
+        resampling; its length and the marks do not change.
+        One utterance.  ids int64 [5,T]; returns (audio float32 [S] or None, mel float32 [n_feats,T_y] or None).
         denoiser_strength (None = off) / denoiser_filter_length (0 = 1024): the vocoder-bias denoiser behind the clamp.
         marks=True (stts_synthesize_marks): a third value, token_ends int64 [T]; audio and marks are then at `sample_rate`
         (None / 0 = the voice's own).  loudness: a capi.loudness_spec() (STTS_FLAG_LOUDNESS): the audio normalised last in the chain
@@ -133,7 +154,7 @@ class SttsModel:
         T = ids.shape[1]
         scales = _f32(scales)
         keep = []
-        opts = SttsOpts() if loudness is None else SttsLoudnessOpts()
+        opts = self._opts_for(loudness, pitch if want_audio else None)
         if noise is not None:
             a = _f32(noise); keep.append(a)
             if a.ndim != 2 or a.shape[0] != self.hp.n_feats:
@@ -171,14 +192,17 @@ class SttsModel:
         return (audio, melo, ends) if marks else (audio, melo)
 
     def stream(self, ids, scales, sid, bert=None, phone_duration_extra=None, seed=0, n_timesteps=0, chunk_frames=64,
-               denoiser_strength=None, denoiser_filter_length=0, on_marks=None, loudness=None):
-        """Streaming form of synthesize() (stts_stream_open): a generator of float32 chunks of chunk_frames*hop samples whose
+               denoiser_strength=None, denoiser_filter_length=0, on_marks=None, loudness=None, pitch=None):
+        """pitch: refused, as loudness is.
+        Streaming form of synthesize() (stts_stream_open): a generator of float32 chunks of chunk_frames*hop samples whose
         concatenation equals synthesize()'s audio for the same arguments.  on_marks: called once with token_ends int64 [T]
         (vits_stream_marks) as soon as the stream is open.  loudness: refused (stts_stream_open refuses STTS_FLAG_LOUDNESS the same
         way; here before any device work)."""
         if loudness is not None:
             raise VitsError(4, "a stream cannot be loudness-normalised: an integrated-loudness or peak target needs the whole utterance "
                                "before the first chunk")
+        if pitch_spec(pitch) is not None:
+            raise VitsError(4, "a stream cannot be pitch-shifted: the phase recursion needs the frames before a chunk")
         if on_marks is not None:
             self._need_marks()
         if self._vocoder is None:
@@ -211,8 +235,10 @@ class SttsModel:
         return self._vocoder._drain(st, chunk_frames)
 
     def synthesize_batch(self, ids, lengths, scales, sid, bert=None, phone_duration_extra=None, seed=0, n_timesteps=0, item_seeds=None,
-                         denoiser_strength=None, denoiser_filter_length=0, marks=False, sample_rate=None, loudness=None, loudness_out=None):
-        """B independent utterances in one pass (stts_synthesize_batch): ids [B,5,T], lengths [B], sid [B];
+                         denoiser_strength=None, denoiser_filter_length=0, marks=False, sample_rate=None, loudness=None, loudness_out=None,
+                         pitch=None):
+        """pitch: as for synthesize, one value for the batch; every item is shifted from its own length.
+        B independent utterances in one pass (stts_synthesize_batch): ids [B,5,T], lengths [B], sid [B];
         returns (audio float32 [B,S] zero-padded, out_lengths int64 [B] in samples).  Item b equals
         synthesize(ids[b][:, :lengths[b]], ..., seed=item_seeds[b]) (seed + b without item seeds).  marks=True
         (stts_synthesize_batch_marks): a third value, token_ends int64 [B,T]; everything is then at `sample_rate`."""
@@ -224,7 +250,7 @@ class SttsModel:
         B, five, T = ids.shape
         b = None if bert is None else _f32(bert)
         p = None if phone_duration_extra is None else _f32(phone_duration_extra)
-        opts = SttsOpts() if loudness is None else SttsLoudnessOpts()
+        opts = self._opts_for(loudness, pitch)
         opts.seed = seed; opts.n_timesteps = n_timesteps
         self._denoise(opts, denoiser_strength, denoiser_filter_length)
         keep = []

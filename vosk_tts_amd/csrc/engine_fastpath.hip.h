@@ -308,7 +308,7 @@ static int device_error_word(int e) {
 
 static int synth_fast(vits_model* m, const int64_t* ids, const int64_t* lengths, int32_t B, int32_t Tx, const float* scales,
                       const int64_t* sid, const vits_synth_opts* opts, bool pcm, float pcm_scale, int rate, void** out, int64_t* out_samples,
-                      int64_t* out_lengths, int64_t* token_ends, const LoudReq& lq) {
+                      int64_t* out_lengths, int64_t* token_ends, const LoudReq& lq, const PitchReq& pq) {
   const vits_hparams& hp = m->hp;
   HIP_TRY(hipSetDevice(m->device));
   const ResampleTab* T = nullptr;  // (uploaded on the first call at this rate, before any capture)
@@ -399,6 +399,42 @@ static int synth_fast(vits_model* m, const int64_t* ids, const int64_t* lengths,
     }
     if (rc != VITS_OK) return rc;
   }
+  if (pq.on) {
+    // include/vits_pitch.h: the float, native-rate form of the graph as it is, then pitch, resample, normalise and the conversion as
+    // launches behind it on the same stream (the graph's own copy of the unshifted float audio to the host is not used)
+    TRY(phase2_launch(F, Bk, solo, false));
+    const long long S0 = (long long)TyB * hp.hop_length;
+    std::vector<long long> h_len(B);
+    for (int b = 0; b < B; ++b) h_len[b] = F->h_ylen[b] * hp.hop_length;
+    PitchTail pt;
+    const void* d_out = nullptr;
+    long long So = 0;
+    std::vector<float> loud_res;
+    int rc = pitch_tail_run(pt, Bk, F->stream, Bk->out_d, S0, Bk->len_y, hp.hop_length, h_len.data(), B, pq, T, lq, pcm, pcm_scale, &d_out, &So, &loud_res);
+    if (rc != VITS_OK) { hipStreamSynchronize(F->stream); return rc; }
+    const int64_t S = T ? T->P.n_out(Ty * hp.hop_length) : Ty * hp.hop_length;
+    const size_t esz = pcm ? sizeof(int16_t) : sizeof(float);
+    char* h_out = static_cast<char*>(malloc(esz * (size_t)B * S));
+    if (!h_out) { hipStreamSynchronize(F->stream); return fail(VITS_ERR_NOMEM, "host alloc failed"); }
+    hipError_t ce = hipMemcpy2DAsync(h_out, esz * (size_t)S, d_out, esz * (size_t)So, esz * (size_t)S, (size_t)B, hipMemcpyDeviceToHost, F->stream);
+    const hipError_t se = hipStreamSynchronize(F->stream);
+    if (ce == hipSuccess) ce = se;
+    if (ce == hipSuccess) ce = hipGetLastError();
+    if (ce != hipSuccess) { free(h_out); return fail(VITS_ERR_DEVICE, "pitch: %s", hipGetErrorString(ce)); }
+    if (*Bk->h_err) {
+      const int e2 = *Bk->h_err;
+      *Bk->h_err = 0;
+      hipMemsetAsync(Bk->d_err, 0, sizeof(int), F->stream);
+      free(h_out);
+      return device_error_word(e2);
+    }
+    if (lq.on) loud_req_results(lq, loud_res.data(), B);
+    *out = h_out;
+    *out_samples = S;
+    if (out_lengths) for (int b = 0; b < B; ++b) out_lengths[b] = T ? T->P.n_out(F->h_ylen[b] * hp.hop_length) : F->h_ylen[b] * hp.hop_length;
+    if (token_ends) for (int b = 0; b < B; ++b) memcpy(token_ends + (size_t)b * Tx, F->marks_h + (size_t)b * TxB, sizeof(int64_t) * Tx);
+    return VITS_OK;
+  }
   vits_session::RateOut* R = nullptr;
   if (T) TRY(back_rate_get(F, Bk, *T, &R));
   // (sizes in output samples)
@@ -446,7 +482,7 @@ static int synth_fast(vits_model* m, const int64_t* ids, const int64_t* lengths,
 
 static int synth_eager(vits_model* m, const int64_t* ids, const int64_t* lengths, int32_t B, int32_t Tx, const float* scales,
                        const int64_t* sid, const vits_synth_opts* opts, bool pcm, float pcm_scale, int rate, void** out, int64_t* out_samples,
-                       int64_t* out_lengths, int64_t* token_ends, const LoudReq& lq) {
+                       int64_t* out_lengths, int64_t* token_ends, const LoudReq& lq, const PitchReq& pq) {
   const vits_hparams& hp = m->hp;
   const ResampleTab* T = nullptr;
   if (rate) TRY(resample_get(m->device, hp.sampling_rate, rate, &T));
@@ -470,7 +506,13 @@ static int synth_eager(vits_model* m, const int64_t* ids, const int64_t* lengths
   const void* d_src = d_audio;
   const int64_t So = T ? T->P.n_out(S) : S;  // samples per item as returned
   std::vector<float> loud_res;
-  if (lq.on) {  // include/vits_loudness.h: the float waveform at the rate it is returned at, measured, then the gain (and the conversion)
+  PitchTail pt;
+  if (pq.on) {  // include/vits_pitch.h: pitch, resample, normalise and the conversion behind the decoder
+    std::vector<long long> h_len(B);
+    for (int b = 0; b < B; ++b) h_len[b] = ylen[b] * hp.hop_length;
+    long long So2 = 0;
+    TRY(pitch_tail_run(pt, s, s->stream, d_audio, S, s->len_y, hp.hop_length, h_len.data(), B, pq, T, lq, pcm, pcm_scale, &d_src, &So2, &loud_res));
+  } else if (lq.on) {  // include/vits_loudness.h: the float waveform at the rate it is returned at, measured, then the gain (and the conversion)
     const float* x_d = d_audio;
     if (T) {
       float* d_y = hs.dev_alloc<float>((size_t)B * So);
@@ -530,6 +572,8 @@ static int synth_dispatch(vits_model* m, const int64_t* ids, const int64_t* leng
   if (opts && (opts->flags & VITS_FLAG_LOUDNESS))
     TRY(loud_req(true, opts->loudness_mode, opts->loudness_target, opts->loudness_ceiling, opts->out_loudness, opts->out_gain,
                  rate ? rate : m->hp.sampling_rate, &lq));
+  PitchReq pq;  // (include/vits_pitch.h: the field behind the struct is read only under the flag)
+  TRY(pitch_req_opts(m, opts, &pq));
   static const bool env_off = getenv("VITS_NO_FASTPATH") != nullptr;
   if (m->hp.bert_dim > 0 && (!opts || !opts->bert)) return fail(VITS_ERR_ARG, "this voice is BERT-conditioned: the bert feed [B,%d,T_x] is required", m->hp.bert_dim);
   if (m->hp.bert_dim == 0 && opts && opts->bert) return fail(VITS_ERR_ARG, "the bert feed was given but this voice has no BERT projection (hparams.bert_dim == 0)");
@@ -542,8 +586,8 @@ static int synth_dispatch(vits_model* m, const int64_t* ids, const int64_t* leng
   for (int attempt = 0;; ++attempt) {
     tl_ps_timed_out = false;
     const int rc = (g_fast_path && !env_off && !injected)
-                       ? synth_fast(m, ids, lengths, B, Tx, scales, sid, opts, pcm, pcm_scale, rate, out, out_samples, out_lengths, token_ends, lq)
-                       : synth_eager(m, ids, lengths, B, Tx, scales, sid, opts, pcm, pcm_scale, rate, out, out_samples, out_lengths, token_ends, lq);
+                       ? synth_fast(m, ids, lengths, B, Tx, scales, sid, opts, pcm, pcm_scale, rate, out, out_samples, out_lengths, token_ends, lq, pq)
+                       : synth_eager(m, ids, lengths, B, Tx, scales, sid, opts, pcm, pcm_scale, rate, out, out_samples, out_lengths, token_ends, lq, pq);
     if (rc == VITS_OK || !tl_ps_timed_out || attempt) return rc;  // a persistent program timed out: once more, on launches
   }
 }

@@ -1,0 +1,560 @@
+// pitch.hip.h -- pitch-shifted output (include/vits_pitch.h): an identity-phase-locked vocoder that stretches the finished waveform by
+// P/Q, then the resampler (P -> Q).  Part of the ONE translation unit engine.hip (included there, after the denoiser, whose transform it
+// shares: dn_load, dn_fft, the DenoiseTab of n = 1024).
+//
+// Launches per group of items (every kernel derives an item's F_a, F_s and N_u from its length: no per-item host tables):
+//   pitch_analysis_kernel  one wave per frame, DN_FPB frames per workgroup, as denoise_frames_kernel: |X| and the phase as a 32-bit
+//                          fixed-point turn, [B][F_a + 2][NB]; the two rows behind an item's last frame are written as zeros
+//   pitch_phase_kernel     one workgroup per item, one thread per bin, a loop over the steps t.  Phi_{t-1}[k] stays in thread k's
+//                          register; a step stages m_t, adv and theta_i in LDS, tests the peak against the four neighbours, publishes
+//                          the peaks as one 64-bit ballot per wave and finds the nearest set bit either side of k in those nine words;
+//                          two barriers per step (the LDS is double-buffered by the parity of t).  The five global rows of the next
+//                          PT_AHEAD steps are in flight while one step computes: their addresses depend on t alone.
+//   pitch_synth_kernel     one wave per step: the interpolated magnitude times sincospif of the phase, packed to the half-size
+//                          spectrum, inverted by dn_fft, windowed: [B][F_s][n]
+//   pitch_ola_kernel       denoise_ola_kernel's gather with the frame count F_s of the item (an F_s of 2 or 3, which a 513-sample item
+//                          has at -12, is below what that kernel takes); 1 / sum w^2 from the DenoiseTab rows, and for the one case
+//                          they do not hold (F_s = 2: both neighbours missing) formed in double in the kernel
+//   pitch_geom_kernel      N_u / H and min(len, N_v) per item, for the resampler
+//   resample_kernel<float, true>   u -> y, cropped; pitch_short_kernel copies the items below n/2 + 1 samples
+#pragma once
+#include <memory>
+#include "../../include/vits_pitch.h"
+
+#define PT_N VITS_PITCH_FRAME
+#define PT_M (PT_N / 2)
+#define PT_H (PT_N / 4)
+#define PT_NB (PT_M + 1)
+#define PT_LOG2M 9
+#define PT_WAVES 9                       // of pitch_phase_kernel: 576 threads, bin k = threadIdx.x < PT_NB
+#define PT_AHEAD 4                       // steps whose rows pitch_phase_kernel has in flight
+static_assert(PT_N == VITS_DENOISE_MAX_FILTER, "the pitch stage runs on the denoiser's 1024-point tables");
+static_assert(PT_WAVES * 64 >= PT_NB, "a thread per bin");
+
+__host__ __device__ __forceinline__ long long pt_frames_a(long long len) { return len >= PT_M + 1 ? 1 + len / PT_H : 0; }
+__host__ __device__ __forceinline__ long long pt_frames_s(long long len, int P, int Q) {
+  const long long fa = pt_frames_a(len);
+  return fa ? ((fa + 1) * P + Q - 1) / Q : 0;
+}
+
+__device__ __forceinline__ unsigned pt_theta(float re, float im) {
+  if (re == 0.f && im == 0.f) return 0u;
+  const float t = __fdiv_rn(atan2f(im, re), 6.28318530717958647692f);
+  return (unsigned)(long long)rintf(t * 4294967296.f);  // |t| <= 0.5: the product is exact, the cast keeps the low 32 bits
+}
+
+// m_t[k] of step 2: one rounding per operation, as the restatement has them
+__device__ __forceinline__ float pt_interp(float a, float b, float alpha) {
+  return __fadd_rn(__fmul_rn(__fsub_rn(1.f, alpha), a), __fmul_rn(alpha, b));
+}
+
+// Rows [0, F_a + 2) of every item: wave w of workgroup blockIdx.x owns row blockIdx.x * DN_FPB + w.  x and len as in
+// denoise_frames_kernel (x_off = 0); mag / th: [B][a_bstride], row f at f * PT_NB.
+__global__ __launch_bounds__(64 * DN_FPB) void pitch_analysis_kernel(const float* __restrict__ x, long long x_bstride, long long x_n,
+                                                                     const int* __restrict__ len_frames, long long len_mul,
+                                                                     const float* __restrict__ win, const float2* __restrict__ tw,
+                                                                     float* __restrict__ mag, unsigned* __restrict__ th, long long a_bstride) {
+  __shared__ float lds[DN_FPB][4][DN_PLANE];
+  const int wv = threadIdx.x >> 6, t = threadIdx.x & 63;
+  const int b = blockIdx.y;
+  const long long len = len_frames ? len_frames[b] * len_mul : len_mul;
+  const long long Fa = pt_frames_a(len);
+  if (Fa == 0 || (long long)blockIdx.x * DN_FPB >= Fa + 2) return;  // uniform over the workgroup
+  const long long f = (long long)blockIdx.x * DN_FPB + wv;
+  const bool valid = f < Fa;
+  float *ar = lds[wv][0], *ai = lds[wv][1], *br = lds[wv][2], *bi = lds[wv][3];
+  const float* xb = x + (long long)b * x_bstride;
+  for (int m = t; m < PT_M; m += 64) {
+    float v0 = 0.f, v1 = 0.f;
+    if (valid) {
+      const long long p = f * PT_H + 2 * m;
+      v0 = dn_load(xb, p, PT_M, len, 0, x_n) * win[2 * m];
+      v1 = dn_load(xb, p + 1, PT_M, len, 0, x_n) * win[2 * m + 1];
+    }
+    ar[DN_PAD(m)] = v0;
+    ai[DN_PAD(m)] = v1;
+  }
+  __syncthreads();
+  dn_fft(ar, ai, br, bi, PT_M, PT_LOG2M, tw, t);
+  if (f >= Fa + 2) return;
+  float* mo = mag + (long long)b * a_bstride + f * PT_NB;
+  unsigned* to = th + (long long)b * a_bstride + f * PT_NB;
+  for (int k = t; k <= (PT_M >> 1); k += 64) {  // the unpacking of denoise_frames_kernel
+    const int kp = PT_M - k, kq = kp & (PT_M - 1);
+    const float zkr = ar[DN_PAD(k)], zki = ai[DN_PAD(k)], zpr = ar[DN_PAD(kq)], zpi = ai[DN_PAD(kq)];
+    const float2 w = tw[k];
+    const float er = 0.5f * (zkr + zpr), ei = 0.5f * (zki - zpi);
+    const float o_r = 0.5f * (zki + zpi), o_i = -0.5f * (zkr - zpr);
+    const float tr = w.x * o_r - w.y * o_i, ti = w.x * o_i + w.y * o_r;
+    const float xkr = er + tr, xki = ei + ti, xpr = er - tr, xpi = -(ei - ti);
+    mo[k] = valid ? sqrtf(xkr * xkr + xki * xki) : 0.f;
+    mo[kp] = valid ? sqrtf(xpr * xpr + xpi * xpi) : 0.f;
+    to[k] = valid ? pt_theta(xkr, xki) : 0u;
+    to[kp] = valid ? pt_theta(xpr, xpi) : 0u;
+  }
+}
+
+// One workgroup per item (blockIdx.x), thread k = bin k.  phi: [B][p_bstride], row t at t * PT_NB.
+__global__ __launch_bounds__(64 * PT_WAVES) void pitch_phase_kernel(const float* __restrict__ mag, const unsigned* __restrict__ th,
+                                                                    long long a_bstride, const int* __restrict__ len_frames,
+                                                                    long long len_mul, int P, int Q, unsigned* __restrict__ phi,
+                                                                    long long p_bstride) {
+  __shared__ float s_m[2][PT_NB + 4];  // m[k] at k + 2; -1 either side
+  __shared__ unsigned s_adv[2][PT_NB], s_th[2][PT_NB];
+  __shared__ unsigned long long s_pk[2][PT_WAVES];
+  const int b = blockIdx.x, k = threadIdx.x, wv = k >> 6, lane = k & 63;
+  const long long len = len_frames ? len_frames[b] * len_mul : len_mul;
+  const long long Fs = pt_frames_s(len, P, Q);
+  if (Fs == 0) return;
+  const bool act = k < PT_NB;
+  const int kc = act ? k : 0;  // (the idle lanes of the last wave form valid addresses and touch nothing)
+  const float* mb = mag + (long long)b * a_bstride + kc;
+  const unsigned* tb = th + (long long)b * a_bstride + kc;
+  unsigned* pb = phi + (long long)b * p_bstride + kc;
+  if (k < 2) {
+    s_m[0][k] = s_m[1][k] = -1.f;
+    s_m[0][PT_NB + 2 + k] = s_m[1][PT_NB + 2 + k] = -1.f;
+  }
+  unsigned ph = act ? tb[0] : 0u;  // Phi_0 = theta_0
+  if (act) pb[0] = ph;
+  if (Fs <= 1) return;
+  // The rows of the next PT_AHEAD steps are in flight while one step computes: the addresses of step t depend on t alone.  Every lane
+  // loads -- the idle lanes of the last wave read bin 0 -- and past the last step the issue loads the last step's rows again, so it has
+  // no branch around a load.  i_t and (t Q mod P) advance by Q / P and Q mod P in 32-bit scalar arithmetic: a 64-bit division per
+  // step, which every lane would carry, cost more than the rest of the step (measured: 1.2 us a step with it).
+  float q_a[PT_AHEAD], q_b[PT_AHEAD];
+  unsigned q_tj[PT_AHEAD], q_tj1[PT_AHEAD], q_ti[PT_AHEAD];
+  int q_r[PT_AHEAD];
+  const int q_div = Q / P, q_rem = Q % P;
+  long long n_t = 1;                    // the step the next issue is for
+  int n_i = q_div, n_r = q_rem, n_j = 0;  // its i_t, t Q mod P and i_{t-1}
+  auto issue = [&](int d) {
+    q_r[d] = n_r;
+    q_a[d] = mb[(long long)n_i * PT_NB]; q_b[d] = mb[(long long)(n_i + 1) * PT_NB];
+    q_tj[d] = tb[(long long)n_j * PT_NB]; q_tj1[d] = tb[(long long)(n_j + 1) * PT_NB]; q_ti[d] = tb[(long long)n_i * PT_NB];
+    if (n_t + 1 < Fs) {  // (uniform)
+      ++n_t;
+      n_j = n_i;
+      n_i += q_div; n_r += q_rem;
+      if (n_r >= P) { n_r -= P; ++n_i; }
+    }
+  };
+#pragma unroll
+  for (int d = 0; d < PT_AHEAD; ++d) issue(d);
+  for (long long tau0 = 1; tau0 < Fs; tau0 += PT_AHEAD) {
+#pragma unroll
+   for (int d = 0; d < PT_AHEAD; ++d) {
+    const long long tau = tau0 + d;
+    if (tau >= Fs) break;  // (uniform)
+    const float c_a = q_a[d], c_b = q_b[d];
+    const unsigned c_tj = q_tj[d], c_tj1 = q_tj1[d], c_ti = q_ti[d];
+    const int c_r = q_r[d];
+    issue(d);
+    const int pp = (int)(tau & 1);
+    const float alpha = __fdiv_rn((float)c_r, (float)P);
+    const float m = pt_interp(c_a, c_b, alpha);
+    const unsigned adv = ph + c_tj1 - c_tj;
+    if (act) { s_m[pp][k + 2] = m; s_adv[pp][k] = adv; s_th[pp][k] = c_ti; }
+    __syncthreads();
+    bool pk = false;
+    if (act) pk = m > s_m[pp][k + 1] && m > s_m[pp][k] && m >= s_m[pp][k + 3] && m >= s_m[pp][k + 4];
+    const unsigned long long bal = __ballot(pk);
+    if (lane == 0) s_pk[pp][wv] = bal;
+    __syncthreads();
+    if (act) {
+      int lo = -1, hi = -1;  // the nearest peak at or below k, at or above k
+      unsigned long long w = s_pk[pp][wv] & (~0ull >> (63 - lane));
+      for (int ww = wv;;) {
+        if (w) { lo = ww * 64 + 63 - __clzll((long long)w); break; }
+        if (--ww < 0) break;
+        w = s_pk[pp][ww];
+      }
+      w = s_pk[pp][wv] & (~0ull << lane);
+      for (int ww = wv;;) {
+        if (w) { hi = ww * 64 + __ffsll((unsigned long long)w) - 1; break; }
+        if (++ww >= PT_WAVES) break;
+        w = s_pk[pp][ww];
+      }
+      const int own = lo < 0 ? hi : (hi < 0 ? lo : (hi - k < k - lo ? hi : lo));  // a tie goes to the lower peak
+      ph = own < 0 ? adv : s_adv[pp][own] + c_ti - s_th[pp][own];
+      pb[tau * PT_NB] = ph;
+    }
+   }
+  }
+}
+
+// Steps [0, F_s) of every item: wave w of workgroup blockIdx.x owns step blockIdx.x * DN_FPB + w.  fr: [B][fr_bstride], frame t at t * n.
+__global__ __launch_bounds__(64 * DN_FPB) void pitch_synth_kernel(const float* __restrict__ mag, long long a_bstride,
+                                                                  const unsigned* __restrict__ phi, long long p_bstride,
+                                                                  const int* __restrict__ len_frames, long long len_mul, int P, int Q,
+                                                                  const float* __restrict__ win, const float2* __restrict__ tw,
+                                                                  float* __restrict__ fr, long long fr_bstride) {
+  __shared__ float lds[DN_FPB][4][DN_PLANE];
+  const int wv = threadIdx.x >> 6, t = threadIdx.x & 63;
+  const int b = blockIdx.y;
+  const long long len = len_frames ? len_frames[b] * len_mul : len_mul;
+  const long long Fs = pt_frames_s(len, P, Q);
+  if ((long long)blockIdx.x * DN_FPB >= Fs) return;  // uniform over the workgroup
+  const long long tau = (long long)blockIdx.x * DN_FPB + wv;
+  const bool valid = tau < Fs;
+  float *ar = lds[wv][0], *ai = lds[wv][1], *br = lds[wv][2], *bi = lds[wv][3];
+  const long long tq = tau * Q, i = tq / P;
+  const float alpha = __fdiv_rn((float)(int)(tq - i * P), (float)P);
+  const float* m0 = mag + (long long)b * a_bstride + i * PT_NB;
+  const unsigned* pr = phi + (long long)b * p_bstride + tau * PT_NB;
+  for (int k = t; k <= (PT_M >> 1); k += 64) {
+    const int kp = PT_M - k;
+    float xkr = 0.f, xki = 0.f, xpr = 0.f, xpi = 0.f;
+    if (valid) {
+      const float mk = pt_interp(m0[k], m0[PT_NB + k], alpha), mp = pt_interp(m0[kp], m0[PT_NB + kp], alpha);
+      float s, c;
+      sincospif(2.f * ((float)(int)pr[k] * 2.3283064365386963e-10f), &s, &c);  // 2^-32: the turn in [-0.5, 0.5)
+      xkr = mk * c; xki = k > 0 ? mk * s : 0.f;
+      sincospif(2.f * ((float)(int)pr[kp] * 2.3283064365386963e-10f), &s, &c);
+      xpr = mp * c; xpi = k > 0 ? mp * s : 0.f;  // (kp = n/2 pairs with k = 0: both imaginary parts are dropped)
+    }
+    // the packing of denoise_frames_kernel: Z'[k] = E2 + i O2, stored conjugated so that the forward passes invert it
+    const float2 w = tw[k];
+    const float e2r = 0.5f * (xkr + xpr), e2i = 0.5f * (xki - xpi);
+    const float dr = 0.5f * (xkr - xpr), di = 0.5f * (xki + xpi);
+    const float o2r = dr * w.x + di * w.y, o2i = di * w.x - dr * w.y;
+    ar[DN_PAD(k)] = e2r - o2i;
+    ai[DN_PAD(k)] = -(e2i + o2r);
+    if (k > 0 && kp != k) {
+      ar[DN_PAD(kp)] = e2r + o2i;
+      ai[DN_PAD(kp)] = -(o2r - e2i);
+    }
+  }
+  __syncthreads();
+  dn_fft(ar, ai, br, bi, PT_M, PT_LOG2M, tw, t);
+  if (!valid) return;
+  const float inv_m = 1.0f / (float)PT_M;
+  float2* of = reinterpret_cast<float2*>(fr + (long long)b * fr_bstride + tau * PT_N);
+  for (int m = t; m < PT_M; m += 64)
+    of[m] = make_float2(ar[DN_PAD(m)] * inv_m * win[2 * m], -ai[DN_PAD(m)] * inv_m * win[2 * m + 1]);
+}
+
+// u[b][j], j < n_count: the overlap-add of the item's F_s frames, exactly 0 at and beyond N_u = H (F_s - 1).
+__global__ __launch_bounds__(256) void pitch_ola_kernel(const float* __restrict__ fr, long long fr_bstride, const int* __restrict__ len_frames,
+                                                        long long len_mul, int P, int Q, const float* __restrict__ inv_env,
+                                                        float* __restrict__ u, long long u_bstride, long long n_count) {
+  const int b = blockIdx.y;
+  const long long j = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (j >= n_count) return;
+  const long long len = len_frames ? len_frames[b] * len_mul : len_mul;
+  const long long Fs = pt_frames_s(len, P, Q);
+  float v = 0.f;
+  if (j < PT_H * (Fs - 1)) {
+    const long long p = j + PT_M, fl = p / PT_H;  // fl in [2, F_s]
+    const int r = (int)(p - fl * PT_H);
+    const bool head = fl < 3, tail = fl >= Fs;
+    const float* fb = fr + (long long)b * fr_bstride;
+    float acc = 0.f;
+    for (int d = 3; d >= 0; --d) {
+      const long long f = fl - d;
+      if (f >= 0 && f < Fs) acc += fb[f * PT_N + r + d * PT_H];
+    }
+    float e;
+    if (head && tail) {  // F_s = 2: frames 0 and 1 alone
+      const double s1 = sinpi((double)(r + PT_H) / PT_N), s2 = sinpi((double)(r + 2 * PT_H) / PT_N);
+      e = (float)(1.0 / (s1 * s1 * s1 * s1 + s2 * s2 * s2 * s2));
+    } else {
+      e = inv_env[(head ? 0 : (tail ? 2 : 1)) * PT_H + r];
+    }
+    v = acc * e;
+  }
+  u[(long long)b * u_bstride + j] = v;
+}
+
+// nu[b] = N_u / H (the resampler's input length in units of H) and crop[b] = min(len, N_v); both 0 for an item below n/2 + 1
+__global__ void pitch_geom_kernel(const int* __restrict__ len_frames, long long len_mul, int B, int P, int Q, int* __restrict__ nu,
+                                  int* __restrict__ crop) {
+  const int b = blockIdx.x * blockDim.x + threadIdx.x;
+  if (b >= B) return;
+  const long long len = len_frames ? len_frames[b] * len_mul : len_mul;
+  const long long Fs = pt_frames_s(len, P, Q);
+  const long long Nu = Fs ? PT_H * (Fs - 1) : 0, Nv = (Nu * Q + P - 1) / P;
+  nu[b] = (int)(Nu / PT_H);
+  crop[b] = (int)(len < Nv ? len : Nv);
+}
+
+// the items shorter than n/2 + 1 samples come back as they are (grid (2, B): 512 samples cover them)
+__global__ __launch_bounds__(256) void pitch_short_kernel(const float* __restrict__ x, long long x_bstride, const int* __restrict__ len_frames,
+                                                          long long len_mul, float* __restrict__ y, long long y_bstride, long long n_count) {
+  const int b = blockIdx.y;
+  const long long j = (long long)blockIdx.x * 256 + threadIdx.x;
+  const long long len = len_frames ? len_frames[b] * len_mul : len_mul;
+  if (len >= PT_M + 1 || j >= len || j >= n_count) return;
+  y[(long long)b * y_bstride + j] = x[(long long)b * x_bstride + j];
+}
+
+// ---- host ---------------------------------------------------------------------------------------------------------------
+struct PitchReq { bool on = false; int P = 1, Q = 1; };
+
+static int pitch_plan(float semitones, int* P, int* Q) {
+  if (!(fabsf(semitones) <= (float)VITS_PITCH_MAX_SEMITONES))  // (NaN fails the comparison)
+    return fail(VITS_ERR_ARG, "pitch: %g semitones outside [-%d, %d]", (double)semitones, VITS_PITCH_MAX_SEMITONES, VITS_PITCH_MAX_SEMITONES);
+  const long p0 = lround(1000.0 * pow(2.0, (double)semitones / 12.0));
+  long a = p0, b = 1000;
+  while (b) { const long t = a % b; a = b; b = t; }
+  *P = (int)(p0 / a);
+  *Q = (int)(1000 / a);
+  return VITS_OK;
+}
+
+// The resampler tables of the ratios in use, per (device, P, Q).  A server may see any of 1501 ratios, so unlike the output-rate tables
+// (which captured graphs point into) these are evicted, least recently used first; a call in flight keeps its table alive.
+#define PT_MAX_TABS 32
+static std::mutex g_pt_mu;
+static std::map<std::tuple<int, int, int>, std::pair<std::shared_ptr<ResampleTab>, uint64_t>> g_pt_tabs;
+static uint64_t g_pt_tick = 0;
+
+static int pitch_tab_get(int device, int P, int Q, std::shared_ptr<ResampleTab>* out) {
+  std::lock_guard<std::mutex> g(g_pt_mu);
+  const auto key = std::make_tuple(device, P, Q);
+  auto it = g_pt_tabs.find(key);
+  if (it == g_pt_tabs.end()) {
+    std::shared_ptr<ResampleTab> T(new ResampleTab, [](ResampleTab* t) { if (t->d) hipFree(t->d); delete t; });
+    TRY(resample_plan(P, Q, &T->P));
+    HIP_TRY(hipSetDevice(device));
+    TRY(resample_upload(device, *T));
+    if (g_pt_tabs.size() >= PT_MAX_TABS) {
+      auto old = g_pt_tabs.begin();
+      for (auto i = g_pt_tabs.begin(); i != g_pt_tabs.end(); ++i) if (i->second.second < old->second.second) old = i;
+      g_pt_tabs.erase(old);
+    }
+    it = g_pt_tabs.emplace(key, std::make_pair(T, 0)).first;
+  }
+  it->second.second = ++g_pt_tick;
+  *out = it->second.first;
+  return VITS_OK;
+}
+
+// bytes of scratch an item of `len` samples takes in a group (the strides of a group are those of its longest item)
+static size_t pitch_item_bytes(long long len, int P, int Q) {
+  const long long Fa = pt_frames_a(len), Fs = pt_frames_s(len, P, Q);
+  if (!Fa) return 2 * sizeof(int);
+  return (size_t)(Fa + 2) * PT_NB * 8 + (size_t)Fs * PT_NB * 4 + (size_t)Fs * PT_N * 4 + (size_t)(Fs - 1) * PT_H * 4 + 2 * sizeof(int) + 64;
+}
+
+// y[b][0 .. n_count) = the shifted item b, for B items on `stream`; x / len_frames / len_mul as in denoise_launch (device pointers),
+// h_len their lengths on the host.  Allocates its scratch and waits for the stream before it frees it: not capturable.  y is not x.
+// u_out (nullable): the stretch door -- u goes to u_out[b * u_bstride + j], j < u_bstride, and nothing is resampled.
+static int pitch_run(int device, hipStream_t stream, const float* x, long long x_bstride, long long x_n, const int* len_frames, long long len_mul,
+                     const long long* h_len, int B, int P, int Q, float* y, long long y_bstride, long long n_count, float* u_out,
+                     long long u_bstride) {
+  if (B <= 0) return VITS_OK;
+  const DenoiseTab* D = nullptr;
+  TRY(denoise_get(device, PT_N, &D));
+  std::shared_ptr<ResampleTab> R;  // (held until the stream has been waited for)
+  if (!u_out) TRY(pitch_tab_get(device, P, Q, &R));
+  // groups of consecutive items whose scratch fits
+  std::vector<std::pair<int, int>> groups;  // (first item, count)
+  size_t need = 0;
+  for (int b0 = 0; b0 < B;) {
+    long long mx = 0;
+    int c = 0;
+    while (b0 + c < B && c < 65535) {
+      const long long m2 = std::max(mx, h_len[b0 + c]);
+      if (pitch_item_bytes(m2, P, Q) * (size_t)(c + 1) > (size_t)VITS_PITCH_MAX_SCRATCH) break;
+      mx = m2;
+      ++c;
+    }
+    if (!c) return fail(VITS_ERR_UNSUPPORTED, "pitch: an item of %lld samples needs %zu bytes of scratch at %d/%d (limit %lld)", h_len[b0],
+                        pitch_item_bytes(h_len[b0], P, Q), P, Q, (long long)VITS_PITCH_MAX_SCRATCH);
+    need = std::max(need, pitch_item_bytes(mx, P, Q) * (size_t)c);
+    groups.emplace_back(b0, c);
+    b0 += c;
+  }
+  HIP_TRY(hipSetDevice(device));
+  char* scr = nullptr;
+  if (hipMalloc((void**)&scr, need) != hipSuccess) return fail(VITS_ERR_NOMEM, "pitch: scratch alloc of %zu bytes failed", need);
+  for (const auto& g : groups) {
+    const int b0 = g.first, c = g.second;
+    long long mx = 0;
+    for (int b = 0; b < c; ++b) mx = std::max(mx, h_len[b0 + b]);
+    const float* xg = x + (long long)b0 * x_bstride;
+    const int* lg = len_frames ? len_frames + b0 : nullptr;
+    const long long Fa = pt_frames_a(mx), Fs = pt_frames_s(mx, P, Q);
+    if (Fa) {
+      const long long a_bs = (Fa + 2) * PT_NB, p_bs = Fs * PT_NB, f_bs = Fs * PT_N, u_bs = (Fs - 1) * PT_H;
+      char* p = scr;
+      float* d_mag = reinterpret_cast<float*>(p); p += sizeof(float) * (size_t)c * a_bs;
+      unsigned* d_th = reinterpret_cast<unsigned*>(p); p += sizeof(unsigned) * (size_t)c * a_bs;
+      unsigned* d_phi = reinterpret_cast<unsigned*>(p); p += sizeof(unsigned) * (size_t)c * p_bs;
+      p += (8 - (p - scr) % 8) % 8;  // (the frames are written as float2)
+      float* d_fr = reinterpret_cast<float*>(p); p += sizeof(float) * (size_t)c * f_bs;
+      float* d_u = reinterpret_cast<float*>(p); p += sizeof(float) * (size_t)c * u_bs;
+      int* d_nu = reinterpret_cast<int*>(p); p += sizeof(int) * (size_t)c;
+      int* d_crop = reinterpret_cast<int*>(p);
+      hipLaunchKernelGGL(pitch_analysis_kernel, dim3((unsigned)((Fa + 2 + DN_FPB - 1) / DN_FPB), c), dim3(64 * DN_FPB), 0, stream, xg, x_bstride,
+                         x_n, lg, len_mul, D->d_win, D->d_tw, d_mag, d_th, a_bs);
+      hipLaunchKernelGGL(pitch_phase_kernel, dim3(c), dim3(64 * PT_WAVES), 0, stream, d_mag, d_th, a_bs, lg, len_mul, P, Q, d_phi, p_bs);
+      hipLaunchKernelGGL(pitch_synth_kernel, dim3((unsigned)((Fs + DN_FPB - 1) / DN_FPB), c), dim3(64 * DN_FPB), 0, stream, d_mag, a_bs, d_phi,
+                         p_bs, lg, len_mul, P, Q, D->d_win, D->d_tw, d_fr, f_bs);
+      if (u_out) {
+        hipLaunchKernelGGL(pitch_ola_kernel, dim3((unsigned)((u_bstride + 255) / 256), c), dim3(256), 0, stream, d_fr, f_bs, lg, len_mul, P, Q,
+                           D->d_env, u_out + (long long)b0 * u_bstride, u_bstride, u_bstride);
+      } else {
+        hipLaunchKernelGGL(pitch_ola_kernel, dim3((unsigned)((u_bs + 255) / 256), c), dim3(256), 0, stream, d_fr, f_bs, lg, len_mul, P, Q, D->d_env,
+                           d_u, u_bs, u_bs);
+        hipLaunchKernelGGL(pitch_geom_kernel, dim3((unsigned)((c + 63) / 64)), dim3(64), 0, stream, lg, len_mul, c, P, Q, d_nu, d_crop);
+        resample_launch_crop(stream, *R, d_u, u_bs, u_bs, d_nu, PT_H, d_crop, c, y + (long long)b0 * y_bstride, y_bstride, n_count);
+      }
+    } else if (u_out) {
+      hipMemsetAsync(u_out + (long long)b0 * u_bstride, 0, sizeof(float) * (size_t)c * u_bstride, stream);
+    } else {
+      for (int b = 0; b < c; ++b) hipMemsetAsync(y + (long long)(b0 + b) * y_bstride, 0, sizeof(float) * (size_t)n_count, stream);
+    }
+    if (!u_out)
+      hipLaunchKernelGGL(pitch_short_kernel, dim3(2, c), dim3(256), 0, stream, xg, x_bstride, lg, len_mul, y + (long long)b0 * y_bstride, y_bstride,
+                         n_count);
+  }
+  hipError_t e = hipGetLastError();
+  const hipError_t e2 = hipStreamSynchronize(stream);
+  hipFree(scr);
+  if (e == hipSuccess) e = e2;
+  if (e != hipSuccess) return fail(VITS_ERR_DEVICE, "pitch: %s", hipGetErrorString(e));
+  return VITS_OK;
+}
+
+// what a shifting entry point of a vocoder needs checked before any work is queued
+static int pitch_req(const vits_model* v, float semitones, PitchReq* q) {
+  q->on = false;
+  int P = 1, Q = 1;
+  TRY(pitch_plan(semitones, &P, &Q));
+  if (P == Q) return VITS_OK;  // the identity: the call as it was
+  if (v->hp.hop_length % PT_H)
+    return fail(VITS_ERR_UNSUPPORTED, "pitch: the vocoder's hop_length %d is not a multiple of the pitch stage's hop %d", v->hp.hop_length, PT_H);
+  ResamplePlan rp;
+  TRY(resample_plan(P, Q, &rp));
+  q->on = true; q->P = P; q->Q = Q;
+  return VITS_OK;
+}
+
+// VITS_FLAG_PITCH of a call: under the flag `opts` is the `base` of a vits_synth_opts_pitch, whose last field is read only then
+static int pitch_req_opts(const vits_model* v, const vits_synth_opts* opts, PitchReq* q) {
+  q->on = false;
+  if (!opts || !(opts->flags & VITS_FLAG_PITCH)) return VITS_OK;
+  static_assert(offsetof(vits_synth_opts_pitch, base) == 0, "the extended options begin with the plain ones");
+  return pitch_req(v, reinterpret_cast<const vits_synth_opts_pitch*>(opts)->pitch_semitones, q);
+}
+
+// The tail of a flagged vits_synthesize* call behind the decoder: pitch, resample, normalise, conversion, as launches on `stream` from
+// the float native-rate waveform x [B, S] on the device (item b is len_y[b] * hop samples, h_len[b] on the host).  The buffers are the
+// call's own (freed with the PitchTail); *d_out is [B, *So] of float or int16.
+struct PitchTail {
+  std::vector<void*> bufs;
+  ~PitchTail() { for (void* p : bufs) hipFree(p); }
+  void* alloc(size_t bytes) {
+    void* p = nullptr;
+    if (hipMalloc(&p, bytes ? bytes : 1) != hipSuccess) { (void)hipGetLastError(); return nullptr; }
+    bufs.push_back(p);
+    return p;
+  }
+};
+static int pitch_tail_run(PitchTail& pt, vits_session* s, hipStream_t stream, const float* x, long long S, const int* len_y, int hop,
+                          const long long* h_len, int B, const PitchReq& pq, const ResampleTab* T, const LoudReq& lq, bool pcm, float pcm_scale,
+                          const void** d_out, long long* So_out, std::vector<float>* loud_res) {
+  const int device = s->m->device;
+  float* d_p = static_cast<float*>(pt.alloc(sizeof(float) * (size_t)B * S));
+  if (!d_p) return fail(VITS_ERR_NOMEM, "pitch: device alloc failed");
+  TRY(pitch_run(device, stream, x, S, S, len_y, hop, h_len, B, pq.P, pq.Q, d_p, S, S, nullptr, 0));
+  const long long So = T ? T->P.n_out(S) : S;
+  const size_t esz = pcm ? sizeof(int16_t) : sizeof(float);
+  *So_out = So;
+  *d_out = d_p;
+  if (lq.on) {
+    const float* x2 = d_p;
+    if (T) {
+      float* d_y = static_cast<float*>(pt.alloc(sizeof(float) * (size_t)B * So));
+      if (!d_y) return fail(VITS_ERR_NOMEM, "pitch: device alloc failed");
+      resample_launch<float>(stream, *T, d_p, S, 0, S, len_y, hop, B, d_y, So, 0, So, 1.f, nullptr);
+      x2 = d_y;
+    }
+    char* d_scr = static_cast<char*>(pt.alloc(loud_scratch_bytes(B, So)));
+    void* d_n = pt.alloc(esz * (size_t)B * So);
+    if (!d_scr || !d_n) return fail(VITS_ERR_NOMEM, "pitch: device alloc failed");
+    LoudScratch LS;
+    loud_scratch_layout(B, So, d_scr, &LS);
+    const int rL = T ? T->P.L : 1, rM = T ? T->P.M : 1;
+    loud_measure_launch(stream, lq.P, lq.prm, LS, x2, So, So, len_y, hop, rL, rM, B, s);
+    if (pcm) loud_apply_launch<int16_t>(stream, LS, x2, So, So, len_y, hop, rL, rM, B, static_cast<int16_t*>(d_n), So, So, pcm_scale, s);
+    else loud_apply_launch<float>(stream, LS, x2, So, So, len_y, hop, rL, rM, B, static_cast<float*>(d_n), So, So, 1.f, s);
+    loud_res->resize((size_t)B * 4);
+    hipMemcpyAsync(loud_res->data(), LS.res, sizeof(float) * loud_res->size(), hipMemcpyDeviceToHost, stream);
+    *d_out = d_n;
+  } else if (T) {
+    void* d_y = pt.alloc(esz * (size_t)B * So);
+    if (!d_y) return fail(VITS_ERR_NOMEM, "pitch: device alloc failed");
+    if (pcm) resample_launch<int16_t>(stream, *T, d_p, S, 0, S, len_y, hop, B, static_cast<int16_t*>(d_y), So, 0, So, pcm_scale, nullptr);
+    else resample_launch<float>(stream, *T, d_p, S, 0, S, len_y, hop, B, static_cast<float*>(d_y), So, 0, So, 1.f, nullptr);
+    *d_out = d_y;
+  } else if (pcm) {
+    int16_t* d_pcm = static_cast<int16_t*>(pt.alloc(sizeof(int16_t) * (size_t)B * S));
+    if (!d_pcm) return fail(VITS_ERR_NOMEM, "pitch: device alloc failed");
+    hipLaunchKernelGGL(pcm16_kernel, dim3(cdiv((int)S, 256), B), dim3(256), 0, stream, d_p, S, d_pcm, S, S, pcm_scale, (const SynthDev*)nullptr);
+    *d_out = d_pcm;
+  }
+  return VITS_OK;
+}
+
+// ---- entry points ----------------------------------------------------------------------------------------------------
+int vits_pitch_plan(float semitones, int32_t* P, int32_t* Q) {
+  int p = 1, q = 1;
+  TRY(pitch_plan(semitones, &p, &q));
+  if (P) *P = p;
+  if (Q) *Q = q;
+  return VITS_OK;
+}
+
+static int pitch_op(int device, const float* x, const int64_t* lengths, int32_t B, int64_t N, float semitones, float* y, bool stretch) {
+  if (!x || !lengths || !y || B <= 0 || B > 65535 || N <= 0 || N >= (1LL << 31)) return fail(VITS_ERR_ARG, "pitch: bad argument");
+  int P = 1, Q = 1;
+  TRY(pitch_plan(semitones, &P, &Q));
+  std::vector<int> len32(B);
+  std::vector<long long> len64(B);
+  for (int b = 0; b < B; ++b) {
+    if (lengths[b] < 0 || lengths[b] > N) return fail(VITS_ERR_ARG, "pitch: length %lld of item %d outside [0, N = %lld]", (long long)lengths[b], b, (long long)N);
+    len32[b] = (int)lengths[b];
+    len64[b] = lengths[b];
+  }
+  if (P == Q) {
+    if (stretch) return fail(VITS_ERR_ARG, "pitch: %g semitones is the identity (P = Q): there is no stretch to return", (double)semitones);
+    for (int b = 0; b < B; ++b) {
+      memcpy(y + (size_t)b * N, x + (size_t)b * N, sizeof(float) * (size_t)lengths[b]);
+      memset(y + (size_t)b * N + lengths[b], 0, sizeof(float) * (size_t)(N - lengths[b]));
+    }
+    return VITS_OK;
+  }
+  const long long Ny = stretch ? (long long)PT_H * (((N / PT_H + 2) * P + Q - 1) / Q - 1) : N;
+  HIP_TRY(hipSetDevice(device));
+  float *dx = nullptr, *dy = nullptr;
+  int* dl = nullptr;
+  hipError_t e = hipMalloc((void**)&dx, sizeof(float) * (size_t)B * N);
+  if (e == hipSuccess) e = hipMalloc((void**)&dy, sizeof(float) * (size_t)B * Ny);
+  if (e == hipSuccess) e = hipMalloc((void**)&dl, sizeof(int) * B);
+  // every item's own samples only: what lies at and beyond lengths[b] never reaches the device
+  if (e == hipSuccess) e = hipMemset(dx, 0, sizeof(float) * (size_t)B * N);
+  for (int b = 0; b < B && e == hipSuccess; ++b)
+    if (lengths[b]) e = hipMemcpy(dx + (size_t)b * N, x + (size_t)b * N, sizeof(float) * (size_t)lengths[b], hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = hipMemcpy(dl, len32.data(), sizeof(int) * B, hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = hipMemset(dy, 0xff, sizeof(float) * (size_t)B * Ny);  // NaN: an output the kernels do not write shows
+  int rc = VITS_OK;
+  if (e == hipSuccess) {
+    rc = stretch ? pitch_run(device, nullptr, dx, N, N, dl, 1, len64.data(), B, P, Q, nullptr, 0, 0, dy, Ny)
+                 : pitch_run(device, nullptr, dx, N, N, dl, 1, len64.data(), B, P, Q, dy, Ny, Ny, nullptr, 0);
+    if (rc == VITS_OK) e = hipMemcpy(y, dy, sizeof(float) * (size_t)B * Ny, hipMemcpyDeviceToHost);
+  }
+  hipFree(dx); hipFree(dy); hipFree(dl);
+  if (rc != VITS_OK) return rc;
+  if (e != hipSuccess) return fail(VITS_ERR_DEVICE, "pitch: %s", hipGetErrorString(e));
+  return VITS_OK;
+}
+
+int vits_op_pitch_shift(int device, const float* x, const int64_t* lengths, int32_t B, int64_t N, float semitones, float* y) {
+  return pitch_op(device, x, lengths, B, N, semitones, y, false);
+}
+int vits_op_pitch_stretch(int device, const float* x, const int64_t* lengths, int32_t B, int64_t N, float semitones, float* y) {
+  return pitch_op(device, x, lengths, B, N, semitones, y, true);
+}

@@ -93,13 +93,14 @@ static void resample_fill(const ResamplePlan& P, float* table) {
 //   y        item b's output at y + b * y_bstride; y[j] is output n_begin + j, written for 0 <= j < n_count
 //            (exactly 0 for outputs at and beyond ceil(len * L / M))
 // OUT = int16_t: pcm16_kernel's epilogue (scale, * 32767, clip, truncating cast); dv (nullable) carries the per-call scale.
-template <typename OUT>
+// CROP (the pitch stage, include/vits_pitch.h): item b's outputs at and beyond crop[b] are 0 as well; without it crop is not read.
+template <typename OUT, bool CROP = false>
 __global__ __launch_bounds__(VITS_RESAMPLE_TILE) void resample_kernel(const float* __restrict__ x, long long x_bstride, long long x_off,
                                                                       long long x_n, const int* __restrict__ len_frames, long long len_mul,
                                                                       const float* __restrict__ tab, int L, int M, int taps, int half,
                                                                       long long W, OUT* __restrict__ y, long long y_bstride,
                                                                       long long n_begin, long long n_count, float scale,
-                                                                      const SynthDev* dv) {
+                                                                      const SynthDev* dv, const int* __restrict__ crop) {
   __shared__ float xs[RS_SPAN_MAX];
   const int b = blockIdx.y, tid = threadIdx.x;
   const long long len = len_frames ? len_frames[b] * len_mul : len_mul;
@@ -121,7 +122,9 @@ __global__ __launch_bounds__(VITS_RESAMPLE_TILE) void resample_kernel(const floa
   if (j_out >= n_count) return;
   const long long n = n0 + tid;
   float acc = 0.f;
-  if (n < (len * L + M - 1) / M) {
+  long long n_end = (len * L + M - 1) / M;
+  if constexpr (CROP) n_end = n_end < crop[b] ? n_end : crop[b];
+  if (n < n_end) {
     const int v = p0 + tid * M;  // < L + 255 * M: 32-bit
     const int dq = v / L, p = v - dq * L;
     int r = r0 + tid;
@@ -151,15 +154,8 @@ static std::mutex g_rs_mu;
 static std::map<std::tuple<int, int, int>, ResampleTab> g_rs_tabs;
 #define RS_MAX_TABS 64  // per process: captured graphs hold the pointers, so entries are never evicted
 
-// Uploads on first use (hipMalloc + a synchronous copy: call it outside stream capture).
-static int resample_get(int device, int rate_in, int rate_out, const ResampleTab** out) {
-  std::lock_guard<std::mutex> g(g_rs_mu);
-  const auto key = std::make_tuple(device, rate_in, rate_out);
-  auto it = g_rs_tabs.find(key);
-  if (it != g_rs_tabs.end()) { *out = &it->second; return VITS_OK; }
-  ResampleTab T;
-  TRY(resample_plan(rate_in, rate_out, &T.P));
-  if (g_rs_tabs.size() >= RS_MAX_TABS) return fail(VITS_ERR_UNSUPPORTED, "resample: more than %d distinct rate pairs in one process", RS_MAX_TABS);
+// the device copy of T.P's table (hipMalloc + a synchronous copy)
+static int resample_upload(int device, ResampleTab& T) {
   const ResamplePlan& P = T.P;
   std::vector<float> tab((size_t)P.L * P.taps), dev((size_t)P.L * P.taps);
   resample_fill(P, tab.data());
@@ -171,8 +167,22 @@ static int resample_get(int device, int rate_in, int rate_out, const ResampleTab
   if (hipMalloc((void**)&T.d, dev.size() * sizeof(float)) != hipSuccess) return fail(VITS_ERR_NOMEM, "resample: table alloc failed");
   if (hipMemcpy(T.d, dev.data(), dev.size() * sizeof(float), hipMemcpyHostToDevice) != hipSuccess) {
     hipFree(T.d);
+    T.d = nullptr;
     return fail(VITS_ERR_DEVICE, "resample: table upload failed");
   }
+  return VITS_OK;
+}
+
+// Uploads on first use (call it outside stream capture).
+static int resample_get(int device, int rate_in, int rate_out, const ResampleTab** out) {
+  std::lock_guard<std::mutex> g(g_rs_mu);
+  const auto key = std::make_tuple(device, rate_in, rate_out);
+  auto it = g_rs_tabs.find(key);
+  if (it != g_rs_tabs.end()) { *out = &it->second; return VITS_OK; }
+  ResampleTab T;
+  TRY(resample_plan(rate_in, rate_out, &T.P));
+  if (g_rs_tabs.size() >= RS_MAX_TABS) return fail(VITS_ERR_UNSUPPORTED, "resample: more than %d distinct rate pairs in one process", RS_MAX_TABS);
+  TRY(resample_upload(device, T));
   *out = &g_rs_tabs.emplace(key, T).first->second;
   return VITS_OK;
 }
@@ -186,7 +196,19 @@ static void resample_launch(hipStream_t stream, const ResampleTab& T, const floa
   const ResamplePlan& P = T.P;
   const unsigned gx = (unsigned)((n_count + VITS_RESAMPLE_TILE - 1) / VITS_RESAMPLE_TILE);
   hipLaunchKernelGGL(resample_kernel<OUT>, dim3(gx, B), dim3(VITS_RESAMPLE_TILE), 0, stream, x, x_bstride, x_off, x_n, len_frames, len_mul,
-                     T.d, P.L, P.M, P.taps, P.half, P.W, y, y_bstride, n_begin, n_count, scale, dv);
+                     T.d, P.L, P.M, P.taps, P.half, P.W, y, y_bstride, n_begin, n_count, scale, dv, nullptr);
+}
+
+// The form of the pitch stage (include/vits_pitch.h): float outputs [0, n_count) of B items whose input lengths are len_units[b] *
+// len_mul and whose outputs at and beyond crop[b] are 0 (both device arrays).
+static void resample_launch_crop(hipStream_t stream, const ResampleTab& T, const float* x, long long x_bstride, long long x_n,
+                                 const int* len_units, long long len_mul, const int* crop, int B, float* y, long long y_bstride,
+                                 long long n_count) {
+  if (n_count <= 0 || B <= 0) return;
+  const ResamplePlan& P = T.P;
+  const unsigned gx = (unsigned)((n_count + VITS_RESAMPLE_TILE - 1) / VITS_RESAMPLE_TILE);
+  hipLaunchKernelGGL((resample_kernel<float, true>), dim3(gx, B), dim3(VITS_RESAMPLE_TILE), 0, stream, x, x_bstride, 0LL, x_n, len_units, len_mul,
+                     T.d, P.L, P.M, P.taps, P.half, P.W, y, y_bstride, 0LL, n_count, 1.f, (const SynthDev*)nullptr, crop);
 }
 
 // 0 / the native rate -> 0 (the entry point's own path); anything else must have a plan

@@ -1143,17 +1143,41 @@ static int stts_loud_out(stts_model* m, const LoudReq& q, int B, float* audio, i
   return VITS_OK;
 }
 
+// STTS_FLAG_PITCH of a call (include/vits_pitch.h): under the flag `opts` is the `base.base` of a stts_synth_opts_pitch, whose last field
+// is read only then.  Checked before anything is synthesised.
+static int stts_pitch_arg(const stts_model* m, const stts_synth_opts* opts, PitchReq* q, float* semitones) {
+  q->on = false;
+  if (!opts || !(opts->flags & STTS_FLAG_PITCH)) return VITS_OK;
+  if (!m->vocoder) return fail(VITS_ERR_ARG, "no vocoder attached");
+  static_assert(offsetof(stts_synth_opts_pitch, base) == 0, "the extended options begin with the plain ones");
+  *semitones = reinterpret_cast<const stts_synth_opts_pitch*>(opts)->pitch_semitones;
+  return pitch_req(m->vocoder, *semitones, q);
+}
+// a call's native-rate audio [B, S] (items of lengths[b] samples) shifted in place: behind the denoiser and before the resampler (the
+// kernels of vits_op_pitch_shift; like stts_resample_out, it crosses the host once more)
+static int stts_pitch_out(stts_model* m, const PitchReq& q, float semitones, int B, float* audio, int64_t S, const int64_t* lengths) {
+  if (!q.on || S <= 0) return VITS_OK;
+  std::vector<float> y((size_t)B * S);
+  TRY(pitch_op(m->base.device, audio, lengths, B, S, semitones, y.data(), false));
+  memcpy(audio, y.data(), sizeof(float) * y.size());
+  return VITS_OK;
+}
+
 extern "C" {
 
 int stts_synthesize(stts_model* m, const int64_t* ids, int32_t Tx, const float* scales, int64_t sid, const float* bert, const float* pde,
                     const stts_synth_opts* opts, float** out_audio, int64_t* out_samples, float** out_mel, int64_t* out_frames) {
   if (!m) return fail(VITS_ERR_ARG, "bad argument");
   LoudReq lq;
+  PitchReq pq;
+  float pst = 0.f;
   if (out_audio) TRY(stts_loud_arg(m, opts, 0, &lq));
+  if (out_audio) TRY(stts_pitch_arg(m, opts, &pq, &pst));
   TRY(stts_synthesize_impl(m, ids, Tx, scales, sid, bert, pde, opts, out_audio, out_samples, out_mel, out_frames, nullptr));
-  if (lq.on) {
+  if (lq.on || pq.on) {
     const int64_t len = *out_samples;
-    const int rc = stts_loud_out(m, lq, 1, *out_audio, len, &len);
+    int rc = stts_pitch_out(m, pq, pst, 1, *out_audio, len, &len);
+    if (rc == VITS_OK) rc = stts_loud_out(m, lq, 1, *out_audio, len, &len);
     if (rc != VITS_OK) { free(*out_audio); *out_audio = nullptr; if (out_mel) { free(*out_mel); *out_mel = nullptr; } return rc; }
   }
   return VITS_OK;
@@ -1168,10 +1192,14 @@ int stts_synthesize_marks(stts_model* m, const int64_t* ids, int32_t Tx, const f
   TRY(stts_marks_arg(m, token_ends, sample_rate, &mk, &rate));
   LoudReq lq;
   if (out_audio) TRY(stts_loud_arg(m, opts, rate, &lq));
+  PitchReq pq;
+  float pst = 0.f;
+  if (out_audio) TRY(stts_pitch_arg(m, opts, &pq, &pst));
   TRY(stts_synthesize_impl(m, ids, Tx, scales, sid, bert, pde, opts, out_audio, out_samples, out_mel, out_frames, &mk));
   if (out_audio) {
     int64_t len = *out_samples;
-    int rc = rate ? stts_resample_out(m, rate, 1, out_audio, out_samples, &len) : VITS_OK;
+    int rc = stts_pitch_out(m, pq, pst, 1, *out_audio, len, &len);
+    if (rc == VITS_OK && rate) rc = stts_resample_out(m, rate, 1, out_audio, out_samples, &len);
     if (rc == VITS_OK) rc = stts_loud_out(m, lq, 1, *out_audio, *out_samples, &len);
     if (rc != VITS_OK) { free(*out_audio); *out_audio = nullptr; if (out_mel) { free(*out_mel); *out_mel = nullptr; } return rc; }
   }
@@ -1184,6 +1212,8 @@ int stts_stream_open(stts_model* m, const int64_t* ids, int32_t Tx, const float*
   if (!m->vocoder) return fail(VITS_ERR_ARG, "no vocoder attached");
   if (opts && (opts->flags & STTS_FLAG_LOUDNESS))
     return fail(VITS_ERR_UNSUPPORTED, "STTS_FLAG_LOUDNESS on a stream: an integrated-loudness or peak target needs the whole utterance before the first chunk");
+  if (opts && (opts->flags & STTS_FLAG_PITCH))
+    return fail(VITS_ERR_UNSUPPORTED, "STTS_FLAG_PITCH on a stream: the phase recursion needs the frames before a chunk, and its state is not carried across chunks");
   float* mel = nullptr;
   int64_t frames = 0;
   std::vector<int64_t> ends(Tx > 0 ? Tx : 0);  // recorded for vits_stream_marks (native rate: this open has no other)
@@ -1326,8 +1356,12 @@ int stts_synthesize_batch(stts_model* m, const int64_t* ids, const int64_t* leng
   if (!m) return fail(VITS_ERR_ARG, "bad argument");
   LoudReq lq;
   TRY(stts_loud_arg(m, opts, 0, &lq));
+  PitchReq pq;
+  float pst = 0.f;
+  TRY(stts_pitch_arg(m, opts, &pq, &pst));
   TRY(stts_synthesize_batch_impl(m, ids, lengths, B, Tx, scales, sid, bert, pde, opts, out_audio, out_samples, out_lengths, nullptr));
-  const int rc = stts_loud_out(m, lq, B, *out_audio, *out_samples, out_lengths);
+  int rc = stts_pitch_out(m, pq, pst, B, *out_audio, *out_samples, out_lengths);
+  if (rc == VITS_OK) rc = stts_loud_out(m, lq, B, *out_audio, *out_samples, out_lengths);
   if (rc != VITS_OK) { free(*out_audio); *out_audio = nullptr; }
   return rc;
 }
@@ -1341,8 +1375,12 @@ int stts_synthesize_batch_marks(stts_model* m, const int64_t* ids, const int64_t
   TRY(stts_marks_arg(m, token_ends, sample_rate, &mk, &rate));
   LoudReq lq;
   TRY(stts_loud_arg(m, opts, rate, &lq));
+  PitchReq pq;
+  float pst = 0.f;
+  TRY(stts_pitch_arg(m, opts, &pq, &pst));
   TRY(stts_synthesize_batch_impl(m, ids, lengths, B, Tx, scales, sid, bert, pde, opts, out_audio, out_samples, out_lengths, &mk));
-  int rc = rate ? stts_resample_out(m, rate, B, out_audio, out_samples, out_lengths) : VITS_OK;
+  int rc = stts_pitch_out(m, pq, pst, B, *out_audio, *out_samples, out_lengths);
+  if (rc == VITS_OK && rate) rc = stts_resample_out(m, rate, B, out_audio, out_samples, out_lengths);
   if (rc == VITS_OK) rc = stts_loud_out(m, lq, B, *out_audio, *out_samples, out_lengths);
   if (rc != VITS_OK) { free(*out_audio); *out_audio = nullptr; }
   return rc;

@@ -18,7 +18,7 @@ import threading
 
 import numpy as np
 
-from .capi import VitsLib, loudness_spec
+from .capi import VitsLib, loudness_spec, pitch_spec
 
 log = logging.getLogger(__name__)
 
@@ -226,7 +226,7 @@ _GRAPH_INPUTS = ("input", "input_lengths", "scales", "sid")
 _OPTIONAL_NONE = ("bert", "phone_duration_extra")
 # extension feeds (not part of the ONNX graph) used by parity tests
 _EXT = ("vits.noise_dp", "vits.noise_prior", "vits.forced_durations", "vits.seed", "vits.solo", "vits.item_seeds", "vits.sample_rate", "vits.marks",
-        "vits.loudness", "vits.peak", "vits.peak_ceiling")
+        "vits.loudness", "vits.peak", "vits.peak_ceiling", "vits.pitch")
 
 
 class _Arg:
@@ -295,15 +295,17 @@ class VitsSession:
         #  part of the key, so a batch has one rate and either every request of it gets a third value or none does)
         # loud: the normalisation of the batch (capi.loudness_spec(), None = none; include/vits_loudness.h): part of the key like the rate, and
         # measured and applied per item, so a request's result does not depend on what it was batched with
-        kind, scales, scale, rate, marks, loud = key
+        # pitch: the shift of the batch in semitones (None = none; include/vits_pitch.h): part of the key as well, one value per call
+        kind, scales, scale, rate, marks, loud, pitch = key
+        pk = {"pitch": pitch} if pitch is not None else {}
         scales = np.array(scales, np.float32)
         if len(reqs) == 1:
             ids, sid, seed = reqs[0]
             lens = np.array([ids.shape[1]], np.int64)
             if kind == "pcm":
                 return [self._model.synthesize_pcm16(ids, lens, scales, np.array([sid], np.int64), pcm_scale=scale, seed=seed, sample_rate=rate,
-                                                     marks=marks, loudness=loud)]
-            return [self._model.synthesize(ids, lens, scales, np.array([sid], np.int64), seed=seed, sample_rate=rate, marks=marks, loudness=loud)]
+                                                     marks=marks, loudness=loud, **pk)]
+            return [self._model.synthesize(ids, lens, scales, np.array([sid], np.int64), seed=seed, sample_rate=rate, marks=marks, loudness=loud, **pk)]
         # batch sizes come in powers of two (filled up with one-token dummies, whose padding tiles the ragged solo batch never
         # computes): every (batch size, length bucket) is a workspace and two captured graphs inside the engine, and a thread pool
         # produces every batch size between 1 and its own size
@@ -320,10 +322,10 @@ class VitsSession:
         seeds = np.array([r[2] for r in reqs], np.uint64)
         if kind == "pcm":
             res = self._model.synthesize_pcm16(batch, lens, scales, sids, pcm_scale=scale, seed=int(seeds[0]), solo=True, item_seeds=seeds,
-                                               sample_rate=rate, marks=marks, loudness=loud)
+                                               sample_rate=rate, marks=marks, loudness=loud, **pk)
         else:
             res = self._model.synthesize(batch, lens, scales, sids, seed=int(seeds[0]), solo=True, item_seeds=seeds, sample_rate=rate, marks=marks,
-                                         loudness=loud)
+                                         loudness=loud, **pk)
         out, ol = res[0], res[1]
         if marks:  # each request its own tokens' ends
             return [(out[b:b + 1, :int(ol[b])].copy(), ol[b:b + 1].copy(), res[2][b:b + 1, :int(lens[b])].copy()) for b in range(n_real)]
@@ -389,6 +391,14 @@ class VitsSession:
             self._lib._need_loudness()
         return spec
 
+    def _pitch(self, feed):
+        """the extension feed "vits.pitch" (semitones in [-12, 12]; include/vits_pitch.h) -> the shift as a float, or None for none and
+        for one that reduces to the identity; a value out of range is ValueError, before any device work"""
+        p = pitch_spec(feed.get("vits.pitch"))
+        if p is not None:
+            self._lib._need_pitch()
+        return p
+
     def run(self, output_names, input_feed, run_options=None):
         """Extension feed "vits.sample_rate" (next to "vits.seed"): output rate in Hz; the time axis of the output is then in output
         samples (include/vits_resample.h).  Extension feed "vits.marks": True -- the result list gets a second entry, token_ends int64
@@ -399,9 +409,10 @@ class VitsSession:
         rate = self._rate(feed.get("vits.sample_rate"))
         marks = self._marks(feed)
         loud = self._loudness(feed)
+        pitch = self._pitch(feed)  # ("vits.pitch": the audio shifted by that many semitones, behind the decoder)
         n = self._coalescable(feed, ids)
         if n:
-            key = ("f32", tuple(float(v) for v in np.asarray(feed["scales"], np.float32).reshape(-1)), 1.0, rate, marks, loud)
+            key = ("f32", tuple(float(v) for v in np.asarray(feed["scales"], np.float32).reshape(-1)), 1.0, rate, marks, loud, pitch)
             res = self.coalescer.submit(key, np.ascontiguousarray(ids[:, :n], np.int64), int(sid[0]), int(seed))
             self.last_lengths = res[1]
             if marks:  # (the request's own tokens; columns beyond its length repeat the last end, as the C ABI pads them)
@@ -411,7 +422,8 @@ class VitsSession:
             ids, np.asarray(feed["input_lengths"]).reshape(-1), np.asarray(feed["scales"], np.float32).reshape(-1), sid,
             noise_dp=feed.get("vits.noise_dp"), noise_prior=feed.get("vits.noise_prior"),
             forced_durations=feed.get("vits.forced_durations"), seed=int(seed), solo=bool(feed.get("vits.solo", False)),
-            item_seeds=feed.get("vits.item_seeds"), bert=feed.get("bert"), sample_rate=rate, marks=marks, loudness=loud)
+            item_seeds=feed.get("vits.item_seeds"), bert=feed.get("bert"), sample_rate=rate, marks=marks, loudness=loud,
+            **({"pitch": pitch} if pitch is not None else {}))
         self.last_lengths = res[1]
         return [res[0][:, None, None, :], res[2]] if marks else [res[0][:, None, None, :]]
 
@@ -444,9 +456,10 @@ class VitsSession:
         rate = self._rate(sample_rate if sample_rate is not None else feed.get("vits.sample_rate"))
         marks = self._marks(feed)
         loud = self._loudness(feed)
+        pitch = self._pitch(feed)
         n = self._coalescable(feed, ids)
         if n:
-            key = ("pcm", tuple(float(v) for v in np.asarray(feed["scales"], np.float32).reshape(-1)), float(scale), rate, marks, loud)
+            key = ("pcm", tuple(float(v) for v in np.asarray(feed["scales"], np.float32).reshape(-1)), float(scale), rate, marks, loud, pitch)
             res = self.coalescer.submit(key, np.ascontiguousarray(ids[:, :n], np.int64), int(sid[0]), int(seed))
             pcm, lengths = res[0], res[1]
             self.last_lengths = lengths
@@ -458,7 +471,8 @@ class VitsSession:
             ids, np.asarray(feed["input_lengths"]).reshape(-1), np.asarray(feed["scales"], np.float32).reshape(-1), sid,
             pcm_scale=float(scale), noise_dp=feed.get("vits.noise_dp"), noise_prior=feed.get("vits.noise_prior"),
             forced_durations=feed.get("vits.forced_durations"), seed=int(seed), solo=bool(feed.get("vits.solo", False)),
-            item_seeds=feed.get("vits.item_seeds"), bert=feed.get("bert"), sample_rate=rate, marks=marks, loudness=loud)
+            item_seeds=feed.get("vits.item_seeds"), bert=feed.get("bert"), sample_rate=rate, marks=marks, loudness=loud,
+            **({"pitch": pitch} if pitch is not None else {}))
         pcm, lengths = res[0], res[1]
         self.last_lengths = lengths
         if marks:
@@ -475,6 +489,9 @@ class VitsSession:
         if self._loudness(feed) is not None:
             raise ValueError("a stream cannot be loudness-normalised: an integrated-loudness or peak target needs the whole utterance before "
                              "the first chunk (run() / run_pcm16() take the loudness feeds)")
+        if self._pitch(feed) is not None:
+            raise ValueError("a stream cannot be pitch-shifted: the phase recursion needs the frames before a chunk (run() / run_pcm16() "
+                             "take \"vits.pitch\")")
         rate = self._rate(sample_rate if sample_rate is not None else feed.get("vits.sample_rate"))
         if ids.shape[0] != 1:
             raise ValueError("run_stream takes one utterance")

@@ -9,12 +9,12 @@ import threading
 
 import numpy as np
 
-from .capi import VitsLib, loudness_spec
+from .capi import VitsLib, loudness_spec, pitch_spec
 from .capi_stts import SttsModel
 
 _INPUTS = ("input", "input_lengths", "scales", "sid", "bert", "phone_duration_extra")
 _EXT = ("vits.noise", "vits.seed", "vits.n_timesteps", "vits.sample_rate", "vits.denoiser_strength", "vits.denoiser_filter_length",
-        "vits.marks", "vits.loudness", "vits.peak", "vits.peak_ceiling")
+        "vits.marks", "vits.loudness", "vits.peak", "vits.peak_ceiling", "vits.pitch")
 
 
 class SttsSession:
@@ -102,6 +102,15 @@ class SttsSession:
             self._lib._need_loudness()
         return spec
 
+    def _pitch(self, feed):
+        """the extension feed "vits.pitch" (semitones in [-12, 12]; include/vits_pitch.h) -> the keyword for the model's calls: empty for
+        none and for a shift that reduces to the identity; a value out of range is ValueError, before any device work"""
+        p = pitch_spec(feed.get("vits.pitch"))
+        if p is None:
+            return {}
+        self._lib._need_pitch()
+        return {"pitch": p}
+
     def normalize(self, audio, lengths, sample_rate, spec):
         """audio float32 [B, S] at `sample_rate` Hz (None / 0 = the vocoder's own) with per-item sample counts -> the audio normalised
         per item by `spec` (vits_op_loudness_normalize on the host buffer); None: unchanged.  What run() / run_batch() do behind
@@ -120,16 +129,17 @@ class SttsSession:
         is what is measured (include/vits_loudness.h)."""
         feed, ids, scales, sid, bert, pde, seed = self._parse(output_names, input_feed)
         loud = self._loudness(feed)
+        pk = self._pitch(feed)  # ("vits.pitch": shifted inside the library, behind the denoiser and before any resampling)
         if feed.get("vits.marks"):
             audio, _, ends = self._model.synthesize(ids, scales, sid, bert, pde, noise=feed.get("vits.noise"), seed=seed,
                                                     n_timesteps=int(feed.get("vits.n_timesteps", 0)), want_mel=False, marks=True,
-                                                    sample_rate=self._rate(feed.get("vits.sample_rate")), loudness=loud, **self._denoiser(feed))
+                                                    sample_rate=self._rate(feed.get("vits.sample_rate")), loudness=loud, **pk, **self._denoiser(feed))
             outs = {"wav": audio[None, :], "wav_lengths": np.array([audio.shape[0]], np.int64)}
             return [outs[n] for n in (output_names or ["wav", "wav_lengths"])] + [ends[None, :]]
         rate = self._rate(feed.get("vits.sample_rate"))
         audio, _ = self._model.synthesize(ids, scales, sid, bert, pde, noise=feed.get("vits.noise"), seed=seed,
                                           n_timesteps=int(feed.get("vits.n_timesteps", 0)), want_mel=False,
-                                          loudness=None if rate else loud, **self._denoiser(feed))
+                                          loudness=None if rate else loud, **pk, **self._denoiser(feed))
         if rate:  # (the library normalises last, and this resampling happens behind it: the normalisation follows it here)
             audio = self.resample(audio[None, :], [audio.shape[0]], rate)[0][0]
             audio = self.normalize(audio[None, :], [audio.shape[0]], rate, loud)[0]
@@ -147,6 +157,9 @@ class SttsSession:
         if self._loudness(feed) is not None:
             raise ValueError("a stream cannot be loudness-normalised: an integrated-loudness or peak target needs the whole utterance before "
                              "the first chunk (run() takes the loudness feeds)")
+        if self._pitch(feed):
+            raise ValueError("a stream cannot be pitch-shifted: the phase recursion needs the frames before a chunk (run() takes "
+                             "\"vits.pitch\")")
         rate = self._rate(sample_rate if sample_rate is not None else feed.get("vits.sample_rate"))
         dn = self._denoiser(feed)
         if rate and dn:
@@ -182,6 +195,7 @@ class SttsSession:
                 raise ValueError(f"Required input {k} is missing")
         dn = self._denoiser(feed)
         loud = self._loudness(feed)  # (per-item gains, last in the chain like run())
+        pk = self._pitch(feed)
         rate = self._rate(feed.get("vits.sample_rate"))
         ids = np.asarray(feed["input"])
         if ids.ndim != 3 or ids.shape[1] != 5:
@@ -191,11 +205,11 @@ class SttsSession:
             return self._model.synthesize_batch(ids, feed["input_lengths"], np.asarray(feed["scales"], np.float32).reshape(-1), sid,
                                                 feed.get("bert"), feed.get("phone_duration_extra"), seed=int(feed.get("vits.seed", 0)),
                                                 n_timesteps=int(feed.get("vits.n_timesteps", 0)), item_seeds=feed.get("vits.item_seeds"),
-                                                marks=True, sample_rate=rate, loudness=loud, **dn)
+                                                marks=True, sample_rate=rate, loudness=loud, **pk, **dn)
         audio, ol = self._model.synthesize_batch(ids, feed["input_lengths"], np.asarray(feed["scales"], np.float32).reshape(-1), sid,
                                                  feed.get("bert"), feed.get("phone_duration_extra"), seed=int(feed.get("vits.seed", 0)),
                                                  n_timesteps=int(feed.get("vits.n_timesteps", 0)), item_seeds=feed.get("vits.item_seeds"),
-                                                 loudness=None if rate else loud, **dn)
+                                                 loudness=None if rate else loud, **pk, **dn)
         if not rate:
             return audio, ol
         audio, ol = self.resample(audio, ol, rate)

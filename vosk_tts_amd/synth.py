@@ -224,6 +224,21 @@ class Synth:
             args["vits.peak"] = float(peak)
         return True
 
+    def _pitch(self, args, pitch):
+        """Pitch shift of the request (include/vits_pitch.h): `pitch` in semitones, [-12, 12], defaulting to the config key
+        inference.pitch; it goes into the feed as "vits.pitch".  None and no config key, or a shift that reduces to the identity = off,
+        the reference's behaviour.  The engine shifts the finished waveform on the device, behind the decoder and the denoiser and before
+        the resampler; duration, sample counts and marks do not change (formants move with the pitch)."""
+        from .capi import pitch_spec
+
+        if pitch is None:
+            pitch = self.model.config.get("inference", {}).get("pitch")
+        p = pitch_spec(pitch)  # (raises on a value out of range)
+        if p is None:
+            return False
+        args["vits.pitch"] = p
+        return True
+
     def measure_loudness(self, audio, rate=None):
         """(lufs, peak) of one utterance: BS.1770 integrated loudness (-inf for silence) and max |sample| in full-scale units, measured
         by the engine's own kernels (vits_op_loudness).  audio: int16 PCM (scaled by 1 / 32767, the conversion's own factor) or float;
@@ -271,8 +286,9 @@ class Synth:
         return build_marks(rate, np.asarray(token_ends).reshape(-1), symbols, counts, blank, word_of, word_texts)
 
     def synth_audio(self, text, speaker_id=0, noise_level=None, speech_rate=None, duration_noise_level=None, scale=None, sample_rate=None,
-                    denoiser_strength=None, marks=False, loudness=None, peak=None, peak_ceiling=None):
-        """sample_rate: output rate in Hz (extension; default None = the voice's own rate, the reference's behaviour): the feed gets
+                    denoiser_strength=None, marks=False, loudness=None, peak=None, peak_ceiling=None, pitch=None):
+        """pitch (extension): semitones by which the returned audio is shifted, see _pitch.
+        sample_rate: output rate in Hz (extension; default None = the voice's own rate, the reference's behaviour): the feed gets
         "vits.sample_rate" and the engine resamples on the device.  denoiser_strength: see _denoiser.
         loudness / peak / peak_ceiling (extension): a LUFS or a peak target for the returned audio, see _loudness.
         marks=True (extension): returns (audio, marks) -- marks.SpeechMarks with rate, token_ends, phonemes [(symbol, start, end)] and
@@ -280,6 +296,7 @@ class Synth:
         args, scale = self._feed(text, speaker_id, noise_level, speech_rate, duration_noise_level, scale)
         self._denoiser(args, denoiser_strength)
         self._loudness(args, loudness, peak, peak_ceiling)
+        self._pitch(args, pitch)
         rate = self.native_rate()
         if sample_rate and int(sample_rate) != rate:
             rate = int(sample_rate)
@@ -316,8 +333,11 @@ class Synth:
         return audio
 
     def synth_stream(self, text, speaker_id=0, noise_level=None, speech_rate=None, duration_noise_level=None, scale=None,
-                     chunk_frames=64, sample_rate=None, denoiser_strength=None, on_marks=None, loudness=None, peak=None, peak_ceiling=None):
-        """Generator of int16 PCM chunks (chunk_frames*256 samples each, ~0.74 s at the default): what a streaming
+                     chunk_frames=64, sample_rate=None, denoiser_strength=None, on_marks=None, loudness=None, peak=None, peak_ceiling=None,
+                     pitch=None):
+        """pitch: ValueError -- the phase recursion needs the frames before a chunk (a voice whose config names inference.pitch streams
+        unshifted).
+        Generator of int16 PCM chunks (chunk_frames*256 samples each, ~0.74 s at the default): what a streaming
         `SynthesizeStream` handler would put into successive AudioChunk messages (tts_service.proto:46-54) instead
         of the single whole-utterance chunk of tts_server.py:54.  Same conversion as synth_audio per chunk.
         on_marks: a callable that receives the utterance's marks.SpeechMarks once, before the first chunk is yielded.
@@ -326,6 +346,9 @@ class Synth:
         if loudness is not None or peak is not None:
             raise ValueError("synth_stream cannot normalise loudness: an integrated-loudness or peak target needs the whole utterance "
                              "before the first chunk (synth_audio takes loudness= / peak=)")
+        if pitch is not None:
+            raise ValueError("synth_stream cannot shift the pitch: the phase recursion needs the frames before a chunk, and its state is "
+                             "not carried across chunks (synth_audio takes pitch=)")
         args, scale = self._feed(text, speaker_id, noise_level, speech_rate, duration_noise_level, scale)
         self._denoiser(args, denoiser_strength)
         if not hasattr(self.model.onnx, "run_stream"):
@@ -341,10 +364,10 @@ class Synth:
             yield self.audio_float_to_int16(chunk * scale)
 
     def synth(self, text, oname, speaker_id=0, noise_level=None, speech_rate=None, duration_noise_level=None, scale=None, sample_rate=None,
-              denoiser_strength=None, marks=False, loudness=None, peak=None, peak_ceiling=None):
+              denoiser_strength=None, marks=False, loudness=None, peak=None, peak_ceiling=None, pitch=None):
         """marks=True: the utterance's marks.SpeechMarks are returned (the default returns None, as the reference does)"""
         audio = self.synth_audio(text, speaker_id, noise_level, speech_rate, duration_noise_level, scale, sample_rate, denoiser_strength, marks=marks,
-                                 loudness=loudness, peak=peak, peak_ceiling=peak_ceiling)
+                                 loudness=loudness, peak=peak, peak_ceiling=peak_ceiling, pitch=pitch)
         sm = None
         if marks:
             audio, sm = audio
