@@ -3,7 +3,9 @@
  * device behind the decoder.  VITS and Matcha have no F0 input, so pitch is signal processing on the waveform: an identity-phase-locked
  * vocoder (Laroche & Dolson, "Improved phase vocoder time-scale modification of audio", 1999) stretches the item by P/Q and the
  * resampler of include/vits_resample.h (P -> Q) brings it back to its length.  (The plain phase vocoder returns a 440 Hz sine at a tenth
- * of its amplitude: DESIGN.md "Pitch shift".)  Formants move with the pitch, as with every resampling shifter.
+ * of its amplitude: DESIGN.md "Pitch shift".)  Formants move with the pitch, as with every resampling shifter, unless the caller sets
+ * VITS_FLAG_PITCH_FORMANT: then steps 3a-3d below pre-warp the magnitudes the synthesis uses, so that the spectral envelope is back
+ * where it was behind the resampler.
  *
  * An extension of the product library: the reference has no counterpart, so these entry points are checked against a float64
  * restatement of the definition below (tests/pitch_ref.py, the authority).  Same status codes and vits_last_error as
@@ -25,6 +27,23 @@
  *                  k is a peak of m_t iff m[k] > m[k-1], m[k] > m[k-2], m[k] >= m[k+1], m[k] >= m[k+2] (outside [0, NB): -1)
  *                  own(k) = the peak nearest to k, the lower one on a tie
  *                  Phi_t[k] = adv[own(k)] + theta_i[k] - theta_i[own(k)]          (no peak: Phi_t = adv)
+ *   Under VITS_FLAG_PITCH_FORMANT, for every analysis row f < F_a (C = VITS_PITCH_LIFTER, floor = VITS_PITCH_LOG_FLOOR,
+ *   g_max = VITS_PITCH_FORMANT_MAX_DB * ln(10) / 20 nepers):
+ *   3a log spectrum  L[k] = ln(max(mag_f[k], floor)), k = 0 .. n/2
+ *   3b cepstrum      the low quefrencies of the real, even log spectrum, q = 0 .. C:
+ *                      c[q] = (D[0] + (-1)^q D[n/2] + 2 sum_{k=1}^{n/2-1} D[k] cos(2 pi k q / n)) / n,   D[k] = L[k] - L[0]
+ *                    (the sums run over L less its first value: the constant adds exactly 0 to c[q], q >= 1, and c[0] cancels in 3d,
+ *                    so a row of one value -- a frame of exact zeros -- has c = 0 and g = 1 exactly, in every precision); the cosine is
+ *                    the n-entry table cos(2 pi j / n) at j = (k q) mod n
+ *   3c envelope      at a real bin position kappa in [0, n/2]: e(kappa) = c[0] + 2 sum_{q=1}^{C} c[q] cos(2 pi kappa q / n).  The
+ *                    shifted position of bin k is kappa_k = min(k P / Q, n/2); its angle is formed from integers:
+ *                    r = (k P q) mod (Q n), angle = 2 pi r / (Q n) (r advances by (k P) mod (Q n) per q with one conditional
+ *                    subtraction; every value stays below 2^31; one division in fp32), and where k P >= (n/2) Q the cosine is (-1)^q
+ *   3d gain          g_f[k] = exp(clamp(e(kappa_k) - e(k), -g_max, +g_max)); mag'_f[k] = mag_f[k] g_f[k]; rows f >= F_a are zero,
+ *                    like mag.  After the resampler bin k of u sits at k P / Q: the envelope wanted there is E(k P / Q), what bin k
+ *                    carries is E(k).
+ *   Steps 2 and 3 (m_t, the peak test, the owners, Phi_t) use the unscaled mag: the phases of a corrected call are those of the plain
+ *   call, bit for bit.  Step 4 then takes m'_t[k] = (1 - alpha_t) mag'_{i_t}[k] + alpha_t mag'_{i_t + 1}[k] in place of m_t.
  *   4 synthesis  turn = (int32) Phi_t[k] * 2^-32; Y_t[k] = m_t[k] (cos 2 pi turn, sin 2 pi turn), the imaginary parts of bins 0 and n/2
  *                dropped; y_t = irFFT(Y_t) * w, overlap-added at hop H, times 1 / (overlap-added w^2), n/2 dropped from both ends:
  *                u[0 .. N_u), N_u = H (F_s - 1)
@@ -33,7 +52,8 @@
  *                multiples of the vocoder's hop, which must be a multiple of H (else VITS_ERR_UNSUPPORTED naming both): nothing is lost.
  * An item shorter than n/2 + 1 samples is returned unshifted (the denoiser's rule for short utterances).
  *
- * Arithmetic: fp32 apart from the integer phases; twiddles, window, 1 / sum w^2 and resampler coefficients are host-computed tables;
+ * Arithmetic: fp32 apart from the integer phases and the magnitude under the logarithm of 3a, which the device takes from a transform of
+ * the frame in double and rounds to fp32 once (the logarithm magnifies the fp32 transform's error at bins near zero); twiddles, window, 1 / sum w^2 and resampler coefficients are host-computed tables;
  * every sum has a fixed order, no atomics: the same call twice gives the same bits, and an item's result does not depend on its batch.
  */
 #ifndef VITS_PITCH_H
@@ -47,8 +67,12 @@ extern "C" {
 
 #define VITS_PITCH_FRAME 1024
 #define VITS_PITCH_MAX_SEMITONES 12
+#define VITS_PITCH_LIFTER 40          /* C: the quefrencies 0 .. C make the envelope */
+#define VITS_PITCH_LOG_FLOOR 1e-4f    /* floor of the magnitude under the logarithm */
+#define VITS_PITCH_FORMANT_MAX_DB 30  /* G: the envelope gain of a bin is clamped to +- G dB */
 /* Device scratch one group of items may take, in bytes.  An item needs about 4 KiB per analysis frame (magnitudes and phases) and 7 KiB
- * per step (phases, the frame, its share of u): 16 bytes per sample plus 28 bytes per sample times P / Q.  The items of a batch run in
+ * per step (phases, the frame, its share of u): 16 bytes per sample plus 28 bytes per sample times P / Q; under VITS_FLAG_PITCH_FORMANT
+ * another 2 KiB per analysis frame (the corrected magnitudes): 24 bytes per sample plus the same.  The items of a batch run in
  * groups of consecutive items that fit, and a single item that does not (about 7 M samples at +12 semitones) is VITS_ERR_UNSUPPORTED
  * naming its length. */
 #define VITS_PITCH_MAX_SCRATCH (512LL << 20)
@@ -60,6 +84,10 @@ extern "C" {
  * still read only under their own flag. */
 #define VITS_FLAG_PITCH 4
 #define STTS_FLAG_PITCH 8
+/* ... and keep the spectral envelope (the formants) where it was: steps 3a-3d.  These bits modify a pitch request and add no field.  Set
+ * without the pitch flag: VITS_ERR_ARG naming both flags.  Set with a shift that reduces to P = Q: the call as it was. */
+#define VITS_FLAG_PITCH_FORMANT 8
+#define STTS_FLAG_PITCH_FORMANT 16
 
 typedef struct vits_synth_opts_pitch {
   vits_synth_opts base;
@@ -86,4 +114,8 @@ int vits_op_pitch_stretch(int device, const float* x, const int64_t* lengths, in
 #ifdef __cplusplus
 }
 #endif
+
+/* the parity doors of steps 3a-3d: vits_op_pitch_shift_formant, vits_op_pitch_stretch_formant, vits_op_pitch_formant_gain */
+#include "vits_pitch_formant.h"
+
 #endif /* VITS_PITCH_H */

@@ -159,7 +159,8 @@ class MultiDeviceSynth:
         return out
 
     def synth_batch(self, texts, speaker_ids=0, noise_level=None, speech_rate=None, duration_noise_level=None, scale=None, seeds=None,
-                    sample_rate=None, denoiser_strength=None, marks=False, loudness=None, peak=None, peak_ceiling=None, pitch=None):
+                    sample_rate=None, denoiser_strength=None, marks=False, loudness=None, peak=None, peak_ceiling=None, pitch=None,
+                    preserve_formants=None):
         """texts: list of str -> list of int16 PCM arrays (22.05 kHz), one per request, in request order.  marks=True: a list of
         (audio, marks.SpeechMarks) per request instead (as Synth.synth_audio(..., marks=True)), through every shard path.  `seeds`: optional
         per-request noise seeds (default: a running counter), `speaker_ids`: one id or one per request.  `sample_rate`: output rate
@@ -171,7 +172,8 @@ class MultiDeviceSynth:
         s0 = self.synths[0]
         loud = {}
         s0._loudness(loud, loudness, peak, peak_ceiling)
-        s0._pitch(loud, pitch)  # ("vits.pitch": one shift for the whole batch, travelling with the loudness feeds; include/vits_pitch.h)
+        # "vits.pitch" (and "vits.pitch_formants"): one shift for the whole batch, travelling with the loudness feeds; include/vits_pitch.h
+        s0._pitch(loud, pitch, preserve_formants)
         dn = {}
         s0._denoiser(dn, denoiser_strength)
         denoiser_strength = dn.get("vits.denoiser_strength")

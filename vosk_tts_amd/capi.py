@@ -90,6 +90,7 @@ def set_loudness(opts, keep, spec, B, flag, out=None):
 
 # include/vits_pitch.h
 FLAG_PITCH = 4          # VITS_FLAG_PITCH
+FLAG_PITCH_FORMANT = 8  # VITS_FLAG_PITCH_FORMANT: keep the spectral envelope where it was; modifies a pitch request
 PITCH_FRAME = 1024      # VITS_PITCH_FRAME
 PITCH_MAX_SEMITONES = 12.0
 
@@ -201,6 +202,7 @@ class VitsLib:
         self.has_marks = False
         self.has_loudness = False
         self.has_pitch = False
+        self.has_pitch_formant = False
         if self.is_device:
             c_i16p = ctypes.POINTER(ctypes.c_int16)
             f("synthesize_pcm16").argtypes = [ctypes.c_void_p, c_i64p, c_i64p, ctypes.c_int32, ctypes.c_int32, c_f32p, c_i64p,
@@ -273,6 +275,11 @@ class VitsLib:
                 f("pitch_plan").argtypes = [ctypes.c_float, c_i32p, c_i32p]
                 for name in ("op_pitch_shift", "op_pitch_stretch"):
                     f(name).argtypes = [ctypes.c_int, c_f32p, c_i64p, ctypes.c_int32, ctypes.c_int64, ctypes.c_float, c_f32p]
+                # include/vits_pitch_formant.h: the doors of the formant-preserving shift
+                self.has_pitch_formant = self.has("op_pitch_formant_gain")
+                if self.has_pitch_formant:
+                    for name in ("op_pitch_shift_formant", "op_pitch_stretch_formant", "op_pitch_formant_gain"):
+                        f(name).argtypes = [ctypes.c_int, c_f32p, c_i64p, ctypes.c_int32, ctypes.c_int64, ctypes.c_float, c_f32p]
             if self.has("debug_clock_probe"):
                 f("debug_clock_probe").argtypes = [ctypes.c_int, ctypes.c_int32, ctypes.POINTER(ctypes.c_double), ctypes.c_int32]
 
@@ -475,23 +482,48 @@ class VitsLib:
         self.check(self._fn("pitch_plan")(float(semitones), ctypes.byref(P), ctypes.byref(Q)))
         return P.value, Q.value
 
-    def op_pitch_shift(self, x, lengths, semitones, device=0):
+    def _need_pitch_formant(self):
+        self._need_pitch()
+        if not self.has_pitch_formant:
+            raise VitsError(4, "this backend has no formant-preserving pitch shift (include/vits_pitch.h, VITS_FLAG_PITCH_FORMANT)")
+
+    def op_pitch_shift(self, x, lengths, semitones, device=0, _door="op_pitch_shift"):
         """vits_op_pitch_shift: x float32 [B, N], lengths [B] -> y float32 [B, N]; item b from x[b, :lengths[b]] only, zero beyond"""
         self._need_pitch()
         x, lengths = self._loud_args(x, lengths)
         B, N = x.shape
         y = np.empty((B, N), np.float32)
-        self.check(self._fn("op_pitch_shift")(device, _p(x, c_f32p), _p(lengths, c_i64p), B, N, float(semitones), _p(y, c_f32p)))
+        self.check(self._fn(_door)(device, _p(x, c_f32p), _p(lengths, c_i64p), B, N, float(semitones), _p(y, c_f32p)))
         return y
 
-    def op_pitch_stretch(self, x, lengths, semitones, device=0):
+    def op_pitch_shift_formant(self, x, lengths, semitones, device=0):
+        """vits_op_pitch_shift_formant: op_pitch_shift with the envelope correction (steps 3a-3d of include/vits_pitch.h)"""
+        self._need_pitch_formant()
+        return self.op_pitch_shift(x, lengths, semitones, device, "op_pitch_shift_formant")
+
+    def op_pitch_stretch_formant(self, x, lengths, semitones, device=0):
+        """vits_op_pitch_stretch_formant: op_pitch_stretch with the envelope correction"""
+        self._need_pitch_formant()
+        return self.op_pitch_stretch(x, lengths, semitones, device, "op_pitch_stretch_formant")
+
+    def op_pitch_formant_gain(self, x, lengths, semitones, device=0):
+        """vits_op_pitch_formant_gain: the gains of step 3d, float32 [B, N // 256 + 3, 513]; row f of item b is g_f for f < F_a[b], every
+        other row exactly 0"""
+        self._need_pitch_formant()
+        x, lengths = self._loud_args(x, lengths)
+        B, N = x.shape
+        g = np.empty((B, N // 256 + 3, PITCH_FRAME // 2 + 1), np.float32)
+        self.check(self._fn("op_pitch_formant_gain")(device, _p(x, c_f32p), _p(lengths, c_i64p), B, N, float(semitones), _p(g, c_f32p)))
+        return g
+
+    def op_pitch_stretch(self, x, lengths, semitones, device=0, _door="op_pitch_stretch"):
         """vits_op_pitch_stretch: the vocoder's output before the resampler, float32 [B, 256 * (ceil((N // 256 + 2) * P / Q) - 1)]"""
         self._need_pitch()
         x, lengths = self._loud_args(x, lengths)
         B, N = x.shape
         P, Q = self.pitch_plan(semitones)
         y = np.empty((B, 256 * (-(-(N // 256 + 2) * P // Q) - 1)), np.float32)
-        self.check(self._fn("op_pitch_stretch")(device, _p(x, c_f32p), _p(lengths, c_i64p), B, N, float(semitones), _p(y, c_f32p)))
+        self.check(self._fn(_door)(device, _p(x, c_f32p), _p(lengths, c_i64p), B, N, float(semitones), _p(y, c_f32p)))
         return y
 
     def mas_maximum_path(self, values, t_ys, t_xs, device=0):
@@ -540,12 +572,12 @@ class VitsModel:
             pass
 
     def _opts(self, B, Tx, noise_dp, noise_prior, forced_durations, seed, max_frames, solo=False, item_seeds=None, bert=None,
-              loudness=None, loudness_out=None, pitch=None):
+              loudness=None, loudness_out=None, pitch=None, preserve_formants=False):
         pitch = pitch_spec(pitch)  # (None, or a shift that does not reduce to P = Q)
         opts = SynthOpts() if pitch is None else SynthPitchOpts()
         keep = []
         if pitch is not None:
-            self.lib._need_pitch()
+            self.lib._need_pitch_formant() if preserve_formants else self.lib._need_pitch()
         if loudness is not None:
             self.lib._need_loudness()
         if bert is not None:
@@ -579,7 +611,7 @@ class VitsModel:
         opts.flags = 1 if solo else 0  # VITS_FLAG_SOLO_BATCH
         set_loudness(opts, keep, loudness, B, FLAG_LOUDNESS, loudness_out)
         if pitch is not None:
-            opts.flags |= FLAG_PITCH
+            opts.flags |= FLAG_PITCH | (FLAG_PITCH_FORMANT if preserve_formants else 0)  # (the formant bit only with a pitch in effect)
             opts.pitch_semitones = pitch
         return opts, keep
 
@@ -595,9 +627,10 @@ class VitsModel:
 
     def synthesize(self, ids, lengths, scales, sid, noise_dp=None, noise_prior=None, forced_durations=None, seed=0,
                    max_frames=0, solo=False, item_seeds=None, bert=None, sample_rate=None, marks=False, loudness=None, loudness_out=None,
-                   pitch=None):
+                   pitch=None, preserve_formants=False):
         """pitch: semitones in [-12, 12] (VITS_FLAG_PITCH, include/vits_pitch.h): every item shifted on the device behind the decoder,
-        before the resampler; lengths and marks do not change.
+        before the resampler; lengths and marks do not change.  preserve_formants (VITS_FLAG_PITCH_FORMANT): the spectral envelope stays
+        where it was; without a pitch in effect it changes nothing.
         One .run(): returns (audio float32 [B,S], out_lengths int64 [B]); with marks=True (vits_synthesize_marks) a third value,
         token_ends int64 [B,T_x] in output samples (include/vits_marks.h).  solo=True (VITS_FLAG_SOLO_BATCH): every
         item equals its own single-utterance call with seed + b instead of the reference's padded-batch result.
@@ -612,7 +645,7 @@ class VitsModel:
         if lengths.shape != (B,) or sid.shape != (B,) or scales.shape != (3,):
             raise ValueError("bad feed shapes")
         opts, keep = self._opts(B, Tx, noise_dp, noise_prior, forced_durations, seed, max_frames, solo, item_seeds, bert, loudness, loudness_out,
-                                pitch)
+                                pitch, preserve_formants)
         out = c_f32p()
         ns = ctypes.c_int64()
         olen = np.zeros(B, dtype=np.int64)
@@ -640,8 +673,8 @@ class VitsModel:
 
     def synthesize_pcm16(self, ids, lengths, scales, sid, pcm_scale=1.0, noise_dp=None, noise_prior=None, forced_durations=None,
                          seed=0, max_frames=0, solo=False, item_seeds=None, bert=None, sample_rate=None, marks=False, loudness=None,
-                         loudness_out=None, pitch=None):
-        """pitch: as for synthesize.
+                         loudness_out=None, pitch=None, preserve_formants=False):
+        """pitch, preserve_formants: as for synthesize.
         synthesize() with Synth.synth_audio's `* scale` and audio_float_to_int16 (vosk_tts/synth.py:127-130) done on the
         device: returns (pcm int16 [B,S], out_lengths int64 [B]).  sample_rate: as for synthesize (vits_synthesize_pcm16_rate:
         the resampler does the conversion in its epilogue).  loudness / loudness_out: as for synthesize (pcm_scale multiplies the
@@ -652,7 +685,7 @@ class VitsModel:
         if lengths.shape != (B,) or sid.shape != (B,) or scales.shape != (3,):
             raise ValueError("bad feed shapes")
         opts, keep = self._opts(B, Tx, noise_dp, noise_prior, forced_durations, seed, max_frames, solo, item_seeds, bert, loudness, loudness_out,
-                                pitch)
+                                pitch, preserve_formants)
         out = ctypes.POINTER(ctypes.c_int16)()
         ns = ctypes.c_int64()
         olen = np.zeros(B, dtype=np.int64)

@@ -29,6 +29,8 @@ class SttsLoudnessOpts(SttsOpts):
 
 STTS_FLAG_LOUDNESS = 4    # include/vits_loudness.h
 STTS_FLAG_PITCH = 8       # include/vits_pitch.h
+STTS_FLAG_PITCH_FORMANT = 16  # ... keep the spectral envelope where it was; modifies a pitch request
+FLAG_PITCH_FORMANT = STTS_FLAG_PITCH_FORMANT
 
 
 class SttsPitchOpts(SttsLoudnessOpts):
@@ -118,13 +120,16 @@ class SttsModel:
             raise VitsError(4, "this backend has no loudness normalisation (include/vits_loudness.h)")
         set_loudness(opts, keep, spec, B, STTS_FLAG_LOUDNESS, out)
 
-    def _opts_for(self, loudness, pitch):
-        """the options struct a call needs: the plain one, the one with the loudness fields, or the one with the pitch behind those"""
+    def _opts_for(self, loudness, pitch, preserve_formants=False):
+        """the options struct a call needs: the plain one, the one with the loudness fields, or the one with the pitch behind those;
+        preserve_formants sets its bit only with a pitch in effect"""
         if pitch_spec(pitch) is not None:
             if not getattr(self.vlib, "has_pitch", False):
                 raise VitsError(4, "this backend has no pitch shifter (include/vits_pitch.h)")
+            if preserve_formants and not getattr(self.vlib, "has_pitch_formant", False):
+                raise VitsError(4, "this backend has no formant-preserving pitch shift (include/vits_pitch.h, STTS_FLAG_PITCH_FORMANT)")
             opts = SttsPitchOpts()
-            opts.flags |= STTS_FLAG_PITCH
+            opts.flags |= STTS_FLAG_PITCH | (STTS_FLAG_PITCH_FORMANT if preserve_formants else 0)
             opts.pitch_semitones = float(pitch)
             return opts
         return SttsOpts() if loudness is None else SttsLoudnessOpts()
@@ -136,9 +141,10 @@ class SttsModel:
     # ---- hot path ----------------------------------------------------------------------------
     def synthesize(self, ids, scales, sid, bert=None, phone_duration_extra=None, noise=None, seed=0, n_timesteps=0,
                    want_audio=True, want_mel=True, denoiser_strength=None, denoiser_filter_length=0, marks=False, sample_rate=None,
-                   loudness=None, loudness_out=None, pitch=None):
+                   loudness=None, loudness_out=None, pitch=None, preserve_formants=False):
         """pitch: semitones in [-12, 12] (STTS_FLAG_PITCH, include/vits_pitch.h): the audio shifted behind the denoiser, before any
-        resampling; its length and the marks do not change.
+        resampling; its length and the marks do not change.  preserve_formants (STTS_FLAG_PITCH_FORMANT): the spectral envelope stays
+        where it was; without a pitch in effect it changes nothing.
         One utterance.  ids int64 [5,T]; returns (audio float32 [S] or None, mel float32 [n_feats,T_y] or None).
         denoiser_strength (None = off) / denoiser_filter_length (0 = 1024): the vocoder-bias denoiser behind the clamp.
         marks=True (stts_synthesize_marks): a third value, token_ends int64 [T]; audio and marks are then at `sample_rate`
@@ -154,7 +160,7 @@ class SttsModel:
         T = ids.shape[1]
         scales = _f32(scales)
         keep = []
-        opts = self._opts_for(loudness, pitch if want_audio else None)
+        opts = self._opts_for(loudness, pitch if want_audio else None, preserve_formants)
         if noise is not None:
             a = _f32(noise); keep.append(a)
             if a.ndim != 2 or a.shape[0] != self.hp.n_feats:
@@ -236,8 +242,8 @@ class SttsModel:
 
     def synthesize_batch(self, ids, lengths, scales, sid, bert=None, phone_duration_extra=None, seed=0, n_timesteps=0, item_seeds=None,
                          denoiser_strength=None, denoiser_filter_length=0, marks=False, sample_rate=None, loudness=None, loudness_out=None,
-                         pitch=None):
-        """pitch: as for synthesize, one value for the batch; every item is shifted from its own length.
+                         pitch=None, preserve_formants=False):
+        """pitch, preserve_formants: as for synthesize, one value for the batch; every item is shifted from its own length.
         B independent utterances in one pass (stts_synthesize_batch): ids [B,5,T], lengths [B], sid [B];
         returns (audio float32 [B,S] zero-padded, out_lengths int64 [B] in samples).  Item b equals
         synthesize(ids[b][:, :lengths[b]], ..., seed=item_seeds[b]) (seed + b without item seeds).  marks=True
@@ -250,7 +256,7 @@ class SttsModel:
         B, five, T = ids.shape
         b = None if bert is None else _f32(bert)
         p = None if phone_duration_extra is None else _f32(phone_duration_extra)
-        opts = self._opts_for(loudness, pitch)
+        opts = self._opts_for(loudness, pitch, preserve_formants)
         opts.seed = seed; opts.n_timesteps = n_timesteps
         self._denoise(opts, denoiser_strength, denoiser_filter_length)
         keep = []

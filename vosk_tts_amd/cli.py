@@ -36,6 +36,9 @@ _OPTIONS = (
     (("--pitch",), dict(type=float, default=None, metavar="SEMITONES",
                         help="shift the pitch of the audio by this many semitones, -12 to 12, at unchanged duration (default: the voice's "
                              "inference.pitch, else none)")),
+    (("--preserve-formants",), dict(action="store_true", default=None,
+                                    help="with a pitch shift: keep the voice's formants where they were (default: the voice's "
+                                         "inference.pitch_formants, else off)")),
     (("--marks",), dict(type=str, default=None, metavar="FILE",
                         help="also write the speech marks as JSON: rate, phonemes and words with their offsets in samples and seconds")),
     (("--log-level",), dict(default="INFO", metavar="LEVEL", help="python logging level (INFO shows the RTF line)")),
@@ -64,7 +67,8 @@ def run(opts):
 
     voice = model_mod.Model(opts.model, opts.model_name, opts.lang)
     marks = Synth(voice).synth(opts.input, opts.output, opts.speaker, speech_rate=opts.speech_rate, sample_rate=opts.sample_rate,
-                               denoiser_strength=opts.denoiser_strength, marks=bool(opts.marks), loudness=opts.loudness, peak=opts.peak, pitch=opts.pitch)
+                               denoiser_strength=opts.denoiser_strength, marks=bool(opts.marks), loudness=opts.loudness, peak=opts.peak, pitch=opts.pitch,
+                               preserve_formants=opts.preserve_formants)
     if opts.marks:
         with open(opts.marks, "w", encoding="utf-8") as f:
             f.write(marks.to_json(indent=1) + "\n")

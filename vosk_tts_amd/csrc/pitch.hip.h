@@ -5,6 +5,9 @@
 // Launches per group of items (every kernel derives an item's F_a, F_s and N_u from its length: no per-item host tables):
 //   pitch_analysis_kernel  one wave per frame, DN_FPB frames per workgroup, as denoise_frames_kernel: |X| and the phase as a 32-bit
 //                          fixed-point turn, [B][F_a + 2][NB]; the two rows behind an item's last frame are written as zeros
+//   pitch_formant_kernel   (VITS_FLAG_PITCH_FORMANT only) one wave per analysis row: the cepstral envelope of the row and the gain that
+//                          pre-warps it, mag' = mag g, [B][F_a + 2][NB]; pitch_synth_kernel then reads mag' where it read mag, and
+//                          pitch_phase_kernel still reads mag: the phases are those of the plain call
 //   pitch_phase_kernel     one workgroup per item, one thread per bin, a loop over the steps t.  Phi_{t-1}[k] stays in thread k's
 //                          register; a step stages m_t, adv and theta_i in LDS, tests the peak against the four neighbours, publishes
 //                          the peaks as one 64-bit ballot per wave and finds the nearest set bit either side of k in those nine words;
@@ -91,6 +94,131 @@ __global__ __launch_bounds__(64 * DN_FPB) void pitch_analysis_kernel(const float
     mo[kp] = valid ? sqrtf(xpr * xpr + xpi * xpi) : 0.f;
     to[k] = valid ? pt_theta(xkr, xki) : 0u;
     to[kp] = valid ? pt_theta(xpr, xpi) : 0u;
+  }
+}
+
+// Steps 3a-3d of include/vits_pitch.h (VITS_FLAG_PITCH_FORMANT) on rows [0, F_a + 2) of every item, the grid and the row ownership of
+// pitch_analysis_kernel: out_f[k] = mag_f[k] g_f[k] (GAIN: g_f[k] itself, and mag is not read), zeros in the two rows behind the last
+// frame.
+//   The magnitudes under the logarithm are not the fp32 rows of pitch_analysis_kernel: those sit a few 1e-7 of the frame's level from
+// the exact spectrum, which the logarithm turns into a relative error of 1e-4 and more at a bin near zero (the reflect-symmetric first
+// frame has many: its spectrum is real up to a linear phase and crosses zero), and every such bin moves the whole envelope of its row
+// (measured through vits_op_pitch_formant_gain: 3.2 to 4.5 times the fp32 restatement's distance from float64, where the rest of this
+// kernel adds nothing that shows).  So a wave transforms its frame again in double: the window as sinpi^2, a 512-point radix-2 transform
+// of the packed frame in LDS and the unpacking of pitch_analysis_kernel, the magnitude rounded to fp32 once.  From there on fp32.
+//   A wave keeps L of its row in LDS; lane t sums D[k] cos(2 pi k q / n), D = L - L[0], over its bins k = t + 64 j into C + 1 registers
+// (k = 0 carries D = 0 and adds nothing; the cosine comes from the n-entry table in LDS, padded by one word per 32 so that the stride
+// 32 k of q = 32 spreads over the banks), a butterfly adds the lanes (the same order in every lane, so every lane holds the same
+// c[q]), and each lane then forms the two series of 3c for its bins: e(k) from the table, e(kappa_k) with cospif of 2 r / (Q n).  No
+// transform for the cepstrum: at C = 40 the direct sums are about 42 k multiply-adds a row.
+#define PT_C VITS_PITCH_LIFTER
+#define PT_COS(i) ((i) + ((i) >> 5))
+static_assert(PT_M * 1999 < (1 << 30) && 1000 * PT_N < (1 << 30), "k P, Q n and r + (k P mod Q n) stay below 2^31");
+
+template <bool GAIN>
+__global__ __launch_bounds__(64 * DN_FPB) void pitch_formant_kernel(const float* __restrict__ x, long long x_bstride, long long x_n,
+                                                                    const float* __restrict__ mag, long long a_bstride,
+                                                                    const int* __restrict__ len_frames, long long len_mul, int P, int Q,
+                                                                    float* __restrict__ out) {
+  __shared__ double2 s_tw[PT_M];  // exp(-2 pi i t / n), t < n/2
+  __shared__ double2 s_z[DN_FPB][PT_M];
+  __shared__ float s_cos[PT_N + PT_N / 32];
+  __shared__ float s_l[DN_FPB][PT_NB];
+  const int wv = threadIdx.x >> 6, t = threadIdx.x & 63;
+  const int b = blockIdx.y;
+  const long long len = len_frames ? len_frames[b] * len_mul : len_mul;
+  const long long Fa = pt_frames_a(len);
+  if (Fa == 0 || (long long)blockIdx.x * DN_FPB >= Fa + 2) return;  // uniform over the workgroup
+  const long long f = (long long)blockIdx.x * DN_FPB + wv;
+  const bool valid = f < Fa;
+  for (int i = threadIdx.x; i < PT_N; i += 64 * DN_FPB) s_cos[PT_COS(i)] = cospif((float)i * (2.f / PT_N));
+  for (int i = threadIdx.x; i < PT_M; i += 64 * DN_FPB) {
+    double sn, cs;
+    sincospi((double)i * (2.0 / PT_N), &sn, &cs);
+    s_tw[i] = make_double2(cs, -sn);
+  }
+  // the windowed frame, two samples to a complex point, in bit-reversed order (a wave whose row is behind the last frame transforms zeros)
+  double2* Z = s_z[wv];
+  const float* xb = x + (long long)b * x_bstride;
+  for (int m = t; m < PT_M; m += 64) {
+    double v0 = 0.0, v1 = 0.0;
+    if (valid) {
+      const long long p = f * PT_H + 2 * m;
+      const double w0 = sinpi((double)(2 * m) * (1.0 / PT_N)), w1 = sinpi((double)(2 * m + 1) * (1.0 / PT_N));
+      v0 = (double)dn_load(xb, p, PT_M, len, 0, x_n) * (w0 * w0);
+      v1 = (double)dn_load(xb, p + 1, PT_M, len, 0, x_n) * (w1 * w1);
+    }
+    Z[__brev((unsigned)m) >> (32 - PT_LOG2M)] = make_double2(v0, v1);
+  }
+  __syncthreads();
+  for (int h = 1; h < PT_M; h <<= 1) {  // groups of 2 h points, twiddle exp(-2 pi i pos / (2 h))
+    for (int j = t; j < PT_M / 2; j += 64) {
+      const int pos = j & (h - 1), i0 = ((j - pos) << 1) + pos, i1 = i0 + h;
+      const double2 w = s_tw[pos * (PT_M / h)], u = Z[i0], v = Z[i1];
+      const double tr = w.x * v.x - w.y * v.y, ti = w.x * v.y + w.y * v.x;
+      Z[i0] = make_double2(u.x + tr, u.y + ti);
+      Z[i1] = make_double2(u.x - tr, u.y - ti);
+    }
+    __syncthreads();
+  }
+  float* L = s_l[wv];
+  if (valid)
+    for (int k = t; k < PT_NB; k += 64) {  // X[k] = E[k] + exp(-2 pi i k / n) O[k] of the packed transform
+      const double2 zk = Z[k & (PT_M - 1)], zp = Z[(PT_M - k) & (PT_M - 1)];
+      const double2 w = k < PT_M ? s_tw[k] : make_double2(-1.0, 0.0);
+      const double er = 0.5 * (zk.x + zp.x), ei = 0.5 * (zk.y - zp.y), o_r = 0.5 * (zk.y + zp.y), o_i = -0.5 * (zk.x - zp.x);
+      const double xr = er + (w.x * o_r - w.y * o_i), xi = ei + (w.x * o_i + w.y * o_r);
+      L[k] = logf(fmaxf((float)sqrt(xr * xr + xi * xi), VITS_PITCH_LOG_FLOOR));
+    }
+  __syncthreads();
+  if (f >= Fa + 2) return;
+  float* o = out + (long long)b * a_bstride + f * PT_NB;
+  if (!valid) {
+    for (int k = t; k < PT_NB; k += 64) o[k] = 0.f;
+    return;
+  }
+  float c[PT_C + 1];
+#pragma unroll
+  for (int q = 0; q <= PT_C; ++q) c[q] = 0.f;
+  const float* mi = mag + (long long)b * a_bstride + f * PT_NB;  // (a row of this item: f < F_a)
+  const float l0 = L[0];
+  for (int k = t; k < PT_M; k += 64) {
+    const float d = L[k] - l0;
+    int idx = 0;
+#pragma unroll
+    for (int q = 0; q <= PT_C; ++q) {
+      c[q] = fmaf(d, s_cos[PT_COS(idx)], c[q]);
+      idx = (idx + k) & (PT_N - 1);
+    }
+  }
+  const float d0 = 0.f, dm = L[PT_M] - l0;  // D[0], D[n/2]
+#pragma unroll
+  for (int q = 0; q <= PT_C; ++q) {
+    float s = c[q];
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) s += __shfl_xor(s, off);
+    c[q] = (d0 + ((q & 1) ? -dm : dm) + 2.f * s) * (1.f / PT_N);
+  }
+  const int QN = Q * PT_N;
+  const float g_max = (float)(VITS_PITCH_FORMANT_MAX_DB * 2.30258509299404568402 / 20.0), qn_f = (float)QN;
+  for (int k = t; k < PT_NB; k += 64) {
+    const int kP = k * P, step = kP % QN;
+    const bool top = kP >= PT_M * Q;  // kappa_k = n/2
+    int idx = 0, r = 0;
+    float sk = 0.f, sx = 0.f;
+#pragma unroll
+    for (int q = 1; q <= PT_C; ++q) {
+      idx = (idx + k) & (PT_N - 1);
+      r += step;
+      if (r >= QN) r -= QN;
+      const float cx = top ? ((q & 1) ? -1.f : 1.f) : cospif(__fdiv_rn((float)(2 * r), qn_f));
+      sk = fmaf(c[q], s_cos[PT_COS(idx)], sk);
+      sx = fmaf(c[q], cx, sx);
+    }
+    const float ek = c[0] + 2.f * sk, ex = c[0] + 2.f * sx;
+    const float g = expf(fminf(fmaxf(ex - ek, -g_max), g_max));
+    if constexpr (GAIN) o[k] = g;
+    else o[k] = mi[k] * g;
   }
 }
 
@@ -289,7 +417,7 @@ __global__ __launch_bounds__(256) void pitch_short_kernel(const float* __restric
 }
 
 // ---- host ---------------------------------------------------------------------------------------------------------------
-struct PitchReq { bool on = false; int P = 1, Q = 1; };
+struct PitchReq { bool on = false; int P = 1, Q = 1; bool formant = false; };
 
 static int pitch_plan(float semitones, int* P, int* Q) {
   if (!(fabsf(semitones) <= (float)VITS_PITCH_MAX_SEMITONES))  // (NaN fails the comparison)
@@ -331,17 +459,18 @@ static int pitch_tab_get(int device, int P, int Q, std::shared_ptr<ResampleTab>*
 }
 
 // bytes of scratch an item of `len` samples takes in a group (the strides of a group are those of its longest item)
-static size_t pitch_item_bytes(long long len, int P, int Q) {
+static size_t pitch_item_bytes(long long len, int P, int Q, bool formant) {
   const long long Fa = pt_frames_a(len), Fs = pt_frames_s(len, P, Q);
   if (!Fa) return 2 * sizeof(int);
-  return (size_t)(Fa + 2) * PT_NB * 8 + (size_t)Fs * PT_NB * 4 + (size_t)Fs * PT_N * 4 + (size_t)(Fs - 1) * PT_H * 4 + 2 * sizeof(int) + 64;
+  return (size_t)(Fa + 2) * PT_NB * (formant ? 12 : 8) + (size_t)Fs * PT_NB * 4 + (size_t)Fs * PT_N * 4 + (size_t)(Fs - 1) * PT_H * 4 + 2 * sizeof(int) + 64;
 }
 
 // y[b][0 .. n_count) = the shifted item b, for B items on `stream`; x / len_frames / len_mul as in denoise_launch (device pointers),
 // h_len their lengths on the host.  Allocates its scratch and waits for the stream before it frees it: not capturable.  y is not x.
 // u_out (nullable): the stretch door -- u goes to u_out[b * u_bstride + j], j < u_bstride, and nothing is resampled.
+// formant: steps 3a-3d -- the synthesis reads the corrected magnitudes, the phase recursion the plain ones.
 static int pitch_run(int device, hipStream_t stream, const float* x, long long x_bstride, long long x_n, const int* len_frames, long long len_mul,
-                     const long long* h_len, int B, int P, int Q, float* y, long long y_bstride, long long n_count, float* u_out,
+                     const long long* h_len, int B, int P, int Q, bool formant, float* y, long long y_bstride, long long n_count, float* u_out,
                      long long u_bstride) {
   if (B <= 0) return VITS_OK;
   const DenoiseTab* D = nullptr;
@@ -356,13 +485,13 @@ static int pitch_run(int device, hipStream_t stream, const float* x, long long x
     int c = 0;
     while (b0 + c < B && c < 65535) {
       const long long m2 = std::max(mx, h_len[b0 + c]);
-      if (pitch_item_bytes(m2, P, Q) * (size_t)(c + 1) > (size_t)VITS_PITCH_MAX_SCRATCH) break;
+      if (pitch_item_bytes(m2, P, Q, formant) * (size_t)(c + 1) > (size_t)VITS_PITCH_MAX_SCRATCH) break;
       mx = m2;
       ++c;
     }
     if (!c) return fail(VITS_ERR_UNSUPPORTED, "pitch: an item of %lld samples needs %zu bytes of scratch at %d/%d (limit %lld)", h_len[b0],
-                        pitch_item_bytes(h_len[b0], P, Q), P, Q, (long long)VITS_PITCH_MAX_SCRATCH);
-    need = std::max(need, pitch_item_bytes(mx, P, Q) * (size_t)c);
+                        pitch_item_bytes(h_len[b0], P, Q, formant), P, Q, (long long)VITS_PITCH_MAX_SCRATCH);
+    need = std::max(need, pitch_item_bytes(mx, P, Q, formant) * (size_t)c);
     groups.emplace_back(b0, c);
     b0 += c;
   }
@@ -381,6 +510,8 @@ static int pitch_run(int device, hipStream_t stream, const float* x, long long x
       char* p = scr;
       float* d_mag = reinterpret_cast<float*>(p); p += sizeof(float) * (size_t)c * a_bs;
       unsigned* d_th = reinterpret_cast<unsigned*>(p); p += sizeof(unsigned) * (size_t)c * a_bs;
+      float* d_magf = d_mag;  // what the synthesis reads
+      if (formant) { d_magf = reinterpret_cast<float*>(p); p += sizeof(float) * (size_t)c * a_bs; }
       unsigned* d_phi = reinterpret_cast<unsigned*>(p); p += sizeof(unsigned) * (size_t)c * p_bs;
       p += (8 - (p - scr) % 8) % 8;  // (the frames are written as float2)
       float* d_fr = reinterpret_cast<float*>(p); p += sizeof(float) * (size_t)c * f_bs;
@@ -389,8 +520,11 @@ static int pitch_run(int device, hipStream_t stream, const float* x, long long x
       int* d_crop = reinterpret_cast<int*>(p);
       hipLaunchKernelGGL(pitch_analysis_kernel, dim3((unsigned)((Fa + 2 + DN_FPB - 1) / DN_FPB), c), dim3(64 * DN_FPB), 0, stream, xg, x_bstride,
                          x_n, lg, len_mul, D->d_win, D->d_tw, d_mag, d_th, a_bs);
+      if (formant)
+        hipLaunchKernelGGL(pitch_formant_kernel<false>, dim3((unsigned)((Fa + 2 + DN_FPB - 1) / DN_FPB), c), dim3(64 * DN_FPB), 0, stream, xg,
+                           x_bstride, x_n, d_mag, a_bs, lg, len_mul, P, Q, d_magf);
       hipLaunchKernelGGL(pitch_phase_kernel, dim3(c), dim3(64 * PT_WAVES), 0, stream, d_mag, d_th, a_bs, lg, len_mul, P, Q, d_phi, p_bs);
-      hipLaunchKernelGGL(pitch_synth_kernel, dim3((unsigned)((Fs + DN_FPB - 1) / DN_FPB), c), dim3(64 * DN_FPB), 0, stream, d_mag, a_bs, d_phi,
+      hipLaunchKernelGGL(pitch_synth_kernel, dim3((unsigned)((Fs + DN_FPB - 1) / DN_FPB), c), dim3(64 * DN_FPB), 0, stream, d_magf, a_bs, d_phi,
                          p_bs, lg, len_mul, P, Q, D->d_win, D->d_tw, d_fr, f_bs);
       if (u_out) {
         hipLaunchKernelGGL(pitch_ola_kernel, dim3((unsigned)((u_bstride + 255) / 256), c), dim3(256), 0, stream, d_fr, f_bs, lg, len_mul, P, Q,
@@ -418,8 +552,15 @@ static int pitch_run(int device, hipStream_t stream, const float* x, long long x
   return VITS_OK;
 }
 
+// the formant bit modifies a pitch request: alone it is refused, before any work is queued (`family`: VITS or STTS, for the names)
+static int pitch_flags_check(uint32_t flags, uint32_t pitch_bit, uint32_t formant_bit, const char* family) {
+  if ((flags & formant_bit) && !(flags & pitch_bit))
+    return fail(VITS_ERR_ARG, "%s_FLAG_PITCH_FORMANT without %s_FLAG_PITCH: the flag modifies a pitch request (include/vits_pitch.h)", family, family);
+  return VITS_OK;
+}
+
 // what a shifting entry point of a vocoder needs checked before any work is queued
-static int pitch_req(const vits_model* v, float semitones, PitchReq* q) {
+static int pitch_req(const vits_model* v, float semitones, bool formant, PitchReq* q) {
   q->on = false;
   int P = 1, Q = 1;
   TRY(pitch_plan(semitones, &P, &Q));
@@ -428,16 +569,18 @@ static int pitch_req(const vits_model* v, float semitones, PitchReq* q) {
     return fail(VITS_ERR_UNSUPPORTED, "pitch: the vocoder's hop_length %d is not a multiple of the pitch stage's hop %d", v->hp.hop_length, PT_H);
   ResamplePlan rp;
   TRY(resample_plan(P, Q, &rp));
-  q->on = true; q->P = P; q->Q = Q;
+  q->on = true; q->P = P; q->Q = Q; q->formant = formant;
   return VITS_OK;
 }
 
 // VITS_FLAG_PITCH of a call: under the flag `opts` is the `base` of a vits_synth_opts_pitch, whose last field is read only then
 static int pitch_req_opts(const vits_model* v, const vits_synth_opts* opts, PitchReq* q) {
   q->on = false;
-  if (!opts || !(opts->flags & VITS_FLAG_PITCH)) return VITS_OK;
+  if (!opts) return VITS_OK;
+  TRY(pitch_flags_check(opts->flags, VITS_FLAG_PITCH, VITS_FLAG_PITCH_FORMANT, "VITS"));
+  if (!(opts->flags & VITS_FLAG_PITCH)) return VITS_OK;
   static_assert(offsetof(vits_synth_opts_pitch, base) == 0, "the extended options begin with the plain ones");
-  return pitch_req(v, reinterpret_cast<const vits_synth_opts_pitch*>(opts)->pitch_semitones, q);
+  return pitch_req(v, reinterpret_cast<const vits_synth_opts_pitch*>(opts)->pitch_semitones, (opts->flags & VITS_FLAG_PITCH_FORMANT) != 0, q);
 }
 
 // The tail of a flagged vits_synthesize* call behind the decoder: pitch, resample, normalise, conversion, as launches on `stream` from
@@ -459,7 +602,7 @@ static int pitch_tail_run(PitchTail& pt, vits_session* s, hipStream_t stream, co
   const int device = s->m->device;
   float* d_p = static_cast<float*>(pt.alloc(sizeof(float) * (size_t)B * S));
   if (!d_p) return fail(VITS_ERR_NOMEM, "pitch: device alloc failed");
-  TRY(pitch_run(device, stream, x, S, S, len_y, hop, h_len, B, pq.P, pq.Q, d_p, S, S, nullptr, 0));
+  TRY(pitch_run(device, stream, x, S, S, len_y, hop, h_len, B, pq.P, pq.Q, pq.formant, d_p, S, S, nullptr, 0));
   const long long So = T ? T->P.n_out(S) : S;
   const size_t esz = pcm ? sizeof(int16_t) : sizeof(float);
   *So_out = So;
@@ -508,7 +651,26 @@ int vits_pitch_plan(float semitones, int32_t* P, int32_t* Q) {
   return VITS_OK;
 }
 
-static int pitch_op(int device, const float* x, const int64_t* lengths, int32_t B, int64_t N, float semitones, float* y, bool stretch) {
+// the gains of step 3d for B items on the device (x [B][N], their lengths in dl): pitch_formant_kernel<true> into g [B][N / H + 3][NB],
+// which the caller has zeroed (the rows at and beyond F_a + 2, and the items too short to have frames)
+static int pitch_gain_run(int device, const float* dx, const int* dl, int B, long long N, int P, int Q, float* g) {
+  const long long Fa = pt_frames_a(N), a_bs = (N / PT_H + 3) * PT_NB;
+  if (!Fa) return VITS_OK;
+  HIP_TRY(hipSetDevice(device));
+  hipLaunchKernelGGL(pitch_formant_kernel<true>, dim3((unsigned)((Fa + 2 + DN_FPB - 1) / DN_FPB), B), dim3(64 * DN_FPB), 0, nullptr, dx, N, N,
+                     (const float*)nullptr, a_bs, dl, 1, P, Q, g);
+  hipError_t e = hipGetLastError();
+  const hipError_t e2 = hipStreamSynchronize(nullptr);
+  if (e == hipSuccess) e = e2;
+  if (e != hipSuccess) return fail(VITS_ERR_DEVICE, "pitch: %s", hipGetErrorString(e));
+  return VITS_OK;
+}
+
+enum PitchDoor { PT_DOOR_SHIFT, PT_DOOR_STRETCH, PT_DOOR_GAIN };
+
+static int pitch_op(int device, const float* x, const int64_t* lengths, int32_t B, int64_t N, float semitones, float* y, PitchDoor door,
+                    bool formant) {
+  const bool stretch = door == PT_DOOR_STRETCH;
   if (!x || !lengths || !y || B <= 0 || B > 65535 || N <= 0 || N >= (1LL << 31)) return fail(VITS_ERR_ARG, "pitch: bad argument");
   int P = 1, Q = 1;
   TRY(pitch_plan(semitones, &P, &Q));
@@ -521,13 +683,14 @@ static int pitch_op(int device, const float* x, const int64_t* lengths, int32_t 
   }
   if (P == Q) {
     if (stretch) return fail(VITS_ERR_ARG, "pitch: %g semitones is the identity (P = Q): there is no stretch to return", (double)semitones);
+    if (door == PT_DOOR_GAIN) return fail(VITS_ERR_ARG, "pitch: %g semitones is the identity (P = Q): there is no gain to return", (double)semitones);
     for (int b = 0; b < B; ++b) {
       memcpy(y + (size_t)b * N, x + (size_t)b * N, sizeof(float) * (size_t)lengths[b]);
       memset(y + (size_t)b * N + lengths[b], 0, sizeof(float) * (size_t)(N - lengths[b]));
     }
     return VITS_OK;
   }
-  const long long Ny = stretch ? (long long)PT_H * (((N / PT_H + 2) * P + Q - 1) / Q - 1) : N;
+  const long long Ny = stretch ? (long long)PT_H * (((N / PT_H + 2) * P + Q - 1) / Q - 1) : door == PT_DOOR_GAIN ? (N / PT_H + 3) * PT_NB : N;
   HIP_TRY(hipSetDevice(device));
   float *dx = nullptr, *dy = nullptr;
   int* dl = nullptr;
@@ -539,11 +702,13 @@ static int pitch_op(int device, const float* x, const int64_t* lengths, int32_t 
   for (int b = 0; b < B && e == hipSuccess; ++b)
     if (lengths[b]) e = hipMemcpy(dx + (size_t)b * N, x + (size_t)b * N, sizeof(float) * (size_t)lengths[b], hipMemcpyHostToDevice);
   if (e == hipSuccess) e = hipMemcpy(dl, len32.data(), sizeof(int) * B, hipMemcpyHostToDevice);
-  if (e == hipSuccess) e = hipMemset(dy, 0xff, sizeof(float) * (size_t)B * Ny);  // NaN: an output the kernels do not write shows
+  // NaN: an output the kernels do not write shows (the gain door's kernel writes rows [0, F_a + 2) only: the others are zeros from here)
+  if (e == hipSuccess) e = hipMemset(dy, door == PT_DOOR_GAIN ? 0 : 0xff, sizeof(float) * (size_t)B * Ny);
   int rc = VITS_OK;
   if (e == hipSuccess) {
-    rc = stretch ? pitch_run(device, nullptr, dx, N, N, dl, 1, len64.data(), B, P, Q, nullptr, 0, 0, dy, Ny)
-                 : pitch_run(device, nullptr, dx, N, N, dl, 1, len64.data(), B, P, Q, dy, Ny, Ny, nullptr, 0);
+    rc = door == PT_DOOR_GAIN ? pitch_gain_run(device, dx, dl, B, N, P, Q, dy)
+         : stretch            ? pitch_run(device, nullptr, dx, N, N, dl, 1, len64.data(), B, P, Q, formant, nullptr, 0, 0, dy, Ny)
+                              : pitch_run(device, nullptr, dx, N, N, dl, 1, len64.data(), B, P, Q, formant, dy, Ny, Ny, nullptr, 0);
     if (rc == VITS_OK) e = hipMemcpy(y, dy, sizeof(float) * (size_t)B * Ny, hipMemcpyDeviceToHost);
   }
   hipFree(dx); hipFree(dy); hipFree(dl);
@@ -553,8 +718,17 @@ static int pitch_op(int device, const float* x, const int64_t* lengths, int32_t 
 }
 
 int vits_op_pitch_shift(int device, const float* x, const int64_t* lengths, int32_t B, int64_t N, float semitones, float* y) {
-  return pitch_op(device, x, lengths, B, N, semitones, y, false);
+  return pitch_op(device, x, lengths, B, N, semitones, y, PT_DOOR_SHIFT, false);
 }
 int vits_op_pitch_stretch(int device, const float* x, const int64_t* lengths, int32_t B, int64_t N, float semitones, float* y) {
-  return pitch_op(device, x, lengths, B, N, semitones, y, true);
+  return pitch_op(device, x, lengths, B, N, semitones, y, PT_DOOR_STRETCH, false);
+}
+int vits_op_pitch_shift_formant(int device, const float* x, const int64_t* lengths, int32_t B, int64_t N, float semitones, float* y) {
+  return pitch_op(device, x, lengths, B, N, semitones, y, PT_DOOR_SHIFT, true);
+}
+int vits_op_pitch_stretch_formant(int device, const float* x, const int64_t* lengths, int32_t B, int64_t N, float semitones, float* y) {
+  return pitch_op(device, x, lengths, B, N, semitones, y, PT_DOOR_STRETCH, true);
+}
+int vits_op_pitch_formant_gain(int device, const float* x, const int64_t* lengths, int32_t B, int64_t N, float semitones, float* gain) {
+  return pitch_op(device, x, lengths, B, N, semitones, gain, PT_DOOR_GAIN, false);
 }

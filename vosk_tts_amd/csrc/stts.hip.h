@@ -1144,21 +1144,23 @@ static int stts_loud_out(stts_model* m, const LoudReq& q, int B, float* audio, i
 }
 
 // STTS_FLAG_PITCH of a call (include/vits_pitch.h): under the flag `opts` is the `base.base` of a stts_synth_opts_pitch, whose last field
-// is read only then.  Checked before anything is synthesised.
+// is read only then; STTS_FLAG_PITCH_FORMANT rides on it.  Checked before anything is synthesised.
 static int stts_pitch_arg(const stts_model* m, const stts_synth_opts* opts, PitchReq* q, float* semitones) {
   q->on = false;
-  if (!opts || !(opts->flags & STTS_FLAG_PITCH)) return VITS_OK;
+  if (!opts) return VITS_OK;
+  TRY(pitch_flags_check(opts->flags, STTS_FLAG_PITCH, STTS_FLAG_PITCH_FORMANT, "STTS"));
+  if (!(opts->flags & STTS_FLAG_PITCH)) return VITS_OK;
   if (!m->vocoder) return fail(VITS_ERR_ARG, "no vocoder attached");
   static_assert(offsetof(stts_synth_opts_pitch, base) == 0, "the extended options begin with the plain ones");
   *semitones = reinterpret_cast<const stts_synth_opts_pitch*>(opts)->pitch_semitones;
-  return pitch_req(m->vocoder, *semitones, q);
+  return pitch_req(m->vocoder, *semitones, (opts->flags & STTS_FLAG_PITCH_FORMANT) != 0, q);
 }
 // a call's native-rate audio [B, S] (items of lengths[b] samples) shifted in place: behind the denoiser and before the resampler (the
 // kernels of vits_op_pitch_shift; like stts_resample_out, it crosses the host once more)
 static int stts_pitch_out(stts_model* m, const PitchReq& q, float semitones, int B, float* audio, int64_t S, const int64_t* lengths) {
   if (!q.on || S <= 0) return VITS_OK;
   std::vector<float> y((size_t)B * S);
-  TRY(pitch_op(m->base.device, audio, lengths, B, S, semitones, y.data(), false));
+  TRY(pitch_op(m->base.device, audio, lengths, B, S, semitones, y.data(), PT_DOOR_SHIFT, q.formant));
   memcpy(audio, y.data(), sizeof(float) * y.size());
   return VITS_OK;
 }
@@ -1212,6 +1214,7 @@ int stts_stream_open(stts_model* m, const int64_t* ids, int32_t Tx, const float*
   if (!m->vocoder) return fail(VITS_ERR_ARG, "no vocoder attached");
   if (opts && (opts->flags & STTS_FLAG_LOUDNESS))
     return fail(VITS_ERR_UNSUPPORTED, "STTS_FLAG_LOUDNESS on a stream: an integrated-loudness or peak target needs the whole utterance before the first chunk");
+  if (opts) TRY(pitch_flags_check(opts->flags, STTS_FLAG_PITCH, STTS_FLAG_PITCH_FORMANT, "STTS"));
   if (opts && (opts->flags & STTS_FLAG_PITCH))
     return fail(VITS_ERR_UNSUPPORTED, "STTS_FLAG_PITCH on a stream: the phase recursion needs the frames before a chunk, and its state is not carried across chunks");
   float* mel = nullptr;

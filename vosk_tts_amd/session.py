@@ -226,7 +226,7 @@ _GRAPH_INPUTS = ("input", "input_lengths", "scales", "sid")
 _OPTIONAL_NONE = ("bert", "phone_duration_extra")
 # extension feeds (not part of the ONNX graph) used by parity tests
 _EXT = ("vits.noise_dp", "vits.noise_prior", "vits.forced_durations", "vits.seed", "vits.solo", "vits.item_seeds", "vits.sample_rate", "vits.marks",
-        "vits.loudness", "vits.peak", "vits.peak_ceiling", "vits.pitch")
+        "vits.loudness", "vits.peak", "vits.peak_ceiling", "vits.pitch", "vits.pitch_formants")
 
 
 class _Arg:
@@ -296,8 +296,9 @@ class VitsSession:
         # loud: the normalisation of the batch (capi.loudness_spec(), None = none; include/vits_loudness.h): part of the key like the rate, and
         # measured and applied per item, so a request's result does not depend on what it was batched with
         # pitch: the shift of the batch in semitones (None = none; include/vits_pitch.h): part of the key as well, one value per call
-        kind, scales, scale, rate, marks, loud, pitch = key
-        pk = {"pitch": pitch} if pitch is not None else {}
+        # formants: that shift with the spectral envelope kept (VITS_FLAG_PITCH_FORMANT); False whenever pitch is None
+        kind, scales, scale, rate, marks, loud, pitch, formants = key
+        pk = self._pitch_kw(pitch, formants)
         scales = np.array(scales, np.float32)
         if len(reqs) == 1:
             ids, sid, seed = reqs[0]
@@ -399,6 +400,21 @@ class VitsSession:
             self._lib._need_pitch()
         return p
 
+    def _formants(self, feed, pitch):
+        """the extension feed "vits.pitch_formants" (bool; VITS_FLAG_PITCH_FORMANT) -> whether the shift `pitch` (what _pitch returned)
+        keeps the spectral envelope.  It modifies a shift: without one in effect it is False, the request as it was"""
+        on = pitch is not None and bool(feed.get("vits.pitch_formants", False))
+        if on:
+            self._lib._need_pitch_formant()
+        return on
+
+    @staticmethod
+    def _pitch_kw(pitch, formants):
+        """the keywords of the model's calls: none without a shift (the call as it was)"""
+        if pitch is None:
+            return {}
+        return {"pitch": pitch, "preserve_formants": True} if formants else {"pitch": pitch}
+
     def run(self, output_names, input_feed, run_options=None):
         """Extension feed "vits.sample_rate" (next to "vits.seed"): output rate in Hz; the time axis of the output is then in output
         samples (include/vits_resample.h).  Extension feed "vits.marks": True -- the result list gets a second entry, token_ends int64
@@ -410,9 +426,10 @@ class VitsSession:
         marks = self._marks(feed)
         loud = self._loudness(feed)
         pitch = self._pitch(feed)  # ("vits.pitch": the audio shifted by that many semitones, behind the decoder)
+        formants = self._formants(feed, pitch)
         n = self._coalescable(feed, ids)
         if n:
-            key = ("f32", tuple(float(v) for v in np.asarray(feed["scales"], np.float32).reshape(-1)), 1.0, rate, marks, loud, pitch)
+            key = ("f32", tuple(float(v) for v in np.asarray(feed["scales"], np.float32).reshape(-1)), 1.0, rate, marks, loud, pitch, formants)
             res = self.coalescer.submit(key, np.ascontiguousarray(ids[:, :n], np.int64), int(sid[0]), int(seed))
             self.last_lengths = res[1]
             if marks:  # (the request's own tokens; columns beyond its length repeat the last end, as the C ABI pads them)
@@ -423,7 +440,7 @@ class VitsSession:
             noise_dp=feed.get("vits.noise_dp"), noise_prior=feed.get("vits.noise_prior"),
             forced_durations=feed.get("vits.forced_durations"), seed=int(seed), solo=bool(feed.get("vits.solo", False)),
             item_seeds=feed.get("vits.item_seeds"), bert=feed.get("bert"), sample_rate=rate, marks=marks, loudness=loud,
-            **({"pitch": pitch} if pitch is not None else {}))
+            **self._pitch_kw(pitch, formants))
         self.last_lengths = res[1]
         return [res[0][:, None, None, :], res[2]] if marks else [res[0][:, None, None, :]]
 
@@ -457,9 +474,10 @@ class VitsSession:
         marks = self._marks(feed)
         loud = self._loudness(feed)
         pitch = self._pitch(feed)
+        formants = self._formants(feed, pitch)
         n = self._coalescable(feed, ids)
         if n:
-            key = ("pcm", tuple(float(v) for v in np.asarray(feed["scales"], np.float32).reshape(-1)), float(scale), rate, marks, loud, pitch)
+            key = ("pcm", tuple(float(v) for v in np.asarray(feed["scales"], np.float32).reshape(-1)), float(scale), rate, marks, loud, pitch, formants)
             res = self.coalescer.submit(key, np.ascontiguousarray(ids[:, :n], np.int64), int(sid[0]), int(seed))
             pcm, lengths = res[0], res[1]
             self.last_lengths = lengths
@@ -472,7 +490,7 @@ class VitsSession:
             pcm_scale=float(scale), noise_dp=feed.get("vits.noise_dp"), noise_prior=feed.get("vits.noise_prior"),
             forced_durations=feed.get("vits.forced_durations"), seed=int(seed), solo=bool(feed.get("vits.solo", False)),
             item_seeds=feed.get("vits.item_seeds"), bert=feed.get("bert"), sample_rate=rate, marks=marks, loudness=loud,
-            **({"pitch": pitch} if pitch is not None else {}))
+            **self._pitch_kw(pitch, formants))
         pcm, lengths = res[0], res[1]
         self.last_lengths = lengths
         if marks:

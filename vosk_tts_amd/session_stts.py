@@ -14,7 +14,7 @@ from .capi_stts import SttsModel
 
 _INPUTS = ("input", "input_lengths", "scales", "sid", "bert", "phone_duration_extra")
 _EXT = ("vits.noise", "vits.seed", "vits.n_timesteps", "vits.sample_rate", "vits.denoiser_strength", "vits.denoiser_filter_length",
-        "vits.marks", "vits.loudness", "vits.peak", "vits.peak_ceiling", "vits.pitch")
+        "vits.marks", "vits.loudness", "vits.peak", "vits.peak_ceiling", "vits.pitch", "vits.pitch_formants")
 
 
 class SttsSession:
@@ -104,11 +104,15 @@ class SttsSession:
 
     def _pitch(self, feed):
         """the extension feed "vits.pitch" (semitones in [-12, 12]; include/vits_pitch.h) -> the keyword for the model's calls: empty for
-        none and for a shift that reduces to the identity; a value out of range is ValueError, before any device work"""
+        none and for a shift that reduces to the identity; a value out of range is ValueError, before any device work.  The feed
+        "vits.pitch_formants" (bool) adds preserve_formants to a shift"""
         p = pitch_spec(feed.get("vits.pitch"))
         if p is None:
             return {}
         self._lib._need_pitch()
+        if feed.get("vits.pitch_formants"):  # (STTS_FLAG_PITCH_FORMANT: modifies a shift, so it is read only with one in effect)
+            self._lib._need_pitch_formant()
+            return {"pitch": p, "preserve_formants": True}
         return {"pitch": p}
 
     def normalize(self, audio, lengths, sample_rate, spec):

@@ -224,11 +224,14 @@ class Synth:
             args["vits.peak"] = float(peak)
         return True
 
-    def _pitch(self, args, pitch):
+    def _pitch(self, args, pitch, preserve_formants=None):
         """Pitch shift of the request (include/vits_pitch.h): `pitch` in semitones, [-12, 12], defaulting to the config key
         inference.pitch; it goes into the feed as "vits.pitch".  None and no config key, or a shift that reduces to the identity = off,
         the reference's behaviour.  The engine shifts the finished waveform on the device, behind the decoder and the denoiser and before
-        the resampler; duration, sample counts and marks do not change (formants move with the pitch)."""
+        the resampler; duration, sample counts and marks do not change.  Formants move with the pitch unless `preserve_formants`
+        (default: the config key inference.pitch_formants, else False) is set: then the feed gets "vits.pitch_formants" and the engine
+        keeps the spectral envelope where it was (VITS_FLAG_PITCH_FORMANT).  It modifies a shift: without one in effect the request is
+        the request it was, so a voice's config can set it for every request."""
         from .capi import pitch_spec
 
         if pitch is None:
@@ -237,6 +240,10 @@ class Synth:
         if p is None:
             return False
         args["vits.pitch"] = p
+        if preserve_formants is None:
+            preserve_formants = self.model.config.get("inference", {}).get("pitch_formants", False)
+        if preserve_formants:
+            args["vits.pitch_formants"] = True
         return True
 
     def measure_loudness(self, audio, rate=None):
@@ -286,8 +293,10 @@ class Synth:
         return build_marks(rate, np.asarray(token_ends).reshape(-1), symbols, counts, blank, word_of, word_texts)
 
     def synth_audio(self, text, speaker_id=0, noise_level=None, speech_rate=None, duration_noise_level=None, scale=None, sample_rate=None,
-                    denoiser_strength=None, marks=False, loudness=None, peak=None, peak_ceiling=None, pitch=None):
-        """pitch (extension): semitones by which the returned audio is shifted, see _pitch.
+                    denoiser_strength=None, marks=False, loudness=None, peak=None, peak_ceiling=None, pitch=None,
+                    preserve_formants=None):
+        """pitch / preserve_formants (extension): semitones by which the returned audio is shifted, and whether its formants stay where
+        they were, see _pitch.
         sample_rate: output rate in Hz (extension; default None = the voice's own rate, the reference's behaviour): the feed gets
         "vits.sample_rate" and the engine resamples on the device.  denoiser_strength: see _denoiser.
         loudness / peak / peak_ceiling (extension): a LUFS or a peak target for the returned audio, see _loudness.
@@ -296,7 +305,7 @@ class Synth:
         args, scale = self._feed(text, speaker_id, noise_level, speech_rate, duration_noise_level, scale)
         self._denoiser(args, denoiser_strength)
         self._loudness(args, loudness, peak, peak_ceiling)
-        self._pitch(args, pitch)
+        self._pitch(args, pitch, preserve_formants)
         rate = self.native_rate()
         if sample_rate and int(sample_rate) != rate:
             rate = int(sample_rate)
@@ -364,10 +373,11 @@ class Synth:
             yield self.audio_float_to_int16(chunk * scale)
 
     def synth(self, text, oname, speaker_id=0, noise_level=None, speech_rate=None, duration_noise_level=None, scale=None, sample_rate=None,
-              denoiser_strength=None, marks=False, loudness=None, peak=None, peak_ceiling=None, pitch=None):
+              denoiser_strength=None, marks=False, loudness=None, peak=None, peak_ceiling=None, pitch=None, preserve_formants=None):
         """marks=True: the utterance's marks.SpeechMarks are returned (the default returns None, as the reference does)"""
         audio = self.synth_audio(text, speaker_id, noise_level, speech_rate, duration_noise_level, scale, sample_rate, denoiser_strength, marks=marks,
-                                 loudness=loudness, peak=peak, peak_ceiling=peak_ceiling, pitch=pitch)
+                                 loudness=loudness, peak=peak, peak_ceiling=peak_ceiling, pitch=pitch,
+                                 preserve_formants=preserve_formants)
         sm = None
         if marks:
             audio, sm = audio
