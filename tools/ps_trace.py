@@ -57,6 +57,10 @@ for s in range(n):
         if kinds[s] == 5 and os.environ.get("PS_ATT_ITEMS") and s == int(os.environ["PS_ATT_ITEMS"]):
             full = st[:, s]
             print("        PV+stores by worker:", [int(full[r, 3] - full[r, 5]) if full[r, 5] > 0 else -1 for r in range(min(P, 120))])
+        if kinds[s] == 2 and a[:, 4].max() > 0:  # fused column step (stamps 2 / 4 around the matrix-vector product)
+            b = a[a[:, 4] > 0]; g2 = got[a[:, 4] > 0]
+            md = lambda x: float(np.median(x))
+            print(f"        fused DDS phases (median cycles): start->poll done {md(g2 - b[:, 0]):.0f} | column work {md(b[:, 2] - g2):.0f} | matrix-vector {md(b[:, 4] - b[:, 2]):.0f} | sum + (spline +) stores {md(b[:, 3] - b[:, 4]):.0f}")
         if a[:, 6].max() > 0:
             md = lambda x: float(np.median(x))
             print(f"        MM phases (median cycles): start->poll done {md(got - a[:, 0]):.0f} | tile+barrier {md(a[:, 2] - got):.0f} | to MFMA loop {md(a[:, 7] - a[:, 2]):.0f} | MFMA loop {md(a[:, 4] - a[:, 7]):.0f} | res poll + partial tiles + barrier {md(a[:, 6] - a[:, 4]):.0f} | epilogue + stores {md(a[:, 3] - a[:, 6]):.0f}")

@@ -22,13 +22,14 @@ struct EncoderW {
 struct DDSW {
   std::vector<float*> sw, sb, g1, b1, g2, b2;
   std::vector<float*> swk[3];  // the depthwise taps as three per-channel vectors (persistent column steps: thread = channel)
-  std::vector<float*> wt;  // 1x1 weights transposed [ci][co] for the fused layer kernel
+  std::vector<float*> wt;  // 1x1 weights transposed wt4[ci / 4][co][ci % 4]: the fused layer kernel and the fused column steps of the step program
   std::vector<ConvW> pw;
 };
 struct ConvFlowW {
   float *pre_w = nullptr, *pre_b = nullptr;
   DDSW dds;
   ConvW proj;
+  float* proj_wt = nullptr;  // proj's weight transposed like DDSW::wt (conv_wt4), null when not built
 };
 struct CouplingW {
   ConvW pre, post;
@@ -182,6 +183,7 @@ struct vits_model {
   ConvW enc_proj;
   ConvW bert_proj;  // BERT-conditioned flavour (hparams.bert_dim > 0): 1x1 projection of the "bert" feed onto the embedding
   ConvW dp_pre, dp_proj;
+  float* dp_proj_wt = nullptr;  // dp_proj's weight transposed like DDSW::wt (conv_wt4) for the fused column steps of the persistent program
   DDSW dp_dds;
   std::vector<ConvFlowW> cf;  // index k -> dp.flows.(2k+1), k = 1..n-1 (k = 0 unused)
   // deterministic DurationPredictor (hparams.dp_n_flows == 0, models.py:104-139): conv_1 / conv_2 on the conv kernels, norm_1, and
@@ -388,6 +390,20 @@ static void load_encoder(vits_model* m, EncoderW& E, const char* pfx, int n_laye
     L.g2 = upload(m, tget(m, 1, H, -1, -1, "%s.norm_layers_2.%d.gamma", pfx, i), H);
     L.b2 = upload(m, tget(m, 1, H, -1, -1, "%s.norm_layers_2.%d.beta", pfx, i), H);
   }
+}
+
+// A 1x1 conv's weight [Cout][Cin] transposed to wt4[ci / 4][co][ci % 4], the layout of DDSW::wt: the conv as a matrix-vector product of
+// one column, thread = output channel, one dwordx4 per four input channels (persist.hip.h ps_mv_request).  Only for the geometries
+// the duration predictor's step program takes (persist_sdp_eligible); null otherwise.
+static float* conv_wt4(vits_model* m, const char* name, int Cout, int Cin) {
+  const vits_hparams& hp = m->hp;
+  if (Cin % 32 || Cin > PS_MAXC || hp.dp_kernel_size != 3 || hp.dp_dds_layers < 1 || hp.dp_dds_layers > 3 || hp.dp_n_flows < 2) return nullptr;
+  const float* w = tget(m, 3, Cout, Cin, 1, "%s.weight", name);
+  if (!w || m->missing) return nullptr;
+  std::vector<float> t((size_t)Cout * Cin);
+  for (int co = 0; co < Cout; ++co)
+    for (int ci = 0; ci < Cin; ++ci) t[((size_t)(ci / 4) * Cout + co) * 4 + (ci & 3)] = w[(size_t)co * Cin + ci];
+  return upload(m, t.data(), t.size());
 }
 
 static void load_dds(vits_model* m, DDSW& D, const char* pfx, int C, int K, int n) {
@@ -652,6 +668,7 @@ static int load_model(vits_model* m) {
     // ---- duration predictor (reverse path)
     m->dp_pre = conv_from(m, "dp.pre", D, H, 1, true);
     m->dp_proj = conv_from(m, "dp.proj", D, D, 1, true);
+    m->dp_proj_wt = conv_wt4(m, "dp.proj", D, D);
     load_dds(m, m->dp_dds, "dp.convs", D, hp.dp_kernel_size, hp.dp_dds_layers);
     m->cf.resize(hp.dp_n_flows);
     const int P = 3 * hp.dp_num_bins - 1;
@@ -663,6 +680,7 @@ static int load_model(vits_model* m) {
       load_dds(m, c.dds, nm, D, hp.dp_kernel_size, hp.dp_dds_layers);
       snprintf(nm, sizeof nm, "dp.flows.%d.proj", 2 * k + 1);
       c.proj = conv_from(m, nm, P, D, 1, true);
+      c.proj_wt = conv_wt4(m, nm, P, D);
     }
     {
       const float* em = tget(m, 2, 2, 1, -1, "dp.flows.0.m");

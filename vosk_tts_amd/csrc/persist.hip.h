@@ -26,6 +26,13 @@
 //     sums, bias, residual, speaker vector), the DDSConv elementwise chain (finish the previous layer at t - d, t, t + d,
 //     depthwise conv, LN, GELU), embedding lookup, attention merge, coupling tail.  A LayerNorm is a DPP wave reduction + one LDS
 //     exchange; every element is computed once;
+//   * fused column steps (PF_MV; the duration predictor up to 64 columns at 256 channels, persist_plan.hip.h persist_sdp_split): the
+//     worker that owns a column has all its channels anyway, so the 1x1 conv that consumes the column runs in the same step as a
+//     matrix-vector product -- the 8 waves split the contraction, lane = output channel, the transposed weights of the worker's <= 64
+//     output channels in registers, partial sums added in wave order through LDS.  Up to four workers share a column: each redoes
+//     the cheap column work (nothing of it is exchanged) and owns a quarter of the output channels, so no worker streams more than
+//     64 KB of weights.  One step per DDSConv layer instead of two, dp.proj and ConvFlow.proj + the spline of ONE column behind the
+//     last finish of a stack: 17 dependent steps instead of 33, 115 -> 77 us at T = 50 (profiles/dp_fused_bench.txt);
 //   * matrix steps, one worker per (16-column tile, group of 16-row blocks, K-slice): gather the [C_in x (16 + taps - 1)] operand
 //     window (<= 40 KB), 16x16x4 fp32 MFMAs with the 8 waves splitting the contraction at tap-unit granularity, epilogue (bias /
 //     per-item bias / ReLU / mask / residual, WaveNet gate, spline inverse), cells out.  Contractions over 768 channels are split
@@ -35,9 +42,11 @@
 //   * a step is whatever records the resolver wrote for it: sequences longer than the worker count (T up to PS_MAX_T = 512 with
 //     P = 256 workers) run a column step as two rounds of P columns and an attention step as rounds of P blocks -- the kernel is
 //     the same (round 4; DESIGN.md "Programs beyond 256 columns").
-// (v1 of the duration predictor ran a whole DDSConv layer per step like conv16_kernel's PRO == 1: every one of the 16 workgroups of
-// a column tile pulled the full 256-channel x 34-column window of two tensors and redid its LayerNorms and 8 k erf evaluations:
-// 12 us per step, 208 us for the predictor against 265 us of launches.)
+// (A DDSConv layer in ONE step can be fused in two directions.  v1 of the duration predictor fused the column work into the matrix
+// step, like conv16_kernel's PRO == 1: every one of the 16 workgroups of a column tile pulled the full 256-channel x 34-column window
+// of two tensors and redid its LayerNorms and 8 k erf evaluations: 12 us per step, 208 us for the predictor against 265 us of launches.
+// The fused column steps above go the other way round -- the matrix work moves into the column step, as a matrix-vector product --
+// and recompute only what they would otherwise wait for: 4.5 us per step.)
 // Reference ops: attentions.py:48-65,133-260,292-317 (Encoder / MultiHeadAttention / FFN), models.py:56-63,93-101 (duration
 // predictor), modules.py:96-108,148-176,363-390 (DDSConv, WN, ConvFlow), models.py:374-393 (coupling layer).
 #pragma once
@@ -73,6 +82,7 @@ enum {
   PF_PLAIN_IN = 1 << 15,   // PK_MM: operand = plain floats [channels][pT]; PK_COUPLE: previous z = plain floats
   PF_DW = 1 << 16, PF_FIN_LN = 1 << 17, PF_FIN_PRE = 1 << 18,  // PK_DDS
   PF_LN = 1 << 19,         // PK_LN: normalise (else: plain sum)
+  PF_MV = 1 << 20,         // PK_DDS: the conv that consumes the column (the layer's 1x1 / the stack's projection) runs in this step
 };
 
 // One work item of one worker in one step, resolved on the host (persist_plan.hip.h): 32 dwords.
@@ -87,7 +97,12 @@ enum {
 //          b0 = n_u | nblk << 7;
 //          b1 = floats between consecutive row blocks of the weights; b2 = ypitch; b3 = rows left (Cout - first row);
 //          b4 = pT; b5 = rpitch; b6 = n0 | z_row << 16 | ea_row << 20; b7 = gate_H
-// PK_DDS   a1 = C | dil << 16; a2 = t; p0 xin, p1 y2, p2 z row, p3 xout, p4 bout
+// PK_DDS   a1 = C | dil << 16; a2 = t; p0 xin, p1 y2, p2 z row, p3 xout (null: not written), p4 bout
+//          PF_MV: p4 = output cells of the fused conv (column 0, first channel of this worker), p6 = its slice of the transposed weights
+//          (ps_mv_request), p7 = bias of its first channel; b1 = output channels of this worker (<= 64), b2 = bytes between consecutive
+//          rows of 4 input channels (16 * C_out), b3 = such rows per wave (C / 32), b5 = channel pitch of the output cells
+//          PF_MV | PF_SPLINE (dw == 0, one worker per column): the conv is ConvFlow.proj and the step ends with the inverse spline of its
+//          column: p5 = z cells [2][Tp], p2 = zout (null for the last flow), b6 = z_row << 16 | ea_row << 20, PF_LAST as in PK_MM
 // PK_LN    a1 = C; a2 = t; a3 = np; p0 part, p1 res, p2 base, p3 out, p4 oplain; b0/b1 = part stride (cells, 64 bit); b4 = pT
 // PK_EMB   a1 = C; a2 = t; p0 emb, p3 out, p4 oplain; b0 = scale (float bits); b1 = n_vocab; b4 = pT
 // PK_ATT   a1 = dk | nh << 8 | W << 16; a2 = i0 | j0 << 16; a3 = head | key tile << 8; p0 qkv, p1 ap
@@ -306,6 +321,87 @@ __device__ __forceinline__ void ps_prefetch(const ps_i4& r, int tid, int wave, i
   ps_load_weights(PR_P(const float, r, 6), PR_B(r, 0) & 0x7f, wave, lane, pre.a);
 }
 
+// Fused column steps (PF_MV): y[o] = bias[o] + sum_k W[o][k] b[k] for the <= 64 output channels o of this worker, the column b in LDS.
+// The weights are packed transposed, Wt[k / 4][o][k % 4] (engine_model.hip.h conv_wt4): lane = output channel, one dwordx4 = four
+// input channels, consecutive lanes read consecutive 16 bytes.  The 8 waves split the contraction (C / 8 input channels each, C / 32
+// dwordx4 <= PS_MAXU), so the whole slice of a worker is ONE request of <= 8 loads per lane at the top of the step.  Rows beyond the
+// wave's share repeat its last one, lanes beyond the worker's channels its last channel (L1 hits, never used).
+// (Registers of the step, not the PsPre of the step loop: nothing of a column step is carried around the loop.)
+struct PsMv { f32x4 a[PS_MAXU]; float bias; };
+__device__ __forceinline__ void ps_mv_request(const ps_i4& r, int tid, int wave, int lane, PsMv& pre) {
+  const PS_G char* base = (const PS_G char*)PR_P(const float, r, 6);
+  const int n = PR_B(r, 1), kq = PR_B(r, 3);
+  const unsigned rowb = (unsigned)PR_B(r, 2);
+  const unsigned lane_off = (unsigned)(lane < n ? lane : n - 1) * 16u;
+#pragma unroll
+  for (int i = 0; i < PS_MAXU; ++i) {
+    const unsigned ro = (unsigned)__builtin_amdgcn_readfirstlane(wave * kq + (i < kq ? i : kq - 1)) * rowb;
+    pre.a[i] = *(const PS_G f32x4*)(base + (ro + lane_off));
+  }
+  pre.bias = PR_P(const float, r, 7)[tid < n ? tid : n - 1];
+}
+// this wave's share of the contraction; b4 = the column in LDS (16-byte aligned: every lane reads the same address -- a broadcast)
+__device__ __forceinline__ float ps_mv_dot(const PsMv& pre, const float* bcol, int wave, int kq) {
+  const f32x4* b4 = reinterpret_cast<const f32x4*>(bcol) + wave * kq;
+  float acc = 0.f;
+#pragma unroll
+  for (int i = 0; i < PS_MAXU; ++i)
+    if (i < kq) {
+      const f32x4 bb = b4[i];
+      acc = fmaf(pre.a[i][0], bb[0], acc); acc = fmaf(pre.a[i][1], bb[1], acc);
+      acc = fmaf(pre.a[i][2], bb[2], acc); acc = fmaf(pre.a[i][3], bb[3], acc);
+    }
+  return acc;
+}
+
+// Inverse rational-quadratic spline of ConvFlow (transforms.py:55-177), the arithmetic of spline_inverse_elem (kernels_misc.hip.h) in
+// the two pieces both step forms use: the matrix step for the 16 columns of its tile (h and the knots at pitch 16), the fused column
+// step for its one column (pitch 1).
+// Knots: softmax over the bins, cumulative sum and knots (transforms.py:96-131) with the 16 lanes of a DPP row = the bins k of ONE
+// (column, widths / heights) pair: row maximum, row sum and the inclusive prefix are DPP row operations (no LDS, no loop).
+__device__ __forceinline__ void ps_spline_knots(const float* h, int hs, int which, int k, int nb, float isd, float bound, float* cdst, int cs) {
+  const bool kok = k < nb;
+  const float u = kok ? h[(which * nb + k) * hs] * isd : -3.0e38f;
+  const float mx = ps_row_max(u);
+  const float e = kok ? expf(u - mx) : 0.f;
+  const float sum = ps_row_sum(e);
+  const float mn = 1e-3f;  // min_bin_width == min_bin_height
+  float c = kok ? mn + (1.f - mn * nb) * (e / sum) : 0.f;
+  c += ps_row_shr<1>(c);
+  c += ps_row_shr<2>(c);
+  c += ps_row_shr<4>(c);
+  c += ps_row_shr<8>(c);
+  if (k == 0) cdst[0] = -bound;
+  if (kok) cdst[(k + 1) * cs] = k == nb - 1 ? bound : 2.f * bound * c - bound;
+}
+// One column: bin search and the quadratic.  cw / ch: its width / height knots (pitch cs), hd: its derivative parameters (pitch hs)
+__device__ __forceinline__ float ps_spline_solve(float y, const float* cw, const float* ch, int cs, const float* hd, int hs, int nb, float bound, float cst) {
+  float v1 = y;
+  if (y >= -bound && y <= bound) {  // identity outside the interval (transforms.py:65-77)
+    int bin = -1;
+    for (int k = 0; k <= nb; ++k) {
+      const float loc = ch[k * cs] + (k == nb ? 1e-6f : 0.f);
+      if (y >= loc) bin++;
+    }
+    bin = bin < 0 ? 0 : (bin > nb - 1 ? nb - 1 : bin);
+    const float in_cw = cw[bin * cs], in_w = cw[(bin + 1) * cs] - in_cw;
+    const float in_ch = ch[bin * cs], in_h = ch[(bin + 1) * cs] - in_ch;
+    const float min_d = 1e-3f;
+    const float ud0 = (bin == 0) ? cst : hd[(bin - 1) * hs];
+    const float ud1 = (bin == nb - 1) ? cst : hd[bin * hs];
+    const float d0 = min_d + softplus_f(ud0), d1 = min_d + softplus_f(ud1);
+    const float delta = in_h / in_w;
+    const float t1 = (y - in_ch) * (d0 + d1 - 2.f * delta);
+    const float qa = t1 + in_h * (delta - d0);
+    const float qb = in_h * d0 - t1;
+    const float qc = -delta * (y - in_ch);
+    const float disc = qb * qb - 4.f * qa * qc;
+    const float root = (2.f * qc) / (-qb - sqrtf(disc));
+    v1 = root * in_w + in_cw;
+  }
+  return v1;
+}
+
 // Placed where a poll has just completed: the record of step s + 1 (requested at the top of this step, older than every poll load) is
 // certainly there -- touching it HERE makes the compiler account for its wait at a point where it costs nothing.  Without this the
 // hand-over rv = rvB at the loop's back edge is the first use, and because loads and stores share the in-order vmcnt counter the
@@ -329,7 +425,7 @@ __global__ void __launch_bounds__(PS_THREADS) persist_kernel(const PProgram* __r
   __shared__ __attribute__((aligned(16))) float tile[PS_LDS_TILE];      // MFMA operand window [C_in][16 + taps - 1] (pitch 21) / attention tiles
   __shared__ __attribute__((aligned(16))) float mred[PS_LDS_MRED];      // partial tiles of the 8 waves / attention scores
   __shared__ float hb[32 * 16];            // ConvFlow.proj output of the tile (spline parameters)
-  __shared__ float xs[3 * PS_MAXC];        // column steps: x_in at t - d, t, t + d
+  __shared__ __attribute__((aligned(16))) float xs[3 * PS_MAXC];  // column steps: x_in at t - d, t, t + d; fused steps: the conv's operand column
   __shared__ float red[4 * 16];            // block reductions (one 16-float scratch per call site)
   __shared__ __attribute__((aligned(16))) float att_r[PS_WAVES * 256];  // attention blocks: partial q E_k^T tiles of the 8 waves
   __shared__ float att_p[16 * 17];         // attention blocks: probabilities [query][key], pitch 17 (conflict-free MFMA A reads)
@@ -424,11 +520,31 @@ __global__ void __launch_bounds__(PS_THREADS) persist_kernel(const PProgram* __r
       PS_G ll_t* bout = PR_P(ll_t, rv, 4);
       const int c = (wave & 3) * 64 + lane, h = wave >> 2;  // (== tid & 255, tid >> 8; the half is wave-uniform: scalar conditions)
       const bool cok = c < D;
+      // The conv fused into this step (PF_MV): its weights are requested here, in front of the poll, as the matrix steps do.  (Loads
+      // return in order, so the 64 KB of a worker hold the poll's answer back by ~1 k cycles -- tools/ps_trace.py: poll done after 3.1 k
+      // instead of 2.1 k cycles.  Requested behind the poll instead, under the column work, the step was 1 k cycles LONGER: c2 0.817
+      // against 0.801 ms.  Steps without a fused conv request nothing: straight-line loads of zeros cost them the same 1 k cycles.)
+      const bool mv = (kf & PF_MV) != 0;
+      const int mv_n = PR_B(rv, 1), mv_kq = PR_B(rv, 3);
+      PsMv mvw;
+#pragma unroll
+      for (int i = 0; i < PS_MAXU; ++i) mvw.a[i] = f32x4{0.f, 0.f, 0.f, 0.f};
+      mvw.bias = 0.f;
+      if (mv) ps_mv_request(rv, tid, wave, lane, mvw);
       {
         if (t >= L) {  // padding column (worker-uniform): zeros, nothing to wait for
           if (h == 1 && cok) {
-            ll_store(xout + (long long)t * D + c, 0.f, epoch);
-            if (dw) ll_store(bout + (long long)t * D + c, 0.f, epoch);
+            if (xout) ll_store(xout + (long long)t * D + c, 0.f, epoch);
+            if (dw && !mv) ll_store(bout + (long long)t * D + c, 0.f, epoch);
+          }
+          if (mv && !(kf & PF_SPLINE) && tid < mv_n) ll_store(bout + (long long)t * PR_B(rv, 5) + tid, 0.f, epoch);
+          if ((kf & PF_SPLINE) && tid == 0) {  // z of a padding column is zero, and so is logw
+            PS_G ll_t* zout = PR_P(ll_t, rv, 2);
+            if (zout) { ll_store(zout + t, 0.f, epoch); ll_store(zout + Tp + t, 0.f, epoch); }
+            if ((kf & PF_LAST) && t < T) {
+              ((PS_G float*)prog->logw)[t] = 0.f;
+              if (prog->logw_cells) ll_store((PS_G ll_t*)prog->logw_cells + t, 0.f, epoch);
+            }
           }
           PS_STAMP(3);
           continue;
@@ -438,12 +554,18 @@ __global__ void __launch_bounds__(PS_THREADS) persist_kernel(const PProgram* __r
         const bool n0 = cok && (h ? true : (dw && t0 >= 0)), n1 = cok && !h && dw && t1 < L;
         const int tc0 = t0 < 0 ? 0 : t0, tc1 = t1 < Tp ? t1 : Tp - 1;
         float x0 = 0.f, y0 = 0.f, z0 = 0.f, x1 = 0.f, y1 = 0.f, z1 = 0.f;
+        // fused spline: z of this column (cells of a much older step) comes with the same poll, every thread reads the two cells
+        const PS_G ll_t* zs = (kf & PF_SPLINE) ? PR_P(const ll_t, rv, 5) : nullptr;
+        const int x0r = (PR_B(rv, 6) >> 16) & 1;
+        float zs0 = 0.f, zs1 = 0.f;
         {
           unsigned o0 = (unsigned)(tc0 * D + c) * 8u, o1 = (unsigned)(tc1 * D + c) * 8u, oz0 = (unsigned)tc0 * 8u, oz1 = (unsigned)tc1 * 8u;
+          unsigned os0 = (unsigned)(x0r * Tp + t) * 8u, os1 = (unsigned)((1 - x0r) * Tp + t) * 8u;
           bool pending;
           do {
-            asm volatile("" : "+v"(o0), "+v"(o1), "+v"(oz0), "+v"(oz1));  // (addresses stay inside the loop body: no hoisted 64-bit pairs)
-            ll_t qx0 = 0, qy0 = 0, qz0 = 0, qx1 = 0, qy1 = 0, qz1 = 0;
+            asm volatile("" : "+v"(o0), "+v"(o1), "+v"(oz0), "+v"(oz1), "+v"(os0), "+v"(os1));  // (addresses stay inside the loop body: no hoisted 64-bit pairs)
+            ll_t qx0 = 0, qy0 = 0, qz0 = 0, qx1 = 0, qy1 = 0, qz1 = 0, qs0 = 0, qs1 = 0;
+            if (zs) { qs0 = ll_load_off(zs, os0); qs1 = ll_load_off(zs, os1); }
             if (n0) {
               qx0 = ll_load_off(xin, o0);
               if (y2) qy0 = ll_load_off(y2, o0);
@@ -457,7 +579,9 @@ __global__ void __launch_bounds__(PS_THREADS) persist_kernel(const PProgram* __r
             unsigned bad = 0;
             if (n0) bad |= ll_bad(qx0, epoch) | (y2 ? ll_bad(qy0, epoch) : 0u) | (zc ? ll_bad(qz0, epoch) : 0u);
             if (n1) bad |= ll_bad(qx1, epoch) | (y2 ? ll_bad(qy1, epoch) : 0u) | (zc ? ll_bad(qz1, epoch) : 0u);
+            if (zs) bad |= ll_bad(qs0, epoch) | ll_bad(qs1, epoch);
             x0 = ll_val(qx0); y0 = ll_val(qy0); z0 = ll_val(qz0); x1 = ll_val(qx1); y1 = ll_val(qy1); z1 = ll_val(qz1);
+            zs0 = ll_val(qs0); zs1 = ll_val(qs1);
             pending = PS_PENDING(bad);
           } while (ps_again(cx, pending));
         }
@@ -477,7 +601,7 @@ __global__ void __launch_bounds__(PS_THREADS) persist_kernel(const PProgram* __r
         // x = (x + y) * mask: columns outside [0, L) are zero (never polled)
         const float xi0 = (n0 && t0 < L) ? x0 : 0.f, xi1 = n1 ? x1 : 0.f;
         if (cok) {
-          if (h) { xs[PS_MAXC + c] = xi0; ll_store(xout + (long long)t * D + c, xi0, epoch); }
+          if (h) { xs[PS_MAXC + c] = xi0; if (xout) ll_store(xout + (long long)t * D + c, xi0, epoch); }
           else { xs[c] = xi0; xs[2 * PS_MAXC + c] = xi1; }
         }
         if (dw) {
@@ -492,7 +616,49 @@ __global__ void __launch_bounds__(PS_THREADS) persist_kernel(const PProgram* __r
           const float e = v - m;
           float q = (cok && h) ? e * e : 0.f;
           ps_half_sum2(q, dummy, red + 48, wave, lane);
-          if (cok && h) ll_store(bout + (long long)t * D + c, PS_GELU(e * (1.0f / sqrtf(q * invD + 1e-5f)) * par[6] + par[7]), epoch);
+          const float bv = PS_GELU(e * (1.0f / sqrtf(q * invD + 1e-5f)) * par[6] + par[7]);
+          // (fused: into xs[0 .. D) -- the depthwise conv's reads of xs lie in front of the two barriers of the reductions above)
+          if (cok && h) { if (mv) xs[c] = bv; else ll_store(bout + (long long)t * D + c, bv, epoch); }
+        }
+        if (mv) {
+          // the 1x1 conv of this layer on b = gelu(LN1(.)), or the stack's projection on the finished column (dw == 0: xs[PS_MAXC ..]),
+          // for this worker's output channels: the waves split the contraction, the partial sums meet in LDS and are added in wave
+          // order (two forwards are bit-identical, and so are the workers that share a column)
+          __syncthreads();
+          PS_STAMP(2);
+          mred[wave * 64 + lane] = ps_mv_dot(mvw, dw ? xs : xs + PS_MAXC, wave, mv_kq);
+          __syncthreads();
+          PS_STAMP(4);
+          if (tid < mv_n) {
+            float v = mvw.bias;
+#pragma unroll
+            for (int w = 0; w < PS_WAVES; ++w) v += mred[w * 64 + tid];
+            if (kf & PF_SPLINE) hb[tid] = v;  // spline parameters of this column: [widths | heights | derivatives]
+            else ll_store(bout + (long long)t * PR_B(rv, 5) + tid, v, epoch);
+          }
+          if (kf & PF_SPLINE) {
+            // the inverse spline of this column on z[1 - z_row]: knots in the two DPP rows (widths, heights) of wave 0, then one lane
+            const int nb = prog->nb;
+            const float bound = prog->bound, isd = prog->inv_sqrt_d;
+            float* sc = mred + PS_WAVES * 64;  // [2][17] knots (behind the partial sums)
+            __syncthreads();
+            if (wave == 0 && lane < 32) ps_spline_knots(hb, 1, lane >> 4, lane & 15, nb, isd, bound, sc + (lane >> 4) * 17, 1);
+            __syncthreads();
+            if (tid == 0) {
+              const int x1r = 1 - x0r, ea_row = (PR_B(rv, 6) >> 20) & 1;
+              PS_G ll_t* zout = PR_P(ll_t, rv, 2);
+              const float v0 = zs0, v1 = ps_spline_solve(zs1, sc, sc + 17, 1, hb + 2 * nb, 1, nb, bound, spline_cst);
+              if (zout) {
+                ll_store(zout + (long long)x0r * Tp + t, v0, epoch);
+                ll_store(zout + (long long)x1r * Tp + t, v1, epoch);
+              }
+              if (kf & PF_LAST) {  // (t < L <= T)
+                const float lw = ((ea_row == x0r ? v0 : v1) - ea_m) * ea_is;
+                ((PS_G float*)prog->logw)[t] = lw;
+                if (prog->logw_cells) ll_store((PS_G ll_t*)prog->logw_cells + t, lw, epoch);
+              }
+            }
+          }
         }
       }
       PS_STAMP(3);
@@ -1190,25 +1356,11 @@ __global__ void __launch_bounds__(PS_THREADS) persist_kernel(const PProgram* __r
         const float bound = prog->bound, isd = prog->inv_sqrt_d;
         float* sc = mred;  // [2][17][16] cumulative widths / heights (knots)
         {
-          // softmax over the bins, cumulative sum and knots (transforms.py:96-131) with the 16 lanes of a DPP row = the bins of ONE
-          // column: thread = (which = wave >> 2: widths / heights, column = 4 (wave & 3) + (lane >> 4), bin k = lane & 15).  Row
-          // maximum, row sum and the inclusive prefix are DPP row operations (no LDS, no loop): the serial form this replaces (32
-          // threads walking the bins: two dependent LDS reads per bin, then a 16-thread bin search) took 11 k cycles per spline step.
+          // thread = (which = wave >> 2: widths / heights, column = 4 (wave & 3) + (lane >> 4), bin k = lane & 15): the serial form
+          // this replaces (32 threads walking the bins: two dependent LDS reads per bin, then a 16-thread bin search) took 11 k cycles
+          // per spline step
           const int which = wave >> 2, col = 4 * (wave & 3) + (lane >> 4), k = lane & 15;
-          const bool kok = k < nb;
-          const float u = kok ? hb[(which * nb + k) * 16 + col] * isd : -3.0e38f;
-          const float mx = ps_row_max(u);
-          const float e = kok ? expf(u - mx) : 0.f;
-          const float sum = ps_row_sum(e);
-          const float mn = 1e-3f;  // min_bin_width == min_bin_height
-          float c = kok ? mn + (1.f - mn * nb) * (e / sum) : 0.f;
-          c += ps_row_shr<1>(c);
-          c += ps_row_shr<2>(c);
-          c += ps_row_shr<4>(c);
-          c += ps_row_shr<8>(c);
-          float* cdst = sc + which * 17 * 16 + col;
-          if (k == 0) cdst[0] = -bound;
-          if (kok) cdst[(k + 1) * 16] = k == nb - 1 ? bound : 2.f * bound * c - bound;
+          ps_spline_knots(hb + col, 16, which, k, nb, isd, bound, sc + which * 17 * 16 + col, 16);
         }
         __syncthreads();
         if (wave == 0) {  // one column per lane (lanes >= 16 ride along in the wave-uniform poll)
@@ -1232,33 +1384,7 @@ __global__ void __launch_bounds__(PS_THREADS) persist_kernel(const PProgram* __r
             float v0 = 0.f, v1 = 0.f;
             if (t < L) {
               v0 = z0;
-              v1 = z1;
-              const float y = z1;
-              if (y >= -bound && y <= bound) {  // identity outside the interval (transforms.py:65-77)
-                const float* cw = sc + col;
-                const float* ch = sc + 17 * 16 + col;
-                int bin = -1;
-                for (int k = 0; k <= nb; ++k) {
-                  const float loc = ch[k * 16] + (k == nb ? 1e-6f : 0.f);
-                  if (y >= loc) bin++;
-                }
-                bin = bin < 0 ? 0 : (bin > nb - 1 ? nb - 1 : bin);
-                const float in_cw = cw[bin * 16], in_w = cw[(bin + 1) * 16] - in_cw;
-                const float in_ch = ch[bin * 16], in_h = ch[(bin + 1) * 16] - in_ch;
-                const float min_d = 1e-3f;
-                const float cst = spline_cst;
-                const float ud0 = (bin == 0) ? cst : hb[(2 * nb + bin - 1) * 16 + col];
-                const float ud1 = (bin == nb - 1) ? cst : hb[(2 * nb + bin) * 16 + col];
-                const float d0 = min_d + softplus_f(ud0), d1 = min_d + softplus_f(ud1);
-                const float delta = in_h / in_w;
-                const float t1 = (y - in_ch) * (d0 + d1 - 2.f * delta);
-                const float qa = t1 + in_h * (delta - d0);
-                const float qb = in_h * d0 - t1;
-                const float qc = -delta * (y - in_ch);
-                const float disc = qb * qb - 4.f * qa * qc;
-                const float root = (2.f * qc) / (-qb - sqrtf(disc));
-                v1 = root * in_w + in_cw;
-              }
+              v1 = ps_spline_solve(z1, sc + col, sc + 17 * 16 + col, 16, hb + 2 * nb * 16 + col, 16, nb, bound, spline_cst);
             }
             if (zout) {
               ll_store(zout + (long long)x0r * Tp + t, v0, epoch);

@@ -1,6 +1,8 @@
 // persist_plan.hip.h — host side of the persistent step programs (persist.hip.h): eligibility, the size of the exchange buffers,
 // the program builders for the three single-utterance stages (text encoder, stochastic duration predictor, flow) and the launch.
 // Included by engine.hip after the model / session types.  Programs are rebuilt at every re-plan of a session (outside any capture).
+// The duration predictor has two forms (seg_sdp): column step + matrix step per DDSConv layer, or -- where the workers are there,
+// persist_sdp_split -- one fused column step per layer and per stack end.
 #pragma once
 
 #define PERSIST_SDP 1
@@ -52,7 +54,7 @@ static bool persist_sdp_eligible(const vits_model* m, int B, int Tx) {
   if (D % 32 || D > PS_MAXC || H % 16 || H > PS_MAXC || hp.dp_kernel_size != 3) return false;
   const int nl = (int)m->dp_dds.pw.size();
   if (nl < 1 || nl > 3 || hp.dp_n_flows < 2 || hp.dp_num_bins > 16 || 3 * hp.dp_num_bins - 1 > 32) return false;
-  if (1 + 2 * (nl + 1) * hp.dp_n_flows > PS_MAX_STEPS) return false;
+  if (1 + 2 * (nl + 1) * hp.dp_n_flows > PS_MAX_STEPS) return false;  // (the two-step form; the fused one has nl + 1 or nl + 2 steps per stack)
   if (!persist_conv_ok(m->dp_pre) || !persist_conv_ok(m->dp_proj) || (int)m->dp_dds.swk[0].size() != nl) return false;
   for (const ConvW& c : m->dp_dds.pw) if (!persist_conv_ok(c)) return false;
   for (int k = 1; k < hp.dp_n_flows; ++k) {
@@ -61,13 +63,32 @@ static bool persist_sdp_eligible(const vits_model* m, int B, int Tx) {
   }
   return true;
 }
+// Fused form of a DDSConv stack (seg_sdp): workers per column of its column steps, 0 = the two-step form.
+// A column step that also runs the conv behind it keeps its slice of the transposed weights in registers (persist.hip.h
+// ps_mv_request: <= 64 output channels per worker), so it needs ceil(D / 64) workers per column; up to 4 are used where the workers are
+// there (T <= 64 at P = 256).  Sequences with fewer spare workers stay on the two-step form, whose matrix step shares one pass over the
+// weights among the 16 columns of a tile.  Measured (profiles/dp_fused_bench.txt): fused against two-step form at 16 / 50 / 64 tokens.
+static int persist_sdp_split(const vits_model* m, int Tx) {
+  const int D = m->hp.dp_filter_channels, Tp = cdiv(Tx, 16) * 16;
+  if (!m->dp_proj_wt || m->dp_dds.wt.size() != m->dp_dds.pw.size() || 3 * m->hp.dp_num_bins - 1 > 64) return 0;
+  for (float* w : m->dp_dds.wt) if (!w) return 0;
+  for (int k = 1; k < m->hp.dp_n_flows; ++k) {
+    if (!m->cf[k].proj_wt) return 0;
+    if (m->cf[k].dds.wt.size() != m->cf[k].dds.pw.size()) return 0;
+    for (float* w : m->cf[k].dds.wt) if (!w) return 0;
+  }
+  const int split = std::min(4, m->n_cu / Tp);
+  return (split >= 1 && cdiv(D, split) <= 64) ? split : 0;
+}
 static size_t persist_sdp_cells(const vits_model* m, int B, int Tx) {
   if (!persist_sdp_eligible(m, B, Tx)) return 0;
   const vits_hparams& hp = m->hp;
   const size_t Tp = (size_t)cdiv(Tx, 16) * 16, D = hp.dp_filter_channels, nl = m->dp_dds.pw.size(), nf = hp.dp_n_flows;
   // x0 (dp.pre); per DDSConv stack: per layer the finished input, the 1x1 operand and the 1x1 output, the last finish, and the
-  // proj output (dc; the ConvFlow projections stay in LDS); z after init and after every flow
-  return Tp * (D * (1 + nf * (3 * nl + 2)) + 2 * (nf + 1));
+  // proj output (dc; the ConvFlow projections stay in LDS); z after init and after every flow.
+  // Fused form: per layer the finished input and the 1x1 output (the operand stays in LDS), per stack dc / the last finish.
+  const size_t per_stack = persist_sdp_split(m, Tx) ? 2 * nl + 1 : 3 * nl + 2;
+  return Tp * (D * (1 + nf * per_stack) + 2 * (nf + 1));
 }
 
 // ---- one attentions.Encoder layer: qkv, attention partials, merged attention, y1, x1, FFN hidden, FFN partials, output
@@ -161,8 +182,12 @@ struct PStep {
   //         b    = gelu(LN(depthwise3(x_in; par3..5, par2, dil); par6, par7))          (dw != 0)
   int dil, dw, fin;
   const ll_t* xin; const ll_t* y2;   // [Tp][C]
-  ll_t* xout;              // x_in column
-  ll_t* bout;              // b column (dw != 0)
+  ll_t* xout;              // x_in column (null: nobody reads it)
+  ll_t* bout;              // b column (dw != 0); fused form: the output of the conv that consumes b (dw != 0) / x_in (dw == 0), [Tp][mv_cout]
+  // fused form (mv_split > 0): mv_split workers per column, each with cdiv(mv_cout, mv_split) <= 64 output channels of the 1x1 conv
+  // mv_wt (transposed, engine_model.hip.h conv_wt4; C input channels) + mv_bias; all of them redo the column work, the first writes xout
+  int mv_split, mv_cout;
+  const float* mv_wt; const float* mv_bias;
   // PK_LN: v = par2 (bias) + sum_{k < np} part[k][t][c] + res[t][c] ; out = (LN(v; par0, par1) + vec + base[t][c]) * mask
   int np, ln;
   const ll_t* part; long long part_stride;   // cells [np][Tp][C]
@@ -489,9 +514,14 @@ static void persist_resolve(vits_session* s, const std::vector<PStep>& steps, in
         pack = persist_pack(s, st.par, st.padd, st.plen, 256);
         if (!pack) { bad = true; return; }
       }
-      for (int t = 0; t < Tp; ++t) {
-        if (t % P == 0) R = new_step();  // (a round of P columns per step)
-        PRec& r = R[t % P];
+      // fused DDSConv steps: mv_split workers per column, worker = column * mv_split + part -- with 2 or 4 parts the workers that stream
+      // the same slice of the weights sit on the same XCDs (block b runs on XCD b % 8).  One round only (seg_sdp).
+      const int sp = (st.kind == PK_DDS && st.mv_split > 0) ? st.mv_split : 1;
+      if (sp > 1 && Tp * sp > P) { bad = true; return; }
+      for (int item = 0; item < Tp * sp; ++item) {
+        const int t = item / sp, part = item % sp;
+        if (item % P == 0) R = new_step();  // (a round of P columns per step)
+        PRec& r = R[item % P];
         r.a1 = st.C; r.a2 = t; r.p[9] = U(pack);
         r.p[3] = U(st.out); r.p[4] = U(st.oplain);
         r.b[4] = st.plain_T;
@@ -499,6 +529,23 @@ static void persist_resolve(vits_session* s, const std::vector<PStep>& steps, in
           r.kf = PK_DDS | (st.dw ? PF_DW : 0) | (st.fin == 1 ? PF_FIN_LN : 0) | (st.fin == 2 ? PF_FIN_PRE : 0);
           r.a1 = st.C | (st.dil << 16);
           r.p[0] = U(st.xin); r.p[1] = U(st.y2); r.p[2] = st.z ? U(st.z + (size_t)st.z_row * Tp) : 0; r.p[3] = U(st.xout); r.p[4] = U(st.bout);
+          r.b[1] = 1; r.b[3] = 1;
+          if (st.mv_split > 0) {
+            const int per = cdiv(st.mv_cout, sp), o0 = part * per, n = std::min(per, st.mv_cout - o0);
+            if (n < 1 || per > 64 || st.C % 32 || st.C / 32 > PS_MAXU) { bad = true; return; }
+            r.kf |= PF_MV;
+            if (part > 0) r.p[3] = 0;
+            r.p[4] = U(st.bout + o0);
+            r.p[6] = U(st.mv_wt + (size_t)o0 * 4);
+            r.p[7] = U(st.mv_bias ? st.mv_bias + o0 : m->zeros);
+            r.b[1] = n; r.b[2] = st.mv_cout * 16; r.b[3] = st.C / 32; r.b[5] = st.mv_cout;
+            if (st.epi == PS_EPI_SPLINE) {  // ConvFlow.proj + the spline of the column: one worker, all rows
+              if (sp != 1 || st.dw) { bad = true; return; }
+              r.kf |= PF_SPLINE | (st.last ? PF_LAST : 0);
+              r.p[2] = U(st.zout); r.p[4] = 0; r.p[5] = U(st.z);
+              r.b[6] = (st.z_row << 16) | (st.ea_row << 20);
+            }
+          }
         } else if (st.kind == PK_LN) {
           r.kf = PK_LN | (st.ln ? PF_LN : 0);
           r.a3 = st.np;
@@ -641,11 +688,16 @@ static void seg_sdp(vits_session* s, PBuild& b, const ll_t* x_cells) {
   const ll_t* z = steps[first].zout;
   // one DDSConv stack + the 1x1 conv that consumes it (modules.py:96-108): per layer a column step (finish the previous layer,
   // depthwise conv, LN1, GELU) and a matrix step (the layer's 1x1 conv); then the last finish and the projection
-  auto stack = [&](const DDSW& Wd, const ConvW& proj, bool spline, const ll_t* xin, const ll_t* zc, int z_row, const float* pw, const float* pb) -> PStep& {
+  // Fused form (split > 0, persist_sdp_split): the worker that owns a column has all its channels anyway, so it runs the layer's 1x1 conv
+  // on its column right behind the GELU -- one step per layer, no exchange and no matrix step between LN1 and the conv -- and the last
+  // finish runs the stack's projection the same way: dp.proj, or ConvFlow.proj followed by the inverse spline of that one column.
+  const int split = persist_sdp_split(m, b.T);
+  auto stack = [&](const DDSW& Wd, const ConvW& proj, const float* proj_wt, bool spline, const ll_t* xin, const ll_t* zc, int z_row, const float* pw, const float* pb) -> PStep& {
     const ll_t* y2 = nullptr;
     int dil = 1;
     for (int i = 0; i <= nl; ++i) {
       const bool fin = i == nl;
+      const bool fused = split > 0;
       st = b.blank(PK_DDS);
       st.C = D; st.plen = D; st.dw = fin ? 0 : 1; st.dil = fin ? 0 : dil;
       st.xin = xin; st.y2 = y2;
@@ -656,8 +708,23 @@ static void seg_sdp(vits_session* s, PBuild& b, const ll_t* x_cells) {
         st.par[6] = Wd.g1[i]; st.par[7] = Wd.b1[i];
         st.bout = b.take_rows(D);
       }
-      st.xout = b.take_rows(D);
       b.flops += 2.0 * b.T * (double)D * (fin ? 0 : K);
+      if (fused) {
+        const ConvW& cv = fin ? proj : Wd.pw[i];
+        st.mv_split = split; st.mv_cout = cv.M; st.mv_wt = fin ? proj_wt : Wd.wt[i]; st.mv_bias = cv.bias;
+        b.flops += 2.0 * b.T * (double)cv.M * D;
+        if (fin && spline) {  // the projection's rows stay in LDS: the step ends with the spline of its column (the caller sets z / zout)
+          st.bout = nullptr; st.mv_split = 1; st.epi = PS_EPI_SPLINE;
+          return b.push(st);
+        }
+        if (fin) { st.bout = b.take_rows(D); return b.push(st); }  // = proj(x) * x_mask (models.py:63): padding columns are written as zeros
+        st.xout = b.take_rows(D);
+        const PStep& col = b.push(st);
+        xin = col.xout; y2 = col.bout;
+        dil *= K;
+        continue;
+      }
+      st.xout = b.take_rows(D);
       const PStep& col = b.push(st);
       xin = col.xout;
       st = b.mm(fin ? proj : Wd.pw[i], fin ? col.xout : col.bout, D);
@@ -673,15 +740,15 @@ static void seg_sdp(vits_session* s, PBuild& b, const ll_t* x_cells) {
     return steps[first];  // not reached
   };
   {
-    PStep& pj = stack(m->dp_dds, m->dp_proj, false, x, nullptr, 0, nullptr, nullptr);
-    pj.yout = b.take_rows(D);
+    PStep& pj = stack(m->dp_dds, m->dp_proj, m->dp_proj_wt, false, x, nullptr, 0, nullptr, nullptr);
+    if (pj.kind == PK_MM) pj.yout = b.take_rows(D);
   }
-  const ll_t* dc = steps.back().yout;
+  const ll_t* dc = steps.back().kind == PK_MM ? steps.back().yout : steps.back().bout;
   int swap = 0;
   for (int k = hp.dp_n_flows - 1; k >= 1; --k) {
     swap ^= 1;  // Flip (modules.py:270-277) is a row relabel on the 2-channel z
     const ConvFlowW& c = m->cf[k];
-    PStep& pj = stack(c.dds, c.proj, true, dc, z, swap, c.pre_w, c.pre_b);
+    PStep& pj = stack(c.dds, c.proj, c.proj_wt, true, dc, z, swap, c.pre_w, c.pre_b);
     pj.z = z; pj.z_row = swap;
     if (k > 1) { pj.zout = b.take_rows(2); z = pj.zout; }
     else { pj.last = 1; pj.ea_row = swap ^ 1; }
