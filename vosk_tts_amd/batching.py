@@ -160,7 +160,7 @@ class MultiDeviceSynth:
 
     def synth_batch(self, texts, speaker_ids=0, noise_level=None, speech_rate=None, duration_noise_level=None, scale=None, seeds=None,
                     sample_rate=None, denoiser_strength=None, marks=False, loudness=None, peak=None, peak_ceiling=None, pitch=None,
-                    preserve_formants=None):
+                    preserve_formants=None, limit=None, limit_lookahead_ms=None, limit_release_ms=None):
         """texts: list of str -> list of int16 PCM arrays (22.05 kHz), one per request, in request order.  marks=True: a list of
         (audio, marks.SpeechMarks) per request instead (as Synth.synth_audio(..., marks=True)), through every shard path.  `seeds`: optional
         per-request noise seeds (default: a running counter), `speaker_ids`: one id or one per request.  `sample_rate`: output rate
@@ -168,10 +168,13 @@ class MultiDeviceSynth:
         denoiser of a multistream voice for the whole batch (default: the voice's inference.denoiser_strength, else off; as
         Synth.synth_audio, a VITS-family voice raises ValueError), every item denoised from its own length before any resampling.
         `loudness` / `peak` / `peak_ceiling`: a LUFS or a peak target for every request of the batch (defaults and rules of
-        Synth.synth_audio): each request is measured and normalised on its own, so it equals its single call with the same seed."""
+        Synth.synth_audio): each request is measured and normalised on its own, so it equals its single call with the same seed.
+        `limit` / `limit_lookahead_ms` / `limit_release_ms`: the look-ahead peak limiter (include/vits_limit.h), one setting per call and a
+        gain per request; `peak_ceiling` is then the limiter's ceiling."""
         s0 = self.synths[0]
         loud = {}
         s0._loudness(loud, loudness, peak, peak_ceiling)
+        s0._limit(loud, limit, peak_ceiling, limit_lookahead_ms, limit_release_ms)
         # "vits.pitch" (and "vits.pitch_formants"): one shift for the whole batch, travelling with the loudness feeds; include/vits_pitch.h
         s0._pitch(loud, pitch, preserve_formants)
         dn = {}
@@ -278,15 +281,16 @@ class MultiDeviceSynth:
         """stts_synthesize_batch of one padded part -> (audio, lengths, token_ends or None) at `sample_rate`; with marks the call takes
         the rate itself (stts_synthesize_batch_marks).  loud: the loudness feeds; every item is normalised last, behind the resampler"""
         spec = sess._loudness(loud or {})
+        lim = sess._limit(loud or {})
         kw = dict(kw, **sess._pitch(loud or {}))
         if marks:
-            return sess._model.synthesize_batch(*args, marks=True, sample_rate=sess._rate(sample_rate), loudness=spec, **kw)
+            return sess._model.synthesize_batch(*args, marks=True, sample_rate=sess._rate(sample_rate), loudness=spec, limit=lim, **kw)
         rate = sess._rate(sample_rate)
-        audio, ol = sess._model.synthesize_batch(*args, loudness=None if rate else spec, **kw)
+        audio, ol = sess._model.synthesize_batch(*args, loudness=None if rate else spec, limit=None if rate else lim, **kw)
         if not rate:
             return audio, ol, None
         audio, ol = sess.resample(audio, ol, rate)
-        return sess.normalize(audio, ol, rate, spec), ol, None
+        return sess.normalize(audio, ol, rate, spec, lim), ol, None
 
     def _run_shard_multistream(self, r, texts, idx, sids, scales, scale, seeds, per_request=False, sample_rate=None, denoiser_strength=None,
                                marks=False, loud=None):

@@ -48,6 +48,11 @@ FLAG_LOUDNESS = 2       # VITS_FLAG_LOUDNESS
 LOUDNESS_LUFS = 1       # VITS_LOUDNESS_LUFS
 LOUDNESS_PEAK = 2       # VITS_LOUDNESS_PEAK
 LOUDNESS_MIN_RATE = 4000
+# include/vits_limit.h
+LIMIT_SAMPLE = 1        # VITS_LIMIT_SAMPLE
+LIMIT_TRUE = 2          # VITS_LIMIT_TRUE
+LIMIT_TILE = 2048
+LIMIT_MAX_LOOKAHEAD = 1024
 
 
 def loudness_spec(loudness=None, peak=None, peak_ceiling=None):
@@ -120,6 +125,55 @@ def pitch_spec(pitch=None):
         return None
     P, Q = pitch_ratio(pitch)
     return None if P == Q else float(pitch)
+
+
+# include/vits_limit.h
+FLAG_LIMIT = 16         # VITS_FLAG_LIMIT
+LIMIT_MODES = {"sample": LIMIT_SAMPLE, "true": LIMIT_TRUE}
+LIMIT_FIELDS = [("limit_mode", ctypes.c_int32), ("limit_ceiling", ctypes.c_float), ("limit_lookahead_ms", ctypes.c_float),
+                ("limit_release_ms", ctypes.c_float), ("limit_gain", ctypes.c_float), ("out_reduction", c_f32p)]
+
+
+class SynthLimitOpts(SynthPitchOpts):
+    """mirror of `struct vits_synth_opts_limit` (include/vits_limit.h): SynthPitchOpts followed by the six limiter fields, which the
+    library reads only under VITS_FLAG_LIMIT (the loudness and pitch fields inside still only under their own flags)"""
+
+    _fields_ = LIMIT_FIELDS
+
+
+def limit_spec(limit=None, ceiling=None, lookahead_ms=5.0, release_ms=50.0, gain=1.0):
+    """The limiter a call asks for -> None (none) or (mode, ceiling, lookahead_ms, release_ms, gain) as vits_synth_opts_limit carries it.
+    limit: None, "sample" (sample peaks) or "true" (4x oversampled peaks); ceiling in (0, 1] (default 1.0); gain: the pre-gain of a call
+    without a loudness target.  A value out of range is a ValueError naming it (the library refuses the same values, VITS_ERR_ARG: here
+    they are refused before any device work)."""
+    if limit is None:
+        return None
+    if limit not in LIMIT_MODES:
+        raise ValueError(f"limit={limit!r}: None, 'sample' or 'true'")
+    c, la, rel, g = 1.0 if ceiling is None else float(ceiling), float(lookahead_ms), float(release_ms), float(gain)
+    if not 0.0 < c <= 1.0:
+        raise ValueError(f"limiter ceiling {c} outside (0, 1]")
+    if not 0.0 < la <= 10.0:
+        raise ValueError(f"limit_lookahead_ms {la} outside (0, 10]")
+    if not 1.0 <= rel <= 1000.0:
+        raise ValueError(f"limit_release_ms {rel} outside [1, 1000]")
+    if not 0.0 <= g <= 64.0:
+        raise ValueError(f"limiter gain {g} outside [0, 64]")
+    return (LIMIT_MODES[limit], c, la, rel, g)
+
+
+def set_limit(opts, keep, spec, B, flag, out=None):
+    """Fills the limiter fields of a SynthLimitOpts / SttsLimitOpts and sets `flag`; the [B] result array is kept alive in `keep` and,
+    when `out` is a dict, published there as out["reduction"] (min of the gain curve per item, 1 = not limited)."""
+    if spec is None:
+        return
+    red = np.full(B, np.nan, np.float32)
+    keep.append(red)
+    opts.flags |= flag
+    opts.limit_mode, opts.limit_ceiling, opts.limit_lookahead_ms, opts.limit_release_ms, opts.limit_gain = spec
+    opts.out_reduction = _p(red, c_f32p)
+    if out is not None:
+        out["reduction"] = red
 
 
 class PersistInfo(ctypes.Structure):
@@ -203,6 +257,7 @@ class VitsLib:
         self.has_loudness = False
         self.has_pitch = False
         self.has_pitch_formant = False
+        self.has_limit = False
         if self.is_device:
             c_i16p = ctypes.POINTER(ctypes.c_int16)
             f("synthesize_pcm16").argtypes = [ctypes.c_void_p, c_i64p, c_i64p, ctypes.c_int32, ctypes.c_int32, c_f32p, c_i64p,
@@ -269,6 +324,16 @@ class VitsLib:
                 f("op_loudness").argtypes = [ctypes.c_int, c_f32p, c_i64p, ctypes.c_int32, ctypes.c_int64, ctypes.c_int32, c_f32p, c_f32p]
                 f("op_loudness_normalize").argtypes = [ctypes.c_int, c_f32p, c_i64p, ctypes.c_int32, ctypes.c_int64, ctypes.c_int32,
                                                        ctypes.c_int32, ctypes.c_float, ctypes.c_float, c_f32p, c_f32p, c_f32p]
+            # include/vits_limit.h: the look-ahead peak limiter (kernel-level doors and the host-only plan)
+            self.has_limit = self.has("op_limit")
+            if self.has_limit:
+                lim = [ctypes.c_int32, ctypes.c_float, ctypes.c_float, ctypes.c_float]  # mode, ceiling, lookahead_ms, release_ms
+                door = [ctypes.c_int, c_f32p, c_i64p, ctypes.c_int32, ctypes.c_int64, ctypes.c_int32]
+                f("limit_plan").argtypes = [ctypes.c_int32, ctypes.c_float, ctypes.c_float, c_i32p, ctypes.POINTER(ctypes.c_double)]
+                f("op_true_peak").argtypes = door + [c_f32p]
+                f("op_limit_gain").argtypes = door + lim + [ctypes.c_float, c_f32p]
+                f("op_limit").argtypes = door + lim + [ctypes.c_float, c_f32p, c_f32p]
+                f("op_loudness_limit").argtypes = door + [ctypes.c_float] + lim + [c_f32p, c_f32p, c_f32p, c_f32p]
             # include/vits_pitch.h: pitch-shifted output, an extension of the product library like the four above
             self.has_pitch = self.has("op_pitch_shift")
             if self.has_pitch:
@@ -470,6 +535,61 @@ class VitsLib:
                                                      float(ceiling), _p(y, c_f32p), _p(loud, c_f32p), _p(gain, c_f32p)))
         return y, loud, gain
 
+    # ---- look-ahead peak limiter (include/vits_limit.h) ------------------------
+    def _need_limit(self):
+        if not self.has_limit:
+            raise VitsError(4, "this backend has no peak limiter (include/vits_limit.h)")
+
+    def limit_plan(self, rate, lookahead_ms=5.0, release_ms=50.0):
+        """vits_limit_plan (host only): (W samples of look-ahead, a = the release coefficient per sample); VitsError names a refused value"""
+        self._need_limit()
+        W, a = ctypes.c_int32(), ctypes.c_double()
+        self.check(self._fn("limit_plan")(int(rate), float(lookahead_ms), float(release_ms), ctypes.byref(W), ctypes.byref(a)))
+        return W.value, a.value
+
+    def op_true_peak(self, x, lengths, rate, device=0):
+        """vits_op_true_peak: x float32 [B, N], lengths [B] -> the 4x oversampled peak of every item, float32 [B]; item b from
+        x[b, :lengths[b]] only"""
+        self._need_limit()
+        x, lengths = self._loud_args(x, lengths)
+        B, N = x.shape
+        tp = np.empty(B, np.float32)
+        self.check(self._fn("op_true_peak")(device, _p(x, c_f32p), _p(lengths, c_i64p), B, N, int(rate), _p(tp, c_f32p)))
+        return tp
+
+    def op_limit_gain(self, x, lengths, rate, mode, ceiling, lookahead_ms=5.0, release_ms=50.0, gain=1.0, device=0):
+        """vits_op_limit_gain -> s float32 [B, N]: the limiter's gain curve, 1 at and beyond lengths[b]"""
+        self._need_limit()
+        x, lengths = self._loud_args(x, lengths)
+        B, N = x.shape
+        s = np.empty((B, N), np.float32)
+        self.check(self._fn("op_limit_gain")(device, _p(x, c_f32p), _p(lengths, c_i64p), B, N, int(rate), int(mode), float(ceiling),
+                                             float(lookahead_ms), float(release_ms), float(gain), _p(s, c_f32p)))
+        return s
+
+    def op_limit(self, x, lengths, rate, mode, ceiling, lookahead_ms=5.0, release_ms=50.0, gain=1.0, device=0):
+        """vits_op_limit -> (y float32 [B, N] = fp32(gain s) x, zero at and beyond lengths[b]; reduction float32 [B] = min s)"""
+        self._need_limit()
+        x, lengths = self._loud_args(x, lengths)
+        B, N = x.shape
+        y, red = np.empty((B, N), np.float32), np.empty(B, np.float32)
+        self.check(self._fn("op_limit")(device, _p(x, c_f32p), _p(lengths, c_i64p), B, N, int(rate), int(mode), float(ceiling),
+                                        float(lookahead_ms), float(release_ms), float(gain), _p(y, c_f32p), _p(red, c_f32p)))
+        return y, red
+
+    def op_loudness_limit(self, x, lengths, rate, target, mode, ceiling, lookahead_ms=5.0, release_ms=50.0, device=0):
+        """vits_op_loudness_limit, the two-pass LUFS form -> (y float32 [B, N]; loudness [B] of the items as given; gain [B] = g_1;
+        reduction [B] = min s of the last pass)"""
+        self._need_limit()
+        x, lengths = self._loud_args(x, lengths)
+        B, N = x.shape
+        y = np.empty((B, N), np.float32)
+        loud, gain, red = np.empty(B, np.float32), np.empty(B, np.float32), np.empty(B, np.float32)
+        self.check(self._fn("op_loudness_limit")(device, _p(x, c_f32p), _p(lengths, c_i64p), B, N, int(rate), float(target), int(mode),
+                                                 float(ceiling), float(lookahead_ms), float(release_ms), _p(y, c_f32p), _p(loud, c_f32p),
+                                                 _p(gain, c_f32p), _p(red, c_f32p)))
+        return y, loud, gain, red
+
     # ---- pitch-shifted output (include/vits_pitch.h) ---------------------------
     def _need_pitch(self):
         if not self.has_pitch:
@@ -572,10 +692,12 @@ class VitsModel:
             pass
 
     def _opts(self, B, Tx, noise_dp, noise_prior, forced_durations, seed, max_frames, solo=False, item_seeds=None, bert=None,
-              loudness=None, loudness_out=None, pitch=None, preserve_formants=False):
+              loudness=None, loudness_out=None, pitch=None, preserve_formants=False, limit=None):
         pitch = pitch_spec(pitch)  # (None, or a shift that does not reduce to P = Q)
-        opts = SynthOpts() if pitch is None else SynthPitchOpts()
+        opts = SynthLimitOpts() if limit is not None else SynthOpts() if pitch is None else SynthPitchOpts()
         keep = []
+        if limit is not None:
+            self.lib._need_limit()
         if pitch is not None:
             self.lib._need_pitch_formant() if preserve_formants else self.lib._need_pitch()
         if loudness is not None:
@@ -610,6 +732,7 @@ class VitsModel:
         opts.max_frames = max_frames
         opts.flags = 1 if solo else 0  # VITS_FLAG_SOLO_BATCH
         set_loudness(opts, keep, loudness, B, FLAG_LOUDNESS, loudness_out)
+        set_limit(opts, keep, limit, B, FLAG_LIMIT, loudness_out)
         if pitch is not None:
             opts.flags |= FLAG_PITCH | (FLAG_PITCH_FORMANT if preserve_formants else 0)  # (the formant bit only with a pitch in effect)
             opts.pitch_semitones = pitch
@@ -627,8 +750,10 @@ class VitsModel:
 
     def synthesize(self, ids, lengths, scales, sid, noise_dp=None, noise_prior=None, forced_durations=None, seed=0,
                    max_frames=0, solo=False, item_seeds=None, bert=None, sample_rate=None, marks=False, loudness=None, loudness_out=None,
-                   pitch=None, preserve_formants=False):
-        """pitch: semitones in [-12, 12] (VITS_FLAG_PITCH, include/vits_pitch.h): every item shifted on the device behind the decoder,
+                   pitch=None, preserve_formants=False, limit=None):
+        """limit: a limit_spec() (VITS_FLAG_LIMIT, include/vits_limit.h): the look-ahead peak limiter with the loudness gain (a LUFS
+        spec whose ceiling is 0) or alone; loudness_out then also receives "reduction" float32 [B].
+        pitch: semitones in [-12, 12] (VITS_FLAG_PITCH, include/vits_pitch.h): every item shifted on the device behind the decoder,
         before the resampler; lengths and marks do not change.  preserve_formants (VITS_FLAG_PITCH_FORMANT): the spectral envelope stays
         where it was; without a pitch in effect it changes nothing.
         One .run(): returns (audio float32 [B,S], out_lengths int64 [B]); with marks=True (vits_synthesize_marks) a third value,
@@ -645,7 +770,7 @@ class VitsModel:
         if lengths.shape != (B,) or sid.shape != (B,) or scales.shape != (3,):
             raise ValueError("bad feed shapes")
         opts, keep = self._opts(B, Tx, noise_dp, noise_prior, forced_durations, seed, max_frames, solo, item_seeds, bert, loudness, loudness_out,
-                                pitch, preserve_formants)
+                                pitch, preserve_formants, limit)
         out = c_f32p()
         ns = ctypes.c_int64()
         olen = np.zeros(B, dtype=np.int64)
@@ -673,8 +798,8 @@ class VitsModel:
 
     def synthesize_pcm16(self, ids, lengths, scales, sid, pcm_scale=1.0, noise_dp=None, noise_prior=None, forced_durations=None,
                          seed=0, max_frames=0, solo=False, item_seeds=None, bert=None, sample_rate=None, marks=False, loudness=None,
-                         loudness_out=None, pitch=None, preserve_formants=False):
-        """pitch, preserve_formants: as for synthesize.
+                         loudness_out=None, pitch=None, preserve_formants=False, limit=None):
+        """pitch, preserve_formants, limit: as for synthesize.
         synthesize() with Synth.synth_audio's `* scale` and audio_float_to_int16 (vosk_tts/synth.py:127-130) done on the
         device: returns (pcm int16 [B,S], out_lengths int64 [B]).  sample_rate: as for synthesize (vits_synthesize_pcm16_rate:
         the resampler does the conversion in its epilogue).  loudness / loudness_out: as for synthesize (pcm_scale multiplies the
@@ -685,7 +810,7 @@ class VitsModel:
         if lengths.shape != (B,) or sid.shape != (B,) or scales.shape != (3,):
             raise ValueError("bad feed shapes")
         opts, keep = self._opts(B, Tx, noise_dp, noise_prior, forced_durations, seed, max_frames, solo, item_seeds, bert, loudness, loudness_out,
-                                pitch, preserve_formants)
+                                pitch, preserve_formants, limit)
         out = ctypes.POINTER(ctypes.c_int16)()
         ns = ctypes.c_int64()
         olen = np.zeros(B, dtype=np.int64)
@@ -714,8 +839,9 @@ class VitsModel:
         return (pcm, olen, ends) if marks else (pcm, olen)
 
     def stream(self, ids, scales, sid, chunk_frames=64, noise_dp=None, noise_prior=None, forced_durations=None, seed=0, bert=None,
-               sample_rate=None, on_marks=None, loudness=None, pitch=None):
-        """pitch: refused (vits_stream_open* refuse VITS_FLAG_PITCH the same way; here before any device work).
+               sample_rate=None, on_marks=None, loudness=None, pitch=None, limit=None):
+        """limit: refused, as loudness is (vits_stream_open* refuse VITS_FLAG_LIMIT).
+        pitch: refused (vits_stream_open* refuse VITS_FLAG_PITCH the same way; here before any device work).
         Streaming synthesis of ONE utterance (vits_stream_*): a generator of float32 chunks of
         chunk_frames*hop_length samples (the last one shorter); their concatenation equals synthesize().
         sample_rate: output rate in Hz (vits_stream_open_rate): the chunk that covers input samples [a, b) holds the outputs
@@ -724,6 +850,9 @@ class VitsModel:
         stream is open, before the first chunk."""
         if loudness is not None:  # (vits_stream_open* refuse VITS_FLAG_LOUDNESS the same way; here before any device work)
             raise VitsError(4, "a stream cannot be loudness-normalised: an integrated-loudness or peak target needs the whole utterance "
+                               "before the first chunk")
+        if limit is not None:
+            raise VitsError(4, "a stream cannot be limited: the limiter's look-ahead and its loudness passes need the whole utterance "
                                "before the first chunk")
         if pitch_spec(pitch) is not None:
             raise VitsError(4, "a stream cannot be pitch-shifted: the phase recursion needs the frames before a chunk")

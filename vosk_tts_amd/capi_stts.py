@@ -5,7 +5,7 @@ import ctypes
 
 import numpy as np
 
-from .capi import VitsError, VitsLib, _f32, _i32, _i64, _p, c_f32p, c_i32p, c_i64p, pitch_spec, set_loudness
+from .capi import LIMIT_FIELDS, VitsError, VitsLib, _f32, _i32, _i64, _p, c_f32p, c_i32p, c_i64p, pitch_spec, set_limit, set_loudness
 from .weights_stts import SttsHParams
 
 
@@ -38,6 +38,16 @@ class SttsPitchOpts(SttsLoudnessOpts):
     reads only under STTS_FLAG_PITCH (the loudness fields inside still only under their own flag)"""
 
     _fields_ = [("pitch_semitones", ctypes.c_float)]
+
+
+STTS_FLAG_LIMIT = 32      # include/vits_limit.h
+
+
+class SttsLimitOpts(SttsPitchOpts):
+    """mirror of `struct stts_synth_opts_limit` (include/vits_limit.h): SttsPitchOpts followed by the six limiter fields, which the library
+    reads only under STTS_FLAG_LIMIT"""
+
+    _fields_ = LIMIT_FIELDS
 
 
 class SttsModel:
@@ -120,15 +130,26 @@ class SttsModel:
             raise VitsError(4, "this backend has no loudness normalisation (include/vits_loudness.h)")
         set_loudness(opts, keep, spec, B, STTS_FLAG_LOUDNESS, out)
 
-    def _opts_for(self, loudness, pitch, preserve_formants=False):
-        """the options struct a call needs: the plain one, the one with the loudness fields, or the one with the pitch behind those;
-        preserve_formants sets its bit only with a pitch in effect"""
-        if pitch_spec(pitch) is not None:
-            if not getattr(self.vlib, "has_pitch", False):
+    def _limit(self, opts, keep, spec, B, out):
+        """STTS_FLAG_LIMIT and its fields (include/vits_limit.h; spec = capi.limit_spec(), None = off); `opts` must then be a SttsLimitOpts"""
+        if spec is None:
+            return
+        assert isinstance(opts, SttsLimitOpts)
+        set_limit(opts, keep, spec, B, STTS_FLAG_LIMIT, out)
+
+    def _opts_for(self, loudness, pitch, preserve_formants=False, limit=None):
+        """the options struct a call needs: the plain one, the one with the loudness fields, the one with the pitch behind those, or the
+        one with the limiter behind that; preserve_formants sets its bit only with a pitch in effect"""
+        if limit is not None and not getattr(self.vlib, "has_limit", False):
+            raise VitsError(4, "this backend has no peak limiter (include/vits_limit.h)")
+        if pitch_spec(pitch) is not None or limit is not None:
+            if pitch_spec(pitch) is not None and not getattr(self.vlib, "has_pitch", False):
                 raise VitsError(4, "this backend has no pitch shifter (include/vits_pitch.h)")
-            if preserve_formants and not getattr(self.vlib, "has_pitch_formant", False):
+            if pitch_spec(pitch) is not None and preserve_formants and not getattr(self.vlib, "has_pitch_formant", False):
                 raise VitsError(4, "this backend has no formant-preserving pitch shift (include/vits_pitch.h, STTS_FLAG_PITCH_FORMANT)")
-            opts = SttsPitchOpts()
+            opts = SttsPitchOpts() if limit is None else SttsLimitOpts()
+            if pitch_spec(pitch) is None:
+                return opts
             opts.flags |= STTS_FLAG_PITCH | (STTS_FLAG_PITCH_FORMANT if preserve_formants else 0)
             opts.pitch_semitones = float(pitch)
             return opts
@@ -141,8 +162,10 @@ class SttsModel:
     # ---- hot path ----------------------------------------------------------------------------
     def synthesize(self, ids, scales, sid, bert=None, phone_duration_extra=None, noise=None, seed=0, n_timesteps=0,
                    want_audio=True, want_mel=True, denoiser_strength=None, denoiser_filter_length=0, marks=False, sample_rate=None,
-                   loudness=None, loudness_out=None, pitch=None, preserve_formants=False):
-        """pitch: semitones in [-12, 12] (STTS_FLAG_PITCH, include/vits_pitch.h): the audio shifted behind the denoiser, before any
+                   loudness=None, loudness_out=None, pitch=None, preserve_formants=False, limit=None):
+        """limit: a capi.limit_spec() (STTS_FLAG_LIMIT, include/vits_limit.h): the peak limiter with the loudness gain or alone;
+        loudness_out then also receives "reduction".
+        pitch: semitones in [-12, 12] (STTS_FLAG_PITCH, include/vits_pitch.h): the audio shifted behind the denoiser, before any
         resampling; its length and the marks do not change.  preserve_formants (STTS_FLAG_PITCH_FORMANT): the spectral envelope stays
         where it was; without a pitch in effect it changes nothing.
         One utterance.  ids int64 [5,T]; returns (audio float32 [S] or None, mel float32 [n_feats,T_y] or None).
@@ -160,7 +183,7 @@ class SttsModel:
         T = ids.shape[1]
         scales = _f32(scales)
         keep = []
-        opts = self._opts_for(loudness, pitch if want_audio else None, preserve_formants)
+        opts = self._opts_for(loudness, pitch if want_audio else None, preserve_formants, limit if want_audio else None)
         if noise is not None:
             a = _f32(noise); keep.append(a)
             if a.ndim != 2 or a.shape[0] != self.hp.n_feats:
@@ -172,6 +195,7 @@ class SttsModel:
         self._denoise(opts, denoiser_strength, denoiser_filter_length)
         if want_audio:
             self._loudness(opts, keep, loudness, 1, loudness_out)
+            self._limit(opts, keep, limit, 1, loudness_out)
         b = None if bert is None else _f32(bert)
         if b is not None and b.shape != (self.hp.bert_dim, T):
             raise ValueError("bert must be [768, T]")
@@ -198,14 +222,17 @@ class SttsModel:
         return (audio, melo, ends) if marks else (audio, melo)
 
     def stream(self, ids, scales, sid, bert=None, phone_duration_extra=None, seed=0, n_timesteps=0, chunk_frames=64,
-               denoiser_strength=None, denoiser_filter_length=0, on_marks=None, loudness=None, pitch=None):
-        """pitch: refused, as loudness is.
+               denoiser_strength=None, denoiser_filter_length=0, on_marks=None, loudness=None, pitch=None, limit=None):
+        """pitch, limit: refused, as loudness is.
         Streaming form of synthesize() (stts_stream_open): a generator of float32 chunks of chunk_frames*hop samples whose
         concatenation equals synthesize()'s audio for the same arguments.  on_marks: called once with token_ends int64 [T]
         (vits_stream_marks) as soon as the stream is open.  loudness: refused (stts_stream_open refuses STTS_FLAG_LOUDNESS the same
         way; here before any device work)."""
         if loudness is not None:
             raise VitsError(4, "a stream cannot be loudness-normalised: an integrated-loudness or peak target needs the whole utterance "
+                               "before the first chunk")
+        if limit is not None:
+            raise VitsError(4, "a stream cannot be limited: the limiter's look-ahead and its loudness passes need the whole utterance "
                                "before the first chunk")
         if pitch_spec(pitch) is not None:
             raise VitsError(4, "a stream cannot be pitch-shifted: the phase recursion needs the frames before a chunk")
@@ -242,8 +269,8 @@ class SttsModel:
 
     def synthesize_batch(self, ids, lengths, scales, sid, bert=None, phone_duration_extra=None, seed=0, n_timesteps=0, item_seeds=None,
                          denoiser_strength=None, denoiser_filter_length=0, marks=False, sample_rate=None, loudness=None, loudness_out=None,
-                         pitch=None, preserve_formants=False):
-        """pitch, preserve_formants: as for synthesize, one value for the batch; every item is shifted from its own length.
+                         pitch=None, preserve_formants=False, limit=None):
+        """pitch, preserve_formants, limit: as for synthesize, one value for the batch; every item is shifted from its own length.
         B independent utterances in one pass (stts_synthesize_batch): ids [B,5,T], lengths [B], sid [B];
         returns (audio float32 [B,S] zero-padded, out_lengths int64 [B] in samples).  Item b equals
         synthesize(ids[b][:, :lengths[b]], ..., seed=item_seeds[b]) (seed + b without item seeds).  marks=True
@@ -256,11 +283,12 @@ class SttsModel:
         B, five, T = ids.shape
         b = None if bert is None else _f32(bert)
         p = None if phone_duration_extra is None else _f32(phone_duration_extra)
-        opts = self._opts_for(loudness, pitch, preserve_formants)
+        opts = self._opts_for(loudness, pitch, preserve_formants, limit)
         opts.seed = seed; opts.n_timesteps = n_timesteps
         self._denoise(opts, denoiser_strength, denoiser_filter_length)
         keep = []
         self._loudness(opts, keep, loudness, B, loudness_out)  # (per-item gains; loudness_out as for synthesize, [B])
+        self._limit(opts, keep, limit, B, loudness_out)
         if item_seeds is not None:
             sd = np.ascontiguousarray(item_seeds, dtype=np.uint64)
             if sd.shape != (B,):

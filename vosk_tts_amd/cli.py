@@ -33,6 +33,10 @@ _OPTIONS = (
                                 "inference.loudness, else off)")),
     (("--peak",), dict(type=float, default=None, metavar="P",
                        help="normalise the audio to this peak in (0, 1] instead (not together with --loudness)")),
+    (("--limit",), dict(choices=("sample", "true"), default=None,
+                        help="look-ahead peak limiter on sample peaks or on true (4x oversampled) peaks: with --loudness the target is met "
+                             "and the peaks above the ceiling (the voice's inference.peak_ceiling, else 1.0) are taken down (default: the "
+                             "voice's inference.limit, else off)")),
     (("--pitch",), dict(type=float, default=None, metavar="SEMITONES",
                         help="shift the pitch of the audio by this many semitones, -12 to 12, at unchanged duration (default: the voice's "
                              "inference.pitch, else none)")),
@@ -68,7 +72,7 @@ def run(opts):
     voice = model_mod.Model(opts.model, opts.model_name, opts.lang)
     marks = Synth(voice).synth(opts.input, opts.output, opts.speaker, speech_rate=opts.speech_rate, sample_rate=opts.sample_rate,
                                denoiser_strength=opts.denoiser_strength, marks=bool(opts.marks), loudness=opts.loudness, peak=opts.peak, pitch=opts.pitch,
-                               preserve_formants=opts.preserve_formants)
+                               preserve_formants=opts.preserve_formants, **({} if opts.limit is None else {"limit": opts.limit}))
     if opts.marks:
         with open(opts.marks, "w", encoding="utf-8") as f:
             f.write(marks.to_json(indent=1) + "\n")

@@ -124,6 +124,7 @@ static int persist_cfg() {
 #include "resample.hip.h"
 #include "denoise.hip.h"
 #include "loudness.hip.h"
+#include "limit.hip.h"
 #include "pitch.hip.h"
 #include "marks.hip.h"
 

@@ -308,7 +308,7 @@ static int device_error_word(int e) {
 
 static int synth_fast(vits_model* m, const int64_t* ids, const int64_t* lengths, int32_t B, int32_t Tx, const float* scales,
                       const int64_t* sid, const vits_synth_opts* opts, bool pcm, float pcm_scale, int rate, void** out, int64_t* out_samples,
-                      int64_t* out_lengths, int64_t* token_ends, const LoudReq& lq, const PitchReq& pq) {
+                      int64_t* out_lengths, int64_t* token_ends, const NormReq& lq, const PitchReq& pq) {
   const vits_hparams& hp = m->hp;
   HIP_TRY(hipSetDevice(m->device));
   const ResampleTab* T = nullptr;  // (uploaded on the first call at this rate, before any capture)
@@ -428,7 +428,7 @@ static int synth_fast(vits_model* m, const int64_t* ids, const int64_t* lengths,
       free(h_out);
       return device_error_word(e2);
     }
-    if (lq.on) loud_req_results(lq, loud_res.data(), B);
+    if (lq.on()) norm_req_results(lq, loud_res.data(), B);
     *out = h_out;
     *out_samples = S;
     if (out_lengths) for (int b = 0; b < B; ++b) out_lengths[b] = T ? T->P.n_out(F->h_ylen[b] * hp.hop_length) : F->h_ylen[b] * hp.hop_length;
@@ -440,18 +440,20 @@ static int synth_fast(vits_model* m, const int64_t* ids, const int64_t* lengths,
   // (sizes in output samples)
   const int64_t S = T ? T->P.n_out(Ty * hp.hop_length) : Ty * hp.hop_length, stride = R ? R->n_cap : (int64_t)TyB * hp.hop_length;
   const char* src_h = R ? R->y_h : Bk->out_h;
-  if (lq.on) {
+  if (lq.on()) {
     // include/vits_loudness.h: the float form of the graph as it is, then the measurement and the gain behind it on the same stream,
     // from the finished waveform on the device (the graph's own copy of the un-normalised float audio to the host is not used)
     LoudWs** pw = R ? &R->lw : &Bk->lw;
     TRY(loud_ws_ensure(pw, B, stride));  // (the first flagged request of this context allocates, before anything is launched)
+    if (lq.lim.on) TRY(lim_ws_ensure(*pw, B, stride));  // (include/vits_limit.h: and its first limited one)
     const LoudWs& W = **pw;
+    NormScratch NS;
+    norm_ws_layout(lq, W, B, stride, &NS);
     TRY(phase2_launch(F, Bk, solo, false, R, T));
     const float* x_d = R ? static_cast<const float*>(R->y_d) : Bk->out_d;
     const int rL = T ? T->P.L : 1, rM = T ? T->P.M : 1;
-    loud_measure_launch(F->stream, lq.P, lq.prm, W.S, x_d, stride, stride, Bk->len_y, hp.hop_length, rL, rM, B, Bk);
-    if (pcm) loud_apply_launch<int16_t>(F->stream, W.S, x_d, stride, stride, Bk->len_y, hp.hop_length, rL, rM, B, static_cast<int16_t*>(W.y_d()), stride, stride, pcm_scale, Bk);
-    else loud_apply_launch<float>(F->stream, W.S, x_d, stride, stride, Bk->len_y, hp.hop_length, rL, rM, B, static_cast<float*>(W.y_d()), stride, stride, 1.f, Bk);
+    if (pcm) norm_launch<int16_t>(F->stream, lq, NS, x_d, stride, stride, Bk->len_y, hp.hop_length, rL, rM, B, static_cast<int16_t*>(W.y_d()), stride, stride, pcm_scale, Bk);
+    else norm_launch<float>(F->stream, lq, NS, x_d, stride, stride, Bk->len_y, hp.hop_length, rL, rM, B, static_cast<float*>(W.y_d()), stride, stride, 1.f, Bk);
     hipMemcpyAsync(W.y_h(), W.y_d(), (size_t)B * stride * (pcm ? sizeof(int16_t) : sizeof(float)), hipMemcpyDeviceToHost, F->stream);
     hipMemcpyAsync(W.res_h(), W.S.res, sizeof(float) * 4 * (size_t)B, hipMemcpyDeviceToHost, F->stream);
     src_h = W.y_h();
@@ -472,7 +474,7 @@ static int synth_fast(vits_model* m, const int64_t* ids, const int64_t* lengths,
     return device_error_word(e2);
   }
   for (int b = 0; b < B; ++b) memcpy(h_out + esz * (size_t)b * S, src_h + esz * (size_t)b * stride, esz * (size_t)S);
-  if (lq.on) loud_req_results(lq, (R ? R->lw : Bk->lw)->res_h(), B);
+  if (lq.on()) norm_req_results(lq, (R ? R->lw : Bk->lw)->res_h(), B);
   *out = h_out;
   *out_samples = S;
   if (out_lengths) for (int b = 0; b < B; ++b) out_lengths[b] = T ? T->P.n_out(F->h_ylen[b] * hp.hop_length) : F->h_ylen[b] * hp.hop_length;
@@ -482,7 +484,7 @@ static int synth_fast(vits_model* m, const int64_t* ids, const int64_t* lengths,
 
 static int synth_eager(vits_model* m, const int64_t* ids, const int64_t* lengths, int32_t B, int32_t Tx, const float* scales,
                        const int64_t* sid, const vits_synth_opts* opts, bool pcm, float pcm_scale, int rate, void** out, int64_t* out_samples,
-                       int64_t* out_lengths, int64_t* token_ends, const LoudReq& lq, const PitchReq& pq) {
+                       int64_t* out_lengths, int64_t* token_ends, const NormReq& lq, const PitchReq& pq) {
   const vits_hparams& hp = m->hp;
   const ResampleTab* T = nullptr;
   if (rate) TRY(resample_get(m->device, hp.sampling_rate, rate, &T));
@@ -512,7 +514,7 @@ static int synth_eager(vits_model* m, const int64_t* ids, const int64_t* lengths
     for (int b = 0; b < B; ++b) h_len[b] = ylen[b] * hp.hop_length;
     long long So2 = 0;
     TRY(pitch_tail_run(pt, s, s->stream, d_audio, S, s->len_y, hp.hop_length, h_len.data(), B, pq, T, lq, pcm, pcm_scale, &d_src, &So2, &loud_res));
-  } else if (lq.on) {  // include/vits_loudness.h: the float waveform at the rate it is returned at, measured, then the gain (and the conversion)
+  } else if (lq.on()) {  // include/vits_loudness.h: the float waveform at the rate it is returned at, measured, then the gain (and the conversion)
     const float* x_d = d_audio;
     if (T) {
       float* d_y = hs.dev_alloc<float>((size_t)B * So);
@@ -521,17 +523,16 @@ static int synth_eager(vits_model* m, const int64_t* ids, const int64_t* lengths
       resample_launch<float>(s->stream, *T, d_audio, S, 0, S, s->len_y, hp.hop_length, B, d_y, So, 0, So, 1.f, nullptr);
       x_d = d_y;
     }
-    char* d_scr = static_cast<char*>(hs.raw_alloc(loud_scratch_bytes(B, So)));
+    char* d_scr = static_cast<char*>(hs.raw_alloc(norm_scratch_bytes(lq, B, So)));
     void* d_n = hs.raw_alloc(esz * (size_t)B * So);
     if (!d_scr || !d_n) return fail(VITS_ERR_NOMEM, "device alloc failed");
-    LoudScratch LS;
-    loud_scratch_layout(B, So, d_scr, &LS);
+    NormScratch NS;
+    norm_scratch_layout(lq, B, So, d_scr, &NS);
     const int rL = T ? T->P.L : 1, rM = T ? T->P.M : 1;
-    loud_measure_launch(s->stream, lq.P, lq.prm, LS, x_d, So, So, s->len_y, hp.hop_length, rL, rM, B, s);
-    if (pcm) loud_apply_launch<int16_t>(s->stream, LS, x_d, So, So, s->len_y, hp.hop_length, rL, rM, B, static_cast<int16_t*>(d_n), So, So, pcm_scale, s);
-    else loud_apply_launch<float>(s->stream, LS, x_d, So, So, s->len_y, hp.hop_length, rL, rM, B, static_cast<float*>(d_n), So, So, 1.f, s);
+    if (pcm) norm_launch<int16_t>(s->stream, lq, NS, x_d, So, So, s->len_y, hp.hop_length, rL, rM, B, static_cast<int16_t*>(d_n), So, So, pcm_scale, s);
+    else norm_launch<float>(s->stream, lq, NS, x_d, So, So, s->len_y, hp.hop_length, rL, rM, B, static_cast<float*>(d_n), So, So, 1.f, s);
     loud_res.resize((size_t)B * 4);
-    hipMemcpyAsync(loud_res.data(), LS.res, sizeof(float) * loud_res.size(), hipMemcpyDeviceToHost, s->stream);
+    hipMemcpyAsync(loud_res.data(), NS.LS.res, sizeof(float) * loud_res.size(), hipMemcpyDeviceToHost, s->stream);
     d_src = d_n;
   } else if (T) {  // item b from its own [0, len) of d_audio; at int16 in place of pcm16_kernel
     void* d_y = hs.raw_alloc(esz * (size_t)B * So);
@@ -553,7 +554,7 @@ static int synth_eager(vits_model* m, const int64_t* ids, const int64_t* lengths
   hipError_t e = hipMemcpyAsync(h_out, d_src, esz * (size_t)B * So, hipMemcpyDeviceToHost, s->stream);
   int rc = e == hipSuccess ? check_err(s) : fail(VITS_ERR_DEVICE, "D2H failed: %s", hipGetErrorString(e));
   if (rc != VITS_OK) { free(h_out); return rc; }
-  if (lq.on) loud_req_results(lq, loud_res.data(), B);
+  if (lq.on()) norm_req_results(lq, loud_res.data(), B);
   *out = h_out;
   *out_samples = So;
   if (out_lengths) for (int b = 0; b < B; ++b) out_lengths[b] = T ? T->P.n_out(ylen[b] * hp.hop_length) : ylen[b] * hp.hop_length;
@@ -568,10 +569,16 @@ static int synth_dispatch(vits_model* m, const int64_t* ids, const int64_t* leng
   for (int b = 0; b < B; ++b) if (lengths[b] < 0 || lengths[b] > Tx) return fail(VITS_ERR_ARG, "length out of range");
   int rate = 0;  // 0: the native rate, on the path as it was
   TRY(resample_rate_arg(m, sample_rate, &rate));
-  LoudReq lq;  // (the five fields are read only under the flag)
+  NormReq lq;  // (the five loudness fields are read only under their flag)
   if (opts && (opts->flags & VITS_FLAG_LOUDNESS))
     TRY(loud_req(true, opts->loudness_mode, opts->loudness_target, opts->loudness_ceiling, opts->out_loudness, opts->out_gain,
-                 rate ? rate : m->hp.sampling_rate, &lq));
+                 rate ? rate : m->hp.sampling_rate, &lq.loud));
+  if (opts && (opts->flags & VITS_FLAG_LIMIT)) {  // (include/vits_limit.h: the six fields behind vits_synth_opts_pitch, read only under the flag)
+    static_assert(offsetof(vits_synth_opts_limit, base) == 0 && offsetof(vits_synth_opts_pitch, base) == 0, "the extended options begin with the plain ones");
+    const vits_synth_opts_limit* mo = reinterpret_cast<const vits_synth_opts_limit*>(opts);
+    TRY(lim_req(true, mo->limit_mode, mo->limit_ceiling, mo->limit_lookahead_ms, mo->limit_release_ms, mo->limit_gain, mo->out_reduction,
+                rate ? rate : m->hp.sampling_rate, lq.loud.on ? opts->loudness_ceiling : 0.f, &lq));
+  }
   PitchReq pq;  // (include/vits_pitch.h: the field behind the struct is read only under the flag)
   TRY(pitch_req_opts(m, opts, &pq));
   static const bool env_off = getenv("VITS_NO_FASTPATH") != nullptr;

@@ -149,6 +149,8 @@ int vits_stream_open_rate(vits_model* m, const int64_t* ids, int32_t Tx, const f
   if (!m || !ids || !scales || !out || Tx <= 0 || chunk_frames <= 0) return fail(VITS_ERR_ARG, "bad argument");
   if (opts && (opts->flags & VITS_FLAG_LOUDNESS))
     return fail(VITS_ERR_UNSUPPORTED, "VITS_FLAG_LOUDNESS on a stream: an integrated-loudness or peak target needs the whole utterance before the first chunk");
+  if (opts && (opts->flags & VITS_FLAG_LIMIT))
+    return fail(VITS_ERR_UNSUPPORTED, "VITS_FLAG_LIMIT on a stream: the limiter's look-ahead and its loudness passes need the whole utterance before the first chunk");
   if (opts) TRY(pitch_flags_check(opts->flags, VITS_FLAG_PITCH, VITS_FLAG_PITCH_FORMANT, "VITS"));
   if (opts && (opts->flags & VITS_FLAG_PITCH))
     return fail(VITS_ERR_UNSUPPORTED, "VITS_FLAG_PITCH on a stream: the phase recursion needs the frames before a chunk, and its state is not carried across chunks");

@@ -490,7 +490,8 @@ static void loud_req_results(const LoudReq& q, const float* res_h, int B) {
 struct LoudWs {
   char* d = nullptr;    // scratch | y
   char* h = nullptr;    // pinned: res [B, 4] | y
-  size_t scr_bytes = 0, y_bytes = 0;
+  char* dm = nullptr;   // limit.hip.h: the limiter's scratch, allocated by the context's first limited request
+  size_t scr_bytes = 0, y_bytes = 0, dm_bytes = 0;
   LoudScratch S;
   void* y_d() const { return d + scr_bytes; }
   float* res_h() const { return reinterpret_cast<float*>(h); }
@@ -498,6 +499,7 @@ struct LoudWs {
 };
 static void loud_ws_free(LoudWs* w) {
   if (w->d) hipFree(w->d);
+  if (w->dm) hipFree(w->dm);
   if (w->h) hipHostFree(w->h);
   *w = LoudWs();
 }
@@ -506,7 +508,7 @@ static void loud_ws_delete(LoudWs* w) {
   loud_ws_free(w);
   delete w;
 }
-static size_t loud_ws_bytes(const LoudWs* w) { return w ? w->scr_bytes + w->y_bytes : 0; }
+static size_t loud_ws_bytes(const LoudWs* w) { return w ? w->scr_bytes + w->y_bytes + w->dm_bytes : 0; }
 static int loud_ws_ensure(LoudWs** pw, int B, long long N) {
   if (!*pw) *pw = new LoudWs();
   LoudWs* w = *pw;

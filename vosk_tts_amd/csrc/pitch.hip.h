@@ -597,7 +597,7 @@ struct PitchTail {
   }
 };
 static int pitch_tail_run(PitchTail& pt, vits_session* s, hipStream_t stream, const float* x, long long S, const int* len_y, int hop,
-                          const long long* h_len, int B, const PitchReq& pq, const ResampleTab* T, const LoudReq& lq, bool pcm, float pcm_scale,
+                          const long long* h_len, int B, const PitchReq& pq, const ResampleTab* T, const NormReq& lq, bool pcm, float pcm_scale,
                           const void** d_out, long long* So_out, std::vector<float>* loud_res) {
   const int device = s->m->device;
   float* d_p = static_cast<float*>(pt.alloc(sizeof(float) * (size_t)B * S));
@@ -607,7 +607,7 @@ static int pitch_tail_run(PitchTail& pt, vits_session* s, hipStream_t stream, co
   const size_t esz = pcm ? sizeof(int16_t) : sizeof(float);
   *So_out = So;
   *d_out = d_p;
-  if (lq.on) {
+  if (lq.on()) {
     const float* x2 = d_p;
     if (T) {
       float* d_y = static_cast<float*>(pt.alloc(sizeof(float) * (size_t)B * So));
@@ -615,17 +615,16 @@ static int pitch_tail_run(PitchTail& pt, vits_session* s, hipStream_t stream, co
       resample_launch<float>(stream, *T, d_p, S, 0, S, len_y, hop, B, d_y, So, 0, So, 1.f, nullptr);
       x2 = d_y;
     }
-    char* d_scr = static_cast<char*>(pt.alloc(loud_scratch_bytes(B, So)));
+    char* d_scr = static_cast<char*>(pt.alloc(norm_scratch_bytes(lq, B, So)));
     void* d_n = pt.alloc(esz * (size_t)B * So);
     if (!d_scr || !d_n) return fail(VITS_ERR_NOMEM, "pitch: device alloc failed");
-    LoudScratch LS;
-    loud_scratch_layout(B, So, d_scr, &LS);
+    NormScratch NS;
+    norm_scratch_layout(lq, B, So, d_scr, &NS);
     const int rL = T ? T->P.L : 1, rM = T ? T->P.M : 1;
-    loud_measure_launch(stream, lq.P, lq.prm, LS, x2, So, So, len_y, hop, rL, rM, B, s);
-    if (pcm) loud_apply_launch<int16_t>(stream, LS, x2, So, So, len_y, hop, rL, rM, B, static_cast<int16_t*>(d_n), So, So, pcm_scale, s);
-    else loud_apply_launch<float>(stream, LS, x2, So, So, len_y, hop, rL, rM, B, static_cast<float*>(d_n), So, So, 1.f, s);
+    if (pcm) norm_launch<int16_t>(stream, lq, NS, x2, So, So, len_y, hop, rL, rM, B, static_cast<int16_t*>(d_n), So, So, pcm_scale, s);
+    else norm_launch<float>(stream, lq, NS, x2, So, So, len_y, hop, rL, rM, B, static_cast<float*>(d_n), So, So, 1.f, s);
     loud_res->resize((size_t)B * 4);
-    hipMemcpyAsync(loud_res->data(), LS.res, sizeof(float) * loud_res->size(), hipMemcpyDeviceToHost, stream);
+    hipMemcpyAsync(loud_res->data(), NS.LS.res, sizeof(float) * loud_res->size(), hipMemcpyDeviceToHost, stream);
     *d_out = d_n;
   } else if (T) {
     void* d_y = pt.alloc(esz * (size_t)B * So);

@@ -1120,25 +1120,37 @@ static int stts_resample_out(stts_model* m, int rate, int B, float** audio, int6
 // STTS_FLAG_LOUDNESS of a call (include/vits_loudness.h): under the flag `opts` is the `base` of a stts_synth_opts_loudness, whose five
 // fields are read only then.  `rate` is the rate the call returns (0: the vocoder's own).  Checked before anything is synthesised: a
 // refusal costs nothing.
-static int stts_loud_arg(const stts_model* m, const stts_synth_opts* opts, int rate, LoudReq* q) {
-  q->on = false;
-  if (!opts || !(opts->flags & STTS_FLAG_LOUDNESS)) return VITS_OK;
+static int stts_loud_arg(const stts_model* m, const stts_synth_opts* opts, int rate, NormReq* q) {
+  *q = NormReq();
+  if (!opts || !(opts->flags & (STTS_FLAG_LOUDNESS | STTS_FLAG_LIMIT))) return VITS_OK;
   if (!m->vocoder) return fail(VITS_ERR_ARG, "no vocoder attached");
   static_assert(offsetof(stts_synth_opts_loudness, base) == 0, "the extended options begin with the plain ones");
   const stts_synth_opts_loudness* lo = reinterpret_cast<const stts_synth_opts_loudness*>(opts);
-  return loud_req(true, lo->loudness_mode, lo->loudness_target, lo->loudness_ceiling, lo->out_loudness, lo->out_gain,
-                  rate ? rate : m->vocoder->hp.sampling_rate, q);
+  const int r = rate ? rate : m->vocoder->hp.sampling_rate;
+  if (opts->flags & STTS_FLAG_LOUDNESS)
+    TRY(loud_req(true, lo->loudness_mode, lo->loudness_target, lo->loudness_ceiling, lo->out_loudness, lo->out_gain, r, &q->loud));
+  if (opts->flags & STTS_FLAG_LIMIT) {  // (include/vits_limit.h: the six fields behind stts_synth_opts_pitch, read only under the flag)
+    static_assert(offsetof(stts_synth_opts_limit, base) == 0 && offsetof(stts_synth_opts_pitch, base) == 0, "the extended options begin with the plain ones");
+    const stts_synth_opts_limit* mo = reinterpret_cast<const stts_synth_opts_limit*>(opts);
+    TRY(lim_req(true, mo->limit_mode, mo->limit_ceiling, mo->limit_lookahead_ms, mo->limit_release_ms, mo->limit_gain, mo->out_reduction, r,
+                q->loud.on ? lo->loudness_ceiling : 0.f, q));
+  }
+  return VITS_OK;
 }
 // a call's audio [B, S] (library-owned, items of lengths[b] samples) normalised in place: last in the order decode, clamp, denoise,
 // resample, normalise, on the finished waveform (the kernels of vits_op_loudness_normalize; like stts_resample_out, it crosses the host
 // once more)
-static int stts_loud_out(stts_model* m, const LoudReq& q, int B, float* audio, int64_t S, const int64_t* lengths) {
-  if (!q.on) return VITS_OK;
-  std::vector<float> loud(B, -INFINITY), gain(B, 1.f);
-  if (S > 0) TRY(loud_op(m->base.device, audio, lengths, B, S, q.P.rate, q.prm, audio, loud.data(), nullptr, gain.data()));
+static int stts_loud_out(stts_model* m, const NormReq& q, int B, float* audio, int64_t S, const int64_t* lengths) {
+  if (!q.on()) return VITS_OK;
+  std::vector<float> loud(B, -INFINITY), gain(B, 1.f), red(B, 1.f);
+  if (S > 0 && q.lim.on)  // (include/vits_limit.h: the kernels of vits_op_limit / vits_op_loudness_limit)
+    TRY(lim_op(m->base.device, audio, lengths, B, S, q.lim.rate, &q.lim.prm, q.loud.on, q.loud.prm.target, nullptr, nullptr, audio, red.data(),
+               loud.data(), gain.data()));
+  else if (S > 0) TRY(loud_op(m->base.device, audio, lengths, B, S, q.loud.P.rate, q.loud.prm, audio, loud.data(), nullptr, gain.data()));
   for (int b = 0; b < B; ++b) {
-    if (q.out_loudness) q.out_loudness[b] = loud[b];
-    if (q.out_gain) q.out_gain[b] = gain[b];
+    if (q.loud.on && q.loud.out_loudness) q.loud.out_loudness[b] = loud[b];
+    if (q.loud.on && q.loud.out_gain) q.loud.out_gain[b] = gain[b];
+    if (q.lim.on && q.lim.out_reduction) q.lim.out_reduction[b] = red[b];
   }
   return VITS_OK;
 }
@@ -1170,13 +1182,13 @@ extern "C" {
 int stts_synthesize(stts_model* m, const int64_t* ids, int32_t Tx, const float* scales, int64_t sid, const float* bert, const float* pde,
                     const stts_synth_opts* opts, float** out_audio, int64_t* out_samples, float** out_mel, int64_t* out_frames) {
   if (!m) return fail(VITS_ERR_ARG, "bad argument");
-  LoudReq lq;
+  NormReq lq;
   PitchReq pq;
   float pst = 0.f;
   if (out_audio) TRY(stts_loud_arg(m, opts, 0, &lq));
   if (out_audio) TRY(stts_pitch_arg(m, opts, &pq, &pst));
   TRY(stts_synthesize_impl(m, ids, Tx, scales, sid, bert, pde, opts, out_audio, out_samples, out_mel, out_frames, nullptr));
-  if (lq.on || pq.on) {
+  if (lq.on() || pq.on) {
     const int64_t len = *out_samples;
     int rc = stts_pitch_out(m, pq, pst, 1, *out_audio, len, &len);
     if (rc == VITS_OK) rc = stts_loud_out(m, lq, 1, *out_audio, len, &len);
@@ -1192,7 +1204,7 @@ int stts_synthesize_marks(stts_model* m, const int64_t* ids, int32_t Tx, const f
   SttsMarks mk;
   int rate = 0;
   TRY(stts_marks_arg(m, token_ends, sample_rate, &mk, &rate));
-  LoudReq lq;
+  NormReq lq;
   if (out_audio) TRY(stts_loud_arg(m, opts, rate, &lq));
   PitchReq pq;
   float pst = 0.f;
@@ -1214,6 +1226,8 @@ int stts_stream_open(stts_model* m, const int64_t* ids, int32_t Tx, const float*
   if (!m->vocoder) return fail(VITS_ERR_ARG, "no vocoder attached");
   if (opts && (opts->flags & STTS_FLAG_LOUDNESS))
     return fail(VITS_ERR_UNSUPPORTED, "STTS_FLAG_LOUDNESS on a stream: an integrated-loudness or peak target needs the whole utterance before the first chunk");
+  if (opts && (opts->flags & STTS_FLAG_LIMIT))
+    return fail(VITS_ERR_UNSUPPORTED, "STTS_FLAG_LIMIT on a stream: the limiter's look-ahead and its loudness passes need the whole utterance before the first chunk");
   if (opts) TRY(pitch_flags_check(opts->flags, STTS_FLAG_PITCH, STTS_FLAG_PITCH_FORMANT, "STTS"));
   if (opts && (opts->flags & STTS_FLAG_PITCH))
     return fail(VITS_ERR_UNSUPPORTED, "STTS_FLAG_PITCH on a stream: the phase recursion needs the frames before a chunk, and its state is not carried across chunks");
@@ -1357,7 +1371,7 @@ int stts_synthesize_batch(stts_model* m, const int64_t* ids, const int64_t* leng
                           const int64_t* sid, const float* bert, const float* pde, const stts_synth_opts* opts, float** out_audio,
                           int64_t* out_samples, int64_t* out_lengths) {
   if (!m) return fail(VITS_ERR_ARG, "bad argument");
-  LoudReq lq;
+  NormReq lq;
   TRY(stts_loud_arg(m, opts, 0, &lq));
   PitchReq pq;
   float pst = 0.f;
@@ -1376,7 +1390,7 @@ int stts_synthesize_batch_marks(stts_model* m, const int64_t* ids, const int64_t
   SttsMarks mk;
   int rate = 0;
   TRY(stts_marks_arg(m, token_ends, sample_rate, &mk, &rate));
-  LoudReq lq;
+  NormReq lq;
   TRY(stts_loud_arg(m, opts, rate, &lq));
   PitchReq pq;
   float pst = 0.f;

@@ -18,7 +18,7 @@ import threading
 
 import numpy as np
 
-from .capi import VitsLib, loudness_spec, pitch_spec
+from .capi import VitsLib, limit_spec, loudness_spec, pitch_spec
 
 log = logging.getLogger(__name__)
 
@@ -226,7 +226,8 @@ _GRAPH_INPUTS = ("input", "input_lengths", "scales", "sid")
 _OPTIONAL_NONE = ("bert", "phone_duration_extra")
 # extension feeds (not part of the ONNX graph) used by parity tests
 _EXT = ("vits.noise_dp", "vits.noise_prior", "vits.forced_durations", "vits.seed", "vits.solo", "vits.item_seeds", "vits.sample_rate", "vits.marks",
-        "vits.loudness", "vits.peak", "vits.peak_ceiling", "vits.pitch", "vits.pitch_formants")
+        "vits.loudness", "vits.peak", "vits.peak_ceiling", "vits.pitch", "vits.pitch_formants", "vits.limit", "vits.limit_lookahead_ms",
+        "vits.limit_release_ms")
 
 
 class _Arg:
@@ -297,8 +298,9 @@ class VitsSession:
         # measured and applied per item, so a request's result does not depend on what it was batched with
         # pitch: the shift of the batch in semitones (None = none; include/vits_pitch.h): part of the key as well, one value per call
         # formants: that shift with the spectral envelope kept (VITS_FLAG_PITCH_FORMANT); False whenever pitch is None
-        kind, scales, scale, rate, marks, loud, pitch, formants = key
-        pk = self._pitch_kw(pitch, formants)
+        # limit: the limiter of the batch (capi.limit_spec(), None = none; include/vits_limit.h): part of the key, applied per item
+        kind, scales, scale, rate, marks, loud, pitch, formants, limit = key
+        pk = self._pitch_kw(pitch, formants, limit)
         scales = np.array(scales, np.float32)
         if len(reqs) == 1:
             ids, sid, seed = reqs[0]
@@ -387,9 +389,22 @@ class VitsSession:
     def _loudness(self, feed):
         """the extension feeds "vits.loudness" (LUFS target), "vits.peak" (peak target) and "vits.peak_ceiling" of a request ->
         capi.loudness_spec() (None = none); both targets at once and values out of range are ValueError, before any device work"""
-        spec = loudness_spec(feed.get("vits.loudness"), feed.get("vits.peak"), feed.get("vits.peak_ceiling"))
+        limited = feed.get("vits.limit") is not None  # (then "vits.peak_ceiling" is the limiter's ceiling and the gain has no cap)
+        spec = loudness_spec(feed.get("vits.loudness"), feed.get("vits.peak"), 0.0 if limited else feed.get("vits.peak_ceiling"))
         if spec is not None:
             self._lib._need_loudness()
+        return spec
+
+    def _limit(self, feed):
+        """the extension feeds "vits.limit" ("sample" or "true"), "vits.limit_lookahead_ms", "vits.limit_release_ms" and, as the
+        limiter's ceiling, "vits.peak_ceiling" -> capi.limit_spec() (None = none; include/vits_limit.h); values out of range and a peak
+        target next to a limiter are ValueError, before any device work"""
+        spec = limit_spec(feed.get("vits.limit"), feed.get("vits.peak_ceiling"), feed.get("vits.limit_lookahead_ms", 5.0),
+                          feed.get("vits.limit_release_ms", 50.0))
+        if spec is not None:
+            if feed.get("vits.peak") is not None:
+                raise ValueError("\"vits.peak\" with \"vits.limit\": a peak target leaves a limiter nothing to do (a LUFS target, or the limiter alone)")
+            self._lib._need_limit()
         return spec
 
     def _pitch(self, feed):
@@ -409,11 +424,12 @@ class VitsSession:
         return on
 
     @staticmethod
-    def _pitch_kw(pitch, formants):
-        """the keywords of the model's calls: none without a shift (the call as it was)"""
+    def _pitch_kw(pitch, formants, limit=None):
+        """the keywords of the model's calls: none without a shift and without a limiter (the call as it was)"""
+        kw = {} if limit is None else {"limit": limit}
         if pitch is None:
-            return {}
-        return {"pitch": pitch, "preserve_formants": True} if formants else {"pitch": pitch}
+            return kw
+        return dict(kw, pitch=pitch, preserve_formants=True) if formants else dict(kw, pitch=pitch)
 
     def run(self, output_names, input_feed, run_options=None):
         """Extension feed "vits.sample_rate" (next to "vits.seed"): output rate in Hz; the time axis of the output is then in output
@@ -427,9 +443,10 @@ class VitsSession:
         loud = self._loudness(feed)
         pitch = self._pitch(feed)  # ("vits.pitch": the audio shifted by that many semitones, behind the decoder)
         formants = self._formants(feed, pitch)
+        limit = self._limit(feed)  # ("vits.limit": the look-ahead peak limiter with the loudness gain, or alone; include/vits_limit.h)
         n = self._coalescable(feed, ids)
         if n:
-            key = ("f32", tuple(float(v) for v in np.asarray(feed["scales"], np.float32).reshape(-1)), 1.0, rate, marks, loud, pitch, formants)
+            key = ("f32", tuple(float(v) for v in np.asarray(feed["scales"], np.float32).reshape(-1)), 1.0, rate, marks, loud, pitch, formants, limit)
             res = self.coalescer.submit(key, np.ascontiguousarray(ids[:, :n], np.int64), int(sid[0]), int(seed))
             self.last_lengths = res[1]
             if marks:  # (the request's own tokens; columns beyond its length repeat the last end, as the C ABI pads them)
@@ -440,7 +457,7 @@ class VitsSession:
             noise_dp=feed.get("vits.noise_dp"), noise_prior=feed.get("vits.noise_prior"),
             forced_durations=feed.get("vits.forced_durations"), seed=int(seed), solo=bool(feed.get("vits.solo", False)),
             item_seeds=feed.get("vits.item_seeds"), bert=feed.get("bert"), sample_rate=rate, marks=marks, loudness=loud,
-            **self._pitch_kw(pitch, formants))
+            **self._pitch_kw(pitch, formants, limit))
         self.last_lengths = res[1]
         return [res[0][:, None, None, :], res[2]] if marks else [res[0][:, None, None, :]]
 
@@ -475,9 +492,10 @@ class VitsSession:
         loud = self._loudness(feed)
         pitch = self._pitch(feed)
         formants = self._formants(feed, pitch)
+        limit = self._limit(feed)
         n = self._coalescable(feed, ids)
         if n:
-            key = ("pcm", tuple(float(v) for v in np.asarray(feed["scales"], np.float32).reshape(-1)), float(scale), rate, marks, loud, pitch, formants)
+            key = ("pcm", tuple(float(v) for v in np.asarray(feed["scales"], np.float32).reshape(-1)), float(scale), rate, marks, loud, pitch, formants, limit)
             res = self.coalescer.submit(key, np.ascontiguousarray(ids[:, :n], np.int64), int(sid[0]), int(seed))
             pcm, lengths = res[0], res[1]
             self.last_lengths = lengths
@@ -490,7 +508,7 @@ class VitsSession:
             pcm_scale=float(scale), noise_dp=feed.get("vits.noise_dp"), noise_prior=feed.get("vits.noise_prior"),
             forced_durations=feed.get("vits.forced_durations"), seed=int(seed), solo=bool(feed.get("vits.solo", False)),
             item_seeds=feed.get("vits.item_seeds"), bert=feed.get("bert"), sample_rate=rate, marks=marks, loudness=loud,
-            **self._pitch_kw(pitch, formants))
+            **self._pitch_kw(pitch, formants, limit))
         pcm, lengths = res[0], res[1]
         self.last_lengths = lengths
         if marks:
@@ -507,6 +525,9 @@ class VitsSession:
         if self._loudness(feed) is not None:
             raise ValueError("a stream cannot be loudness-normalised: an integrated-loudness or peak target needs the whole utterance before "
                              "the first chunk (run() / run_pcm16() take the loudness feeds)")
+        if self._limit(feed) is not None:
+            raise ValueError("a stream cannot be limited: the limiter's look-ahead and its loudness passes need the whole utterance before the "
+                             "first chunk (run() / run_pcm16() take \"vits.limit\")")
         if self._pitch(feed) is not None:
             raise ValueError("a stream cannot be pitch-shifted: the phase recursion needs the frames before a chunk (run() / run_pcm16() "
                              "take \"vits.pitch\")")

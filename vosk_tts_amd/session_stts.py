@@ -9,12 +9,13 @@ import threading
 
 import numpy as np
 
-from .capi import VitsLib, loudness_spec, pitch_spec
+from .capi import VitsLib, limit_spec, loudness_spec, pitch_spec
 from .capi_stts import SttsModel
 
 _INPUTS = ("input", "input_lengths", "scales", "sid", "bert", "phone_duration_extra")
 _EXT = ("vits.noise", "vits.seed", "vits.n_timesteps", "vits.sample_rate", "vits.denoiser_strength", "vits.denoiser_filter_length",
-        "vits.marks", "vits.loudness", "vits.peak", "vits.peak_ceiling", "vits.pitch", "vits.pitch_formants")
+        "vits.marks", "vits.loudness", "vits.peak", "vits.peak_ceiling", "vits.pitch", "vits.pitch_formants",
+        "vits.limit", "vits.limit_lookahead_ms", "vits.limit_release_ms")
 
 
 class SttsSession:
@@ -97,9 +98,21 @@ class SttsSession:
     def _loudness(self, feed):
         """the extension feeds "vits.loudness" (LUFS target), "vits.peak" (peak target), "vits.peak_ceiling" -> capi.loudness_spec()
         (None = none); both targets at once and values out of range are ValueError, before any device work"""
-        spec = loudness_spec(feed.get("vits.loudness"), feed.get("vits.peak"), feed.get("vits.peak_ceiling"))
+        limited = feed.get("vits.limit") is not None  # (then "vits.peak_ceiling" is the limiter's ceiling and the gain has no cap)
+        spec = loudness_spec(feed.get("vits.loudness"), feed.get("vits.peak"), 0.0 if limited else feed.get("vits.peak_ceiling"))
         if spec is not None:
             self._lib._need_loudness()
+        return spec
+
+    def _limit(self, feed):
+        """the extension feeds "vits.limit" ("sample" or "true"), "vits.limit_lookahead_ms", "vits.limit_release_ms" and, as the
+        limiter's ceiling, "vits.peak_ceiling" -> capi.limit_spec() (None = none; include/vits_limit.h)"""
+        spec = limit_spec(feed.get("vits.limit"), feed.get("vits.peak_ceiling"), feed.get("vits.limit_lookahead_ms", 5.0),
+                          feed.get("vits.limit_release_ms", 50.0))
+        if spec is not None:
+            if feed.get("vits.peak") is not None:
+                raise ValueError("\"vits.peak\" with \"vits.limit\": a peak target leaves a limiter nothing to do (a LUFS target, or the limiter alone)")
+            self._lib._need_limit()
         return spec
 
     def _pitch(self, feed):
@@ -115,13 +128,19 @@ class SttsSession:
             return {"pitch": p, "preserve_formants": True}
         return {"pitch": p}
 
-    def normalize(self, audio, lengths, sample_rate, spec):
+    def normalize(self, audio, lengths, sample_rate, spec, limit=None):
         """audio float32 [B, S] at `sample_rate` Hz (None / 0 = the vocoder's own) with per-item sample counts -> the audio normalised
-        per item by `spec` (vits_op_loudness_normalize on the host buffer); None: unchanged.  What run() / run_batch() do behind
-        resample(): the order is decode, clamp, denoise, resample, normalise"""
-        if spec is None or audio.shape[-1] == 0:
+        per item by `spec` (vits_op_loudness_normalize on the host buffer) and / or limited by `limit` (vits_op_loudness_limit,
+        vits_op_limit); both None: unchanged.  What run() / run_batch() do behind resample(): the order is decode, clamp, denoise,
+        resample, normalise + limit"""
+        if (spec is None and limit is None) or audio.shape[-1] == 0:
             return audio
         rate = int(sample_rate or 0) or self._vocoder.hp.sampling_rate
+        if limit is not None:
+            mode, ceiling, la, rel, gain = limit
+            if spec is None:
+                return self._lib.op_limit(audio, lengths, rate, mode, ceiling, la, rel, gain, device=self._vocoder.device)[0]
+            return self._lib.op_loudness_limit(audio, lengths, rate, spec[1], mode, ceiling, la, rel, device=self._vocoder.device)[0]
         return self._lib.op_loudness_normalize(audio, lengths, rate, *spec, device=self._vocoder.device)[0]
 
     def run(self, output_names, input_feed, run_options=None):
@@ -133,20 +152,22 @@ class SttsSession:
         is what is measured (include/vits_loudness.h)."""
         feed, ids, scales, sid, bert, pde, seed = self._parse(output_names, input_feed)
         loud = self._loudness(feed)
+        lim = self._limit(feed)  # ("vits.limit": the peak limiter with the loudness gain or alone, last in the chain like the gain)
         pk = self._pitch(feed)  # ("vits.pitch": shifted inside the library, behind the denoiser and before any resampling)
         if feed.get("vits.marks"):
             audio, _, ends = self._model.synthesize(ids, scales, sid, bert, pde, noise=feed.get("vits.noise"), seed=seed,
                                                     n_timesteps=int(feed.get("vits.n_timesteps", 0)), want_mel=False, marks=True,
-                                                    sample_rate=self._rate(feed.get("vits.sample_rate")), loudness=loud, **pk, **self._denoiser(feed))
+                                                    sample_rate=self._rate(feed.get("vits.sample_rate")), loudness=loud, limit=lim, **pk,
+                                                    **self._denoiser(feed))
             outs = {"wav": audio[None, :], "wav_lengths": np.array([audio.shape[0]], np.int64)}
             return [outs[n] for n in (output_names or ["wav", "wav_lengths"])] + [ends[None, :]]
         rate = self._rate(feed.get("vits.sample_rate"))
         audio, _ = self._model.synthesize(ids, scales, sid, bert, pde, noise=feed.get("vits.noise"), seed=seed,
                                           n_timesteps=int(feed.get("vits.n_timesteps", 0)), want_mel=False,
-                                          loudness=None if rate else loud, **pk, **self._denoiser(feed))
+                                          loudness=None if rate else loud, limit=None if rate else lim, **pk, **self._denoiser(feed))
         if rate:  # (the library normalises last, and this resampling happens behind it: the normalisation follows it here)
             audio = self.resample(audio[None, :], [audio.shape[0]], rate)[0][0]
-            audio = self.normalize(audio[None, :], [audio.shape[0]], rate, loud)[0]
+            audio = self.normalize(audio[None, :], [audio.shape[0]], rate, loud, lim)[0]
         outs = {"wav": audio[None, :], "wav_lengths": np.array([audio.shape[0]], np.int64)}
         return [outs[n] for n in (output_names or ["wav", "wav_lengths"])]
 
@@ -161,6 +182,9 @@ class SttsSession:
         if self._loudness(feed) is not None:
             raise ValueError("a stream cannot be loudness-normalised: an integrated-loudness or peak target needs the whole utterance before "
                              "the first chunk (run() takes the loudness feeds)")
+        if self._limit(feed) is not None:
+            raise ValueError("a stream cannot be limited: the limiter's look-ahead and its loudness passes need the whole utterance before the "
+                             "first chunk (run() takes \"vits.limit\")")
         if self._pitch(feed):
             raise ValueError("a stream cannot be pitch-shifted: the phase recursion needs the frames before a chunk (run() takes "
                              "\"vits.pitch\")")
@@ -199,6 +223,7 @@ class SttsSession:
                 raise ValueError(f"Required input {k} is missing")
         dn = self._denoiser(feed)
         loud = self._loudness(feed)  # (per-item gains, last in the chain like run())
+        lim = self._limit(feed)
         pk = self._pitch(feed)
         rate = self._rate(feed.get("vits.sample_rate"))
         ids = np.asarray(feed["input"])
@@ -209,15 +234,15 @@ class SttsSession:
             return self._model.synthesize_batch(ids, feed["input_lengths"], np.asarray(feed["scales"], np.float32).reshape(-1), sid,
                                                 feed.get("bert"), feed.get("phone_duration_extra"), seed=int(feed.get("vits.seed", 0)),
                                                 n_timesteps=int(feed.get("vits.n_timesteps", 0)), item_seeds=feed.get("vits.item_seeds"),
-                                                marks=True, sample_rate=rate, loudness=loud, **pk, **dn)
+                                                marks=True, sample_rate=rate, loudness=loud, limit=lim, **pk, **dn)
         audio, ol = self._model.synthesize_batch(ids, feed["input_lengths"], np.asarray(feed["scales"], np.float32).reshape(-1), sid,
                                                  feed.get("bert"), feed.get("phone_duration_extra"), seed=int(feed.get("vits.seed", 0)),
                                                  n_timesteps=int(feed.get("vits.n_timesteps", 0)), item_seeds=feed.get("vits.item_seeds"),
-                                                 loudness=None if rate else loud, **pk, **dn)
+                                                 loudness=None if rate else loud, limit=None if rate else lim, **pk, **dn)
         if not rate:
             return audio, ol
         audio, ol = self.resample(audio, ol, rate)
-        return self.normalize(audio, ol, rate, loud), ol
+        return self.normalize(audio, ol, rate, loud, lim), ol
 
     def close(self):
         self._model.close()

@@ -224,6 +224,36 @@ class Synth:
             args["vits.peak"] = float(peak)
         return True
 
+    def _limit(self, args, limit, peak_ceiling=None, lookahead_ms=None, release_ms=None):
+        """The look-ahead peak limiter of the request (include/vits_limit.h): `limit`, None, "sample" or "true" (4x oversampled peaks),
+        defaulting to the config key inference.limit; `lookahead_ms` / `release_ms` default to inference.limit_lookahead_ms /
+        inference.limit_release_ms, else 5 and 50 ms.  peak_ceiling (inference.peak_ceiling, else 1.0) is the limiter's ceiling: with a
+        limiter the loudness gain is not capped, the peaks above the ceiling are taken down around themselves and the LUFS target is met
+        in two passes.  Without a loudness target it is a plain limiter at gain 1.  The feed gets "vits.limit", "vits.limit_lookahead_ms",
+        "vits.limit_release_ms" (and "vits.peak_ceiling"); none given and no config key = off.  A peak target next to a limiter is
+        ValueError."""
+        from .capi import limit_spec
+
+        inf = self.model.config.get("inference", {})
+        if limit is None:
+            limit = inf.get("limit")
+        if limit is None:
+            return False
+        if peak_ceiling is None:
+            peak_ceiling = inf.get("peak_ceiling")
+        la = inf.get("limit_lookahead_ms", 5.0) if lookahead_ms is None else lookahead_ms
+        rel = inf.get("limit_release_ms", 50.0) if release_ms is None else release_ms
+        limit_spec(limit, peak_ceiling, la, rel)  # (raises on a value out of range)
+        if "vits.peak" in args:
+            raise ValueError(f"peak={args['vits.peak']} with limit={limit!r}: a peak target leaves a limiter nothing to do (a LUFS target, or the "
+                             "limiter alone)")
+        args["vits.limit"] = str(limit)
+        args["vits.limit_lookahead_ms"] = float(la)
+        args["vits.limit_release_ms"] = float(rel)
+        if peak_ceiling is not None:
+            args["vits.peak_ceiling"] = float(peak_ceiling)
+        return True
+
     def _pitch(self, args, pitch, preserve_formants=None):
         """Pitch shift of the request (include/vits_pitch.h): `pitch` in semitones, [-12, 12], defaulting to the config key
         inference.pitch; it goes into the feed as "vits.pitch".  None and no config key, or a shift that reduces to the identity = off,
@@ -246,10 +276,11 @@ class Synth:
             args["vits.pitch_formants"] = True
         return True
 
-    def measure_loudness(self, audio, rate=None):
+    def measure_loudness(self, audio, rate=None, true_peak=False):
         """(lufs, peak) of one utterance: BS.1770 integrated loudness (-inf for silence) and max |sample| in full-scale units, measured
         by the engine's own kernels (vits_op_loudness).  audio: int16 PCM (scaled by 1 / 32767, the conversion's own factor) or float;
-        rate: its sample rate in Hz (default: the voice's own)."""
+        rate: its sample rate in Hz (default: the voice's own).  true_peak=True: (lufs, peak, true_peak), the last the 4x oversampled
+        peak of include/vits_limit.h (vits_op_true_peak)."""
         a = np.asarray(audio)
         x = a.astype(np.float32) / np.float32(32767.0) if a.dtype == np.int16 else a.astype(np.float32)
         x = x.reshape(1, -1)
@@ -257,10 +288,14 @@ class Synth:
         lib = getattr(sess, "_lib", None)
         if lib is None or not getattr(lib, "has_loudness", False):
             raise NotImplementedError("this session type has no loudness measurement (include/vits_loudness.h)")
+        if true_peak and not getattr(lib, "has_limit", False):
+            raise NotImplementedError("this session type has no true-peak measurement (include/vits_limit.h)")
         if x.shape[1] == 0:
-            return float("-inf"), 0.0
+            return (float("-inf"), 0.0, 0.0) if true_peak else (float("-inf"), 0.0)
         dev = getattr(getattr(sess, "_vocoder", None) or getattr(sess, "_model", None), "device", 0)
         loud, pk = lib.op_loudness(x, [x.shape[1]], int(rate or self.native_rate()), device=dev)
+        if true_peak:
+            return float(loud[0]), float(pk[0]), float(lib.op_true_peak(x, [x.shape[1]], int(rate or self.native_rate()), device=dev)[0])
         return float(loud[0]), float(pk[0])
 
     def marks_layout(self, text):
@@ -294,8 +329,10 @@ class Synth:
 
     def synth_audio(self, text, speaker_id=0, noise_level=None, speech_rate=None, duration_noise_level=None, scale=None, sample_rate=None,
                     denoiser_strength=None, marks=False, loudness=None, peak=None, peak_ceiling=None, pitch=None,
-                    preserve_formants=None):
-        """pitch / preserve_formants (extension): semitones by which the returned audio is shifted, and whether its formants stay where
+                    preserve_formants=None, limit=None, limit_lookahead_ms=None, limit_release_ms=None):
+        """limit / limit_lookahead_ms / limit_release_ms (extension): the look-ahead peak limiter, see _limit; peak_ceiling is then its
+        ceiling.
+        pitch / preserve_formants (extension): semitones by which the returned audio is shifted, and whether its formants stay where
         they were, see _pitch.
         sample_rate: output rate in Hz (extension; default None = the voice's own rate, the reference's behaviour): the feed gets
         "vits.sample_rate" and the engine resamples on the device.  denoiser_strength: see _denoiser.
@@ -305,6 +342,7 @@ class Synth:
         args, scale = self._feed(text, speaker_id, noise_level, speech_rate, duration_noise_level, scale)
         self._denoiser(args, denoiser_strength)
         self._loudness(args, loudness, peak, peak_ceiling)
+        self._limit(args, limit, peak_ceiling, limit_lookahead_ms, limit_release_ms)
         self._pitch(args, pitch, preserve_formants)
         rate = self.native_rate()
         if sample_rate and int(sample_rate) != rate:
@@ -343,8 +381,10 @@ class Synth:
 
     def synth_stream(self, text, speaker_id=0, noise_level=None, speech_rate=None, duration_noise_level=None, scale=None,
                      chunk_frames=64, sample_rate=None, denoiser_strength=None, on_marks=None, loudness=None, peak=None, peak_ceiling=None,
-                     pitch=None):
-        """pitch: ValueError -- the phase recursion needs the frames before a chunk (a voice whose config names inference.pitch streams
+                     pitch=None, limit=None):
+        """limit: ValueError -- the limiter's look-ahead and its loudness passes need the whole utterance (a voice whose config names
+        inference.limit streams unlimited).
+        pitch: ValueError -- the phase recursion needs the frames before a chunk (a voice whose config names inference.pitch streams
         unshifted).
         Generator of int16 PCM chunks (chunk_frames*256 samples each, ~0.74 s at the default): what a streaming
         `SynthesizeStream` handler would put into successive AudioChunk messages (tts_service.proto:46-54) instead
@@ -355,6 +395,9 @@ class Synth:
         if loudness is not None or peak is not None:
             raise ValueError("synth_stream cannot normalise loudness: an integrated-loudness or peak target needs the whole utterance "
                              "before the first chunk (synth_audio takes loudness= / peak=)")
+        if limit is not None:
+            raise ValueError("synth_stream cannot limit: the limiter's look-ahead and its loudness passes need the whole utterance before the "
+                             "first chunk (synth_audio takes limit=)")
         if pitch is not None:
             raise ValueError("synth_stream cannot shift the pitch: the phase recursion needs the frames before a chunk, and its state is "
                              "not carried across chunks (synth_audio takes pitch=)")
@@ -373,11 +416,13 @@ class Synth:
             yield self.audio_float_to_int16(chunk * scale)
 
     def synth(self, text, oname, speaker_id=0, noise_level=None, speech_rate=None, duration_noise_level=None, scale=None, sample_rate=None,
-              denoiser_strength=None, marks=False, loudness=None, peak=None, peak_ceiling=None, pitch=None, preserve_formants=None):
+              denoiser_strength=None, marks=False, loudness=None, peak=None, peak_ceiling=None, pitch=None, preserve_formants=None,
+              limit=None, limit_lookahead_ms=None, limit_release_ms=None):
         """marks=True: the utterance's marks.SpeechMarks are returned (the default returns None, as the reference does)"""
         audio = self.synth_audio(text, speaker_id, noise_level, speech_rate, duration_noise_level, scale, sample_rate, denoiser_strength, marks=marks,
                                  loudness=loudness, peak=peak, peak_ceiling=peak_ceiling, pitch=pitch,
-                                 preserve_formants=preserve_formants)
+                                 preserve_formants=preserve_formants, limit=limit, limit_lookahead_ms=limit_lookahead_ms,
+                                 limit_release_ms=limit_release_ms)
         sm = None
         if marks:
             audio, sm = audio
