@@ -126,6 +126,7 @@ static int persist_cfg() {
 #include "loudness.hip.h"
 #include "limit.hip.h"
 #include "pitch.hip.h"
+#include "out_tail.hip.h"
 #include "marks.hip.h"
 
 // ------------------------------------------------------------------------------------ C ABI

@@ -307,12 +307,15 @@ static int device_error_word(int e) {
 }
 
 static int synth_fast(vits_model* m, const int64_t* ids, const int64_t* lengths, int32_t B, int32_t Tx, const float* scales,
-                      const int64_t* sid, const vits_synth_opts* opts, bool pcm, float pcm_scale, int rate, void** out, int64_t* out_samples,
-                      int64_t* out_lengths, int64_t* token_ends, const NormReq& lq, const PitchReq& pq) {
+                      const int64_t* sid, const vits_synth_opts* opts, const TailReq& req, void** out, int64_t* out_samples,
+                      int64_t* out_lengths, int64_t* token_ends) {
   const vits_hparams& hp = m->hp;
   HIP_TRY(hipSetDevice(m->device));
-  const ResampleTab* T = nullptr;  // (uploaded on the first call at this rate, before any capture)
-  if (rate) TRY(resample_get(m->device, hp.sampling_rate, rate, &T));
+  TailReq q = req;  // (its table: uploaded on the first call at this rate, before any capture)
+  if (q.rate) TRY(resample_get(m->device, hp.sampling_rate, q.rate, &q.T));
+  const ResampleTab* T = q.T;
+  const NormReq& lq = q.norm;
+  const bool pcm = q.pcm;
   const int TxB = (Tx + 7) / 8 * 8;
   const bool forced = opts && opts->forced_durations, solo = opts && (opts->flags & VITS_FLAG_SOLO_BATCH);
   // (declared before the session guard: the call's last stream synchronisation happens before this scope ends)
@@ -338,7 +341,7 @@ static int synth_fast(vits_model* m, const int64_t* ids, const int64_t* lengths,
   SynthDev* hv = reinterpret_cast<SynthDev*>(F->io_h);
   hv->rate_L = T ? T->P.L : 1; hv->rate_M = T ? T->P.M : 1;
   hv->scales[0] = scales[0]; hv->scales[1] = scales[1]; hv->scales[2] = scales[2];
-  hv->pcm_scale = pcm_scale;
+  hv->pcm_scale = q.pcm_scale;
   hv->seed = opts ? opts->seed : 0;
   int64_t* h_len = reinterpret_cast<int64_t*>(F->io_h + F->io_len);
   int64_t* h_sid = reinterpret_cast<int64_t*>(F->io_h + F->io_sid);
@@ -399,28 +402,21 @@ static int synth_fast(vits_model* m, const int64_t* ids, const int64_t* lengths,
     }
     if (rc != VITS_OK) return rc;
   }
-  if (pq.on) {
-    // include/vits_pitch.h: the float, native-rate form of the graph as it is, then pitch, resample, normalise and the conversion as
-    // launches behind it on the same stream (the graph's own copy of the unshifted float audio to the host is not used)
-    TRY(phase2_launch(F, Bk, solo, false));
-    const long long S0 = (long long)TyB * hp.hop_length;
-    std::vector<long long> h_len(B);
-    for (int b = 0; b < B; ++b) h_len[b] = F->h_ylen[b] * hp.hop_length;
-    PitchTail pt;
-    const void* d_out = nullptr;
-    long long So = 0;
-    std::vector<float> loud_res;
-    int rc = pitch_tail_run(pt, Bk, F->stream, Bk->out_d, S0, Bk->len_y, hp.hop_length, h_len.data(), B, pq, T, lq, pcm, pcm_scale, &d_out, &So, &loud_res);
-    if (rc != VITS_OK) { hipStreamSynchronize(F->stream); return rc; }
-    const int64_t S = T ? T->P.n_out(Ty * hp.hop_length) : Ty * hp.hop_length;
-    const size_t esz = pcm ? sizeof(int16_t) : sizeof(float);
-    char* h_out = static_cast<char*>(malloc(esz * (size_t)B * S));
-    if (!h_out) { hipStreamSynchronize(F->stream); return fail(VITS_ERR_NOMEM, "host alloc failed"); }
-    hipError_t ce = hipMemcpy2DAsync(h_out, esz * (size_t)S, d_out, esz * (size_t)So, esz * (size_t)S, (size_t)B, hipMemcpyDeviceToHost, F->stream);
-    const hipError_t se = hipStreamSynchronize(F->stream);
-    if (ce == hipSuccess) ce = se;
-    if (ce == hipSuccess) ce = hipGetLastError();
-    if (ce != hipSuccess) { free(h_out); return fail(VITS_ERR_DEVICE, "pitch: %s", hipGetErrorString(ce)); }
+  // (sizes in output samples)
+  const int64_t S = T ? T->P.n_out(Ty * hp.hop_length) : Ty * hp.hop_length;
+  const size_t esz = pcm ? sizeof(int16_t) : sizeof(float);
+  // what either branch below ends with, once its work is queued: the buffer the caller gets ...
+  auto host_out = [&]() -> char* {
+    char* h = static_cast<char*>(malloc(esz * (size_t)B * S));
+    if (!h) { hipStreamSynchronize(F->stream); fail(VITS_ERR_NOMEM, "host alloc failed"); }
+    return h;
+  };
+  // ... and the wait, the launch error (`queued`: of the branch's own copies), the flow program's error word, the lengths and the marks
+  auto finish = [&](char* h_out, hipError_t queued) -> int {
+    hipError_t e = hipStreamSynchronize(F->stream);
+    if (queued != hipSuccess) e = queued;
+    if (e == hipSuccess) e = hipGetLastError();
+    if (e != hipSuccess) { free(h_out); return fail(VITS_ERR_DEVICE, "kernel launch failed: %s", hipGetErrorString(e)); }
     if (*Bk->h_err) {
       const int e2 = *Bk->h_err;
       *Bk->h_err = 0;
@@ -428,17 +424,37 @@ static int synth_fast(vits_model* m, const int64_t* ids, const int64_t* lengths,
       free(h_out);
       return device_error_word(e2);
     }
-    if (lq.on()) norm_req_results(lq, loud_res.data(), B);
     *out = h_out;
     *out_samples = S;
     if (out_lengths) for (int b = 0; b < B; ++b) out_lengths[b] = T ? T->P.n_out(F->h_ylen[b] * hp.hop_length) : F->h_ylen[b] * hp.hop_length;
-    if (token_ends) for (int b = 0; b < B; ++b) memcpy(token_ends + (size_t)b * Tx, F->marks_h + (size_t)b * TxB, sizeof(int64_t) * Tx);
+    if (token_ends) for (int b = 0; b < B; ++b) memcpy(token_ends + (size_t)b * Tx, F->marks_h + (size_t)b * TxB, sizeof(int64_t) * Tx);  // (bucket columns dropped)
+    return VITS_OK;
+  };
+  if (q.pitch.on) {
+    // include/vits_pitch.h: the float, native-rate form of the graph as it is, then the tail (out_tail.hip.h) as launches behind it on
+    // the same stream, in buffers of this call (the graph's own copy of the unshifted float audio to the host is not used)
+    TRY(phase2_launch(F, Bk, solo, false));
+    std::vector<long long> h_len(B);
+    for (int b = 0; b < B; ++b) h_len[b] = F->h_ylen[b] * hp.hop_length;
+    TailBufs bufs;
+    const void* d_out = nullptr;
+    const float* d_res = nullptr;
+    long long So = 0;
+    std::vector<float> res((size_t)B * 4);
+    const int rc = tail_run(bufs, Bk, F->stream, Bk->out_d, (long long)TyB * hp.hop_length, Bk->len_y, hp.hop_length, h_len.data(), B, q, &d_out, &So, &d_res);
+    if (rc != VITS_OK) { hipStreamSynchronize(F->stream); return rc; }
+    if (d_res) hipMemcpyAsync(res.data(), d_res, sizeof(float) * res.size(), hipMemcpyDeviceToHost, F->stream);
+    char* h_out = host_out();
+    if (!h_out) return VITS_ERR_NOMEM;
+    TRY(finish(h_out, hipMemcpy2DAsync(h_out, esz * (size_t)S, d_out, esz * (size_t)So, esz * (size_t)S, (size_t)B, hipMemcpyDeviceToHost, F->stream)));
+    if (d_res) norm_req_results(lq, res.data(), B);
     return VITS_OK;
   }
+  // Without a shift a flagged request allocates nothing after the first call of its bucket: the resampler is part of the graph and the
+  // last stage runs in buffers the bucket owns (RateOut, LoudWs), so this branch does not go through tail_run's allocator.
   vits_session::RateOut* R = nullptr;
   if (T) TRY(back_rate_get(F, Bk, *T, &R));
-  // (sizes in output samples)
-  const int64_t S = T ? T->P.n_out(Ty * hp.hop_length) : Ty * hp.hop_length, stride = R ? R->n_cap : (int64_t)TyB * hp.hop_length;
+  const int64_t stride = R ? R->n_cap : (int64_t)TyB * hp.hop_length;
   const char* src_h = R ? R->y_h : Bk->out_h;
   if (lq.on()) {
     // include/vits_loudness.h: the float form of the graph as it is, then the measurement and the gain behind it on the same stream,
@@ -452,42 +468,30 @@ static int synth_fast(vits_model* m, const int64_t* ids, const int64_t* lengths,
     TRY(phase2_launch(F, Bk, solo, false, R, T));
     const float* x_d = R ? static_cast<const float*>(R->y_d) : Bk->out_d;
     const int rL = T ? T->P.L : 1, rM = T ? T->P.M : 1;
-    if (pcm) norm_launch<int16_t>(F->stream, lq, NS, x_d, stride, stride, Bk->len_y, hp.hop_length, rL, rM, B, static_cast<int16_t*>(W.y_d()), stride, stride, pcm_scale, Bk);
+    if (pcm) norm_launch<int16_t>(F->stream, lq, NS, x_d, stride, stride, Bk->len_y, hp.hop_length, rL, rM, B, static_cast<int16_t*>(W.y_d()), stride, stride, q.pcm_scale, Bk);
     else norm_launch<float>(F->stream, lq, NS, x_d, stride, stride, Bk->len_y, hp.hop_length, rL, rM, B, static_cast<float*>(W.y_d()), stride, stride, 1.f, Bk);
-    hipMemcpyAsync(W.y_h(), W.y_d(), (size_t)B * stride * (pcm ? sizeof(int16_t) : sizeof(float)), hipMemcpyDeviceToHost, F->stream);
+    hipMemcpyAsync(W.y_h(), W.y_d(), (size_t)B * stride * esz, hipMemcpyDeviceToHost, F->stream);
     hipMemcpyAsync(W.res_h(), W.S.res, sizeof(float) * 4 * (size_t)B, hipMemcpyDeviceToHost, F->stream);
     src_h = W.y_h();
   } else {
     TRY(phase2_launch(F, Bk, solo, pcm, R, T));
   }
-  const size_t esz = pcm ? sizeof(int16_t) : sizeof(float);
-  char* h_out = static_cast<char*>(malloc(esz * (size_t)B * S));
-  if (!h_out) { hipStreamSynchronize(F->stream); return fail(VITS_ERR_NOMEM, "host alloc failed"); }
-  HIP_TRY(hipStreamSynchronize(F->stream));
-  hipError_t le = hipGetLastError();
-  if (le != hipSuccess) { free(h_out); return fail(VITS_ERR_DEVICE, "kernel launch failed: %s", hipGetErrorString(le)); }
-  if (*Bk->h_err) {
-    const int e2 = *Bk->h_err;
-    *Bk->h_err = 0;
-    hipMemsetAsync(Bk->d_err, 0, sizeof(int), F->stream);
-    free(h_out);
-    return device_error_word(e2);
-  }
+  char* h_out = host_out();
+  if (!h_out) return VITS_ERR_NOMEM;
+  TRY(finish(h_out, hipSuccess));
   for (int b = 0; b < B; ++b) memcpy(h_out + esz * (size_t)b * S, src_h + esz * (size_t)b * stride, esz * (size_t)S);
   if (lq.on()) norm_req_results(lq, (R ? R->lw : Bk->lw)->res_h(), B);
-  *out = h_out;
-  *out_samples = S;
-  if (out_lengths) for (int b = 0; b < B; ++b) out_lengths[b] = T ? T->P.n_out(F->h_ylen[b] * hp.hop_length) : F->h_ylen[b] * hp.hop_length;
-  if (token_ends) for (int b = 0; b < B; ++b) memcpy(token_ends + (size_t)b * Tx, F->marks_h + (size_t)b * TxB, sizeof(int64_t) * Tx);  // (bucket columns dropped)
   return VITS_OK;
 }
 
 static int synth_eager(vits_model* m, const int64_t* ids, const int64_t* lengths, int32_t B, int32_t Tx, const float* scales,
-                       const int64_t* sid, const vits_synth_opts* opts, bool pcm, float pcm_scale, int rate, void** out, int64_t* out_samples,
-                       int64_t* out_lengths, int64_t* token_ends, const NormReq& lq, const PitchReq& pq) {
+                       const int64_t* sid, const vits_synth_opts* opts, const TailReq& req, void** out, int64_t* out_samples,
+                       int64_t* out_lengths, int64_t* token_ends) {
   const vits_hparams& hp = m->hp;
-  const ResampleTab* T = nullptr;
-  if (rate) TRY(resample_get(m->device, hp.sampling_rate, rate, &T));
+  TailReq q = req;
+  if (q.rate) TRY(resample_get(m->device, hp.sampling_rate, q.rate, &q.T));
+  const ResampleTab* T = q.T;
+  std::vector<float> res((size_t)B * 4);  // (the last stage's result rows: declared before the stage, whose end waits for the stream)
   HostStage hs(m);
   std::vector<int64_t> ylen;
   std::vector<int> cum;  // (marks: copied out next to ylen, in acoustic_host's own round trip)
@@ -504,57 +508,21 @@ static int synth_eager(vits_model* m, const int64_t* ids, const int64_t* lengths
   float* d_audio = hs.dev_alloc<float>((size_t)B * S);
   if (!d_audio) return fail(VITS_ERR_NOMEM, "device alloc failed");
   run_decoder(s, z, true, B, (int)Ty, d_audio, S, true, !s->solo);
-  const size_t esz = pcm ? sizeof(int16_t) : sizeof(float);
-  const void* d_src = d_audio;
-  const int64_t So = T ? T->P.n_out(S) : S;  // samples per item as returned
-  std::vector<float> loud_res;
-  PitchTail pt;
-  if (pq.on) {  // include/vits_pitch.h: pitch, resample, normalise and the conversion behind the decoder
-    std::vector<long long> h_len(B);
-    for (int b = 0; b < B; ++b) h_len[b] = ylen[b] * hp.hop_length;
-    long long So2 = 0;
-    TRY(pitch_tail_run(pt, s, s->stream, d_audio, S, s->len_y, hp.hop_length, h_len.data(), B, pq, T, lq, pcm, pcm_scale, &d_src, &So2, &loud_res));
-  } else if (lq.on()) {  // include/vits_loudness.h: the float waveform at the rate it is returned at, measured, then the gain (and the conversion)
-    const float* x_d = d_audio;
-    if (T) {
-      float* d_y = hs.dev_alloc<float>((size_t)B * So);
-      if (!d_y) return fail(VITS_ERR_NOMEM, "device alloc failed");
-      ProfScope ps(s, "out.resample", 2.0 * B * So * T->P.taps, "resample_kernel<float>");
-      resample_launch<float>(s->stream, *T, d_audio, S, 0, S, s->len_y, hp.hop_length, B, d_y, So, 0, So, 1.f, nullptr);
-      x_d = d_y;
-    }
-    char* d_scr = static_cast<char*>(hs.raw_alloc(norm_scratch_bytes(lq, B, So)));
-    void* d_n = hs.raw_alloc(esz * (size_t)B * So);
-    if (!d_scr || !d_n) return fail(VITS_ERR_NOMEM, "device alloc failed");
-    NormScratch NS;
-    norm_scratch_layout(lq, B, So, d_scr, &NS);
-    const int rL = T ? T->P.L : 1, rM = T ? T->P.M : 1;
-    if (pcm) norm_launch<int16_t>(s->stream, lq, NS, x_d, So, So, s->len_y, hp.hop_length, rL, rM, B, static_cast<int16_t*>(d_n), So, So, pcm_scale, s);
-    else norm_launch<float>(s->stream, lq, NS, x_d, So, So, s->len_y, hp.hop_length, rL, rM, B, static_cast<float*>(d_n), So, So, 1.f, s);
-    loud_res.resize((size_t)B * 4);
-    hipMemcpyAsync(loud_res.data(), NS.LS.res, sizeof(float) * loud_res.size(), hipMemcpyDeviceToHost, s->stream);
-    d_src = d_n;
-  } else if (T) {  // item b from its own [0, len) of d_audio; at int16 in place of pcm16_kernel
-    void* d_y = hs.raw_alloc(esz * (size_t)B * So);
-    if (!d_y) return fail(VITS_ERR_NOMEM, "device alloc failed");
-    ProfScope ps(s, "out.resample", 2.0 * B * So * T->P.taps, pcm ? "resample_kernel<int16>" : "resample_kernel<float>");
-    if (pcm) resample_launch<int16_t>(s->stream, *T, d_audio, S, 0, S, s->len_y, hp.hop_length, B, static_cast<int16_t*>(d_y), So, 0, So, pcm_scale, nullptr);
-    else resample_launch<float>(s->stream, *T, d_audio, S, 0, S, s->len_y, hp.hop_length, B, static_cast<float*>(d_y), So, 0, So, 1.f, nullptr);
-    d_src = d_y;
-  } else if (pcm) {
-    int16_t* d_pcm = hs.dev_alloc<int16_t>((size_t)B * S);
-    if (!d_pcm) return fail(VITS_ERR_NOMEM, "device alloc failed");
-    ProfScope ps(s, "out.pcm16", 0, "pcm16_kernel");
-    hipLaunchKernelGGL(pcm16_kernel, dim3(cdiv((int)S, 256), B), dim3(256), 0, s->stream, d_audio, (long long)S, d_pcm, (long long)S, (long long)S, pcm_scale,
-                       (const SynthDev*)nullptr);
-    d_src = d_pcm;
-  }
+  // the tail (out_tail.hip.h) behind the decoder, in the staging area of this call
+  std::vector<long long> h_len(B);
+  for (int b = 0; b < B; ++b) h_len[b] = ylen[b] * hp.hop_length;
+  const void* d_src = nullptr;
+  const float* d_res = nullptr;
+  long long So = 0;  // samples per item as returned
+  TRY(tail_run([&](size_t bytes) { return hs.raw_alloc(bytes); }, s, s->stream, d_audio, S, s->len_y, hp.hop_length, h_len.data(), B, q, &d_src, &So, &d_res));
+  if (d_res) hipMemcpyAsync(res.data(), d_res, sizeof(float) * res.size(), hipMemcpyDeviceToHost, s->stream);
+  const size_t esz = q.pcm ? sizeof(int16_t) : sizeof(float);
   void* h_out = malloc(esz * (size_t)B * So);
   if (!h_out) return fail(VITS_ERR_NOMEM, "host alloc failed");
   hipError_t e = hipMemcpyAsync(h_out, d_src, esz * (size_t)B * So, hipMemcpyDeviceToHost, s->stream);
   int rc = e == hipSuccess ? check_err(s) : fail(VITS_ERR_DEVICE, "D2H failed: %s", hipGetErrorString(e));
   if (rc != VITS_OK) { free(h_out); return rc; }
-  if (lq.on()) norm_req_results(lq, loud_res.data(), B);
+  if (d_res) norm_req_results(q.norm, res.data(), B);
   *out = h_out;
   *out_samples = So;
   if (out_lengths) for (int b = 0; b < B; ++b) out_lengths[b] = T ? T->P.n_out(ylen[b] * hp.hop_length) : ylen[b] * hp.hop_length;
@@ -567,20 +535,8 @@ static int synth_dispatch(vits_model* m, const int64_t* ids, const int64_t* leng
   if (!m || !ids || !lengths || !scales || !out || !out_samples || B <= 0 || Tx <= 0) return fail(VITS_ERR_ARG, "bad argument");
   if (!m->acoustic) return fail(VITS_ERR_UNSUPPORTED, "vocoder-only model: only the decoder stage is available");
   for (int b = 0; b < B; ++b) if (lengths[b] < 0 || lengths[b] > Tx) return fail(VITS_ERR_ARG, "length out of range");
-  int rate = 0;  // 0: the native rate, on the path as it was
-  TRY(resample_rate_arg(m, sample_rate, &rate));
-  NormReq lq;  // (the five loudness fields are read only under their flag)
-  if (opts && (opts->flags & VITS_FLAG_LOUDNESS))
-    TRY(loud_req(true, opts->loudness_mode, opts->loudness_target, opts->loudness_ceiling, opts->out_loudness, opts->out_gain,
-                 rate ? rate : m->hp.sampling_rate, &lq.loud));
-  if (opts && (opts->flags & VITS_FLAG_LIMIT)) {  // (include/vits_limit.h: the six fields behind vits_synth_opts_pitch, read only under the flag)
-    static_assert(offsetof(vits_synth_opts_limit, base) == 0 && offsetof(vits_synth_opts_pitch, base) == 0, "the extended options begin with the plain ones");
-    const vits_synth_opts_limit* mo = reinterpret_cast<const vits_synth_opts_limit*>(opts);
-    TRY(lim_req(true, mo->limit_mode, mo->limit_ceiling, mo->limit_lookahead_ms, mo->limit_release_ms, mo->limit_gain, mo->out_reduction,
-                rate ? rate : m->hp.sampling_rate, lq.loud.on ? opts->loudness_ceiling : 0.f, &lq));
-  }
-  PitchReq pq;  // (include/vits_pitch.h: the field behind the struct is read only under the flag)
-  TRY(pitch_req_opts(m, opts, &pq));
+  TailReq q;  // (out_tail.hip.h: the rate, the loudness target, the limiter and the shift, checked before anything is queued)
+  TRY(tail_req(m, tail_fields_vits(opts), sample_rate, pcm, pcm_scale, &q));
   static const bool env_off = getenv("VITS_NO_FASTPATH") != nullptr;
   if (m->hp.bert_dim > 0 && (!opts || !opts->bert)) return fail(VITS_ERR_ARG, "this voice is BERT-conditioned: the bert feed [B,%d,T_x] is required", m->hp.bert_dim);
   if (m->hp.bert_dim == 0 && opts && opts->bert) return fail(VITS_ERR_ARG, "the bert feed was given but this voice has no BERT projection (hparams.bert_dim == 0)");
@@ -593,8 +549,8 @@ static int synth_dispatch(vits_model* m, const int64_t* ids, const int64_t* leng
   for (int attempt = 0;; ++attempt) {
     tl_ps_timed_out = false;
     const int rc = (g_fast_path && !env_off && !injected)
-                       ? synth_fast(m, ids, lengths, B, Tx, scales, sid, opts, pcm, pcm_scale, rate, out, out_samples, out_lengths, token_ends, lq, pq)
-                       : synth_eager(m, ids, lengths, B, Tx, scales, sid, opts, pcm, pcm_scale, rate, out, out_samples, out_lengths, token_ends, lq, pq);
+                       ? synth_fast(m, ids, lengths, B, Tx, scales, sid, opts, q, out, out_samples, out_lengths, token_ends)
+                       : synth_eager(m, ids, lengths, B, Tx, scales, sid, opts, q, out, out_samples, out_lengths, token_ends);
     if (rc == VITS_OK || !tl_ps_timed_out || attempt) return rc;  // a persistent program timed out: once more, on launches
   }
 }

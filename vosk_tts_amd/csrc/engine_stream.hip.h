@@ -147,13 +147,7 @@ int vits_stream_open(vits_model* m, const int64_t* ids, int32_t Tx, const float*
 int vits_stream_open_rate(vits_model* m, const int64_t* ids, int32_t Tx, const float* scales, int64_t sid, const vits_synth_opts* opts,
                           int32_t chunk_frames, int32_t sample_rate, vits_stream** out, int64_t* total_samples) {
   if (!m || !ids || !scales || !out || Tx <= 0 || chunk_frames <= 0) return fail(VITS_ERR_ARG, "bad argument");
-  if (opts && (opts->flags & VITS_FLAG_LOUDNESS))
-    return fail(VITS_ERR_UNSUPPORTED, "VITS_FLAG_LOUDNESS on a stream: an integrated-loudness or peak target needs the whole utterance before the first chunk");
-  if (opts && (opts->flags & VITS_FLAG_LIMIT))
-    return fail(VITS_ERR_UNSUPPORTED, "VITS_FLAG_LIMIT on a stream: the limiter's look-ahead and its loudness passes need the whole utterance before the first chunk");
-  if (opts) TRY(pitch_flags_check(opts->flags, VITS_FLAG_PITCH, VITS_FLAG_PITCH_FORMANT, "VITS"));
-  if (opts && (opts->flags & VITS_FLAG_PITCH))
-    return fail(VITS_ERR_UNSUPPORTED, "VITS_FLAG_PITCH on a stream: the phase recursion needs the frames before a chunk, and its state is not carried across chunks");
+  if (opts) TRY(tail_refuse_stream(opts->flags, TAIL_VITS));
   const ResampleTab* T = nullptr;
   TRY(stream_rate(m, sample_rate, &T));
   for (int attempt = 0;; ++attempt) {

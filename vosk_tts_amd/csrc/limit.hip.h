@@ -534,12 +534,8 @@ int vits_limit_plan(int32_t rate, float lookahead_ms, float release_ms, int32_t*
 // x [B, N] on the host through step 1 (prm null: true peak only) or a whole limited call; lufs: the two-pass form at `target`
 static int lim_op(int device, const float* x, const int64_t* lengths, int32_t B, int64_t N, int32_t rate, const LimPrm* prm, bool lufs,
                   float target, float* tp, float* s, float* y, float* reduction, float* loudness, float* gain) {
-  if (!x || !lengths || B <= 0 || B > 65535 || N <= 0 || N >= (1LL << 31)) return fail(VITS_ERR_ARG, "limit: bad argument");
-  std::vector<int> len32(B);
-  for (int b = 0; b < B; ++b) {
-    if (lengths[b] < 0 || lengths[b] > N) return fail(VITS_ERR_ARG, "limit: length %lld of item %d outside [0, %lld]", (long long)lengths[b], b, (long long)N);
-    len32[b] = (int)lengths[b];
-  }
+  std::vector<int> len32;
+  TRY(op_items_check("limit", x, lengths, B, N, &len32));
   const int mode = prm ? prm->mode : VITS_LIMIT_TRUE;
   LimTab tab;
   memset(&tab, 0, sizeof(tab));

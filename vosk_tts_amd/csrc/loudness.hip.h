@@ -534,15 +534,25 @@ int vits_loudness_plan(int32_t rate, double sos[2][6], int32_t* hop) {
   return VITS_OK;
 }
 
+// what the parity doors over B items x [B, N] on the host (loud_op, lim_op, pitch_op) check first; len32: the lengths as the kernels
+// take them.  `what` is the door's name in its messages, `n_name` what it calls N there.
+static int op_items_check(const char* what, const float* x, const int64_t* lengths, int32_t B, int64_t N, std::vector<int>* len32,
+                          const char* n_name = "") {
+  if (!x || !lengths || B <= 0 || B > 65535 || N <= 0 || N >= (1LL << 31)) return fail(VITS_ERR_ARG, "%s: bad argument", what);
+  len32->resize(B);
+  for (int b = 0; b < B; ++b) {
+    if (lengths[b] < 0 || lengths[b] > N)
+      return fail(VITS_ERR_ARG, "%s: length %lld of item %d outside [0, %s%lld]", what, (long long)lengths[b], b, n_name, (long long)N);
+    (*len32)[b] = (int)lengths[b];
+  }
+  return VITS_OK;
+}
+
 // x [B, N] on the host measured (prm.mode 0) or normalised into y; results for every item
 static int loud_op(int device, const float* x, const int64_t* lengths, int32_t B, int64_t N, int32_t rate, const LoudParams& prm, float* y,
                    float* loudness, float* peak, float* gain) {
-  if (!x || !lengths || B <= 0 || B > 65535 || N <= 0 || N >= (1LL << 31)) return fail(VITS_ERR_ARG, "loudness: bad argument");
-  std::vector<int> len32(B);
-  for (int b = 0; b < B; ++b) {
-    if (lengths[b] < 0 || lengths[b] > N) return fail(VITS_ERR_ARG, "loudness: length %lld of item %d outside [0, %lld]", (long long)lengths[b], b, (long long)N);
-    len32[b] = (int)lengths[b];
-  }
+  std::vector<int> len32;
+  TRY(op_items_check("loudness", x, lengths, B, N, &len32));
   LoudPlan P;
   TRY(loud_plan(rate, &P));
   HIP_TRY(hipSetDevice(device));

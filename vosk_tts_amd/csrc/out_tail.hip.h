@@ -1,0 +1,173 @@
+// out_tail.hip.h -- the output tail: what a synthesize call asks of the stages behind the decoder (TailReq, built by tail_req from the
+// plain fields behind the option flags), and the one runner of the chain  pitch -> resample -> normalise / limit -> int16  on the device
+// (tail_run).  The kernels and their launches are those of resample / loudness / limit / pitch.hip.h; this file only orders them.
+// Part of the ONE translation unit engine.hip (included there, behind limit.hip.h and pitch.hip.h; not a standalone header).
+#pragma once
+
+// ---- the request ----------------------------------------------------------------------------------------------------------
+// The flag bits and the name of an API family: the two families number the same four flags differently.
+struct TailFamily { const char* name; uint32_t loudness, limit, pitch, formant; };
+static const TailFamily TAIL_VITS = {"VITS", VITS_FLAG_LOUDNESS, VITS_FLAG_LIMIT, VITS_FLAG_PITCH, VITS_FLAG_PITCH_FORMANT};
+static const TailFamily TAIL_STTS = {"STTS", STTS_FLAG_LOUDNESS, STTS_FLAG_LIMIT, STTS_FLAG_PITCH, STTS_FLAG_PITCH_FORMANT};
+
+// The values behind the flags of a call, flat.  A group is meaningful only where its `on` is set (`formant` is the bare flag bit).
+struct TailFields {
+  const char* family = "VITS";
+  bool loud_on = false;
+  int loud_mode = 0;
+  float loud_target = 0.f, loud_ceiling = 0.f;
+  float *out_loudness = nullptr, *out_gain = nullptr;
+  bool lim_on = false;
+  int lim_mode = 0;
+  float lim_ceiling = 0.f, lim_lookahead_ms = 0.f, lim_release_ms = 0.f, lim_gain = 0.f;
+  float* out_reduction = nullptr;
+  bool pitch_on = false, formant = false;
+  float semitones = 0.f;
+};
+
+// The only two places that cast down the `base` chain of the extended option structs: a struct's own fields are read under its flag
+// alone, so a caller who sets no flag may pass the plain struct (include/vits_loudness.h, vits_pitch.h, vits_limit.h).
+template <typename Pitch, typename Limit, typename Loud, typename Opts>
+static TailFields tail_fields(const TailFamily& fam, const Opts* opts, const Loud* lo) {
+  TailFields f;
+  f.family = fam.name;
+  if (!opts) return f;
+  const uint32_t fl = opts->flags;
+  f.loud_on = (fl & fam.loudness) != 0; f.lim_on = (fl & fam.limit) != 0; f.pitch_on = (fl & fam.pitch) != 0; f.formant = (fl & fam.formant) != 0;
+  if (f.loud_on) {
+    f.loud_mode = lo->loudness_mode; f.loud_target = lo->loudness_target; f.loud_ceiling = lo->loudness_ceiling;
+    f.out_loudness = lo->out_loudness; f.out_gain = lo->out_gain;
+  }
+  if (f.lim_on) {
+    const Limit* mo = reinterpret_cast<const Limit*>(opts);
+    f.lim_mode = mo->limit_mode; f.lim_ceiling = mo->limit_ceiling; f.lim_lookahead_ms = mo->limit_lookahead_ms;
+    f.lim_release_ms = mo->limit_release_ms; f.lim_gain = mo->limit_gain; f.out_reduction = mo->out_reduction;
+  }
+  if (f.pitch_on) f.semitones = reinterpret_cast<const Pitch*>(opts)->pitch_semitones;
+  return f;
+}
+static TailFields tail_fields_vits(const vits_synth_opts* opts) {  // (the loudness fields are the plain struct's own)
+  static_assert(offsetof(vits_synth_opts_limit, base) == 0 && offsetof(vits_synth_opts_pitch, base) == 0, "the extended options begin with the plain ones");
+  return tail_fields<vits_synth_opts_pitch, vits_synth_opts_limit>(TAIL_VITS, opts, opts);
+}
+static TailFields tail_fields_stts(const stts_synth_opts* opts) {
+  static_assert(offsetof(stts_synth_opts_limit, base) == 0 && offsetof(stts_synth_opts_pitch, base) == 0 && offsetof(stts_synth_opts_loudness, base) == 0,
+                "the extended options begin with the plain ones");
+  return tail_fields<stts_synth_opts_pitch, stts_synth_opts_limit>(TAIL_STTS, opts, reinterpret_cast<const stts_synth_opts_loudness*>(opts));
+}
+
+// the formant bit modifies a pitch request: alone it is refused, before any work is queued
+static int tail_formant_check(bool formant, bool pitch, const char* family) {
+  if (formant && !pitch)
+    return fail(VITS_ERR_ARG, "%s_FLAG_PITCH_FORMANT without %s_FLAG_PITCH: the flag modifies a pitch request (include/vits_pitch.h)", family, family);
+  return VITS_OK;
+}
+
+// a stream has no tail: each of its stages needs the whole utterance
+static int tail_refuse_stream(uint32_t flags, const TailFamily& fam) {
+  if (flags & fam.loudness)
+    return fail(VITS_ERR_UNSUPPORTED, "%s_FLAG_LOUDNESS on a stream: an integrated-loudness or peak target needs the whole utterance before the first chunk", fam.name);
+  if (flags & fam.limit)
+    return fail(VITS_ERR_UNSUPPORTED, "%s_FLAG_LIMIT on a stream: the limiter's look-ahead and its loudness passes need the whole utterance before the first chunk", fam.name);
+  TRY(tail_formant_check((flags & fam.formant) != 0, (flags & fam.pitch) != 0, fam.name));
+  if (flags & fam.pitch)
+    return fail(VITS_ERR_UNSUPPORTED, "%s_FLAG_PITCH on a stream: the phase recursion needs the frames before a chunk, and its state is not carried across chunks", fam.name);
+  return VITS_OK;
+}
+
+// Everything a call asks of the stages behind the decoder.  T: the table of `rate` on the device, set by the callers that resample there
+// (resample_get: uploaded on first use, before any capture); rate 0: the vocoder's own.
+struct TailReq {
+  PitchReq pitch;
+  const ResampleTab* T = nullptr;
+  int rate = 0;
+  NormReq norm;
+  bool pcm = false;
+  float pcm_scale = 1.f;
+};
+
+// Checked before anything is synthesised, so a refusal costs nothing: the rate, the loudness target, the limiter, the shift.  `vocoder`
+// is null for a multistream model without one: its entry point has resolved the rate (stts_marks_arg) and any stage asked for is refused.
+static int tail_req(const vits_model* vocoder, const TailFields& f, int32_t sample_rate, bool pcm, float pcm_scale, TailReq* out) {
+  *out = TailReq();
+  out->pcm = pcm; out->pcm_scale = pcm_scale;
+  if (vocoder) TRY(resample_rate_arg(vocoder, sample_rate, &out->rate));
+  else out->rate = sample_rate;
+  if ((f.loud_on || f.lim_on) && !vocoder) return fail(VITS_ERR_ARG, "no vocoder attached");
+  const int rate = out->rate ? out->rate : vocoder ? vocoder->hp.sampling_rate : 0;  // (what the last stage measures is the audio as returned)
+  TRY(loud_req(f.loud_on, f.loud_mode, f.loud_target, f.loud_ceiling, f.out_loudness, f.out_gain, rate, &out->norm.loud));
+  TRY(lim_req(f.lim_on, f.lim_mode, f.lim_ceiling, f.lim_lookahead_ms, f.lim_release_ms, f.lim_gain, f.out_reduction, rate,
+              out->norm.loud.on ? f.loud_ceiling : 0.f, &out->norm));
+  TRY(tail_formant_check(f.formant, f.pitch_on, f.family));
+  if (!f.pitch_on) return VITS_OK;
+  if (!vocoder) return fail(VITS_ERR_ARG, "no vocoder attached");
+  return pitch_req(vocoder, f.semitones, f.formant, &out->pitch);
+}
+
+// ---- the runner -----------------------------------------------------------------------------------------------------------
+// device buffers owned by one call (the allocator of a tail_run that has no arena to draw from), freed with it
+struct TailBufs {
+  std::vector<void*> bufs;
+  ~TailBufs() { for (void* p : bufs) hipFree(p); }
+  void* operator()(size_t bytes) {
+    void* p = nullptr;
+    if (hipMalloc(&p, bytes ? bytes : 1) != hipSuccess) { (void)hipGetLastError(); return nullptr; }
+    bufs.push_back(p);
+    return p;
+  }
+};
+
+// The tail of a vits_synthesize* call, as launches on `stream` from the float native-rate waveform x [B, S] on the device (item b is
+// len_y[b] * hop samples, h_len[b] on the host): pitch, resample, normalise and / or limit; the last stage that runs converts to int16
+// where q.pcm.  *d_out is [B, *So] of float or int16 (x itself where nothing is asked), *d_res the [B, 4] result rows of the last
+// stage on the device (null without one), for the caller's own copies to the host.  alloc(bytes) -> void* is the caller's: buffers
+// that outlive the launches queued here.  s: the session the launches are counted under (ProfScope).
+template <typename Alloc>
+static int tail_run(Alloc&& alloc, vits_session* s, hipStream_t stream, const float* x, long long S, const int* len_y, int hop, const long long* h_len,
+                    int B, const TailReq& q, const void** d_out, long long* So_out, const float** d_res) {
+  const ResampleTab* T = q.T;
+  const long long So = T ? T->P.n_out(S) : S;
+  const size_t esz = q.pcm ? sizeof(int16_t) : sizeof(float);
+  *So_out = So;
+  *d_res = nullptr;
+  if (q.pitch.on) {
+    float* d_p = static_cast<float*>(alloc(sizeof(float) * (size_t)B * S));
+    if (!d_p) return fail(VITS_ERR_NOMEM, "device alloc failed");
+    TRY(pitch_run(s->m->device, stream, x, S, S, len_y, hop, h_len, B, q.pitch.P, q.pitch.Q, q.pitch.formant, d_p, S, S, nullptr, 0));
+    x = d_p;
+  }
+  *d_out = x;
+  if (q.norm.on()) {  // the float waveform at the rate it is returned at, measured, then the gain (and the conversion)
+    if (T) {
+      float* d_y = static_cast<float*>(alloc(sizeof(float) * (size_t)B * So));
+      if (!d_y) return fail(VITS_ERR_NOMEM, "device alloc failed");
+      ProfScope ps(s, "out.resample", 2.0 * B * So * T->P.taps, "resample_kernel<float>");
+      resample_launch<float>(stream, *T, x, S, 0, S, len_y, hop, B, d_y, So, 0, So, 1.f, nullptr);
+      x = d_y;
+    }
+    char* d_scr = static_cast<char*>(alloc(norm_scratch_bytes(q.norm, B, So)));
+    void* d_n = alloc(esz * (size_t)B * So);
+    if (!d_scr || !d_n) return fail(VITS_ERR_NOMEM, "device alloc failed");
+    NormScratch NS;
+    norm_scratch_layout(q.norm, B, So, d_scr, &NS);
+    const int rL = T ? T->P.L : 1, rM = T ? T->P.M : 1;
+    if (q.pcm) norm_launch<int16_t>(stream, q.norm, NS, x, So, So, len_y, hop, rL, rM, B, static_cast<int16_t*>(d_n), So, So, q.pcm_scale, s);
+    else norm_launch<float>(stream, q.norm, NS, x, So, So, len_y, hop, rL, rM, B, static_cast<float*>(d_n), So, So, 1.f, s);
+    *d_res = NS.LS.res;
+    *d_out = d_n;
+  } else if (T) {  // item b from its own [0, len) of x; at int16 in place of pcm16_kernel
+    void* d_y = alloc(esz * (size_t)B * So);
+    if (!d_y) return fail(VITS_ERR_NOMEM, "device alloc failed");
+    ProfScope ps(s, "out.resample", 2.0 * B * So * T->P.taps, q.pcm ? "resample_kernel<int16>" : "resample_kernel<float>");
+    if (q.pcm) resample_launch<int16_t>(stream, *T, x, S, 0, S, len_y, hop, B, static_cast<int16_t*>(d_y), So, 0, So, q.pcm_scale, nullptr);
+    else resample_launch<float>(stream, *T, x, S, 0, S, len_y, hop, B, static_cast<float*>(d_y), So, 0, So, 1.f, nullptr);
+    *d_out = d_y;
+  } else if (q.pcm) {
+    int16_t* d_pcm = static_cast<int16_t*>(alloc(sizeof(int16_t) * (size_t)B * S));
+    if (!d_pcm) return fail(VITS_ERR_NOMEM, "device alloc failed");
+    ProfScope ps(s, "out.pcm16", 0, "pcm16_kernel");
+    hipLaunchKernelGGL(pcm16_kernel, dim3(cdiv((int)S, 256), B), dim3(256), 0, stream, x, S, d_pcm, S, S, q.pcm_scale, (const SynthDev*)nullptr);
+    *d_out = d_pcm;
+  }
+  return VITS_OK;
+}

@@ -417,7 +417,7 @@ __global__ __launch_bounds__(256) void pitch_short_kernel(const float* __restric
 }
 
 // ---- host ---------------------------------------------------------------------------------------------------------------
-struct PitchReq { bool on = false; int P = 1, Q = 1; bool formant = false; };
+struct PitchReq { bool on = false; int P = 1, Q = 1; bool formant = false; float semitones = 0.f; };  // (semitones: what P / Q were planned from)
 
 static int pitch_plan(float semitones, int* P, int* Q) {
   if (!(fabsf(semitones) <= (float)VITS_PITCH_MAX_SEMITONES))  // (NaN fails the comparison)
@@ -552,13 +552,6 @@ static int pitch_run(int device, hipStream_t stream, const float* x, long long x
   return VITS_OK;
 }
 
-// the formant bit modifies a pitch request: alone it is refused, before any work is queued (`family`: VITS or STTS, for the names)
-static int pitch_flags_check(uint32_t flags, uint32_t pitch_bit, uint32_t formant_bit, const char* family) {
-  if ((flags & formant_bit) && !(flags & pitch_bit))
-    return fail(VITS_ERR_ARG, "%s_FLAG_PITCH_FORMANT without %s_FLAG_PITCH: the flag modifies a pitch request (include/vits_pitch.h)", family, family);
-  return VITS_OK;
-}
-
 // what a shifting entry point of a vocoder needs checked before any work is queued
 static int pitch_req(const vits_model* v, float semitones, bool formant, PitchReq* q) {
   q->on = false;
@@ -569,75 +562,7 @@ static int pitch_req(const vits_model* v, float semitones, bool formant, PitchRe
     return fail(VITS_ERR_UNSUPPORTED, "pitch: the vocoder's hop_length %d is not a multiple of the pitch stage's hop %d", v->hp.hop_length, PT_H);
   ResamplePlan rp;
   TRY(resample_plan(P, Q, &rp));
-  q->on = true; q->P = P; q->Q = Q; q->formant = formant;
-  return VITS_OK;
-}
-
-// VITS_FLAG_PITCH of a call: under the flag `opts` is the `base` of a vits_synth_opts_pitch, whose last field is read only then
-static int pitch_req_opts(const vits_model* v, const vits_synth_opts* opts, PitchReq* q) {
-  q->on = false;
-  if (!opts) return VITS_OK;
-  TRY(pitch_flags_check(opts->flags, VITS_FLAG_PITCH, VITS_FLAG_PITCH_FORMANT, "VITS"));
-  if (!(opts->flags & VITS_FLAG_PITCH)) return VITS_OK;
-  static_assert(offsetof(vits_synth_opts_pitch, base) == 0, "the extended options begin with the plain ones");
-  return pitch_req(v, reinterpret_cast<const vits_synth_opts_pitch*>(opts)->pitch_semitones, (opts->flags & VITS_FLAG_PITCH_FORMANT) != 0, q);
-}
-
-// The tail of a flagged vits_synthesize* call behind the decoder: pitch, resample, normalise, conversion, as launches on `stream` from
-// the float native-rate waveform x [B, S] on the device (item b is len_y[b] * hop samples, h_len[b] on the host).  The buffers are the
-// call's own (freed with the PitchTail); *d_out is [B, *So] of float or int16.
-struct PitchTail {
-  std::vector<void*> bufs;
-  ~PitchTail() { for (void* p : bufs) hipFree(p); }
-  void* alloc(size_t bytes) {
-    void* p = nullptr;
-    if (hipMalloc(&p, bytes ? bytes : 1) != hipSuccess) { (void)hipGetLastError(); return nullptr; }
-    bufs.push_back(p);
-    return p;
-  }
-};
-static int pitch_tail_run(PitchTail& pt, vits_session* s, hipStream_t stream, const float* x, long long S, const int* len_y, int hop,
-                          const long long* h_len, int B, const PitchReq& pq, const ResampleTab* T, const NormReq& lq, bool pcm, float pcm_scale,
-                          const void** d_out, long long* So_out, std::vector<float>* loud_res) {
-  const int device = s->m->device;
-  float* d_p = static_cast<float*>(pt.alloc(sizeof(float) * (size_t)B * S));
-  if (!d_p) return fail(VITS_ERR_NOMEM, "pitch: device alloc failed");
-  TRY(pitch_run(device, stream, x, S, S, len_y, hop, h_len, B, pq.P, pq.Q, pq.formant, d_p, S, S, nullptr, 0));
-  const long long So = T ? T->P.n_out(S) : S;
-  const size_t esz = pcm ? sizeof(int16_t) : sizeof(float);
-  *So_out = So;
-  *d_out = d_p;
-  if (lq.on()) {
-    const float* x2 = d_p;
-    if (T) {
-      float* d_y = static_cast<float*>(pt.alloc(sizeof(float) * (size_t)B * So));
-      if (!d_y) return fail(VITS_ERR_NOMEM, "pitch: device alloc failed");
-      resample_launch<float>(stream, *T, d_p, S, 0, S, len_y, hop, B, d_y, So, 0, So, 1.f, nullptr);
-      x2 = d_y;
-    }
-    char* d_scr = static_cast<char*>(pt.alloc(norm_scratch_bytes(lq, B, So)));
-    void* d_n = pt.alloc(esz * (size_t)B * So);
-    if (!d_scr || !d_n) return fail(VITS_ERR_NOMEM, "pitch: device alloc failed");
-    NormScratch NS;
-    norm_scratch_layout(lq, B, So, d_scr, &NS);
-    const int rL = T ? T->P.L : 1, rM = T ? T->P.M : 1;
-    if (pcm) norm_launch<int16_t>(stream, lq, NS, x2, So, So, len_y, hop, rL, rM, B, static_cast<int16_t*>(d_n), So, So, pcm_scale, s);
-    else norm_launch<float>(stream, lq, NS, x2, So, So, len_y, hop, rL, rM, B, static_cast<float*>(d_n), So, So, 1.f, s);
-    loud_res->resize((size_t)B * 4);
-    hipMemcpyAsync(loud_res->data(), NS.LS.res, sizeof(float) * loud_res->size(), hipMemcpyDeviceToHost, stream);
-    *d_out = d_n;
-  } else if (T) {
-    void* d_y = pt.alloc(esz * (size_t)B * So);
-    if (!d_y) return fail(VITS_ERR_NOMEM, "pitch: device alloc failed");
-    if (pcm) resample_launch<int16_t>(stream, *T, d_p, S, 0, S, len_y, hop, B, static_cast<int16_t*>(d_y), So, 0, So, pcm_scale, nullptr);
-    else resample_launch<float>(stream, *T, d_p, S, 0, S, len_y, hop, B, static_cast<float*>(d_y), So, 0, So, 1.f, nullptr);
-    *d_out = d_y;
-  } else if (pcm) {
-    int16_t* d_pcm = static_cast<int16_t*>(pt.alloc(sizeof(int16_t) * (size_t)B * S));
-    if (!d_pcm) return fail(VITS_ERR_NOMEM, "pitch: device alloc failed");
-    hipLaunchKernelGGL(pcm16_kernel, dim3(cdiv((int)S, 256), B), dim3(256), 0, stream, d_p, S, d_pcm, S, S, pcm_scale, (const SynthDev*)nullptr);
-    *d_out = d_pcm;
-  }
+  q->on = true; q->P = P; q->Q = Q; q->formant = formant; q->semitones = semitones;
   return VITS_OK;
 }
 
@@ -670,16 +595,12 @@ enum PitchDoor { PT_DOOR_SHIFT, PT_DOOR_STRETCH, PT_DOOR_GAIN };
 static int pitch_op(int device, const float* x, const int64_t* lengths, int32_t B, int64_t N, float semitones, float* y, PitchDoor door,
                     bool formant) {
   const bool stretch = door == PT_DOOR_STRETCH;
-  if (!x || !lengths || !y || B <= 0 || B > 65535 || N <= 0 || N >= (1LL << 31)) return fail(VITS_ERR_ARG, "pitch: bad argument");
+  if (!y) return fail(VITS_ERR_ARG, "pitch: bad argument");
+  std::vector<int> len32;
+  TRY(op_items_check("pitch", x, lengths, B, N, &len32, "N = "));
   int P = 1, Q = 1;
   TRY(pitch_plan(semitones, &P, &Q));
-  std::vector<int> len32(B);
-  std::vector<long long> len64(B);
-  for (int b = 0; b < B; ++b) {
-    if (lengths[b] < 0 || lengths[b] > N) return fail(VITS_ERR_ARG, "pitch: length %lld of item %d outside [0, N = %lld]", (long long)lengths[b], b, (long long)N);
-    len32[b] = (int)lengths[b];
-    len64[b] = lengths[b];
-  }
+  const std::vector<long long> len64(lengths, lengths + B);
   if (P == Q) {
     if (stretch) return fail(VITS_ERR_ARG, "pitch: %g semitones is the identity (P = Q): there is no stretch to return", (double)semitones);
     if (door == PT_DOOR_GAIN) return fail(VITS_ERR_ARG, "pitch: %g semitones is the identity (P = Q): there is no gain to return", (double)semitones);

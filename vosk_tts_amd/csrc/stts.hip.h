@@ -1101,80 +1101,58 @@ static int stts_synthesize_impl(stts_model* m, const int64_t* ids, int32_t Tx, c
   return VITS_OK;
 }
 
-// a call's audio [B, S] (library-owned, items of lengths[b] samples) replaced by its copy at `rate` (vits_op_resample: the finished
-// waveform crosses the host once more, as it does for every multistream request at another rate)
-static int stts_resample_out(stts_model* m, int rate, int B, float** audio, int64_t* S, int64_t* lengths) {
-  ResamplePlan P;
-  TRY(resample_plan(m->vocoder->hp.sampling_rate, rate, &P));
-  const int64_t So = P.n_out(*S);
-  float* y = static_cast<float*>(malloc(sizeof(float) * (size_t)B * (So ? So : 1)));
-  if (!y) return fail(VITS_ERR_NOMEM, "host alloc failed");
-  const int rc = *S > 0 ? vits_op_resample(m->base.device, *audio, lengths, B, *S, m->vocoder->hp.sampling_rate, rate, y) : VITS_OK;
-  if (rc != VITS_OK) { free(y); return rc; }
-  free(*audio);
-  *audio = y; *S = So;
-  for (int b = 0; b < B; ++b) lengths[b] = P.n_out(lengths[b]);
-  return VITS_OK;
-}
-
-// STTS_FLAG_LOUDNESS of a call (include/vits_loudness.h): under the flag `opts` is the `base` of a stts_synth_opts_loudness, whose five
-// fields are read only then.  `rate` is the rate the call returns (0: the vocoder's own).  Checked before anything is synthesised: a
-// refusal costs nothing.
-static int stts_loud_arg(const stts_model* m, const stts_synth_opts* opts, int rate, NormReq* q) {
-  *q = NormReq();
-  if (!opts || !(opts->flags & (STTS_FLAG_LOUDNESS | STTS_FLAG_LIMIT))) return VITS_OK;
-  if (!m->vocoder) return fail(VITS_ERR_ARG, "no vocoder attached");
-  static_assert(offsetof(stts_synth_opts_loudness, base) == 0, "the extended options begin with the plain ones");
-  const stts_synth_opts_loudness* lo = reinterpret_cast<const stts_synth_opts_loudness*>(opts);
-  const int r = rate ? rate : m->vocoder->hp.sampling_rate;
-  if (opts->flags & STTS_FLAG_LOUDNESS)
-    TRY(loud_req(true, lo->loudness_mode, lo->loudness_target, lo->loudness_ceiling, lo->out_loudness, lo->out_gain, r, &q->loud));
-  if (opts->flags & STTS_FLAG_LIMIT) {  // (include/vits_limit.h: the six fields behind stts_synth_opts_pitch, read only under the flag)
-    static_assert(offsetof(stts_synth_opts_limit, base) == 0 && offsetof(stts_synth_opts_pitch, base) == 0, "the extended options begin with the plain ones");
-    const stts_synth_opts_limit* mo = reinterpret_cast<const stts_synth_opts_limit*>(opts);
-    TRY(lim_req(true, mo->limit_mode, mo->limit_ceiling, mo->limit_lookahead_ms, mo->limit_release_ms, mo->limit_gain, mo->out_reduction, r,
-                q->loud.on ? lo->loudness_ceiling : 0.f, q));
+// The output tail of a multistream call (out_tail.hip.h) on its finished audio [B, *S] (library-owned, items of lengths[b] samples), in
+// the order of tail_run: shifted in place at the native rate, replaced by its copy at q.rate, normalised and / or limited in place.
+// (It crosses the host through the parity doors' kernels; running it on the device behind the vocoder would be a speed change of its own.)
+static int stts_tail_host(stts_model* m, const TailReq& q, int B, float** audio, int64_t* S, int64_t* lengths) {
+  const int device = m->base.device;
+  if (q.pitch.on && *S > 0) {
+    std::vector<float> y((size_t)B * *S);
+    TRY(pitch_op(device, *audio, lengths, B, *S, q.pitch.semitones, y.data(), PT_DOOR_SHIFT, q.pitch.formant));
+    memcpy(*audio, y.data(), sizeof(float) * y.size());
   }
-  return VITS_OK;
-}
-// a call's audio [B, S] (library-owned, items of lengths[b] samples) normalised in place: last in the order decode, clamp, denoise,
-// resample, normalise, on the finished waveform (the kernels of vits_op_loudness_normalize; like stts_resample_out, it crosses the host
-// once more)
-static int stts_loud_out(stts_model* m, const NormReq& q, int B, float* audio, int64_t S, const int64_t* lengths) {
-  if (!q.on()) return VITS_OK;
-  std::vector<float> loud(B, -INFINITY), gain(B, 1.f), red(B, 1.f);
-  if (S > 0 && q.lim.on)  // (include/vits_limit.h: the kernels of vits_op_limit / vits_op_loudness_limit)
-    TRY(lim_op(m->base.device, audio, lengths, B, S, q.lim.rate, &q.lim.prm, q.loud.on, q.loud.prm.target, nullptr, nullptr, audio, red.data(),
-               loud.data(), gain.data()));
-  else if (S > 0) TRY(loud_op(m->base.device, audio, lengths, B, S, q.loud.P.rate, q.loud.prm, audio, loud.data(), nullptr, gain.data()));
-  for (int b = 0; b < B; ++b) {
-    if (q.loud.on && q.loud.out_loudness) q.loud.out_loudness[b] = loud[b];
-    if (q.loud.on && q.loud.out_gain) q.loud.out_gain[b] = gain[b];
-    if (q.lim.on && q.lim.out_reduction) q.lim.out_reduction[b] = red[b];
+  if (q.rate) {
+    const int native = m->vocoder->hp.sampling_rate;
+    ResamplePlan P;
+    TRY(resample_plan(native, q.rate, &P));
+    const int64_t So = P.n_out(*S);
+    float* y = static_cast<float*>(malloc(sizeof(float) * (size_t)B * (So ? So : 1)));
+    if (!y) return fail(VITS_ERR_NOMEM, "host alloc failed");
+    const int rc = *S > 0 ? vits_op_resample(device, *audio, lengths, B, *S, native, q.rate, y) : VITS_OK;
+    if (rc != VITS_OK) { free(y); return rc; }
+    free(*audio);
+    *audio = y; *S = So;
+    for (int b = 0; b < B; ++b) lengths[b] = P.n_out(lengths[b]);
+  }
+  if (q.norm.on()) {
+    const LoudReq& lo = q.norm.loud;
+    const LimReq& li = q.norm.lim;
+    std::vector<float> loud(B, -INFINITY), gain(B, 1.f), red(B, 1.f);
+    if (*S > 0 && li.on)  // (the kernels of vits_op_limit / vits_op_loudness_limit)
+      TRY(lim_op(device, *audio, lengths, B, *S, li.rate, &li.prm, lo.on, lo.prm.target, nullptr, nullptr, *audio, red.data(), loud.data(), gain.data()));
+    else if (*S > 0) TRY(loud_op(device, *audio, lengths, B, *S, lo.P.rate, lo.prm, *audio, loud.data(), nullptr, gain.data()));
+    for (int b = 0; b < B; ++b) {
+      if (lo.on && lo.out_loudness) lo.out_loudness[b] = loud[b];
+      if (lo.on && lo.out_gain) lo.out_gain[b] = gain[b];
+      if (li.on && li.out_reduction) li.out_reduction[b] = red[b];
+    }
   }
   return VITS_OK;
 }
 
-// STTS_FLAG_PITCH of a call (include/vits_pitch.h): under the flag `opts` is the `base.base` of a stts_synth_opts_pitch, whose last field
-// is read only then; STTS_FLAG_PITCH_FORMANT rides on it.  Checked before anything is synthesised.
-static int stts_pitch_arg(const stts_model* m, const stts_synth_opts* opts, PitchReq* q, float* semitones) {
-  q->on = false;
-  if (!opts) return VITS_OK;
-  TRY(pitch_flags_check(opts->flags, STTS_FLAG_PITCH, STTS_FLAG_PITCH_FORMANT, "STTS"));
-  if (!(opts->flags & STTS_FLAG_PITCH)) return VITS_OK;
-  if (!m->vocoder) return fail(VITS_ERR_ARG, "no vocoder attached");
-  static_assert(offsetof(stts_synth_opts_pitch, base) == 0, "the extended options begin with the plain ones");
-  *semitones = reinterpret_cast<const stts_synth_opts_pitch*>(opts)->pitch_semitones;
-  return pitch_req(m->vocoder, *semitones, (opts->flags & STTS_FLAG_PITCH_FORMANT) != 0, q);
-}
-// a call's native-rate audio [B, S] (items of lengths[b] samples) shifted in place: behind the denoiser and before the resampler (the
-// kernels of vits_op_pitch_shift; like stts_resample_out, it crosses the host once more)
-static int stts_pitch_out(stts_model* m, const PitchReq& q, float semitones, int B, float* audio, int64_t S, const int64_t* lengths) {
-  if (!q.on || S <= 0) return VITS_OK;
-  std::vector<float> y((size_t)B * S);
-  TRY(pitch_op(m->base.device, audio, lengths, B, S, semitones, y.data(), PT_DOOR_SHIFT, q.formant));
-  memcpy(audio, y.data(), sizeof(float) * y.size());
-  return VITS_OK;
+// The single-utterance entry points: the tail's request first (a refusal costs nothing), the call, then the tail on its audio.
+// rate / mk: of the marks call (0 / null without).
+static int stts_synthesize_tail(stts_model* m, const int64_t* ids, int32_t Tx, const float* scales, int64_t sid, const float* bert, const float* pde,
+                                const stts_synth_opts* opts, int rate, float** out_audio, int64_t* out_samples, float** out_mel, int64_t* out_frames,
+                                const SttsMarks* mk) {
+  TailReq q;
+  if (out_audio) TRY(tail_req(m->vocoder, tail_fields_stts(opts), rate, false, 1.f, &q));
+  TRY(stts_synthesize_impl(m, ids, Tx, scales, sid, bert, pde, opts, out_audio, out_samples, out_mel, out_frames, mk));
+  if (!out_audio) return VITS_OK;
+  int64_t len = *out_samples;
+  const int rc = stts_tail_host(m, q, 1, out_audio, out_samples, &len);
+  if (rc != VITS_OK) { free(*out_audio); *out_audio = nullptr; if (out_mel) { free(*out_mel); *out_mel = nullptr; } }
+  return rc;
 }
 
 extern "C" {
@@ -1182,19 +1160,7 @@ extern "C" {
 int stts_synthesize(stts_model* m, const int64_t* ids, int32_t Tx, const float* scales, int64_t sid, const float* bert, const float* pde,
                     const stts_synth_opts* opts, float** out_audio, int64_t* out_samples, float** out_mel, int64_t* out_frames) {
   if (!m) return fail(VITS_ERR_ARG, "bad argument");
-  NormReq lq;
-  PitchReq pq;
-  float pst = 0.f;
-  if (out_audio) TRY(stts_loud_arg(m, opts, 0, &lq));
-  if (out_audio) TRY(stts_pitch_arg(m, opts, &pq, &pst));
-  TRY(stts_synthesize_impl(m, ids, Tx, scales, sid, bert, pde, opts, out_audio, out_samples, out_mel, out_frames, nullptr));
-  if (lq.on() || pq.on) {
-    const int64_t len = *out_samples;
-    int rc = stts_pitch_out(m, pq, pst, 1, *out_audio, len, &len);
-    if (rc == VITS_OK) rc = stts_loud_out(m, lq, 1, *out_audio, len, &len);
-    if (rc != VITS_OK) { free(*out_audio); *out_audio = nullptr; if (out_mel) { free(*out_mel); *out_mel = nullptr; } return rc; }
-  }
-  return VITS_OK;
+  return stts_synthesize_tail(m, ids, Tx, scales, sid, bert, pde, opts, 0, out_audio, out_samples, out_mel, out_frames, nullptr);
 }
 
 int stts_synthesize_marks(stts_model* m, const int64_t* ids, int32_t Tx, const float* scales, int64_t sid, const float* bert, const float* pde,
@@ -1204,33 +1170,14 @@ int stts_synthesize_marks(stts_model* m, const int64_t* ids, int32_t Tx, const f
   SttsMarks mk;
   int rate = 0;
   TRY(stts_marks_arg(m, token_ends, sample_rate, &mk, &rate));
-  NormReq lq;
-  if (out_audio) TRY(stts_loud_arg(m, opts, rate, &lq));
-  PitchReq pq;
-  float pst = 0.f;
-  if (out_audio) TRY(stts_pitch_arg(m, opts, &pq, &pst));
-  TRY(stts_synthesize_impl(m, ids, Tx, scales, sid, bert, pde, opts, out_audio, out_samples, out_mel, out_frames, &mk));
-  if (out_audio) {
-    int64_t len = *out_samples;
-    int rc = stts_pitch_out(m, pq, pst, 1, *out_audio, len, &len);
-    if (rc == VITS_OK && rate) rc = stts_resample_out(m, rate, 1, out_audio, out_samples, &len);
-    if (rc == VITS_OK) rc = stts_loud_out(m, lq, 1, *out_audio, *out_samples, &len);
-    if (rc != VITS_OK) { free(*out_audio); *out_audio = nullptr; if (out_mel) { free(*out_mel); *out_mel = nullptr; } return rc; }
-  }
-  return VITS_OK;
+  return stts_synthesize_tail(m, ids, Tx, scales, sid, bert, pde, opts, rate, out_audio, out_samples, out_mel, out_frames, &mk);
 }
 
 int stts_stream_open(stts_model* m, const int64_t* ids, int32_t Tx, const float* scales, int64_t sid, const float* bert, const float* pde,
                      const stts_synth_opts* opts, int32_t chunk_frames, vits_stream** out, int64_t* total_samples) {
   if (!m || !out || chunk_frames <= 0) return fail(VITS_ERR_ARG, "bad argument");
   if (!m->vocoder) return fail(VITS_ERR_ARG, "no vocoder attached");
-  if (opts && (opts->flags & STTS_FLAG_LOUDNESS))
-    return fail(VITS_ERR_UNSUPPORTED, "STTS_FLAG_LOUDNESS on a stream: an integrated-loudness or peak target needs the whole utterance before the first chunk");
-  if (opts && (opts->flags & STTS_FLAG_LIMIT))
-    return fail(VITS_ERR_UNSUPPORTED, "STTS_FLAG_LIMIT on a stream: the limiter's look-ahead and its loudness passes need the whole utterance before the first chunk");
-  if (opts) TRY(pitch_flags_check(opts->flags, STTS_FLAG_PITCH, STTS_FLAG_PITCH_FORMANT, "STTS"));
-  if (opts && (opts->flags & STTS_FLAG_PITCH))
-    return fail(VITS_ERR_UNSUPPORTED, "STTS_FLAG_PITCH on a stream: the phase recursion needs the frames before a chunk, and its state is not carried across chunks");
+  if (opts) TRY(tail_refuse_stream(opts->flags, TAIL_STTS));
   float* mel = nullptr;
   int64_t frames = 0;
   std::vector<int64_t> ends(Tx > 0 ? Tx : 0);  // recorded for vits_stream_marks (native rate: this open has no other)
@@ -1367,20 +1314,23 @@ static int stts_synthesize_batch_impl(stts_model* m, const int64_t* ids, const i
   return VITS_OK;
 }
 
+// the batch entry points, as stts_synthesize_tail
+static int stts_synthesize_batch_tail(stts_model* m, const int64_t* ids, const int64_t* lengths, int32_t B, int32_t Tx, const float* scales,
+                                      const int64_t* sid, const float* bert, const float* pde, const stts_synth_opts* opts, int rate,
+                                      float** out_audio, int64_t* out_samples, int64_t* out_lengths, const SttsMarks* mk) {
+  TailReq q;
+  TRY(tail_req(m->vocoder, tail_fields_stts(opts), rate, false, 1.f, &q));
+  TRY(stts_synthesize_batch_impl(m, ids, lengths, B, Tx, scales, sid, bert, pde, opts, out_audio, out_samples, out_lengths, mk));
+  const int rc = stts_tail_host(m, q, B, out_audio, out_samples, out_lengths);
+  if (rc != VITS_OK) { free(*out_audio); *out_audio = nullptr; }
+  return rc;
+}
+
 int stts_synthesize_batch(stts_model* m, const int64_t* ids, const int64_t* lengths, int32_t B, int32_t Tx, const float* scales,
                           const int64_t* sid, const float* bert, const float* pde, const stts_synth_opts* opts, float** out_audio,
                           int64_t* out_samples, int64_t* out_lengths) {
   if (!m) return fail(VITS_ERR_ARG, "bad argument");
-  NormReq lq;
-  TRY(stts_loud_arg(m, opts, 0, &lq));
-  PitchReq pq;
-  float pst = 0.f;
-  TRY(stts_pitch_arg(m, opts, &pq, &pst));
-  TRY(stts_synthesize_batch_impl(m, ids, lengths, B, Tx, scales, sid, bert, pde, opts, out_audio, out_samples, out_lengths, nullptr));
-  int rc = stts_pitch_out(m, pq, pst, B, *out_audio, *out_samples, out_lengths);
-  if (rc == VITS_OK) rc = stts_loud_out(m, lq, B, *out_audio, *out_samples, out_lengths);
-  if (rc != VITS_OK) { free(*out_audio); *out_audio = nullptr; }
-  return rc;
+  return stts_synthesize_batch_tail(m, ids, lengths, B, Tx, scales, sid, bert, pde, opts, 0, out_audio, out_samples, out_lengths, nullptr);
 }
 
 int stts_synthesize_batch_marks(stts_model* m, const int64_t* ids, const int64_t* lengths, int32_t B, int32_t Tx, const float* scales,
@@ -1390,17 +1340,7 @@ int stts_synthesize_batch_marks(stts_model* m, const int64_t* ids, const int64_t
   SttsMarks mk;
   int rate = 0;
   TRY(stts_marks_arg(m, token_ends, sample_rate, &mk, &rate));
-  NormReq lq;
-  TRY(stts_loud_arg(m, opts, rate, &lq));
-  PitchReq pq;
-  float pst = 0.f;
-  TRY(stts_pitch_arg(m, opts, &pq, &pst));
-  TRY(stts_synthesize_batch_impl(m, ids, lengths, B, Tx, scales, sid, bert, pde, opts, out_audio, out_samples, out_lengths, &mk));
-  int rc = stts_pitch_out(m, pq, pst, B, *out_audio, *out_samples, out_lengths);
-  if (rc == VITS_OK && rate) rc = stts_resample_out(m, rate, B, out_audio, out_samples, out_lengths);
-  if (rc == VITS_OK) rc = stts_loud_out(m, lq, B, *out_audio, *out_samples, out_lengths);
-  if (rc != VITS_OK) { free(*out_audio); *out_audio = nullptr; }
-  return rc;
+  return stts_synthesize_batch_tail(m, ids, lengths, B, Tx, scales, sid, bert, pde, opts, rate, out_audio, out_samples, out_lengths, &mk);
 }
 
 }  // extern "C"

@@ -1,0 +1,41 @@
+"""The extension feeds of the output tail (pitch -> resample -> normalise / limit, DESIGN.md "Output tail"), read once for both session
+types: what a request's feed asks of the loudness, limiter and pitch stages, checked before any device work.  `lib` is the session's
+library: a stage the loaded library does not export is refused here (its _need_* check)."""
+from .capi import limit_spec, loudness_spec, pitch_spec
+
+
+def loudness_from_feed(lib, feed):
+    """"vits.loudness" (LUFS target), "vits.peak" (peak target) and "vits.peak_ceiling" -> capi.loudness_spec() (None = none); both
+    targets at once and values out of range are ValueError"""
+    limited = feed.get("vits.limit") is not None  # (then "vits.peak_ceiling" is the limiter's ceiling and the gain has no cap)
+    spec = loudness_spec(feed.get("vits.loudness"), feed.get("vits.peak"), 0.0 if limited else feed.get("vits.peak_ceiling"))
+    if spec is not None:
+        lib._need_loudness()
+    return spec
+
+
+def limit_from_feed(lib, feed):
+    """"vits.limit" ("sample" or "true"), "vits.limit_lookahead_ms", "vits.limit_release_ms" and, as the limiter's ceiling,
+    "vits.peak_ceiling" -> capi.limit_spec() (None = none; include/vits_limit.h); values out of range and a peak target next to a
+    limiter are ValueError"""
+    spec = limit_spec(feed.get("vits.limit"), feed.get("vits.peak_ceiling"), feed.get("vits.limit_lookahead_ms", 5.0),
+                      feed.get("vits.limit_release_ms", 50.0))
+    if spec is not None:
+        if feed.get("vits.peak") is not None:
+            raise ValueError("\"vits.peak\" with \"vits.limit\": a peak target leaves a limiter nothing to do (a LUFS target, or the limiter alone)")
+        lib._need_limit()
+    return spec
+
+
+def pitch_from_feed(lib, feed):
+    """"vits.pitch" (semitones in [-12, 12]; include/vits_pitch.h) and "vits.pitch_formants" (bool) -> (the shift as a float, or None
+    for none and for one that reduces to the identity; whether it keeps the spectral envelope).  The second modifies a shift: without
+    one in effect it is False, the request as it was.  A value out of range is ValueError"""
+    p = pitch_spec(feed.get("vits.pitch"))
+    if p is None:
+        return None, False
+    lib._need_pitch()
+    formants = bool(feed.get("vits.pitch_formants", False))
+    if formants:
+        lib._need_pitch_formant()
+    return p, formants

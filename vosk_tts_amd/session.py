@@ -18,7 +18,8 @@ import threading
 
 import numpy as np
 
-from .capi import VitsLib, limit_spec, loudness_spec, pitch_spec
+from .capi import VitsLib
+from .outopts import limit_from_feed, loudness_from_feed, pitch_from_feed
 
 log = logging.getLogger(__name__)
 
@@ -387,41 +388,10 @@ class VitsSession:
         return 0 if rate == self.hp.sampling_rate else rate
 
     def _loudness(self, feed):
-        """the extension feeds "vits.loudness" (LUFS target), "vits.peak" (peak target) and "vits.peak_ceiling" of a request ->
-        capi.loudness_spec() (None = none); both targets at once and values out of range are ValueError, before any device work"""
-        limited = feed.get("vits.limit") is not None  # (then "vits.peak_ceiling" is the limiter's ceiling and the gain has no cap)
-        spec = loudness_spec(feed.get("vits.loudness"), feed.get("vits.peak"), 0.0 if limited else feed.get("vits.peak_ceiling"))
-        if spec is not None:
-            self._lib._need_loudness()
-        return spec
+        return loudness_from_feed(self._lib, feed)
 
     def _limit(self, feed):
-        """the extension feeds "vits.limit" ("sample" or "true"), "vits.limit_lookahead_ms", "vits.limit_release_ms" and, as the
-        limiter's ceiling, "vits.peak_ceiling" -> capi.limit_spec() (None = none; include/vits_limit.h); values out of range and a peak
-        target next to a limiter are ValueError, before any device work"""
-        spec = limit_spec(feed.get("vits.limit"), feed.get("vits.peak_ceiling"), feed.get("vits.limit_lookahead_ms", 5.0),
-                          feed.get("vits.limit_release_ms", 50.0))
-        if spec is not None:
-            if feed.get("vits.peak") is not None:
-                raise ValueError("\"vits.peak\" with \"vits.limit\": a peak target leaves a limiter nothing to do (a LUFS target, or the limiter alone)")
-            self._lib._need_limit()
-        return spec
-
-    def _pitch(self, feed):
-        """the extension feed "vits.pitch" (semitones in [-12, 12]; include/vits_pitch.h) -> the shift as a float, or None for none and
-        for one that reduces to the identity; a value out of range is ValueError, before any device work"""
-        p = pitch_spec(feed.get("vits.pitch"))
-        if p is not None:
-            self._lib._need_pitch()
-        return p
-
-    def _formants(self, feed, pitch):
-        """the extension feed "vits.pitch_formants" (bool; VITS_FLAG_PITCH_FORMANT) -> whether the shift `pitch` (what _pitch returned)
-        keeps the spectral envelope.  It modifies a shift: without one in effect it is False, the request as it was"""
-        on = pitch is not None and bool(feed.get("vits.pitch_formants", False))
-        if on:
-            self._lib._need_pitch_formant()
-        return on
+        return limit_from_feed(self._lib, feed)
 
     @staticmethod
     def _pitch_kw(pitch, formants, limit=None):
@@ -441,8 +411,7 @@ class VitsSession:
         rate = self._rate(feed.get("vits.sample_rate"))
         marks = self._marks(feed)
         loud = self._loudness(feed)
-        pitch = self._pitch(feed)  # ("vits.pitch": the audio shifted by that many semitones, behind the decoder)
-        formants = self._formants(feed, pitch)
+        pitch, formants = pitch_from_feed(self._lib, feed)  # ("vits.pitch": the audio shifted by that many semitones, behind the decoder)
         limit = self._limit(feed)  # ("vits.limit": the look-ahead peak limiter with the loudness gain, or alone; include/vits_limit.h)
         n = self._coalescable(feed, ids)
         if n:
@@ -490,8 +459,7 @@ class VitsSession:
         rate = self._rate(sample_rate if sample_rate is not None else feed.get("vits.sample_rate"))
         marks = self._marks(feed)
         loud = self._loudness(feed)
-        pitch = self._pitch(feed)
-        formants = self._formants(feed, pitch)
+        pitch, formants = pitch_from_feed(self._lib, feed)
         limit = self._limit(feed)
         n = self._coalescable(feed, ids)
         if n:
@@ -528,7 +496,7 @@ class VitsSession:
         if self._limit(feed) is not None:
             raise ValueError("a stream cannot be limited: the limiter's look-ahead and its loudness passes need the whole utterance before the "
                              "first chunk (run() / run_pcm16() take \"vits.limit\")")
-        if self._pitch(feed) is not None:
+        if pitch_from_feed(self._lib, feed)[0] is not None:
             raise ValueError("a stream cannot be pitch-shifted: the phase recursion needs the frames before a chunk (run() / run_pcm16() "
                              "take \"vits.pitch\")")
         rate = self._rate(sample_rate if sample_rate is not None else feed.get("vits.sample_rate"))

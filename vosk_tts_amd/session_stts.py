@@ -9,8 +9,9 @@ import threading
 
 import numpy as np
 
-from .capi import VitsLib, limit_spec, loudness_spec, pitch_spec
+from .capi import VitsLib
 from .capi_stts import SttsModel
+from .outopts import limit_from_feed, loudness_from_feed, pitch_from_feed
 
 _INPUTS = ("input", "input_lengths", "scales", "sid", "bert", "phone_duration_extra")
 _EXT = ("vits.noise", "vits.seed", "vits.n_timesteps", "vits.sample_rate", "vits.denoiser_strength", "vits.denoiser_filter_length",
@@ -96,37 +97,15 @@ class SttsSession:
         return out, np.array([self._lib.out_samples(n, native, rate) for n in lengths], np.int64)
 
     def _loudness(self, feed):
-        """the extension feeds "vits.loudness" (LUFS target), "vits.peak" (peak target), "vits.peak_ceiling" -> capi.loudness_spec()
-        (None = none); both targets at once and values out of range are ValueError, before any device work"""
-        limited = feed.get("vits.limit") is not None  # (then "vits.peak_ceiling" is the limiter's ceiling and the gain has no cap)
-        spec = loudness_spec(feed.get("vits.loudness"), feed.get("vits.peak"), 0.0 if limited else feed.get("vits.peak_ceiling"))
-        if spec is not None:
-            self._lib._need_loudness()
-        return spec
+        return loudness_from_feed(self._lib, feed)
 
     def _limit(self, feed):
-        """the extension feeds "vits.limit" ("sample" or "true"), "vits.limit_lookahead_ms", "vits.limit_release_ms" and, as the
-        limiter's ceiling, "vits.peak_ceiling" -> capi.limit_spec() (None = none; include/vits_limit.h)"""
-        spec = limit_spec(feed.get("vits.limit"), feed.get("vits.peak_ceiling"), feed.get("vits.limit_lookahead_ms", 5.0),
-                          feed.get("vits.limit_release_ms", 50.0))
-        if spec is not None:
-            if feed.get("vits.peak") is not None:
-                raise ValueError("\"vits.peak\" with \"vits.limit\": a peak target leaves a limiter nothing to do (a LUFS target, or the limiter alone)")
-            self._lib._need_limit()
-        return spec
+        return limit_from_feed(self._lib, feed)
 
     def _pitch(self, feed):
-        """the extension feed "vits.pitch" (semitones in [-12, 12]; include/vits_pitch.h) -> the keyword for the model's calls: empty for
-        none and for a shift that reduces to the identity; a value out of range is ValueError, before any device work.  The feed
-        "vits.pitch_formants" (bool) adds preserve_formants to a shift"""
-        p = pitch_spec(feed.get("vits.pitch"))
-        if p is None:
-            return {}
-        self._lib._need_pitch()
-        if feed.get("vits.pitch_formants"):  # (STTS_FLAG_PITCH_FORMANT: modifies a shift, so it is read only with one in effect)
-            self._lib._need_pitch_formant()
-            return {"pitch": p, "preserve_formants": True}
-        return {"pitch": p}
+        """outopts.pitch_from_feed as the keywords of the model's calls: empty without a shift"""
+        p, formants = pitch_from_feed(self._lib, feed)
+        return {} if p is None else {"pitch": p, "preserve_formants": True} if formants else {"pitch": p}
 
     def normalize(self, audio, lengths, sample_rate, spec, limit=None):
         """audio float32 [B, S] at `sample_rate` Hz (None / 0 = the vocoder's own) with per-item sample counts -> the audio normalised
