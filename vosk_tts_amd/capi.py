@@ -427,6 +427,20 @@ class VitsLib:
         self._fn("debug_launch_dump")(buf, ctypes.c_size_t(len(buf)))
         return {k: int(n) for k, n in (line.rsplit(" ", 1) for line in buf.value.decode().splitlines())}
 
+    def _items_door(self, name, x, lengths, device, scalars, outs):
+        """One kernel-level door over B items: vits_<name>(device, x, lengths, B, N, *scalars, *outputs) with x float32 [B, N] and
+        lengths [B] checked here and float32 outputs of the shapes outs(B, N) -> the outputs (a lone one as itself)"""
+        x = _f32(x)
+        if x.ndim != 2:
+            raise ValueError("x must be [B, N]")
+        B, N = x.shape
+        lengths = _i64(lengths).reshape(-1)
+        if lengths.shape != (B,):
+            raise ValueError("lengths must be [B]")
+        ys = [np.empty(shape, np.float32) for shape in outs(B, N)]
+        self.check(self._fn(name)(device, _p(x, c_f32p), _p(lengths, c_i64p), B, N, *scalars, *[_p(y, c_f32p) for y in ys]))
+        return ys[0] if len(ys) == 1 else tuple(ys)
+
     # ---- output sample rate (include/vits_resample.h) -----------------------
     def _need_resample(self):
         if not self.has_resample:
@@ -456,16 +470,8 @@ class VitsLib:
     def op_resample(self, x, lengths, rate_in, rate_out, device=0):
         """vits_op_resample: x float32 [B, N], lengths [B] -> y float32 [B, ceil(N*L/M)]; item b from x[b, :lengths[b]] only"""
         self._need_resample()
-        x = _f32(x)
-        if x.ndim != 2:
-            raise ValueError("x must be [B, N]")
-        B, N = x.shape
-        lengths = _i64(lengths).reshape(-1)
-        if lengths.shape != (B,):
-            raise ValueError("lengths must be [B]")
-        y = np.empty((B, self.out_samples(N, rate_in, rate_out)), np.float32)
-        self.check(self._fn("op_resample")(device, _p(x, c_f32p), _p(lengths, c_i64p), B, N, int(rate_in), int(rate_out), _p(y, c_f32p)))
-        return y
+        return self._items_door("op_resample", x, lengths, device, (int(rate_in), int(rate_out)),
+                                lambda B, N: [(B, self.out_samples(N, rate_in, rate_out))])
 
     # ---- vocoder-bias denoiser (include/vits_denoise.h) ---------------------
     def _need_denoise(self):
@@ -476,21 +482,12 @@ class VitsLib:
         """vits_op_denoise: x float32 [B, N], lengths [B], bias [filter_length / 2 + 1] -> y float32 [B, hop * (N // hop)], hop =
         filter_length / 4; item b from x[b, :lengths[b]] only, zero at and beyond hop * (lengths[b] // hop)"""
         self._need_denoise()
-        x = _f32(x)
-        if x.ndim != 2:
-            raise ValueError("x must be [B, N]")
-        B, N = x.shape
-        lengths = _i64(lengths).reshape(-1)
-        if lengths.shape != (B,):
-            raise ValueError("lengths must be [B]")
         n = int(filter_length)
         bias = _f32(bias).reshape(-1)
         if 0 < n <= 4096 and bias.shape[0] != n // 2 + 1:  # (a filter length the library refuses is refused there, by name)
             raise ValueError(f"bias must hold filter_length / 2 + 1 = {n // 2 + 1} values")
         hop = max(n // 4, 1)
-        y = np.empty((B, hop * (N // hop)), np.float32)
-        self.check(self._fn("op_denoise")(device, _p(x, c_f32p), _p(lengths, c_i64p), B, N, _p(bias, c_f32p), n, float(strength), _p(y, c_f32p)))
-        return y
+        return self._items_door("op_denoise", x, lengths, device, (_p(bias, c_f32p), n, float(strength)), lambda B, N: [(B, hop * (N // hop))])
 
     # ---- loudness normalisation (include/vits_loudness.h) --------------------
     def _need_loudness(self):
@@ -505,35 +502,17 @@ class VitsLib:
         self.check(self._fn("loudness_plan")(int(rate), sos.ctypes.data_as(ctypes.POINTER(ctypes.c_double)), ctypes.byref(hop)))
         return sos, hop.value
 
-    def _loud_args(self, x, lengths):
-        x = _f32(x)
-        if x.ndim != 2:
-            raise ValueError("x must be [B, N]")
-        lengths = _i64(lengths).reshape(-1)
-        if lengths.shape != (x.shape[0],):
-            raise ValueError("lengths must be [B]")
-        return x, lengths
-
     def op_loudness(self, x, lengths, rate, device=0):
         """vits_op_loudness: x float32 [B, N], lengths [B] -> (loudness float32 [B] in LUFS, -inf for silence; peak float32 [B]);
         item b from x[b, :lengths[b]] only"""
         self._need_loudness()
-        x, lengths = self._loud_args(x, lengths)
-        B, N = x.shape
-        loud, peak = np.empty(B, np.float32), np.empty(B, np.float32)
-        self.check(self._fn("op_loudness")(device, _p(x, c_f32p), _p(lengths, c_i64p), B, N, int(rate), _p(loud, c_f32p), _p(peak, c_f32p)))
-        return loud, peak
+        return self._items_door("op_loudness", x, lengths, device, (int(rate),), lambda B, N: [(B,), (B,)])
 
     def op_loudness_normalize(self, x, lengths, rate, mode, target, ceiling=0.0, device=0):
         """vits_op_loudness_normalize -> (y float32 [B, N] = gain[b] * x[b], zero at and beyond lengths[b]; loudness [B]; gain [B])"""
         self._need_loudness()
-        x, lengths = self._loud_args(x, lengths)
-        B, N = x.shape
-        y = np.empty((B, N), np.float32)
-        loud, gain = np.empty(B, np.float32), np.empty(B, np.float32)
-        self.check(self._fn("op_loudness_normalize")(device, _p(x, c_f32p), _p(lengths, c_i64p), B, N, int(rate), int(mode), float(target),
-                                                     float(ceiling), _p(y, c_f32p), _p(loud, c_f32p), _p(gain, c_f32p)))
-        return y, loud, gain
+        return self._items_door("op_loudness_normalize", x, lengths, device, (int(rate), int(mode), float(target), float(ceiling)),
+                                lambda B, N: [(B, N), (B,), (B,)])
 
     # ---- look-ahead peak limiter (include/vits_limit.h) ------------------------
     def _need_limit(self):
@@ -551,44 +530,28 @@ class VitsLib:
         """vits_op_true_peak: x float32 [B, N], lengths [B] -> the 4x oversampled peak of every item, float32 [B]; item b from
         x[b, :lengths[b]] only"""
         self._need_limit()
-        x, lengths = self._loud_args(x, lengths)
-        B, N = x.shape
-        tp = np.empty(B, np.float32)
-        self.check(self._fn("op_true_peak")(device, _p(x, c_f32p), _p(lengths, c_i64p), B, N, int(rate), _p(tp, c_f32p)))
-        return tp
+        return self._items_door("op_true_peak", x, lengths, device, (int(rate),), lambda B, N: [(B,)])
 
     def op_limit_gain(self, x, lengths, rate, mode, ceiling, lookahead_ms=5.0, release_ms=50.0, gain=1.0, device=0):
         """vits_op_limit_gain -> s float32 [B, N]: the limiter's gain curve, 1 at and beyond lengths[b]"""
         self._need_limit()
-        x, lengths = self._loud_args(x, lengths)
-        B, N = x.shape
-        s = np.empty((B, N), np.float32)
-        self.check(self._fn("op_limit_gain")(device, _p(x, c_f32p), _p(lengths, c_i64p), B, N, int(rate), int(mode), float(ceiling),
-                                             float(lookahead_ms), float(release_ms), float(gain), _p(s, c_f32p)))
-        return s
+        return self._items_door("op_limit_gain", x, lengths, device,
+                                (int(rate), int(mode), float(ceiling), float(lookahead_ms), float(release_ms), float(gain)), lambda B, N: [(B, N)])
 
     def op_limit(self, x, lengths, rate, mode, ceiling, lookahead_ms=5.0, release_ms=50.0, gain=1.0, device=0):
         """vits_op_limit -> (y float32 [B, N] = fp32(gain s) x, zero at and beyond lengths[b]; reduction float32 [B] = min s)"""
         self._need_limit()
-        x, lengths = self._loud_args(x, lengths)
-        B, N = x.shape
-        y, red = np.empty((B, N), np.float32), np.empty(B, np.float32)
-        self.check(self._fn("op_limit")(device, _p(x, c_f32p), _p(lengths, c_i64p), B, N, int(rate), int(mode), float(ceiling),
-                                        float(lookahead_ms), float(release_ms), float(gain), _p(y, c_f32p), _p(red, c_f32p)))
-        return y, red
+        return self._items_door("op_limit", x, lengths, device,
+                                (int(rate), int(mode), float(ceiling), float(lookahead_ms), float(release_ms), float(gain)),
+                                lambda B, N: [(B, N), (B,)])
 
     def op_loudness_limit(self, x, lengths, rate, target, mode, ceiling, lookahead_ms=5.0, release_ms=50.0, device=0):
         """vits_op_loudness_limit, the two-pass LUFS form -> (y float32 [B, N]; loudness [B] of the items as given; gain [B] = g_1;
         reduction [B] = min s of the last pass)"""
         self._need_limit()
-        x, lengths = self._loud_args(x, lengths)
-        B, N = x.shape
-        y = np.empty((B, N), np.float32)
-        loud, gain, red = np.empty(B, np.float32), np.empty(B, np.float32), np.empty(B, np.float32)
-        self.check(self._fn("op_loudness_limit")(device, _p(x, c_f32p), _p(lengths, c_i64p), B, N, int(rate), float(target), int(mode),
-                                                 float(ceiling), float(lookahead_ms), float(release_ms), _p(y, c_f32p), _p(loud, c_f32p),
-                                                 _p(gain, c_f32p), _p(red, c_f32p)))
-        return y, loud, gain, red
+        return self._items_door("op_loudness_limit", x, lengths, device,
+                                (int(rate), float(target), int(mode), float(ceiling), float(lookahead_ms), float(release_ms)),
+                                lambda B, N: [(B, N), (B,), (B,), (B,)])
 
     # ---- pitch-shifted output (include/vits_pitch.h) ---------------------------
     def _need_pitch(self):
@@ -610,11 +573,7 @@ class VitsLib:
     def op_pitch_shift(self, x, lengths, semitones, device=0, _door="op_pitch_shift"):
         """vits_op_pitch_shift: x float32 [B, N], lengths [B] -> y float32 [B, N]; item b from x[b, :lengths[b]] only, zero beyond"""
         self._need_pitch()
-        x, lengths = self._loud_args(x, lengths)
-        B, N = x.shape
-        y = np.empty((B, N), np.float32)
-        self.check(self._fn(_door)(device, _p(x, c_f32p), _p(lengths, c_i64p), B, N, float(semitones), _p(y, c_f32p)))
-        return y
+        return self._items_door(_door, x, lengths, device, (float(semitones),), lambda B, N: [(B, N)])
 
     def op_pitch_shift_formant(self, x, lengths, semitones, device=0):
         """vits_op_pitch_shift_formant: op_pitch_shift with the envelope correction (steps 3a-3d of include/vits_pitch.h)"""
@@ -630,21 +589,18 @@ class VitsLib:
         """vits_op_pitch_formant_gain: the gains of step 3d, float32 [B, N // 256 + 3, 513]; row f of item b is g_f for f < F_a[b], every
         other row exactly 0"""
         self._need_pitch_formant()
-        x, lengths = self._loud_args(x, lengths)
-        B, N = x.shape
-        g = np.empty((B, N // 256 + 3, PITCH_FRAME // 2 + 1), np.float32)
-        self.check(self._fn("op_pitch_formant_gain")(device, _p(x, c_f32p), _p(lengths, c_i64p), B, N, float(semitones), _p(g, c_f32p)))
-        return g
+        return self._items_door("op_pitch_formant_gain", x, lengths, device, (float(semitones),),
+                                lambda B, N: [(B, N // 256 + 3, PITCH_FRAME // 2 + 1)])
 
     def op_pitch_stretch(self, x, lengths, semitones, device=0, _door="op_pitch_stretch"):
         """vits_op_pitch_stretch: the vocoder's output before the resampler, float32 [B, 256 * (ceil((N // 256 + 2) * P / Q) - 1)]"""
         self._need_pitch()
-        x, lengths = self._loud_args(x, lengths)
-        B, N = x.shape
-        P, Q = self.pitch_plan(semitones)
-        y = np.empty((B, 256 * (-(-(N // 256 + 2) * P // Q) - 1)), np.float32)
-        self.check(self._fn(_door)(device, _p(x, c_f32p), _p(lengths, c_i64p), B, N, float(semitones), _p(y, c_f32p)))
-        return y
+
+        def outs(B, N):
+            P, Q = self.pitch_plan(semitones)
+            return [(B, 256 * (-(-(N // 256 + 2) * P // Q) - 1))]
+
+        return self._items_door(_door, x, lengths, device, (float(semitones),), outs)
 
     def mas_maximum_path(self, values, t_ys, t_xs, device=0):
         """monotonic_align.maximum_path_c (core.pyx:35-42): values float32 [B,T_y,T_x] -> paths int32 [B,T_y,T_x]."""

@@ -302,21 +302,16 @@ static int denoise_bias_get(vits_model* m, int n, const float** d_bias, const st
     TRY(denoise_get(m->device, n, &T));
     std::vector<float> z((size_t)hp.inter_channels * Tb, 0.f), audio((size_t)S), mag((size_t)M + 1);
     TRY(vits_stage_decoder(m, z.data(), 1, Tb, nullptr, audio.data(), nullptr));
-    HIP_TRY(hipSetDevice(m->device));
-    // frame 0 reads samples 0 .. n/2 only
-    float *dx = nullptr, *db = nullptr;
-    hipError_t e = hipMalloc((void**)&dx, sizeof(float) * (size_t)(M + 1));
-    if (e == hipSuccess) e = hipMalloc((void**)&db, sizeof(float) * (size_t)(M + 1));
-    if (e == hipSuccess) e = hipMemcpy(dx, audio.data(), sizeof(float) * (size_t)(M + 1), hipMemcpyHostToDevice);
-    if (e == hipSuccess) {
+    OpDoor d("denoise: bias", m->device);
+    float* dx = d.up(audio.data(), (size_t)(M + 1));  // frame 0 reads samples 0 .. n/2 only
+    float* db = d.dev<float>((size_t)(M + 1));
+    if (d.ok())
       hipLaunchKernelGGL(denoise_frames_kernel, dim3(1, 1), dim3(64 * DN_FPB), 0, nullptr, dx, 0, 0, (long long)(M + 1), nullptr, S, T->d_win, T->d_tw,
                          nullptr, 0.f, n, T->log2m, 0, 1, db, 0, 1);
-      e = hipGetLastError();
-    }
-    if (e == hipSuccess) e = hipDeviceSynchronize();
-    if (e == hipSuccess) e = hipMemcpy(mag.data(), db, sizeof(float) * (size_t)(M + 1), hipMemcpyDeviceToHost);
-    hipFree(dx);
-    if (e != hipSuccess) { hipFree(db); return fail(VITS_ERR_DEVICE, "denoise: bias: %s", hipGetErrorString(e)); }
+    d.finish();
+    d.down(mag.data(), db, (size_t)(M + 1));
+    if (!d.ok()) return d.rc();
+    d.bufs.release(db);  // the model's from here
     m->allocs.push_back(db);
     it = m->dn_bias.emplace(n, std::make_pair(std::move(mag), db)).first;
   }
@@ -362,27 +357,16 @@ int vits_op_denoise(int device, const float* x, const int64_t* lengths, int32_t 
   }
   const DenoiseTab* T = nullptr;
   TRY(denoise_get(device, n, &T));
-  HIP_TRY(hipSetDevice(device));
+  OpDoor d("denoise", device);
   const long long Ny = (long long)hop * (N / hop);
   const size_t sc = denoise_scratch_elems(n, Ny);
-  float *dx = nullptr, *dy = nullptr, *db = nullptr, *ds = nullptr;
-  int* dl = nullptr;
-  hipError_t e = hipMalloc((void**)&dx, sizeof(float) * (size_t)B * N);
-  if (e == hipSuccess) e = hipMalloc((void**)&dy, sizeof(float) * (size_t)B * Ny);
-  if (e == hipSuccess) e = hipMalloc((void**)&db, sizeof(float) * (size_t)(M + 1));
-  if (e == hipSuccess) e = hipMalloc((void**)&ds, sizeof(float) * (size_t)B * sc);
-  if (e == hipSuccess) e = hipMalloc((void**)&dl, sizeof(int) * B);
-  if (e == hipSuccess) e = hipMemcpy(dx, x, sizeof(float) * (size_t)B * N, hipMemcpyHostToDevice);
-  if (e == hipSuccess) e = hipMemcpy(db, bias, sizeof(float) * (size_t)(M + 1), hipMemcpyHostToDevice);
-  if (e == hipSuccess) e = hipMemcpy(dl, len32.data(), sizeof(int) * B, hipMemcpyHostToDevice);
-  if (e == hipSuccess) e = hipMemset(dy, 0xff, sizeof(float) * (size_t)B * Ny);  // NaN: an output the kernel does not write shows
-  if (e == hipSuccess) {
-    denoise_launch(nullptr, *T, dx, N, 0, N, dl, 1, B, db, strength, ds, (long long)sc, dy, Ny, 0, Ny);
-    e = hipGetLastError();
-  }
-  if (e == hipSuccess) e = hipDeviceSynchronize();
-  if (e == hipSuccess) e = hipMemcpy(y, dy, sizeof(float) * (size_t)B * Ny, hipMemcpyDeviceToHost);
-  hipFree(dx); hipFree(dy); hipFree(db); hipFree(ds); hipFree(dl);
-  if (e != hipSuccess) return fail(VITS_ERR_DEVICE, "denoise: %s", hipGetErrorString(e));
-  return VITS_OK;
+  float* dx = d.up(x, (size_t)B * N);
+  float* db = d.up(bias, (size_t)(M + 1));
+  int* dl = d.up(len32.data(), B);
+  float* ds = d.dev<float>(B * sc);
+  float* dy = d.out<float>((size_t)B * Ny);
+  if (d.ok()) denoise_launch(nullptr, *T, dx, N, 0, N, dl, 1, B, db, strength, ds, (long long)sc, dy, Ny, 0, Ny);
+  d.finish();
+  d.down(y, dy, (size_t)B * Ny);
+  return d.rc();
 }

@@ -121,6 +121,7 @@ static int persist_cfg() {
 #include "engine_convdbg.hip.h"
 #include "engine_launch.hip.h"
 #include "engine_stages.hip.h"
+#include "op_door.hip.h"
 #include "resample.hip.h"
 #include "denoise.hip.h"
 #include "loudness.hip.h"
@@ -457,24 +458,16 @@ int vits_mas_maximum_path(int device, const float* values, const int32_t* t_ys, 
   for (int b = 0; b < B; ++b)
     if (t_ys[b] < 0 || t_ys[b] > Ty || t_xs[b] < 0 || t_xs[b] > Tx) return fail(VITS_ERR_ARG, "extent out of range");
   if ((size_t)2 * Tx * sizeof(float) > 160 * 1024) return fail(VITS_ERR_ARG, "T_x %d too large for the LDS row buffers", Tx);
-  HIP_TRY(hipSetDevice(device));
-  const size_t n = (size_t)B * Ty * Tx;
-  float* d_v = nullptr; int *d_ty = nullptr, *d_tx = nullptr, *d_p = nullptr; unsigned char* d_d = nullptr;
-  struct Free { std::vector<void*> p; ~Free() { for (void* q : p) hipFree(q); } } fr;
-  auto alloc = [&](void** q, size_t bytes) { if (hipMalloc(q, bytes) != hipSuccess) return false; fr.p.push_back(*q); return true; };
-  if (!alloc((void**)&d_v, n * 4) || !alloc((void**)&d_p, n * 4) || !alloc((void**)&d_d, n) || !alloc((void**)&d_ty, B * 4) ||
-      !alloc((void**)&d_tx, B * 4))
-    return fail(VITS_ERR_NOMEM, "device alloc failed");
-  HIP_TRY(hipMemcpy(d_v, values, n * 4, hipMemcpyHostToDevice));
-  HIP_TRY(hipMemcpy(d_ty, t_ys, B * 4, hipMemcpyHostToDevice));
-  HIP_TRY(hipMemcpy(d_tx, t_xs, B * 4, hipMemcpyHostToDevice));
-  const size_t lds = (size_t)2 * Tx * sizeof(float);
-  if (lds > 64 * 1024) HIP_TRY(hipFuncSetAttribute((const void*)mas_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-  hipLaunchKernelGGL(mas_kernel, dim3(B), dim3(256), lds, 0, d_v, d_ty, d_tx, Ty, Tx, d_d, d_p);
-  hipError_t le = hipGetLastError();
-  if (le != hipSuccess) return fail(VITS_ERR_DEVICE, "launch failed: %s", hipGetErrorString(le));
-  HIP_TRY(hipMemcpy(paths, d_p, n * 4, hipMemcpyDeviceToHost));
-  return VITS_OK;
+  OpDoor d("mas", device);
+  const size_t n = (size_t)B * Ty * Tx, lds = (size_t)2 * Tx * sizeof(float);
+  float* d_v = d.up(values, n);
+  int *d_ty = d.up(t_ys, B), *d_tx = d.up(t_xs, B), *d_p = d.dev<int>(n);
+  unsigned char* d_d = d.dev<unsigned char>(n);
+  if (d.ok() && lds > 64 * 1024) d.hip(hipFuncSetAttribute((const void*)mas_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+  if (d.ok()) hipLaunchKernelGGL(mas_kernel, dim3(B), dim3(256), lds, 0, d_v, d_ty, d_tx, Ty, Tx, d_d, d_p);
+  d.finish();
+  d.down(paths, d_p, n);
+  return d.rc();
 }
 
 // ---- device-resident sessions (bench / serving loop)
@@ -655,24 +648,30 @@ int vits_debug_decoder_needs(const vits_hparams* hp, int32_t* out, int32_t cap) 
 }
 void vits_debug_conv_sp(int mode) { conv_select().sp_mode = mode; }
 int vits_debug_clock_probe(int device, int32_t duration_us, double* ghz, int32_t n) {
-  if (!ghz || n < 1 || n > 1024 || duration_us < 1 || duration_us > 2000000 || device < 0 || device >= 64) return fail(VITS_ERR_ARG, "clock probe: bad arguments");
-  HIP_TRY(hipSetDevice(device));
+  if (!ghz || n < 1 || n > 1024 || duration_us < 1 || duration_us > 2000000 || device < 0 || device >= 64) return -fail(VITS_ERR_ARG, "clock probe: bad arguments");
+  const auto bad = [](hipError_t e) { return -fail(VITS_ERR_DEVICE, "clock probe failed: %s", hipGetErrorString(e)); };
+  hipError_t e = hipSetDevice(device);
+  if (e != hipSuccess) return bad(e);
   // stream and result buffer are created ONCE per device and kept: hipMalloc / hipStreamCreate wait for the device's work in flight, and
   // the probe exists to run NEXT to that work (call it once before the burst it is to watch)
   static std::mutex mu;
   static hipStream_t st[64];
   static double* buf[64];
   std::lock_guard<std::mutex> g(mu);
-  if (!st[device]) {
-    HIP_TRY(hipStreamCreateWithFlags(&st[device], hipStreamNonBlocking));  // its own hardware queue
-    if (hipMalloc((void**)&buf[device], sizeof(double) * 1024) != hipSuccess) { buf[device] = nullptr; return fail(VITS_ERR_NOMEM, "clock probe: device alloc failed"); }
+  if (!buf[device]) {  // (the buffer marks the device initialised: a call after a failure here tries again)
+    if (!st[device]) e = hipStreamCreateWithFlags(&st[device], hipStreamNonBlocking);  // its own hardware queue
+    if (e != hipSuccess) { st[device] = nullptr; return bad(e); }
+    if (hipMalloc((void**)&buf[device], sizeof(double) * 1024) != hipSuccess) {
+      buf[device] = nullptr;
+      (void)hipGetLastError();
+      return -fail(VITS_ERR_NOMEM, "clock probe: device alloc failed");
+    }
   }
-  if (!buf[device]) return fail(VITS_ERR_NOMEM, "clock probe: no buffer");
   hipLaunchKernelGGL(clock_probe_kernel, dim3(n), dim3(64), 0, st[device], buf[device], (long long)duration_us * 100);
-  hipError_t e = hipStreamSynchronize(st[device]);
+  e = hipStreamSynchronize(st[device]);
   if (e == hipSuccess) e = hipMemcpyAsync(ghz, buf[device], sizeof(double) * n, hipMemcpyDeviceToHost, st[device]);
   if (e == hipSuccess) e = hipStreamSynchronize(st[device]);
-  if (e != hipSuccess) return fail(VITS_ERR_DEVICE, "clock probe failed: %s", hipGetErrorString(e));
+  if (e != hipSuccess) return bad(e);
   return n;
 }
 void vits_debug_no_bf16x3(int on) { conv_select().no_bf3 = on; }
@@ -685,30 +684,17 @@ int vits_debug_plain_attention(int device, const float* qkv, const int64_t* leng
   if (!qkv || !lengths || !out || B <= 0 || B > 65535 || T <= 0 || C <= 0 || n_heads <= 0 || n_heads > 64 || C % n_heads)
     return fail(VITS_ERR_ARG, "plain attention: bad arguments");
   if (!plain_attention_dk_ok(C / n_heads)) return fail(VITS_ERR_UNSUPPORTED, "plain attention: head dim %d not built", C / n_heads);
-  std::vector<int> len32(B);
-  for (int b = 0; b < B; ++b) {
-    if (lengths[b] < 0 || lengths[b] > T) return fail(VITS_ERR_ARG, "plain attention: length out of range");
-    len32[b] = (int)lengths[b];
-  }
-  HIP_TRY(hipSetDevice(device));
-  const size_t nq = (size_t)B * 3 * C * T, no = (size_t)B * C * T;
-  float *d_qkv = nullptr, *d_out = nullptr;
-  int* d_len = nullptr;
-  hipError_t e = hipMalloc((void**)&d_qkv, nq * sizeof(float));
-  if (e == hipSuccess) e = hipMalloc((void**)&d_out, no * sizeof(float));
-  if (e == hipSuccess) e = hipMalloc((void**)&d_len, B * sizeof(int));
-  if (e == hipSuccess) e = hipMemcpy(d_qkv, qkv, nq * sizeof(float), hipMemcpyHostToDevice);
-  if (e == hipSuccess) e = hipMemcpy(d_len, len32.data(), B * sizeof(int), hipMemcpyHostToDevice);
-  if (e == hipSuccess) e = hipMemset(d_out, 0xff, no * sizeof(float));  // NaN: an output the kernel does not write shows
-  if (e == hipSuccess) {
-    launch_plain_attention_on(nullptr, d_qkv, d_len, d_out, B, C, T, n_heads);
-    e = hipGetLastError();
-  }
-  if (e == hipSuccess) e = hipDeviceSynchronize();
-  if (e == hipSuccess) e = hipMemcpy(out, d_out, no * sizeof(float), hipMemcpyDeviceToHost);
-  hipFree(d_qkv); hipFree(d_out); hipFree(d_len);
-  if (e != hipSuccess) return fail(VITS_ERR_DEVICE, "plain attention: %s", hipGetErrorString(e));
-  return VITS_OK;
+  std::vector<int> len32;
+  TRY(op_items_check("plain attention", qkv, lengths, B, T, &len32));
+  OpDoor d("plain attention", device);
+  const size_t no = (size_t)B * C * T;
+  float* d_qkv = d.up(qkv, 3 * no);
+  int* d_len = d.up(len32.data(), B);
+  float* d_out = d.out<float>(no);
+  if (d.ok()) launch_plain_attention_on(nullptr, d_qkv, d_len, d_out, B, C, T, n_heads);
+  d.finish();
+  d.down(out, d_out, no);
+  return d.rc();
 }
 
 // The relative-position attention (attentions.py:165-260; relpos_attention*_kernel) on caller buffers: qkv [B, 3C, T], shared tables
@@ -722,34 +708,18 @@ int vits_debug_relpos_attention(int device, const float* qkv, const float* ek, c
   if (dk != 32 && dk != 64 && dk != 96) return fail(VITS_ERR_UNSUPPORTED, "relpos attention: head dim %d not built", dk);
   if (ek && (window < 0 || window > 4)) return fail(VITS_ERR_UNSUPPORTED, "relpos attention: window %d not in [0, 4]", window);
   const int W = ek ? window : 4;  // (the engine's own argument for table-less calls, stts.hip.h)
-  std::vector<int> len32(B);
-  for (int b = 0; b < B; ++b) {
-    if (lengths[b] < 0 || lengths[b] > T) return fail(VITS_ERR_ARG, "relpos attention: length out of range");
-    len32[b] = (int)lengths[b];
-  }
-  HIP_TRY(hipSetDevice(device));
-  const size_t nq = (size_t)B * 3 * C * T, no = (size_t)B * C * T, ne = ek ? (size_t)(2 * W + 1) * dk : 0;
-  float *d_qkv = nullptr, *d_out = nullptr, *d_ek = nullptr, *d_ev = nullptr;
-  int* d_len = nullptr;
-  hipError_t e = hipMalloc((void**)&d_qkv, nq * sizeof(float));
-  if (e == hipSuccess) e = hipMalloc((void**)&d_out, no * sizeof(float));
-  if (e == hipSuccess) e = hipMalloc((void**)&d_len, B * sizeof(int));
-  if (e == hipSuccess && ne) e = hipMalloc((void**)&d_ek, ne * sizeof(float));
-  if (e == hipSuccess && ne) e = hipMalloc((void**)&d_ev, ne * sizeof(float));
-  if (e == hipSuccess) e = hipMemcpy(d_qkv, qkv, nq * sizeof(float), hipMemcpyHostToDevice);
-  if (e == hipSuccess) e = hipMemcpy(d_len, len32.data(), B * sizeof(int), hipMemcpyHostToDevice);
-  if (e == hipSuccess && ne) e = hipMemcpy(d_ek, ek, ne * sizeof(float), hipMemcpyHostToDevice);
-  if (e == hipSuccess && ne) e = hipMemcpy(d_ev, ev, ne * sizeof(float), hipMemcpyHostToDevice);
-  if (e == hipSuccess) e = hipMemset(d_out, 0xff, no * sizeof(float));  // NaN: an output the kernel does not write shows
-  if (e == hipSuccess) {
-    launch_relpos_attention_on(nullptr, d_qkv, d_ek, d_ev, d_len, d_out, B, C, T, n_heads, W);
-    e = hipGetLastError();
-  }
-  if (e == hipSuccess) e = hipDeviceSynchronize();
-  if (e == hipSuccess) e = hipMemcpy(out, d_out, no * sizeof(float), hipMemcpyDeviceToHost);
-  hipFree(d_qkv); hipFree(d_out); hipFree(d_len); hipFree(d_ek); hipFree(d_ev);
-  if (e != hipSuccess) return fail(VITS_ERR_DEVICE, "relpos attention: %s", hipGetErrorString(e));
-  return VITS_OK;
+  std::vector<int> len32;
+  TRY(op_items_check("relpos attention", qkv, lengths, B, T, &len32));
+  OpDoor d("relpos attention", device);
+  const size_t no = (size_t)B * C * T, ne = (size_t)(2 * W + 1) * dk;
+  float* d_qkv = d.up(qkv, 3 * no);
+  float *d_ek = d.up(ek, ne), *d_ev = d.up(ev, ne);  // (both or neither)
+  int* d_len = d.up(len32.data(), B);
+  float* d_out = d.out<float>(no);
+  if (d.ok()) launch_relpos_attention_on(nullptr, d_qkv, d_ek, d_ev, d_len, d_out, B, C, T, n_heads, W);
+  d.finish();
+  d.down(out, d_out, no);
+  return d.rc();
 }
 // The tail of a MonoTransformerFlowLayer (mono_couple_kernel) on caller buffers: h [B, C, T], u and z [B, 2C, T], W [C, C], b [C].
 int vits_debug_mono_couple(int device, const float* h, const float* u, const float* W, const float* b, const int64_t* lengths, int32_t B,
@@ -757,36 +727,17 @@ int vits_debug_mono_couple(int device, const float* h, const float* u, const flo
   if (!h || !u || !W || !b || !lengths || !z || B <= 0 || B > 65535 || T <= 0 || C <= 0 || (mode != 0 && mode != 1))
     return fail(VITS_ERR_ARG, "mono couple: bad arguments");
   if (!mono_couple_c_ok(C)) return fail(VITS_ERR_UNSUPPORTED, "mono couple: width %d not built (a multiple of 32 in [32, 192])", C);
-  std::vector<int> len32(B);
-  for (int i = 0; i < B; ++i) {
-    if (lengths[i] < 0 || lengths[i] > T) return fail(VITS_ERR_ARG, "mono couple: length out of range");
-    len32[i] = (int)lengths[i];
-  }
-  HIP_TRY(hipSetDevice(device));
+  std::vector<int> len32;
+  TRY(op_items_check("mono couple", h, lengths, B, T, &len32));
+  OpDoor d("mono couple", device);
   const size_t nh = (size_t)B * C * T, nz = 2 * nh;
-  float *d_h = nullptr, *d_u = nullptr, *d_W = nullptr, *d_b = nullptr, *d_z = nullptr;
-  int* d_len = nullptr;
-  hipError_t e = hipMalloc((void**)&d_h, nh * sizeof(float));
-  if (e == hipSuccess) e = hipMalloc((void**)&d_u, nz * sizeof(float));
-  if (e == hipSuccess) e = hipMalloc((void**)&d_z, nz * sizeof(float));
-  if (e == hipSuccess) e = hipMalloc((void**)&d_W, (size_t)C * C * sizeof(float));
-  if (e == hipSuccess) e = hipMalloc((void**)&d_b, C * sizeof(float));
-  if (e == hipSuccess) e = hipMalloc((void**)&d_len, B * sizeof(int));
-  if (e == hipSuccess) e = hipMemcpy(d_h, h, nh * sizeof(float), hipMemcpyHostToDevice);
-  if (e == hipSuccess) e = hipMemcpy(d_u, u, nz * sizeof(float), hipMemcpyHostToDevice);
-  if (e == hipSuccess) e = hipMemcpy(d_W, W, (size_t)C * C * sizeof(float), hipMemcpyHostToDevice);
-  if (e == hipSuccess) e = hipMemcpy(d_b, b, C * sizeof(float), hipMemcpyHostToDevice);
-  if (e == hipSuccess) e = hipMemcpy(d_len, len32.data(), B * sizeof(int), hipMemcpyHostToDevice);
-  if (e == hipSuccess) e = hipMemset(d_z, 0xff, nz * sizeof(float));  // NaN: an output the kernel does not write shows
-  if (e == hipSuccess) {
-    launch_mono_couple_on(nullptr, d_h, d_u, d_W, d_b, d_len, d_z, B, C, T, mode);
-    e = hipGetLastError();
-  }
-  if (e == hipSuccess) e = hipDeviceSynchronize();
-  if (e == hipSuccess) e = hipMemcpy(z, d_z, nz * sizeof(float), hipMemcpyDeviceToHost);
-  hipFree(d_h); hipFree(d_u); hipFree(d_z); hipFree(d_W); hipFree(d_b); hipFree(d_len);
-  if (e != hipSuccess) return fail(VITS_ERR_DEVICE, "mono couple: %s", hipGetErrorString(e));
-  return VITS_OK;
+  float *d_h = d.up(h, nh), *d_u = d.up(u, nz), *d_W = d.up(W, (size_t)C * C), *d_b = d.up(b, C);
+  int* d_len = d.up(len32.data(), B);
+  float* d_z = d.out<float>(nz);
+  if (d.ok()) launch_mono_couple_on(nullptr, d_h, d_u, d_W, d_b, d_len, d_z, B, C, T, mode);
+  d.finish();
+  d.down(z, d_z, nz);
+  return d.rc();
 }
 
 int vits_session_sync(vits_session* s) {
@@ -841,38 +792,32 @@ int vits_op_conv1d(int device, const float* x, const float* w, const float* bias
   if (Cin % CONV_CI_T) return fail(VITS_ERR_UNSUPPORTED, "C_in must be a multiple of %d", CONV_CI_T);
   if ((K - 1) * dil > CONV_MAX_HALO) return fail(VITS_ERR_UNSUPPORTED, "(K-1)*dil > %d", CONV_MAX_HALO);
   if ((long long)(Cin > Cout ? Cin : Cout) * T * 4 >= (1LL << 31)) return fail(VITS_ERR_ARG, "one item's tensor must stay below 2 GiB (32-bit offsets inside an item)");
-  HIP_TRY(hipSetDevice(device));
+  OpDoor d("conv1d", device);
+  if (!d.ok()) return d.rc();
   vits_model tmp;
   tmp.device = device;
   ConvW W = make_conv(&tmp, Cout, Cin, K, bias, [&](int r, int ci, int kk) { return w[((size_t)r * Cin + ci) * K + kk]; });
-  int rc = VITS_OK;
-  float *dx = nullptr, *dy = nullptr;
+  struct TmpAllocs { vits_model& m; ~TmpAllocs() { for (void* a : m.allocs) hipFree(a); } } tmp_allocs{tmp};
+  if (tmp.missing) return VITS_ERR_NOMEM;
   vits_session s;
   s.m = &tmp;
-  if (tmp.missing) rc = VITS_ERR_NOMEM;
-  if (rc == VITS_OK && hipMalloc((void**)&dx, sizeof(float) * (size_t)B * Cin * T) != hipSuccess) rc = fail(VITS_ERR_NOMEM, "alloc");
-  if (rc == VITS_OK && hipMalloc((void**)&dy, sizeof(float) * (size_t)B * Cout * T) != hipSuccess) rc = fail(VITS_ERR_NOMEM, "alloc");
-  if (rc == VITS_OK) {
-    hipMemcpy(dx, x, sizeof(float) * (size_t)B * Cin * T, hipMemcpyHostToDevice);
-    ConvParams P = conv_params(W, dx, dy, B, T, dil, (K - 1) * dil / 2);
-    P.in_slope = slope;
-    ConvOpDbg dbg(P);
+  const size_t nx = (size_t)B * Cin * T, ny = (size_t)B * Cout * T;
+  float* dx = d.up(x, nx);
+  float* dy = d.dev<float>(ny);
+  ConvParams P = conv_params(W, dx, dy, B, T, dil, (K - 1) * dil / 2);
+  P.in_slope = slope;
+  ConvOpDbg dbg(P);
+  if (d.ok()) {
     for (int r = 0; r < dbg.reps; ++r) {
       dbg.before_launch(r);
       launch_conv(&s, P, EPI_STORE, "op.conv1d");
     }
     dbg.after_launches();
-    hipError_t e = hipDeviceSynchronize();
-    if (e != hipSuccess) rc = fail(VITS_ERR_DEVICE, "conv kernel failed: %s", hipGetErrorString(e));
-    else {
-      hipMemcpy(y, dy, sizeof(float) * (size_t)B * Cout * T, hipMemcpyDeviceToHost);
-      dbg.report(B, Cin, Cout, W.Mpad, T, K, dil);
-    }
   }
-  if (dx) hipFree(dx);
-  if (dy) hipFree(dy);
-  for (void* a : tmp.allocs) hipFree(a);
-  return rc;
+  d.finish();
+  d.down(y, dy, ny);
+  if (d.ok()) dbg.report(B, Cin, Cout, W.Mpad, T, K, dil);
+  return d.rc();
 }
 
 }  // extern "C"

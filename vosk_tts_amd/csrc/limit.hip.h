@@ -546,28 +546,20 @@ static int lim_op(int device, const float* x, const int64_t* lengths, int32_t B,
     TRY(loud_params(VITS_LOUDNESS_LUFS, target, 0.f, &lprm));
     TRY(loud_plan(rate, &LP));
   }
-  HIP_TRY(hipSetDevice(device));
-  const size_t lscr = align_up(loud_scratch_bytes(B, N), 256), scr = lim_scratch_layout(B, N, lufs, nullptr, nullptr), xb = sizeof(float) * (size_t)B * N;
-  char* dscr = nullptr;
-  float *dx = nullptr, *dy = nullptr, *ds = nullptr;
-  int* dl = nullptr;
+  OpDoor d("limit", device);
+  const size_t lscr = align_up(loud_scratch_bytes(B, N), 256), scr = lim_scratch_layout(B, N, lufs, nullptr, nullptr), nx = (size_t)B * N;
+  char* dscr = d.dev<char>(scr + 2 * lscr);
+  float* dx = d.up(x, nx);
+  int* dl = d.up(len32.data(), B);
+  float* dy = prm ? d.out<float>(nx) : nullptr;
+  float* ds = s ? d.out<float>(nx) : nullptr;
   LimScratch S;
   LoudScratch S0, S1;
-  std::vector<float> res0((size_t)B * 4), gv((size_t)B * 2), tiles;
-  hipError_t e = hipMalloc((void**)&dscr, scr + 2 * lscr);
-  if (e == hipSuccess) e = hipMalloc((void**)&dx, xb);
-  if (e == hipSuccess && prm) e = hipMalloc((void**)&dy, xb);
-  if (e == hipSuccess && s) e = hipMalloc((void**)&ds, xb);
-  if (e == hipSuccess) e = hipMalloc((void**)&dl, sizeof(int) * B);
-  if (e == hipSuccess) e = hipMemcpy(dx, x, xb, hipMemcpyHostToDevice);
-  if (e == hipSuccess) e = hipMemcpy(dl, len32.data(), sizeof(int) * B, hipMemcpyHostToDevice);
-  if (e == hipSuccess && prm) e = hipMemset(dy, 0xff, xb);  // NaN: an output the kernel does not write shows
-  if (e == hipSuccess && s) e = hipMemset(ds, 0xff, xb);
-  if (e == hipSuccess) {
-    lim_scratch_layout(B, N, lufs, dscr, &S);
-    loud_scratch_layout(B, N, dscr + scr, &S0);
-    loud_scratch_layout(B, N, dscr + scr + lscr, &S1);
-    tiles.resize((size_t)B * S.ntiles);
+  lim_scratch_layout(B, N, lufs, dscr, &S);
+  loud_scratch_layout(B, N, dscr ? dscr + scr : nullptr, &S0);
+  loud_scratch_layout(B, N, dscr ? dscr + scr + lscr : nullptr, &S1);
+  std::vector<float> res0((size_t)B * 4), gv((size_t)B * 2), tiles((size_t)B * S.ntiles);
+  if (d.ok()) {
     lim_env_launch(nullptr, mode, tab, S, dx, N, N, dl, 1, 1, 1, B);
     if (prm && !lufs) {
       lim_pass_launch<float>(nullptr, *prm, S, 0, nullptr, nullptr, dx, N, N, dl, 1, 1, 1, B, dy, N, N, 1.f, ds);
@@ -577,16 +569,14 @@ static int lim_op(int device, const float* x, const int64_t* lengths, int32_t B,
       loud_measure_launch(nullptr, LP, lprm, S1, S.y0, N, N, dl, 1, 1, 1, B);
       lim_pass_launch<float>(nullptr, *prm, S, 2, S0.res, S1.res, dx, N, N, dl, 1, 1, 1, B, dy, N, N, 1.f, ds);
     }
-    e = hipGetLastError();
-    if (e == hipSuccess) e = hipDeviceSynchronize();
-    if (e == hipSuccess) e = hipMemcpy(tiles.data(), prm ? S.smin : S.tpeak, sizeof(float) * tiles.size(), hipMemcpyDeviceToHost);
-    if (e == hipSuccess && prm) e = hipMemcpy(gv.data(), S.gv, sizeof(float) * gv.size(), hipMemcpyDeviceToHost);
-    if (e == hipSuccess && lufs) e = hipMemcpy(res0.data(), S0.res, sizeof(float) * res0.size(), hipMemcpyDeviceToHost);
   }
-  if (e == hipSuccess && y) e = hipMemcpy(y, dy, xb, hipMemcpyDeviceToHost);
-  if (e == hipSuccess && s) e = hipMemcpy(s, ds, xb, hipMemcpyDeviceToHost);
-  hipFree(dscr); hipFree(dx); hipFree(dy); hipFree(ds); hipFree(dl);
-  if (e != hipSuccess) return fail(VITS_ERR_DEVICE, "limit: %s", hipGetErrorString(e));
+  d.finish();
+  d.down(tiles.data(), prm ? S.smin : S.tpeak, tiles.size());
+  if (prm) d.down(gv.data(), S.gv, gv.size());
+  if (lufs) d.down(res0.data(), S0.res, res0.size());
+  if (y) d.down(y, dy, nx);
+  if (s) d.down(s, ds, nx);
+  if (!d.ok()) return d.rc();
   for (int b = 0; b < B; ++b) {  // the tiles of an item: max p, or min s (both exact in any order)
     const int nt = (int)((lengths[b] + VITS_LIMIT_TILE - 1) / VITS_LIMIT_TILE);
     float v = prm ? 1.f : 0.f;

@@ -534,20 +534,6 @@ int vits_loudness_plan(int32_t rate, double sos[2][6], int32_t* hop) {
   return VITS_OK;
 }
 
-// what the parity doors over B items x [B, N] on the host (loud_op, lim_op, pitch_op) check first; len32: the lengths as the kernels
-// take them.  `what` is the door's name in its messages, `n_name` what it calls N there.
-static int op_items_check(const char* what, const float* x, const int64_t* lengths, int32_t B, int64_t N, std::vector<int>* len32,
-                          const char* n_name = "") {
-  if (!x || !lengths || B <= 0 || B > 65535 || N <= 0 || N >= (1LL << 31)) return fail(VITS_ERR_ARG, "%s: bad argument", what);
-  len32->resize(B);
-  for (int b = 0; b < B; ++b) {
-    if (lengths[b] < 0 || lengths[b] > N)
-      return fail(VITS_ERR_ARG, "%s: length %lld of item %d outside [0, %s%lld]", what, (long long)lengths[b], b, n_name, (long long)N);
-    (*len32)[b] = (int)lengths[b];
-  }
-  return VITS_OK;
-}
-
 // x [B, N] on the host measured (prm.mode 0) or normalised into y; results for every item
 static int loud_op(int device, const float* x, const int64_t* lengths, int32_t B, int64_t N, int32_t rate, const LoudParams& prm, float* y,
                    float* loudness, float* peak, float* gain) {
@@ -555,31 +541,23 @@ static int loud_op(int device, const float* x, const int64_t* lengths, int32_t B
   TRY(op_items_check("loudness", x, lengths, B, N, &len32));
   LoudPlan P;
   TRY(loud_plan(rate, &P));
-  HIP_TRY(hipSetDevice(device));
-  const size_t scr = loud_scratch_bytes(B, N), xb = sizeof(float) * (size_t)B * N;
-  char* dscr = nullptr;
-  float *dx = nullptr, *dy = nullptr;
-  int* dl = nullptr;
+  OpDoor d("loudness", device);
+  const size_t nx = (size_t)B * N;
+  char* dscr = d.dev<char>(loud_scratch_bytes(B, N));
+  float* dx = d.up(x, nx);
+  int* dl = d.up(len32.data(), B);
+  float* dy = y ? d.out<float>(nx) : nullptr;
   std::vector<float> res((size_t)B * 4);
-  hipError_t e = hipMalloc((void**)&dscr, scr);
-  if (e == hipSuccess) e = hipMalloc((void**)&dx, xb);
-  if (e == hipSuccess && y) e = hipMalloc((void**)&dy, xb);
-  if (e == hipSuccess) e = hipMalloc((void**)&dl, sizeof(int) * B);
-  if (e == hipSuccess) e = hipMemcpy(dx, x, xb, hipMemcpyHostToDevice);
-  if (e == hipSuccess) e = hipMemcpy(dl, len32.data(), sizeof(int) * B, hipMemcpyHostToDevice);
-  if (e == hipSuccess && y) e = hipMemset(dy, 0xff, xb);  // NaN: an output the kernel does not write shows
-  if (e == hipSuccess) {
-    LoudScratch S;
-    loud_scratch_layout(B, N, dscr, &S);
+  LoudScratch S;
+  loud_scratch_layout(B, N, dscr, &S);
+  if (d.ok()) {
     loud_measure_launch(nullptr, P, prm, S, dx, N, N, dl, 1, 1, 1, B);
     if (y) loud_apply_launch<float>(nullptr, S, dx, N, N, dl, 1, 1, 1, B, dy, N, N, 1.f);
-    e = hipGetLastError();
-    if (e == hipSuccess) e = hipDeviceSynchronize();
-    if (e == hipSuccess) e = hipMemcpy(res.data(), S.res, sizeof(float) * (size_t)B * 4, hipMemcpyDeviceToHost);
   }
-  if (e == hipSuccess && y) e = hipMemcpy(y, dy, xb, hipMemcpyDeviceToHost);
-  hipFree(dscr); hipFree(dx); hipFree(dy); hipFree(dl);
-  if (e != hipSuccess) return fail(VITS_ERR_DEVICE, "loudness: %s", hipGetErrorString(e));
+  d.finish();
+  d.down(res.data(), S.res, res.size());
+  if (y) d.down(y, dy, nx);
+  if (!d.ok()) return d.rc();
   for (int b = 0; b < B; ++b) {
     if (loudness) loudness[b] = res[(size_t)b * 4 + 0];
     if (peak) peak[b] = res[(size_t)b * 4 + 1];

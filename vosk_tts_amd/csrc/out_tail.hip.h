@@ -106,16 +106,7 @@ static int tail_req(const vits_model* vocoder, const TailFields& f, int32_t samp
 
 // ---- the runner -----------------------------------------------------------------------------------------------------------
 // device buffers owned by one call (the allocator of a tail_run that has no arena to draw from), freed with it
-struct TailBufs {
-  std::vector<void*> bufs;
-  ~TailBufs() { for (void* p : bufs) hipFree(p); }
-  void* operator()(size_t bytes) {
-    void* p = nullptr;
-    if (hipMalloc(&p, bytes ? bytes : 1) != hipSuccess) { (void)hipGetLastError(); return nullptr; }
-    bufs.push_back(p);
-    return p;
-  }
-};
+using TailBufs = DevBufs;  // op_door.hip.h
 
 // The tail of a vits_synthesize* call, as launches on `stream` from the float native-rate waveform x [B, S] on the device (item b is
 // len_y[b] * hop samples, h_len[b] on the host): pitch, resample, normalise and / or limit; the last stage that runs converts to int16

@@ -611,30 +611,21 @@ static int pitch_op(int device, const float* x, const int64_t* lengths, int32_t 
     return VITS_OK;
   }
   const long long Ny = stretch ? (long long)PT_H * (((N / PT_H + 2) * P + Q - 1) / Q - 1) : door == PT_DOOR_GAIN ? (N / PT_H + 3) * PT_NB : N;
-  HIP_TRY(hipSetDevice(device));
-  float *dx = nullptr, *dy = nullptr;
-  int* dl = nullptr;
-  hipError_t e = hipMalloc((void**)&dx, sizeof(float) * (size_t)B * N);
-  if (e == hipSuccess) e = hipMalloc((void**)&dy, sizeof(float) * (size_t)B * Ny);
-  if (e == hipSuccess) e = hipMalloc((void**)&dl, sizeof(int) * B);
+  OpDoor d("pitch", device);
   // every item's own samples only: what lies at and beyond lengths[b] never reaches the device
-  if (e == hipSuccess) e = hipMemset(dx, 0, sizeof(float) * (size_t)B * N);
-  for (int b = 0; b < B && e == hipSuccess; ++b)
-    if (lengths[b]) e = hipMemcpy(dx + (size_t)b * N, x + (size_t)b * N, sizeof(float) * (size_t)lengths[b], hipMemcpyHostToDevice);
-  if (e == hipSuccess) e = hipMemcpy(dl, len32.data(), sizeof(int) * B, hipMemcpyHostToDevice);
-  // NaN: an output the kernels do not write shows (the gain door's kernel writes rows [0, F_a + 2) only: the others are zeros from here)
-  if (e == hipSuccess) e = hipMemset(dy, door == PT_DOOR_GAIN ? 0 : 0xff, sizeof(float) * (size_t)B * Ny);
-  int rc = VITS_OK;
-  if (e == hipSuccess) {
-    rc = door == PT_DOOR_GAIN ? pitch_gain_run(device, dx, dl, B, N, P, Q, dy)
-         : stretch            ? pitch_run(device, nullptr, dx, N, N, dl, 1, len64.data(), B, P, Q, formant, nullptr, 0, 0, dy, Ny)
-                              : pitch_run(device, nullptr, dx, N, N, dl, 1, len64.data(), B, P, Q, formant, dy, Ny, Ny, nullptr, 0);
-    if (rc == VITS_OK) e = hipMemcpy(y, dy, sizeof(float) * (size_t)B * Ny, hipMemcpyDeviceToHost);
-  }
-  hipFree(dx); hipFree(dy); hipFree(dl);
-  if (rc != VITS_OK) return rc;
-  if (e != hipSuccess) return fail(VITS_ERR_DEVICE, "pitch: %s", hipGetErrorString(e));
-  return VITS_OK;
+  float* dx = d.out<float>((size_t)B * N, 0);
+  for (int b = 0; b < B && d.ok(); ++b)
+    if (lengths[b]) d.hip(hipMemcpy(dx + (size_t)b * N, x + (size_t)b * N, sizeof(float) * (size_t)lengths[b], hipMemcpyHostToDevice));
+  int* dl = d.up(len32.data(), B);
+  // (the gain door's kernel writes rows [0, F_a + 2) only: the others are zeros from here)
+  float* dy = d.out<float>((size_t)B * Ny, door == PT_DOOR_GAIN ? 0 : 0xff);
+  if (d.ok())
+    TRY(door == PT_DOOR_GAIN ? pitch_gain_run(device, dx, dl, B, N, P, Q, dy)
+        : stretch            ? pitch_run(device, nullptr, dx, N, N, dl, 1, len64.data(), B, P, Q, formant, nullptr, 0, 0, dy, Ny)
+                             : pitch_run(device, nullptr, dx, N, N, dl, 1, len64.data(), B, P, Q, formant, dy, Ny, Ny, nullptr, 0));
+  d.finish();
+  d.down(y, dy, (size_t)B * Ny);
+  return d.rc();
 }
 
 int vits_op_pitch_shift(int device, const float* x, const int64_t* lengths, int32_t B, int64_t N, float semitones, float* y) {

@@ -242,12 +242,9 @@ int vits_resample_table(int32_t rate_in, int32_t rate_out, float* table, int64_t
 }
 
 int vits_op_resample(int device, const float* x, const int64_t* lengths, int32_t B, int64_t N, int32_t rate_in, int32_t rate_out, float* y) {
-  if (!x || !lengths || !y || B <= 0 || B > 65535 || N <= 0 || N >= (1LL << 31)) return fail(VITS_ERR_ARG, "resample: bad argument");
-  std::vector<int> len32(B);
-  for (int b = 0; b < B; ++b) {
-    if (lengths[b] < 0 || lengths[b] > N) return fail(VITS_ERR_ARG, "resample: length out of range");
-    len32[b] = (int)lengths[b];
-  }
+  if (!y) return fail(VITS_ERR_ARG, "resample: bad argument");
+  std::vector<int> len32;
+  TRY(op_items_check("resample", x, lengths, B, N, &len32));
   if (rate_in > 0 && rate_in == rate_out) {  // the identity (zeros beyond each item's end, like every other rate)
     for (int b = 0; b < B; ++b) {
       memcpy(y + (size_t)b * N, x + (size_t)b * N, sizeof(float) * (size_t)lengths[b]);
@@ -257,25 +254,15 @@ int vits_op_resample(int device, const float* x, const int64_t* lengths, int32_t
   }
   ResamplePlan P;
   TRY(resample_plan(rate_in, rate_out, &P));
-  HIP_TRY(hipSetDevice(device));
   const ResampleTab* T = nullptr;
   TRY(resample_get(device, rate_in, rate_out, &T));
-  const long long Ny = P.n_out(N);
-  float *dx = nullptr, *dy = nullptr;
-  int* dl = nullptr;
-  hipError_t e = hipMalloc((void**)&dx, sizeof(float) * (size_t)B * N);
-  if (e == hipSuccess) e = hipMalloc((void**)&dy, sizeof(float) * (size_t)B * Ny);
-  if (e == hipSuccess) e = hipMalloc((void**)&dl, sizeof(int) * B);
-  if (e == hipSuccess) e = hipMemcpy(dx, x, sizeof(float) * (size_t)B * N, hipMemcpyHostToDevice);
-  if (e == hipSuccess) e = hipMemcpy(dl, len32.data(), sizeof(int) * B, hipMemcpyHostToDevice);
-  if (e == hipSuccess) e = hipMemset(dy, 0xff, sizeof(float) * (size_t)B * Ny);  // NaN: an output the kernel does not write shows
-  if (e == hipSuccess) {
-    resample_launch<float>(nullptr, *T, dx, N, 0, N, dl, 1, B, dy, Ny, 0, Ny, 1.f, nullptr);
-    e = hipGetLastError();
-  }
-  if (e == hipSuccess) e = hipDeviceSynchronize();
-  if (e == hipSuccess) e = hipMemcpy(y, dy, sizeof(float) * (size_t)B * Ny, hipMemcpyDeviceToHost);
-  hipFree(dx); hipFree(dy); hipFree(dl);
-  if (e != hipSuccess) return fail(VITS_ERR_DEVICE, "resample: %s", hipGetErrorString(e));
-  return VITS_OK;
+  OpDoor d("resample", device);
+  const size_t Ny = (size_t)P.n_out(N);
+  float* dx = d.up(x, (size_t)B * N);
+  int* dl = d.up(len32.data(), B);
+  float* dy = d.out<float>(B * Ny);
+  if (d.ok()) resample_launch<float>(nullptr, *T, dx, N, 0, N, dl, 1, B, dy, Ny, 0, Ny, 1.f, nullptr);
+  d.finish();
+  d.down(y, dy, B * Ny);
+  return d.rc();
 }
