@@ -5,7 +5,7 @@
  *   - kernel-selection / path switches (force_tile, attention_impl, fast_path, ks_waves, ln_stats, wn_fold, conv_wp, conv_sp,
  *     no_bf16x3, tail_impl, poison_workspace) are THREAD-LOCAL: they change what the CALLING thread's engine calls launch and nothing
  *     another thread is running (the engine runs every call on the caller's thread);
- *   - the persistent-program switches (persist, persist_spin, persist_rearm_ms) are process-wide on purpose: the programs are a
+ *   - the persistent-program switches (persist, persist_spin, persist_rearm_ms, persist_attn_fused) are process-wide on purpose: the programs are a
  *     per-device resource with one owner at a time; they are atomics and take effect for calls that start afterwards.
  */
 #ifndef VITS_MI355_DEBUG_H
@@ -45,6 +45,20 @@ void vits_debug_persist_spin(int limit);
  * against 1240 requests/s); profiles/r6_owners.txt.  0 = only a call that starts alone; -1 = whenever the token is free (rounds 3-5).
  * Device sessions (vits_session_*) take the token for their lifetime either way. */
 void vits_debug_persist_when(int max_others_in_flight);
+/* Test hook (process-wide, an atomic like the other persistent-program switches; environment VITS_PERSIST_ATTN_FUSED): the attention
+ * half of every encoder layer in the step programs.  0 = the planner's rule (default), 1 = never fused (merge, conv_o and LayerNorm 1
+ * as three steps), 2 = form A only (the merge step runs conv_o + residual with up to 4 workers per column), 3 = form B wherever it fits
+ * (one worker per column runs merge, conv_o, residual and LayerNorm 1).  Where a mode cannot apply the old form runs.  Takes effect for
+ * sessions laid out afterwards; a session that is reserved again under another value is planned again (the stage entry points reserve
+ * at every call, cached fast-path sessions keep the form they were built with). */
+void vits_debug_persist_attn_fused(int mode);
+/* Test hook, host arithmetic only: the planner's answer for an encoder of `hidden` channels on `padded_columns` columns with `workers`
+ * workgroups under `mode` (above), given the transposed conv_o weights exist: 0 = three steps, 1..4 = form A with that many workers
+ * per column, -1 = form B. */
+int vits_debug_persist_attn_form(int hidden, int padded_columns, int workers, int mode);
+/* Test hook: dependent steps of the persistent program this process launched most recently (0: none yet).  Lets a test assert which
+ * form of a stage's program ran, not only what it computed: a text-encoder layer is 8 steps, 7 with form A, 6 with form B. */
+int vits_debug_persist_last_steps(void);
 /* Test hook: base re-arm interval in milliseconds (0 = VITS_PERSIST_REARM_MS or 1000). */
 void vits_debug_persist_rearm_ms(int ms);
 /* Test hook: persistent-program launches of this model that ran to completion (no timeout) since vits_create; -1 on error.

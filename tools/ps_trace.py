@@ -61,6 +61,10 @@ for s in range(n):
             b = a[a[:, 4] > 0]; g2 = got[a[:, 4] > 0]
             md = lambda x: float(np.median(x))
             print(f"        fused DDS phases (median cycles): start->poll done {md(g2 - b[:, 0]):.0f} | column work {md(b[:, 2] - g2):.0f} | matrix-vector {md(b[:, 4] - b[:, 2]):.0f} | sum + (spline +) stores {md(b[:, 3] - b[:, 4]):.0f}")
+        if kinds[s] == 6 and a[:, 4].max() > 0:  # fused merge step (conv_o, residual [+ LN1]; stamps 2 / 4 around the matrix-vector product)
+            b = a[a[:, 4] > 0]; g2 = got[a[:, 4] > 0]
+            md = lambda x: float(np.median(x))
+            print(f"        fused MERGE phases (median cycles): start->poll done {md(g2 - b[:, 0]):.0f} | merge -> column in LDS {md(b[:, 2] - g2):.0f} | matrix-vector {md(b[:, 4] - b[:, 2]):.0f} | sum (+ LN1) + stores {md(b[:, 3] - b[:, 4]):.0f}")
         if a[:, 6].max() > 0:
             md = lambda x: float(np.median(x))
             print(f"        MM phases (median cycles): start->poll done {md(got - a[:, 0]):.0f} | tile+barrier {md(a[:, 2] - got):.0f} | to MFMA loop {md(a[:, 7] - a[:, 2]):.0f} | MFMA loop {md(a[:, 4] - a[:, 7]):.0f} | res poll + partial tiles + barrier {md(a[:, 6] - a[:, 4]):.0f} | epilogue + stores {md(a[:, 3] - a[:, 6]):.0f}")

@@ -101,6 +101,12 @@ static std::atomic<long long> g_ps_off_until_ns{0};  // steady-clock ns; 0 = arm
 static std::atomic<long long> g_ps_rearmed_at_ns{0};
 static std::atomic<long long> g_ps_rearm_ns{0};      // current interval (0 = base)
 static std::atomic<int> g_ps_timeouts{0}, g_ps_rearms{0};
+// Attention half of the encoder layers in the programs (persist_plan.hip.h persist_attn_form): 0 = the planner's rule, 1 = never fused,
+// 2 = form A only, 3 = form B wherever it fits (vits_debug_persist_attn_fused / VITS_PERSIST_ATTN_FUSED: tests and A/B runs of bench.py).
+// Read by session_reserve: a session whose layout was planned under another value is planned again.
+static int ps_attn_mode_clamp(int mode) { return (mode < 0 || mode > 3) ? 0 : mode; }
+static std::atomic<int> g_ps_attn_fused{ps_attn_mode_clamp(getenv("VITS_PERSIST_ATTN_FUSED") ? atoi(getenv("VITS_PERSIST_ATTN_FUSED")) : 0)};
+static std::atomic<int> g_ps_last_steps{0};  // steps of the most recently launched program (vits_debug_persist_last_steps)
 static inline long long steady_ns() {
   return std::chrono::duration_cast<std::chrono::nanoseconds>(std::chrono::steady_clock::now().time_since_epoch()).count();
 }
@@ -545,6 +551,11 @@ void vits_debug_ln_stats(int on) { g_ln_stats = on; }
 void vits_debug_persist(int on) {  // (also arms the programs at once: a test that switches them on means now)
   g_persist = on;
   g_ps_off_until_ns.store(0); g_ps_rearm_ns.store(0); g_ps_rearmed_at_ns.store(0);
+}
+void vits_debug_persist_attn_fused(int mode) { g_ps_attn_fused = ps_attn_mode_clamp(mode); }
+int vits_debug_persist_last_steps(void) { return g_ps_last_steps.load(); }
+int vits_debug_persist_attn_form(int hidden, int padded_columns, int workers, int mode) {
+  return persist_attn_form(hidden, padded_columns, workers, mode, true);
 }
 void vits_debug_persist_when(int max_others_in_flight) { g_persist_when = max_others_in_flight < -1 ? -1 : max_others_in_flight; }
 void vits_debug_persist_rearm_ms(int ms) {

@@ -50,7 +50,9 @@ static void persist_launch(vits_session* s, vits_session::PersistProg& pp, const
     hipMalloc((void**)&c.trace, trace_n * sizeof(long long));
     hipMemsetAsync(c.trace, 0, trace_n * sizeof(long long), s->stream);
   }
-  hipLaunchKernelGGL(persist_kernel, dim3(m->n_cu), dim3(PS_THREADS), 0, s->stream, pp.d, c);
+  g_ps_last_steps.store(pp.h.n_steps, std::memory_order_relaxed);
+  if (pp.fused) hipLaunchKernelGGL(persist_kernel_fz, dim3(m->n_cu), dim3(PS_THREADS), 0, s->stream, pp.d, c);
+  else hipLaunchKernelGGL(persist_kernel, dim3(m->n_cu), dim3(PS_THREADS), 0, s->stream, pp.d, c);
   if (c.trace) {
     std::vector<long long> h(trace_n);
     hipMemcpyAsync(h.data(), c.trace, trace_n * sizeof(long long), hipMemcpyDeviceToHost, s->stream);

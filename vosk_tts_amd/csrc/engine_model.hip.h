@@ -13,6 +13,7 @@ struct ConvW {
 struct EncLayerW {
   ConvW qkv, o, f1, f2;
   float *ek = nullptr, *ev = nullptr, *g1 = nullptr, *b1 = nullptr, *g2 = nullptr, *b2 = nullptr;
+  float* o_wt = nullptr;  // conv_o's weight transposed like DDSW::wt (conv_wt4) for the fused merge step of the persistent programs, null when not built
 };
 struct EncoderW {
   std::vector<EncLayerW> layers;
@@ -350,6 +351,7 @@ static ConvW conv_from(vits_model* m, const char* name, int Cout, int Cin, int K
   return c;
 }
 
+static float* conv_wt4(vits_model* m, const char* name, int Cout, int Cin, bool for_dp = true);
 static void load_encoder(vits_model* m, EncoderW& E, const char* pfx, int n_layers, int H, int F, int K, int nh, int W) {
   const vits_hparams& hp = m->hp;
   const int dk = H / nh, NW = 2 * W + 1;
@@ -377,6 +379,7 @@ static void load_encoder(vits_model* m, EncoderW& E, const char* pfx, int n_laye
     if (bf3) add_bf3_packing(m, L.qkv, qkv_src);
     snprintf(nm, sizeof nm, "%s.attn_layers.%d.conv_o", pfx, i);
     L.o = conv_from(m, nm, H, H, 1, true, true, bf3);
+    L.o_wt = conv_wt4(m, nm, H, H, false);
     if (W >= 0) {
       L.ek = upload(m, tget(m, 3, 1, NW, dk, "%s.attn_layers.%d.emb_rel_k", pfx, i), (size_t)NW * dk);
       L.ev = upload(m, tget(m, 3, 1, NW, dk, "%s.attn_layers.%d.emb_rel_v", pfx, i), (size_t)NW * dk);
@@ -394,10 +397,12 @@ static void load_encoder(vits_model* m, EncoderW& E, const char* pfx, int n_laye
 
 // A 1x1 conv's weight [Cout][Cin] transposed to wt4[ci / 4][co][ci % 4], the layout of DDSW::wt: the conv as a matrix-vector product of
 // one column, thread = output channel, one dwordx4 per four input channels (persist.hip.h ps_mv_request).  Only for the geometries
-// the duration predictor's step program takes (persist_sdp_eligible); null otherwise.
-static float* conv_wt4(vits_model* m, const char* name, int Cout, int Cin) {
+// the duration predictor's step program takes (persist_sdp_eligible; for_dp) or, for an encoder layer's conv_o, the widths the fused
+// merge step takes (persist_attn_form); null otherwise.
+static float* conv_wt4(vits_model* m, const char* name, int Cout, int Cin, bool for_dp) {
   const vits_hparams& hp = m->hp;
-  if (Cin % 32 || Cin > PS_MAXC || hp.dp_kernel_size != 3 || hp.dp_dds_layers < 1 || hp.dp_dds_layers > 3 || hp.dp_n_flows < 2) return nullptr;
+  if (Cin % 32 || Cin > PS_MAXC) return nullptr;
+  if (for_dp && (hp.dp_kernel_size != 3 || hp.dp_dds_layers < 1 || hp.dp_dds_layers > 3 || hp.dp_n_flows < 2)) return nullptr;
   const float* w = tget(m, 3, Cout, Cin, 1, "%s.weight", name);
   if (!w || m->missing) return nullptr;
   std::vector<float> t((size_t)Cout * Cin);

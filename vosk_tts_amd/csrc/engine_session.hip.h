@@ -68,6 +68,7 @@ struct vits_session {
     ll_t* ll = nullptr;    // exchange cells
     size_t cells = 0;
     bool ok = false;
+    bool fused = false;    // a step of the program is a fused merge step (PK_MERGE | PF_MV): launched as persist_kernel_fz
     double flops = 0;
   };
   PersistProg ps_enc, ps_sdp, ps_flow;
@@ -77,6 +78,7 @@ struct vits_session {
   PersistProg ps_front[2], ps_back, ps_full[2], ps_x;
   ll_t *ps_x_stats = nullptr, *ps_x_logw = nullptr, *ps_x_cum = nullptr, *ps_x_leny = nullptr, *ps_x_zp = nullptr;
   int ps_planned_roles = -1;  // ps_roles of the current layout (a change of roles re-plans like a change of shape)
+  int ps_attn_mode = 0;    // vits_debug_persist_attn_fused as session_reserve found it: cells and programs of ONE layout follow one value
   int ps_roles = 7;        // PERSIST_* mask of the programs this session can ever launch: fronts of the fast path run the text encoder and the
                            // duration predictor, their backs the flow -- cells and records are only laid out / built for those
   bool ps_defer = false;   // the owner calls persist_plan itself after re-pointing shared tensors (backs): session_reserve skips it
@@ -262,11 +264,11 @@ static void plan(vits_session* s, int B, int Tx, int Ty) {
   s->dc = bump<float>(s, B * D * Tx); s->dfh = bump<float>(s, B * D * Tx);
   s->dq1 = bump<float>(s, B * D * Tx); s->dq2 = bump<float>(s, B * D * Tx);
   s->dz = bump<float>(s, (size_t)B * 2 * Tx); s->dpr = bump<float>(s, (size_t)B * 32 * Tx); s->logw = bump<float>(s, (size_t)B * Tx);
-  s->ps_enc.cells = (s->ps_roles & PERSIST_ENC) ? persist_enc_cells(s->m, B, Tx) : 0;
+  s->ps_enc.cells = (s->ps_roles & PERSIST_ENC) ? persist_enc_cells(s->m, B, Tx, s->ps_attn_mode) : 0;
   s->ps_enc.ll = bump<ll_t>(s, s->ps_enc.cells);
   s->ps_sdp.cells = (s->ps_roles & PERSIST_SDP) ? persist_sdp_cells(s->m, B, Tx) : 0;
   s->ps_sdp.ll = bump<ll_t>(s, s->ps_sdp.cells);
-  s->ps_flow.cells = (s->ps_roles & PERSIST_FLOW) ? persist_flow_cells(s->m, B, Ty) : 0;
+  s->ps_flow.cells = (s->ps_roles & PERSIST_FLOW) ? persist_flow_cells(s->m, B, Ty, s->ps_attn_mode) : 0;
   s->ps_flow.ll = bump<ll_t>(s, s->ps_flow.cells);
   {
     // cells of the multi-stage programs: stats [Tp_x][2I], logw [Tp_x], cum [Tp_x], frame count, z_p [Tp_y][I]
@@ -309,7 +311,16 @@ static void drop_graphs(vits_session* s) {
 // (re)lays the workspace out for exactly (B,Tx,Ty) so every [B,C,T] tensor is dense; grows the
 // arena when needed.  Captured graphs hold raw workspace pointers, so a re-plan drops them.
 static int session_reserve(vits_session* s, int B, int Tx, int Ty) {
-  if (s->arena && B == s->B && Tx == s->Tx && Ty == s->Ty && s->ps_planned_roles == s->ps_roles) return VITS_OK;
+  int attn_mode = g_ps_attn_fused.load(std::memory_order_relaxed);
+  // A session whose programs cover both sides of the forward fuses the attention half only when the flow takes a fused form too: the
+  // kernel with the fused step compiled in (persist_kernel_fz) runs every OTHER step of its program slower than persist_kernel does
+  // (~13 us over the c2 program), which the text encoder's six fused layers alone do not pay back -- 100 tokens / 300 frames measured
+  // 1.2336 against 1.2240 ms per forward (profiles/persist_attn_fused_bench.txt).  Such a session is planned as "never fused".
+  if (attn_mode != 1 && (s->ps_roles & PERSIST_ENC) && (s->ps_roles & PERSIST_FLOW) && persist_flow_eligible(s->m, B, Ty) &&
+      persist_attn_form(s->m, s->m->flow[0].enc, cdiv(Ty, 16) * 16, attn_mode) == 0)
+    attn_mode = 1;
+  if (s->arena && B == s->B && Tx == s->Tx && Ty == s->Ty && s->ps_planned_roles == s->ps_roles && s->ps_attn_mode == attn_mode) return VITS_OK;
+  s->ps_attn_mode = attn_mode;
   {
     // the batch-size conv kernels address one item's [C, T] tensor with 32-bit byte offsets (buffer loads, conv_mfma.hip.h bt_ld):
     // every per-item tensor must stay below 2 GiB.  The widest are the decoder stages, C_i x T_y x prod(rates[0..i]).

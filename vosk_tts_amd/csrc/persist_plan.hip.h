@@ -91,11 +91,33 @@ static size_t persist_sdp_cells(const vits_model* m, int B, int Tx) {
   return Tp * (D * (1 + nf * per_stack) + 2 * (nf + 1));
 }
 
+// Fused form of the attention half of an encoder layer (persist_encoder_layer): the merge column step also runs conv_o + the residual
+// on its column (persist.hip.h PK_MERGE | PF_MV).  Returns 0 = the three steps MERGE, conv_o, LN1;  w in 1..4 = form A: w workers per
+// column, each with ceil(H / w) <= 64 output channels in one pass, LN1 stays a step;  -1 = form B: one worker per column, all H
+// channels in ceil(H / 64) passes, LN1 inside the step.  `mode` (vits_debug_persist_attn_fused): 0 = the rule, 1 = never, 2 = form A
+// only, 3 = form B wherever it fits.  The rule is form B wherever it fits (one round of columns): measured at c2
+// (profiles/persist_attn_fused_bench.txt) form A alone is slower than the parent and form B everywhere is the fastest program; form A
+// (H = 192: 4 workers up to 64 columns, 3 up to 80) stays reachable through mode 2 and shares form B's device path.
+static int persist_attn_form(int H, int Tp, int P, int mode, bool have_wt) {
+  if (mode == 1 || !have_wt || H % 32 || H / 32 > PS_MAXU || Tp < 16 || Tp > P) return 0;
+  const int w = std::min(4, P / Tp);
+  if (mode == 2) return (w >= 1 && cdiv(H, w) <= 64) ? w : 0;
+  return -1;  // (H <= 256: at most 4 passes of 64.  Form B: at c2 form A alone measured slower than the parent, form B everywhere fastest)
+}
+static int persist_attn_form(const vits_model* m, const EncoderW& E, int Tp, int mode) {
+  bool have = !E.layers.empty();
+  for (const EncLayerW& L : E.layers) have = have && L.o_wt && L.o.K == 1 && L.o.Cin == E.H && L.o.M == E.H && L.o.bias;
+  return persist_attn_form(E.H, Tp, m->n_cu, mode, have);
+}
+
 // ---- one attentions.Encoder layer: qkv, attention partials, merged attention, y1, x1, FFN hidden, FFN partials, output
-static size_t persist_enc_layer_cells(const vits_model* m, const EncoderW& E, size_t Tp) {
+// (fused attention half: form A takes no cells for the merged attention, form B none for y1 either)
+static size_t persist_enc_layer_cells(const vits_model* m, const EncoderW& E, size_t Tp, int amode) {
   const size_t H = E.H, F = E.F, nh = E.nh, dk = H / nh, ntn = Tp / 16;
   const size_t ks2 = E.layers[0].f2.Cin / persist_slice(E.layers[0].f2.Cin, E.layers[0].f2.K);
-  return Tp * (3 * H + ntn * nh * (dk + 2) + H + H + H + F + ks2 * H + H);
+  const int form = persist_attn_form(m, E, (int)Tp, amode);
+  const size_t att_y1_x1 = form == 0 ? 3 * H : (form > 0 ? 2 * H : H);
+  return Tp * (3 * H + ntn * nh * (dk + 2) + att_y1_x1 + F + ks2 * H + H);
 }
 static bool persist_enc_eligible(const vits_model* m, int B, int Tx) {
   const vits_hparams& hp = m->hp;
@@ -105,12 +127,12 @@ static bool persist_enc_eligible(const vits_model* m, int B, int Tx) {
   if (hp.bert_dim > 0 && (!persist_conv_ok(m->bert_proj) || m->bert_proj.K != 1)) return false;
   return 4 + 8 * (int)m->enc_p.layers.size() <= PS_MAX_STEPS;
 }
-static size_t persist_enc_cells(const vits_model* m, int B, int Tx) {
+static size_t persist_enc_cells(const vits_model* m, int B, int Tx, int amode) {
   if (!persist_enc_eligible(m, B, Tx)) return 0;
   const size_t Tp = (size_t)cdiv(Tx, 16) * 16, H = m->hp.hidden_channels;
   size_t bert = 0;
   if (m->hp.bert_dim > 0) bert = Tp * H * (m->bert_proj.Cin / persist_slice(m->bert_proj.Cin, 1) + 1);  // K-slice partials + the sum
-  return Tp * H + bert + m->enc_p.layers.size() * persist_enc_layer_cells(m, m->enc_p, Tp);
+  return Tp * H + bert + m->enc_p.layers.size() * persist_enc_layer_cells(m, m->enc_p, Tp, amode);
 }
 
 // ---- flow (ResidualCouplingTransformersBlock reverse, folded WaveNet tail)
@@ -128,12 +150,12 @@ static bool persist_flow_eligible(const vits_model* m, int B, int Ty) {
   }
   return hp.flow_n_flows * (11 + 2 * L) <= PS_MAX_STEPS;
 }
-static size_t persist_flow_cells(const vits_model* m, int B, int Ty) {
+static size_t persist_flow_cells(const vits_model* m, int B, int Ty, int amode) {
   if (!persist_flow_eligible(m, B, Ty)) return 0;
   const vits_hparams& hp = m->hp;
   const size_t Tp = (size_t)cdiv(Ty, 16) * 16, H = hp.hidden_channels, I = hp.inter_channels, L = hp.flow_wn_layers;
   // per coupling layer: pre output, the encoder layer, stacked gate outputs, L - 1 residual streams, L post partials, the new z
-  const size_t per = Tp * (H + L * H + (L - 1) * H + L * (I / 2) + I) + persist_enc_layer_cells(m, m->flow[0].enc, Tp);
+  const size_t per = Tp * (H + L * H + (L - 1) * H + L * (I / 2) + I) + persist_enc_layer_cells(m, m->flow[0].enc, Tp, amode);
   return per * hp.flow_n_flows;
 }
 
@@ -249,6 +271,7 @@ struct PBuild {
   ll_t* cur;
   ll_t* end;
   int T, Tp, ntn;
+  int amode = 0;              // vits_debug_persist_attn_fused as the session's layout was planned (persist_attn_form)
   double flops = 0;
   bool overflow = false;
   ll_t* take(size_t cells) {
@@ -342,19 +365,35 @@ static const ll_t* persist_encoder_layer(PBuild& b, const EncLayerW& L, const En
   const ll_t* ap = b.push(st).ap;
   st = b.blank(PK_MERGE);
   st.C = H; st.nh = nh; st.dk = dk; st.ap = const_cast<ll_t*>(ap);
-  st.out = b.take_rows(H);
-  const ll_t* att = b.push(st).out;
-  // y1 = x + conv_o(att)
-  st = b.mm(L.o, att, H);
-  st.res = x; st.rpitch = H;
-  st.yout = b.take_rows(H);
-  const ll_t* y1 = b.push(st).yout;
-  // x1 = norm_layers_1(y1)
-  st = b.blank(PK_LN);
-  b.col_par(st, H, L.g1, L.b1, nullptr, nullptr);
-  st.np = 1; st.ln = 1; st.part = y1; st.part_stride = 0;
-  st.out = b.take_rows(H);
-  const ll_t* x1 = b.push(st).out;
+  // Fused forms (persist_attn_form): the worker that merges a column has all its H attention channels, so conv_o -- a matrix-vector
+  // product of exactly that column -- and the residual run in the merge step; the merged attention is never written.  Form A: LN1 stays
+  // the next step.  Form B: the one worker of a column has all of y1 too and ends with LN1; y1 is not written either.
+  const int form = persist_attn_form(m, E, Tp, b.amode);
+  const ll_t* x1;
+  if (form != 0) {
+    st.mv_split = form > 0 ? form : 1; st.mv_cout = H; st.mv_wt = L.o_wt; st.mv_bias = L.o.bias; st.res = x;
+    b.flops += 2.0 * b.T * (double)H * H;
+    if (form < 0) { st.ln = 1; st.plen = H; st.par[0] = L.g1; st.par[1] = L.b1; }
+    st.out = b.take_rows(H);  // y1 (form A) / x1 (form B)
+    x1 = b.push(st).out;
+  } else {
+    st.out = b.take_rows(H);
+    const ll_t* att = b.push(st).out;
+    // y1 = x + conv_o(att)
+    st = b.mm(L.o, att, H);
+    st.res = x; st.rpitch = H;
+    st.yout = b.take_rows(H);
+    x1 = b.push(st).yout;
+  }
+  if (form >= 0) {
+    // x1 = norm_layers_1(y1)
+    const ll_t* y1 = x1;
+    st = b.blank(PK_LN);
+    b.col_par(st, H, L.g1, L.b1, nullptr, nullptr);
+    st.np = 1; st.ln = 1; st.part = y1; st.part_stride = 0;
+    st.out = b.take_rows(H);
+    x1 = b.push(st).out;
+  }
   // FFN (attentions.py:308-317): conv_1(pad(x * mask)) -> relu -> * mask -> conv_2(pad(.)) -> * mask
   st = b.mm(L.f1, x1, H);
   st.in_mask = 1; st.relu = 1; st.out_mask = 1;
@@ -510,14 +549,15 @@ static void persist_resolve(vits_session* s, const std::vector<PStep>& steps, in
     } else {
       PRec* R = nullptr;
       const float* pack = m->zeros;
-      if (st.kind != PK_MERGE && st.kind != PK_EMB) {
+      if (st.kind == PK_MERGE ? st.ln != 0 : st.kind != PK_EMB) {  // (a merge step has parameters only where it ends with LayerNorm 1)
         pack = persist_pack(s, st.par, st.padd, st.plen, 256);
         if (!pack) { bad = true; return; }
       }
       // fused DDSConv steps: mv_split workers per column, worker = column * mv_split + part -- with 2 or 4 parts the workers that stream
-      // the same slice of the weights sit on the same XCDs (block b runs on XCD b % 8).  One round only (seg_sdp).
-      const int sp = (st.kind == PK_DDS && st.mv_split > 0) ? st.mv_split : 1;
-      if (sp > 1 && Tp * sp > P) { bad = true; return; }
+      // the same slice of the weights sit on the same XCDs (block b runs on XCD b % 8).  One round only (seg_sdp).  The fused merge
+      // steps of the encoder layers (persist_attn_form) are laid out the same way.
+      const int sp = ((st.kind == PK_DDS || st.kind == PK_MERGE) && st.mv_split > 0) ? st.mv_split : 1;
+      if (((sp > 1) || (st.kind == PK_MERGE && st.mv_split > 0)) && Tp * sp > P) { bad = true; return; }
       for (int item = 0; item < Tp * sp; ++item) {
         const int t = item / sp, part = item % sp;
         if (item % P == 0) R = new_step();  // (a round of P columns per step)
@@ -563,6 +603,18 @@ static void persist_resolve(vits_session* s, const std::vector<PStep>& steps, in
           r.a3 = st.dk | (st.nh << 8);
           r.p[0] = U(st.ap);
           r.b[0] = Tp * st.nh * (st.dk + 2);
+          r.b[1] = 1; r.b[3] = 1;
+          if (st.mv_split > 0) {  // conv_o + residual (+ LN1 where one worker has the whole column) on this worker's output channels
+            const int per = cdiv(st.mv_cout, sp), o0 = part * per, n = std::min(per, st.mv_cout - o0);
+            if (n < 1 || (sp > 1 && per > 64) || n > PS_MAXC || st.mv_cout != st.C || st.C != st.nh * st.dk || st.C % 32 || st.C / 32 > PS_MAXU || !st.res ||
+                (st.ln && sp != 1)) { bad = true; return; }
+            r.kf |= PF_MV | (st.ln ? PF_LN : 0);
+            r.p[1] = U(st.res + o0);
+            r.p[3] = U(st.out + o0);
+            r.p[6] = U(st.mv_wt + (size_t)o0 * 4);
+            r.p[7] = U(st.mv_bias + o0);
+            r.b[1] = n; r.b[2] = st.mv_cout * 16; r.b[3] = st.C / 32;
+          }
         } else {  // PK_COUPLE
           r.kf = PK_COUPLE | (st.u_plain ? PF_PLAIN_IN : 0);
           r.a3 = st.np | (st.H << 16);
@@ -597,6 +649,8 @@ static void persist_upload(vits_session* s, vits_session::PersistProg& pp, PBuil
   pp.h.n_steps = (int)(recs.size() / P);
   pp.h.P = P;
   pp.h.recs = pp.recs_d;
+  pp.fused = false;
+  for (const PRec& r : recs) if ((r.kf & 0xff) == PK_MERGE && (r.kf & PF_MV)) { pp.fused = true; break; }
   pp.kinds.clear();
   for (int i = 0; i < pp.h.n_steps; ++i) {  // (for tools/ps_trace.py: the kind of a step = the kind of its first busy worker)
     int k = 0;
@@ -619,6 +673,7 @@ static void persist_begin(vits_session* s, vits_session::PersistProg& pp, PBuild
   steps.clear();
   steps.reserve(PS_MAX_STEPS + 1);
   b.m = m; b.steps = &steps; b.cur = pp.ll; b.end = pp.ll + pp.cells;
+  b.amode = s->ps_attn_mode;
   seg_geom(b, T);
   PProgram& P = pp.h;
   P.T = T; P.Tp = b.Tp;
