@@ -121,6 +121,7 @@ static int persist_cfg() {
   return cfg;
 }
 
+#include "ctx_cache.hip.h"
 #include "engine_model.hip.h"
 #include "engine_session.hip.h"
 #include "engine_convplan.hip.h"
@@ -205,7 +206,7 @@ void vits_destroy(vits_model* m) {
   }
   hipSetDevice(m->device);
   for (vits_session* s : m->pool) session_free(s);
-  for (auto& kv : m->fronts) session_free(kv.second);
+  for (FastFront* F : m->fronts.take_all()) front_free(F);
   for (void* a : m->allocs) hipFree(a);
   const int dev = m->device;
   delete m;

@@ -11,15 +11,17 @@
 //     item (exactly the ragged-batch machinery), and the decoder of a bucketed single utterance reads zeros beyond the
 //     item's own end at every stage (rag halo 0) -- the arithmetic of the exact-size run on every valid sample;
 //   * T_y is only known after the duration predictor: phase 1 (text encoder .. durations) is one graph of a FRONT
-//     session keyed by (B, T_x bucket); phase 2 (prior sample, flow, decoder, optional int16 conversion, D2H) one graph of
-//     a BACK session per frame bucket, which reads the front's stats / cum / cond vectors / lengths in place.
-// Per call: fill the pinned block, launch graph 1, wait (the one host round trip the path needs), launch graph 2, wait,
-// copy out.  No hipMalloc / hipFree / re-plan in steady state.  Calls that inject noise tensors (parity tests) take the
-// eager path below (vits_synthesize_eager), which is also the A/B reference of the fast path in tests.
+//     context (FastFront) keyed by (B, T_x bucket); phase 2 (prior sample, flow, decoder, optional int16 conversion, D2H) one
+//     graph of a BACK context (FastBack) per frame bucket, which reads the front's stats / cum / cond vectors / lengths in place.
+// Per call: take an idle front out of the model's cache (or build one), fill the pinned block, launch graph 1, wait (the one host
+// round trip the path needs), find or build the back, launch graph 2, wait, copy out, put the front back.  No hipMalloc / hipFree /
+// re-plan in steady state.  Who is kept and who goes is ctx_cache.hip.h (IdleCache of fronts per model, LruSlots of backs per front
+// and of rates per back; the caps are named there); what a context owns and how it is freed is below.  Calls that inject noise
+// tensors (parity tests) take the eager path below (synth_eager), which is also the A/B reference of the fast path in tests.
 static thread_local int g_fast_path = 1;
-// cap on the device memory idle fast-path sessions may pin per model: VITS_CACHE_MB, else a quarter of what was free on the device
+// cap on the device memory idle fast-path contexts may pin per model: VITS_CACHE_MB, else a quarter of what was free on the device
 // when the first call asked (at most 24 GiB).  Besides the cap, an allocation failure on the request path evicts every idle
-// session and retries once (fronts_evict_all).
+// front and retries once (retry_nomem, fronts_evict_all).
 static size_t fast_cache_cap() {
   static const size_t cap = [] {
     if (getenv("VITS_CACHE_MB")) return (size_t)atol(getenv("VITS_CACHE_MB")) << 20;
@@ -31,160 +33,207 @@ static size_t fast_cache_cap() {
   return cap;
 }
 
-static size_t session_device_bytes(const vits_session* s) {
-  size_t n = s->arena_bytes + s->io_bytes + s->out_elems * (sizeof(float) + sizeof(int16_t));
-  if (s->marks_d) n += sizeof(long long) * (size_t)s->B * s->Tx;
-  for (auto& kv : s->rates) n += (size_t)s->B * kv.second.n_cap * sizeof(float) + loud_ws_bytes(kv.second.lw);
-  n += loud_ws_bytes(s->lw);
-  for (auto& kv : s->backs) n += session_device_bytes(kv.second);
+// ---- the two contexts.  Each owns a session (`s`: workspace, error word, the fields the stages read) and, next to it, exactly what
+// its phase of the call needs; front_free / back_free / rate_free release exactly that.
+// BACK: phase 2 of one frame bucket.  Its session borrows the front's stream.
+struct FastBack {
+  vits_session* s = nullptr;
+  float* out_d = nullptr;          // fp32 audio [B, T_y bucket * hop] on the device
+  int16_t* pcm_d = nullptr;        // int16 PCM, same shape
+  char* out_h = nullptr;           // pinned host copy of whichever output the call asked for
+  size_t out_elems = 0;
+  int* h_err = nullptr;            // pinned copy of s->d_err, written by the phase-2 graph
+  hipGraphExec_t g2[8] = {};       // [persist*4 + solo*2 + pcm]
+  // phase 2 at another output rate (include/vits_resample.h).  The rate changes a launch and the size of the output, so it is part of
+  // the graph key: one entry per rate, with its own graphs and its own output buffers [B, ceil(T_y bucket * hop * L / M)].
+  struct RateOut {
+    hipGraphExec_t g2[8] = {};     // as g2 above
+    void* y_d = nullptr;           // device: float or int16 (sized for float)
+    char* y_h = nullptr;           // pinned host copy
+    long long n_cap = 0;           // outputs per item
+    LoudWs* lw = nullptr;          // as FastBack::lw below
+  };
+  LruSlots<int, RateOut> rates;    // by rate_out
+  LoudWs* lw = nullptr;            // scratch and output buffers of the calls with VITS_FLAG_LOUDNESS, allocated by the first of them
+};
+// FRONT: phase 1 of one (B, T_x bucket), the call's stream, its input block and its backs.
+struct FastFront {
+  vits_session* s = nullptr;
+  char *io_h = nullptr, *io_d = nullptr;  // per-call inputs: pinned host mirror and device copy (SynthDev | lengths | sid | ids | forced | seeds [| bert])
+  size_t io_bytes = 0, io_len = 0, io_sid = 0, io_ids = 0, io_forced = 0, io_seeds = 0, io_bert = 0;  // io_bert: float [B, bert_dim, TxB] (BERT-conditioned voices), 0 = none
+  int64_t* h_ylen = nullptr;       // pinned [B] + one int error word behind it
+  hipGraphExec_t g1[16] = {};      // [marks*8 + persist*4 + forced*2 + solo]; a call without marks only ever touches 0..7
+  // speech marks (include/vits_marks.h): token ends int64 [B, T_x bucket] on the device and their pinned copy, allocated by the first
+  // request that asks for marks; the marks variants of g1 write and copy them in front of the h_ylen copy
+  long long* marks_d = nullptr;
+  int64_t* marks_h = nullptr;
+  LruSlots<int, FastBack> backs;   // by frame bucket
+};
+
+// (every free of a rate or a back comes after a wait on the front's stream: their graphs and buffers may still be queued there)
+static void rate_free(FastBack::RateOut* R) {
+  for (hipGraphExec_t g : R->g2) if (g) hipGraphExecDestroy(g);
+  if (R->y_d) hipFree(R->y_d);
+  if (R->y_h) hipHostFree(R->y_h);
+  loud_ws_delete(R->lw);
+  delete R;
+}
+static void back_free(FastBack* Bk) {
+  for (FastBack::RateOut* R : Bk->rates.drain()) rate_free(R);
+  loud_ws_delete(Bk->lw);
+  for (hipGraphExec_t g : Bk->g2) if (g) hipGraphExecDestroy(g);
+  if (Bk->out_d) hipFree(Bk->out_d);
+  if (Bk->pcm_d) hipFree(Bk->pcm_d);
+  if (Bk->out_h) hipHostFree(Bk->out_h);
+  if (Bk->h_err) hipHostFree(Bk->h_err);
+  session_unborrow(Bk->s);
+  delete Bk;
+}
+static void front_drop_backs(FastFront* F) {
+  hipStreamSynchronize(F->s->stream);
+  for (FastBack* Bk : F->backs.drain()) back_free(Bk);
+}
+static void front_free(FastFront* F) {
+  if (!F) return;
+  if (F->s) {
+    hipSetDevice(F->s->m->device);
+    front_drop_backs(F);
+  }
+  for (hipGraphExec_t g : F->g1) if (g) hipGraphExecDestroy(g);
+  if (F->marks_d) hipFree(F->marks_d);
+  if (F->marks_h) hipHostFree(F->marks_h);
+  if (F->io_h) hipHostFree(F->io_h);
+  if (F->io_d) hipFree(F->io_d);
+  if (F->h_ylen) hipHostFree(F->h_ylen);
+  session_free(F->s);
+  delete F;
+}
+
+// device bytes a context pins while it is cached (a front: with its backs)
+static size_t back_device_bytes(const FastBack* Bk) {
+  size_t n = Bk->s->arena_bytes + Bk->out_elems * (sizeof(float) + sizeof(int16_t)) + loud_ws_bytes(Bk->lw);
+  Bk->rates.for_each([&](const FastBack::RateOut& R) { n += (size_t)Bk->s->B * R.n_cap * sizeof(float) + loud_ws_bytes(R.lw); });
+  return n;
+}
+static size_t front_device_bytes(const FastFront* F) {
+  size_t n = F->s->arena_bytes + F->io_bytes;
+  if (F->marks_d) n += sizeof(long long) * (size_t)F->s->B * F->s->Tx;
+  F->backs.for_each([&](const FastBack& Bk) { n += back_device_bytes(&Bk); });
   return n;
 }
 
-static int front_acquire(vits_model* m, int B, int TxB, vits_session** out) {
-  {
-    std::lock_guard<std::mutex> g(m->pool_mu);
-    auto it = m->fronts.find(std::make_pair(B, TxB));
-    if (it != m->fronts.end()) {
-      *out = it->second;
-      m->fronts_bytes -= it->second->cache_bytes;
-      m->fronts.erase(it);
-      return VITS_OK;
-    }
-  }
-  vits_session* s = nullptr;
-  TRY(session_new(m, &s));
+static int front_acquire(vits_model* m, int B, int TxB, FastFront** out) {
+  if ((*out = m->fronts.take(std::make_pair(B, TxB)))) return VITS_OK;
+  FastFront* F = new FastFront();
+  int rc = session_new(m, &F->s);
+  if (rc != VITS_OK) { front_free(F); return rc; }
+  vits_session* s = F->s;
   s->ps_roles = PERSIST_ENC | PERSIST_SDP;
   // per-call input block: [SynthDev | lengths int64 [B] | sid int64 [B] | ids int64 [B,TxB] | forced int32 [B,TxB]]
   // (allocated BEFORE the workspace is laid out: the text-encoder program of a BERT-conditioned voice is resolved against io_d + io_bert)
-  s->io_len = align_up(sizeof(SynthDev), 64);
-  s->io_sid = s->io_len + align_up(sizeof(int64_t) * B, 64);
-  s->io_ids = s->io_sid + align_up(sizeof(int64_t) * B, 64);
-  s->io_forced = s->io_ids + align_up(sizeof(int64_t) * (size_t)B * TxB, 64);
-  s->io_seeds = s->io_forced + align_up(sizeof(int32_t) * (size_t)B * TxB, 64);
-  s->io_bytes = s->io_seeds + align_up(sizeof(unsigned long long) * B, 64);
+  F->io_len = align_up(sizeof(SynthDev), 64);
+  F->io_sid = F->io_len + align_up(sizeof(int64_t) * B, 64);
+  F->io_ids = F->io_sid + align_up(sizeof(int64_t) * B, 64);
+  F->io_forced = F->io_ids + align_up(sizeof(int64_t) * (size_t)B * TxB, 64);
+  F->io_seeds = F->io_forced + align_up(sizeof(int32_t) * (size_t)B * TxB, 64);
+  F->io_bytes = F->io_seeds + align_up(sizeof(unsigned long long) * B, 64);
   if (m->hp.bert_dim > 0) {  // the `bert` feed of a BERT-conditioned voice (vosk_tts/synth.py:88-99) rides in the same block: [B, bert_dim, TxB]
-    s->io_bert = s->io_bytes;
-    s->io_bytes += align_up(sizeof(float) * (size_t)B * m->hp.bert_dim * TxB, 64) + 256;  // (+ slack: the program's operand window reads whole 16-column tiles)
+    F->io_bert = F->io_bytes;
+    F->io_bytes += align_up(sizeof(float) * (size_t)B * m->hp.bert_dim * TxB, 64) + 256;  // (+ slack: the program's operand window reads whole 16-column tiles)
   }
-  if (hipHostMalloc((void**)&s->io_h, s->io_bytes) != hipSuccess || hipMalloc((void**)&s->io_d, s->io_bytes) != hipSuccess ||
-      hipHostMalloc((void**)&s->h_ylen, sizeof(int64_t) * (B + 1)) != hipSuccess) {
-    session_free(s);
+  if (hipHostMalloc((void**)&F->io_h, F->io_bytes) != hipSuccess || hipMalloc((void**)&F->io_d, F->io_bytes) != hipSuccess ||
+      hipHostMalloc((void**)&F->h_ylen, sizeof(int64_t) * (B + 1)) != hipSuccess) {
+    front_free(F);
     return fail(VITS_ERR_NOMEM, "fast-path staging buffers");
   }
-  memset(s->io_h, 0, s->io_bytes);
-  if (s->io_bert && B == 1) s->ps_bert = reinterpret_cast<const float*>(s->io_d + s->io_bert);
-  const int rc = session_reserve(s, B, TxB, 1);
-  if (rc != VITS_OK) { session_free(s); return rc; }
-  *out = s;
+  memset(F->io_h, 0, F->io_bytes);
+  if (F->io_bert && B == 1) s->ps_bert = reinterpret_cast<const float*>(F->io_d + F->io_bert);
+  rc = session_reserve(s, B, TxB, 1);
+  if (rc != VITS_OK) { front_free(F); return rc; }
+  *out = F;
   return VITS_OK;
 }
 
-static void front_release(vits_model* m, vits_session* s) {
-  std::vector<vits_session*> evict;
-  {
-    std::lock_guard<std::mutex> g(m->pool_mu);
-    s->last_use = ++m->use_clock;
-    s->cache_bytes = session_device_bytes(s);
-    m->fronts.emplace(std::make_pair(s->B, s->Tx), s);
-    m->fronts_bytes += s->cache_bytes;
-    while ((m->fronts_bytes > fast_cache_cap() && m->fronts.size() > 1) || m->fronts.size() > 48) {
-      auto lru = m->fronts.begin();
-      for (auto it = m->fronts.begin(); it != m->fronts.end(); ++it)
-        if (it->second->last_use < lru->second->last_use) lru = it;
-      m->fronts_bytes -= lru->second->cache_bytes;
-      evict.push_back(lru->second);
-      m->fronts.erase(lru);
-    }
-  }
-  for (vits_session* e : evict) session_free(e);
+static void front_release(vits_model* m, FastFront* F) {
+  for (FastFront* e : m->fronts.put(std::make_pair(F->s->B, F->s->Tx), F, front_device_bytes(F))) front_free(e);
 }
 
 // frees every idle front (and its backs): the answer to a failed allocation on the request path
 static void fronts_evict_all(vits_model* m) {
-  std::vector<vits_session*> evict;
-  {
-    std::lock_guard<std::mutex> g(m->pool_mu);
-    for (auto& kv : m->fronts) evict.push_back(kv.second);
-    m->fronts.clear();
-    m->fronts_bytes = 0;
-  }
-  for (vits_session* e : evict) session_free(e);
+  for (FastFront* e : m->fronts.take_all()) front_free(e);
   (void)hipGetLastError();
 }
+extern "C++" {  // (two templates; this file is included inside engine.hip's extern "C")
+// that answer itself: what failed for want of memory is tried once more after `relieve` has freed what the call can spare
+template <typename Try, typename Relieve>
+static int retry_nomem(Try attempt, Relieve relieve) {
+  int rc = attempt();
+  if (rc == VITS_ERR_NOMEM) { relieve(); rc = attempt(); }
+  return rc;
+}
 
-// back session of `F` for frame bucket TyB (created on first use; at most 6 buckets stay cached per front)
-static int back_get(vits_session* F, int TyB, vits_session** out) {
-  auto it = F->backs.find(TyB);
-  if (it != F->backs.end()) { it->second->last_use = ++F->last_use; *out = it->second; return VITS_OK; }
-  if (F->backs.size() >= 6) {
-    auto lru = F->backs.begin();
-    for (auto jt = F->backs.begin(); jt != F->backs.end(); ++jt)
-      if (jt->second->last_use < lru->second->last_use) lru = jt;
-    hipStreamSynchronize(F->stream);
-    session_free(lru->second);
-    F->backs.erase(lru);
+// rows of Tx values -> rows of the bucket TxB, bucket columns zero
+template <typename T>
+static void pad_rows(T* dst, const T* src, size_t rows, int Tx, int TxB) {
+  for (size_t r = 0; r < rows; ++r) {
+    memcpy(dst + r * TxB, src + r * Tx, sizeof(T) * Tx);
+    for (int t = Tx; t < TxB; ++t) dst[r * TxB + t] = 0;
   }
-  vits_model* m = F->m;
-  vits_session* s = new vits_session();
-  s->m = m;
-  s->stream = F->stream;
-  s->own_stream = false;
-  s->front = F;
-  int rc = VITS_OK;
-  if (hipMalloc((void**)&s->d_err, sizeof(int)) != hipSuccess || hipMemsetAsync(s->d_err, 0, sizeof(int), s->stream) != hipSuccess)
-    rc = fail(VITS_ERR_NOMEM, "back session");
+}
+}  // extern "C++"
+
+// back context of `F` for frame bucket TyB (created on first use; at most VITS_BACKS_PER_FRONT buckets stay cached per front)
+static int back_get(FastFront* F, int TyB, FastBack** out) {
+  if ((*out = F->backs.find(TyB))) return VITS_OK;
+  if (FastBack* lru = F->backs.make_room(VITS_BACKS_PER_FRONT)) {
+    hipStreamSynchronize(F->s->stream);
+    back_free(lru);
+  }
+  vits_model* m = F->s->m;
+  FastBack* Bk = new FastBack();
+  int rc = session_borrow(m, F->s->stream, "back session", &Bk->s);
+  if (rc != VITS_OK) { back_free(Bk); return rc; }
+  vits_session* s = Bk->s;
   s->ps_roles = PERSIST_FLOW;
   s->ps_defer = true;  // planned below, once the shared tensors point into the front
-  if (rc == VITS_OK) rc = session_reserve(s, F->B, F->Tx, TyB);
-  s->out_elems = (size_t)F->B * TyB * m->hp.hop_length;
-  if (rc == VITS_OK && (hipMalloc((void**)&s->out_d, s->out_elems * sizeof(float)) != hipSuccess ||
-                        hipMalloc((void**)&s->pcm_d, s->out_elems * sizeof(int16_t)) != hipSuccess ||
-                        hipHostMalloc((void**)&s->out_h, s->out_elems * sizeof(float)) != hipSuccess ||
-                        hipHostMalloc((void**)&s->h_err, 64) != hipSuccess))
-    rc = fail(VITS_ERR_NOMEM, "fast-path output buffers (%zu samples)", s->out_elems);
-  if (s->h_err) *s->h_err = 0;
-  if (rc != VITS_OK) { s->stream = nullptr; session_free(s); return rc; }
+  rc = session_reserve(s, F->s->B, F->s->Tx, TyB);
+  Bk->out_elems = (size_t)F->s->B * TyB * m->hp.hop_length;
+  if (rc == VITS_OK && (hipMalloc((void**)&Bk->out_d, Bk->out_elems * sizeof(float)) != hipSuccess ||
+                        hipMalloc((void**)&Bk->pcm_d, Bk->out_elems * sizeof(int16_t)) != hipSuccess ||
+                        hipHostMalloc((void**)&Bk->out_h, Bk->out_elems * sizeof(float)) != hipSuccess ||
+                        hipHostMalloc((void**)&Bk->h_err, 64) != hipSuccess))
+    rc = fail(VITS_ERR_NOMEM, "fast-path output buffers (%zu samples)", Bk->out_elems);
+  if (Bk->h_err) *Bk->h_err = 0;
+  if (rc != VITS_OK) { back_free(Bk); return rc; }
   // phase 2 reads the front's phase-1 results in place
-  s->stats = F->stats; s->cum = F->cum; s->condv = F->condv; s->len_y = F->len_y; s->len_x = F->len_x; s->ylen64 = F->ylen64;
+  const vits_session* f = F->s;
+  s->stats = f->stats; s->cum = f->cum; s->condv = f->condv; s->len_y = f->len_y; s->len_x = f->len_x; s->ylen64 = f->ylen64;
   s->dv = reinterpret_cast<const SynthDev*>(F->io_d);
   s->item_seeds = reinterpret_cast<const unsigned long long*>(F->io_d + F->io_seeds);
   // the persistent flow program was resolved against this session's own len_y / condv: resolve it again against the front's
   persist_plan(s);
-  s->last_use = ++F->last_use;
-  F->backs[TyB] = s;
-  *out = s;
+  F->backs.insert(TyB, Bk);
+  *out = Bk;
   return VITS_OK;
 }
 
-// output buffers and graphs of back session Bk at the rate of `T` (created on first use; at most 4 rates stay cached per back)
-static int back_rate_get(vits_session* F, vits_session* Bk, const ResampleTab& T, vits_session::RateOut** out) {
-  auto drop = [&](std::map<int, vits_session::RateOut>::iterator it) {
-    hipStreamSynchronize(F->stream);
-    for (hipGraphExec_t g : it->second.g2) if (g) hipGraphExecDestroy(g);
-    if (it->second.y_d) hipFree(it->second.y_d);
-    if (it->second.y_h) hipHostFree(it->second.y_h);
-    loud_ws_delete(it->second.lw);
-    Bk->rates.erase(it);
-  };
-  auto it = Bk->rates.find(T.P.rate_out);
-  if (it == Bk->rates.end()) {
-    if (Bk->rates.size() >= 4) {
-      auto lru = Bk->rates.begin();
-      for (auto jt = Bk->rates.begin(); jt != Bk->rates.end(); ++jt) if (jt->second.last_use < lru->second.last_use) lru = jt;
-      drop(lru);
-    }
-    it = Bk->rates.emplace(T.P.rate_out, vits_session::RateOut()).first;
-    vits_session::RateOut& R = it->second;
-    R.n_cap = T.P.n_out((long long)Bk->Ty * F->m->hp.hop_length);
-    const size_t bytes = (size_t)F->B * R.n_cap * sizeof(float);
-    if (hipMalloc(&R.y_d, bytes) != hipSuccess || hipHostMalloc((void**)&R.y_h, bytes) != hipSuccess) {
-      drop(it);
-      (void)hipGetLastError();
-      return fail(VITS_ERR_NOMEM, "fast-path output buffers at %d Hz (%zu bytes)", T.P.rate_out, bytes);
-    }
+// output buffers and graphs of back Bk at the rate of `T` (created on first use; at most VITS_RATES_PER_BACK rates stay cached per back)
+static int back_rate_get(FastFront* F, FastBack* Bk, const ResampleTab& T, FastBack::RateOut** out) {
+  if ((*out = Bk->rates.find(T.P.rate_out))) return VITS_OK;
+  if (FastBack::RateOut* lru = Bk->rates.make_room(VITS_RATES_PER_BACK)) {
+    hipStreamSynchronize(F->s->stream);
+    rate_free(lru);
   }
-  it->second.last_use = ++F->last_use;
-  *out = &it->second;
+  FastBack::RateOut* R = new FastBack::RateOut();
+  R->n_cap = T.P.n_out((long long)Bk->s->Ty * F->s->m->hp.hop_length);
+  const size_t bytes = (size_t)F->s->B * R->n_cap * sizeof(float);
+  if (hipMalloc(&R->y_d, bytes) != hipSuccess || hipHostMalloc((void**)&R->y_h, bytes) != hipSuccess) {
+    rate_free(R);
+    (void)hipGetLastError();
+    return fail(VITS_ERR_NOMEM, "fast-path output buffers at %d Hz (%zu bytes)", T.P.rate_out, bytes);
+  }
+  Bk->rates.insert(T.P.rate_out, R);
+  *out = R;
   return VITS_OK;
 }
 
@@ -216,85 +265,87 @@ static int capture_end(vits_session* s, hipGraphExec_t* out, CaptureGuard* guard
 
 // marks: the variants that also turn cum into token ends (marks.hip.h) and copy them to F->marks_h, in front of the h_ylen copy -- the
 // host reads them after the one synchronisation the call performs anyway.  L / M of the call ride in the per-call block.
-static int phase1_launch(vits_session* F, bool forced, bool solo, bool marks = false) {
+static int phase1_launch(FastFront* F, bool forced, bool solo, bool marks = false) {
+  vits_session* s = F->s;
   const int gi = (marks ? 8 : 0) + (persist_mask() ? 4 : 0) + (forced ? 2 : 0) + (solo ? 1 : 0);
   if (!F->g1[gi]) {
-    const int B = F->B, TxB = F->Tx;
-    HIP_TRY(hipStreamBeginCapture(F->stream, hipStreamCaptureModeThreadLocal));
-    CaptureGuard cg(F->stream);
-    hipMemcpyAsync(F->io_d, F->io_h, F->io_bytes, hipMemcpyHostToDevice, F->stream);
-    F->ragged = true; F->solo = solo; F->tile_keys.clear();
-    F->dv = reinterpret_cast<const SynthDev*>(F->io_d);
-    F->item_seeds = reinterpret_cast<const unsigned long long*>(F->io_d + F->io_seeds);
+    const int B = s->B, TxB = s->Tx;
+    HIP_TRY(hipStreamBeginCapture(s->stream, hipStreamCaptureModeThreadLocal));
+    CaptureGuard cg(s->stream);
+    hipMemcpyAsync(F->io_d, F->io_h, F->io_bytes, hipMemcpyHostToDevice, s->stream);
+    s->ragged = true; s->solo = solo; s->tile_keys.clear();
+    s->dv = reinterpret_cast<const SynthDev*>(F->io_d);
+    s->item_seeds = reinterpret_cast<const unsigned long long*>(F->io_d + F->io_seeds);
     const int64_t* d_len = reinterpret_cast<const int64_t*>(F->io_d + F->io_len);
     const int64_t* d_sid = reinterpret_cast<const int64_t*>(F->io_d + F->io_sid);
     const int64_t* d_ids = reinterpret_cast<const int64_t*>(F->io_d + F->io_ids);
     const int32_t* d_forced = reinterpret_cast<const int32_t*>(F->io_d + F->io_forced);
-    run_cond(F, d_sid, B, d_len, F->len_x, TxB);
-    if (persist_mask() == (PERSIST_SDP | PERSIST_ENC | PERSIST_FLOW) && B == 1 && F->ps_front[forced ? 0 : 1].ok && (!F->io_bert || F->ps_bert)) {
+    run_cond(s, d_sid, B, d_len, s->len_x, TxB);
+    if (persist_mask() == (PERSIST_SDP | PERSIST_ENC | PERSIST_FLOW) && B == 1 && s->ps_front[forced ? 0 : 1].ok && (!F->io_bert || s->ps_bert)) {
       // text encoder [+ duration predictor] + durations as one persistent launch (a BERT-conditioned voice: the program reads the
       // `bert` tensor straight from the input block, two more steps)
-      persist_launch(F, F->ps_front[forced ? 0 : 1], "front.persist", nullptr, 0.f, 0, d_ids, forced ? d_forced : nullptr, 1.f, 0.f);
-      F->ea_pending = false;
+      persist_launch(s, s->ps_front[forced ? 0 : 1], "front.persist", nullptr, 0.f, 0, d_ids, forced ? d_forced : nullptr, 1.f, 0.f);
+      s->ea_pending = false;
     } else {
-      run_text_encoder(F, d_ids, B, TxB, F->io_bert ? reinterpret_cast<const float*>(F->io_d + F->io_bert) : nullptr);
-      if (!forced) run_duration(F, F->x, nullptr, 0.f, 0, B, TxB, true);
-      run_durations(F, forced ? d_forced : nullptr, 1.f, B, TxB, 0);
+      run_text_encoder(s, d_ids, B, TxB, F->io_bert ? reinterpret_cast<const float*>(F->io_d + F->io_bert) : nullptr);
+      if (!forced) run_duration(s, s->x, nullptr, 0.f, 0, B, TxB, true);
+      run_durations(s, forced ? d_forced : nullptr, 1.f, B, TxB, 0);
     }
     if (marks) {
-      token_ends_launch(F, F->cum, F->len_x, B, TxB, F->m->hp.hop_length, 1, 1, F->dv, F->marks_d);
-      hipMemcpyAsync(F->marks_h, F->marks_d, sizeof(int64_t) * (size_t)B * TxB, hipMemcpyDeviceToHost, F->stream);
+      token_ends_launch(s, s->cum, s->len_x, B, TxB, s->m->hp.hop_length, 1, 1, s->dv, F->marks_d);
+      hipMemcpyAsync(F->marks_h, F->marks_d, sizeof(int64_t) * (size_t)B * TxB, hipMemcpyDeviceToHost, s->stream);
     }
-    hipMemcpyAsync(F->h_ylen, F->ylen64, sizeof(int64_t) * B, hipMemcpyDeviceToHost, F->stream);
-    hipMemcpyAsync(F->h_ylen + B, F->d_err, sizeof(int), hipMemcpyDeviceToHost, F->stream);
-    F->ragged = false; F->solo = false;
-    TRY(capture_end(F, &F->g1[gi], &cg));
+    hipMemcpyAsync(F->h_ylen, s->ylen64, sizeof(int64_t) * B, hipMemcpyDeviceToHost, s->stream);
+    hipMemcpyAsync(F->h_ylen + B, s->d_err, sizeof(int), hipMemcpyDeviceToHost, s->stream);
+    s->ragged = false; s->solo = false;
+    TRY(capture_end(s, &F->g1[gi], &cg));
   }
-  HIP_TRY(hipGraphLaunch(F->g1[gi], F->stream));
+  HIP_TRY(hipGraphLaunch(F->g1[gi], s->stream));
   return VITS_OK;
 }
 
 // R / T: the output rate's buffers and table (both null: the native rate)
-static int phase2_launch(vits_session* F, vits_session* Bk, bool solo, bool pcm, vits_session::RateOut* R = nullptr, const ResampleTab* T = nullptr) {
+static int phase2_launch(FastFront* F, FastBack* Bk, bool solo, bool pcm, FastBack::RateOut* R = nullptr, const ResampleTab* T = nullptr) {
+  vits_session* s = Bk->s;  // (its stream is the front's)
   const int gi = (persist_mask() ? 4 : 0) + (solo ? 2 : 0) + (pcm ? 1 : 0);
   hipGraphExec_t* g2 = R ? R->g2 : Bk->g2;
   if (!g2[gi]) {
-    const int B = F->B, TxB = F->Tx, TyB = Bk->Ty;
-    const long long stride = (long long)TyB * F->m->hp.hop_length;
-    HIP_TRY(hipStreamBeginCapture(F->stream, hipStreamCaptureModeThreadLocal));
-    CaptureGuard cg(F->stream);
-    Bk->ragged = true; Bk->solo = solo; Bk->rag_b1 = true; Bk->tile_keys.clear();
+    const int B = F->s->B, TxB = F->s->Tx, TyB = s->Ty;
+    const long long stride = (long long)TyB * F->s->m->hp.hop_length;
+    HIP_TRY(hipStreamBeginCapture(s->stream, hipStreamCaptureModeThreadLocal));
+    CaptureGuard cg(s->stream);
+    s->ragged = true; s->solo = solo; s->rag_b1 = true; s->tile_keys.clear();
     float* z;
-    if (persist_mask() == (PERSIST_SDP | PERSIST_ENC | PERSIST_FLOW) && B == 1 && Bk->ps_back.ok) {  // prior sample + flow as one persistent launch
-      persist_launch(Bk, Bk->ps_back, "back.persist");
-      z = Bk->zB;
+    if (persist_mask() == (PERSIST_SDP | PERSIST_ENC | PERSIST_FLOW) && B == 1 && s->ps_back.ok) {  // prior sample + flow as one persistent launch
+      persist_launch(s, s->ps_back, "back.persist");
+      z = s->zB;
     } else {
-      run_expand(Bk, nullptr, TyB, 0.f, 0, Bk->zA, B, TxB, TyB);
-      z = run_flow(Bk, B, TyB);
+      run_expand(s, nullptr, TyB, 0.f, 0, s->zA, B, TxB, TyB);
+      z = run_flow(s, B, TyB);
     }
     // a lone utterance decodes as the exact-size run does (zeros beyond its end); batches keep the reference's padded-batch
     // continuation over the halo unless the caller asked for independent items
-    run_decoder(Bk, z, true, B, TyB, Bk->out_d, stride, true, !(solo || B == 1));
+    run_decoder(s, z, true, B, TyB, Bk->out_d, stride, true, !(solo || B == 1));
     if (R) {  // the resampler reads each item's own [0, len) of the decoder's output; at int16 it stands where pcm16_kernel stands
-      ProfScope ps(Bk, "out.resample", 2.0 * B * R->n_cap * T->P.taps, pcm ? "resample_kernel<int16>" : "resample_kernel<float>");
-      const int hop = F->m->hp.hop_length;
-      if (pcm) resample_launch<int16_t>(F->stream, *T, Bk->out_d, stride, 0, stride, Bk->len_y, hop, B, static_cast<int16_t*>(R->y_d), R->n_cap, 0, R->n_cap, 1.f, Bk->dv);
-      else resample_launch<float>(F->stream, *T, Bk->out_d, stride, 0, stride, Bk->len_y, hop, B, static_cast<float*>(R->y_d), R->n_cap, 0, R->n_cap, 1.f, nullptr);
-      hipMemcpyAsync(R->y_h, R->y_d, (size_t)B * R->n_cap * (pcm ? sizeof(int16_t) : sizeof(float)), hipMemcpyDeviceToHost, F->stream);
+      ProfScope ps(s, "out.resample", 2.0 * B * R->n_cap * T->P.taps, pcm ? "resample_kernel<int16>" : "resample_kernel<float>");
+      const int hop = F->s->m->hp.hop_length;
+      if (pcm) resample_launch<int16_t>(s->stream, *T, Bk->out_d, stride, 0, stride, s->len_y, hop, B, static_cast<int16_t*>(R->y_d), R->n_cap, 0, R->n_cap, 1.f, s->dv);
+      else resample_launch<float>(s->stream, *T, Bk->out_d, stride, 0, stride, s->len_y, hop, B, static_cast<float*>(R->y_d), R->n_cap, 0, R->n_cap, 1.f, nullptr);
+      hipMemcpyAsync(R->y_h, R->y_d, (size_t)B * R->n_cap * (pcm ? sizeof(int16_t) : sizeof(float)), hipMemcpyDeviceToHost, s->stream);
     } else if (pcm) {
       {
-        ProfScope ps(Bk, "out.pcm16", 0, "pcm16_kernel");
-        hipLaunchKernelGGL(pcm16_kernel, dim3(cdiv((int)stride, 256), B), dim3(256), 0, F->stream, Bk->out_d, stride, Bk->pcm_d, stride, stride, 1.f, Bk->dv);
+        ProfScope ps(s, "out.pcm16", 0, "pcm16_kernel");
+        hipLaunchKernelGGL(pcm16_kernel, dim3(cdiv((int)stride, 256), B), dim3(256), 0, s->stream, Bk->out_d, stride, Bk->pcm_d, stride, stride, 1.f, s->dv);
       }
-      hipMemcpyAsync(Bk->out_h, Bk->pcm_d, Bk->out_elems * sizeof(int16_t), hipMemcpyDeviceToHost, F->stream);
+      hipMemcpyAsync(Bk->out_h, Bk->pcm_d, Bk->out_elems * sizeof(int16_t), hipMemcpyDeviceToHost, s->stream);
     } else {
-      hipMemcpyAsync(Bk->out_h, Bk->out_d, Bk->out_elems * sizeof(float), hipMemcpyDeviceToHost, F->stream);
+      hipMemcpyAsync(Bk->out_h, Bk->out_d, Bk->out_elems * sizeof(float), hipMemcpyDeviceToHost, s->stream);
     }
-    hipMemcpyAsync(Bk->h_err, Bk->d_err, sizeof(int), hipMemcpyDeviceToHost, F->stream);  // (the flow program's error bits)
-    Bk->ragged = false; Bk->solo = false;
-    TRY(capture_end(F, &g2[gi], &cg));
+    hipMemcpyAsync(Bk->h_err, s->d_err, sizeof(int), hipMemcpyDeviceToHost, s->stream);  // (the flow program's error bits)
+    s->ragged = false; s->solo = false;
+    TRY(capture_end(s, &g2[gi], &cg));
   }
-  HIP_TRY(hipGraphLaunch(g2[gi], F->stream));
+  HIP_TRY(hipGraphLaunch(g2[gi], s->stream));
   return VITS_OK;
 }
 
@@ -321,13 +372,10 @@ static int synth_fast(vits_model* m, const int64_t* ids, const int64_t* lengths,
   // (declared before the session guard: the call's last stream synchronisation happens before this scope ends)
   InFlight inflight(m->device);
   PersistScope pscope(B == 1 ? m->device : -1, inflight.before);  // a single utterance takes the persistent stages when the device is quiet enough as it starts
-  vits_session* F = nullptr;
-  {
-    int rc = front_acquire(m, B, TxB, &F);
-    if (rc == VITS_ERR_NOMEM) { fronts_evict_all(m); rc = front_acquire(m, B, TxB, &F); }
-    if (rc != VITS_OK) return rc;
-  }
-  struct Rel { vits_model* m; vits_session* s; ~Rel() { front_release(m, s); } } rel{m, F};
+  FastFront* F = nullptr;
+  TRY(retry_nomem([&] { return front_acquire(m, B, TxB, &F); }, [&] { fronts_evict_all(m); }));
+  struct Rel { vits_model* m; FastFront* F; ~Rel() { front_release(m, F); } } rel{m, F};
+  const hipStream_t st = F->s->stream;
   if (token_ends && !F->marks_d) {  // the first marks request of this bucket (before any capture)
     const size_t bytes = sizeof(int64_t) * (size_t)B * TxB;
     if (hipMalloc((void**)&F->marks_d, bytes) != hipSuccess || hipHostMalloc((void**)&F->marks_h, bytes) != hipSuccess) {
@@ -352,29 +400,18 @@ static int synth_fast(vits_model* m, const int64_t* ids, const int64_t* lengths,
     h_seeds[b] = (opts && opts->item_seeds) ? opts->item_seeds[b] : hv->seed + (uint64_t)b;
     h_len[b] = lengths[b];
     h_sid[b] = sid ? sid[b] : 0;
-    memcpy(h_ids + (size_t)b * TxB, ids + (size_t)b * Tx, sizeof(int64_t) * Tx);
-    for (int t = Tx; t < TxB; ++t) h_ids[(size_t)b * TxB + t] = 0;
-    if (forced) {
-      memcpy(h_forced + (size_t)b * TxB, opts->forced_durations + (size_t)b * Tx, sizeof(int32_t) * Tx);
-      for (int t = Tx; t < TxB; ++t) h_forced[(size_t)b * TxB + t] = 0;
-    }
   }
-  if (F->io_bert) {  // [B, bert_dim, Tx] -> [B, bert_dim, TxB], bucket columns zero
-    float* h_bert = reinterpret_cast<float*>(F->io_h + F->io_bert);
-    const size_t rows = (size_t)B * hp.bert_dim;
-    for (size_t r = 0; r < rows; ++r) {
-      memcpy(h_bert + r * TxB, opts->bert + r * Tx, sizeof(float) * Tx);
-      for (int t = Tx; t < TxB; ++t) h_bert[r * TxB + t] = 0.f;
-    }
-  }
+  pad_rows(h_ids, ids, B, Tx, TxB);
+  if (forced) pad_rows(h_forced, opts->forced_durations, B, Tx, TxB);
+  if (F->io_bert) pad_rows(reinterpret_cast<float*>(F->io_h + F->io_bert), opts->bert, (size_t)B * hp.bert_dim, Tx, TxB);  // [B, bert_dim, Tx] -> [B, bert_dim, TxB]
   // ---- phase 1 and the one host round trip
   TRY(phase1_launch(F, forced, solo, token_ends != nullptr));
-  HIP_TRY(hipStreamSynchronize(F->stream));
+  HIP_TRY(hipStreamSynchronize(st));
   {
     int e = 0;
     memcpy(&e, F->h_ylen + B, sizeof(int));
     if (e) {
-      hipMemsetAsync(F->d_err, 0, sizeof(int), F->stream);
+      hipMemsetAsync(F->s->d_err, 0, sizeof(int), st);
       return device_error_word(e);
     }
   }
@@ -390,37 +427,28 @@ static int synth_fast(vits_model* m, const int64_t* ids, const int64_t* lengths,
   if (B > 1) { int p2 = 32; while (p2 * 2 <= Ty) p2 *= 2; if (p2 / 8 > ty_step) ty_step = p2 / 8; }
   const int TyB = (int)((Ty + ty_step - 1) / ty_step * ty_step);
   // ---- phase 2
-  vits_session* Bk = nullptr;
-  {
-    int rc = back_get(F, TyB, &Bk);
-    if (rc == VITS_ERR_NOMEM) {  // idle fronts of other buckets and this front's other backs go first, then once more
-      fronts_evict_all(m);
-      hipStreamSynchronize(F->stream);
-      for (auto& kv : F->backs) session_free(kv.second);
-      F->backs.clear();
-      rc = back_get(F, TyB, &Bk);
-    }
-    if (rc != VITS_OK) return rc;
-  }
+  FastBack* Bk = nullptr;
+  // (idle fronts of other buckets and this front's other backs go first)
+  TRY(retry_nomem([&] { return back_get(F, TyB, &Bk); }, [&] { fronts_evict_all(m); front_drop_backs(F); }));
   // (sizes in output samples)
   const int64_t S = T ? T->P.n_out(Ty * hp.hop_length) : Ty * hp.hop_length;
   const size_t esz = pcm ? sizeof(int16_t) : sizeof(float);
   // what either branch below ends with, once its work is queued: the buffer the caller gets ...
   auto host_out = [&]() -> char* {
     char* h = static_cast<char*>(malloc(esz * (size_t)B * S));
-    if (!h) { hipStreamSynchronize(F->stream); fail(VITS_ERR_NOMEM, "host alloc failed"); }
+    if (!h) { hipStreamSynchronize(st); fail(VITS_ERR_NOMEM, "host alloc failed"); }
     return h;
   };
   // ... and the wait, the launch error (`queued`: of the branch's own copies), the flow program's error word, the lengths and the marks
   auto finish = [&](char* h_out, hipError_t queued) -> int {
-    hipError_t e = hipStreamSynchronize(F->stream);
+    hipError_t e = hipStreamSynchronize(st);
     if (queued != hipSuccess) e = queued;
     if (e == hipSuccess) e = hipGetLastError();
     if (e != hipSuccess) { free(h_out); return fail(VITS_ERR_DEVICE, "kernel launch failed: %s", hipGetErrorString(e)); }
     if (*Bk->h_err) {
       const int e2 = *Bk->h_err;
       *Bk->h_err = 0;
-      hipMemsetAsync(Bk->d_err, 0, sizeof(int), F->stream);
+      hipMemsetAsync(Bk->s->d_err, 0, sizeof(int), st);
       free(h_out);
       return device_error_word(e2);
     }
@@ -441,18 +469,18 @@ static int synth_fast(vits_model* m, const int64_t* ids, const int64_t* lengths,
     const float* d_res = nullptr;
     long long So = 0;
     std::vector<float> res((size_t)B * 4);
-    const int rc = tail_run(bufs, Bk, F->stream, Bk->out_d, (long long)TyB * hp.hop_length, Bk->len_y, hp.hop_length, h_len.data(), B, q, &d_out, &So, &d_res);
-    if (rc != VITS_OK) { hipStreamSynchronize(F->stream); return rc; }
-    if (d_res) hipMemcpyAsync(res.data(), d_res, sizeof(float) * res.size(), hipMemcpyDeviceToHost, F->stream);
+    const int rc = tail_run(bufs, Bk->s, st, Bk->out_d, (long long)TyB * hp.hop_length, Bk->s->len_y, hp.hop_length, h_len.data(), B, q, &d_out, &So, &d_res);
+    if (rc != VITS_OK) { hipStreamSynchronize(st); return rc; }
+    if (d_res) hipMemcpyAsync(res.data(), d_res, sizeof(float) * res.size(), hipMemcpyDeviceToHost, st);
     char* h_out = host_out();
     if (!h_out) return VITS_ERR_NOMEM;
-    TRY(finish(h_out, hipMemcpy2DAsync(h_out, esz * (size_t)S, d_out, esz * (size_t)So, esz * (size_t)S, (size_t)B, hipMemcpyDeviceToHost, F->stream)));
+    TRY(finish(h_out, hipMemcpy2DAsync(h_out, esz * (size_t)S, d_out, esz * (size_t)So, esz * (size_t)S, (size_t)B, hipMemcpyDeviceToHost, st)));
     if (d_res) norm_req_results(lq, res.data(), B);
     return VITS_OK;
   }
   // Without a shift a flagged request allocates nothing after the first call of its bucket: the resampler is part of the graph and the
   // last stage runs in buffers the bucket owns (RateOut, LoudWs), so this branch does not go through tail_run's allocator.
-  vits_session::RateOut* R = nullptr;
+  FastBack::RateOut* R = nullptr;
   if (T) TRY(back_rate_get(F, Bk, *T, &R));
   const int64_t stride = R ? R->n_cap : (int64_t)TyB * hp.hop_length;
   const char* src_h = R ? R->y_h : Bk->out_h;
@@ -468,10 +496,10 @@ static int synth_fast(vits_model* m, const int64_t* ids, const int64_t* lengths,
     TRY(phase2_launch(F, Bk, solo, false, R, T));
     const float* x_d = R ? static_cast<const float*>(R->y_d) : Bk->out_d;
     const int rL = T ? T->P.L : 1, rM = T ? T->P.M : 1;
-    if (pcm) norm_launch<int16_t>(F->stream, lq, NS, x_d, stride, stride, Bk->len_y, hp.hop_length, rL, rM, B, static_cast<int16_t*>(W.y_d()), stride, stride, q.pcm_scale, Bk);
-    else norm_launch<float>(F->stream, lq, NS, x_d, stride, stride, Bk->len_y, hp.hop_length, rL, rM, B, static_cast<float*>(W.y_d()), stride, stride, 1.f, Bk);
-    hipMemcpyAsync(W.y_h(), W.y_d(), (size_t)B * stride * esz, hipMemcpyDeviceToHost, F->stream);
-    hipMemcpyAsync(W.res_h(), W.S.res, sizeof(float) * 4 * (size_t)B, hipMemcpyDeviceToHost, F->stream);
+    if (pcm) norm_launch<int16_t>(st, lq, NS, x_d, stride, stride, Bk->s->len_y, hp.hop_length, rL, rM, B, static_cast<int16_t*>(W.y_d()), stride, stride, q.pcm_scale, Bk->s);
+    else norm_launch<float>(st, lq, NS, x_d, stride, stride, Bk->s->len_y, hp.hop_length, rL, rM, B, static_cast<float*>(W.y_d()), stride, stride, 1.f, Bk->s);
+    hipMemcpyAsync(W.y_h(), W.y_d(), (size_t)B * stride * esz, hipMemcpyDeviceToHost, st);
+    hipMemcpyAsync(W.res_h(), W.S.res, sizeof(float) * 4 * (size_t)B, hipMemcpyDeviceToHost, st);
     src_h = W.y_h();
   } else {
     TRY(phase2_launch(F, Bk, solo, pcm, R, T));

@@ -163,6 +163,9 @@ static DecGeom dec_geom(const vits_hparams& hp) {
 }
 
 struct vits_session;
+struct FastFront;               // engine_fastpath.hip.h
+static void front_free(FastFront* F);
+static size_t fast_cache_cap();
 
 struct vits_model {
   bool acoustic = true;  // false: vocoder-only blob (n_vocab == 0)
@@ -214,10 +217,8 @@ struct vits_model {
 
   std::mutex pool_mu;
   std::vector<vits_session*> pool;
-  // fast path: idle front sessions by (B, T_x bucket), least-recently-used eviction under a device-memory cap
-  std::multimap<std::pair<int, int>, vits_session*> fronts;
-  uint64_t use_clock = 0;
-  size_t fronts_bytes = 0;
+  // fast path: idle front contexts by (B, T_x bucket), least-recently-used eviction under a count and a device-memory cap
+  IdleCache<std::pair<int, int>, FastFront> fronts{pool_mu, {VITS_FRONTS_PER_MODEL, true, fast_cache_cap}};
 };
 
 // live models (vits_debug_persist_spin writes the poll limit into each model's device word)

@@ -8,8 +8,6 @@
 // the gRPC server's worker threads (server/tts_server.py:39-40,57) never share buffers.
 struct ProfRec { std::string name; std::string kernel; hipEvent_t e0, e1; double flops; };
 
-struct LoudWs;                         // loudness.hip.h: the buffers of a context's normalised calls (include/vits_loudness.h)
-static void loud_ws_delete(LoudWs* w);
 struct vits_session {
   vits_model* m = nullptr;
   hipStream_t stream = nullptr;
@@ -18,7 +16,6 @@ struct vits_session {
   char* arena = nullptr;
   size_t arena_bytes = 0, arena_used = 0;
   int* d_err = nullptr;
-  int* h_err = nullptr;  // back sessions of the fast path: pinned copy of d_err, written by the phase-2 graph
   hipEvent_t ev0 = nullptr, ev1 = nullptr;
   bool timed = false;
   bool profile = false;
@@ -84,50 +81,18 @@ struct vits_session {
   bool ps_defer = false;   // the owner calls persist_plan itself after re-pointing shared tensors (backs): session_reserve skips it
   PersistCtl* ps_ctl = nullptr;
   std::vector<std::pair<std::vector<long long>, const float*>> ps_pending;  // parameter packs built by the plan in progress (persist_pack), published after its one stream sync
-  const float* ps_bert = nullptr;  // BERT-conditioned voices: the fixed device buffer [bert_dim][Tx] the text-encoder program reads (front sessions: io_d + io_bert)
+  const float* ps_bert = nullptr;  // BERT-conditioned voices: the fixed device buffer [bert_dim][Tx] the text-encoder program reads (FastFront: io_d + io_bert)
   bool ps_owner = false;   // device sessions (asynchronous entry point): this session holds the device's persistent-path token for its lifetime
   // staging area of the host-buffer entry points (inputs, noise, audio): a bump allocator that lives with the pooled
   // session, so a steady stream of vits_synthesize calls does no hipMalloc / hipFree (both synchronise the device)
   char* stage = nullptr;
   size_t stage_bytes = 0, stage_used = 0;
 
-  // ---- graph-replayed fast path of vits_synthesize (see "fast path" below).  A FRONT session is laid out for
-  // (B, T_x bucket) and owns phase 1 (text encoder .. durations); its BACK sessions, one per frame bucket, own phase 2
-  // (prior .. decoder) and read the front's phase-1 results in place.
   int graph_nodes = 0;             // nodes (= launches) of the most recently captured forward graph
   bool ea_pending = false;         // run_duration left the final ElementwiseAffine to durations_kernel (row of z in ea_row)
   int ea_row = 0;
   bool rag_b1 = false;             // single utterance in a frame bucket: decoder sees zeros beyond the item's own end
   bool sdp_always = false;         // device-session option: run the duration predictor even when durations are forced
-  char *io_h = nullptr, *io_d = nullptr;  // per-call inputs: pinned host mirror and device copy (SynthDev | lengths | sid | ids | forced)
-  size_t io_bytes = 0, io_len = 0, io_sid = 0, io_ids = 0, io_forced = 0, io_seeds = 0, io_bert = 0;  // io_bert: float [B, bert_dim, TxB] (BERT-conditioned voices), 0 = none
-  int64_t* h_ylen = nullptr;       // pinned [B] + one int error word behind it
-  hipGraphExec_t g1[16] = {};      // [marks*8 + persist*4 + forced*2 + solo]; a call without marks only ever touches 0..7
-  // speech marks (include/vits_marks.h), front: token ends int64 [B, T_x bucket] on the device and their pinned copy, allocated by the
-  // first request that asks for marks; the marks variants of g1 write and copy them in front of the h_ylen copy
-  long long* marks_d = nullptr;
-  int64_t* marks_h = nullptr;
-  std::map<int, vits_session*> backs;
-  vits_session* front = nullptr;
-  float* out_d = nullptr;          // back: fp32 audio [B, T_y bucket * hop] on the device
-  int16_t* pcm_d = nullptr;        // back: int16 PCM, same shape
-  char* out_h = nullptr;           // back: pinned host copy of whichever output the call asked for
-  size_t out_elems = 0;
-  hipGraphExec_t g2[8] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};  // [persist*4 + solo*2 + pcm]
-  // back: phase 2 at another output rate (include/vits_resample.h).  The rate changes a launch and the size of the output, so it is part
-  // of the graph key: one entry per rate, with its own graphs and its own output buffers [B, ceil(T_y bucket * hop * L / M)].
-  struct RateOut {
-    hipGraphExec_t g2[8] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};  // as g2 above
-    void* y_d = nullptr;   // device: float or int16 (sized for float)
-    char* y_h = nullptr;   // pinned host copy
-    long long n_cap = 0;   // outputs per item
-    uint64_t last_use = 0;
-    LoudWs* lw = nullptr;  // as vits_session::lw below
-  };
-  std::map<int, RateOut> rates;
-  LoudWs* lw = nullptr;            // back: scratch and output buffers of the calls with VITS_FLAG_LOUDNESS, allocated by the first of them
-  uint64_t last_use = 0;
-  size_t cache_bytes = 0;          // device bytes this session pins while cached (front: incl. its backs)
 };
 
 
@@ -378,26 +343,6 @@ static void session_free(vits_session* s) {
   hipSetDevice(s->m->device);
   if (s->stream) hipStreamSynchronize(s->stream);
   drop_graphs(s);
-  for (auto& kv : s->backs) session_free(kv.second);
-  s->backs.clear();
-  for (auto& kv : s->rates) {
-    for (hipGraphExec_t g : kv.second.g2) if (g) hipGraphExecDestroy(g);
-    if (kv.second.y_d) hipFree(kv.second.y_d);
-    if (kv.second.y_h) hipHostFree(kv.second.y_h);
-    loud_ws_delete(kv.second.lw);
-  }
-  s->rates.clear();
-  loud_ws_delete(s->lw);
-  for (hipGraphExec_t g : s->g1) if (g) hipGraphExecDestroy(g);
-  for (hipGraphExec_t g : s->g2) if (g) hipGraphExecDestroy(g);
-  if (s->marks_d) hipFree(s->marks_d);
-  if (s->marks_h) hipHostFree(s->marks_h);
-  if (s->io_h) hipHostFree(s->io_h);
-  if (s->io_d) hipFree(s->io_d);
-  if (s->h_ylen) hipHostFree(s->h_ylen);
-  if (s->out_d) hipFree(s->out_d);
-  if (s->pcm_d) hipFree(s->pcm_d);
-  if (s->out_h) hipHostFree(s->out_h);
   for (auto& r : s->prof) { hipEventDestroy(r.e0); hipEventDestroy(r.e1); }
   if (s->arena) hipFree(s->arena);
   if (s->ps_ctl) hipFree(s->ps_ctl);
@@ -407,12 +352,32 @@ static void session_free(vits_session* s) {
   }
   if (s->stage) hipFree(s->stage);
   if (s->d_err) hipFree(s->d_err);
-  if (s->h_err) hipHostFree(s->h_err);
   if (s->ev0) hipEventDestroy(s->ev0);
   if (s->ev1) hipEventDestroy(s->ev1);
   if (s->copy_stream) hipStreamDestroy(s->copy_stream);
   if (s->stream && s->own_stream) hipStreamDestroy(s->stream);
   delete s;
+}
+
+// A session on somebody else's stream (the back contexts of the fast paths launch onto their front's): a workspace and an error word of
+// its own, zeroed in that stream's order; no stream, no events.  `what` names the context in the refusal.  Returned through
+// session_unborrow, by an owner that has waited for the stream.
+static void session_unborrow(vits_session* s) {
+  if (!s) return;
+  s->stream = nullptr;
+  session_free(s);
+}
+static int session_borrow(vits_model* m, hipStream_t stream, const char* what, vits_session** out) {
+  vits_session* s = new vits_session();
+  s->m = m;
+  s->stream = stream;
+  s->own_stream = false;
+  if (hipMalloc((void**)&s->d_err, sizeof(int)) != hipSuccess || hipMemsetAsync(s->d_err, 0, sizeof(int), stream) != hipSuccess) {
+    session_unborrow(s);
+    return fail(VITS_ERR_NOMEM, "%s", what);
+  }
+  *out = s;
+  return VITS_OK;
 }
 
 static int pool_acquire(vits_model* m, vits_session** out) {

@@ -25,8 +25,8 @@ struct stts_model {
   std::vector<ConvW> lsc;
   float *t0w = nullptr, *t0b = nullptr, *t2w = nullptr, *t2b = nullptr;
   std::vector<float*> film_w, film_b;
-  std::map<int, SttsFront*> fronts;  // graph-replayed fast path of stts_synthesize: cached contexts by T_x bucket (under base.pool_mu)
-  uint64_t use_clock = 0;
+  // graph-replayed fast path of stts_synthesize: idle front contexts by T_x bucket (under base.pool_mu)
+  IdleCache<int, SttsFront> fronts{base.pool_mu, {STTS_FRONTS_PER_MODEL, false}};
 };
 
 static DitW load_dit(vits_model* b, const char* p, int H, int F, int K, int G) {
@@ -484,7 +484,7 @@ int stts_create(const void* blob, size_t bytes, vits_model* vocoder, int device,
 void stts_destroy(stts_model* m) {
   if (!m) return;
   hipSetDevice(m->base.device);
-  for (auto& kv : m->fronts) stts_front_free(kv.second);
+  for (SttsFront* f : m->fronts.take_all()) stts_front_free(f);
   for (vits_session* s : m->base.pool) session_free(s);
   for (void* a : m->base.allocs) hipFree(a);
   delete m;
@@ -605,7 +605,6 @@ struct SttsBack {
   hipGraphExec_t g[2] = {nullptr, nullptr};  // [with vocoder]
   float* d_dn = nullptr;       // denoised audio [audio_elems] | frames scratch: allocated by the first request that sets STTS_FLAG_DENOISE
   size_t dn_scr_elems = 0;
-  uint64_t last_use = 0;
 };
 struct SttsFront {
   vits_session* s = nullptr;   // stream + encoder workspace
@@ -615,8 +614,7 @@ struct SttsFront {
   float *d_x = nullptr, *d_mu = nullptr;
   float* mu_h = nullptr;       // pinned [dp_out * TxB] + one int error word behind it
   hipGraphExec_t g1 = nullptr;
-  std::map<std::pair<int, int>, SttsBack*> backs;  // (frame bucket, n_steps)
-  uint64_t last_use = 0, clock = 0;
+  LruSlots<std::pair<int, int>, SttsBack> backs;  // (frame bucket, n_steps)
 };
 
 static void stts_back_free(SttsBack* b) {
@@ -626,13 +624,16 @@ static void stts_back_free(SttsBack* b) {
   if (b->d_dn) hipFree(b->d_dn);
   if (b->out_h) hipHostFree(b->out_h);
   if (b->sv) session_free(b->sv);
-  if (b->s) { b->s->stream = nullptr; session_free(b->s); }
+  session_unborrow(b->s);
   delete b;
+}
+static void stts_front_drop_backs(SttsFront* f) {
+  hipStreamSynchronize(f->s->stream);
+  for (SttsBack* b : f->backs.drain()) stts_back_free(b);
 }
 static void stts_front_free(SttsFront* f) {
   if (!f) return;
-  if (f->s && f->s->stream) hipStreamSynchronize(f->s->stream);
-  for (auto& kv : f->backs) stts_back_free(kv.second);
+  if (f->s && f->s->stream) stts_front_drop_backs(f);
   if (f->g1) hipGraphExecDestroy(f->g1);
   if (f->io_h) hipHostFree(f->io_h);
   if (f->io_d) hipFree(f->io_d);
@@ -644,11 +645,7 @@ static void stts_front_free(SttsFront* f) {
 }
 
 static int stts_front_acquire(stts_model* m, int TxB, SttsFront** out) {
-  {
-    std::lock_guard<std::mutex> g(m->base.pool_mu);
-    auto it = m->fronts.find(TxB);
-    if (it != m->fronts.end()) { *out = it->second; m->fronts.erase(it); return VITS_OK; }
-  }
+  if ((*out = m->fronts.take(TxB))) return VITS_OK;
   const stts_hparams& hp = m->hp;
   SttsFront* f = new SttsFront();
   f->TxB = TxB;
@@ -680,56 +677,28 @@ static int stts_front_acquire(stts_model* m, int TxB, SttsFront** out) {
   return VITS_OK;
 }
 static void stts_front_release(stts_model* m, SttsFront* f) {
-  std::vector<SttsFront*> evict;
-  {
-    std::lock_guard<std::mutex> g(m->base.pool_mu);
-    f->last_use = ++m->use_clock;
-    auto it = m->fronts.find(f->TxB);
-    if (it != m->fronts.end()) { evict.push_back(it->second); m->fronts.erase(it); }  // a concurrent call built the same bucket: keep the newer
-    m->fronts[f->TxB] = f;
-    while (m->fronts.size() > 16) {
-      auto lru = m->fronts.begin();
-      for (auto jt = m->fronts.begin(); jt != m->fronts.end(); ++jt) if (jt->second->last_use < lru->second->last_use) lru = jt;
-      evict.push_back(lru->second);
-      m->fronts.erase(lru);
-    }
-  }
-  for (SttsFront* e : evict) stts_front_free(e);
+  for (SttsFront* e : m->fronts.put(f->TxB, f, 0)) stts_front_free(e);
 }
 
 // frees every idle front context (with its back contexts): the answer to a failed allocation on the request path (the cache is
-// bounded by count -- 16 text buckets x 4 frame buckets -- not by bytes)
+// bounded by count -- STTS_FRONTS_PER_MODEL text buckets x STTS_BACKS_PER_FRONT frame buckets -- not by bytes)
 static void stts_fronts_evict_all(stts_model* m) {
-  std::vector<SttsFront*> evict;
-  {
-    std::lock_guard<std::mutex> g(m->base.pool_mu);
-    for (auto& kv : m->fronts) evict.push_back(kv.second);
-    m->fronts.clear();
-  }
-  for (SttsFront* e : evict) stts_front_free(e);
+  for (SttsFront* e : m->fronts.take_all()) stts_front_free(e);
   (void)hipGetLastError();
 }
 
 static int stts_back_get(stts_model* m, SttsFront* F, int TB, int n, SttsBack** out) {
   const auto key = std::make_pair(TB, n);
-  auto it = F->backs.find(key);
-  if (it != F->backs.end()) { it->second->last_use = ++F->clock; *out = it->second; return VITS_OK; }
-  if (F->backs.size() >= 4) {
-    auto lru = F->backs.begin();
-    for (auto jt = F->backs.begin(); jt != F->backs.end(); ++jt) if (jt->second->last_use < lru->second->last_use) lru = jt;
+  if ((*out = F->backs.find(key))) return VITS_OK;
+  if (SttsBack* lru = F->backs.make_room(STTS_BACKS_PER_FRONT)) {
     hipStreamSynchronize(F->s->stream);
-    stts_back_free(lru->second);
-    F->backs.erase(lru);
+    stts_back_free(lru);
   }
   const stts_hparams& hp = m->hp;
   const int NF = hp.n_feats, CC = hp.enc_hidden, G = hp.spk_emb_dim;
   SttsBack* b = new SttsBack();
   b->TB = TB; b->n = n; b->nb = hp.guidance_scale > 0.f ? 2 : 1;
-  b->s = new vits_session();
-  b->s->m = &m->base; b->s->stream = F->s->stream; b->s->own_stream = false;
-  int rc = VITS_OK;
-  if (hipMalloc((void**)&b->s->d_err, sizeof(int)) != hipSuccess || hipMemsetAsync(b->s->d_err, 0, sizeof(int), F->s->stream) != hipSuccess)
-    rc = fail(VITS_ERR_NOMEM, "back context");
+  int rc = session_borrow(&m->base, F->s->stream, "back context", &b->s);
   if (rc == VITS_OK) rc = stts_arena(b->s, stts_est_bytes(hp, b->nb, TB, n));
   const int hop = m->vocoder ? m->vocoder->hp.hop_length : 0;
   b->audio_elems = (size_t)TB * hop;
@@ -757,8 +726,7 @@ static int stts_back_get(stts_model* m, SttsFront* F, int TB, int n, SttsBack** 
     b->E.tables_ready = true;
   }
   if (rc != VITS_OK) { stts_back_free(b); return rc; }
-  b->last_use = ++F->clock;
-  F->backs[key] = b;
+  F->backs.insert(key, b);
   *out = b;
   return VITS_OK;
 }
@@ -879,30 +847,16 @@ static int stts_synth_fast(stts_model* m, const int64_t* ids, int32_t Tx, const 
   if (out_audio) TRY(stts_denoise_arg(m, opts, &dn));
   const int TxB = (Tx + 7) / 8 * 8;
   SttsFront* F = nullptr;
-  {
-    int rc = stts_front_acquire(m, TxB, &F);
-    if (rc == VITS_ERR_NOMEM) { stts_fronts_evict_all(m); rc = stts_front_acquire(m, TxB, &F); }
-    if (rc != VITS_OK) return rc;
-  }
+  TRY(retry_nomem([&] { return stts_front_acquire(m, TxB, &F); }, [&] { stts_fronts_evict_all(m); }));
   struct Rel { stts_model* m; SttsFront* f; ~Rel() { stts_front_release(m, f); } } rel{m, F};
   hipStream_t st = F->s->stream;
   // ---- inputs -> pinned block (rows re-strided to the bucket, padding zero)
-  int64_t* h_ids = reinterpret_cast<int64_t*>(F->io_h);
-  for (int r = 0; r < 5; ++r) {
-    memcpy(h_ids + (size_t)r * TxB, ids + (size_t)r * Tx, sizeof(int64_t) * Tx);
-    for (int t = Tx; t < TxB; ++t) h_ids[(size_t)r * TxB + t] = 0;
-  }
+  pad_rows(reinterpret_cast<int64_t*>(F->io_h), ids, 5, Tx, TxB);
   *reinterpret_cast<int*>(F->io_h + F->o_len) = Tx;
   *reinterpret_cast<int64_t*>(F->io_h + F->o_sid) = sid;
   float* h_bert = reinterpret_cast<float*>(F->io_h + F->o_bert);
-  if (bert) {
-    for (int r = 0; r < hp.bert_dim; ++r) {
-      memcpy(h_bert + (size_t)r * TxB, bert + (size_t)r * Tx, sizeof(float) * Tx);
-      for (int t = Tx; t < TxB; ++t) h_bert[(size_t)r * TxB + t] = 0.f;
-    }
-  } else {
-    memset(h_bert, 0, sizeof(float) * (size_t)hp.bert_dim * TxB);
-  }
+  if (bert) pad_rows(h_bert, bert, hp.bert_dim, Tx, TxB);
+  else memset(h_bert, 0, sizeof(float) * (size_t)hp.bert_dim * TxB);
   // ---- phase 1 and the one host round trip
   TRY(stts_phase1(m, F));
   HIP_TRY(hipStreamSynchronize(st));
@@ -935,17 +889,7 @@ static int stts_synth_fast(stts_model* m, const int64_t* ids, int32_t Tx, const 
   h_lenT[0] = h_lenT[1] = T4;
   // ---- phase 2
   SttsBack* Bk = nullptr;
-  {
-    int rc = stts_back_get(m, F, TB, n, &Bk);
-    if (rc == VITS_ERR_NOMEM) {
-      stts_fronts_evict_all(m);
-      hipStreamSynchronize(F->s->stream);
-      for (auto& kv : F->backs) stts_back_free(kv.second);
-      F->backs.clear();
-      rc = stts_back_get(m, F, TB, n, &Bk);
-    }
-    if (rc != VITS_OK) return rc;
-  }
+  TRY(retry_nomem([&] { return stts_back_get(m, F, TB, n, &Bk); }, [&] { stts_fronts_evict_all(m); stts_front_drop_backs(F); }));
   const bool audio = out_audio != nullptr;
   TRY(stts_phase2(m, F, Bk, audio));
   const int64_t S = audio ? (int64_t)ylen * m->vocoder->hp.hop_length : 0;

@@ -220,7 +220,7 @@ class RequestCoalescer:
             raise me.error
         return me.result
 
-# frame-bucket ("back") contexts the engine keeps per T_x bucket before it evicts the least recently used one (csrc/engine_fastpath.hip.h back_get)
+# frame-bucket ("back") contexts the engine keeps per T_x bucket before it evicts the least recently used one (mirror of csrc/ctx_cache.hip.h VITS_BACKS_PER_FRONT)
 BACK_SESSIONS_PER_FRONT = 6
 
 _GRAPH_INPUTS = ("input", "input_lengths", "scales", "sid")
