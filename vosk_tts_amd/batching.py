@@ -136,6 +136,14 @@ class MultiDeviceSynth:
         return sess.run_pcm16(dict(feed, **{"vits.marks": True}), scale, return_lengths=True, sample_rate=sample_rate)
 
     @staticmethod
+    def _scales_feed(scales, part):
+        """the feed entries of the scales for the requests `part`: one triple for the call, or -- where noise_level / speech_rate /
+        duration_noise_level came per request -- every request's own triple as the item scales of the solo batch (include/vits_prosody.h)"""
+        if scales.ndim == 1:
+            return {"scales": scales}
+        return {"scales": scales[part[0]], "vits.item_scales": np.ascontiguousarray(scales[list(part)])}
+
+    @staticmethod
     def _item(pcm, n, ends, n_tokens):
         """one request's result: its samples, and with marks (samples, its own tokens' ends)"""
         a = pcm[:int(n)].copy()
@@ -150,7 +158,7 @@ class MultiDeviceSynth:
         for k in range(0, len(idx), self.max_batch):
             part = idx[k:k + self.max_batch]
             ids, lens = pad_batch(token_lists, part)
-            feed = {"input": ids, "input_lengths": lens, "scales": scales, "sid": np.array([sids[i] for i in part], np.int64),
+            feed = {"input": ids, "input_lengths": lens, **self._scales_feed(scales, part), "sid": np.array([sids[i] for i in part], np.int64),
                     "bert": None, "phone_duration_extra": None, "vits.solo": True,
                     "vits.item_seeds": np.array([seeds[i] for i in part], np.uint64), **(loud or {})}
             with self._replica_locks[r]:  # concurrent synth_batch() calls do not interleave on one replica
@@ -163,7 +171,9 @@ class MultiDeviceSynth:
                     preserve_formants=None, limit=None, limit_lookahead_ms=None, limit_release_ms=None):
         """texts: list of str -> list of int16 PCM arrays (22.05 kHz), one per request, in request order.  marks=True: a list of
         (audio, marks.SpeechMarks) per request instead (as Synth.synth_audio(..., marks=True)), through every shard path.  `seeds`: optional
-        per-request noise seeds (default: a running counter), `speaker_ids`: one id or one per request.  `sample_rate`: output rate
+        per-request noise seeds (default: a running counter), `speaker_ids`: one id or one per request.  `noise_level` / `speech_rate` /
+        `duration_noise_level`: one value or one per request (VITS-family voices: the requests still share their batches, each with its own
+        scales, include/vits_prosody.h).  `sample_rate`: output rate
         in Hz for the whole batch (default: the voice's own; include/vits_resample.h).  `denoiser_strength`: the vocoder-bias
         denoiser of a multistream voice for the whole batch (default: the voice's inference.denoiser_strength, else off; as
         Synth.synth_audio, a VITS-family voice raises ValueError), every item denoised from its own length before any resampling.
@@ -202,13 +212,26 @@ class MultiDeviceSynth:
         return with_marks(scatter_results(n, [idx for idx in shards if idx], [f.result() for f in futs if f is not None]))
 
     def _call_params(self, n, speaker_ids, noise_level, speech_rate, duration_noise_level, scale, seeds):
-        """runtime defaults (synth.py:50-56,106) and per-request speaker ids / seeds"""
+        """runtime defaults (synth.py:50-56,106) and per-request speaker ids / seeds.  noise_level / speech_rate / duration_noise_level:
+        one value, or one per request -- `scales` is then float32 [n, 3], every request's own triple (the reference server hands every
+        request its own speech_rate hint, server/tts_service.proto Hints.speech_rate)"""
         inf = self.synths[0].model.config.get("inference", {})
         noise_level = inf.get("noise_level", 0.8) if noise_level is None else noise_level
         speech_rate = inf.get("speech_rate", 1.0) if speech_rate is None else speech_rate
         duration_noise_level = inf.get("duration_noise_level", 0.8) if duration_noise_level is None else duration_noise_level
         scale = inf.get("scale", 1.0) if scale is None else scale
-        scales = np.array([noise_level, 1.0 / speech_rate, duration_noise_level], np.float32)  # synth.py:106
+        if all(np.isscalar(v) for v in (noise_level, speech_rate, duration_noise_level)):
+            scales = np.array([noise_level, 1.0 / speech_rate, duration_noise_level], np.float32)  # synth.py:106
+        else:
+            if self.family == "multistream":
+                raise ValueError("noise_level / speech_rate / duration_noise_level per request: the VITS-family voices only (include/vits_prosody.h)")
+            cols = []
+            for name, v in (("noise_level", noise_level), ("speech_rate", speech_rate), ("duration_noise_level", duration_noise_level)):
+                a = np.full(n, v, np.float64) if np.isscalar(v) else np.asarray(list(v), np.float64)
+                if a.shape != (n,):
+                    raise ValueError(f"{name}: one value, or one per request ({n})")
+                cols.append(a)
+            scales = np.stack([cols[0], 1.0 / cols[1], cols[2]], axis=1).astype(np.float32)
         sids = [speaker_ids] * n if np.isscalar(speaker_ids) or speaker_ids is None else list(speaker_ids)
         sids = [0 if v is None else int(v) for v in sids]
         if seeds is None:
@@ -243,7 +266,7 @@ class MultiDeviceSynth:
         if not per_request:
             def run_part(part):
                 f = synth.front_batch([texts[i] for i in part], [sids[i] for i in part])
-                feed = {"input": f["input"], "input_lengths": f["input_lengths"], "scales": scales, "sid": f["sid"], "bert": f["bert"],
+                feed = {"input": f["input"], "input_lengths": f["input_lengths"], **self._scales_feed(scales, part), "sid": f["sid"], "bert": f["bert"],
                         "phone_duration_extra": None, "vits.solo": True, "vits.item_seeds": np.array([seeds[i] for i in part], np.uint64),
                         **(loud or {})}
                 with self._replica_locks[r]:
@@ -268,8 +291,8 @@ class MultiDeviceSynth:
             for b, k in enumerate(part):
                 ids[b, :lens[b]] = fronts[k][0]
                 bert[b, :, :lens[b]] = fronts[k][1]
-            feed = {"input": ids, "input_lengths": lens, "scales": scales, "sid": np.array([sids[idx[k]] for k in part], np.int64),
-                    "bert": bert, "phone_duration_extra": None, "vits.solo": True,
+            feed = {"input": ids, "input_lengths": lens, **self._scales_feed(scales, [idx[k] for k in part]),
+                    "sid": np.array([sids[idx[k]] for k in part], np.int64), "bert": bert, "phone_duration_extra": None, "vits.solo": True,
                     "vits.item_seeds": np.array([seeds[idx[k]] for k in part], np.uint64), **(loud or {})}
             with self._replica_locks[r]:
                 pcm, lengths, ends = self._pcm16_marks(sess, feed, scale, sample_rate, marks)

@@ -176,6 +176,66 @@ def set_limit(opts, keep, spec, B, flag, out=None):
         out["reduction"] = red
 
 
+# include/vits_prosody.h
+FLAG_PROSODY = 32                # VITS_FLAG_PROSODY
+PROSODY_MAX_TOKEN_SCALE = 16.0   # VITS_PROSODY_MAX_TOKEN_SCALE
+PROSODY_FIT_RATIO = (0.25, 4.0)  # VITS_PROSODY_MIN_FIT_RATIO, VITS_PROSODY_MAX_FIT_RATIO
+
+
+class Prosody(ctypes.Structure):
+    """mirror of `struct vits_prosody` (include/vits_prosody.h)"""
+
+    _fields_ = [("item_scales", c_f32p), ("token_length_scale", c_f32p), ("token_pause", c_i32p), ("fit_frames", c_i32p),
+                ("out_fit_ratio", c_f32p)]
+
+
+class SynthProsodyOpts(SynthLimitOpts):
+    """mirror of `struct vits_synth_opts_prosody` (include/vits_prosody.h): SynthLimitOpts followed by the pointer to the controls, which
+    the library reads only under VITS_FLAG_PROSODY (the loudness, pitch and limiter fields inside still only under their own flags)"""
+
+    _fields_ = [("prosody", ctypes.POINTER(Prosody))]
+
+
+def prosody_arrays(B, Tx, item_scales=None, token_length_scale=None, token_pause=None, fit_frames=None):
+    """The controls a call asks for -> None (none) or a dict of contiguous arrays of the shapes include/vits_prosody.h states.  Only the
+    shapes are checked here (ValueError): the values are the library's to refuse, by name (VITS_ERR_ARG)."""
+    if item_scales is None and token_length_scale is None and token_pause is None and fit_frames is None:
+        return None
+    out = {}
+    for name, a, conv, shape in (("item_scales", item_scales, _f32, (B, 3)), ("token_length_scale", token_length_scale, _f32, (B, Tx)),
+                                 ("token_pause", token_pause, _i32, (B, Tx)), ("fit_frames", fit_frames, _i32, (B,))):
+        if a is None:
+            continue
+        a = conv(a)
+        if a.shape != shape:
+            raise ValueError(f"{name} must be {list(shape)} (got {list(a.shape)})")
+        out[name] = a
+    return out
+
+
+def prosody_struct(arrays):
+    """a Prosody whose input pointers name the arrays of prosody_arrays() (which the caller keeps alive); absent ones are NULL"""
+    P = Prosody()
+    for name, typ in (("item_scales", c_f32p), ("token_length_scale", c_f32p), ("token_pause", c_i32p), ("fit_frames", c_i32p)):
+        setattr(P, name, _p(arrays.get(name), typ))
+    return P
+
+
+def set_prosody(opts, keep, arrays, B, out=None):
+    """Points a SynthProsodyOpts at the controls of prosody_arrays() and sets VITS_FLAG_PROSODY; the struct, the arrays and the [B] result
+    array are kept alive in `keep` and, when `out` is a dict, the result is published there as out["fit_ratio"]."""
+    if arrays is None:
+        return
+    P = prosody_struct(arrays)
+    ratio = np.full(B, np.nan, np.float32)
+    keep += [P, ratio] + list(arrays.values())
+    P.out_fit_ratio = _p(ratio, c_f32p)
+    opts.prosody = ctypes.pointer(P)
+    opts.flags |= FLAG_PROSODY
+    if out is not None:
+        out["fit_ratio"] = ratio
+
+
 class PersistInfo(ctypes.Structure):
     """mirror of `struct vits_persist_info` (vits_persist_state)"""
 
@@ -258,6 +318,7 @@ class VitsLib:
         self.has_pitch = False
         self.has_pitch_formant = False
         self.has_limit = False
+        self.has_prosody = False
         if self.is_device:
             c_i16p = ctypes.POINTER(ctypes.c_int16)
             f("synthesize_pcm16").argtypes = [ctypes.c_void_p, c_i64p, c_i64p, ctypes.c_int32, ctypes.c_int32, c_f32p, c_i64p,
@@ -345,6 +406,11 @@ class VitsLib:
                 if self.has_pitch_formant:
                     for name in ("op_pitch_shift_formant", "op_pitch_stretch_formant", "op_pitch_formant_gain"):
                         f(name).argtypes = [ctypes.c_int, c_f32p, c_i64p, ctypes.c_int32, ctypes.c_int64, ctypes.c_float, c_f32p]
+            # include/vits_prosody.h: prosody controls (the flag of the synthesize calls and the regulator's own door)
+            self.has_prosody = self.has("op_regulate")
+            if self.has_prosody:
+                f("op_regulate").argtypes = [ctypes.c_int, c_f32p, c_i32p, c_i64p, ctypes.c_int32, ctypes.c_int32, ctypes.c_float,
+                                             ctypes.POINTER(Prosody), c_i32p, c_i32p, c_i64p, c_f32p]
             if self.has("debug_clock_probe"):
                 f("debug_clock_probe").argtypes = [ctypes.c_int, ctypes.c_int32, ctypes.POINTER(ctypes.c_double), ctypes.c_int32]
 
@@ -602,6 +668,34 @@ class VitsLib:
 
         return self._items_door(_door, x, lengths, device, (float(semitones),), outs)
 
+    # ---- prosody controls (include/vits_prosody.h) ------------------------------
+    def _need_prosody(self):
+        if not self.has_prosody:
+            raise VitsError(4, "this backend has no prosody controls (include/vits_prosody.h)")
+
+    def op_regulate(self, logw, forced, lengths, length_scale=1.0, item_scales=None, token_length_scale=None, token_pause=None,
+                    fit_frames=None, device=0):
+        """vits_op_regulate, the controlled length regulator alone: logw float32 [B, T_x] or None with forced int32 [B, T_x], lengths [B]
+        -> (durations int32 [B, T_x], cum int32 [B, T_x], y_lengths int64 [B], fit_ratio float32 [B])"""
+        self._need_prosody()
+        logw = _f32(logw) if logw is not None else None
+        forced = _i32(forced) if forced is not None else None
+        src = logw if logw is not None else forced
+        if src is None or src.ndim != 2 or (logw is not None and forced is not None and logw.shape != forced.shape):
+            raise ValueError("logw / forced must be [B, T_x]")
+        B, Tx = src.shape
+        lengths = _i64(lengths).reshape(-1)
+        if lengths.shape != (B,):
+            raise ValueError("lengths must be [B]")
+        arrays = prosody_arrays(B, Tx, item_scales, token_length_scale, token_pause, fit_frames)
+        P = prosody_struct(arrays) if arrays is not None else None
+        dur, cum = np.zeros((B, Tx), np.int32), np.zeros((B, Tx), np.int32)
+        ylen, ratio = np.zeros(B, np.int64), np.zeros(B, np.float32)
+        self.check(self._fn("op_regulate")(device, _p(logw, c_f32p), _p(forced, c_i32p), _p(lengths, c_i64p), B, Tx, float(length_scale),
+                                           ctypes.byref(P) if P is not None else None, _p(dur, c_i32p), _p(cum, c_i32p), _p(ylen, c_i64p),
+                                           _p(ratio, c_f32p)))
+        return dur, cum, ylen, ratio
+
     def mas_maximum_path(self, values, t_ys, t_xs, device=0):
         """monotonic_align.maximum_path_c (core.pyx:35-42): values float32 [B,T_y,T_x] -> paths int32 [B,T_y,T_x]."""
         values = _f32(values)
@@ -648,10 +742,12 @@ class VitsModel:
             pass
 
     def _opts(self, B, Tx, noise_dp, noise_prior, forced_durations, seed, max_frames, solo=False, item_seeds=None, bert=None,
-              loudness=None, loudness_out=None, pitch=None, preserve_formants=False, limit=None):
+              loudness=None, loudness_out=None, pitch=None, preserve_formants=False, limit=None, prosody=None, prosody_out=None):
         pitch = pitch_spec(pitch)  # (None, or a shift that does not reduce to P = Q)
-        opts = SynthLimitOpts() if limit is not None else SynthOpts() if pitch is None else SynthPitchOpts()
+        opts = SynthProsodyOpts() if prosody is not None else SynthLimitOpts() if limit is not None else SynthOpts() if pitch is None else SynthPitchOpts()
         keep = []
+        if prosody is not None:
+            self.lib._need_prosody()
         if limit is not None:
             self.lib._need_limit()
         if pitch is not None:
@@ -692,6 +788,7 @@ class VitsModel:
         if pitch is not None:
             opts.flags |= FLAG_PITCH | (FLAG_PITCH_FORMANT if preserve_formants else 0)  # (the formant bit only with a pitch in effect)
             opts.pitch_semitones = pitch
+        set_prosody(opts, keep, prosody, B, prosody_out)
         return opts, keep
 
     # ---- the hot path -----------------------------------------------------
@@ -706,8 +803,13 @@ class VitsModel:
 
     def synthesize(self, ids, lengths, scales, sid, noise_dp=None, noise_prior=None, forced_durations=None, seed=0,
                    max_frames=0, solo=False, item_seeds=None, bert=None, sample_rate=None, marks=False, loudness=None, loudness_out=None,
-                   pitch=None, preserve_formants=False, limit=None):
-        """limit: a limit_spec() (VITS_FLAG_LIMIT, include/vits_limit.h): the look-ahead peak limiter with the loudness gain (a LUFS
+                   pitch=None, preserve_formants=False, limit=None, item_scales=None, token_length_scale=None, token_pause=None,
+                   fit_frames=None, fit_ratio=False):
+        """item_scales float [B, 3], token_length_scale float [B, T_x], token_pause int32 [B, T_x] frames, fit_frames int32 [B]
+        (VITS_FLAG_PROSODY, include/vits_prosody.h): per-item [noise_scale, length_scale, noise_scale_w], per-token rates, pauses appended
+        to a token's own span, and the frame count an item is fitted to (0: not fitted); fit_ratio=True appends the ratio s of every item,
+        float32 [B] (1 where nothing was fitted), to the returned tuple.
+        limit: a limit_spec() (VITS_FLAG_LIMIT, include/vits_limit.h): the look-ahead peak limiter with the loudness gain (a LUFS
         spec whose ceiling is 0) or alone; loudness_out then also receives "reduction" float32 [B].
         pitch: semitones in [-12, 12] (VITS_FLAG_PITCH, include/vits_pitch.h): every item shifted on the device behind the decoder,
         before the resampler; lengths and marks do not change.  preserve_formants (VITS_FLAG_PITCH_FORMANT): the spectral envelope stays
@@ -725,8 +827,10 @@ class VitsModel:
         scales = _f32(scales)
         if lengths.shape != (B,) or sid.shape != (B,) or scales.shape != (3,):
             raise ValueError("bad feed shapes")
+        pros_out = {}
         opts, keep = self._opts(B, Tx, noise_dp, noise_prior, forced_durations, seed, max_frames, solo, item_seeds, bert, loudness, loudness_out,
-                                pitch, preserve_formants, limit)
+                                pitch, preserve_formants, limit, prosody_arrays(B, Tx, item_scales, token_length_scale, token_pause, fit_frames),
+                                pros_out)
         out = c_f32p()
         ns = ctypes.c_int64()
         olen = np.zeros(B, dtype=np.int64)
@@ -750,12 +854,14 @@ class VitsModel:
             audio = np.ctypeslib.as_array(out, shape=(B, ns.value)).copy()
         finally:
             self.lib._fn("free_output")(out)
-        return (audio, olen, ends) if marks else (audio, olen)
+        res = (audio, olen, ends) if marks else (audio, olen)
+        return res + (pros_out.get("fit_ratio", np.ones(B, np.float32)),) if fit_ratio else res
 
     def synthesize_pcm16(self, ids, lengths, scales, sid, pcm_scale=1.0, noise_dp=None, noise_prior=None, forced_durations=None,
                          seed=0, max_frames=0, solo=False, item_seeds=None, bert=None, sample_rate=None, marks=False, loudness=None,
-                         loudness_out=None, pitch=None, preserve_formants=False, limit=None):
-        """pitch, preserve_formants, limit: as for synthesize.
+                         loudness_out=None, pitch=None, preserve_formants=False, limit=None, item_scales=None, token_length_scale=None,
+                         token_pause=None, fit_frames=None, fit_ratio=False):
+        """pitch, preserve_formants, limit, item_scales, token_length_scale, token_pause, fit_frames, fit_ratio: as for synthesize.
         synthesize() with Synth.synth_audio's `* scale` and audio_float_to_int16 (vosk_tts/synth.py:127-130) done on the
         device: returns (pcm int16 [B,S], out_lengths int64 [B]).  sample_rate: as for synthesize (vits_synthesize_pcm16_rate:
         the resampler does the conversion in its epilogue).  loudness / loudness_out: as for synthesize (pcm_scale multiplies the
@@ -765,8 +871,10 @@ class VitsModel:
         lengths = _i64(lengths); sid = _i64(sid); scales = _f32(scales)
         if lengths.shape != (B,) or sid.shape != (B,) or scales.shape != (3,):
             raise ValueError("bad feed shapes")
+        pros_out = {}
         opts, keep = self._opts(B, Tx, noise_dp, noise_prior, forced_durations, seed, max_frames, solo, item_seeds, bert, loudness, loudness_out,
-                                pitch, preserve_formants, limit)
+                                pitch, preserve_formants, limit, prosody_arrays(B, Tx, item_scales, token_length_scale, token_pause, fit_frames),
+                                pros_out)
         out = ctypes.POINTER(ctypes.c_int16)()
         ns = ctypes.c_int64()
         olen = np.zeros(B, dtype=np.int64)
@@ -792,11 +900,16 @@ class VitsModel:
             pcm = np.ctypeslib.as_array(out, shape=(B, ns.value)).copy()
         finally:
             self.lib._fn("free_pcm16")(out)
-        return (pcm, olen, ends) if marks else (pcm, olen)
+        res = (pcm, olen, ends) if marks else (pcm, olen)
+        return res + (pros_out.get("fit_ratio", np.ones(B, np.float32)),) if fit_ratio else res
 
     def stream(self, ids, scales, sid, chunk_frames=64, noise_dp=None, noise_prior=None, forced_durations=None, seed=0, bert=None,
-               sample_rate=None, on_marks=None, loudness=None, pitch=None, limit=None):
-        """limit: refused, as loudness is (vits_stream_open* refuse VITS_FLAG_LIMIT).
+               sample_rate=None, on_marks=None, loudness=None, pitch=None, limit=None, item_scales=None, token_length_scale=None,
+               token_pause=None, fit_frames=None, fit_ratio=None):
+        """item_scales [1, 3], token_length_scale [1, T_x], token_pause [1, T_x], fit_frames [1]: the prosody controls of synthesize
+        (the open runs the controlled regulator; total_samples and the marks reflect them); fit_ratio: called once with the ratio,
+        float32 [1], as soon as the stream is open.
+        limit: refused, as loudness is (vits_stream_open* refuse VITS_FLAG_LIMIT).
         pitch: refused (vits_stream_open* refuse VITS_FLAG_PITCH the same way; here before any device work).
         Streaming synthesis of ONE utterance (vits_stream_*): a generator of float32 chunks of
         chunk_frames*hop_length samples (the last one shorter); their concatenation equals synthesize().
@@ -819,7 +932,9 @@ class VitsModel:
         ids = _i64(ids).reshape(1, -1)
         Tx = ids.shape[1]
         scales = _f32(scales)
-        opts, keep = self._opts(1, Tx, noise_dp, noise_prior, forced_durations, seed, 0, bert=bert)
+        pros_out = {}
+        opts, keep = self._opts(1, Tx, noise_dp, noise_prior, forced_durations, seed, 0, bert=bert,
+                                prosody=prosody_arrays(1, Tx, item_scales, token_length_scale, token_pause, fit_frames), prosody_out=pros_out)
         L = self.lib
         st = ctypes.c_void_p()
         total = ctypes.c_int64()
@@ -837,6 +952,8 @@ class VitsModel:
                 L._fn("stream_close")(st)
                 raise
             on_marks(ends)
+        if fit_ratio is not None:
+            fit_ratio(pros_out.get("fit_ratio", np.ones(1, np.float32)))
         return self._drain(st, chunk_frames, rate)
 
     def denoise_bias(self, filter_length=1024):

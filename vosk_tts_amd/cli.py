@@ -43,6 +43,12 @@ _OPTIONS = (
     (("--preserve-formants",), dict(action="store_true", default=None,
                                     help="with a pitch shift: keep the voice's formants where they were (default: the voice's "
                                          "inference.pitch_formants, else off)")),
+    (("--duration",), dict(type=float, default=None, metavar="SECONDS",
+                           help="speak the text in this many seconds: the durations are fitted to round(SECONDS * rate / hop) frames in one pass")),
+    (("--pause",), dict(action="append", default=None, metavar="INDEX:SECONDS",
+                        help="a pause of SECONDS behind word INDEX (counted from 0); repeatable")),
+    (("--word-rate",), dict(action="append", default=None, metavar="INDEX:RATE",
+                            help="speak word INDEX at RATE times the tempo (>1 is faster); repeatable")),
     (("--marks",), dict(type=str, default=None, metavar="FILE",
                         help="also write the speech marks as JSON: rate, phonemes and words with their offsets in samples and seconds")),
     (("--log-level",), dict(default="INFO", metavar="LEVEL", help="python logging level (INFO shows the RTF line)")),
@@ -54,6 +60,20 @@ def build_parser():
     for flags, kw in _OPTIONS:
         ap.add_argument(*flags, **kw)
     return ap
+
+
+def _indexed(pairs, flag):
+    """["INDEX:VALUE", ...] of a repeatable flag -> {index: value}, or None"""
+    if not pairs:
+        return None
+    out = {}
+    for p in pairs:
+        try:
+            k, v = p.split(":", 1)
+            out[int(k)] = float(v)
+        except ValueError:
+            raise SystemExit(f"{flag} {p!r}: expected INDEX:VALUE, e.g. 0:0.5")
+    return out
 
 
 def run(opts):
@@ -72,7 +92,9 @@ def run(opts):
     voice = model_mod.Model(opts.model, opts.model_name, opts.lang)
     marks = Synth(voice).synth(opts.input, opts.output, opts.speaker, speech_rate=opts.speech_rate, sample_rate=opts.sample_rate,
                                denoiser_strength=opts.denoiser_strength, marks=bool(opts.marks), loudness=opts.loudness, peak=opts.peak, pitch=opts.pitch,
-                               preserve_formants=opts.preserve_formants, **({} if opts.limit is None else {"limit": opts.limit}))
+                               preserve_formants=opts.preserve_formants, **({} if opts.limit is None else {"limit": opts.limit}),
+                               **{k: v for k, v in (("duration", getattr(opts, "duration", None)), ("pauses", _indexed(getattr(opts, "pause", None), "--pause")),
+                                                    ("word_rates", _indexed(getattr(opts, "word_rate", None), "--word-rate"))) if v is not None})
     if opts.marks:
         with open(opts.marks, "w", encoding="utf-8") as f:
             f.write(marks.to_json(indent=1) + "\n")

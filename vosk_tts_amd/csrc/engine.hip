@@ -29,11 +29,13 @@
 
 #include "../../include/vits_mi355.h"
 #include "../../include/vits_mi355_debug.h"
+#include "../../include/vits_prosody.h"
 #include "conv_mfma.hip.h"
 #include "conv_small.hip.h"
 #include "conv_sp.hip.h"
 #include "conv_bf3.hip.h"
 #include "kernels_misc.hip.h"
+#include "prosody.hip.h"
 #include "persist.hip.h"
 
 // ------------------------------------------------------------------------------------ errors
@@ -378,7 +380,9 @@ static int acoustic_host(HostStage& hs, const int64_t* ids, const int64_t* lengt
   vits_model* m = hs.m;
   const vits_hparams& hp = m->hp;
   const int I = hp.inter_channels;
-  const float noise_scale = scales[0], length_scale = scales[1], noise_scale_w = scales[2];
+  ProsodyReq pr;  // (include/vits_prosody.h: checked before anything is launched; at B == 1 item_scales are the call's scalars)
+  TRY(prosody_req(opts, lengths, B, Tx, scales, &pr));
+  const float noise_scale = pr.scales[0], length_scale = pr.scales[1], noise_scale_w = pr.scales[2];
   const uint64_t seed = opts ? opts->seed : 0;
   TRY(begin_stage(hs, B, Tx, 1, PERSIST_ENC | PERSIST_SDP));  // (text side first: no flow program for a one-frame layout)
   vits_session* s = hs.s;
@@ -394,7 +398,25 @@ static int acoustic_host(HostStage& hs, const int64_t* ids, const int64_t* lengt
     s->item_seeds = hs.to_dev(reinterpret_cast<const unsigned long long*>(opts->item_seeds), (size_t)B);
   }
   s->tile_keys.clear();
-  struct RaggedOff { vits_session* s; ~RaggedOff() { s->ragged = false; s->solo = false; } } ragged_off{s};
+  struct RaggedOff {
+    vits_session* s;
+    ~RaggedOff() { s->ragged = false; s->solo = false; s->item_scales = nullptr; s->ctl_on = false; s->ctl = RegCtl{}; s->ctl_req = nullptr; }
+  } ragged_off{s};
+  std::vector<float> fit_ratio;  // the regulator's ratio block on the host (controlled calls)
+  if (pr.per_item_noise) {
+    s->item_scales = hs.to_dev(pr.p->item_scales, (size_t)B * 3);
+    if (!s->item_scales) return fail(VITS_ERR_NOMEM, "device alloc failed");
+  }
+  if (pr.regulate) {
+    const vits_prosody* p = pr.p;
+    s->ctl = RegCtl{s->item_scales, hs.to_dev(p->token_length_scale, (size_t)B * Tx), hs.to_dev(p->token_pause, (size_t)B * Tx),
+                    hs.to_dev(p->fit_frames, (size_t)B), hs.dev_alloc<float>((size_t)2 * B)};
+    if ((p->token_length_scale && !s->ctl.tls) || (p->token_pause && !s->ctl.pause) || (p->fit_frames && !s->ctl.fit) || !s->ctl.ratio)
+      return fail(VITS_ERR_NOMEM, "device alloc failed");
+    s->ctl_on = true;
+    s->ctl_req = &pr;
+    fit_ratio.assign((size_t)2 * B, 1.f);
+  }
   float* d_bert = nullptr;
   if (hp.bert_dim > 0) {
     if (!opts || !opts->bert) return fail(VITS_ERR_ARG, "this voice is BERT-conditioned: the bert feed [B,%d,T_x] is required", hp.bert_dim);
@@ -420,7 +442,10 @@ static int acoustic_host(HostStage& hs, const int64_t* ids, const int64_t* lengt
     cum_out->assign((size_t)B * Tx, 0);
     HIP_TRY(hipMemcpyAsync(cum_out->data(), s->cum, sizeof(int) * (size_t)B * Tx, hipMemcpyDeviceToHost, s->stream));
   }
+  if (pr.regulate) HIP_TRY(hipMemcpyAsync(fit_ratio.data(), s->ctl.ratio, sizeof(float) * fit_ratio.size(), hipMemcpyDeviceToHost, s->stream));
   TRY(check_err(s));
+  if (pr.p && pr.p->out_fit_ratio)
+    for (int b = 0; b < B; ++b) pr.p->out_fit_ratio[b] = pr.regulate ? fit_ratio[b] : 1.f;
   int64_t Ty = 1;
   for (int b = 0; b < B; ++b) if (ylen[b] > Ty) Ty = ylen[b];
   if (opts && opts->max_frames > 0 && Ty > opts->max_frames) return fail(VITS_ERR_ARG, "T_y %lld exceeds max_frames %d", (long long)Ty, opts->max_frames);
@@ -474,6 +499,48 @@ int vits_mas_maximum_path(int device, const float* values, const int32_t* t_ys, 
   if (d.ok()) hipLaunchKernelGGL(mas_kernel, dim3(B), dim3(256), lds, 0, d_v, d_ty, d_tx, Ty, Tx, d_d, d_p);
   d.finish();
   d.down(paths, d_p, n);
+  return d.rc();
+}
+
+// ---- the controlled length regulator alone (include/vits_prosody.h), host buffers
+int vits_op_regulate(int device, const float* logw, const int32_t* forced, const int64_t* lengths, int32_t B, int32_t Tx, float length_scale,
+                     const vits_prosody* p, int32_t* durations, int32_t* cum, int64_t* y_lengths, float* fit_ratio) {
+  if ((!logw && !forced) || !lengths || !durations || !cum || !y_lengths || B <= 0 || B > 65535 || Tx <= 0 || (long long)B * Tx >= (1LL << 31))
+    return fail(VITS_ERR_ARG, "regulate: bad argument");
+  std::vector<int> len32(B);
+  for (int b = 0; b < B; ++b) {
+    if (lengths[b] < 0 || lengths[b] > Tx) return fail(VITS_ERR_ARG, "regulate: length %lld of item %d outside [0, %d]", (long long)lengths[b], b, Tx);
+    len32[b] = (int)lengths[b];
+  }
+  static const vits_prosody none = {nullptr, nullptr, nullptr, nullptr, nullptr};
+  if (!p) p = &none;
+  TRY(prosody_check(p, forced != nullptr, lengths, B, Tx));
+  OpDoor d("regulate", device);
+  const size_t n = (size_t)B * Tx;
+  const float* d_logw = d.up(logw, n);
+  const int* d_forced = d.up(forced, n);
+  const int* d_len = d.up(len32.data(), B);
+  RegCtl c{d.up(p->item_scales, (size_t)B * 3), forced ? nullptr : d.up(p->token_length_scale, n), d.up(p->token_pause, n),
+           d.up(p->fit_frames, (size_t)B), d.out<float>((size_t)2 * B)};
+  int *d_dur = d.out<int>(n), *d_cum = d.out<int>(n), *d_y32 = d.out<int>(B), *d_err = d.out<int>(1, 0);
+  int64_t* d_y64 = d.out<int64_t>(B);
+  if (d.ok())
+    hipLaunchKernelGGL(regulate_ctl_kernel, dim3(B), dim3(256), 0, 0, d_logw, d_forced, d_len, length_scale, Tx, d_dur, d_cum, d_y32, d_y64, 0,
+                       d_err, (const SynthDev*)nullptr, (const float*)nullptr, 0, (const float*)nullptr, (const float*)nullptr, c);
+  d.finish();
+  int e = 0;
+  std::vector<float> ratio((size_t)2 * B);
+  d.down(&e, d_err, 1);
+  d.down(ratio.data(), c.ratio, ratio.size());
+  if (d.ok() && (e & REG_ERR_FIT)) {
+    ProsodyReq q;
+    q.p = p; q.lengths = lengths; q.B = B; q.Tx = Tx;
+    return prosody_fit_refused(q, ratio.data());
+  }
+  d.down(durations, d_dur, n);
+  d.down(cum, d_cum, n);
+  d.down(y_lengths, d_y64, B);
+  if (d.ok() && fit_ratio) for (int b = 0; b < B; ++b) fit_ratio[b] = ratio[b];
   return d.rc();
 }
 

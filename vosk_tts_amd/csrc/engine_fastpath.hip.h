@@ -43,11 +43,11 @@ struct FastBack {
   char* out_h = nullptr;           // pinned host copy of whichever output the call asked for
   size_t out_elems = 0;
   int* h_err = nullptr;            // pinned copy of s->d_err, written by the phase-2 graph
-  hipGraphExec_t g2[8] = {};       // [persist*4 + solo*2 + pcm]
+  hipGraphExec_t g2[16] = {};      // [item_scales*8 + persist*4 + solo*2 + pcm]; a call without per-item noise scales only ever touches 0..7
   // phase 2 at another output rate (include/vits_resample.h).  The rate changes a launch and the size of the output, so it is part of
   // the graph key: one entry per rate, with its own graphs and its own output buffers [B, ceil(T_y bucket * hop * L / M)].
   struct RateOut {
-    hipGraphExec_t g2[8] = {};     // as g2 above
+    hipGraphExec_t g2[16] = {};    // as g2 above
     void* y_d = nullptr;           // device: float or int16 (sized for float)
     char* y_h = nullptr;           // pinned host copy
     long long n_cap = 0;           // outputs per item
@@ -62,7 +62,11 @@ struct FastFront {
   char *io_h = nullptr, *io_d = nullptr;  // per-call inputs: pinned host mirror and device copy (SynthDev | lengths | sid | ids | forced | seeds [| bert])
   size_t io_bytes = 0, io_len = 0, io_sid = 0, io_ids = 0, io_forced = 0, io_seeds = 0, io_bert = 0;  // io_bert: float [B, bert_dim, TxB] (BERT-conditioned voices), 0 = none
   int64_t* h_ylen = nullptr;       // pinned [B] + one int error word behind it
-  hipGraphExec_t g1[16] = {};      // [marks*8 + persist*4 + forced*2 + solo]; a call without marks only ever touches 0..7
+  hipGraphExec_t g1[32] = {};      // [ctl*16 + marks*8 + persist*4 + forced*2 + solo]; a call without marks only ever touches 0..7, one without controls 0..15
+  // prosody controls (include/vits_prosody.h), behind everything an uncontrolled call copies (io_plain bytes): item scales float [B, 3],
+  // token_length_scale float [B, TxB], token_pause int32 [B, TxB], fit_frames int32 [B], and the regulator's ratio block (float [B] +
+  // int [B]), which the controlled variants of g1 copy back into the same place of the pinned mirror
+  size_t io_plain = 0, io_iscales = 0, io_tls = 0, io_pause = 0, io_fit = 0, io_ratio = 0;
   // speech marks (include/vits_marks.h): token ends int64 [B, T_x bucket] on the device and their pinned copy, allocated by the first
   // request that asks for marks; the marks variants of g1 write and copy them in front of the h_ylen copy
   long long* marks_d = nullptr;
@@ -141,6 +145,13 @@ static int front_acquire(vits_model* m, int B, int TxB, FastFront** out) {
     F->io_bert = F->io_bytes;
     F->io_bytes += align_up(sizeof(float) * (size_t)B * m->hp.bert_dim * TxB, 64) + 256;  // (+ slack: the program's operand window reads whole 16-column tiles)
   }
+  F->io_plain = F->io_bytes;  // (what the uncontrolled graphs copy: the block as it was before the controls)
+  F->io_iscales = F->io_bytes;
+  F->io_tls = F->io_iscales + align_up(sizeof(float) * (size_t)B * 3, 64);
+  F->io_pause = F->io_tls + align_up(sizeof(float) * (size_t)B * TxB, 64);
+  F->io_fit = F->io_pause + align_up(sizeof(int32_t) * (size_t)B * TxB, 64);
+  F->io_ratio = F->io_fit + align_up(sizeof(int32_t) * (size_t)B, 64);
+  F->io_bytes = F->io_ratio + align_up(sizeof(float) * (size_t)2 * B, 64);
   if (hipHostMalloc((void**)&F->io_h, F->io_bytes) != hipSuccess || hipMalloc((void**)&F->io_d, F->io_bytes) != hipSuccess ||
       hipHostMalloc((void**)&F->h_ylen, sizeof(int64_t) * (B + 1)) != hipSuccess) {
     front_free(F);
@@ -265,15 +276,25 @@ static int capture_end(vits_session* s, hipGraphExec_t* out, CaptureGuard* guard
 
 // marks: the variants that also turn cum into token ends (marks.hip.h) and copy them to F->marks_h, in front of the h_ylen copy -- the
 // host reads them after the one synchronisation the call performs anyway.  L / M of the call ride in the per-call block.
-static int phase1_launch(FastFront* F, bool forced, bool solo, bool marks = false) {
+// ctl (include/vits_prosody.h): the variants of a call whose controls reach past scalars -- they copy the whole input block, run the
+// launch branch with regulate_ctl_kernel in place of durations_kernel (never the single-utterance program), let the noise-scale kernel read
+// the item scales, and copy the regulator's ratio block back in front of the h_ylen copy.
+static int phase1_launch(FastFront* F, bool forced, bool solo, bool marks = false, bool ctl = false) {
   vits_session* s = F->s;
-  const int gi = (marks ? 8 : 0) + (persist_mask() ? 4 : 0) + (forced ? 2 : 0) + (solo ? 1 : 0);
+  const int gi = (ctl ? 16 : 0) + (marks ? 8 : 0) + (persist_mask() ? 4 : 0) + (forced ? 2 : 0) + (solo ? 1 : 0);
   if (!F->g1[gi]) {
     const int B = s->B, TxB = s->Tx;
     HIP_TRY(hipStreamBeginCapture(s->stream, hipStreamCaptureModeThreadLocal));
     CaptureGuard cg(s->stream);
-    hipMemcpyAsync(F->io_d, F->io_h, F->io_bytes, hipMemcpyHostToDevice, s->stream);
+    hipMemcpyAsync(F->io_d, F->io_h, ctl ? F->io_bytes : F->io_plain, hipMemcpyHostToDevice, s->stream);
     s->ragged = true; s->solo = solo; s->tile_keys.clear();
+    if (ctl) {
+      s->item_scales = reinterpret_cast<const float*>(F->io_d + F->io_iscales);
+      s->ctl = RegCtl{s->item_scales, reinterpret_cast<const float*>(F->io_d + F->io_tls), reinterpret_cast<const int*>(F->io_d + F->io_pause),
+                      reinterpret_cast<const int*>(F->io_d + F->io_fit), reinterpret_cast<float*>(F->io_d + F->io_ratio)};
+      s->ctl_on = true;
+    }
+    struct CtlOff { vits_session* s; ~CtlOff() { s->item_scales = nullptr; s->ctl_on = false; s->ctl = RegCtl{}; } } ctl_off{s};
     s->dv = reinterpret_cast<const SynthDev*>(F->io_d);
     s->item_seeds = reinterpret_cast<const unsigned long long*>(F->io_d + F->io_seeds);
     const int64_t* d_len = reinterpret_cast<const int64_t*>(F->io_d + F->io_len);
@@ -281,7 +302,7 @@ static int phase1_launch(FastFront* F, bool forced, bool solo, bool marks = fals
     const int64_t* d_ids = reinterpret_cast<const int64_t*>(F->io_d + F->io_ids);
     const int32_t* d_forced = reinterpret_cast<const int32_t*>(F->io_d + F->io_forced);
     run_cond(s, d_sid, B, d_len, s->len_x, TxB);
-    if (persist_mask() == (PERSIST_SDP | PERSIST_ENC | PERSIST_FLOW) && B == 1 && s->ps_front[forced ? 0 : 1].ok && (!F->io_bert || s->ps_bert)) {
+    if (!ctl && persist_mask() == (PERSIST_SDP | PERSIST_ENC | PERSIST_FLOW) && B == 1 && s->ps_front[forced ? 0 : 1].ok && (!F->io_bert || s->ps_bert)) {
       // text encoder [+ duration predictor] + durations as one persistent launch (a BERT-conditioned voice: the program reads the
       // `bert` tensor straight from the input block, two more steps)
       persist_launch(s, s->ps_front[forced ? 0 : 1], "front.persist", nullptr, 0.f, 0, d_ids, forced ? d_forced : nullptr, 1.f, 0.f);
@@ -295,6 +316,7 @@ static int phase1_launch(FastFront* F, bool forced, bool solo, bool marks = fals
       token_ends_launch(s, s->cum, s->len_x, B, TxB, s->m->hp.hop_length, 1, 1, s->dv, F->marks_d);
       hipMemcpyAsync(F->marks_h, F->marks_d, sizeof(int64_t) * (size_t)B * TxB, hipMemcpyDeviceToHost, s->stream);
     }
+    if (ctl) hipMemcpyAsync(F->io_h + F->io_ratio, F->io_d + F->io_ratio, sizeof(float) * (size_t)2 * B, hipMemcpyDeviceToHost, s->stream);
     hipMemcpyAsync(F->h_ylen, s->ylen64, sizeof(int64_t) * B, hipMemcpyDeviceToHost, s->stream);
     hipMemcpyAsync(F->h_ylen + B, s->d_err, sizeof(int), hipMemcpyDeviceToHost, s->stream);
     s->ragged = false; s->solo = false;
@@ -305,9 +327,11 @@ static int phase1_launch(FastFront* F, bool forced, bool solo, bool marks = fals
 }
 
 // R / T: the output rate's buffers and table (both null: the native rate)
-static int phase2_launch(FastFront* F, FastBack* Bk, bool solo, bool pcm, FastBack::RateOut* R = nullptr, const ResampleTab* T = nullptr) {
+// iscales (include/vits_prosody.h): the variants whose prior sample reads the item scales of the front's input block (B > 1 only)
+static int phase2_launch(FastFront* F, FastBack* Bk, bool solo, bool pcm, FastBack::RateOut* R = nullptr, const ResampleTab* T = nullptr,
+                         bool iscales = false) {
   vits_session* s = Bk->s;  // (its stream is the front's)
-  const int gi = (persist_mask() ? 4 : 0) + (solo ? 2 : 0) + (pcm ? 1 : 0);
+  const int gi = (iscales ? 8 : 0) + (persist_mask() ? 4 : 0) + (solo ? 2 : 0) + (pcm ? 1 : 0);
   hipGraphExec_t* g2 = R ? R->g2 : Bk->g2;
   if (!g2[gi]) {
     const int B = F->s->B, TxB = F->s->Tx, TyB = s->Ty;
@@ -315,8 +339,10 @@ static int phase2_launch(FastFront* F, FastBack* Bk, bool solo, bool pcm, FastBa
     HIP_TRY(hipStreamBeginCapture(s->stream, hipStreamCaptureModeThreadLocal));
     CaptureGuard cg(s->stream);
     s->ragged = true; s->solo = solo; s->rag_b1 = true; s->tile_keys.clear();
+    s->item_scales = iscales ? reinterpret_cast<const float*>(F->io_d + F->io_iscales) : nullptr;
+    struct ScalesOff { vits_session* s; ~ScalesOff() { s->item_scales = nullptr; } } scales_off{s};
     float* z;
-    if (persist_mask() == (PERSIST_SDP | PERSIST_ENC | PERSIST_FLOW) && B == 1 && s->ps_back.ok) {  // prior sample + flow as one persistent launch
+    if (!iscales && persist_mask() == (PERSIST_SDP | PERSIST_ENC | PERSIST_FLOW) && B == 1 && s->ps_back.ok) {  // prior sample + flow as one persistent launch
       persist_launch(s, s->ps_back, "back.persist");
       z = s->zB;
     } else {
@@ -354,6 +380,7 @@ static int device_error_word(int e) {
   if (e & 1) return fail(VITS_ERR_ARG, "token id out of range");
   if (e & 2) return fail(VITS_ERR_ARG, "speaker id out of range");
   if (e & 4) return fail(VITS_ERR_ARG, "T_y exceeds frame capacity");
+  if (e & REG_ERR_FIT) return fail(VITS_ERR_UNSUPPORTED, "fit_frames: a fit was refused");
   return e ? fail(VITS_ERR_DEVICE, "device error word %d", e) : VITS_OK;
 }
 
@@ -369,6 +396,8 @@ static int synth_fast(vits_model* m, const int64_t* ids, const int64_t* lengths,
   const bool pcm = q.pcm;
   const int TxB = (Tx + 7) / 8 * 8;
   const bool forced = opts && opts->forced_durations, solo = opts && (opts->flags & VITS_FLAG_SOLO_BATCH);
+  ProsodyReq pr;  // (include/vits_prosody.h: checked before anything is launched; at B == 1 item_scales are the call's scalars)
+  TRY(prosody_req(opts, lengths, B, Tx, scales, &pr));
   // (declared before the session guard: the call's last stream synchronisation happens before this scope ends)
   InFlight inflight(m->device);
   PersistScope pscope(B == 1 ? m->device : -1, inflight.before);  // a single utterance takes the persistent stages when the device is quiet enough as it starts
@@ -388,7 +417,7 @@ static int synth_fast(vits_model* m, const int64_t* ids, const int64_t* lengths,
   // ---- inputs -> pinned block
   SynthDev* hv = reinterpret_cast<SynthDev*>(F->io_h);
   hv->rate_L = T ? T->P.L : 1; hv->rate_M = T ? T->P.M : 1;
-  hv->scales[0] = scales[0]; hv->scales[1] = scales[1]; hv->scales[2] = scales[2];
+  hv->scales[0] = pr.scales[0]; hv->scales[1] = pr.scales[1]; hv->scales[2] = pr.scales[2];
   hv->pcm_scale = q.pcm_scale;
   hv->seed = opts ? opts->seed : 0;
   int64_t* h_len = reinterpret_cast<int64_t*>(F->io_h + F->io_len);
@@ -404,17 +433,36 @@ static int synth_fast(vits_model* m, const int64_t* ids, const int64_t* lengths,
   pad_rows(h_ids, ids, B, Tx, TxB);
   if (forced) pad_rows(h_forced, opts->forced_durations, B, Tx, TxB);
   if (F->io_bert) pad_rows(reinterpret_cast<float*>(F->io_h + F->io_bert), opts->bert, (size_t)B * hp.bert_dim, Tx, TxB);  // [B, bert_dim, Tx] -> [B, bert_dim, TxB]
+  if (pr.regulate) {  // the controls, an absent one as its neutral value: the call's scalars, ones, no pause, no fit
+    const vits_prosody* p = pr.p;
+    float* h_isc = reinterpret_cast<float*>(F->io_h + F->io_iscales);
+    float* h_tls = reinterpret_cast<float*>(F->io_h + F->io_tls);
+    int32_t* h_pause = reinterpret_cast<int32_t*>(F->io_h + F->io_pause);
+    int32_t* h_fit = reinterpret_cast<int32_t*>(F->io_h + F->io_fit);
+    for (int b = 0; b < B; ++b) {
+      for (int k = 0; k < 3; ++k) h_isc[b * 3 + k] = pr.per_item_noise ? p->item_scales[(size_t)b * 3 + k] : pr.scales[k];
+      h_fit[b] = p->fit_frames ? p->fit_frames[b] : 0;
+    }
+    if (p->token_length_scale) pad_rows(h_tls, p->token_length_scale, B, Tx, TxB);
+    else std::fill(h_tls, h_tls + (size_t)B * TxB, 1.f);
+    if (p->token_pause) pad_rows(h_pause, p->token_pause, B, Tx, TxB);
+    else std::fill(h_pause, h_pause + (size_t)B * TxB, 0);
+  }
   // ---- phase 1 and the one host round trip
-  TRY(phase1_launch(F, forced, solo, token_ends != nullptr));
+  TRY(phase1_launch(F, forced, solo, token_ends != nullptr, pr.regulate));
   HIP_TRY(hipStreamSynchronize(st));
   {
     int e = 0;
     memcpy(&e, F->h_ylen + B, sizeof(int));
     if (e) {
       hipMemsetAsync(F->s->d_err, 0, sizeof(int), st);
+      if ((e & REG_ERR_FIT) && !(e & (PS_ERR_TIMEOUT | 7)) && pr.regulate)  // the regulator refused a fit: its ratio block names the item
+        return prosody_fit_refused(pr, reinterpret_cast<const float*>(F->io_h + F->io_ratio));
       return device_error_word(e);
     }
   }
+  if (pr.p && pr.p->out_fit_ratio)
+    for (int b = 0; b < B; ++b) pr.p->out_fit_ratio[b] = pr.regulate ? reinterpret_cast<const float*>(F->io_h + F->io_ratio)[b] : 1.f;
   int64_t Ty = 1;
   for (int b = 0; b < B; ++b) if (F->h_ylen[b] > Ty) Ty = F->h_ylen[b];
   if (opts && opts->max_frames > 0 && Ty > opts->max_frames) return fail(VITS_ERR_ARG, "T_y %lld exceeds max_frames %d", (long long)Ty, opts->max_frames);
@@ -461,7 +509,7 @@ static int synth_fast(vits_model* m, const int64_t* ids, const int64_t* lengths,
   if (q.pitch.on) {
     // include/vits_pitch.h: the float, native-rate form of the graph as it is, then the tail (out_tail.hip.h) as launches behind it on
     // the same stream, in buffers of this call (the graph's own copy of the unshifted float audio to the host is not used)
-    TRY(phase2_launch(F, Bk, solo, false));
+    TRY(phase2_launch(F, Bk, solo, false, nullptr, nullptr, pr.per_item_noise));
     std::vector<long long> h_len(B);
     for (int b = 0; b < B; ++b) h_len[b] = F->h_ylen[b] * hp.hop_length;
     TailBufs bufs;
@@ -493,7 +541,7 @@ static int synth_fast(vits_model* m, const int64_t* ids, const int64_t* lengths,
     const LoudWs& W = **pw;
     NormScratch NS;
     norm_ws_layout(lq, W, B, stride, &NS);
-    TRY(phase2_launch(F, Bk, solo, false, R, T));
+    TRY(phase2_launch(F, Bk, solo, false, R, T, pr.per_item_noise));
     const float* x_d = R ? static_cast<const float*>(R->y_d) : Bk->out_d;
     const int rL = T ? T->P.L : 1, rM = T ? T->P.M : 1;
     if (pcm) norm_launch<int16_t>(st, lq, NS, x_d, stride, stride, Bk->s->len_y, hp.hop_length, rL, rM, B, static_cast<int16_t*>(W.y_d()), stride, stride, q.pcm_scale, Bk->s);
@@ -502,7 +550,7 @@ static int synth_fast(vits_model* m, const int64_t* ids, const int64_t* lengths,
     hipMemcpyAsync(W.res_h(), W.S.res, sizeof(float) * 4 * (size_t)B, hipMemcpyDeviceToHost, st);
     src_h = W.y_h();
   } else {
-    TRY(phase2_launch(F, Bk, solo, pcm, R, T));
+    TRY(phase2_launch(F, Bk, solo, pcm, R, T, pr.per_item_noise));
   }
   char* h_out = host_out();
   if (!h_out) return VITS_ERR_NOMEM;

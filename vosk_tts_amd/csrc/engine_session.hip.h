@@ -26,6 +26,13 @@ struct vits_session {
   bool use_graph = true;
   const SynthDev* dv = nullptr;  // device parameter block of the graph-replayed fast path (null: scalars by value)
   const unsigned long long* item_seeds = nullptr;  // device [B]: per-item Philox seeds of a solo batch (null: seed + b)
+  // prosody controls of the call in progress (include/vits_prosody.h; set and cleared by the host paths): item_scales is what the two
+  // noise-scale kernels read (device [B, 3], null: the call's scalars); with ctl_on run_durations launches regulate_ctl_kernel on ctl.
+  // ctl_req: the call's request on the host, from which check_err words the refusal of a fit (null: the graph-replayed path words its own)
+  const float* item_scales = nullptr;
+  bool ctl_on = false;
+  RegCtl ctl = {};
+  const struct ProsodyReq* ctl_req = nullptr;
   bool ragged = false;  // full-path calls with B > 1: skip padding tiles of masked stages (set per call)
   bool solo = false;    // VITS_FLAG_SOLO_BATCH: every item as if synthesized alone (noise streams, decoder halo 0)
 

@@ -102,6 +102,73 @@ static int persist_timed_out() {
   return fail(VITS_ERR_DEVICE, "persistent kernel: exchange timed out (workgroups not co-resident?); off for %.1f s", iv * 1e-9);
 }
 
+// ---- prosody controls of a call (include/vits_prosody.h), on the host
+// What a call asks of the regulator and the noise-scale kernels.  p null: an uncontrolled call.  regulate: the controls reach past scalars
+// (the controlled regulator runs, the single-utterance programs do not); per_item_noise: the noise-scale kernels read item_scales.
+struct ProsodyReq {
+  const vits_prosody* p = nullptr;
+  bool regulate = false, per_item_noise = false;
+  float scales[3] = {0.f, 0.f, 0.f};  // the call's scalars, with item_scales folded in at B == 1
+  const int64_t* lengths = nullptr;
+  int B = 0, Tx = 0;
+};
+
+// The checks that need no device, before anything is launched: VITS_ERR_ARG naming item, token and value.
+static int prosody_check(const vits_prosody* p, bool forced, const int64_t* lengths, int B, int Tx) {
+  if (p->token_length_scale && forced)
+    return fail(VITS_ERR_ARG, "token_length_scale with forced_durations: a forced duration is the caller's own number and is not scaled");
+  for (int b = 0; b < B; ++b) {
+    if (p->item_scales)
+      for (int k = 0; k < 3; ++k) {
+        const float v = p->item_scales[(size_t)b * 3 + k];
+        if (!(v >= 0.f && v <= 3.4028235e38f)) return fail(VITS_ERR_ARG, "item_scales[%d, %d] = %g: an item scale must be finite and >= 0", b, k, (double)v);
+      }
+    if (p->fit_frames && p->fit_frames[b] < 0) return fail(VITS_ERR_ARG, "fit_frames[%d] = %d: must be >= 0 (0 = the item is not fitted)", b, p->fit_frames[b]);
+    const int64_t L = lengths[b] < Tx ? lengths[b] : Tx;
+    for (int64_t t = 0; t < L; ++t) {
+      const size_t o = (size_t)b * Tx + t;
+      if (p->token_length_scale) {
+        const float v = p->token_length_scale[o];
+        if (!(v >= 0.f && v <= VITS_PROSODY_MAX_TOKEN_SCALE))
+          return fail(VITS_ERR_ARG, "token_length_scale[%d, %lld] = %g: must be finite and in [0, %g]", b, (long long)t, (double)v, (double)VITS_PROSODY_MAX_TOKEN_SCALE);
+      }
+      if (p->token_pause && p->token_pause[o] < 0)
+        return fail(VITS_ERR_ARG, "token_pause[%d, %lld] = %d: a pause must be >= 0 frames", b, (long long)t, p->token_pause[o]);
+    }
+  }
+  return VITS_OK;
+}
+
+static int prosody_req(const vits_synth_opts* opts, const int64_t* lengths, int B, int Tx, const float* scales, ProsodyReq* out) {
+  *out = ProsodyReq();
+  for (int k = 0; k < 3; ++k) out->scales[k] = scales[k];
+  if (!opts || !(opts->flags & VITS_FLAG_PROSODY)) return VITS_OK;
+  static_assert(offsetof(vits_synth_opts_prosody, base) == 0, "the extended options begin with the plain ones");
+  const vits_prosody* p = reinterpret_cast<const vits_synth_opts_prosody*>(opts)->prosody;
+  if (!p) return fail(VITS_ERR_ARG, "VITS_FLAG_PROSODY with a NULL prosody pointer (include/vits_prosody.h)");
+  TRY(prosody_check(p, opts->forced_durations != nullptr, lengths, B, Tx));
+  out->p = p; out->lengths = lengths; out->B = B; out->Tx = Tx;
+  out->per_item_noise = p->item_scales && B > 1;
+  out->regulate = p->token_length_scale || p->token_pause || p->fit_frames || out->per_item_noise;
+  if (p->item_scales && B == 1) for (int k = 0; k < 3; ++k) out->scales[k] = p->item_scales[k];
+  return VITS_OK;
+}
+
+// The refusal of a fit, from the ratio block the regulator wrote (host copy: s [B], then the refused marks int [B]).
+static int prosody_fit_refused(const ProsodyReq& q, const float* ratio) {
+  const int* bad = reinterpret_cast<const int*>(ratio) + q.B;
+  for (int b = 0; b < q.B; ++b) {
+    if (!bad[b]) continue;
+    long long P = 0;
+    const int64_t L = q.lengths[b] < q.Tx ? q.lengths[b] : q.Tx;
+    if (q.p->token_pause) for (int64_t t = 0; t < L; ++t) P += q.p->token_pause[(size_t)b * q.Tx + t];
+    const int F = q.p->fit_frames ? q.p->fit_frames[b] : 0;
+    return fail(VITS_ERR_UNSUPPORTED, "fit_frames: item %d cannot be fitted to F = %d frames with P = %lld pause frames: s = (F - P) / U = %g, "
+                "and a fit needs F > P, U > 0 and s in [%g, %g]", b, F, P, (double)ratio[b], VITS_PROSODY_MIN_FIT_RATIO, VITS_PROSODY_MAX_FIT_RATIO);
+  }
+  return fail(VITS_ERR_UNSUPPORTED, "fit_frames: a fit was refused");
+}
+
 static int check_err(vits_session* s) {
   int e = 0;
   HIP_TRY(hipMemcpyAsync(&e, s->d_err, sizeof(int), hipMemcpyDeviceToHost, s->stream));
@@ -116,6 +183,12 @@ static int check_err(vits_session* s) {
     if (e & 1) return fail(VITS_ERR_ARG, "token id out of range");
     if (e & 2) return fail(VITS_ERR_ARG, "speaker id out of range");
     if (e & 4) return fail(VITS_ERR_ARG, "T_y exceeds frame capacity");
+    if (e & REG_ERR_FIT) {  // the regulator refused a fit: its ratio block says which item and at what ratio
+      if (!s->ctl_req || !s->ctl.ratio) return fail(VITS_ERR_UNSUPPORTED, "fit_frames: a fit was refused");
+      std::vector<float> ratio((size_t)2 * s->ctl_req->B);
+      HIP_TRY(hipMemcpy(ratio.data(), s->ctl.ratio, sizeof(float) * ratio.size(), hipMemcpyDeviceToHost));
+      return prosody_fit_refused(*s->ctl_req, ratio.data());
+    }
   }
   return VITS_OK;
 }
@@ -316,7 +389,8 @@ static void run_duration(vits_session* s, const float* x, const float* d_noise, 
   mark_masked(s, P, s->len_x);
   launch_conv(s, P, EPI_STORE, "dp.pre");
   run_dds_proj(s, m->dp_dds, s->dh, m->dp_proj, s->dc, "dp.proj", B, Tx);
-  hipLaunchKernelGGL(dp_init_z_kernel, dim3(cdiv(Tx, 64), 2, B), dim3(64), 0, s->stream, s->dz, d_noise, nsw, seed, Tx, s->solo ? 1 : 0, s->dv, s->item_seeds);
+  hipLaunchKernelGGL(dp_init_z_kernel, dim3(cdiv(Tx, 64), 2, B), dim3(64), 0, s->stream, s->dz, d_noise, nsw, seed, Tx, s->solo ? 1 : 0, s->dv, s->item_seeds,
+                     s->item_scales);
   int swap = 0;
   for (int k = hp.dp_n_flows - 1; k >= 1; --k) {
     swap ^= 1;  // Flip (modules.py:270-277) is a row relabel on the 2-channel z
@@ -336,6 +410,14 @@ static void run_duration(vits_session* s, const float* x, const float* d_noise, 
 static void run_durations(vits_session* s, const int* d_forced, float length_scale, int B, int Tx, int Tcap) {
   const bool ea = s->ea_pending && !d_forced;
   s->ea_pending = false;
+  if (s->ctl_on) {  // a controlled call (include/vits_prosody.h): a forced duration is not scaled per token
+    RegCtl c = s->ctl;
+    if (d_forced) c.tls = nullptr;
+    hipLaunchKernelGGL(regulate_ctl_kernel, dim3(B), dim3(256), 0, s->stream, s->logw, d_forced, s->len_x, length_scale, Tx, s->dur, s->cum,
+                       s->len_y, s->ylen64, Tcap, s->d_err, s->dv, ea ? s->dz : (const float*)nullptr, s->ea_row, (const float*)s->m->ea_m,
+                       (const float*)s->m->ea_logs, c);
+    return;
+  }
   hipLaunchKernelGGL(durations_kernel, dim3(B), dim3(256), 0, s->stream, s->logw, d_forced, s->len_x, length_scale, Tx, s->dur,
                      s->cum, s->len_y, s->ylen64, Tcap, s->d_err, s->dv, ea ? s->dz : (const float*)nullptr, s->ea_row,
                      (const float*)s->m->ea_m, (const float*)s->m->ea_logs);
@@ -346,7 +428,7 @@ static void run_expand(vits_session* s, const float* d_noise, long long noise_st
                        float* z_p, int B, int Tx, int Ty) {
   const int I = s->m->hp.inter_channels;
   hipLaunchKernelGGL(expand_prior_kernel, dim3(cdiv(Ty, 64), cdiv(I, EXPAND_CPB), B), dim3(256), 0, s->stream, s->stats, s->cum, s->len_y,
-                     d_noise, noise_stride, noise_scale, seed, z_p, I, Tx, Ty, s->solo ? 1 : 0, s->dv, s->item_seeds);
+                     d_noise, noise_stride, noise_scale, seed, z_p, I, Tx, Ty, s->solo ? 1 : 0, s->dv, s->item_seeds, s->item_scales);
 }
 
 // ---- a12-a14: ResidualCouplingTransformersBlock.forward(reverse=True) (models.py:750-757).

@@ -795,11 +795,13 @@ __global__ void __launch_bounds__(256, 2) relpos_attention_mfma_kernel(const flo
 // z[b,c,t] = noise * noise_scale_w  (models.py:96)
 // solo != 0 (VITS_FLAG_SOLO_BATCH): item b draws what a single-utterance call with seed + b would draw
 // item_seeds (optional, solo batches): per-item seeds instead of seed + b (requests batched by a server keep their own draw)
+// item_scales (optional, include/vits_prosody.h): [B, 3], nsw_b = item_scales[b, 2] replaces noise_scale_w
 __global__ void dp_init_z_kernel(float* z, const float* noise, float nsw, uint64_t seed, int T, int solo, const SynthDev* dv,
-                                 const unsigned long long* item_seeds) {
+                                 const unsigned long long* item_seeds, const float* item_scales) {
   const int t = blockIdx.x * blockDim.x + threadIdx.x, c = blockIdx.y, b = blockIdx.z;
   if (t >= T) return;
   if (dv) { nsw = dv->scales[2]; seed = dv->seed; }
+  if (item_scales) nsw = item_scales[b * 3 + 2];
   const long long o = ((long long)b * 2 + c) * T + t;
   const float e = noise ? noise[o] : (solo ? philox_normal(item_seeds ? item_seeds[b] : seed + (uint64_t)b, 1, (uint32_t)c, (uint32_t)t)
                                             : philox_normal(seed, 1, (uint32_t)(b * 2 + c), (uint32_t)t));
@@ -952,10 +954,11 @@ __global__ void durations_kernel(const float* logw, const int* forced, const int
 __global__ void __launch_bounds__(256) expand_prior_kernel(const float* stats, const int* cum, const int* ylen, const float* noise,
                                                            long long noise_stride, float noise_scale, uint64_t seed, float* z_p,
                                                            int I, int Tx, int Ty, int solo, const SynthDev* dv,
-                                                           const unsigned long long* item_seeds) {
+                                                           const unsigned long long* item_seeds, const float* item_scales) {
   const int f = blockIdx.x * 64 + (threadIdx.x & 63), cl = threadIdx.x >> 6, b = blockIdx.z;
   if (f >= Ty) return;
   if (dv) { noise_scale = dv->scales[0]; seed = dv->seed; }  // device parameter block (graph replay) instead of by value
+  if (item_scales) noise_scale = item_scales[b * 3];         // [B, 3] (include/vits_prosody.h): ns_b replaces noise_scale
   const int* cb = cum + (long long)b * Tx;
   int tok = -1;
   if (f < ylen[b] && f < cb[Tx - 1]) {

@@ -27,10 +27,10 @@ log = logging.getLogger(__name__)
 class _Pending:
     """one request waiting in the coalescer: its owner sleeps on `event` until a result (or an exception) is posted, or until it
     is handed a batch to lead"""
-    __slots__ = ("key", "ids", "sid", "seed", "event", "result", "error", "lead")
+    __slots__ = ("key", "ids", "sid", "seed", "extra", "event", "result", "error", "lead")
 
-    def __init__(self, key, ids, sid, seed):
-        self.key, self.ids, self.sid, self.seed = key, ids, sid, seed
+    def __init__(self, key, ids, sid, seed, extra=None):
+        self.key, self.ids, self.sid, self.seed, self.extra = key, ids, sid, seed, extra
         self.event = threading.Event()
         self.result = self.error = self.lead = None
 
@@ -41,8 +41,8 @@ class RequestCoalescer:
 
     Natural batching: a request that finds fewer than `max_inflight` engine calls running runs at once (the first of them on the
     persistent single-utterance path; nothing added to a lone client's latency).  Requests that arrive while `max_inflight` calls are in
-    flight queue up; when one of those calls returns, its thread hands the queue's compatible requests (same scales / output kind /
-    conversion scale / output sample rate, at most `max_batch`) to the first waiter, which runs them as ONE padded VITS_FLAG_SOLO_BATCH call with per-request
+    flight queue up; when one of those calls returns, its thread hands the queue's compatible requests (same output kind /
+    conversion scale / output sample rate, at most `max_batch`; a request's scales ride with it as `extra`, include/vits_prosody.h) to the first waiter, which runs them as ONE padded VITS_FLAG_SOLO_BATCH call with per-request
     item seeds -- every item of a solo batch is its own single-utterance synthesis (own Philox streams, zeros beyond its own end), so
     what a request gets does not depend on what it was batched with -- and scatters the results.
 
@@ -53,7 +53,7 @@ class RequestCoalescer:
     A lone client never waits (peak 1), a burst waits at most once per batch."""
 
     def __init__(self, run_batch, max_batch=32, max_inflight=1, gather_us=0):
-        self._run_batch = run_batch  # (key, [(ids, sid, seed), ...]) -> list of per-request results
+        self._run_batch = run_batch  # (key, [(ids, sid, seed, extra), ...]) -> list of per-request results
         self.max_batch = int(max_batch)
         self.max_inflight = max(1, int(max_inflight))  # engine calls that may run at the same time (the GPU overlaps a few small forwards)
         self.gather_us = float(gather_us)
@@ -125,10 +125,11 @@ class RequestCoalescer:
         head.lead = [head]
         return head
 
-    def submit(self, key, ids, sid, seed):
+    def submit(self, key, ids, sid, seed, extra=None):
+        """extra: what rides with the request into its batch without deciding which batch that is (the adapter: its scales)"""
         import time
 
-        me = _Pending(key, ids, sid, seed)
+        me = _Pending(key, ids, sid, seed, extra)
         promote = None
         with self._lock:
             if self._busy >= self.max_inflight or self._gathering:
@@ -163,7 +164,7 @@ class RequestCoalescer:
         # this thread leads `batch` (which contains its own request)
         try:
             try:
-                outs = self._run_batch(batch[0].key, [(p.ids, p.sid, p.seed) for p in batch])
+                outs = self._run_batch(batch[0].key, [(p.ids, p.sid, p.seed, p.extra) for p in batch])
                 for p, o in zip(batch, outs):
                     p.result = o
             except Exception as e:
@@ -176,7 +177,7 @@ class RequestCoalescer:
                     try:
                         for p in batch:
                             try:
-                                p.result = self._run_batch(p.key, [(p.ids, p.sid, p.seed)])[0]
+                                p.result = self._run_batch(p.key, [(p.ids, p.sid, p.seed, p.extra)])[0]
                             except Exception as e1:
                                 p.error = e1
                     except BaseException as e2:  # interrupted in the middle of the retries (the sibling handler below does not cover this one)
@@ -228,7 +229,10 @@ _OPTIONAL_NONE = ("bert", "phone_duration_extra")
 # extension feeds (not part of the ONNX graph) used by parity tests
 _EXT = ("vits.noise_dp", "vits.noise_prior", "vits.forced_durations", "vits.seed", "vits.solo", "vits.item_seeds", "vits.sample_rate", "vits.marks",
         "vits.loudness", "vits.peak", "vits.peak_ceiling", "vits.pitch", "vits.pitch_formants", "vits.limit", "vits.limit_lookahead_ms",
-        "vits.limit_release_ms")
+        "vits.limit_release_ms", "vits.item_scales", "vits.token_length_scale", "vits.token_pause", "vits.fit_frames")
+# the prosody controls of a request (include/vits_prosody.h): feed key -> keyword of capi.VitsModel.synthesize*
+_PROSODY = {"vits.item_scales": "item_scales", "vits.token_length_scale": "token_length_scale", "vits.token_pause": "token_pause",
+            "vits.fit_frames": "fit_frames"}
 
 
 class _Arg:
@@ -283,7 +287,7 @@ class VitsSession:
         Returns the request's token count (> 0) when it may be merged, 0 otherwise -- a length outside (0, T] is NOT sliced here:
         such a request takes the direct call, whose C-side check answers VITS_ERR_ARG as it always did."""
         if not (self.coalescer is not None and ids.shape[0] == 1 and self.hp.bert_dim == 0 and
-                not any(k in feed for k in ("vits.noise_dp", "vits.noise_prior", "vits.forced_durations", "vits.solo", "vits.item_seeds", "bert"))):
+                not any(k in feed for k in ("vits.noise_dp", "vits.noise_prior", "vits.forced_durations", "vits.solo", "vits.item_seeds", "bert") + tuple(_PROSODY))):
             return 0
         lens = np.asarray(feed["input_lengths"]).reshape(-1)
         if lens.shape[0] != 1:
@@ -292,7 +296,9 @@ class VitsSession:
         return n if 0 < n <= ids.shape[1] else 0
 
     def _run_solo_batch(self, key, reqs):
-        """reqs: [(ids [1,T] int64, sid, seed)] -> per request (audio-or-pcm [1,S_b], lengths [1]); one request: the plain call"""
+        """reqs: [(ids [1,T] int64, sid, seed, scales)] -> per request (audio-or-pcm [1,S_b], lengths [1]); one request: the plain call.
+        The scales ride with the request (include/vits_prosody.h): requests that agree on them run as the batch they always were, requests
+        that differ run as ONE solo batch with their scales as its item_scales."""
         # (rate: output sample rate in Hz, 0 = the voice's own; marks: the requests want their token ends, include/vits_marks.h.  Both are
         #  part of the key, so a batch has one rate and either every request of it gets a third value or none does)
         # loud: the normalisation of the batch (capi.loudness_spec(), None = none; include/vits_loudness.h): part of the key like the rate, and
@@ -300,11 +306,11 @@ class VitsSession:
         # pitch: the shift of the batch in semitones (None = none; include/vits_pitch.h): part of the key as well, one value per call
         # formants: that shift with the spectral envelope kept (VITS_FLAG_PITCH_FORMANT); False whenever pitch is None
         # limit: the limiter of the batch (capi.limit_spec(), None = none; include/vits_limit.h): part of the key, applied per item
-        kind, scales, scale, rate, marks, loud, pitch, formants, limit = key
+        kind, scale, rate, marks, loud, pitch, formants, limit = key
         pk = self._pitch_kw(pitch, formants, limit)
-        scales = np.array(scales, np.float32)
+        scales = np.array(reqs[0][3], np.float32)
         if len(reqs) == 1:
-            ids, sid, seed = reqs[0]
+            ids, sid, seed = reqs[0][:3]
             lens = np.array([ids.shape[1]], np.int64)
             if kind == "pcm":
                 return [self._model.synthesize_pcm16(ids, lens, scales, np.array([sid], np.int64), pcm_scale=scale, seed=seed, sample_rate=rate,
@@ -317,7 +323,9 @@ class VitsSession:
         n_pad = 1
         while n_pad < n_real:
             n_pad *= 2
-        reqs = list(reqs) + [(np.ones((1, 1), np.int64), 0, 0)] * (n_pad - n_real)
+        reqs = list(reqs) + [(np.ones((1, 1), np.int64), 0, 0, reqs[0][3])] * (n_pad - n_real)
+        if any(tuple(r[3]) != tuple(reqs[0][3]) for r in reqs):  # every item its own [noise_scale, length_scale, noise_scale_w]
+            pk = dict(pk, item_scales=np.array([r[3] for r in reqs], np.float32))
         lens = np.array([r[0].shape[1] for r in reqs], np.int64)
         batch = np.zeros((len(reqs), int(lens.max())), np.int64)
         for b, r in enumerate(reqs):
@@ -415,8 +423,8 @@ class VitsSession:
         limit = self._limit(feed)  # ("vits.limit": the look-ahead peak limiter with the loudness gain, or alone; include/vits_limit.h)
         n = self._coalescable(feed, ids)
         if n:
-            key = ("f32", tuple(float(v) for v in np.asarray(feed["scales"], np.float32).reshape(-1)), 1.0, rate, marks, loud, pitch, formants, limit)
-            res = self.coalescer.submit(key, np.ascontiguousarray(ids[:, :n], np.int64), int(sid[0]), int(seed))
+            key = ("f32", 1.0, rate, marks, loud, pitch, formants, limit)
+            res = self.coalescer.submit(key, np.ascontiguousarray(ids[:, :n], np.int64), int(sid[0]), int(seed), self._scales(feed))
             self.last_lengths = res[1]
             if marks:  # (the request's own tokens; columns beyond its length repeat the last end, as the C ABI pads them)
                 return [res[0][:, None, None, :], self._pad_ends(res[2], ids.shape[1])]
@@ -426,9 +434,26 @@ class VitsSession:
             noise_dp=feed.get("vits.noise_dp"), noise_prior=feed.get("vits.noise_prior"),
             forced_durations=feed.get("vits.forced_durations"), seed=int(seed), solo=bool(feed.get("vits.solo", False)),
             item_seeds=feed.get("vits.item_seeds"), bert=feed.get("bert"), sample_rate=rate, marks=marks, loudness=loud,
-            **self._pitch_kw(pitch, formants, limit))
+            **self._pitch_kw(pitch, formants, limit), **self._prosody(feed))
         self.last_lengths = res[1]
         return [res[0][:, None, None, :], res[2]] if marks else [res[0][:, None, None, :]]
+
+    @staticmethod
+    def _scales(feed):
+        """the request's scales as the tuple that rides with it through the coalescer"""
+        return tuple(float(v) for v in np.asarray(feed["scales"], np.float32).reshape(-1))
+
+    def _prosody(self, feed):
+        """The prosody controls of a request (include/vits_prosody.h) -> keywords of the model's calls, none without one (the call as it
+        was).  Feeds "vits.item_scales" float [B, 3], "vits.token_length_scale" float [B, T_x], "vits.token_pause" int32 [B, T_x] frames,
+        "vits.fit_frames" int32 [B]; values the engine would refuse are refused here, before any device work (ValueError naming them)."""
+        kw = {v: feed[k] for k, v in _PROSODY.items() if k in feed}
+        if kw:
+            from .prosody import check_controls
+
+            self._lib._need_prosody()
+            check_controls(np.asarray(feed["input_lengths"]).reshape(-1), forced="vits.forced_durations" in feed, **kw)
+        return kw
 
     def _marks(self, feed):
         """the "vits.marks" feed of a request -> bool; the CPU oracle has no marks, and says so"""
@@ -463,8 +488,8 @@ class VitsSession:
         limit = self._limit(feed)
         n = self._coalescable(feed, ids)
         if n:
-            key = ("pcm", tuple(float(v) for v in np.asarray(feed["scales"], np.float32).reshape(-1)), float(scale), rate, marks, loud, pitch, formants, limit)
-            res = self.coalescer.submit(key, np.ascontiguousarray(ids[:, :n], np.int64), int(sid[0]), int(seed))
+            key = ("pcm", float(scale), rate, marks, loud, pitch, formants, limit)
+            res = self.coalescer.submit(key, np.ascontiguousarray(ids[:, :n], np.int64), int(sid[0]), int(seed), self._scales(feed))
             pcm, lengths = res[0], res[1]
             self.last_lengths = lengths
             if marks:
@@ -476,7 +501,7 @@ class VitsSession:
             pcm_scale=float(scale), noise_dp=feed.get("vits.noise_dp"), noise_prior=feed.get("vits.noise_prior"),
             forced_durations=feed.get("vits.forced_durations"), seed=int(seed), solo=bool(feed.get("vits.solo", False)),
             item_seeds=feed.get("vits.item_seeds"), bert=feed.get("bert"), sample_rate=rate, marks=marks, loudness=loud,
-            **self._pitch_kw(pitch, formants, limit))
+            **self._pitch_kw(pitch, formants, limit), **self._prosody(feed))
         pcm, lengths = res[0], res[1]
         self.last_lengths = lengths
         if marks:
@@ -511,7 +536,7 @@ class VitsSession:
             noise_dp=None if nd is None else np.asarray(nd)[:, :, :n], noise_prior=feed.get("vits.noise_prior"),
             forced_durations=None if fd is None else np.asarray(fd)[:, :n], seed=seed,
             bert=None if bert is None else np.ascontiguousarray(np.asarray(bert, np.float32)[:, :, :n]), sample_rate=rate,
-            on_marks=on_marks)
+            on_marks=on_marks, **{k: (np.asarray(v)[:, :n] if k in ("token_length_scale", "token_pause") else v) for k, v in self._prosody(feed).items()})
 
     def warmup(self, max_tokens=128, frames_per_token=(2.0, 5.0), speaker_id=0, freeze_gc=False, typical_frames_per_token=3.0,
                stream_chunk_frames=None):

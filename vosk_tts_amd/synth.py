@@ -298,6 +298,59 @@ class Synth:
             return float(loud[0]), float(pk[0]), float(lib.op_true_peak(x, [x.shape[1]], int(rate or self.native_rate()), device=dev)[0])
         return float(loud[0]), float(pk[0])
 
+    def hop_length(self):
+        """frames to samples at the voice's own rate (the session's hparams; 256 for sessions that do not say)"""
+        sess = self.model.onnx
+        hp = getattr(getattr(sess, "_vocoder", None), "hp", None) or getattr(sess, "hp", None)
+        return int(getattr(hp, "hop_length", 0) or 256)
+
+    def _prosody_text(self, text, word_rates, pauses, duration):
+        """Before the front end sees the text: a multistream voice refuses the prosody keywords (that family keeps its own '_' markup),
+        and with the config key inference.pause_markup a VITS voice accepts the reference's '_' behind a word as a pause of
+        inference.pause_frames frames (default 20, the reference's value; off by default: '_' then reaches the front end as before).
+        -> (text, pauses)"""
+        multistream = (self.model.config.get("model_type") or "").startswith("multistream")
+        if multistream:
+            if word_rates or pauses or duration is not None:
+                raise ValueError("word_rates / pauses / duration are the prosody controls of the VITS-family voices; a multistream voice keeps "
+                                 "its own '_' pause markup")
+            return text, pauses
+        inf = self.model.config.get("inference", {})
+        if inf.get("pause_markup") and "_" in text:
+            from .prosody import PAUSE_FRAMES, split_pause_markup
+
+            text, after = split_pause_markup(text)
+            sec = int(inf.get("pause_frames", PAUSE_FRAMES)) * self.hop_length() / self.native_rate()
+            pauses = dict(pauses or {})
+            for w in after:
+                pauses[w] = pauses.get(w, 0.0) + sec
+        return text, pauses
+
+    def _prosody(self, args, text, word_rates=None, pauses=None, duration=None):
+        """Prosody controls of the request (include/vits_prosody.h; VITS-family voices): word_rates {word index: rate}, pauses {word
+        index: seconds behind that word}, duration = seconds the whole utterance is fitted to.  Words are counted as the speech marks
+        count them.  The feed gets "vits.token_length_scale", "vits.token_pause" (vosk_tts_amd/prosody.py token_controls) and
+        "vits.fit_frames" = round(duration * rate / hop); none given = off, the reference's behaviour."""
+        if not word_rates and not pauses and duration is None:
+            return False
+        from . import prosody as P
+
+        rate, hop = self.native_rate(), self.hop_length()
+        tls, pause = P.token_controls(self.marks_layout(text), word_rates, pauses, rate, hop)
+        T = np.asarray(args["input"]).shape[-1]
+        for name, a in (("vits.token_length_scale", tls), ("vits.token_pause", pause)):
+            if a is None:
+                continue
+            if a.shape[0] != T:
+                raise ValueError(f"token layout does not match: {a.shape[0]} tokens laid out for {T} ids")
+            args[name] = a[None]
+        if duration is not None:
+            F = P.frames(duration, rate, hop)
+            if F <= 0:
+                raise ValueError(f"duration {duration} s is less than one frame ({hop} samples at {rate} Hz)")
+            args["vits.fit_frames"] = np.array([F], np.int32)
+        return True
+
     def marks_layout(self, text):
         """The token layout of `text` under the front end _feed picks, for speech marks (vosk_tts_amd/marks.py):
         -> (symbols, ids per symbol, blank layout?, word_of per symbol, word_texts).  Needs the voice's config and dictionary only."""
@@ -329,8 +382,11 @@ class Synth:
 
     def synth_audio(self, text, speaker_id=0, noise_level=None, speech_rate=None, duration_noise_level=None, scale=None, sample_rate=None,
                     denoiser_strength=None, marks=False, loudness=None, peak=None, peak_ceiling=None, pitch=None,
-                    preserve_formants=None, limit=None, limit_lookahead_ms=None, limit_release_ms=None):
-        """limit / limit_lookahead_ms / limit_release_ms (extension): the look-ahead peak limiter, see _limit; peak_ceiling is then its
+                    preserve_formants=None, limit=None, limit_lookahead_ms=None, limit_release_ms=None, word_rates=None, pauses=None,
+                    duration=None):
+        """word_rates / pauses / duration (extension): per-word tempo, pauses behind words and the length of the whole utterance in
+        seconds, see _prosody.
+        limit / limit_lookahead_ms / limit_release_ms (extension): the look-ahead peak limiter, see _limit; peak_ceiling is then its
         ceiling.
         pitch / preserve_formants (extension): semitones by which the returned audio is shifted, and whether its formants stay where
         they were, see _pitch.
@@ -339,7 +395,9 @@ class Synth:
         loudness / peak / peak_ceiling (extension): a LUFS or a peak target for the returned audio, see _loudness.
         marks=True (extension): returns (audio, marks) -- marks.SpeechMarks with rate, token_ends, phonemes [(symbol, start, end)] and
         words [(text, start, end)] in samples of the returned audio, and seconds(); the default returns the array alone."""
+        text, pauses = self._prosody_text(text, word_rates, pauses, duration)
         args, scale = self._feed(text, speaker_id, noise_level, speech_rate, duration_noise_level, scale)
+        self._prosody(args, self.normalize(text), word_rates, pauses, duration)
         self._denoiser(args, denoiser_strength)
         self._loudness(args, loudness, peak, peak_ceiling)
         self._limit(args, limit, peak_ceiling, limit_lookahead_ms, limit_release_ms)
@@ -381,8 +439,9 @@ class Synth:
 
     def synth_stream(self, text, speaker_id=0, noise_level=None, speech_rate=None, duration_noise_level=None, scale=None,
                      chunk_frames=64, sample_rate=None, denoiser_strength=None, on_marks=None, loudness=None, peak=None, peak_ceiling=None,
-                     pitch=None, limit=None):
-        """limit: ValueError -- the limiter's look-ahead and its loudness passes need the whole utterance (a voice whose config names
+                     pitch=None, limit=None, word_rates=None, pauses=None, duration=None):
+        """word_rates / pauses / duration: as for synth_audio (the stream's open runs the controlled regulator; chunking is untouched).
+        limit: ValueError -- the limiter's look-ahead and its loudness passes need the whole utterance (a voice whose config names
         inference.limit streams unlimited).
         pitch: ValueError -- the phase recursion needs the frames before a chunk (a voice whose config names inference.pitch streams
         unshifted).
@@ -401,7 +460,9 @@ class Synth:
         if pitch is not None:
             raise ValueError("synth_stream cannot shift the pitch: the phase recursion needs the frames before a chunk, and its state is "
                              "not carried across chunks (synth_audio takes pitch=)")
+        text, pauses = self._prosody_text(text, word_rates, pauses, duration)
         args, scale = self._feed(text, speaker_id, noise_level, speech_rate, duration_noise_level, scale)
+        self._prosody(args, self.normalize(text), word_rates, pauses, duration)
         self._denoiser(args, denoiser_strength)
         if not hasattr(self.model.onnx, "run_stream"):
             raise NotImplementedError("this session type has no run_stream (VitsSession: vits_stream_open, SttsSession: stts_stream_open)")
@@ -417,12 +478,13 @@ class Synth:
 
     def synth(self, text, oname, speaker_id=0, noise_level=None, speech_rate=None, duration_noise_level=None, scale=None, sample_rate=None,
               denoiser_strength=None, marks=False, loudness=None, peak=None, peak_ceiling=None, pitch=None, preserve_formants=None,
-              limit=None, limit_lookahead_ms=None, limit_release_ms=None):
+              limit=None, limit_lookahead_ms=None, limit_release_ms=None, word_rates=None, pauses=None, duration=None):
         """marks=True: the utterance's marks.SpeechMarks are returned (the default returns None, as the reference does)"""
         audio = self.synth_audio(text, speaker_id, noise_level, speech_rate, duration_noise_level, scale, sample_rate, denoiser_strength, marks=marks,
                                  loudness=loudness, peak=peak, peak_ceiling=peak_ceiling, pitch=pitch,
                                  preserve_formants=preserve_formants, limit=limit, limit_lookahead_ms=limit_lookahead_ms,
-                                 limit_release_ms=limit_release_ms)
+                                 limit_release_ms=limit_release_ms, **{k: v for k, v in (("word_rates", word_rates), ("pauses", pauses), ("duration", duration))
+                                                                      if v is not None})
         sm = None
         if marks:
             audio, sm = audio
