@@ -236,6 +236,65 @@ def set_prosody(opts, keep, arrays, B, out=None):
         out["fit_ratio"] = ratio
 
 
+# include/vits_contour.h
+FLAG_CONTOUR = 64                # VITS_FLAG_CONTOUR (STTS_FLAG_CONTOUR has the same value)
+CONTOUR_DB = (-40.0, 12.0)       # VITS_CONTOUR_MIN_DB, VITS_CONTOUR_MAX_DB
+CONTOUR_RAMP = 4                 # VITS_CONTOUR_RAMP
+
+
+class Contour(ctypes.Structure):
+    """mirror of `struct vits_contour` (include/vits_contour.h)"""
+
+    _fields_ = [("token_semitones", c_f32p), ("token_gain_db", c_f32p)]
+
+
+class SynthContourOpts(SynthProsodyOpts):
+    """mirror of `struct vits_synth_opts_contour` (include/vits_contour.h): SynthProsodyOpts followed by the pointer to the contour, which
+    the library reads only under VITS_FLAG_CONTOUR"""
+
+    _fields_ = [("contour", ctypes.POINTER(Contour))]
+
+
+def contour_arrays(B, Tx, token_pitch=None, token_gain_db=None, lengths=None, pitch=None):
+    """The contour a call asks for -> None (none, or one whose every token is neutral) or a dict of contiguous float32 [B, T_x] arrays.
+    Values out of range (NaN included) are a ValueError naming item, token and value, as the library's VITS_ERR_ARG does: here they are
+    refused before any device work.  lengths: the items' token counts (values beyond them are not looked at); pitch: the call's own
+    shift, which the library adds to every token."""
+    if token_pitch is None and token_gain_db is None:
+        return None
+    out = {}
+    live = np.ones((B, Tx), bool) if lengths is None else np.arange(Tx)[None, :] < np.asarray(lengths).reshape(B, 1)
+    add = 0.0 if pitch is None else float(pitch)
+    for name, a, lo, hi, unit, off in (("token_semitones", token_pitch, -PITCH_MAX_SEMITONES, PITCH_MAX_SEMITONES, "semitones", add),
+                                       ("token_gain_db", token_gain_db, CONTOUR_DB[0], CONTOUR_DB[1], "dB", 0.0)):
+        if a is None:
+            continue
+        a = _f32(a)
+        if a.shape != (B, Tx):
+            raise ValueError(f"{name} must be {[B, Tx]} (got {list(a.shape)})")
+        v = a.astype(np.float64) + off
+        bad = live & ~((v >= lo) & (v <= hi))
+        if bad.any():
+            b, t = (int(i) for i in np.argwhere(bad)[0])
+            raise ValueError(f"contour: {v[b, t]:g} {unit} at item {b}, token {t} outside [{lo:g}, {hi:g}]")
+        out[name] = a
+    if all(not np.any(a[live]) for a in out.values()):
+        return None
+    return out
+
+
+def set_contour(opts, keep, arrays, flag=FLAG_CONTOUR):
+    """Points a SynthContourOpts / SttsContourOpts at the arrays of contour_arrays() and sets the flag; everything is kept alive in `keep`"""
+    if arrays is None:
+        return
+    C = Contour()
+    C.token_semitones = _p(arrays.get("token_semitones"), c_f32p)
+    C.token_gain_db = _p(arrays.get("token_gain_db"), c_f32p)
+    keep += [C] + list(arrays.values())
+    opts.contour = ctypes.pointer(C)
+    opts.flags |= flag
+
+
 class PersistInfo(ctypes.Structure):
     """mirror of `struct vits_persist_info` (vits_persist_state)"""
 
@@ -319,6 +378,7 @@ class VitsLib:
         self.has_pitch_formant = False
         self.has_limit = False
         self.has_prosody = False
+        self.has_contour = False
         if self.is_device:
             c_i16p = ctypes.POINTER(ctypes.c_int16)
             f("synthesize_pcm16").argtypes = [ctypes.c_void_p, c_i64p, c_i64p, ctypes.c_int32, ctypes.c_int32, c_f32p, c_i64p,
@@ -411,6 +471,12 @@ class VitsLib:
             if self.has_prosody:
                 f("op_regulate").argtypes = [ctypes.c_int, c_f32p, c_i32p, c_i64p, ctypes.c_int32, ctypes.c_int32, ctypes.c_float,
                                              ctypes.POINTER(Prosody), c_i32p, c_i32p, c_i64p, c_f32p]
+            # include/vits_contour.h: per-token pitch and volume contours (the flag of the synthesize calls and the two doors)
+            self.has_contour = self.has("op_contour")
+            if self.has_contour:
+                door = [ctypes.c_int, c_f32p, c_i64p, ctypes.c_int32, ctypes.c_int64, c_i32p, c_i64p, ctypes.c_int32, ctypes.c_int32, c_f32p, c_f32p]
+                f("op_contour").argtypes = door + [c_f32p]
+                f("op_contour_stretch").argtypes = door + [c_f32p, c_i64p]
             if self.has("debug_clock_probe"):
                 f("debug_clock_probe").argtypes = [ctypes.c_int, ctypes.c_int32, ctypes.POINTER(ctypes.c_double), ctypes.c_int32]
 
@@ -668,6 +734,46 @@ class VitsLib:
 
         return self._items_door(_door, x, lengths, device, (float(semitones),), outs)
 
+    # ---- per-token contours (include/vits_contour.h) ----------------------------
+    def _need_contour(self):
+        if not self.has_contour:
+            raise VitsError(4, "this backend has no pitch / volume contours (include/vits_contour.h)")
+
+    def _contour_door(self, name, x, lengths, cum, tok_lengths, hop, token_semitones, token_gain_db, device, outs):
+        self._need_contour()
+        x = _f32(x)
+        if x.ndim != 2:
+            raise ValueError("x must be [B, N]")
+        B, N = x.shape
+        lengths = _i64(lengths).reshape(-1)
+        cum = _i32(cum)
+        tok_lengths = _i64(tok_lengths).reshape(-1)
+        if lengths.shape != (B,) or tok_lengths.shape != (B,) or cum.ndim != 2 or cum.shape[0] != B:
+            raise ValueError("lengths and tok_lengths must be [B], cum [B, T_x]")
+        Tx = cum.shape[1]
+        st = None if token_semitones is None else _f32(token_semitones)
+        db = None if token_gain_db is None else _f32(token_gain_db)
+        for a in (st, db):
+            if a is not None and a.shape != (B, Tx):
+                raise ValueError("token_semitones / token_gain_db must be [B, T_x]")
+        ys = outs(B, N)
+        self.check(self._fn(name)(device, _p(x, c_f32p), _p(lengths, c_i64p), B, N, _p(cum, c_i32p), _p(tok_lengths, c_i64p), Tx, int(hop),
+                                  _p(st, c_f32p), _p(db, c_f32p), *[_p(y, c_f32p if y.dtype == np.float32 else c_i64p) for y in ys]))
+        return ys
+
+    def op_contour(self, x, lengths, cum, tok_lengths, hop, token_semitones=None, token_gain_db=None, device=0):
+        """vits_op_contour: x float32 [B, N], lengths [B], cum int32 [B, T_x] (inclusive frame counts), tok_lengths [B], hop samples per
+        frame, token_semitones / token_gain_db float32 [B, T_x] or None -> y float32 [B, N]; item b from x[b, :lengths[b]] only"""
+        return self._contour_door("op_contour", x, lengths, cum, tok_lengths, hop, token_semitones, token_gain_db, device,
+                                  lambda B, N: [np.empty((B, N), np.float32)])[0]
+
+    def op_contour_stretch(self, x, lengths, cum, tok_lengths, hop, token_semitones=None, token_gain_db=None, device=0):
+        """vits_op_contour_stretch: (u float32 [B, 256 * (2 * (N // 256 + 2) - 1)], steps int64 [B, 2 * (N // 256 + 2) + 2]); row b of steps
+        is F_s, a_0 .. a_{F_s}, then zeros"""
+        return tuple(self._contour_door("op_contour_stretch", x, lengths, cum, tok_lengths, hop, token_semitones, token_gain_db, device,
+                                        lambda B, N: [np.empty((B, 256 * (2 * (N // 256 + 2) - 1)), np.float32),
+                                                      np.empty((B, 2 * (N // 256 + 2) + 2), np.int64)]))
+
     # ---- prosody controls (include/vits_prosody.h) ------------------------------
     def _need_prosody(self):
         if not self.has_prosody:
@@ -742,9 +848,11 @@ class VitsModel:
             pass
 
     def _opts(self, B, Tx, noise_dp, noise_prior, forced_durations, seed, max_frames, solo=False, item_seeds=None, bert=None,
-              loudness=None, loudness_out=None, pitch=None, preserve_formants=False, limit=None, prosody=None, prosody_out=None):
+              loudness=None, loudness_out=None, pitch=None, preserve_formants=False, limit=None, prosody=None, prosody_out=None, contour=None):
         pitch = pitch_spec(pitch)  # (None, or a shift that does not reduce to P = Q)
-        opts = SynthProsodyOpts() if prosody is not None else SynthLimitOpts() if limit is not None else SynthOpts() if pitch is None else SynthPitchOpts()
+        if contour is not None:
+            self.lib._need_contour()
+        opts = SynthContourOpts() if contour is not None else SynthProsodyOpts() if prosody is not None else SynthLimitOpts() if limit is not None else SynthOpts() if pitch is None else SynthPitchOpts()
         keep = []
         if prosody is not None:
             self.lib._need_prosody()
@@ -789,6 +897,7 @@ class VitsModel:
             opts.flags |= FLAG_PITCH | (FLAG_PITCH_FORMANT if preserve_formants else 0)  # (the formant bit only with a pitch in effect)
             opts.pitch_semitones = pitch
         set_prosody(opts, keep, prosody, B, prosody_out)
+        set_contour(opts, keep, contour)
         return opts, keep
 
     # ---- the hot path -----------------------------------------------------
@@ -804,8 +913,11 @@ class VitsModel:
     def synthesize(self, ids, lengths, scales, sid, noise_dp=None, noise_prior=None, forced_durations=None, seed=0,
                    max_frames=0, solo=False, item_seeds=None, bert=None, sample_rate=None, marks=False, loudness=None, loudness_out=None,
                    pitch=None, preserve_formants=False, limit=None, item_scales=None, token_length_scale=None, token_pause=None,
-                   fit_frames=None, fit_ratio=False):
-        """item_scales float [B, 3], token_length_scale float [B, T_x], token_pause int32 [B, T_x] frames, fit_frames int32 [B]
+                   fit_frames=None, fit_ratio=False, token_pitch=None, token_gain_db=None):
+        """token_pitch / token_gain_db: float [B, T_x] semitones / dB per token (VITS_FLAG_CONTOUR, include/vits_contour.h): every token
+        raised or lowered by its own amount on the device, in the pitch stage's place; `pitch` is added to every token; lengths and marks
+        do not change.  Not with preserve_formants.
+        item_scales float [B, 3], token_length_scale float [B, T_x], token_pause int32 [B, T_x] frames, fit_frames int32 [B]
         (VITS_FLAG_PROSODY, include/vits_prosody.h): per-item [noise_scale, length_scale, noise_scale_w], per-token rates, pauses appended
         to a token's own span, and the frame count an item is fitted to (0: not fitted); fit_ratio=True appends the ratio s of every item,
         float32 [B] (1 where nothing was fitted), to the returned tuple.
@@ -830,7 +942,7 @@ class VitsModel:
         pros_out = {}
         opts, keep = self._opts(B, Tx, noise_dp, noise_prior, forced_durations, seed, max_frames, solo, item_seeds, bert, loudness, loudness_out,
                                 pitch, preserve_formants, limit, prosody_arrays(B, Tx, item_scales, token_length_scale, token_pause, fit_frames),
-                                pros_out)
+                                pros_out, contour_arrays(B, Tx, token_pitch, token_gain_db, lengths, pitch_spec(pitch)))
         out = c_f32p()
         ns = ctypes.c_int64()
         olen = np.zeros(B, dtype=np.int64)
@@ -860,8 +972,9 @@ class VitsModel:
     def synthesize_pcm16(self, ids, lengths, scales, sid, pcm_scale=1.0, noise_dp=None, noise_prior=None, forced_durations=None,
                          seed=0, max_frames=0, solo=False, item_seeds=None, bert=None, sample_rate=None, marks=False, loudness=None,
                          loudness_out=None, pitch=None, preserve_formants=False, limit=None, item_scales=None, token_length_scale=None,
-                         token_pause=None, fit_frames=None, fit_ratio=False):
-        """pitch, preserve_formants, limit, item_scales, token_length_scale, token_pause, fit_frames, fit_ratio: as for synthesize.
+                         token_pause=None, fit_frames=None, fit_ratio=False, token_pitch=None, token_gain_db=None):
+        """pitch, preserve_formants, limit, item_scales, token_length_scale, token_pause, fit_frames, fit_ratio, token_pitch,
+        token_gain_db: as for synthesize.
         synthesize() with Synth.synth_audio's `* scale` and audio_float_to_int16 (vosk_tts/synth.py:127-130) done on the
         device: returns (pcm int16 [B,S], out_lengths int64 [B]).  sample_rate: as for synthesize (vits_synthesize_pcm16_rate:
         the resampler does the conversion in its epilogue).  loudness / loudness_out: as for synthesize (pcm_scale multiplies the
@@ -874,7 +987,7 @@ class VitsModel:
         pros_out = {}
         opts, keep = self._opts(B, Tx, noise_dp, noise_prior, forced_durations, seed, max_frames, solo, item_seeds, bert, loudness, loudness_out,
                                 pitch, preserve_formants, limit, prosody_arrays(B, Tx, item_scales, token_length_scale, token_pause, fit_frames),
-                                pros_out)
+                                pros_out, contour_arrays(B, Tx, token_pitch, token_gain_db, lengths, pitch_spec(pitch)))
         out = ctypes.POINTER(ctypes.c_int16)()
         ns = ctypes.c_int64()
         olen = np.zeros(B, dtype=np.int64)

@@ -5,7 +5,8 @@ import ctypes
 
 import numpy as np
 
-from .capi import LIMIT_FIELDS, VitsError, VitsLib, _f32, _i32, _i64, _p, c_f32p, c_i32p, c_i64p, pitch_spec, set_limit, set_loudness
+from .capi import (LIMIT_FIELDS, Contour, VitsError, VitsLib, _f32, _i32, _i64, _p, c_f32p, c_i32p, c_i64p, contour_arrays, pitch_spec,
+                   set_contour, set_limit, set_loudness)
 from .weights_stts import SttsHParams
 
 
@@ -48,6 +49,16 @@ class SttsLimitOpts(SttsPitchOpts):
     reads only under STTS_FLAG_LIMIT"""
 
     _fields_ = LIMIT_FIELDS
+
+
+STTS_FLAG_CONTOUR = 64    # include/vits_contour.h
+
+
+class SttsContourOpts(SttsLimitOpts):
+    """mirror of `struct stts_synth_opts_contour` (include/vits_contour.h): SttsLimitOpts followed by the pointer to the contour, which
+    the library reads only under STTS_FLAG_CONTOUR"""
+
+    _fields_ = [("contour", ctypes.POINTER(Contour))]
 
 
 class SttsModel:
@@ -137,17 +148,20 @@ class SttsModel:
         assert isinstance(opts, SttsLimitOpts)
         set_limit(opts, keep, spec, B, STTS_FLAG_LIMIT, out)
 
-    def _opts_for(self, loudness, pitch, preserve_formants=False, limit=None):
-        """the options struct a call needs: the plain one, the one with the loudness fields, the one with the pitch behind those, or the
-        one with the limiter behind that; preserve_formants sets its bit only with a pitch in effect"""
+    def _opts_for(self, loudness, pitch, preserve_formants=False, limit=None, contour=None):
+        """the options struct a call needs: the plain one, the one with the loudness fields, the one with the pitch behind those, the
+        one with the limiter behind that, or the one with the contour pointer last; preserve_formants sets its bit only with a pitch in
+        effect"""
         if limit is not None and not getattr(self.vlib, "has_limit", False):
             raise VitsError(4, "this backend has no peak limiter (include/vits_limit.h)")
-        if pitch_spec(pitch) is not None or limit is not None:
+        if contour is not None and not getattr(self.vlib, "has_contour", False):
+            raise VitsError(4, "this backend has no pitch / volume contours (include/vits_contour.h)")
+        if pitch_spec(pitch) is not None or limit is not None or contour is not None:
             if pitch_spec(pitch) is not None and not getattr(self.vlib, "has_pitch", False):
                 raise VitsError(4, "this backend has no pitch shifter (include/vits_pitch.h)")
             if pitch_spec(pitch) is not None and preserve_formants and not getattr(self.vlib, "has_pitch_formant", False):
                 raise VitsError(4, "this backend has no formant-preserving pitch shift (include/vits_pitch.h, STTS_FLAG_PITCH_FORMANT)")
-            opts = SttsPitchOpts() if limit is None else SttsLimitOpts()
+            opts = SttsContourOpts() if contour is not None else SttsPitchOpts() if limit is None else SttsLimitOpts()
             if pitch_spec(pitch) is None:
                 return opts
             opts.flags |= STTS_FLAG_PITCH | (STTS_FLAG_PITCH_FORMANT if preserve_formants else 0)
@@ -162,8 +176,10 @@ class SttsModel:
     # ---- hot path ----------------------------------------------------------------------------
     def synthesize(self, ids, scales, sid, bert=None, phone_duration_extra=None, noise=None, seed=0, n_timesteps=0,
                    want_audio=True, want_mel=True, denoiser_strength=None, denoiser_filter_length=0, marks=False, sample_rate=None,
-                   loudness=None, loudness_out=None, pitch=None, preserve_formants=False, limit=None):
-        """limit: a capi.limit_spec() (STTS_FLAG_LIMIT, include/vits_limit.h): the peak limiter with the loudness gain or alone;
+                   loudness=None, loudness_out=None, pitch=None, preserve_formants=False, limit=None, token_pitch=None, token_gain_db=None):
+        """token_pitch / token_gain_db: float [T] semitones / dB per token (STTS_FLAG_CONTOUR, include/vits_contour.h): every token raised
+        or lowered by its own amount, in the pitch stage's place; `pitch` is added to every token.  Lengths and marks do not change.
+        limit: a capi.limit_spec() (STTS_FLAG_LIMIT, include/vits_limit.h): the peak limiter with the loudness gain or alone;
         loudness_out then also receives "reduction".
         pitch: semitones in [-12, 12] (STTS_FLAG_PITCH, include/vits_pitch.h): the audio shifted behind the denoiser, before any
         resampling; its length and the marks do not change.  preserve_formants (STTS_FLAG_PITCH_FORMANT): the spectral envelope stays
@@ -183,7 +199,12 @@ class SttsModel:
         T = ids.shape[1]
         scales = _f32(scales)
         keep = []
-        opts = self._opts_for(loudness, pitch if want_audio else None, preserve_formants, limit if want_audio else None)
+        con = None
+        if want_audio and (token_pitch is not None or token_gain_db is not None):
+            con = contour_arrays(1, T, None if token_pitch is None else _f32(token_pitch).reshape(1, -1),
+                                 None if token_gain_db is None else _f32(token_gain_db).reshape(1, -1), None, pitch_spec(pitch))
+        opts = self._opts_for(loudness, pitch if want_audio else None, preserve_formants, limit if want_audio else None, con)
+        set_contour(opts, keep, con, STTS_FLAG_CONTOUR)
         if noise is not None:
             a = _f32(noise); keep.append(a)
             if a.ndim != 2 or a.shape[0] != self.hp.n_feats:
@@ -269,8 +290,9 @@ class SttsModel:
 
     def synthesize_batch(self, ids, lengths, scales, sid, bert=None, phone_duration_extra=None, seed=0, n_timesteps=0, item_seeds=None,
                          denoiser_strength=None, denoiser_filter_length=0, marks=False, sample_rate=None, loudness=None, loudness_out=None,
-                         pitch=None, preserve_formants=False, limit=None):
-        """pitch, preserve_formants, limit: as for synthesize, one value for the batch; every item is shifted from its own length.
+                         pitch=None, preserve_formants=False, limit=None, token_pitch=None, token_gain_db=None):
+        """token_pitch / token_gain_db: float [B, T], as for synthesize.
+        pitch, preserve_formants, limit: as for synthesize, one value for the batch; every item is shifted from its own length.
         B independent utterances in one pass (stts_synthesize_batch): ids [B,5,T], lengths [B], sid [B];
         returns (audio float32 [B,S] zero-padded, out_lengths int64 [B] in samples).  Item b equals
         synthesize(ids[b][:, :lengths[b]], ..., seed=item_seeds[b]) (seed + b without item seeds).  marks=True
@@ -283,10 +305,12 @@ class SttsModel:
         B, five, T = ids.shape
         b = None if bert is None else _f32(bert)
         p = None if phone_duration_extra is None else _f32(phone_duration_extra)
-        opts = self._opts_for(loudness, pitch, preserve_formants, limit)
+        con = contour_arrays(B, T, token_pitch, token_gain_db, lengths, pitch_spec(pitch))
+        opts = self._opts_for(loudness, pitch, preserve_formants, limit, con)
         opts.seed = seed; opts.n_timesteps = n_timesteps
         self._denoise(opts, denoiser_strength, denoiser_filter_length)
         keep = []
+        set_contour(opts, keep, con, STTS_FLAG_CONTOUR)
         self._loudness(opts, keep, loudness, B, loudness_out)  # (per-item gains; loudness_out as for synthesize, [B])
         self._limit(opts, keep, limit, B, loudness_out)
         if item_seeds is not None:

@@ -49,6 +49,11 @@ _OPTIONS = (
                         help="a pause of SECONDS behind word INDEX (counted from 0); repeatable")),
     (("--word-rate",), dict(action="append", default=None, metavar="INDEX:RATE",
                             help="speak word INDEX at RATE times the tempo (>1 is faster); repeatable")),
+    (("--word-pitch",), dict(action="append", default=None, metavar="INDEX=SEMITONES",
+                             help="raise or lower word INDEX by SEMITONES, -12 to 12, at unchanged duration; repeatable")),
+    (("--word-gain",), dict(action="append", default=None, metavar="INDEX=DB",
+                            help="speak word INDEX DB decibels louder (-40 to 12); repeatable")),
+    (("--ssml",), dict(action="store_true", help="the input is an SSML document: speak, p, s, sub, break, prosody, mark")),
     (("--marks",), dict(type=str, default=None, metavar="FILE",
                         help="also write the speech marks as JSON: rate, phonemes and words with their offsets in samples and seconds")),
     (("--log-level",), dict(default="INFO", metavar="LEVEL", help="python logging level (INFO shows the RTF line)")),
@@ -62,17 +67,17 @@ def build_parser():
     return ap
 
 
-def _indexed(pairs, flag):
+def _indexed(pairs, flag, sep=":"):
     """["INDEX:VALUE", ...] of a repeatable flag -> {index: value}, or None"""
     if not pairs:
         return None
     out = {}
     for p in pairs:
         try:
-            k, v = p.split(":", 1)
+            k, v = p.split(sep, 1)
             out[int(k)] = float(v)
         except ValueError:
-            raise SystemExit(f"{flag} {p!r}: expected INDEX:VALUE, e.g. 0:0.5")
+            raise SystemExit(f"{flag} {p!r}: expected INDEX{sep}VALUE, e.g. 0{sep}0.5")
     return out
 
 
@@ -90,11 +95,31 @@ def run(opts):
     from .synth import Synth
 
     voice = model_mod.Model(opts.model, opts.model_name, opts.lang)
-    marks = Synth(voice).synth(opts.input, opts.output, opts.speaker, speech_rate=opts.speech_rate, sample_rate=opts.sample_rate,
+    synth = Synth(voice)
+    if getattr(opts, "ssml", False):  # the document's markup takes the place of the per-word flags
+        import wave
+
+        res = synth.synth_ssml(opts.input, speaker_id=opts.speaker, speech_rate=opts.speech_rate, sample_rate=opts.sample_rate,
+                               denoiser_strength=opts.denoiser_strength, marks=bool(opts.marks), loudness=opts.loudness, peak=opts.peak,
+                               pitch=opts.pitch, **({} if opts.limit is None else {"limit": opts.limit}),
+                               **({} if getattr(opts, "duration", None) is None else {"duration": opts.duration}))
+        audio, marks = res if opts.marks else (res, None)
+        with wave.open(opts.output, "w") as f:
+            f.setnchannels(1)
+            f.setsampwidth(2)
+            f.setframerate(int(opts.sample_rate) if opts.sample_rate else synth.native_rate())
+            f.writeframes(audio.tobytes())
+        if opts.marks:
+            with open(opts.marks, "w", encoding="utf-8") as f:
+                f.write(marks.to_json(indent=1) + "\n")
+        return 0
+    marks = synth.synth(opts.input, opts.output, opts.speaker, speech_rate=opts.speech_rate, sample_rate=opts.sample_rate,
                                denoiser_strength=opts.denoiser_strength, marks=bool(opts.marks), loudness=opts.loudness, peak=opts.peak, pitch=opts.pitch,
                                preserve_formants=opts.preserve_formants, **({} if opts.limit is None else {"limit": opts.limit}),
                                **{k: v for k, v in (("duration", getattr(opts, "duration", None)), ("pauses", _indexed(getattr(opts, "pause", None), "--pause")),
-                                                    ("word_rates", _indexed(getattr(opts, "word_rate", None), "--word-rate"))) if v is not None})
+                                                    ("word_rates", _indexed(getattr(opts, "word_rate", None), "--word-rate")),
+                                                    ("word_pitch", _indexed(getattr(opts, "word_pitch", None), "--word-pitch", "=")),
+                                                    ("word_gains", _indexed(getattr(opts, "word_gain", None), "--word-gain", "="))) if v is not None})
     if opts.marks:
         with open(opts.marks, "w", encoding="utf-8") as f:
             f.write(marks.to_json(indent=1) + "\n")

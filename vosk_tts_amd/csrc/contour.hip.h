@@ -1,0 +1,516 @@
+// contour.hip.h -- per-token pitch and volume contours (include/vits_contour.h): frame tracks from the tokens, the position recurrence,
+// the vocoder of pitch.hip.h driven by its step table, a warping windowed-sinc resampler and the gain curve.  Part of the ONE
+// translation unit engine.hip (included there, after pitch.hip.h, whose analysis kernel and TAB instantiations it launches).
+//
+// Launches per group of items (d_len: every item's samples; d_vlen: the same for the items that go through the vocoder, 0 for the
+// items of cases (b) and (c), which every vocoder kernel then leaves at once):
+//   contour_tracks_kernel   a thread per analysis row: Sigma_f by 2 R + 1 binary searches in cum, inc_f, gbar_f
+//   contour_steps_kernel    one wave per item, lane 0 walks the recurrence: F_s, a_0 .. a_{F_s}
+//   contour_analysis_kernel step 1 of the vocoder with the frame's transform in double (the reason stands at the kernel)
+//   pitch_phase_kernel<true>, pitch_synth_kernel<true>, pitch_ola_kernel<true>
+//   contour_warp_kernel     a workgroup per CT_TILE consecutive outputs of one item: u window, step slice and filter table in LDS
+//   contour_gain_kernel     the items of cases (b) and (c): y = G x
+#pragma once
+#include "../../include/vits_contour.h"
+
+#define CT_R VITS_CONTOUR_RAMP
+#define CT_K (2 * CT_R + 1)
+#define CT_RES VITS_CONTOUR_TABLE_RES
+#define CT_TAB (RS_Z * CT_RES + 2)       // floats of the filter table
+#define CT_TILE 256                      // outputs of one workgroup of contour_warp_kernel, one per thread
+#define CT_ASL 8                         // steps of the table a tile stages: it spans one analysis frame, a step is at least half of one
+#define CT_REACH (2 * RS_Z)              // Z / s at rho = 2
+#define CT_SPAN (2 * CT_TILE + 2 * CT_REACH + 16)  // u samples a tile stages (2 * 256 + 2 * 32 + 2 are needed at rho <= 2)
+#define CT_MIN_INC (1LL << 23)
+static_assert(PT_H == 256 && CT_TILE == PT_H, "a tile of the warp is one analysis hop: A = n << 16");
+
+__host__ __device__ __forceinline__ long long ct_frames(long long len) { return 1 + len / PT_H; }
+
+// the first t < n with cum[t] * hop > p, or n (cum is non-decreasing; at most 32 halvings)
+__device__ __forceinline__ int ct_tok(const int* __restrict__ cum, int n, long long hop, long long p) {
+  int lo = 0, hi = n;
+  for (int it = 0; it < 32 && lo < hi; ++it) {
+    const int mid = (lo + hi) >> 1;
+    if ((long long)cum[mid] * hop > p) hi = mid;
+    else lo = mid + 1;
+  }
+  return lo;
+}
+
+// inc [B][t_bstride] (rows f < F), gbar [B][t_bstride] (rows f <= F), F = 1 + len / H <= t_bstride - 1
+__global__ __launch_bounds__(256) void contour_tracks_kernel(const int* __restrict__ d_len, const int* __restrict__ cum, long long cum_bstride,
+                                                             const int* __restrict__ tok_len, long long hop, const int* __restrict__ ptok,
+                                                             const float* __restrict__ gtok, long long tok_bstride, int tok_max,
+                                                             long long* __restrict__ inc, float* __restrict__ gbar, long long t_bstride) {
+  const int b = blockIdx.y;
+  const long long f = (long long)blockIdx.x * 256 + threadIdx.x;
+  const long long len = d_len[b];
+  const long long F = ct_frames(len);
+  if (len <= 0 || f >= F || f + 1 >= t_bstride) return;
+  int n = tok_len[b];
+  n = n < 0 ? 0 : (n > tok_max ? tok_max : n);
+  const int* cb = cum + (long long)b * cum_bstride;
+  const int* pb = ptok + (long long)b * tok_bstride;
+  const float* gb = gtok + (long long)b * tok_bstride;
+  long long sig = 0;
+  double gs = 0.0;
+#pragma unroll
+  for (int j = -CT_R; j <= CT_R; ++j) {  // ascending j
+    long long ff = f + j;
+    ff = ff < 0 ? 0 : (ff > F - 1 ? F - 1 : ff);
+    long long p = ff * PT_H;
+    if (p > len - 1) p = len - 1;
+    const int t = ct_tok(cb, n, hop, p);
+    sig += t < n ? pb[t] : 1000;
+    gs += (double)(t < n ? gb[t] : 1.f);
+  }
+  long long v = sig > 0 ? (PT_ONE * 1000 * CT_K) / sig : CT_MIN_INC;
+  if (v < CT_MIN_INC) v = CT_MIN_INC;  // (never for the P the host hands over: Sigma <= 2000 K)
+  inc[(long long)b * t_bstride + f] = v;
+  const float g = (float)(gs / (double)CT_K);
+  gbar[(long long)b * t_bstride + f] = g;
+  if (f == F - 1) gbar[(long long)b * t_bstride + F] = g;
+}
+
+// steps [B][s_bstride]: row b = F_s, a_0 .. a_{F_s}.  The loop is bounded by 2 (F_a + 1) + 1 and every step is at least 2^23, so it ends
+// whatever inc holds; s_bstride >= 2 (F_a + 1) + 2.
+__global__ __launch_bounds__(64) void contour_steps_kernel(const int* __restrict__ d_vlen, const long long* __restrict__ inc, long long t_bstride,
+                                                           long long* __restrict__ steps, long long s_bstride) {
+  const int b = blockIdx.x;
+  if (threadIdx.x != 0) return;
+  long long* row = steps + (long long)b * s_bstride;
+  const long long Fa = pt_frames_a(d_vlen[b]);
+  long long cap = 2 * (Fa + 1);
+  if (cap > s_bstride - 2) cap = s_bstride - 2;
+  if (!Fa || cap < 0) { row[0] = 0; return; }
+  const long long* ib = inc + (long long)b * t_bstride;
+  const long long end = (Fa + 1) << 24;
+  long long a = 0, fs = 0;
+  for (long long t = 0; t <= cap; ++t) {
+    row[1 + t] = a;
+    if (a >= end) break;
+    fs = t + 1;
+    long long i = a >> 24;
+    if (i > Fa - 1) i = Fa - 1;
+    long long v = ib[i];
+    if (v < CT_MIN_INC) v = CT_MIN_INC;
+    a += v;
+  }
+  if (fs > cap) fs = cap;  // (a table cut short by s_bstride: never with the strides contour_run forms)
+  row[0] = fs;
+}
+
+// Step 1 of include/vits_pitch.h for the contour stage: rows [0, F_a + 2) of every item, the grid, the row ownership and the outputs of
+// pitch_analysis_kernel (mag / th: [B][a_bstride], row f at f * PT_NB; zeros in the two rows behind the last frame), with the transform of
+// the frame formed in double and the magnitude and the 32-bit turn rounded once.  The fp32 transform of pitch_analysis_kernel leaves
+// every bin a few 1e-7 of the frame's level from the exact spectrum; in the phases that error is added twice a step by the recursion,
+// and a contour runs up to two steps per analysis frame with weights that are exact: measured through vits_op_contour_stretch, u sat
+// at 4.8 to 4.9 times the float32 restatement's distance from float64 with it (and the same with atan2 alone taken in double).  The
+// transform is pitch_formant_kernel's: the window as sinpi^2, a 512-point radix-2 transform of the packed frame in LDS, its unpacking.
+__global__ __launch_bounds__(64 * DN_FPB) void contour_analysis_kernel(const float* __restrict__ x, long long x_bstride, long long x_n,
+                                                                       const int* __restrict__ d_vlen, float* __restrict__ mag,
+                                                                       unsigned* __restrict__ th, long long a_bstride) {
+  __shared__ double2 s_tw[PT_M];  // exp(-2 pi i t / n), t < n/2
+  __shared__ double2 s_z[DN_FPB][PT_M];
+  const int wv = threadIdx.x >> 6, t = threadIdx.x & 63;
+  const int b = blockIdx.y;
+  const long long len = d_vlen[b];
+  const long long Fa = pt_frames_a(len);
+  if (Fa == 0 || (long long)blockIdx.x * DN_FPB >= Fa + 2) return;  // uniform over the workgroup
+  const long long f = (long long)blockIdx.x * DN_FPB + wv;
+  const bool valid = f < Fa;
+  for (int i = threadIdx.x; i < PT_M; i += 64 * DN_FPB) {
+    double sn, cs;
+    sincospi((double)i * (2.0 / PT_N), &sn, &cs);
+    s_tw[i] = make_double2(cs, -sn);
+  }
+  // the windowed frame, two samples to a complex point, in bit-reversed order (a wave whose row is behind the last frame transforms zeros)
+  double2* Z = s_z[wv];
+  const float* xb = x + (long long)b * x_bstride;
+  for (int m = t; m < PT_M; m += 64) {
+    double v0 = 0.0, v1 = 0.0;
+    if (valid) {
+      const long long p = f * PT_H + 2 * m;
+      const double w0 = sinpi((double)(2 * m) * (1.0 / PT_N)), w1 = sinpi((double)(2 * m + 1) * (1.0 / PT_N));
+      v0 = (double)dn_load(xb, p, PT_M, len, 0, x_n) * (w0 * w0);
+      v1 = (double)dn_load(xb, p + 1, PT_M, len, 0, x_n) * (w1 * w1);
+    }
+    Z[__brev((unsigned)m) >> (32 - PT_LOG2M)] = make_double2(v0, v1);
+  }
+  __syncthreads();
+  for (int h = 1; h < PT_M; h <<= 1) {  // groups of 2 h points, twiddle exp(-2 pi i pos / (2 h))
+    for (int j = t; j < PT_M / 2; j += 64) {
+      const int pos = j & (h - 1), i0 = ((j - pos) << 1) + pos, i1 = i0 + h;
+      const double2 w = s_tw[pos * (PT_M / h)], u = Z[i0], v = Z[i1];
+      const double tr = w.x * v.x - w.y * v.y, ti = w.x * v.y + w.y * v.x;
+      Z[i0] = make_double2(u.x + tr, u.y + ti);
+      Z[i1] = make_double2(u.x - tr, u.y - ti);
+    }
+    __syncthreads();
+  }
+  if (f >= Fa + 2) return;
+  float* mo = mag + (long long)b * a_bstride + f * PT_NB;
+  unsigned* to = th + (long long)b * a_bstride + f * PT_NB;
+  for (int k = t; k < PT_NB; k += 64) {  // X[k] = E[k] + exp(-2 pi i k / n) O[k] of the packed transform
+    float m = 0.f;
+    unsigned a = 0u;
+    if (valid) {
+      const double2 zk = Z[k & (PT_M - 1)], zp = Z[(PT_M - k) & (PT_M - 1)];
+      const double2 w = k < PT_M ? s_tw[k] : make_double2(-1.0, 0.0);
+      const double er = 0.5 * (zk.x + zp.x), ei = 0.5 * (zk.y - zp.y), o_r = 0.5 * (zk.y + zp.y), o_i = -0.5 * (zk.x - zp.x);
+      const double xr = er + (w.x * o_r - w.y * o_i), xi = ei + (w.x * o_i + w.y * o_r);
+      m = (float)sqrt(xr * xr + xi * xi);
+      if (xr != 0.0 || xi != 0.0) a = (unsigned)(long long)rint(atan2(xi, xr) * 0.15915494309189533577 * 4294967296.0);  // the low 32 bits
+    }
+    mo[k] = m;
+    to[k] = a;
+  }
+}
+
+// G[n] of include/vits_contour.h: one rounding per operation, as the restatement has them
+__device__ __forceinline__ float ct_gain(const float* __restrict__ gb, long long n) {
+  const long long f = n >> 8;
+  const float fr = (float)(int)(n & 255) * (1.f / 256.f);
+  return __fadd_rn(__fmul_rn(__fsub_rn(1.f, fr), gb[f]), __fmul_rn(fr, gb[f + 1]));
+}
+
+template <typename OUT>
+__device__ __forceinline__ void ct_store(OUT* __restrict__ y, float v, float scale) {
+  if constexpr (sizeof(OUT) == sizeof(int16_t)) {  // pcm16_kernel's epilogue
+    float s = v * scale;
+    s = s * 32767.0f;
+    s = fminf(fmaxf(s, -32767.0f), 32767.0f);
+    *y = (OUT)(int)s;
+  } else {
+    *y = v;
+  }
+}
+
+// Outputs [0, n_count) of the items with d_vlen[b] > 0; u: [B][u_bstride]; y exactly 0 at and beyond len.
+template <typename OUT>
+__global__ __launch_bounds__(CT_TILE) void contour_warp_kernel(const float* __restrict__ u, long long u_bstride, const long long* __restrict__ steps,
+                                                               long long s_bstride, const float* __restrict__ gbar, long long t_bstride,
+                                                               const int* __restrict__ d_len, const int* __restrict__ d_vlen,
+                                                               const float* __restrict__ tab, OUT* __restrict__ y, long long y_bstride,
+                                                               long long n_count, float scale) {
+  __shared__ long long s_a[CT_ASL];
+  __shared__ float s_u[CT_SPAN];
+  __shared__ float s_T[CT_TAB];
+  const int b = blockIdx.y, tid = threadIdx.x;
+  const long long vlen = d_vlen[b], len = d_len[b];
+  if (vlen <= 0) return;  // (uniform) contour_gain_kernel's item
+  const long long n0 = (long long)blockIdx.x * CT_TILE, n = n0 + tid;
+  OUT* yo = y + (long long)b * y_bstride + n;
+  const long long Fa = pt_frames_a(vlen);
+  const long long* row = steps + (long long)b * s_bstride;
+  const long long Fs = pt_tab_fs(row, Fa);
+  if (n0 >= len || Fs < 2) {  // (uniform)
+    if (n < n_count) ct_store<OUT>(yo, 0.f, scale);
+    return;
+  }
+  const long long* ab = row + 1;  // a_0 .. a_{F_s}
+  const long long Nu = PT_H * (Fs - 1);
+  // the tile's first step: the largest t <= F_s - 1 with a_t <= A0 (a_0 = 0 <= A0); every thread runs the same search
+  const long long A0 = n0 << 16;
+  long long lo = 0, hi = Fs - 1;
+  for (int it = 0; it < 48 && lo < hi; ++it) {
+    const long long mid = (lo + hi + 1) >> 1;
+    if (ab[mid] <= A0) lo = mid;
+    else hi = mid - 1;
+  }
+  const long long t0 = lo;
+  if (tid < CT_ASL) s_a[tid] = ab[t0 + tid < Fs ? t0 + tid : Fs];
+  for (int j = tid; j < CT_TAB; j += CT_TILE) s_T[j] = tab[j];
+  // the u window of the tile: from floor(tau(n0)) - reach - 2
+  const long long a0 = ab[t0], d0 = ab[t0 + 1] - a0;  // (t0 + 1 <= F_s)
+  const double tau0 = d0 > 0 ? (double)PT_H * ((double)t0 + (double)(A0 - a0) / (double)d0) : 0.0;
+  const long long w_lo = (long long)floor(tau0) - CT_REACH - 2;
+  const float* ub = u + (long long)b * u_bstride;
+  const long long u_end = Nu < u_bstride ? Nu : u_bstride;
+  for (int j = tid; j < CT_SPAN; j += CT_TILE) {
+    const long long k = w_lo + j;
+    s_u[j] = (k >= 0 && k < u_end) ? ub[k] : 0.f;
+  }
+  __syncthreads();
+  if (n >= n_count) return;
+  float acc = 0.f;
+  bool live = n < len;
+  if (live) {
+    const long long A = n << 16;
+    int t = 0;
+#pragma unroll
+    for (int it = 0; it < CT_ASL - 2; ++it)
+      if (s_a[t + 1] <= A) ++t;
+    const long long at = s_a[t], d = s_a[t + 1] - at;
+    if (at <= A && d > 0 && A - at < d) {  // (else: a table that does not cover the tile; never with contour_steps_kernel's)
+      const double tau = (double)PT_H * ((double)(t0 + t) + (double)(A - at) / (double)d);
+      if (tau < (double)Nu) {
+        const double s = fmin(1.0, (double)d * (1.0 / (double)PT_ONE));
+        const double hw = (double)RS_Z / s;
+        long long klo = (long long)ceil(tau - hw), khi = (long long)floor(tau + hw);
+        if (klo < 0) klo = 0;
+        if (khi > u_end - 1) khi = u_end - 1;
+        if (khi - klo > 2 * CT_REACH + 2) khi = klo + 2 * CT_REACH + 2;  // (never: Z / s <= 2 Z)
+        const double sR = s * (double)CT_RES;
+        const float sf = (float)s;
+        for (long long k = klo; k <= khi; ++k) {  // ascending k
+          const double p = fabs(tau - (double)k) * sR;
+          int j = (int)p;
+          if (j > RS_Z * CT_RES) j = RS_Z * CT_RES;
+          const float fr = (float)(p - (double)j);
+          const float T0 = s_T[j];
+          const float h = sf * (T0 + fr * (s_T[j + 1] - T0));
+          const long long w = k - w_lo;
+          const float uu = (w >= 0 && w < CT_SPAN) ? s_u[w] : ub[k];  // (the window holds every tap at rho <= 2)
+          acc += uu * h;
+        }
+      }
+    }
+    acc = __fmul_rn(ct_gain(gbar + (long long)b * t_bstride, n), acc);
+  }
+  ct_store<OUT>(yo, acc, scale);
+}
+
+// Outputs [0, n_count) of the items with d_vlen[b] == 0: y[n] = G[n] x[n], exactly 0 at and beyond len.
+template <typename OUT>
+__global__ __launch_bounds__(256) void contour_gain_kernel(const float* __restrict__ x, long long x_bstride, const float* __restrict__ gbar,
+                                                           long long t_bstride, const int* __restrict__ d_len, const int* __restrict__ d_vlen,
+                                                           OUT* __restrict__ y, long long y_bstride, long long n_count, float scale) {
+  const int b = blockIdx.y;
+  const long long n = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (d_vlen[b] > 0 || n >= n_count) return;
+  const long long len = d_len[b];
+  float v = 0.f;
+  if (n < len && n < x_bstride) v = __fmul_rn(ct_gain(gbar + (long long)b * t_bstride, n), x[(long long)b * x_bstride + n]);
+  ct_store<OUT>(y + (long long)b * y_bstride + n, v, scale);
+}
+
+// ---- host ---------------------------------------------------------------------------------------------------------------
+// What a contoured call hands the device: P_t and g_t per token [B][Tx] (neutral beyond an item's tokens), and per item whether any of
+// its tokens is shifted.  on: some token of the call is not neutral (case (a) of the header otherwise).
+struct ContourReq {
+  bool on = false;
+  int Tx = 0;
+  std::vector<int> P;
+  std::vector<float> g;
+  std::vector<char> shift;
+};
+
+static int contour_plan(const float* semitones, const float* gain_db, float add_semitones, const int64_t* tok_lengths, int B, int Tx, ContourReq* q) {
+  *q = ContourReq();
+  q->Tx = Tx;
+  q->P.assign((size_t)B * Tx, 1000);
+  q->g.assign((size_t)B * Tx, 1.f);
+  q->shift.assign(B, 0);
+  for (int b = 0; b < B; ++b)
+    for (int t = 0; t < tok_lengths[b]; ++t) {
+      const size_t i = (size_t)b * Tx + t;
+      const double s = (semitones ? (double)semitones[i] : 0.0) + (double)add_semitones;
+      const double v = gain_db ? (double)gain_db[i] : 0.0;
+      if (!(fabs(s) <= (double)VITS_PITCH_MAX_SEMITONES))  // (NaN fails the comparison)
+        return fail(VITS_ERR_ARG, "contour: %g semitones at item %d, token %d outside [-%d, %d]", s, b, t, VITS_PITCH_MAX_SEMITONES, VITS_PITCH_MAX_SEMITONES);
+      if (!(v >= (double)VITS_CONTOUR_MIN_DB && v <= (double)VITS_CONTOUR_MAX_DB))
+        return fail(VITS_ERR_ARG, "contour: %g dB at item %d, token %d outside [%g, %g]", v, b, t, (double)VITS_CONTOUR_MIN_DB, (double)VITS_CONTOUR_MAX_DB);
+      q->P[i] = (int)lround(1000.0 * pow(2.0, s / 12.0));
+      q->g[i] = (float)pow(10.0, v / 20.0);
+      if (q->P[i] != 1000) q->shift[b] = 1;
+      if (q->P[i] != 1000 || q->g[i] != 1.f) q->on = true;
+    }
+  return VITS_OK;
+}
+
+// h_1 of include/vits_contour.h on the device, one copy per device (uploaded on first use, outside any capture; never freed)
+static std::mutex g_ct_mu;
+static std::map<int, float*> g_ct_tabs;
+
+static int contour_tab_get(int device, const float** out) {
+  std::lock_guard<std::mutex> g(g_ct_mu);
+  auto it = g_ct_tabs.find(device);
+  if (it == g_ct_tabs.end()) {
+    std::vector<float> T(CT_TAB, 0.f);
+    const double i0b = rs_bessel_i0(RS_BETA);
+    for (int j = 0; j <= RS_Z * CT_RES; ++j) {
+      const double yv = (double)j / (double)CT_RES, v = RS_RHO * yv, pv = M_PI * v;
+      const double sinc = j == 0 ? 1.0 : sin(pv) / pv;
+      const double r2 = std::max(1.0 - (yv / RS_Z) * (yv / RS_Z), 0.0);
+      T[j] = (float)(RS_RHO * sinc * rs_bessel_i0(RS_BETA * sqrt(r2)) / i0b);
+    }
+    HIP_TRY(hipSetDevice(device));
+    float* d = nullptr;
+    if (hipMalloc((void**)&d, sizeof(float) * CT_TAB) != hipSuccess) return fail(VITS_ERR_NOMEM, "contour: table alloc failed");
+    if (hipMemcpy(d, T.data(), sizeof(float) * CT_TAB, hipMemcpyHostToDevice) != hipSuccess) {
+      hipFree(d);
+      return fail(VITS_ERR_DEVICE, "contour: table upload failed");
+    }
+    it = g_ct_tabs.emplace(device, d).first;
+  }
+  *out = it->second;
+  return VITS_OK;
+}
+
+// bytes of scratch an item of `len` samples takes in a group (the strides of a group are those of its longest item); F_s <= 2 (F_a + 1)
+static size_t contour_item_bytes(long long len) {
+  const long long Fa = pt_frames_a(len), F = ct_frames(len), cap = 2 * (Fa + 1);
+  size_t n = (size_t)(F + 1) * 12 + (size_t)(cap + 2) * 8 + 64;
+  if (Fa) n += (size_t)(Fa + 2) * PT_NB * 8 + (size_t)cap * PT_NB * 4 + (size_t)cap * PT_N * 4 + (size_t)(cap - 1) * PT_H * 4;
+  return n;
+}
+
+// y[b][0 .. n_count) = the contoured item b, for B items on `stream`: x [B][x_bstride] float on the device, h_len their lengths on the
+// host; d_cum [B][cum_bstride], d_toklen [B] on the device.  y is float, or int16 (pcm: pcm16_kernel's conversion at pcm_scale).
+// Allocates its scratch and waits for the stream before it frees it: not capturable.  y is not x.
+// u_out / steps_out (both or neither; device): the stretch door -- u goes to u_out[b * u_bstride + j], the step tables to
+// steps_out[b * s_bstride + ..] (zeroed by the caller), and nothing is warped.
+static int contour_run(int device, hipStream_t stream, const float* x, long long x_bstride, const long long* h_len, int B, const ContourReq& q,
+                       const int* d_cum, long long cum_bstride, const int* d_toklen, int hop, void* y, bool pcm, float pcm_scale,
+                       long long y_bstride, long long n_count, float* u_out, long long u_bstride, long long* steps_out, long long s_bstride) {
+  if (B <= 0) return VITS_OK;
+  const DenoiseTab* D = nullptr;
+  TRY(denoise_get(device, PT_N, &D));
+  const float* d_T = nullptr;
+  TRY(contour_tab_get(device, &d_T));
+  std::vector<int> len32(B), vlen32(B);
+  for (int b = 0; b < B; ++b) {
+    if (h_len[b] < 0 || h_len[b] >= (1LL << 31)) return fail(VITS_ERR_ARG, "contour: length %lld of item %d", h_len[b], b);
+    len32[b] = (int)h_len[b];
+    vlen32[b] = (q.shift[b] && h_len[b] >= PT_M + 1) ? (int)h_len[b] : 0;
+  }
+  std::vector<std::pair<int, int>> groups;  // (first item, count): consecutive items whose scratch fits
+  size_t need = 0;
+  for (int b0 = 0; b0 < B;) {
+    long long mx = 0;
+    int c = 0;
+    while (b0 + c < B && c < 65535) {
+      const long long m2 = std::max(mx, h_len[b0 + c]);
+      if (contour_item_bytes(m2) * (size_t)(c + 1) > (size_t)VITS_PITCH_MAX_SCRATCH) break;
+      mx = m2;
+      ++c;
+    }
+    if (!c) return fail(VITS_ERR_UNSUPPORTED, "contour: an item of %lld samples needs %zu bytes of scratch (limit %lld)", h_len[b0],
+                        contour_item_bytes(h_len[b0]), (long long)VITS_PITCH_MAX_SCRATCH);
+    need = std::max(need, contour_item_bytes(mx) * (size_t)c);
+    groups.emplace_back(b0, c);
+    b0 += c;
+  }
+  HIP_TRY(hipSetDevice(device));
+  const size_t tok_bytes = (size_t)B * q.Tx * 4, head = (2 * (size_t)B * 4 + 2 * tok_bytes + 63) / 64 * 64;
+  char* scr = nullptr;
+  if (hipMalloc((void**)&scr, head + need) != hipSuccess) return fail(VITS_ERR_NOMEM, "contour: scratch alloc of %zu bytes failed", head + need);
+  int* d_len = reinterpret_cast<int*>(scr);
+  int* d_vlen = d_len + B;
+  int* d_P = d_vlen + B;
+  float* d_g = reinterpret_cast<float*>(d_P + (size_t)B * q.Tx);
+  hipError_t e = hipMemcpyAsync(d_len, len32.data(), sizeof(int) * B, hipMemcpyHostToDevice, stream);
+  if (e == hipSuccess) e = hipMemcpyAsync(d_vlen, vlen32.data(), sizeof(int) * B, hipMemcpyHostToDevice, stream);
+  if (e == hipSuccess) e = hipMemcpyAsync(d_P, q.P.data(), tok_bytes, hipMemcpyHostToDevice, stream);
+  if (e == hipSuccess) e = hipMemcpyAsync(d_g, q.g.data(), tok_bytes, hipMemcpyHostToDevice, stream);
+  for (size_t gi = 0; gi < groups.size() && e == hipSuccess; ++gi) {
+    const int b0 = groups[gi].first, c = groups[gi].second;
+    long long mx = 0, vmx = 0;
+    for (int b = 0; b < c; ++b) { mx = std::max(mx, h_len[b0 + b]); vmx = std::max(vmx, (long long)vlen32[b0 + b]); }
+    const long long F = ct_frames(mx), Fa = pt_frames_a(vmx), cap = 2 * (Fa + 1);
+    const long long t_bs = F + 1, s_bs = steps_out ? s_bstride : cap + 2;
+    const long long a_bs = (Fa + 2) * PT_NB, p_bs = cap * PT_NB, f_bs = cap * PT_N, u_bs = (cap - 1) * PT_H;
+    char* p = scr + head;
+    long long* d_inc = reinterpret_cast<long long*>(p); p += 8 * (size_t)c * t_bs;
+    long long* d_steps = steps_out ? steps_out + (long long)b0 * s_bstride : reinterpret_cast<long long*>(p);
+    p += 8 * (size_t)c * (cap + 2);
+    float* d_gbar = reinterpret_cast<float*>(p); p += 4 * (size_t)c * t_bs;
+    p += (8 - (p - scr) % 8) % 8;
+    const float* xg = x + (long long)b0 * x_bstride;
+    const int *lg = d_len + b0, *vg = d_vlen + b0;
+    hipLaunchKernelGGL(contour_tracks_kernel, dim3((unsigned)((F + 255) / 256), c), dim3(256), 0, stream, lg, d_cum + (long long)b0 * cum_bstride,
+                       cum_bstride, d_toklen + b0, (long long)hop, d_P + (size_t)b0 * q.Tx, d_g + (size_t)b0 * q.Tx, (long long)q.Tx, q.Tx, d_inc,
+                       d_gbar, t_bs);
+    float* d_u = nullptr;
+    if (Fa && s_bs >= cap + 2) {
+      float* d_mag = reinterpret_cast<float*>(p); p += sizeof(float) * (size_t)c * a_bs;
+      unsigned* d_th = reinterpret_cast<unsigned*>(p); p += sizeof(unsigned) * (size_t)c * a_bs;
+      unsigned* d_phi = reinterpret_cast<unsigned*>(p); p += sizeof(unsigned) * (size_t)c * p_bs;
+      p += (8 - (p - scr) % 8) % 8;  // (the frames are written as float2)
+      float* d_fr = reinterpret_cast<float*>(p); p += sizeof(float) * (size_t)c * f_bs;
+      d_u = reinterpret_cast<float*>(p);
+      hipLaunchKernelGGL(contour_steps_kernel, dim3(c), dim3(64), 0, stream, vg, d_inc, t_bs, d_steps, s_bs);
+      hipLaunchKernelGGL(contour_analysis_kernel, dim3((unsigned)((Fa + 2 + DN_FPB - 1) / DN_FPB), c), dim3(64 * DN_FPB), 0, stream, xg, x_bstride,
+                         x_bstride, vg, d_mag, d_th, a_bs);
+      hipLaunchKernelGGL(pitch_phase_kernel<true>, dim3(c), dim3(64 * PT_WAVES), 0, stream, d_mag, d_th, a_bs, vg, 1LL, 1, 1, d_steps, s_bs, d_phi, p_bs);
+      hipLaunchKernelGGL(pitch_synth_kernel<true>, dim3((unsigned)((cap + DN_FPB - 1) / DN_FPB), c), dim3(64 * DN_FPB), 0, stream, d_mag, a_bs, d_phi,
+                         p_bs, vg, 1LL, 1, 1, d_steps, s_bs, D->d_win, D->d_tw, d_fr, f_bs);
+      if (u_out)
+        hipLaunchKernelGGL(pitch_ola_kernel<true>, dim3((unsigned)((u_bstride + 255) / 256), c), dim3(256), 0, stream, d_fr, f_bs, vg, 1LL, 1, 1, d_steps,
+                           s_bs, D->d_env, u_out + (long long)b0 * u_bstride, u_bstride, u_bstride);
+      else
+        hipLaunchKernelGGL(pitch_ola_kernel<true>, dim3((unsigned)((u_bs + 255) / 256), c), dim3(256), 0, stream, d_fr, f_bs, vg, 1LL, 1, 1, d_steps, s_bs,
+                           D->d_env, d_u, u_bs, u_bs);
+    } else if (u_out) {
+      hipMemsetAsync(u_out + (long long)b0 * u_bstride, 0, sizeof(float) * (size_t)c * u_bstride, stream);
+    }
+    if (!u_out && n_count > 0) {
+      const dim3 grid((unsigned)((n_count + CT_TILE - 1) / CT_TILE), c);
+      if (pcm) {
+        int16_t* yg = static_cast<int16_t*>(y) + (long long)b0 * y_bstride;
+        if (d_u) hipLaunchKernelGGL(contour_warp_kernel<int16_t>, grid, dim3(CT_TILE), 0, stream, d_u, u_bs, d_steps, s_bs, d_gbar, t_bs, lg, vg, d_T, yg, y_bstride, n_count, pcm_scale);
+        hipLaunchKernelGGL(contour_gain_kernel<int16_t>, grid, dim3(256), 0, stream, xg, x_bstride, d_gbar, t_bs, lg, vg, yg, y_bstride, n_count, pcm_scale);
+      } else {
+        float* yg = static_cast<float*>(y) + (long long)b0 * y_bstride;
+        if (d_u) hipLaunchKernelGGL(contour_warp_kernel<float>, grid, dim3(CT_TILE), 0, stream, d_u, u_bs, d_steps, s_bs, d_gbar, t_bs, lg, vg, d_T, yg, y_bstride, n_count, 1.f);
+        hipLaunchKernelGGL(contour_gain_kernel<float>, grid, dim3(256), 0, stream, xg, x_bstride, d_gbar, t_bs, lg, vg, yg, y_bstride, n_count, 1.f);
+      }
+    }
+  }
+  if (e == hipSuccess) e = hipGetLastError();
+  const hipError_t e2 = hipStreamSynchronize(stream);
+  hipFree(scr);
+  if (e == hipSuccess) e = e2;
+  if (e != hipSuccess) return fail(VITS_ERR_DEVICE, "contour: %s", hipGetErrorString(e));
+  return VITS_OK;
+}
+
+// ---- the parity doors ---------------------------------------------------------------------------------------------------
+static int contour_op(int device, const float* x, const int64_t* lengths, int32_t B, int64_t N, const int32_t* cum, const int64_t* tok_lengths,
+                      int32_t Tx, int32_t hop, const float* token_semitones, const float* token_gain_db, float* y, float* u, int64_t* steps) {
+  const bool stretch = u != nullptr;
+  if ((!stretch && !y) || (stretch && !steps) || !cum || !tok_lengths || Tx <= 0 || hop <= 0) return fail(VITS_ERR_ARG, "contour: bad argument");
+  std::vector<int> len32;
+  TRY(op_items_check("contour", x, lengths, B, N, &len32, "N = "));
+  std::vector<int> tl32(B);
+  for (int b = 0; b < B; ++b) {
+    if (tok_lengths[b] < 0 || tok_lengths[b] > Tx) return fail(VITS_ERR_ARG, "contour: token length %lld of item %d outside [0, T_x = %d]", (long long)tok_lengths[b], b, Tx);
+    tl32[b] = (int)tok_lengths[b];
+    for (int t = 0; t < tl32[b]; ++t) {
+      const int32_t c0 = t ? cum[(size_t)b * Tx + t - 1] : 0, c1 = cum[(size_t)b * Tx + t];
+      if (c1 < c0) return fail(VITS_ERR_ARG, "contour: cum of item %d decreases at token %d (%d after %d)", b, t, c1, c0);
+    }
+  }
+  ContourReq q;
+  TRY(contour_plan(token_semitones, token_gain_db, 0.f, tok_lengths, B, Tx, &q));
+  const std::vector<long long> len64(lengths, lengths + B);
+  const long long Nu = (long long)PT_H * (2 * (N / PT_H + 2) - 1), Ns = 2 * (N / PT_H + 2) + 2;
+  OpDoor d("contour", device);
+  // every item's own samples only: what lies at and beyond lengths[b] never reaches the device
+  float* dx = d.out<float>((size_t)B * N, 0);
+  for (int b = 0; b < B && d.ok(); ++b)
+    if (lengths[b]) d.hip(hipMemcpy(dx + (size_t)b * N, x + (size_t)b * N, sizeof(float) * (size_t)lengths[b], hipMemcpyHostToDevice));
+  int* dc = d.up(cum, (size_t)B * Tx);
+  int* dt = d.up(tl32.data(), B);
+  float* dy = stretch ? d.out<float>((size_t)B * Nu) : d.out<float>((size_t)B * N);
+  long long* ds = stretch ? d.out<long long>((size_t)B * Ns, 0) : nullptr;
+  if (d.ok())
+    TRY(stretch ? contour_run(device, nullptr, dx, N, len64.data(), B, q, dc, Tx, dt, hop, nullptr, false, 1.f, 0, 0, dy, Nu, ds, Ns)
+                : contour_run(device, nullptr, dx, N, len64.data(), B, q, dc, Tx, dt, hop, dy, false, 1.f, N, N, nullptr, 0, nullptr, 0));
+  d.finish();
+  d.down(stretch ? u : y, dy, stretch ? (size_t)B * Nu : (size_t)B * N);
+  if (stretch) d.down(reinterpret_cast<long long*>(steps), ds, (size_t)B * Ns);
+  return d.rc();
+}
+
+int vits_op_contour(int device, const float* x, const int64_t* lengths, int32_t B, int64_t N, const int32_t* cum, const int64_t* tok_lengths,
+                    int32_t T_x, int32_t hop, const float* token_semitones, const float* token_gain_db, float* y) {
+  return contour_op(device, x, lengths, B, N, cum, tok_lengths, T_x, hop, token_semitones, token_gain_db, y, nullptr, nullptr);
+}
+int vits_op_contour_stretch(int device, const float* x, const int64_t* lengths, int32_t B, int64_t N, const int32_t* cum,
+                            const int64_t* tok_lengths, int32_t T_x, int32_t hop, const float* token_semitones, const float* token_gain_db,
+                            float* u, int64_t* steps) {
+  if (!u) return fail(VITS_ERR_ARG, "contour: bad argument");
+  return contour_op(device, x, lengths, B, N, cum, tok_lengths, T_x, hop, token_semitones, token_gain_db, nullptr, u, steps);
+}

@@ -136,6 +136,7 @@ static int persist_cfg() {
 #include "loudness.hip.h"
 #include "limit.hip.h"
 #include "pitch.hip.h"
+#include "contour.hip.h"
 #include "out_tail.hip.h"
 #include "marks.hip.h"
 

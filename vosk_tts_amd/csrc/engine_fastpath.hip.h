@@ -506,8 +506,8 @@ static int synth_fast(vits_model* m, const int64_t* ids, const int64_t* lengths,
     if (token_ends) for (int b = 0; b < B; ++b) memcpy(token_ends + (size_t)b * Tx, F->marks_h + (size_t)b * TxB, sizeof(int64_t) * Tx);  // (bucket columns dropped)
     return VITS_OK;
   };
-  if (q.pitch.on) {
-    // include/vits_pitch.h: the float, native-rate form of the graph as it is, then the tail (out_tail.hip.h) as launches behind it on
+  if (q.pitch.on || q.contour.on) {
+    // include/vits_pitch.h, vits_contour.h: the float, native-rate form of the graph as it is, then the tail (out_tail.hip.h) as launches behind it on
     // the same stream, in buffers of this call (the graph's own copy of the unshifted float audio to the host is not used)
     TRY(phase2_launch(F, Bk, solo, false, nullptr, nullptr, pr.per_item_noise));
     std::vector<long long> h_len(B);
@@ -517,7 +517,7 @@ static int synth_fast(vits_model* m, const int64_t* ids, const int64_t* lengths,
     const float* d_res = nullptr;
     long long So = 0;
     std::vector<float> res((size_t)B * 4);
-    const int rc = tail_run(bufs, Bk->s, st, Bk->out_d, (long long)TyB * hp.hop_length, Bk->s->len_y, hp.hop_length, h_len.data(), B, q, &d_out, &So, &d_res);
+    const int rc = tail_run(bufs, Bk->s, st, Bk->out_d, (long long)TyB * hp.hop_length, Bk->s->len_y, hp.hop_length, h_len.data(), B, F->s->cum, TxB, F->s->len_x, q, &d_out, &So, &d_res);
     if (rc != VITS_OK) { hipStreamSynchronize(st); return rc; }
     if (d_res) hipMemcpyAsync(res.data(), d_res, sizeof(float) * res.size(), hipMemcpyDeviceToHost, st);
     char* h_out = host_out();
@@ -590,7 +590,7 @@ static int synth_eager(vits_model* m, const int64_t* ids, const int64_t* lengths
   const void* d_src = nullptr;
   const float* d_res = nullptr;
   long long So = 0;  // samples per item as returned
-  TRY(tail_run([&](size_t bytes) { return hs.raw_alloc(bytes); }, s, s->stream, d_audio, S, s->len_y, hp.hop_length, h_len.data(), B, q, &d_src, &So, &d_res));
+  TRY(tail_run([&](size_t bytes) { return hs.raw_alloc(bytes); }, s, s->stream, d_audio, S, s->len_y, hp.hop_length, h_len.data(), B, s->cum, Tx, s->len_x, q, &d_src, &So, &d_res));
   if (d_res) hipMemcpyAsync(res.data(), d_res, sizeof(float) * res.size(), hipMemcpyDeviceToHost, s->stream);
   const size_t esz = q.pcm ? sizeof(int16_t) : sizeof(float);
   void* h_out = malloc(esz * (size_t)B * So);
@@ -612,7 +612,9 @@ static int synth_dispatch(vits_model* m, const int64_t* ids, const int64_t* leng
   if (!m->acoustic) return fail(VITS_ERR_UNSUPPORTED, "vocoder-only model: only the decoder stage is available");
   for (int b = 0; b < B; ++b) if (lengths[b] < 0 || lengths[b] > Tx) return fail(VITS_ERR_ARG, "length out of range");
   TailReq q;  // (out_tail.hip.h: the rate, the loudness target, the limiter and the shift, checked before anything is queued)
-  TRY(tail_req(m, tail_fields_vits(opts), sample_rate, pcm, pcm_scale, &q));
+  const TailFields tf = tail_fields_vits(opts);
+  TRY(tail_req(m, tf, sample_rate, pcm, pcm_scale, &q));
+  TRY(tail_contour_req(m, tf, lengths, B, Tx, &q));
   static const bool env_off = getenv("VITS_NO_FASTPATH") != nullptr;
   if (m->hp.bert_dim > 0 && (!opts || !opts->bert)) return fail(VITS_ERR_ARG, "this voice is BERT-conditioned: the bert feed [B,%d,T_x] is required", m->hp.bert_dim);
   if (m->hp.bert_dim == 0 && opts && opts->bert) return fail(VITS_ERR_ARG, "the bert feed was given but this voice has no BERT projection (hparams.bert_dim == 0)");

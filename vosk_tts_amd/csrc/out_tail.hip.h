@@ -1,14 +1,14 @@
 // out_tail.hip.h -- the output tail: what a synthesize call asks of the stages behind the decoder (TailReq, built by tail_req from the
-// plain fields behind the option flags), and the one runner of the chain  pitch -> resample -> normalise / limit -> int16  on the device
-// (tail_run).  The kernels and their launches are those of resample / loudness / limit / pitch.hip.h; this file only orders them.
-// Part of the ONE translation unit engine.hip (included there, behind limit.hip.h and pitch.hip.h; not a standalone header).
+// plain fields behind the option flags), and the one runner of the chain  pitch / contour -> resample -> normalise / limit -> int16  on the device
+// (tail_run).  The kernels and their launches are those of resample / loudness / limit / pitch / contour.hip.h; this file only orders them.
+// Part of the ONE translation unit engine.hip (included there, behind limit.hip.h, pitch.hip.h and contour.hip.h; not a standalone header).
 #pragma once
 
 // ---- the request ----------------------------------------------------------------------------------------------------------
 // The flag bits and the name of an API family: the two families number the same four flags differently.
-struct TailFamily { const char* name; uint32_t loudness, limit, pitch, formant; };
-static const TailFamily TAIL_VITS = {"VITS", VITS_FLAG_LOUDNESS, VITS_FLAG_LIMIT, VITS_FLAG_PITCH, VITS_FLAG_PITCH_FORMANT};
-static const TailFamily TAIL_STTS = {"STTS", STTS_FLAG_LOUDNESS, STTS_FLAG_LIMIT, STTS_FLAG_PITCH, STTS_FLAG_PITCH_FORMANT};
+struct TailFamily { const char* name; uint32_t loudness, limit, pitch, formant, contour; };
+static const TailFamily TAIL_VITS = {"VITS", VITS_FLAG_LOUDNESS, VITS_FLAG_LIMIT, VITS_FLAG_PITCH, VITS_FLAG_PITCH_FORMANT, VITS_FLAG_CONTOUR};
+static const TailFamily TAIL_STTS = {"STTS", STTS_FLAG_LOUDNESS, STTS_FLAG_LIMIT, STTS_FLAG_PITCH, STTS_FLAG_PITCH_FORMANT, STTS_FLAG_CONTOUR};
 
 // The values behind the flags of a call, flat.  A group is meaningful only where its `on` is set (`formant` is the bare flag bit).
 struct TailFields {
@@ -23,11 +23,13 @@ struct TailFields {
   float* out_reduction = nullptr;
   bool pitch_on = false, formant = false;
   float semitones = 0.f;
+  bool contour_on = false;
+  const vits_contour* contour = nullptr;
 };
 
 // The only two places that cast down the `base` chain of the extended option structs: a struct's own fields are read under its flag
 // alone, so a caller who sets no flag may pass the plain struct (include/vits_loudness.h, vits_pitch.h, vits_limit.h).
-template <typename Pitch, typename Limit, typename Loud, typename Opts>
+template <typename Pitch, typename Limit, typename Contour, typename Loud, typename Opts>
 static TailFields tail_fields(const TailFamily& fam, const Opts* opts, const Loud* lo) {
   TailFields f;
   f.family = fam.name;
@@ -44,16 +46,21 @@ static TailFields tail_fields(const TailFamily& fam, const Opts* opts, const Lou
     f.lim_release_ms = mo->limit_release_ms; f.lim_gain = mo->limit_gain; f.out_reduction = mo->out_reduction;
   }
   if (f.pitch_on) f.semitones = reinterpret_cast<const Pitch*>(opts)->pitch_semitones;
+  f.contour_on = (fl & fam.contour) != 0;
+  if (f.contour_on) f.contour = reinterpret_cast<const Contour*>(opts)->contour;
   return f;
 }
 static TailFields tail_fields_vits(const vits_synth_opts* opts) {  // (the loudness fields are the plain struct's own)
-  static_assert(offsetof(vits_synth_opts_limit, base) == 0 && offsetof(vits_synth_opts_pitch, base) == 0, "the extended options begin with the plain ones");
-  return tail_fields<vits_synth_opts_pitch, vits_synth_opts_limit>(TAIL_VITS, opts, opts);
+  static_assert(offsetof(vits_synth_opts_limit, base) == 0 && offsetof(vits_synth_opts_pitch, base) == 0 && offsetof(vits_synth_opts_prosody, base) == 0 &&
+                    offsetof(vits_synth_opts_contour, base) == 0,
+                "the extended options begin with the plain ones");
+  return tail_fields<vits_synth_opts_pitch, vits_synth_opts_limit, vits_synth_opts_contour>(TAIL_VITS, opts, opts);
 }
 static TailFields tail_fields_stts(const stts_synth_opts* opts) {
-  static_assert(offsetof(stts_synth_opts_limit, base) == 0 && offsetof(stts_synth_opts_pitch, base) == 0 && offsetof(stts_synth_opts_loudness, base) == 0,
+  static_assert(offsetof(stts_synth_opts_limit, base) == 0 && offsetof(stts_synth_opts_pitch, base) == 0 && offsetof(stts_synth_opts_loudness, base) == 0 &&
+                    offsetof(stts_synth_opts_contour, base) == 0,
                 "the extended options begin with the plain ones");
-  return tail_fields<stts_synth_opts_pitch, stts_synth_opts_limit>(TAIL_STTS, opts, reinterpret_cast<const stts_synth_opts_loudness*>(opts));
+  return tail_fields<stts_synth_opts_pitch, stts_synth_opts_limit, stts_synth_opts_contour>(TAIL_STTS, opts, reinterpret_cast<const stts_synth_opts_loudness*>(opts));
 }
 
 // the formant bit modifies a pitch request: alone it is refused, before any work is queued
@@ -72,6 +79,8 @@ static int tail_refuse_stream(uint32_t flags, const TailFamily& fam) {
   TRY(tail_formant_check((flags & fam.formant) != 0, (flags & fam.pitch) != 0, fam.name));
   if (flags & fam.pitch)
     return fail(VITS_ERR_UNSUPPORTED, "%s_FLAG_PITCH on a stream: the phase recursion needs the frames before a chunk, and its state is not carried across chunks", fam.name);
+  if (flags & fam.contour)
+    return fail(VITS_ERR_UNSUPPORTED, "%s_FLAG_CONTOUR on a stream: the position recurrence and the phase recursion need the whole utterance before the first chunk", fam.name);
   return VITS_OK;
 }
 
@@ -79,6 +88,7 @@ static int tail_refuse_stream(uint32_t flags, const TailFamily& fam) {
 // (resample_get: uploaded on first use, before any capture); rate 0: the vocoder's own.
 struct TailReq {
   PitchReq pitch;
+  ContourReq contour;  // (include/vits_contour.h; where it is on, the call's own shift is part of its tokens and `pitch` is off)
   const ResampleTab* T = nullptr;
   int rate = 0;
   NormReq norm;
@@ -104,18 +114,40 @@ static int tail_req(const vits_model* vocoder, const TailFields& f, int32_t samp
   return pitch_req(vocoder, f.semitones, f.formant, &out->pitch);
 }
 
+// The contour of a call (include/vits_contour.h), behind tail_req, which knows nothing of the tokens: refused or planned before anything is
+// synthesised.  A contour whose every token is neutral leaves the request as tail_req made it (case (a): the call as it was, the
+// pitch stage included); otherwise VITS_FLAG_PITCH's semitones are added to every token and the pitch stage itself does not run.
+static int tail_contour_req(const vits_model* vocoder, const TailFields& f, const int64_t* tok_lengths, int B, int Tx, TailReq* out) {
+  if (!f.contour_on) return VITS_OK;
+  if (!f.contour) return fail(VITS_ERR_ARG, "%s_FLAG_CONTOUR with a NULL contour pointer (include/vits_contour.h)", f.family);
+  if (f.formant)
+    return fail(VITS_ERR_UNSUPPORTED, "%s_FLAG_CONTOUR with %s_FLAG_PITCH_FORMANT: the envelope pre-warp assumes one ratio per call (include/vits_contour.h)",
+                f.family, f.family);
+  if (!vocoder) return fail(VITS_ERR_ARG, "no vocoder attached");
+  TRY(contour_plan(f.contour->token_semitones, f.contour->token_gain_db, 0.f, tok_lengths, B, Tx, &out->contour));
+  if (!out->contour.on) return VITS_OK;
+  if (f.pitch_on) TRY(contour_plan(f.contour->token_semitones, f.contour->token_gain_db, f.semitones, tok_lengths, B, Tx, &out->contour));
+  out->contour.on = true;
+  out->pitch = PitchReq();
+  if (vocoder->hp.hop_length % PT_H)
+    return fail(VITS_ERR_UNSUPPORTED, "contour: the vocoder's hop_length %d is not a multiple of the pitch stage's hop %d", vocoder->hp.hop_length, PT_H);
+  return VITS_OK;
+}
+
 // ---- the runner -----------------------------------------------------------------------------------------------------------
 // device buffers owned by one call (the allocator of a tail_run that has no arena to draw from), freed with it
 using TailBufs = DevBufs;  // op_door.hip.h
 
 // The tail of a vits_synthesize* call, as launches on `stream` from the float native-rate waveform x [B, S] on the device (item b is
-// len_y[b] * hop samples, h_len[b] on the host): pitch, resample, normalise and / or limit; the last stage that runs converts to int16
+// len_y[b] * hop samples, h_len[b] on the host; its tokens' inclusive frame counts cum [B][cum_bstride] and their number tok_len [B] on the
+// device, read by a contoured call only): pitch or contour, resample, normalise and / or limit; the last stage that runs converts to int16
 // where q.pcm.  *d_out is [B, *So] of float or int16 (x itself where nothing is asked), *d_res the [B, 4] result rows of the last
 // stage on the device (null without one), for the caller's own copies to the host.  alloc(bytes) -> void* is the caller's: buffers
 // that outlive the launches queued here.  s: the session the launches are counted under (ProfScope).
 template <typename Alloc>
 static int tail_run(Alloc&& alloc, vits_session* s, hipStream_t stream, const float* x, long long S, const int* len_y, int hop, const long long* h_len,
-                    int B, const TailReq& q, const void** d_out, long long* So_out, const float** d_res) {
+                    int B, const int* d_cum, long long cum_bstride, const int* d_toklen, const TailReq& q, const void** d_out, long long* So_out,
+                    const float** d_res) {
   const ResampleTab* T = q.T;
   const long long So = T ? T->P.n_out(S) : S;
   const size_t esz = q.pcm ? sizeof(int16_t) : sizeof(float);
@@ -126,6 +158,14 @@ static int tail_run(Alloc&& alloc, vits_session* s, hipStream_t stream, const fl
     if (!d_p) return fail(VITS_ERR_NOMEM, "device alloc failed");
     TRY(pitch_run(s->m->device, stream, x, S, S, len_y, hop, h_len, B, q.pitch.P, q.pitch.Q, q.pitch.formant, d_p, S, S, nullptr, 0));
     x = d_p;
+  }
+  if (q.contour.on) {  // in the pitch stage's place; the last stage of a call that neither resamples nor normalises
+    const bool cp = q.pcm && !T && !q.norm.on();
+    void* d_c = alloc((cp ? sizeof(int16_t) : sizeof(float)) * (size_t)B * S);
+    if (!d_c) return fail(VITS_ERR_NOMEM, "device alloc failed");
+    TRY(contour_run(s->m->device, stream, x, S, h_len, B, q.contour, d_cum, cum_bstride, d_toklen, hop, d_c, cp, q.pcm_scale, S, S, nullptr, 0, nullptr, 0));
+    if (cp) { *d_out = d_c; return VITS_OK; }
+    x = static_cast<const float*>(d_c);
   }
   *d_out = x;
   if (q.norm.on()) {  // the float waveform at the rate it is returned at, measured, then the gain (and the conversion)

@@ -222,17 +222,35 @@ __global__ __launch_bounds__(64 * DN_FPB) void pitch_formant_kernel(const float*
   }
 }
 
+// The step table of include/vits_contour.h (TAB instantiations of the three kernels below): row b of `steps` is F_s, a_0 .. a_{F_s} at
+// stride s_bstride.  What a kernel takes from it is clamped to what the item's length allows -- F_s <= 2 (F_a + 1), i_t <= F_a -- so no
+// loop bound and no row address rests on the table's contents alone.  The plain instantiations do not read it.
+#define PT_ONE (1LL << 24)
+__device__ __forceinline__ long long pt_tab_fs(const long long* __restrict__ row, long long Fa) {
+  const long long fs = row[0], cap = 2 * (Fa + 1);
+  return Fa ? (fs < 0 ? 0 : (fs > cap ? cap : fs)) : 0;
+}
+__device__ __forceinline__ int pt_tab_i(long long a, long long Fa) {
+  const long long i = a >> 24;
+  return (int)(i < 0 ? 0 : (i > Fa ? Fa : i));
+}
+
 // One workgroup per item (blockIdx.x), thread k = bin k.  phi: [B][p_bstride], row t at t * PT_NB.
+template <bool TAB>
 __global__ __launch_bounds__(64 * PT_WAVES) void pitch_phase_kernel(const float* __restrict__ mag, const unsigned* __restrict__ th,
                                                                     long long a_bstride, const int* __restrict__ len_frames,
-                                                                    long long len_mul, int P, int Q, unsigned* __restrict__ phi,
-                                                                    long long p_bstride) {
+                                                                    long long len_mul, int P, int Q, const long long* __restrict__ steps,
+                                                                    long long s_bstride, unsigned* __restrict__ phi, long long p_bstride) {
   __shared__ float s_m[2][PT_NB + 4];  // m[k] at k + 2; -1 either side
   __shared__ unsigned s_adv[2][PT_NB], s_th[2][PT_NB];
   __shared__ unsigned long long s_pk[2][PT_WAVES];
   const int b = blockIdx.x, k = threadIdx.x, wv = k >> 6, lane = k & 63;
   const long long len = len_frames ? len_frames[b] * len_mul : len_mul;
-  const long long Fs = pt_frames_s(len, P, Q);
+  const long long Fa = pt_frames_a(len);
+  const long long* ab = TAB ? steps + (long long)b * s_bstride + 1 : nullptr;  // a_0 ..
+  long long Fs;
+  if constexpr (TAB) Fs = pt_tab_fs(ab - 1, Fa);
+  else Fs = pt_frames_s(len, P, Q);
   if (Fs == 0) return;
   const bool act = k < PT_NB;
   const int kc = act ? k : 0;  // (the idle lanes of the last wave form valid addresses and touch nothing)
@@ -255,7 +273,8 @@ __global__ __launch_bounds__(64 * PT_WAVES) void pitch_phase_kernel(const float*
   int q_r[PT_AHEAD];
   const int q_div = Q / P, q_rem = Q % P;
   long long n_t = 1;                    // the step the next issue is for
-  int n_i = q_div, n_r = q_rem, n_j = 0;  // its i_t, t Q mod P and i_{t-1}
+  int n_i = q_div, n_r = q_rem, n_j = 0;  // its i_t, t Q mod P (TAB: a_t mod 2^24) and i_{t-1}
+  if constexpr (TAB) { n_i = pt_tab_i(ab[1], Fa); n_r = (int)(ab[1] & (PT_ONE - 1)); }
   auto issue = [&](int d) {
     q_r[d] = n_r;
     q_a[d] = mb[(long long)n_i * PT_NB]; q_b[d] = mb[(long long)(n_i + 1) * PT_NB];
@@ -263,8 +282,13 @@ __global__ __launch_bounds__(64 * PT_WAVES) void pitch_phase_kernel(const float*
     if (n_t + 1 < Fs) {  // (uniform)
       ++n_t;
       n_j = n_i;
-      n_i += q_div; n_r += q_rem;
-      if (n_r >= P) { n_r -= P; ++n_i; }
+      if constexpr (TAB) {
+        const long long a = ab[n_t];
+        n_i = pt_tab_i(a, Fa); n_r = (int)(a & (PT_ONE - 1));
+      } else {
+        n_i += q_div; n_r += q_rem;
+        if (n_r >= P) { n_r -= P; ++n_i; }
+      }
     }
   };
 #pragma unroll
@@ -279,7 +303,9 @@ __global__ __launch_bounds__(64 * PT_WAVES) void pitch_phase_kernel(const float*
     const int c_r = q_r[d];
     issue(d);
     const int pp = (int)(tau & 1);
-    const float alpha = __fdiv_rn((float)c_r, (float)P);
+    float alpha;
+    if constexpr (TAB) alpha = (float)c_r * 5.9604644775390625e-08f;  // 2^-24: exact
+    else alpha = __fdiv_rn((float)c_r, (float)P);
     const float m = pt_interp(c_a, c_b, alpha);
     const unsigned adv = ph + c_tj1 - c_tj;
     if (act) { s_m[pp][k + 2] = m; s_adv[pp][k] = adv; s_th[pp][k] = c_ti; }
@@ -312,22 +338,35 @@ __global__ __launch_bounds__(64 * PT_WAVES) void pitch_phase_kernel(const float*
 }
 
 // Steps [0, F_s) of every item: wave w of workgroup blockIdx.x owns step blockIdx.x * DN_FPB + w.  fr: [B][fr_bstride], frame t at t * n.
+template <bool TAB>
 __global__ __launch_bounds__(64 * DN_FPB) void pitch_synth_kernel(const float* __restrict__ mag, long long a_bstride,
                                                                   const unsigned* __restrict__ phi, long long p_bstride,
                                                                   const int* __restrict__ len_frames, long long len_mul, int P, int Q,
+                                                                  const long long* __restrict__ steps, long long s_bstride,
                                                                   const float* __restrict__ win, const float2* __restrict__ tw,
                                                                   float* __restrict__ fr, long long fr_bstride) {
   __shared__ float lds[DN_FPB][4][DN_PLANE];
   const int wv = threadIdx.x >> 6, t = threadIdx.x & 63;
   const int b = blockIdx.y;
   const long long len = len_frames ? len_frames[b] * len_mul : len_mul;
-  const long long Fs = pt_frames_s(len, P, Q);
+  long long Fs;
+  if constexpr (TAB) Fs = pt_tab_fs(steps + (long long)b * s_bstride, pt_frames_a(len));
+  else Fs = pt_frames_s(len, P, Q);
   if ((long long)blockIdx.x * DN_FPB >= Fs) return;  // uniform over the workgroup
   const long long tau = (long long)blockIdx.x * DN_FPB + wv;
   const bool valid = tau < Fs;
   float *ar = lds[wv][0], *ai = lds[wv][1], *br = lds[wv][2], *bi = lds[wv][3];
-  const long long tq = tau * Q, i = tq / P;
-  const float alpha = __fdiv_rn((float)(int)(tq - i * P), (float)P);
+  long long i;
+  float alpha;
+  if constexpr (TAB) {
+    const long long a = valid ? steps[(long long)b * s_bstride + 1 + tau] : 0;
+    i = pt_tab_i(a, pt_frames_a(len));
+    alpha = (float)(int)(a & (PT_ONE - 1)) * 5.9604644775390625e-08f;
+  } else {
+    const long long tq = tau * Q;
+    i = tq / P;
+    alpha = __fdiv_rn((float)(int)(tq - i * P), (float)P);
+  }
   const float* m0 = mag + (long long)b * a_bstride + i * PT_NB;
   const unsigned* pr = phi + (long long)b * p_bstride + tau * PT_NB;
   for (int k = t; k <= (PT_M >> 1); k += 64) {
@@ -363,14 +402,18 @@ __global__ __launch_bounds__(64 * DN_FPB) void pitch_synth_kernel(const float* _
 }
 
 // u[b][j], j < n_count: the overlap-add of the item's F_s frames, exactly 0 at and beyond N_u = H (F_s - 1).
+template <bool TAB>
 __global__ __launch_bounds__(256) void pitch_ola_kernel(const float* __restrict__ fr, long long fr_bstride, const int* __restrict__ len_frames,
-                                                        long long len_mul, int P, int Q, const float* __restrict__ inv_env,
+                                                        long long len_mul, int P, int Q, const long long* __restrict__ steps,
+                                                        long long s_bstride, const float* __restrict__ inv_env,
                                                         float* __restrict__ u, long long u_bstride, long long n_count) {
   const int b = blockIdx.y;
   const long long j = (long long)blockIdx.x * 256 + threadIdx.x;
   if (j >= n_count) return;
   const long long len = len_frames ? len_frames[b] * len_mul : len_mul;
-  const long long Fs = pt_frames_s(len, P, Q);
+  long long Fs;
+  if constexpr (TAB) Fs = pt_tab_fs(steps + (long long)b * s_bstride, pt_frames_a(len));
+  else Fs = pt_frames_s(len, P, Q);
   float v = 0.f;
   if (j < PT_H * (Fs - 1)) {
     const long long p = j + PT_M, fl = p / PT_H;  // fl in [2, F_s]
@@ -523,15 +566,16 @@ static int pitch_run(int device, hipStream_t stream, const float* x, long long x
       if (formant)
         hipLaunchKernelGGL(pitch_formant_kernel<false>, dim3((unsigned)((Fa + 2 + DN_FPB - 1) / DN_FPB), c), dim3(64 * DN_FPB), 0, stream, xg,
                            x_bstride, x_n, d_mag, a_bs, lg, len_mul, P, Q, d_magf);
-      hipLaunchKernelGGL(pitch_phase_kernel, dim3(c), dim3(64 * PT_WAVES), 0, stream, d_mag, d_th, a_bs, lg, len_mul, P, Q, d_phi, p_bs);
-      hipLaunchKernelGGL(pitch_synth_kernel, dim3((unsigned)((Fs + DN_FPB - 1) / DN_FPB), c), dim3(64 * DN_FPB), 0, stream, d_magf, a_bs, d_phi,
-                         p_bs, lg, len_mul, P, Q, D->d_win, D->d_tw, d_fr, f_bs);
+      hipLaunchKernelGGL(pitch_phase_kernel<false>, dim3(c), dim3(64 * PT_WAVES), 0, stream, d_mag, d_th, a_bs, lg, len_mul, P, Q,
+                         (const long long*)nullptr, 0LL, d_phi, p_bs);
+      hipLaunchKernelGGL(pitch_synth_kernel<false>, dim3((unsigned)((Fs + DN_FPB - 1) / DN_FPB), c), dim3(64 * DN_FPB), 0, stream, d_magf, a_bs, d_phi,
+                         p_bs, lg, len_mul, P, Q, (const long long*)nullptr, 0LL, D->d_win, D->d_tw, d_fr, f_bs);
       if (u_out) {
-        hipLaunchKernelGGL(pitch_ola_kernel, dim3((unsigned)((u_bstride + 255) / 256), c), dim3(256), 0, stream, d_fr, f_bs, lg, len_mul, P, Q,
-                           D->d_env, u_out + (long long)b0 * u_bstride, u_bstride, u_bstride);
+        hipLaunchKernelGGL(pitch_ola_kernel<false>, dim3((unsigned)((u_bstride + 255) / 256), c), dim3(256), 0, stream, d_fr, f_bs, lg, len_mul, P, Q,
+                           (const long long*)nullptr, 0LL, D->d_env, u_out + (long long)b0 * u_bstride, u_bstride, u_bstride);
       } else {
-        hipLaunchKernelGGL(pitch_ola_kernel, dim3((unsigned)((u_bs + 255) / 256), c), dim3(256), 0, stream, d_fr, f_bs, lg, len_mul, P, Q, D->d_env,
-                           d_u, u_bs, u_bs);
+        hipLaunchKernelGGL(pitch_ola_kernel<false>, dim3((unsigned)((u_bs + 255) / 256), c), dim3(256), 0, stream, d_fr, f_bs, lg, len_mul, P, Q,
+                           (const long long*)nullptr, 0LL, D->d_env, d_u, u_bs, u_bs);
         hipLaunchKernelGGL(pitch_geom_kernel, dim3((unsigned)((c + 63) / 64)), dim3(64), 0, stream, lg, len_mul, c, P, Q, d_nu, d_crop);
         resample_launch_crop(stream, *R, d_u, u_bs, u_bs, d_nu, PT_H, d_crop, c, y + (long long)b0 * y_bstride, y_bstride, n_count);
       }

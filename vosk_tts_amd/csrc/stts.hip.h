@@ -816,7 +816,13 @@ static int stts_denoise_arg(stts_model* m, const stts_synth_opts* opts, SttsDeno
 struct SttsMarks {
   int64_t* token_ends = nullptr;  // [B, T_x]
   long long L = 1, M = 1;
+  int* cum_out = nullptr;  // [B, T_x] or null: the inclusive frame counts themselves, for a contoured call (include/vits_contour.h)
 };
+static void stts_marks_fill(const SttsMarks* mk, const int* cum, long long len, int Tx, int hop, size_t row) {
+  if (!mk) return;
+  if (mk->token_ends) marks_fill_host(cum, len, Tx, hop, mk->L, mk->M, mk->token_ends + row * Tx);
+  if (mk->cum_out) memcpy(mk->cum_out + row * Tx, cum, sizeof(int) * (size_t)Tx);
+}
 static int stts_hop(const stts_model* m) { return m->vocoder ? m->vocoder->hp.hop_length : m->hp.hop_length; }
 // the marks argument of an entry point: rate 0 / the voice's own = native time axis; another rate only fixes L / M (host arithmetic)
 static int stts_marks_arg(const stts_model* m, int64_t* token_ends, int32_t sample_rate, SttsMarks* mk, int* rate_out) {
@@ -878,7 +884,7 @@ static int stts_synth_fast(stts_model* m, const int64_t* ids, int32_t Tx, const 
   int ylen = 0;
   for (int j = 0; j < TxB; ++j) { if (j < Tx) ylen += dur[j]; h_cum[j] = ylen; }  // only the utterance's own tokens count
   if (ylen > (1 << 18)) return fail(VITS_ERR_ARG, "T_y unreasonably large");  // (also keeps every per-item [C <= 2048, T] tensor below the 2 GiB the conv kernels' 32-bit offsets address)
-  if (mk) marks_fill_host(h_cum, Tx, Tx, stts_hop(m), mk->L, mk->M, mk->token_ends);
+  stts_marks_fill(mk, h_cum, Tx, Tx, stts_hop(m), 0);
   const int T4 = (ylen + 3) / 4 * 4;  // fix_len_compatibility (utils/model.py:14-20): where the exact-size run's tensors end
   const int TB = (T4 + 31) / 32 * 32;
   SttsDev* hv = reinterpret_cast<SttsDev*>(F->io_h + F->o_dev);
@@ -966,7 +972,7 @@ static int stts_synthesize_impl(stts_model* m, const int64_t* ids, int32_t Tx, c
   const int T = (int)((ylen + 3) / 4 * 4);  // fix_len_compatibility (utils/model.py:14-20)
   std::vector<int> cum(Tx);
   for (int j = 0, a = 0; j < Tx; ++j) { a += dur[j]; cum[j] = a; }
-  if (mk) marks_fill_host(cum.data(), Tx, Tx, stts_hop(m), mk->L, mk->M, mk->token_ends);
+  stts_marks_fill(mk, cum.data(), Tx, Tx, stts_hop(m), 0);
   // ---- flow-matching decoder
   TRY(stts_arena(s, stts_est_bytes(hp, nb, T, n)));
   int* d_cum = call.up(cum.data(), Tx);
@@ -1048,8 +1054,25 @@ static int stts_synthesize_impl(stts_model* m, const int64_t* ids, int32_t Tx, c
 // The output tail of a multistream call (out_tail.hip.h) on its finished audio [B, *S] (library-owned, items of lengths[b] samples), in
 // the order of tail_run: shifted in place at the native rate, replaced by its copy at q.rate, normalised and / or limited in place.
 // (It crosses the host through the parity doors' kernels; running it on the device behind the vocoder would be a speed change of its own.)
-static int stts_tail_host(stts_model* m, const TailReq& q, int B, float** audio, int64_t* S, int64_t* lengths) {
+// cum / tok_lengths / Tx: the tokens' inclusive frame counts on the host, read by a contoured call only.
+static int stts_tail_host(stts_model* m, const TailReq& q, int B, float** audio, int64_t* S, int64_t* lengths, const int* cum,
+                          const int64_t* tok_lengths, int Tx) {
   const int device = m->base.device;
+  if (q.contour.on && *S > 0) {  // (the kernels of vits_op_contour, from the tokens as contour_plan left them)
+    std::vector<float> y((size_t)B * *S);
+    const std::vector<long long> len64(lengths, lengths + B);
+    std::vector<int> tl32(tok_lengths, tok_lengths + B);
+    OpDoor d("contour", device);
+    float* dx = d.up(*audio, (size_t)B * *S);
+    int* dc = d.up(cum, (size_t)B * Tx);
+    int* dt = d.up(tl32.data(), B);
+    float* dy = d.out<float>((size_t)B * *S);
+    if (d.ok()) TRY(contour_run(device, nullptr, dx, *S, len64.data(), B, q.contour, dc, Tx, dt, stts_hop(m), dy, false, 1.f, *S, *S, nullptr, 0, nullptr, 0));
+    d.finish();
+    d.down(y.data(), dy, y.size());
+    if (!d.ok()) return d.rc();
+    memcpy(*audio, y.data(), sizeof(float) * y.size());
+  }
   if (q.pitch.on && *S > 0) {
     std::vector<float> y((size_t)B * *S);
     TRY(pitch_op(device, *audio, lengths, B, *S, q.pitch.semitones, y.data(), PT_DOOR_SHIFT, q.pitch.formant));
@@ -1090,11 +1113,19 @@ static int stts_synthesize_tail(stts_model* m, const int64_t* ids, int32_t Tx, c
                                 const stts_synth_opts* opts, int rate, float** out_audio, int64_t* out_samples, float** out_mel, int64_t* out_frames,
                                 const SttsMarks* mk) {
   TailReq q;
-  if (out_audio) TRY(tail_req(m->vocoder, tail_fields_stts(opts), rate, false, 1.f, &q));
+  const int64_t tl = Tx;
+  if (out_audio) {
+    const TailFields tf = tail_fields_stts(opts);
+    TRY(tail_req(m->vocoder, tf, rate, false, 1.f, &q));
+    if (Tx > 0) TRY(tail_contour_req(m->vocoder, tf, &tl, 1, Tx, &q));
+  }
+  std::vector<int> cum(q.contour.on ? Tx : 0);
+  SttsMarks mc = mk ? *mk : SttsMarks();
+  if (q.contour.on) { mc.cum_out = cum.data(); mk = &mc; }
   TRY(stts_synthesize_impl(m, ids, Tx, scales, sid, bert, pde, opts, out_audio, out_samples, out_mel, out_frames, mk));
   if (!out_audio) return VITS_OK;
   int64_t len = *out_samples;
-  const int rc = stts_tail_host(m, q, 1, out_audio, out_samples, &len);
+  const int rc = stts_tail_host(m, q, 1, out_audio, out_samples, &len, cum.data(), &tl, Tx);
   if (rc != VITS_OK) { free(*out_audio); *out_audio = nullptr; if (out_mel) { free(*out_mel); *out_mel = nullptr; } }
   return rc;
 }
@@ -1184,7 +1215,7 @@ static int stts_synthesize_batch_impl(stts_model* m, const int64_t* ids, const i
     l2[b] = l2[B + b] = a; lT[b] = lT[B + b] = Tb;
     if (Tb > T) T = Tb;
     if (a > Tm) Tm = a;
-    if (mk) marks_fill_host(cum.data() + (size_t)b * Tx, lengths[b], Tx, stts_hop(m), mk->L, mk->M, mk->token_ends + (size_t)b * Tx);
+    stts_marks_fill(mk, cum.data() + (size_t)b * Tx, lengths[b], Tx, stts_hop(m), b);
   }
   // ---- flow matching over all items (and their CFG twins) at once
   TRY(stts_arena(s, stts_est_bytes(hp, nb, T, n)));
@@ -1263,9 +1294,18 @@ static int stts_synthesize_batch_tail(stts_model* m, const int64_t* ids, const i
                                       const int64_t* sid, const float* bert, const float* pde, const stts_synth_opts* opts, int rate,
                                       float** out_audio, int64_t* out_samples, int64_t* out_lengths, const SttsMarks* mk) {
   TailReq q;
-  TRY(tail_req(m->vocoder, tail_fields_stts(opts), rate, false, 1.f, &q));
+  const TailFields tf = tail_fields_stts(opts);
+  TRY(tail_req(m->vocoder, tf, rate, false, 1.f, &q));
+  if (lengths && B > 0 && Tx > 0) {
+    bool lens_ok = true;  // (a bad length is the call's own refusal, below)
+    for (int b = 0; b < B; ++b) if (lengths[b] < 0 || lengths[b] > Tx) lens_ok = false;
+    if (lens_ok) TRY(tail_contour_req(m->vocoder, tf, lengths, B, Tx, &q));
+  }
+  std::vector<int> cum(q.contour.on ? (size_t)B * Tx : 0);
+  SttsMarks mc = mk ? *mk : SttsMarks();
+  if (q.contour.on) { mc.cum_out = cum.data(); mk = &mc; }
   TRY(stts_synthesize_batch_impl(m, ids, lengths, B, Tx, scales, sid, bert, pde, opts, out_audio, out_samples, out_lengths, mk));
-  const int rc = stts_tail_host(m, q, B, out_audio, out_samples, out_lengths);
+  const int rc = stts_tail_host(m, q, B, out_audio, out_samples, out_lengths, cum.data(), lengths, Tx);
   if (rc != VITS_OK) { free(*out_audio); *out_audio = nullptr; }
   return rc;
 }

@@ -107,6 +107,7 @@ class SpeechMarks:
         self.token_ends = np.asarray(token_ends, np.int64).reshape(-1)
         self.phonemes = list(phonemes)
         self.words = list(words)
+        self.named = {}  # {mark name: sample} of an SSML document's <mark> elements (Synth.synth_ssml)
 
     def seconds(self):
         """the same two lists with the offsets in seconds"""

@@ -71,6 +71,35 @@ def token_controls(layout, word_rates=None, pauses=None, native_rate=22050, hop=
     return tls, pause
 
 
+def token_contour(layout, word_pitch=None, word_gains=None):
+    """layout as for token_controls; word_pitch {word index: semitones}, word_gains {word index: dB} (include/vits_contour.h)
+    -> (token_pitch float32 [T] or None, token_gain_db float32 [T] or None): a word's setting covers the tokens of its phonemes and the
+    blank in front of each, as a word's rate does.  ValueError names a word that does not exist or a value the engine refuses."""
+    from .capi import CONTOUR_DB, PITCH_MAX_SEMITONES
+
+    symbols, counts, blank, word_of, word_texts = layout
+    ranges = symbol_tokens(counts, blank)
+    T = ranges[-1][1] if ranges else 0
+    out = []
+    for name, unit, values, lo, hi in (("word_pitch", "semitones", word_pitch, -PITCH_MAX_SEMITONES, PITCH_MAX_SEMITONES),
+                                       ("word_gains", "dB", word_gains, CONTOUR_DB[0], CONTOUR_DB[1])):
+        if not values:
+            out.append(None)
+            continue
+        a = np.zeros(T, np.float32)
+        for w, v in values.items():
+            if w not in word_texts:
+                raise ValueError(f"{name}: no word {w!r} (the text has {len(word_texts)} words)")
+            v = float(v)
+            if not lo <= v <= hi:  # (NaN fails the comparison)
+                raise ValueError(f"{name}[{w!r}] = {v}: {unit} must lie in [{lo:g}, {hi:g}]")
+            for (i, j), wo in zip(ranges, word_of):
+                if wo == w:
+                    a[i:j] = np.float32(v)
+        out.append(a)
+    return out[0], out[1]
+
+
 def split_pause_markup(text):
     """The reference's '_' pause markup in VITS text (config inference.pause_markup): -> (text without the marks, [index of the word each
     mark follows]).  Words are counted as marks.vits_layout counts them; a mark in front of the first word is dropped."""

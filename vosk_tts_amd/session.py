@@ -229,10 +229,13 @@ _OPTIONAL_NONE = ("bert", "phone_duration_extra")
 # extension feeds (not part of the ONNX graph) used by parity tests
 _EXT = ("vits.noise_dp", "vits.noise_prior", "vits.forced_durations", "vits.seed", "vits.solo", "vits.item_seeds", "vits.sample_rate", "vits.marks",
         "vits.loudness", "vits.peak", "vits.peak_ceiling", "vits.pitch", "vits.pitch_formants", "vits.limit", "vits.limit_lookahead_ms",
-        "vits.limit_release_ms", "vits.item_scales", "vits.token_length_scale", "vits.token_pause", "vits.fit_frames")
+        "vits.limit_release_ms", "vits.item_scales", "vits.token_length_scale", "vits.token_pause", "vits.fit_frames", "vits.token_pitch",
+        "vits.token_gain_db")
 # the prosody controls of a request (include/vits_prosody.h): feed key -> keyword of capi.VitsModel.synthesize*
 _PROSODY = {"vits.item_scales": "item_scales", "vits.token_length_scale": "token_length_scale", "vits.token_pause": "token_pause",
             "vits.fit_frames": "fit_frames"}
+# the contour of a request (include/vits_contour.h): feed key -> keyword of capi.VitsModel.synthesize*
+_CONTOUR = {"vits.token_pitch": "token_pitch", "vits.token_gain_db": "token_gain_db"}
 
 
 class _Arg:
@@ -287,7 +290,7 @@ class VitsSession:
         Returns the request's token count (> 0) when it may be merged, 0 otherwise -- a length outside (0, T] is NOT sliced here:
         such a request takes the direct call, whose C-side check answers VITS_ERR_ARG as it always did."""
         if not (self.coalescer is not None and ids.shape[0] == 1 and self.hp.bert_dim == 0 and
-                not any(k in feed for k in ("vits.noise_dp", "vits.noise_prior", "vits.forced_durations", "vits.solo", "vits.item_seeds", "bert") + tuple(_PROSODY))):
+                not any(k in feed for k in ("vits.noise_dp", "vits.noise_prior", "vits.forced_durations", "vits.solo", "vits.item_seeds", "bert") + tuple(_PROSODY) + tuple(_CONTOUR))):
             return 0
         lens = np.asarray(feed["input_lengths"]).reshape(-1)
         if lens.shape[0] != 1:
@@ -434,7 +437,7 @@ class VitsSession:
             noise_dp=feed.get("vits.noise_dp"), noise_prior=feed.get("vits.noise_prior"),
             forced_durations=feed.get("vits.forced_durations"), seed=int(seed), solo=bool(feed.get("vits.solo", False)),
             item_seeds=feed.get("vits.item_seeds"), bert=feed.get("bert"), sample_rate=rate, marks=marks, loudness=loud,
-            **self._pitch_kw(pitch, formants, limit), **self._prosody(feed))
+            **self._pitch_kw(pitch, formants, limit), **self._prosody(feed), **self._contour(feed))
         self.last_lengths = res[1]
         return [res[0][:, None, None, :], res[2]] if marks else [res[0][:, None, None, :]]
 
@@ -453,6 +456,15 @@ class VitsSession:
 
             self._lib._need_prosody()
             check_controls(np.asarray(feed["input_lengths"]).reshape(-1), forced="vits.forced_durations" in feed, **kw)
+        return kw
+
+    def _contour(self, feed):
+        """The contour of a request (include/vits_contour.h) -> keywords of the model's calls, none without one (the call as it was).
+        Feeds "vits.token_pitch" float [B, T_x] semitones and "vits.token_gain_db" float [B, T_x] dB; the model's call refuses values out
+        of range before any device work (ValueError naming item, token and value)."""
+        kw = {v: feed[k] for k, v in _CONTOUR.items() if k in feed}
+        if kw:
+            self._lib._need_contour()
         return kw
 
     def _marks(self, feed):
@@ -501,7 +513,7 @@ class VitsSession:
             pcm_scale=float(scale), noise_dp=feed.get("vits.noise_dp"), noise_prior=feed.get("vits.noise_prior"),
             forced_durations=feed.get("vits.forced_durations"), seed=int(seed), solo=bool(feed.get("vits.solo", False)),
             item_seeds=feed.get("vits.item_seeds"), bert=feed.get("bert"), sample_rate=rate, marks=marks, loudness=loud,
-            **self._pitch_kw(pitch, formants, limit), **self._prosody(feed))
+            **self._pitch_kw(pitch, formants, limit), **self._prosody(feed), **self._contour(feed))
         pcm, lengths = res[0], res[1]
         self.last_lengths = lengths
         if marks:
@@ -524,6 +536,9 @@ class VitsSession:
         if pitch_from_feed(self._lib, feed)[0] is not None:
             raise ValueError("a stream cannot be pitch-shifted: the phase recursion needs the frames before a chunk (run() / run_pcm16() "
                              "take \"vits.pitch\")")
+        if any(k in feed for k in _CONTOUR):
+            raise ValueError("a stream cannot be contoured: the position recurrence and the phase recursion need the whole utterance before "
+                             "the first chunk (run() / run_pcm16() take \"vits.token_pitch\" / \"vits.token_gain_db\")")
         rate = self._rate(sample_rate if sample_rate is not None else feed.get("vits.sample_rate"))
         if ids.shape[0] != 1:
             raise ValueError("run_stream takes one utterance")

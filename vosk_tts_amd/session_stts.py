@@ -16,7 +16,7 @@ from .outopts import limit_from_feed, loudness_from_feed, pitch_from_feed
 _INPUTS = ("input", "input_lengths", "scales", "sid", "bert", "phone_duration_extra")
 _EXT = ("vits.noise", "vits.seed", "vits.n_timesteps", "vits.sample_rate", "vits.denoiser_strength", "vits.denoiser_filter_length",
         "vits.marks", "vits.loudness", "vits.peak", "vits.peak_ceiling", "vits.pitch", "vits.pitch_formants",
-        "vits.limit", "vits.limit_lookahead_ms", "vits.limit_release_ms")
+        "vits.limit", "vits.limit_lookahead_ms", "vits.limit_release_ms", "vits.token_pitch", "vits.token_gain_db")
 
 
 class SttsSession:
@@ -103,9 +103,14 @@ class SttsSession:
         return limit_from_feed(self._lib, feed)
 
     def _pitch(self, feed):
-        """outopts.pitch_from_feed as the keywords of the model's calls: empty without a shift"""
+        """outopts.pitch_from_feed and the contour feeds "vits.token_pitch" / "vits.token_gain_db" (float [1, T], include/vits_contour.h)
+        as the keywords of the model's calls: empty without a shift and without a contour"""
         p, formants = pitch_from_feed(self._lib, feed)
-        return {} if p is None else {"pitch": p, "preserve_formants": True} if formants else {"pitch": p}
+        kw = {} if p is None else {"pitch": p, "preserve_formants": True} if formants else {"pitch": p}
+        for k, name in (("vits.token_pitch", "token_pitch"), ("vits.token_gain_db", "token_gain_db")):
+            if k in feed:
+                kw[name] = np.asarray(feed[k], np.float32).reshape(-1)
+        return kw
 
     def normalize(self, audio, lengths, sample_rate, spec, limit=None):
         """audio float32 [B, S] at `sample_rate` Hz (None / 0 = the vocoder's own) with per-item sample counts -> the audio normalised

@@ -351,6 +351,25 @@ class Synth:
             args["vits.fit_frames"] = np.array([F], np.int32)
         return True
 
+    def _contour(self, args, text, word_pitch=None, word_gains=None):
+        """Per-word pitch and volume of the request (include/vits_contour.h; both voice families): word_pitch {word index: semitones},
+        word_gains {word index: dB}, words counted as the speech marks count them.  A word's setting covers the tokens of its phonemes
+        and the blank in front of each; the engine ramps between neighbours over about 100 ms.  The feed gets "vits.token_pitch" /
+        "vits.token_gain_db" (vosk_tts_amd/prosody.py token_contour); none given = off.  Values out of range are a ValueError here."""
+        if not word_pitch and not word_gains:
+            return False
+        from . import prosody as P
+
+        tp, tg = P.token_contour(self.marks_layout(text), word_pitch, word_gains)
+        T = np.asarray(args["input"]).shape[-1]
+        for name, a in (("vits.token_pitch", tp), ("vits.token_gain_db", tg)):
+            if a is None:
+                continue
+            if a.shape[0] != T:
+                raise ValueError(f"token layout does not match: {a.shape[0]} tokens laid out for {T} ids")
+            args[name] = a[None]
+        return True
+
     def marks_layout(self, text):
         """The token layout of `text` under the front end _feed picks, for speech marks (vosk_tts_amd/marks.py):
         -> (symbols, ids per symbol, blank layout?, word_of per symbol, word_texts).  Needs the voice's config and dictionary only."""
@@ -383,8 +402,9 @@ class Synth:
     def synth_audio(self, text, speaker_id=0, noise_level=None, speech_rate=None, duration_noise_level=None, scale=None, sample_rate=None,
                     denoiser_strength=None, marks=False, loudness=None, peak=None, peak_ceiling=None, pitch=None,
                     preserve_formants=None, limit=None, limit_lookahead_ms=None, limit_release_ms=None, word_rates=None, pauses=None,
-                    duration=None):
-        """word_rates / pauses / duration (extension): per-word tempo, pauses behind words and the length of the whole utterance in
+                    duration=None, word_pitch=None, word_gains=None):
+        """word_pitch / word_gains (extension): per-word semitones and decibels, see _contour.
+        word_rates / pauses / duration (extension): per-word tempo, pauses behind words and the length of the whole utterance in
         seconds, see _prosody.
         limit / limit_lookahead_ms / limit_release_ms (extension): the look-ahead peak limiter, see _limit; peak_ceiling is then its
         ceiling.
@@ -398,6 +418,7 @@ class Synth:
         text, pauses = self._prosody_text(text, word_rates, pauses, duration)
         args, scale = self._feed(text, speaker_id, noise_level, speech_rate, duration_noise_level, scale)
         self._prosody(args, self.normalize(text), word_rates, pauses, duration)
+        self._contour(args, self.normalize(text), word_pitch, word_gains)
         self._denoiser(args, denoiser_strength)
         self._loudness(args, loudness, peak, peak_ceiling)
         self._limit(args, limit, peak_ceiling, limit_lookahead_ms, limit_release_ms)
@@ -436,6 +457,24 @@ class Synth:
         if marks:
             return audio, self._marks(text, ends, rate)
         return audio
+
+    def synth_ssml(self, ssml, **kw):
+        """synth_audio for an SSML document (vosk_tts_amd/ssml.py: speak, p, s, sub, break, prosody rate / pitch / volume, mark): the
+        document becomes the text and the word_rates / pauses / word_pitch / word_gains keywords, so those four are not accepted next
+        to it; every other keyword of synth_audio is.  With marks=True the returned marks carry `named`: {mark name: start sample of the
+        next word, or the end of the audio behind the last one}.  Whatever the subset does not cover is a ValueError before the model
+        is touched; on a multistream voice rate and break raise that family's own refusal."""
+        from . import ssml as S
+
+        plan = S.parse(ssml)
+        for k in ("word_rates", "pauses", "word_pitch", "word_gains"):
+            if kw.get(k) is not None:
+                raise ValueError(f"synth_ssml takes {k} from the document's markup, not as a keyword")
+        res = self.synth_audio(plan.text, **dict(kw, **plan.keywords()))
+        if kw.get("marks"):
+            audio, sm = res
+            sm.named = {name: (int(sm.words[w][1]) if w < len(sm.words) else int(audio.shape[-1])) for name, w in plan.marks}
+        return res
 
     def synth_stream(self, text, speaker_id=0, noise_level=None, speech_rate=None, duration_noise_level=None, scale=None,
                      chunk_frames=64, sample_rate=None, denoiser_strength=None, on_marks=None, loudness=None, peak=None, peak_ceiling=None,
@@ -478,12 +517,14 @@ class Synth:
 
     def synth(self, text, oname, speaker_id=0, noise_level=None, speech_rate=None, duration_noise_level=None, scale=None, sample_rate=None,
               denoiser_strength=None, marks=False, loudness=None, peak=None, peak_ceiling=None, pitch=None, preserve_formants=None,
-              limit=None, limit_lookahead_ms=None, limit_release_ms=None, word_rates=None, pauses=None, duration=None):
+              limit=None, limit_lookahead_ms=None, limit_release_ms=None, word_rates=None, pauses=None, duration=None, word_pitch=None,
+              word_gains=None):
         """marks=True: the utterance's marks.SpeechMarks are returned (the default returns None, as the reference does)"""
         audio = self.synth_audio(text, speaker_id, noise_level, speech_rate, duration_noise_level, scale, sample_rate, denoiser_strength, marks=marks,
                                  loudness=loudness, peak=peak, peak_ceiling=peak_ceiling, pitch=pitch,
                                  preserve_formants=preserve_formants, limit=limit, limit_lookahead_ms=limit_lookahead_ms,
-                                 limit_release_ms=limit_release_ms, **{k: v for k, v in (("word_rates", word_rates), ("pauses", pauses), ("duration", duration))
+                                 limit_release_ms=limit_release_ms, **{k: v for k, v in (("word_rates", word_rates), ("pauses", pauses), ("duration", duration),
+                                                                                           ("word_pitch", word_pitch), ("word_gains", word_gains))
                                                                       if v is not None})
         sm = None
         if marks:
