@@ -168,7 +168,7 @@ class MultiDeviceSynth:
 
     def synth_batch(self, texts, speaker_ids=0, noise_level=None, speech_rate=None, duration_noise_level=None, scale=None, seeds=None,
                     sample_rate=None, denoiser_strength=None, marks=False, loudness=None, peak=None, peak_ceiling=None, pitch=None,
-                    preserve_formants=None, limit=None, limit_lookahead_ms=None, limit_release_ms=None):
+                    preserve_formants=None, limit=None, limit_lookahead_ms=None, limit_release_ms=None, pitch_range=None):
         """texts: list of str -> list of int16 PCM arrays (22.05 kHz), one per request, in request order.  marks=True: a list of
         (audio, marks.SpeechMarks) per request instead (as Synth.synth_audio(..., marks=True)), through every shard path.  `seeds`: optional
         per-request noise seeds (default: a running counter), `speaker_ids`: one id or one per request.  `noise_level` / `speech_rate` /
@@ -180,13 +180,16 @@ class MultiDeviceSynth:
         `loudness` / `peak` / `peak_ceiling`: a LUFS or a peak target for every request of the batch (defaults and rules of
         Synth.synth_audio): each request is measured and normalised on its own, so it equals its single call with the same seed.
         `limit` / `limit_lookahead_ms` / `limit_release_ms`: the look-ahead peak limiter (include/vits_limit.h), one setting per call and a
-        gain per request; `peak_ceiling` is then the limiter's ceiling."""
+        gain per request; `peak_ceiling` is then the limiter's ceiling.
+        `pitch_range`: the intonation range (include/vits_intonation.h), one value per call; every request is tracked and scaled about
+        its own median, so it equals its single call with the same seed."""
         s0 = self.synths[0]
         loud = {}
         s0._loudness(loud, loudness, peak, peak_ceiling)
         s0._limit(loud, limit, peak_ceiling, limit_lookahead_ms, limit_release_ms)
         # "vits.pitch" (and "vits.pitch_formants"): one shift for the whole batch, travelling with the loudness feeds; include/vits_pitch.h
         s0._pitch(loud, pitch, preserve_formants)
+        s0._range(loud, pitch_range)  # ("vits.pitch_range": travels the same way)
         dn = {}
         s0._denoiser(dn, denoiser_strength)
         denoiser_strength = dn.get("vits.denoiser_strength")

@@ -295,6 +295,39 @@ def set_contour(opts, keep, arrays, flag=FLAG_CONTOUR):
     opts.flags |= flag
 
 
+# include/vits_intonation.h
+FLAG_INTONATION = 128            # VITS_FLAG_INTONATION (STTS_FLAG_INTONATION has the same value)
+INTONATION_MAX_RANGE = 4.0       # VITS_INTONATION_MAX_RANGE
+INTONATION_RATES = (8000, 32000)  # VITS_INTONATION_MIN_RATE, VITS_INTONATION_MAX_RATE
+
+
+class SynthIntonationOpts(SynthContourOpts):
+    """mirror of `struct vits_synth_opts_intonation` (include/vits_intonation.h): SynthContourOpts followed by pitch_range, which the
+    library reads only under VITS_FLAG_INTONATION"""
+
+    _fields_ = [("pitch_range", ctypes.c_float)]
+
+
+def range_spec(pitch_range=None):
+    """The intonation range a call asks for -> None (none, or one whose r_m = lround(1000 r) is 1000: the call as it was) or r as a
+    float.  ValueError names a value out of range (NaN included), as the library's VITS_ERR_ARG does: here before any device work"""
+    if pitch_range is None:
+        return None
+    import math
+    r = float(np.float32(pitch_range))  # (the value the library is handed)
+    if not 0.0 <= r <= INTONATION_MAX_RANGE:
+        raise ValueError(f"pitch_range {float(pitch_range)} outside [0, {INTONATION_MAX_RANGE:g}]")
+    return None if int(math.floor(1000.0 * r + 0.5)) == 1000 else r
+
+
+def set_intonation(opts, pitch_range, flag=FLAG_INTONATION):
+    """Sets the flag and the field of a SynthIntonationOpts / SttsIntonationOpts from a range_spec()"""
+    if pitch_range is None:
+        return
+    opts.pitch_range = pitch_range
+    opts.flags |= flag
+
+
 class PersistInfo(ctypes.Structure):
     """mirror of `struct vits_persist_info` (vits_persist_state)"""
 
@@ -379,6 +412,7 @@ class VitsLib:
         self.has_limit = False
         self.has_prosody = False
         self.has_contour = False
+        self.has_intonation = False
         if self.is_device:
             c_i16p = ctypes.POINTER(ctypes.c_int16)
             f("synthesize_pcm16").argtypes = [ctypes.c_void_p, c_i64p, c_i64p, ctypes.c_int32, ctypes.c_int32, c_f32p, c_i64p,
@@ -477,6 +511,14 @@ class VitsLib:
                 door = [ctypes.c_int, c_f32p, c_i64p, ctypes.c_int32, ctypes.c_int64, c_i32p, c_i64p, ctypes.c_int32, ctypes.c_int32, c_f32p, c_f32p]
                 f("op_contour").argtypes = door + [c_f32p]
                 f("op_contour_stretch").argtypes = door + [c_f32p, c_i64p]
+            # include/vits_intonation.h: the intonation range (the flag of the synthesize calls and the three doors)
+            self.has_intonation = self.has("op_intonation")
+            if self.has_intonation:
+                door = [ctypes.c_int, c_f32p, c_i64p, ctypes.c_int32, ctypes.c_int64, ctypes.c_int32, c_i32p, c_i64p, ctypes.c_int32, ctypes.c_int32,
+                        c_f32p, c_f32p, ctypes.c_float]
+                f("op_f0_track").argtypes = [ctypes.c_int, c_f32p, c_i64p, ctypes.c_int32, ctypes.c_int64, ctypes.c_int32, c_i32p]
+                f("op_intonation").argtypes = door + [c_f32p]
+                f("op_intonation_stretch").argtypes = door + [c_f32p, c_i64p, c_i32p]
             if self.has("debug_clock_probe"):
                 f("debug_clock_probe").argtypes = [ctypes.c_int, ctypes.c_int32, ctypes.POINTER(ctypes.c_double), ctypes.c_int32]
 
@@ -774,6 +816,72 @@ class VitsLib:
                                         lambda B, N: [np.empty((B, 256 * (2 * (N // 256 + 2) - 1)), np.float32),
                                                       np.empty((B, 2 * (N // 256 + 2) + 2), np.int64)]))
 
+    # ---- intonation range (include/vits_intonation.h) ----------------------------
+    def _need_intonation(self):
+        if not self.has_intonation:
+            raise VitsError(4, "this backend has no intonation control (include/vits_intonation.h)")
+
+    def op_f0_track(self, x, lengths, rate, device=0):
+        """vits_op_f0_track: x float32 [B, N], lengths [B], rate in Hz -> cents int32 [B, 1 + N // 256]: 1200 log2(f0 / 27.5) of every
+        analysis row, 0 where unvoiced, behind an item's rows and for an item below 513 samples"""
+        self._need_intonation()
+        x = _f32(x)
+        if x.ndim != 2:
+            raise ValueError("x must be [B, N]")
+        B, N = x.shape
+        lengths = _i64(lengths).reshape(-1)
+        if lengths.shape != (B,):
+            raise ValueError("lengths must be [B]")
+        cents = np.empty((B, 1 + N // 256), np.int32)
+        self.check(self._fn("op_f0_track")(device, _p(x, c_f32p), _p(lengths, c_i64p), B, N, int(rate), _p(cents, c_i32p)))
+        return cents
+
+    def _intonation_door(self, name, x, lengths, rate, pitch_range, cum, tok_lengths, hop, token_semitones, token_gain_db, device, outs):
+        self._need_intonation()
+        x = _f32(x)
+        if x.ndim != 2:
+            raise ValueError("x must be [B, N]")
+        B, N = x.shape
+        lengths = _i64(lengths).reshape(-1)
+        if lengths.shape != (B,):
+            raise ValueError("lengths must be [B]")
+        Tx, st, db = 0, None, None
+        if cum is not None:
+            cum = _i32(cum)
+            tok_lengths = _i64(tok_lengths).reshape(-1)
+            if tok_lengths.shape != (B,) or cum.ndim != 2 or cum.shape[0] != B:
+                raise ValueError("tok_lengths must be [B], cum [B, T_x]")
+            Tx = cum.shape[1]
+            st = None if token_semitones is None else _f32(token_semitones)
+            db = None if token_gain_db is None else _f32(token_gain_db)
+            for a in (st, db):
+                if a is not None and a.shape != (B, Tx):
+                    raise ValueError("token_semitones / token_gain_db must be [B, T_x]")
+        elif tok_lengths is not None or token_semitones is not None or token_gain_db is not None:
+            raise ValueError("tok_lengths, token_semitones and token_gain_db need cum")
+        else:
+            tok_lengths = None
+        ys = outs(B, N)
+        typ = {np.dtype(np.float32): c_f32p, np.dtype(np.int64): c_i64p, np.dtype(np.int32): c_i32p}
+        self.check(self._fn(name)(device, _p(x, c_f32p), _p(lengths, c_i64p), B, N, int(rate), _p(cum, c_i32p), _p(tok_lengths, c_i64p), Tx, int(hop),
+                                  _p(st, c_f32p), _p(db, c_f32p), float(pitch_range), *[_p(y, typ[y.dtype]) for y in ys]))
+        return ys
+
+    def op_intonation(self, x, lengths, rate, pitch_range, cum=None, tok_lengths=None, hop=256, token_semitones=None, token_gain_db=None, device=0):
+        """vits_op_intonation: x float32 [B, N], lengths [B], rate in Hz, pitch_range r in [0, 4]; optionally the tokens of op_contour (cum
+        int32 [B, T_x], tok_lengths [B], hop, token_semitones / token_gain_db) -> y float32 [B, N]; item b from x[b, :lengths[b]] only"""
+        return self._intonation_door("op_intonation", x, lengths, rate, pitch_range, cum, tok_lengths, hop, token_semitones, token_gain_db, device,
+                                     lambda B, N: [np.empty((B, N), np.float32)])[0]
+
+    def op_intonation_stretch(self, x, lengths, rate, pitch_range, cum=None, tok_lengths=None, hop=256, token_semitones=None, token_gain_db=None,
+                              device=0):
+        """vits_op_intonation_stretch: (u, steps) with the shapes of op_contour_stretch and cents int32 [B, 1 + N // 256], the track the
+        ratios came from"""
+        return tuple(self._intonation_door("op_intonation_stretch", x, lengths, rate, pitch_range, cum, tok_lengths, hop, token_semitones,
+                                           token_gain_db, device,
+                                           lambda B, N: [np.empty((B, 256 * (2 * (N // 256 + 2) - 1)), np.float32),
+                                                         np.empty((B, 2 * (N // 256 + 2) + 2), np.int64), np.empty((B, 1 + N // 256), np.int32)]))
+
     # ---- prosody controls (include/vits_prosody.h) ------------------------------
     def _need_prosody(self):
         if not self.has_prosody:
@@ -848,11 +956,15 @@ class VitsModel:
             pass
 
     def _opts(self, B, Tx, noise_dp, noise_prior, forced_durations, seed, max_frames, solo=False, item_seeds=None, bert=None,
-              loudness=None, loudness_out=None, pitch=None, preserve_formants=False, limit=None, prosody=None, prosody_out=None, contour=None):
+              loudness=None, loudness_out=None, pitch=None, preserve_formants=False, limit=None, prosody=None, prosody_out=None, contour=None,
+              pitch_range=None):
         pitch = pitch_spec(pitch)  # (None, or a shift that does not reduce to P = Q)
+        pitch_range = range_spec(pitch_range)  # (None, or a range whose r_m is not 1000)
         if contour is not None:
             self.lib._need_contour()
-        opts = SynthContourOpts() if contour is not None else SynthProsodyOpts() if prosody is not None else SynthLimitOpts() if limit is not None else SynthOpts() if pitch is None else SynthPitchOpts()
+        if pitch_range is not None:
+            self.lib._need_intonation()
+        opts = SynthIntonationOpts() if pitch_range is not None else SynthContourOpts() if contour is not None else SynthProsodyOpts() if prosody is not None else SynthLimitOpts() if limit is not None else SynthOpts() if pitch is None else SynthPitchOpts()
         keep = []
         if prosody is not None:
             self.lib._need_prosody()
@@ -898,6 +1010,7 @@ class VitsModel:
             opts.pitch_semitones = pitch
         set_prosody(opts, keep, prosody, B, prosody_out)
         set_contour(opts, keep, contour)
+        set_intonation(opts, pitch_range)
         return opts, keep
 
     # ---- the hot path -----------------------------------------------------
@@ -913,8 +1026,11 @@ class VitsModel:
     def synthesize(self, ids, lengths, scales, sid, noise_dp=None, noise_prior=None, forced_durations=None, seed=0,
                    max_frames=0, solo=False, item_seeds=None, bert=None, sample_rate=None, marks=False, loudness=None, loudness_out=None,
                    pitch=None, preserve_formants=False, limit=None, item_scales=None, token_length_scale=None, token_pause=None,
-                   fit_frames=None, fit_ratio=False, token_pitch=None, token_gain_db=None):
-        """token_pitch / token_gain_db: float [B, T_x] semitones / dB per token (VITS_FLAG_CONTOUR, include/vits_contour.h): every token
+                   fit_frames=None, fit_ratio=False, token_pitch=None, token_gain_db=None, pitch_range=None):
+        """pitch_range: r in [0, 4] (VITS_FLAG_INTONATION, include/vits_intonation.h): how far every item moves about its own median pitch,
+        times r, from an F0 track of the finished waveform on the device; 0 is a monotone, 1 the call as it was.  Lengths and marks do not
+        change.  Not with preserve_formants.
+        token_pitch / token_gain_db: float [B, T_x] semitones / dB per token (VITS_FLAG_CONTOUR, include/vits_contour.h): every token
         raised or lowered by its own amount on the device, in the pitch stage's place; `pitch` is added to every token; lengths and marks
         do not change.  Not with preserve_formants.
         item_scales float [B, 3], token_length_scale float [B, T_x], token_pause int32 [B, T_x] frames, fit_frames int32 [B]
@@ -942,7 +1058,7 @@ class VitsModel:
         pros_out = {}
         opts, keep = self._opts(B, Tx, noise_dp, noise_prior, forced_durations, seed, max_frames, solo, item_seeds, bert, loudness, loudness_out,
                                 pitch, preserve_formants, limit, prosody_arrays(B, Tx, item_scales, token_length_scale, token_pause, fit_frames),
-                                pros_out, contour_arrays(B, Tx, token_pitch, token_gain_db, lengths, pitch_spec(pitch)))
+                                pros_out, contour_arrays(B, Tx, token_pitch, token_gain_db, lengths, pitch_spec(pitch)), pitch_range)
         out = c_f32p()
         ns = ctypes.c_int64()
         olen = np.zeros(B, dtype=np.int64)
@@ -972,9 +1088,9 @@ class VitsModel:
     def synthesize_pcm16(self, ids, lengths, scales, sid, pcm_scale=1.0, noise_dp=None, noise_prior=None, forced_durations=None,
                          seed=0, max_frames=0, solo=False, item_seeds=None, bert=None, sample_rate=None, marks=False, loudness=None,
                          loudness_out=None, pitch=None, preserve_formants=False, limit=None, item_scales=None, token_length_scale=None,
-                         token_pause=None, fit_frames=None, fit_ratio=False, token_pitch=None, token_gain_db=None):
+                         token_pause=None, fit_frames=None, fit_ratio=False, token_pitch=None, token_gain_db=None, pitch_range=None):
         """pitch, preserve_formants, limit, item_scales, token_length_scale, token_pause, fit_frames, fit_ratio, token_pitch,
-        token_gain_db: as for synthesize.
+        token_gain_db, pitch_range: as for synthesize.
         synthesize() with Synth.synth_audio's `* scale` and audio_float_to_int16 (vosk_tts/synth.py:127-130) done on the
         device: returns (pcm int16 [B,S], out_lengths int64 [B]).  sample_rate: as for synthesize (vits_synthesize_pcm16_rate:
         the resampler does the conversion in its epilogue).  loudness / loudness_out: as for synthesize (pcm_scale multiplies the
@@ -987,7 +1103,7 @@ class VitsModel:
         pros_out = {}
         opts, keep = self._opts(B, Tx, noise_dp, noise_prior, forced_durations, seed, max_frames, solo, item_seeds, bert, loudness, loudness_out,
                                 pitch, preserve_formants, limit, prosody_arrays(B, Tx, item_scales, token_length_scale, token_pause, fit_frames),
-                                pros_out, contour_arrays(B, Tx, token_pitch, token_gain_db, lengths, pitch_spec(pitch)))
+                                pros_out, contour_arrays(B, Tx, token_pitch, token_gain_db, lengths, pitch_spec(pitch)), pitch_range)
         out = ctypes.POINTER(ctypes.c_int16)()
         ns = ctypes.c_int64()
         olen = np.zeros(B, dtype=np.int64)

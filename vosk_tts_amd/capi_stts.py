@@ -6,7 +6,7 @@ import ctypes
 import numpy as np
 
 from .capi import (LIMIT_FIELDS, Contour, VitsError, VitsLib, _f32, _i32, _i64, _p, c_f32p, c_i32p, c_i64p, contour_arrays, pitch_spec,
-                   set_contour, set_limit, set_loudness)
+                   range_spec, set_contour, set_intonation, set_limit, set_loudness)
 from .weights_stts import SttsHParams
 
 
@@ -59,6 +59,16 @@ class SttsContourOpts(SttsLimitOpts):
     the library reads only under STTS_FLAG_CONTOUR"""
 
     _fields_ = [("contour", ctypes.POINTER(Contour))]
+
+
+STTS_FLAG_INTONATION = 128    # include/vits_intonation.h
+
+
+class SttsIntonationOpts(SttsContourOpts):
+    """mirror of `struct stts_synth_opts_intonation` (include/vits_intonation.h): SttsContourOpts followed by pitch_range, which the
+    library reads only under STTS_FLAG_INTONATION"""
+
+    _fields_ = [("pitch_range", ctypes.c_float)]
 
 
 class SttsModel:
@@ -148,20 +158,24 @@ class SttsModel:
         assert isinstance(opts, SttsLimitOpts)
         set_limit(opts, keep, spec, B, STTS_FLAG_LIMIT, out)
 
-    def _opts_for(self, loudness, pitch, preserve_formants=False, limit=None, contour=None):
+    def _opts_for(self, loudness, pitch, preserve_formants=False, limit=None, contour=None, pitch_range=None):
         """the options struct a call needs: the plain one, the one with the loudness fields, the one with the pitch behind those, the
-        one with the limiter behind that, or the one with the contour pointer last; preserve_formants sets its bit only with a pitch in
-        effect"""
+        one with the limiter behind that, the one with the contour pointer behind that, or the one with pitch_range (a range_spec(),
+        include/vits_intonation.h) last; preserve_formants sets its bit only with a pitch in effect"""
+        if pitch_range is not None and not getattr(self.vlib, "has_intonation", False):
+            raise VitsError(4, "this backend has no intonation control (include/vits_intonation.h)")
         if limit is not None and not getattr(self.vlib, "has_limit", False):
             raise VitsError(4, "this backend has no peak limiter (include/vits_limit.h)")
         if contour is not None and not getattr(self.vlib, "has_contour", False):
             raise VitsError(4, "this backend has no pitch / volume contours (include/vits_contour.h)")
-        if pitch_spec(pitch) is not None or limit is not None or contour is not None:
+        if pitch_spec(pitch) is not None or limit is not None or contour is not None or pitch_range is not None:
             if pitch_spec(pitch) is not None and not getattr(self.vlib, "has_pitch", False):
                 raise VitsError(4, "this backend has no pitch shifter (include/vits_pitch.h)")
             if pitch_spec(pitch) is not None and preserve_formants and not getattr(self.vlib, "has_pitch_formant", False):
                 raise VitsError(4, "this backend has no formant-preserving pitch shift (include/vits_pitch.h, STTS_FLAG_PITCH_FORMANT)")
-            opts = SttsContourOpts() if contour is not None else SttsPitchOpts() if limit is None else SttsLimitOpts()
+            opts = (SttsIntonationOpts() if pitch_range is not None else SttsContourOpts() if contour is not None
+                    else SttsPitchOpts() if limit is None else SttsLimitOpts())
+            set_intonation(opts, pitch_range, STTS_FLAG_INTONATION)
             if pitch_spec(pitch) is None:
                 return opts
             opts.flags |= STTS_FLAG_PITCH | (STTS_FLAG_PITCH_FORMANT if preserve_formants else 0)
@@ -176,8 +190,11 @@ class SttsModel:
     # ---- hot path ----------------------------------------------------------------------------
     def synthesize(self, ids, scales, sid, bert=None, phone_duration_extra=None, noise=None, seed=0, n_timesteps=0,
                    want_audio=True, want_mel=True, denoiser_strength=None, denoiser_filter_length=0, marks=False, sample_rate=None,
-                   loudness=None, loudness_out=None, pitch=None, preserve_formants=False, limit=None, token_pitch=None, token_gain_db=None):
-        """token_pitch / token_gain_db: float [T] semitones / dB per token (STTS_FLAG_CONTOUR, include/vits_contour.h): every token raised
+                   loudness=None, loudness_out=None, pitch=None, preserve_formants=False, limit=None, token_pitch=None, token_gain_db=None,
+                   pitch_range=None):
+        """pitch_range: r in [0, 4] (STTS_FLAG_INTONATION, include/vits_intonation.h): the utterance's movement about its own median pitch
+        times r; 1 is the call as it was.
+        token_pitch / token_gain_db: float [T] semitones / dB per token (STTS_FLAG_CONTOUR, include/vits_contour.h): every token raised
         or lowered by its own amount, in the pitch stage's place; `pitch` is added to every token.  Lengths and marks do not change.
         limit: a capi.limit_spec() (STTS_FLAG_LIMIT, include/vits_limit.h): the peak limiter with the loudness gain or alone;
         loudness_out then also receives "reduction".
@@ -203,7 +220,8 @@ class SttsModel:
         if want_audio and (token_pitch is not None or token_gain_db is not None):
             con = contour_arrays(1, T, None if token_pitch is None else _f32(token_pitch).reshape(1, -1),
                                  None if token_gain_db is None else _f32(token_gain_db).reshape(1, -1), None, pitch_spec(pitch))
-        opts = self._opts_for(loudness, pitch if want_audio else None, preserve_formants, limit if want_audio else None, con)
+        opts = self._opts_for(loudness, pitch if want_audio else None, preserve_formants, limit if want_audio else None, con,
+                              range_spec(pitch_range) if want_audio else None)
         set_contour(opts, keep, con, STTS_FLAG_CONTOUR)
         if noise is not None:
             a = _f32(noise); keep.append(a)
@@ -290,8 +308,8 @@ class SttsModel:
 
     def synthesize_batch(self, ids, lengths, scales, sid, bert=None, phone_duration_extra=None, seed=0, n_timesteps=0, item_seeds=None,
                          denoiser_strength=None, denoiser_filter_length=0, marks=False, sample_rate=None, loudness=None, loudness_out=None,
-                         pitch=None, preserve_formants=False, limit=None, token_pitch=None, token_gain_db=None):
-        """token_pitch / token_gain_db: float [B, T], as for synthesize.
+                         pitch=None, preserve_formants=False, limit=None, token_pitch=None, token_gain_db=None, pitch_range=None):
+        """token_pitch / token_gain_db: float [B, T], as for synthesize; pitch_range: as for synthesize, one value for the batch.
         pitch, preserve_formants, limit: as for synthesize, one value for the batch; every item is shifted from its own length.
         B independent utterances in one pass (stts_synthesize_batch): ids [B,5,T], lengths [B], sid [B];
         returns (audio float32 [B,S] zero-padded, out_lengths int64 [B] in samples).  Item b equals
@@ -306,7 +324,7 @@ class SttsModel:
         b = None if bert is None else _f32(bert)
         p = None if phone_duration_extra is None else _f32(phone_duration_extra)
         con = contour_arrays(B, T, token_pitch, token_gain_db, lengths, pitch_spec(pitch))
-        opts = self._opts_for(loudness, pitch, preserve_formants, limit, con)
+        opts = self._opts_for(loudness, pitch, preserve_formants, limit, con, range_spec(pitch_range))
         opts.seed = seed; opts.n_timesteps = n_timesteps
         self._denoise(opts, denoiser_strength, denoiser_filter_length)
         keep = []

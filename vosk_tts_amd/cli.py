@@ -53,6 +53,8 @@ _OPTIONS = (
                              help="raise or lower word INDEX by SEMITONES, -12 to 12, at unchanged duration; repeatable")),
     (("--word-gain",), dict(action="append", default=None, metavar="INDEX=DB",
                             help="speak word INDEX DB decibels louder (-40 to 12); repeatable")),
+    (("--pitch-range",), dict(type=float, default=None, metavar="R",
+                              help="intonation range: how far the voice moves about its median pitch, 0 (monotone) to 4, 1 = unchanged")),
     (("--ssml",), dict(action="store_true", help="the input is an SSML document: speak, p, s, sub, break, prosody, mark")),
     (("--marks",), dict(type=str, default=None, metavar="FILE",
                         help="also write the speech marks as JSON: rate, phonemes and words with their offsets in samples and seconds")),
@@ -102,6 +104,7 @@ def run(opts):
         res = synth.synth_ssml(opts.input, speaker_id=opts.speaker, speech_rate=opts.speech_rate, sample_rate=opts.sample_rate,
                                denoiser_strength=opts.denoiser_strength, marks=bool(opts.marks), loudness=opts.loudness, peak=opts.peak,
                                pitch=opts.pitch, **({} if opts.limit is None else {"limit": opts.limit}),
+                               **({} if getattr(opts, "pitch_range", None) is None else {"pitch_range": opts.pitch_range}),
                                **({} if getattr(opts, "duration", None) is None else {"duration": opts.duration}))
         audio, marks = res if opts.marks else (res, None)
         with wave.open(opts.output, "w") as f:
@@ -119,7 +122,8 @@ def run(opts):
                                **{k: v for k, v in (("duration", getattr(opts, "duration", None)), ("pauses", _indexed(getattr(opts, "pause", None), "--pause")),
                                                     ("word_rates", _indexed(getattr(opts, "word_rate", None), "--word-rate")),
                                                     ("word_pitch", _indexed(getattr(opts, "word_pitch", None), "--word-pitch", "=")),
-                                                    ("word_gains", _indexed(getattr(opts, "word_gain", None), "--word-gain", "="))) if v is not None})
+                                                    ("word_gains", _indexed(getattr(opts, "word_gain", None), "--word-gain", "=")),
+                                                    ("pitch_range", getattr(opts, "pitch_range", None))) if v is not None})
     if opts.marks:
         with open(opts.marks, "w", encoding="utf-8") as f:
             f.write(marks.to_json(indent=1) + "\n")

@@ -285,6 +285,9 @@ __global__ __launch_bounds__(256) void contour_gain_kernel(const float* __restri
   ct_store<OUT>(y + (long long)b * y_bstride + n, v, scale);
 }
 
+// the frame table from the signal instead of the tokens (include/vits_intonation.h): its kernels, IntonReq and the table of its ratios
+#include "intonation.hip.h"
+
 // ---- host ---------------------------------------------------------------------------------------------------------------
 // What a contoured call hands the device: P_t and g_t per token [B][Tx] (neutral beyond an item's tokens), and per item whether any of
 // its tokens is shifted.  on: some token of the call is not neutral (case (a) of the header otherwise).
@@ -349,9 +352,11 @@ static int contour_tab_get(int device, const float** out) {
 }
 
 // bytes of scratch an item of `len` samples takes in a group (the strides of a group are those of its longest item); F_s <= 2 (F_a + 1)
-static size_t contour_item_bytes(long long len) {
+// inton: with the track, the offsets and the ratios of include/vits_intonation.h (three ints a row)
+static size_t contour_item_bytes(long long len, bool inton = false) {
   const long long Fa = pt_frames_a(len), F = ct_frames(len), cap = 2 * (Fa + 1);
   size_t n = (size_t)(F + 1) * 12 + (size_t)(cap + 2) * 8 + 64;
+  if (inton) n += (size_t)(F + 1) * 12 + 16;
   if (Fa) n += (size_t)(Fa + 2) * PT_NB * 8 + (size_t)cap * PT_NB * 4 + (size_t)cap * PT_N * 4 + (size_t)(cap - 1) * PT_H * 4;
   return n;
 }
@@ -361,19 +366,25 @@ static size_t contour_item_bytes(long long len) {
 // Allocates its scratch and waits for the stream before it frees it: not capturable.  y is not x.
 // u_out / steps_out (both or neither; device): the stretch door -- u goes to u_out[b * u_bstride + j], the step tables to
 // steps_out[b * s_bstride + ..] (zeroed by the caller), and nothing is warped.
+// in (optional): the frame table comes from the item's own F0 track (include/vits_intonation.h) -- the tokens' ratios times the track's,
+// row by row; which items go through the vocoder is then the device's word, read back once per group.  cents_out (with `in` only, or
+// null; device, [B][c_bstride] with c_bstride >= 1 + (the longest length) / H): where the track is left.  q.Tx may be 0 with `in`.
 static int contour_run(int device, hipStream_t stream, const float* x, long long x_bstride, const long long* h_len, int B, const ContourReq& q,
                        const int* d_cum, long long cum_bstride, const int* d_toklen, int hop, void* y, bool pcm, float pcm_scale,
-                       long long y_bstride, long long n_count, float* u_out, long long u_bstride, long long* steps_out, long long s_bstride) {
+                       long long y_bstride, long long n_count, float* u_out, long long u_bstride, long long* steps_out, long long s_bstride,
+                       const IntonReq* in = nullptr, int* cents_out = nullptr, long long c_bstride = 0) {
   if (B <= 0) return VITS_OK;
   const DenoiseTab* D = nullptr;
   TRY(denoise_get(device, PT_N, &D));
   const float* d_T = nullptr;
   TRY(contour_tab_get(device, &d_T));
+  const int* d_R = nullptr;
+  if (in) TRY(inton_tab_get(device, &d_R));
   std::vector<int> len32(B), vlen32(B);
   for (int b = 0; b < B; ++b) {
     if (h_len[b] < 0 || h_len[b] >= (1LL << 31)) return fail(VITS_ERR_ARG, "contour: length %lld of item %d", h_len[b], b);
     len32[b] = (int)h_len[b];
-    vlen32[b] = (q.shift[b] && h_len[b] >= PT_M + 1) ? (int)h_len[b] : 0;
+    vlen32[b] = (q.shift[b] && h_len[b] >= PT_M + 1) ? (int)h_len[b] : 0;  // (with `in`: set from the device's word, group by group)
   }
   std::vector<std::pair<int, int>> groups;  // (first item, count): consecutive items whose scratch fits
   size_t need = 0;
@@ -382,13 +393,13 @@ static int contour_run(int device, hipStream_t stream, const float* x, long long
     int c = 0;
     while (b0 + c < B && c < 65535) {
       const long long m2 = std::max(mx, h_len[b0 + c]);
-      if (contour_item_bytes(m2) * (size_t)(c + 1) > (size_t)VITS_PITCH_MAX_SCRATCH) break;
+      if (contour_item_bytes(m2, in != nullptr) * (size_t)(c + 1) > (size_t)VITS_PITCH_MAX_SCRATCH) break;
       mx = m2;
       ++c;
     }
     if (!c) return fail(VITS_ERR_UNSUPPORTED, "contour: an item of %lld samples needs %zu bytes of scratch (limit %lld)", h_len[b0],
-                        contour_item_bytes(h_len[b0]), (long long)VITS_PITCH_MAX_SCRATCH);
-    need = std::max(need, contour_item_bytes(mx) * (size_t)c);
+                        contour_item_bytes(h_len[b0], in != nullptr), (long long)VITS_PITCH_MAX_SCRATCH);
+    need = std::max(need, contour_item_bytes(mx, in != nullptr) * (size_t)c);
     groups.emplace_back(b0, c);
     b0 += c;
   }
@@ -401,27 +412,54 @@ static int contour_run(int device, hipStream_t stream, const float* x, long long
   int* d_P = d_vlen + B;
   float* d_g = reinterpret_cast<float*>(d_P + (size_t)B * q.Tx);
   hipError_t e = hipMemcpyAsync(d_len, len32.data(), sizeof(int) * B, hipMemcpyHostToDevice, stream);
-  if (e == hipSuccess) e = hipMemcpyAsync(d_vlen, vlen32.data(), sizeof(int) * B, hipMemcpyHostToDevice, stream);
-  if (e == hipSuccess) e = hipMemcpyAsync(d_P, q.P.data(), tok_bytes, hipMemcpyHostToDevice, stream);
-  if (e == hipSuccess) e = hipMemcpyAsync(d_g, q.g.data(), tok_bytes, hipMemcpyHostToDevice, stream);
+  if (e == hipSuccess && !in) e = hipMemcpyAsync(d_vlen, vlen32.data(), sizeof(int) * B, hipMemcpyHostToDevice, stream);
+  if (e == hipSuccess && tok_bytes) e = hipMemcpyAsync(d_P, q.P.data(), tok_bytes, hipMemcpyHostToDevice, stream);
+  if (e == hipSuccess && tok_bytes) e = hipMemcpyAsync(d_g, q.g.data(), tok_bytes, hipMemcpyHostToDevice, stream);
+  std::vector<int> h_flag(in ? B : 0);
   for (size_t gi = 0; gi < groups.size() && e == hipSuccess; ++gi) {
     const int b0 = groups[gi].first, c = groups[gi].second;
     long long mx = 0, vmx = 0;
-    for (int b = 0; b < c; ++b) { mx = std::max(mx, h_len[b0 + b]); vmx = std::max(vmx, (long long)vlen32[b0 + b]); }
-    const long long F = ct_frames(mx), Fa = pt_frames_a(vmx), cap = 2 * (Fa + 1);
-    const long long t_bs = F + 1, s_bs = steps_out ? s_bstride : cap + 2;
-    const long long a_bs = (Fa + 2) * PT_NB, p_bs = cap * PT_NB, f_bs = cap * PT_N, u_bs = (cap - 1) * PT_H;
-    char* p = scr + head;
-    long long* d_inc = reinterpret_cast<long long*>(p); p += 8 * (size_t)c * t_bs;
-    long long* d_steps = steps_out ? steps_out + (long long)b0 * s_bstride : reinterpret_cast<long long*>(p);
-    p += 8 * (size_t)c * (cap + 2);
-    float* d_gbar = reinterpret_cast<float*>(p); p += 4 * (size_t)c * t_bs;
-    p += (8 - (p - scr) % 8) % 8;
+    for (int b = 0; b < c; ++b) mx = std::max(mx, h_len[b0 + b]);
+    const long long F = ct_frames(mx), t_bs = F + 1;
     const float* xg = x + (long long)b0 * x_bstride;
     const int *lg = d_len + b0, *vg = d_vlen + b0;
-    hipLaunchKernelGGL(contour_tracks_kernel, dim3((unsigned)((F + 255) / 256), c), dim3(256), 0, stream, lg, d_cum + (long long)b0 * cum_bstride,
-                       cum_bstride, d_toklen + b0, (long long)hop, d_P + (size_t)b0 * q.Tx, d_g + (size_t)b0 * q.Tx, (long long)q.Tx, q.Tx, d_inc,
-                       d_gbar, t_bs);
+    const int* cumg = d_cum ? d_cum + (long long)b0 * cum_bstride : nullptr;
+    const int* tlg = d_toklen ? d_toklen + b0 : nullptr;
+    char* p = scr + head;
+    long long* d_inc = reinterpret_cast<long long*>(p); p += 8 * (size_t)c * t_bs;
+    float* d_gbar = reinterpret_cast<float*>(p); p += 4 * (size_t)c * t_bs;
+    int* d_Pf = nullptr;
+    if (in) {  // the track, the offsets, the ratios and the items' words; then which items the vocoder takes
+      int* d_cents = cents_out ? cents_out + (long long)b0 * c_bstride : reinterpret_cast<int*>(p);
+      const long long c_bs = cents_out ? c_bstride : t_bs;
+      p += 4 * (size_t)c * t_bs;
+      int* d_o = reinterpret_cast<int*>(p); p += 4 * (size_t)c * t_bs;
+      d_Pf = reinterpret_cast<int*>(p); p += 4 * (size_t)c * t_bs;
+      int* d_flag = reinterpret_cast<int*>(p); p += 4 * (size_t)c;
+      inton_track_launch(stream, xg, x_bstride, lg, c, F, in->rate, d_cents, c_bs);
+      hipLaunchKernelGGL(intonation_item_kernel, dim3(c), dim3(IN_ITEM_T), 0, stream, lg, d_cents, c_bs, in->r_m, d_R, cumg, cum_bstride, tlg,
+                         (long long)hop, d_P + (size_t)b0 * q.Tx, (long long)q.Tx, q.Tx, d_o, d_Pf, t_bs, d_flag);
+      e = hipMemcpyAsync(h_flag.data() + b0, d_flag, sizeof(int) * c, hipMemcpyDeviceToHost, stream);
+      if (e == hipSuccess) e = hipStreamSynchronize(stream);
+      if (e != hipSuccess) break;
+      for (int b = b0; b < b0 + c; ++b) vlen32[b] = (h_flag[b] && h_len[b] >= PT_M + 1) ? (int)h_len[b] : 0;
+      e = hipMemcpyAsync(d_vlen + b0, vlen32.data() + b0, sizeof(int) * c, hipMemcpyHostToDevice, stream);
+      if (e != hipSuccess) break;
+    }
+    for (int b = 0; b < c; ++b) vmx = std::max(vmx, (long long)vlen32[b0 + b]);
+    const long long Fa = pt_frames_a(vmx), cap = 2 * (Fa + 1);
+    const long long s_bs = steps_out ? s_bstride : cap + 2;
+    const long long a_bs = (Fa + 2) * PT_NB, p_bs = cap * PT_NB, f_bs = cap * PT_N, u_bs = (cap - 1) * PT_H;
+    p += (8 - (p - scr) % 8) % 8;
+    long long* d_steps = steps_out ? steps_out + (long long)b0 * s_bstride : reinterpret_cast<long long*>(p);
+    p += 8 * (size_t)c * (cap + 2);
+    p += (8 - (p - scr) % 8) % 8;
+    if (in)
+      hipLaunchKernelGGL(intonation_tracks_kernel, dim3((unsigned)((F + 255) / 256), c), dim3(256), 0, stream, lg, cumg, cum_bstride, tlg,
+                         (long long)hop, d_g + (size_t)b0 * q.Tx, (long long)q.Tx, q.Tx, d_Pf, d_inc, d_gbar, t_bs);
+    else
+      hipLaunchKernelGGL(contour_tracks_kernel, dim3((unsigned)((F + 255) / 256), c), dim3(256), 0, stream, lg, cumg, cum_bstride, tlg, (long long)hop,
+                         d_P + (size_t)b0 * q.Tx, d_g + (size_t)b0 * q.Tx, (long long)q.Tx, q.Tx, d_inc, d_gbar, t_bs);
     float* d_u = nullptr;
     if (Fa && s_bs >= cap + 2) {
       float* d_mag = reinterpret_cast<float*>(p); p += sizeof(float) * (size_t)c * a_bs;
@@ -468,13 +506,18 @@ static int contour_run(int device, hipStream_t stream, const float* x, long long
 
 // ---- the parity doors ---------------------------------------------------------------------------------------------------
 static int contour_op(int device, const float* x, const int64_t* lengths, int32_t B, int64_t N, const int32_t* cum, const int64_t* tok_lengths,
-                      int32_t Tx, int32_t hop, const float* token_semitones, const float* token_gain_db, float* y, float* u, int64_t* steps) {
+                      int32_t Tx, int32_t hop, const float* token_semitones, const float* token_gain_db, float* y, float* u, int64_t* steps,
+                      const IntonReq* in = nullptr, int32_t* cents = nullptr) {
   const bool stretch = u != nullptr;
-  if ((!stretch && !y) || (stretch && !steps) || !cum || !tok_lengths || Tx <= 0 || hop <= 0) return fail(VITS_ERR_ARG, "contour: bad argument");
+  const char* what = in ? "intonation" : "contour";
+  const bool no_tokens = in && !cum && Tx == 0;  // (include/vits_intonation.h: the stage without a contour)
+  if ((!stretch && !y) || (stretch && !steps) || hop <= 0 || (!no_tokens && (!cum || !tok_lengths || Tx <= 0))) return fail(VITS_ERR_ARG, "%s: bad argument", what);
   std::vector<int> len32;
-  TRY(op_items_check("contour", x, lengths, B, N, &len32, "N = "));
-  std::vector<int> tl32(B);
-  for (int b = 0; b < B; ++b) {
+  TRY(op_items_check(what, x, lengths, B, N, &len32, "N = "));
+  std::vector<int> tl32(B, 0);
+  const std::vector<int64_t> no_tl(B, 0);
+  if (no_tokens) tok_lengths = no_tl.data();
+  for (int b = 0; b < B && !no_tokens; ++b) {
     if (tok_lengths[b] < 0 || tok_lengths[b] > Tx) return fail(VITS_ERR_ARG, "contour: token length %lld of item %d outside [0, T_x = %d]", (long long)tok_lengths[b], b, Tx);
     tl32[b] = (int)tok_lengths[b];
     for (int t = 0; t < tl32[b]; ++t) {
@@ -485,22 +528,24 @@ static int contour_op(int device, const float* x, const int64_t* lengths, int32_
   ContourReq q;
   TRY(contour_plan(token_semitones, token_gain_db, 0.f, tok_lengths, B, Tx, &q));
   const std::vector<long long> len64(lengths, lengths + B);
-  const long long Nu = (long long)PT_H * (2 * (N / PT_H + 2) - 1), Ns = 2 * (N / PT_H + 2) + 2;
-  OpDoor d("contour", device);
+  const long long Nu = (long long)PT_H * (2 * (N / PT_H + 2) - 1), Ns = 2 * (N / PT_H + 2) + 2, Nc = 1 + N / PT_H;
+  OpDoor d(what, device);
   // every item's own samples only: what lies at and beyond lengths[b] never reaches the device
   float* dx = d.out<float>((size_t)B * N, 0);
   for (int b = 0; b < B && d.ok(); ++b)
     if (lengths[b]) d.hip(hipMemcpy(dx + (size_t)b * N, x + (size_t)b * N, sizeof(float) * (size_t)lengths[b], hipMemcpyHostToDevice));
-  int* dc = d.up(cum, (size_t)B * Tx);
+  int* dc = no_tokens ? nullptr : d.up(cum, (size_t)B * Tx);
   int* dt = d.up(tl32.data(), B);
   float* dy = stretch ? d.out<float>((size_t)B * Nu) : d.out<float>((size_t)B * N);
   long long* ds = stretch ? d.out<long long>((size_t)B * Ns, 0) : nullptr;
+  int* dcents = cents ? d.out<int>((size_t)B * Nc, 0) : nullptr;
   if (d.ok())
-    TRY(stretch ? contour_run(device, nullptr, dx, N, len64.data(), B, q, dc, Tx, dt, hop, nullptr, false, 1.f, 0, 0, dy, Nu, ds, Ns)
-                : contour_run(device, nullptr, dx, N, len64.data(), B, q, dc, Tx, dt, hop, dy, false, 1.f, N, N, nullptr, 0, nullptr, 0));
+    TRY(stretch ? contour_run(device, nullptr, dx, N, len64.data(), B, q, dc, Tx, dt, hop, nullptr, false, 1.f, 0, 0, dy, Nu, ds, Ns, in, dcents, Nc)
+                : contour_run(device, nullptr, dx, N, len64.data(), B, q, dc, Tx, dt, hop, dy, false, 1.f, N, N, nullptr, 0, nullptr, 0, in, dcents, Nc));
   d.finish();
   d.down(stretch ? u : y, dy, stretch ? (size_t)B * Nu : (size_t)B * N);
   if (stretch) d.down(reinterpret_cast<long long*>(steps), ds, (size_t)B * Ns);
+  if (cents) d.down(reinterpret_cast<int*>(cents), dcents, (size_t)B * Nc);
   return d.rc();
 }
 
@@ -513,4 +558,47 @@ int vits_op_contour_stretch(int device, const float* x, const int64_t* lengths, 
                             float* u, int64_t* steps) {
   if (!u) return fail(VITS_ERR_ARG, "contour: bad argument");
   return contour_op(device, x, lengths, B, N, cum, tok_lengths, T_x, hop, token_semitones, token_gain_db, nullptr, u, steps);
+}
+
+// ---- the doors of include/vits_intonation.h -------------------------------------------------------------------------------
+int vits_op_f0_track(int device, const float* x, const int64_t* lengths, int32_t B, int64_t N, int32_t rate, int32_t* cents) {
+  if (!cents) return fail(VITS_ERR_ARG, "f0 track: bad argument");
+  std::vector<int> len32;
+  TRY(op_items_check("f0 track", x, lengths, B, N, &len32, "N = "));
+  TRY(inton_rate_arg(rate));
+  const long long Nc = 1 + N / PT_H;
+  OpDoor d("f0 track", device);
+  // every item's own samples only: what lies at and beyond lengths[b] never reaches the device
+  float* dx = d.out<float>((size_t)B * N, 0);
+  for (int b = 0; b < B && d.ok(); ++b)
+    if (lengths[b]) d.hip(hipMemcpy(dx + (size_t)b * N, x + (size_t)b * N, sizeof(float) * (size_t)lengths[b], hipMemcpyHostToDevice));
+  int* dl = d.up(len32.data(), B);
+  int* dc = d.dev<int>((size_t)B * Nc);
+  if (d.ok()) inton_track_launch(nullptr, dx, N, dl, B, Nc, rate, dc, Nc);
+  d.finish();
+  d.down(reinterpret_cast<int*>(cents), dc, (size_t)B * Nc);
+  return d.rc();
+}
+
+static int inton_op(int device, const float* x, const int64_t* lengths, int32_t B, int64_t N, int32_t rate, const int32_t* cum,
+                    const int64_t* tok_lengths, int32_t T_x, int32_t hop, const float* token_semitones, const float* token_gain_db, float pitch_range,
+                    float* y, float* u, int64_t* steps, int32_t* cents) {
+  IntonReq in;
+  TRY(inton_range_arg(pitch_range, &in.r_m));
+  TRY(inton_rate_arg(rate));
+  in.on = true;  // (a door runs the stage at r_m == 1000 too: every R_f is 1000 then)
+  in.rate = rate;
+  return contour_op(device, x, lengths, B, N, cum, tok_lengths, T_x, hop, token_semitones, token_gain_db, y, u, steps, &in, cents);
+}
+
+int vits_op_intonation(int device, const float* x, const int64_t* lengths, int32_t B, int64_t N, int32_t rate, const int32_t* cum,
+                       const int64_t* tok_lengths, int32_t T_x, int32_t hop, const float* token_semitones, const float* token_gain_db,
+                       float pitch_range, float* y) {
+  return inton_op(device, x, lengths, B, N, rate, cum, tok_lengths, T_x, hop, token_semitones, token_gain_db, pitch_range, y, nullptr, nullptr, nullptr);
+}
+int vits_op_intonation_stretch(int device, const float* x, const int64_t* lengths, int32_t B, int64_t N, int32_t rate, const int32_t* cum,
+                               const int64_t* tok_lengths, int32_t T_x, int32_t hop, const float* token_semitones,
+                               const float* token_gain_db, float pitch_range, float* u, int64_t* steps, int32_t* cents) {
+  if (!u || !cents) return fail(VITS_ERR_ARG, "intonation: bad argument");
+  return inton_op(device, x, lengths, B, N, rate, cum, tok_lengths, T_x, hop, token_semitones, token_gain_db, pitch_range, nullptr, u, steps, cents);
 }

@@ -1,14 +1,16 @@
 // out_tail.hip.h -- the output tail: what a synthesize call asks of the stages behind the decoder (TailReq, built by tail_req from the
-// plain fields behind the option flags), and the one runner of the chain  pitch / contour -> resample -> normalise / limit -> int16  on the device
+// plain fields behind the option flags), and the one runner of the chain  pitch / contour / intonation -> resample -> normalise / limit -> int16  on the device
 // (tail_run).  The kernels and their launches are those of resample / loudness / limit / pitch / contour.hip.h; this file only orders them.
 // Part of the ONE translation unit engine.hip (included there, behind limit.hip.h, pitch.hip.h and contour.hip.h; not a standalone header).
 #pragma once
 
 // ---- the request ----------------------------------------------------------------------------------------------------------
 // The flag bits and the name of an API family: the two families number the same four flags differently.
-struct TailFamily { const char* name; uint32_t loudness, limit, pitch, formant, contour; };
-static const TailFamily TAIL_VITS = {"VITS", VITS_FLAG_LOUDNESS, VITS_FLAG_LIMIT, VITS_FLAG_PITCH, VITS_FLAG_PITCH_FORMANT, VITS_FLAG_CONTOUR};
-static const TailFamily TAIL_STTS = {"STTS", STTS_FLAG_LOUDNESS, STTS_FLAG_LIMIT, STTS_FLAG_PITCH, STTS_FLAG_PITCH_FORMANT, STTS_FLAG_CONTOUR};
+struct TailFamily { const char* name; uint32_t loudness, limit, pitch, formant, contour, intonation; };
+static const TailFamily TAIL_VITS = {"VITS", VITS_FLAG_LOUDNESS, VITS_FLAG_LIMIT, VITS_FLAG_PITCH, VITS_FLAG_PITCH_FORMANT, VITS_FLAG_CONTOUR,
+                                     VITS_FLAG_INTONATION};
+static const TailFamily TAIL_STTS = {"STTS", STTS_FLAG_LOUDNESS, STTS_FLAG_LIMIT, STTS_FLAG_PITCH, STTS_FLAG_PITCH_FORMANT, STTS_FLAG_CONTOUR,
+                                     STTS_FLAG_INTONATION};
 
 // The values behind the flags of a call, flat.  A group is meaningful only where its `on` is set (`formant` is the bare flag bit).
 struct TailFields {
@@ -25,11 +27,13 @@ struct TailFields {
   float semitones = 0.f;
   bool contour_on = false;
   const vits_contour* contour = nullptr;
+  bool inton_on = false;
+  float pitch_range = 1.f;
 };
 
 // The only two places that cast down the `base` chain of the extended option structs: a struct's own fields are read under its flag
 // alone, so a caller who sets no flag may pass the plain struct (include/vits_loudness.h, vits_pitch.h, vits_limit.h).
-template <typename Pitch, typename Limit, typename Contour, typename Loud, typename Opts>
+template <typename Pitch, typename Limit, typename Contour, typename Inton, typename Loud, typename Opts>
 static TailFields tail_fields(const TailFamily& fam, const Opts* opts, const Loud* lo) {
   TailFields f;
   f.family = fam.name;
@@ -48,19 +52,22 @@ static TailFields tail_fields(const TailFamily& fam, const Opts* opts, const Lou
   if (f.pitch_on) f.semitones = reinterpret_cast<const Pitch*>(opts)->pitch_semitones;
   f.contour_on = (fl & fam.contour) != 0;
   if (f.contour_on) f.contour = reinterpret_cast<const Contour*>(opts)->contour;
+  f.inton_on = (fl & fam.intonation) != 0;
+  if (f.inton_on) f.pitch_range = reinterpret_cast<const Inton*>(opts)->pitch_range;
   return f;
 }
 static TailFields tail_fields_vits(const vits_synth_opts* opts) {  // (the loudness fields are the plain struct's own)
   static_assert(offsetof(vits_synth_opts_limit, base) == 0 && offsetof(vits_synth_opts_pitch, base) == 0 && offsetof(vits_synth_opts_prosody, base) == 0 &&
-                    offsetof(vits_synth_opts_contour, base) == 0,
+                    offsetof(vits_synth_opts_contour, base) == 0 && offsetof(vits_synth_opts_intonation, base) == 0,
                 "the extended options begin with the plain ones");
-  return tail_fields<vits_synth_opts_pitch, vits_synth_opts_limit, vits_synth_opts_contour>(TAIL_VITS, opts, opts);
+  return tail_fields<vits_synth_opts_pitch, vits_synth_opts_limit, vits_synth_opts_contour, vits_synth_opts_intonation>(TAIL_VITS, opts, opts);
 }
 static TailFields tail_fields_stts(const stts_synth_opts* opts) {
   static_assert(offsetof(stts_synth_opts_limit, base) == 0 && offsetof(stts_synth_opts_pitch, base) == 0 && offsetof(stts_synth_opts_loudness, base) == 0 &&
-                    offsetof(stts_synth_opts_contour, base) == 0,
+                    offsetof(stts_synth_opts_contour, base) == 0 && offsetof(stts_synth_opts_intonation, base) == 0,
                 "the extended options begin with the plain ones");
-  return tail_fields<stts_synth_opts_pitch, stts_synth_opts_limit, stts_synth_opts_contour>(TAIL_STTS, opts, reinterpret_cast<const stts_synth_opts_loudness*>(opts));
+  return tail_fields<stts_synth_opts_pitch, stts_synth_opts_limit, stts_synth_opts_contour, stts_synth_opts_intonation>(
+      TAIL_STTS, opts, reinterpret_cast<const stts_synth_opts_loudness*>(opts));
 }
 
 // the formant bit modifies a pitch request: alone it is refused, before any work is queued
@@ -81,6 +88,8 @@ static int tail_refuse_stream(uint32_t flags, const TailFamily& fam) {
     return fail(VITS_ERR_UNSUPPORTED, "%s_FLAG_PITCH on a stream: the phase recursion needs the frames before a chunk, and its state is not carried across chunks", fam.name);
   if (flags & fam.contour)
     return fail(VITS_ERR_UNSUPPORTED, "%s_FLAG_CONTOUR on a stream: the position recurrence and the phase recursion need the whole utterance before the first chunk", fam.name);
+  if (flags & fam.intonation)
+    return fail(VITS_ERR_UNSUPPORTED, "%s_FLAG_INTONATION on a stream: the median of the F0 track needs the whole utterance before the first chunk", fam.name);
   return VITS_OK;
 }
 
@@ -89,6 +98,8 @@ static int tail_refuse_stream(uint32_t flags, const TailFamily& fam) {
 struct TailReq {
   PitchReq pitch;
   ContourReq contour;  // (include/vits_contour.h; where it is on, the call's own shift is part of its tokens and `pitch` is off)
+  IntonReq inton;      // (include/vits_intonation.h; where it is on, `contour` is on too and carries the tokens, neutral without a contour)
+  const IntonReq* inton_arg() const { return inton.on ? &inton : nullptr; }  // what contour_run takes
   const ResampleTab* T = nullptr;
   int rate = 0;
   NormReq norm;
@@ -118,19 +129,37 @@ static int tail_req(const vits_model* vocoder, const TailFields& f, int32_t samp
 // synthesised.  A contour whose every token is neutral leaves the request as tail_req made it (case (a): the call as it was, the
 // pitch stage included); otherwise VITS_FLAG_PITCH's semitones are added to every token and the pitch stage itself does not run.
 static int tail_contour_req(const vits_model* vocoder, const TailFields& f, const int64_t* tok_lengths, int B, int Tx, TailReq* out) {
-  if (!f.contour_on) return VITS_OK;
-  if (!f.contour) return fail(VITS_ERR_ARG, "%s_FLAG_CONTOUR with a NULL contour pointer (include/vits_contour.h)", f.family);
-  if (f.formant)
+  // include/vits_intonation.h: refused or planned here too, as its frame table is the contour's; r_m == 1000 is the call without the flag
+  int r_m = 1000;
+  if (f.inton_on) {
+    TRY(inton_range_arg(f.pitch_range, &r_m));
+    if (f.formant)
+      return fail(VITS_ERR_UNSUPPORTED, "%s_FLAG_INTONATION with %s_FLAG_PITCH_FORMANT: the envelope pre-warp assumes one ratio per call (include/vits_intonation.h)",
+                  f.family, f.family);
+  }
+  const bool inton = r_m != 1000;
+  if (!f.contour_on && !inton) return VITS_OK;
+  if (f.contour_on && !f.contour) return fail(VITS_ERR_ARG, "%s_FLAG_CONTOUR with a NULL contour pointer (include/vits_contour.h)", f.family);
+  if (f.contour_on && f.formant)
     return fail(VITS_ERR_UNSUPPORTED, "%s_FLAG_CONTOUR with %s_FLAG_PITCH_FORMANT: the envelope pre-warp assumes one ratio per call (include/vits_contour.h)",
                 f.family, f.family);
   if (!vocoder) return fail(VITS_ERR_ARG, "no vocoder attached");
-  TRY(contour_plan(f.contour->token_semitones, f.contour->token_gain_db, 0.f, tok_lengths, B, Tx, &out->contour));
-  if (!out->contour.on) return VITS_OK;
-  if (f.pitch_on) TRY(contour_plan(f.contour->token_semitones, f.contour->token_gain_db, f.semitones, tok_lengths, B, Tx, &out->contour));
+  const float* ts = f.contour_on ? f.contour->token_semitones : nullptr;
+  const float* tg = f.contour_on ? f.contour->token_gain_db : nullptr;
+  TRY(contour_plan(ts, tg, 0.f, tok_lengths, B, Tx, &out->contour));
+  if (!out->contour.on && !inton) return VITS_OK;
+  if (f.pitch_on) TRY(contour_plan(ts, tg, f.semitones, tok_lengths, B, Tx, &out->contour));
   out->contour.on = true;
   out->pitch = PitchReq();
   if (vocoder->hp.hop_length % PT_H)
-    return fail(VITS_ERR_UNSUPPORTED, "contour: the vocoder's hop_length %d is not a multiple of the pitch stage's hop %d", vocoder->hp.hop_length, PT_H);
+    return fail(VITS_ERR_UNSUPPORTED, "%s: the vocoder's hop_length %d is not a multiple of the pitch stage's hop %d", f.contour_on ? "contour" : "intonation",
+                vocoder->hp.hop_length, PT_H);
+  if (inton) {
+    TRY(inton_rate_arg(vocoder->hp.sampling_rate));
+    out->inton.on = true;
+    out->inton.r_m = r_m;
+    out->inton.rate = vocoder->hp.sampling_rate;
+  }
   return VITS_OK;
 }
 
@@ -163,7 +192,8 @@ static int tail_run(Alloc&& alloc, vits_session* s, hipStream_t stream, const fl
     const bool cp = q.pcm && !T && !q.norm.on();
     void* d_c = alloc((cp ? sizeof(int16_t) : sizeof(float)) * (size_t)B * S);
     if (!d_c) return fail(VITS_ERR_NOMEM, "device alloc failed");
-    TRY(contour_run(s->m->device, stream, x, S, h_len, B, q.contour, d_cum, cum_bstride, d_toklen, hop, d_c, cp, q.pcm_scale, S, S, nullptr, 0, nullptr, 0));
+    TRY(contour_run(s->m->device, stream, x, S, h_len, B, q.contour, d_cum, cum_bstride, d_toklen, hop, d_c, cp, q.pcm_scale, S, S, nullptr, 0, nullptr, 0,
+                    q.inton_arg()));
     if (cp) { *d_out = d_c; return VITS_OK; }
     x = static_cast<const float*>(d_c);
   }

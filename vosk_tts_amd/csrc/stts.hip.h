@@ -1067,7 +1067,8 @@ static int stts_tail_host(stts_model* m, const TailReq& q, int B, float** audio,
     int* dc = d.up(cum, (size_t)B * Tx);
     int* dt = d.up(tl32.data(), B);
     float* dy = d.out<float>((size_t)B * *S);
-    if (d.ok()) TRY(contour_run(device, nullptr, dx, *S, len64.data(), B, q.contour, dc, Tx, dt, stts_hop(m), dy, false, 1.f, *S, *S, nullptr, 0, nullptr, 0));
+    if (d.ok()) TRY(contour_run(device, nullptr, dx, *S, len64.data(), B, q.contour, dc, Tx, dt, stts_hop(m), dy, false, 1.f, *S, *S, nullptr, 0, nullptr, 0,
+                                  q.inton_arg()));
     d.finish();
     d.down(y.data(), dy, y.size());
     if (!d.ok()) return d.rc();

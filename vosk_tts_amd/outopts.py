@@ -1,7 +1,7 @@
 """The extension feeds of the output tail (pitch -> resample -> normalise / limit, DESIGN.md "Output tail"), read once for both session
-types: what a request's feed asks of the loudness, limiter and pitch stages, checked before any device work.  `lib` is the session's
+types: what a request's feed asks of the loudness, limiter, pitch and intonation stages, checked before any device work.  `lib` is the session's
 library: a stage the loaded library does not export is refused here (its _need_* check)."""
-from .capi import limit_spec, loudness_spec, pitch_spec
+from .capi import limit_spec, loudness_spec, pitch_spec, range_spec
 
 
 def loudness_from_feed(lib, feed):
@@ -39,3 +39,12 @@ def pitch_from_feed(lib, feed):
     if formants:
         lib._need_pitch_formant()
     return p, formants
+
+
+def range_from_feed(lib, feed):
+    """"vits.pitch_range" (r in [0, 4]; include/vits_intonation.h) -> r as a float, or None for none and for one whose
+    lround(1000 r) is 1000 (the request as it was).  A value out of range is ValueError"""
+    r = range_spec(feed.get("vits.pitch_range"))
+    if r is not None:
+        lib._need_intonation()
+    return r

@@ -19,7 +19,7 @@ import threading
 import numpy as np
 
 from .capi import VitsLib
-from .outopts import limit_from_feed, loudness_from_feed, pitch_from_feed
+from .outopts import limit_from_feed, loudness_from_feed, pitch_from_feed, range_from_feed
 
 log = logging.getLogger(__name__)
 
@@ -230,7 +230,7 @@ _OPTIONAL_NONE = ("bert", "phone_duration_extra")
 _EXT = ("vits.noise_dp", "vits.noise_prior", "vits.forced_durations", "vits.seed", "vits.solo", "vits.item_seeds", "vits.sample_rate", "vits.marks",
         "vits.loudness", "vits.peak", "vits.peak_ceiling", "vits.pitch", "vits.pitch_formants", "vits.limit", "vits.limit_lookahead_ms",
         "vits.limit_release_ms", "vits.item_scales", "vits.token_length_scale", "vits.token_pause", "vits.fit_frames", "vits.token_pitch",
-        "vits.token_gain_db")
+        "vits.token_gain_db", "vits.pitch_range")
 # the prosody controls of a request (include/vits_prosody.h): feed key -> keyword of capi.VitsModel.synthesize*
 _PROSODY = {"vits.item_scales": "item_scales", "vits.token_length_scale": "token_length_scale", "vits.token_pause": "token_pause",
             "vits.fit_frames": "fit_frames"}
@@ -309,8 +309,11 @@ class VitsSession:
         # pitch: the shift of the batch in semitones (None = none; include/vits_pitch.h): part of the key as well, one value per call
         # formants: that shift with the spectral envelope kept (VITS_FLAG_PITCH_FORMANT); False whenever pitch is None
         # limit: the limiter of the batch (capi.limit_spec(), None = none; include/vits_limit.h): part of the key, applied per item
-        kind, scale, rate, marks, loud, pitch, formants, limit = key
+        # prange: the intonation range of the batch (None = none; include/vits_intonation.h): a ninth entry that only a request with one has
+        kind, scale, rate, marks, loud, pitch, formants, limit = key[:8]
         pk = self._pitch_kw(pitch, formants, limit)
+        if len(key) > 8:
+            pk = dict(pk, pitch_range=key[8])
         scales = np.array(reqs[0][3], np.float32)
         if len(reqs) == 1:
             ids, sid, seed = reqs[0][:3]
@@ -412,6 +415,16 @@ class VitsSession:
             return kw
         return dict(kw, pitch=pitch, preserve_formants=True) if formants else dict(kw, pitch=pitch)
 
+    @staticmethod
+    def _range_key(prange):
+        """what an intonation range adds to a coalescer key: nothing without one (the key of before), so requests with different ranges
+        do not share a batch"""
+        return () if prange is None else (prange,)
+
+    @staticmethod
+    def _range_kw(prange):
+        return {} if prange is None else {"pitch_range": prange}
+
     def run(self, output_names, input_feed, run_options=None):
         """Extension feed "vits.sample_rate" (next to "vits.seed"): output rate in Hz; the time axis of the output is then in output
         samples (include/vits_resample.h).  Extension feed "vits.marks": True -- the result list gets a second entry, token_ends int64
@@ -424,9 +437,10 @@ class VitsSession:
         loud = self._loudness(feed)
         pitch, formants = pitch_from_feed(self._lib, feed)  # ("vits.pitch": the audio shifted by that many semitones, behind the decoder)
         limit = self._limit(feed)  # ("vits.limit": the look-ahead peak limiter with the loudness gain, or alone; include/vits_limit.h)
+        prange = range_from_feed(self._lib, feed)  # ("vits.pitch_range": the intonation range; include/vits_intonation.h)
         n = self._coalescable(feed, ids)
         if n:
-            key = ("f32", 1.0, rate, marks, loud, pitch, formants, limit)
+            key = ("f32", 1.0, rate, marks, loud, pitch, formants, limit) + self._range_key(prange)
             res = self.coalescer.submit(key, np.ascontiguousarray(ids[:, :n], np.int64), int(sid[0]), int(seed), self._scales(feed))
             self.last_lengths = res[1]
             if marks:  # (the request's own tokens; columns beyond its length repeat the last end, as the C ABI pads them)
@@ -437,7 +451,7 @@ class VitsSession:
             noise_dp=feed.get("vits.noise_dp"), noise_prior=feed.get("vits.noise_prior"),
             forced_durations=feed.get("vits.forced_durations"), seed=int(seed), solo=bool(feed.get("vits.solo", False)),
             item_seeds=feed.get("vits.item_seeds"), bert=feed.get("bert"), sample_rate=rate, marks=marks, loudness=loud,
-            **self._pitch_kw(pitch, formants, limit), **self._prosody(feed), **self._contour(feed))
+            **self._pitch_kw(pitch, formants, limit), **self._prosody(feed), **self._contour(feed), **self._range_kw(prange))
         self.last_lengths = res[1]
         return [res[0][:, None, None, :], res[2]] if marks else [res[0][:, None, None, :]]
 
@@ -498,9 +512,10 @@ class VitsSession:
         loud = self._loudness(feed)
         pitch, formants = pitch_from_feed(self._lib, feed)
         limit = self._limit(feed)
+        prange = range_from_feed(self._lib, feed)
         n = self._coalescable(feed, ids)
         if n:
-            key = ("pcm", float(scale), rate, marks, loud, pitch, formants, limit)
+            key = ("pcm", float(scale), rate, marks, loud, pitch, formants, limit) + self._range_key(prange)
             res = self.coalescer.submit(key, np.ascontiguousarray(ids[:, :n], np.int64), int(sid[0]), int(seed), self._scales(feed))
             pcm, lengths = res[0], res[1]
             self.last_lengths = lengths
@@ -513,7 +528,7 @@ class VitsSession:
             pcm_scale=float(scale), noise_dp=feed.get("vits.noise_dp"), noise_prior=feed.get("vits.noise_prior"),
             forced_durations=feed.get("vits.forced_durations"), seed=int(seed), solo=bool(feed.get("vits.solo", False)),
             item_seeds=feed.get("vits.item_seeds"), bert=feed.get("bert"), sample_rate=rate, marks=marks, loudness=loud,
-            **self._pitch_kw(pitch, formants, limit), **self._prosody(feed), **self._contour(feed))
+            **self._pitch_kw(pitch, formants, limit), **self._prosody(feed), **self._contour(feed), **self._range_kw(prange))
         pcm, lengths = res[0], res[1]
         self.last_lengths = lengths
         if marks:
@@ -536,6 +551,9 @@ class VitsSession:
         if pitch_from_feed(self._lib, feed)[0] is not None:
             raise ValueError("a stream cannot be pitch-shifted: the phase recursion needs the frames before a chunk (run() / run_pcm16() "
                              "take \"vits.pitch\")")
+        if range_from_feed(self._lib, feed) is not None:
+            raise ValueError("a stream cannot take an intonation range: the median of the F0 track needs the whole utterance before the "
+                             "first chunk (run() / run_pcm16() take \"vits.pitch_range\")")
         if any(k in feed for k in _CONTOUR):
             raise ValueError("a stream cannot be contoured: the position recurrence and the phase recursion need the whole utterance before "
                              "the first chunk (run() / run_pcm16() take \"vits.token_pitch\" / \"vits.token_gain_db\")")

@@ -11,12 +11,13 @@ import numpy as np
 
 from .capi import VitsLib
 from .capi_stts import SttsModel
-from .outopts import limit_from_feed, loudness_from_feed, pitch_from_feed
+from .outopts import limit_from_feed, loudness_from_feed, pitch_from_feed, range_from_feed
 
 _INPUTS = ("input", "input_lengths", "scales", "sid", "bert", "phone_duration_extra")
 _EXT = ("vits.noise", "vits.seed", "vits.n_timesteps", "vits.sample_rate", "vits.denoiser_strength", "vits.denoiser_filter_length",
         "vits.marks", "vits.loudness", "vits.peak", "vits.peak_ceiling", "vits.pitch", "vits.pitch_formants",
-        "vits.limit", "vits.limit_lookahead_ms", "vits.limit_release_ms", "vits.token_pitch", "vits.token_gain_db")
+        "vits.limit", "vits.limit_lookahead_ms", "vits.limit_release_ms", "vits.token_pitch", "vits.token_gain_db",
+        "vits.pitch_range")
 
 
 class SttsSession:
@@ -110,6 +111,9 @@ class SttsSession:
         for k, name in (("vits.token_pitch", "token_pitch"), ("vits.token_gain_db", "token_gain_db")):
             if k in feed:
                 kw[name] = np.asarray(feed[k], np.float32).reshape(-1)
+        r = range_from_feed(self._lib, feed)  # ("vits.pitch_range": the intonation range, include/vits_intonation.h)
+        if r is not None:
+            kw["pitch_range"] = r
         return kw
 
     def normalize(self, audio, lengths, sample_rate, spec, limit=None):
@@ -169,6 +173,9 @@ class SttsSession:
         if self._limit(feed) is not None:
             raise ValueError("a stream cannot be limited: the limiter's look-ahead and its loudness passes need the whole utterance before the "
                              "first chunk (run() takes \"vits.limit\")")
+        if range_from_feed(self._lib, feed) is not None:
+            raise ValueError("a stream cannot take an intonation range: the median of the F0 track needs the whole utterance before the "
+                             "first chunk (run() takes \"vits.pitch_range\")")
         if self._pitch(feed):
             raise ValueError("a stream cannot be pitch-shifted: the phase recursion needs the frames before a chunk (run() takes "
                              "\"vits.pitch\")")

@@ -8,6 +8,9 @@
         rate    N%  (100% = unchanged)               or  x-slow 0.5, slow 0.75, medium 1.0, fast 1.5, x-fast 2.0
         pitch   +Nst / -Nst, +N% / -N% (12 log2(1 + N / 100) semitones)  or  x-low -6, low -3, medium 0, high +3, x-high +6 semitones
         volume  +NdB / -NdB                          or  x-soft -12, soft -6, medium 0, loud +6, x-loud +12 dB
+        range   N% / +N% / -N% (100% = +0% = unchanged)  or  x-low 0.25, low 0.5, medium / default 1, high 1.5, x-high 2: the intonation
+                range of include/vits_intonation.h, one value per utterance -- accepted only on a prosody element that covers every
+                word of the document (`pitch_range` of the plan); a range for some of the words is a ValueError
     <mark name="..."/>         with marks=True, marks.named[name] = the start sample of the next word, or the end of the audio
 
 Anything else is a ValueError that names it, raised before a model is touched: another element, an unknown attribute, a tag that starts
@@ -17,29 +20,34 @@ import math
 import re
 import xml.etree.ElementTree as ET
 
-from .capi import CONTOUR_DB, PITCH_MAX_SEMITONES, PROSODY_MAX_TOKEN_SCALE
+from .capi import CONTOUR_DB, INTONATION_MAX_RANGE, PITCH_MAX_SEMITONES, PROSODY_MAX_TOKEN_SCALE
 from .marks import _SPLIT
 
 RATE_LABELS = {"x-slow": 0.5, "slow": 0.75, "medium": 1.0, "fast": 1.5, "x-fast": 2.0}
 PITCH_LABELS = {"x-low": -6.0, "low": -3.0, "medium": 0.0, "high": 3.0, "x-high": 6.0}
 VOLUME_LABELS = {"x-soft": -12.0, "soft": -6.0, "medium": 0.0, "loud": 6.0, "x-loud": 12.0}
+RANGE_LABELS = {"x-low": 0.25, "low": 0.5, "medium": 1.0, "high": 1.5, "x-high": 2.0, "default": 1.0}
 
 _NUM = r"[0-9]+(?:\.[0-9]*)?|\.[0-9]+"
 _XML_LANG = "{http://www.w3.org/XML/1998/namespace}lang"
 _ATTRS = {"speak": {"version", _XML_LANG}, "p": {_XML_LANG}, "s": {_XML_LANG}, "sub": {"alias"}, "break": {"time"},
-          "prosody": {"rate", "pitch", "volume"}, "mark": {"name"}}
+          "prosody": {"rate", "pitch", "volume", "range"}, "mark": {"name"}}
 
 
 class Plan:
     """What a document asks for: text, word_rates {word: rate}, pauses {word: seconds}, word_pitch {word: semitones}, word_gains
-    {word: dB} (the keywords of Synth.synth_audio; empty ones are None) and marks [(name, index of the next word)]."""
+    {word: dB}, pitch_range (the keywords of Synth.synth_audio; empty ones are None) and marks [(name, index of the next word)]."""
 
-    def __init__(self, text, word_rates, pauses, word_pitch, word_gains, marks):
+    def __init__(self, text, word_rates, pauses, word_pitch, word_gains, marks, pitch_range=None):
         self.text, self.word_rates, self.pauses, self.word_pitch, self.word_gains, self.marks = text, word_rates, pauses, word_pitch, word_gains, marks
+        self.pitch_range = pitch_range
 
     def keywords(self):
-        return {k: v for k, v in (("word_rates", self.word_rates), ("pauses", self.pauses), ("word_pitch", self.word_pitch),
-                                  ("word_gains", self.word_gains)) if v}
+        kw = {k: v for k, v in (("word_rates", self.word_rates), ("pauses", self.pauses), ("word_pitch", self.word_pitch),
+                                ("word_gains", self.word_gains)) if v}
+        if self.pitch_range is not None:
+            kw["pitch_range"] = self.pitch_range
+        return kw
 
 
 def count_words(text):
@@ -85,6 +93,20 @@ def parse_volume(v):
     return float(m.group(2)) * (1.0 if m.group(1) == "+" else -1.0)
 
 
+def parse_range(v):
+    v = v.strip()
+    if v in RANGE_LABELS:
+        return RANGE_LABELS[v]
+    m = re.fullmatch(rf"([+-]?)({_NUM})%", v)
+    if not m:
+        raise ValueError(f"prosody range={v!r}: '50%', '+20%' or one of {', '.join(RANGE_LABELS)}")
+    x = float(m.group(2))
+    r = x / 100.0 if m.group(1) == "" else 1.0 + x / 100.0 if m.group(1) == "+" else 1.0 - x / 100.0
+    if not 0.0 <= r <= INTONATION_MAX_RANGE:
+        raise ValueError(f"prosody range={v!r}: {r:g} times the voice's own range is outside [0, {INTONATION_MAX_RANGE:g}]")
+    return r
+
+
 def parse_time(v):
     m = re.fullmatch(rf"({_NUM})(ms|s)", v.strip())
     if not m:
@@ -108,6 +130,7 @@ def parse(ssml):
     runs = []        # (start, end, rate, semitones, dB) per piece under a prosody element
     edges = []       # (position in the text, tag) of every tag boundary
     breaks, marks = [], []
+    ranges = []      # (start, end, r, raw value) of every prosody element with a range
 
     def pos():
         return sum(len(t) for t in text)
@@ -157,10 +180,13 @@ def parse(ssml):
                 if "volume" in el.attrib:
                     g += parse_volume(el.attrib["volume"])
                 ctx = (r, s, g)
+            a0 = pos()
             say(el.text, ctx)
             for child in el:
                 walk(child, ctx)
                 say(child.tail, ctx)
+            if tag == "prosody" and "range" in el.attrib:
+                ranges.append((a0, pos(), parse_range(el.attrib["range"]), el.attrib["range"]))
         if el is not root:
             edges.append((pos(), tag))
 
@@ -185,10 +211,18 @@ def parse(ssml):
                 if not CONTOUR_DB[0] <= g <= CONTOUR_DB[1]:
                     raise ValueError(f"prosody volume of word {w} composes to {g:g} dB: outside [{CONTOUR_DB[0]:g}, {CONTOUR_DB[1]:g}]")
                 word_gains[w] = g
+    pitch_range = None
+    for a, b, r, raw in ranges:  # one intonation range per utterance: the element must hold every word
+        if words_before(a) != 0 or words_before(b) != count_words(full):
+            raise ValueError(f"prosody range={raw!r} covers words {words_before(a)} to {words_before(b) - 1} of {count_words(full)}: the "
+                             "intonation range is one value per utterance, so `range` is accepted only on a prosody element around every word")
+        pitch_range = r if pitch_range is None else pitch_range * r
+        if not 0.0 <= pitch_range <= INTONATION_MAX_RANGE:
+            raise ValueError(f"prosody range composes to {pitch_range:g}: outside [0, {INTONATION_MAX_RANGE:g}]")
     for p, sec in breaks:
         w = words_before(p) - 1
         if w < 0:
             raise ValueError("<break> in front of the first word: a pause follows a word")
         pauses[w] = pauses.get(w, 0.0) + sec
     return Plan(full.strip(), word_rates or None, pauses or None, word_pitch or None, word_gains or None,
-                [(name, words_before(p)) for name, p in marks])
+                [(name, words_before(p)) for name, p in marks], pitch_range)

@@ -276,6 +276,43 @@ class Synth:
             args["vits.pitch_formants"] = True
         return True
 
+    def _range(self, args, pitch_range):
+        """Intonation range of the request (include/vits_intonation.h; both voice families): `pitch_range` r in [0, 4], defaulting to the
+        config key inference.pitch_range; it goes into the feed as "vits.pitch_range".  The engine tracks the F0 of the finished waveform
+        on the device and scales its movement about the utterance's own median by r: 0 is a monotone, 0.5 a calm reading, 1.5 a lively
+        one.  None and no config key, or a value within 0.0005 of 1 = off, the request as it was.  Duration, sample counts and marks do
+        not change; a value out of range is a ValueError naming it."""
+        from .capi import range_spec
+
+        if pitch_range is None:
+            pitch_range = self.model.config.get("inference", {}).get("pitch_range")
+        r = range_spec(pitch_range)
+        if r is None:
+            return False
+        args["vits.pitch_range"] = r
+        return True
+
+    def measure_pitch(self, audio, rate=None):
+        """(hz, median_hz) of one utterance: hz float32 [1 + n // 256], the F0 of every analysis frame of include/vits_intonation.h (hop
+        256, 0 where unvoiced) as the engine's own tracker finds it (vits_op_f0_track, the track `pitch_range` scales), and the median of
+        the voiced frames (0.0 without one).  audio: int16 PCM or float; rate: its sample rate in Hz (default: the voice's own), tracked at
+        that rate if the tracker takes it (8 to 32 kHz)."""
+        a = np.asarray(audio)
+        x = a.astype(np.float32) / np.float32(32767.0) if a.dtype == np.int16 else a.astype(np.float32)
+        x = x.reshape(1, -1)
+        sess = self.model.onnx
+        lib = getattr(sess, "_lib", None)
+        if lib is None or not getattr(lib, "has_intonation", False):
+            raise NotImplementedError("this session type has no F0 tracker (include/vits_intonation.h)")
+        if x.shape[1] == 0:
+            return np.zeros(1, np.float32), 0.0
+        dev = getattr(getattr(sess, "_vocoder", None) or getattr(sess, "_model", None), "device", 0)
+        cents = lib.op_f0_track(x, [x.shape[1]], int(rate or self.native_rate()), device=dev)[0]
+        voiced = cents > 0
+        hz = np.where(voiced, 27.5 * 2.0 ** (cents / 1200.0), 0.0).astype(np.float32)
+        med = float(27.5 * 2.0 ** (np.sort(cents[voiced])[(int(voiced.sum()) - 1) // 2] / 1200.0)) if voiced.any() else 0.0
+        return hz, med
+
     def measure_loudness(self, audio, rate=None, true_peak=False):
         """(lufs, peak) of one utterance: BS.1770 integrated loudness (-inf for silence) and max |sample| in full-scale units, measured
         by the engine's own kernels (vits_op_loudness).  audio: int16 PCM (scaled by 1 / 32767, the conversion's own factor) or float;
@@ -402,8 +439,9 @@ class Synth:
     def synth_audio(self, text, speaker_id=0, noise_level=None, speech_rate=None, duration_noise_level=None, scale=None, sample_rate=None,
                     denoiser_strength=None, marks=False, loudness=None, peak=None, peak_ceiling=None, pitch=None,
                     preserve_formants=None, limit=None, limit_lookahead_ms=None, limit_release_ms=None, word_rates=None, pauses=None,
-                    duration=None, word_pitch=None, word_gains=None):
-        """word_pitch / word_gains (extension): per-word semitones and decibels, see _contour.
+                    duration=None, word_pitch=None, word_gains=None, pitch_range=None):
+        """pitch_range (extension): the intonation range, 0 (monotone) to 4, 1 = unchanged, see _range.
+        word_pitch / word_gains (extension): per-word semitones and decibels, see _contour.
         word_rates / pauses / duration (extension): per-word tempo, pauses behind words and the length of the whole utterance in
         seconds, see _prosody.
         limit / limit_lookahead_ms / limit_release_ms (extension): the look-ahead peak limiter, see _limit; peak_ceiling is then its
@@ -423,6 +461,7 @@ class Synth:
         self._loudness(args, loudness, peak, peak_ceiling)
         self._limit(args, limit, peak_ceiling, limit_lookahead_ms, limit_release_ms)
         self._pitch(args, pitch, preserve_formants)
+        self._range(args, pitch_range)
         rate = self.native_rate()
         if sample_rate and int(sample_rate) != rate:
             rate = int(sample_rate)
@@ -461,13 +500,14 @@ class Synth:
     def synth_ssml(self, ssml, **kw):
         """synth_audio for an SSML document (vosk_tts_amd/ssml.py: speak, p, s, sub, break, prosody rate / pitch / volume, mark): the
         document becomes the text and the word_rates / pauses / word_pitch / word_gains keywords, so those four are not accepted next
-        to it; every other keyword of synth_audio is.  With marks=True the returned marks carry `named`: {mark name: start sample of the
+        to it; every other keyword of synth_audio is (a `range` on a prosody element that covers the whole document becomes pitch_range,
+        and a pitch_range keyword next to it is refused the same way).  With marks=True the returned marks carry `named`: {mark name: start sample of the
         next word, or the end of the audio behind the last one}.  Whatever the subset does not cover is a ValueError before the model
         is touched; on a multistream voice rate and break raise that family's own refusal."""
         from . import ssml as S
 
         plan = S.parse(ssml)
-        for k in ("word_rates", "pauses", "word_pitch", "word_gains"):
+        for k in ("word_rates", "pauses", "word_pitch", "word_gains") + (("pitch_range",) if plan.pitch_range is not None else ()):
             if kw.get(k) is not None:
                 raise ValueError(f"synth_ssml takes {k} from the document's markup, not as a keyword")
         res = self.synth_audio(plan.text, **dict(kw, **plan.keywords()))
@@ -478,8 +518,10 @@ class Synth:
 
     def synth_stream(self, text, speaker_id=0, noise_level=None, speech_rate=None, duration_noise_level=None, scale=None,
                      chunk_frames=64, sample_rate=None, denoiser_strength=None, on_marks=None, loudness=None, peak=None, peak_ceiling=None,
-                     pitch=None, limit=None, word_rates=None, pauses=None, duration=None):
+                     pitch=None, limit=None, word_rates=None, pauses=None, duration=None, pitch_range=None):
         """word_rates / pauses / duration: as for synth_audio (the stream's open runs the controlled regulator; chunking is untouched).
+        pitch_range: ValueError -- the median of the F0 track needs the whole utterance (a voice whose config names
+        inference.pitch_range streams with the range it has).
         limit: ValueError -- the limiter's look-ahead and its loudness passes need the whole utterance (a voice whose config names
         inference.limit streams unlimited).
         pitch: ValueError -- the phase recursion needs the frames before a chunk (a voice whose config names inference.pitch streams
@@ -496,6 +538,9 @@ class Synth:
         if limit is not None:
             raise ValueError("synth_stream cannot limit: the limiter's look-ahead and its loudness passes need the whole utterance before the "
                              "first chunk (synth_audio takes limit=)")
+        if pitch_range is not None:
+            raise ValueError("synth_stream cannot change the intonation range: the median of the F0 track needs the whole utterance before "
+                             "the first chunk (synth_audio takes pitch_range=)")
         if pitch is not None:
             raise ValueError("synth_stream cannot shift the pitch: the phase recursion needs the frames before a chunk, and its state is "
                              "not carried across chunks (synth_audio takes pitch=)")
@@ -518,13 +563,14 @@ class Synth:
     def synth(self, text, oname, speaker_id=0, noise_level=None, speech_rate=None, duration_noise_level=None, scale=None, sample_rate=None,
               denoiser_strength=None, marks=False, loudness=None, peak=None, peak_ceiling=None, pitch=None, preserve_formants=None,
               limit=None, limit_lookahead_ms=None, limit_release_ms=None, word_rates=None, pauses=None, duration=None, word_pitch=None,
-              word_gains=None):
+              word_gains=None, pitch_range=None):
         """marks=True: the utterance's marks.SpeechMarks are returned (the default returns None, as the reference does)"""
         audio = self.synth_audio(text, speaker_id, noise_level, speech_rate, duration_noise_level, scale, sample_rate, denoiser_strength, marks=marks,
                                  loudness=loudness, peak=peak, peak_ceiling=peak_ceiling, pitch=pitch,
                                  preserve_formants=preserve_formants, limit=limit, limit_lookahead_ms=limit_lookahead_ms,
                                  limit_release_ms=limit_release_ms, **{k: v for k, v in (("word_rates", word_rates), ("pauses", pauses), ("duration", duration),
-                                                                                           ("word_pitch", word_pitch), ("word_gains", word_gains))
+                                                                                           ("word_pitch", word_pitch), ("word_gains", word_gains),
+                                                                                           ("pitch_range", pitch_range))
                                                                       if v is not None})
         sm = None
         if marks:
