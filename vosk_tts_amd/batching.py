@@ -214,6 +214,41 @@ class MultiDeviceSynth:
                 for r, idx in enumerate(shards)]
         return with_marks(scatter_results(n, [idx for idx in shards if idx], [f.result() for f in futs if f is not None]))
 
+    def synth_documents(self, docs, seeds=None, **kw):
+        """docs: a list of documents, each a string or a list of document.Segment -> a list of Synth.synth_document's results, in request
+        order (marks=True: (audio, SpeechMarks) each).  A document goes whole to ONE replica -- its join and the stages behind it need every
+        segment on one device -- and the documents are spread over the replicas by their total token counts (plan_shards; a cheap
+        phoneme count, no BERT needed).  `seeds`: one noise seed per document (default: a running counter; segment b draws seed + b);
+        **kw: the keywords of Synth.synth_document, one setting for all."""
+        from . import document as D
+
+        n = len(docs)
+        if n == 0:
+            return []
+        s0 = self.synths[0]
+        est = []
+        for d in docs:
+            segs = D.split(d) if isinstance(d, str) else list(d)
+            est.append(sum(len(s0.phonemize(s0.normalize(s.text).replace("_", " "))) for s in segs))
+        if seeds is None:
+            with self._lock:
+                seeds = [self._seed + 1 + 1000 * i for i in range(n)]
+                self._seed += 1000 * n
+        seeds = list(seeds)
+        if len(seeds) != n:
+            raise ValueError(f"seeds: one per document ({n})")
+        shards = plan_shards(est, len(self.devices))
+
+        def run(r, idx):
+            out = []
+            for i in idx:
+                with self._replica_locks[r]:
+                    out.append(self.synths[r].synth_document(docs[i], seed=seeds[i], **kw))
+            return out
+
+        futs = [self._pool.submit(run, r, idx) if idx else None for r, idx in enumerate(shards)]
+        return scatter_results(n, [idx for idx in shards if idx], [f.result() for f in futs if f is not None])
+
     def _call_params(self, n, speaker_ids, noise_level, speech_rate, duration_noise_level, scale, seeds):
         """runtime defaults (synth.py:50-56,106) and per-request speaker ids / seeds.  noise_level / speech_rate / duration_noise_level:
         one value, or one per request -- `scales` is then float32 [n, 3], every request's own triple (the reference server hands every

@@ -341,6 +341,45 @@ class VitsError(RuntimeError):
         self.code = code
 
 
+class Document(ctypes.Structure):
+    """mirror of `struct vits_document` (include/vits_document.h)"""
+
+    _fields_ = [
+        ("lead_frames", ctypes.c_int32),
+        ("gap_frames", c_i32p),
+        ("fade_samples", ctypes.c_int32),
+        ("trim_db", ctypes.c_float),
+        ("trim_keep_frames", ctypes.c_int32),
+        ("out_seg_start", c_i64p),
+        ("out_seg_end", c_i64p),
+        ("out_trim", c_i32p),
+    ]
+
+
+def document_struct(B, lead_frames=0, gap_frames=None, fade_samples=0, trim_db=None, trim_keep_frames=0, outputs=True):
+    """-> (Document, keep, out): the controls of include/vits_document.h for B segments.  gap_frames: None, one int for every segment or
+    [B]; trim_db None / 0 = off.  out (with outputs): the arrays the call fills, "seg_start" / "seg_end" int64 [B], "trim" int32 [B, 2].
+    Values are passed as they are: the library refuses what the header refuses."""
+    d = Document()
+    keep, out = [], {}
+    d.lead_frames = int(lead_frames)
+    if gap_frames is not None:
+        g = _i32(np.broadcast_to(np.asarray(gap_frames), (B,)) if np.ndim(gap_frames) == 0 else gap_frames)
+        if g.shape != (B,):
+            raise ValueError(f"gap_frames must be one value or [B = {B}] (got {g.shape})")
+        keep.append(g)
+        d.gap_frames = _p(g, c_i32p)
+    d.fade_samples = int(fade_samples)
+    d.trim_db = 0.0 if trim_db is None else float(trim_db)
+    d.trim_keep_frames = int(trim_keep_frames)
+    if outputs:
+        out = {"seg_start": np.zeros(B, np.int64), "seg_end": np.zeros(B, np.int64), "trim": np.zeros((B, 2), np.int32)}
+        d.out_seg_start = _p(out["seg_start"], c_i64p)
+        d.out_seg_end = _p(out["seg_end"], c_i64p)
+        d.out_trim = _p(out["trim"], c_i32p)
+    return d, keep, out
+
+
 def _f32(a):
     return np.ascontiguousarray(a, dtype=np.float32)
 
@@ -412,6 +451,7 @@ class VitsLib:
         self.has_limit = False
         self.has_prosody = False
         self.has_contour = False
+        self.has_document = False
         self.has_intonation = False
         if self.is_device:
             c_i16p = ctypes.POINTER(ctypes.c_int16)
@@ -519,6 +559,17 @@ class VitsLib:
                 f("op_f0_track").argtypes = [ctypes.c_int, c_f32p, c_i64p, ctypes.c_int32, ctypes.c_int64, ctypes.c_int32, c_i32p]
                 f("op_intonation").argtypes = door + [c_f32p]
                 f("op_intonation_stretch").argtypes = door + [c_f32p, c_i64p, c_i32p]
+            # include/vits_document.h: documents (the two joined synthesize calls and the join's own door)
+            self.has_document = self.has("op_document_join")
+            if self.has_document:
+                f("synthesize_document").argtypes = [ctypes.c_void_p, c_i64p, c_i64p, ctypes.c_int32, ctypes.c_int32, c_f32p, c_i64p,
+                                                     ctypes.POINTER(SynthOpts), ctypes.POINTER(Document), ctypes.c_int32, ctypes.POINTER(c_f32p),
+                                                     c_i64p, c_i64p]
+                f("synthesize_document_pcm16").argtypes = [ctypes.c_void_p, c_i64p, c_i64p, ctypes.c_int32, ctypes.c_int32, c_f32p, c_i64p,
+                                                           ctypes.POINTER(SynthOpts), ctypes.POINTER(Document), ctypes.c_float, ctypes.c_int32,
+                                                           ctypes.POINTER(c_i16p), c_i64p, c_i64p]
+                f("op_document_join").argtypes = [ctypes.c_int, c_f32p, c_i64p, ctypes.c_int32, ctypes.c_int64, ctypes.c_int32,
+                                                  ctypes.POINTER(Document), c_f32p, ctypes.c_int64, c_i64p, c_i32p, c_i32p]
             if self.has("debug_clock_probe"):
                 f("debug_clock_probe").argtypes = [ctypes.c_int, ctypes.c_int32, ctypes.POINTER(ctypes.c_double), ctypes.c_int32]
 
@@ -777,6 +828,37 @@ class VitsLib:
         return self._items_door(_door, x, lengths, device, (float(semitones),), outs)
 
     # ---- per-token contours (include/vits_contour.h) ----------------------------
+    def _need_document(self):
+        if not self.has_document:
+            raise VitsError(4, "this backend has no documents (include/vits_document.h)")
+
+    def op_document_join(self, x, len_frames, hop, y=None, y_cap=None, device=0, **doc):
+        """vits_op_document_join: x float32 [B, N], len_frames [B] -> (y float32 [y_cap], F, start int32 [B], trim int32 [B, 2]).  y: the
+        buffer the join writes into (its samples at and beyond F * hop come back as they went), default NaN-filled, of y_cap samples
+        (default: the untrimmed bound).  **doc: the controls of document_struct()."""
+        self._need_document()
+        x = _f32(x)
+        if x.ndim != 2:
+            raise ValueError("x must be [B, N]")
+        B, N = x.shape
+        lf = _i64(len_frames).reshape(-1)
+        if lf.shape != (B,):
+            raise ValueError("len_frames must be [B]")
+        d, keep, _ = document_struct(B, outputs=False, **doc)
+        if y is None:
+            if y_cap is None:
+                g = keep[0] if keep else np.zeros(B, np.int32)
+                y_cap = (int(d.lead_frames) + int(lf.sum()) + int(g.sum())) * int(hop)
+            y = np.full(max(int(y_cap), 0), np.nan, np.float32)
+        else:
+            y = _f32(y).copy()
+        F = ctypes.c_int64()
+        start = np.zeros(B, np.int32)
+        trim = np.zeros((B, 2), np.int32)
+        self.check(self._fn("op_document_join")(device, _p(x, c_f32p), _p(lf, c_i64p), B, N, int(hop), ctypes.byref(d), _p(y, c_f32p), y.shape[0],
+                                                ctypes.byref(F), _p(start, c_i32p), _p(trim, c_i32p)))
+        return y, int(F.value), start, trim
+
     def _need_contour(self):
         if not self.has_contour:
             raise VitsError(4, "this backend has no pitch / volume contours (include/vits_contour.h)")
@@ -1131,6 +1213,48 @@ class VitsModel:
             self.lib._fn("free_pcm16")(out)
         res = (pcm, olen, ends) if marks else (pcm, olen)
         return res + (pros_out.get("fit_ratio", np.ones(B, np.float32)),) if fit_ratio else res
+
+    def synthesize_document(self, ids, lengths, scales, sid, pcm=False, pcm_scale=1.0, lead_frames=0, gap_frames=None, fade_samples=0,
+                            trim_db=None, trim_keep_frames=0, marks=False, seed=0, max_frames=0, item_seeds=None, bert=None, sample_rate=None,
+                            loudness=None, loudness_out=None, pitch=None, preserve_formants=False, limit=None, item_scales=None,
+                            token_length_scale=None, token_pause=None, fit_frames=None, token_pitch=None, token_gain_db=None, pitch_range=None,
+                            forced_durations=None):
+        """vits_synthesize_document / _pcm16 (include/vits_document.h): the B items of one SOLO batch call joined on the device into one
+        piece of audio, in front of the resampler, the loudness stage, the limiter and the int16 conversion.  Returns (audio float32 or
+        int16 [S], info): info["seg_start"] / ["seg_end"] int64 [B] in output samples, info["trim"] int32 [B, 2] frames, and with
+        marks=True info["token_ends"] int64 [B, T_x].  The per-item keywords are those of synthesize; loudness_out receives ONE value per
+        key, of the whole document."""
+        self.lib._need_document()
+        ids = _i64(ids)
+        B, Tx = ids.shape
+        lengths = _i64(lengths); sid = _i64(sid); scales = _f32(scales)
+        if lengths.shape != (B,) or sid.shape != (B,) or scales.shape != (3,):
+            raise ValueError("bad feed shapes")
+        pros_out = {}
+        opts, keep = self._opts(B, Tx, None, None, forced_durations, seed, max_frames, True, item_seeds, bert, loudness, loudness_out,
+                                pitch, preserve_formants, limit, prosody_arrays(B, Tx, item_scales, token_length_scale, token_pause, fit_frames),
+                                pros_out, contour_arrays(B, Tx, token_pitch, token_gain_db, lengths, pitch_spec(pitch)), pitch_range)
+        d, dkeep, info = document_struct(B, lead_frames, gap_frames, fade_samples, trim_db, trim_keep_frames)
+        rate = self._rate(sample_rate)
+        ends = np.zeros((B, Tx), np.int64) if marks else None
+        ns = ctypes.c_int64()
+        head = (self._h, _p(ids, c_i64p), _p(lengths, c_i64p), B, Tx, _p(scales, c_f32p), _p(sid, c_i64p), ctypes.byref(opts), ctypes.byref(d))
+        if pcm:
+            out = ctypes.POINTER(ctypes.c_int16)()
+            self.lib.check(self.lib._fn("synthesize_document_pcm16")(*head, float(pcm_scale), rate, ctypes.byref(out), ctypes.byref(ns), _p(ends, c_i64p)))
+        else:
+            out = c_f32p()
+            self.lib.check(self.lib._fn("synthesize_document")(*head, rate, ctypes.byref(out), ctypes.byref(ns), _p(ends, c_i64p)))
+        try:
+            audio = np.ctypeslib.as_array(out, shape=(ns.value,)).copy() if ns.value else np.zeros(0, np.int16 if pcm else np.float32)
+        finally:
+            self.lib._fn("free_pcm16" if pcm else "free_output")(out)
+        if marks:
+            info["token_ends"] = ends
+        if loudness_out:  # (one item behind the join)
+            for k in list(loudness_out):
+                loudness_out[k] = np.asarray(loudness_out[k])[:1]
+        return audio, info
 
     def stream(self, ids, scales, sid, chunk_frames=64, noise_dp=None, noise_prior=None, forced_durations=None, seed=0, bert=None,
                sample_rate=None, on_marks=None, loudness=None, pitch=None, limit=None, item_scales=None, token_length_scale=None,

@@ -99,6 +99,14 @@ class SttsModel:
                                               ctypes.c_int32, ctypes.POINTER(c_f32p), c_i64p, ctypes.POINTER(c_f32p), c_i64p, c_i64p]
             f("synthesize_batch_marks").argtypes = [vp, c_i64p, c_i64p, ctypes.c_int32, ctypes.c_int32, c_f32p, c_i64p, c_f32p, c_f32p,
                                                     ctypes.POINTER(SttsOpts), ctypes.c_int32, ctypes.POINTER(c_f32p), c_i64p, c_i64p, c_i64p]
+        # include/vits_document.h: the batch call joined into one piece of audio
+        self.has_document = hasattr(L, self.prefix + "synthesize_document")
+        if self.has_document:
+            from .capi import Document
+
+            f("synthesize_document").argtypes = [vp, c_i64p, c_i64p, ctypes.c_int32, ctypes.c_int32, c_f32p, c_i64p, c_f32p, c_f32p,
+                                                 ctypes.POINTER(SttsOpts), ctypes.POINTER(Document), ctypes.c_int32, ctypes.POINTER(c_f32p),
+                                                 c_i64p, c_i64p]
         f("stage_encoder").argtypes = [vp, c_i64p, c_i64p, ctypes.c_int32, ctypes.c_int32, c_i64p, c_f32p, c_f32p, c_f32p]
         f("stage_durations").argtypes = [vp, c_f32p, ctypes.c_int32, ctypes.c_int32, ctypes.c_float, c_f32p, c_i32p, c_i64p]
         f("stage_estimator").argtypes = [vp, c_f32p, c_f32p, c_i64p, ctypes.c_int32, ctypes.c_int32, ctypes.c_float, c_f32p, c_f32p]
@@ -319,27 +327,10 @@ class SttsModel:
             self._need_marks()
         elif sample_rate:
             raise ValueError("sample_rate is an argument of the marks call (SttsSession.resample serves the call without marks)")
-        ids = _i64(ids); lengths = _i64(lengths); sid = _i64(sid); scales = _f32(scales)
-        B, five, T = ids.shape
-        b = None if bert is None else _f32(bert)
-        p = None if phone_duration_extra is None else _f32(phone_duration_extra)
-        con = contour_arrays(B, T, token_pitch, token_gain_db, lengths, pitch_spec(pitch))
-        opts = self._opts_for(loudness, pitch, preserve_formants, limit, con, range_spec(pitch_range))
-        opts.seed = seed; opts.n_timesteps = n_timesteps
-        self._denoise(opts, denoiser_strength, denoiser_filter_length)
-        keep = []
-        set_contour(opts, keep, con, STTS_FLAG_CONTOUR)
-        self._loudness(opts, keep, loudness, B, loudness_out)  # (per-item gains; loudness_out as for synthesize, [B])
-        self._limit(opts, keep, limit, B, loudness_out)
-        if item_seeds is not None:
-            sd = np.ascontiguousarray(item_seeds, dtype=np.uint64)
-            if sd.shape != (B,):
-                raise ValueError("item_seeds must be [B]")
-            opts.item_seeds = sd.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64))
-            opts.flags |= STTS_FLAG_ITEM_SEEDS  # (the trailing field is only read under this flag: include/stts_mi355.h)
+        B, T, head, keep = self._batch_head(ids, lengths, scales, sid, bert, phone_duration_extra, seed, n_timesteps, item_seeds, denoiser_strength,
+                                            denoiser_filter_length, loudness, loudness_out, pitch, preserve_formants, limit, token_pitch,
+                                            token_gain_db, pitch_range)
         au = c_f32p(); ns = ctypes.c_int64(); ol = np.zeros(B, np.int64)
-        head = (self._h, _p(ids, c_i64p), _p(lengths, c_i64p), B, T, _p(scales, c_f32p), _p(sid, c_i64p),
-                None if b is None else _p(b, c_f32p), None if p is None else _p(p, c_f32p), ctypes.byref(opts))
         ends = np.zeros((B, T), np.int64) if marks else None
         if marks:
             self.check(self._fn("synthesize_batch_marks")(*head, int(sample_rate or 0), ctypes.byref(au), ctypes.byref(ns), _p(ol, c_i64p),
@@ -349,6 +340,59 @@ class SttsModel:
         audio = np.ctypeslib.as_array(au, shape=(B, ns.value)).copy()
         self.vlib._fn("free_output")(au)
         return (audio, ol, ends) if marks else (audio, ol)
+
+    def _batch_head(self, ids, lengths, scales, sid, bert, phone_duration_extra, seed, n_timesteps, item_seeds, denoiser_strength,
+                    denoiser_filter_length, loudness, loudness_out, pitch, preserve_formants, limit, token_pitch, token_gain_db, pitch_range,
+                    results=None):
+        """the leading arguments of the batch entry points -> (B, T, head, keep); results: how many result values the loudness / limiter
+        outputs hold (default B; 1 for a document)"""
+        ids = _i64(ids); lengths = _i64(lengths); sid = _i64(sid); scales = _f32(scales)
+        B, five, T = ids.shape
+        b = None if bert is None else _f32(bert)
+        p = None if phone_duration_extra is None else _f32(phone_duration_extra)
+        con = contour_arrays(B, T, token_pitch, token_gain_db, lengths, pitch_spec(pitch))
+        opts = self._opts_for(loudness, pitch, preserve_formants, limit, con, range_spec(pitch_range))
+        opts.seed = seed; opts.n_timesteps = n_timesteps
+        self._denoise(opts, denoiser_strength, denoiser_filter_length)
+        keep = [ids, lengths, sid, scales, b, p, opts]
+        set_contour(opts, keep, con, STTS_FLAG_CONTOUR)
+        self._loudness(opts, keep, loudness, results or B, loudness_out)  # (per-item gains; loudness_out as for synthesize, [B])
+        self._limit(opts, keep, limit, results or B, loudness_out)
+        if item_seeds is not None:
+            sd = np.ascontiguousarray(item_seeds, dtype=np.uint64)
+            if sd.shape != (B,):
+                raise ValueError("item_seeds must be [B]")
+            keep.append(sd)
+            opts.item_seeds = sd.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64))
+            opts.flags |= STTS_FLAG_ITEM_SEEDS  # (the trailing field is only read under this flag: include/stts_mi355.h)
+        head = (self._h, _p(ids, c_i64p), _p(lengths, c_i64p), B, T, _p(scales, c_f32p), _p(sid, c_i64p),
+                None if b is None else _p(b, c_f32p), None if p is None else _p(p, c_f32p), ctypes.byref(opts))
+        return B, T, head, keep
+
+    def synthesize_document(self, ids, lengths, scales, sid, bert=None, phone_duration_extra=None, seed=0, n_timesteps=0, item_seeds=None,
+                            denoiser_strength=None, denoiser_filter_length=0, marks=False, sample_rate=None, loudness=None, loudness_out=None,
+                            pitch=None, preserve_formants=False, limit=None, token_pitch=None, token_gain_db=None, pitch_range=None,
+                            lead_frames=0, gap_frames=None, fade_samples=0, trim_db=None, trim_keep_frames=0):
+        """stts_synthesize_document (include/vits_document.h): the items of synthesize_batch joined into one piece of audio behind the
+        pitch stage, in front of the resampler and the loudness / limiter stage, which see one item.  Returns (audio float32 [S], info):
+        info["seg_start"] / ["seg_end"] int64 [B] in output samples, info["trim"] int32 [B, 2] frames, and with marks=True
+        info["token_ends"] int64 [B, T].  The other keywords are those of synthesize_batch; loudness_out receives one value per key."""
+        from .capi import document_struct
+
+        if not self.has_document:
+            raise VitsError(4, "this backend has no documents (include/vits_document.h)")
+        B, T, head, keep = self._batch_head(ids, lengths, scales, sid, bert, phone_duration_extra, seed, n_timesteps, item_seeds, denoiser_strength,
+                                            denoiser_filter_length, loudness, loudness_out, pitch, preserve_formants, limit, token_pitch,
+                                            token_gain_db, pitch_range, results=1)
+        d, dkeep, info = document_struct(B, lead_frames, gap_frames, fade_samples, trim_db, trim_keep_frames)
+        au = c_f32p(); ns = ctypes.c_int64()
+        ends = np.zeros((B, T), np.int64) if marks else None
+        self.check(self._fn("synthesize_document")(*head, ctypes.byref(d), int(sample_rate or 0), ctypes.byref(au), ctypes.byref(ns), _p(ends, c_i64p)))
+        audio = np.ctypeslib.as_array(au, shape=(ns.value,)).copy() if ns.value else np.zeros(0, np.float32)
+        self.vlib._fn("free_output")(au)
+        if marks:
+            info["token_ends"] = ends
+        return audio, info
 
     # ---- stages --------------------------------------------------------------------------------
     def encoder(self, ids, lengths, sid, bert=None):

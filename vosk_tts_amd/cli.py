@@ -8,6 +8,7 @@ synthesised to a 22.05 kHz mono 16-bit WAV through the MI355X engine.
     python -m vosk_tts_amd.cli -m /path/to/model-dir -i "прив+ет м+ир" -s 2 -o out.wav
 """
 import argparse
+import json
 import logging
 import sys
 
@@ -56,6 +57,13 @@ _OPTIONS = (
     (("--pitch-range",), dict(type=float, default=None, metavar="R",
                               help="intonation range: how far the voice moves about its median pitch, 0 (monotone) to 4, 1 = unchanged")),
     (("--ssml",), dict(action="store_true", help="the input is an SSML document: speak, p, s, sub, break, prosody, mark")),
+    (("--document",), dict(action="store_true",
+                           help="the input is a document: split into sentences and paragraphs (blank lines), synthesised as one batch and "
+                                "joined on the device, so --loudness / --limit see the whole output; with --ssml: s, p and voice end segments")),
+    (("--sentence-pause",), dict(type=float, default=0.2, metavar="SECONDS", help="with --document: silence behind a sentence (default 0.2)")),
+    (("--paragraph-pause",), dict(type=float, default=0.6, metavar="SECONDS", help="with --document: silence behind a paragraph (default 0.6)")),
+    (("--trim-db",), dict(type=float, default=None, metavar="DBFS",
+                          help="with --document: cut the frames below this level, e.g. -50, from both ends of every sentence (default: off)")),
     (("--marks",), dict(type=str, default=None, metavar="FILE",
                         help="also write the speech marks as JSON: rate, phonemes and words with their offsets in samples and seconds")),
     (("--log-level",), dict(default="INFO", metavar="LEVEL", help="python logging level (INFO shows the RTF line)")),
@@ -98,6 +106,29 @@ def run(opts):
 
     voice = model_mod.Model(opts.model, opts.model_name, opts.lang)
     synth = Synth(voice)
+    if getattr(opts, "document", False):  # many sentences in one call (Synth.synth_document); the per-word flags index one utterance
+        import wave
+
+        for flag in ("duration", "pause", "word_rate", "word_pitch", "word_gain"):
+            if getattr(opts, flag, None) is not None:
+                raise SystemExit(f"--{flag.replace('_', '-')} indexes the words of one utterance: not with --document")
+        fn = synth.synth_document_ssml if getattr(opts, "ssml", False) else synth.synth_document
+        res = fn(opts.input, speaker_id=opts.speaker or 0, sentence_pause=opts.sentence_pause, paragraph_pause=opts.paragraph_pause,
+                 trim_db=opts.trim_db, speech_rate=opts.speech_rate, sample_rate=opts.sample_rate, denoiser_strength=opts.denoiser_strength,
+                 marks=bool(opts.marks), loudness=opts.loudness, peak=opts.peak, pitch=opts.pitch, preserve_formants=opts.preserve_formants,
+                 **({} if opts.limit is None else {"limit": opts.limit}),
+                 **({} if getattr(opts, "pitch_range", None) is None else {"pitch_range": opts.pitch_range}))
+        audio, marks = res if opts.marks else (res, None)
+        with wave.open(opts.output, "w") as f:
+            f.setnchannels(1)
+            f.setsampwidth(2)
+            f.setframerate(int(opts.sample_rate) if opts.sample_rate else synth.native_rate())
+            f.writeframes(audio.tobytes())
+        if opts.marks:
+            with open(opts.marks, "w", encoding="utf-8") as f:
+                f.write(json.dumps(dict(marks.to_dict(), segments=[{"start_sample": a, "end_sample": b} for a, b in marks.segments]),
+                                   ensure_ascii=False, indent=1) + "\n")
+        return 0
     if getattr(opts, "ssml", False):  # the document's markup takes the place of the per-word flags
         import wave
 

@@ -23,6 +23,7 @@
 #include <chrono>
 #include <map>
 #include <mutex>
+#include <optional>
 #include <string>
 #include <tuple>
 #include <vector>
@@ -137,6 +138,7 @@ static int persist_cfg() {
 #include "limit.hip.h"
 #include "pitch.hip.h"
 #include "contour.hip.h"
+#include "document.hip.h"
 #include "out_tail.hip.h"
 #include "marks.hip.h"
 
@@ -376,7 +378,8 @@ int vits_stage_decoder(vits_model* m, const float* z, int32_t B, int32_t Ty, con
 // session workspace (masked by the decoder's first staging), the per-item frame counts in ylen.
 static int acoustic_host(HostStage& hs, const int64_t* ids, const int64_t* lengths, int32_t B, int32_t Tx, const float* scales,
                          const int64_t* sid, const vits_synth_opts* opts, std::vector<int64_t>& ylen, int64_t& Ty_out, float*& z_out,
-                         std::vector<int>* cum_out = nullptr) {  // cum_out: the cumulative frame counts [B, Tx] on the host (speech marks)
+                         std::vector<int>* cum_out = nullptr,  // cum_out: the cumulative frame counts [B, Tx] on the host (speech marks)
+                         bool solo_implied = false) {          // a document's items are SOLO items whatever the flags say (include/vits_document.h)
   if (!hs.m->acoustic) return fail(VITS_ERR_UNSUPPORTED, "vocoder-only model: only the decoder stage is available");
   vits_model* m = hs.m;
   const vits_hparams& hp = m->hp;
@@ -392,9 +395,9 @@ static int acoustic_host(HostStage& hs, const int64_t* ids, const int64_t* lengt
   int64_t* d_sid = hs.to_dev(sid, B);
   if (!d_ids || !d_len) return fail(VITS_ERR_NOMEM, "device alloc failed");
   s->ragged = B > 1;
-  s->solo = opts && (opts->flags & VITS_FLAG_SOLO_BATCH);
+  s->solo = solo_implied || (opts && (opts->flags & VITS_FLAG_SOLO_BATCH));
   s->item_seeds = nullptr;
-  if (s->solo && opts->item_seeds) {
+  if (s->solo && opts && opts->item_seeds) {
     static_assert(sizeof(unsigned long long) == sizeof(uint64_t), "seed width");
     s->item_seeds = hs.to_dev(reinterpret_cast<const unsigned long long*>(opts->item_seeds), (size_t)B);
   }

@@ -395,7 +395,7 @@ static int synth_fast(vits_model* m, const int64_t* ids, const int64_t* lengths,
   const NormReq& lq = q.norm;
   const bool pcm = q.pcm;
   const int TxB = (Tx + 7) / 8 * 8;
-  const bool forced = opts && opts->forced_durations, solo = opts && (opts->flags & VITS_FLAG_SOLO_BATCH);
+  const bool forced = opts && opts->forced_durations, solo = q.doc.on || (opts && (opts->flags & VITS_FLAG_SOLO_BATCH));
   ProsodyReq pr;  // (include/vits_prosody.h: checked before anything is launched; at B == 1 item_scales are the call's scalars)
   TRY(prosody_req(opts, lengths, B, Tx, scales, &pr));
   // (declared before the session guard: the call's last stream synchronisation happens before this scope ends)
@@ -482,8 +482,8 @@ static int synth_fast(vits_model* m, const int64_t* ids, const int64_t* lengths,
   const int64_t S = T ? T->P.n_out(Ty * hp.hop_length) : Ty * hp.hop_length;
   const size_t esz = pcm ? sizeof(int16_t) : sizeof(float);
   // what either branch below ends with, once its work is queued: the buffer the caller gets ...
-  auto host_out = [&]() -> char* {
-    char* h = static_cast<char*>(malloc(esz * (size_t)B * S));
+  auto host_out = [&](size_t n) -> char* {
+    char* h = static_cast<char*>(malloc(n ? n : 1));
     if (!h) { hipStreamSynchronize(st); fail(VITS_ERR_NOMEM, "host alloc failed"); }
     return h;
   };
@@ -506,21 +506,35 @@ static int synth_fast(vits_model* m, const int64_t* ids, const int64_t* lengths,
     if (token_ends) for (int b = 0; b < B; ++b) memcpy(token_ends + (size_t)b * Tx, F->marks_h + (size_t)b * TxB, sizeof(int64_t) * Tx);  // (bucket columns dropped)
     return VITS_OK;
   };
-  if (q.pitch.on || q.contour.on) {
-    // include/vits_pitch.h, vits_contour.h: the float, native-rate form of the graph as it is, then the tail (out_tail.hip.h) as launches behind it on
-    // the same stream, in buffers of this call (the graph's own copy of the unshifted float audio to the host is not used)
-    TRY(phase2_launch(F, Bk, solo, false, nullptr, nullptr, pr.per_item_noise));
+  if (q.pitch.on || q.contour.on || q.doc.on) {
+    // include/vits_pitch.h, vits_contour.h, vits_document.h: the float, native-rate form of the graph as it is, then the tail (out_tail.hip.h) as launches
+    // behind it on the same stream, in buffers of this call (the graph's own copy of the unshifted float audio to the host is not used)
     std::vector<long long> h_len(B);
     for (int b = 0; b < B; ++b) h_len[b] = F->h_ylen[b] * hp.hop_length;
     TailBufs bufs;
+    if (q.doc.on) TRY(doc_prepare(bufs, st, q.doc, h_len.data(), hp.hop_length));  // (the bound is refused, the controls go up, in front of the decoder)
+    TRY(phase2_launch(F, Bk, solo, false, nullptr, nullptr, pr.per_item_noise));
     const void* d_out = nullptr;
     const float* d_res = nullptr;
     long long So = 0;
     std::vector<float> res((size_t)B * 4);
+    std::vector<int> doc_blk(q.doc.on ? q.doc.blk_ints() : 0), doc_cum(q.doc.token_ends ? (size_t)B * TxB : 0);
+    const int rows = q.doc.on ? 1 : B;  // (a document goes on as one item)
     const int rc = tail_run(bufs, Bk->s, st, Bk->out_d, (long long)TyB * hp.hop_length, Bk->s->len_y, hp.hop_length, h_len.data(), B, F->s->cum, TxB, F->s->len_x, q, &d_out, &So, &d_res);
     if (rc != VITS_OK) { hipStreamSynchronize(st); return rc; }
-    if (d_res) hipMemcpyAsync(res.data(), d_res, sizeof(float) * res.size(), hipMemcpyDeviceToHost, st);
-    char* h_out = host_out();
+    if (d_res) hipMemcpyAsync(res.data(), d_res, sizeof(float) * 4 * (size_t)rows, hipMemcpyDeviceToHost, st);
+    if (q.doc.on) {  // the layout block (and the frame counts behind the marks) come back with the audio; F * hop of the row are the document
+      hipMemcpyAsync(doc_blk.data(), q.doc.d_blk, sizeof(int) * doc_blk.size(), hipMemcpyDeviceToHost, st);
+      if (q.doc.token_ends) hipMemcpyAsync(doc_cum.data(), F->s->cum, sizeof(int) * doc_cum.size(), hipMemcpyDeviceToHost, st);
+      char* h_out = host_out(esz * (size_t)So);
+      if (!h_out) return VITS_ERR_NOMEM;
+      TRY(finish(h_out, hipMemcpyAsync(h_out, d_out, esz * (size_t)So, hipMemcpyDeviceToHost, st)));
+      *out_samples = doc_results(q.doc, doc_blk.data(), doc_cum.data(), TxB, lengths, Tx, hp.hop_length, T ? T->P.L : 1, T ? T->P.M : 1);
+      if (*out_samples < So) memset(h_out + esz * (size_t)*out_samples, 0, esz * (size_t)(So - *out_samples));  // (trim: the row was sized by the bound)
+      if (d_res) norm_req_results(lq, res.data(), 1);
+      return VITS_OK;
+    }
+    char* h_out = host_out(esz * (size_t)B * S);
     if (!h_out) return VITS_ERR_NOMEM;
     TRY(finish(h_out, hipMemcpy2DAsync(h_out, esz * (size_t)S, d_out, esz * (size_t)So, esz * (size_t)S, (size_t)B, hipMemcpyDeviceToHost, st)));
     if (d_res) norm_req_results(lq, res.data(), B);
@@ -552,7 +566,7 @@ static int synth_fast(vits_model* m, const int64_t* ids, const int64_t* lengths,
   } else {
     TRY(phase2_launch(F, Bk, solo, pcm, R, T, pr.per_item_noise));
   }
-  char* h_out = host_out();
+  char* h_out = host_out(esz * (size_t)B * S);
   if (!h_out) return VITS_ERR_NOMEM;
   TRY(finish(h_out, hipSuccess));
   for (int b = 0; b < B; ++b) memcpy(h_out + esz * (size_t)b * S, src_h + esz * (size_t)b * stride, esz * (size_t)S);
@@ -573,41 +587,52 @@ static int synth_eager(vits_model* m, const int64_t* ids, const int64_t* lengths
   std::vector<int> cum;  // (marks: copied out next to ylen, in acoustic_host's own round trip)
   int64_t Ty = 0;
   float* z = nullptr;
-  TRY(acoustic_host(hs, ids, lengths, B, Tx, scales, sid, opts, ylen, Ty, z, token_ends ? &cum : nullptr));
+  TRY(acoustic_host(hs, ids, lengths, B, Tx, scales, sid, opts, ylen, Ty, z, (token_ends || q.doc.token_ends) ? &cum : nullptr, q.doc.on));
   if (token_ends)
     for (int b = 0; b < B; ++b) marks_fill_host(cum.data() + (size_t)b * Tx, lengths[b], Tx, hp.hop_length, T ? T->P.L : 1, T ? T->P.M : 1, token_ends + (size_t)b * Tx);
   vits_session* s = hs.s;
   s->ragged = B > 1;
-  s->solo = opts && (opts->flags & VITS_FLAG_SOLO_BATCH);
+  s->solo = q.doc.on || (opts && (opts->flags & VITS_FLAG_SOLO_BATCH));
   struct RaggedOff { vits_session* s; ~RaggedOff() { s->ragged = false; s->solo = false; } } ragged_off{s};
   const int64_t S = Ty * hp.hop_length;
   float* d_audio = hs.dev_alloc<float>((size_t)B * S);
   if (!d_audio) return fail(VITS_ERR_NOMEM, "device alloc failed");
-  run_decoder(s, z, true, B, (int)Ty, d_audio, S, true, !s->solo);
-  // the tail (out_tail.hip.h) behind the decoder, in the staging area of this call
   std::vector<long long> h_len(B);
   for (int b = 0; b < B; ++b) h_len[b] = ylen[b] * hp.hop_length;
+  std::vector<int> doc_blk(q.doc.on ? q.doc.blk_ints() : 0);
+  if (q.doc.on)  // (the bound is refused, the controls go up, in front of the decoder)
+    TRY(doc_prepare([&](size_t bytes) { return hs.raw_alloc(bytes); }, s->stream, q.doc, h_len.data(), hp.hop_length));
+  run_decoder(s, z, true, B, (int)Ty, d_audio, S, true, !s->solo);
+  // the tail (out_tail.hip.h) behind the decoder, in the staging area of this call
   const void* d_src = nullptr;
   const float* d_res = nullptr;
   long long So = 0;  // samples per item as returned
   TRY(tail_run([&](size_t bytes) { return hs.raw_alloc(bytes); }, s, s->stream, d_audio, S, s->len_y, hp.hop_length, h_len.data(), B, s->cum, Tx, s->len_x, q, &d_src, &So, &d_res));
-  if (d_res) hipMemcpyAsync(res.data(), d_res, sizeof(float) * res.size(), hipMemcpyDeviceToHost, s->stream);
+  const int rows = q.doc.on ? 1 : B;  // (a document goes on as one item)
+  if (d_res) hipMemcpyAsync(res.data(), d_res, sizeof(float) * 4 * (size_t)rows, hipMemcpyDeviceToHost, s->stream);
+  if (q.doc.on) hipMemcpyAsync(doc_blk.data(), q.doc.d_blk, sizeof(int) * doc_blk.size(), hipMemcpyDeviceToHost, s->stream);
   const size_t esz = q.pcm ? sizeof(int16_t) : sizeof(float);
-  void* h_out = malloc(esz * (size_t)B * So);
+  const size_t out_bytes = esz * (size_t)rows * So;
+  void* h_out = malloc(out_bytes ? out_bytes : 1);
   if (!h_out) return fail(VITS_ERR_NOMEM, "host alloc failed");
-  hipError_t e = hipMemcpyAsync(h_out, d_src, esz * (size_t)B * So, hipMemcpyDeviceToHost, s->stream);
+  hipError_t e = hipMemcpyAsync(h_out, d_src, out_bytes, hipMemcpyDeviceToHost, s->stream);
   int rc = e == hipSuccess ? check_err(s) : fail(VITS_ERR_DEVICE, "D2H failed: %s", hipGetErrorString(e));
   if (rc != VITS_OK) { free(h_out); return rc; }
-  if (d_res) norm_req_results(q.norm, res.data(), B);
+  if (d_res) norm_req_results(q.norm, res.data(), rows);
   *out = h_out;
   *out_samples = So;
+  if (q.doc.on) {
+    *out_samples = doc_results(q.doc, doc_blk.data(), cum.data(), Tx, lengths, Tx, hp.hop_length, T ? T->P.L : 1, T ? T->P.M : 1);
+    if (*out_samples < So)  // (trim: the row was sized by the bound)
+      memset(static_cast<char*>(h_out) + esz * (size_t)*out_samples, 0, esz * (size_t)(So - *out_samples));
+  }
   if (out_lengths) for (int b = 0; b < B; ++b) out_lengths[b] = T ? T->P.n_out(ylen[b] * hp.hop_length) : ylen[b] * hp.hop_length;
   return VITS_OK;
 }
 
 static int synth_dispatch(vits_model* m, const int64_t* ids, const int64_t* lengths, int32_t B, int32_t Tx, const float* scales,
                           const int64_t* sid, const vits_synth_opts* opts, bool pcm, float pcm_scale, int32_t sample_rate, void** out,
-                          int64_t* out_samples, int64_t* out_lengths, int64_t* token_ends = nullptr) {
+                          int64_t* out_samples, int64_t* out_lengths, int64_t* token_ends = nullptr, const DocReq* doc = nullptr) {
   if (!m || !ids || !lengths || !scales || !out || !out_samples || B <= 0 || Tx <= 0) return fail(VITS_ERR_ARG, "bad argument");
   if (!m->acoustic) return fail(VITS_ERR_UNSUPPORTED, "vocoder-only model: only the decoder stage is available");
   for (int b = 0; b < B; ++b) if (lengths[b] < 0 || lengths[b] > Tx) return fail(VITS_ERR_ARG, "length out of range");
@@ -615,6 +640,7 @@ static int synth_dispatch(vits_model* m, const int64_t* ids, const int64_t* leng
   const TailFields tf = tail_fields_vits(opts);
   TRY(tail_req(m, tf, sample_rate, pcm, pcm_scale, &q));
   TRY(tail_contour_req(m, tf, lengths, B, Tx, &q));
+  if (doc) q.doc = *doc;
   static const bool env_off = getenv("VITS_NO_FASTPATH") != nullptr;
   if (m->hp.bert_dim > 0 && (!opts || !opts->bert)) return fail(VITS_ERR_ARG, "this voice is BERT-conditioned: the bert feed [B,%d,T_x] is required", m->hp.bert_dim);
   if (m->hp.bert_dim == 0 && opts && opts->bert) return fail(VITS_ERR_ARG, "the bert feed was given but this voice has no BERT projection (hparams.bert_dim == 0)");
@@ -674,6 +700,32 @@ int vits_synthesize_pcm16_marks(vits_model* m, const int64_t* ids, const int64_t
   if (!token_ends) return fail(VITS_ERR_ARG, "token_ends must not be NULL (vits_synthesize_pcm16_rate is the call without marks)");
   if (sample_rate < 0) return fail(VITS_ERR_UNSUPPORTED, "sample_rate %d: must be positive, or 0 for the voice's own rate", sample_rate);
   return synth_dispatch(m, ids, lengths, B, Tx, scales, sid, opts, true, pcm_scale, sample_rate, reinterpret_cast<void**>(out_pcm), out_samples, out_lengths,
+                        token_ends);
+}
+
+// ---- include/vits_document.h
+static int synth_document(vits_model* m, const int64_t* ids, const int64_t* lengths, int32_t B, int32_t Tx, const float* scales, const int64_t* sid,
+                          const vits_synth_opts* opts, const vits_document* doc, bool pcm, float pcm_scale, int32_t sample_rate, void** out,
+                          int64_t* out_samples, int64_t* token_ends) {
+  if (!m) return fail(VITS_ERR_ARG, "bad argument");
+  if (sample_rate < 0) return fail(VITS_ERR_UNSUPPORTED, "sample_rate %d: must be positive, or 0 for the voice's own rate", sample_rate);
+  DocReq dq;  // (refused before anything is launched)
+  TRY(doc_req(doc, B, m->hp.hop_length, &dq));
+  dq.token_ends = token_ends;
+  return synth_dispatch(m, ids, lengths, B, Tx, scales, sid, opts, pcm, pcm_scale, sample_rate, out, out_samples, nullptr, nullptr, &dq);
+}
+
+int vits_synthesize_document(vits_model* m, const int64_t* ids, const int64_t* lengths, int32_t B, int32_t Tx, const float* scales,
+                             const int64_t* sid, const vits_synth_opts* opts, const vits_document* doc, int32_t sample_rate, float** out_audio,
+                             int64_t* out_samples, int64_t* token_ends) {
+  return synth_document(m, ids, lengths, B, Tx, scales, sid, opts, doc, false, 1.f, sample_rate, reinterpret_cast<void**>(out_audio), out_samples,
+                        token_ends);
+}
+
+int vits_synthesize_document_pcm16(vits_model* m, const int64_t* ids, const int64_t* lengths, int32_t B, int32_t Tx, const float* scales,
+                                   const int64_t* sid, const vits_synth_opts* opts, const vits_document* doc, float pcm_scale, int32_t sample_rate,
+                                   int16_t** out_pcm, int64_t* out_samples, int64_t* token_ends) {
+  return synth_document(m, ids, lengths, B, Tx, scales, sid, opts, doc, true, pcm_scale, sample_rate, reinterpret_cast<void**>(out_pcm), out_samples,
                         token_ends);
 }
 

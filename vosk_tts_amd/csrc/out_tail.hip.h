@@ -105,6 +105,7 @@ struct TailReq {
   NormReq norm;
   bool pcm = false;
   float pcm_scale = 1.f;
+  DocReq doc;  // (include/vits_document.h; empty: the call is not a document)
 };
 
 // Checked before anything is synthesised, so a refusal costs nothing: the rate, the loudness target, the limiter, the shift.  `vocoder`
@@ -171,16 +172,17 @@ using TailBufs = DevBufs;  // op_door.hip.h
 // len_y[b] * hop samples, h_len[b] on the host; its tokens' inclusive frame counts cum [B][cum_bstride] and their number tok_len [B] on the
 // device, read by a contoured call only): pitch or contour, resample, normalise and / or limit; the last stage that runs converts to int16
 // where q.pcm.  *d_out is [B, *So] of float or int16 (x itself where nothing is asked), *d_res the [B, 4] result rows of the last
-// stage on the device (null without one), for the caller's own copies to the host.  alloc(bytes) -> void* is the caller's: buffers
+// stage on the device (null without one), for the caller's own copies to the host.  A document (q.doc, prepared by doc_prepare) is joined
+// behind the contour stage and goes on as ONE item: *d_out is then [1, *So], the joined length F in frames is q.doc.d_blk[0] on the device
+// and *d_res has one row.  alloc(bytes) -> void* is the caller's: buffers
 // that outlive the launches queued here.  s: the session the launches are counted under (ProfScope).
 template <typename Alloc>
 static int tail_run(Alloc&& alloc, vits_session* s, hipStream_t stream, const float* x, long long S, const int* len_y, int hop, const long long* h_len,
                     int B, const int* d_cum, long long cum_bstride, const int* d_toklen, const TailReq& q, const void** d_out, long long* So_out,
                     const float** d_res) {
   const ResampleTab* T = q.T;
-  const long long So = T ? T->P.n_out(S) : S;
   const size_t esz = q.pcm ? sizeof(int16_t) : sizeof(float);
-  *So_out = So;
+  *So_out = T ? T->P.n_out(S) : S;
   *d_res = nullptr;
   if (q.pitch.on) {
     float* d_p = static_cast<float*>(alloc(sizeof(float) * (size_t)B * S));
@@ -189,7 +191,7 @@ static int tail_run(Alloc&& alloc, vits_session* s, hipStream_t stream, const fl
     x = d_p;
   }
   if (q.contour.on) {  // in the pitch stage's place; the last stage of a call that neither resamples nor normalises
-    const bool cp = q.pcm && !T && !q.norm.on();
+    const bool cp = q.pcm && !T && !q.norm.on() && !q.doc.on;
     void* d_c = alloc((cp ? sizeof(int16_t) : sizeof(float)) * (size_t)B * S);
     if (!d_c) return fail(VITS_ERR_NOMEM, "device alloc failed");
     TRY(contour_run(s->m->device, stream, x, S, h_len, B, q.contour, d_cum, cum_bstride, d_toklen, hop, d_c, cp, q.pcm_scale, S, S, nullptr, 0, nullptr, 0,
@@ -197,6 +199,18 @@ static int tail_run(Alloc&& alloc, vits_session* s, hipStream_t stream, const fl
     if (cp) { *d_out = d_c; return VITS_OK; }
     x = static_cast<const float*>(d_c);
   }
+  if (q.doc.on) {  // the items become one: the last stage of a call that neither resamples nor normalises
+    const bool jp = q.pcm && !T && !q.norm.on();
+    const long long Sd = q.doc.bound * hop;
+    void* d_j = alloc((jp ? sizeof(int16_t) : sizeof(float)) * (size_t)Sd);
+    if (!d_j) return fail(VITS_ERR_NOMEM, "device alloc failed");
+    doc_join_launch(s, stream, x, S, len_y, hop, q.doc, d_j, jp, q.pcm_scale);
+    B = 1; S = Sd; len_y = q.doc.d_blk;
+    *So_out = T ? T->P.n_out(S) : S;
+    if (jp) { *d_out = d_j; return VITS_OK; }
+    x = static_cast<const float*>(d_j);
+  }
+  const long long So = *So_out;
   *d_out = x;
   if (q.norm.on()) {  // the float waveform at the rate it is returned at, measured, then the gain (and the conversion)
     if (T) {

@@ -1055,8 +1055,10 @@ static int stts_synthesize_impl(stts_model* m, const int64_t* ids, int32_t Tx, c
 // the order of tail_run: shifted in place at the native rate, replaced by its copy at q.rate, normalised and / or limited in place.
 // (It crosses the host through the parity doors' kernels; running it on the device behind the vocoder would be a speed change of its own.)
 // cum / tok_lengths / Tx: the tokens' inclusive frame counts on the host, read by a contoured call only.
+// A document (include/vits_document.h) is joined behind the pitch stage and in front of the rate, where tail_run joins: from there on
+// the audio is one item, lengths[0] its length, and *doc_blk the layout block {F, start[B], lo[B], hi[B]}.
 static int stts_tail_host(stts_model* m, const TailReq& q, int B, float** audio, int64_t* S, int64_t* lengths, const int* cum,
-                          const int64_t* tok_lengths, int Tx) {
+                          const int64_t* tok_lengths, int Tx, std::vector<int>* doc_blk = nullptr) {
   const int device = m->base.device;
   if (q.contour.on && *S > 0) {  // (the kernels of vits_op_contour, from the tokens as contour_plan left them)
     std::vector<float> y((size_t)B * *S);
@@ -1078,6 +1080,21 @@ static int stts_tail_host(stts_model* m, const TailReq& q, int B, float** audio,
     std::vector<float> y((size_t)B * *S);
     TRY(pitch_op(device, *audio, lengths, B, *S, q.pitch.semitones, y.data(), PT_DOOR_SHIFT, q.pitch.formant));
     memcpy(*audio, y.data(), sizeof(float) * y.size());
+  }
+  if (q.doc.on) {  // (the kernels of vits_op_document_join)
+    const int hop = stts_hop(m);
+    DocReq dq = q.doc;
+    std::vector<int64_t> frames(B);
+    long long bound = dq.lead;
+    for (int b = 0; b < B; ++b) { frames[b] = lengths[b] / hop; bound += frames[b] + dq.gap[b]; }
+    if (bound * hop >= (1LL << 31)) return fail(VITS_ERR_ARG, "document: %lld samples before trimming, beyond the limit of 2^31 - 1", bound * hop);
+    float* y = static_cast<float*>(calloc((size_t)(bound * hop ? bound * hop : 1), sizeof(float)));
+    if (!y) return fail(VITS_ERR_NOMEM, "host alloc failed");
+    const int rc = doc_op(device, *audio, frames.data(), B, *S, hop, dq, y, bound * hop, doc_blk);
+    if (rc != VITS_OK) { free(y); return rc; }
+    free(*audio);
+    *audio = y; *S = (int64_t)(*doc_blk)[0] * hop;
+    B = 1; lengths[0] = *S;
   }
   if (q.rate) {
     const int native = m->vocoder->hp.sampling_rate;
@@ -1293,20 +1310,33 @@ static int stts_synthesize_batch_impl(stts_model* m, const int64_t* ids, const i
 // the batch entry points, as stts_synthesize_tail
 static int stts_synthesize_batch_tail(stts_model* m, const int64_t* ids, const int64_t* lengths, int32_t B, int32_t Tx, const float* scales,
                                       const int64_t* sid, const float* bert, const float* pde, const stts_synth_opts* opts, int rate,
-                                      float** out_audio, int64_t* out_samples, int64_t* out_lengths, const SttsMarks* mk) {
+                                      float** out_audio, int64_t* out_samples, int64_t* out_lengths, const SttsMarks* mk,
+                                      const DocReq* doc = nullptr) {
   TailReq q;
   const TailFields tf = tail_fields_stts(opts);
   TRY(tail_req(m->vocoder, tf, rate, false, 1.f, &q));
+  if (doc) {
+    if (!m->vocoder) return fail(VITS_ERR_ARG, "no vocoder attached");
+    q.doc = *doc;
+  }
   if (lengths && B > 0 && Tx > 0) {
     bool lens_ok = true;  // (a bad length is the call's own refusal, below)
     for (int b = 0; b < B; ++b) if (lengths[b] < 0 || lengths[b] > Tx) lens_ok = false;
     if (lens_ok) TRY(tail_contour_req(m->vocoder, tf, lengths, B, Tx, &q));
   }
-  std::vector<int> cum(q.contour.on ? (size_t)B * Tx : 0);
+  const bool doc_marks = q.doc.on && q.doc.token_ends;
+  std::vector<int> cum((q.contour.on || doc_marks) ? (size_t)B * Tx : 0);
   SttsMarks mc = mk ? *mk : SttsMarks();
-  if (q.contour.on) { mc.cum_out = cum.data(); mk = &mc; }
+  if (q.contour.on || doc_marks) { mc.cum_out = cum.data(); mk = &mc; }
   TRY(stts_synthesize_batch_impl(m, ids, lengths, B, Tx, scales, sid, bert, pde, opts, out_audio, out_samples, out_lengths, mk));
-  const int rc = stts_tail_host(m, q, B, out_audio, out_samples, out_lengths, cum.data(), lengths, Tx);
+  std::vector<int> blk;
+  int rc = stts_tail_host(m, q, B, out_audio, out_samples, out_lengths, cum.data(), lengths, Tx, &blk);
+  if (rc == VITS_OK && q.doc.on) {  // one item of out_lengths[0] samples; the marks from the layout block
+    ResamplePlan P;
+    long long L = 1, M = 1;
+    if (q.rate) { rc = resample_plan(m->vocoder->hp.sampling_rate, q.rate, &P); L = P.L; M = P.M; }
+    if (rc == VITS_OK) *out_samples = doc_results(q.doc, blk.data(), cum.data(), Tx, lengths, Tx, stts_hop(m), L, M);
+  }
   if (rc != VITS_OK) { free(*out_audio); *out_audio = nullptr; }
   return rc;
 }
@@ -1326,6 +1356,22 @@ int stts_synthesize_batch_marks(stts_model* m, const int64_t* ids, const int64_t
   int rate = 0;
   TRY(stts_marks_arg(m, token_ends, sample_rate, &mk, &rate));
   return stts_synthesize_batch_tail(m, ids, lengths, B, Tx, scales, sid, bert, pde, opts, rate, out_audio, out_samples, out_lengths, &mk);
+}
+
+// include/vits_document.h: the batch call, joined where stts_tail_host joins
+int stts_synthesize_document(stts_model* m, const int64_t* ids, const int64_t* lengths, int32_t B, int32_t Tx, const float* scales,
+                             const int64_t* sid, const float* bert, const float* pde, const stts_synth_opts* opts, const vits_document* doc,
+                             int32_t sample_rate, float** out_audio, int64_t* out_samples, int64_t* token_ends) {
+  if (!m || !out_audio || !out_samples || B <= 0) return fail(VITS_ERR_ARG, "bad argument");
+  if (sample_rate < 0) return fail(VITS_ERR_UNSUPPORTED, "sample_rate %d: must be positive, or 0 for the voice's own rate", sample_rate);
+  if (!m->vocoder) return fail(VITS_ERR_ARG, "no vocoder attached");
+  DocReq dq;  // (refused before anything is launched)
+  TRY(doc_req(doc, B, stts_hop(m), &dq));
+  dq.token_ends = token_ends;
+  const int native = m->vocoder ? m->vocoder->hp.sampling_rate : m->hp.sampling_rate;
+  const int rate = (sample_rate && sample_rate != native) ? sample_rate : 0;
+  std::vector<int64_t> item_len(B);
+  return stts_synthesize_batch_tail(m, ids, lengths, B, Tx, scales, sid, bert, pde, opts, rate, out_audio, out_samples, item_len.data(), nullptr, &dq);
 }
 
 }  // extern "C"

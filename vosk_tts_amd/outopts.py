@@ -48,3 +48,19 @@ def range_from_feed(lib, feed):
     if r is not None:
         lib._need_intonation()
     return r
+
+
+# the document feeds (include/vits_document.h): feed key -> keyword of the models' synthesize_document
+DOCUMENT_FEEDS = {"vits.doc_gap_frames": "gap_frames", "vits.doc_lead_frames": "lead_frames", "vits.doc_fade_samples": "fade_samples",
+                  "vits.doc_trim_db": "trim_db", "vits.doc_trim_keep": "trim_keep_frames"}
+
+
+def document_from_feed(lib, feed):
+    """"vits.doc_gap_frames" (int [B] or one int), "vits.doc_lead_frames", "vits.doc_fade_samples", "vits.doc_trim_db" (None = off),
+    "vits.doc_trim_keep" -> the keywords of synthesize_document; None when the feed names none of them (the request is no document).
+    The library refuses values out of range, naming segment and value, before anything is launched."""
+    kw = {v: feed[k] for k, v in DOCUMENT_FEEDS.items() if k in feed}
+    if not kw:
+        return None
+    lib._need_document()
+    return kw

@@ -19,7 +19,7 @@ import threading
 import numpy as np
 
 from .capi import VitsLib
-from .outopts import limit_from_feed, loudness_from_feed, pitch_from_feed, range_from_feed
+from .outopts import DOCUMENT_FEEDS, document_from_feed, limit_from_feed, loudness_from_feed, pitch_from_feed, range_from_feed
 
 log = logging.getLogger(__name__)
 
@@ -230,7 +230,7 @@ _OPTIONAL_NONE = ("bert", "phone_duration_extra")
 _EXT = ("vits.noise_dp", "vits.noise_prior", "vits.forced_durations", "vits.seed", "vits.solo", "vits.item_seeds", "vits.sample_rate", "vits.marks",
         "vits.loudness", "vits.peak", "vits.peak_ceiling", "vits.pitch", "vits.pitch_formants", "vits.limit", "vits.limit_lookahead_ms",
         "vits.limit_release_ms", "vits.item_scales", "vits.token_length_scale", "vits.token_pause", "vits.fit_frames", "vits.token_pitch",
-        "vits.token_gain_db", "vits.pitch_range")
+        "vits.token_gain_db", "vits.pitch_range") + tuple(DOCUMENT_FEEDS)
 # the prosody controls of a request (include/vits_prosody.h): feed key -> keyword of capi.VitsModel.synthesize*
 _PROSODY = {"vits.item_scales": "item_scales", "vits.token_length_scale": "token_length_scale", "vits.token_pause": "token_pause",
             "vits.fit_frames": "fit_frames"}
@@ -425,12 +425,41 @@ class VitsSession:
     def _range_kw(prange):
         return {} if prange is None else {"pitch_range": prange}
 
+    def run_document(self, input_feed, scale=1.0, pcm16=True):
+        """A document (include/vits_document.h): the feed of a batch -- "input" [B, T], "input_lengths" [B], "sid" [B], "bert" -- with at
+        least one of the document feeds "vits.doc_gap_frames" int [B], "vits.doc_lead_frames", "vits.doc_fade_samples",
+        "vits.doc_trim_db", "vits.doc_trim_keep"; its items are synthesised as a SOLO batch and joined on the device in front of the
+        resampler, the loudness stage, the limiter and the int16 conversion.  -> (audio int16 or float32 [S], info): info["seg_start"] /
+        ["seg_end"] int64 [B] in output samples, info["trim"] int32 [B, 2], and with "vits.marks" info["token_ends"] int64 [B, T].
+        Every other extension feed of run() applies: the per-item ones per item, the output tail to the whole document."""
+        feed, ids, sid, seed = self._validated(None, input_feed)
+        doc = document_from_feed(self._lib, feed)
+        if doc is None:
+            raise ValueError("run_document: the feed names no document key (\"vits.doc_gap_frames\", ...)")
+        for k in ("vits.noise_dp", "vits.noise_prior"):
+            if k in feed:
+                raise ValueError(f"feed '{k}' with a document: injected noise belongs to the parity calls")
+        self._watch()
+        pitch, formants = pitch_from_feed(self._lib, feed)
+        audio, info = self._model.synthesize_document(
+            ids, np.asarray(feed["input_lengths"]).reshape(-1), np.asarray(feed["scales"], np.float32).reshape(-1), sid, pcm=bool(pcm16),
+            pcm_scale=float(scale), forced_durations=feed.get("vits.forced_durations"), seed=int(seed), item_seeds=feed.get("vits.item_seeds"),
+            bert=feed.get("bert"), sample_rate=self._rate(feed.get("vits.sample_rate")), marks=self._marks(feed), loudness=self._loudness(feed),
+            **self._pitch_kw(pitch, formants, self._limit(feed)), **self._prosody(feed), **self._contour(feed),
+            **self._range_kw(range_from_feed(self._lib, feed)), **doc)
+        self.last_lengths = np.array([audio.shape[0]], np.int64)
+        return audio, info
+
     def run(self, output_names, input_feed, run_options=None):
-        """Extension feed "vits.sample_rate" (next to "vits.seed"): output rate in Hz; the time axis of the output is then in output
+        """The document feeds ("vits.doc_gap_frames", ...; run_document): the batch of the feed comes back as ONE row [1, 1, 1, S].
+        Extension feed "vits.sample_rate" (next to "vits.seed"): output rate in Hz; the time axis of the output is then in output
         samples (include/vits_resample.h).  Extension feed "vits.marks": True -- the result list gets a second entry, token_ends int64
         [B, T_x] in output samples (include/vits_marks.h).  Extension feeds "vits.loudness" / "vits.peak" / "vits.peak_ceiling": every
         item normalised to a LUFS or a peak target on the device, last in the chain (include/vits_loudness.h)."""
         feed, ids, sid, seed = self._validated(output_names, input_feed)
+        if any(k in feed for k in DOCUMENT_FEEDS):
+            audio, info = self.run_document(input_feed, pcm16=False)
+            return [audio[None, None, None, :]] + ([info["token_ends"]] if "token_ends" in info else [])
         self._watch()
         rate = self._rate(feed.get("vits.sample_rate"))
         marks = self._marks(feed)
@@ -506,6 +535,12 @@ class VitsSession:
         With the feed "vits.marks": True the result is a tuple that ends with token_ends int64 [B, T_x]: (pcm, token_ends), or
         (pcm, lengths, token_ends) with return_lengths.  The loudness feeds: as for run(); `scale` multiplies the normalised audio."""
         feed, ids, sid, seed = self._validated(None, input_feed)
+        if any(k in feed for k in DOCUMENT_FEEDS):  # (run_document: the batch comes back as one row)
+            if sample_rate is not None:
+                input_feed = dict(input_feed, **{"vits.sample_rate": sample_rate})
+            pcm, info = self.run_document(input_feed, scale=scale)
+            res = (pcm[None, :],) + ((self.last_lengths,) if return_lengths else ()) + ((info["token_ends"],) if "token_ends" in info else ())
+            return res if len(res) > 1 else res[0]
         self._watch()
         rate = self._rate(sample_rate if sample_rate is not None else feed.get("vits.sample_rate"))
         marks = self._marks(feed)
@@ -542,6 +577,9 @@ class VitsSession:
         samples whose concatenation equals run(...)[0].squeeze() for the same feed (same "vits.seed").
         sample_rate (default: the feed's "vits.sample_rate"): output rate in Hz; chunk sizes then vary by one sample."""
         feed, ids, sid, seed = self._validated(output_names, input_feed)
+        if any(k in feed for k in DOCUMENT_FEEDS):
+            raise ValueError("a stream cannot take a document: the join and the stages behind it need every segment before the first chunk "
+                             "(run() / run_pcm16() / run_document() take the \"vits.doc_*\" feeds)")
         if self._loudness(feed) is not None:
             raise ValueError("a stream cannot be loudness-normalised: an integrated-loudness or peak target needs the whole utterance before "
                              "the first chunk (run() / run_pcm16() take the loudness feeds)")

@@ -11,13 +11,13 @@ import numpy as np
 
 from .capi import VitsLib
 from .capi_stts import SttsModel
-from .outopts import limit_from_feed, loudness_from_feed, pitch_from_feed, range_from_feed
+from .outopts import DOCUMENT_FEEDS, document_from_feed, limit_from_feed, loudness_from_feed, pitch_from_feed, range_from_feed
 
 _INPUTS = ("input", "input_lengths", "scales", "sid", "bert", "phone_duration_extra")
 _EXT = ("vits.noise", "vits.seed", "vits.n_timesteps", "vits.sample_rate", "vits.denoiser_strength", "vits.denoiser_filter_length",
         "vits.marks", "vits.loudness", "vits.peak", "vits.peak_ceiling", "vits.pitch", "vits.pitch_formants",
         "vits.limit", "vits.limit_lookahead_ms", "vits.limit_release_ms", "vits.token_pitch", "vits.token_gain_db",
-        "vits.pitch_range")
+        "vits.pitch_range") + tuple(DOCUMENT_FEEDS)
 
 
 class SttsSession:
@@ -138,6 +138,12 @@ class SttsSession:
         to the result list (include/vits_marks.h; stts_synthesize_marks takes the rate itself); "vits.loudness" / "vits.peak" /
         "vits.peak_ceiling": the audio normalised to a LUFS or a peak target, last in the chain -- at another rate the resampled audio
         is what is measured (include/vits_loudness.h)."""
+        if any(input_feed.get(k) is not None for k in DOCUMENT_FEEDS):  # (run_document: the batch of the feed comes back as one row)
+            if output_names is not None and not set(output_names) <= {"wav", "wav_lengths"}:
+                raise ValueError(f"unknown output names {output_names}")
+            audio, info = self.run_document(input_feed)
+            outs = {"wav": audio[None, :], "wav_lengths": np.array([audio.shape[0]], np.int64)}
+            return [outs[n] for n in (output_names or ["wav", "wav_lengths"])] + ([info["token_ends"]] if "token_ends" in info else [])
         feed, ids, scales, sid, bert, pde, seed = self._parse(output_names, input_feed)
         loud = self._loudness(feed)
         lim = self._limit(feed)  # ("vits.limit": the peak limiter with the loudness gain or alone, last in the chain like the gain)
@@ -164,6 +170,9 @@ class SttsSession:
         Streaming form of run() (extension; the reference's transport is already `stream AudioChunk`,
         server/tts_service.proto:46-54): yields float32 [n] chunks of chunk_frames * hop samples whose concatenation equals
         run(...)[0].squeeze() for the same feed (same "vits.seed").  The acoustic model runs once, the vocoder is streamed."""
+        if any(input_feed.get(k) is not None for k in DOCUMENT_FEEDS):
+            raise ValueError("a stream cannot take a document: the join and the stages behind it need every segment before the first chunk "
+                             "(run() / run_document() take the \"vits.doc_*\" feeds)")
         feed, ids, scales, sid, bert, pde, seed = self._parse(output_names, input_feed)
         if "vits.noise" in feed:
             raise NotImplementedError("run_stream draws the CFM noise on the device (vits.seed)")
@@ -209,6 +218,8 @@ class SttsSession:
                 raise ValueError(f"Invalid input name: {k}")
         if "vits.noise" in feed:
             raise NotImplementedError("injected noise is a single-utterance option")
+        if any(k in feed for k in DOCUMENT_FEEDS):
+            raise ValueError("run_batch returns the items of a batch; a document feed (\"vits.doc_*\") belongs to run_document() / run()")
         for k in ("input", "input_lengths", "scales"):
             if k not in feed:
                 raise ValueError(f"Required input {k} is missing")
@@ -234,6 +245,47 @@ class SttsSession:
             return audio, ol
         audio, ol = self.resample(audio, ol, rate)
         return self.normalize(audio, ol, rate, loud, lim), ol
+
+    def run_document(self, input_feed, scale=1.0, pcm16=False):
+        """A document (include/vits_document.h): run_batch's feed with at least one of the document feeds "vits.doc_gap_frames" int [B],
+        "vits.doc_lead_frames", "vits.doc_fade_samples", "vits.doc_trim_db", "vits.doc_trim_keep": the items of the batch joined into
+        one piece of audio behind the pitch stage (stts_synthesize_document), in front of the resampler and the loudness / limiter
+        stage.  -> (audio float32 [S], info) as VitsSession.run_document; pcm16=True converts on the host, as Synth does for this
+        family (audio * scale, then Synth.audio_float_to_int16's rule)."""
+        feed = {k: v for k, v in input_feed.items() if v is not None}
+        for k in feed:
+            if k not in _INPUTS and k not in _EXT and k != "vits.item_seeds":
+                raise ValueError(f"Invalid input name: {k}")
+        if "vits.noise" in feed:
+            raise NotImplementedError("injected noise is a single-utterance option")
+        for k in ("input", "input_lengths", "scales"):
+            if k not in feed:
+                raise ValueError(f"Required input {k} is missing")
+        doc = document_from_feed(self._lib, feed)
+        if doc is None:
+            raise ValueError("run_document: the feed names no document key (\"vits.doc_gap_frames\", ...)")
+        ids = np.asarray(feed["input"])
+        if ids.ndim != 3 or ids.shape[1] != 5:
+            raise ValueError("input must be int64 [B, 5, T]")
+        sid = np.asarray(feed.get("sid", np.zeros(ids.shape[0])), np.int64).reshape(-1)
+        if sid.shape[0] == 1 and ids.shape[0] > 1:
+            sid = np.repeat(sid, ids.shape[0])
+        seed = feed.get("vits.seed")
+        if seed is None and "vits.item_seeds" not in feed:
+            with self._seed_lock:
+                seed = next(self._seed)
+        pk = self._pitch(feed)
+        for k in ("token_pitch", "token_gain_db"):  # ([B, T] here, not the single utterance's [T])
+            if k in pk:
+                pk[k] = np.asarray(feed["vits." + k], np.float32).reshape(ids.shape[0], -1)
+        audio, info = self._model.synthesize_document(
+            ids, feed["input_lengths"], np.asarray(feed["scales"], np.float32).reshape(-1), sid, feed.get("bert"), feed.get("phone_duration_extra"),
+            seed=int(seed or 0), n_timesteps=int(feed.get("vits.n_timesteps", 0)), item_seeds=feed.get("vits.item_seeds"),
+            marks=bool(feed.get("vits.marks")), sample_rate=self._rate(feed.get("vits.sample_rate")), loudness=self._loudness(feed),
+            limit=self._limit(feed), **pk, **self._denoiser(feed), **doc)
+        if pcm16:
+            audio = np.clip((audio * scale) * 32767.0, -32767.0, 32767.0).astype("int16")
+        return audio, info
 
     def close(self):
         self._model.close()

@@ -118,14 +118,23 @@ def _local(tag):
     return tag.rsplit("}", 1)[-1] if isinstance(tag, str) else str(tag)
 
 
-def parse(ssml):
-    """SSML text -> Plan; ValueError names whatever is refused"""
+def _root(ssml):
     try:
         root = ET.fromstring(ssml)
     except ET.ParseError as e:
         raise ValueError(f"malformed SSML: {e}") from None
     if _local(root.tag) != "speak":
         raise ValueError(f"the root element must be <speak>, not <{_local(root.tag)}>")
+    return root
+
+
+def parse(ssml):
+    """SSML text -> Plan; ValueError names whatever is refused"""
+    return _plan(_root(ssml))
+
+
+def _plan(root):
+    """the Plan of one <speak> tree"""
     text = []        # the pieces of the spoken text
     runs = []        # (start, end, rate, semitones, dB) per piece under a prosody element
     edges = []       # (position in the text, tag) of every tag boundary
@@ -226,3 +235,174 @@ def parse(ssml):
         pauses[w] = pauses.get(w, 0.0) + sec
     return Plan(full.strip(), word_rates or None, pauses or None, word_pitch or None, word_gains or None,
                 [(name, words_before(p)) for name, p in marks], pitch_range)
+
+
+# ---- documents (include/vits_document.h; Synth.synth_document_ssml) ---------------------------------------------------------------------
+_DOC_ATTRS = dict(_ATTRS, voice={"name", _XML_LANG})
+
+
+class DocumentPlan:
+    """What an SSML document asks of Synth.synth_document: segments [document.Segment], lead (seconds of silence in front, from a <break>
+    ahead of the first word), pitch_range (from a prosody `range` around every word, else None) and marks [(name, index of the next word,
+    counted over the whole document)]."""
+
+    def __init__(self, segments, lead, pitch_range, marks):
+        self.segments, self.lead, self.pitch_range, self.marks = segments, lead, pitch_range, marks
+
+
+def parse_document(ssml):
+    """SSML text -> DocumentPlan.  On top of parse()'s subset: <s>, <p> and <voice name="N"> (N an integer speaker id) end a segment, both
+    where they open and where they close; the segment in front of a </p> is a paragraph's last.  A <break> with no word between it and
+    a segment boundary becomes the silence at that boundary (in front of the first segment: the lead) in place of the default pause;
+    anywhere else it stays a pause behind its word.  prosody, sub and mark work as in parse(), per segment: a prosody element that spans
+    several segments applies to each.  `range` is accepted on a prosody element around every word of the document only.  Anything else
+    is a ValueError that names it."""
+    from .document import Segment
+
+    root = _root(ssml)
+    events = []  # ("text", str) | ("open", attrib) | ("close",) | ("leaf", element) | ("bound", tag, opening?, speaker or None)
+
+    def walk(el):
+        tag = _local(el.tag)
+        if tag not in _DOC_ATTRS:
+            raise ValueError(f"SSML element <{tag}> is not supported in a document (speak, p, s, voice, sub, break, prosody, mark)")
+        for k in el.attrib:
+            if k not in _DOC_ATTRS[tag]:
+                raise ValueError(f"<{tag}> has no attribute {_local(k)!r} here ({', '.join(sorted(_local(a) for a in _DOC_ATTRS[tag])) or 'none'})")
+        if tag in ("break", "mark", "sub"):
+            if len(el):
+                raise ValueError(f"<{tag}> cannot contain <{_local(el[0].tag)}>")
+            if tag == "break":
+                if (el.text or "").strip():
+                    raise ValueError("<break> cannot contain text")
+                parse_time(el.attrib.get("time", "250ms"))
+            if tag == "mark" and "name" not in el.attrib:
+                raise ValueError("<mark> needs a name")
+            if tag == "sub" and "alias" not in el.attrib:
+                raise ValueError("<sub> needs an alias")
+            events.append(("leaf", el))
+            return
+        sid = None
+        if tag == "voice":
+            name = el.attrib.get("name", "").strip()
+            if not re.fullmatch(r"[0-9]+", name):
+                raise ValueError(f"<voice name={el.attrib.get('name')!r}>: the name is an integer speaker id of the voice, such as '1'")
+            sid = int(name)
+        if tag in ("p", "s", "voice"):
+            events.append(("bound", tag, True, sid))
+        elif tag == "prosody":
+            events.append(("open", dict(el.attrib)))
+        events.append(("text", el.text or ""))
+        for child in el:
+            walk(child)
+            events.append(("text", child.tail or ""))
+        if tag in ("p", "s", "voice"):
+            events.append(("bound", tag, False, sid))
+        elif tag == "prosody":
+            events.append(("close",))
+
+    walk(root)
+    segments, marks, ranges = [], [], []
+    state = {"lead": 0.0, "words": 0}
+    voices, open_pros = [None], []     # the speakers and the prosody attributes in effect
+    pending, pending_pros = [], []     # the events of the segment being collected, and the prosody stack where it began
+
+    def words_in(evs):
+        return count_words(re.sub(r"\s+", " ", " ".join(e[1] if e[0] == "text" else e[1].attrib["alias"] for e in evs
+                                                        if e[0] == "text" or (e[0] == "leaf" and _local(e[1].tag) == "sub"))))
+
+    def boundary_pause(sec):
+        if segments:
+            segments[-1].pause_after = (segments[-1].pause_after or 0.0) + sec
+        else:
+            state["lead"] += sec
+
+    def finish(kind):
+        evs = list(pending)
+        del pending[:]
+        spoken = [i for i, e in enumerate(evs) if words_in([e])]
+        is_break = lambda e: e[0] == "leaf" and _local(e[1].tag) == "break"
+        if not spoken:  # no word: its breaks belong to the boundary, its punctuation to nobody
+            for e in evs:
+                if is_break(e):
+                    boundary_pause(parse_time(e[1].attrib.get("time", "250ms")))
+            return
+        after = None
+        keep = []
+        for i, e in enumerate(evs):
+            if is_break(e) and (i < spoken[0] or i > spoken[-1]):
+                sec = parse_time(e[1].attrib.get("time", "250ms"))
+                if i < spoken[0]:
+                    boundary_pause(sec)
+                else:
+                    after = (after or 0.0) + sec
+            else:
+                keep.append(e)
+        seg_root = ET.Element("speak")
+        stack = [seg_root]
+        for attrib in pending_pros:
+            stack.append(ET.SubElement(stack[-1], "prosody", attrib))
+        for e in keep:
+            if e[0] == "text":
+                top = stack[-1]
+                if len(top):
+                    top[-1].tail = (top[-1].tail or "") + e[1]
+                else:
+                    top.text = (top.text or "") + e[1]
+            elif e[0] == "open":
+                stack.append(ET.SubElement(stack[-1], "prosody", e[1]))
+            elif e[0] == "close":
+                stack.pop()
+            else:
+                leaf = ET.SubElement(stack[-1], e[1].tag, dict(e[1].attrib))
+                leaf.text = e[1].text
+        plan = _plan(seg_root)
+        segments.append(Segment(plan.text, speaker_id=voices[-1], pause_after=after, word_rates=plan.word_rates, pauses=plan.pauses,
+                                word_pitch=plan.word_pitch, word_gains=plan.word_gains, kind=kind))
+        state["words"] += count_words(plan.text)
+
+    range_open = []
+    for e in events:
+        if e[0] == "bound":
+            _, tag, opening, sid = e
+            had = bool(pending) and words_in(pending) > 0
+            finish("paragraph-end" if (tag == "p" and not opening) else "sentence")
+            if tag == "p" and not opening and not had and segments:
+                segments[-1].kind = "paragraph-end"
+            if tag == "voice":
+                voices.append(sid) if opening else voices.pop()
+            pending_pros[:] = [dict(a) for a in open_pros]
+            continue
+        if e[0] == "leaf" and _local(e[1].tag) == "mark":
+            marks.append((e[1].attrib["name"], state["words"] + words_in(pending)))
+            continue
+        if e[0] == "open":
+            attrib = dict(e[1])
+            if "range" in attrib:
+                range_open.append((state["words"] + words_in(pending), parse_range(attrib["range"]), attrib.pop("range")))
+            else:
+                range_open.append(None)
+            open_pros.append(attrib)
+            e = ("open", attrib)
+        elif e[0] == "close":
+            open_pros.pop()
+            r = range_open.pop()
+            if r is not None:
+                ranges.append((r[0], state["words"] + words_in(pending), r[1], r[2]))
+        if not pending:
+            pending_pros[:] = [dict(a) for a in (open_pros[:-1] if e[0] == "open" else open_pros + [{}] if e[0] == "close" else open_pros)]
+        pending.append(e)
+    finish("paragraph-end")
+    if not segments:
+        raise ValueError("the document has no word")
+    segments[-1].kind = "paragraph-end"  # (the end of the document ends a paragraph)
+    total = state["words"]
+    pitch_range = None
+    for a, b, r, raw in ranges:
+        if a != 0 or b != total:
+            raise ValueError(f"prosody range={raw!r} covers words {a} to {b - 1} of {total}: the intonation range is one value per call, so "
+                             "`range` is accepted only on a prosody element around every word of the document")
+        pitch_range = r if pitch_range is None else pitch_range * r
+        if not 0.0 <= pitch_range <= INTONATION_MAX_RANGE:
+            raise ValueError(f"prosody range composes to {pitch_range:g}: outside [0, {INTONATION_MAX_RANGE:g}]")
+    return DocumentPlan(segments, state["lead"], pitch_range, marks)

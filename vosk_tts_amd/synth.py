@@ -3,6 +3,7 @@
 RTF log line and WAV output.  The only change is what sits behind `self.model.onnx.run`.
 """
 import logging
+import math
 import re
 import time
 import wave
@@ -516,10 +517,169 @@ class Synth:
             sm.named = {name: (int(sm.words[w][1]) if w < len(sm.words) else int(audio.shape[-1])) for name, w in plan.marks}
         return res
 
+    # ---- documents (include/vits_document.h; vosk_tts_amd/document.py) ---------------------------------------------------------
+    def count_tokens(self, text):
+        """how many tokens the front end _feed picks makes of `text` (what document.split counts sentences in)"""
+        text = self.normalize(text)
+        if self.model.tokenizer is None and not (self.model.config.get("model_type") or "").startswith("multistream"):
+            return len(self.g2p_noembed(text))
+        return int(self._front_rows(text)[0].shape[-1])
+
+    def _document_feed(self, segments, speaker_id, noise_level, speech_rate, duration_noise_level, scale):
+        """The batch feed of a document's segments: one front end (front_batch for the BERT-conditioned and multistream voices, else
+        g2p_noembed per segment, padded), per-segment speakers, rates (-> "vits.item_scales") and per-word controls
+        (-> "vits.token_length_scale" / "vits.token_pause" / "vits.token_pitch" / "vits.token_gain_db", rows padded with their neutral
+        values).  -> (feed, scale)"""
+        from . import prosody as P
+
+        inf = self.model.config.get("inference", {})
+        noise_level = inf.get("noise_level", 0.8) if noise_level is None else noise_level
+        speech_rate = inf.get("speech_rate", 1.0) if speech_rate is None else speech_rate
+        duration_noise_level = inf.get("duration_noise_level", 0.8) if duration_noise_level is None else duration_noise_level
+        scale = inf.get("scale", 1.0) if scale is None else scale
+        multistream = (self.model.config.get("model_type") or "").startswith("multistream")
+        texts = [self.normalize(s.text) for s in segments]
+        sids = [int((speaker_id or 0) if s.speaker_id is None else s.speaker_id) for s in segments]
+        B = len(segments)
+        if multistream or self.model.tokenizer is not None:
+            fb = self.front_batch(texts, sids)
+            ids, lens, bert, pde = fb["input"], fb["input_lengths"], fb["bert"], fb["phone_duration_extra"]
+        else:
+            rows = [np.array(self.g2p_noembed(t), np.int64) for t in texts]
+            lens = np.array([r.shape[0] for r in rows], np.int64)
+            ids = np.zeros((B, int(lens.max())), np.int64)
+            for b, r in enumerate(rows):
+                ids[b, :lens[b]] = r
+            bert = pde = None
+        T = ids.shape[-1]
+        feed = {"input": ids, "input_lengths": lens, "scales": np.array([noise_level, 1.0 / speech_rate, duration_noise_level], np.float32),
+                "sid": np.array(sids, np.int64), "bert": bert, "phone_duration_extra": pde}
+        if any(s.speech_rate is not None for s in segments):
+            if multistream:
+                raise ValueError("Segment.speech_rate is a prosody control of the VITS-family voices (\"vits.item_scales\"); a multistream "
+                                 "voice has one rate per call")
+            feed["vits.item_scales"] = np.array([[noise_level, 1.0 / (speech_rate if s.speech_rate is None else s.speech_rate),
+                                                  duration_noise_level] for s in segments], np.float32)
+        rate, hop = self.native_rate(), self.hop_length()
+        rows = {"vits.token_length_scale": (np.ones((B, T), np.float32), False), "vits.token_pause": (np.zeros((B, T), np.int32), False),
+                "vits.token_pitch": (np.zeros((B, T), np.float32), False), "vits.token_gain_db": (np.zeros((B, T), np.float32), False)}
+        for b, (s, text) in enumerate(zip(segments, texts)):
+            if multistream and (s.word_rates or s.pauses):
+                self._prosody_text(text, s.word_rates, s.pauses, None)  # (that family's own refusal)
+            vals = {}
+            if s.word_rates or s.pauses:
+                vals["vits.token_length_scale"], vals["vits.token_pause"] = P.token_controls(self.marks_layout(text), s.word_rates, s.pauses, rate, hop)
+            if s.word_pitch or s.word_gains:
+                vals["vits.token_pitch"], vals["vits.token_gain_db"] = P.token_contour(self.marks_layout(text), s.word_pitch, s.word_gains)
+            for k, a in vals.items():
+                if a is None:
+                    continue
+                if a.shape[0] != int(lens[b]):
+                    raise ValueError(f"token layout of segment {b} does not match: {a.shape[0]} tokens laid out for {int(lens[b])} ids")
+                rows[k][0][b, :a.shape[0]] = a
+                rows[k] = (rows[k][0], True)
+        for k, (a, used) in rows.items():
+            if used:
+                feed[k] = a
+        return feed, scale
+
+    def synth_document(self, doc, speaker_id=0, sentence_pause=0.2, paragraph_pause=0.6, lead=0.0, fade_ms=2.0, trim_db=None, trim_keep=1,
+                       marks=False, seed=None, noise_level=None, speech_rate=None, duration_noise_level=None, scale=None, sample_rate=None,
+                       denoiser_strength=None, loudness=None, peak=None, peak_ceiling=None, pitch=None, preserve_formants=None, limit=None,
+                       limit_lookahead_ms=None, limit_release_ms=None, pitch_range=None, max_tokens=None, **refused):
+        """Many sentences and speakers in one call (extension; include/vits_document.h).  doc: a string -- split by document.split into
+        sentences and paragraphs under the documented rule, sentences longer than max_tokens (default 512) tokens cut at clause marks --
+        or a list of document.Segment(text, speaker_id=None, pause_after=None, speech_rate=None, word_rates=, pauses=, word_pitch=,
+        word_gains=).  The segments are synthesised as one batch, every one as if alone, and joined on the device: `lead` seconds of
+        silence in front, sentence_pause (default 0.2 s) / paragraph_pause (default 0.6 s; both design choices, not measurements) or a
+        segment's own pause_after behind each, the last one trailing; fade_ms raised-cosine fades at both ends of every segment (at most
+        half a frame); trim_db (None = off, else a negative dBFS value) cuts the frames below it from both ends of every segment, keeping
+        trim_keep frames.  Seconds become frames as floor(sec * rate / hop + 0.5).  The resampler (sample_rate), the loudness target, the
+        limiter and the int16 conversion then see ONE piece of audio; pitch and pitch_range are one value per call, applied per segment.
+        Returns int16 audio; with marks=True (audio, SpeechMarks) whose words and phonemes run over the whole document, plus
+        marks.segments = [(start, end)] in samples.  The call-wide per-word keywords of synth_audio (word_rates, pauses, duration,
+        word_pitch, word_gains) index one utterance and are refused by name: they belong to a Segment."""
+        from . import document as D
+
+        for k in refused:
+            if k in ("word_rates", "pauses", "duration", "word_pitch", "word_gains"):
+                raise ValueError(f"synth_document takes no {k}=: it indexes the words of one utterance (give it to a document.Segment)")
+            raise TypeError(f"synth_document() got an unexpected keyword argument {k!r}")
+        segments = D.split(doc, max_tokens or D.MAX_TOKENS, self.count_tokens) if isinstance(doc, str) else list(doc)
+        if not segments:
+            raise ValueError("an empty document")
+        for b, s in enumerate(segments):
+            if not isinstance(s, D.Segment):
+                raise TypeError(f"segment {b} is {type(s).__name__}: a document is a string or a list of document.Segment")
+            if not D.has_word(s.text):
+                raise ValueError(f"segment {b} ({s.text!r}) has no word")
+        rate, hop = self.native_rate(), self.hop_length()
+        args, scale = self._document_feed(segments, speaker_id, noise_level, speech_rate, duration_noise_level, scale)
+        args["vits.doc_gap_frames"] = D.gap_frames(segments, sentence_pause, paragraph_pause, rate, hop)
+        args["vits.doc_lead_frames"] = D.frames(lead, rate, hop)
+        fade = int(math.floor(float(fade_ms) * rate / 1000.0 + 0.5))
+        if fade < 0 or fade > hop // 2:
+            raise ValueError(f"fade_ms {fade_ms}: {fade} samples at {rate} Hz, outside [0, half a frame = {hop // 2}]")
+        args["vits.doc_fade_samples"] = fade
+        if trim_db is not None:
+            if not (math.isfinite(float(trim_db)) and float(trim_db) < 0):
+                raise ValueError(f"trim_db {trim_db}: None (off) or a negative finite dBFS value")
+            args["vits.doc_trim_db"] = float(trim_db)
+            args["vits.doc_trim_keep"] = int(trim_keep)
+        if seed is not None:
+            args["vits.seed"] = int(seed)
+        self._denoiser(args, denoiser_strength)
+        self._loudness(args, loudness, peak, peak_ceiling)
+        self._limit(args, limit, peak_ceiling, limit_lookahead_ms, limit_release_ms)
+        self._pitch(args, pitch, preserve_formants)
+        self._range(args, pitch_range)
+        out_rate = rate
+        if sample_rate and int(sample_rate) != rate:
+            out_rate = int(sample_rate)
+            args["vits.sample_rate"] = out_rate
+        if marks:
+            args["vits.marks"] = True
+        run = getattr(self.model.onnx, "run_document", None)
+        if run is None:
+            raise NotImplementedError("this session type has no run_document (VitsSession: vits_synthesize_document_pcm16, SttsSession: "
+                                      "stts_synthesize_document)")
+        start_time = time.perf_counter()
+        audio, info = run(args, scale=scale, pcm16=True)
+        infer_sec = time.perf_counter() - start_time
+        sec = audio.shape[-1] / out_rate
+        logging.info("Real-time factor: %0.2f (infer=%0.2f sec, audio=%0.2f sec)" % (infer_sec / sec if sec > 0 else 0.0, infer_sec, sec))
+        if not marks:
+            return audio
+        sm = D.stitch_marks(out_rate, info["token_ends"], args["input_lengths"], [self.marks_layout(s.text) for s in segments],
+                            info["seg_start"], info["seg_end"])
+        return audio, sm
+
+    def synth_document_ssml(self, ssml, **kw):
+        """synth_document for an SSML document (ssml.parse_document): <s>, <p> and <voice name="N"> (N an integer speaker id) end a
+        segment, a <break> at a segment boundary becomes the silence there, prosody / sub / mark work per segment as in synth_ssml, and a
+        prosody `range` around the whole document becomes pitch_range.  With marks=True the marks carry `named` as synth_ssml's do."""
+        from . import ssml as S
+
+        plan = S.parse_document(ssml)
+        if plan.pitch_range is not None:
+            if kw.get("pitch_range") is not None:
+                raise ValueError("synth_document_ssml takes pitch_range from the document's markup, not as a keyword")
+            kw = dict(kw, pitch_range=plan.pitch_range)
+        if plan.lead:
+            if kw.get("lead"):
+                raise ValueError("synth_document_ssml takes lead from the <break> in front of the first segment, not as a keyword")
+            kw = dict(kw, lead=plan.lead)
+        res = self.synth_document(plan.segments, **kw)
+        if kw.get("marks"):
+            audio, sm = res
+            sm.named = {name: (int(sm.words[w][1]) if w < len(sm.words) else int(audio.shape[-1])) for name, w in plan.marks}
+        return res
+
     def synth_stream(self, text, speaker_id=0, noise_level=None, speech_rate=None, duration_noise_level=None, scale=None,
                      chunk_frames=64, sample_rate=None, denoiser_strength=None, on_marks=None, loudness=None, peak=None, peak_ceiling=None,
-                     pitch=None, limit=None, word_rates=None, pauses=None, duration=None, pitch_range=None):
-        """word_rates / pauses / duration: as for synth_audio (the stream's open runs the controlled regulator; chunking is untouched).
+                     pitch=None, limit=None, word_rates=None, pauses=None, duration=None, pitch_range=None, document=None):
+        """document: ValueError -- the join and the stages behind it need every segment before the first chunk (synth_document).
+        word_rates / pauses / duration: as for synth_audio (the stream's open runs the controlled regulator; chunking is untouched).
         pitch_range: ValueError -- the median of the F0 track needs the whole utterance (a voice whose config names
         inference.pitch_range streams with the range it has).
         limit: ValueError -- the limiter's look-ahead and its loudness passes need the whole utterance (a voice whose config names
@@ -532,6 +692,9 @@ class Synth:
         on_marks: a callable that receives the utterance's marks.SpeechMarks once, before the first chunk is yielded.
         loudness / peak: ValueError -- an integrated-loudness or peak target needs the whole utterance before the first chunk (a voice
         whose config names inference.loudness / inference.peak streams un-normalised)."""
+        if document is not None:
+            raise ValueError("synth_stream cannot take document=: the join and the stages behind it need every segment before the first "
+                             "chunk (synth_document takes a document)")
         if loudness is not None or peak is not None:
             raise ValueError("synth_stream cannot normalise loudness: an integrated-loudness or peak target needs the whole utterance "
                              "before the first chunk (synth_audio takes loudness= / peak=)")
