@@ -168,7 +168,8 @@ class MultiDeviceSynth:
 
     def synth_batch(self, texts, speaker_ids=0, noise_level=None, speech_rate=None, duration_noise_level=None, scale=None, seeds=None,
                     sample_rate=None, denoiser_strength=None, marks=False, loudness=None, peak=None, peak_ceiling=None, pitch=None,
-                    preserve_formants=None, limit=None, limit_lookahead_ms=None, limit_release_ms=None, pitch_range=None):
+                    preserve_formants=None, limit=None, limit_lookahead_ms=None, limit_release_ms=None, pitch_range=None, watermark=None,
+                    watermark_depth_db=None):
         """texts: list of str -> list of int16 PCM arrays (22.05 kHz), one per request, in request order.  marks=True: a list of
         (audio, marks.SpeechMarks) per request instead (as Synth.synth_audio(..., marks=True)), through every shard path.  `seeds`: optional
         per-request noise seeds (default: a running counter), `speaker_ids`: one id or one per request.  `noise_level` / `speech_rate` /
@@ -182,7 +183,9 @@ class MultiDeviceSynth:
         `limit` / `limit_lookahead_ms` / `limit_release_ms`: the look-ahead peak limiter (include/vits_limit.h), one setting per call and a
         gain per request; `peak_ceiling` is then the limiter's ceiling.
         `pitch_range`: the intonation range (include/vits_intonation.h), one value per call; every request is tracked and scaled about
-        its own median, so it equals its single call with the same seed."""
+        its own median, so it equals its single call with the same seed.
+        `watermark` / `watermark_depth_db`: the audio watermark (include/vits_watermark.h; Synth._watermark), one key per call; every
+        request is marked from its own samples, so it equals its single call with the same seed."""
         s0 = self.synths[0]
         loud = {}
         s0._loudness(loud, loudness, peak, peak_ceiling)
@@ -190,6 +193,7 @@ class MultiDeviceSynth:
         # "vits.pitch" (and "vits.pitch_formants"): one shift for the whole batch, travelling with the loudness feeds; include/vits_pitch.h
         s0._pitch(loud, pitch, preserve_formants)
         s0._range(loud, pitch_range)  # ("vits.pitch_range": travels the same way)
+        s0._watermark(loud, watermark, watermark_depth_db)  # ("vits.watermark_key" / "vits.watermark_depth_db": as well)
         dn = {}
         s0._denoiser(dn, denoiser_strength)
         denoiser_strength = dn.get("vits.denoiser_strength")
@@ -344,14 +348,15 @@ class MultiDeviceSynth:
         spec = sess._loudness(loud or {})
         lim = sess._limit(loud or {})
         kw = dict(kw, **sess._pitch(loud or {}))
+        wm = sess._wm(loud or {})  # (the watermark: behind the resampler, in front of the normalisation)
         if marks:
-            return sess._model.synthesize_batch(*args, marks=True, sample_rate=sess._rate(sample_rate), loudness=spec, limit=lim, **kw)
+            return sess._model.synthesize_batch(*args, marks=True, sample_rate=sess._rate(sample_rate), loudness=spec, limit=lim, **kw, **wm)
         rate = sess._rate(sample_rate)
-        audio, ol = sess._model.synthesize_batch(*args, loudness=None if rate else spec, limit=None if rate else lim, **kw)
+        audio, ol = sess._model.synthesize_batch(*args, loudness=None if rate else spec, limit=None if rate else lim, **kw, **({} if rate else wm))
         if not rate:
             return audio, ol, None
         audio, ol = sess.resample(audio, ol, rate)
-        return sess.normalize(audio, ol, rate, spec, lim), ol, None
+        return sess.normalize(sess.mark(audio, ol, wm), ol, rate, spec, lim), ol, None
 
     def _run_shard_multistream(self, r, texts, idx, sids, scales, scale, seeds, per_request=False, sample_rate=None, denoiser_strength=None,
                                marks=False, loud=None):

@@ -328,6 +328,46 @@ def set_intonation(opts, pitch_range, flag=FLAG_INTONATION):
     opts.flags |= flag
 
 
+# include/vits_watermark.h
+FLAG_WATERMARK = 256             # VITS_FLAG_WATERMARK (STTS_FLAG_WATERMARK has the same value)
+WATERMARK_MAX_DEPTH_DB = 2.0     # VITS_WATERMARK_MAX_DEPTH_DB
+WATERMARK_THRESHOLD = 6.0        # VITS_WATERMARK_THRESHOLD
+WATERMARK_OFFSETS = 128          # VITS_WATERMARK_OFFSETS
+WATERMARK_FIELDS = [("watermark_key", ctypes.c_uint32), ("watermark_depth_db", ctypes.c_float)]
+
+
+class SynthWatermarkOpts(SynthIntonationOpts):
+    """mirror of `struct vits_synth_opts_watermark` (include/vits_watermark.h): SynthIntonationOpts followed by the key and the depth,
+    which the library reads only under VITS_FLAG_WATERMARK"""
+
+    _fields_ = WATERMARK_FIELDS
+
+
+def watermark_spec(watermark=None, depth_db=None):
+    """The mark a call asks for -> None (none) or (key, depth_db) as vits_synth_opts_watermark carries it (depth 0 = the default,
+    1 dB).  watermark: the 32-bit key (a selector, not a secret).  ValueError names a key outside [0, 2^32) or a depth outside (0, 2] dB
+    (NaN included), as the library's VITS_ERR_ARG does for the depth: here before any device work."""
+    if watermark is None or watermark is False:
+        return None
+    if isinstance(watermark, bool) or not isinstance(watermark, (int, np.integer)):
+        raise ValueError(f"watermark={watermark!r}: a key is an integer in [0, 2^32)")
+    key = int(watermark)
+    if not 0 <= key < 1 << 32:
+        raise ValueError(f"watermark key {key} outside [0, 2^32)")
+    d = 0.0 if depth_db is None else float(depth_db)
+    if depth_db is not None and not 0.0 < d <= WATERMARK_MAX_DEPTH_DB:
+        raise ValueError(f"watermark_depth_db {d} outside (0, {WATERMARK_MAX_DEPTH_DB:g}]")
+    return (key, d)
+
+
+def set_watermark(opts, spec, flag=FLAG_WATERMARK):
+    """Sets the flag and the two fields of a SynthWatermarkOpts / SttsWatermarkOpts from a watermark_spec()"""
+    if spec is None:
+        return
+    opts.watermark_key, opts.watermark_depth_db = spec
+    opts.flags |= flag
+
+
 class PersistInfo(ctypes.Structure):
     """mirror of `struct vits_persist_info` (vits_persist_state)"""
 
@@ -453,6 +493,7 @@ class VitsLib:
         self.has_contour = False
         self.has_document = False
         self.has_intonation = False
+        self.has_watermark = False
         if self.is_device:
             c_i16p = ctypes.POINTER(ctypes.c_int16)
             f("synthesize_pcm16").argtypes = [ctypes.c_void_p, c_i64p, c_i64p, ctypes.c_int32, ctypes.c_int32, c_f32p, c_i64p,
@@ -570,6 +611,12 @@ class VitsLib:
                                                            ctypes.POINTER(c_i16p), c_i64p, c_i64p]
                 f("op_document_join").argtypes = [ctypes.c_int, c_f32p, c_i64p, ctypes.c_int32, ctypes.c_int64, ctypes.c_int32,
                                                   ctypes.POINTER(Document), c_f32p, ctypes.c_int64, c_i64p, c_i32p, c_i32p]
+            # include/vits_watermark.h: the keyed audio watermark (the flag of the synthesize calls and the two doors)
+            self.has_watermark = self.has("op_watermark")
+            if self.has_watermark:
+                f("op_watermark").argtypes = [ctypes.c_int, c_f32p, c_i64p, ctypes.c_int32, ctypes.c_int64, ctypes.c_uint32, ctypes.c_float, c_f32p]
+                f("op_watermark_detect").argtypes = [ctypes.c_int, c_f32p, c_i64p, ctypes.c_int32, ctypes.c_int64, ctypes.c_uint32,
+                                                     ctypes.POINTER(ctypes.c_double), c_i32p, c_i32p, ctypes.POINTER(ctypes.c_double)]
             if self.has("debug_clock_probe"):
                 f("debug_clock_probe").argtypes = [ctypes.c_int, ctypes.c_int32, ctypes.POINTER(ctypes.c_double), ctypes.c_int32]
 
@@ -964,6 +1011,35 @@ class VitsLib:
                                            lambda B, N: [np.empty((B, 256 * (2 * (N // 256 + 2) - 1)), np.float32),
                                                          np.empty((B, 2 * (N // 256 + 2) + 2), np.int64), np.empty((B, 1 + N // 256), np.int32)]))
 
+    # ---- keyed audio watermark (include/vits_watermark.h) ---------------------------
+    def _need_watermark(self):
+        if not self.has_watermark:
+            raise VitsError(4, "this backend has no audio watermark (include/vits_watermark.h)")
+
+    def op_watermark(self, x, lengths, key, depth_db=0.0, device=0):
+        """vits_op_watermark: x float32 [B, N], lengths [B], key uint32, depth_db (0 = 1 dB) -> y float32 [B, N]; item b marked on
+        [0, 256 * (lengths[b] // 256)), x from there up to lengths[b], zero beyond; an item below 513 samples as it went in"""
+        self._need_watermark()
+        return self._items_door("op_watermark", x, lengths, device, (int(key) & 0xFFFFFFFF, float(depth_db)), lambda B, N: [(B, N)])
+
+    def op_watermark_detect(self, x, lengths, key, device=0):
+        """vits_op_watermark_detect: x float32 [B, N], lengths [B] -> (z float64 [B], offset int32 [B] in samples, rows int32 [B],
+        z_all float64 [B, 128]); detected iff z >= WATERMARK_THRESHOLD"""
+        self._need_watermark()
+        x = _f32(x)
+        if x.ndim != 2:
+            raise ValueError("x must be [B, N]")
+        B, N = x.shape
+        lengths = _i64(lengths).reshape(-1)
+        if lengths.shape != (B,):
+            raise ValueError("lengths must be [B]")
+        z, z_all = np.empty(B, np.float64), np.empty((B, WATERMARK_OFFSETS), np.float64)
+        off, rows = np.empty(B, np.int32), np.empty(B, np.int32)
+        c_f64p = ctypes.POINTER(ctypes.c_double)
+        self.check(self._fn("op_watermark_detect")(device, _p(x, c_f32p), _p(lengths, c_i64p), B, N, int(key) & 0xFFFFFFFF, _p(z, c_f64p),
+                                                   _p(off, c_i32p), _p(rows, c_i32p), _p(z_all, c_f64p)))
+        return z, off, rows, z_all
+
     # ---- prosody controls (include/vits_prosody.h) ------------------------------
     def _need_prosody(self):
         if not self.has_prosody:
@@ -1039,14 +1115,16 @@ class VitsModel:
 
     def _opts(self, B, Tx, noise_dp, noise_prior, forced_durations, seed, max_frames, solo=False, item_seeds=None, bert=None,
               loudness=None, loudness_out=None, pitch=None, preserve_formants=False, limit=None, prosody=None, prosody_out=None, contour=None,
-              pitch_range=None):
+              pitch_range=None, watermark=None):
         pitch = pitch_spec(pitch)  # (None, or a shift that does not reduce to P = Q)
         pitch_range = range_spec(pitch_range)  # (None, or a range whose r_m is not 1000)
         if contour is not None:
             self.lib._need_contour()
         if pitch_range is not None:
             self.lib._need_intonation()
-        opts = SynthIntonationOpts() if pitch_range is not None else SynthContourOpts() if contour is not None else SynthProsodyOpts() if prosody is not None else SynthLimitOpts() if limit is not None else SynthOpts() if pitch is None else SynthPitchOpts()
+        if watermark is not None:  # (a watermark_spec())
+            self.lib._need_watermark()
+        opts = SynthWatermarkOpts() if watermark is not None else SynthIntonationOpts() if pitch_range is not None else SynthContourOpts() if contour is not None else SynthProsodyOpts() if prosody is not None else SynthLimitOpts() if limit is not None else SynthOpts() if pitch is None else SynthPitchOpts()
         keep = []
         if prosody is not None:
             self.lib._need_prosody()
@@ -1093,6 +1171,7 @@ class VitsModel:
         set_prosody(opts, keep, prosody, B, prosody_out)
         set_contour(opts, keep, contour)
         set_intonation(opts, pitch_range)
+        set_watermark(opts, watermark)
         return opts, keep
 
     # ---- the hot path -----------------------------------------------------
@@ -1108,8 +1187,12 @@ class VitsModel:
     def synthesize(self, ids, lengths, scales, sid, noise_dp=None, noise_prior=None, forced_durations=None, seed=0,
                    max_frames=0, solo=False, item_seeds=None, bert=None, sample_rate=None, marks=False, loudness=None, loudness_out=None,
                    pitch=None, preserve_formants=False, limit=None, item_scales=None, token_length_scale=None, token_pause=None,
-                   fit_frames=None, fit_ratio=False, token_pitch=None, token_gain_db=None, pitch_range=None):
-        """pitch_range: r in [0, 4] (VITS_FLAG_INTONATION, include/vits_intonation.h): how far every item moves about its own median pitch,
+                   fit_frames=None, fit_ratio=False, token_pitch=None, token_gain_db=None, pitch_range=None, watermark=None,
+                   watermark_depth_db=None):
+        """watermark: a 32-bit key (VITS_FLAG_WATERMARK, include/vits_watermark.h): every item marked on the device behind the resampler,
+        in front of the loudness stage, the limiter and the int16 conversion; watermark_depth_db in (0, 2], default 1.  Lengths and marks
+        do not change.
+        pitch_range: r in [0, 4] (VITS_FLAG_INTONATION, include/vits_intonation.h): how far every item moves about its own median pitch,
         times r, from an F0 track of the finished waveform on the device; 0 is a monotone, 1 the call as it was.  Lengths and marks do not
         change.  Not with preserve_formants.
         token_pitch / token_gain_db: float [B, T_x] semitones / dB per token (VITS_FLAG_CONTOUR, include/vits_contour.h): every token
@@ -1140,7 +1223,8 @@ class VitsModel:
         pros_out = {}
         opts, keep = self._opts(B, Tx, noise_dp, noise_prior, forced_durations, seed, max_frames, solo, item_seeds, bert, loudness, loudness_out,
                                 pitch, preserve_formants, limit, prosody_arrays(B, Tx, item_scales, token_length_scale, token_pause, fit_frames),
-                                pros_out, contour_arrays(B, Tx, token_pitch, token_gain_db, lengths, pitch_spec(pitch)), pitch_range)
+                                pros_out, contour_arrays(B, Tx, token_pitch, token_gain_db, lengths, pitch_spec(pitch)), pitch_range,
+                                watermark_spec(watermark, watermark_depth_db))
         out = c_f32p()
         ns = ctypes.c_int64()
         olen = np.zeros(B, dtype=np.int64)
@@ -1170,8 +1254,9 @@ class VitsModel:
     def synthesize_pcm16(self, ids, lengths, scales, sid, pcm_scale=1.0, noise_dp=None, noise_prior=None, forced_durations=None,
                          seed=0, max_frames=0, solo=False, item_seeds=None, bert=None, sample_rate=None, marks=False, loudness=None,
                          loudness_out=None, pitch=None, preserve_formants=False, limit=None, item_scales=None, token_length_scale=None,
-                         token_pause=None, fit_frames=None, fit_ratio=False, token_pitch=None, token_gain_db=None, pitch_range=None):
-        """pitch, preserve_formants, limit, item_scales, token_length_scale, token_pause, fit_frames, fit_ratio, token_pitch,
+                         token_pause=None, fit_frames=None, fit_ratio=False, token_pitch=None, token_gain_db=None, pitch_range=None,
+                         watermark=None, watermark_depth_db=None):
+        """watermark, watermark_depth_db, pitch, preserve_formants, limit, item_scales, token_length_scale, token_pause, fit_frames, fit_ratio, token_pitch,
         token_gain_db, pitch_range: as for synthesize.
         synthesize() with Synth.synth_audio's `* scale` and audio_float_to_int16 (vosk_tts/synth.py:127-130) done on the
         device: returns (pcm int16 [B,S], out_lengths int64 [B]).  sample_rate: as for synthesize (vits_synthesize_pcm16_rate:
@@ -1185,7 +1270,8 @@ class VitsModel:
         pros_out = {}
         opts, keep = self._opts(B, Tx, noise_dp, noise_prior, forced_durations, seed, max_frames, solo, item_seeds, bert, loudness, loudness_out,
                                 pitch, preserve_formants, limit, prosody_arrays(B, Tx, item_scales, token_length_scale, token_pause, fit_frames),
-                                pros_out, contour_arrays(B, Tx, token_pitch, token_gain_db, lengths, pitch_spec(pitch)), pitch_range)
+                                pros_out, contour_arrays(B, Tx, token_pitch, token_gain_db, lengths, pitch_spec(pitch)), pitch_range,
+                                watermark_spec(watermark, watermark_depth_db))
         out = ctypes.POINTER(ctypes.c_int16)()
         ns = ctypes.c_int64()
         olen = np.zeros(B, dtype=np.int64)
@@ -1218,12 +1304,12 @@ class VitsModel:
                             trim_db=None, trim_keep_frames=0, marks=False, seed=0, max_frames=0, item_seeds=None, bert=None, sample_rate=None,
                             loudness=None, loudness_out=None, pitch=None, preserve_formants=False, limit=None, item_scales=None,
                             token_length_scale=None, token_pause=None, fit_frames=None, token_pitch=None, token_gain_db=None, pitch_range=None,
-                            forced_durations=None):
+                            forced_durations=None, watermark=None, watermark_depth_db=None):
         """vits_synthesize_document / _pcm16 (include/vits_document.h): the B items of one SOLO batch call joined on the device into one
         piece of audio, in front of the resampler, the loudness stage, the limiter and the int16 conversion.  Returns (audio float32 or
         int16 [S], info): info["seg_start"] / ["seg_end"] int64 [B] in output samples, info["trim"] int32 [B, 2] frames, and with
         marks=True info["token_ends"] int64 [B, T_x].  The per-item keywords are those of synthesize; loudness_out receives ONE value per
-        key, of the whole document."""
+        key, of the whole document.  watermark: the document is marked as the one item it has become."""
         self.lib._need_document()
         ids = _i64(ids)
         B, Tx = ids.shape
@@ -1233,7 +1319,8 @@ class VitsModel:
         pros_out = {}
         opts, keep = self._opts(B, Tx, None, None, forced_durations, seed, max_frames, True, item_seeds, bert, loudness, loudness_out,
                                 pitch, preserve_formants, limit, prosody_arrays(B, Tx, item_scales, token_length_scale, token_pause, fit_frames),
-                                pros_out, contour_arrays(B, Tx, token_pitch, token_gain_db, lengths, pitch_spec(pitch)), pitch_range)
+                                pros_out, contour_arrays(B, Tx, token_pitch, token_gain_db, lengths, pitch_spec(pitch)), pitch_range,
+                                watermark_spec(watermark, watermark_depth_db))
         d, dkeep, info = document_struct(B, lead_frames, gap_frames, fade_samples, trim_db, trim_keep_frames)
         rate = self._rate(sample_rate)
         ends = np.zeros((B, Tx), np.int64) if marks else None
@@ -1258,8 +1345,9 @@ class VitsModel:
 
     def stream(self, ids, scales, sid, chunk_frames=64, noise_dp=None, noise_prior=None, forced_durations=None, seed=0, bert=None,
                sample_rate=None, on_marks=None, loudness=None, pitch=None, limit=None, item_scales=None, token_length_scale=None,
-               token_pause=None, fit_frames=None, fit_ratio=None):
-        """item_scales [1, 3], token_length_scale [1, T_x], token_pause [1, T_x], fit_frames [1]: the prosody controls of synthesize
+               token_pause=None, fit_frames=None, fit_ratio=None, watermark=None):
+        """watermark: refused (vits_stream_open* refuse VITS_FLAG_WATERMARK the same way: a stream has no tail).
+        item_scales [1, 3], token_length_scale [1, T_x], token_pause [1, T_x], fit_frames [1]: the prosody controls of synthesize
         (the open runs the controlled regulator; total_samples and the marks reflect them); fit_ratio: called once with the ratio,
         float32 [1], as soon as the stream is open.
         limit: refused, as loudness is (vits_stream_open* refuse VITS_FLAG_LIMIT).
@@ -1278,6 +1366,8 @@ class VitsModel:
                                "before the first chunk")
         if pitch_spec(pitch) is not None:
             raise VitsError(4, "a stream cannot be pitch-shifted: the phase recursion needs the frames before a chunk")
+        if watermark_spec(watermark) is not None:
+            raise VitsError(4, "a stream cannot be watermarked (VITS_FLAG_WATERMARK): the mark is a stage of the output tail, and a stream has none")
         if on_marks is not None:
             self.lib._need_marks()
         if not self.lib.has("stream_open"):

@@ -6,7 +6,7 @@ import ctypes
 import numpy as np
 
 from .capi import (LIMIT_FIELDS, Contour, VitsError, VitsLib, _f32, _i32, _i64, _p, c_f32p, c_i32p, c_i64p, contour_arrays, pitch_spec,
-                   range_spec, set_contour, set_intonation, set_limit, set_loudness)
+                   range_spec, set_contour, set_intonation, set_limit, set_loudness, set_watermark, watermark_spec)
 from .weights_stts import SttsHParams
 
 
@@ -69,6 +69,16 @@ class SttsIntonationOpts(SttsContourOpts):
     library reads only under STTS_FLAG_INTONATION"""
 
     _fields_ = [("pitch_range", ctypes.c_float)]
+
+
+STTS_FLAG_WATERMARK = 256     # include/vits_watermark.h
+
+
+class SttsWatermarkOpts(SttsIntonationOpts):
+    """mirror of `struct stts_synth_opts_watermark` (include/vits_watermark.h): SttsIntonationOpts followed by the key and the depth, which
+    the library reads only under STTS_FLAG_WATERMARK"""
+
+    _fields_ = [("watermark_key", ctypes.c_uint32), ("watermark_depth_db", ctypes.c_float)]
 
 
 class SttsModel:
@@ -166,24 +176,28 @@ class SttsModel:
         assert isinstance(opts, SttsLimitOpts)
         set_limit(opts, keep, spec, B, STTS_FLAG_LIMIT, out)
 
-    def _opts_for(self, loudness, pitch, preserve_formants=False, limit=None, contour=None, pitch_range=None):
+    def _opts_for(self, loudness, pitch, preserve_formants=False, limit=None, contour=None, pitch_range=None, watermark=None):
         """the options struct a call needs: the plain one, the one with the loudness fields, the one with the pitch behind those, the
         one with the limiter behind that, the one with the contour pointer behind that, or the one with pitch_range (a range_spec(),
-        include/vits_intonation.h) last; preserve_formants sets its bit only with a pitch in effect"""
+        include/vits_intonation.h), or the one with the watermark's key and depth (a capi.watermark_spec(), include/vits_watermark.h) last;
+        preserve_formants sets its bit only with a pitch in effect"""
+        if watermark is not None and not getattr(self.vlib, "has_watermark", False):
+            raise VitsError(4, "this backend has no audio watermark (include/vits_watermark.h)")
         if pitch_range is not None and not getattr(self.vlib, "has_intonation", False):
             raise VitsError(4, "this backend has no intonation control (include/vits_intonation.h)")
         if limit is not None and not getattr(self.vlib, "has_limit", False):
             raise VitsError(4, "this backend has no peak limiter (include/vits_limit.h)")
         if contour is not None and not getattr(self.vlib, "has_contour", False):
             raise VitsError(4, "this backend has no pitch / volume contours (include/vits_contour.h)")
-        if pitch_spec(pitch) is not None or limit is not None or contour is not None or pitch_range is not None:
+        if pitch_spec(pitch) is not None or limit is not None or contour is not None or pitch_range is not None or watermark is not None:
             if pitch_spec(pitch) is not None and not getattr(self.vlib, "has_pitch", False):
                 raise VitsError(4, "this backend has no pitch shifter (include/vits_pitch.h)")
             if pitch_spec(pitch) is not None and preserve_formants and not getattr(self.vlib, "has_pitch_formant", False):
                 raise VitsError(4, "this backend has no formant-preserving pitch shift (include/vits_pitch.h, STTS_FLAG_PITCH_FORMANT)")
-            opts = (SttsIntonationOpts() if pitch_range is not None else SttsContourOpts() if contour is not None
+            opts = (SttsWatermarkOpts() if watermark is not None else SttsIntonationOpts() if pitch_range is not None else SttsContourOpts() if contour is not None
                     else SttsPitchOpts() if limit is None else SttsLimitOpts())
             set_intonation(opts, pitch_range, STTS_FLAG_INTONATION)
+            set_watermark(opts, watermark, STTS_FLAG_WATERMARK)
             if pitch_spec(pitch) is None:
                 return opts
             opts.flags |= STTS_FLAG_PITCH | (STTS_FLAG_PITCH_FORMANT if preserve_formants else 0)
@@ -199,8 +213,10 @@ class SttsModel:
     def synthesize(self, ids, scales, sid, bert=None, phone_duration_extra=None, noise=None, seed=0, n_timesteps=0,
                    want_audio=True, want_mel=True, denoiser_strength=None, denoiser_filter_length=0, marks=False, sample_rate=None,
                    loudness=None, loudness_out=None, pitch=None, preserve_formants=False, limit=None, token_pitch=None, token_gain_db=None,
-                   pitch_range=None):
-        """pitch_range: r in [0, 4] (STTS_FLAG_INTONATION, include/vits_intonation.h): the utterance's movement about its own median pitch
+                   pitch_range=None, watermark=None, watermark_depth_db=None):
+        """watermark: a 32-bit key (STTS_FLAG_WATERMARK, include/vits_watermark.h): the audio marked behind the resampler, in front of the
+        loudness stage and the limiter; watermark_depth_db in (0, 2], default 1.
+        pitch_range: r in [0, 4] (STTS_FLAG_INTONATION, include/vits_intonation.h): the utterance's movement about its own median pitch
         times r; 1 is the call as it was.
         token_pitch / token_gain_db: float [T] semitones / dB per token (STTS_FLAG_CONTOUR, include/vits_contour.h): every token raised
         or lowered by its own amount, in the pitch stage's place; `pitch` is added to every token.  Lengths and marks do not change.
@@ -229,7 +245,8 @@ class SttsModel:
             con = contour_arrays(1, T, None if token_pitch is None else _f32(token_pitch).reshape(1, -1),
                                  None if token_gain_db is None else _f32(token_gain_db).reshape(1, -1), None, pitch_spec(pitch))
         opts = self._opts_for(loudness, pitch if want_audio else None, preserve_formants, limit if want_audio else None, con,
-                              range_spec(pitch_range) if want_audio else None)
+                              range_spec(pitch_range) if want_audio else None,
+                              watermark_spec(watermark, watermark_depth_db) if want_audio else None)
         set_contour(opts, keep, con, STTS_FLAG_CONTOUR)
         if noise is not None:
             a = _f32(noise); keep.append(a)
@@ -269,8 +286,8 @@ class SttsModel:
         return (audio, melo, ends) if marks else (audio, melo)
 
     def stream(self, ids, scales, sid, bert=None, phone_duration_extra=None, seed=0, n_timesteps=0, chunk_frames=64,
-               denoiser_strength=None, denoiser_filter_length=0, on_marks=None, loudness=None, pitch=None, limit=None):
-        """pitch, limit: refused, as loudness is.
+               denoiser_strength=None, denoiser_filter_length=0, on_marks=None, loudness=None, pitch=None, limit=None, watermark=None):
+        """pitch, limit, watermark: refused, as loudness is.
         Streaming form of synthesize() (stts_stream_open): a generator of float32 chunks of chunk_frames*hop samples whose
         concatenation equals synthesize()'s audio for the same arguments.  on_marks: called once with token_ends int64 [T]
         (vits_stream_marks) as soon as the stream is open.  loudness: refused (stts_stream_open refuses STTS_FLAG_LOUDNESS the same
@@ -283,6 +300,8 @@ class SttsModel:
                                "before the first chunk")
         if pitch_spec(pitch) is not None:
             raise VitsError(4, "a stream cannot be pitch-shifted: the phase recursion needs the frames before a chunk")
+        if watermark_spec(watermark) is not None:
+            raise VitsError(4, "a stream cannot be watermarked (STTS_FLAG_WATERMARK): the mark is a stage of the output tail, and a stream has none")
         if on_marks is not None:
             self._need_marks()
         if self._vocoder is None:
@@ -316,8 +335,9 @@ class SttsModel:
 
     def synthesize_batch(self, ids, lengths, scales, sid, bert=None, phone_duration_extra=None, seed=0, n_timesteps=0, item_seeds=None,
                          denoiser_strength=None, denoiser_filter_length=0, marks=False, sample_rate=None, loudness=None, loudness_out=None,
-                         pitch=None, preserve_formants=False, limit=None, token_pitch=None, token_gain_db=None, pitch_range=None):
-        """token_pitch / token_gain_db: float [B, T], as for synthesize; pitch_range: as for synthesize, one value for the batch.
+                         pitch=None, preserve_formants=False, limit=None, token_pitch=None, token_gain_db=None, pitch_range=None,
+                         watermark=None, watermark_depth_db=None):
+        """token_pitch / token_gain_db: float [B, T], as for synthesize; pitch_range, watermark: as for synthesize, one value for the batch.
         pitch, preserve_formants, limit: as for synthesize, one value for the batch; every item is shifted from its own length.
         B independent utterances in one pass (stts_synthesize_batch): ids [B,5,T], lengths [B], sid [B];
         returns (audio float32 [B,S] zero-padded, out_lengths int64 [B] in samples).  Item b equals
@@ -329,7 +349,7 @@ class SttsModel:
             raise ValueError("sample_rate is an argument of the marks call (SttsSession.resample serves the call without marks)")
         B, T, head, keep = self._batch_head(ids, lengths, scales, sid, bert, phone_duration_extra, seed, n_timesteps, item_seeds, denoiser_strength,
                                             denoiser_filter_length, loudness, loudness_out, pitch, preserve_formants, limit, token_pitch,
-                                            token_gain_db, pitch_range)
+                                            token_gain_db, pitch_range, watermark=watermark_spec(watermark, watermark_depth_db))
         au = c_f32p(); ns = ctypes.c_int64(); ol = np.zeros(B, np.int64)
         ends = np.zeros((B, T), np.int64) if marks else None
         if marks:
@@ -343,7 +363,7 @@ class SttsModel:
 
     def _batch_head(self, ids, lengths, scales, sid, bert, phone_duration_extra, seed, n_timesteps, item_seeds, denoiser_strength,
                     denoiser_filter_length, loudness, loudness_out, pitch, preserve_formants, limit, token_pitch, token_gain_db, pitch_range,
-                    results=None):
+                    results=None, watermark=None):
         """the leading arguments of the batch entry points -> (B, T, head, keep); results: how many result values the loudness / limiter
         outputs hold (default B; 1 for a document)"""
         ids = _i64(ids); lengths = _i64(lengths); sid = _i64(sid); scales = _f32(scales)
@@ -351,7 +371,7 @@ class SttsModel:
         b = None if bert is None else _f32(bert)
         p = None if phone_duration_extra is None else _f32(phone_duration_extra)
         con = contour_arrays(B, T, token_pitch, token_gain_db, lengths, pitch_spec(pitch))
-        opts = self._opts_for(loudness, pitch, preserve_formants, limit, con, range_spec(pitch_range))
+        opts = self._opts_for(loudness, pitch, preserve_formants, limit, con, range_spec(pitch_range), watermark)
         opts.seed = seed; opts.n_timesteps = n_timesteps
         self._denoise(opts, denoiser_strength, denoiser_filter_length)
         keep = [ids, lengths, sid, scales, b, p, opts]
@@ -372,7 +392,8 @@ class SttsModel:
     def synthesize_document(self, ids, lengths, scales, sid, bert=None, phone_duration_extra=None, seed=0, n_timesteps=0, item_seeds=None,
                             denoiser_strength=None, denoiser_filter_length=0, marks=False, sample_rate=None, loudness=None, loudness_out=None,
                             pitch=None, preserve_formants=False, limit=None, token_pitch=None, token_gain_db=None, pitch_range=None,
-                            lead_frames=0, gap_frames=None, fade_samples=0, trim_db=None, trim_keep_frames=0):
+                            lead_frames=0, gap_frames=None, fade_samples=0, trim_db=None, trim_keep_frames=0, watermark=None,
+                            watermark_depth_db=None):
         """stts_synthesize_document (include/vits_document.h): the items of synthesize_batch joined into one piece of audio behind the
         pitch stage, in front of the resampler and the loudness / limiter stage, which see one item.  Returns (audio float32 [S], info):
         info["seg_start"] / ["seg_end"] int64 [B] in output samples, info["trim"] int32 [B, 2] frames, and with marks=True
@@ -383,7 +404,7 @@ class SttsModel:
             raise VitsError(4, "this backend has no documents (include/vits_document.h)")
         B, T, head, keep = self._batch_head(ids, lengths, scales, sid, bert, phone_duration_extra, seed, n_timesteps, item_seeds, denoiser_strength,
                                             denoiser_filter_length, loudness, loudness_out, pitch, preserve_formants, limit, token_pitch,
-                                            token_gain_db, pitch_range, results=1)
+                                            token_gain_db, pitch_range, results=1, watermark=watermark_spec(watermark, watermark_depth_db))
         d, dkeep, info = document_struct(B, lead_frames, gap_frames, fade_samples, trim_db, trim_keep_frames)
         au = c_f32p(); ns = ctypes.c_int64()
         ends = np.zeros((B, T), np.int64) if marks else None

@@ -56,6 +56,12 @@ _OPTIONS = (
                             help="speak word INDEX DB decibels louder (-40 to 12); repeatable")),
     (("--pitch-range",), dict(type=float, default=None, metavar="R",
                               help="intonation range: how far the voice moves about its median pitch, 0 (monotone) to 4, 1 = unchanged")),
+    (("--watermark",), dict(type=lambda text: _key(text), default=None, metavar="KEY",
+                            help="mark the audio with this 32-bit key (decimal or 0x...), a +-1 dB spectral ripple that --detect-watermark "
+                                 "recognises; a selector, not a secret")),
+    (("--detect-watermark",), dict(type=str, default=None, metavar="FILE",
+                                   help="instead of synthesising: look for the mark of --watermark KEY (default: the voice's "
+                                        "inference.watermark_key) in this 16-bit mono WAV and print detected, z and the offset in samples")),
     (("--ssml",), dict(action="store_true", help="the input is an SSML document: speak, p, s, sub, break, prosody, mark")),
     (("--document",), dict(action="store_true",
                            help="the input is a document: split into sentences and paragraphs (blank lines), synthesised as one batch and "
@@ -68,6 +74,32 @@ _OPTIONS = (
                         help="also write the speech marks as JSON: rate, phonemes and words with their offsets in samples and seconds")),
     (("--log-level",), dict(default="INFO", metavar="LEVEL", help="python logging level (INFO shows the RTF line)")),
 )
+
+
+def _key(text):
+    """a watermark key on the command line: decimal or 0x-prefixed, in [0, 2^32)"""
+    try:
+        k = int(text, 0)
+    except ValueError:
+        raise argparse.ArgumentTypeError(f"{text!r}: a key is an integer, decimal or 0x...")
+    if not 0 <= k < 1 << 32:
+        raise argparse.ArgumentTypeError(f"key {k} outside [0, 2^32)")
+    return k
+
+
+def detect_watermark(synth, path, key):
+    """--detect-watermark: the triple of Synth.detect_watermark for a 16-bit mono WAV, printed as one JSON line"""
+    import wave
+
+    import numpy as np
+
+    with wave.open(path, "r") as f:
+        if f.getsampwidth() != 2 or f.getnchannels() != 1:
+            raise SystemExit(f"--detect-watermark {path}: a 16-bit mono WAV is expected")
+        pcm = np.frombuffer(f.readframes(f.getnframes()), np.int16)
+    detected, z, offset = synth.detect_watermark(pcm, key)
+    print(json.dumps({"detected": detected, "z": round(z, 3), "offset_samples": offset}))
+    return 0
 
 
 def build_parser():
@@ -99,13 +131,17 @@ def run(opts):
         if wanted:
             action()
             return 0
-    if not opts.input:
+    detect = getattr(opts, "detect_watermark", None)
+    if not opts.input and not detect:
         logging.info("Please specify input text or file")
         return 1
     from .synth import Synth
 
     voice = model_mod.Model(opts.model, opts.model_name, opts.lang)
     synth = Synth(voice)
+    if detect:
+        return detect_watermark(synth, detect, getattr(opts, "watermark", None))
+    wm = {} if getattr(opts, "watermark", None) is None else {"watermark": opts.watermark}
     if getattr(opts, "document", False):  # many sentences in one call (Synth.synth_document); the per-word flags index one utterance
         import wave
 
@@ -117,7 +153,7 @@ def run(opts):
                  trim_db=opts.trim_db, speech_rate=opts.speech_rate, sample_rate=opts.sample_rate, denoiser_strength=opts.denoiser_strength,
                  marks=bool(opts.marks), loudness=opts.loudness, peak=opts.peak, pitch=opts.pitch, preserve_formants=opts.preserve_formants,
                  **({} if opts.limit is None else {"limit": opts.limit}),
-                 **({} if getattr(opts, "pitch_range", None) is None else {"pitch_range": opts.pitch_range}))
+                 **({} if getattr(opts, "pitch_range", None) is None else {"pitch_range": opts.pitch_range}), **wm)
         audio, marks = res if opts.marks else (res, None)
         with wave.open(opts.output, "w") as f:
             f.setnchannels(1)
@@ -136,7 +172,7 @@ def run(opts):
                                denoiser_strength=opts.denoiser_strength, marks=bool(opts.marks), loudness=opts.loudness, peak=opts.peak,
                                pitch=opts.pitch, **({} if opts.limit is None else {"limit": opts.limit}),
                                **({} if getattr(opts, "pitch_range", None) is None else {"pitch_range": opts.pitch_range}),
-                               **({} if getattr(opts, "duration", None) is None else {"duration": opts.duration}))
+                               **({} if getattr(opts, "duration", None) is None else {"duration": opts.duration}), **wm)
         audio, marks = res if opts.marks else (res, None)
         with wave.open(opts.output, "w") as f:
             f.setnchannels(1)
@@ -154,7 +190,7 @@ def run(opts):
                                                     ("word_rates", _indexed(getattr(opts, "word_rate", None), "--word-rate")),
                                                     ("word_pitch", _indexed(getattr(opts, "word_pitch", None), "--word-pitch", "=")),
                                                     ("word_gains", _indexed(getattr(opts, "word_gain", None), "--word-gain", "=")),
-                                                    ("pitch_range", getattr(opts, "pitch_range", None))) if v is not None})
+                                                    ("pitch_range", getattr(opts, "pitch_range", None))) if v is not None}, **wm)
     if opts.marks:
         with open(opts.marks, "w", encoding="utf-8") as f:
             f.write(marks.to_json(indent=1) + "\n")

@@ -139,6 +139,7 @@ static int persist_cfg() {
 #include "pitch.hip.h"
 #include "contour.hip.h"
 #include "document.hip.h"
+#include "watermark.hip.h"
 #include "out_tail.hip.h"
 #include "marks.hip.h"
 

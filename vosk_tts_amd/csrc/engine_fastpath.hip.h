@@ -391,6 +391,7 @@ static int synth_fast(vits_model* m, const int64_t* ids, const int64_t* lengths,
   HIP_TRY(hipSetDevice(m->device));
   TailReq q = req;  // (its table: uploaded on the first call at this rate, before any capture)
   if (q.rate) TRY(resample_get(m->device, hp.sampling_rate, q.rate, &q.T));
+  if (q.wm.on) TRY(wm_get(m->device, &q.wm.T));  // (include/vits_watermark.h: the denoiser's tables, as early)
   const ResampleTab* T = q.T;
   const NormReq& lq = q.norm;
   const bool pcm = q.pcm;
@@ -506,8 +507,8 @@ static int synth_fast(vits_model* m, const int64_t* ids, const int64_t* lengths,
     if (token_ends) for (int b = 0; b < B; ++b) memcpy(token_ends + (size_t)b * Tx, F->marks_h + (size_t)b * TxB, sizeof(int64_t) * Tx);  // (bucket columns dropped)
     return VITS_OK;
   };
-  if (q.pitch.on || q.contour.on || q.doc.on) {
-    // include/vits_pitch.h, vits_contour.h, vits_document.h: the float, native-rate form of the graph as it is, then the tail (out_tail.hip.h) as launches
+  if (q.pitch.on || q.contour.on || q.doc.on || q.wm.on) {
+    // include/vits_pitch.h, vits_contour.h, vits_document.h, vits_watermark.h: the float, native-rate form of the graph as it is, then the tail (out_tail.hip.h) as launches
     // behind it on the same stream, in buffers of this call (the graph's own copy of the unshifted float audio to the host is not used)
     std::vector<long long> h_len(B);
     for (int b = 0; b < B; ++b) h_len[b] = F->h_ylen[b] * hp.hop_length;
@@ -580,6 +581,7 @@ static int synth_eager(vits_model* m, const int64_t* ids, const int64_t* lengths
   const vits_hparams& hp = m->hp;
   TailReq q = req;
   if (q.rate) TRY(resample_get(m->device, hp.sampling_rate, q.rate, &q.T));
+  if (q.wm.on) TRY(wm_get(m->device, &q.wm.T));  // (include/vits_watermark.h: the denoiser's tables, as early)
   const ResampleTab* T = q.T;
   std::vector<float> res((size_t)B * 4);  // (the last stage's result rows: declared before the stage, whose end waits for the stream)
   HostStage hs(m);

@@ -1,16 +1,17 @@
 // out_tail.hip.h -- the output tail: what a synthesize call asks of the stages behind the decoder (TailReq, built by tail_req from the
-// plain fields behind the option flags), and the one runner of the chain  pitch / contour / intonation -> resample -> normalise / limit -> int16  on the device
-// (tail_run).  The kernels and their launches are those of resample / loudness / limit / pitch / contour.hip.h; this file only orders them.
-// Part of the ONE translation unit engine.hip (included there, behind limit.hip.h, pitch.hip.h and contour.hip.h; not a standalone header).
+// plain fields behind the option flags), and the one runner of the chain  pitch / contour / intonation -> resample -> watermark -> normalise / limit -> int16
+// on the device (tail_run).  The kernels and their launches are those of resample / loudness / limit / pitch / contour / watermark.hip.h; this file
+// only orders them.
+// Part of the ONE translation unit engine.hip (included there, behind limit.hip.h, pitch.hip.h, contour.hip.h and watermark.hip.h; not a standalone header).
 #pragma once
 
 // ---- the request ----------------------------------------------------------------------------------------------------------
 // The flag bits and the name of an API family: the two families number the same four flags differently.
-struct TailFamily { const char* name; uint32_t loudness, limit, pitch, formant, contour, intonation; };
+struct TailFamily { const char* name; uint32_t loudness, limit, pitch, formant, contour, intonation, watermark; };
 static const TailFamily TAIL_VITS = {"VITS", VITS_FLAG_LOUDNESS, VITS_FLAG_LIMIT, VITS_FLAG_PITCH, VITS_FLAG_PITCH_FORMANT, VITS_FLAG_CONTOUR,
-                                     VITS_FLAG_INTONATION};
+                                     VITS_FLAG_INTONATION, VITS_FLAG_WATERMARK};
 static const TailFamily TAIL_STTS = {"STTS", STTS_FLAG_LOUDNESS, STTS_FLAG_LIMIT, STTS_FLAG_PITCH, STTS_FLAG_PITCH_FORMANT, STTS_FLAG_CONTOUR,
-                                     STTS_FLAG_INTONATION};
+                                     STTS_FLAG_INTONATION, STTS_FLAG_WATERMARK};
 
 // The values behind the flags of a call, flat.  A group is meaningful only where its `on` is set (`formant` is the bare flag bit).
 struct TailFields {
@@ -29,11 +30,14 @@ struct TailFields {
   const vits_contour* contour = nullptr;
   bool inton_on = false;
   float pitch_range = 1.f;
+  bool wm_on = false;
+  uint32_t wm_key = 0;
+  float wm_depth_db = 0.f;
 };
 
 // The only two places that cast down the `base` chain of the extended option structs: a struct's own fields are read under its flag
 // alone, so a caller who sets no flag may pass the plain struct (include/vits_loudness.h, vits_pitch.h, vits_limit.h).
-template <typename Pitch, typename Limit, typename Contour, typename Inton, typename Loud, typename Opts>
+template <typename Pitch, typename Limit, typename Contour, typename Inton, typename Wm, typename Loud, typename Opts>
 static TailFields tail_fields(const TailFamily& fam, const Opts* opts, const Loud* lo) {
   TailFields f;
   f.family = fam.name;
@@ -54,19 +58,27 @@ static TailFields tail_fields(const TailFamily& fam, const Opts* opts, const Lou
   if (f.contour_on) f.contour = reinterpret_cast<const Contour*>(opts)->contour;
   f.inton_on = (fl & fam.intonation) != 0;
   if (f.inton_on) f.pitch_range = reinterpret_cast<const Inton*>(opts)->pitch_range;
+  f.wm_on = (fl & fam.watermark) != 0;
+  if (f.wm_on) {
+    const Wm* wo = reinterpret_cast<const Wm*>(opts);
+    f.wm_key = wo->watermark_key; f.wm_depth_db = wo->watermark_depth_db;
+  }
   return f;
 }
 static TailFields tail_fields_vits(const vits_synth_opts* opts) {  // (the loudness fields are the plain struct's own)
   static_assert(offsetof(vits_synth_opts_limit, base) == 0 && offsetof(vits_synth_opts_pitch, base) == 0 && offsetof(vits_synth_opts_prosody, base) == 0 &&
-                    offsetof(vits_synth_opts_contour, base) == 0 && offsetof(vits_synth_opts_intonation, base) == 0,
+                    offsetof(vits_synth_opts_contour, base) == 0 && offsetof(vits_synth_opts_intonation, base) == 0 &&
+                    offsetof(vits_synth_opts_watermark, base) == 0,
                 "the extended options begin with the plain ones");
-  return tail_fields<vits_synth_opts_pitch, vits_synth_opts_limit, vits_synth_opts_contour, vits_synth_opts_intonation>(TAIL_VITS, opts, opts);
+  return tail_fields<vits_synth_opts_pitch, vits_synth_opts_limit, vits_synth_opts_contour, vits_synth_opts_intonation, vits_synth_opts_watermark>(
+      TAIL_VITS, opts, opts);
 }
 static TailFields tail_fields_stts(const stts_synth_opts* opts) {
   static_assert(offsetof(stts_synth_opts_limit, base) == 0 && offsetof(stts_synth_opts_pitch, base) == 0 && offsetof(stts_synth_opts_loudness, base) == 0 &&
-                    offsetof(stts_synth_opts_contour, base) == 0 && offsetof(stts_synth_opts_intonation, base) == 0,
+                    offsetof(stts_synth_opts_contour, base) == 0 && offsetof(stts_synth_opts_intonation, base) == 0 &&
+                    offsetof(stts_synth_opts_watermark, base) == 0,
                 "the extended options begin with the plain ones");
-  return tail_fields<stts_synth_opts_pitch, stts_synth_opts_limit, stts_synth_opts_contour, stts_synth_opts_intonation>(
+  return tail_fields<stts_synth_opts_pitch, stts_synth_opts_limit, stts_synth_opts_contour, stts_synth_opts_intonation, stts_synth_opts_watermark>(
       TAIL_STTS, opts, reinterpret_cast<const stts_synth_opts_loudness*>(opts));
 }
 
@@ -90,6 +102,8 @@ static int tail_refuse_stream(uint32_t flags, const TailFamily& fam) {
     return fail(VITS_ERR_UNSUPPORTED, "%s_FLAG_CONTOUR on a stream: the position recurrence and the phase recursion need the whole utterance before the first chunk", fam.name);
   if (flags & fam.intonation)
     return fail(VITS_ERR_UNSUPPORTED, "%s_FLAG_INTONATION on a stream: the median of the F0 track needs the whole utterance before the first chunk", fam.name);
+  if (flags & fam.watermark)
+    return fail(VITS_ERR_UNSUPPORTED, "%s_FLAG_WATERMARK on a stream: the mark is a stage of the output tail, and a stream has none (include/vits_watermark.h)", fam.name);
   return VITS_OK;
 }
 
@@ -102,6 +116,7 @@ struct TailReq {
   const IntonReq* inton_arg() const { return inton.on ? &inton : nullptr; }  // what contour_run takes
   const ResampleTab* T = nullptr;
   int rate = 0;
+  WmReq wm;  // (include/vits_watermark.h: behind the rate and the join, in front of `norm`)
   NormReq norm;
   bool pcm = false;
   float pcm_scale = 1.f;
@@ -121,6 +136,8 @@ static int tail_req(const vits_model* vocoder, const TailFields& f, int32_t samp
   TRY(lim_req(f.lim_on, f.lim_mode, f.lim_ceiling, f.lim_lookahead_ms, f.lim_release_ms, f.lim_gain, f.out_reduction, rate,
               out->norm.loud.on ? f.loud_ceiling : 0.f, &out->norm));
   TRY(tail_formant_check(f.formant, f.pitch_on, f.family));
+  if (f.wm_on && !vocoder) return fail(VITS_ERR_ARG, "no vocoder attached");
+  TRY(wm_req(f.wm_on, f.wm_key, f.wm_depth_db, &out->wm));
   if (!f.pitch_on) return VITS_OK;
   if (!vocoder) return fail(VITS_ERR_ARG, "no vocoder attached");
   return pitch_req(vocoder, f.semitones, f.formant, &out->pitch);
@@ -170,7 +187,7 @@ using TailBufs = DevBufs;  // op_door.hip.h
 
 // The tail of a vits_synthesize* call, as launches on `stream` from the float native-rate waveform x [B, S] on the device (item b is
 // len_y[b] * hop samples, h_len[b] on the host; its tokens' inclusive frame counts cum [B][cum_bstride] and their number tok_len [B] on the
-// device, read by a contoured call only): pitch or contour, resample, normalise and / or limit; the last stage that runs converts to int16
+// device, read by a contoured call only): pitch or contour, resample, watermark, normalise and / or limit; the last stage that runs converts to int16
 // where q.pcm.  *d_out is [B, *So] of float or int16 (x itself where nothing is asked), *d_res the [B, 4] result rows of the last
 // stage on the device (null without one), for the caller's own copies to the host.  A document (q.doc, prepared by doc_prepare) is joined
 // behind the contour stage and goes on as ONE item: *d_out is then [1, *So], the joined length F in frames is q.doc.d_blk[0] on the device
@@ -191,7 +208,7 @@ static int tail_run(Alloc&& alloc, vits_session* s, hipStream_t stream, const fl
     x = d_p;
   }
   if (q.contour.on) {  // in the pitch stage's place; the last stage of a call that neither resamples nor normalises
-    const bool cp = q.pcm && !T && !q.norm.on() && !q.doc.on;
+    const bool cp = q.pcm && !T && !q.norm.on() && !q.doc.on && !q.wm.on;
     void* d_c = alloc((cp ? sizeof(int16_t) : sizeof(float)) * (size_t)B * S);
     if (!d_c) return fail(VITS_ERR_NOMEM, "device alloc failed");
     TRY(contour_run(s->m->device, stream, x, S, h_len, B, q.contour, d_cum, cum_bstride, d_toklen, hop, d_c, cp, q.pcm_scale, S, S, nullptr, 0, nullptr, 0,
@@ -200,7 +217,7 @@ static int tail_run(Alloc&& alloc, vits_session* s, hipStream_t stream, const fl
     x = static_cast<const float*>(d_c);
   }
   if (q.doc.on) {  // the items become one: the last stage of a call that neither resamples nor normalises
-    const bool jp = q.pcm && !T && !q.norm.on();
+    const bool jp = q.pcm && !T && !q.norm.on() && !q.wm.on;
     const long long Sd = q.doc.bound * hop;
     void* d_j = alloc((jp ? sizeof(int16_t) : sizeof(float)) * (size_t)Sd);
     if (!d_j) return fail(VITS_ERR_NOMEM, "device alloc failed");
@@ -212,8 +229,33 @@ static int tail_run(Alloc&& alloc, vits_session* s, hipStream_t stream, const fl
   }
   const long long So = *So_out;
   *d_out = x;
-  if (q.norm.on()) {  // the float waveform at the rate it is returned at, measured, then the gain (and the conversion)
+  bool at_rate = !T;  // x is at the rate it is returned at
+  if (q.wm.on) {  // marked at the rate it is returned at (the resampler in front writes float); the last stage of a call that does not normalise
     if (T) {
+      float* d_y = static_cast<float*>(alloc(sizeof(float) * (size_t)B * So));
+      if (!d_y) return fail(VITS_ERR_NOMEM, "device alloc failed");
+      ProfScope ps(s, "out.resample", 2.0 * B * So * T->P.taps, "resample_kernel<float>");
+      resample_launch<float>(stream, *T, x, S, 0, S, len_y, hop, B, d_y, So, 0, So, 1.f, nullptr);
+      x = d_y;
+      at_rate = true;
+    }
+    const bool wp = q.pcm && !q.norm.on();
+    const size_t sc = wm_scratch_elems(So);
+    float* d_scr = static_cast<float*>(alloc(sizeof(float) * (size_t)B * sc));
+    void* d_w = alloc((wp ? sizeof(int16_t) : sizeof(float)) * (size_t)B * So);
+    if (!d_scr || !d_w) return fail(VITS_ERR_NOMEM, "device alloc failed");
+    const int wL = T ? T->P.L : 1, wM = T ? T->P.M : 1;
+    {
+      ProfScope ps(s, "out.watermark", 0, wp ? "wm_frames_kernel + wm_ola_kernel<int16>" : "wm_frames_kernel + wm_ola_kernel<float>");
+      if (wp) wm_launch<int16_t>(stream, q.wm, x, So, So, len_y, hop, wL, wM, B, d_scr, (long long)sc, static_cast<int16_t*>(d_w), So, So, q.pcm_scale);
+      else wm_launch<float>(stream, q.wm, x, So, So, len_y, hop, wL, wM, B, d_scr, (long long)sc, static_cast<float*>(d_w), So, So, 1.f);
+    }
+    *d_out = d_w;
+    if (!q.norm.on()) return VITS_OK;
+    x = static_cast<const float*>(d_w);
+  }
+  if (q.norm.on()) {  // the float waveform at the rate it is returned at, measured, then the gain (and the conversion)
+    if (!at_rate) {
       float* d_y = static_cast<float*>(alloc(sizeof(float) * (size_t)B * So));
       if (!d_y) return fail(VITS_ERR_NOMEM, "device alloc failed");
       ProfScope ps(s, "out.resample", 2.0 * B * So * T->P.taps, "resample_kernel<float>");

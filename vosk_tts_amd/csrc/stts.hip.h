@@ -1052,7 +1052,7 @@ static int stts_synthesize_impl(stts_model* m, const int64_t* ids, int32_t Tx, c
 }
 
 // The output tail of a multistream call (out_tail.hip.h) on its finished audio [B, *S] (library-owned, items of lengths[b] samples), in
-// the order of tail_run: shifted in place at the native rate, replaced by its copy at q.rate, normalised and / or limited in place.
+// the order of tail_run: shifted in place at the native rate, replaced by its copy at q.rate, marked (include/vits_watermark.h), normalised and / or limited in place.
 // (It crosses the host through the parity doors' kernels; running it on the device behind the vocoder would be a speed change of its own.)
 // cum / tok_lengths / Tx: the tokens' inclusive frame counts on the host, read by a contoured call only.
 // A document (include/vits_document.h) is joined behind the pitch stage and in front of the rate, where tail_run joins: from there on
@@ -1108,6 +1108,11 @@ static int stts_tail_host(stts_model* m, const TailReq& q, int B, float** audio,
     free(*audio);
     *audio = y; *S = So;
     for (int b = 0; b < B; ++b) lengths[b] = P.n_out(lengths[b]);
+  }
+  if (q.wm.on && *S > 0) {  // (the kernels of vits_op_watermark, at the rate the audio is returned at)
+    std::vector<float> y((size_t)B * *S);
+    TRY(wm_op(device, *audio, lengths, B, *S, q.wm, y.data()));
+    memcpy(*audio, y.data(), sizeof(float) * y.size());
   }
   if (q.norm.on()) {
     const LoudReq& lo = q.norm.loud;

@@ -1,7 +1,7 @@
 """The extension feeds of the output tail (pitch -> resample -> normalise / limit, DESIGN.md "Output tail"), read once for both session
 types: what a request's feed asks of the loudness, limiter, pitch and intonation stages, checked before any device work.  `lib` is the session's
 library: a stage the loaded library does not export is refused here (its _need_* check)."""
-from .capi import limit_spec, loudness_spec, pitch_spec, range_spec
+from .capi import limit_spec, loudness_spec, pitch_spec, range_spec, watermark_spec
 
 
 def loudness_from_feed(lib, feed):
@@ -48,6 +48,20 @@ def range_from_feed(lib, feed):
     if r is not None:
         lib._need_intonation()
     return r
+
+
+def watermark_from_feed(lib, feed):
+    """"vits.watermark_key" (a 32-bit key; include/vits_watermark.h) and "vits.watermark_depth_db" (in (0, 2], default 1) -> the
+    keywords of the models' calls, {} without a key (the request as it was).  A depth without a key and values out of range are
+    ValueError"""
+    key = feed.get("vits.watermark_key")
+    if key is None:
+        if feed.get("vits.watermark_depth_db") is not None:
+            raise ValueError("\"vits.watermark_depth_db\" needs \"vits.watermark_key\"")
+        return {}
+    key, depth = watermark_spec(int(key), feed.get("vits.watermark_depth_db"))
+    lib._need_watermark()
+    return {"watermark": key} if not depth else {"watermark": key, "watermark_depth_db": depth}
 
 
 # the document feeds (include/vits_document.h): feed key -> keyword of the models' synthesize_document

@@ -19,7 +19,8 @@ import threading
 import numpy as np
 
 from .capi import VitsLib
-from .outopts import DOCUMENT_FEEDS, document_from_feed, limit_from_feed, loudness_from_feed, pitch_from_feed, range_from_feed
+from .outopts import (DOCUMENT_FEEDS, document_from_feed, limit_from_feed, loudness_from_feed, pitch_from_feed, range_from_feed,
+                      watermark_from_feed)
 
 log = logging.getLogger(__name__)
 
@@ -230,7 +231,7 @@ _OPTIONAL_NONE = ("bert", "phone_duration_extra")
 _EXT = ("vits.noise_dp", "vits.noise_prior", "vits.forced_durations", "vits.seed", "vits.solo", "vits.item_seeds", "vits.sample_rate", "vits.marks",
         "vits.loudness", "vits.peak", "vits.peak_ceiling", "vits.pitch", "vits.pitch_formants", "vits.limit", "vits.limit_lookahead_ms",
         "vits.limit_release_ms", "vits.item_scales", "vits.token_length_scale", "vits.token_pause", "vits.fit_frames", "vits.token_pitch",
-        "vits.token_gain_db", "vits.pitch_range") + tuple(DOCUMENT_FEEDS)
+        "vits.token_gain_db", "vits.pitch_range", "vits.watermark_key", "vits.watermark_depth_db") + tuple(DOCUMENT_FEEDS)
 # the prosody controls of a request (include/vits_prosody.h): feed key -> keyword of capi.VitsModel.synthesize*
 _PROSODY = {"vits.item_scales": "item_scales", "vits.token_length_scale": "token_length_scale", "vits.token_pause": "token_pause",
             "vits.fit_frames": "fit_frames"}
@@ -309,11 +310,15 @@ class VitsSession:
         # pitch: the shift of the batch in semitones (None = none; include/vits_pitch.h): part of the key as well, one value per call
         # formants: that shift with the spectral envelope kept (VITS_FLAG_PITCH_FORMANT); False whenever pitch is None
         # limit: the limiter of the batch (capi.limit_spec(), None = none; include/vits_limit.h): part of the key, applied per item
-        # prange: the intonation range of the batch (None = none; include/vits_intonation.h): a ninth entry that only a request with one has
+        # prange: the intonation range of the batch (None = none; include/vits_intonation.h): a further entry that only a request with one has
+        # the watermark of the batch (include/vits_watermark.h): a further entry ("wm", key, depth) that only a marked request has
         kind, scale, rate, marks, loud, pitch, formants, limit = key[:8]
         pk = self._pitch_kw(pitch, formants, limit)
-        if len(key) > 8:
-            pk = dict(pk, pitch_range=key[8])
+        for extra in key[8:]:
+            if isinstance(extra, tuple) and extra[0] == "wm":
+                pk = dict(pk, watermark=extra[1], **({"watermark_depth_db": extra[2]} if extra[2] else {}))
+            else:
+                pk = dict(pk, pitch_range=extra)
         scales = np.array(reqs[0][3], np.float32)
         if len(reqs) == 1:
             ids, sid, seed = reqs[0][:3]
@@ -422,6 +427,12 @@ class VitsSession:
         return () if prange is None else (prange,)
 
     @staticmethod
+    def _wm_key(wm):
+        """what a watermark adds to a coalescer key: nothing without one (the key of before); a marked request is batched only with
+        requests that carry the same key and depth"""
+        return (("wm", wm["watermark"], wm.get("watermark_depth_db", 0.0)),) if wm else ()
+
+    @staticmethod
     def _range_kw(prange):
         return {} if prange is None else {"pitch_range": prange}
 
@@ -446,7 +457,7 @@ class VitsSession:
             pcm_scale=float(scale), forced_durations=feed.get("vits.forced_durations"), seed=int(seed), item_seeds=feed.get("vits.item_seeds"),
             bert=feed.get("bert"), sample_rate=self._rate(feed.get("vits.sample_rate")), marks=self._marks(feed), loudness=self._loudness(feed),
             **self._pitch_kw(pitch, formants, self._limit(feed)), **self._prosody(feed), **self._contour(feed),
-            **self._range_kw(range_from_feed(self._lib, feed)), **doc)
+            **self._range_kw(range_from_feed(self._lib, feed)), **watermark_from_feed(self._lib, feed), **doc)
         self.last_lengths = np.array([audio.shape[0]], np.int64)
         return audio, info
 
@@ -467,9 +478,10 @@ class VitsSession:
         pitch, formants = pitch_from_feed(self._lib, feed)  # ("vits.pitch": the audio shifted by that many semitones, behind the decoder)
         limit = self._limit(feed)  # ("vits.limit": the look-ahead peak limiter with the loudness gain, or alone; include/vits_limit.h)
         prange = range_from_feed(self._lib, feed)  # ("vits.pitch_range": the intonation range; include/vits_intonation.h)
+        wm = watermark_from_feed(self._lib, feed)  # ("vits.watermark_key" / "vits.watermark_depth_db"; include/vits_watermark.h)
         n = self._coalescable(feed, ids)
         if n:
-            key = ("f32", 1.0, rate, marks, loud, pitch, formants, limit) + self._range_key(prange)
+            key = ("f32", 1.0, rate, marks, loud, pitch, formants, limit) + self._range_key(prange) + self._wm_key(wm)
             res = self.coalescer.submit(key, np.ascontiguousarray(ids[:, :n], np.int64), int(sid[0]), int(seed), self._scales(feed))
             self.last_lengths = res[1]
             if marks:  # (the request's own tokens; columns beyond its length repeat the last end, as the C ABI pads them)
@@ -480,7 +492,7 @@ class VitsSession:
             noise_dp=feed.get("vits.noise_dp"), noise_prior=feed.get("vits.noise_prior"),
             forced_durations=feed.get("vits.forced_durations"), seed=int(seed), solo=bool(feed.get("vits.solo", False)),
             item_seeds=feed.get("vits.item_seeds"), bert=feed.get("bert"), sample_rate=rate, marks=marks, loudness=loud,
-            **self._pitch_kw(pitch, formants, limit), **self._prosody(feed), **self._contour(feed), **self._range_kw(prange))
+            **self._pitch_kw(pitch, formants, limit), **self._prosody(feed), **self._contour(feed), **self._range_kw(prange), **wm)
         self.last_lengths = res[1]
         return [res[0][:, None, None, :], res[2]] if marks else [res[0][:, None, None, :]]
 
@@ -548,9 +560,10 @@ class VitsSession:
         pitch, formants = pitch_from_feed(self._lib, feed)
         limit = self._limit(feed)
         prange = range_from_feed(self._lib, feed)
+        wm = watermark_from_feed(self._lib, feed)
         n = self._coalescable(feed, ids)
         if n:
-            key = ("pcm", float(scale), rate, marks, loud, pitch, formants, limit) + self._range_key(prange)
+            key = ("pcm", float(scale), rate, marks, loud, pitch, formants, limit) + self._range_key(prange) + self._wm_key(wm)
             res = self.coalescer.submit(key, np.ascontiguousarray(ids[:, :n], np.int64), int(sid[0]), int(seed), self._scales(feed))
             pcm, lengths = res[0], res[1]
             self.last_lengths = lengths
@@ -563,7 +576,7 @@ class VitsSession:
             pcm_scale=float(scale), noise_dp=feed.get("vits.noise_dp"), noise_prior=feed.get("vits.noise_prior"),
             forced_durations=feed.get("vits.forced_durations"), seed=int(seed), solo=bool(feed.get("vits.solo", False)),
             item_seeds=feed.get("vits.item_seeds"), bert=feed.get("bert"), sample_rate=rate, marks=marks, loudness=loud,
-            **self._pitch_kw(pitch, formants, limit), **self._prosody(feed), **self._contour(feed), **self._range_kw(prange))
+            **self._pitch_kw(pitch, formants, limit), **self._prosody(feed), **self._contour(feed), **self._range_kw(prange), **wm)
         pcm, lengths = res[0], res[1]
         self.last_lengths = lengths
         if marks:
@@ -592,6 +605,9 @@ class VitsSession:
         if range_from_feed(self._lib, feed) is not None:
             raise ValueError("a stream cannot take an intonation range: the median of the F0 track needs the whole utterance before the "
                              "first chunk (run() / run_pcm16() take \"vits.pitch_range\")")
+        if watermark_from_feed(self._lib, feed):
+            raise ValueError("a stream cannot be watermarked (VITS_FLAG_WATERMARK): the mark is a stage of the output tail, and a stream has "
+                             "none (run() / run_pcm16() take \"vits.watermark_key\")")
         if any(k in feed for k in _CONTOUR):
             raise ValueError("a stream cannot be contoured: the position recurrence and the phase recursion need the whole utterance before "
                              "the first chunk (run() / run_pcm16() take \"vits.token_pitch\" / \"vits.token_gain_db\")")

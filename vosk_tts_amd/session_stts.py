@@ -11,13 +11,14 @@ import numpy as np
 
 from .capi import VitsLib
 from .capi_stts import SttsModel
-from .outopts import DOCUMENT_FEEDS, document_from_feed, limit_from_feed, loudness_from_feed, pitch_from_feed, range_from_feed
+from .outopts import (DOCUMENT_FEEDS, document_from_feed, limit_from_feed, loudness_from_feed, pitch_from_feed, range_from_feed,
+                      watermark_from_feed)
 
 _INPUTS = ("input", "input_lengths", "scales", "sid", "bert", "phone_duration_extra")
 _EXT = ("vits.noise", "vits.seed", "vits.n_timesteps", "vits.sample_rate", "vits.denoiser_strength", "vits.denoiser_filter_length",
         "vits.marks", "vits.loudness", "vits.peak", "vits.peak_ceiling", "vits.pitch", "vits.pitch_formants",
         "vits.limit", "vits.limit_lookahead_ms", "vits.limit_release_ms", "vits.token_pitch", "vits.token_gain_db",
-        "vits.pitch_range") + tuple(DOCUMENT_FEEDS)
+        "vits.pitch_range", "vits.watermark_key", "vits.watermark_depth_db") + tuple(DOCUMENT_FEEDS)
 
 
 class SttsSession:
@@ -116,6 +117,17 @@ class SttsSession:
             kw["pitch_range"] = r
         return kw
 
+    def _wm(self, feed):
+        """"vits.watermark_key" / "vits.watermark_depth_db" (include/vits_watermark.h) as the keywords of the model's calls"""
+        return watermark_from_feed(self._lib, feed)
+
+    def mark(self, audio, lengths, wm):
+        """audio float32 [B, S] with per-item sample counts -> the audio marked per item (vits_op_watermark on the host buffer); wm = {}:
+        unchanged.  What run() / run_batch() do behind resample() and in front of normalize(): the mark goes in at the rate returned"""
+        if not wm or audio.shape[-1] == 0:
+            return audio
+        return self._lib.op_watermark(audio, lengths, wm["watermark"], wm.get("watermark_depth_db", 0.0), device=self._vocoder.device)
+
     def normalize(self, audio, lengths, sample_rate, spec, limit=None):
         """audio float32 [B, S] at `sample_rate` Hz (None / 0 = the vocoder's own) with per-item sample counts -> the audio normalised
         per item by `spec` (vits_op_loudness_normalize on the host buffer) and / or limited by `limit` (vits_op_loudness_limit,
@@ -148,19 +160,22 @@ class SttsSession:
         loud = self._loudness(feed)
         lim = self._limit(feed)  # ("vits.limit": the peak limiter with the loudness gain or alone, last in the chain like the gain)
         pk = self._pitch(feed)  # ("vits.pitch": shifted inside the library, behind the denoiser and before any resampling)
+        wm = self._wm(feed)  # ("vits.watermark_key": marked behind the resampler, in front of the normalisation)
         if feed.get("vits.marks"):
             audio, _, ends = self._model.synthesize(ids, scales, sid, bert, pde, noise=feed.get("vits.noise"), seed=seed,
                                                     n_timesteps=int(feed.get("vits.n_timesteps", 0)), want_mel=False, marks=True,
-                                                    sample_rate=self._rate(feed.get("vits.sample_rate")), loudness=loud, limit=lim, **pk,
+                                                    sample_rate=self._rate(feed.get("vits.sample_rate")), loudness=loud, limit=lim, **pk, **wm,
                                                     **self._denoiser(feed))
             outs = {"wav": audio[None, :], "wav_lengths": np.array([audio.shape[0]], np.int64)}
             return [outs[n] for n in (output_names or ["wav", "wav_lengths"])] + [ends[None, :]]
         rate = self._rate(feed.get("vits.sample_rate"))
         audio, _ = self._model.synthesize(ids, scales, sid, bert, pde, noise=feed.get("vits.noise"), seed=seed,
                                           n_timesteps=int(feed.get("vits.n_timesteps", 0)), want_mel=False,
-                                          loudness=None if rate else loud, limit=None if rate else lim, **pk, **self._denoiser(feed))
-        if rate:  # (the library normalises last, and this resampling happens behind it: the normalisation follows it here)
+                                          loudness=None if rate else loud, limit=None if rate else lim, **pk, **({} if rate else wm),
+                                          **self._denoiser(feed))
+        if rate:  # (the library marks and normalises last, and this resampling happens behind it: both follow it here)
             audio = self.resample(audio[None, :], [audio.shape[0]], rate)[0][0]
+            audio = self.mark(audio[None, :], [audio.shape[0]], wm)[0]
             audio = self.normalize(audio[None, :], [audio.shape[0]], rate, loud, lim)[0]
         outs = {"wav": audio[None, :], "wav_lengths": np.array([audio.shape[0]], np.int64)}
         return [outs[n] for n in (output_names or ["wav", "wav_lengths"])]
@@ -185,6 +200,9 @@ class SttsSession:
         if range_from_feed(self._lib, feed) is not None:
             raise ValueError("a stream cannot take an intonation range: the median of the F0 track needs the whole utterance before the "
                              "first chunk (run() takes \"vits.pitch_range\")")
+        if self._wm(feed):
+            raise ValueError("a stream cannot be watermarked (STTS_FLAG_WATERMARK): the mark is a stage of the output tail, and a stream has "
+                             "none (run() takes \"vits.watermark_key\")")
         if self._pitch(feed):
             raise ValueError("a stream cannot be pitch-shifted: the phase recursion needs the frames before a chunk (run() takes "
                              "\"vits.pitch\")")
@@ -227,6 +245,7 @@ class SttsSession:
         loud = self._loudness(feed)  # (per-item gains, last in the chain like run())
         lim = self._limit(feed)
         pk = self._pitch(feed)
+        wm = self._wm(feed)
         rate = self._rate(feed.get("vits.sample_rate"))
         ids = np.asarray(feed["input"])
         if ids.ndim != 3 or ids.shape[1] != 5:
@@ -236,15 +255,15 @@ class SttsSession:
             return self._model.synthesize_batch(ids, feed["input_lengths"], np.asarray(feed["scales"], np.float32).reshape(-1), sid,
                                                 feed.get("bert"), feed.get("phone_duration_extra"), seed=int(feed.get("vits.seed", 0)),
                                                 n_timesteps=int(feed.get("vits.n_timesteps", 0)), item_seeds=feed.get("vits.item_seeds"),
-                                                marks=True, sample_rate=rate, loudness=loud, limit=lim, **pk, **dn)
+                                                marks=True, sample_rate=rate, loudness=loud, limit=lim, **pk, **wm, **dn)
         audio, ol = self._model.synthesize_batch(ids, feed["input_lengths"], np.asarray(feed["scales"], np.float32).reshape(-1), sid,
                                                  feed.get("bert"), feed.get("phone_duration_extra"), seed=int(feed.get("vits.seed", 0)),
                                                  n_timesteps=int(feed.get("vits.n_timesteps", 0)), item_seeds=feed.get("vits.item_seeds"),
-                                                 loudness=None if rate else loud, limit=None if rate else lim, **pk, **dn)
+                                                 loudness=None if rate else loud, limit=None if rate else lim, **pk, **({} if rate else wm), **dn)
         if not rate:
             return audio, ol
         audio, ol = self.resample(audio, ol, rate)
-        return self.normalize(audio, ol, rate, loud, lim), ol
+        return self.normalize(self.mark(audio, ol, wm), ol, rate, loud, lim), ol
 
     def run_document(self, input_feed, scale=1.0, pcm16=False):
         """A document (include/vits_document.h): run_batch's feed with at least one of the document feeds "vits.doc_gap_frames" int [B],
@@ -282,7 +301,7 @@ class SttsSession:
             ids, feed["input_lengths"], np.asarray(feed["scales"], np.float32).reshape(-1), sid, feed.get("bert"), feed.get("phone_duration_extra"),
             seed=int(seed or 0), n_timesteps=int(feed.get("vits.n_timesteps", 0)), item_seeds=feed.get("vits.item_seeds"),
             marks=bool(feed.get("vits.marks")), sample_rate=self._rate(feed.get("vits.sample_rate")), loudness=self._loudness(feed),
-            limit=self._limit(feed), **pk, **self._denoiser(feed), **doc)
+            limit=self._limit(feed), **pk, **self._wm(feed), **self._denoiser(feed), **doc)
         if pcm16:
             audio = np.clip((audio * scale) * 32767.0, -32767.0, 32767.0).astype("int16")
         return audio, info

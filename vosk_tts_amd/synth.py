@@ -293,6 +293,55 @@ class Synth:
         args["vits.pitch_range"] = r
         return True
 
+    def _watermark_key(self, watermark):
+        """a watermark= / key= argument -> the 32-bit key: True (or None where a key is needed) takes the config key
+        inference.watermark_key, a ValueError where the voice's config names none"""
+        if watermark is True or watermark is None:
+            watermark = self.model.config.get("inference", {}).get("watermark_key")
+            if watermark is None:
+                raise ValueError("watermark=True needs the config key inference.watermark_key (or pass the key itself)")
+        return int(watermark)
+
+    def _watermark(self, args, watermark, watermark_depth_db=None):
+        """The audio watermark of the request (include/vits_watermark.h; both voice families): `watermark`, a 32-bit key (a selector, not
+        a secret) or True for the config key inference.watermark_key; None / False = off, the reference's behaviour (a config key alone
+        marks nothing).  watermark_depth_db in (0, 2], default 1 dB.  The feed gets "vits.watermark_key" / "vits.watermark_depth_db"; the
+        engine marks the audio on the device behind the resampler, in front of the loudness stage, the limiter and the int16 conversion.
+        Sample counts and marks do not change; a value out of range is a ValueError naming it."""
+        from .capi import watermark_spec
+
+        if watermark is None or watermark is False:
+            if watermark_depth_db is not None:
+                raise ValueError("watermark_depth_db needs watermark=")
+            return False
+        key, depth = watermark_spec(self._watermark_key(watermark), watermark_depth_db)
+        args["vits.watermark_key"] = key
+        if depth:
+            args["vits.watermark_depth_db"] = depth
+        return True
+
+    def detect_watermark(self, audio, key=None):
+        """(detected, z, offset_samples) of one piece of audio under `key` (default: the config key inference.watermark_key), by the
+        engine's own detector (vits_op_watermark_detect): z is the best normalised correlation over the 128 pattern offsets, detected iff
+        z >= 6 (a false-alarm bound of 1.9e-6 per item, include/vits_watermark.h), offset_samples how far into the 16384-sample pattern
+        the audio starts (a multiple of 128: a crop is found where it was cut).  audio: int16 PCM or float, at the rate it was returned
+        at; audio below 513 samples is never detected."""
+        from .capi import WATERMARK_THRESHOLD
+
+        k = self._watermark_key(key)
+        a = np.asarray(audio)
+        x = a.astype(np.float32) / np.float32(32767.0) if a.dtype == np.int16 else a.astype(np.float32)
+        x = x.reshape(1, -1)
+        sess = self.model.onnx
+        lib = getattr(sess, "_lib", None)
+        if lib is None or not getattr(lib, "has_watermark", False):
+            raise NotImplementedError("this session type has no watermark detector (include/vits_watermark.h)")
+        if x.shape[1] == 0:
+            return False, 0.0, 0
+        dev = getattr(getattr(sess, "_vocoder", None) or getattr(sess, "_model", None), "device", 0)
+        z, off, _, _ = lib.op_watermark_detect(x, [x.shape[1]], k, device=dev)
+        return bool(z[0] >= WATERMARK_THRESHOLD), float(z[0]), int(off[0])
+
     def measure_pitch(self, audio, rate=None):
         """(hz, median_hz) of one utterance: hz float32 [1 + n // 256], the F0 of every analysis frame of include/vits_intonation.h (hop
         256, 0 where unvoiced) as the engine's own tracker finds it (vits_op_f0_track, the track `pitch_range` scales), and the median of
@@ -440,8 +489,9 @@ class Synth:
     def synth_audio(self, text, speaker_id=0, noise_level=None, speech_rate=None, duration_noise_level=None, scale=None, sample_rate=None,
                     denoiser_strength=None, marks=False, loudness=None, peak=None, peak_ceiling=None, pitch=None,
                     preserve_formants=None, limit=None, limit_lookahead_ms=None, limit_release_ms=None, word_rates=None, pauses=None,
-                    duration=None, word_pitch=None, word_gains=None, pitch_range=None):
-        """pitch_range (extension): the intonation range, 0 (monotone) to 4, 1 = unchanged, see _range.
+                    duration=None, word_pitch=None, word_gains=None, pitch_range=None, watermark=None, watermark_depth_db=None):
+        """watermark / watermark_depth_db (extension): a keyed mark in the returned audio that detect_watermark recognises, see _watermark.
+        pitch_range (extension): the intonation range, 0 (monotone) to 4, 1 = unchanged, see _range.
         word_pitch / word_gains (extension): per-word semitones and decibels, see _contour.
         word_rates / pauses / duration (extension): per-word tempo, pauses behind words and the length of the whole utterance in
         seconds, see _prosody.
@@ -463,6 +513,7 @@ class Synth:
         self._limit(args, limit, peak_ceiling, limit_lookahead_ms, limit_release_ms)
         self._pitch(args, pitch, preserve_formants)
         self._range(args, pitch_range)
+        self._watermark(args, watermark, watermark_depth_db)
         rate = self.native_rate()
         if sample_rate and int(sample_rate) != rate:
             rate = int(sample_rate)
@@ -586,7 +637,8 @@ class Synth:
     def synth_document(self, doc, speaker_id=0, sentence_pause=0.2, paragraph_pause=0.6, lead=0.0, fade_ms=2.0, trim_db=None, trim_keep=1,
                        marks=False, seed=None, noise_level=None, speech_rate=None, duration_noise_level=None, scale=None, sample_rate=None,
                        denoiser_strength=None, loudness=None, peak=None, peak_ceiling=None, pitch=None, preserve_formants=None, limit=None,
-                       limit_lookahead_ms=None, limit_release_ms=None, pitch_range=None, max_tokens=None, **refused):
+                       limit_lookahead_ms=None, limit_release_ms=None, pitch_range=None, max_tokens=None, watermark=None,
+                       watermark_depth_db=None, **refused):
         """Many sentences and speakers in one call (extension; include/vits_document.h).  doc: a string -- split by document.split into
         sentences and paragraphs under the documented rule, sentences longer than max_tokens (default 512) tokens cut at clause marks --
         or a list of document.Segment(text, speaker_id=None, pause_after=None, speech_rate=None, word_rates=, pauses=, word_pitch=,
@@ -595,7 +647,8 @@ class Synth:
         segment's own pause_after behind each, the last one trailing; fade_ms raised-cosine fades at both ends of every segment (at most
         half a frame); trim_db (None = off, else a negative dBFS value) cuts the frames below it from both ends of every segment, keeping
         trim_keep frames.  Seconds become frames as floor(sec * rate / hop + 0.5).  The resampler (sample_rate), the loudness target, the
-        limiter and the int16 conversion then see ONE piece of audio; pitch and pitch_range are one value per call, applied per segment.
+        limiter and the int16 conversion then see ONE piece of audio, as does the watermark (watermark=, see _watermark) in front of them;
+        pitch and pitch_range are one value per call, applied per segment.
         Returns int16 audio; with marks=True (audio, SpeechMarks) whose words and phonemes run over the whole document, plus
         marks.segments = [(start, end)] in samples.  The call-wide per-word keywords of synth_audio (word_rates, pauses, duration,
         word_pitch, word_gains) index one utterance and are refused by name: they belong to a Segment."""
@@ -633,6 +686,7 @@ class Synth:
         self._limit(args, limit, peak_ceiling, limit_lookahead_ms, limit_release_ms)
         self._pitch(args, pitch, preserve_formants)
         self._range(args, pitch_range)
+        self._watermark(args, watermark, watermark_depth_db)
         out_rate = rate
         if sample_rate and int(sample_rate) != rate:
             out_rate = int(sample_rate)
@@ -677,8 +731,9 @@ class Synth:
 
     def synth_stream(self, text, speaker_id=0, noise_level=None, speech_rate=None, duration_noise_level=None, scale=None,
                      chunk_frames=64, sample_rate=None, denoiser_strength=None, on_marks=None, loudness=None, peak=None, peak_ceiling=None,
-                     pitch=None, limit=None, word_rates=None, pauses=None, duration=None, pitch_range=None, document=None):
-        """document: ValueError -- the join and the stages behind it need every segment before the first chunk (synth_document).
+                     pitch=None, limit=None, word_rates=None, pauses=None, duration=None, pitch_range=None, document=None, watermark=None):
+        """watermark: ValueError naming VITS_FLAG_WATERMARK -- the mark is a stage of the output tail, and a stream has none.
+        document: ValueError -- the join and the stages behind it need every segment before the first chunk (synth_document).
         word_rates / pauses / duration: as for synth_audio (the stream's open runs the controlled regulator; chunking is untouched).
         pitch_range: ValueError -- the median of the F0 track needs the whole utterance (a voice whose config names
         inference.pitch_range streams with the range it has).
@@ -695,6 +750,9 @@ class Synth:
         if document is not None:
             raise ValueError("synth_stream cannot take document=: the join and the stages behind it need every segment before the first "
                              "chunk (synth_document takes a document)")
+        if watermark is not None and watermark is not False:
+            raise ValueError("synth_stream cannot watermark (VITS_FLAG_WATERMARK): the mark is a stage of the output tail, and a stream has "
+                             "none (synth_audio takes watermark=)")
         if loudness is not None or peak is not None:
             raise ValueError("synth_stream cannot normalise loudness: an integrated-loudness or peak target needs the whole utterance "
                              "before the first chunk (synth_audio takes loudness= / peak=)")
@@ -726,14 +784,15 @@ class Synth:
     def synth(self, text, oname, speaker_id=0, noise_level=None, speech_rate=None, duration_noise_level=None, scale=None, sample_rate=None,
               denoiser_strength=None, marks=False, loudness=None, peak=None, peak_ceiling=None, pitch=None, preserve_formants=None,
               limit=None, limit_lookahead_ms=None, limit_release_ms=None, word_rates=None, pauses=None, duration=None, word_pitch=None,
-              word_gains=None, pitch_range=None):
+              word_gains=None, pitch_range=None, watermark=None, watermark_depth_db=None):
         """marks=True: the utterance's marks.SpeechMarks are returned (the default returns None, as the reference does)"""
         audio = self.synth_audio(text, speaker_id, noise_level, speech_rate, duration_noise_level, scale, sample_rate, denoiser_strength, marks=marks,
                                  loudness=loudness, peak=peak, peak_ceiling=peak_ceiling, pitch=pitch,
                                  preserve_formants=preserve_formants, limit=limit, limit_lookahead_ms=limit_lookahead_ms,
                                  limit_release_ms=limit_release_ms, **{k: v for k, v in (("word_rates", word_rates), ("pauses", pauses), ("duration", duration),
                                                                                            ("word_pitch", word_pitch), ("word_gains", word_gains),
-                                                                                           ("pitch_range", pitch_range))
+                                                                                           ("pitch_range", pitch_range), ("watermark", watermark),
+                                                                                           ("watermark_depth_db", watermark_depth_db))
                                                                       if v is not None})
         sm = None
         if marks:
