@@ -203,6 +203,7 @@ def _feed(**ext):
 
 def test_sessions_take_the_feed_key_and_it_is_a_coalescer_key():
     from vosk_tts_amd import session, session_stts
+    from vosk_tts_amd.outopts import Tail
     from vosk_tts_amd.session import VitsSession
 
     for mod in (session, session_stts):
@@ -218,7 +219,7 @@ def test_sessions_take_the_feed_key_and_it_is_a_coalescer_key():
     sess.run_pcm16(_feed(**{"vits.pitch_range": 1.5}), 1.0)
     sess.run_pcm16(_feed(**{"vits.pitch_range": 0.5, "vits.pitch": 2.0}), 1.0)
     assert [c[1] for c in lib.model.calls] == [{}, {}, {"pitch_range": 0.5}, {"pitch_range": 1.5}, {"pitch_range": 0.5, "pitch": 2.0}]
-    assert keys[0] == keys[1] and len(keys[0]) == 8 and len({keys[0], keys[2], keys[3], keys[4]}) == 4  # different ranges do not share a batch
+    assert keys[0] == keys[1] and keys[0] == ("pcm", 1.0, 0, False, Tail()) and len({keys[0], keys[2], keys[3], keys[4]}) == 4  # different ranges do not share a batch
     # two requests of one key in one batch carry the range once, for the batch
     out = sess._run_solo_batch(keys[2], [(np.ones((1, 4), np.int64), 0, 1, (0.8, 1.0, 0.8)), (np.ones((1, 3), np.int64), 1, 2, (0.8, 1.0, 0.8))])
     assert len(out) == 2 and lib.model.calls[-1] == (2, {"pitch_range": 0.5})
@@ -229,8 +230,8 @@ def test_sessions_take_the_feed_key_and_it_is_a_coalescer_key():
         sess.run_stream(None, _feed(**{"vits.pitch_range": 0.5}))
     st = session_stts.SttsSession.__new__(session_stts.SttsSession)
     st._lib = lib
-    assert st._pitch({}) == {} and st._pitch({"vits.pitch_range": 1.0}) == {}
-    assert st._pitch({"vits.pitch_range": 0.25, "vits.pitch": -5}) == {"pitch": -5.0, "pitch_range": 0.25}
+    assert Tail.from_feed(lib, {}).kw() == {} and Tail.from_feed(lib, {"vits.pitch_range": 1.0}).kw() == {}
+    assert Tail.from_feed(lib, {"vits.pitch_range": 0.25, "vits.pitch": -5}).kw() == {"pitch": -5.0, "pitch_range": 0.25}
 
 
 def _synth(config):

@@ -226,6 +226,7 @@ def test_sessions_read_the_feeds_before_any_device_work():
     the limiter's ceiling"""
     from vosk_tts_amd import session, session_stts
     from vosk_tts_amd.capi import LIMIT_TRUE, LOUDNESS_LUFS
+    from vosk_tts_amd.outopts import Tail
 
     class Lib:
         has_limit = has_loudness = True
@@ -241,13 +242,13 @@ def test_sessions_read_the_feeds_before_any_device_work():
         s = cls.__new__(cls)
         s._lib = Lib()
         feed = {"vits.loudness": -16.0, "vits.peak_ceiling": 0.89, "vits.limit": "true", "vits.limit_release_ms": 80.0}
-        assert s._limit(feed) == (LIMIT_TRUE, 0.89, 5.0, 80.0, 1.0)
-        assert s._loudness(feed) == (LOUDNESS_LUFS, -16.0, 0.0)
-        assert s._limit({"vits.loudness": -16.0}) is None and s._loudness({"vits.loudness": -16.0, "vits.peak_ceiling": 0.89})[2] == 0.89
+        assert Tail.from_feed(s._lib, feed).limit == (LIMIT_TRUE, 0.89, 5.0, 80.0, 1.0)
+        assert Tail.from_feed(s._lib, feed).loudness == (LOUDNESS_LUFS, -16.0, 0.0)
+        assert Tail.from_feed(s._lib, {"vits.loudness": -16.0}).limit is None and Tail.from_feed(s._lib, {"vits.loudness": -16.0, "vits.peak_ceiling": 0.89}).loudness[2] == 0.89
         with pytest.raises(ValueError, match="vits.peak"):
-            s._limit({"vits.limit": "sample", "vits.peak": 0.5})
+            Tail.from_feed(s._lib, {"vits.limit": "sample", "vits.peak": 0.5})
         with pytest.raises(ValueError, match="bogus"):
-            s._limit({"vits.limit": "bogus"})
+            Tail.from_feed(s._lib, {"vits.limit": "bogus"})
 
 
 def test_cli_has_the_flag():

@@ -236,6 +236,7 @@ def test_coalescer_never_mixes_shifts_and_an_unshifted_request_is_the_call_it_wa
 
 def test_session_feed_names_and_refusals():
     from vosk_tts_amd import session, session_stts
+    from vosk_tts_amd.outopts import Tail
     from vosk_tts_amd.session import VitsSession
 
     for mod in (session, session_stts):
@@ -250,9 +251,9 @@ def test_session_feed_names_and_refusals():
     # the multistream session: the same key, turned into the model's keyword; nothing for no shift
     st = session_stts.SttsSession.__new__(session_stts.SttsSession)
     st._lib = lib
-    assert st._pitch({}) == {} and st._pitch({"vits.pitch": 0.0}) == {} and st._pitch({"vits.pitch": -5}) == {"pitch": -5.0}
+    assert Tail.from_feed(lib, {}).kw() == {} and Tail.from_feed(lib, {"vits.pitch": 0.0}).kw() == {} and Tail.from_feed(lib, {"vits.pitch": -5}).kw() == {"pitch": -5.0}
     with pytest.raises(ValueError, match="-12.5"):
-        st._pitch({"vits.pitch": -12.5})
+        Tail.from_feed(lib, {"vits.pitch": -12.5})
 
 
 def test_synth_takes_pitch_and_the_config_key_and_streams_refuse():

@@ -223,6 +223,7 @@ def _feed(**ext):
 
 def test_sessions_take_the_feed_key_and_it_is_a_coalescer_key():
     from vosk_tts_amd import session, session_stts
+    from vosk_tts_amd.outopts import Tail
     from vosk_tts_amd.session import VitsSession
 
     for mod in (session, session_stts):
@@ -244,9 +245,9 @@ def test_sessions_take_the_feed_key_and_it_is_a_coalescer_key():
         sess.run_stream(None, _feed(**{"vits.pitch": 2.0, "vits.pitch_formants": True}))
     st = session_stts.SttsSession.__new__(session_stts.SttsSession)
     st._lib = lib
-    assert st._pitch({"vits.pitch_formants": True}) == {} and st._pitch({"vits.pitch": 0.0, "vits.pitch_formants": True}) == {}
-    assert st._pitch({"vits.pitch": -5}) == {"pitch": -5.0}
-    assert st._pitch({"vits.pitch": -5, "vits.pitch_formants": True}) == {"pitch": -5.0, "preserve_formants": True}
+    assert Tail.from_feed(lib, {"vits.pitch_formants": True}).kw() == {} and Tail.from_feed(lib, {"vits.pitch": 0.0, "vits.pitch_formants": True}).kw() == {}
+    assert Tail.from_feed(lib, {"vits.pitch": -5}).kw() == {"pitch": -5.0}
+    assert Tail.from_feed(lib, {"vits.pitch": -5, "vits.pitch_formants": True}).kw() == {"pitch": -5.0, "preserve_formants": True}
 
 
 def test_synth_takes_the_argument_and_the_config_key():

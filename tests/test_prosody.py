@@ -261,12 +261,13 @@ def test_requests_with_different_speech_rates_share_a_batch():
 
 
 def test_requests_with_equal_scales_run_the_call_they_always_ran():
+    from vosk_tts_amd.outopts import Tail
     from vosk_tts_amd.session import RequestCoalescer, VitsSession
 
     lib = _LibStub()
     lib.model.gate.set()
     sess = VitsSession(b"", lib=lib)
-    out = sess._run_solo_batch(("pcm", 1.0, 0, False, None, None, False, None),
+    out = sess._run_solo_batch(("pcm", 1.0, 0, False, Tail()),
                                [(np.ones((1, 4), np.int64), 0, 1, (0.8, 1.0, 0.8)), (np.ones((1, 6), np.int64), 1, 2, (0.8, 1.0, 0.8))])
     assert len(out) == 2 and len(lib.model.calls) == 1
     assert lib.model.calls[0][0] == 2 and lib.model.calls[0][1] == pytest.approx([0.8, 1.0, 0.8]) and lib.model.calls[0][2:] == (None, [4, 6])

@@ -220,6 +220,7 @@ def _feed(**ext):
 
 def test_sessions_take_the_feed_keys_and_a_marked_feed_is_not_coalesced_with_an_unmarked_one():
     from vosk_tts_amd import session, session_stts
+    from vosk_tts_amd.outopts import Tail
     from vosk_tts_amd.session import VitsSession
 
     for mod in (session, session_stts):
@@ -236,7 +237,7 @@ def test_sessions_take_the_feed_keys_and_a_marked_feed_is_not_coalesced_with_an_
     sess.run_pcm16(_feed(**{"vits.watermark_key": KEY, "vits.pitch_range": 0.5}), 1.0)
     assert [c[1] for c in lib.model.calls] == [{}, {"watermark": KEY}, {"watermark": KEY + 1}, {"watermark": KEY, "watermark_depth_db": 2.0},
                                                {"watermark": KEY, "pitch_range": 0.5}]
-    assert len(keys[0]) == 8 and len(set(keys)) == 5  # the key of before without a mark; with one, only the same key and depth share a batch
+    assert keys[0] == ("pcm", 1.0, 0, False, Tail()) and len(set(keys)) == 5  # the key of before without a mark; with one, only the same key and depth share a batch
     out = sess._run_solo_batch(keys[3], [(np.ones((1, 4), np.int64), 0, 1, (0.8, 1.0, 0.8)), (np.ones((1, 3), np.int64), 1, 2, (0.8, 1.0, 0.8))])
     assert len(out) == 2 and lib.model.calls[-1] == (2, {"watermark": KEY, "watermark_depth_db": 2.0})
     for bad, match in (({"vits.watermark_key": -1}, "-1"), ({"vits.watermark_key": KEY, "vits.watermark_depth_db": 3.0}, "3.0"),
@@ -247,9 +248,9 @@ def test_sessions_take_the_feed_keys_and_a_marked_feed_is_not_coalesced_with_an_
         sess.run_stream(None, _feed(**{"vits.watermark_key": KEY}))
     st = session_stts.SttsSession.__new__(session_stts.SttsSession)
     st._lib = lib
-    assert st._wm({}) == {} and st._wm({"vits.watermark_key": KEY}) == {"watermark": KEY}
-    assert st._wm({"vits.watermark_key": 5, "vits.watermark_depth_db": 0.5}) == {"watermark": 5, "watermark_depth_db": 0.5}
-    assert st.mark(np.zeros((1, 8), np.float32), [8], {}).shape == (1, 8)  # no key: the audio as it was, no library call
+    assert Tail.from_feed(lib, {}).kw() == {} and Tail.from_feed(lib, {"vits.watermark_key": KEY}).kw() == {"watermark": KEY}
+    assert Tail.from_feed(lib, {"vits.watermark_key": 5, "vits.watermark_depth_db": 0.5}).kw() == {"watermark": 5, "watermark_depth_db": 0.5}
+    assert st.mark(np.zeros((1, 8), np.float32), [8], None).shape == (1, 8)  # no key: the audio as it was, no library call
 
 
 def _synth(config):

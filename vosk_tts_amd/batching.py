@@ -149,10 +149,10 @@ class MultiDeviceSynth:
         a = pcm[:int(n)].copy()
         return a if ends is None else (a, ends[:int(n_tokens)].copy())
 
-    def _run_shard(self, r, token_lists, idx, sids, scales, scale, seeds, sample_rate=None, marks=False, loud=None):
+    def _run_shard(self, r, token_lists, idx, sids, scales, scale, seeds, sample_rate=None, marks=False, tail_feed=None):
         """the requests `idx` on replica r, in batches of <= max_batch (already sorted by descending length) -> list of int16 arrays
-        (marks: of (int16 array, token ends)).  loud: the loudness feeds of the batch ("vits.loudness" / "vits.peak" / "vits.peak_ceiling",
-        include/vits_loudness.h), merged into every feed; the engine normalises per item"""
+        (marks: of (int16 array, token ends)).  tail_feed: the tail's feed fragment of the batch (outopts.TAIL_FEEDS: "vits.loudness",
+        "vits.pitch", "vits.watermark_key", ...), merged into every feed; the engine applies every stage per item"""
         out = []
         sess = self.models[r].onnx
         for k in range(0, len(idx), self.max_batch):
@@ -160,7 +160,7 @@ class MultiDeviceSynth:
             ids, lens = pad_batch(token_lists, part)
             feed = {"input": ids, "input_lengths": lens, **self._scales_feed(scales, part), "sid": np.array([sids[i] for i in part], np.int64),
                     "bert": None, "phone_duration_extra": None, "vits.solo": True,
-                    "vits.item_seeds": np.array([seeds[i] for i in part], np.uint64), **(loud or {})}
+                    "vits.item_seeds": np.array([seeds[i] for i in part], np.uint64), **(tail_feed or {})}
             with self._replica_locks[r]:  # concurrent synth_batch() calls do not interleave on one replica
                 pcm, lengths, ends = self._pcm16_marks(sess, feed, scale, sample_rate, marks)  # lengths of THIS call (not the shared attribute)
             out.extend(self._item(pcm[j], lengths[j], None if ends is None else ends[j], lens[j]) for j in range(len(part)))
@@ -187,13 +187,12 @@ class MultiDeviceSynth:
         `watermark` / `watermark_depth_db`: the audio watermark (include/vits_watermark.h; Synth._watermark), one key per call; every
         request is marked from its own samples, so it equals its single call with the same seed."""
         s0 = self.synths[0]
-        loud = {}
-        s0._loudness(loud, loudness, peak, peak_ceiling)
-        s0._limit(loud, limit, peak_ceiling, limit_lookahead_ms, limit_release_ms)
-        # "vits.pitch" (and "vits.pitch_formants"): one shift for the whole batch, travelling with the loudness feeds; include/vits_pitch.h
-        s0._pitch(loud, pitch, preserve_formants)
-        s0._range(loud, pitch_range)  # ("vits.pitch_range": travels the same way)
-        s0._watermark(loud, watermark, watermark_depth_db)  # ("vits.watermark_key" / "vits.watermark_depth_db": as well)
+        tail_feed = {}  # (the tail's feed keys, one setting for the whole batch: merged into every shard's feed)
+        s0._loudness(tail_feed, loudness, peak, peak_ceiling)
+        s0._limit(tail_feed, limit, peak_ceiling, limit_lookahead_ms, limit_release_ms)
+        s0._pitch(tail_feed, pitch, preserve_formants)
+        s0._range(tail_feed, pitch_range)
+        s0._watermark(tail_feed, watermark, watermark_depth_db)
         dn = {}
         s0._denoiser(dn, denoiser_strength)
         denoiser_strength = dn.get("vits.denoiser_strength")
@@ -202,7 +201,7 @@ class MultiDeviceSynth:
         if self.family == "vits":
             token_lists = [s0.g2p_noembed(s0.normalize(t)) for t in texts]
             return with_marks(self.synth_tokens(token_lists, speaker_ids, noise_level, speech_rate, duration_noise_level, scale, seeds, sample_rate,
-                                                marks=marks, loud=loud))
+                                                marks=marks, tail_feed=tail_feed))
         # BERT-conditioned families: the front end needs the replica's BERT encoder, so it runs on the replica that gets the request;
         # requests are sharded by a cheap length estimate (phoneme count, no BERT needed)
         n = len(texts)
@@ -214,7 +213,7 @@ class MultiDeviceSynth:
         shards = plan_shards(est, len(self.devices))
         run = self._run_shard_bert if self.family == "vits_bert" else self._run_shard_multistream
         kw = {"denoiser_strength": denoiser_strength} if self.family == "multistream" else {}
-        futs = [self._pool.submit(run, r, texts, idx, sids, scales, scale, seeds, sample_rate=sample_rate, marks=marks, loud=loud, **kw) if idx else None
+        futs = [self._pool.submit(run, r, texts, idx, sids, scales, scale, seeds, sample_rate=sample_rate, marks=marks, tail_feed=tail_feed, **kw) if idx else None
                 for r, idx in enumerate(shards)]
         return with_marks(scatter_results(n, [idx for idx in shards if idx], [f.result() for f in futs if f is not None]))
 
@@ -301,7 +300,7 @@ class MultiDeviceSynth:
             out.update(zip(rest, per_request(rest)))
         return [out[i] for i in idx]
 
-    def _run_shard_bert(self, r, texts, idx, sids, scales, scale, seeds, per_request=False, sample_rate=None, marks=False, loud=None):
+    def _run_shard_bert(self, r, texts, idx, sids, scales, scale, seeds, per_request=False, sample_rate=None, marks=False, tail_feed=None):
         """BERT-conditioned VITS requests `idx` on replica r: get_word_bert + g2p / g2p_noblank per request (synth.py:88-99), then padded
         solo batches with a padded `bert` feed [B, 768, T]"""
         synth, sess = self.synths[r], self.models[r].onnx
@@ -310,13 +309,13 @@ class MultiDeviceSynth:
                 f = synth.front_batch([texts[i] for i in part], [sids[i] for i in part])
                 feed = {"input": f["input"], "input_lengths": f["input_lengths"], **self._scales_feed(scales, part), "sid": f["sid"], "bert": f["bert"],
                         "phone_duration_extra": None, "vits.solo": True, "vits.item_seeds": np.array([seeds[i] for i in part], np.uint64),
-                        **(loud or {})}
+                        **(tail_feed or {})}
                 with self._replica_locks[r]:
                     pcm, lengths, ends = self._pcm16_marks(sess, feed, scale, sample_rate, marks)
                 return [self._item(pcm[b], lengths[b], None if ends is None else ends[b], f["input_lengths"][b]) for b in range(len(part))]
 
             return self._run_parts(r, idx, run_part, lambda rest: self._run_shard_bert(r, texts, rest, sids, scales, scale, seeds, per_request=True,
-                                                                                      sample_rate=sample_rate, marks=marks, loud=loud))
+                                                                                      sample_rate=sample_rate, marks=marks, tail_feed=tail_feed))
         fe = synth.g2p_noblank if synth.model.config.get("no_blank", 0) != 0 else synth.g2p
         fronts = []
         for i in idx:
@@ -335,31 +334,24 @@ class MultiDeviceSynth:
                 bert[b, :, :lens[b]] = fronts[k][1]
             feed = {"input": ids, "input_lengths": lens, **self._scales_feed(scales, [idx[k] for k in part]),
                     "sid": np.array([sids[idx[k]] for k in part], np.int64), "bert": bert, "phone_duration_extra": None, "vits.solo": True,
-                    "vits.item_seeds": np.array([seeds[idx[k]] for k in part], np.uint64), **(loud or {})}
+                    "vits.item_seeds": np.array([seeds[idx[k]] for k in part], np.uint64), **(tail_feed or {})}
             with self._replica_locks[r]:
                 pcm, lengths, ends = self._pcm16_marks(sess, feed, scale, sample_rate, marks)
             for b, k in enumerate(part):
                 out[k] = self._item(pcm[b], lengths[b], None if ends is None else ends[b], lens[b])
         return out
 
-    def _stts_batch(self, sess, args, kw, sample_rate, marks, loud=None):
-        """stts_synthesize_batch of one padded part -> (audio, lengths, token_ends or None) at `sample_rate`; with marks the call takes
-        the rate itself (stts_synthesize_batch_marks).  loud: the loudness feeds; every item is normalised last, behind the resampler"""
-        spec = sess._loudness(loud or {})
-        lim = sess._limit(loud or {})
-        kw = dict(kw, **sess._pitch(loud or {}))
-        wm = sess._wm(loud or {})  # (the watermark: behind the resampler, in front of the normalisation)
-        if marks:
-            return sess._model.synthesize_batch(*args, marks=True, sample_rate=sess._rate(sample_rate), loudness=spec, limit=lim, **kw, **wm)
-        rate = sess._rate(sample_rate)
-        audio, ol = sess._model.synthesize_batch(*args, loudness=None if rate else spec, limit=None if rate else lim, **kw, **({} if rate else wm))
-        if not rate:
-            return audio, ol, None
-        audio, ol = sess.resample(audio, ol, rate)
-        return sess.normalize(sess.mark(audio, ol, wm), ol, rate, spec, lim), ol, None
+    @staticmethod
+    def _stts_batch(sess, args, kw, sample_rate, marks, tail_feed=None):
+        """stts_synthesize_batch of one padded part and the tail behind it (SttsSession.tail_chain) -> (audio, lengths, token_ends or None)
+        at `sample_rate`.  tail_feed: the tail's feed fragment; every item is marked and normalised on its own, behind the resampler"""
+        from .outopts import Tail
+
+        res = sess.tail_chain(lambda **t: sess._model.synthesize_batch(*args, **kw, **t), Tail.from_feed(sess._lib, tail_feed or {}), sample_rate, marks)
+        return res if marks else res + (None,)
 
     def _run_shard_multistream(self, r, texts, idx, sids, scales, scale, seeds, per_request=False, sample_rate=None, denoiser_strength=None,
-                               marks=False, loud=None):
+                               marks=False, tail_feed=None):
         """multistream (StableTTS / Matcha) requests `idx` on replica r: the five-stream front end of Synth._feed per request
         (synth.py:64-87), then stts_synthesize_batch with per-request seeds (and the denoiser, where a strength is given);
         float -> int16 as Synth.audio_float_to_int16"""
@@ -370,13 +362,13 @@ class MultiDeviceSynth:
                 with self._replica_locks[r]:
                     audio, ol, ends = self._stts_batch(
                         sess, (f["input"], f["input_lengths"], scales, f["sid"], f["bert"], f["phone_duration_extra"]),
-                        dict(seed=0, item_seeds=np.array([seeds[i] for i in part], np.uint64), denoiser_strength=denoiser_strength), sample_rate, marks, loud)
+                        dict(seed=0, item_seeds=np.array([seeds[i] for i in part], np.uint64), denoiser_strength=denoiser_strength), sample_rate, marks, tail_feed)
                 pcm = [synth.audio_float_to_int16(audio[b, :int(ol[b])] * scale) for b in range(len(part))]
                 return pcm if ends is None else [(pcm[b], ends[b, :int(f["input_lengths"][b])].copy()) for b in range(len(part))]
 
             return self._run_parts(r, idx, run_part, lambda rest: self._run_shard_multistream(r, texts, rest, sids, scales, scale, seeds, per_request=True,
                                                                                              sample_rate=sample_rate, denoiser_strength=denoiser_strength,
-                                                                                             marks=marks, loud=loud))
+                                                                                             marks=marks, tail_feed=tail_feed))
         fronts = []
         for i in idx:
             feed, _ = synth._feed(texts[i], sids[i], None, None, None, None)
@@ -400,7 +392,7 @@ class MultiDeviceSynth:
             with self._replica_locks[r]:
                 audio, ol, ends = self._stts_batch(
                     sess, (ids, lens, scales, np.array([sids[idx[k]] for k in part], np.int64), bert, pde),
-                    dict(seed=0, item_seeds=np.array([seeds[idx[k]] for k in part], np.uint64), denoiser_strength=denoiser_strength), sample_rate, marks, loud)
+                    dict(seed=0, item_seeds=np.array([seeds[idx[k]] for k in part], np.uint64), denoiser_strength=denoiser_strength), sample_rate, marks, tail_feed)
             for b, k in enumerate(part):
                 out[k] = synth.audio_float_to_int16(audio[b, :int(ol[b])] * scale)
                 if ends is not None:
@@ -408,9 +400,9 @@ class MultiDeviceSynth:
         return out
 
     def synth_tokens(self, token_lists, speaker_ids=0, noise_level=None, speech_rate=None, duration_noise_level=None, scale=None, seeds=None,
-                     sample_rate=None, marks=False, loud=None):
+                     sample_rate=None, marks=False, tail_feed=None):
         """synth_batch() behind the front end: token id lists in, int16 PCM arrays out (request order).  marks=True: (PCM, token ends
-        int64 [len(tokens)] in output samples) per request.  loud: the loudness feeds of the batch (Synth._loudness)."""
+        int64 [len(tokens)] in output samples) per request.  tail_feed: the tail's feed fragment of the batch (Synth._loudness, _limit, ...)."""
         n = len(token_lists)
         if n == 0:
             return []
@@ -418,6 +410,6 @@ class MultiDeviceSynth:
             raise NotImplementedError("synth_tokens takes plain VITS token ids; BERT-conditioned and multistream voices need the text (synth_batch)")
         scales, scale, sids, seeds = self._call_params(n, speaker_ids, noise_level, speech_rate, duration_noise_level, scale, seeds)
         shards = plan_shards([len(t) for t in token_lists], len(self.devices))
-        futs = [self._pool.submit(self._run_shard, r, token_lists, idx, sids, scales, scale, seeds, sample_rate, marks, loud) if idx else None
+        futs = [self._pool.submit(self._run_shard, r, token_lists, idx, sids, scales, scale, seeds, sample_rate, marks, tail_feed) if idx else None
                 for r, idx in enumerate(shards)]
         return scatter_results(n, [idx for idx in shards if idx], [f.result() for f in futs if f is not None])

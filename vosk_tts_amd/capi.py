@@ -11,6 +11,7 @@ import os
 
 import numpy as np
 
+from .outopts import PLAIN, Tail
 from .weights import HParams
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -75,22 +76,6 @@ def loudness_spec(loudness=None, peak=None, peak_ceiling=None):
             raise ValueError(f"peak target {t} outside (0, 1]")
         return (LOUDNESS_PEAK, t, 0.0)
     return None
-
-
-def set_loudness(opts, keep, spec, B, flag, out=None):
-    """Fills the loudness fields of a SynthOpts / SttsOpts and sets `flag`; the [B] result arrays are kept alive in `keep` and, when
-    `out` is a dict, published there as out["loudness"] (LUFS of the un-normalised item, -inf for silence) and out["gain"]."""
-    if spec is None:
-        return
-    mode, target, ceiling = spec
-    loud = np.full(B, np.nan, np.float32)
-    gain = np.full(B, np.nan, np.float32)
-    keep += [loud, gain]
-    opts.flags |= flag
-    opts.loudness_mode, opts.loudness_target, opts.loudness_ceiling = int(mode), float(target), float(ceiling)
-    opts.out_loudness, opts.out_gain = _p(loud, c_f32p), _p(gain, c_f32p)
-    if out is not None:
-        out["loudness"], out["gain"] = loud, gain
 
 
 # include/vits_pitch.h
@@ -162,20 +147,6 @@ def limit_spec(limit=None, ceiling=None, lookahead_ms=5.0, release_ms=50.0, gain
     return (LIMIT_MODES[limit], c, la, rel, g)
 
 
-def set_limit(opts, keep, spec, B, flag, out=None):
-    """Fills the limiter fields of a SynthLimitOpts / SttsLimitOpts and sets `flag`; the [B] result array is kept alive in `keep` and,
-    when `out` is a dict, published there as out["reduction"] (min of the gain curve per item, 1 = not limited)."""
-    if spec is None:
-        return
-    red = np.full(B, np.nan, np.float32)
-    keep.append(red)
-    opts.flags |= flag
-    opts.limit_mode, opts.limit_ceiling, opts.limit_lookahead_ms, opts.limit_release_ms, opts.limit_gain = spec
-    opts.out_reduction = _p(red, c_f32p)
-    if out is not None:
-        out["reduction"] = red
-
-
 # include/vits_prosody.h
 FLAG_PROSODY = 32                # VITS_FLAG_PROSODY
 PROSODY_MAX_TOKEN_SCALE = 16.0   # VITS_PROSODY_MAX_TOKEN_SCALE
@@ -221,8 +192,8 @@ def prosody_struct(arrays):
     return P
 
 
-def set_prosody(opts, keep, arrays, B, out=None):
-    """Points a SynthProsodyOpts at the controls of prosody_arrays() and sets VITS_FLAG_PROSODY; the struct, the arrays and the [B] result
+def set_prosody(opts, keep, arrays, B, flag, out=None):
+    """Points a SynthProsodyOpts at the controls of prosody_arrays() and sets the family's flag; the struct, the arrays and the [B] result
     array are kept alive in `keep` and, when `out` is a dict, the result is published there as out["fit_ratio"]."""
     if arrays is None:
         return
@@ -231,7 +202,7 @@ def set_prosody(opts, keep, arrays, B, out=None):
     keep += [P, ratio] + list(arrays.values())
     P.out_fit_ratio = _p(ratio, c_f32p)
     opts.prosody = ctypes.pointer(P)
-    opts.flags |= FLAG_PROSODY
+    opts.flags |= flag
     if out is not None:
         out["fit_ratio"] = ratio
 
@@ -283,7 +254,7 @@ def contour_arrays(B, Tx, token_pitch=None, token_gain_db=None, lengths=None, pi
     return out
 
 
-def set_contour(opts, keep, arrays, flag=FLAG_CONTOUR):
+def set_contour(opts, keep, arrays, flag):
     """Points a SynthContourOpts / SttsContourOpts at the arrays of contour_arrays() and sets the flag; everything is kept alive in `keep`"""
     if arrays is None:
         return
@@ -320,14 +291,6 @@ def range_spec(pitch_range=None):
     return None if int(math.floor(1000.0 * r + 0.5)) == 1000 else r
 
 
-def set_intonation(opts, pitch_range, flag=FLAG_INTONATION):
-    """Sets the flag and the field of a SynthIntonationOpts / SttsIntonationOpts from a range_spec()"""
-    if pitch_range is None:
-        return
-    opts.pitch_range = pitch_range
-    opts.flags |= flag
-
-
 # include/vits_watermark.h
 FLAG_WATERMARK = 256             # VITS_FLAG_WATERMARK (STTS_FLAG_WATERMARK has the same value)
 WATERMARK_MAX_DEPTH_DB = 2.0     # VITS_WATERMARK_MAX_DEPTH_DB
@@ -360,12 +323,68 @@ def watermark_spec(watermark=None, depth_db=None):
     return (key, d)
 
 
-def set_watermark(opts, spec, flag=FLAG_WATERMARK):
-    """Sets the flag and the two fields of a SynthWatermarkOpts / SttsWatermarkOpts from a watermark_spec()"""
-    if spec is None:
-        return
-    opts.watermark_key, opts.watermark_depth_db = spec
-    opts.flags |= flag
+def tail_of(loudness=None, limit=None, pitch=None, preserve_formants=False, pitch_range=None, watermark=None):
+    """The Tail of a model's call: loudness, limit and watermark as their specs, pitch and pitch_range as the caller gave them (a shift
+    that reduces to P = Q and a range whose r_m is 1000 are none; preserve_formants counts only with a shift in effect)"""
+    if loudness is None and limit is None and pitch is None and pitch_range is None and watermark is None:
+        return PLAIN
+    pitch = pitch_spec(pitch)
+    return Tail(loudness, limit, pitch, pitch is not None and bool(preserve_formants), range_spec(pitch_range), watermark)
+
+
+class TailFamily:
+    """What differs between the two APIs in how a call's options carry the tail; the Python twin of TailFamily in csrc/out_tail.hip.h.
+    flags: the flag bit of every stage; chain: the options structs in the order each extends the one before."""
+
+    FIELDS = ("loudness_mode", "pitch_semitones", "limit_mode", "prosody", "contour", "pitch_range", "watermark_key")  # one per stage, in opts()'s order
+
+    def __init__(self, word, chain, loudness, limit, pitch, formant, contour, intonation, watermark, prosody=0):
+        self.word, self.chain = word, chain
+        self.loudness, self.limit, self.pitch, self.formant = loudness, limit, pitch, formant
+        self.contour, self.intonation, self.watermark, self.prosody = contour, intonation, watermark, prosody
+
+    def opts(self, tail, prosody=None, contour=None):
+        """the options struct of a call: the first of the chain that has every field asked for (a plain call: the plain struct)"""
+        if tail is PLAIN and prosody is None and contour is None:  # (the hot path: not worth a search)
+            return self.chain[0]()
+        asked = (tail.loudness, tail.pitch, tail.limit, prosody, contour, tail.pitch_range, tail.watermark)
+        need = [f for f, v in zip(self.FIELDS, asked) if v is not None]
+        return next(c for c in self.chain if all(hasattr(c, f) for f in need))()
+
+    def fill(self, opts, keep, tail, B, out=None):
+        """Writes the flags and fields of `tail` into an opts() struct.  The [B] result arrays of the loudness stage and the limiter are
+        kept alive in `keep` and, when `out` is a dict, published there: out["loudness"] (LUFS of the un-normalised item, -inf for
+        silence), out["gain"], out["reduction"] (min of the limiter's gain curve per item, 1 = not limited)."""
+        if tail.loudness is not None:
+            opts.flags |= self.loudness
+            opts.loudness_mode, opts.loudness_target, opts.loudness_ceiling = tail.loudness
+            results = ("loudness", "out_loudness"), ("gain", "out_gain")
+        else:
+            results = ()
+        if tail.limit is not None:
+            opts.flags |= self.limit
+            opts.limit_mode, opts.limit_ceiling, opts.limit_lookahead_ms, opts.limit_release_ms, opts.limit_gain = tail.limit
+            results += (("reduction", "out_reduction"),)
+        for name, field in results:
+            a = np.full(B, np.nan, np.float32)
+            keep.append(a)
+            setattr(opts, field, _p(a, c_f32p))
+            if out is not None:
+                out[name] = a
+        if tail.pitch is not None:
+            opts.flags |= self.pitch | (self.formant if tail.formants else 0)
+            opts.pitch_semitones = tail.pitch
+        if tail.pitch_range is not None:
+            opts.flags |= self.intonation
+            opts.pitch_range = tail.pitch_range
+        if tail.watermark is not None:
+            opts.flags |= self.watermark
+            opts.watermark_key, opts.watermark_depth_db = tail.watermark
+
+
+VITS_TAIL = TailFamily("VITS", (SynthOpts, SynthPitchOpts, SynthLimitOpts, SynthProsodyOpts, SynthContourOpts, SynthIntonationOpts, SynthWatermarkOpts),
+                       loudness=FLAG_LOUDNESS, limit=FLAG_LIMIT, pitch=FLAG_PITCH, formant=FLAG_PITCH_FORMANT, contour=FLAG_CONTOUR,
+                       intonation=FLAG_INTONATION, watermark=FLAG_WATERMARK, prosody=FLAG_PROSODY)
 
 
 class PersistInfo(ctypes.Structure):
@@ -644,6 +663,19 @@ class VitsLib:
         if not self.has_marks:
             raise VitsError(4, "this backend has no speech marks (include/vits_marks.h): the CPU oracle returns audio only")
 
+    def _need_tail(self, tail, family="VITS"):
+        """every stage `tail` asks for must be one this library exports (VitsError 4 names the first that is not)"""
+        if tail.watermark is not None:
+            self._need_watermark()
+        if tail.pitch_range is not None:
+            self._need_intonation()
+        if tail.limit is not None:
+            self._need_limit()
+        if tail.pitch is not None:
+            self._need_pitch_formant(family) if tail.formants else self._need_pitch()
+        if tail.loudness is not None:
+            self._need_loudness()
+
     def stream_marks(self, st):
         """vits_stream_marks of an open stream handle -> int64 [T_x] (empty for a latent stream)"""
         self._need_marks()
@@ -837,10 +869,10 @@ class VitsLib:
         self.check(self._fn("pitch_plan")(float(semitones), ctypes.byref(P), ctypes.byref(Q)))
         return P.value, Q.value
 
-    def _need_pitch_formant(self):
+    def _need_pitch_formant(self, family="VITS"):
         self._need_pitch()
         if not self.has_pitch_formant:
-            raise VitsError(4, "this backend has no formant-preserving pitch shift (include/vits_pitch.h, VITS_FLAG_PITCH_FORMANT)")
+            raise VitsError(4, f"this backend has no formant-preserving pitch shift (include/vits_pitch.h, {family}_FLAG_PITCH_FORMANT)")
 
     def op_pitch_shift(self, x, lengths, semitones, device=0, _door="op_pitch_shift"):
         """vits_op_pitch_shift: x float32 [B, N], lengths [B] -> y float32 [B, N]; item b from x[b, :lengths[b]] only, zero beyond"""
@@ -1113,27 +1145,19 @@ class VitsModel:
         except Exception:
             pass
 
-    def _opts(self, B, Tx, noise_dp, noise_prior, forced_durations, seed, max_frames, solo=False, item_seeds=None, bert=None,
-              loudness=None, loudness_out=None, pitch=None, preserve_formants=False, limit=None, prosody=None, prosody_out=None, contour=None,
-              pitch_range=None, watermark=None):
-        pitch = pitch_spec(pitch)  # (None, or a shift that does not reduce to P = Q)
-        pitch_range = range_spec(pitch_range)  # (None, or a range whose r_m is not 1000)
+    def _opts(self, B, Tx, noise_dp, noise_prior, forced_durations, seed, max_frames, solo=False, item_seeds=None, bert=None, loudness_out=None,
+              prosody=None, prosody_out=None, contour=None, tail=None, **tail_kw):
+        """the options struct of a call and what it points at -> (opts, keep).  tail: the call's Tail, or **tail_kw: the keywords of
+        tail_of() (loudness, limit, pitch, preserve_formants, pitch_range, watermark)"""
+        tail = tail or tail_of(**tail_kw)
         if contour is not None:
             self.lib._need_contour()
-        if pitch_range is not None:
-            self.lib._need_intonation()
-        if watermark is not None:  # (a watermark_spec())
-            self.lib._need_watermark()
-        opts = SynthWatermarkOpts() if watermark is not None else SynthIntonationOpts() if pitch_range is not None else SynthContourOpts() if contour is not None else SynthProsodyOpts() if prosody is not None else SynthLimitOpts() if limit is not None else SynthOpts() if pitch is None else SynthPitchOpts()
-        keep = []
         if prosody is not None:
             self.lib._need_prosody()
-        if limit is not None:
-            self.lib._need_limit()
-        if pitch is not None:
-            self.lib._need_pitch_formant() if preserve_formants else self.lib._need_pitch()
-        if loudness is not None:
-            self.lib._need_loudness()
+        if tail is not PLAIN:
+            self.lib._need_tail(tail)
+        opts = VITS_TAIL.opts(tail, prosody, contour)
+        keep = []
         if bert is not None:
             a = _f32(bert); keep.append(a)
             if a.shape != (B, self.hp.bert_dim, Tx):
@@ -1163,15 +1187,12 @@ class VitsModel:
         opts.seed = seed
         opts.max_frames = max_frames
         opts.flags = 1 if solo else 0  # VITS_FLAG_SOLO_BATCH
-        set_loudness(opts, keep, loudness, B, FLAG_LOUDNESS, loudness_out)
-        set_limit(opts, keep, limit, B, FLAG_LIMIT, loudness_out)
-        if pitch is not None:
-            opts.flags |= FLAG_PITCH | (FLAG_PITCH_FORMANT if preserve_formants else 0)  # (the formant bit only with a pitch in effect)
-            opts.pitch_semitones = pitch
-        set_prosody(opts, keep, prosody, B, prosody_out)
-        set_contour(opts, keep, contour)
-        set_intonation(opts, pitch_range)
-        set_watermark(opts, watermark)
+        if tail is not PLAIN:
+            VITS_TAIL.fill(opts, keep, tail, B, loudness_out)
+        if prosody is not None:
+            set_prosody(opts, keep, prosody, B, VITS_TAIL.prosody, prosody_out)
+        if contour is not None:
+            set_contour(opts, keep, contour, VITS_TAIL.contour)
         return opts, keep
 
     # ---- the hot path -----------------------------------------------------
@@ -1183,6 +1204,57 @@ class VitsModel:
         if rate:
             self.lib._need_resample()
         return rate
+
+    def _call(self, ids, lengths, scales, sid, pcm, pcm_scale, document, sample_rate, marks, fit_ratio, loudness_out, inputs, tail, prosody, contour):
+        """The body of synthesize / synthesize_pcm16 / synthesize_document: shape checks, options, one of the eight entry points
+        vits_synthesize[_pcm16][_rate | _marks] and vits_synthesize_document[_pcm16] by (pcm, rate, marks, document), copy out, free.
+        document: None, or the controls of document_struct(); inputs: the arguments of _opts from noise_dp to bert; prosody:
+        (item_scales, token_length_scale, token_pause, fit_frames); contour: (token_pitch, token_gain_db)"""
+        ids = _i64(ids)
+        B, Tx = ids.shape
+        lengths = _i64(lengths); sid = _i64(sid); scales = _f32(scales)
+        if lengths.shape != (B,) or sid.shape != (B,) or scales.shape != (3,):
+            raise ValueError("bad feed shapes")
+        pros_out = {}
+        opts, keep = self._opts(B, Tx, *inputs, loudness_out, prosody_arrays(B, Tx, *prosody), pros_out,
+                                contour_arrays(B, Tx, *contour, lengths, tail.pitch), tail)
+        head = (self._h, _p(ids, c_i64p), _p(lengths, c_i64p), B, Tx, _p(scales, c_f32p), _p(sid, c_i64p), ctypes.byref(opts))
+        out = ctypes.POINTER(ctypes.c_int16)() if pcm else c_f32p()
+        ns = ctypes.c_int64()
+        scale = (float(pcm_scale),) if pcm else ()
+        name = "_pcm16" if pcm else ""
+        if document is not None:
+            d, dkeep, info = document_struct(B, *document)
+            rate = self._rate(sample_rate)
+            ends = np.zeros((B, Tx), np.int64) if marks else None
+            self.lib.check(self.lib._fn("synthesize_document" + name)(*head, ctypes.byref(d), *scale, rate, ctypes.byref(out), ctypes.byref(ns),
+                                                                      _p(ends, c_i64p)))
+        else:
+            olen = np.zeros(B, dtype=np.int64)
+            rate = self._rate(sample_rate)
+            ends = None
+            if marks:  # (token_ends int64 [B,T_x] as a third value)
+                self.lib._need_marks()
+                ends = np.zeros((B, Tx), np.int64)
+            name += "_marks" if marks else "_rate" if rate else ""
+            self.lib.check(self.lib._fn("synthesize" + name)(*head, *scale, *((rate,) if marks or rate else ()), ctypes.byref(out), ctypes.byref(ns),
+                                                             _p(olen, c_i64p), *((_p(ends, c_i64p),) if marks else ())))
+        try:
+            if document is None:
+                audio = np.ctypeslib.as_array(out, shape=(B, ns.value)).copy()
+            else:
+                audio = np.ctypeslib.as_array(out, shape=(ns.value,)).copy() if ns.value else np.zeros(0, np.int16 if pcm else np.float32)
+        finally:
+            self.lib._fn("free_pcm16" if pcm else "free_output")(out)
+        if document is not None:
+            if marks:
+                info["token_ends"] = ends
+            if loudness_out:  # (one item behind the join)
+                for k in list(loudness_out):
+                    loudness_out[k] = np.asarray(loudness_out[k])[:1]
+            return audio, info
+        res = (audio, olen, ends) if marks else (audio, olen)
+        return res + (pros_out.get("fit_ratio", np.ones(B, np.float32)),) if fit_ratio else res
 
     def synthesize(self, ids, lengths, scales, sid, noise_dp=None, noise_prior=None, forced_durations=None, seed=0,
                    max_frames=0, solo=False, item_seeds=None, bert=None, sample_rate=None, marks=False, loudness=None, loudness_out=None,
@@ -1213,43 +1285,10 @@ class VitsModel:
         sample_rate: output rate in Hz (vits_synthesize_rate; S and out_lengths are then in output samples).
         loudness: a loudness_spec() (VITS_FLAG_LOUDNESS, include/vits_loudness.h): every item normalised on the device, last in the
         chain; loudness_out: a dict that receives "loudness" (LUFS of each un-normalised item) and "gain" float32 [B]."""
-        ids = _i64(ids)
-        B, Tx = ids.shape
-        lengths = _i64(lengths)
-        sid = _i64(sid)
-        scales = _f32(scales)
-        if lengths.shape != (B,) or sid.shape != (B,) or scales.shape != (3,):
-            raise ValueError("bad feed shapes")
-        pros_out = {}
-        opts, keep = self._opts(B, Tx, noise_dp, noise_prior, forced_durations, seed, max_frames, solo, item_seeds, bert, loudness, loudness_out,
-                                pitch, preserve_formants, limit, prosody_arrays(B, Tx, item_scales, token_length_scale, token_pause, fit_frames),
-                                pros_out, contour_arrays(B, Tx, token_pitch, token_gain_db, lengths, pitch_spec(pitch)), pitch_range,
-                                watermark_spec(watermark, watermark_depth_db))
-        out = c_f32p()
-        ns = ctypes.c_int64()
-        olen = np.zeros(B, dtype=np.int64)
-        rate = self._rate(sample_rate)
-        ends = None
-        if marks:
-            self.lib._need_marks()
-            ends = np.zeros((B, Tx), np.int64)
-            self.lib.check(self.lib._fn("synthesize_marks")(self._h, _p(ids, c_i64p), _p(lengths, c_i64p), B, Tx, _p(scales, c_f32p),
-                                                            _p(sid, c_i64p), ctypes.byref(opts), rate, ctypes.byref(out),
-                                                            ctypes.byref(ns), _p(olen, c_i64p), _p(ends, c_i64p)))
-        elif rate:
-            self.lib.check(self.lib._fn("synthesize_rate")(self._h, _p(ids, c_i64p), _p(lengths, c_i64p), B, Tx, _p(scales, c_f32p),
-                                                           _p(sid, c_i64p), ctypes.byref(opts), rate, ctypes.byref(out),
-                                                           ctypes.byref(ns), _p(olen, c_i64p)))
-        else:
-            self.lib.check(self.lib._fn("synthesize")(self._h, _p(ids, c_i64p), _p(lengths, c_i64p), B, Tx, _p(scales, c_f32p),
-                                                      _p(sid, c_i64p), ctypes.byref(opts), ctypes.byref(out),
-                                                      ctypes.byref(ns), _p(olen, c_i64p)))
-        try:
-            audio = np.ctypeslib.as_array(out, shape=(B, ns.value)).copy()
-        finally:
-            self.lib._fn("free_output")(out)
-        res = (audio, olen, ends) if marks else (audio, olen)
-        return res + (pros_out.get("fit_ratio", np.ones(B, np.float32)),) if fit_ratio else res
+        return self._call(ids, lengths, scales, sid, False, 1.0, None, sample_rate, marks, fit_ratio, loudness_out,
+                          (noise_dp, noise_prior, forced_durations, seed, max_frames, solo, item_seeds, bert),
+                          tail_of(loudness, limit, pitch, preserve_formants, pitch_range, watermark_spec(watermark, watermark_depth_db)),
+                          (item_scales, token_length_scale, token_pause, fit_frames), (token_pitch, token_gain_db))
 
     def synthesize_pcm16(self, ids, lengths, scales, sid, pcm_scale=1.0, noise_dp=None, noise_prior=None, forced_durations=None,
                          seed=0, max_frames=0, solo=False, item_seeds=None, bert=None, sample_rate=None, marks=False, loudness=None,
@@ -1262,43 +1301,10 @@ class VitsModel:
         device: returns (pcm int16 [B,S], out_lengths int64 [B]).  sample_rate: as for synthesize (vits_synthesize_pcm16_rate:
         the resampler does the conversion in its epilogue).  loudness / loudness_out: as for synthesize (pcm_scale multiplies the
         normalised audio, as before)."""
-        ids = _i64(ids)
-        B, Tx = ids.shape
-        lengths = _i64(lengths); sid = _i64(sid); scales = _f32(scales)
-        if lengths.shape != (B,) or sid.shape != (B,) or scales.shape != (3,):
-            raise ValueError("bad feed shapes")
-        pros_out = {}
-        opts, keep = self._opts(B, Tx, noise_dp, noise_prior, forced_durations, seed, max_frames, solo, item_seeds, bert, loudness, loudness_out,
-                                pitch, preserve_formants, limit, prosody_arrays(B, Tx, item_scales, token_length_scale, token_pause, fit_frames),
-                                pros_out, contour_arrays(B, Tx, token_pitch, token_gain_db, lengths, pitch_spec(pitch)), pitch_range,
-                                watermark_spec(watermark, watermark_depth_db))
-        out = ctypes.POINTER(ctypes.c_int16)()
-        ns = ctypes.c_int64()
-        olen = np.zeros(B, dtype=np.int64)
-        rate = self._rate(sample_rate)
-        ends = None
-        if marks:  # (vits_synthesize_pcm16_marks: token_ends int64 [B,T_x] as a third value)
-            self.lib._need_marks()
-            ends = np.zeros((B, Tx), np.int64)
-            self.lib.check(self.lib._fn("synthesize_pcm16_marks")(self._h, _p(ids, c_i64p), _p(lengths, c_i64p), B, Tx,
-                                                                  _p(scales, c_f32p), _p(sid, c_i64p), ctypes.byref(opts),
-                                                                  float(pcm_scale), rate, ctypes.byref(out), ctypes.byref(ns),
-                                                                  _p(olen, c_i64p), _p(ends, c_i64p)))
-        elif rate:
-            self.lib.check(self.lib._fn("synthesize_pcm16_rate")(self._h, _p(ids, c_i64p), _p(lengths, c_i64p), B, Tx,
-                                                                 _p(scales, c_f32p), _p(sid, c_i64p), ctypes.byref(opts),
-                                                                 float(pcm_scale), rate, ctypes.byref(out), ctypes.byref(ns),
-                                                                 _p(olen, c_i64p)))
-        else:
-            self.lib.check(self.lib._fn("synthesize_pcm16")(self._h, _p(ids, c_i64p), _p(lengths, c_i64p), B, Tx, _p(scales, c_f32p),
-                                                            _p(sid, c_i64p), ctypes.byref(opts), float(pcm_scale), ctypes.byref(out),
-                                                            ctypes.byref(ns), _p(olen, c_i64p)))
-        try:
-            pcm = np.ctypeslib.as_array(out, shape=(B, ns.value)).copy()
-        finally:
-            self.lib._fn("free_pcm16")(out)
-        res = (pcm, olen, ends) if marks else (pcm, olen)
-        return res + (pros_out.get("fit_ratio", np.ones(B, np.float32)),) if fit_ratio else res
+        return self._call(ids, lengths, scales, sid, True, pcm_scale, None, sample_rate, marks, fit_ratio, loudness_out,
+                          (noise_dp, noise_prior, forced_durations, seed, max_frames, solo, item_seeds, bert),
+                          tail_of(loudness, limit, pitch, preserve_formants, pitch_range, watermark_spec(watermark, watermark_depth_db)),
+                          (item_scales, token_length_scale, token_pause, fit_frames), (token_pitch, token_gain_db))
 
     def synthesize_document(self, ids, lengths, scales, sid, pcm=False, pcm_scale=1.0, lead_frames=0, gap_frames=None, fade_samples=0,
                             trim_db=None, trim_keep_frames=0, marks=False, seed=0, max_frames=0, item_seeds=None, bert=None, sample_rate=None,
@@ -1311,37 +1317,10 @@ class VitsModel:
         marks=True info["token_ends"] int64 [B, T_x].  The per-item keywords are those of synthesize; loudness_out receives ONE value per
         key, of the whole document.  watermark: the document is marked as the one item it has become."""
         self.lib._need_document()
-        ids = _i64(ids)
-        B, Tx = ids.shape
-        lengths = _i64(lengths); sid = _i64(sid); scales = _f32(scales)
-        if lengths.shape != (B,) or sid.shape != (B,) or scales.shape != (3,):
-            raise ValueError("bad feed shapes")
-        pros_out = {}
-        opts, keep = self._opts(B, Tx, None, None, forced_durations, seed, max_frames, True, item_seeds, bert, loudness, loudness_out,
-                                pitch, preserve_formants, limit, prosody_arrays(B, Tx, item_scales, token_length_scale, token_pause, fit_frames),
-                                pros_out, contour_arrays(B, Tx, token_pitch, token_gain_db, lengths, pitch_spec(pitch)), pitch_range,
-                                watermark_spec(watermark, watermark_depth_db))
-        d, dkeep, info = document_struct(B, lead_frames, gap_frames, fade_samples, trim_db, trim_keep_frames)
-        rate = self._rate(sample_rate)
-        ends = np.zeros((B, Tx), np.int64) if marks else None
-        ns = ctypes.c_int64()
-        head = (self._h, _p(ids, c_i64p), _p(lengths, c_i64p), B, Tx, _p(scales, c_f32p), _p(sid, c_i64p), ctypes.byref(opts), ctypes.byref(d))
-        if pcm:
-            out = ctypes.POINTER(ctypes.c_int16)()
-            self.lib.check(self.lib._fn("synthesize_document_pcm16")(*head, float(pcm_scale), rate, ctypes.byref(out), ctypes.byref(ns), _p(ends, c_i64p)))
-        else:
-            out = c_f32p()
-            self.lib.check(self.lib._fn("synthesize_document")(*head, rate, ctypes.byref(out), ctypes.byref(ns), _p(ends, c_i64p)))
-        try:
-            audio = np.ctypeslib.as_array(out, shape=(ns.value,)).copy() if ns.value else np.zeros(0, np.int16 if pcm else np.float32)
-        finally:
-            self.lib._fn("free_pcm16" if pcm else "free_output")(out)
-        if marks:
-            info["token_ends"] = ends
-        if loudness_out:  # (one item behind the join)
-            for k in list(loudness_out):
-                loudness_out[k] = np.asarray(loudness_out[k])[:1]
-        return audio, info
+        return self._call(ids, lengths, scales, sid, bool(pcm), pcm_scale, (lead_frames, gap_frames, fade_samples, trim_db, trim_keep_frames),
+                          sample_rate, marks, False, loudness_out, (None, None, forced_durations, seed, max_frames, True, item_seeds, bert),
+                          tail_of(loudness, limit, pitch, preserve_formants, pitch_range, watermark_spec(watermark, watermark_depth_db)),
+                          (item_scales, token_length_scale, token_pause, fit_frames), (token_pitch, token_gain_db))
 
     def stream(self, ids, scales, sid, chunk_frames=64, noise_dp=None, noise_prior=None, forced_durations=None, seed=0, bert=None,
                sample_rate=None, on_marks=None, loudness=None, pitch=None, limit=None, item_scales=None, token_length_scale=None,
@@ -1358,16 +1337,8 @@ class VitsModel:
         ceil(a*L/M) <= n < ceil(b*L/M), so chunk sizes vary by one sample.
         on_marks: called once with token_ends int64 [T_x] (vits_stream_marks, the stream's own output samples) as soon as the
         stream is open, before the first chunk."""
-        if loudness is not None:  # (vits_stream_open* refuse VITS_FLAG_LOUDNESS the same way; here before any device work)
-            raise VitsError(4, "a stream cannot be loudness-normalised: an integrated-loudness or peak target needs the whole utterance "
-                               "before the first chunk")
-        if limit is not None:
-            raise VitsError(4, "a stream cannot be limited: the limiter's look-ahead and its loudness passes need the whole utterance "
-                               "before the first chunk")
-        if pitch_spec(pitch) is not None:
-            raise VitsError(4, "a stream cannot be pitch-shifted: the phase recursion needs the frames before a chunk")
-        if watermark_spec(watermark) is not None:
-            raise VitsError(4, "a stream cannot be watermarked (VITS_FLAG_WATERMARK): the mark is a stage of the output tail, and a stream has none")
+        # (vits_stream_open* refuse the flags the same way; here before any device work)
+        tail_of(loudness, limit, pitch, watermark=watermark_spec(watermark)).refuse_stream(VITS_TAIL.word, None, lambda msg: VitsError(4, msg))
         if on_marks is not None:
             self.lib._need_marks()
         if not self.lib.has("stream_open"):

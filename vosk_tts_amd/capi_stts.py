@@ -5,8 +5,8 @@ import ctypes
 
 import numpy as np
 
-from .capi import (LIMIT_FIELDS, Contour, VitsError, VitsLib, _f32, _i32, _i64, _p, c_f32p, c_i32p, c_i64p, contour_arrays, pitch_spec,
-                   range_spec, set_contour, set_intonation, set_limit, set_loudness, set_watermark, watermark_spec)
+from .capi import (LIMIT_FIELDS, Contour, TailFamily, VitsError, VitsLib, _f32, _i32, _i64, _p, c_f32p, c_i32p, c_i64p, contour_arrays,
+                   pitch_spec, set_contour, tail_of, watermark_spec)
 from .weights_stts import SttsHParams
 
 
@@ -81,6 +81,11 @@ class SttsWatermarkOpts(SttsIntonationOpts):
     _fields_ = [("watermark_key", ctypes.c_uint32), ("watermark_depth_db", ctypes.c_float)]
 
 
+STTS_TAIL = TailFamily("STTS", (SttsOpts, SttsLoudnessOpts, SttsPitchOpts, SttsLimitOpts, SttsContourOpts, SttsIntonationOpts, SttsWatermarkOpts),
+                       loudness=STTS_FLAG_LOUDNESS, limit=STTS_FLAG_LIMIT, pitch=STTS_FLAG_PITCH, formant=STTS_FLAG_PITCH_FORMANT,
+                       contour=STTS_FLAG_CONTOUR, intonation=STTS_FLAG_INTONATION, watermark=STTS_FLAG_WATERMARK)
+
+
 class SttsModel:
     """Owns one stts_model* ; `vocoder` is a capi.VitsModel created from a vocoder-only blob (kept alive here)."""
 
@@ -153,57 +158,24 @@ class SttsModel:
         oracle would ignore the flag, which is refused here instead"""
         if denoiser_strength is None:
             return
-        if not getattr(self.vlib, "has_denoise", False):
-            raise VitsError(4, "this backend has no denoiser (include/vits_denoise.h)")
+        self.vlib._need_denoise()
         opts.flags |= STTS_FLAG_DENOISE
         opts.denoiser_strength = float(denoiser_strength)
         opts.denoiser_filter_length = int(denoiser_filter_length or 0)
 
-    def _loudness(self, opts, keep, spec, B, out):
-        """STTS_FLAG_LOUDNESS and its fields (include/vits_loudness.h; spec = capi.loudness_spec(), None = off).  Only the device library
-        normalises: the CPU oracle would ignore the flag, which is refused here instead.  `opts` must then be a SttsLoudnessOpts"""
-        if spec is None:
-            return
-        assert isinstance(opts, SttsLoudnessOpts)  # (SttsPitchOpts is one)
-        if not getattr(self.vlib, "has_loudness", False):
-            raise VitsError(4, "this backend has no loudness normalisation (include/vits_loudness.h)")
-        set_loudness(opts, keep, spec, B, STTS_FLAG_LOUDNESS, out)
-
-    def _limit(self, opts, keep, spec, B, out):
-        """STTS_FLAG_LIMIT and its fields (include/vits_limit.h; spec = capi.limit_spec(), None = off); `opts` must then be a SttsLimitOpts"""
-        if spec is None:
-            return
-        assert isinstance(opts, SttsLimitOpts)
-        set_limit(opts, keep, spec, B, STTS_FLAG_LIMIT, out)
-
-    def _opts_for(self, loudness, pitch, preserve_formants=False, limit=None, contour=None, pitch_range=None, watermark=None):
-        """the options struct a call needs: the plain one, the one with the loudness fields, the one with the pitch behind those, the
-        one with the limiter behind that, the one with the contour pointer behind that, or the one with pitch_range (a range_spec(),
-        include/vits_intonation.h), or the one with the watermark's key and depth (a capi.watermark_spec(), include/vits_watermark.h) last;
-        preserve_formants sets its bit only with a pitch in effect"""
-        if watermark is not None and not getattr(self.vlib, "has_watermark", False):
-            raise VitsError(4, "this backend has no audio watermark (include/vits_watermark.h)")
-        if pitch_range is not None and not getattr(self.vlib, "has_intonation", False):
-            raise VitsError(4, "this backend has no intonation control (include/vits_intonation.h)")
-        if limit is not None and not getattr(self.vlib, "has_limit", False):
-            raise VitsError(4, "this backend has no peak limiter (include/vits_limit.h)")
-        if contour is not None and not getattr(self.vlib, "has_contour", False):
-            raise VitsError(4, "this backend has no pitch / volume contours (include/vits_contour.h)")
-        if pitch_spec(pitch) is not None or limit is not None or contour is not None or pitch_range is not None or watermark is not None:
-            if pitch_spec(pitch) is not None and not getattr(self.vlib, "has_pitch", False):
-                raise VitsError(4, "this backend has no pitch shifter (include/vits_pitch.h)")
-            if pitch_spec(pitch) is not None and preserve_formants and not getattr(self.vlib, "has_pitch_formant", False):
-                raise VitsError(4, "this backend has no formant-preserving pitch shift (include/vits_pitch.h, STTS_FLAG_PITCH_FORMANT)")
-            opts = (SttsWatermarkOpts() if watermark is not None else SttsIntonationOpts() if pitch_range is not None else SttsContourOpts() if contour is not None
-                    else SttsPitchOpts() if limit is None else SttsLimitOpts())
-            set_intonation(opts, pitch_range, STTS_FLAG_INTONATION)
-            set_watermark(opts, watermark, STTS_FLAG_WATERMARK)
-            if pitch_spec(pitch) is None:
-                return opts
-            opts.flags |= STTS_FLAG_PITCH | (STTS_FLAG_PITCH_FORMANT if preserve_formants else 0)
-            opts.pitch_semitones = float(pitch)
-            return opts
-        return SttsOpts() if loudness is None else SttsLoudnessOpts()
+    def _opts_for(self, loudness, pitch, preserve_formants=False, limit=None, contour=None, pitch_range=None, watermark=None, B=1, keep=None,
+                  out=None):
+        """The options struct of a call, with the tail's flags and fields written (capi.TailFamily: the plain struct for a plain call, else
+        the first of the chain that has every field asked for).  loudness, limit, watermark: their specs; pitch, pitch_range: as tail_of()
+        takes them; contour: the arrays of contour_arrays().  B, keep, out: the result arrays of the loudness stage and the limiter
+        (TailFamily.fill).  A stage the library does not export is refused: the CPU oracle would ignore the flag"""
+        tail = tail_of(loudness, limit, pitch, preserve_formants, pitch_range, watermark)
+        if contour is not None:
+            self.vlib._need_contour()
+        self.vlib._need_tail(tail, STTS_TAIL.word)
+        opts = STTS_TAIL.opts(tail, contour=contour)
+        STTS_TAIL.fill(opts, [] if keep is None else keep, tail, B, out)
+        return opts
 
     def _need_marks(self):
         if not self.has_marks:
@@ -244,10 +216,12 @@ class SttsModel:
         if want_audio and (token_pitch is not None or token_gain_db is not None):
             con = contour_arrays(1, T, None if token_pitch is None else _f32(token_pitch).reshape(1, -1),
                                  None if token_gain_db is None else _f32(token_gain_db).reshape(1, -1), None, pitch_spec(pitch))
-        opts = self._opts_for(loudness, pitch if want_audio else None, preserve_formants, limit if want_audio else None, con,
-                              range_spec(pitch_range) if want_audio else None,
-                              watermark_spec(watermark, watermark_depth_db) if want_audio else None)
-        set_contour(opts, keep, con, STTS_FLAG_CONTOUR)
+        if want_audio:
+            opts = self._opts_for(loudness, pitch, preserve_formants, limit, con, pitch_range, watermark_spec(watermark, watermark_depth_db),
+                                  1, keep, loudness_out)
+        else:  # (the mel alone: no stage of the tail applies)
+            opts = self._opts_for(None, None)
+        set_contour(opts, keep, con, STTS_TAIL.contour)
         if noise is not None:
             a = _f32(noise); keep.append(a)
             if a.ndim != 2 or a.shape[0] != self.hp.n_feats:
@@ -257,9 +231,6 @@ class SttsModel:
         opts.seed = seed
         opts.n_timesteps = n_timesteps
         self._denoise(opts, denoiser_strength, denoiser_filter_length)
-        if want_audio:
-            self._loudness(opts, keep, loudness, 1, loudness_out)
-            self._limit(opts, keep, limit, 1, loudness_out)
         b = None if bert is None else _f32(bert)
         if b is not None and b.shape != (self.hp.bert_dim, T):
             raise ValueError("bert must be [768, T]")
@@ -292,16 +263,7 @@ class SttsModel:
         concatenation equals synthesize()'s audio for the same arguments.  on_marks: called once with token_ends int64 [T]
         (vits_stream_marks) as soon as the stream is open.  loudness: refused (stts_stream_open refuses STTS_FLAG_LOUDNESS the same
         way; here before any device work)."""
-        if loudness is not None:
-            raise VitsError(4, "a stream cannot be loudness-normalised: an integrated-loudness or peak target needs the whole utterance "
-                               "before the first chunk")
-        if limit is not None:
-            raise VitsError(4, "a stream cannot be limited: the limiter's look-ahead and its loudness passes need the whole utterance "
-                               "before the first chunk")
-        if pitch_spec(pitch) is not None:
-            raise VitsError(4, "a stream cannot be pitch-shifted: the phase recursion needs the frames before a chunk")
-        if watermark_spec(watermark) is not None:
-            raise VitsError(4, "a stream cannot be watermarked (STTS_FLAG_WATERMARK): the mark is a stage of the output tail, and a stream has none")
+        tail_of(loudness, limit, pitch, watermark=watermark_spec(watermark)).refuse_stream(STTS_TAIL.word, None, lambda msg: VitsError(4, msg))
         if on_marks is not None:
             self._need_marks()
         if self._vocoder is None:
@@ -371,13 +333,13 @@ class SttsModel:
         b = None if bert is None else _f32(bert)
         p = None if phone_duration_extra is None else _f32(phone_duration_extra)
         con = contour_arrays(B, T, token_pitch, token_gain_db, lengths, pitch_spec(pitch))
-        opts = self._opts_for(loudness, pitch, preserve_formants, limit, con, range_spec(pitch_range), watermark)
+        keep = [ids, lengths, sid, scales, b, p]
+        opts = self._opts_for(loudness, pitch, preserve_formants, limit, con, pitch_range, watermark, results or B, keep,
+                              loudness_out)  # (per-item gains; loudness_out as for synthesize, [B])
         opts.seed = seed; opts.n_timesteps = n_timesteps
         self._denoise(opts, denoiser_strength, denoiser_filter_length)
-        keep = [ids, lengths, sid, scales, b, p, opts]
-        set_contour(opts, keep, con, STTS_FLAG_CONTOUR)
-        self._loudness(opts, keep, loudness, results or B, loudness_out)  # (per-item gains; loudness_out as for synthesize, [B])
-        self._limit(opts, keep, limit, results or B, loudness_out)
+        keep.append(opts)
+        set_contour(opts, keep, con, STTS_TAIL.contour)
         if item_seeds is not None:
             sd = np.ascontiguousarray(item_seeds, dtype=np.uint64)
             if sd.shape != (B,):

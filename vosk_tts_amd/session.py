@@ -19,8 +19,7 @@ import threading
 import numpy as np
 
 from .capi import VitsLib
-from .outopts import (DOCUMENT_FEEDS, document_from_feed, limit_from_feed, loudness_from_feed, pitch_from_feed, range_from_feed,
-                      watermark_from_feed)
+from .outopts import DOCUMENT_FEEDS, Tail, document_from_feed
 
 log = logging.getLogger(__name__)
 
@@ -79,7 +78,7 @@ class RequestCoalescer:
         peak, t = self._peaks.get(key, (1, 0.0))
         if present >= peak or now - t > 0.05:
             self._peaks[key] = (max(present, 1), now)
-        if len(self._peaks) > 64:  # (keys are (kind, scales, scale) tuples: bounded in practice, bounded here for good)
+        if len(self._peaks) > 64:  # (keys are (kind, scale, rate, marks, tail) tuples: bounded in practice, bounded here for good)
             self._peaks = {key: self._peaks[key]}
 
     def _gather(self, me, batch):
@@ -303,30 +302,20 @@ class VitsSession:
         """reqs: [(ids [1,T] int64, sid, seed, scales)] -> per request (audio-or-pcm [1,S_b], lengths [1]); one request: the plain call.
         The scales ride with the request (include/vits_prosody.h): requests that agree on them run as the batch they always were, requests
         that differ run as ONE solo batch with their scales as its item_scales."""
-        # (rate: output sample rate in Hz, 0 = the voice's own; marks: the requests want their token ends, include/vits_marks.h.  Both are
-        #  part of the key, so a batch has one rate and either every request of it gets a third value or none does)
-        # loud: the normalisation of the batch (capi.loudness_spec(), None = none; include/vits_loudness.h): part of the key like the rate, and
-        # measured and applied per item, so a request's result does not depend on what it was batched with
-        # pitch: the shift of the batch in semitones (None = none; include/vits_pitch.h): part of the key as well, one value per call
-        # formants: that shift with the spectral envelope kept (VITS_FLAG_PITCH_FORMANT); False whenever pitch is None
-        # limit: the limiter of the batch (capi.limit_spec(), None = none; include/vits_limit.h): part of the key, applied per item
-        # prange: the intonation range of the batch (None = none; include/vits_intonation.h): a further entry that only a request with one has
-        # the watermark of the batch (include/vits_watermark.h): a further entry ("wm", key, depth) that only a marked request has
-        kind, scale, rate, marks, loud, pitch, formants, limit = key[:8]
-        pk = self._pitch_kw(pitch, formants, limit)
-        for extra in key[8:]:
-            if isinstance(extra, tuple) and extra[0] == "wm":
-                pk = dict(pk, watermark=extra[1], **({"watermark_depth_db": extra[2]} if extra[2] else {}))
-            else:
-                pk = dict(pk, pitch_range=extra)
+        # key: (kind "pcm" / "f32", pcm scale, rate: output sample rate in Hz, 0 = the voice's own, marks: the requests want their token
+        # ends, include/vits_marks.h, tail: the outopts.Tail of the batch).  A batch has one rate, either every request of it gets a third
+        # value or none does, and one tail, whose stages measure and apply per item: a request's result does not depend on what it
+        # was batched with
+        kind, scale, rate, marks, tail = key
+        pk = tail.kw()
         scales = np.array(reqs[0][3], np.float32)
         if len(reqs) == 1:
             ids, sid, seed = reqs[0][:3]
             lens = np.array([ids.shape[1]], np.int64)
             if kind == "pcm":
                 return [self._model.synthesize_pcm16(ids, lens, scales, np.array([sid], np.int64), pcm_scale=scale, seed=seed, sample_rate=rate,
-                                                     marks=marks, loudness=loud, **pk)]
-            return [self._model.synthesize(ids, lens, scales, np.array([sid], np.int64), seed=seed, sample_rate=rate, marks=marks, loudness=loud, **pk)]
+                                                     marks=marks, **pk)]
+            return [self._model.synthesize(ids, lens, scales, np.array([sid], np.int64), seed=seed, sample_rate=rate, marks=marks, **pk)]
         # batch sizes come in powers of two (filled up with one-token dummies, whose padding tiles the ragged solo batch never
         # computes): every (batch size, length bucket) is a workspace and two captured graphs inside the engine, and a thread pool
         # produces every batch size between 1 and its own size
@@ -345,10 +334,10 @@ class VitsSession:
         seeds = np.array([r[2] for r in reqs], np.uint64)
         if kind == "pcm":
             res = self._model.synthesize_pcm16(batch, lens, scales, sids, pcm_scale=scale, seed=int(seeds[0]), solo=True, item_seeds=seeds,
-                                               sample_rate=rate, marks=marks, loudness=loud, **pk)
+                                               sample_rate=rate, marks=marks, **pk)
         else:
             res = self._model.synthesize(batch, lens, scales, sids, seed=int(seeds[0]), solo=True, item_seeds=seeds, sample_rate=rate, marks=marks,
-                                         loudness=loud, **pk)
+                                         **pk)
         out, ol = res[0], res[1]
         if marks:  # each request its own tokens' ends
             return [(out[b:b + 1, :int(ol[b])].copy(), ol[b:b + 1].copy(), res[2][b:b + 1, :int(lens[b])].copy()) for b in range(n_real)]
@@ -406,36 +395,6 @@ class VitsSession:
             raise ValueError(f"sample_rate {rate}: must be positive, or None for the voice's own {self.hp.sampling_rate} Hz")
         return 0 if rate == self.hp.sampling_rate else rate
 
-    def _loudness(self, feed):
-        return loudness_from_feed(self._lib, feed)
-
-    def _limit(self, feed):
-        return limit_from_feed(self._lib, feed)
-
-    @staticmethod
-    def _pitch_kw(pitch, formants, limit=None):
-        """the keywords of the model's calls: none without a shift and without a limiter (the call as it was)"""
-        kw = {} if limit is None else {"limit": limit}
-        if pitch is None:
-            return kw
-        return dict(kw, pitch=pitch, preserve_formants=True) if formants else dict(kw, pitch=pitch)
-
-    @staticmethod
-    def _range_key(prange):
-        """what an intonation range adds to a coalescer key: nothing without one (the key of before), so requests with different ranges
-        do not share a batch"""
-        return () if prange is None else (prange,)
-
-    @staticmethod
-    def _wm_key(wm):
-        """what a watermark adds to a coalescer key: nothing without one (the key of before); a marked request is batched only with
-        requests that carry the same key and depth"""
-        return (("wm", wm["watermark"], wm.get("watermark_depth_db", 0.0)),) if wm else ()
-
-    @staticmethod
-    def _range_kw(prange):
-        return {} if prange is None else {"pitch_range": prange}
-
     def run_document(self, input_feed, scale=1.0, pcm16=True):
         """A document (include/vits_document.h): the feed of a batch -- "input" [B, T], "input_lengths" [B], "sid" [B], "bert" -- with at
         least one of the document feeds "vits.doc_gap_frames" int [B], "vits.doc_lead_frames", "vits.doc_fade_samples",
@@ -451,13 +410,11 @@ class VitsSession:
             if k in feed:
                 raise ValueError(f"feed '{k}' with a document: injected noise belongs to the parity calls")
         self._watch()
-        pitch, formants = pitch_from_feed(self._lib, feed)
         audio, info = self._model.synthesize_document(
             ids, np.asarray(feed["input_lengths"]).reshape(-1), np.asarray(feed["scales"], np.float32).reshape(-1), sid, pcm=bool(pcm16),
             pcm_scale=float(scale), forced_durations=feed.get("vits.forced_durations"), seed=int(seed), item_seeds=feed.get("vits.item_seeds"),
-            bert=feed.get("bert"), sample_rate=self._rate(feed.get("vits.sample_rate")), marks=self._marks(feed), loudness=self._loudness(feed),
-            **self._pitch_kw(pitch, formants, self._limit(feed)), **self._prosody(feed), **self._contour(feed),
-            **self._range_kw(range_from_feed(self._lib, feed)), **watermark_from_feed(self._lib, feed), **doc)
+            bert=feed.get("bert"), sample_rate=self._rate(feed.get("vits.sample_rate")), marks=self._marks(feed),
+            **Tail.from_feed(self._lib, feed).kw(), **self._prosody(feed), **self._contour(feed), **doc)
         self.last_lengths = np.array([audio.shape[0]], np.int64)
         return audio, info
 
@@ -474,14 +431,10 @@ class VitsSession:
         self._watch()
         rate = self._rate(feed.get("vits.sample_rate"))
         marks = self._marks(feed)
-        loud = self._loudness(feed)
-        pitch, formants = pitch_from_feed(self._lib, feed)  # ("vits.pitch": the audio shifted by that many semitones, behind the decoder)
-        limit = self._limit(feed)  # ("vits.limit": the look-ahead peak limiter with the loudness gain, or alone; include/vits_limit.h)
-        prange = range_from_feed(self._lib, feed)  # ("vits.pitch_range": the intonation range; include/vits_intonation.h)
-        wm = watermark_from_feed(self._lib, feed)  # ("vits.watermark_key" / "vits.watermark_depth_db"; include/vits_watermark.h)
+        tail = Tail.from_feed(self._lib, feed)  # (the loudness, limiter, pitch, intonation and watermark feeds; outopts.TAIL_FEEDS)
         n = self._coalescable(feed, ids)
         if n:
-            key = ("f32", 1.0, rate, marks, loud, pitch, formants, limit) + self._range_key(prange) + self._wm_key(wm)
+            key = ("f32", 1.0, rate, marks, tail)
             res = self.coalescer.submit(key, np.ascontiguousarray(ids[:, :n], np.int64), int(sid[0]), int(seed), self._scales(feed))
             self.last_lengths = res[1]
             if marks:  # (the request's own tokens; columns beyond its length repeat the last end, as the C ABI pads them)
@@ -491,8 +444,8 @@ class VitsSession:
             ids, np.asarray(feed["input_lengths"]).reshape(-1), np.asarray(feed["scales"], np.float32).reshape(-1), sid,
             noise_dp=feed.get("vits.noise_dp"), noise_prior=feed.get("vits.noise_prior"),
             forced_durations=feed.get("vits.forced_durations"), seed=int(seed), solo=bool(feed.get("vits.solo", False)),
-            item_seeds=feed.get("vits.item_seeds"), bert=feed.get("bert"), sample_rate=rate, marks=marks, loudness=loud,
-            **self._pitch_kw(pitch, formants, limit), **self._prosody(feed), **self._contour(feed), **self._range_kw(prange), **wm)
+            item_seeds=feed.get("vits.item_seeds"), bert=feed.get("bert"), sample_rate=rate, marks=marks,
+            **tail.kw(), **self._prosody(feed), **self._contour(feed))
         self.last_lengths = res[1]
         return [res[0][:, None, None, :], res[2]] if marks else [res[0][:, None, None, :]]
 
@@ -556,14 +509,10 @@ class VitsSession:
         self._watch()
         rate = self._rate(sample_rate if sample_rate is not None else feed.get("vits.sample_rate"))
         marks = self._marks(feed)
-        loud = self._loudness(feed)
-        pitch, formants = pitch_from_feed(self._lib, feed)
-        limit = self._limit(feed)
-        prange = range_from_feed(self._lib, feed)
-        wm = watermark_from_feed(self._lib, feed)
+        tail = Tail.from_feed(self._lib, feed)
         n = self._coalescable(feed, ids)
         if n:
-            key = ("pcm", float(scale), rate, marks, loud, pitch, formants, limit) + self._range_key(prange) + self._wm_key(wm)
+            key = ("pcm", float(scale), rate, marks, tail)
             res = self.coalescer.submit(key, np.ascontiguousarray(ids[:, :n], np.int64), int(sid[0]), int(seed), self._scales(feed))
             pcm, lengths = res[0], res[1]
             self.last_lengths = lengths
@@ -575,8 +524,8 @@ class VitsSession:
             ids, np.asarray(feed["input_lengths"]).reshape(-1), np.asarray(feed["scales"], np.float32).reshape(-1), sid,
             pcm_scale=float(scale), noise_dp=feed.get("vits.noise_dp"), noise_prior=feed.get("vits.noise_prior"),
             forced_durations=feed.get("vits.forced_durations"), seed=int(seed), solo=bool(feed.get("vits.solo", False)),
-            item_seeds=feed.get("vits.item_seeds"), bert=feed.get("bert"), sample_rate=rate, marks=marks, loudness=loud,
-            **self._pitch_kw(pitch, formants, limit), **self._prosody(feed), **self._contour(feed), **self._range_kw(prange), **wm)
+            item_seeds=feed.get("vits.item_seeds"), bert=feed.get("bert"), sample_rate=rate, marks=marks,
+            **tail.kw(), **self._prosody(feed), **self._contour(feed))
         pcm, lengths = res[0], res[1]
         self.last_lengths = lengths
         if marks:
@@ -593,21 +542,7 @@ class VitsSession:
         if any(k in feed for k in DOCUMENT_FEEDS):
             raise ValueError("a stream cannot take a document: the join and the stages behind it need every segment before the first chunk "
                              "(run() / run_pcm16() / run_document() take the \"vits.doc_*\" feeds)")
-        if self._loudness(feed) is not None:
-            raise ValueError("a stream cannot be loudness-normalised: an integrated-loudness or peak target needs the whole utterance before "
-                             "the first chunk (run() / run_pcm16() take the loudness feeds)")
-        if self._limit(feed) is not None:
-            raise ValueError("a stream cannot be limited: the limiter's look-ahead and its loudness passes need the whole utterance before the "
-                             "first chunk (run() / run_pcm16() take \"vits.limit\")")
-        if pitch_from_feed(self._lib, feed)[0] is not None:
-            raise ValueError("a stream cannot be pitch-shifted: the phase recursion needs the frames before a chunk (run() / run_pcm16() "
-                             "take \"vits.pitch\")")
-        if range_from_feed(self._lib, feed) is not None:
-            raise ValueError("a stream cannot take an intonation range: the median of the F0 track needs the whole utterance before the "
-                             "first chunk (run() / run_pcm16() take \"vits.pitch_range\")")
-        if watermark_from_feed(self._lib, feed):
-            raise ValueError("a stream cannot be watermarked (VITS_FLAG_WATERMARK): the mark is a stage of the output tail, and a stream has "
-                             "none (run() / run_pcm16() take \"vits.watermark_key\")")
+        Tail.from_feed(self._lib, feed).refuse_stream("VITS", "run() / run_pcm16() take")
         if any(k in feed for k in _CONTOUR):
             raise ValueError("a stream cannot be contoured: the position recurrence and the phase recursion need the whole utterance before "
                              "the first chunk (run() / run_pcm16() take \"vits.token_pitch\" / \"vits.token_gain_db\")")

@@ -6,13 +6,13 @@ and returns [wav float32 [1,S], wav_lengths int64 [1]] like the exported graph (
 The arithmetic runs in HIP kernels behind include/stts_mi355.h; there is no CPU path."""
 import itertools
 import threading
+from dataclasses import replace
 
 import numpy as np
 
 from .capi import VitsLib
 from .capi_stts import SttsModel
-from .outopts import (DOCUMENT_FEEDS, document_from_feed, limit_from_feed, loudness_from_feed, pitch_from_feed, range_from_feed,
-                      watermark_from_feed)
+from .outopts import DOCUMENT_FEEDS, Tail, document_from_feed
 
 _INPUTS = ("input", "input_lengths", "scales", "sid", "bert", "phone_duration_extra")
 _EXT = ("vits.noise", "vits.seed", "vits.n_timesteps", "vits.sample_rate", "vits.denoiser_strength", "vits.denoiser_filter_length",
@@ -98,41 +98,25 @@ class SttsSession:
         out = self._lib.op_resample(audio, lengths, native, rate, device=self._vocoder.device)
         return out, np.array([self._lib.out_samples(n, native, rate) for n in lengths], np.int64)
 
-    def _loudness(self, feed):
-        return loudness_from_feed(self._lib, feed)
-
-    def _limit(self, feed):
-        return limit_from_feed(self._lib, feed)
-
-    def _pitch(self, feed):
-        """outopts.pitch_from_feed and the contour feeds "vits.token_pitch" / "vits.token_gain_db" (float [1, T], include/vits_contour.h)
-        as the keywords of the model's calls: empty without a shift and without a contour"""
-        p, formants = pitch_from_feed(self._lib, feed)
-        kw = {} if p is None else {"pitch": p, "preserve_formants": True} if formants else {"pitch": p}
-        for k, name in (("vits.token_pitch", "token_pitch"), ("vits.token_gain_db", "token_gain_db")):
-            if k in feed:
-                kw[name] = np.asarray(feed[k], np.float32).reshape(-1)
-        r = range_from_feed(self._lib, feed)  # ("vits.pitch_range": the intonation range, include/vits_intonation.h)
-        if r is not None:
-            kw["pitch_range"] = r
-        return kw
-
-    def _wm(self, feed):
-        """"vits.watermark_key" / "vits.watermark_depth_db" (include/vits_watermark.h) as the keywords of the model's calls"""
-        return watermark_from_feed(self._lib, feed)
+    @staticmethod
+    def _contour(feed):
+        """the contour feeds "vits.token_pitch" / "vits.token_gain_db" (float [1, T], include/vits_contour.h) as the keywords of the model's
+        single-utterance call: empty without a contour"""
+        return {k[5:]: np.asarray(feed[k], np.float32).reshape(-1) for k in ("vits.token_pitch", "vits.token_gain_db") if k in feed}
 
     def mark(self, audio, lengths, wm):
-        """audio float32 [B, S] with per-item sample counts -> the audio marked per item (vits_op_watermark on the host buffer); wm = {}:
-        unchanged.  What run() / run_batch() do behind resample() and in front of normalize(): the mark goes in at the rate returned"""
-        if not wm or audio.shape[-1] == 0:
+        """audio float32 [B, S] with per-item sample counts -> the audio marked per item (vits_op_watermark on the host buffer); wm: a
+        capi.watermark_spec() (key, depth), None: unchanged.  What tail_chain() does behind resample() and in front of normalize(): the
+        mark goes in at the rate returned"""
+        if wm is None or audio.shape[-1] == 0:
             return audio
-        return self._lib.op_watermark(audio, lengths, wm["watermark"], wm.get("watermark_depth_db", 0.0), device=self._vocoder.device)
+        return self._lib.op_watermark(audio, lengths, *wm, device=self._vocoder.device)
 
     def normalize(self, audio, lengths, sample_rate, spec, limit=None):
         """audio float32 [B, S] at `sample_rate` Hz (None / 0 = the vocoder's own) with per-item sample counts -> the audio normalised
         per item by `spec` (vits_op_loudness_normalize on the host buffer) and / or limited by `limit` (vits_op_loudness_limit,
-        vits_op_limit); both None: unchanged.  What run() / run_batch() do behind resample(): the order is decode, clamp, denoise,
-        resample, normalise + limit"""
+        vits_op_limit); both None: unchanged.  What tail_chain() does behind resample(): the order is decode, clamp, denoise,
+        resample, mark, normalise + limit"""
         if (spec is None and limit is None) or audio.shape[-1] == 0:
             return audio
         rate = int(sample_rate or 0) or self._vocoder.hp.sampling_rate
@@ -157,28 +141,32 @@ class SttsSession:
             outs = {"wav": audio[None, :], "wav_lengths": np.array([audio.shape[0]], np.int64)}
             return [outs[n] for n in (output_names or ["wav", "wav_lengths"])] + ([info["token_ends"]] if "token_ends" in info else [])
         feed, ids, scales, sid, bert, pde, seed = self._parse(output_names, input_feed)
-        loud = self._loudness(feed)
-        lim = self._limit(feed)  # ("vits.limit": the peak limiter with the loudness gain or alone, last in the chain like the gain)
-        pk = self._pitch(feed)  # ("vits.pitch": shifted inside the library, behind the denoiser and before any resampling)
-        wm = self._wm(feed)  # ("vits.watermark_key": marked behind the resampler, in front of the normalisation)
-        if feed.get("vits.marks"):
-            audio, _, ends = self._model.synthesize(ids, scales, sid, bert, pde, noise=feed.get("vits.noise"), seed=seed,
-                                                    n_timesteps=int(feed.get("vits.n_timesteps", 0)), want_mel=False, marks=True,
-                                                    sample_rate=self._rate(feed.get("vits.sample_rate")), loudness=loud, limit=lim, **pk, **wm,
-                                                    **self._denoiser(feed))
-            outs = {"wav": audio[None, :], "wav_lengths": np.array([audio.shape[0]], np.int64)}
-            return [outs[n] for n in (output_names or ["wav", "wav_lengths"])] + [ends[None, :]]
-        rate = self._rate(feed.get("vits.sample_rate"))
-        audio, _ = self._model.synthesize(ids, scales, sid, bert, pde, noise=feed.get("vits.noise"), seed=seed,
-                                          n_timesteps=int(feed.get("vits.n_timesteps", 0)), want_mel=False,
-                                          loudness=None if rate else loud, limit=None if rate else lim, **pk, **({} if rate else wm),
-                                          **self._denoiser(feed))
-        if rate:  # (the library marks and normalises last, and this resampling happens behind it: both follow it here)
-            audio = self.resample(audio[None, :], [audio.shape[0]], rate)[0][0]
-            audio = self.mark(audio[None, :], [audio.shape[0]], wm)[0]
-            audio = self.normalize(audio[None, :], [audio.shape[0]], rate, loud, lim)[0]
-        outs = {"wav": audio[None, :], "wav_lengths": np.array([audio.shape[0]], np.int64)}
-        return [outs[n] for n in (output_names or ["wav", "wav_lengths"])]
+        n_steps = int(feed.get("vits.n_timesteps", 0))
+        marks = bool(feed.get("vits.marks"))
+
+        def call(**kw):  # (the single-utterance call in the batch door's form)
+            res = self._model.synthesize(ids, scales, sid, bert, pde, noise=feed.get("vits.noise"), seed=seed, n_timesteps=n_steps, want_mel=False,
+                                         **kw, **self._contour(feed), **self._denoiser(feed))
+            return (res[0][None, :], np.array([res[0].shape[0]], np.int64)) + ((res[2][None, :],) if marks else ())
+
+        res = self.tail_chain(call, Tail.from_feed(self._lib, feed), feed.get("vits.sample_rate"), marks)
+        outs = {"wav": res[0], "wav_lengths": np.array([res[0].shape[1]], np.int64)}
+        return [outs[n] for n in (output_names or ["wav", "wav_lengths"])] + list(res[2:])
+
+    def tail_chain(self, call, tail, sample_rate, marks):
+        """One synthesize call and the tail behind it -> what the call returns, (audio float32 [B, S], lengths int64 [B]) and with marks
+        token_ends, at `sample_rate`.  call(**keywords): the model's batch call, taking the tail's keywords (Tail.kw()) and, for marks,
+        marks=True with the rate (the marks entry points resample inside the library, tail and all).  Without marks the library has
+        no rate: the call keeps the stages in front of the resampler (pitch, intonation range), and the resampler, the mark and the
+        normalisation / limiter follow it here on the host buffer, in the library's order."""
+        rate = self._rate(sample_rate)
+        if marks:
+            return call(marks=True, sample_rate=rate, **tail.kw())
+        if not rate:
+            return call(**tail.kw())
+        audio, ol = call(**replace(tail, loudness=None, limit=None, watermark=None).kw())
+        audio, ol = self.resample(audio, ol, rate)
+        return self.normalize(self.mark(audio, ol, tail.watermark), ol, rate, tail.loudness, tail.limit), ol
 
     def run_stream(self, output_names, input_feed, chunk_frames=64, sample_rate=None, on_marks=None):
         """on_marks: called once with token_ends int64 [T] in the stream's output samples, before the first chunk.
@@ -191,21 +179,8 @@ class SttsSession:
         feed, ids, scales, sid, bert, pde, seed = self._parse(output_names, input_feed)
         if "vits.noise" in feed:
             raise NotImplementedError("run_stream draws the CFM noise on the device (vits.seed)")
-        if self._loudness(feed) is not None:
-            raise ValueError("a stream cannot be loudness-normalised: an integrated-loudness or peak target needs the whole utterance before "
-                             "the first chunk (run() takes the loudness feeds)")
-        if self._limit(feed) is not None:
-            raise ValueError("a stream cannot be limited: the limiter's look-ahead and its loudness passes need the whole utterance before the "
-                             "first chunk (run() takes \"vits.limit\")")
-        if range_from_feed(self._lib, feed) is not None:
-            raise ValueError("a stream cannot take an intonation range: the median of the F0 track needs the whole utterance before the "
-                             "first chunk (run() takes \"vits.pitch_range\")")
-        if self._wm(feed):
-            raise ValueError("a stream cannot be watermarked (STTS_FLAG_WATERMARK): the mark is a stage of the output tail, and a stream has "
-                             "none (run() takes \"vits.watermark_key\")")
-        if self._pitch(feed):
-            raise ValueError("a stream cannot be pitch-shifted: the phase recursion needs the frames before a chunk (run() takes "
-                             "\"vits.pitch\")")
+        tail = Tail.from_feed(self._lib, feed)
+        (replace(tail, pitch=0.0) if self._contour(feed) else tail).refuse_stream("STTS", "run() takes")  # (a contour: the pitch stage's refusal)
         rate = self._rate(sample_rate if sample_rate is not None else feed.get("vits.sample_rate"))
         dn = self._denoiser(feed)
         if rate and dn:
@@ -242,28 +217,17 @@ class SttsSession:
             if k not in feed:
                 raise ValueError(f"Required input {k} is missing")
         dn = self._denoiser(feed)
-        loud = self._loudness(feed)  # (per-item gains, last in the chain like run())
-        lim = self._limit(feed)
-        pk = self._pitch(feed)
-        wm = self._wm(feed)
-        rate = self._rate(feed.get("vits.sample_rate"))
+        tail = Tail.from_feed(self._lib, feed)  # (per-item gains, last in the chain like run())
         ids = np.asarray(feed["input"])
         if ids.ndim != 3 or ids.shape[1] != 5:
             raise ValueError("input must be int64 [B, 5, T]")
         sid = np.asarray(feed.get("sid", np.zeros(ids.shape[0])), np.int64).reshape(-1)
-        if feed.get("vits.marks"):
-            return self._model.synthesize_batch(ids, feed["input_lengths"], np.asarray(feed["scales"], np.float32).reshape(-1), sid,
-                                                feed.get("bert"), feed.get("phone_duration_extra"), seed=int(feed.get("vits.seed", 0)),
-                                                n_timesteps=int(feed.get("vits.n_timesteps", 0)), item_seeds=feed.get("vits.item_seeds"),
-                                                marks=True, sample_rate=rate, loudness=loud, limit=lim, **pk, **wm, **dn)
-        audio, ol = self._model.synthesize_batch(ids, feed["input_lengths"], np.asarray(feed["scales"], np.float32).reshape(-1), sid,
-                                                 feed.get("bert"), feed.get("phone_duration_extra"), seed=int(feed.get("vits.seed", 0)),
-                                                 n_timesteps=int(feed.get("vits.n_timesteps", 0)), item_seeds=feed.get("vits.item_seeds"),
-                                                 loudness=None if rate else loud, limit=None if rate else lim, **pk, **({} if rate else wm), **dn)
-        if not rate:
-            return audio, ol
-        audio, ol = self.resample(audio, ol, rate)
-        return self.normalize(self.mark(audio, ol, wm), ol, rate, loud, lim), ol
+        return self.tail_chain(
+            lambda **kw: self._model.synthesize_batch(ids, feed["input_lengths"], np.asarray(feed["scales"], np.float32).reshape(-1), sid,
+                                                      feed.get("bert"), feed.get("phone_duration_extra"), seed=int(feed.get("vits.seed", 0)),
+                                                      n_timesteps=int(feed.get("vits.n_timesteps", 0)), item_seeds=feed.get("vits.item_seeds"),
+                                                      **kw, **self._contour(feed), **dn),
+            tail, feed.get("vits.sample_rate"), bool(feed.get("vits.marks")))
 
     def run_document(self, input_feed, scale=1.0, pcm16=False):
         """A document (include/vits_document.h): run_batch's feed with at least one of the document feeds "vits.doc_gap_frames" int [B],
@@ -293,15 +257,12 @@ class SttsSession:
         if seed is None and "vits.item_seeds" not in feed:
             with self._seed_lock:
                 seed = next(self._seed)
-        pk = self._pitch(feed)
-        for k in ("token_pitch", "token_gain_db"):  # ([B, T] here, not the single utterance's [T])
-            if k in pk:
-                pk[k] = np.asarray(feed["vits." + k], np.float32).reshape(ids.shape[0], -1)
+        con = {k: a.reshape(ids.shape[0], -1) for k, a in self._contour(feed).items()}  # ([B, T] here, not the single utterance's [T])
         audio, info = self._model.synthesize_document(
             ids, feed["input_lengths"], np.asarray(feed["scales"], np.float32).reshape(-1), sid, feed.get("bert"), feed.get("phone_duration_extra"),
             seed=int(seed or 0), n_timesteps=int(feed.get("vits.n_timesteps", 0)), item_seeds=feed.get("vits.item_seeds"),
-            marks=bool(feed.get("vits.marks")), sample_rate=self._rate(feed.get("vits.sample_rate")), loudness=self._loudness(feed),
-            limit=self._limit(feed), **pk, **self._wm(feed), **self._denoiser(feed), **doc)
+            marks=bool(feed.get("vits.marks")), sample_rate=self._rate(feed.get("vits.sample_rate")), **Tail.from_feed(self._lib, feed).kw(),
+            **con, **self._denoiser(feed), **doc)
         if pcm16:
             audio = np.clip((audio * scale) * 32767.0, -32767.0, 32767.0).astype("int16")
         return audio, info
