@@ -31,6 +31,7 @@
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
+typedef float f32x4u __attribute__((ext_vector_type(4), aligned(4)));  // an unaligned dwordx4 load (slab staging)
 
 #define CONV_CI_T 16        // input channels per LDS chunk (8 MFMA k-steps per tap)
 #define CONV_MAX_HALO 64    // (K-1)*dil <= 64 (largest on the path: (11-1)*5 = 50)
@@ -141,6 +142,9 @@ struct ConvParams {
   // output is either column-local or masks its input at len[b], so tiles that start at or beyond len[b]
   // are not computed at all (their memory keeps whatever it held; see DESIGN.md "ragged batches").
   int skip_len;
+  // K-split kernel, 16 waves: the contraction is split by input-channel chunk with the operand window staged once per chunk
+  // (ks_chunk_body) instead of by tap.  Set by the executor (launch_ks, engine_launch.hip.h), never by a stage or the planner.
+  int ks_chunk;
   // Compact tile map of a ragged launch: tile_start[b] = number of column tiles of items < b (B+1 entries,
   // built on the device by ragged_tiles_kernel for this launch's tile width).  Working tiles get the lowest
   // block ids so they are dispatched first and spread over all CUs; ids >= tile_start[B] * ... exit at once.
@@ -802,6 +806,162 @@ __device__ __forceinline__ float ks_ld(const float* base, unsigned byte_off) {
 }
 struct ks_true { static constexpr bool value = true; };
 struct ks_false { static constexpr bool value = false; };
+
+// ---------------------------------------------------------------------------------------------
+// Chunk-owned contraction of the 16-wave K-split kernel (P.ks_chunk; who gets it: ks_chunk_takes, engine_launch.hip.h).
+// The tap split above gives a wave one tap in 16 of the tap stream: every tap re-fetches its shifted operand window (three times
+// over for the MRF mean) and a wave's weight fragments arrive as a chain of cold misses, one tap ahead of their use.  Here the
+// contraction is split by UNIT -- a 16-channel chunk (UP = 8 MFMA k-steps per tap), or an 8-channel half chunk (UP = 4) where the
+// conv has fewer chunks than waves or sums three inputs -- unit u going to wave u % 16.  A wave stages its unit's window (32 + halo columns) ONCE into
+// a wave-private slab, the way conv_wp_body does (unaligned dwordx4 loads from clamped starts, validity by select); input sum and
+// scale, leaky-relu, the reflection column, the length limits, the channel flip and the x_split second input are all applied there,
+// once per element.  Taps then read B fragments from the slab at shifted columns, one tap ahead.
+// KT = compile-time tap count (4: polyphase upsamplers, 7: conv_pre / conv_post): the weight ring holds the fragments of a WHOLE
+// unit, slot = tap, every register named statically (conv_small.hip.h on what a rolled ring costs); a slot is re-requested for the
+// next unit right after its last MFMA, so all of a unit's weights are in flight together.  KT = 0: run-time tap count, rolled loop,
+// two-slot ring.
+// The slab is this wave's 4 KB of the reduction buffer (16 rows of KS_SLAB_PITCH floats): no LDS beyond what the kernel has, and no
+// workgroup barrier before the reduction, which finds each wave's partial tile where its slab was.
+// ---------------------------------------------------------------------------------------------
+#define KS_SLAB_PITCH 64  // floats; 32 + halo <= 64 is part of the launch predicate (the two 32-lane halves of a ds_read_b32 never conflict)
+template <int NIN, int KT, int UP>
+__device__ __forceinline__ void ks_chunk_body(const ConvParams& P, const ConvGroup& G, float* lds, int b, int m0, int n0, int tap_base, int t_lim,
+                                              int wave, int lane, f32x16& acc) {
+  constexpr int NW = 16, ROWS = 2 * UP, NJ = ROWS / 4, NA = UP / 4, NV = NIN > 2 ? 3 : 1, D = KT ? KT : 2;
+  const int h = lane >> 5, l31 = lane & 31;
+  const int K = KT ? KT : G.K, dil = G.dil;
+  const int nunits = P.Cin / ROWS;
+  if (wave >= nunits) return;  // (wave-uniform) nothing to contract: the zero tile goes into the reduction
+  const int my_units = (nunits - wave + NW - 1) / NW;
+  const int last_u = wave + NW * (my_units - 1);
+  // ---- weight fragments: step group of (unit, tap, vector i) -- a chunk owns 2 K groups, tap-major; a half unit takes one of each pair
+  int mb = m0 >> 5;
+  if (mb >= (P.M >> 5)) mb = 0;
+  const f32x4* wp = reinterpret_cast<const f32x4*>(G.w) + (size_t)mb * G.n_sg * 64 + lane;
+  auto load_a = [&](f32x4 (&d)[NA], int i, int ui, int tap) {  // a dead prefetch (beyond the last unit) re-requests the last unit's
+    const int u0 = wave + NW * ui;
+    const int u = u0 <= last_u ? u0 : last_u;
+    const size_t sg = UP == 8 ? 2 * ((size_t)u * K + tap) + i : 2 * ((size_t)(u >> 1) * K + tap) + (u & 1);
+    d[i] = wp[sg * 64];
+  };
+
+  // ---- slab geometry: one load instruction = vector v16 of rows 4 j + r4; NJ instructions per input stage the unit
+  const int row_len = 32 + (K - 1) * dil;
+  const int nvec = (row_len + 3) >> 2;  // <= 16
+  const int t_base = n0 - G.pad_l + tap_base;
+  const int r4 = lane >> 4, v16 = lane & 15;
+  const int tv = t_base + 4 * v16;
+  const int tc0 = tv < 0 ? 0 : tv;
+  const int tc = tc0 > P.Tin - 4 ? P.Tin - 4 : tc0;  // clamped (always valid) vector start, Tin >= 4; exact for interior tiles
+  const long long rs = (long long)P.x_ch_sign * P.Tin_stride;  // one input channel, in elements (may be < 0)
+  const long long ars = rs < 0 ? -rs : rs;
+  // lane part as a non-negative byte offset (saddr + 32-bit voffset form): rows run downwards from the biased base when rs < 0
+  const unsigned loff = ((unsigned)((rs < 0 ? 3 - r4 : r4) * ars) + (unsigned)tc) * 4u;
+  const long long ubase = (long long)b * P.x_bstride + (long long)P.x_ch_off * P.Tin_stride + (rs < 0 ? 3 * rs : 0);
+  const float* xu = G.x + ubase;
+  const float* xu2 = G.x2 ? G.x2 + ubase : xu;
+  const float* xu3 = G.x3 ? G.x3 + ubase : xu2;  // NIN == 3: x3 may be absent (two ResBlock chains)
+  const float s3 = (NIN > 2 && G.x3) ? 1.f : 0.f;
+  const int split_unit = NIN == 2 ? P.x_split / ROWS : 0x7fffffff;  // NIN == 2: channel-concatenated second input
+  const float in_scale = P.in_scale, slope = P.in_slope;
+  const int refl_t = P.reflect ? ((P.Tin > 1) ? 1 : 0) : -1;
+  float* sl = lds + wave * (16 * KS_SLAB_PITCH);
+  float* sw = sl + r4 * KS_SLAB_PITCH + 4 * v16;
+  f32x4 v[NV][NJ];
+  auto load_slab = [&](int ui) {
+    const int u = wave + NW * ui;
+    const bool second = NIN == 2 && u >= split_unit;  // wave-uniform
+    const long long co = (long long)(second ? u - split_unit : u) * ROWS * rs;
+    const float* src[3] = {(second ? xu2 : xu) + co, xu2 + co, xu3 + co};
+#pragma unroll
+    for (int n = 0; n < NV; ++n)
+#pragma unroll
+      for (int j = 0; j < NJ; ++j) v[n][j] = *reinterpret_cast<const f32x4u*>(reinterpret_cast<const char*>(src[n] + 4 * j * rs) + loff);
+  };
+  load_slab(0);  // requested ahead of the weights: the wait in front of the first stage() then leaves the weight ring in flight
+  __builtin_amdgcn_sched_barrier(0);  // (pins that order)
+  f32x4 a[D][NA];
+#pragma unroll
+  for (int t = 0; t < D; ++t)
+#pragma unroll
+    for (int i = 0; i < NA; ++i) load_a(a[t], i, 0, t < K ? t : K - 1);
+  const bool interior = t_base >= 0 && t_base + 4 * nvec <= t_lim;  // block-uniform: no clamp, no limit, no reflection inside the window
+  // sum and scale (the MRF mean only, as the tap split), leaky-relu as max(x, slope x) (the identity at slope 1), then the slab.  Edge
+  // tiles: every element they need lies inside the clamped vector, at index (wanted column - loaded start) in 0..3
+  auto stage = [&]() {
+    if (v16 >= nvec) return;
+#pragma unroll
+    for (int j = 0; j < NJ; ++j) {
+      f32x4 x = v[0][j], o;
+      if (NIN > 2) x = (x + v[1][j] + s3 * v[2][j]) * in_scale;
+      if (interior) {
+#pragma unroll
+        for (int q = 0; q < 4; ++q) o[q] = fmaxf(x[q], x[q] * slope);
+      } else {
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+          const int t = tv + q, te = (t == -1 && refl_t >= 0) ? refl_t : t, idx = te - tc;
+          const float e = idx <= 0 ? x[0] : (idx == 1 ? x[1] : (idx == 2 ? x[2] : x[3]));
+          o[q] = (te >= 0 && te < t_lim) ? fmaxf(e, e * slope) : 0.f;  // select: stale padding may hold NaN
+        }
+      }
+      *reinterpret_cast<f32x4*>(sw + 4 * j * KS_SLAB_PITCH) = o;
+    }
+  };
+  // ---- UP K MFMAs on the slab: B fragment of (tap, channel pair p) = rows 2p + h at columns l31 + tap * dil, read one tap ahead
+  const float* bl = sl + h * KS_SLAB_PITCH + l31;
+  auto read_b = [&](float (&d)[UP], int tap) {
+#pragma unroll
+    for (int p = 0; p < UP; ++p) d[p] = bl[2 * p * KS_SLAB_PITCH + tap * dil];
+  };
+  auto mfma4 = [&](const f32x4& w, const float (&d)[UP], int p0) {
+#pragma unroll
+    for (int p = 0; p < 4; ++p) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(w[p], d[p0 + p], acc, 0, 0, 0);
+  };
+#pragma unroll 1
+  for (int ui = 0; ui < my_units; ++ui) {
+    stage();
+    if (ui == 0) CONV_DBG(6);  // (timing build: the first slab is staged)
+    if (ui + 1 < my_units) load_slab(ui + 1);
+    float bb[2][UP];
+    read_b(bb[0], 0);
+    if (KT) {
+      // program order pinned per tap (as conv_wp_body): [B of tap + 1] | 4 MFMAs, the slot's next vector, 4 MFMAs, its second |
+#pragma unroll
+      for (int tap = 0; tap < (KT ? KT : 1); ++tap) {
+        if (tap + 1 < KT) read_b(bb[(tap + 1) & 1], tap + 1);
+        __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+        for (int i = 0; i < NA; ++i) {
+          mfma4(a[tap][i], bb[tap & 1], 4 * i);
+          load_a(a[tap], i, ui + 1, tap);
+        }
+        __builtin_amdgcn_sched_barrier(0);
+      }
+    } else {
+#pragma unroll 1
+      for (int tap = 0; tap < K; tap += 2) {  // slot = tap & 1; an odd K leaves the next unit's first tap in slot 1: swapped below
+        read_b(bb[1], tap + 1 < K ? tap + 1 : tap);
+#pragma unroll
+        for (int i = 0; i < NA; ++i) mfma4(a[0][i], bb[0], 4 * i);
+#pragma unroll
+        for (int i = 0; i < NA; ++i) load_a(a[0], i, tap + 2 < K ? ui : ui + 1, tap + 2 < K ? tap + 2 : tap + 2 - K);
+        if (tap + 1 < K) {
+          read_b(bb[0], tap + 2 < K ? tap + 2 : tap + 1);
+#pragma unroll
+          for (int i = 0; i < NA; ++i) mfma4(a[1][i], bb[1], 4 * i);
+#pragma unroll
+          for (int i = 0; i < NA; ++i) load_a(a[1], i, tap + 3 < K ? ui : ui + 1, tap + 3 < K ? tap + 3 : tap + 3 - K);
+        }
+      }
+      if (K & 1) {
+#pragma unroll
+        for (int i = 0; i < NA; ++i) { const f32x4 t = a[0][i]; a[0][i] = a[1][i]; a[1][i] = t; }
+      }
+    }
+  }
+}
+
 // NW = waves per workgroup (4, 8 or 16) that split the contraction at TAP granularity (tap q = chunk*K + kk belongs
 // to wave q % NW).  More waves = shorter serial MFMA chains per wave and 2..4 waves per SIMD to hide the issue latency
 // of the fragment loads; the register budget per wave shrinks accordingly (KS_U taps per pipeline stage).
@@ -857,6 +1017,33 @@ __global__ void __launch_bounds__(NW * 64) conv_mfma_ks_kernel(const ConvParams 
 #pragma unroll
       for (int e = 0; e < 16; ++e) acc[mi][ni][e] = 0.f;
 
+  bool chunked = false;
+  if constexpr (NW == 16 && MI == 1 && NI == 1 && EPI == EPI_STORE) {
+    if (P.ks_chunk) {  // block-uniform
+      chunked = true;
+      // (an accumulator of its own, stored from here: merged with the tap split's, the tap loop of the three-input kernel spills)
+      f32x16 part;
+#pragma unroll
+      for (int e = 0; e < 16; ++e) part[e] = 0.f;
+      // units of a chunk; of half a chunk where there are fewer chunks than waves, and for the three-input mean, whose staging
+      // registers (12 vectors per chunk) would not fit beside a chunk's weight ring in the 128 registers of a 16-wave workgroup
+      bool whole = false;
+      if constexpr (NIN < 3) whole = nchunks >= NW;
+      if (whole) {
+        if constexpr (NIN < 3) {
+          if (K == 4) ks_chunk_body<NIN, 4, 8>(P, G, lds, b, m0, n0, tap_base, t_lim, wave, lane, part);
+          else if (K == 7) ks_chunk_body<NIN, 7, 8>(P, G, lds, b, m0, n0, tap_base, t_lim, wave, lane, part);
+          else ks_chunk_body<NIN, 0, 8>(P, G, lds, b, m0, n0, tap_base, t_lim, wave, lane, part);
+        }
+      } else {
+        if (K == 4) ks_chunk_body<NIN, 4, 4>(P, G, lds, b, m0, n0, tap_base, t_lim, wave, lane, part);
+        else if (K == 7) ks_chunk_body<NIN, 7, 4>(P, G, lds, b, m0, n0, tap_base, t_lim, wave, lane, part);
+        else ks_chunk_body<NIN, 0, 4>(P, G, lds, b, m0, n0, tap_base, t_lim, wave, lane, part);
+      }
+#pragma unroll
+      for (int e = 0; e < 16; ++e) lds[(wave * 16 + e) * 64 + lane] = part[e];  // where the reduction below expects this wave's tile
+    }
+  }
   const int n_mblocks = P.M >> 5;
   const f32x4* wp[MI];  // uniform per wave; + lane
 #pragma unroll
@@ -962,7 +1149,7 @@ __global__ void __launch_bounds__(NW * 64) conv_mfma_ks_kernel(const ConvParams 
       if (tp + KS_U < my_taps) pipe_step(ks_true{}, act, t1, t0);
     }
   };
-  if (my_taps > 0) {
+  if (!chunked && my_taps > 0) {
     if (in_slope == 1.f) run_pipe(ks_false{});
     else run_pipe(ks_true{});
   }
@@ -970,12 +1157,14 @@ __global__ void __launch_bounds__(NW * 64) conv_mfma_ks_kernel(const ConvParams 
 
   // ---- cross-wave reduction through LDS
   float* red = lds;  // [wave][mi][ni][e][64]
+  if (!chunked) {
 #pragma unroll
-  for (int mi = 0; mi < MI; ++mi)
+    for (int mi = 0; mi < MI; ++mi)
 #pragma unroll
-    for (int ni = 0; ni < NI; ++ni)
+      for (int ni = 0; ni < NI; ++ni)
 #pragma unroll
-      for (int e = 0; e < 16; ++e) red[(((wave * MI + mi) * NI + ni) * 16 + e) * 64 + lane] = acc[mi][ni][e];
+        for (int e = 0; e < 16; ++e) red[(((wave * MI + mi) * NI + ni) * 16 + e) * 64 + lane] = acc[mi][ni][e];
+  }
   __syncthreads();
   CONV_DBG(3);
   const int lenb = (P.out_mask || EPI == EPI_RESSKIP || EPI == EPI_COUPLE) ? P.len[b] : 0x7fffffff;

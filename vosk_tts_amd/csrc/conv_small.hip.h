@@ -601,7 +601,6 @@ __global__ void __launch_bounds__(NW * 64) conv16_kernel(const ConvParams P) {
 // their slab ~5 k cycles after the first ones (outstanding-miss limited fetch from the Infinity Cache).
 // ---------------------------------------------------------------------------------------------
 #define WP_PITCH 96  // slab row pitch in floats: == 32 mod 64 (rows 2p / 2p + 1 of a B fragment land in different bank halves)
-typedef float f32x4u __attribute__((ext_vector_type(4), aligned(4)));
 template <int V> struct wp_int { static constexpr int value = V; };
 // KT = compile-time tap count (3 / 7 / 11: the decoder's ResBlock kernels, fully unrolled so that every register of the weight
 // and B-fragment rings is named statically -- a rolled loop makes hipcc rotate the rings with v_mov behind s_waitcnt vmcnt(0)),

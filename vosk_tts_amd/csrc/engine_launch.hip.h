@@ -117,10 +117,22 @@ static void launch_cfg(vits_session* s, ConvParams& P, const ConvPlan& pl, int h
   const size_t lds = (size_t)2 * CONV_CI_T * P.row_len * sizeof(float);
   hipLaunchKernelGGL((conv_mfma_kernel<WM, WN, MI, NI, EPI>), dim3(nblk), dim3(WM * WN * 64), lds, s->stream, P);
 }
+// Which K-split launches contract by input-channel chunk, the operand window staged once per chunk (ks_chunk_body, conv_mfma.hip.h), instead
+// of by tap: one group on the 16-wave 32 x 32 STORE tile, at least 4 taps to share a window of at most KS_SLAB_PITCH columns, rows long
+// enough for the vector loads, and a grid of about one workgroup per CU -- the single utterance's conv_pre, upsamplers and conv_post
+// (measured: profiles/ks_chunk_bench.txt).  Not a planner leaf: the kernel instantiation, its name and the launch log do not change.
+static bool ks_chunk_takes(const vits_session* s, const ConvParams& P, const ConvPlan& pl, long nblk) {
+  const ConvGroup& G = P.g[0];
+  if (!conv_select().env_ks_chunk || pl.NW != 16 || pl.MI != 1 || pl.NI != 1 || pl.epi != EPI_STORE || P.n_groups != 1) return false;
+  if (G.K < 4 || G.dil < 1 || 32 + (G.K - 1) * G.dil > KS_SLAB_PITCH || P.Tin < 4) return false;
+  const long cus = s->m->n_cu > 0 ? s->m->n_cu : 256;  // (vits_op_conv1d's scratch model carries no device description)
+  return 4 * nblk <= 5 * cus;
+}
 template <int MI, int NI, int EPI, int NIN>
 static void launch_ks(vits_session* s, ConvParams& P, const ConvPlan& pl) {
   const dim3 grid(plan_grid(s, P, pl, true));
   P.row_len = 0;  // no staging window: B fragments come straight from global memory
+  P.ks_chunk = ks_chunk_takes(s, P, pl, (long)grid.x) ? 1 : 0;
   const size_t lds = (size_t)pl.NW * MI * NI * 16 * 64 * sizeof(float);  // cross-wave reduction only
   static std::atomic<unsigned long long> done16{0};  // (only 16 waves of the 64 x 32 tile go beyond 64 KB)
   if (pl.NW == 16) launch_big_lds(conv_mfma_ks_kernel<MI, NI, EPI, NIN, 16>, done16, grid, 16 * 64, lds, (int)lds, s->stream, P);
