@@ -42,7 +42,7 @@ def _torch_fp32(x, bias, strength, n):
     return torch.istft(spec, n_fft=n, hop_length=n // 4, win_length=n, window=w)[0].numpy()
 
 
-@pytest.mark.parametrize("n", [64, 256, 1024])
+@pytest.mark.parametrize("n", [64, 128, 256, 512, 1024])  # log2 (n/2) odd: the transform ends in the radix-2 pass; even (128, 512): radix-4 alone
 def test_op_against_float64(hip_lib, n):
     lengths, x, bias, strength = _op_case(n)
     hop = n // 4

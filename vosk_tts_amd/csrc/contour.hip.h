@@ -6,7 +6,7 @@
 // items of cases (b) and (c), which every vocoder kernel then leaves at once):
 //   contour_tracks_kernel   a thread per analysis row: Sigma_f by 2 R + 1 binary searches in cum, inc_f, gbar_f
 //   contour_steps_kernel    one wave per item, lane 0 walks the recurrence: F_s, a_0 .. a_{F_s}
-//   contour_analysis_kernel step 1 of the vocoder with the frame's transform in double (the reason stands at the kernel)
+//   contour_analysis_kernel step 1 of the vocoder with the frame's transform in double (stft.hip.h; the reason stands at the kernel)
 //   pitch_phase_kernel<true>, pitch_synth_kernel<true>, pitch_ola_kernel<true>
 //   contour_warp_kernel     a workgroup per CT_TILE consecutive outputs of one item: u window, step slice and filter table in LDS
 //   contour_gain_kernel     the items of cases (b) and (c): y = G x
@@ -106,61 +106,31 @@ __global__ __launch_bounds__(64) void contour_steps_kernel(const int* __restrict
 // every bin a few 1e-7 of the frame's level from the exact spectrum; in the phases that error is added twice a step by the recursion,
 // and a contour runs up to two steps per analysis frame with weights that are exact: measured through vits_op_contour_stretch, u sat
 // at 4.8 to 4.9 times the float32 restatement's distance from float64 with it (and the same with atan2 alone taken in double).  The
-// transform is pitch_formant_kernel's: the window as sinpi^2, a 512-point radix-2 transform of the packed frame in LDS, its unpacking.
-__global__ __launch_bounds__(64 * DN_FPB) void contour_analysis_kernel(const float* __restrict__ x, long long x_bstride, long long x_n,
+// transform is sf_frame_spectrum_f64 and sf_bin_f64 of stft.hip.h.
+__global__ __launch_bounds__(64 * SF_FPB) void contour_analysis_kernel(const float* __restrict__ x, long long x_bstride, long long x_n,
                                                                        const int* __restrict__ d_vlen, float* __restrict__ mag,
                                                                        unsigned* __restrict__ th, long long a_bstride) {
   __shared__ double2 s_tw[PT_M];  // exp(-2 pi i t / n), t < n/2
-  __shared__ double2 s_z[DN_FPB][PT_M];
+  __shared__ double2 s_z[SF_FPB][PT_M];
   const int wv = threadIdx.x >> 6, t = threadIdx.x & 63;
   const int b = blockIdx.y;
   const long long len = d_vlen[b];
   const long long Fa = pt_frames_a(len);
-  if (Fa == 0 || (long long)blockIdx.x * DN_FPB >= Fa + 2) return;  // uniform over the workgroup
-  const long long f = (long long)blockIdx.x * DN_FPB + wv;
+  if (Fa == 0 || (long long)blockIdx.x * SF_FPB >= Fa + 2) return;  // uniform over the workgroup
+  const long long f = (long long)blockIdx.x * SF_FPB + wv;
   const bool valid = f < Fa;
-  for (int i = threadIdx.x; i < PT_M; i += 64 * DN_FPB) {
-    double sn, cs;
-    sincospi((double)i * (2.0 / PT_N), &sn, &cs);
-    s_tw[i] = make_double2(cs, -sn);
-  }
-  // the windowed frame, two samples to a complex point, in bit-reversed order (a wave whose row is behind the last frame transforms zeros)
   double2* Z = s_z[wv];
-  const float* xb = x + (long long)b * x_bstride;
-  for (int m = t; m < PT_M; m += 64) {
-    double v0 = 0.0, v1 = 0.0;
-    if (valid) {
-      const long long p = f * PT_H + 2 * m;
-      const double w0 = sinpi((double)(2 * m) * (1.0 / PT_N)), w1 = sinpi((double)(2 * m + 1) * (1.0 / PT_N));
-      v0 = (double)dn_load(xb, p, PT_M, len, 0, x_n) * (w0 * w0);
-      v1 = (double)dn_load(xb, p + 1, PT_M, len, 0, x_n) * (w1 * w1);
-    }
-    Z[__brev((unsigned)m) >> (32 - PT_LOG2M)] = make_double2(v0, v1);
-  }
-  __syncthreads();
-  for (int h = 1; h < PT_M; h <<= 1) {  // groups of 2 h points, twiddle exp(-2 pi i pos / (2 h))
-    for (int j = t; j < PT_M / 2; j += 64) {
-      const int pos = j & (h - 1), i0 = ((j - pos) << 1) + pos, i1 = i0 + h;
-      const double2 w = s_tw[pos * (PT_M / h)], u = Z[i0], v = Z[i1];
-      const double tr = w.x * v.x - w.y * v.y, ti = w.x * v.y + w.y * v.x;
-      Z[i0] = make_double2(u.x + tr, u.y + ti);
-      Z[i1] = make_double2(u.x - tr, u.y - ti);
-    }
-    __syncthreads();
-  }
+  sf_frame_spectrum_f64(x + (long long)b * x_bstride, f * PT_H, len, x_n, valid, t, s_tw, Z);
   if (f >= Fa + 2) return;
   float* mo = mag + (long long)b * a_bstride + f * PT_NB;
   unsigned* to = th + (long long)b * a_bstride + f * PT_NB;
-  for (int k = t; k < PT_NB; k += 64) {  // X[k] = E[k] + exp(-2 pi i k / n) O[k] of the packed transform
+  for (int k = t; k < PT_NB; k += 64) {
     float m = 0.f;
     unsigned a = 0u;
     if (valid) {
-      const double2 zk = Z[k & (PT_M - 1)], zp = Z[(PT_M - k) & (PT_M - 1)];
-      const double2 w = k < PT_M ? s_tw[k] : make_double2(-1.0, 0.0);
-      const double er = 0.5 * (zk.x + zp.x), ei = 0.5 * (zk.y - zp.y), o_r = 0.5 * (zk.y + zp.y), o_i = -0.5 * (zk.x - zp.x);
-      const double xr = er + (w.x * o_r - w.y * o_i), xi = ei + (w.x * o_i + w.y * o_r);
-      m = (float)sqrt(xr * xr + xi * xi);
-      if (xr != 0.0 || xi != 0.0) a = (unsigned)(long long)rint(atan2(xi, xr) * 0.15915494309189533577 * 4294967296.0);  // the low 32 bits
+      const double2 X = sf_bin_f64(Z, s_tw, k);
+      m = (float)sqrt(X.x * X.x + X.y * X.y);
+      if (X.x != 0.0 || X.y != 0.0) a = (unsigned)(long long)rint(atan2(X.y, X.x) * 0.15915494309189533577 * 4294967296.0);  // the low 32 bits
     }
     mo[k] = m;
     to[k] = a;
@@ -176,14 +146,8 @@ __device__ __forceinline__ float ct_gain(const float* __restrict__ gb, long long
 
 template <typename OUT>
 __device__ __forceinline__ void ct_store(OUT* __restrict__ y, float v, float scale) {
-  if constexpr (sizeof(OUT) == sizeof(int16_t)) {  // pcm16_kernel's epilogue
-    float s = v * scale;
-    s = s * 32767.0f;
-    s = fminf(fmaxf(s, -32767.0f), 32767.0f);
-    *y = (OUT)(int)s;
-  } else {
-    *y = v;
-  }
+  if constexpr (sizeof(OUT) == sizeof(int16_t)) *y = pcm16_of(v, scale);
+  else *y = v;
 }
 
 // Outputs [0, n_count) of the items with d_vlen[b] > 0; u: [B][u_bstride]; y exactly 0 at and beyond len.
@@ -338,13 +302,8 @@ static int contour_tab_get(int device, const float** out) {
       const double r2 = std::max(1.0 - (yv / RS_Z) * (yv / RS_Z), 0.0);
       T[j] = (float)(RS_RHO * sinc * rs_bessel_i0(RS_BETA * sqrt(r2)) / i0b);
     }
-    HIP_TRY(hipSetDevice(device));
     float* d = nullptr;
-    if (hipMalloc((void**)&d, sizeof(float) * CT_TAB) != hipSuccess) return fail(VITS_ERR_NOMEM, "contour: table alloc failed");
-    if (hipMemcpy(d, T.data(), sizeof(float) * CT_TAB, hipMemcpyHostToDevice) != hipSuccess) {
-      hipFree(d);
-      return fail(VITS_ERR_DEVICE, "contour: table upload failed");
-    }
+    TRY(dev_table_upload(device, "contour", T.data(), sizeof(float) * CT_TAB, (void**)&d));
     it = g_ct_tabs.emplace(device, d).first;
   }
   *out = it->second;
@@ -362,7 +321,7 @@ static size_t contour_item_bytes(long long len, bool inton = false) {
 }
 
 // y[b][0 .. n_count) = the contoured item b, for B items on `stream`: x [B][x_bstride] float on the device, h_len their lengths on the
-// host; d_cum [B][cum_bstride], d_toklen [B] on the device.  y is float, or int16 (pcm: pcm16_kernel's conversion at pcm_scale).
+// host; d_cum [B][cum_bstride], d_toklen [B] on the device.  y is float, or int16 (pcm: pcm16_of at pcm_scale).
 // Allocates its scratch and waits for the stream before it frees it: not capturable.  y is not x.
 // u_out / steps_out (both or neither; device): the stretch door -- u goes to u_out[b * u_bstride + j], the step tables to
 // steps_out[b * s_bstride + ..] (zeroed by the caller), and nothing is warped.
@@ -374,8 +333,8 @@ static int contour_run(int device, hipStream_t stream, const float* x, long long
                        long long y_bstride, long long n_count, float* u_out, long long u_bstride, long long* steps_out, long long s_bstride,
                        const IntonReq* in = nullptr, int* cents_out = nullptr, long long c_bstride = 0) {
   if (B <= 0) return VITS_OK;
-  const DenoiseTab* D = nullptr;
-  TRY(denoise_get(device, PT_N, &D));
+  const StftTab* D = nullptr;
+  TRY(stft_tab_get(device, PT_N, &D));
   const float* d_T = nullptr;
   TRY(contour_tab_get(device, &d_T));
   const int* d_R = nullptr;
@@ -469,10 +428,10 @@ static int contour_run(int device, hipStream_t stream, const float* x, long long
       float* d_fr = reinterpret_cast<float*>(p); p += sizeof(float) * (size_t)c * f_bs;
       d_u = reinterpret_cast<float*>(p);
       hipLaunchKernelGGL(contour_steps_kernel, dim3(c), dim3(64), 0, stream, vg, d_inc, t_bs, d_steps, s_bs);
-      hipLaunchKernelGGL(contour_analysis_kernel, dim3((unsigned)((Fa + 2 + DN_FPB - 1) / DN_FPB), c), dim3(64 * DN_FPB), 0, stream, xg, x_bstride,
+      hipLaunchKernelGGL(contour_analysis_kernel, dim3((unsigned)((Fa + 2 + SF_FPB - 1) / SF_FPB), c), dim3(64 * SF_FPB), 0, stream, xg, x_bstride,
                          x_bstride, vg, d_mag, d_th, a_bs);
       hipLaunchKernelGGL(pitch_phase_kernel<true>, dim3(c), dim3(64 * PT_WAVES), 0, stream, d_mag, d_th, a_bs, vg, 1LL, 1, 1, d_steps, s_bs, d_phi, p_bs);
-      hipLaunchKernelGGL(pitch_synth_kernel<true>, dim3((unsigned)((cap + DN_FPB - 1) / DN_FPB), c), dim3(64 * DN_FPB), 0, stream, d_mag, a_bs, d_phi,
+      hipLaunchKernelGGL(pitch_synth_kernel<true>, dim3((unsigned)((cap + SF_FPB - 1) / SF_FPB), c), dim3(64 * SF_FPB), 0, stream, d_mag, a_bs, d_phi,
                          p_bs, vg, 1LL, 1, 1, d_steps, s_bs, D->d_win, D->d_tw, d_fr, f_bs);
       if (u_out)
         hipLaunchKernelGGL(pitch_ola_kernel<true>, dim3((unsigned)((u_bstride + 255) / 256), c), dim3(256), 0, stream, d_fr, f_bs, vg, 1LL, 1, 1, d_steps,

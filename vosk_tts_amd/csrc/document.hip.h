@@ -152,14 +152,8 @@ __global__ void __launch_bounds__(256) doc_layout_kernel(const int* __restrict__
 
 template <typename T>
 __device__ __forceinline__ T doc_out(float v, float scale) {
-  if constexpr (sizeof(T) == sizeof(int16_t)) {  // pcm16_kernel's arithmetic
-    v = v * scale;
-    v = v * 32767.0f;
-    v = fminf(fmaxf(v, -32767.0f), 32767.0f);
-    return (T)(int)v;
-  } else {
-    return v;
-  }
+  if constexpr (sizeof(T) == sizeof(int16_t)) return pcm16_of(v, scale);
+  else return v;
 }
 
 // The segment tables of one workgroup: LDS copies for documents of up to DOC_LDS_SEG segments, the device block itself beyond.

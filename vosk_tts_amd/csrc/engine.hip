@@ -133,6 +133,7 @@ static int persist_cfg() {
 #include "engine_stages.hip.h"
 #include "op_door.hip.h"
 #include "resample.hip.h"
+#include "stft.hip.h"
 #include "denoise.hip.h"
 #include "loudness.hip.h"
 #include "limit.hip.h"

@@ -391,7 +391,7 @@ static int synth_fast(vits_model* m, const int64_t* ids, const int64_t* lengths,
   HIP_TRY(hipSetDevice(m->device));
   TailReq q = req;  // (its table: uploaded on the first call at this rate, before any capture)
   if (q.rate) TRY(resample_get(m->device, hp.sampling_rate, q.rate, &q.T));
-  if (q.wm.on) TRY(wm_get(m->device, &q.wm.T));  // (include/vits_watermark.h: the denoiser's tables, as early)
+  if (q.wm.on) TRY(stft_tab_get(m->device, WM_N, &q.wm.T));  // (include/vits_watermark.h: the frame transform's tables, as early)
   const ResampleTab* T = q.T;
   const NormReq& lq = q.norm;
   const bool pcm = q.pcm;
@@ -581,7 +581,7 @@ static int synth_eager(vits_model* m, const int64_t* ids, const int64_t* lengths
   const vits_hparams& hp = m->hp;
   TailReq q = req;
   if (q.rate) TRY(resample_get(m->device, hp.sampling_rate, q.rate, &q.T));
-  if (q.wm.on) TRY(wm_get(m->device, &q.wm.T));  // (include/vits_watermark.h: the denoiser's tables, as early)
+  if (q.wm.on) TRY(stft_tab_get(m->device, WM_N, &q.wm.T));  // (include/vits_watermark.h: the frame transform's tables, as early)
   const ResampleTab* T = q.T;
   std::vector<float> res((size_t)B * 4);  // (the last stage's result rows: declared before the stage, whose end waits for the stream)
   HostStage hs(m);

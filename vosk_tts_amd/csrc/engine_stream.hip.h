@@ -31,7 +31,7 @@ struct vits_stream {
   long long rs_cap = 0;             // outputs one chunk can have: ceil(chunk * hop * L / M) + 1
   // the vocoder-bias denoiser (include/vits_denoise.h): every emitted chunk is denoised from its window's audio slot into d_dn on the
   // copy stream (two launches), then copied out.  The windows carry ceil(filter_length / hop) more halo frames.
-  const DenoiseTab* dn = nullptr;
+  const StftTab* dn = nullptr;
   const float* dn_bias = nullptr;
   float dn_strength = 0.f;
   float *d_dn = nullptr, *d_dn_scr = nullptr;
@@ -181,7 +181,7 @@ int vits_stream_open_latent(vits_model* m, const float* z, int32_t Ty, int32_t c
 // the latent opens' common body: a stream over the device copy of z, with the resampler's table (null: native rate) or the denoiser's
 // tables and bias (dn null: none) behind every chunk
 static int stream_open_latent(vits_model* m, const float* z, int32_t Ty, int32_t chunk_frames, uint32_t flags, const ResampleTab* rs,
-                              const DenoiseTab* dn, const float* dn_bias, float dn_strength, vits_stream** out, int64_t* total_samples) {
+                              const StftTab* dn, const float* dn_bias, float dn_strength, vits_stream** out, int64_t* total_samples) {
   vits_stream* st = new vits_stream();
   st->m = m;
   st->rs = rs;
@@ -210,7 +210,7 @@ int vits_stream_open_latent_denoise(vits_model* m, const float* z, int32_t Ty, i
                                     int32_t filter_length, vits_stream** out, int64_t* total_samples) {
   if (!m || !z || !out || Ty <= 0 || chunk_frames <= 0) return fail(VITS_ERR_ARG, "bad argument");
   if (Ty > (1 << 18)) return fail(VITS_ERR_ARG, "T_y unreasonably large");
-  const DenoiseTab* T = nullptr;
+  const StftTab* T = nullptr;
   const float* d_bias = nullptr;
   TRY(denoise_prepare(m, strength, filter_length, &T, &d_bias));
   return stream_open_latent(m, z, Ty, chunk_frames, flags, nullptr, T, d_bias, strength, out, total_samples);

@@ -68,7 +68,7 @@ __global__ __launch_bounds__(64) void f0_track_kernel(const float* __restrict__ 
     return;
   }
   const float* xb = x + (long long)b * x_bstride;
-  for (int i = lane; i < PT_N; i += 64) s_fr[i] = dn_load(xb, f * PT_H + i, PT_M, len, 0, x_n);
+  for (int i = lane; i < PT_N; i += 64) s_fr[i] = sf_load(xb, f * PT_H + i, PT_M, len, 0, x_n);
   __syncthreads();
   const int tmin = in_tau_min(rate), tmax = in_tau_max(rate);
   const int ni = (tmax + 1) / 64 + 1;  // blocks that hold a lag <= tmax + 1 (uniform)
@@ -324,13 +324,8 @@ static int inton_tab_get(int device, const int** out) {
   if (it == g_in_tabs.end()) {
     std::vector<int> T(IN_TABN);
     for (int j = 0; j < IN_TABN; ++j) T[j] = (int)lround(1000.0 * pow(2.0, (double)(j - IN_CENTS) / 1200.0));
-    HIP_TRY(hipSetDevice(device));
     int* d = nullptr;
-    if (hipMalloc((void**)&d, sizeof(int) * IN_TABN) != hipSuccess) return fail(VITS_ERR_NOMEM, "intonation: table alloc failed");
-    if (hipMemcpy(d, T.data(), sizeof(int) * IN_TABN, hipMemcpyHostToDevice) != hipSuccess) {
-      hipFree(d);
-      return fail(VITS_ERR_DEVICE, "intonation: table upload failed");
-    }
+    TRY(dev_table_upload(device, "intonation", T.data(), sizeof(int) * IN_TABN, (void**)&d));
     it = g_in_tabs.emplace(device, d).first;
   }
   *out = it->second;

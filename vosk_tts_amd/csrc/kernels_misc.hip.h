@@ -1016,17 +1016,22 @@ __global__ void ragged_len_kernel(const int* len_y, int* rag, int* tail, int B, 
 }
 
 // Synth.audio_float_to_int16 after `audio * scale` (vosk_tts/synth.py:16-23,128-130) on the device:
-// int16(clip(a * scale * 32767, -32767, 32767)), numpy's astype truncates toward zero like the C cast
+// int16(clip(a * scale * 32767, -32767, 32767)), numpy's astype truncates toward zero like the C cast.  Every int16 output of the
+// tail ends in these two (a * scale and * 32767 are two roundings).
+__device__ __forceinline__ int16_t pcm16_round(float s) {
+  s = s * 32767.0f;
+  s = fminf(fmaxf(s, -32767.0f), 32767.0f);
+  return (int16_t)(int)s;
+}
+__device__ __forceinline__ int16_t pcm16_of(float v, float scale) { return pcm16_round(v * scale); }
+
 __global__ void pcm16_kernel(const float* audio, long long a_bstride, int16_t* out, long long o_bstride, long long n, float scale,
                              const SynthDev* dv) {
   const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
   const int b = blockIdx.y;
   if (i >= n) return;
   if (dv) scale = dv->pcm_scale;
-  float v = audio[(long long)b * a_bstride + i] * scale;
-  v = v * 32767.0f;
-  v = fminf(fmaxf(v, -32767.0f), 32767.0f);
-  out[(long long)b * o_bstride + i] = (int16_t)(int)v;
+  out[(long long)b * o_bstride + i] = pcm16_of(audio[(long long)b * a_bstride + i], scale);
 }
 
 // ----------------------------------------------------------------------------- decoder tail

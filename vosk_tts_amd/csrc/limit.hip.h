@@ -18,7 +18,7 @@
 //   4. limit_carry_kernel   one wave per item: cin[b][0] = 0, cin[b][kt + 1] = max(cend[b][kt], a^TILE cin[b][kt])
 //   5. limit_apply_kernel   sample tile kn needs d over j in [kn TILE, kn TILE + TILE + W): 256 runs of 12 from cin[b][kn], each run again
 //                           from its true incoming value, an LDS prefix sum in double, s[n] = 1 - (D[n+W] - D[n-1]) / (W + 1), then
-//                           y = fp32(g s) x (or pcm16_kernel's epilogue) and the tile's min s
+//                           y = fp32(g s) x (or pcm16_of) and the tile's min s
 //   6. limit_final_kernel   (the entry points only) one wave per item: min s over its tiles and the gain into the call's result row
 // Cost written down: p is written once and read twice per pass with up to W (2 W in 5) samples of halo; the sliding maximum is log2(W + 1)
 // doubling levels over the staged span.  No atomics, no waiting between workgroups, fixed slots and fixed order.
@@ -327,14 +327,8 @@ __global__ __launch_bounds__(LM_THREADS) void limit_apply_kernel(const float* __
     }
     if (s_out && n < N) s_out[(long long)b * N + n] = s32;
     if (n < n_count) {
-      if constexpr (sizeof(OUT) == sizeof(int16_t)) {
-        float q = v * scale;
-        q = q * 32767.0f;
-        q = fminf(fmaxf(q, -32767.0f), 32767.0f);
-        y[(long long)b * y_bstride + n] = (OUT)(int)q;
-      } else {
-        y[(long long)b * y_bstride + n] = v;
-      }
+      if constexpr (sizeof(OUT) == sizeof(int16_t)) y[(long long)b * y_bstride + n] = pcm16_of(v, scale);
+      else y[(long long)b * y_bstride + n] = v;
     }
   }
   float* red = pa;  // (every read of pa / pb lies before lm_release's barriers)

@@ -16,7 +16,7 @@
 //                           state: y^2 summed per 100 ms hop into fixed slots part[b][k][hop - first hop of the tile]
 //   4. loud_final_kernel    one workgroup per item, in double: hop energies (the tiles of a hop added in ascending order), both gates,
 //                           L, the peak over tiles and the gain -> res[b] = {L, peak, gain}
-//   5. loud_apply_kernel    y = gain[b] * x, float or with pcm16_kernel's epilogue
+//   5. loud_apply_kernel    y = gain[b] * x, float or with pcm16_of
 // Cost written down: the x tile is read from memory three times (1, 3, 5) and the runs are computed three times (once in 1, twice in 3)
 // rather than storing 4 words of state per LD_S samples; 2 (one lane per item) is 64 + 20 k cycles for k tiles, 15 us for a
 // 2000-token utterance.  No atomics and no waiting between workgroups; every sum has a fixed order.
@@ -375,7 +375,7 @@ __global__ __launch_bounds__(LD_THREADS) void loud_final_kernel(const int* __res
   }
 }
 
-// y[b, j] = res[b].gain * x[b, j] for j < len, 0 beyond (x is not read there), 0 <= j < n_count.  OUT = int16_t: pcm16_kernel's epilogue.
+// y[b, j] = res[b].gain * x[b, j] for j < len, 0 beyond (x is not read there), 0 <= j < n_count.  OUT = int16_t: pcm16_of.
 template <typename OUT>
 __global__ __launch_bounds__(256) void loud_apply_kernel(const float* __restrict__ x, long long x_bstride, long long N,
                                                          const int* __restrict__ len_frames, long long len_mul, int L, int M,
@@ -386,14 +386,8 @@ __global__ __launch_bounds__(256) void loud_apply_kernel(const float* __restrict
   if (j >= n_count) return;
   const long long len = ld_len(len_frames, len_mul, L, M, N, b);
   const float v = j < len ? res[b * 4 + 2] * x[(long long)b * x_bstride + j] : 0.f;
-  if constexpr (sizeof(OUT) == sizeof(int16_t)) {
-    float s = v * scale;
-    s = s * 32767.0f;
-    s = fminf(fmaxf(s, -32767.0f), 32767.0f);
-    y[(long long)b * y_bstride + j] = (OUT)(int)s;
-  } else {
-    y[(long long)b * y_bstride + j] = v;
-  }
+  if constexpr (sizeof(OUT) == sizeof(int16_t)) y[(long long)b * y_bstride + j] = pcm16_of(v, scale);
+  else y[(long long)b * y_bstride + j] = v;
 }
 
 // ---- launches ----------------------------------------------------------------------------------------------------------------

@@ -20,6 +20,20 @@ struct DevBufs {
   void release(void* p) { bufs.erase(std::remove(bufs.begin(), bufs.end(), p), bufs.end()); }  // p outlives the call: the caller's now
 };
 
+// A table that lives as long as the process: src[0 .. bytes) to a fresh allocation on `device`, *d (null on failure).  hipMalloc and a
+// synchronous copy: call it outside stream capture.  `what` is the stage's name in the two messages.
+static int dev_table_upload(int device, const char* what, const void* src, size_t bytes, void** d) {
+  *d = nullptr;
+  HIP_TRY(hipSetDevice(device));
+  if (hipMalloc(d, bytes) != hipSuccess) { *d = nullptr; return fail(VITS_ERR_NOMEM, "%s: table alloc failed", what); }
+  if (hipMemcpy(*d, src, bytes, hipMemcpyHostToDevice) != hipSuccess) {
+    hipFree(*d);
+    *d = nullptr;
+    return fail(VITS_ERR_DEVICE, "%s: table upload failed", what);
+  }
+  return VITS_OK;
+}
+
 // One door call on the null stream.  The first failure is kept (fail() has its message, under the door's name) and every later step is
 // skipped; a door guards its launches with ok().  A failed allocation is VITS_ERR_NOMEM, any other HIP error VITS_ERR_DEVICE.
 struct OpDoor {

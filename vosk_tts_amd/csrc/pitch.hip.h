@@ -1,9 +1,9 @@
 // pitch.hip.h -- pitch-shifted output (include/vits_pitch.h): an identity-phase-locked vocoder that stretches the finished waveform by
-// P/Q, then the resampler (P -> Q).  Part of the ONE translation unit engine.hip (included there, after the denoiser, whose transform it
-// shares: dn_load, dn_fft, the DenoiseTab of n = 1024).
+// P/Q, then the resampler (P -> Q).  Part of the ONE translation unit engine.hip (included there, after stft.hip.h, whose frame
+// transform it runs at n = 1024: the device functions, the LDS layout and the StftTab).
 //
 // Launches per group of items (every kernel derives an item's F_a, F_s and N_u from its length: no per-item host tables):
-//   pitch_analysis_kernel  one wave per frame, DN_FPB frames per workgroup, as denoise_frames_kernel: |X| and the phase as a 32-bit
+//   pitch_analysis_kernel  one wave per frame, load, transform and unpack of stft.hip.h: |X| and the phase as a 32-bit
 //                          fixed-point turn, [B][F_a + 2][NB]; the two rows behind an item's last frame are written as zeros
 //   pitch_formant_kernel   (VITS_FLAG_PITCH_FORMANT only) one wave per analysis row: the cepstral envelope of the row and the gain that
 //                          pre-warps it, mag' = mag g, [B][F_a + 2][NB]; pitch_synth_kernel then reads mag' where it read mag, and
@@ -13,10 +13,10 @@
 //                          the peaks as one 64-bit ballot per wave and finds the nearest set bit either side of k in those nine words;
 //                          two barriers per step (the LDS is double-buffered by the parity of t).  The five global rows of the next
 //                          PT_AHEAD steps are in flight while one step computes: their addresses depend on t alone.
-//   pitch_synth_kernel     one wave per step: the interpolated magnitude times sincospif of the phase, packed to the half-size
-//                          spectrum, inverted by dn_fft, windowed: [B][F_s][n]
-//   pitch_ola_kernel       denoise_ola_kernel's gather with the frame count F_s of the item (an F_s of 2 or 3, which a 513-sample item
-//                          has at -12, is below what that kernel takes); 1 / sum w^2 from the DenoiseTab rows, and for the one case
+//   pitch_synth_kernel     one wave per step: the interpolated magnitude times sincospif of the phase, then pack, inverse and
+//                          windowed store of stft.hip.h: [B][F_s][n]
+//   pitch_ola_kernel       the gather of stft.hip.h with the frame count F_s of the item (an F_s of 2 or 3, which a 513-sample item
+//                          has at -12, is below what the denoiser takes); 1 / sum w^2 from the StftTab rows, and for the one case
 //                          they do not hold (F_s = 2: both neighbours missing) formed in double in the kernel
 //   pitch_geom_kernel      N_u / H and min(len, N_v) per item, for the resampler
 //   resample_kernel<float, true>   u -> y, cropped; pitch_short_kernel copies the items below n/2 + 1 samples
@@ -31,7 +31,7 @@
 #define PT_LOG2M 9
 #define PT_WAVES 9                       // of pitch_phase_kernel: 576 threads, bin k = threadIdx.x < PT_NB
 #define PT_AHEAD 4                       // steps whose rows pitch_phase_kernel has in flight
-static_assert(PT_N == VITS_DENOISE_MAX_FILTER, "the pitch stage runs on the denoiser's 1024-point tables");
+static_assert(PT_N == SF_N && PT_LOG2M == SF_LOG2MAXM, "the pitch stage runs on the 1024-point frame transform of stft.hip.h");
 static_assert(PT_WAVES * 64 >= PT_NB, "a thread per bin");
 
 __host__ __device__ __forceinline__ long long pt_frames_a(long long len) { return len >= PT_M + 1 ? 1 + len / PT_H : 0; }
@@ -51,49 +51,35 @@ __device__ __forceinline__ float pt_interp(float a, float b, float alpha) {
   return __fadd_rn(__fmul_rn(__fsub_rn(1.f, alpha), a), __fmul_rn(alpha, b));
 }
 
-// Rows [0, F_a + 2) of every item: wave w of workgroup blockIdx.x owns row blockIdx.x * DN_FPB + w.  x and len as in
-// denoise_frames_kernel (x_off = 0); mag / th: [B][a_bstride], row f at f * PT_NB.
-__global__ __launch_bounds__(64 * DN_FPB) void pitch_analysis_kernel(const float* __restrict__ x, long long x_bstride, long long x_n,
+// Rows [0, F_a + 2) of every item: wave w of workgroup blockIdx.x owns row blockIdx.x * SF_FPB + w.  x, x_n and len as
+// sf_frame_load takes them (x_off = 0); mag / th: [B][a_bstride], row f at f * PT_NB.
+__global__ __launch_bounds__(64 * SF_FPB) void pitch_analysis_kernel(const float* __restrict__ x, long long x_bstride, long long x_n,
                                                                      const int* __restrict__ len_frames, long long len_mul,
                                                                      const float* __restrict__ win, const float2* __restrict__ tw,
                                                                      float* __restrict__ mag, unsigned* __restrict__ th, long long a_bstride) {
-  __shared__ float lds[DN_FPB][4][DN_PLANE];
+  __shared__ float lds[SF_FPB][4][SF_PLANE];
   const int wv = threadIdx.x >> 6, t = threadIdx.x & 63;
   const int b = blockIdx.y;
   const long long len = len_frames ? len_frames[b] * len_mul : len_mul;
   const long long Fa = pt_frames_a(len);
-  if (Fa == 0 || (long long)blockIdx.x * DN_FPB >= Fa + 2) return;  // uniform over the workgroup
-  const long long f = (long long)blockIdx.x * DN_FPB + wv;
+  if (Fa == 0 || (long long)blockIdx.x * SF_FPB >= Fa + 2) return;  // uniform over the workgroup
+  const long long f = (long long)blockIdx.x * SF_FPB + wv;
   const bool valid = f < Fa;
   float *ar = lds[wv][0], *ai = lds[wv][1], *br = lds[wv][2], *bi = lds[wv][3];
   const float* xb = x + (long long)b * x_bstride;
-  for (int m = t; m < PT_M; m += 64) {
-    float v0 = 0.f, v1 = 0.f;
-    if (valid) {
-      const long long p = f * PT_H + 2 * m;
-      v0 = dn_load(xb, p, PT_M, len, 0, x_n) * win[2 * m];
-      v1 = dn_load(xb, p + 1, PT_M, len, 0, x_n) * win[2 * m + 1];
-    }
-    ar[DN_PAD(m)] = v0;
-    ai[DN_PAD(m)] = v1;
-  }
+  sf_frame_load(xb, f * PT_H, PT_M, len, 0, x_n, win, valid, t, ar, ai);
   __syncthreads();
-  dn_fft(ar, ai, br, bi, PT_M, PT_LOG2M, tw, t);
+  sf_fft(ar, ai, br, bi, PT_M, PT_LOG2M, tw, t);
   if (f >= Fa + 2) return;
   float* mo = mag + (long long)b * a_bstride + f * PT_NB;
   unsigned* to = th + (long long)b * a_bstride + f * PT_NB;
-  for (int k = t; k <= (PT_M >> 1); k += 64) {  // the unpacking of denoise_frames_kernel
-    const int kp = PT_M - k, kq = kp & (PT_M - 1);
-    const float zkr = ar[DN_PAD(k)], zki = ai[DN_PAD(k)], zpr = ar[DN_PAD(kq)], zpi = ai[DN_PAD(kq)];
-    const float2 w = tw[k];
-    const float er = 0.5f * (zkr + zpr), ei = 0.5f * (zki - zpi);
-    const float o_r = 0.5f * (zki + zpi), o_i = -0.5f * (zkr - zpr);
-    const float tr = w.x * o_r - w.y * o_i, ti = w.x * o_i + w.y * o_r;
-    const float xkr = er + tr, xki = ei + ti, xpr = er - tr, xpi = -(ei - ti);
-    mo[k] = valid ? sqrtf(xkr * xkr + xki * xki) : 0.f;
-    mo[kp] = valid ? sqrtf(xpr * xpr + xpi * xpi) : 0.f;
-    to[k] = valid ? pt_theta(xkr, xki) : 0u;
-    to[kp] = valid ? pt_theta(xpr, xpi) : 0u;
+  for (int k = t; k <= (PT_M >> 1); k += 64) {
+    const int kp = PT_M - k;
+    const SfBins X = sf_unpack(ar, ai, tw, PT_M, k);
+    mo[k] = valid ? sqrtf(X.kr * X.kr + X.ki * X.ki) : 0.f;
+    mo[kp] = valid ? sqrtf(X.pr * X.pr + X.pi * X.pi) : 0.f;
+    to[k] = valid ? pt_theta(X.kr, X.ki) : 0u;
+    to[kp] = valid ? pt_theta(X.pr, X.pi) : 0u;
   }
 }
 
@@ -104,8 +90,8 @@ __global__ __launch_bounds__(64 * DN_FPB) void pitch_analysis_kernel(const float
 // the exact spectrum, which the logarithm turns into a relative error of 1e-4 and more at a bin near zero (the reflect-symmetric first
 // frame has many: its spectrum is real up to a linear phase and crosses zero), and every such bin moves the whole envelope of its row
 // (measured through vits_op_pitch_formant_gain: 3.2 to 4.5 times the fp32 restatement's distance from float64, where the rest of this
-// kernel adds nothing that shows).  So a wave transforms its frame again in double: the window as sinpi^2, a 512-point radix-2 transform
-// of the packed frame in LDS and the unpacking of pitch_analysis_kernel, the magnitude rounded to fp32 once.  From there on fp32.
+// kernel adds nothing that shows).  So a wave transforms its frame again in double (sf_frame_spectrum_f64 and sf_bin_f64
+// of stft.hip.h), the magnitude rounded to fp32 once.  From there on fp32.
 //   A wave keeps L of its row in LDS; lane t sums D[k] cos(2 pi k q / n), D = L - L[0], over its bins k = t + 64 j into C + 1 registers
 // (k = 0 carries D = 0 and adds nothing; the cosine comes from the n-entry table in LDS, padded by one word per 32 so that the stride
 // 32 k of q = 32 spreads over the banks), a butterfly adds the lanes (the same order in every lane, so every lane holds the same
@@ -116,59 +102,29 @@ __global__ __launch_bounds__(64 * DN_FPB) void pitch_analysis_kernel(const float
 static_assert(PT_M * 1999 < (1 << 30) && 1000 * PT_N < (1 << 30), "k P, Q n and r + (k P mod Q n) stay below 2^31");
 
 template <bool GAIN>
-__global__ __launch_bounds__(64 * DN_FPB) void pitch_formant_kernel(const float* __restrict__ x, long long x_bstride, long long x_n,
+__global__ __launch_bounds__(64 * SF_FPB) void pitch_formant_kernel(const float* __restrict__ x, long long x_bstride, long long x_n,
                                                                     const float* __restrict__ mag, long long a_bstride,
                                                                     const int* __restrict__ len_frames, long long len_mul, int P, int Q,
                                                                     float* __restrict__ out) {
   __shared__ double2 s_tw[PT_M];  // exp(-2 pi i t / n), t < n/2
-  __shared__ double2 s_z[DN_FPB][PT_M];
+  __shared__ double2 s_z[SF_FPB][PT_M];
   __shared__ float s_cos[PT_N + PT_N / 32];
-  __shared__ float s_l[DN_FPB][PT_NB];
+  __shared__ float s_l[SF_FPB][PT_NB];
   const int wv = threadIdx.x >> 6, t = threadIdx.x & 63;
   const int b = blockIdx.y;
   const long long len = len_frames ? len_frames[b] * len_mul : len_mul;
   const long long Fa = pt_frames_a(len);
-  if (Fa == 0 || (long long)blockIdx.x * DN_FPB >= Fa + 2) return;  // uniform over the workgroup
-  const long long f = (long long)blockIdx.x * DN_FPB + wv;
+  if (Fa == 0 || (long long)blockIdx.x * SF_FPB >= Fa + 2) return;  // uniform over the workgroup
+  const long long f = (long long)blockIdx.x * SF_FPB + wv;
   const bool valid = f < Fa;
-  for (int i = threadIdx.x; i < PT_N; i += 64 * DN_FPB) s_cos[PT_COS(i)] = cospif((float)i * (2.f / PT_N));
-  for (int i = threadIdx.x; i < PT_M; i += 64 * DN_FPB) {
-    double sn, cs;
-    sincospi((double)i * (2.0 / PT_N), &sn, &cs);
-    s_tw[i] = make_double2(cs, -sn);
-  }
-  // the windowed frame, two samples to a complex point, in bit-reversed order (a wave whose row is behind the last frame transforms zeros)
+  for (int i = threadIdx.x; i < PT_N; i += 64 * SF_FPB) s_cos[PT_COS(i)] = cospif((float)i * (2.f / PT_N));
   double2* Z = s_z[wv];
-  const float* xb = x + (long long)b * x_bstride;
-  for (int m = t; m < PT_M; m += 64) {
-    double v0 = 0.0, v1 = 0.0;
-    if (valid) {
-      const long long p = f * PT_H + 2 * m;
-      const double w0 = sinpi((double)(2 * m) * (1.0 / PT_N)), w1 = sinpi((double)(2 * m + 1) * (1.0 / PT_N));
-      v0 = (double)dn_load(xb, p, PT_M, len, 0, x_n) * (w0 * w0);
-      v1 = (double)dn_load(xb, p + 1, PT_M, len, 0, x_n) * (w1 * w1);
-    }
-    Z[__brev((unsigned)m) >> (32 - PT_LOG2M)] = make_double2(v0, v1);
-  }
-  __syncthreads();
-  for (int h = 1; h < PT_M; h <<= 1) {  // groups of 2 h points, twiddle exp(-2 pi i pos / (2 h))
-    for (int j = t; j < PT_M / 2; j += 64) {
-      const int pos = j & (h - 1), i0 = ((j - pos) << 1) + pos, i1 = i0 + h;
-      const double2 w = s_tw[pos * (PT_M / h)], u = Z[i0], v = Z[i1];
-      const double tr = w.x * v.x - w.y * v.y, ti = w.x * v.y + w.y * v.x;
-      Z[i0] = make_double2(u.x + tr, u.y + ti);
-      Z[i1] = make_double2(u.x - tr, u.y - ti);
-    }
-    __syncthreads();
-  }
+  sf_frame_spectrum_f64(x + (long long)b * x_bstride, f * PT_H, len, x_n, valid, t, s_tw, Z);
   float* L = s_l[wv];
   if (valid)
-    for (int k = t; k < PT_NB; k += 64) {  // X[k] = E[k] + exp(-2 pi i k / n) O[k] of the packed transform
-      const double2 zk = Z[k & (PT_M - 1)], zp = Z[(PT_M - k) & (PT_M - 1)];
-      const double2 w = k < PT_M ? s_tw[k] : make_double2(-1.0, 0.0);
-      const double er = 0.5 * (zk.x + zp.x), ei = 0.5 * (zk.y - zp.y), o_r = 0.5 * (zk.y + zp.y), o_i = -0.5 * (zk.x - zp.x);
-      const double xr = er + (w.x * o_r - w.y * o_i), xi = ei + (w.x * o_i + w.y * o_r);
-      L[k] = logf(fmaxf((float)sqrt(xr * xr + xi * xi), VITS_PITCH_LOG_FLOOR));
+    for (int k = t; k < PT_NB; k += 64) {
+      const double2 X = sf_bin_f64(Z, s_tw, k);
+      L[k] = logf(fmaxf((float)sqrt(X.x * X.x + X.y * X.y), VITS_PITCH_LOG_FLOOR));
     }
   __syncthreads();
   if (f >= Fa + 2) return;
@@ -337,23 +293,23 @@ __global__ __launch_bounds__(64 * PT_WAVES) void pitch_phase_kernel(const float*
   }
 }
 
-// Steps [0, F_s) of every item: wave w of workgroup blockIdx.x owns step blockIdx.x * DN_FPB + w.  fr: [B][fr_bstride], frame t at t * n.
+// Steps [0, F_s) of every item: wave w of workgroup blockIdx.x owns step blockIdx.x * SF_FPB + w.  fr: [B][fr_bstride], frame t at t * n.
 template <bool TAB>
-__global__ __launch_bounds__(64 * DN_FPB) void pitch_synth_kernel(const float* __restrict__ mag, long long a_bstride,
+__global__ __launch_bounds__(64 * SF_FPB) void pitch_synth_kernel(const float* __restrict__ mag, long long a_bstride,
                                                                   const unsigned* __restrict__ phi, long long p_bstride,
                                                                   const int* __restrict__ len_frames, long long len_mul, int P, int Q,
                                                                   const long long* __restrict__ steps, long long s_bstride,
                                                                   const float* __restrict__ win, const float2* __restrict__ tw,
                                                                   float* __restrict__ fr, long long fr_bstride) {
-  __shared__ float lds[DN_FPB][4][DN_PLANE];
+  __shared__ float lds[SF_FPB][4][SF_PLANE];
   const int wv = threadIdx.x >> 6, t = threadIdx.x & 63;
   const int b = blockIdx.y;
   const long long len = len_frames ? len_frames[b] * len_mul : len_mul;
   long long Fs;
   if constexpr (TAB) Fs = pt_tab_fs(steps + (long long)b * s_bstride, pt_frames_a(len));
   else Fs = pt_frames_s(len, P, Q);
-  if ((long long)blockIdx.x * DN_FPB >= Fs) return;  // uniform over the workgroup
-  const long long tau = (long long)blockIdx.x * DN_FPB + wv;
+  if ((long long)blockIdx.x * SF_FPB >= Fs) return;  // uniform over the workgroup
+  const long long tau = (long long)blockIdx.x * SF_FPB + wv;
   const bool valid = tau < Fs;
   float *ar = lds[wv][0], *ai = lds[wv][1], *br = lds[wv][2], *bi = lds[wv][3];
   long long i;
@@ -380,25 +336,12 @@ __global__ __launch_bounds__(64 * DN_FPB) void pitch_synth_kernel(const float* _
       sincospif(2.f * ((float)(int)pr[kp] * 2.3283064365386963e-10f), &s, &c);
       xpr = mp * c; xpi = k > 0 ? mp * s : 0.f;  // (kp = n/2 pairs with k = 0: both imaginary parts are dropped)
     }
-    // the packing of denoise_frames_kernel: Z'[k] = E2 + i O2, stored conjugated so that the forward passes invert it
-    const float2 w = tw[k];
-    const float e2r = 0.5f * (xkr + xpr), e2i = 0.5f * (xki - xpi);
-    const float dr = 0.5f * (xkr - xpr), di = 0.5f * (xki + xpi);
-    const float o2r = dr * w.x + di * w.y, o2i = di * w.x - dr * w.y;
-    ar[DN_PAD(k)] = e2r - o2i;
-    ai[DN_PAD(k)] = -(e2i + o2r);
-    if (k > 0 && kp != k) {
-      ar[DN_PAD(kp)] = e2r + o2i;
-      ai[DN_PAD(kp)] = -(o2r - e2i);
-    }
+    sf_pack(ar, ai, tw, PT_M, k, xkr, xki, xpr, xpi);
   }
   __syncthreads();
-  dn_fft(ar, ai, br, bi, PT_M, PT_LOG2M, tw, t);
+  sf_fft(ar, ai, br, bi, PT_M, PT_LOG2M, tw, t);
   if (!valid) return;
-  const float inv_m = 1.0f / (float)PT_M;
-  float2* of = reinterpret_cast<float2*>(fr + (long long)b * fr_bstride + tau * PT_N);
-  for (int m = t; m < PT_M; m += 64)
-    of[m] = make_float2(ar[DN_PAD(m)] * inv_m * win[2 * m], -ai[DN_PAD(m)] * inv_m * win[2 * m + 1]);
+  sf_frame_store(ar, ai, PT_M, win, t, fr + (long long)b * fr_bstride + tau * PT_N);
 }
 
 // u[b][j], j < n_count: the overlap-add of the item's F_s frames, exactly 0 at and beyond N_u = H (F_s - 1).
@@ -418,19 +361,14 @@ __global__ __launch_bounds__(256) void pitch_ola_kernel(const float* __restrict_
   if (j < PT_H * (Fs - 1)) {
     const long long p = j + PT_M, fl = p / PT_H;  // fl in [2, F_s]
     const int r = (int)(p - fl * PT_H);
-    const bool head = fl < 3, tail = fl >= Fs;
-    const float* fb = fr + (long long)b * fr_bstride;
-    float acc = 0.f;
-    for (int d = 3; d >= 0; --d) {
-      const long long f = fl - d;
-      if (f >= 0 && f < Fs) acc += fb[f * PT_N + r + d * PT_H];
-    }
+    int region;
+    const float acc = sf_ola_sum(fr + (long long)b * fr_bstride, fl, r, PT_N, PT_H, Fs, 0, &region);
     float e;
-    if (head && tail) {  // F_s = 2: frames 0 and 1 alone
+    if (fl < 3 && fl >= Fs) {  // F_s = 2: frames 0 and 1 alone, head and tail at once
       const double s1 = sinpi((double)(r + PT_H) / PT_N), s2 = sinpi((double)(r + 2 * PT_H) / PT_N);
       e = (float)(1.0 / (s1 * s1 * s1 * s1 + s2 * s2 * s2 * s2));
     } else {
-      e = inv_env[(head ? 0 : (tail ? 2 : 1)) * PT_H + r];
+      e = inv_env[region * PT_H + r];
     }
     v = acc * e;
   }
@@ -516,8 +454,8 @@ static int pitch_run(int device, hipStream_t stream, const float* x, long long x
                      const long long* h_len, int B, int P, int Q, bool formant, float* y, long long y_bstride, long long n_count, float* u_out,
                      long long u_bstride) {
   if (B <= 0) return VITS_OK;
-  const DenoiseTab* D = nullptr;
-  TRY(denoise_get(device, PT_N, &D));
+  const StftTab* D = nullptr;
+  TRY(stft_tab_get(device, PT_N, &D));
   std::shared_ptr<ResampleTab> R;  // (held until the stream has been waited for)
   if (!u_out) TRY(pitch_tab_get(device, P, Q, &R));
   // groups of consecutive items whose scratch fits
@@ -561,14 +499,14 @@ static int pitch_run(int device, hipStream_t stream, const float* x, long long x
       float* d_u = reinterpret_cast<float*>(p); p += sizeof(float) * (size_t)c * u_bs;
       int* d_nu = reinterpret_cast<int*>(p); p += sizeof(int) * (size_t)c;
       int* d_crop = reinterpret_cast<int*>(p);
-      hipLaunchKernelGGL(pitch_analysis_kernel, dim3((unsigned)((Fa + 2 + DN_FPB - 1) / DN_FPB), c), dim3(64 * DN_FPB), 0, stream, xg, x_bstride,
+      hipLaunchKernelGGL(pitch_analysis_kernel, dim3((unsigned)((Fa + 2 + SF_FPB - 1) / SF_FPB), c), dim3(64 * SF_FPB), 0, stream, xg, x_bstride,
                          x_n, lg, len_mul, D->d_win, D->d_tw, d_mag, d_th, a_bs);
       if (formant)
-        hipLaunchKernelGGL(pitch_formant_kernel<false>, dim3((unsigned)((Fa + 2 + DN_FPB - 1) / DN_FPB), c), dim3(64 * DN_FPB), 0, stream, xg,
+        hipLaunchKernelGGL(pitch_formant_kernel<false>, dim3((unsigned)((Fa + 2 + SF_FPB - 1) / SF_FPB), c), dim3(64 * SF_FPB), 0, stream, xg,
                            x_bstride, x_n, d_mag, a_bs, lg, len_mul, P, Q, d_magf);
       hipLaunchKernelGGL(pitch_phase_kernel<false>, dim3(c), dim3(64 * PT_WAVES), 0, stream, d_mag, d_th, a_bs, lg, len_mul, P, Q,
                          (const long long*)nullptr, 0LL, d_phi, p_bs);
-      hipLaunchKernelGGL(pitch_synth_kernel<false>, dim3((unsigned)((Fs + DN_FPB - 1) / DN_FPB), c), dim3(64 * DN_FPB), 0, stream, d_magf, a_bs, d_phi,
+      hipLaunchKernelGGL(pitch_synth_kernel<false>, dim3((unsigned)((Fs + SF_FPB - 1) / SF_FPB), c), dim3(64 * SF_FPB), 0, stream, d_magf, a_bs, d_phi,
                          p_bs, lg, len_mul, P, Q, (const long long*)nullptr, 0LL, D->d_win, D->d_tw, d_fr, f_bs);
       if (u_out) {
         hipLaunchKernelGGL(pitch_ola_kernel<false>, dim3((unsigned)((u_bstride + 255) / 256), c), dim3(256), 0, stream, d_fr, f_bs, lg, len_mul, P, Q,
@@ -625,7 +563,7 @@ static int pitch_gain_run(int device, const float* dx, const int* dl, int B, lon
   const long long Fa = pt_frames_a(N), a_bs = (N / PT_H + 3) * PT_NB;
   if (!Fa) return VITS_OK;
   HIP_TRY(hipSetDevice(device));
-  hipLaunchKernelGGL(pitch_formant_kernel<true>, dim3((unsigned)((Fa + 2 + DN_FPB - 1) / DN_FPB), B), dim3(64 * DN_FPB), 0, nullptr, dx, N, N,
+  hipLaunchKernelGGL(pitch_formant_kernel<true>, dim3((unsigned)((Fa + 2 + SF_FPB - 1) / SF_FPB), B), dim3(64 * SF_FPB), 0, nullptr, dx, N, N,
                      (const float*)nullptr, a_bs, dl, 1, P, Q, g);
   hipError_t e = hipGetLastError();
   const hipError_t e2 = hipStreamSynchronize(nullptr);

@@ -92,7 +92,7 @@ static void resample_fill(const ResamplePlan& P, float* table) {
 //   tab      the device table [taps][L] described at the top
 //   y        item b's output at y + b * y_bstride; y[j] is output n_begin + j, written for 0 <= j < n_count
 //            (exactly 0 for outputs at and beyond ceil(len * L / M))
-// OUT = int16_t: pcm16_kernel's epilogue (scale, * 32767, clip, truncating cast); dv (nullable) carries the per-call scale.
+// OUT = int16_t: pcm16_of; dv (nullable) carries the per-call scale.
 // CROP (the pitch stage, include/vits_pitch.h): item b's outputs at and beyond crop[b] are 0 as well; without it crop is not read.
 template <typename OUT, bool CROP = false>
 __global__ __launch_bounds__(VITS_RESAMPLE_TILE) void resample_kernel(const float* __restrict__ x, long long x_bstride, long long x_off,
@@ -139,10 +139,7 @@ __global__ __launch_bounds__(VITS_RESAMPLE_TILE) void resample_kernel(const floa
   }
   if constexpr (sizeof(OUT) == sizeof(int16_t)) {
     if (dv) scale = dv->pcm_scale;
-    float s = acc * scale;
-    s = s * 32767.0f;
-    s = fminf(fmaxf(s, -32767.0f), 32767.0f);
-    y[(long long)b * y_bstride + j_out] = (OUT)(int)s;
+    y[(long long)b * y_bstride + j_out] = pcm16_of(acc, scale);
   } else {
     y[(long long)b * y_bstride + j_out] = acc;
   }
@@ -163,14 +160,7 @@ static int resample_upload(int device, ResampleTab& T) {
     const int p = (int)(((long long)r * P.M) % P.L);
     for (int i = 0; i < P.taps; ++i) dev[(size_t)i * P.L + r] = tab[(size_t)p * P.taps + i];
   }
-  HIP_TRY(hipSetDevice(device));
-  if (hipMalloc((void**)&T.d, dev.size() * sizeof(float)) != hipSuccess) return fail(VITS_ERR_NOMEM, "resample: table alloc failed");
-  if (hipMemcpy(T.d, dev.data(), dev.size() * sizeof(float), hipMemcpyHostToDevice) != hipSuccess) {
-    hipFree(T.d);
-    T.d = nullptr;
-    return fail(VITS_ERR_DEVICE, "resample: table upload failed");
-  }
-  return VITS_OK;
+  return dev_table_upload(device, "resample", dev.data(), dev.size() * sizeof(float), (void**)&T.d);
 }
 
 // Uploads on first use (call it outside stream capture).

@@ -799,7 +799,7 @@ static int stts_phase2(stts_model* m, SttsFront* F, SttsBack* Bk, bool audio) {
 
 // STTS_FLAG_DENOISE of a call (include/vits_denoise.h): the two appended fields are read only under the flag
 struct SttsDenoise {
-  const DenoiseTab* T = nullptr;  // null: off
+  const StftTab* T = nullptr;  // null: off
   const float* bias = nullptr;
   float strength = 0.f;
 };

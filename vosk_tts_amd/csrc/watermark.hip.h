@@ -1,15 +1,13 @@
 // watermark.hip.h -- the keyed audio watermark (include/vits_watermark.h): the embed stage of the output tail and the detector.
-// Part of the ONE translation unit engine.hip (included there, behind denoise.hip.h and loudness.hip.h, in front of out_tail.hip.h).
+// Part of the ONE translation unit engine.hip (included there, behind stft.hip.h and loudness.hip.h, in front of out_tail.hip.h).
 //
-// Embed, two launches (the denoiser's transform, its device functions and its host tables; its kernels stay as they are):
-//   wm_frames_kernel   one wave per frame, DN_FPB frames per workgroup: the frame and its half-size complex FFT in LDS (dn_fft), the
-//                      spectrum unpacked to the bins k and M - k in registers, the chip of each bin computed there from f and k, the
-//                      pair packed back and inverted, the windowed frame to a scratch [frames, n]
-//   wm_ola_kernel      a gather as denoise_ola_kernel: every output sample sums its four or fewer frames in ascending frame order;
-//                      behind H floor(len / H) it copies x, beyond len it writes 0; OUT = int16_t: pcm16_kernel's epilogue
+// Embed, two launches (the frame transform of stft.hip.h at n = 1024: its device functions, LDS layout and StftTab):
+//   wm_frames_kernel   one wave per frame: load, transform and unpack, the chip of each bin computed in registers from f and k, pack,
+//                      inverse, the windowed frame to a scratch [frames, n]
+//   wm_ola_kernel      the gather of stft.hip.h; behind H floor(len / H) it copies x, beyond len it writes 0; OUT = int16_t: pcm16_of
 // Detect, three launches:
-//   wm_lb_kernel       the hop-128 transform, one wave per frame: band magnitudes to the wave's free LDS plane, their maximum by a
-//                      wave reduction, the four-bin log mean before the store: Lb [F', 96] floats
+//   wm_lb_kernel       the same load, transform and unpack at hop 128: band magnitudes to the wave's free LDS plane, their maximum
+//                      by a wave reduction, the four-bin log mean before the store: Lb [F', 96] floats
 //   wm_score_kernel    one workgroup per (item, offset index): 16 tile rows at a time, T of a row of every q in LDS as doubles
 //                      [16][96], D and the running G of the thread's six (q, j) in registers, then the two sums in a fixed tree
 //   wm_argmax_kernel   one thread per item over its 128 scores
@@ -32,7 +30,7 @@
 #define WM_Q VITS_WATERMARK_ROWS
 #define WM_DH VITS_WATERMARK_DETECT_HOP
 #define WM_SCORE_THREADS 256
-static_assert(WM_N <= VITS_DENOISE_MAX_FILTER && (1 << WM_LOG2M) == WM_M, "the watermark runs on the denoiser's transform");
+static_assert(WM_N <= SF_N && (1 << WM_LOG2M) == WM_M, "the watermark runs on the frame transform of stft.hip.h");
 static_assert((WM_HI - WM_LO) == 4 * WM_G && (WM_Q * WM_G) % WM_SCORE_THREADS == 0, "96 groups of 4 bins; whole (q, j) per thread");
 
 __host__ __device__ __forceinline__ uint32_t wm_mix(uint32_t x) {
@@ -47,69 +45,42 @@ __device__ __forceinline__ float wm_bin_gain(uint32_t mk, int q, int k, float gp
   return wm_chip(mk, q, (k - WM_LO) >> 2) ? gp : gm;
 }
 
-// The marked, windowed frames of every item: wave w of workgroup blockIdx.x owns frame f = blockIdx.x * DN_FPB + w.
+// The marked, windowed frames of every item: wave w of workgroup blockIdx.x owns frame f = blockIdx.x * SF_FPB + w.
 //   x      item b at x + b * x_bstride, samples [0, len), len = ld_len(..) (loudness.hip.h: the item as returned, at most N)
 //   out    out[b * out_bstride + f * n + i]; an item shorter than n/2 + 1 has no frames (wm_ola_kernel passes it through)
-__global__ __launch_bounds__(64 * DN_FPB) void wm_frames_kernel(const float* __restrict__ x, long long x_bstride, long long N,
+__global__ __launch_bounds__(64 * SF_FPB) void wm_frames_kernel(const float* __restrict__ x, long long x_bstride, long long N,
                                                                 const int* __restrict__ len_frames, long long len_mul, int L, int Mr,
                                                                 const float* __restrict__ win, const float2* __restrict__ tw, uint32_t mk,
                                                                 float gp, float gm, float* __restrict__ out, long long out_bstride) {
-  __shared__ float lds[DN_FPB][4][DN_PLANE];
+  __shared__ float lds[SF_FPB][4][SF_PLANE];
   const int wv = threadIdx.x >> 6, t = threadIdx.x & 63;
   const int b = blockIdx.y;
   const long long len = ld_len(len_frames, len_mul, L, Mr, N, b);
   const long long F = len >= WM_M + 1 ? 1 + len / WM_H : 0;
-  const long long f = (long long)blockIdx.x * DN_FPB + wv;
-  if ((long long)blockIdx.x * DN_FPB >= F) return;  // the whole workgroup is beyond the item: uniform exit
+  const long long f = (long long)blockIdx.x * SF_FPB + wv;
+  if ((long long)blockIdx.x * SF_FPB >= F) return;  // the whole workgroup is beyond the item: uniform exit
   const bool valid = f < F;
   float *ar = lds[wv][0], *ai = lds[wv][1], *br = lds[wv][2], *bi = lds[wv][3];
   const float* xb = x + (long long)b * x_bstride;
-  for (int m = t; m < WM_M; m += 64) {
-    float v0 = 0.f, v1 = 0.f;
-    if (valid) {
-      const long long p = f * WM_H + 2 * m;
-      v0 = dn_load(xb, p, WM_M, len, 0, len) * win[2 * m];
-      v1 = dn_load(xb, p + 1, WM_M, len, 0, len) * win[2 * m + 1];
-    }
-    ar[DN_PAD(m)] = v0;
-    ai[DN_PAD(m)] = v1;
-  }
+  sf_frame_load(xb, f * WM_H, WM_M, len, 0, len, win, valid, t, ar, ai);
   __syncthreads();
-  dn_fft(ar, ai, br, bi, WM_M, WM_LOG2M, tw, t);
+  sf_fft(ar, ai, br, bi, WM_M, WM_LOG2M, tw, t);
   const int q = (int)((f >> 2) & (WM_Q - 1));
-  // unpack, gain, pack: the algebra of denoise_frames_kernel with the chip's gain in the threshold's place
-  for (int k = t; k <= (WM_M >> 1); k += 64) {
-    const int kp = WM_M - k, kq = kp & (WM_M - 1);
-    const float zkr = ar[DN_PAD(k)], zki = ai[DN_PAD(k)], zpr = ar[DN_PAD(kq)], zpi = ai[DN_PAD(kq)];
-    const float2 w = tw[k];
-    const float er = 0.5f * (zkr + zpr), ei = 0.5f * (zki - zpi);
-    const float o_r = 0.5f * (zki + zpi), o_i = -0.5f * (zkr - zpr);
-    const float tr = w.x * o_r - w.y * o_i, ti = w.x * o_i + w.y * o_r;
-    float xkr = er + tr, xki = ei + ti, xpr = er - tr, xpi = -(ei - ti);
-    const float gk = wm_bin_gain(mk, q, k, gp, gm), gq = wm_bin_gain(mk, q, kp, gp, gm);
-    xkr *= gk; xki *= gk; xpr *= gq; xpi *= gq;
-    const float e2r = 0.5f * (xkr + xpr), e2i = 0.5f * (xki - xpi);
-    const float dr = 0.5f * (xkr - xpr), di = 0.5f * (xki + xpi);
-    const float o2r = dr * w.x + di * w.y, o2i = di * w.x - dr * w.y;
-    br[DN_PAD(k)] = e2r - o2i;
-    bi[DN_PAD(k)] = -(e2i + o2r);
-    if (k > 0 && kp != k) {
-      br[DN_PAD(kp)] = e2r + o2i;
-      bi[DN_PAD(kp)] = -(o2r - e2i);
-    }
+  for (int k = t; k <= (WM_M >> 1); k += 64) {  // unpack, the chip's gain, pack
+    SfBins X = sf_unpack(ar, ai, tw, WM_M, k);
+    const float gk = wm_bin_gain(mk, q, k, gp, gm), gq = wm_bin_gain(mk, q, WM_M - k, gp, gm);
+    X.kr *= gk; X.ki *= gk; X.pr *= gq; X.pi *= gq;
+    sf_pack(br, bi, tw, WM_M, k, X.kr, X.ki, X.pr, X.pi);
   }
   __syncthreads();
   { float* s = ar; ar = br; br = s; s = ai; ai = bi; bi = s; }
-  dn_fft(ar, ai, br, bi, WM_M, WM_LOG2M, tw, t);
+  sf_fft(ar, ai, br, bi, WM_M, WM_LOG2M, tw, t);
   if (!valid) return;
-  const float inv_m = 1.0f / (float)WM_M;
-  float2* of = reinterpret_cast<float2*>(out + (long long)b * out_bstride + f * WM_N);  // (n and every stride are even: 8-byte aligned)
-  for (int m = t; m < WM_M; m += 64)
-    of[m] = make_float2(ar[DN_PAD(m)] * inv_m * win[2 * m], -ai[DN_PAD(m)] * inv_m * win[2 * m + 1]);
+  sf_frame_store(ar, ai, WM_M, win, t, out + (long long)b * out_bstride + f * WM_N);
 }
 
 // y[b * y_bstride + j], 0 <= j < n_count: the overlap-added frames on [0, H floor(len / H)), x from there up to len, exactly 0 at and
-// beyond len; an item shorter than n/2 + 1 samples is x.  OUT = int16_t: pcm16_kernel's epilogue (scale, * 32767, clip, truncating cast).
+// beyond len; an item shorter than n/2 + 1 samples is x.  OUT = int16_t: pcm16_of.
 template <typename OUT>
 __global__ __launch_bounds__(256) void wm_ola_kernel(const float* __restrict__ fr, long long fr_bstride, const float* __restrict__ x,
                                                      long long x_bstride, long long N, const int* __restrict__ len_frames, long long len_mul,
@@ -125,71 +96,46 @@ __global__ __launch_bounds__(256) void wm_ola_kernel(const float* __restrict__ f
     if (len >= WM_M + 1 && j < WM_H * (F - 1)) {
       const long long p = j + WM_M, fl = p / WM_H;
       const int r = (int)(p - fl * WM_H);
-      const int region = fl < 3 ? 0 : (fl >= F ? 2 : 1);
-      const float* fb = fr + (long long)b * fr_bstride;
-      float acc = 0.f;
-      for (int d = 3; d >= 0; --d) {
-        const long long f = fl - d;
-        if (f >= 0 && f < F) acc += fb[f * WM_N + r + d * WM_H];
-      }
+      int region;
+      const float acc = sf_ola_sum(fr + (long long)b * fr_bstride, fl, r, WM_N, WM_H, F, 0, &region);
       v = acc * inv_env[region * WM_H + r];
     } else {
       v = x[(long long)b * x_bstride + j];
     }
   }
-  if constexpr (sizeof(OUT) == sizeof(int16_t)) {
-    float s = v * scale;
-    s = s * 32767.0f;
-    s = fminf(fmaxf(s, -32767.0f), 32767.0f);
-    y[(long long)b * y_bstride + j] = (OUT)(int)s;
-  } else {
-    y[(long long)b * y_bstride + j] = v;
-  }
+  if constexpr (sizeof(OUT) == sizeof(int16_t)) y[(long long)b * y_bstride + j] = pcm16_of(v, scale);
+  else y[(long long)b * y_bstride + j] = v;
 }
 
 // Lb[b * lb_bstride + g * 96 + j] of the hop-128 frames g < F' = 1 + len / 128 of every item (none below n/2 + 1 samples).
-__global__ __launch_bounds__(64 * DN_FPB) void wm_lb_kernel(const float* __restrict__ x, long long x_bstride, const int* __restrict__ lens,
+__global__ __launch_bounds__(64 * SF_FPB) void wm_lb_kernel(const float* __restrict__ x, long long x_bstride, const int* __restrict__ lens,
                                                             const float* __restrict__ win, const float2* __restrict__ tw,
                                                             float* __restrict__ Lb, long long lb_bstride) {
-  __shared__ float lds[DN_FPB][4][DN_PLANE];
+  __shared__ float lds[SF_FPB][4][SF_PLANE];
   const int wv = threadIdx.x >> 6, t = threadIdx.x & 63;
   const int b = blockIdx.y;
   const long long len = lens[b];
   const long long F = len >= WM_M + 1 ? 1 + len / WM_DH : 0;
-  const long long g = (long long)blockIdx.x * DN_FPB + wv;
-  if ((long long)blockIdx.x * DN_FPB >= F) return;  // uniform exit
+  const long long g = (long long)blockIdx.x * SF_FPB + wv;
+  if ((long long)blockIdx.x * SF_FPB >= F) return;  // uniform exit
   const bool valid = g < F;
   float *ar = lds[wv][0], *ai = lds[wv][1], *br = lds[wv][2], *bi = lds[wv][3];
   const float* xb = x + (long long)b * x_bstride;
-  for (int m = t; m < WM_M; m += 64) {
-    float v0 = 0.f, v1 = 0.f;
-    if (valid) {
-      const long long p = g * WM_DH + 2 * m;  // (the padded signal from 128 g on: centred on sample 128 g)
-      v0 = dn_load(xb, p, WM_M, len, 0, len) * win[2 * m];
-      v1 = dn_load(xb, p + 1, WM_M, len, 0, len) * win[2 * m + 1];
-    }
-    ar[DN_PAD(m)] = v0;
-    ai[DN_PAD(m)] = v1;
-  }
+  sf_frame_load(xb, g * WM_DH, WM_M, len, 0, len, win, valid, t, ar, ai);  // (the padded signal from 128 g on: centred on sample 128 g)
   __syncthreads();
-  dn_fft(ar, ai, br, bi, WM_M, WM_LOG2M, tw, t);
+  sf_fft(ar, ai, br, bi, WM_M, WM_LOG2M, tw, t);
   // |X[k]| and |X[M - k]| of the band into the free plane br, at k - 16 (unpadded: 384 floats, read four in a row per lane below)
   float mx = 0.f;
   for (int k = t; k <= (WM_M >> 1); k += 64) {
-    const int kp = WM_M - k, kq = kp & (WM_M - 1);
-    const float zkr = ar[DN_PAD(k)], zki = ai[DN_PAD(k)], zpr = ar[DN_PAD(kq)], zpi = ai[DN_PAD(kq)];
-    const float2 w = tw[k];
-    const float er = 0.5f * (zkr + zpr), ei = 0.5f * (zki - zpi);
-    const float o_r = 0.5f * (zki + zpi), o_i = -0.5f * (zkr - zpr);
-    const float tr = w.x * o_r - w.y * o_i, ti = w.x * o_i + w.y * o_r;
-    const float xkr = er + tr, xki = ei + ti, xpr = er - tr, xpi = -(ei - ti);
+    const int kp = WM_M - k;
+    const SfBins X = sf_unpack(ar, ai, tw, WM_M, k);
     if (k >= WM_LO && k < WM_HI) {
-      const float a = sqrtf(xkr * xkr + xki * xki);
+      const float a = sqrtf(X.kr * X.kr + X.ki * X.ki);
       br[k - WM_LO] = a;
       mx = fmaxf(mx, a);
     }
     if (kp != k && kp >= WM_LO && kp < WM_HI) {
-      const float a = sqrtf(xpr * xpr + xpi * xpi);
+      const float a = sqrtf(X.pr * X.pr + X.pi * X.pi);
       br[kp - WM_LO] = a;
       mx = fmaxf(mx, a);
     }
@@ -289,7 +235,7 @@ struct WmReq {
   bool on = false;
   uint32_t key = 0;
   float gp = 1.f, gm = 1.f;  // fp32(1 + a), fp32(1 - a)
-  const DenoiseTab* T = nullptr;  // set by the callers that launch on the device (wm_get: uploaded on first use, before any capture)
+  const StftTab* T = nullptr;  // set by the callers that launch on the device (stft_tab_get: uploaded on first use, before any capture)
 };
 
 // 0 -> the default; a depth outside (0, 2] dB, NaN included, is refused by name
@@ -307,7 +253,6 @@ static int wm_req(bool on, uint32_t key, float depth_db, WmReq* out) {
   out->gm = 1.0f - a;
   return VITS_OK;
 }
-static int wm_get(int device, const DenoiseTab** T) { return denoise_get(device, WM_N, T); }
 // floats of scratch one item of N samples needs
 static size_t wm_scratch_elems(long long N) { return (size_t)(N / WM_H + 1) * WM_N; }
 
@@ -318,11 +263,11 @@ static void wm_launch(hipStream_t stream, const WmReq& q, const float* x, long l
                       long long len_mul, int L, int Mr, int B, float* scratch, long long scratch_bstride, OUT* y, long long y_bstride,
                       long long n_count, float scale) {
   if (n_count <= 0 || B <= 0) return;
-  const DenoiseTab& T = *q.T;
+  const StftTab& T = *q.T;
   const long long Fmax = N >= WM_M + 1 ? 1 + N / WM_H : 0;
   const uint32_t mk = wm_mix(q.key);
   if (Fmax > 0)
-    hipLaunchKernelGGL(wm_frames_kernel, dim3((unsigned)cdiv((int)Fmax, DN_FPB), B), dim3(64 * DN_FPB), 0, stream, x, x_bstride, N, len_frames, len_mul, L,
+    hipLaunchKernelGGL(wm_frames_kernel, dim3((unsigned)cdiv((int)Fmax, SF_FPB), B), dim3(64 * SF_FPB), 0, stream, x, x_bstride, N, len_frames, len_mul, L,
                        Mr, T.d_win, T.d_tw, mk, q.gp, q.gm, scratch, scratch_bstride);
   hipLaunchKernelGGL(wm_ola_kernel<OUT>, dim3((unsigned)((n_count + 255) / 256), B), dim3(256), 0, stream, scratch, scratch_bstride, x, x_bstride, N,
                      len_frames, len_mul, L, Mr, T.d_env, y, y_bstride, n_count, scale);
@@ -334,7 +279,7 @@ static int wm_op(int device, const float* x, const int64_t* lengths, int32_t B, 
   std::vector<int> len32;
   TRY(op_items_check("watermark", x, lengths, B, N, &len32));
   if (!y) return fail(VITS_ERR_ARG, "watermark: bad argument");
-  TRY(wm_get(device, &q.T));
+  TRY(stft_tab_get(device, WM_N, &q.T));
   OpDoor d("watermark", device);
   const size_t sc = wm_scratch_elems(N);
   float* dx = d.up(x, (size_t)B * N);
@@ -358,8 +303,8 @@ int vits_op_watermark_detect(int device, const float* x, const int64_t* lengths,
   std::vector<int> len32;
   TRY(op_items_check("watermark detect", x, lengths, B, N, &len32));
   if (!z || !offset || !rows) return fail(VITS_ERR_ARG, "watermark detect: bad argument");
-  const DenoiseTab* T = nullptr;
-  TRY(wm_get(device, &T));
+  const StftTab* T = nullptr;
+  TRY(stft_tab_get(device, WM_N, &T));
   OpDoor d("watermark detect", device);
   const long long Fmax = N >= WM_M + 1 ? 1 + N / WM_DH : 0;
   const long long lbs = (Fmax ? Fmax : 1) * WM_G;
@@ -375,7 +320,7 @@ int vits_op_watermark_detect(int device, const float* x, const int64_t* lengths,
   if (d.ok()) {
     const uint32_t mk = wm_mix(key);
     if (Fmax > 0)
-      hipLaunchKernelGGL(wm_lb_kernel, dim3((unsigned)cdiv((int)Fmax, DN_FPB), B), dim3(64 * DN_FPB), 0, nullptr, dx, N, dl, T->d_win, T->d_tw, dlb, lbs);
+      hipLaunchKernelGGL(wm_lb_kernel, dim3((unsigned)cdiv((int)Fmax, SF_FPB), B), dim3(64 * SF_FPB), 0, nullptr, dx, N, dl, T->d_win, T->d_tw, dlb, lbs);
     hipLaunchKernelGGL(wm_score_kernel, dim3(VITS_WATERMARK_OFFSETS, B), dim3(WM_SCORE_THREADS), 0, nullptr, dlb, lbs, dl, mk, dza, dra);
     hipLaunchKernelGGL(wm_argmax_kernel, dim3(cdiv(B, 64)), dim3(64), 0, nullptr, dza, dra, B, dz, dof, dro);
   }
