@@ -28,6 +28,7 @@
 #include <type_traits>
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include "dec_end_rules.h"  // KS_SLAB_PITCH and the launch rules of the chunk split
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
@@ -144,6 +145,7 @@ struct ConvParams {
   int skip_len;
   // K-split kernel, 16 waves: the contraction is split by input-channel chunk with the operand window staged once per chunk
   // (ks_chunk_body) instead of by tap.  Set by the executor (launch_ks, engine_launch.hip.h), never by a stage or the planner.
+  // 2: the same with a workgroup owning two adjacent column tiles; ntiles_n then counts pairs.
   int ks_chunk;
   // Compact tile map of a ragged launch: tile_start[b] = number of column tiles of items < b (B+1 entries,
   // built on the device by ragged_tiles_kernel for this launch's tile width).  Working tiles get the lowest
@@ -823,11 +825,24 @@ struct ks_false { static constexpr bool value = false; };
 // The slab is this wave's 4 KB of the reduction buffer (16 rows of KS_SLAB_PITCH floats): no LDS beyond what the kernel has, and no
 // workgroup barrier before the reduction, which finds each wave's partial tile where its slab was.
 // ---------------------------------------------------------------------------------------------
-#define KS_SLAB_PITCH 64  // floats; 32 + halo <= 64 is part of the launch predicate (the two 32-lane halves of a ds_read_b32 never conflict)
-template <int NIN, int KT, int UP>
-__device__ __forceinline__ void ks_chunk_body(const ConvParams& P, const ConvGroup& G, float* lds, int b, int m0, int n0, int tap_base, int t_lim,
-                                              int wave, int lane, f32x16& acc) {
-  constexpr int NW = 16, ROWS = 2 * UP, NJ = ROWS / 4, NA = UP / 4, NV = NIN > 2 ? 3 : 1, D = KT ? KT : 2;
+//
+// NT = 2 (P.ks_chunk == 2; who gets it: ks_pair_takes): the workgroup owns the column tiles 2 j and 2 j + 1 of its row tile.  A launch of
+// a little more than one workgroup per CU runs two rounds of the chip for hardly more than one round of work; with two accumulators
+// every weight fragment feeds twice the MFMAs and the grid is one round (ups[1] of the single utterance: 304 -> 160 workgroups, 19.9 ->
+// 18.1 us -- the second tile's MFMAs are 3.4 us of matrix pipe per workgroup; profiles/dec_end_bench.txt).
+// The wave stages the 64 + halo columns of its unit once (a load instruction = 32 vectors of 2 rows), each weight vector of a tap runs
+// its 4 MFMAs on the first tile, then on the second, and only then is re-requested.  Units, their waves, the tap order and every
+// accumulator's MFMA sequence are the single tile's: the result is bit-identical.  The slab pitch is 64 NT floats: a 32-lane half of a
+// ds_read_b32 reads 32 consecutive floats of one row at any pitch (only lanes of the same half can conflict), and 16 rows of 128 floats
+// are the 8 KB a wave's two partial tiles take in the reduction buffer.  Built for KT = 4 only: with 7 taps the seven-slot ring beside
+// two accumulators and twice the staging vectors does not fit 128 registers (spills), and KT = 0 has no pair form.
+// KS_SLAB_PITCH (dec_end_rules.h) = 64 floats per column tile; 32 NT + halo <= 64 NT is part of the launch predicate (the two 32-lane halves of a ds_read_b32 never conflict)
+template <int NIN, int KT, int UP, int NT>
+__device__ __forceinline__ void ks_chunk_body(const ConvParams& P, const ConvGroup& G, float* sl, int b, int m0, int n0, int tap_base, int t_lim,
+                                              int wave, int lane, f32x16* acc) {
+  static_assert(NT == 1 || KT != 0, "the pair form has compile-time tap counts only");
+  constexpr int PITCH = NT * KS_SLAB_PITCH, VPR = PITCH / 4, RPI = 64 / VPR;  // vectors per slab row, rows per load instruction
+  constexpr int NW = 16, ROWS = 2 * UP, NJ = ROWS / RPI, NA = UP / 4, NV = NIN > 2 ? 3 : 1, D = KT ? KT : 2;
   const int h = lane >> 5, l31 = lane & 31;
   const int K = KT ? KT : G.K, dil = G.dil;
   const int nunits = P.Cin / ROWS;
@@ -845,19 +860,20 @@ __device__ __forceinline__ void ks_chunk_body(const ConvParams& P, const ConvGro
     d[i] = wp[sg * 64];
   };
 
-  // ---- slab geometry: one load instruction = vector v16 of rows 4 j + r4; NJ instructions per input stage the unit
-  const int row_len = 32 + (K - 1) * dil;
-  const int nvec = (row_len + 3) >> 2;  // <= 16
+  // ---- slab geometry: one load instruction = vector v16 (of VPR = 16 NT per row) of rows RPI j + r4 (RPI = 4 / NT rows per
+  // instruction); NJ instructions per input stage the unit
+  const int row_len = 32 * NT + (K - 1) * dil;
+  const int nvec = (row_len + 3) >> 2;  // <= VPR
   const int t_base = n0 - G.pad_l + tap_base;
-  const int r4 = lane >> 4, v16 = lane & 15;
+  const int r4 = lane / VPR, v16 = lane % VPR;  // (row of the instruction, vector of the row)
   const int tv = t_base + 4 * v16;
   const int tc0 = tv < 0 ? 0 : tv;
   const int tc = tc0 > P.Tin - 4 ? P.Tin - 4 : tc0;  // clamped (always valid) vector start, Tin >= 4; exact for interior tiles
   const long long rs = (long long)P.x_ch_sign * P.Tin_stride;  // one input channel, in elements (may be < 0)
   const long long ars = rs < 0 ? -rs : rs;
   // lane part as a non-negative byte offset (saddr + 32-bit voffset form): rows run downwards from the biased base when rs < 0
-  const unsigned loff = ((unsigned)((rs < 0 ? 3 - r4 : r4) * ars) + (unsigned)tc) * 4u;
-  const long long ubase = (long long)b * P.x_bstride + (long long)P.x_ch_off * P.Tin_stride + (rs < 0 ? 3 * rs : 0);
+  const unsigned loff = ((unsigned)((rs < 0 ? RPI - 1 - r4 : r4) * ars) + (unsigned)tc) * 4u;
+  const long long ubase = (long long)b * P.x_bstride + (long long)P.x_ch_off * P.Tin_stride + (rs < 0 ? (RPI - 1) * rs : 0);
   const float* xu = G.x + ubase;
   const float* xu2 = G.x2 ? G.x2 + ubase : xu;
   const float* xu3 = G.x3 ? G.x3 + ubase : xu2;  // NIN == 3: x3 may be absent (two ResBlock chains)
@@ -865,8 +881,7 @@ __device__ __forceinline__ void ks_chunk_body(const ConvParams& P, const ConvGro
   const int split_unit = NIN == 2 ? P.x_split / ROWS : 0x7fffffff;  // NIN == 2: channel-concatenated second input
   const float in_scale = P.in_scale, slope = P.in_slope;
   const int refl_t = P.reflect ? ((P.Tin > 1) ? 1 : 0) : -1;
-  float* sl = lds + wave * (16 * KS_SLAB_PITCH);
-  float* sw = sl + r4 * KS_SLAB_PITCH + 4 * v16;
+  float* sw = sl + r4 * PITCH + 4 * v16;
   f32x4 v[NV][NJ];
   auto load_slab = [&](int ui) {
     const int u = wave + NW * ui;
@@ -876,7 +891,7 @@ __device__ __forceinline__ void ks_chunk_body(const ConvParams& P, const ConvGro
 #pragma unroll
     for (int n = 0; n < NV; ++n)
 #pragma unroll
-      for (int j = 0; j < NJ; ++j) v[n][j] = *reinterpret_cast<const f32x4u*>(reinterpret_cast<const char*>(src[n] + 4 * j * rs) + loff);
+      for (int j = 0; j < NJ; ++j) v[n][j] = *reinterpret_cast<const f32x4u*>(reinterpret_cast<const char*>(src[n] + RPI * j * rs) + loff);
   };
   load_slab(0);  // requested ahead of the weights: the wait in front of the first stage() then leaves the weight ring in flight
   __builtin_amdgcn_sched_barrier(0);  // (pins that order)
@@ -905,18 +920,18 @@ __device__ __forceinline__ void ks_chunk_body(const ConvParams& P, const ConvGro
           o[q] = (te >= 0 && te < t_lim) ? fmaxf(e, e * slope) : 0.f;  // select: stale padding may hold NaN
         }
       }
-      *reinterpret_cast<f32x4*>(sw + 4 * j * KS_SLAB_PITCH) = o;
+      *reinterpret_cast<f32x4*>(sw + RPI * j * PITCH) = o;
     }
   };
   // ---- UP K MFMAs on the slab: B fragment of (tap, channel pair p) = rows 2p + h at columns l31 + tap * dil, read one tap ahead
-  const float* bl = sl + h * KS_SLAB_PITCH + l31;
+  const float* bl = sl + h * PITCH + l31;
   auto read_b = [&](float (&d)[UP], int tap) {
 #pragma unroll
-    for (int p = 0; p < UP; ++p) d[p] = bl[2 * p * KS_SLAB_PITCH + tap * dil];
+    for (int p = 0; p < UP; ++p) d[p] = bl[2 * p * PITCH + tap * dil];
   };
   auto mfma4 = [&](const f32x4& w, const float (&d)[UP], int p0) {
 #pragma unroll
-    for (int p = 0; p < 4; ++p) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(w[p], d[p0 + p], acc, 0, 0, 0);
+    for (int p = 0; p < 4; ++p) acc[0] = __builtin_amdgcn_mfma_f32_32x32x2f32(w[p], d[p0 + p], acc[0], 0, 0, 0);
   };
 #pragma unroll 1
   for (int ui = 0; ui < my_units; ++ui) {
@@ -924,8 +939,36 @@ __device__ __forceinline__ void ks_chunk_body(const ConvParams& P, const ConvGro
     if (ui == 0) CONV_DBG(6);  // (timing build: the first slab is staged)
     if (ui + 1 < my_units) load_slab(ui + 1);
     float bb[2][UP];
-    read_b(bb[0], 0);
-    if (KT) {
+    if constexpr (NT == 1) read_b(bb[0], 0);
+    if constexpr (NT == 2) {
+      // a step = the 4 MFMAs of one weight vector on one tile, B read one step ahead into the other tile's four registers:
+      // [second tile's B] | vector (tap, i) on the first tile | [first tile's B of the next vector] | the same vector on the second
+      // tile, then the vector is re-requested for the next unit.  Per accumulator the MFMA sequence is the single tile's.
+      auto read_q = [&](int tile, int tap, int i) {
+#pragma unroll
+        for (int p = 0; p < 4; ++p) bb[tile][p] = bl[2 * (4 * i + p) * PITCH + tap * dil + 32 * tile];
+      };
+      auto mfma_q = [&](const f32x4& w, int tile) {
+#pragma unroll
+        for (int p = 0; p < 4; ++p) acc[tile] = __builtin_amdgcn_mfma_f32_32x32x2f32(w[p], bb[tile][p], acc[tile], 0, 0, 0);
+      };
+      read_q(0, 0, 0);
+#pragma unroll
+      for (int tap = 0; tap < KT; ++tap) {
+#pragma unroll
+        for (int i = 0; i < NA; ++i) {
+          read_q(1, tap, i);
+          __builtin_amdgcn_sched_barrier(0);
+          mfma_q(a[tap][i], 0);
+          if (i + 1 < NA) read_q(0, tap, i + 1);
+          else if (tap + 1 < KT) read_q(0, tap + 1, 0);
+          __builtin_amdgcn_sched_barrier(0);
+          mfma_q(a[tap][i], 1);
+          load_a(a[tap], i, ui + 1, tap);
+          __builtin_amdgcn_sched_barrier(0);
+        }
+      }
+    } else if (KT) {
       // program order pinned per tap (as conv_wp_body): [B of tap + 1] | 4 MFMAs, the slot's next vector, 4 MFMAs, its second |
 #pragma unroll
       for (int tap = 0; tap < (KT ? KT : 1); ++tap) {
@@ -981,21 +1024,71 @@ __global__ void __launch_bounds__(NW * 64) conv_mfma_ks_kernel(const ConvParams 
   if (!conv_decode_block(P, mt, grp, nt, b)) return;
   const ConvGroup& G = P.g[grp];
 
-  const int n0 = nt * N_T, m0 = mt * M_T;
+  bool pairs = false;  // column-pair workgroups (ks_chunk_body, NT = 2): nt counts pairs of column tiles
+  if constexpr (NW == 16 && MI == 1 && NI == 1 && EPI == EPI_STORE) pairs = P.ks_chunk == 2;
+  const int n0 = nt * (pairs ? 2 * N_T : N_T), m0 = mt * M_T;
   const int K = G.K, dil = G.dil;
   int tap_base = 0;
   if (P.ups_u) tap_base = P.ups_shift[m0 / P.ups_cout];
   const int nchunks = P.Cin / CONV_CI_T;
   int t_lim = P.Tin;
+  int n_end = P.Tout;  // columns from here on are nobody's work (pairs: whether the second tile has any)
   if (P.in_mask) { int lb = P.len[b]; t_lim = lb < t_lim ? lb : t_lim; }
   if (P.rag) {
     const int rl = P.rag[b], rc = P.rag[P.B];  // rag[B]: where the padded batch tensor ends (frames): no limit reaches beyond it
-    if (n0 >= conv_rag_limit(rl, rc, P.rag_out_mul, P.rag_out_add, P.rag_out_cap_add)) return;  // whole tile is padding of this item (block-uniform)
+    const int ol = conv_rag_limit(rl, rc, P.rag_out_mul, P.rag_out_add, P.rag_out_cap_add);
+    if (n0 >= ol) return;  // whole tile is padding of this item (block-uniform)
+    n_end = ol < n_end ? ol : n_end;
     const int il = conv_rag_limit(rl, rc, P.rag_in_mul, P.rag_in_add);
     t_lim = il < t_lim ? il : t_lim;
   }
-  if (P.skip_len && n0 >= P.len[b]) return;  // masked stage: the whole tile lies in this item's padding
+  if (P.skip_len) {
+    const int lb = P.len[b];
+    if (n0 >= lb) return;  // masked stage: the whole tile lies in this item's padding
+    n_end = lb < n_end ? lb : n_end;
+  }
   const float in_scale = P.in_scale, in_slope = P.in_slope;
+
+  // ---- column-pair workgroup of the chunk split (4 taps; ks_pair_takes): a path of its own from here to the store, so that nothing
+  // of the tap split is live beside its two accumulators
+  if constexpr (NW == 16 && MI == 1 && NI == 1 && EPI == EPI_STORE) {
+    if (pairs) {  // block-uniform
+      f32x16 part[2];
+#pragma unroll
+      for (int e = 0; e < 16; ++e) part[0][e] = part[1][e] = 0.f;
+      bool whole = false;  // units as in the single tile's path below
+      if constexpr (NIN < 3) whole = nchunks >= NW;
+      // a wave's slab, then its two partial tiles: 8 KB (16 rows of 128 floats).  A pair whose second tile has no column to compute
+      // (odd tile count, or all of it beyond the item's end) runs the single-tile body: no MFMAs and no store for the missing tile
+      const bool two = n0 + N_T < n_end;  // block-uniform
+      float* mine = lds + wave * (2 * 16 * KS_SLAB_PITCH);
+      if (whole) {
+        if constexpr (NIN < 3) {
+          if (two) ks_chunk_body<NIN, 4, 8, 2>(P, G, mine, b, m0, n0, tap_base, t_lim, wave, lane, part);
+          else ks_chunk_body<NIN, 4, 8, 1>(P, G, mine, b, m0, n0, tap_base, t_lim, wave, lane, part);
+        }
+      } else {
+        if (two) ks_chunk_body<NIN, 4, 4, 2>(P, G, mine, b, m0, n0, tap_base, t_lim, wave, lane, part);
+        else ks_chunk_body<NIN, 4, 4, 1>(P, G, mine, b, m0, n0, tap_base, t_lim, wave, lane, part);
+      }
+#pragma unroll
+      for (int e = 0; e < 16; ++e) mine[e * 64 + lane] = part[0][e];
+      if (two) {
+#pragma unroll
+        for (int e = 0; e < 16; ++e) mine[(16 + e) * 64 + lane] = part[1][e];
+      }
+      __syncthreads();
+      // per tile the sum over the waves in the single tile's order, wave w finishing accumulator element e = w
+      const int lenb = P.out_mask ? P.len[b] : 0x7fffffff;
+      for (int tile = 0; tile < (two ? 2 : 1); ++tile) {
+        float sum[1] = {0.f};
+#pragma unroll
+        for (int w = 0; w < NW; ++w) sum[0] += lds[((w * 2 + tile) * 16 + wave) * 64 + lane];
+        conv_epilogue_frag<EPI, 1>(P, G, b, lenb, m0 + 4 * h, wave, n0 + tile * N_T + l31, sum);
+      }
+      return;
+    }
+  }
 
   // lane geometry.  Input addresses are  uniform_base(b, chunk, p)  +  lane_off(h, t)  with the
   // lane part a non-negative 32-bit element offset, so the loads use the SGPR-base + VGPR-offset form.
@@ -1029,16 +1122,17 @@ __global__ void __launch_bounds__(NW * 64) conv_mfma_ks_kernel(const ConvParams 
       // registers (12 vectors per chunk) would not fit beside a chunk's weight ring in the 128 registers of a 16-wave workgroup
       bool whole = false;
       if constexpr (NIN < 3) whole = nchunks >= NW;
+      float* mine = lds + wave * (16 * KS_SLAB_PITCH);  // this wave's slab, then its partial tile
       if (whole) {
         if constexpr (NIN < 3) {
-          if (K == 4) ks_chunk_body<NIN, 4, 8>(P, G, lds, b, m0, n0, tap_base, t_lim, wave, lane, part);
-          else if (K == 7) ks_chunk_body<NIN, 7, 8>(P, G, lds, b, m0, n0, tap_base, t_lim, wave, lane, part);
-          else ks_chunk_body<NIN, 0, 8>(P, G, lds, b, m0, n0, tap_base, t_lim, wave, lane, part);
+          if (K == 4) ks_chunk_body<NIN, 4, 8, 1>(P, G, mine, b, m0, n0, tap_base, t_lim, wave, lane, &part);
+          else if (K == 7) ks_chunk_body<NIN, 7, 8, 1>(P, G, mine, b, m0, n0, tap_base, t_lim, wave, lane, &part);
+          else ks_chunk_body<NIN, 0, 8, 1>(P, G, mine, b, m0, n0, tap_base, t_lim, wave, lane, &part);
         }
       } else {
-        if (K == 4) ks_chunk_body<NIN, 4, 4>(P, G, lds, b, m0, n0, tap_base, t_lim, wave, lane, part);
-        else if (K == 7) ks_chunk_body<NIN, 7, 4>(P, G, lds, b, m0, n0, tap_base, t_lim, wave, lane, part);
-        else ks_chunk_body<NIN, 0, 4>(P, G, lds, b, m0, n0, tap_base, t_lim, wave, lane, part);
+        if (K == 4) ks_chunk_body<NIN, 4, 4, 1>(P, G, mine, b, m0, n0, tap_base, t_lim, wave, lane, &part);
+        else if (K == 7) ks_chunk_body<NIN, 7, 4, 1>(P, G, mine, b, m0, n0, tap_base, t_lim, wave, lane, &part);
+        else ks_chunk_body<NIN, 0, 4, 1>(P, G, mine, b, m0, n0, tap_base, t_lim, wave, lane, &part);
       }
 #pragma unroll
       for (int e = 0; e < 16; ++e) lds[(wave * 16 + e) * 64 + lane] = part[e];  // where the reduction below expects this wave's tile

@@ -17,6 +17,7 @@ struct ConvSelect {
   int env_ks_waves = 0;         // VITS_KS_WAVES: as ks_waves
   int env_wp_mode = 0;          // VITS_CONV_WP: as wp_mode
   int env_ks_chunk = 1;         // VITS_KS_CHUNK: 0 = the 16-wave K-split kernel always splits by tap (A/B of ks_chunk_takes, engine_launch.hip.h)
+  int env_ks_pair = 1;          // VITS_KS_PAIR: column-pair workgroups of the chunk split: 0 = never, 1 = ks_pair_takes, 2 = wherever there are two column tiles (tests)
   int ks_force() const { return ks_waves ? ks_waves : env_ks_waves; }
   int wp() const { return wp_mode ? wp_mode : env_wp_mode; }
   int sp() const { return sp_mode >= 0 ? sp_mode : 1; }
@@ -29,6 +30,7 @@ static ConvSelect conv_select_env() {
   if (const char* v = getenv("VITS_KS_WAVES")) e.env_ks_waves = atoi(v);
   if (const char* v = getenv("VITS_CONV_WP")) e.env_wp_mode = atoi(v);
   if (const char* v = getenv("VITS_KS_CHUNK")) e.env_ks_chunk = atoi(v);
+  e.env_ks_pair = ks_pair_mode_env();  // VITS_KS_PAIR (dec_end_rules.h)
   return e;
 }
 static ConvSelect& conv_select() {  // the calling thread's copy (the vits_debug_* setters write it)

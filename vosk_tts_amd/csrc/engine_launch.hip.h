@@ -124,17 +124,31 @@ static void launch_cfg(vits_session* s, ConvParams& P, const ConvPlan& pl, int h
 static bool ks_chunk_takes(const vits_session* s, const ConvParams& P, const ConvPlan& pl, long nblk) {
   const ConvGroup& G = P.g[0];
   if (!conv_select().env_ks_chunk || pl.NW != 16 || pl.MI != 1 || pl.NI != 1 || pl.epi != EPI_STORE || P.n_groups != 1) return false;
-  if (G.K < 4 || G.dil < 1 || 32 + (G.K - 1) * G.dil > KS_SLAB_PITCH || P.Tin < 4) return false;
   const long cus = s->m->n_cu > 0 ? s->m->n_cu : 256;  // (vits_op_conv1d's scratch model carries no device description)
-  return 4 * nblk <= 5 * cus;
+  return ks_chunk_rule(G.K, G.dil, P.Tin, nblk, cus);  // (the shape part: dec_end_rules.h, asserted by tests/test_dec_end_rules.py)
+}
+// Which chunk-split launches give a workgroup two adjacent column tiles (ks_chunk_body NT = 2, conv_mfma.hip.h): a compile-time tap count,
+// 64 + halo columns inside the pair's slab pitch, no compact tile map (it counts single tiles), and a grid that is more than one round
+// of the chip in single tiles and at most one in pairs -- of the single utterance's four launches, ups[1] (304 -> 160 workgroups;
+// measured: profiles/dec_end_bench.txt).  VITS_KS_PAIR = 2 (tests): wherever there are two column tiles.  Not a planner leaf either.
+static bool ks_pair_takes(const vits_session* s, const ConvParams& P, long nblk) {
+  const ConvGroup& G = P.g[0];
+  const long cus = s->m->n_cu > 0 ? s->m->n_cu : 256;
+  return ks_pair_rule(conv_select().env_ks_pair, G.K, G.dil, P.ntiles_m, P.ntiles_n, P.B, P.tile_start != nullptr, nblk, cus);  // (dec_end_rules.h)
 }
 template <int MI, int NI, int EPI, int NIN>
 static void launch_ks(vits_session* s, ConvParams& P, const ConvPlan& pl) {
-  const dim3 grid(plan_grid(s, P, pl, true));
+  dim3 grid(plan_grid(s, P, pl, true));
   P.row_len = 0;  // no staging window: B fragments come straight from global memory
   P.ks_chunk = ks_chunk_takes(s, P, pl, (long)grid.x) ? 1 : 0;
-  const size_t lds = (size_t)pl.NW * MI * NI * 16 * 64 * sizeof(float);  // cross-wave reduction only
-  static std::atomic<unsigned long long> done16{0};  // (only 16 waves of the 64 x 32 tile go beyond 64 KB)
+  size_t lds = (size_t)pl.NW * MI * NI * 16 * 64 * sizeof(float);  // cross-wave reduction only
+  if (P.ks_chunk && ks_pair_takes(s, P, (long)grid.x)) {  // column tiles in pairs: half the column tiles, two partial tiles per wave
+    P.ks_chunk = 2;
+    P.ntiles_n = cdiv(P.ntiles_n, 2);
+    grid.x = P.ntiles_m * P.ntiles_n * P.B;
+    lds *= 2;
+  }
+  static std::atomic<unsigned long long> done16{0};  // (beyond 64 KB: 16 waves of the 64 x 32 tile, and of the 32 x 32 tile in column pairs; 128 KB both)
   if (pl.NW == 16) launch_big_lds(conv_mfma_ks_kernel<MI, NI, EPI, NIN, 16>, done16, grid, 16 * 64, lds, (int)lds, s->stream, P);
   else if (pl.NW == 8) hipLaunchKernelGGL((conv_mfma_ks_kernel<MI, NI, EPI, NIN, 8>), grid, dim3(8 * 64), lds, s->stream, P);
   else hipLaunchKernelGGL((conv_mfma_ks_kernel<MI, NI, EPI, NIN, 4>), grid, dim3(4 * 64), lds, s->stream, P);

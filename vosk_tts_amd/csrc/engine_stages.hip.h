@@ -551,6 +551,12 @@ static ConvParams dec_sum_conv(const ConvW& W, const float* const in[3], float i
   }
   return P;
 }
+// Which fused tails run the compile-time geometry's body (tail_body, kernels_misc.hip.h): (4, 16, 4, 62) and the single-band N 16 / hop 4.
+// VITS_TAIL_GENERIC=1 (read once): the run-time form for every geometry (A/B runs, tests/test_dec_end_gpu.py).
+static bool tail_fixed_geometry(bool synth, int S, int N, int hop, int taps) {
+  static const bool generic = tail_generic_env();
+  return tail_fixed_rule(generic, synth, S, N, hop, taps);  // (dec_end_rules.h, asserted by tests/test_dec_end_rules.py)
+}
 // cont (with ragged): the reference's padded-batch continuation -- every valid sample equals the dense padded run (the per-layer limits
 // of DecGeom::needs); off, every item is decoded as if it were alone (zeros beyond its own end at every stage), which is what a batch
 // of independent utterances wants (solo batches, the StableTTS path).
@@ -635,7 +641,8 @@ static void run_decoder(vits_session* s, const float* z, bool mask_in, int B, in
   if (!G.has_mb) {  // single band: the iSTFT samples are the waveform
     if (g_tail_impl == 0) {  // one launch: exp/sin and iSTFT through LDS, straight to audio
       ProfScope ps(s, "istft", 0, "istft_tail_kernel<false>");
-      TailParams tp{post, m->istft_basis, nullptr, nullptr, d_audio, 1, N, hop, Tp, Tm, 0, audio_bstride, rag_tail, hop};
+      TailParams tp{post, m->istft_basis, nullptr, nullptr, d_audio, 1, N, hop, Tp, Tm, 0, audio_bstride, rag_tail, hop,
+                    tail_fixed_geometry(false, 1, N, hop, 0) ? 1 : 0};
       hipLaunchKernelGGL(istft_tail_kernel<false>, dim3(cdiv(Tm, TAIL_SB), B), dim3(256), m->tail_lds, s->stream, tp);
     } else {
       ProfScope ps(s, "istft", 0, "istft_kernel");
@@ -644,8 +651,10 @@ static void run_decoder(vits_session* s, const float* z, bool mask_in, int B, in
     }
   } else if (g_tail_impl == 0) {  // one launch: exp/sin, iSTFT and PQMF (dec_type 2: the learned filter) through LDS
     ProfScope ps(s, "istft_pqmf", 0, "istft_tail_kernel<true>");
-    TailParams tp{post, m->istft_basis, m->pqmf, mb, d_audio, S, N, hop, Tp, Tm, hp.pqmf_taps, audio_bstride, rag_tail, hop};  // (rag_tail: conv_post columns that exist)
-    hipLaunchKernelGGL(istft_tail_kernel<true>, dim3(cdiv(Tm, TAIL_MB), B), dim3(256), m->tail_lds, s->stream, tp);
+    const bool fixed = tail_fixed_geometry(true, S, N, hop, hp.pqmf_taps);  // its blocks own TAIL_MB_FIXED sub-band samples
+    TailParams tp{post, m->istft_basis, m->pqmf, mb, d_audio, S, N, hop, Tp, Tm, hp.pqmf_taps, audio_bstride, rag_tail, hop, fixed ? 1 : 0};  // (rag_tail: conv_post columns that exist)
+    const size_t lds = fixed ? tail_lds_bytes_mb(true, S, N, hop, hp.pqmf_taps, TAIL_MB_FIXED) : m->tail_lds;
+    hipLaunchKernelGGL(istft_tail_kernel<true>, dim3(cdiv(Tm, fixed ? TAIL_MB_FIXED : TAIL_MB), B), dim3(256), lds, s->stream, tp);
   } else {
     {
       ProfScope ps(s, "istft", 0, "istft_kernel");

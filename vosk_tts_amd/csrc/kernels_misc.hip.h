@@ -1105,28 +1105,43 @@ __global__ void pqmf_synthesis_kernel(const float* mb, const float* filt, float*
 // kSynth = true: the multi-band (dec_type 0, PQMF filter) and multi-stream (dec_type 2, learned filter) decoders.
 // kSynth = false: the single-band iSTFT decoder (dec_type 3, S = 1): no synthesis stage, a block owns TAIL_SB output samples
 // and step 2 writes them straight to audio (no sub-band / filter arrays in LDS, no halo).
+//
+// The body is tail_body<kSynth, S, N, hop, taps, MB>.  All-zero geometry = every dimension a run-time integer (the form above, any
+// geometry the loader accepts).  The two geometries the shipped voices have -- (4, 16, 4, 62) and the single-band (N 16, hop 4) -- are
+// compiled with their dimensions as constants (P.fixed, chosen by the host: tail_fixed_geometry): no run-time division is left, step 1
+// requests ALL of a thread's `post` values (a compile-time count, clamped addresses, validity by select) behind the basis and filter
+// loads and before the first expf -- one cold round trip instead of one per grid-stride iteration --, the FIR of step 3 is unrolled,
+// and the multi-band block owns TAIL_MB_FIXED = 32 sub-band samples, so that the single utterance's 150 frames make 300 blocks (every
+// CU) instead of 150.  Every output element keeps its sequence of floating-point operations: the two forms are bit-identical
+// (tests/test_dec_end_gpu.py; VITS_TAIL_GENERIC=1 runs the run-time form everywhere).
 #define TAIL_MB 64
 #define TAIL_SB 256
+#define TAIL_MB_FIXED 32  // (64, i.e. 150 blocks: 8.1 us against 7.2 for the single utterance's tail; profiles/dec_end_bench.txt)
 struct TailParams {
   const float* post; const float* basis; const float* filt; float* mb; float* audio;
   int S, N, hop, Tp, Tm, taps;
   long long audio_bstride;
   const int* rag; int rag_mul;  // item b is valid for rag[b]*rag_mul sub-band samples (ragged batches), null = dense
+  int fixed;                    // the compile-time geometry's body (block-uniform; the grid is built for its block ownership)
 };
-// dynamic LDS of istft_tail_kernel<kSynth> in bytes (the same sizes as the kernel's carve-up below)
-__host__ __device__ inline size_t tail_lds_bytes(bool synth, int S, int N, int hop, int taps) {
-  const int HM = synth ? (taps / 2 + S - 1) / S + 1 : 0, nsub = (synth ? TAIL_MB : TAIL_SB) + 2 * HM, FR = (nsub + N) / hop + 2;
+// dynamic LDS of a tail block that owns MB samples, in bytes (the same sizes as the body's carve-up below)
+__host__ __device__ inline size_t tail_lds_bytes_mb(bool synth, int S, int N, int hop, int taps, int MB) {
+  const int HM = synth ? (taps / 2 + S - 1) / S + 1 : 0, nsub = MB + 2 * HM, FR = (nsub + N) / hop + 2;
   return ((size_t)2 * S * (N / 2 + 1) * FR + (synth ? (size_t)S * nsub : 0) + (size_t)(N + 2) * N + (synth ? (size_t)S * (taps + 1) : 0)) *
          sizeof(float);
 }
-template <bool kSynth>
-__global__ void __launch_bounds__(256) istft_tail_kernel(const TailParams P) {
-  extern __shared__ float sm[];
-  kernarg_warm<sizeof(TailParams)>();
-  constexpr int MB = kSynth ? TAIL_MB : TAIL_SB;
+// the run-time form's: what a geometry must fit to be loaded
+__host__ __device__ inline size_t tail_lds_bytes(bool synth, int S, int N, int hop, int taps) {
+  return tail_lds_bytes_mb(synth, S, N, hop, taps, synth ? TAIL_MB : TAIL_SB);
+}
+// S_ = N_ = HOP_ = TAPS_ = 0: run-time geometry from P
+template <bool kSynth, int S_, int N_, int HOP_, int TAPS_, int MB>
+__device__ __forceinline__ void tail_body(const TailParams& P, float* sm) {
+  constexpr bool FIXED = N_ != 0;
   const int tid = threadIdx.x, b = blockIdx.y, m0 = blockIdx.x * MB;
-  const int S = kSynth ? P.S : 1, N = P.N, hop = P.hop, Tp = P.Tp, Tm = P.Tm;
-  const int cut = N / 2 + 1, C = S * (N + 2), L = P.taps + 1, padl = P.taps / 2;
+  const int S = kSynth ? (FIXED ? S_ : P.S) : 1, N = FIXED ? N_ : P.N, hop = FIXED ? HOP_ : P.hop, Tp = P.Tp, Tm = P.Tm;
+  const int taps = FIXED ? TAPS_ : P.taps;
+  const int cut = N / 2 + 1, C = S * (N + 2), L = taps + 1, padl = taps / 2;
   const int HM = kSynth ? (padl + S - 1) / S + 1 : 0;
   const int n_lo = m0 - HM, nsub = MB + 2 * HM;
   const int FR = (nsub + N) / hop + 2;
@@ -1143,24 +1158,70 @@ __global__ void __launch_bounds__(256) istft_tail_kernel(const TailParams P) {
   float* sub = im + S * cut * FR;       // [S][nsub]   (kSynth only)
   float* bas = sub + (kSynth ? S * nsub : 0);  // [(N+2)][N]   windowed inverse basis
   float* flt = bas + (N + 2) * N;       // [S][L]       synthesis filters (kSynth only)
-  for (int i = tid; i < (N + 2) * N; i += 256) bas[i] = P.basis[i];
-  if (kSynth)
-    for (int i = tid; i < S * L; i += 256) flt[i] = P.filt[i];
-  for (int i = tid; i < S * cut * nfr; i += 256) {
-    const int fr = i % nfr, sk = i / nfr, s = sk / cut, k = sk - s * cut;
-    const float* pb = P.post + ((long long)b * C + (long long)s * (N + 2)) * Tp + f_lo + fr;
-    const float mag = expf(pb[(long long)k * Tp]);
-    const float ph = PI_F * sinf(pb[(long long)(cut + k) * Tp]);
-    float sn, cs;
-    sincosf(ph, &sn, &cs);
-    re[sk * FR + fr] = mag * cs;
-    im[sk * FR + fr] = mag * sn;
+  if constexpr (FIXED) {
+    // item i = sk * FR + fr is the LDS index itself; frames beyond nfr (<= FR - 1) are loaded from a clamped address and dropped
+    constexpr int CUT = N_ / 2 + 1, SK = (kSynth ? S_ : 1) * CUT, HMc = kSynth ? (TAPS_ / 2 + S_ - 1) / S_ + 1 : 0;
+    constexpr int FRc = (MB + 2 * HMc + N_) / HOP_ + 2, NIT = (SK * FRc + 255) / 256;
+    constexpr int NBAS = (N_ + 2) * N_, NB = (NBAS + 255) / 256, NFLT = kSynth ? S_ * (TAPS_ + 1) : 1, NF = (NFLT + 255) / 256;
+    float vb[NB], vf[NF], x0[NIT], x1[NIT];
+#pragma unroll
+    for (int n = 0; n < NB; ++n) { const int i = tid + 256 * n; vb[n] = P.basis[i < NBAS ? i : NBAS - 1]; }
+    if (kSynth) {
+#pragma unroll
+      for (int n = 0; n < NF; ++n) { const int i = tid + 256 * n; vf[n] = P.filt[i < NFLT ? i : NFLT - 1]; }
+    }
+    const float* pb0 = P.post + (long long)b * C * Tp + f_lo;
+    const int fr_max = nfr > 0 ? nfr - 1 : 0;
+#pragma unroll
+    for (int n = 0; n < NIT; ++n) {
+      const int i = tid + 256 * n, sk0 = i / FRc, fr0 = i - sk0 * FRc;
+      const int sk = sk0 < SK ? sk0 : SK - 1, s = sk / CUT, k = sk - s * CUT, fr = fr0 < fr_max ? fr0 : fr_max;
+      const float* pb = pb0 + (long long)(s * (N_ + 2) + k) * Tp + fr;
+      x0[n] = pb[0];
+      x1[n] = pb[(long long)CUT * Tp];
+    }
+    __builtin_amdgcn_sched_barrier(0);  // every request is out before the first wait
+#pragma unroll
+    for (int n = 0; n < NB; ++n) { const int i = tid + 256 * n; if (i < NBAS) bas[i] = vb[n]; }
+    if (kSynth) {
+#pragma unroll
+      for (int n = 0; n < NF; ++n) { const int i = tid + 256 * n; if (i < NFLT) flt[i] = vf[n]; }
+    }
+#pragma unroll
+    for (int n = 0; n < NIT; ++n) {
+      const int i = tid + 256 * n, sk0 = i / FRc, fr0 = i - sk0 * FRc;
+      if (sk0 < SK && fr0 < nfr) {
+        const float mag = expf(x0[n]);
+        const float ph = PI_F * sinf(x1[n]);
+        float sn, cs;
+        sincosf(ph, &sn, &cs);
+        re[i] = mag * cs;
+        im[i] = mag * sn;
+      }
+    }
+  } else {
+    for (int i = tid; i < (N + 2) * N; i += 256) bas[i] = P.basis[i];
+    if (kSynth)
+      for (int i = tid; i < S * L; i += 256) flt[i] = P.filt[i];
+    for (int i = tid; i < S * cut * nfr; i += 256) {
+      const int fr = i % nfr, sk = i / nfr, s = sk / cut, k = sk - s * cut;
+      const float* pb = P.post + ((long long)b * C + (long long)s * (N + 2)) * Tp + f_lo + fr;
+      const float mag = expf(pb[(long long)k * Tp]);
+      const float ph = PI_F * sinf(pb[(long long)(cut + k) * Tp]);
+      float sn, cs;
+      sincosf(ph, &sn, &cs);
+      re[sk * FR + fr] = mag * cs;
+      im[sk * FR + fr] = mag * sn;
+    }
   }
   __syncthreads();
   for (int i = tid; i < S * nsub; i += 256) {
     const int s = i / nsub, q = i - s * nsub, n = n_lo + q;
     float a = 0.f;
     if (n >= 0 && n < n_valid) {
+      // both products rounded, then their sum, then the running sum -- what the run-time form compiles to (a packed multiply); pinned
+      // so that the compile-time form, whose unrolled loop would fuse one product into the add, stays bit-identical to it
+#pragma clang fp contract(off)
       const int np = n + N / 2;
       int t_hi = np / hop;
       t_hi = t_hi < f_hi_lim ? t_hi : f_hi_lim;
@@ -1173,7 +1234,7 @@ __global__ void __launch_bounds__(256) istft_tail_kernel(const TailParams P) {
         for (int k = 0; k < cut; ++k) a += rp[k * FR] * bas[k * N + j] + ip[k * FR] * bas[(cut + k) * N + j];
       }
       a *= (float)N / (float)hop;
-      if (kSynth && P.mb && q >= HM && q < HM + TAIL_MB) P.mb[((long long)b * S + s) * Tm + n] = a;
+      if (kSynth && P.mb && q >= HM && q < HM + MB) P.mb[((long long)b * S + s) * Tm + n] = a;
     }
     if (kSynth) sub[i] = a;
     else if (n < Tm) P.audio[(long long)b * P.audio_bstride + n] = a;  // (zeros beyond a ragged item's valid samples)
@@ -1181,24 +1242,53 @@ __global__ void __launch_bounds__(256) istft_tail_kernel(const TailParams P) {
   if (!kSynth) return;
   __syncthreads();
   const int To = Tm * S;
-  for (int r = 0; r * 256 < TAIL_MB * S; ++r) {
+  for (int r = 0; r * 256 < MB * S; ++r) {
     const int o = r * 256 + tid;
     const int t = m0 * S + o;
-    if (o >= TAIL_MB * S || t >= To) continue;
+    if (o >= MB * S || t >= To) continue;
     float a = 0.f;
     if (t < n_valid * S) {
       const int j0 = ((padl - t) % S + S) % S;
-      for (int s = 0; s < S; ++s) {
-        const float* xb = sub + s * nsub - n_lo;
-        for (int j = j0; j < L; j += S) {
-          const int u = t + j - padl;  // a multiple of S by construction of j0
-          const int m = u >= 0 ? u / S : -((-u) / S);
-          a += flt[s * L + j] * (xb[m] * (float)S);
+      if constexpr (FIXED && kSynth) {
+        // the same taps in the same order, j = j0 + i S: all but the last exist for every j0 (j <= (NT - 1) S - 1 < L)
+        constexpr int NT = (TAPS_ + S_) / S_;
+#pragma unroll
+        for (int s = 0; s < S_; ++s) {
+          const float* xb = sub + s * nsub - n_lo;
+#pragma unroll
+          for (int i = 0; i < NT; ++i) {
+            const int j = j0 + i * S_;
+            if (i < NT - 1 || j < L) {
+              const int u = t + j - padl;
+              const int m = u >= 0 ? u / S : -((-u) / S);
+              a = fmaf(flt[s * L + j], xb[m] * (float)S, a);  // (the fusion the run-time form compiles to, pinned for both)
+            }
+          }
+        }
+      } else {
+        for (int s = 0; s < S; ++s) {
+          const float* xb = sub + s * nsub - n_lo;
+          for (int j = j0; j < L; j += S) {
+            const int u = t + j - padl;  // a multiple of S by construction of j0
+            const int m = u >= 0 ? u / S : -((-u) / S);
+            a = fmaf(flt[s * L + j], xb[m] * (float)S, a);
+          }
         }
       }
     }
     P.audio[(long long)b * P.audio_bstride + t] = a;
   }
+}
+template <bool kSynth>
+__global__ void __launch_bounds__(256) istft_tail_kernel(const TailParams P) {
+  extern __shared__ float sm[];
+  kernarg_warm<sizeof(TailParams)>();
+  if (P.fixed) {  // block-uniform
+    if constexpr (kSynth) tail_body<true, 4, 16, 4, 62, TAIL_MB_FIXED>(P, sm);
+    else tail_body<false, 1, 16, 4, 0, TAIL_SB>(P, sm);
+    return;
+  }
+  tail_body<kSynth, 0, 0, 0, 0, kSynth ? TAIL_MB : TAIL_SB>(P, sm);
 }
 
 // plain HiFi-GAN tail: tanh (models.py:889)
