@@ -6,7 +6,7 @@ inputs, for every door that runs a kernel built on it and for the tail end to en
     VITS_MI355_LIB=/path/to/the/other/libvits_mi355.so python tools/stft_identity.py --label parent --out profiles/stft_frames_identity.txt
 
 Doors: vits_op_denoise at the five filter lengths; the pitch doors (shift, stretch, their formant forms, the formant gain) at +3 and -12
-semitones; vits_op_contour / _stretch; vits_op_intonation / _stretch; vits_op_watermark / _detect.  One padded batch of four items of
+semitones; vits_op_contour / _stretch; vits_op_intonation / _stretch; vits_op_watermark / _detect / _payload / _read.  One padded batch of four items of
 400 samples (no frame), 513 (F_s of 2 or 3 at -12), 5000 and 22050; the denoiser's door refuses an item below n/2 + 1 samples, so its
 first item is that long.  End to end, on the tiny voice as float and as int16: plain, 8000 Hz, -23 LUFS, the limiter, pitch, a contour,
 the watermark, a two-item document; and on the toy multistream voice a denoised utterance in one call and streamed.
@@ -27,6 +27,7 @@ sys.path.insert(0, ROOT)
 
 SCALES = np.array([0.667, 1.0, 0.8], np.float32)
 KEY = 0x5EED1234
+PAYLOADS = (0xBEEF, 0x0000, 0xFFFF, 0x1234)  # one per item of the doors' batch
 LOUD = (1, -23.0, 0.0)  # capi.loudness_spec(loudness=-23, peak_ceiling=0)
 LENGTHS = np.array([400, 513, 5000, 22050], np.int64)
 RATE = 22050
@@ -93,6 +94,10 @@ def doors(lib):
     lines.append(f"  op_watermark                                      {sha(y)}")
     lines.append(f"  op_watermark 2 dB                                 {sha(lib.op_watermark(x, LENGTHS, KEY, 2.0))}")
     lines.append(f"  op_watermark_detect                               {sha(*lib.op_watermark_detect(y, LENGTHS, KEY))}")
+    if getattr(lib, "has_watermark_payload", False):  # (include/vits_watermark_payload.h; a build from before it lists the doors above only)
+        yp = lib.op_watermark_payload(x, LENGTHS, KEY, PAYLOADS)
+        lines.append(f"  op_watermark_payload                              {sha(yp)}")
+        lines.append(f"  op_watermark_read                                 {sha(*lib.op_watermark_read(yp, LENGTHS, KEY))}")
     return lines
 
 

@@ -52,7 +52,7 @@ def _layout(name):
 _FIELD_COUNT = {"item_seeds": lambda B, T, D: B, "forced_durations": lambda B, T, D: B * T, "bert": lambda B, T, D: B * D * T,
                 "item_scales": lambda B, T, D: B * 3, "token_length_scale": lambda B, T, D: B * T, "token_pause": lambda B, T, D: B * T,
                 "fit_frames": lambda B, T, D: B, "token_semitones": lambda B, T, D: B * T, "token_gain_db": lambda B, T, D: B * T,
-                "gap_frames": lambda B, T, D: B}
+                "gap_frames": lambda B, T, D: B, "watermark_payloads": lambda B, T, D: B}
 
 
 def _all_fields(cls):
@@ -144,7 +144,7 @@ def _lib(P, bert_dim=0):
     lib.lib = Recorder(bert_dim)
     lib.prefix, lib.path, lib.is_device = "vits_", "<recorder>", True
     for k in ("resample", "denoise", "marks", "loudness", "pitch", "pitch_formant", "limit", "prosody", "contour", "document", "intonation",
-              "watermark"):
+              "watermark", "watermark_payload"):
         setattr(lib, "has_" + k, True)
     return lib
 

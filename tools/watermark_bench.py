@@ -2,7 +2,9 @@
 """What the audio watermark costs per request (include/vits_watermark.h), and that a call without the flag is the call it was: host
 wall time of vits_synthesize_pcm16 for the c2 request (1 x 50 tokens) and the c3 batch (32 ragged utterances, independent items) plain
 and with watermark=KEY, alone and next to a loudness target (where the stage is no longer the last one); and the detector alone through
-vits_op_watermark_detect on 3 s and 60 s of audio.  Synthetic default-size weights.
+vits_op_watermark_detect on 3 s and 60 s of audio.  Where the build has the payload (include/vits_watermark_payload.h): the marked request
+and batch with a payload (the batch: one per item) next to the plain mark, and the reader (vits_op_watermark_read) next to the detector on
+the same 3 s and 60 s.  Synthetic default-size weights.
 Every call ends in the engine's own stream synchronise and the copy to the host, so the clock brackets finished work.  The legs are
 timed in alternation (`--rounds` times `--calls` calls each) so that drift of the machine hits them alike, and the plain leg runs
 twice per round: the difference of its two medians is the spread every other difference has to be read against.  The figure is the
@@ -54,6 +56,8 @@ def call(model, w, leg):
     kw = {}
     if "watermark" in leg:
         kw["watermark"] = KEY
+    if "payload" in leg:  # (one per item: the array of a coalesced batch)
+        kw["watermark_payload"] = 0xBEEF if B == 1 else [(0xBEEF + 257 * b) & 0xFFFF for b in range(B)]
     if "loudness" in leg:
         kw["loudness"] = LOUD
     return model.synthesize_pcm16(w["ids"], w["lens"], SCALES, np.arange(B, dtype=np.int64) % 7, seed=1, solo=w["solo"], **kw)[0]
@@ -125,7 +129,9 @@ def main():
         hp = W.default_hparams()
         model = lib.create(W.synthetic_blob(hp, 1234), 0)
         has = getattr(lib, "has_watermark", False)
-        legs = ["plain", "plain again"] + (["watermark"] if has else []) + ["loudness"] + (["loudness + watermark"] if has else [])
+        has_payload = getattr(lib, "has_watermark_payload", False)
+        legs = (["plain", "plain again"] + (["watermark"] if has else []) + (["watermark + payload"] if has_payload else []) + ["loudness"] +
+                (["loudness + watermark"] if has else []))
         lines = [f"watermark_bench  {head}",
                  f"host wall time per call (ms): median over {args.rounds} rounds of the mean of {args.calls} calls, legs alternated"]
         for name, w in workloads(hp.n_vocab).items():
@@ -159,6 +165,28 @@ def main():
                     per.append((time.perf_counter() - t0) / args.calls * 1e3)
                 lines.append(f"  op_watermark_detect {name:>5}  {statistics.median(per):8.4f} ms  (min {min(per):.4f}, max {max(per):.4f})  "
                              f"z {z[0]:.2f} offset {off[0]} rows {rows[0]}, door with its copies")
+        if has_payload:  # the reader next to the detector, on 3 s and 60 s of the test signal marked with a payload at 2 dB, rounds alternated
+            import watermark_payload_ref as P
+
+            x3 = P.embed(R.voiced_signal(3.0), KEY, 0xBEEF, 2.0).astype(np.float32)
+            for name, x in (("3 s", x3), ("60 s", np.tile(x3[:65536], 21)[:60 * 22050])):
+                doors = {"op_watermark_read": lib.op_watermark_read, "op_watermark_detect": lib.op_watermark_detect}
+                for fn in doors.values():
+                    for _ in range(args.warmup):
+                        fn(x[None], [x.shape[0]], KEY)
+                per = {k: [] for k in doors}
+                for _ in range(args.rounds):
+                    for k, fn in doors.items():
+                        t0 = time.perf_counter()
+                        for _ in range(args.calls):
+                            fn(x[None], [x.shape[0]], KEY)
+                        per[k].append((time.perf_counter() - t0) / args.calls * 1e3)
+                z, off, rows, payload, valid, _, bit_z = lib.op_watermark_read(x[None], [x.shape[0]], KEY)
+                zd = lib.op_watermark_detect(x[None], [x.shape[0]], KEY)[0]
+                for k in doors:
+                    what = (f"z {z[0]:.2f} offset {off[0]} rows {rows[0]} payload {int(payload[0]):#06x} valid {valid[0]} min |z_i| {np.abs(bit_z[0]).min():.2f}"
+                            if k == "op_watermark_read" else f"z {zd[0]:.2f} on the payload mark")
+                    lines.append(f"  {k:>19} {name:>5}  {statistics.median(per[k]):8.4f} ms  (min {min(per[k]):.4f}, max {max(per[k]):.4f})  {what}, door with its copies")
         model.close()
     report = "\n".join(lines)
     print(report)

@@ -66,6 +66,16 @@ def scatter_results(n_requests, shards, shard_outputs):
 BATCHED_FRONT_MIN = 2
 
 
+def tail_part(tail_feed, part):
+    """the tail's feed fragment for the requests `part` of a call: what is one value per call as it is, a per-request
+    "vits.watermark_payload" cut to the part"""
+    feed = dict(tail_feed or {})
+    payload = feed.get("vits.watermark_payload")
+    if isinstance(payload, tuple):
+        feed["vits.watermark_payload"] = [payload[i] for i in part]
+    return feed
+
+
 class MultiDeviceSynth:
     """Batched multi-utterance synthesis over N device replicas in ONE process (BASELINE north_star: "Batched multi-utterance
     synthesis shards across the 8 GPUs of one node as embarrassingly-parallel data replicas"; SURVEY.md 8e: "one host thread
@@ -160,7 +170,7 @@ class MultiDeviceSynth:
             ids, lens = pad_batch(token_lists, part)
             feed = {"input": ids, "input_lengths": lens, **self._scales_feed(scales, part), "sid": np.array([sids[i] for i in part], np.int64),
                     "bert": None, "phone_duration_extra": None, "vits.solo": True,
-                    "vits.item_seeds": np.array([seeds[i] for i in part], np.uint64), **(tail_feed or {})}
+                    "vits.item_seeds": np.array([seeds[i] for i in part], np.uint64), **tail_part(tail_feed, part)}
             with self._replica_locks[r]:  # concurrent synth_batch() calls do not interleave on one replica
                 pcm, lengths, ends = self._pcm16_marks(sess, feed, scale, sample_rate, marks)  # lengths of THIS call (not the shared attribute)
             out.extend(self._item(pcm[j], lengths[j], None if ends is None else ends[j], lens[j]) for j in range(len(part)))
@@ -169,8 +179,10 @@ class MultiDeviceSynth:
     def synth_batch(self, texts, speaker_ids=0, noise_level=None, speech_rate=None, duration_noise_level=None, scale=None, seeds=None,
                     sample_rate=None, denoiser_strength=None, marks=False, loudness=None, peak=None, peak_ceiling=None, pitch=None,
                     preserve_formants=None, limit=None, limit_lookahead_ms=None, limit_release_ms=None, pitch_range=None, watermark=None,
-                    watermark_depth_db=None):
-        """texts: list of str -> list of int16 PCM arrays (22.05 kHz), one per request, in request order.  marks=True: a list of
+                    watermark_depth_db=None, watermark_payload=None):
+        """`watermark_payload`: 16 bits inside the mark (include/vits_watermark_payload.h), one int for the call or one per request: the
+        requests of a shard still share their batches, each item with its own payload.
+        texts: list of str -> list of int16 PCM arrays (22.05 kHz), one per request, in request order.  marks=True: a list of
         (audio, marks.SpeechMarks) per request instead (as Synth.synth_audio(..., marks=True)), through every shard path.  `seeds`: optional
         per-request noise seeds (default: a running counter), `speaker_ids`: one id or one per request.  `noise_level` / `speech_rate` /
         `duration_noise_level`: one value or one per request (VITS-family voices: the requests still share their batches, each with its own
@@ -192,7 +204,10 @@ class MultiDeviceSynth:
         s0._limit(tail_feed, limit, peak_ceiling, limit_lookahead_ms, limit_release_ms)
         s0._pitch(tail_feed, pitch, preserve_formants)
         s0._range(tail_feed, pitch_range)
-        s0._watermark(tail_feed, watermark, watermark_depth_db)
+        per_request = isinstance(watermark_payload, (list, tuple, np.ndarray))
+        if per_request and len(watermark_payload) != len(texts):
+            raise ValueError(f"watermark_payload: {len(watermark_payload)} values for {len(texts)} requests")
+        s0._watermark(tail_feed, watermark, watermark_depth_db, list(watermark_payload) if per_request else watermark_payload)
         dn = {}
         s0._denoiser(dn, denoiser_strength)
         denoiser_strength = dn.get("vits.denoiser_strength")
@@ -309,7 +324,7 @@ class MultiDeviceSynth:
                 f = synth.front_batch([texts[i] for i in part], [sids[i] for i in part])
                 feed = {"input": f["input"], "input_lengths": f["input_lengths"], **self._scales_feed(scales, part), "sid": f["sid"], "bert": f["bert"],
                         "phone_duration_extra": None, "vits.solo": True, "vits.item_seeds": np.array([seeds[i] for i in part], np.uint64),
-                        **(tail_feed or {})}
+                        **tail_part(tail_feed, part)}
                 with self._replica_locks[r]:
                     pcm, lengths, ends = self._pcm16_marks(sess, feed, scale, sample_rate, marks)
                 return [self._item(pcm[b], lengths[b], None if ends is None else ends[b], f["input_lengths"][b]) for b in range(len(part))]
@@ -334,7 +349,7 @@ class MultiDeviceSynth:
                 bert[b, :, :lens[b]] = fronts[k][1]
             feed = {"input": ids, "input_lengths": lens, **self._scales_feed(scales, [idx[k] for k in part]),
                     "sid": np.array([sids[idx[k]] for k in part], np.int64), "bert": bert, "phone_duration_extra": None, "vits.solo": True,
-                    "vits.item_seeds": np.array([seeds[idx[k]] for k in part], np.uint64), **(tail_feed or {})}
+                    "vits.item_seeds": np.array([seeds[idx[k]] for k in part], np.uint64), **tail_part(tail_feed, [idx[k] for k in part])}
             with self._replica_locks[r]:
                 pcm, lengths, ends = self._pcm16_marks(sess, feed, scale, sample_rate, marks)
             for b, k in enumerate(part):
@@ -362,7 +377,8 @@ class MultiDeviceSynth:
                 with self._replica_locks[r]:
                     audio, ol, ends = self._stts_batch(
                         sess, (f["input"], f["input_lengths"], scales, f["sid"], f["bert"], f["phone_duration_extra"]),
-                        dict(seed=0, item_seeds=np.array([seeds[i] for i in part], np.uint64), denoiser_strength=denoiser_strength), sample_rate, marks, tail_feed)
+                        dict(seed=0, item_seeds=np.array([seeds[i] for i in part], np.uint64), denoiser_strength=denoiser_strength), sample_rate, marks,
+                        tail_part(tail_feed, part))
                 pcm = [synth.audio_float_to_int16(audio[b, :int(ol[b])] * scale) for b in range(len(part))]
                 return pcm if ends is None else [(pcm[b], ends[b, :int(f["input_lengths"][b])].copy()) for b in range(len(part))]
 
@@ -392,7 +408,8 @@ class MultiDeviceSynth:
             with self._replica_locks[r]:
                 audio, ol, ends = self._stts_batch(
                     sess, (ids, lens, scales, np.array([sids[idx[k]] for k in part], np.int64), bert, pde),
-                    dict(seed=0, item_seeds=np.array([seeds[idx[k]] for k in part], np.uint64), denoiser_strength=denoiser_strength), sample_rate, marks, tail_feed)
+                    dict(seed=0, item_seeds=np.array([seeds[idx[k]] for k in part], np.uint64), denoiser_strength=denoiser_strength), sample_rate, marks,
+                    tail_part(tail_feed, [idx[k] for k in part]))
             for b, k in enumerate(part):
                 out[k] = synth.audio_float_to_int16(audio[b, :int(ol[b])] * scale)
                 if ends is not None:

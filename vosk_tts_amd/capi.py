@@ -306,11 +306,45 @@ class SynthWatermarkOpts(SynthIntonationOpts):
     _fields_ = WATERMARK_FIELDS
 
 
-def watermark_spec(watermark=None, depth_db=None):
+# include/vits_watermark_payload.h
+FLAG_WATERMARK_PAYLOAD = 512     # VITS_FLAG_WATERMARK_PAYLOAD (STTS_FLAG_WATERMARK_PAYLOAD has the same value)
+WATERMARK_PAYLOAD_MAX = 65535    # VITS_WATERMARK_PAYLOAD_MAX
+WATERMARK_CODED_BITS = 24        # VITS_WATERMARK_CODED_BITS
+WATERMARK_PAYLOAD_FIELDS = [("watermark_payload", ctypes.c_uint32), ("watermark_payloads", ctypes.POINTER(ctypes.c_uint32))]
+PAYLOAD_RIDES = "rides"  # in a session's Tail, in the payload's place: the value rides with the request (it does not decide the batch)
+
+
+class SynthWatermarkPayloadOpts(SynthWatermarkOpts):
+    """mirror of `struct vits_synth_opts_watermark_payload` (include/vits_watermark_payload.h): SynthWatermarkOpts followed by the
+    payload and the per-item payloads, which the library reads only under VITS_FLAG_WATERMARK_PAYLOAD"""
+
+    _fields_ = WATERMARK_PAYLOAD_FIELDS
+
+
+def payload_spec(payload):
+    """watermark_payload= -> None, an int, or a tuple of ints (one per item of a batch); a value outside [0, 65535] is a ValueError
+    naming it, as the library's VITS_ERR_ARG does: here before any device work"""
+    if payload is None:
+        return None
+
+    def one(v):
+        if isinstance(v, (bool, np.bool_)) or not isinstance(v, (int, np.integer)) or not 0 <= int(v) <= WATERMARK_PAYLOAD_MAX:
+            raise ValueError(f"watermark_payload {v!r} outside [0, {WATERMARK_PAYLOAD_MAX}]")
+        return int(v)
+
+    if isinstance(payload, (list, tuple, np.ndarray)):
+        return tuple(one(v) for v in np.asarray(payload).reshape(-1).tolist()) if isinstance(payload, np.ndarray) else tuple(one(v) for v in payload)
+    return one(payload)
+
+
+def watermark_spec(watermark=None, depth_db=None, payload=None):
     """The mark a call asks for -> None (none) or (key, depth_db) as vits_synth_opts_watermark carries it (depth 0 = the default,
-    1 dB).  watermark: the 32-bit key (a selector, not a secret).  ValueError names a key outside [0, 2^32) or a depth outside (0, 2] dB
-    (NaN included), as the library's VITS_ERR_ARG does for the depth: here before any device work."""
+    1 dB), or (key, depth_db, payload) with a payload_spec() (include/vits_watermark_payload.h; depth 0 is then 2 dB).  watermark: the
+    32-bit key (a selector, not a secret).  ValueError names a key outside [0, 2^32), a depth outside (0, 2] dB (NaN included) or a
+    payload outside [0, 65535], as the library's VITS_ERR_ARG does, and a payload without a key: here before any device work."""
     if watermark is None or watermark is False:
+        if payload is not None:
+            raise ValueError("watermark_payload needs watermark=: VITS_FLAG_WATERMARK_PAYLOAD modifies a watermark request")
         return None
     if isinstance(watermark, bool) or not isinstance(watermark, (int, np.integer)):
         raise ValueError(f"watermark={watermark!r}: a key is an integer in [0, 2^32)")
@@ -320,7 +354,14 @@ def watermark_spec(watermark=None, depth_db=None):
     d = 0.0 if depth_db is None else float(depth_db)
     if depth_db is not None and not 0.0 < d <= WATERMARK_MAX_DEPTH_DB:
         raise ValueError(f"watermark_depth_db {d} outside (0, {WATERMARK_MAX_DEPTH_DB:g}]")
+    if payload is not None:
+        return (key, d, payload if payload is PAYLOAD_RIDES else payload_spec(payload))
     return (key, d)
+
+
+def tail_payload(tail):
+    """the payload of a Tail's mark: None, an int, a tuple of ints, or PAYLOAD_RIDES"""
+    return tail.watermark[2] if tail.watermark is not None and len(tail.watermark) > 2 else None
 
 
 def tail_of(loudness=None, limit=None, pitch=None, preserve_formants=False, pitch_range=None, watermark=None):
@@ -336,10 +377,11 @@ class TailFamily:
     """What differs between the two APIs in how a call's options carry the tail; the Python twin of TailFamily in csrc/out_tail.hip.h.
     flags: the flag bit of every stage; chain: the options structs in the order each extends the one before."""
 
-    FIELDS = ("loudness_mode", "pitch_semitones", "limit_mode", "prosody", "contour", "pitch_range", "watermark_key")  # one per stage, in opts()'s order
+    FIELDS = ("loudness_mode", "pitch_semitones", "limit_mode", "prosody", "contour", "pitch_range", "watermark_key",
+              "watermark_payload")  # one per stage, in opts()'s order
 
-    def __init__(self, word, chain, loudness, limit, pitch, formant, contour, intonation, watermark, prosody=0):
-        self.word, self.chain = word, chain
+    def __init__(self, word, chain, loudness, limit, pitch, formant, contour, intonation, watermark, prosody=0, watermark_payload=FLAG_WATERMARK_PAYLOAD):
+        self.word, self.chain, self.watermark_payload = word, chain, watermark_payload
         self.loudness, self.limit, self.pitch, self.formant = loudness, limit, pitch, formant
         self.contour, self.intonation, self.watermark, self.prosody = contour, intonation, watermark, prosody
 
@@ -347,7 +389,7 @@ class TailFamily:
         """the options struct of a call: the first of the chain that has every field asked for (a plain call: the plain struct)"""
         if tail is PLAIN and prosody is None and contour is None:  # (the hot path: not worth a search)
             return self.chain[0]()
-        asked = (tail.loudness, tail.pitch, tail.limit, prosody, contour, tail.pitch_range, tail.watermark)
+        asked = (tail.loudness, tail.pitch, tail.limit, prosody, contour, tail.pitch_range, tail.watermark, tail_payload(tail))
         need = [f for f, v in zip(self.FIELDS, asked) if v is not None]
         return next(c for c in self.chain if all(hasattr(c, f) for f in need))()
 
@@ -379,10 +421,24 @@ class TailFamily:
             opts.pitch_range = tail.pitch_range
         if tail.watermark is not None:
             opts.flags |= self.watermark
-            opts.watermark_key, opts.watermark_depth_db = tail.watermark
+            opts.watermark_key, opts.watermark_depth_db = tail.watermark[:2]
+            payload = tail_payload(tail)
+            if payload is PAYLOAD_RIDES:
+                raise ValueError("a session's Tail reached the options struct with its payload still riding with the request")
+            if isinstance(payload, tuple):  # one per item; it overrides the scalar
+                if len(payload) != B:
+                    raise ValueError(f"watermark_payload: {len(payload)} values for a batch of {B}")
+                a = np.array(payload, np.uint32)
+                keep.append(a)
+                opts.flags |= self.watermark_payload
+                opts.watermark_payloads = a.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32))
+            elif payload is not None:
+                opts.flags |= self.watermark_payload
+                opts.watermark_payload = payload
 
 
-VITS_TAIL = TailFamily("VITS", (SynthOpts, SynthPitchOpts, SynthLimitOpts, SynthProsodyOpts, SynthContourOpts, SynthIntonationOpts, SynthWatermarkOpts),
+VITS_TAIL = TailFamily("VITS", (SynthOpts, SynthPitchOpts, SynthLimitOpts, SynthProsodyOpts, SynthContourOpts, SynthIntonationOpts, SynthWatermarkOpts,
+                                SynthWatermarkPayloadOpts),
                        loudness=FLAG_LOUDNESS, limit=FLAG_LIMIT, pitch=FLAG_PITCH, formant=FLAG_PITCH_FORMANT, contour=FLAG_CONTOUR,
                        intonation=FLAG_INTONATION, watermark=FLAG_WATERMARK, prosody=FLAG_PROSODY)
 
@@ -513,6 +569,7 @@ class VitsLib:
         self.has_document = False
         self.has_intonation = False
         self.has_watermark = False
+        self.has_watermark_payload = False
         if self.is_device:
             c_i16p = ctypes.POINTER(ctypes.c_int16)
             f("synthesize_pcm16").argtypes = [ctypes.c_void_p, c_i64p, c_i64p, ctypes.c_int32, ctypes.c_int32, c_f32p, c_i64p,
@@ -636,6 +693,14 @@ class VitsLib:
                 f("op_watermark").argtypes = [ctypes.c_int, c_f32p, c_i64p, ctypes.c_int32, ctypes.c_int64, ctypes.c_uint32, ctypes.c_float, c_f32p]
                 f("op_watermark_detect").argtypes = [ctypes.c_int, c_f32p, c_i64p, ctypes.c_int32, ctypes.c_int64, ctypes.c_uint32,
                                                      ctypes.POINTER(ctypes.c_double), c_i32p, c_i32p, ctypes.POINTER(ctypes.c_double)]
+            # include/vits_watermark_payload.h: 16 payload bits in the mark (the flag of the synthesize calls and the two doors)
+            self.has_watermark_payload = self.has("op_watermark_payload")
+            if self.has_watermark_payload:
+                c_u32p, c_f64p = ctypes.POINTER(ctypes.c_uint32), ctypes.POINTER(ctypes.c_double)
+                f("op_watermark_payload").argtypes = [ctypes.c_int, c_f32p, c_i64p, ctypes.c_int32, ctypes.c_int64, ctypes.c_uint32, ctypes.c_float,
+                                                      c_u32p, c_f32p]
+                f("op_watermark_read").argtypes = [ctypes.c_int, c_f32p, c_i64p, ctypes.c_int32, ctypes.c_int64, ctypes.c_uint32, c_f64p, c_i32p,
+                                                   c_i32p, c_u32p, c_i32p, c_f64p, c_f64p]
             if self.has("debug_clock_probe"):
                 f("debug_clock_probe").argtypes = [ctypes.c_int, ctypes.c_int32, ctypes.POINTER(ctypes.c_double), ctypes.c_int32]
 
@@ -667,6 +732,8 @@ class VitsLib:
         """every stage `tail` asks for must be one this library exports (VitsError 4 names the first that is not)"""
         if tail.watermark is not None:
             self._need_watermark()
+            if tail_payload(tail) is not None:
+                self._need_watermark_payload()
         if tail.pitch_range is not None:
             self._need_intonation()
         if tail.limit is not None:
@@ -1072,6 +1139,40 @@ class VitsLib:
                                                    _p(off, c_i32p), _p(rows, c_i32p), _p(z_all, c_f64p)))
         return z, off, rows, z_all
 
+    # ---- watermark payload (include/vits_watermark_payload.h) ------------------------
+    def _need_watermark_payload(self):
+        if not self.has_watermark_payload:
+            raise VitsError(4, "this backend has no watermark payload (include/vits_watermark_payload.h)")
+
+    def op_watermark_payload(self, x, lengths, key, payloads, depth_db=0.0, device=0):
+        """vits_op_watermark_payload: op_watermark with one payload in [0, 65535] per item (payloads [B]; depth_db 0 = 2 dB)"""
+        self._need_watermark_payload()
+        pl = np.ascontiguousarray(np.asarray(payloads).reshape(-1), np.uint32)
+        if pl.shape[0] != np.shape(x)[0]:
+            raise ValueError("payloads must be [B]")
+        return self._items_door("op_watermark_payload", x, lengths, device,
+                                (int(key) & 0xFFFFFFFF, float(depth_db), pl.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32))), lambda B, N: [(B, N)])
+
+    def op_watermark_read(self, x, lengths, key, device=0):
+        """vits_op_watermark_read: x float32 [B, N], lengths [B] -> (z float64 [B], offset int32 [B] in samples, rows int32 [B],
+        payload uint32 [B], valid int32 [B], z_all float64 [B, 128], bit_z float64 [B, 24]); detected iff z >= WATERMARK_THRESHOLD, the
+        payload is to be believed iff valid"""
+        self._need_watermark_payload()
+        x = _f32(x)
+        if x.ndim != 2:
+            raise ValueError("x must be [B, N]")
+        B, N = x.shape
+        lengths = _i64(lengths).reshape(-1)
+        if lengths.shape != (B,):
+            raise ValueError("lengths must be [B]")
+        z, z_all, bit_z = np.empty(B, np.float64), np.empty((B, WATERMARK_OFFSETS), np.float64), np.empty((B, WATERMARK_CODED_BITS), np.float64)
+        off, rows, valid, payload = np.empty(B, np.int32), np.empty(B, np.int32), np.empty(B, np.int32), np.empty(B, np.uint32)
+        c_f64p = ctypes.POINTER(ctypes.c_double)
+        self.check(self._fn("op_watermark_read")(device, _p(x, c_f32p), _p(lengths, c_i64p), B, N, int(key) & 0xFFFFFFFF, _p(z, c_f64p),
+                                                 _p(off, c_i32p), _p(rows, c_i32p), payload.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32)),
+                                                 _p(valid, c_i32p), _p(z_all, c_f64p), _p(bit_z, c_f64p)))
+        return z, off, rows, payload, valid, z_all, bit_z
+
     # ---- prosody controls (include/vits_prosody.h) ------------------------------
     def _need_prosody(self):
         if not self.has_prosody:
@@ -1260,8 +1361,10 @@ class VitsModel:
                    max_frames=0, solo=False, item_seeds=None, bert=None, sample_rate=None, marks=False, loudness=None, loudness_out=None,
                    pitch=None, preserve_formants=False, limit=None, item_scales=None, token_length_scale=None, token_pause=None,
                    fit_frames=None, fit_ratio=False, token_pitch=None, token_gain_db=None, pitch_range=None, watermark=None,
-                   watermark_depth_db=None):
-        """watermark: a 32-bit key (VITS_FLAG_WATERMARK, include/vits_watermark.h): every item marked on the device behind the resampler,
+                   watermark_depth_db=None, watermark_payload=None):
+        """watermark_payload: an int in [0, 65535], or one per item (VITS_FLAG_WATERMARK_PAYLOAD, include/vits_watermark_payload.h): the mark
+        carries it, and op_watermark_read returns it; needs watermark=, and watermark_depth_db then defaults to 2.
+        watermark: a 32-bit key (VITS_FLAG_WATERMARK, include/vits_watermark.h): every item marked on the device behind the resampler,
         in front of the loudness stage, the limiter and the int16 conversion; watermark_depth_db in (0, 2], default 1.  Lengths and marks
         do not change.
         pitch_range: r in [0, 4] (VITS_FLAG_INTONATION, include/vits_intonation.h): how far every item moves about its own median pitch,
@@ -1287,15 +1390,15 @@ class VitsModel:
         chain; loudness_out: a dict that receives "loudness" (LUFS of each un-normalised item) and "gain" float32 [B]."""
         return self._call(ids, lengths, scales, sid, False, 1.0, None, sample_rate, marks, fit_ratio, loudness_out,
                           (noise_dp, noise_prior, forced_durations, seed, max_frames, solo, item_seeds, bert),
-                          tail_of(loudness, limit, pitch, preserve_formants, pitch_range, watermark_spec(watermark, watermark_depth_db)),
+                          tail_of(loudness, limit, pitch, preserve_formants, pitch_range, watermark_spec(watermark, watermark_depth_db, watermark_payload)),
                           (item_scales, token_length_scale, token_pause, fit_frames), (token_pitch, token_gain_db))
 
     def synthesize_pcm16(self, ids, lengths, scales, sid, pcm_scale=1.0, noise_dp=None, noise_prior=None, forced_durations=None,
                          seed=0, max_frames=0, solo=False, item_seeds=None, bert=None, sample_rate=None, marks=False, loudness=None,
                          loudness_out=None, pitch=None, preserve_formants=False, limit=None, item_scales=None, token_length_scale=None,
                          token_pause=None, fit_frames=None, fit_ratio=False, token_pitch=None, token_gain_db=None, pitch_range=None,
-                         watermark=None, watermark_depth_db=None):
-        """watermark, watermark_depth_db, pitch, preserve_formants, limit, item_scales, token_length_scale, token_pause, fit_frames, fit_ratio, token_pitch,
+                         watermark=None, watermark_depth_db=None, watermark_payload=None):
+        """watermark, watermark_depth_db, watermark_payload, pitch, preserve_formants, limit, item_scales, token_length_scale, token_pause, fit_frames, fit_ratio, token_pitch,
         token_gain_db, pitch_range: as for synthesize.
         synthesize() with Synth.synth_audio's `* scale` and audio_float_to_int16 (vosk_tts/synth.py:127-130) done on the
         device: returns (pcm int16 [B,S], out_lengths int64 [B]).  sample_rate: as for synthesize (vits_synthesize_pcm16_rate:
@@ -1303,29 +1406,32 @@ class VitsModel:
         normalised audio, as before)."""
         return self._call(ids, lengths, scales, sid, True, pcm_scale, None, sample_rate, marks, fit_ratio, loudness_out,
                           (noise_dp, noise_prior, forced_durations, seed, max_frames, solo, item_seeds, bert),
-                          tail_of(loudness, limit, pitch, preserve_formants, pitch_range, watermark_spec(watermark, watermark_depth_db)),
+                          tail_of(loudness, limit, pitch, preserve_formants, pitch_range, watermark_spec(watermark, watermark_depth_db, watermark_payload)),
                           (item_scales, token_length_scale, token_pause, fit_frames), (token_pitch, token_gain_db))
 
     def synthesize_document(self, ids, lengths, scales, sid, pcm=False, pcm_scale=1.0, lead_frames=0, gap_frames=None, fade_samples=0,
                             trim_db=None, trim_keep_frames=0, marks=False, seed=0, max_frames=0, item_seeds=None, bert=None, sample_rate=None,
                             loudness=None, loudness_out=None, pitch=None, preserve_formants=False, limit=None, item_scales=None,
                             token_length_scale=None, token_pause=None, fit_frames=None, token_pitch=None, token_gain_db=None, pitch_range=None,
-                            forced_durations=None, watermark=None, watermark_depth_db=None):
+                            forced_durations=None, watermark=None, watermark_depth_db=None, watermark_payload=None):
         """vits_synthesize_document / _pcm16 (include/vits_document.h): the B items of one SOLO batch call joined on the device into one
         piece of audio, in front of the resampler, the loudness stage, the limiter and the int16 conversion.  Returns (audio float32 or
         int16 [S], info): info["seg_start"] / ["seg_end"] int64 [B] in output samples, info["trim"] int32 [B, 2] frames, and with
         marks=True info["token_ends"] int64 [B, T_x].  The per-item keywords are those of synthesize; loudness_out receives ONE value per
-        key, of the whole document.  watermark: the document is marked as the one item it has become."""
+        key, of the whole document.  watermark: the document is marked as the one item it has become; watermark_payload: ONE value."""
         self.lib._need_document()
+        if isinstance(watermark_payload, (list, tuple, np.ndarray)):
+            raise ValueError("watermark_payload of a document: one value, it is marked as the one item it has become")
         return self._call(ids, lengths, scales, sid, bool(pcm), pcm_scale, (lead_frames, gap_frames, fade_samples, trim_db, trim_keep_frames),
                           sample_rate, marks, False, loudness_out, (None, None, forced_durations, seed, max_frames, True, item_seeds, bert),
-                          tail_of(loudness, limit, pitch, preserve_formants, pitch_range, watermark_spec(watermark, watermark_depth_db)),
+                          tail_of(loudness, limit, pitch, preserve_formants, pitch_range, watermark_spec(watermark, watermark_depth_db, watermark_payload)),
                           (item_scales, token_length_scale, token_pause, fit_frames), (token_pitch, token_gain_db))
 
     def stream(self, ids, scales, sid, chunk_frames=64, noise_dp=None, noise_prior=None, forced_durations=None, seed=0, bert=None,
                sample_rate=None, on_marks=None, loudness=None, pitch=None, limit=None, item_scales=None, token_length_scale=None,
-               token_pause=None, fit_frames=None, fit_ratio=None, watermark=None):
-        """watermark: refused (vits_stream_open* refuse VITS_FLAG_WATERMARK the same way: a stream has no tail).
+               token_pause=None, fit_frames=None, fit_ratio=None, watermark=None, watermark_payload=None):
+        """watermark_payload: refused, naming VITS_FLAG_WATERMARK_PAYLOAD.
+        watermark: refused (vits_stream_open* refuse VITS_FLAG_WATERMARK the same way: a stream has no tail).
         item_scales [1, 3], token_length_scale [1, T_x], token_pause [1, T_x], fit_frames [1]: the prosody controls of synthesize
         (the open runs the controlled regulator; total_samples and the marks reflect them); fit_ratio: called once with the ratio,
         float32 [1], as soon as the stream is open.
@@ -1338,7 +1444,7 @@ class VitsModel:
         on_marks: called once with token_ends int64 [T_x] (vits_stream_marks, the stream's own output samples) as soon as the
         stream is open, before the first chunk."""
         # (vits_stream_open* refuse the flags the same way; here before any device work)
-        tail_of(loudness, limit, pitch, watermark=watermark_spec(watermark)).refuse_stream(VITS_TAIL.word, None, lambda msg: VitsError(4, msg))
+        tail_of(loudness, limit, pitch, watermark=watermark_spec(watermark, None, watermark_payload)).refuse_stream(VITS_TAIL.word, None, lambda msg: VitsError(4, msg))
         if on_marks is not None:
             self.lib._need_marks()
         if not self.lib.has("stream_open"):

@@ -81,9 +81,21 @@ class SttsWatermarkOpts(SttsIntonationOpts):
     _fields_ = [("watermark_key", ctypes.c_uint32), ("watermark_depth_db", ctypes.c_float)]
 
 
-STTS_TAIL = TailFamily("STTS", (SttsOpts, SttsLoudnessOpts, SttsPitchOpts, SttsLimitOpts, SttsContourOpts, SttsIntonationOpts, SttsWatermarkOpts),
+STTS_FLAG_WATERMARK_PAYLOAD = 512     # include/vits_watermark_payload.h
+
+
+class SttsWatermarkPayloadOpts(SttsWatermarkOpts):
+    """mirror of `struct stts_synth_opts_watermark_payload` (include/vits_watermark_payload.h): SttsWatermarkOpts followed by the payload
+    and the per-item payloads, which the library reads only under STTS_FLAG_WATERMARK_PAYLOAD"""
+
+    _fields_ = [("watermark_payload", ctypes.c_uint32), ("watermark_payloads", ctypes.POINTER(ctypes.c_uint32))]
+
+
+STTS_TAIL = TailFamily("STTS", (SttsOpts, SttsLoudnessOpts, SttsPitchOpts, SttsLimitOpts, SttsContourOpts, SttsIntonationOpts, SttsWatermarkOpts,
+                                SttsWatermarkPayloadOpts),
                        loudness=STTS_FLAG_LOUDNESS, limit=STTS_FLAG_LIMIT, pitch=STTS_FLAG_PITCH, formant=STTS_FLAG_PITCH_FORMANT,
-                       contour=STTS_FLAG_CONTOUR, intonation=STTS_FLAG_INTONATION, watermark=STTS_FLAG_WATERMARK)
+                       contour=STTS_FLAG_CONTOUR, intonation=STTS_FLAG_INTONATION, watermark=STTS_FLAG_WATERMARK,
+                       watermark_payload=STTS_FLAG_WATERMARK_PAYLOAD)
 
 
 class SttsModel:
@@ -185,8 +197,10 @@ class SttsModel:
     def synthesize(self, ids, scales, sid, bert=None, phone_duration_extra=None, noise=None, seed=0, n_timesteps=0,
                    want_audio=True, want_mel=True, denoiser_strength=None, denoiser_filter_length=0, marks=False, sample_rate=None,
                    loudness=None, loudness_out=None, pitch=None, preserve_formants=False, limit=None, token_pitch=None, token_gain_db=None,
-                   pitch_range=None, watermark=None, watermark_depth_db=None):
-        """watermark: a 32-bit key (STTS_FLAG_WATERMARK, include/vits_watermark.h): the audio marked behind the resampler, in front of the
+                   pitch_range=None, watermark=None, watermark_depth_db=None, watermark_payload=None):
+        """watermark_payload: an int in [0, 65535] (STTS_FLAG_WATERMARK_PAYLOAD, include/vits_watermark_payload.h): the mark carries it;
+        needs watermark=, and watermark_depth_db then defaults to 2.
+        watermark: a 32-bit key (STTS_FLAG_WATERMARK, include/vits_watermark.h): the audio marked behind the resampler, in front of the
         loudness stage and the limiter; watermark_depth_db in (0, 2], default 1.
         pitch_range: r in [0, 4] (STTS_FLAG_INTONATION, include/vits_intonation.h): the utterance's movement about its own median pitch
         times r; 1 is the call as it was.
@@ -217,8 +231,8 @@ class SttsModel:
             con = contour_arrays(1, T, None if token_pitch is None else _f32(token_pitch).reshape(1, -1),
                                  None if token_gain_db is None else _f32(token_gain_db).reshape(1, -1), None, pitch_spec(pitch))
         if want_audio:
-            opts = self._opts_for(loudness, pitch, preserve_formants, limit, con, pitch_range, watermark_spec(watermark, watermark_depth_db),
-                                  1, keep, loudness_out)
+            opts = self._opts_for(loudness, pitch, preserve_formants, limit, con, pitch_range,
+                                  watermark_spec(watermark, watermark_depth_db, watermark_payload), 1, keep, loudness_out)
         else:  # (the mel alone: no stage of the tail applies)
             opts = self._opts_for(None, None)
         set_contour(opts, keep, con, STTS_TAIL.contour)
@@ -257,13 +271,14 @@ class SttsModel:
         return (audio, melo, ends) if marks else (audio, melo)
 
     def stream(self, ids, scales, sid, bert=None, phone_duration_extra=None, seed=0, n_timesteps=0, chunk_frames=64,
-               denoiser_strength=None, denoiser_filter_length=0, on_marks=None, loudness=None, pitch=None, limit=None, watermark=None):
-        """pitch, limit, watermark: refused, as loudness is.
+               denoiser_strength=None, denoiser_filter_length=0, on_marks=None, loudness=None, pitch=None, limit=None, watermark=None,
+               watermark_payload=None):
+        """pitch, limit, watermark, watermark_payload: refused, as loudness is.
         Streaming form of synthesize() (stts_stream_open): a generator of float32 chunks of chunk_frames*hop samples whose
         concatenation equals synthesize()'s audio for the same arguments.  on_marks: called once with token_ends int64 [T]
         (vits_stream_marks) as soon as the stream is open.  loudness: refused (stts_stream_open refuses STTS_FLAG_LOUDNESS the same
         way; here before any device work)."""
-        tail_of(loudness, limit, pitch, watermark=watermark_spec(watermark)).refuse_stream(STTS_TAIL.word, None, lambda msg: VitsError(4, msg))
+        tail_of(loudness, limit, pitch, watermark=watermark_spec(watermark, None, watermark_payload)).refuse_stream(STTS_TAIL.word, None, lambda msg: VitsError(4, msg))
         if on_marks is not None:
             self._need_marks()
         if self._vocoder is None:
@@ -298,8 +313,9 @@ class SttsModel:
     def synthesize_batch(self, ids, lengths, scales, sid, bert=None, phone_duration_extra=None, seed=0, n_timesteps=0, item_seeds=None,
                          denoiser_strength=None, denoiser_filter_length=0, marks=False, sample_rate=None, loudness=None, loudness_out=None,
                          pitch=None, preserve_formants=False, limit=None, token_pitch=None, token_gain_db=None, pitch_range=None,
-                         watermark=None, watermark_depth_db=None):
-        """token_pitch / token_gain_db: float [B, T], as for synthesize; pitch_range, watermark: as for synthesize, one value for the batch.
+                         watermark=None, watermark_depth_db=None, watermark_payload=None):
+        """watermark_payload: as for synthesize, or one value per item.
+        token_pitch / token_gain_db: float [B, T], as for synthesize; pitch_range, watermark: as for synthesize, one value for the batch.
         pitch, preserve_formants, limit: as for synthesize, one value for the batch; every item is shifted from its own length.
         B independent utterances in one pass (stts_synthesize_batch): ids [B,5,T], lengths [B], sid [B];
         returns (audio float32 [B,S] zero-padded, out_lengths int64 [B] in samples).  Item b equals
@@ -311,7 +327,7 @@ class SttsModel:
             raise ValueError("sample_rate is an argument of the marks call (SttsSession.resample serves the call without marks)")
         B, T, head, keep = self._batch_head(ids, lengths, scales, sid, bert, phone_duration_extra, seed, n_timesteps, item_seeds, denoiser_strength,
                                             denoiser_filter_length, loudness, loudness_out, pitch, preserve_formants, limit, token_pitch,
-                                            token_gain_db, pitch_range, watermark=watermark_spec(watermark, watermark_depth_db))
+                                            token_gain_db, pitch_range, watermark=watermark_spec(watermark, watermark_depth_db, watermark_payload))
         au = c_f32p(); ns = ctypes.c_int64(); ol = np.zeros(B, np.int64)
         ends = np.zeros((B, T), np.int64) if marks else None
         if marks:
@@ -355,7 +371,7 @@ class SttsModel:
                             denoiser_strength=None, denoiser_filter_length=0, marks=False, sample_rate=None, loudness=None, loudness_out=None,
                             pitch=None, preserve_formants=False, limit=None, token_pitch=None, token_gain_db=None, pitch_range=None,
                             lead_frames=0, gap_frames=None, fade_samples=0, trim_db=None, trim_keep_frames=0, watermark=None,
-                            watermark_depth_db=None):
+                            watermark_depth_db=None, watermark_payload=None):
         """stts_synthesize_document (include/vits_document.h): the items of synthesize_batch joined into one piece of audio behind the
         pitch stage, in front of the resampler and the loudness / limiter stage, which see one item.  Returns (audio float32 [S], info):
         info["seg_start"] / ["seg_end"] int64 [B] in output samples, info["trim"] int32 [B, 2] frames, and with marks=True
@@ -364,9 +380,11 @@ class SttsModel:
 
         if not self.has_document:
             raise VitsError(4, "this backend has no documents (include/vits_document.h)")
+        if isinstance(watermark_payload, (list, tuple, np.ndarray)):
+            raise ValueError("watermark_payload of a document: one value, it is marked as the one item it has become")
         B, T, head, keep = self._batch_head(ids, lengths, scales, sid, bert, phone_duration_extra, seed, n_timesteps, item_seeds, denoiser_strength,
                                             denoiser_filter_length, loudness, loudness_out, pitch, preserve_formants, limit, token_pitch,
-                                            token_gain_db, pitch_range, results=1, watermark=watermark_spec(watermark, watermark_depth_db))
+                                            token_gain_db, pitch_range, results=1, watermark=watermark_spec(watermark, watermark_depth_db, watermark_payload))
         d, dkeep, info = document_struct(B, lead_frames, gap_frames, fade_samples, trim_db, trim_keep_frames)
         au = c_f32p(); ns = ctypes.c_int64()
         ends = np.zeros((B, T), np.int64) if marks else None

@@ -62,6 +62,12 @@ _OPTIONS = (
     (("--detect-watermark",), dict(type=str, default=None, metavar="FILE",
                                    help="instead of synthesising: look for the mark of --watermark KEY (default: the voice's "
                                         "inference.watermark_key) in this 16-bit mono WAV and print detected, z and the offset in samples")),
+    (("--watermark-payload",), dict(type=int, default=None, metavar="N",
+                                    help="with --watermark: carry N, 0 to 65535, inside the mark (2 dB deep by default); --read-watermark returns it")),
+    (("--read-watermark",), dict(type=str, default=None, metavar="FILE",
+                                 help="instead of synthesising: read the mark of --watermark KEY (default: the voice's inference.watermark_key) "
+                                      "in this 16-bit mono WAV and print detected, z, the offset in samples, the payload (null unless valid) "
+                                      "and the weakest coded bit's score")),
     (("--ssml",), dict(action="store_true", help="the input is an SSML document: speak, p, s, sub, break, prosody, mark")),
     (("--document",), dict(action="store_true",
                            help="the input is a document: split into sentences and paragraphs (blank lines), synthesised as one batch and "
@@ -87,18 +93,29 @@ def _key(text):
     return k
 
 
-def detect_watermark(synth, path, key):
-    """--detect-watermark: the triple of Synth.detect_watermark for a 16-bit mono WAV, printed as one JSON line"""
+def _wav_pcm(path, flag):
     import wave
 
     import numpy as np
 
     with wave.open(path, "r") as f:
         if f.getsampwidth() != 2 or f.getnchannels() != 1:
-            raise SystemExit(f"--detect-watermark {path}: a 16-bit mono WAV is expected")
-        pcm = np.frombuffer(f.readframes(f.getnframes()), np.int16)
-    detected, z, offset = synth.detect_watermark(pcm, key)
+            raise SystemExit(f"{flag} {path}: a 16-bit mono WAV is expected")
+        return np.frombuffer(f.readframes(f.getnframes()), np.int16)
+
+
+def detect_watermark(synth, path, key):
+    """--detect-watermark: the triple of Synth.detect_watermark for a 16-bit mono WAV, printed as one JSON line"""
+    detected, z, offset = synth.detect_watermark(_wav_pcm(path, "--detect-watermark"), key)
     print(json.dumps({"detected": detected, "z": round(z, 3), "offset_samples": offset}))
+    return 0
+
+
+def read_watermark(synth, path, key):
+    """--read-watermark: Synth.read_watermark for a 16-bit mono WAV, printed as one JSON line"""
+    detected, z, offset, payload, bit_z = synth.read_watermark(_wav_pcm(path, "--read-watermark"), key)
+    print(json.dumps({"detected": detected, "z": round(z, 3), "offset_samples": offset, "payload": payload,
+                      "min_abs_bit_z": round(float(abs(bit_z).min()), 3)}))
     return 0
 
 
@@ -132,7 +149,10 @@ def run(opts):
             action()
             return 0
     detect = getattr(opts, "detect_watermark", None)
-    if not opts.input and not detect:
+    read = getattr(opts, "read_watermark", None)
+    if getattr(opts, "watermark_payload", None) is not None and getattr(opts, "watermark", None) is None:
+        raise SystemExit("--watermark-payload needs --watermark KEY")
+    if not opts.input and not detect and not read:
         logging.info("Please specify input text or file")
         return 1
     from .synth import Synth
@@ -141,7 +161,11 @@ def run(opts):
     synth = Synth(voice)
     if detect:
         return detect_watermark(synth, detect, getattr(opts, "watermark", None))
+    if read:
+        return read_watermark(synth, read, getattr(opts, "watermark", None))
     wm = {} if getattr(opts, "watermark", None) is None else {"watermark": opts.watermark}
+    if getattr(opts, "watermark_payload", None) is not None:
+        wm["watermark_payload"] = opts.watermark_payload
     if getattr(opts, "document", False):  # many sentences in one call (Synth.synth_document); the per-word flags index one utterance
         import wave
 

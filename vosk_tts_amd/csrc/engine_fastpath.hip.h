@@ -640,7 +640,7 @@ static int synth_dispatch(vits_model* m, const int64_t* ids, const int64_t* leng
   for (int b = 0; b < B; ++b) if (lengths[b] < 0 || lengths[b] > Tx) return fail(VITS_ERR_ARG, "length out of range");
   TailReq q;  // (out_tail.hip.h: the rate, the loudness target, the limiter and the shift, checked before anything is queued)
   const TailFields tf = tail_fields_vits(opts);
-  TRY(tail_req(m, tf, sample_rate, pcm, pcm_scale, &q));
+  TRY(tail_req(m, tf, sample_rate, pcm, pcm_scale, B, &q));
   TRY(tail_contour_req(m, tf, lengths, B, Tx, &q));
   if (doc) q.doc = *doc;
   static const bool env_off = getenv("VITS_NO_FASTPATH") != nullptr;

@@ -7,11 +7,11 @@
 
 // ---- the request ----------------------------------------------------------------------------------------------------------
 // The flag bits and the name of an API family: the two families number the same four flags differently.
-struct TailFamily { const char* name; uint32_t loudness, limit, pitch, formant, contour, intonation, watermark; };
+struct TailFamily { const char* name; uint32_t loudness, limit, pitch, formant, contour, intonation, watermark, watermark_payload; };
 static const TailFamily TAIL_VITS = {"VITS", VITS_FLAG_LOUDNESS, VITS_FLAG_LIMIT, VITS_FLAG_PITCH, VITS_FLAG_PITCH_FORMANT, VITS_FLAG_CONTOUR,
-                                     VITS_FLAG_INTONATION, VITS_FLAG_WATERMARK};
+                                     VITS_FLAG_INTONATION, VITS_FLAG_WATERMARK, VITS_FLAG_WATERMARK_PAYLOAD};
 static const TailFamily TAIL_STTS = {"STTS", STTS_FLAG_LOUDNESS, STTS_FLAG_LIMIT, STTS_FLAG_PITCH, STTS_FLAG_PITCH_FORMANT, STTS_FLAG_CONTOUR,
-                                     STTS_FLAG_INTONATION, STTS_FLAG_WATERMARK};
+                                     STTS_FLAG_INTONATION, STTS_FLAG_WATERMARK, STTS_FLAG_WATERMARK_PAYLOAD};
 
 // The values behind the flags of a call, flat.  A group is meaningful only where its `on` is set (`formant` is the bare flag bit).
 struct TailFields {
@@ -33,11 +33,14 @@ struct TailFields {
   bool wm_on = false;
   uint32_t wm_key = 0;
   float wm_depth_db = 0.f;
+  bool wm_payload_on = false;  // (include/vits_watermark_payload.h; the bare flag bit: without wm_on it is refused by tail_req)
+  uint32_t wm_payload = 0;
+  const uint32_t* wm_payloads = nullptr;  // null or one per item of the call
 };
 
 // The only two places that cast down the `base` chain of the extended option structs: a struct's own fields are read under its flag
 // alone, so a caller who sets no flag may pass the plain struct (include/vits_loudness.h, vits_pitch.h, vits_limit.h).
-template <typename Pitch, typename Limit, typename Contour, typename Inton, typename Wm, typename Loud, typename Opts>
+template <typename Pitch, typename Limit, typename Contour, typename Inton, typename Wm, typename WmP, typename Loud, typename Opts>
 static TailFields tail_fields(const TailFamily& fam, const Opts* opts, const Loud* lo) {
   TailFields f;
   f.family = fam.name;
@@ -63,22 +66,29 @@ static TailFields tail_fields(const TailFamily& fam, const Opts* opts, const Lou
     const Wm* wo = reinterpret_cast<const Wm*>(opts);
     f.wm_key = wo->watermark_key; f.wm_depth_db = wo->watermark_depth_db;
   }
+  f.wm_payload_on = (fl & fam.watermark_payload) != 0;
+  if (f.wm_payload_on) {
+    const WmP* po = reinterpret_cast<const WmP*>(opts);
+    f.wm_payload = po->watermark_payload; f.wm_payloads = po->watermark_payloads;
+  }
   return f;
 }
 static TailFields tail_fields_vits(const vits_synth_opts* opts) {  // (the loudness fields are the plain struct's own)
   static_assert(offsetof(vits_synth_opts_limit, base) == 0 && offsetof(vits_synth_opts_pitch, base) == 0 && offsetof(vits_synth_opts_prosody, base) == 0 &&
                     offsetof(vits_synth_opts_contour, base) == 0 && offsetof(vits_synth_opts_intonation, base) == 0 &&
-                    offsetof(vits_synth_opts_watermark, base) == 0,
+                    offsetof(vits_synth_opts_watermark, base) == 0 && offsetof(vits_synth_opts_watermark_payload, base) == 0,
                 "the extended options begin with the plain ones");
-  return tail_fields<vits_synth_opts_pitch, vits_synth_opts_limit, vits_synth_opts_contour, vits_synth_opts_intonation, vits_synth_opts_watermark>(
+  return tail_fields<vits_synth_opts_pitch, vits_synth_opts_limit, vits_synth_opts_contour, vits_synth_opts_intonation, vits_synth_opts_watermark,
+                     vits_synth_opts_watermark_payload>(
       TAIL_VITS, opts, opts);
 }
 static TailFields tail_fields_stts(const stts_synth_opts* opts) {
   static_assert(offsetof(stts_synth_opts_limit, base) == 0 && offsetof(stts_synth_opts_pitch, base) == 0 && offsetof(stts_synth_opts_loudness, base) == 0 &&
                     offsetof(stts_synth_opts_contour, base) == 0 && offsetof(stts_synth_opts_intonation, base) == 0 &&
-                    offsetof(stts_synth_opts_watermark, base) == 0,
+                    offsetof(stts_synth_opts_watermark, base) == 0 && offsetof(stts_synth_opts_watermark_payload, base) == 0,
                 "the extended options begin with the plain ones");
-  return tail_fields<stts_synth_opts_pitch, stts_synth_opts_limit, stts_synth_opts_contour, stts_synth_opts_intonation, stts_synth_opts_watermark>(
+  return tail_fields<stts_synth_opts_pitch, stts_synth_opts_limit, stts_synth_opts_contour, stts_synth_opts_intonation, stts_synth_opts_watermark,
+                     stts_synth_opts_watermark_payload>(
       TAIL_STTS, opts, reinterpret_cast<const stts_synth_opts_loudness*>(opts));
 }
 
@@ -102,6 +112,8 @@ static int tail_refuse_stream(uint32_t flags, const TailFamily& fam) {
     return fail(VITS_ERR_UNSUPPORTED, "%s_FLAG_CONTOUR on a stream: the position recurrence and the phase recursion need the whole utterance before the first chunk", fam.name);
   if (flags & fam.intonation)
     return fail(VITS_ERR_UNSUPPORTED, "%s_FLAG_INTONATION on a stream: the median of the F0 track needs the whole utterance before the first chunk", fam.name);
+  if (flags & fam.watermark_payload)
+    return fail(VITS_ERR_UNSUPPORTED, "%s_FLAG_WATERMARK_PAYLOAD on a stream: the mark is a stage of the output tail, and a stream has none (include/vits_watermark_payload.h)", fam.name);
   if (flags & fam.watermark)
     return fail(VITS_ERR_UNSUPPORTED, "%s_FLAG_WATERMARK on a stream: the mark is a stage of the output tail, and a stream has none (include/vits_watermark.h)", fam.name);
   return VITS_OK;
@@ -125,7 +137,8 @@ struct TailReq {
 
 // Checked before anything is synthesised, so a refusal costs nothing: the rate, the loudness target, the limiter, the shift.  `vocoder`
 // is null for a multistream model without one: its entry point has resolved the rate (stts_marks_arg) and any stage asked for is refused.
-static int tail_req(const vits_model* vocoder, const TailFields& f, int32_t sample_rate, bool pcm, float pcm_scale, TailReq* out) {
+// B: the items of the call (what a per-item payload array is read with).
+static int tail_req(const vits_model* vocoder, const TailFields& f, int32_t sample_rate, bool pcm, float pcm_scale, int B, TailReq* out) {
   *out = TailReq();
   out->pcm = pcm; out->pcm_scale = pcm_scale;
   if (vocoder) TRY(resample_rate_arg(vocoder, sample_rate, &out->rate));
@@ -137,7 +150,10 @@ static int tail_req(const vits_model* vocoder, const TailFields& f, int32_t samp
               out->norm.loud.on ? f.loud_ceiling : 0.f, &out->norm));
   TRY(tail_formant_check(f.formant, f.pitch_on, f.family));
   if (f.wm_on && !vocoder) return fail(VITS_ERR_ARG, "no vocoder attached");
-  TRY(wm_req(f.wm_on, f.wm_key, f.wm_depth_db, &out->wm));
+  if (f.wm_payload_on && !f.wm_on)
+    return fail(VITS_ERR_ARG, "%s_FLAG_WATERMARK_PAYLOAD without %s_FLAG_WATERMARK: the flag modifies a watermark request (include/vits_watermark_payload.h)",
+                f.family, f.family);
+  TRY(wm_req(f.wm_on, f.wm_key, f.wm_depth_db, &out->wm, f.wm_payload_on, f.wm_payload, f.wm_payloads, B));
   if (!f.pitch_on) return VITS_OK;
   if (!vocoder) return fail(VITS_ERR_ARG, "no vocoder attached");
   return pitch_req(vocoder, f.semitones, f.formant, &out->pitch);
@@ -244,11 +260,17 @@ static int tail_run(Alloc&& alloc, vits_session* s, hipStream_t stream, const fl
     float* d_scr = static_cast<float*>(alloc(sizeof(float) * (size_t)B * sc));
     void* d_w = alloc((wp ? sizeof(int16_t) : sizeof(float)) * (size_t)B * So);
     if (!d_scr || !d_w) return fail(VITS_ERR_NOMEM, "device alloc failed");
+    uint32_t* d_words = nullptr;
+    if (q.wm.payload) {  // (include/vits_watermark_payload.h: the words of THIS call go up in front of its launch; B is 1 behind a join)
+      d_words = static_cast<uint32_t*>(alloc(sizeof(uint32_t) * (size_t)B));
+      if (!d_words) return fail(VITS_ERR_NOMEM, "device alloc failed");
+      HIP_TRY(hipMemcpyAsync(d_words, q.wm.host_words(q.doc.on), sizeof(uint32_t) * (size_t)B, hipMemcpyHostToDevice, stream));
+    }
     const int wL = T ? T->P.L : 1, wM = T ? T->P.M : 1;
     {
       ProfScope ps(s, "out.watermark", 0, wp ? "wm_frames_kernel + wm_ola_kernel<int16>" : "wm_frames_kernel + wm_ola_kernel<float>");
-      if (wp) wm_launch<int16_t>(stream, q.wm, x, So, So, len_y, hop, wL, wM, B, d_scr, (long long)sc, static_cast<int16_t*>(d_w), So, So, q.pcm_scale);
-      else wm_launch<float>(stream, q.wm, x, So, So, len_y, hop, wL, wM, B, d_scr, (long long)sc, static_cast<float*>(d_w), So, So, 1.f);
+      if (wp) wm_launch<int16_t>(stream, q.wm, x, So, So, len_y, hop, wL, wM, B, d_scr, (long long)sc, static_cast<int16_t*>(d_w), So, So, q.pcm_scale, d_words);
+      else wm_launch<float>(stream, q.wm, x, So, So, len_y, hop, wL, wM, B, d_scr, (long long)sc, static_cast<float*>(d_w), So, So, 1.f, d_words);
     }
     *d_out = d_w;
     if (!q.norm.on()) return VITS_OK;

@@ -1111,7 +1111,7 @@ static int stts_tail_host(stts_model* m, const TailReq& q, int B, float** audio,
   }
   if (q.wm.on && *S > 0) {  // (the kernels of vits_op_watermark, at the rate the audio is returned at)
     std::vector<float> y((size_t)B * *S);
-    TRY(wm_op(device, *audio, lengths, B, *S, q.wm, y.data()));
+    TRY(wm_op(device, *audio, lengths, B, *S, q.wm, y.data(), q.wm.host_words(q.doc.on)));
     memcpy(*audio, y.data(), sizeof(float) * y.size());
   }
   if (q.norm.on()) {
@@ -1139,7 +1139,7 @@ static int stts_synthesize_tail(stts_model* m, const int64_t* ids, int32_t Tx, c
   const int64_t tl = Tx;
   if (out_audio) {
     const TailFields tf = tail_fields_stts(opts);
-    TRY(tail_req(m->vocoder, tf, rate, false, 1.f, &q));
+    TRY(tail_req(m->vocoder, tf, rate, false, 1.f, 1, &q));
     if (Tx > 0) TRY(tail_contour_req(m->vocoder, tf, &tl, 1, Tx, &q));
   }
   std::vector<int> cum(q.contour.on ? Tx : 0);
@@ -1319,7 +1319,7 @@ static int stts_synthesize_batch_tail(stts_model* m, const int64_t* ids, const i
                                       const DocReq* doc = nullptr) {
   TailReq q;
   const TailFields tf = tail_fields_stts(opts);
-  TRY(tail_req(m->vocoder, tf, rate, false, 1.f, &q));
+  TRY(tail_req(m->vocoder, tf, rate, false, 1.f, B, &q));
   if (doc) {
     if (!m->vocoder) return fail(VITS_ERR_ARG, "no vocoder attached");
     q.doc = *doc;

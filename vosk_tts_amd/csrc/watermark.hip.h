@@ -16,9 +16,17 @@
 // of an 8-byte read once each, and the 96-wide rows need no padding BECAUSE the mapping is linear in id (lanes walking down a column
 // of [16][96] doubles would all meet on one bank pair).  The band magnitudes of wm_lb_kernel are read four in a row per lane (stride 4
 // dwords, 4 lanes to a bank): 384 reads per frame next to the FFT's 9 passes, left as it is.
+// The payload (include/vits_watermark_payload.h) is a template parameter of two of these kernels and one kernel more:
+//   wm_frames_kernel<true>   the chip of a payload position flipped by its coded bit of the item's word (words[blockIdx.y])
+//   wm_score_kernel<true>    the two sums over the pilot positions only
+//   wm_bits_kernel           one workgroup per item at the offset wm_argmax_kernel chose (read on the device): G again by the shared row
+//                            loop (wm_rows_G), c G and G^2 of every position to LDS at the thread's linear id 96 q + j -- the layout argued
+//                            above, T's own plane and one more, 2 x 1536 doubles = 24 KiB -- then 24 threads sum their bit's positions in
+//                            ascending id (all 24 lanes read the same address: a broadcast), one thread packs the word and checks the CRC
+// The <false> forms are the kernels as they were.
 // Nothing waits between workgroups; there are no atomics.
 #pragma once
-#include "../../include/vits_watermark.h"
+#include "../../include/vits_watermark_payload.h"
 
 #define WM_N VITS_WATERMARK_FRAME
 #define WM_M (WM_N / 2)
@@ -39,19 +47,47 @@ __host__ __device__ __forceinline__ uint32_t wm_mix(uint32_t x) {
 }
 // the chip of tile row q, group j under mk = wm_mix(key): true = +1
 __host__ __device__ __forceinline__ bool wm_chip(uint32_t mk, int q, int j) { return (wm_mix(mk ^ (uint32_t)(WM_G * q + j + 1)) & 1u) != 0; }
-// the gain of bin k in a frame of tile row q: gp = fp32(1 + a), gm = fp32(1 - a)
-__device__ __forceinline__ float wm_bin_gain(uint32_t mk, int q, int k, float gp, float gm) {
+// include/vits_watermark_payload.h: crc8 over the 16 payload bits MSB first (polynomial 0x07, initial value 0xFF, no final xor) ...
+__host__ __device__ __forceinline__ uint32_t wm_crc8(uint32_t p) {
+  uint32_t c = 0xFFu;
+  for (int i = 15; i >= 0; --i) {
+    const uint32_t fb = ((c >> 7) ^ (p >> i)) & 1u;
+    c = (c << 1) & 0xFFu;
+    if (fb) c ^= 0x07u;
+  }
+  return c;
+}
+// ... the coded word of a payload ...
+__host__ __device__ __forceinline__ uint32_t wm_word(uint32_t p) { return (p << 8) | wm_crc8(p); }
+// ... a pilot position, and the coded bit a payload position carries
+__host__ __device__ __forceinline__ bool wm_pilot(int q, int j) { return ((q + j) & 1) != 0; }
+__host__ __device__ __forceinline__ int wm_bit_index(uint32_t mk, int q, int j) {
+  return (int)(wm_mix(mk ^ (0x80000000u | (uint32_t)(WM_G * q + j + 1))) % VITS_WATERMARK_CODED_BITS);
+}
+// c'(q, j) under the coded word: the chip, flipped on a payload position whose bit is set
+__host__ __device__ __forceinline__ bool wm_chip_word(uint32_t mk, int q, int j, uint32_t word) {
+  bool c = wm_chip(mk, q, j);
+  if (!wm_pilot(q, j) && ((word >> (VITS_WATERMARK_CODED_BITS - 1 - wm_bit_index(mk, q, j))) & 1u)) c = !c;
+  return c;
+}
+// the gain of bin k in a frame of tile row q: gp = fp32(1 + a), gm = fp32(1 - a); PAYLOAD: under the item's coded word
+template <bool PAYLOAD>
+__device__ __forceinline__ float wm_bin_gain(uint32_t mk, int q, int k, float gp, float gm, uint32_t word) {
   if (k < WM_LO || k >= WM_HI) return 1.f;
-  return wm_chip(mk, q, (k - WM_LO) >> 2) ? gp : gm;
+  if constexpr (PAYLOAD) return wm_chip_word(mk, q, (k - WM_LO) >> 2, word) ? gp : gm;
+  else return wm_chip(mk, q, (k - WM_LO) >> 2) ? gp : gm;
 }
 
 // The marked, windowed frames of every item: wave w of workgroup blockIdx.x owns frame f = blockIdx.x * SF_FPB + w.
 //   x      item b at x + b * x_bstride, samples [0, len), len = ld_len(..) (loudness.hip.h: the item as returned, at most N)
 //   out    out[b * out_bstride + f * n + i]; an item shorter than n/2 + 1 has no frames (wm_ola_kernel passes it through)
+//   words  PAYLOAD: the coded word of item b at words[b]; not read otherwise
+template <bool PAYLOAD>
 __global__ __launch_bounds__(64 * SF_FPB) void wm_frames_kernel(const float* __restrict__ x, long long x_bstride, long long N,
                                                                 const int* __restrict__ len_frames, long long len_mul, int L, int Mr,
                                                                 const float* __restrict__ win, const float2* __restrict__ tw, uint32_t mk,
-                                                                float gp, float gm, float* __restrict__ out, long long out_bstride) {
+                                                                float gp, float gm, float* __restrict__ out, long long out_bstride,
+                                                                const uint32_t* __restrict__ words) {
   __shared__ float lds[SF_FPB][4][SF_PLANE];
   const int wv = threadIdx.x >> 6, t = threadIdx.x & 63;
   const int b = blockIdx.y;
@@ -66,9 +102,11 @@ __global__ __launch_bounds__(64 * SF_FPB) void wm_frames_kernel(const float* __r
   __syncthreads();
   sf_fft(ar, ai, br, bi, WM_M, WM_LOG2M, tw, t);
   const int q = (int)((f >> 2) & (WM_Q - 1));
+  uint32_t word = 0;
+  if constexpr (PAYLOAD) word = words[b];
   for (int k = t; k <= (WM_M >> 1); k += 64) {  // unpack, the chip's gain, pack
     SfBins X = sf_unpack(ar, ai, tw, WM_M, k);
-    const float gk = wm_bin_gain(mk, q, k, gp, gm), gq = wm_bin_gain(mk, q, WM_M - k, gp, gm);
+    const float gk = wm_bin_gain<PAYLOAD>(mk, q, k, gp, gm, word), gq = wm_bin_gain<PAYLOAD>(mk, q, WM_M - k, gp, gm, word);
     X.kr *= gk; X.ki *= gk; X.pr *= gq; X.pi *= gq;
     sf_pack(br, bi, tw, WM_M, k, X.kr, X.ki, X.pr, X.pi);
   }
@@ -158,48 +196,62 @@ __global__ __launch_bounds__(64 * SF_FPB) void wm_lb_kernel(const float* __restr
   }
 }
 
-// z_all[b * 128 + o] and rows_all[b * 128 + o] of offset index o = blockIdx.x of item b = blockIdx.y, from Lb.
-__global__ __launch_bounds__(WM_SCORE_THREADS) void wm_score_kernel(const float* __restrict__ Lb, long long lb_bstride,
-                                                                   const int* __restrict__ lens, uint32_t mk, double* __restrict__ z_all,
-                                                                   int* __restrict__ rows_all) {
-  constexpr int PER = WM_Q * WM_G / WM_SCORE_THREADS;  // (q, j) pairs per thread: 6
-  __shared__ double T[WM_Q * WM_G];
-  __shared__ double red[2][WM_SCORE_THREADS];
-  const int o = blockIdx.x, b = blockIdx.y, tid = threadIdx.x;
-  const long long len = lens[b];
+constexpr int WM_PER = WM_Q * WM_G / WM_SCORE_THREADS;  // (q, j) pairs per thread: 6, at the linear ids tid + i * WM_SCORE_THREADS
+// the complete rows [r0, r1] of offset index o of an item of F hop-128 frames, and where its pattern starts
+struct WmRows { int g0; long long pbase, r0, r1, rows; };
+__device__ __forceinline__ WmRows wm_rows_of(long long len, int o) {
+  WmRows R;
   const long long F = len >= WM_M + 1 ? 1 + len / WM_DH : 0;
-  const int g0 = o & 1;
-  const long long pbase = (o + g0) >> 1;
-  const long long nf = F > g0 ? (F - g0 + 1) / 2 : 0;             // frames g = g0 + 2 f < F
-  const long long r0 = (pbase + 3) >> 2, r1 = ((pbase + nf) >> 2) - 1;  // the complete rows, inclusive
-  const long long rows = r1 >= r0 ? r1 - r0 + 1 : 0;
-  const float* lb = Lb + (long long)b * lb_bstride;
-  double G[PER];
-  for (int i = 0; i < PER; ++i) G[i] = 0.0;
-  for (long long c = r0; c <= r1; c += WM_Q) {  // rows c .. c + 15: every q once (uniform trip count)
-    bool live[PER];
-    for (int i = 0; i < PER; ++i) {
+  R.g0 = o & 1;
+  R.pbase = (o + R.g0) >> 1;
+  const long long nf = F > R.g0 ? (F - R.g0 + 1) / 2 : 0;  // frames g = g0 + 2 f < F
+  R.r0 = (R.pbase + 3) >> 2; R.r1 = ((R.pbase + nf) >> 2) - 1;  // inclusive
+  R.rows = R.r1 >= R.r0 ? R.r1 - R.r0 + 1 : 0;
+  return R;
+}
+// G of the thread's six (q, j) over the complete rows, 16 tile rows at a time: T of a row of every q in LDS as doubles [16][96], D and
+// the running G in registers.  The whole workgroup calls it (uniform trip count, two barriers per round); T is free again on return.
+__device__ __forceinline__ void wm_rows_G(const float* __restrict__ lb, const WmRows& R, int tid, double* __restrict__ T, double (&G)[WM_PER]) {
+  for (int i = 0; i < WM_PER; ++i) G[i] = 0.0;
+  for (long long c = R.r0; c <= R.r1; c += WM_Q) {  // rows c .. c + 15: every q once
+    bool live[WM_PER];
+    for (int i = 0; i < WM_PER; ++i) {
       const int id = tid + i * WM_SCORE_THREADS, q = id / WM_G, j = id - q * WM_G;
       const long long rho = c + ((q - (int)(c & (WM_Q - 1))) & (WM_Q - 1));
-      live[i] = rho <= r1;
+      live[i] = rho <= R.r1;
       double v = 0.0;
       if (live[i]) {
-        const long long gf = g0 + 2 * (4 * rho - pbase);  // the row's first frame; its four are 2 apart
+        const long long gf = R.g0 + 2 * (4 * rho - R.pbase);  // the row's first frame; its four are 2 apart
         const float* p = lb + gf * WM_G + j;
         v = (((double)p[0] + (double)p[2 * WM_G]) + (double)p[4 * WM_G] + (double)p[6 * WM_G]) * 0.25;
       }
       T[id] = v;
     }
     __syncthreads();
-    for (int i = 0; i < PER; ++i) {
+    for (int i = 0; i < WM_PER; ++i) {
       const int id = tid + i * WM_SCORE_THREADS, j = id % WM_G;
       if (live[i] && j >= 1 && j <= WM_G - 2) G[i] += T[id] - 0.5 * (T[id - 1] + T[id + 1]);
     }
     __syncthreads();
   }
+}
+
+// z_all[b * 128 + o] and rows_all[b * 128 + o] of offset index o = blockIdx.x of item b = blockIdx.y, from Lb.  PILOT: the two sums
+// over the pilot positions only (include/vits_watermark_payload.h, step 6').
+template <bool PILOT>
+__global__ __launch_bounds__(WM_SCORE_THREADS) void wm_score_kernel(const float* __restrict__ Lb, long long lb_bstride,
+                                                                   const int* __restrict__ lens, uint32_t mk, double* __restrict__ z_all,
+                                                                   int* __restrict__ rows_all) {
+  __shared__ double T[WM_Q * WM_G];
+  __shared__ double red[2][WM_SCORE_THREADS];
+  const int o = blockIdx.x, b = blockIdx.y, tid = threadIdx.x;
+  const WmRows R = wm_rows_of(lens[b], o);
+  double G[WM_PER];
+  wm_rows_G(Lb + (long long)b * lb_bstride, R, tid, T, G);
   double num = 0.0, den = 0.0;
-  for (int i = 0; i < PER; ++i) {
+  for (int i = 0; i < WM_PER; ++i) {
     const int id = tid + i * WM_SCORE_THREADS, q = id / WM_G, j = id - q * WM_G;
+    if (PILOT && !wm_pilot(q, j)) continue;
     num += wm_chip(mk, q, j) ? G[i] : -G[i];
     den += G[i] * G[i];
   }
@@ -212,8 +264,46 @@ __global__ __launch_bounds__(WM_SCORE_THREADS) void wm_score_kernel(const float*
   }
   if (tid == 0) {
     const double d = red[1][0];
-    z_all[(long long)b * VITS_WATERMARK_OFFSETS + o] = (rows > 0 && d > 0.0) ? red[0][0] / sqrt(d) : 0.0;
-    rows_all[(long long)b * VITS_WATERMARK_OFFSETS + o] = (int)rows;
+    z_all[(long long)b * VITS_WATERMARK_OFFSETS + o] = (R.rows > 0 && d > 0.0) ? red[0][0] / sqrt(d) : 0.0;
+    rows_all[(long long)b * VITS_WATERMARK_OFFSETS + o] = (int)R.rows;
+  }
+}
+
+// The coded word of item b = blockIdx.x at the offset wm_argmax_kernel chose for it (offset[b], z[b]: read here, on the device):
+// payload[b] = W' >> 8, valid[b] = z[b] >= 6 and the CRC holds, bit_z[b * 24 + i] = z_i (steps 8' and 9').
+__global__ __launch_bounds__(WM_SCORE_THREADS) void wm_bits_kernel(const float* __restrict__ Lb, long long lb_bstride, const int* __restrict__ lens,
+                                                                  uint32_t mk, const double* __restrict__ z, const int* __restrict__ offset,
+                                                                  uint32_t* __restrict__ payload, int* __restrict__ valid, double* __restrict__ bit_z) {
+  __shared__ double T[WM_Q * WM_G];   // the row loop's plane, then c G at 96 q + j
+  __shared__ double G2[WM_Q * WM_G];  // G^2 at 96 q + j
+  __shared__ unsigned char bix[WM_Q * WM_G];  // the coded bit of a scored payload position, 255 elsewhere
+  __shared__ double bz[VITS_WATERMARK_CODED_BITS];
+  const int b = blockIdx.x, tid = threadIdx.x;
+  const int o = (offset[b] / WM_DH) & (VITS_WATERMARK_OFFSETS - 1);
+  const WmRows R = wm_rows_of(lens[b], o);
+  double G[WM_PER];
+  wm_rows_G(Lb + (long long)b * lb_bstride, R, tid, T, G);  // (ends behind a barrier: T is free)
+  for (int i = 0; i < WM_PER; ++i) {
+    const int id = tid + i * WM_SCORE_THREADS, q = id / WM_G, j = id - q * WM_G;
+    T[id] = wm_chip(mk, q, j) ? G[i] : -G[i];
+    G2[id] = G[i] * G[i];
+    bix[id] = (!wm_pilot(q, j) && j >= 1 && j <= WM_G - 2) ? (unsigned char)wm_bit_index(mk, q, j) : (unsigned char)255;
+  }
+  __syncthreads();
+  if (tid < VITS_WATERMARK_CODED_BITS) {
+    double s = 0.0, n = 0.0;
+    for (int id = 0; id < WM_Q * WM_G; ++id)  // ascending 96 q + j
+      if (bix[id] == tid) { s += T[id]; n += G2[id]; }
+    const double zi = n > 0.0 ? s / sqrt(n) : 0.0;
+    bz[tid] = zi;
+    bit_z[(long long)b * VITS_WATERMARK_CODED_BITS + tid] = zi;
+  }
+  __syncthreads();
+  if (tid == 0) {
+    uint32_t W = 0;
+    for (int i = 0; i < VITS_WATERMARK_CODED_BITS; ++i) W = (W << 1) | (bz[i] < 0.0 ? 1u : 0u);
+    payload[b] = W >> 8;
+    valid[b] = (z[b] >= VITS_WATERMARK_THRESHOLD && wm_crc8(W >> 8) == (W & 0xFFu)) ? 1 : 0;
   }
 }
 
@@ -236,57 +326,95 @@ struct WmReq {
   uint32_t key = 0;
   float gp = 1.f, gm = 1.f;  // fp32(1 + a), fp32(1 - a)
   const StftTab* T = nullptr;  // set by the callers that launch on the device (stft_tab_get: uploaded on first use, before any capture)
+  // include/vits_watermark_payload.h: the coded words, on the host; they go up with each call that launches
+  bool payload = false;
+  uint32_t word = 0;            // of the scalar: what a document, the one item it has become, is marked with
+  std::vector<uint32_t> words;  // of each item of the call, [B]
+  const uint32_t* host_words(bool doc) const { return !payload ? nullptr : doc ? &word : words.data(); }
 };
 
-// 0 -> the default; a depth outside (0, 2] dB, NaN included, is refused by name
-static int wm_req(bool on, uint32_t key, float depth_db, WmReq* out) {
+static int wm_payload_arg(uint32_t p, int item, uint32_t* word) {
+  if (p > VITS_WATERMARK_PAYLOAD_MAX) {
+    if (item < 0) return fail(VITS_ERR_ARG, "watermark: payload %u outside [0, %u]", p, VITS_WATERMARK_PAYLOAD_MAX);
+    return fail(VITS_ERR_ARG, "watermark: payload %u of item %d outside [0, %u]", p, item, VITS_WATERMARK_PAYLOAD_MAX);
+  }
+  *word = wm_word(p);
+  return VITS_OK;
+}
+
+// 0 -> the default (1 dB, 2 dB with a payload); a depth outside (0, 2] dB, NaN included, is refused by name.  payload_on: the scalar
+// `payload`, or payloads[0 .. B) where that is not null; a value above 65535 is refused by name.
+static int wm_req(bool on, uint32_t key, float depth_db, WmReq* out, bool payload_on = false, uint32_t payload = 0,
+                  const uint32_t* payloads = nullptr, int B = 0) {
   *out = WmReq();
   if (!on) return VITS_OK;
-  const float d = depth_db == 0.f ? VITS_WATERMARK_DEFAULT_DEPTH_DB : depth_db;
+  const float dflt = payload_on ? VITS_WATERMARK_PAYLOAD_DEFAULT_DEPTH_DB : VITS_WATERMARK_DEFAULT_DEPTH_DB;
+  const float d = depth_db == 0.f ? dflt : depth_db;
   if (!(d > 0.f && d <= VITS_WATERMARK_MAX_DEPTH_DB))
     return fail(VITS_ERR_ARG, "watermark: depth %g dB outside (0, %g] (0 = the default, %g dB)", (double)depth_db, (double)VITS_WATERMARK_MAX_DEPTH_DB,
-                (double)VITS_WATERMARK_DEFAULT_DEPTH_DB);
+                (double)dflt);
   const float a = (float)(pow(10.0, (double)d / 20.0) - 1.0);
   out->on = true;
   out->key = key;
   out->gp = 1.0f + a;
   out->gm = 1.0f - a;
+  if (payload_on) {
+    out->payload = true;
+    out->words.resize(B > 0 ? B : 0);
+    if (payloads) {
+      for (int b = 0; b < B; ++b) TRY(wm_payload_arg(payloads[b], b, &out->words[b]));
+      if (payload <= VITS_WATERMARK_PAYLOAD_MAX) out->word = wm_word(payload);  // (overridden; a document reads it)
+      else out->word = out->words.empty() ? 0 : out->words[0];
+    } else {
+      TRY(wm_payload_arg(payload, -1, &out->word));
+      std::fill(out->words.begin(), out->words.end(), out->word);
+    }
+  }
   return VITS_OK;
 }
 // floats of scratch one item of N samples needs
 static size_t wm_scratch_elems(long long N) { return (size_t)(N / WM_H + 1) * WM_N; }
 
 // B items x [B, N] (item b: ld_len(len_frames, len_mul, L, Mr, N, b) samples) -> y [B, n_count columns] on `stream` (capturable: no
-// allocation, no synchronisation).  scratch holds B * scratch_bstride floats, scratch_bstride >= wm_scratch_elems(N).
+// allocation, no synchronisation).  scratch holds B * scratch_bstride floats, scratch_bstride >= wm_scratch_elems(N).  d_words: the
+// coded words [B] on the device where q.payload (an argument of the launch), not read otherwise.
 template <typename OUT>
 static void wm_launch(hipStream_t stream, const WmReq& q, const float* x, long long x_bstride, long long N, const int* len_frames,
                       long long len_mul, int L, int Mr, int B, float* scratch, long long scratch_bstride, OUT* y, long long y_bstride,
-                      long long n_count, float scale) {
+                      long long n_count, float scale, const uint32_t* d_words = nullptr) {
   if (n_count <= 0 || B <= 0) return;
   const StftTab& T = *q.T;
   const long long Fmax = N >= WM_M + 1 ? 1 + N / WM_H : 0;
   const uint32_t mk = wm_mix(q.key);
-  if (Fmax > 0)
-    hipLaunchKernelGGL(wm_frames_kernel, dim3((unsigned)cdiv((int)Fmax, SF_FPB), B), dim3(64 * SF_FPB), 0, stream, x, x_bstride, N, len_frames, len_mul, L,
-                       Mr, T.d_win, T.d_tw, mk, q.gp, q.gm, scratch, scratch_bstride);
+  if (Fmax > 0) {
+    const dim3 grid((unsigned)cdiv((int)Fmax, SF_FPB), B), block(64 * SF_FPB);
+    if (q.payload)
+      hipLaunchKernelGGL(wm_frames_kernel<true>, grid, block, 0, stream, x, x_bstride, N, len_frames, len_mul, L, Mr, T.d_win, T.d_tw, mk, q.gp, q.gm, scratch,
+                         scratch_bstride, d_words);
+    else
+      hipLaunchKernelGGL(wm_frames_kernel<false>, grid, block, 0, stream, x, x_bstride, N, len_frames, len_mul, L, Mr, T.d_win, T.d_tw, mk, q.gp, q.gm, scratch,
+                         scratch_bstride, (const uint32_t*)nullptr);
+  }
   hipLaunchKernelGGL(wm_ola_kernel<OUT>, dim3((unsigned)((n_count + 255) / 256), B), dim3(256), 0, stream, scratch, scratch_bstride, x, x_bstride, N,
                      len_frames, len_mul, L, Mr, T.d_env, y, y_bstride, n_count, scale);
 }
 
 // ---- entry points ----------------------------------------------------------------------------------------------------------
-// the door behind a request (stts_tail_host runs the stage through it, as it runs the others through theirs)
-static int wm_op(int device, const float* x, const int64_t* lengths, int32_t B, int64_t N, WmReq q, float* y) {
+// the door behind a request (stts_tail_host runs the stage through it, as it runs the others through theirs); words: the coded words
+// [B] on the host where q.payload
+static int wm_op(int device, const float* x, const int64_t* lengths, int32_t B, int64_t N, WmReq q, float* y, const uint32_t* words = nullptr) {
   std::vector<int> len32;
   TRY(op_items_check("watermark", x, lengths, B, N, &len32));
-  if (!y) return fail(VITS_ERR_ARG, "watermark: bad argument");
+  if (!y || (q.payload && !words)) return fail(VITS_ERR_ARG, "watermark: bad argument");
   TRY(stft_tab_get(device, WM_N, &q.T));
   OpDoor d("watermark", device);
   const size_t sc = wm_scratch_elems(N);
   float* dx = d.up(x, (size_t)B * N);
   int* dl = d.up(len32.data(), B);
+  uint32_t* dw = q.payload ? d.up(words, (size_t)B) : nullptr;
   float* ds = d.dev<float>((size_t)B * sc);
   float* dy = d.out<float>((size_t)B * N);
-  if (d.ok()) wm_launch<float>(nullptr, q, dx, N, N, dl, 1, 1, 1, B, ds, (long long)sc, dy, N, N, 1.f);
+  if (d.ok()) wm_launch<float>(nullptr, q, dx, N, N, dl, 1, 1, 1, B, ds, (long long)sc, dy, N, N, 1.f, dw);
   d.finish();
   d.down(y, dy, (size_t)B * N);
   return d.rc();
@@ -298,17 +426,26 @@ int vits_op_watermark(int device, const float* x, const int64_t* lengths, int32_
   return wm_op(device, x, lengths, B, N, q, y);
 }
 
-int vits_op_watermark_detect(int device, const float* x, const int64_t* lengths, int32_t B, int64_t N, uint32_t key, double* z,
-                             int32_t* offset, int32_t* rows, double* z_all) {
+int vits_op_watermark_payload(int device, const float* x, const int64_t* lengths, int32_t B, int64_t N, uint32_t key, float depth_db,
+                              const uint32_t* payloads, float* y) {
+  if (!payloads || B <= 0) return fail(VITS_ERR_ARG, "watermark: bad argument");
+  WmReq q;
+  TRY(wm_req(true, key, depth_db, &q, true, 0, payloads, B));
+  return wm_op(device, x, lengths, B, N, q, y, q.words.data());
+}
+
+// the detector, and the reader where `payload` is not null (the pilot scores, then the word at the best offset)
+static int wm_detect_op(const char* what, int device, const float* x, const int64_t* lengths, int32_t B, int64_t N, uint32_t key, double* z,
+                        int32_t* offset, int32_t* rows, double* z_all, uint32_t* payload, int32_t* valid, double* bit_z) {
   std::vector<int> len32;
-  TRY(op_items_check("watermark detect", x, lengths, B, N, &len32));
-  if (!z || !offset || !rows) return fail(VITS_ERR_ARG, "watermark detect: bad argument");
+  TRY(op_items_check(what, x, lengths, B, N, &len32));
+  if (!z || !offset || !rows || (payload && !valid)) return fail(VITS_ERR_ARG, "%s: bad argument", what);
   const StftTab* T = nullptr;
   TRY(stft_tab_get(device, WM_N, &T));
-  OpDoor d("watermark detect", device);
+  OpDoor d(what, device);
   const long long Fmax = N >= WM_M + 1 ? 1 + N / WM_DH : 0;
   const long long lbs = (Fmax ? Fmax : 1) * WM_G;
-  const size_t nz = (size_t)B * VITS_WATERMARK_OFFSETS;
+  const size_t nz = (size_t)B * VITS_WATERMARK_OFFSETS, nb = (size_t)B * VITS_WATERMARK_CODED_BITS;
   float* dx = d.up(x, (size_t)B * N);
   int* dl = d.up(len32.data(), B);
   float* dlb = d.dev<float>((size_t)B * lbs);
@@ -317,17 +454,38 @@ int vits_op_watermark_detect(int device, const float* x, const int64_t* lengths,
   double* dz = d.out<double>(B);
   int* dof = d.out<int>(B);
   int* dro = d.out<int>(B);
+  uint32_t* dpl = payload ? d.out<uint32_t>(B) : nullptr;
+  int* dva = payload ? d.out<int>(B) : nullptr;
+  double* dbz = payload ? d.out<double>(nb) : nullptr;
   if (d.ok()) {
     const uint32_t mk = wm_mix(key);
     if (Fmax > 0)
       hipLaunchKernelGGL(wm_lb_kernel, dim3((unsigned)cdiv((int)Fmax, SF_FPB), B), dim3(64 * SF_FPB), 0, nullptr, dx, N, dl, T->d_win, T->d_tw, dlb, lbs);
-    hipLaunchKernelGGL(wm_score_kernel, dim3(VITS_WATERMARK_OFFSETS, B), dim3(WM_SCORE_THREADS), 0, nullptr, dlb, lbs, dl, mk, dza, dra);
+    if (payload) hipLaunchKernelGGL(wm_score_kernel<true>, dim3(VITS_WATERMARK_OFFSETS, B), dim3(WM_SCORE_THREADS), 0, nullptr, dlb, lbs, dl, mk, dza, dra);
+    else hipLaunchKernelGGL(wm_score_kernel<false>, dim3(VITS_WATERMARK_OFFSETS, B), dim3(WM_SCORE_THREADS), 0, nullptr, dlb, lbs, dl, mk, dza, dra);
     hipLaunchKernelGGL(wm_argmax_kernel, dim3(cdiv(B, 64)), dim3(64), 0, nullptr, dza, dra, B, dz, dof, dro);
+    if (payload) hipLaunchKernelGGL(wm_bits_kernel, dim3(B), dim3(WM_SCORE_THREADS), 0, nullptr, dlb, lbs, dl, mk, dz, dof, dpl, dva, dbz);
   }
   d.finish();
   d.down(z, dz, (size_t)B);
   d.down(offset, dof, (size_t)B);
   d.down(rows, dro, (size_t)B);
   if (z_all) d.down(z_all, dza, nz);
+  if (payload) {
+    d.down(payload, dpl, (size_t)B);
+    d.down(valid, dva, (size_t)B);
+    if (bit_z) d.down(bit_z, dbz, nb);
+  }
   return d.rc();
+}
+
+int vits_op_watermark_detect(int device, const float* x, const int64_t* lengths, int32_t B, int64_t N, uint32_t key, double* z,
+                             int32_t* offset, int32_t* rows, double* z_all) {
+  return wm_detect_op("watermark detect", device, x, lengths, B, N, key, z, offset, rows, z_all, nullptr, nullptr, nullptr);
+}
+
+int vits_op_watermark_read(int device, const float* x, const int64_t* lengths, int32_t B, int64_t N, uint32_t key, double* z,
+                           int32_t* offset, int32_t* rows, uint32_t* payload, int32_t* valid, double* z_all, double* bit_z) {
+  if (!payload || !valid) return fail(VITS_ERR_ARG, "watermark read: bad argument");
+  return wm_detect_op("watermark read", device, x, lengths, B, N, key, z, offset, rows, z_all, payload, valid, bit_z);
 }

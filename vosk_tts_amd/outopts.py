@@ -13,7 +13,8 @@ from dataclasses import dataclass
 
 # the feed keys Tail.from_feed reads
 TAIL_FEEDS = ("vits.loudness", "vits.peak", "vits.peak_ceiling", "vits.pitch", "vits.pitch_formants", "vits.limit", "vits.limit_lookahead_ms",
-              "vits.limit_release_ms", "vits.pitch_range", "vits.watermark_key", "vits.watermark_depth_db")
+              "vits.limit_release_ms", "vits.pitch_range", "vits.watermark_key", "vits.watermark_depth_db",
+              "vits.watermark_payload")
 
 # why a stream has no tail: (field, what it cannot be, why, the feed a whole-utterance call takes)
 _STREAM = (("loudness", "be loudness-normalised", "an integrated-loudness or peak target needs the whole utterance before the first chunk",
@@ -23,6 +24,8 @@ _STREAM = (("loudness", "be loudness-normalised", "an integrated-loudness or pea
            ("pitch", "be pitch-shifted", "the phase recursion needs the frames before a chunk", "\"vits.pitch\""),
            ("pitch_range", "take an intonation range", "the median of the F0 track needs the whole utterance before the first chunk",
             "\"vits.pitch_range\""),
+           ("payload", "carry a watermark payload ({family}_FLAG_WATERMARK_PAYLOAD)", "the mark is a stage of the output tail, and a stream has none",
+            "\"vits.watermark_payload\""),
            ("watermark", "be watermarked ({family}_FLAG_WATERMARK)", "the mark is a stage of the output tail, and a stream has none",
             "\"vits.watermark_key\""))
 
@@ -34,11 +37,19 @@ class Tail:
     pitch: float = None        # semitones, already reduced by capi.pitch_spec() (None: none, or one that is the identity)
     formants: bool = False     # that shift with the spectral envelope kept; False whenever pitch is None
     pitch_range: float = None  # capi.range_spec(); include/vits_intonation.h
-    watermark: tuple = None    # capi.watermark_spec(): (key, depth_db, 0 = the default); include/vits_watermark.h
+    watermark: tuple = None    # capi.watermark_spec(): (key, depth_db, 0 = the default); include/vits_watermark.h.  A third entry: the
+    #                            mark carries a payload (include/vits_watermark_payload.h): an int, one int per item, or, in a session's
+    #                            Tail, capi.PAYLOAD_RIDES: the value rides with the request and does not decide its batch
+
+    @property
+    def payload(self):
+        return self.watermark[2] if self.watermark is not None and len(self.watermark) > 2 else None
 
     @classmethod
-    def from_feed(cls, lib, feed):
-        """The tail a feed asks for, checked before any device work, in the order loudness, pitch, limit, range, watermark.  `lib` is the
+    def from_feed(cls, lib, feed, payload_rides=False):
+        """payload_rides: "vits.watermark_payload" is checked here and then kept OUT of the Tail (capi.PAYLOAD_RIDES in its place): the
+        caller hands the value on with the request, so requests of one key with different payloads share a coalescer key.
+        The tail a feed asks for, checked before any device work, in the order loudness, pitch, limit, range, watermark.  `lib` is the
         session's library: a stage it does not export is refused here (its _need_* check).  Values out of range, both loudness targets
         at once, "vits.peak" next to "vits.limit" and a depth without a key are ValueError.  "vits.pitch_formants" modifies a shift:
         without one in effect it changes nothing.  With "vits.limit", "vits.peak_ceiling" is the limiter's ceiling and the gain has no cap."""
@@ -66,9 +77,18 @@ class Tail:
         key = feed.get("vits.watermark_key")
         if key is None and feed.get("vits.watermark_depth_db") is not None:
             raise ValueError("\"vits.watermark_depth_db\" needs \"vits.watermark_key\"")
-        watermark = None if key is None else watermark_spec(int(key), feed.get("vits.watermark_depth_db"))
+        payload = feed.get("vits.watermark_payload")
+        if key is None and payload is not None:
+            raise ValueError("\"vits.watermark_payload\" needs \"vits.watermark_key\": watermark_payload without watermark")
+        watermark = None if key is None else watermark_spec(int(key), feed.get("vits.watermark_depth_db"), payload)
         if watermark is not None:
             lib._need_watermark()
+            if payload is not None:
+                lib._need_watermark_payload()
+                if payload_rides:
+                    from .capi import PAYLOAD_RIDES
+
+                    watermark = watermark[:2] + (PAYLOAD_RIDES,)
         return cls(loudness, limit, pitch, formants, pitch_range, watermark)
 
     def kw(self):
@@ -88,6 +108,8 @@ class Tail:
             kw["watermark"] = self.watermark[0]
             if self.watermark[1]:
                 kw["watermark_depth_db"] = self.watermark[1]
+            if self.payload is not None and not isinstance(self.payload, str):  # (capi.PAYLOAD_RIDES: the request's caller adds the value)
+                kw["watermark_payload"] = self.payload
         return kw
 
     def refuse_stream(self, family, hint, error=ValueError):

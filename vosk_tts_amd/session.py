@@ -230,12 +230,37 @@ _OPTIONAL_NONE = ("bert", "phone_duration_extra")
 _EXT = ("vits.noise_dp", "vits.noise_prior", "vits.forced_durations", "vits.seed", "vits.solo", "vits.item_seeds", "vits.sample_rate", "vits.marks",
         "vits.loudness", "vits.peak", "vits.peak_ceiling", "vits.pitch", "vits.pitch_formants", "vits.limit", "vits.limit_lookahead_ms",
         "vits.limit_release_ms", "vits.item_scales", "vits.token_length_scale", "vits.token_pause", "vits.fit_frames", "vits.token_pitch",
-        "vits.token_gain_db", "vits.pitch_range", "vits.watermark_key", "vits.watermark_depth_db") + tuple(DOCUMENT_FEEDS)
+        "vits.token_gain_db", "vits.pitch_range", "vits.watermark_key", "vits.watermark_depth_db",
+        "vits.watermark_payload") + tuple(DOCUMENT_FEEDS)
 # the prosody controls of a request (include/vits_prosody.h): feed key -> keyword of capi.VitsModel.synthesize*
 _PROSODY = {"vits.item_scales": "item_scales", "vits.token_length_scale": "token_length_scale", "vits.token_pause": "token_pause",
             "vits.fit_frames": "fit_frames"}
 # the contour of a request (include/vits_contour.h): feed key -> keyword of capi.VitsModel.synthesize*
 _CONTOUR = {"vits.token_pitch": "token_pitch", "vits.token_gain_db": "token_gain_db"}
+
+
+class RequestExtra(tuple):
+    """What rides with a request through the coalescer without deciding its batch: the scales (the tuple itself) and, as an attribute,
+    the payload of its mark (include/vits_watermark_payload.h; None: none)"""
+
+    payload = None
+
+    @classmethod
+    def of(cls, scales, payload=None):
+        me = cls(scales)
+        me.payload = None if payload is None else int(np.asarray(payload).reshape(-1)[0])  # (one request: one value)
+        return me
+
+
+def ride_payloads(pk, tail, reqs, n_real):
+    """the keywords of a coalesced call whose Tail says its payloads ride with the requests: one value for a lone request, one per item
+    (the one-token dummies behind n_real: 0) for a batch"""
+    from .capi import PAYLOAD_RIDES
+
+    if tail.payload != PAYLOAD_RIDES:
+        return pk
+    vals = [getattr(r[3], "payload", None) or 0 for r in reqs[:n_real]] + [0] * (len(reqs) - n_real)
+    return dict(pk, watermark_payload=vals[0] if len(reqs) == 1 else vals)
 
 
 class _Arg:
@@ -307,7 +332,7 @@ class VitsSession:
         # value or none does, and one tail, whose stages measure and apply per item: a request's result does not depend on what it
         # was batched with
         kind, scale, rate, marks, tail = key
-        pk = tail.kw()
+        pk = ride_payloads(tail.kw(), tail, reqs, len(reqs))
         scales = np.array(reqs[0][3], np.float32)
         if len(reqs) == 1:
             ids, sid, seed = reqs[0][:3]
@@ -324,6 +349,7 @@ class VitsSession:
         while n_pad < n_real:
             n_pad *= 2
         reqs = list(reqs) + [(np.ones((1, 1), np.int64), 0, 0, reqs[0][3])] * (n_pad - n_real)
+        pk = ride_payloads(tail.kw(), tail, reqs, n_real)  # (requests of one key with different payloads: one call, watermark_payloads [B])
         if any(tuple(r[3]) != tuple(reqs[0][3]) for r in reqs):  # every item its own [noise_scale, length_scale, noise_scale_w]
             pk = dict(pk, item_scales=np.array([r[3] for r in reqs], np.float32))
         lens = np.array([r[0].shape[1] for r in reqs], np.int64)
@@ -431,8 +457,9 @@ class VitsSession:
         self._watch()
         rate = self._rate(feed.get("vits.sample_rate"))
         marks = self._marks(feed)
-        tail = Tail.from_feed(self._lib, feed)  # (the loudness, limiter, pitch, intonation and watermark feeds; outopts.TAIL_FEEDS)
         n = self._coalescable(feed, ids)
+        # (the loudness, limiter, pitch, intonation and watermark feeds; outopts.TAIL_FEEDS.  A coalesced request's payload rides with it)
+        tail = Tail.from_feed(self._lib, feed, payload_rides=bool(n))
         if n:
             key = ("f32", 1.0, rate, marks, tail)
             res = self.coalescer.submit(key, np.ascontiguousarray(ids[:, :n], np.int64), int(sid[0]), int(seed), self._scales(feed))
@@ -451,8 +478,8 @@ class VitsSession:
 
     @staticmethod
     def _scales(feed):
-        """the request's scales as the tuple that rides with it through the coalescer"""
-        return tuple(float(v) for v in np.asarray(feed["scales"], np.float32).reshape(-1))
+        """the request's scales as the tuple that rides with it through the coalescer, and with them the payload of its mark"""
+        return RequestExtra.of((float(v) for v in np.asarray(feed["scales"], np.float32).reshape(-1)), feed.get("vits.watermark_payload"))
 
     def _prosody(self, feed):
         """The prosody controls of a request (include/vits_prosody.h) -> keywords of the model's calls, none without one (the call as it
@@ -509,8 +536,8 @@ class VitsSession:
         self._watch()
         rate = self._rate(sample_rate if sample_rate is not None else feed.get("vits.sample_rate"))
         marks = self._marks(feed)
-        tail = Tail.from_feed(self._lib, feed)
         n = self._coalescable(feed, ids)
+        tail = Tail.from_feed(self._lib, feed, payload_rides=bool(n))
         if n:
             key = ("pcm", float(scale), rate, marks, tail)
             res = self.coalescer.submit(key, np.ascontiguousarray(ids[:, :n], np.int64), int(sid[0]), int(seed), self._scales(feed))

@@ -18,7 +18,7 @@ _INPUTS = ("input", "input_lengths", "scales", "sid", "bert", "phone_duration_ex
 _EXT = ("vits.noise", "vits.seed", "vits.n_timesteps", "vits.sample_rate", "vits.denoiser_strength", "vits.denoiser_filter_length",
         "vits.marks", "vits.loudness", "vits.peak", "vits.peak_ceiling", "vits.pitch", "vits.pitch_formants",
         "vits.limit", "vits.limit_lookahead_ms", "vits.limit_release_ms", "vits.token_pitch", "vits.token_gain_db",
-        "vits.pitch_range", "vits.watermark_key", "vits.watermark_depth_db") + tuple(DOCUMENT_FEEDS)
+        "vits.pitch_range", "vits.watermark_key", "vits.watermark_depth_db", "vits.watermark_payload") + tuple(DOCUMENT_FEEDS)
 
 
 class SttsSession:
@@ -106,10 +106,13 @@ class SttsSession:
 
     def mark(self, audio, lengths, wm):
         """audio float32 [B, S] with per-item sample counts -> the audio marked per item (vits_op_watermark on the host buffer); wm: a
-        capi.watermark_spec() (key, depth), None: unchanged.  What tail_chain() does behind resample() and in front of normalize(): the
-        mark goes in at the rate returned"""
+        capi.watermark_spec() (key, depth) or (key, depth, payload: vits_op_watermark_payload), None: unchanged.  What tail_chain() does
+        behind resample() and in front of normalize(): the mark goes in at the rate returned"""
         if wm is None or audio.shape[-1] == 0:
             return audio
+        if len(wm) > 2:
+            payloads = wm[2] if isinstance(wm[2], tuple) else (wm[2],) * audio.shape[0]
+            return self._lib.op_watermark_payload(audio, lengths, wm[0], payloads, wm[1], device=self._vocoder.device)
         return self._lib.op_watermark(audio, lengths, *wm, device=self._vocoder.device)
 
     def normalize(self, audio, lengths, sample_rate, spec, limit=None):

@@ -302,8 +302,11 @@ class Synth:
                 raise ValueError("watermark=True needs the config key inference.watermark_key (or pass the key itself)")
         return int(watermark)
 
-    def _watermark(self, args, watermark, watermark_depth_db=None):
-        """The audio watermark of the request (include/vits_watermark.h; both voice families): `watermark`, a 32-bit key (a selector, not
+    def _watermark(self, args, watermark, watermark_depth_db=None, watermark_payload=None):
+        """watermark_payload: an int in [0, 65535] that the mark carries and read_watermark returns (include/vits_watermark_payload.h; the
+        feed gets "vits.watermark_payload", and the default depth is then 2 dB); without watermark= it is a ValueError, as is a value out of
+        range, before any device work.
+        The audio watermark of the request (include/vits_watermark.h; both voice families): `watermark`, a 32-bit key (a selector, not
         a secret) or True for the config key inference.watermark_key; None / False = off, the reference's behaviour (a config key alone
         marks nothing).  watermark_depth_db in (0, 2], default 1 dB.  The feed gets "vits.watermark_key" / "vits.watermark_depth_db"; the
         engine marks the audio on the device behind the resampler, in front of the loudness stage, the limiter and the int16 conversion.
@@ -313,9 +316,13 @@ class Synth:
         if watermark is None or watermark is False:
             if watermark_depth_db is not None:
                 raise ValueError("watermark_depth_db needs watermark=")
+            if watermark_payload is not None:
+                raise ValueError("watermark_payload needs watermark=: VITS_FLAG_WATERMARK_PAYLOAD modifies a watermark request")
             return False
-        key, depth = watermark_spec(self._watermark_key(watermark), watermark_depth_db)
+        key, depth, *payload = watermark_spec(self._watermark_key(watermark), watermark_depth_db, watermark_payload)
         args["vits.watermark_key"] = key
+        if payload:
+            args["vits.watermark_payload"] = payload[0]  # (an int; MultiDeviceSynth.synth_batch: or a tuple, one per request)
         if depth:
             args["vits.watermark_depth_db"] = depth
         return True
@@ -341,6 +348,29 @@ class Synth:
         dev = getattr(getattr(sess, "_vocoder", None) or getattr(sess, "_model", None), "device", 0)
         z, off, _, _ = lib.op_watermark_detect(x, [x.shape[1]], k, device=dev)
         return bool(z[0] >= WATERMARK_THRESHOLD), float(z[0]), int(off[0])
+
+    def read_watermark(self, audio, key=None):
+        """(detected, z, offset_samples, payload_or_None, bit_z) of one piece of audio under `key` (default: the config key
+        inference.watermark_key), by the engine's reader (vits_op_watermark_read, include/vits_watermark_payload.h): z is the best
+        correlation of the PILOT chips over the 128 pattern offsets, detected iff z >= 6 (the same false-alarm bound of 1.9e-6 per item);
+        payload is the 16-bit value the mark carries, None unless the read is valid (detected, and the word's CRC holds: a plain mark
+        of the same key is detected and has no payload); bit_z float64 [24]: the score of every coded bit, negative = 1, near 0 = weak.
+        audio as for detect_watermark, which is unchanged and is NOT the detector of a payload mark."""
+        from .capi import WATERMARK_CODED_BITS, WATERMARK_THRESHOLD
+
+        k = self._watermark_key(key)
+        a = np.asarray(audio)
+        x = a.astype(np.float32) / np.float32(32767.0) if a.dtype == np.int16 else a.astype(np.float32)
+        x = x.reshape(1, -1)
+        sess = self.model.onnx
+        lib = getattr(sess, "_lib", None)
+        if lib is None or not getattr(lib, "has_watermark_payload", False):
+            raise NotImplementedError("this session type has no watermark reader (include/vits_watermark_payload.h)")
+        if x.shape[1] == 0:
+            return False, 0.0, 0, None, np.zeros(WATERMARK_CODED_BITS)
+        dev = getattr(getattr(sess, "_vocoder", None) or getattr(sess, "_model", None), "device", 0)
+        z, off, _, payload, valid, _, bit_z = lib.op_watermark_read(x, [x.shape[1]], k, device=dev)
+        return bool(z[0] >= WATERMARK_THRESHOLD), float(z[0]), int(off[0]), int(payload[0]) if valid[0] else None, bit_z[0]
 
     def measure_pitch(self, audio, rate=None):
         """(hz, median_hz) of one utterance: hz float32 [1 + n // 256], the F0 of every analysis frame of include/vits_intonation.h (hop
@@ -489,8 +519,10 @@ class Synth:
     def synth_audio(self, text, speaker_id=0, noise_level=None, speech_rate=None, duration_noise_level=None, scale=None, sample_rate=None,
                     denoiser_strength=None, marks=False, loudness=None, peak=None, peak_ceiling=None, pitch=None,
                     preserve_formants=None, limit=None, limit_lookahead_ms=None, limit_release_ms=None, word_rates=None, pauses=None,
-                    duration=None, word_pitch=None, word_gains=None, pitch_range=None, watermark=None, watermark_depth_db=None):
-        """watermark / watermark_depth_db (extension): a keyed mark in the returned audio that detect_watermark recognises, see _watermark.
+                    duration=None, word_pitch=None, word_gains=None, pitch_range=None, watermark=None, watermark_depth_db=None,
+                    watermark_payload=None):
+        """watermark_payload (extension): 16 bits inside the mark, which read_watermark returns, see _watermark.
+        watermark / watermark_depth_db (extension): a keyed mark in the returned audio that detect_watermark recognises, see _watermark.
         pitch_range (extension): the intonation range, 0 (monotone) to 4, 1 = unchanged, see _range.
         word_pitch / word_gains (extension): per-word semitones and decibels, see _contour.
         word_rates / pauses / duration (extension): per-word tempo, pauses behind words and the length of the whole utterance in
@@ -513,7 +545,7 @@ class Synth:
         self._limit(args, limit, peak_ceiling, limit_lookahead_ms, limit_release_ms)
         self._pitch(args, pitch, preserve_formants)
         self._range(args, pitch_range)
-        self._watermark(args, watermark, watermark_depth_db)
+        self._watermark(args, watermark, watermark_depth_db, watermark_payload)
         rate = self.native_rate()
         if sample_rate and int(sample_rate) != rate:
             rate = int(sample_rate)
@@ -638,7 +670,7 @@ class Synth:
                        marks=False, seed=None, noise_level=None, speech_rate=None, duration_noise_level=None, scale=None, sample_rate=None,
                        denoiser_strength=None, loudness=None, peak=None, peak_ceiling=None, pitch=None, preserve_formants=None, limit=None,
                        limit_lookahead_ms=None, limit_release_ms=None, pitch_range=None, max_tokens=None, watermark=None,
-                       watermark_depth_db=None, **refused):
+                       watermark_depth_db=None, watermark_payload=None, **refused):
         """Many sentences and speakers in one call (extension; include/vits_document.h).  doc: a string -- split by document.split into
         sentences and paragraphs under the documented rule, sentences longer than max_tokens (default 512) tokens cut at clause marks --
         or a list of document.Segment(text, speaker_id=None, pause_after=None, speech_rate=None, word_rates=, pauses=, word_pitch=,
@@ -686,7 +718,7 @@ class Synth:
         self._limit(args, limit, peak_ceiling, limit_lookahead_ms, limit_release_ms)
         self._pitch(args, pitch, preserve_formants)
         self._range(args, pitch_range)
-        self._watermark(args, watermark, watermark_depth_db)
+        self._watermark(args, watermark, watermark_depth_db, watermark_payload)
         out_rate = rate
         if sample_rate and int(sample_rate) != rate:
             out_rate = int(sample_rate)
@@ -731,8 +763,10 @@ class Synth:
 
     def synth_stream(self, text, speaker_id=0, noise_level=None, speech_rate=None, duration_noise_level=None, scale=None,
                      chunk_frames=64, sample_rate=None, denoiser_strength=None, on_marks=None, loudness=None, peak=None, peak_ceiling=None,
-                     pitch=None, limit=None, word_rates=None, pauses=None, duration=None, pitch_range=None, document=None, watermark=None):
-        """watermark: ValueError naming VITS_FLAG_WATERMARK -- the mark is a stage of the output tail, and a stream has none.
+                     pitch=None, limit=None, word_rates=None, pauses=None, duration=None, pitch_range=None, document=None, watermark=None,
+                     watermark_payload=None):
+        """watermark_payload: ValueError naming VITS_FLAG_WATERMARK_PAYLOAD, as for watermark.
+        watermark: ValueError naming VITS_FLAG_WATERMARK -- the mark is a stage of the output tail, and a stream has none.
         document: ValueError -- the join and the stages behind it need every segment before the first chunk (synth_document).
         word_rates / pauses / duration: as for synth_audio (the stream's open runs the controlled regulator; chunking is untouched).
         pitch_range: ValueError -- the median of the F0 track needs the whole utterance (a voice whose config names
@@ -750,6 +784,9 @@ class Synth:
         if document is not None:
             raise ValueError("synth_stream cannot take document=: the join and the stages behind it need every segment before the first "
                              "chunk (synth_document takes a document)")
+        if watermark_payload is not None:
+            raise ValueError("synth_stream cannot carry a watermark payload (VITS_FLAG_WATERMARK_PAYLOAD): the mark is a stage of the output "
+                             "tail, and a stream has none (synth_audio takes watermark= and watermark_payload=)")
         if watermark is not None and watermark is not False:
             raise ValueError("synth_stream cannot watermark (VITS_FLAG_WATERMARK): the mark is a stage of the output tail, and a stream has "
                              "none (synth_audio takes watermark=)")
@@ -784,7 +821,7 @@ class Synth:
     def synth(self, text, oname, speaker_id=0, noise_level=None, speech_rate=None, duration_noise_level=None, scale=None, sample_rate=None,
               denoiser_strength=None, marks=False, loudness=None, peak=None, peak_ceiling=None, pitch=None, preserve_formants=None,
               limit=None, limit_lookahead_ms=None, limit_release_ms=None, word_rates=None, pauses=None, duration=None, word_pitch=None,
-              word_gains=None, pitch_range=None, watermark=None, watermark_depth_db=None):
+              word_gains=None, pitch_range=None, watermark=None, watermark_depth_db=None, watermark_payload=None):
         """marks=True: the utterance's marks.SpeechMarks are returned (the default returns None, as the reference does)"""
         audio = self.synth_audio(text, speaker_id, noise_level, speech_rate, duration_noise_level, scale, sample_rate, denoiser_strength, marks=marks,
                                  loudness=loudness, peak=peak, peak_ceiling=peak_ceiling, pitch=pitch,
@@ -792,7 +829,8 @@ class Synth:
                                  limit_release_ms=limit_release_ms, **{k: v for k, v in (("word_rates", word_rates), ("pauses", pauses), ("duration", duration),
                                                                                            ("word_pitch", word_pitch), ("word_gains", word_gains),
                                                                                            ("pitch_range", pitch_range), ("watermark", watermark),
-                                                                                           ("watermark_depth_db", watermark_depth_db))
+                                                                                           ("watermark_depth_db", watermark_depth_db),
+                                                                                           ("watermark_payload", watermark_payload))
                                                                       if v is not None})
         sm = None
         if marks:
