@@ -1,15 +1,19 @@
 #!/usr/bin/env python3
-"""That a build computes the tail's frame transform (csrc/stft.hip.h) bit for bit as another does: one SHA-256 per line over fixed seeded
-inputs, for every door that runs a kernel built on it and for the tail end to end.
+"""That a build computes the output tail (the frame transform of csrc/stft.hip.h and every stage that takes the batch descriptor of
+csrc/ragged.hip.h) bit for bit as another does: one SHA-256 per line over fixed seeded inputs, for every door of a tail stage and for the
+tail end to end.
 
     python tools/stft_identity.py --out profiles/stft_frames_identity.txt
     VITS_MI355_LIB=/path/to/the/other/libvits_mi355.so python tools/stft_identity.py --label parent --out profiles/stft_frames_identity.txt
 
 Doors: vits_op_denoise at the five filter lengths; the pitch doors (shift, stretch, their formant forms, the formant gain) at +3 and -12
-semitones; vits_op_contour / _stretch; vits_op_intonation / _stretch; vits_op_watermark / _detect / _payload / _read.  One padded batch of four items of
+semitones; vits_op_contour / _stretch; vits_op_intonation / _stretch; vits_op_watermark / _detect / _payload / _read; vits_op_resample down and
+up; vits_op_loudness / _normalize; vits_op_true_peak; vits_op_limit in both modes; vits_op_loudness_limit.  One padded batch of four items of
 400 samples (no frame), 513 (F_s of 2 or 3 at -12), 5000 and 22050; the denoiser's door refuses an item below n/2 + 1 samples, so its
-first item is that long.  End to end, on the tiny voice as float and as int16: plain, 8000 Hz, -23 LUFS, the limiter, pitch, a contour,
-the watermark, a two-item document; and on the toy multistream voice a denoised utterance in one call and streamed.
+first item is that long.  The pitch and contour doors once more on six items of up to 2,000,000 samples, which their runners must split
+into groups (the group counts, from the scratch formulas of csrc/pitch.hip.h and csrc/contour.hip.h, are on the line).  End to end, on
+the tiny voice as float and as int16: plain, 8000 Hz, -23 LUFS, the limiter, pitch, a contour, the watermark, every stage at once, a
+two-item document; and on the toy multistream voice a denoised utterance in one call and streamed.
 
 A helper, not a gate: it prints, the reader compares the two listings.
 """
@@ -61,6 +65,50 @@ def signal():
     return x
 
 
+def pv_groups(lengths, item_bytes, limit=512 << 20):
+    """the groups of consecutive items pv_run (csrc/pitch.hip.h) forms: how many"""
+    n, b0 = 0, 0
+    while b0 < len(lengths):
+        mx, c = 0, 0
+        while b0 + c < len(lengths) and item_bytes(max(mx, int(lengths[b0 + c]))) * (c + 1) <= limit:
+            mx, c = max(mx, int(lengths[b0 + c])), c + 1
+        assert c, "an item fits no group"
+        n, b0 = n + 1, b0 + c
+    return n
+
+
+def pitch_item_bytes(n, P, Q):
+    fa = 1 + n // 256 if n >= 513 else 0
+    fs = ((fa + 1) * P + Q - 1) // Q if fa else 0
+    return (fa + 2) * 513 * 8 + fs * 513 * 4 + fs * 1024 * 4 + (fs - 1) * 256 * 4 + 8 + 64 if fa else 8
+
+
+def contour_item_bytes(n):
+    fa, f = (1 + n // 256 if n >= 513 else 0), 1 + n // 256
+    cap = 2 * (fa + 1)
+    return (f + 1) * 12 + (cap + 2) * 8 + 64 + ((fa + 2) * 513 * 8 + cap * 513 * 4 + cap * 1024 * 4 + (cap - 1) * 256 * 4 if fa else 0)
+
+
+def grouped(lib):
+    """the pitch and contour doors on a batch their runners split: six items of up to 2,000,000 samples"""
+    ln = np.array([2_000_000, 1_999_000, 1_500_000, 2_000_000, 1_800_001, 1_234_567], np.int64)
+    rng = np.random.default_rng(33)
+    N = int(ln.max())
+    t = np.arange(N, dtype=np.float64) / RATE
+    x = np.zeros((len(ln), N), np.float32)
+    for b, n in enumerate(ln):
+        x[b, :n] = (0.2 * np.sin(2 * np.pi * (120.0 + 15.0 * b) * t) + 0.02 * rng.standard_normal(N))[:n].astype(np.float32)
+    P, Q = lib.pitch_plan(3.0)
+    gp, gc = pv_groups(ln, lambda n: pitch_item_bytes(n, P, Q)), pv_groups(ln, contour_item_bytes)
+    Tx = 8
+    cum = np.stack([np.maximum(1, (np.arange(1, Tx + 1) * f) // Tx) for f in (ln + 255) // 256]).astype(np.int32)
+    tl = np.full(len(ln), Tx, np.int64)
+    semi = np.tile(np.array([0, 2, 4, 7, 0, -3, -12, 0], np.float32), (len(ln), 1))
+    gain = np.tile(np.array([0, 0, 3, 3, -6, -6, 0, 0], np.float32), (len(ln), 1))
+    return [f"  op_pitch_shift +3, 6 x 2e6 samples, {gp} groups        {sha(lib.op_pitch_shift(x, ln, 3.0))}",
+            f"  op_contour, 6 x 2e6 samples, {gc} groups              {sha(lib.op_contour(x, ln, cum, tl, 256, semi, gain))}"]
+
+
 def doors(lib):
     x = signal()
     B, N = x.shape
@@ -98,7 +146,15 @@ def doors(lib):
         yp = lib.op_watermark_payload(x, LENGTHS, KEY, PAYLOADS)
         lines.append(f"  op_watermark_payload                              {sha(yp)}")
         lines.append(f"  op_watermark_read                                 {sha(*lib.op_watermark_read(yp, LENGTHS, KEY))}")
-    return lines
+    for ro in (8000, 48000):
+        lines.append(f"  op_resample {RATE} -> {ro:<5}                        {sha(lib.op_resample(x, LENGTHS, RATE, ro))}")
+    lines.append(f"  op_loudness                                       {sha(*lib.op_loudness(x, LENGTHS, RATE))}")
+    lines.append(f"  op_loudness_normalize -23 LUFS                    {sha(*lib.op_loudness_normalize(x, LENGTHS, RATE, 1, -23.0))}")
+    lines.append(f"  op_true_peak                                      {sha(lib.op_true_peak(x, LENGTHS, RATE))}")
+    for mode, name in ((1, "sample"), (2, "true")):
+        lines.append(f"  op_limit {name:<6} ceiling 0.05                       {sha(*lib.op_limit(x, LENGTHS, RATE, mode, 0.05))}")
+    lines.append(f"  op_loudness_limit -23 LUFS, true, 0.05            {sha(*lib.op_loudness_limit(x, LENGTHS, RATE, -23.0, 2, 0.05))}")
+    return lines + grouped(lib)
 
 
 def tail(lib, W):
@@ -119,6 +175,8 @@ def tail(lib, W):
         lines.append(f"  tiny voice, {name + ', float':<38}{sha(model.synthesize(*a, seed=3, solo=True, **kw)[0])}")
         lines.append(f"  tiny voice, {name + ', int16':<38}{sha(model.synthesize_pcm16(*a, seed=3, solo=True, **kw)[0])}")
     doc = (ids, ln, SCALES, sid)
+    every = dict(sample_rate=8000, token_pitch=tp, watermark=KEY, loudness=LOUD, limit=limit_spec("true", 0.05))
+    lines.append(f"  tiny voice, {'every stage at once, int16':<38}{sha(model.synthesize_pcm16(ids, ln, SCALES, sid, seed=3, solo=True, **every)[0])}")
     lines.append(f"  tiny voice, document, float                       {sha(model.synthesize_document(*doc, seed=3, gap_frames=[2, 1], fade_samples=9)[0])}")
     lines.append(f"  tiny voice, document, watermark, int16            {sha(model.synthesize_document(*doc, seed=3, gap_frames=[2, 1], pcm=True, watermark=KEY)[0])}")
     model.close()

@@ -1,6 +1,6 @@
 // contour.hip.h -- per-token pitch and volume contours (include/vits_contour.h): frame tracks from the tokens, the position recurrence,
 // the vocoder of pitch.hip.h driven by its step table, a warping windowed-sinc resampler and the gain curve.  Part of the ONE
-// translation unit engine.hip (included there, after pitch.hip.h, whose analysis kernel and TAB instantiations it launches).
+// translation unit engine.hip (included there, after pitch.hip.h, whose group runner pv_run and TAB instantiations it runs on).
 //
 // Launches per group of items (d_len: every item's samples; d_vlen: the same for the items that go through the vocoder, 0 for the
 // items of cases (b) and (c), which every vocoder kernel then leaves at once):
@@ -287,13 +287,11 @@ static int contour_plan(const float* semitones, const float* gain_db, float add_
 }
 
 // h_1 of include/vits_contour.h on the device, one copy per device (uploaded on first use, outside any capture; never freed)
-static std::mutex g_ct_mu;
-static std::map<int, float*> g_ct_tabs;
+static DevTabs<int, float*> g_ct_tabs;
 
 static int contour_tab_get(int device, const float** out) {
-  std::lock_guard<std::mutex> g(g_ct_mu);
-  auto it = g_ct_tabs.find(device);
-  if (it == g_ct_tabs.end()) {
+  float* const* d = nullptr;
+  TRY(g_ct_tabs.get(device, &d, [&](float*& tab) {
     std::vector<float> T(CT_TAB, 0.f);
     const double i0b = rs_bessel_i0(RS_BETA);
     for (int j = 0; j <= RS_Z * CT_RES; ++j) {
@@ -302,11 +300,9 @@ static int contour_tab_get(int device, const float** out) {
       const double r2 = std::max(1.0 - (yv / RS_Z) * (yv / RS_Z), 0.0);
       T[j] = (float)(RS_RHO * sinc * rs_bessel_i0(RS_BETA * sqrt(r2)) / i0b);
     }
-    float* d = nullptr;
-    TRY(dev_table_upload(device, "contour", T.data(), sizeof(float) * CT_TAB, (void**)&d));
-    it = g_ct_tabs.emplace(device, d).first;
-  }
-  *out = it->second;
+    return dev_table_upload(device, "contour", T.data(), sizeof(float) * CT_TAB, (void**)&tab);
+  }));
+  *out = *d;
   return VITS_OK;
 }
 
@@ -333,8 +329,6 @@ static int contour_run(int device, hipStream_t stream, const float* x, long long
                        long long y_bstride, long long n_count, float* u_out, long long u_bstride, long long* steps_out, long long s_bstride,
                        const IntonReq* in = nullptr, int* cents_out = nullptr, long long c_bstride = 0) {
   if (B <= 0) return VITS_OK;
-  const StftTab* D = nullptr;
-  TRY(stft_tab_get(device, PT_N, &D));
   const float* d_T = nullptr;
   TRY(contour_tab_get(device, &d_T));
   const int* d_R = nullptr;
@@ -345,122 +339,88 @@ static int contour_run(int device, hipStream_t stream, const float* x, long long
     len32[b] = (int)h_len[b];
     vlen32[b] = (q.shift[b] && h_len[b] >= PT_M + 1) ? (int)h_len[b] : 0;  // (with `in`: set from the device's word, group by group)
   }
-  std::vector<std::pair<int, int>> groups;  // (first item, count): consecutive items whose scratch fits
-  size_t need = 0;
-  for (int b0 = 0; b0 < B;) {
-    long long mx = 0;
-    int c = 0;
-    while (b0 + c < B && c < 65535) {
-      const long long m2 = std::max(mx, h_len[b0 + c]);
-      if (contour_item_bytes(m2, in != nullptr) * (size_t)(c + 1) > (size_t)VITS_PITCH_MAX_SCRATCH) break;
-      mx = m2;
-      ++c;
-    }
-    if (!c) return fail(VITS_ERR_UNSUPPORTED, "contour: an item of %lld samples needs %zu bytes of scratch (limit %lld)", h_len[b0],
-                        contour_item_bytes(h_len[b0], in != nullptr), (long long)VITS_PITCH_MAX_SCRATCH);
-    need = std::max(need, contour_item_bytes(mx, in != nullptr) * (size_t)c);
-    groups.emplace_back(b0, c);
-    b0 += c;
-  }
-  HIP_TRY(hipSetDevice(device));
+  // in front of the groups: len | vlen | P | g
   const size_t tok_bytes = (size_t)B * q.Tx * 4, head = (2 * (size_t)B * 4 + 2 * tok_bytes + 63) / 64 * 64;
-  char* scr = nullptr;
-  if (hipMalloc((void**)&scr, head + need) != hipSuccess) return fail(VITS_ERR_NOMEM, "contour: scratch alloc of %zu bytes failed", head + need);
-  int* d_len = reinterpret_cast<int*>(scr);
-  int* d_vlen = d_len + B;
-  int* d_P = d_vlen + B;
-  float* d_g = reinterpret_cast<float*>(d_P + (size_t)B * q.Tx);
-  hipError_t e = hipMemcpyAsync(d_len, len32.data(), sizeof(int) * B, hipMemcpyHostToDevice, stream);
-  if (e == hipSuccess && !in) e = hipMemcpyAsync(d_vlen, vlen32.data(), sizeof(int) * B, hipMemcpyHostToDevice, stream);
-  if (e == hipSuccess && tok_bytes) e = hipMemcpyAsync(d_P, q.P.data(), tok_bytes, hipMemcpyHostToDevice, stream);
-  if (e == hipSuccess && tok_bytes) e = hipMemcpyAsync(d_g, q.g.data(), tok_bytes, hipMemcpyHostToDevice, stream);
+  struct { int *len, *vlen, *P; float* g; } hd{};     // what head() lays out, for every group
+  struct { float* gbar; long long t_bs; } grp{};      // the group's gain rows: front() sets them, finish() reads them
   std::vector<int> h_flag(in ? B : 0);
-  for (size_t gi = 0; gi < groups.size() && e == hipSuccess; ++gi) {
-    const int b0 = groups[gi].first, c = groups[gi].second;
-    long long mx = 0, vmx = 0;
-    for (int b = 0; b < c; ++b) mx = std::max(mx, h_len[b0 + b]);
-    const long long F = ct_frames(mx), t_bs = F + 1;
-    const float* xg = x + (long long)b0 * x_bstride;
-    const int *lg = d_len + b0, *vg = d_vlen + b0;
-    const int* cumg = d_cum ? d_cum + (long long)b0 * cum_bstride : nullptr;
-    const int* tlg = d_toklen ? d_toklen + b0 : nullptr;
-    char* p = scr + head;
-    long long* d_inc = reinterpret_cast<long long*>(p); p += 8 * (size_t)c * t_bs;
-    float* d_gbar = reinterpret_cast<float*>(p); p += 4 * (size_t)c * t_bs;
-    int* d_Pf = nullptr;
-    if (in) {  // the track, the offsets, the ratios and the items' words; then which items the vocoder takes
-      int* d_cents = cents_out ? cents_out + (long long)b0 * c_bstride : reinterpret_cast<int*>(p);
-      const long long c_bs = cents_out ? c_bstride : t_bs;
-      p += 4 * (size_t)c * t_bs;
-      int* d_o = reinterpret_cast<int*>(p); p += 4 * (size_t)c * t_bs;
-      d_Pf = reinterpret_cast<int*>(p); p += 4 * (size_t)c * t_bs;
-      int* d_flag = reinterpret_cast<int*>(p); p += 4 * (size_t)c;
-      inton_track_launch(stream, xg, x_bstride, lg, c, F, in->rate, d_cents, c_bs);
-      hipLaunchKernelGGL(intonation_item_kernel, dim3(c), dim3(IN_ITEM_T), 0, stream, lg, d_cents, c_bs, in->r_m, d_R, cumg, cum_bstride, tlg,
-                         (long long)hop, d_P + (size_t)b0 * q.Tx, (long long)q.Tx, q.Tx, d_o, d_Pf, t_bs, d_flag);
-      e = hipMemcpyAsync(h_flag.data() + b0, d_flag, sizeof(int) * c, hipMemcpyDeviceToHost, stream);
-      if (e == hipSuccess) e = hipStreamSynchronize(stream);
-      if (e != hipSuccess) break;
-      for (int b = b0; b < b0 + c; ++b) vlen32[b] = (h_flag[b] && h_len[b] >= PT_M + 1) ? (int)h_len[b] : 0;
-      e = hipMemcpyAsync(d_vlen + b0, vlen32.data() + b0, sizeof(int) * c, hipMemcpyHostToDevice, stream);
-      if (e != hipSuccess) break;
-    }
-    for (int b = 0; b < c; ++b) vmx = std::max(vmx, (long long)vlen32[b0 + b]);
-    const long long Fa = pt_frames_a(vmx), cap = 2 * (Fa + 1);
-    const long long s_bs = steps_out ? s_bstride : cap + 2;
-    const long long a_bs = (Fa + 2) * PT_NB, p_bs = cap * PT_NB, f_bs = cap * PT_N, u_bs = (cap - 1) * PT_H;
-    p += (8 - (p - scr) % 8) % 8;
-    long long* d_steps = steps_out ? steps_out + (long long)b0 * s_bstride : reinterpret_cast<long long*>(p);
-    p += 8 * (size_t)c * (cap + 2);
-    p += (8 - (p - scr) % 8) % 8;
-    if (in)
-      hipLaunchKernelGGL(intonation_tracks_kernel, dim3((unsigned)((F + 255) / 256), c), dim3(256), 0, stream, lg, cumg, cum_bstride, tlg,
-                         (long long)hop, d_g + (size_t)b0 * q.Tx, (long long)q.Tx, q.Tx, d_Pf, d_inc, d_gbar, t_bs);
-    else
-      hipLaunchKernelGGL(contour_tracks_kernel, dim3((unsigned)((F + 255) / 256), c), dim3(256), 0, stream, lg, cumg, cum_bstride, tlg, (long long)hop,
-                         d_P + (size_t)b0 * q.Tx, d_g + (size_t)b0 * q.Tx, (long long)q.Tx, q.Tx, d_inc, d_gbar, t_bs);
-    float* d_u = nullptr;
-    if (Fa && s_bs >= cap + 2) {
-      float* d_mag = reinterpret_cast<float*>(p); p += sizeof(float) * (size_t)c * a_bs;
-      unsigned* d_th = reinterpret_cast<unsigned*>(p); p += sizeof(unsigned) * (size_t)c * a_bs;
-      unsigned* d_phi = reinterpret_cast<unsigned*>(p); p += sizeof(unsigned) * (size_t)c * p_bs;
-      p += (8 - (p - scr) % 8) % 8;  // (the frames are written as float2)
-      float* d_fr = reinterpret_cast<float*>(p); p += sizeof(float) * (size_t)c * f_bs;
-      d_u = reinterpret_cast<float*>(p);
-      hipLaunchKernelGGL(contour_steps_kernel, dim3(c), dim3(64), 0, stream, vg, d_inc, t_bs, d_steps, s_bs);
-      hipLaunchKernelGGL(contour_analysis_kernel, dim3((unsigned)((Fa + 2 + SF_FPB - 1) / SF_FPB), c), dim3(64 * SF_FPB), 0, stream, xg, x_bstride,
-                         x_bstride, vg, d_mag, d_th, a_bs);
-      hipLaunchKernelGGL(pitch_phase_kernel<true>, dim3(c), dim3(64 * PT_WAVES), 0, stream, d_mag, d_th, a_bs, vg, 1LL, 1, 1, d_steps, s_bs, d_phi, p_bs);
-      hipLaunchKernelGGL(pitch_synth_kernel<true>, dim3((unsigned)((cap + SF_FPB - 1) / SF_FPB), c), dim3(64 * SF_FPB), 0, stream, d_mag, a_bs, d_phi,
-                         p_bs, vg, 1LL, 1, 1, d_steps, s_bs, D->d_win, D->d_tw, d_fr, f_bs);
-      if (u_out)
-        hipLaunchKernelGGL(pitch_ola_kernel<true>, dim3((unsigned)((u_bstride + 255) / 256), c), dim3(256), 0, stream, d_fr, f_bs, vg, 1LL, 1, 1, d_steps,
-                           s_bs, D->d_env, u_out + (long long)b0 * u_bstride, u_bstride, u_bstride);
-      else
-        hipLaunchKernelGGL(pitch_ola_kernel<true>, dim3((unsigned)((u_bs + 255) / 256), c), dim3(256), 0, stream, d_fr, f_bs, vg, 1LL, 1, 1, d_steps, s_bs,
-                           D->d_env, d_u, u_bs, u_bs);
-    } else if (u_out) {
-      hipMemsetAsync(u_out + (long long)b0 * u_bstride, 0, sizeof(float) * (size_t)c * u_bstride, stream);
-    }
-    if (!u_out && n_count > 0) {
-      const dim3 grid((unsigned)((n_count + CT_TILE - 1) / CT_TILE), c);
-      if (pcm) {
-        int16_t* yg = static_cast<int16_t*>(y) + (long long)b0 * y_bstride;
-        if (d_u) hipLaunchKernelGGL(contour_warp_kernel<int16_t>, grid, dim3(CT_TILE), 0, stream, d_u, u_bs, d_steps, s_bs, d_gbar, t_bs, lg, vg, d_T, yg, y_bstride, n_count, pcm_scale);
-        hipLaunchKernelGGL(contour_gain_kernel<int16_t>, grid, dim3(256), 0, stream, xg, x_bstride, d_gbar, t_bs, lg, vg, yg, y_bstride, n_count, pcm_scale);
-      } else {
-        float* yg = static_cast<float*>(y) + (long long)b0 * y_bstride;
-        if (d_u) hipLaunchKernelGGL(contour_warp_kernel<float>, grid, dim3(CT_TILE), 0, stream, d_u, u_bs, d_steps, s_bs, d_gbar, t_bs, lg, vg, d_T, yg, y_bstride, n_count, 1.f);
-        hipLaunchKernelGGL(contour_gain_kernel<float>, grid, dim3(256), 0, stream, xg, x_bstride, d_gbar, t_bs, lg, vg, yg, y_bstride, n_count, 1.f);
-      }
-    }
-  }
-  if (e == hipSuccess) e = hipGetLastError();
-  const hipError_t e2 = hipStreamSynchronize(stream);
-  hipFree(scr);
-  if (e == hipSuccess) e = e2;
-  if (e != hipSuccess) return fail(VITS_ERR_DEVICE, "contour: %s", hipGetErrorString(e));
-  return VITS_OK;
+  return pv_run<true>(
+      "contour", "", device, stream, h_len, B, head, u_out, u_bstride, [&](long long len) { return contour_item_bytes(len, in != nullptr); },
+      [&](char* scr) {
+        hd.len = reinterpret_cast<int*>(scr); hd.vlen = hd.len + B; hd.P = hd.vlen + B; hd.g = reinterpret_cast<float*>(hd.P + (size_t)B * q.Tx);
+        hipError_t e = hipMemcpyAsync(hd.len, len32.data(), sizeof(int) * B, hipMemcpyHostToDevice, stream);
+        if (e == hipSuccess && !in) e = hipMemcpyAsync(hd.vlen, vlen32.data(), sizeof(int) * B, hipMemcpyHostToDevice, stream);
+        if (e == hipSuccess && tok_bytes) e = hipMemcpyAsync(hd.P, q.P.data(), tok_bytes, hipMemcpyHostToDevice, stream);
+        if (e == hipSuccess && tok_bytes) e = hipMemcpyAsync(hd.g, q.g.data(), tok_bytes, hipMemcpyHostToDevice, stream);
+        return e;
+      },
+      // inc | gbar | (in: cents | o | Pf | flag) | (align 8) | steps | (align 8); the tracks, and which of the group's items the vocoder takes
+      [&](PvCarve& S, const PvGroup& g, PvGeom* v) {
+        const int b0 = g.b0, c = g.c;
+        const long long F = ct_frames(g.mx);
+        const long long t_bs = grp.t_bs = F + 1;
+        const int *lg = hd.len + b0, *cumg = d_cum ? d_cum + (long long)b0 * cum_bstride : nullptr, *tlg = d_toklen ? d_toklen + b0 : nullptr;
+        long long* d_inc = S.take<long long>((size_t)c * t_bs);
+        float* d_gbar = grp.gbar = S.take<float>((size_t)c * t_bs);
+        int* d_Pf = nullptr;
+        if (in) {  // the track, the offsets, the ratios and the items' words; then which items the vocoder takes
+          int* d_track = S.take<int>((size_t)c * t_bs);
+          int* d_cents = cents_out ? cents_out + (long long)b0 * c_bstride : d_track;
+          const long long c_bs = cents_out ? c_bstride : t_bs;
+          int* d_o = S.take<int>((size_t)c * t_bs);
+          d_Pf = S.take<int>((size_t)c * t_bs);
+          int* d_flag = S.take<int>(c);
+          inton_track_launch(stream, x + (long long)b0 * x_bstride, x_bstride, lg, c, F, in->rate, d_cents, c_bs);
+          hipLaunchKernelGGL(intonation_item_kernel, dim3(c), dim3(IN_ITEM_T), 0, stream, lg, d_cents, c_bs, in->r_m, d_R, cumg, cum_bstride, tlg,
+                             (long long)hop, hd.P + (size_t)b0 * q.Tx, (long long)q.Tx, q.Tx, d_o, d_Pf, t_bs, d_flag);
+          hipError_t e = hipMemcpyAsync(h_flag.data() + b0, d_flag, sizeof(int) * c, hipMemcpyDeviceToHost, stream);
+          if (e == hipSuccess) e = hipStreamSynchronize(stream);
+          if (e != hipSuccess) return e;
+          for (int b = b0; b < b0 + c; ++b) vlen32[b] = (h_flag[b] && h_len[b] >= PT_M + 1) ? (int)h_len[b] : 0;
+          e = hipMemcpyAsync(hd.vlen + b0, vlen32.data() + b0, sizeof(int) * c, hipMemcpyHostToDevice, stream);
+          if (e != hipSuccess) return e;
+        }
+        long long vmx = 0;
+        for (int b = 0; b < c; ++b) vmx = std::max(vmx, (long long)vlen32[b0 + b]);
+        const long long Fa = pt_frames_a(vmx), cap = 2 * (Fa + 1);
+        v->s_bs = steps_out ? s_bstride : cap + 2;
+        S.align8();
+        long long* d_steps = S.take<long long>((size_t)c * (cap + 2));
+        v->steps = steps_out ? steps_out + (long long)b0 * s_bstride : d_steps;
+        S.align8();
+        if (in)
+          hipLaunchKernelGGL(intonation_tracks_kernel, dim3((unsigned)((F + 255) / 256), c), dim3(256), 0, stream, lg, cumg, cum_bstride, tlg,
+                             (long long)hop, hd.g + (size_t)b0 * q.Tx, (long long)q.Tx, q.Tx, d_Pf, d_inc, d_gbar, t_bs);
+        else
+          hipLaunchKernelGGL(contour_tracks_kernel, dim3((unsigned)((F + 255) / 256), c), dim3(256), 0, stream, lg, cumg, cum_bstride, tlg, (long long)hop,
+                             hd.P + (size_t)b0 * q.Tx, hd.g + (size_t)b0 * q.Tx, (long long)q.Tx, q.Tx, d_inc, d_gbar, t_bs);
+        v->it = Items{hd.vlen + b0, 1}; v->Fs = cap;
+        if (Fa && v->s_bs >= cap + 2) {
+          v->Fa = Fa;
+          hipLaunchKernelGGL(contour_steps_kernel, dim3(c), dim3(64), 0, stream, v->it.units, d_inc, t_bs, v->steps, v->s_bs);
+        }
+        return hipSuccess;
+      },
+      [&](PvCarve&, const PvGroup& g, const PvGeom& v, const StftTab&, float* mag, unsigned* th, long long a_bs) -> const float* {
+        hipLaunchKernelGGL(contour_analysis_kernel, dim3((unsigned)((v.Fa + 2 + SF_FPB - 1) / SF_FPB), g.c), dim3(64 * SF_FPB), 0, stream,
+                           x + (long long)g.b0 * x_bstride, x_bstride, x_bstride, v.it.units, mag, th, a_bs);
+        return mag;
+      },
+      // u warped along the step table and scaled by the gain curve; the items the vocoder left alone are y = G x
+      [&](PvCarve&, const PvGroup& g, const PvGeom& v, const float* u, long long u_bs) {
+        if (u_out || n_count <= 0) return;
+        const dim3 grid((unsigned)((n_count + CT_TILE - 1) / CT_TILE), g.c);
+        const float* xg = x + (long long)g.b0 * x_bstride;
+        const int *lg = hd.len + g.b0, *vg = v.it.units;
+        auto out = [&](auto* y0, float scale) {
+          using OUT = std::remove_pointer_t<decltype(y0)>;
+          OUT* yg = y0 + (long long)g.b0 * y_bstride;
+          if (u) hipLaunchKernelGGL(contour_warp_kernel<OUT>, grid, dim3(CT_TILE), 0, stream, u, u_bs, v.steps, v.s_bs, grp.gbar, grp.t_bs, lg, vg, d_T, yg, y_bstride, n_count, scale);
+          hipLaunchKernelGGL(contour_gain_kernel<OUT>, grid, dim3(256), 0, stream, xg, x_bstride, grp.gbar, grp.t_bs, lg, vg, yg, y_bstride, n_count, scale);
+        };
+        if (pcm) out(static_cast<int16_t*>(y), pcm_scale);
+        else out(static_cast<float*>(y), 1.f);
+      });
 }
 
 // ---- the parity doors ---------------------------------------------------------------------------------------------------
@@ -489,10 +449,7 @@ static int contour_op(int device, const float* x, const int64_t* lengths, int32_
   const std::vector<long long> len64(lengths, lengths + B);
   const long long Nu = (long long)PT_H * (2 * (N / PT_H + 2) - 1), Ns = 2 * (N / PT_H + 2) + 2, Nc = 1 + N / PT_H;
   OpDoor d(what, device);
-  // every item's own samples only: what lies at and beyond lengths[b] never reaches the device
-  float* dx = d.out<float>((size_t)B * N, 0);
-  for (int b = 0; b < B && d.ok(); ++b)
-    if (lengths[b]) d.hip(hipMemcpy(dx + (size_t)b * N, x + (size_t)b * N, sizeof(float) * (size_t)lengths[b], hipMemcpyHostToDevice));
+  float* dx = d.up_items(x, lengths, B, N);
   int* dc = no_tokens ? nullptr : d.up(cum, (size_t)B * Tx);
   int* dt = d.up(tl32.data(), B);
   float* dy = stretch ? d.out<float>((size_t)B * Nu) : d.out<float>((size_t)B * N);
@@ -527,10 +484,7 @@ int vits_op_f0_track(int device, const float* x, const int64_t* lengths, int32_t
   TRY(inton_rate_arg(rate));
   const long long Nc = 1 + N / PT_H;
   OpDoor d("f0 track", device);
-  // every item's own samples only: what lies at and beyond lengths[b] never reaches the device
-  float* dx = d.out<float>((size_t)B * N, 0);
-  for (int b = 0; b < B && d.ok(); ++b)
-    if (lengths[b]) d.hip(hipMemcpy(dx + (size_t)b * N, x + (size_t)b * N, sizeof(float) * (size_t)lengths[b], hipMemcpyHostToDevice));
+  float* dx = d.up_items(x, lengths, B, N);
   int* dl = d.up(len32.data(), B);
   int* dc = d.dev<int>((size_t)B * Nc);
   if (d.ok()) inton_track_launch(nullptr, dx, N, dl, B, Nc, rate, dc, Nc);

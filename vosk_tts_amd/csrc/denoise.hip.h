@@ -15,21 +15,20 @@ __device__ __forceinline__ float dn_gain(float re, float im, float sb) {
 
 // Frames [f_begin, f_begin + f_count) of every item; wave w of workgroup blockIdx.x owns frame f_begin + blockIdx.x * SF_FPB + w.
 //   x        item b's input at x + b * x_bstride; x[j] is sample x_off + j, and only 0 <= j < x_n is ever read
-//   len      valid samples of item b: len_frames[b] * len_mul (len_frames null: len_mul itself); an item shorter than n/2 + 1 has
+//   len      valid samples of item b: it.len_in(b) (ragged.hip.h); an item shorter than n/2 + 1 has
 //            no frames (denoise_ola_kernel passes it through)
 //   out      mag_only 0: the windowed inverse frames, out[b * out_bstride + (f - f_begin) * n + i]
 //            mag_only 1: |X_f[k]|, out[b * out_bstride + (f - f_begin) * (n/2 + 1) + k]  (the bias; no gain, no inverse)
-__global__ __launch_bounds__(64 * SF_FPB) void denoise_frames_kernel(const float* __restrict__ x, long long x_bstride, long long x_off,
-                                                                     long long x_n, const int* __restrict__ len_frames, long long len_mul,
-                                                                     const float* __restrict__ win, const float2* __restrict__ tw,
+__global__ __launch_bounds__(64 * SF_FPB) void denoise_frames_kernel(const float* __restrict__ x, long long x_bstride, long long x_off, long long x_n,
+                                                                     const Items it, const float* __restrict__ win, const float2* __restrict__ tw,
                                                                      const float* __restrict__ bias, float strength, int n, int log2m,
-                                                                     long long f_begin, int f_count, float* __restrict__ out,
-                                                                     long long out_bstride, int mag_only) {
+                                                                     long long f_begin, int f_count, float* __restrict__ out, long long out_bstride,
+                                                                     int mag_only) {
   __shared__ float lds[SF_FPB][4][SF_PLANE];
   const int M = n >> 1, hop = n >> 2;
   const int wv = threadIdx.x >> 6, t = threadIdx.x & 63;
   const int b = blockIdx.y;
-  const long long len = len_frames ? len_frames[b] * len_mul : len_mul;
+  const long long len = it.len_in(b);
   const long long F = len >= M + 1 ? 1 + len / hop : 0;
   const long long fi = (long long)blockIdx.x * SF_FPB + wv;  // index in the scratch
   const long long f = f_begin + fi;
@@ -68,15 +67,14 @@ __global__ __launch_bounds__(64 * SF_FPB) void denoise_frames_kernel(const float
 // is copied from x (same addressing as denoise_frames_kernel) and is 0 beyond its length.
 __global__ __launch_bounds__(256) void denoise_ola_kernel(const float* __restrict__ fr, long long fr_bstride, long long f_begin,
                                                           const float* __restrict__ x, long long x_bstride, long long x_off, long long x_n,
-                                                          const int* __restrict__ len_frames, long long len_mul,
-                                                          const float* __restrict__ inv_env, int n, float* __restrict__ y,
+                                                          const Items it, const float* __restrict__ inv_env, int n, float* __restrict__ y,
                                                           long long y_bstride, long long n_begin, long long n_count) {
   const int b = blockIdx.y;
   const long long jo = (long long)blockIdx.x * 256 + threadIdx.x;
   if (jo >= n_count) return;
   const long long j = n_begin + jo;
   const int M = n >> 1, hop = n >> 2;
-  const long long len = len_frames ? len_frames[b] * len_mul : len_mul;
+  const long long len = it.len_in(b);
   float v = 0.f;
   if (len >= M + 1) {
     const long long F = 1 + len / hop;
@@ -118,16 +116,16 @@ static size_t denoise_scratch_elems(int n, long long n_count) { return (size_t)(
 
 // Outputs [n_begin, n_begin + n_count) of B items on `stream` (capturable: no allocation, no synchronisation).  scratch holds
 // B * scratch_bstride floats, scratch_bstride >= denoise_scratch_elems(n, n_count).  Arguments as for the two kernels.
-static void denoise_launch(hipStream_t stream, const StftTab& T, const float* x, long long x_bstride, long long x_off, long long x_n,
-                           const int* len_frames, long long len_mul, int B, const float* d_bias, float strength, float* scratch,
-                           long long scratch_bstride, float* y, long long y_bstride, long long n_begin, long long n_count) {
+static void denoise_launch(hipStream_t stream, const StftTab& T, const float* x, long long x_bstride, long long x_off, long long x_n, const Items& it,
+                           int B, const float* d_bias, float strength, float* scratch, long long scratch_bstride, float* y, long long y_bstride,
+                           long long n_begin, long long n_count) {
   if (n_count <= 0 || B <= 0) return;
   long long f_begin = 0, f_count = 0;
   denoise_frame_span(T.n, n_begin, n_count, &f_begin, &f_count);
-  hipLaunchKernelGGL(denoise_frames_kernel, dim3((unsigned)cdiv((int)f_count, SF_FPB), B), dim3(64 * SF_FPB), 0, stream, x, x_bstride, x_off, x_n,
-                     len_frames, len_mul, T.d_win, T.d_tw, d_bias, strength, T.n, T.log2m, f_begin, (int)f_count, scratch, scratch_bstride, 0);
+  hipLaunchKernelGGL(denoise_frames_kernel, dim3((unsigned)cdiv((int)f_count, SF_FPB), B), dim3(64 * SF_FPB), 0, stream, x, x_bstride, x_off, x_n, it,
+                     T.d_win, T.d_tw, d_bias, strength, T.n, T.log2m, f_begin, (int)f_count, scratch, scratch_bstride, 0);
   hipLaunchKernelGGL(denoise_ola_kernel, dim3((unsigned)((n_count + 255) / 256), B), dim3(256), 0, stream, scratch, scratch_bstride, f_begin, x,
-                     x_bstride, x_off, x_n, len_frames, len_mul, T.d_env, T.n, y, y_bstride, n_begin, n_count);
+                     x_bstride, x_off, x_n, it, T.d_env, T.n, y, y_bstride, n_begin, n_count);
 }
 
 // ---- the bias of a vocoder, cached in the model per filter_length -----------------------------------------------------------
@@ -149,9 +147,8 @@ static int denoise_bias_get(vits_model* m, int n, const float** d_bias, const st
     OpDoor d("denoise: bias", m->device);
     float* dx = d.up(audio.data(), (size_t)(M + 1));  // frame 0 reads samples 0 .. n/2 only
     float* db = d.dev<float>((size_t)(M + 1));
-    if (d.ok())
-      hipLaunchKernelGGL(denoise_frames_kernel, dim3(1, 1), dim3(64 * SF_FPB), 0, nullptr, dx, 0, 0, (long long)(M + 1), nullptr, S, T->d_win, T->d_tw,
-                         nullptr, 0.f, n, T->log2m, 0, 1, db, 0, 1);
+    if (d.ok()) hipLaunchKernelGGL(denoise_frames_kernel, dim3(1, 1), dim3(64 * SF_FPB), 0, nullptr, dx, 0, 0, (long long)(M + 1), Items{nullptr, S},
+                                   T->d_win, T->d_tw, nullptr, 0.f, n, T->log2m, 0, 1, db, 0, 1);
     d.finish();
     d.down(mag.data(), db, (size_t)(M + 1));
     if (!d.ok()) return d.rc();
@@ -209,7 +206,7 @@ int vits_op_denoise(int device, const float* x, const int64_t* lengths, int32_t 
   int* dl = d.up(len32.data(), B);
   float* ds = d.dev<float>(B * sc);
   float* dy = d.out<float>((size_t)B * Ny);
-  if (d.ok()) denoise_launch(nullptr, *T, dx, N, 0, N, dl, 1, B, db, strength, ds, (long long)sc, dy, Ny, 0, Ny);
+  if (d.ok()) denoise_launch(nullptr, *T, dx, N, 0, N, Items{dl, 1}, B, db, strength, ds, (long long)sc, dy, Ny, 0, Ny);
   d.finish();
   d.down(y, dy, (size_t)B * Ny);
   return d.rc();

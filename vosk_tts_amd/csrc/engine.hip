@@ -132,6 +132,7 @@ static int persist_cfg() {
 #include "engine_launch.hip.h"
 #include "engine_stages.hip.h"
 #include "op_door.hip.h"
+#include "ragged.hip.h"
 #include "resample.hip.h"
 #include "stft.hip.h"
 #include "denoise.hip.h"

@@ -355,8 +355,8 @@ static int phase2_launch(FastFront* F, FastBack* Bk, bool solo, bool pcm, FastBa
     if (R) {  // the resampler reads each item's own [0, len) of the decoder's output; at int16 it stands where pcm16_kernel stands
       ProfScope ps(s, "out.resample", 2.0 * B * R->n_cap * T->P.taps, pcm ? "resample_kernel<int16>" : "resample_kernel<float>");
       const int hop = F->s->m->hp.hop_length;
-      if (pcm) resample_launch<int16_t>(s->stream, *T, Bk->out_d, stride, 0, stride, s->len_y, hop, B, static_cast<int16_t*>(R->y_d), R->n_cap, 0, R->n_cap, 1.f, s->dv);
-      else resample_launch<float>(s->stream, *T, Bk->out_d, stride, 0, stride, s->len_y, hop, B, static_cast<float*>(R->y_d), R->n_cap, 0, R->n_cap, 1.f, nullptr);
+      if (pcm) resample_launch<int16_t>(s->stream, *T, Bk->out_d, stride, 0, stride, Items{s->len_y, hop}, B, static_cast<int16_t*>(R->y_d), R->n_cap, 0, R->n_cap, 1.f, s->dv);
+      else resample_launch<float>(s->stream, *T, Bk->out_d, stride, 0, stride, Items{s->len_y, hop}, B, static_cast<float*>(R->y_d), R->n_cap, 0, R->n_cap, 1.f, nullptr);
       hipMemcpyAsync(R->y_h, R->y_d, (size_t)B * R->n_cap * (pcm ? sizeof(int16_t) : sizeof(float)), hipMemcpyDeviceToHost, s->stream);
     } else if (pcm) {
       {
@@ -393,6 +393,7 @@ static int synth_fast(vits_model* m, const int64_t* ids, const int64_t* lengths,
   if (q.rate) TRY(resample_get(m->device, hp.sampling_rate, q.rate, &q.T));
   if (q.wm.on) TRY(stft_tab_get(m->device, WM_N, &q.wm.T));  // (include/vits_watermark.h: the frame transform's tables, as early)
   const ResampleTab* T = q.T;
+  const Rate rt = rate_of(T);
   const NormReq& lq = q.norm;
   const bool pcm = q.pcm;
   const int TxB = (Tx + 7) / 8 * 8;
@@ -417,7 +418,7 @@ static int synth_fast(vits_model* m, const int64_t* ids, const int64_t* lengths,
   }
   // ---- inputs -> pinned block
   SynthDev* hv = reinterpret_cast<SynthDev*>(F->io_h);
-  hv->rate_L = T ? T->P.L : 1; hv->rate_M = T ? T->P.M : 1;
+  hv->rate_L = rt.L; hv->rate_M = rt.M;
   hv->scales[0] = pr.scales[0]; hv->scales[1] = pr.scales[1]; hv->scales[2] = pr.scales[2];
   hv->pcm_scale = q.pcm_scale;
   hv->seed = opts ? opts->seed : 0;
@@ -530,7 +531,7 @@ static int synth_fast(vits_model* m, const int64_t* ids, const int64_t* lengths,
       char* h_out = host_out(esz * (size_t)So);
       if (!h_out) return VITS_ERR_NOMEM;
       TRY(finish(h_out, hipMemcpyAsync(h_out, d_out, esz * (size_t)So, hipMemcpyDeviceToHost, st)));
-      *out_samples = doc_results(q.doc, doc_blk.data(), doc_cum.data(), TxB, lengths, Tx, hp.hop_length, T ? T->P.L : 1, T ? T->P.M : 1);
+      *out_samples = doc_results(q.doc, doc_blk.data(), doc_cum.data(), TxB, lengths, Tx, hp.hop_length, rt.L, rt.M);
       if (*out_samples < So) memset(h_out + esz * (size_t)*out_samples, 0, esz * (size_t)(So - *out_samples));  // (trim: the row was sized by the bound)
       if (d_res) norm_req_results(lq, res.data(), 1);
       return VITS_OK;
@@ -558,9 +559,9 @@ static int synth_fast(vits_model* m, const int64_t* ids, const int64_t* lengths,
     norm_ws_layout(lq, W, B, stride, &NS);
     TRY(phase2_launch(F, Bk, solo, false, R, T, pr.per_item_noise));
     const float* x_d = R ? static_cast<const float*>(R->y_d) : Bk->out_d;
-    const int rL = T ? T->P.L : 1, rM = T ? T->P.M : 1;
-    if (pcm) norm_launch<int16_t>(st, lq, NS, x_d, stride, stride, Bk->s->len_y, hp.hop_length, rL, rM, B, static_cast<int16_t*>(W.y_d()), stride, stride, q.pcm_scale, Bk->s);
-    else norm_launch<float>(st, lq, NS, x_d, stride, stride, Bk->s->len_y, hp.hop_length, rL, rM, B, static_cast<float*>(W.y_d()), stride, stride, 1.f, Bk->s);
+    const Items it = items_at(T, Bk->s->len_y, hp.hop_length, stride);
+    if (pcm) norm_launch<int16_t>(st, lq, NS, x_d, stride, it, B, static_cast<int16_t*>(W.y_d()), stride, stride, q.pcm_scale, Bk->s);
+    else norm_launch<float>(st, lq, NS, x_d, stride, it, B, static_cast<float*>(W.y_d()), stride, stride, 1.f, Bk->s);
     hipMemcpyAsync(W.y_h(), W.y_d(), (size_t)B * stride * esz, hipMemcpyDeviceToHost, st);
     hipMemcpyAsync(W.res_h(), W.S.res, sizeof(float) * 4 * (size_t)B, hipMemcpyDeviceToHost, st);
     src_h = W.y_h();
@@ -583,6 +584,7 @@ static int synth_eager(vits_model* m, const int64_t* ids, const int64_t* lengths
   if (q.rate) TRY(resample_get(m->device, hp.sampling_rate, q.rate, &q.T));
   if (q.wm.on) TRY(stft_tab_get(m->device, WM_N, &q.wm.T));  // (include/vits_watermark.h: the frame transform's tables, as early)
   const ResampleTab* T = q.T;
+  const Rate rt = rate_of(T);
   std::vector<float> res((size_t)B * 4);  // (the last stage's result rows: declared before the stage, whose end waits for the stream)
   HostStage hs(m);
   std::vector<int64_t> ylen;
@@ -591,7 +593,7 @@ static int synth_eager(vits_model* m, const int64_t* ids, const int64_t* lengths
   float* z = nullptr;
   TRY(acoustic_host(hs, ids, lengths, B, Tx, scales, sid, opts, ylen, Ty, z, (token_ends || q.doc.token_ends) ? &cum : nullptr, q.doc.on));
   if (token_ends)
-    for (int b = 0; b < B; ++b) marks_fill_host(cum.data() + (size_t)b * Tx, lengths[b], Tx, hp.hop_length, T ? T->P.L : 1, T ? T->P.M : 1, token_ends + (size_t)b * Tx);
+    for (int b = 0; b < B; ++b) marks_fill_host(cum.data() + (size_t)b * Tx, lengths[b], Tx, hp.hop_length, rt.L, rt.M, token_ends + (size_t)b * Tx);
   vits_session* s = hs.s;
   s->ragged = B > 1;
   s->solo = q.doc.on || (opts && (opts->flags & VITS_FLAG_SOLO_BATCH));
@@ -624,7 +626,7 @@ static int synth_eager(vits_model* m, const int64_t* ids, const int64_t* lengths
   *out = h_out;
   *out_samples = So;
   if (q.doc.on) {
-    *out_samples = doc_results(q.doc, doc_blk.data(), cum.data(), Tx, lengths, Tx, hp.hop_length, T ? T->P.L : 1, T ? T->P.M : 1);
+    *out_samples = doc_results(q.doc, doc_blk.data(), cum.data(), Tx, lengths, Tx, hp.hop_length, rt.L, rt.M);
     if (*out_samples < So)  // (trim: the row was sized by the bound)
       memset(static_cast<char*>(h_out) + esz * (size_t)*out_samples, 0, esz * (size_t)(So - *out_samples));
   }

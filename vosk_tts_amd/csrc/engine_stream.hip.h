@@ -163,7 +163,8 @@ int vits_stream_open_rate(vits_model* m, const int64_t* ids, int32_t Tx, const f
     const int rc = acoustic_host(*st->hs, ids, &len, 1, Tx, scales, &sid, opts, ylen, Ty, z, &cum);
     if (rc == VITS_OK) {
       st->marks.resize(Tx);
-      marks_fill_host(cum.data(), Tx, Tx, m->hp.hop_length, T ? T->P.L : 1, T ? T->P.M : 1, st->marks.data());
+      const Rate rt = rate_of(T);
+      marks_fill_host(cum.data(), Tx, Tx, m->hp.hop_length, rt.L, rt.M, st->marks.data());
       return stream_start(st, z, (int)Ty, chunk_frames, out, total_samples);
     }
     vits_stream_close(st);
@@ -243,12 +244,12 @@ int vits_stream_next(vits_stream* st, float* audio, int64_t capacity, int64_t* n
   HIP_TRY(hipStreamWaitEvent(s->copy_stream, w.done, 0));
   if (st->rs) {
     // the window's slot holds input samples [w.start * hop, (w.start + width) * hop); beyond the utterance's end the filter sees zeros
-    resample_launch<float>(s->copy_stream, *st->rs, w.aud, 0, (long long)w.start * hop, (long long)w.width * hop, nullptr, (long long)st->Ty * hop, 1, st->d_rs, 0,
+    resample_launch<float>(s->copy_stream, *st->rs, w.aud, 0, (long long)w.start * hop, (long long)w.width * hop, Items{nullptr, (long long)st->Ty * hop}, 1, st->d_rs, 0,
                            n_first, n, 1.f, nullptr);
     HIP_TRY(hipMemcpyAsync(st->h_pin, st->d_rs, sizeof(float) * n, hipMemcpyDeviceToHost, s->copy_stream));
   } else if (st->dn) {
     // outputs [lo * hop, hi * hop) of the utterance's transform: its frames read the slot, which holds samples [w.start * hop, ...)
-    denoise_launch(s->copy_stream, *st->dn, w.aud, 0, (long long)w.start * hop, (long long)w.width * hop, nullptr, (long long)st->Ty * hop, 1, st->dn_bias,
+    denoise_launch(s->copy_stream, *st->dn, w.aud, 0, (long long)w.start * hop, (long long)w.width * hop, Items{nullptr, (long long)st->Ty * hop}, 1, st->dn_bias,
                    st->dn_strength, st->d_dn_scr, (long long)st->dn_scr_elems, st->d_dn, 0, (long long)lo * hop, n);
     HIP_TRY(hipMemcpyAsync(st->h_pin, st->d_dn, sizeof(float) * n, hipMemcpyDeviceToHost, s->copy_stream));
   } else {

@@ -315,20 +315,16 @@ static int inton_rate_arg(int rate) {
 }
 
 // TAB of include/vits_intonation.h on the device, one copy per device (uploaded on first use, outside any capture; never freed)
-static std::mutex g_in_mu;
-static std::map<int, int*> g_in_tabs;
+static DevTabs<int, int*> g_in_tabs;
 
 static int inton_tab_get(int device, const int** out) {
-  std::lock_guard<std::mutex> g(g_in_mu);
-  auto it = g_in_tabs.find(device);
-  if (it == g_in_tabs.end()) {
+  int* const* d = nullptr;
+  TRY(g_in_tabs.get(device, &d, [&](int*& tab) {
     std::vector<int> T(IN_TABN);
     for (int j = 0; j < IN_TABN; ++j) T[j] = (int)lround(1000.0 * pow(2.0, (double)(j - IN_CENTS) / 1200.0));
-    int* d = nullptr;
-    TRY(dev_table_upload(device, "intonation", T.data(), sizeof(int) * IN_TABN, (void**)&d));
-    it = g_in_tabs.emplace(device, d).first;
-  }
-  *out = it->second;
+    return dev_table_upload(device, "intonation", T.data(), sizeof(int) * IN_TABN, (void**)&tab);
+  }));
+  *out = *d;
   return VITS_OK;
 }
 

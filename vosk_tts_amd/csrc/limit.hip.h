@@ -1,6 +1,6 @@
 // limit.hip.h -- the look-ahead peak limiter of include/vits_limit.h: envelope (sample peak, or true peak through the 4x polyphase
 // interpolator), look-ahead minimum, release, box attack and the gain applied, for every item of a batch on the device.  Part of the ONE
-// translation unit engine.hip (included there, behind loudness.hip.h, whose length helper, measurement and profiling scope it uses).
+// translation unit engine.hip (included there, behind loudness.hip.h, whose measurement and profiling scope it uses).
 //
 // Index shift: the definition runs k over [-W, len); here j = k + W >= 0, so e[k] is d-space value j and s[n] averages j in [n, n + W].
 // m[k] = min r[k .. k+W] is r(max p[j-W .. j]): a trailing window in j, and r is non-increasing in p, so the maximum is slid over fp32 p.
@@ -100,15 +100,14 @@ __device__ __forceinline__ double lm_need(double c, double g, float p) {
   return gp > 0.0 ? fmin(1.0, c / gp) : 1.0;
 }
 
-// p [B, N]; tpeak [B, ntiles], written for the tiles that hold samples of the item
-__global__ __launch_bounds__(LM_THREADS) void limit_env_kernel(const float* __restrict__ x, long long x_bstride, long long N,
-                                                               const int* __restrict__ len_frames, long long len_mul, int L, int M, int mode,
+// p [B, it.cap]; tpeak [B, ntiles], written for the tiles that hold samples of the item
+__global__ __launch_bounds__(LM_THREADS) void limit_env_kernel(const float* __restrict__ x, long long x_bstride, const Items it, int mode,
                                                                const LimTab tab, int ntiles, float* __restrict__ p, float* __restrict__ tpeak) {
   __shared__ float xs[VITS_LIMIT_TILE + 2 * LM_HALF];
   __shared__ float tb[VITS_LIMIT_OVERSAMPLE * LM_TAPS];
   __shared__ float pk[LM_THREADS];
   const int b = blockIdx.y, k = blockIdx.x, t = threadIdx.x;
-  const long long len = ld_len(len_frames, len_mul, L, M, N, b), n0 = (long long)k * VITS_LIMIT_TILE;
+  const long long len = it.len_out(b), n0 = (long long)k * VITS_LIMIT_TILE;
   if (n0 >= len) return;  // (the whole workgroup)
   const float* xb = x + (long long)b * x_bstride;
   for (int i = t; i < VITS_LIMIT_TILE + 2 * LM_HALF; i += LM_THREADS) {
@@ -132,7 +131,7 @@ __global__ __launch_bounds__(LM_THREADS) void limit_env_kernel(const float* __re
         v = fmaxf(v, fabsf(acc));
       }
     }
-    p[(long long)b * N + n0 + l] = v;
+    p[(long long)b * it.cap + n0 + l] = v;
     pm = fmaxf(pm, v);
   }
   pk[t] = pm;
@@ -145,11 +144,10 @@ __global__ __launch_bounds__(LM_THREADS) void limit_env_kernel(const float* __re
 }
 
 // gv[b] = {g, max p}.  src 0: prm.gain; 1: res0[b].gain (pass 1 of the LUFS form); 2: pass 2, res1 the measurement of y_0.
-__global__ __launch_bounds__(64) void limit_gain_kernel(const int* __restrict__ len_frames, long long len_mul, int L, int M, long long N,
-                                                        int ntiles, const float* __restrict__ tpeak, int src, const LimPrm prm,
+__global__ __launch_bounds__(64) void limit_gain_kernel(const Items it, int ntiles, const float* __restrict__ tpeak, int src, const LimPrm prm,
                                                         const float* __restrict__ res0, const float* __restrict__ res1, float* __restrict__ gv) {
   const int b = blockIdx.x, t = threadIdx.x;
-  const long long len = ld_len(len_frames, len_mul, L, M, N, b);
+  const long long len = it.len_out(b);
   const int nt = (int)((len + VITS_LIMIT_TILE - 1) / VITS_LIMIT_TILE);
   float pm = 0.f;
   for (int k = t; k < nt; k += 64) pm = fmaxf(pm, tpeak[(long long)b * ntiles + k]);
@@ -221,16 +219,15 @@ __device__ __forceinline__ double lm_release(const LimPrm& prm, const double* Pk
 }
 
 // cend [B, ntj]: the deficit at the end of j-tile kt entered with 0; written for kt TILE < len + W
-__global__ __launch_bounds__(LM_THREADS) void limit_scan_kernel(const float* __restrict__ p, long long N, const int* __restrict__ len_frames,
-                                                                long long len_mul, int L, int M, const LimPrm prm,
+__global__ __launch_bounds__(LM_THREADS) void limit_scan_kernel(const float* __restrict__ p, const Items it, const LimPrm prm,
                                                                 const float* __restrict__ gv, int ntj, double* __restrict__ cend) {
   constexpr int SPAN = VITS_LIMIT_TILE + VITS_LIMIT_MAX_LOOKAHEAD;
   __shared__ float pa[SPAN], pb[SPAN];
   __shared__ double sc[2][LM_THREADS];
   const int b = blockIdx.y, kt = blockIdx.x;
-  const long long len = ld_len(len_frames, len_mul, L, M, N, b), j0 = (long long)kt * VITS_LIMIT_TILE;
+  const long long len = it.len_out(b), j0 = (long long)kt * VITS_LIMIT_TILE;
   if (j0 >= len + prm.W) return;  // (the whole workgroup)
-  lm_fill(pa, p + (long long)b * N, j0 - prm.W, SPAN, len);
+  lm_fill(pa, p + (long long)b * it.cap, j0 - prm.W, SPAN, len);
   int off2;
   const float* mq = lm_wmax(pa, pb, SPAN, prm.W + 1, &off2);
   const double e = lm_release<LM_RS, false>(prm, prm.PS, mq, off2, (double)gv[b * 2], 0.0, sc, nullptr);
@@ -238,11 +235,11 @@ __global__ __launch_bounds__(LM_THREADS) void limit_scan_kernel(const float* __r
 }
 
 // cin [B, ntj]: the deficit j-tile kt is entered with.  One wave per item.
-__global__ __launch_bounds__(64) void limit_carry_kernel(const int* __restrict__ len_frames, long long len_mul, int L, int M, long long N,
-                                                         const LimPrm prm, int ntj, const double* __restrict__ cend, double* __restrict__ cin) {
+__global__ __launch_bounds__(64) void limit_carry_kernel(const Items it, const LimPrm prm, int ntj, const double* __restrict__ cend,
+                                                         double* __restrict__ cin) {
   __shared__ double es[64];
   const int b = blockIdx.x, t = threadIdx.x;
-  const long long len = ld_len(len_frames, len_mul, L, M, N, b);
+  const long long len = it.len_out(b);
   const int nt = (int)((len + prm.W + VITS_LIMIT_TILE - 1) / VITS_LIMIT_TILE);
   double v = 0.0;
   for (int k0 = 0; k0 < nt; k0 += 64) {
@@ -259,32 +256,31 @@ __global__ __launch_bounds__(64) void limit_carry_kernel(const int* __restrict__
   }
 }
 
-// y[b, n] for 0 <= n < n_count (exactly 0 at and beyond len, where x and p are not read); s_out (nullable) [B, N]: fp32(s), 1 beyond len;
+// y[b, n] for 0 <= n < n_count (exactly 0 at and beyond len, where x and p are not read); s_out (nullable) [B, it.cap]: fp32(s), 1 beyond len;
 // smin [B, ntiles]: min fp32(s) over the tile's samples of the item, written for the tiles that hold some.
 template <typename OUT>
-__global__ __launch_bounds__(LM_THREADS) void limit_apply_kernel(const float* __restrict__ x, long long x_bstride, long long N,
-                                                                 const int* __restrict__ len_frames, long long len_mul, int L, int M,
+__global__ __launch_bounds__(LM_THREADS) void limit_apply_kernel(const float* __restrict__ x, long long x_bstride, const Items it,
                                                                  const float* __restrict__ p, const LimPrm prm, const float* __restrict__ gv,
                                                                  int ntiles, int ntj, const double* __restrict__ cin, OUT* __restrict__ y,
-                                                                 long long y_bstride, long long n_count, float scale,
-                                                                 float* __restrict__ s_out, float* __restrict__ smin) {
+                                                                 long long y_bstride, long long n_count, float scale, float* __restrict__ s_out,
+                                                                 float* __restrict__ smin) {
   constexpr int NJ = LM_RA * LM_THREADS, SPAN = NJ + VITS_LIMIT_MAX_LOOKAHEAD, ROW = LM_RA + 1;
   __shared__ float pa[SPAN], pb[SPAN];
   __shared__ double dd[LM_THREADS * ROW];
   __shared__ double sc[2][LM_THREADS];
   const int b = blockIdx.y, kn = blockIdx.x, t = threadIdx.x;
-  const long long len = ld_len(len_frames, len_mul, L, M, N, b), n0 = (long long)kn * VITS_LIMIT_TILE;
+  const long long len = it.len_out(b), n0 = (long long)kn * VITS_LIMIT_TILE;
   if (n0 >= len) {  // (the whole workgroup)
     for (int i = 0; i < VITS_LIMIT_TILE / LM_THREADS; ++i) {
       const long long n = n0 + t + i * LM_THREADS;
       if (n < n_count) y[(long long)b * y_bstride + n] = (OUT)0;
-      if (s_out && n < N) s_out[(long long)b * N + n] = 1.f;
+      if (s_out && n < it.cap) s_out[(long long)b * it.cap + n] = 1.f;
     }
     return;
   }
   const int W = prm.W;
   const double g = (double)gv[b * 2];
-  lm_fill(pa, p + (long long)b * N, n0 - W, SPAN, len);
+  lm_fill(pa, p + (long long)b * it.cap, n0 - W, SPAN, len);
   int off2;
   const float* mq = lm_wmax(pa, pb, SPAN, W + 1, &off2);
   double d[LM_RA];
@@ -325,7 +321,7 @@ __global__ __launch_bounds__(LM_THREADS) void limit_apply_kernel(const float* __
       sm = fminf(sm, s32);
       v = (float)(g * s) * xb[n];
     }
-    if (s_out && n < N) s_out[(long long)b * N + n] = s32;
+    if (s_out && n < it.cap) s_out[(long long)b * it.cap + n] = s32;
     if (n < n_count) {
       if constexpr (sizeof(OUT) == sizeof(int16_t)) y[(long long)b * y_bstride + n] = pcm16_of(v, scale);
       else y[(long long)b * y_bstride + n] = v;
@@ -372,39 +368,37 @@ struct LimProf {
   LimProf(vits_session* s, const char* kernel) { if (s) p.emplace(s, "out.limit", 0, kernel); }
 };
 
-// step 1 of B items x[b, 0 : len_b) of capacity N on `stream` (no allocation, no synchronisation)
-static void lim_env_launch(hipStream_t stream, int mode, const LimTab& tab, const LimScratch& S, const float* x, long long x_bstride, long long N,
-                           const int* len_frames, long long len_mul, int L, int M, int B, vits_session* ps = nullptr) {
+// step 1 of B items x[b, 0 : it.len_out(b)) of capacity it.cap on `stream` (no allocation, no synchronisation)
+static void lim_env_launch(hipStream_t stream, int mode, const LimTab& tab, const LimScratch& S, const float* x, long long x_bstride, const Items& it,
+                           int B, vits_session* ps = nullptr) {
   if (B <= 0 || S.ntiles <= 0) return;
   LimProf lp(ps, "limit_env_kernel");
-  hipLaunchKernelGGL(limit_env_kernel, dim3(S.ntiles, B), dim3(LM_THREADS), 0, stream, x, x_bstride, N, len_frames, len_mul, L, M, mode, tab,
-                     S.ntiles, S.p, S.tpeak);
+  hipLaunchKernelGGL(limit_env_kernel, dim3(S.ntiles, B), dim3(LM_THREADS), 0, stream, x, x_bstride, it, mode, tab, S.ntiles, S.p, S.tpeak);
 }
 
-// one pass behind lim_env_launch: the gain (src as limit_gain_kernel takes it), steps 2-6 into y[b, 0 : n_count), n_count <= N
+// one pass behind lim_env_launch: the gain (src as limit_gain_kernel takes it), steps 2-6 into y[b, 0 : n_count), n_count <= it.cap
 template <typename OUT>
-static void lim_pass_launch(hipStream_t stream, const LimPrm& prm, const LimScratch& S, int src, const float* res0, const float* res1,
-                            const float* x, long long x_bstride, long long N, const int* len_frames, long long len_mul, int L, int M, int B,
-                            OUT* y, long long y_bstride, long long n_count, float scale, float* s_out, vits_session* ps = nullptr) {
+static void lim_pass_launch(hipStream_t stream, const LimPrm& prm, const LimScratch& S, int src, const float* res0, const float* res1, const float* x,
+                            long long x_bstride, const Items& it, int B, OUT* y, long long y_bstride, long long n_count, float scale, float* s_out,
+                            vits_session* ps = nullptr) {
   if (B <= 0 || S.ntiles <= 0) return;
   { LimProf lp(ps, "limit_gain_kernel");
-  hipLaunchKernelGGL(limit_gain_kernel, dim3(B), dim3(64), 0, stream, len_frames, len_mul, L, M, N, S.ntiles, S.tpeak, src, prm, res0, res1, S.gv); }
+  hipLaunchKernelGGL(limit_gain_kernel, dim3(B), dim3(64), 0, stream, it, S.ntiles, S.tpeak, src, prm, res0, res1, S.gv); }
   { LimProf lp(ps, "limit_scan_kernel");
-  hipLaunchKernelGGL(limit_scan_kernel, dim3(S.ntj, B), dim3(LM_THREADS), 0, stream, S.p, N, len_frames, len_mul, L, M, prm, S.gv, S.ntj, S.cend); }
+  hipLaunchKernelGGL(limit_scan_kernel, dim3(S.ntj, B), dim3(LM_THREADS), 0, stream, S.p, it, prm, S.gv, S.ntj, S.cend); }
   { LimProf lp(ps, "limit_carry_kernel");
-  hipLaunchKernelGGL(limit_carry_kernel, dim3(B), dim3(64), 0, stream, len_frames, len_mul, L, M, N, prm, S.ntj, S.cend, S.cin); }
+  hipLaunchKernelGGL(limit_carry_kernel, dim3(B), dim3(64), 0, stream, it, prm, S.ntj, S.cend, S.cin); }
   LimProf lp(ps, sizeof(OUT) == sizeof(int16_t) ? "limit_apply_kernel<int16>" : "limit_apply_kernel<float>");
   hipLaunchKernelGGL(limit_apply_kernel<OUT>, dim3((unsigned)((n_count + VITS_LIMIT_TILE - 1) / VITS_LIMIT_TILE), B), dim3(LM_THREADS), 0, stream, x,
-                     x_bstride, N, len_frames, len_mul, L, M, S.p, prm, S.gv, S.ntiles, S.ntj, S.cin, y, y_bstride, n_count, scale, s_out, S.smin);
+                     x_bstride, it, S.p, prm, S.gv, S.ntiles, S.ntj, S.cin, y, y_bstride, n_count, scale, s_out, S.smin);
 }
 
 // res[b] = {L, peak, gain, 0} of a measurement becomes {L, peak, g, min s} of the limited call (keep), or {0, max p, g, min s}.  One wave
 // per item.
-__global__ __launch_bounds__(64) void limit_final_kernel(const int* __restrict__ len_frames, long long len_mul, int L, int M, long long N,
-                                                         int ntiles, const float* __restrict__ smin, const float* __restrict__ gv, int keep,
-                                                         float* __restrict__ res) {
+__global__ __launch_bounds__(64) void limit_final_kernel(const Items it, int ntiles, const float* __restrict__ smin, const float* __restrict__ gv,
+                                                         int keep, float* __restrict__ res) {
   const int b = blockIdx.x, t = threadIdx.x;
-  const long long len = ld_len(len_frames, len_mul, L, M, N, b);
+  const long long len = it.len_out(b);
   const int nt = (int)((len + VITS_LIMIT_TILE - 1) / VITS_LIMIT_TILE);
   float sm = 1.f;
   for (int k = t; k < nt; k += 64) sm = fminf(sm, smin[(long long)b * ntiles + k]);
@@ -485,34 +479,32 @@ static void norm_ws_layout(const NormReq& lq, const LoudWs& W, int B, long long 
   if (lq.lim.on) lim_extra_layout(B, N, W.dm, out);
 }
 
-// The last stage of a flagged call on `stream` (no allocation, no synchronisation): B items x[b, 0 : len_b) of capacity N measured,
+// The last stage of a flagged call on `stream` (no allocation, no synchronisation): B items x[b, 0 : it.len_out(b)) of capacity it.cap measured,
 // normalised and / or limited into y[b, 0 : n_count), NS.LS.res[b] = {L, peak, gain, min s}.  Without a limiter these are exactly
 // loud_measure_launch and loud_apply_launch.
 template <typename OUT>
-static void norm_launch(hipStream_t stream, const NormReq& nq, const NormScratch& NS, const float* x, long long x_bstride, long long N,
-                        const int* len_frames, long long len_mul, int L, int M, int B, OUT* y, long long y_bstride, long long n_count, float scale,
-                        vits_session* ps = nullptr) {
+static void norm_launch(hipStream_t stream, const NormReq& nq, const NormScratch& NS, const float* x, long long x_bstride, const Items& it, int B,
+                        OUT* y, long long y_bstride, long long n_count, float scale, vits_session* ps = nullptr) {
   const LoudReq& lq = nq.loud;
   if (!nq.lim.on) {
-    loud_measure_launch(stream, lq.P, lq.prm, NS.LS, x, x_bstride, N, len_frames, len_mul, L, M, B, ps);
-    loud_apply_launch<OUT>(stream, NS.LS, x, x_bstride, N, len_frames, len_mul, L, M, B, y, y_bstride, n_count, scale, ps);
+    loud_measure_launch(stream, lq.P, lq.prm, NS.LS, x, x_bstride, it, B, ps);
+    loud_apply_launch<OUT>(stream, NS.LS, x, x_bstride, it, B, y, y_bstride, n_count, scale, ps);
     return;
   }
   if (B <= 0 || n_count <= 0) return;
   const LimReq& q = nq.lim;
   const bool lufs = lq.on;  // (with a limiter a loudness request is a LUFS target: lim_req refuses the peak mode)
-  lim_env_launch(stream, q.prm.mode, q.tab, NS.MS, x, x_bstride, N, len_frames, len_mul, L, M, B, ps);
+  lim_env_launch(stream, q.prm.mode, q.tab, NS.MS, x, x_bstride, it, B, ps);
   if (lufs) {
-    loud_measure_launch(stream, lq.P, lq.prm, NS.LS, x, x_bstride, N, len_frames, len_mul, L, M, B, ps);
-    lim_pass_launch<float>(stream, q.prm, NS.MS, 1, NS.LS.res, nullptr, x, x_bstride, N, len_frames, len_mul, L, M, B, NS.MS.y0, N, N, 1.f, nullptr, ps);
-    loud_measure_launch(stream, lq.P, lq.prm, NS.LS1, NS.MS.y0, N, N, len_frames, len_mul, L, M, B, ps);
-    lim_pass_launch<OUT>(stream, q.prm, NS.MS, 2, NS.LS.res, NS.LS1.res, x, x_bstride, N, len_frames, len_mul, L, M, B, y, y_bstride, n_count, scale, nullptr, ps);
+    loud_measure_launch(stream, lq.P, lq.prm, NS.LS, x, x_bstride, it, B, ps);
+    lim_pass_launch<float>(stream, q.prm, NS.MS, 1, NS.LS.res, nullptr, x, x_bstride, it, B, NS.MS.y0, it.cap, it.cap, 1.f, nullptr, ps);
+    loud_measure_launch(stream, lq.P, lq.prm, NS.LS1, NS.MS.y0, it.cap, it, B, ps);
+    lim_pass_launch<OUT>(stream, q.prm, NS.MS, 2, NS.LS.res, NS.LS1.res, x, x_bstride, it, B, y, y_bstride, n_count, scale, nullptr, ps);
   } else {
-    lim_pass_launch<OUT>(stream, q.prm, NS.MS, 0, nullptr, nullptr, x, x_bstride, N, len_frames, len_mul, L, M, B, y, y_bstride, n_count, scale, nullptr, ps);
+    lim_pass_launch<OUT>(stream, q.prm, NS.MS, 0, nullptr, nullptr, x, x_bstride, it, B, y, y_bstride, n_count, scale, nullptr, ps);
   }
   LimProf lp(ps, "limit_final_kernel");
-  hipLaunchKernelGGL(limit_final_kernel, dim3(B), dim3(64), 0, stream, len_frames, len_mul, L, M, N, NS.MS.ntiles, NS.MS.smin, NS.MS.gv, lufs ? 1 : 0,
-                     NS.LS.res);
+  hipLaunchKernelGGL(limit_final_kernel, dim3(B), dim3(64), 0, stream, it, NS.MS.ntiles, NS.MS.smin, NS.MS.gv, lufs ? 1 : 0, NS.LS.res);
 }
 
 // ---- host-only entry point and the kernel-level parity doors --------------------------------------------------------------------
@@ -553,15 +545,16 @@ static int lim_op(int device, const float* x, const int64_t* lengths, int32_t B,
   loud_scratch_layout(B, N, dscr ? dscr + scr : nullptr, &S0);
   loud_scratch_layout(B, N, dscr ? dscr + scr + lscr : nullptr, &S1);
   std::vector<float> res0((size_t)B * 4), gv((size_t)B * 2), tiles((size_t)B * S.ntiles);
+  const Items it{dl, 1, 1, 1, N};
   if (d.ok()) {
-    lim_env_launch(nullptr, mode, tab, S, dx, N, N, dl, 1, 1, 1, B);
+    lim_env_launch(nullptr, mode, tab, S, dx, N, it, B);
     if (prm && !lufs) {
-      lim_pass_launch<float>(nullptr, *prm, S, 0, nullptr, nullptr, dx, N, N, dl, 1, 1, 1, B, dy, N, N, 1.f, ds);
+      lim_pass_launch<float>(nullptr, *prm, S, 0, nullptr, nullptr, dx, N, it, B, dy, N, N, 1.f, ds);
     } else if (prm) {
-      loud_measure_launch(nullptr, LP, lprm, S0, dx, N, N, dl, 1, 1, 1, B);
-      lim_pass_launch<float>(nullptr, *prm, S, 1, S0.res, nullptr, dx, N, N, dl, 1, 1, 1, B, S.y0, N, N, 1.f, (float*)nullptr);
-      loud_measure_launch(nullptr, LP, lprm, S1, S.y0, N, N, dl, 1, 1, 1, B);
-      lim_pass_launch<float>(nullptr, *prm, S, 2, S0.res, S1.res, dx, N, N, dl, 1, 1, 1, B, dy, N, N, 1.f, ds);
+      loud_measure_launch(nullptr, LP, lprm, S0, dx, N, it, B);
+      lim_pass_launch<float>(nullptr, *prm, S, 1, S0.res, nullptr, dx, N, it, B, S.y0, N, N, 1.f, (float*)nullptr);
+      loud_measure_launch(nullptr, LP, lprm, S1, S.y0, N, it, B);
+      lim_pass_launch<float>(nullptr, *prm, S, 2, S0.res, S1.res, dx, N, it, B, dy, N, N, 1.f, ds);
     }
   }
   d.finish();

@@ -152,13 +152,6 @@ __device__ __forceinline__ LdState ld_mv(const ld_t* M, const LdState& v) {
   return r;
 }
 
-// samples of item b as returned: len_frames[b] * len_mul input samples (len_frames null: len_mul) taken to the output rate L / M, at most N
-__device__ __forceinline__ long long ld_len(const int* len_frames, long long len_mul, int L, int M, long long N, int b) {
-  long long l = len_frames ? len_frames[b] * len_mul : len_mul;
-  l = (l * L + M - 1) / M;
-  return l < 0 ? 0 : (l > N ? N : l);
-}
-
 // stages samples [n0, n0 + TILE) of the item, zero at and beyond len (those are never read), padded rows
 __device__ __forceinline__ void ld_stage(float* xs, const float* __restrict__ xb, long long n0, long long len) {
   for (int j = threadIdx.x; j < VITS_LOUDNESS_TILE; j += LD_THREADS) {
@@ -190,14 +183,13 @@ __device__ __forceinline__ int ld_scan(const LoudCoef& c, LdState (*sc)[LD_THREA
 }
 
 // E / tpeak: [B, ntiles]; written for the tiles that hold samples of the item (k < ceil(len / TILE)), the only ones read later
-__global__ __launch_bounds__(LD_THREADS) void loud_tile_kernel(const float* __restrict__ x, long long x_bstride, long long N,
-                                                               const int* __restrict__ len_frames, long long len_mul, int L, int M,
-                                                               const LoudCoef c, int ntiles, LdState* __restrict__ E, float* __restrict__ tpeak) {
+__global__ __launch_bounds__(LD_THREADS) void loud_tile_kernel(const float* __restrict__ x, long long x_bstride, const Items it, const LoudCoef c,
+                                                               int ntiles, LdState* __restrict__ E, float* __restrict__ tpeak) {
   __shared__ float xs[LD_THREADS * LD_ROW];
   __shared__ LdState sc[2][LD_THREADS];
   __shared__ float pk[LD_THREADS];
   const int b = blockIdx.y, k = blockIdx.x, t = threadIdx.x;
-  const long long len = ld_len(len_frames, len_mul, L, M, N, b), n0 = (long long)k * VITS_LOUDNESS_TILE;
+  const long long len = it.len_out(b), n0 = (long long)k * VITS_LOUDNESS_TILE;
   if (n0 >= len) return;  // (the whole workgroup)
   ld_stage(xs, x + (long long)b * x_bstride, n0, len);
   __syncthreads();
@@ -222,11 +214,11 @@ __global__ __launch_bounds__(LD_THREADS) void loud_tile_kernel(const float* __re
 }
 
 // C[b][k]: the state the item's tile k starts from.  One wave per item.
-__global__ __launch_bounds__(64) void loud_carry_kernel(const int* __restrict__ len_frames, long long len_mul, int L, int M, long long N,
-                                                        const LoudCoef c, int ntiles, const LdState* __restrict__ E, LdState* __restrict__ C) {
+__global__ __launch_bounds__(64) void loud_carry_kernel(const Items it, const LoudCoef c, int ntiles, const LdState* __restrict__ E,
+                                                        LdState* __restrict__ C) {
   __shared__ LdState es[64];
   const int b = blockIdx.x, t = threadIdx.x;
-  const long long len = ld_len(len_frames, len_mul, L, M, N, b);
+  const long long len = it.len_out(b);
   const int nt = (int)((len + VITS_LOUDNESS_TILE - 1) / VITS_LOUDNESS_TILE);
   LdState s = {0, 0, 0, 0};
   for (int k0 = 0; k0 < nt; k0 += 64) {
@@ -245,16 +237,14 @@ __global__ __launch_bounds__(64) void loud_carry_kernel(const int* __restrict__ 
 }
 
 // part[b][k][j]: the sum of y[n]^2 over the samples n < len of tile k that lie in hop (k TILE) / hop + j
-__global__ __launch_bounds__(LD_THREADS) void loud_square_kernel(const float* __restrict__ x, long long x_bstride, long long N,
-                                                                 const int* __restrict__ len_frames, long long len_mul, int L, int M,
-                                                                 const LoudCoef c, int ntiles, const LdState* __restrict__ C,
-                                                                 ld_t* __restrict__ part) {
+__global__ __launch_bounds__(LD_THREADS) void loud_square_kernel(const float* __restrict__ x, long long x_bstride, const Items it, const LoudCoef c,
+                                                                 int ntiles, const LdState* __restrict__ C, ld_t* __restrict__ part) {
   __shared__ float xs[LD_THREADS * LD_ROW];
   __shared__ LdState sc[2][LD_THREADS];
   __shared__ ld_t ca[LD_THREADS], cb[LD_THREADS];
   __shared__ int sl[LD_THREADS];
   const int b = blockIdx.y, k = blockIdx.x, t = threadIdx.x;
-  const long long len = ld_len(len_frames, len_mul, L, M, N, b), n0 = (long long)k * VITS_LOUDNESS_TILE;
+  const long long len = it.len_out(b), n0 = (long long)k * VITS_LOUDNESS_TILE;
   if (n0 >= len) return;
   ld_stage(xs, x + (long long)b * x_bstride, n0, len);
   __syncthreads();
@@ -305,14 +295,13 @@ __device__ __forceinline__ double ld_block_sum(double* red, double v) {
 }
 
 // Eh: double [B, eh_stride] scratch (hop energies); res: float [B, 4] = {L, peak, gain, 0}
-__global__ __launch_bounds__(LD_THREADS) void loud_final_kernel(const int* __restrict__ len_frames, long long len_mul, int L, int M, long long N,
-                                                                int hop, int ntiles, const ld_t* __restrict__ part,
-                                                                const float* __restrict__ tpeak, double* __restrict__ Eh,
-                                                                long long eh_stride, const LoudParams prm, float* __restrict__ res) {
+__global__ __launch_bounds__(LD_THREADS) void loud_final_kernel(const Items it, int hop, int ntiles, const ld_t* __restrict__ part,
+                                                                const float* __restrict__ tpeak, double* __restrict__ Eh, long long eh_stride,
+                                                                const LoudParams prm, float* __restrict__ res) {
   __shared__ double red[LD_THREADS];
   __shared__ float pk[LD_THREADS];
   const int b = blockIdx.x, t = threadIdx.x;
-  const long long len = ld_len(len_frames, len_mul, L, M, N, b);
+  const long long len = it.len_out(b);
   const int nt = (int)((len + VITS_LOUDNESS_TILE - 1) / VITS_LOUDNESS_TILE);
   const long long nh = len / hop, nh_all = (len + hop - 1) / hop;
   double* eh = Eh + (long long)b * eh_stride;
@@ -377,14 +366,13 @@ __global__ __launch_bounds__(LD_THREADS) void loud_final_kernel(const int* __res
 
 // y[b, j] = res[b].gain * x[b, j] for j < len, 0 beyond (x is not read there), 0 <= j < n_count.  OUT = int16_t: pcm16_of.
 template <typename OUT>
-__global__ __launch_bounds__(256) void loud_apply_kernel(const float* __restrict__ x, long long x_bstride, long long N,
-                                                         const int* __restrict__ len_frames, long long len_mul, int L, int M,
-                                                         const float* __restrict__ res, OUT* __restrict__ y, long long y_bstride,
-                                                         long long n_count, float scale) {
+__global__ __launch_bounds__(256) void loud_apply_kernel(const float* __restrict__ x, long long x_bstride, const Items it,
+                                                         const float* __restrict__ res, OUT* __restrict__ y, long long y_bstride, long long n_count,
+                                                         float scale) {
   const long long j = (long long)blockIdx.x * 256 + threadIdx.x;
   const int b = blockIdx.y;
   if (j >= n_count) return;
-  const long long len = ld_len(len_frames, len_mul, L, M, N, b);
+  const long long len = it.len_out(b);
   const float v = j < len ? res[b * 4 + 2] * x[(long long)b * x_bstride + j] : 0.f;
   if constexpr (sizeof(OUT) == sizeof(int16_t)) y[(long long)b * y_bstride + j] = pcm16_of(v, scale);
   else y[(long long)b * y_bstride + j] = v;
@@ -426,34 +414,28 @@ struct LoudProf {
   ~LoudProf() { if (p) p->~ProfScope(); }
 };
 
-// Measures B items x[b, 0 : len_b) of capacity N on `stream` (no allocation, no synchronisation): S.res[b] = {L, peak, gain}.
+// Measures B items x[b, 0 : it.len_out(b)) of capacity it.cap on `stream` (no allocation, no synchronisation): S.res[b] = {L, peak, gain}.
 static void loud_measure_launch(hipStream_t stream, const LoudPlan& P, const LoudParams& prm, const LoudScratch& S, const float* x,
-                                long long x_bstride, long long N, const int* len_frames, long long len_mul, int L, int M, int B,
-                                vits_session* ps = nullptr) {
+                                long long x_bstride, const Items& it, int B, vits_session* ps = nullptr) {
   if (B <= 0) return;
   if (S.ntiles > 0) {
     { LoudProf lp(ps, "loud_tile_kernel");
-    hipLaunchKernelGGL(loud_tile_kernel, dim3(S.ntiles, B), dim3(LD_THREADS), 0, stream, x, x_bstride, N, len_frames, len_mul, L, M, P.c, S.ntiles,
-                       S.E, S.tpeak); }
+    hipLaunchKernelGGL(loud_tile_kernel, dim3(S.ntiles, B), dim3(LD_THREADS), 0, stream, x, x_bstride, it, P.c, S.ntiles, S.E, S.tpeak); }
     { LoudProf lp(ps, "loud_carry_kernel");
-    hipLaunchKernelGGL(loud_carry_kernel, dim3(B), dim3(64), 0, stream, len_frames, len_mul, L, M, N, P.c, S.ntiles, S.E, S.C); }
+    hipLaunchKernelGGL(loud_carry_kernel, dim3(B), dim3(64), 0, stream, it, P.c, S.ntiles, S.E, S.C); }
     { LoudProf lp(ps, "loud_square_kernel");
-    hipLaunchKernelGGL(loud_square_kernel, dim3(S.ntiles, B), dim3(LD_THREADS), 0, stream, x, x_bstride, N, len_frames, len_mul, L, M, P.c,
-                       S.ntiles, S.C, S.part); }
+    hipLaunchKernelGGL(loud_square_kernel, dim3(S.ntiles, B), dim3(LD_THREADS), 0, stream, x, x_bstride, it, P.c, S.ntiles, S.C, S.part); }
   }
   LoudProf lp(ps, "loud_final_kernel");
-  hipLaunchKernelGGL(loud_final_kernel, dim3(B), dim3(LD_THREADS), 0, stream, len_frames, len_mul, L, M, N, P.hop, S.ntiles, S.part, S.tpeak, S.Eh,
-                     S.eh_stride, prm, S.res);
+  hipLaunchKernelGGL(loud_final_kernel, dim3(B), dim3(LD_THREADS), 0, stream, it, P.hop, S.ntiles, S.part, S.tpeak, S.Eh, S.eh_stride, prm, S.res);
 }
 
 template <typename OUT>
-static void loud_apply_launch(hipStream_t stream, const LoudScratch& S, const float* x, long long x_bstride, long long N, const int* len_frames,
-                              long long len_mul, int L, int M, int B, OUT* y, long long y_bstride, long long n_count, float scale,
-                              vits_session* ps = nullptr) {
+static void loud_apply_launch(hipStream_t stream, const LoudScratch& S, const float* x, long long x_bstride, const Items& it, int B, OUT* y,
+                              long long y_bstride, long long n_count, float scale, vits_session* ps = nullptr) {
   if (B <= 0 || n_count <= 0) return;
   LoudProf lp(ps, sizeof(OUT) == sizeof(int16_t) ? "loud_apply_kernel<int16>" : "loud_apply_kernel<float>");
-  hipLaunchKernelGGL(loud_apply_kernel<OUT>, dim3((unsigned)((n_count + 255) / 256), B), dim3(256), 0, stream, x, x_bstride, N, len_frames, len_mul,
-                     L, M, S.res, y, y_bstride, n_count, scale);
+  hipLaunchKernelGGL(loud_apply_kernel<OUT>, dim3((unsigned)((n_count + 255) / 256), B), dim3(256), 0, stream, x, x_bstride, it, S.res, y, y_bstride, n_count, scale);
 }
 
 // ---- a call's request (the fields behind VITS_FLAG_LOUDNESS / STTS_FLAG_LOUDNESS) ----------------------------------------------
@@ -544,9 +526,10 @@ static int loud_op(int device, const float* x, const int64_t* lengths, int32_t B
   std::vector<float> res((size_t)B * 4);
   LoudScratch S;
   loud_scratch_layout(B, N, dscr, &S);
+  const Items it{dl, 1, 1, 1, N};
   if (d.ok()) {
-    loud_measure_launch(nullptr, P, prm, S, dx, N, N, dl, 1, 1, 1, B);
-    if (y) loud_apply_launch<float>(nullptr, S, dx, N, N, dl, 1, 1, 1, B, dy, N, N, 1.f);
+    loud_measure_launch(nullptr, P, prm, S, dx, N, it, B);
+    if (y) loud_apply_launch<float>(nullptr, S, dx, N, it, B, dy, N, N, 1.f);
   }
   d.finish();
   d.down(res.data(), S.res, res.size());

@@ -2,14 +2,14 @@
 // the length regulator already left behind.  Part of the ONE translation unit engine.hip (included there, after resample.hip.h).
 //
 // Nothing is predicted here: frame f belongs to token j with cum[j-1] <= f < cum[j], so token t ends at output sample
-// n_out(cum[t] * hop), n_out(x) = ceil(x * L / M) being the resampler's length rule (the identity at L = M = 1).  One rule, stated
-// once (marks_end), used by the kernel of the graph-replayed path and by the host function of the paths that have the counts on the
-// host anyway (the eager VITS path, streams, every multistream call).
+// n_out(cum[t] * hop), n_out(x) = ceil(x * L / M) being the resampler's length rule (the identity at L = M = 1).  The rule is stated
+// once, in ragged.hip.h; marks_end applies it in the kernel of the graph-replayed path and in the host function of the paths that have
+// the counts on the host anyway (the eager VITS path, streams, every multistream call).
 #pragma once
 #include "../../include/vits_marks.h"
 
 __host__ __device__ static inline long long marks_end(long long cum, long long hop, long long L, long long M) {
-  return (cum * hop * L + M - 1) / M;
+  return n_out(cum * hop, L, M);
 }
 
 // Host: token_ends[t] for the T tokens of one item from its inclusive cumulative frame counts; entries at and beyond `len` repeat the

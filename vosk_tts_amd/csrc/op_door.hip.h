@@ -34,6 +34,28 @@ static int dev_table_upload(int device, const char* what, const void* src, size_
   return VITS_OK;
 }
 
+// The tables of a stage that live as long as the process, by key (the device, and whatever else tells two tables apart).  get() leaves
+// *out at the entry of `key`; on a miss build(Val&) fills a fresh one under the lock (dev_table_upload: outside stream capture).  What
+// build refuses is not kept, and nothing is ever evicted: captured graphs and cached contexts hold the pointers.
+template <typename Key, typename Val>
+struct DevTabs {
+  std::mutex mu;
+  std::map<Key, Val> tabs;
+  size_t size() const { return tabs.size(); }  // (for a build that bounds the table count: it runs under the lock)
+  template <typename Build>
+  int get(const Key& key, const Val** out, Build&& build) {
+    std::lock_guard<std::mutex> g(mu);
+    auto it = tabs.find(key);
+    if (it == tabs.end()) {
+      Val v{};
+      TRY(build(v));
+      it = tabs.emplace(key, v).first;
+    }
+    *out = &it->second;
+    return VITS_OK;
+  }
+};
+
 // One door call on the null stream.  The first failure is kept (fail() has its message, under the door's name) and every later step is
 // skipped; a door guards its launches with ok().  A failed allocation is VITS_ERR_NOMEM, any other HIP error VITS_ERR_DEVICE.
 struct OpDoor {
@@ -58,6 +80,13 @@ struct OpDoor {
     T* p = host ? dev<T>(n) : nullptr;
     if (p) hip(hipMemcpy(p, host, n * sizeof(T), hipMemcpyHostToDevice));
     return p;
+  }
+  // x [B, N] as a zero-filled [B, N] on the device with every item's own samples only: what lies at and beyond lengths[b] never gets there
+  float* up_items(const float* x, const int64_t* lengths, int B, int64_t N) {
+    float* dx = out<float>((size_t)B * N, 0);
+    for (int b = 0; b < B && ok(); ++b)
+      if (lengths[b]) hip(hipMemcpy(dx + (size_t)b * N, x + (size_t)b * N, sizeof(float) * (size_t)lengths[b], hipMemcpyHostToDevice));
+    return dx;
   }
   template <typename T>
   T* out(size_t n, int fill = 0xff) {  // 0xff: an element the kernel does not write shows as NaN

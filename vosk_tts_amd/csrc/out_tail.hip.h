@@ -217,10 +217,11 @@ static int tail_run(Alloc&& alloc, vits_session* s, hipStream_t stream, const fl
   const size_t esz = q.pcm ? sizeof(int16_t) : sizeof(float);
   *So_out = T ? T->P.n_out(S) : S;
   *d_res = nullptr;
+  Items in{len_y, hop};  // the items at the vocoder's rate
   if (q.pitch.on) {
     float* d_p = static_cast<float*>(alloc(sizeof(float) * (size_t)B * S));
     if (!d_p) return fail(VITS_ERR_NOMEM, "device alloc failed");
-    TRY(pitch_run(s->m->device, stream, x, S, S, len_y, hop, h_len, B, q.pitch.P, q.pitch.Q, q.pitch.formant, d_p, S, S, nullptr, 0));
+    TRY(pitch_run(s->m->device, stream, x, S, S, in, h_len, B, q.pitch.P, q.pitch.Q, q.pitch.formant, d_p, S, S, nullptr, 0));
     x = d_p;
   }
   if (q.contour.on) {  // in the pitch stage's place; the last stage of a call that neither resamples nor normalises
@@ -239,11 +240,13 @@ static int tail_run(Alloc&& alloc, vits_session* s, hipStream_t stream, const fl
     if (!d_j) return fail(VITS_ERR_NOMEM, "device alloc failed");
     doc_join_launch(s, stream, x, S, len_y, hop, q.doc, d_j, jp, q.pcm_scale);
     B = 1; S = Sd; len_y = q.doc.d_blk;
+    in = Items{len_y, hop};
     *So_out = T ? T->P.n_out(S) : S;
     if (jp) { *d_out = d_j; return VITS_OK; }
     x = static_cast<const float*>(d_j);
   }
   const long long So = *So_out;
+  const Items ret = items_at(T, len_y, hop, So);  // the items as they are returned
   *d_out = x;
   bool at_rate = !T;  // x is at the rate it is returned at
   if (q.wm.on) {  // marked at the rate it is returned at (the resampler in front writes float); the last stage of a call that does not normalise
@@ -251,7 +254,7 @@ static int tail_run(Alloc&& alloc, vits_session* s, hipStream_t stream, const fl
       float* d_y = static_cast<float*>(alloc(sizeof(float) * (size_t)B * So));
       if (!d_y) return fail(VITS_ERR_NOMEM, "device alloc failed");
       ProfScope ps(s, "out.resample", 2.0 * B * So * T->P.taps, "resample_kernel<float>");
-      resample_launch<float>(stream, *T, x, S, 0, S, len_y, hop, B, d_y, So, 0, So, 1.f, nullptr);
+      resample_launch<float>(stream, *T, x, S, 0, S, in, B, d_y, So, 0, So, 1.f, nullptr);
       x = d_y;
       at_rate = true;
     }
@@ -266,11 +269,10 @@ static int tail_run(Alloc&& alloc, vits_session* s, hipStream_t stream, const fl
       if (!d_words) return fail(VITS_ERR_NOMEM, "device alloc failed");
       HIP_TRY(hipMemcpyAsync(d_words, q.wm.host_words(q.doc.on), sizeof(uint32_t) * (size_t)B, hipMemcpyHostToDevice, stream));
     }
-    const int wL = T ? T->P.L : 1, wM = T ? T->P.M : 1;
     {
       ProfScope ps(s, "out.watermark", 0, wp ? "wm_frames_kernel + wm_ola_kernel<int16>" : "wm_frames_kernel + wm_ola_kernel<float>");
-      if (wp) wm_launch<int16_t>(stream, q.wm, x, So, So, len_y, hop, wL, wM, B, d_scr, (long long)sc, static_cast<int16_t*>(d_w), So, So, q.pcm_scale, d_words);
-      else wm_launch<float>(stream, q.wm, x, So, So, len_y, hop, wL, wM, B, d_scr, (long long)sc, static_cast<float*>(d_w), So, So, 1.f, d_words);
+      if (wp) wm_launch<int16_t>(stream, q.wm, x, So, ret, B, d_scr, (long long)sc, static_cast<int16_t*>(d_w), So, So, q.pcm_scale, d_words);
+      else wm_launch<float>(stream, q.wm, x, So, ret, B, d_scr, (long long)sc, static_cast<float*>(d_w), So, So, 1.f, d_words);
     }
     *d_out = d_w;
     if (!q.norm.on()) return VITS_OK;
@@ -281,7 +283,7 @@ static int tail_run(Alloc&& alloc, vits_session* s, hipStream_t stream, const fl
       float* d_y = static_cast<float*>(alloc(sizeof(float) * (size_t)B * So));
       if (!d_y) return fail(VITS_ERR_NOMEM, "device alloc failed");
       ProfScope ps(s, "out.resample", 2.0 * B * So * T->P.taps, "resample_kernel<float>");
-      resample_launch<float>(stream, *T, x, S, 0, S, len_y, hop, B, d_y, So, 0, So, 1.f, nullptr);
+      resample_launch<float>(stream, *T, x, S, 0, S, in, B, d_y, So, 0, So, 1.f, nullptr);
       x = d_y;
     }
     char* d_scr = static_cast<char*>(alloc(norm_scratch_bytes(q.norm, B, So)));
@@ -289,17 +291,16 @@ static int tail_run(Alloc&& alloc, vits_session* s, hipStream_t stream, const fl
     if (!d_scr || !d_n) return fail(VITS_ERR_NOMEM, "device alloc failed");
     NormScratch NS;
     norm_scratch_layout(q.norm, B, So, d_scr, &NS);
-    const int rL = T ? T->P.L : 1, rM = T ? T->P.M : 1;
-    if (q.pcm) norm_launch<int16_t>(stream, q.norm, NS, x, So, So, len_y, hop, rL, rM, B, static_cast<int16_t*>(d_n), So, So, q.pcm_scale, s);
-    else norm_launch<float>(stream, q.norm, NS, x, So, So, len_y, hop, rL, rM, B, static_cast<float*>(d_n), So, So, 1.f, s);
+    if (q.pcm) norm_launch<int16_t>(stream, q.norm, NS, x, So, ret, B, static_cast<int16_t*>(d_n), So, So, q.pcm_scale, s);
+    else norm_launch<float>(stream, q.norm, NS, x, So, ret, B, static_cast<float*>(d_n), So, So, 1.f, s);
     *d_res = NS.LS.res;
     *d_out = d_n;
   } else if (T) {  // item b from its own [0, len) of x; at int16 in place of pcm16_kernel
     void* d_y = alloc(esz * (size_t)B * So);
     if (!d_y) return fail(VITS_ERR_NOMEM, "device alloc failed");
     ProfScope ps(s, "out.resample", 2.0 * B * So * T->P.taps, q.pcm ? "resample_kernel<int16>" : "resample_kernel<float>");
-    if (q.pcm) resample_launch<int16_t>(stream, *T, x, S, 0, S, len_y, hop, B, static_cast<int16_t*>(d_y), So, 0, So, q.pcm_scale, nullptr);
-    else resample_launch<float>(stream, *T, x, S, 0, S, len_y, hop, B, static_cast<float*>(d_y), So, 0, So, 1.f, nullptr);
+    if (q.pcm) resample_launch<int16_t>(stream, *T, x, S, 0, S, in, B, static_cast<int16_t*>(d_y), So, 0, So, q.pcm_scale, nullptr);
+    else resample_launch<float>(stream, *T, x, S, 0, S, in, B, static_cast<float*>(d_y), So, 0, So, 1.f, nullptr);
     *d_out = d_y;
   } else if (q.pcm) {
     int16_t* d_pcm = static_cast<int16_t*>(alloc(sizeof(int16_t) * (size_t)B * S));

@@ -53,14 +53,13 @@ __device__ __forceinline__ float pt_interp(float a, float b, float alpha) {
 
 // Rows [0, F_a + 2) of every item: wave w of workgroup blockIdx.x owns row blockIdx.x * SF_FPB + w.  x, x_n and len as
 // sf_frame_load takes them (x_off = 0); mag / th: [B][a_bstride], row f at f * PT_NB.
-__global__ __launch_bounds__(64 * SF_FPB) void pitch_analysis_kernel(const float* __restrict__ x, long long x_bstride, long long x_n,
-                                                                     const int* __restrict__ len_frames, long long len_mul,
+__global__ __launch_bounds__(64 * SF_FPB) void pitch_analysis_kernel(const float* __restrict__ x, long long x_bstride, long long x_n, const Items it,
                                                                      const float* __restrict__ win, const float2* __restrict__ tw,
                                                                      float* __restrict__ mag, unsigned* __restrict__ th, long long a_bstride) {
   __shared__ float lds[SF_FPB][4][SF_PLANE];
   const int wv = threadIdx.x >> 6, t = threadIdx.x & 63;
   const int b = blockIdx.y;
-  const long long len = len_frames ? len_frames[b] * len_mul : len_mul;
+  const long long len = it.len_in(b);
   const long long Fa = pt_frames_a(len);
   if (Fa == 0 || (long long)blockIdx.x * SF_FPB >= Fa + 2) return;  // uniform over the workgroup
   const long long f = (long long)blockIdx.x * SF_FPB + wv;
@@ -103,8 +102,7 @@ static_assert(PT_M * 1999 < (1 << 30) && 1000 * PT_N < (1 << 30), "k P, Q n and 
 
 template <bool GAIN>
 __global__ __launch_bounds__(64 * SF_FPB) void pitch_formant_kernel(const float* __restrict__ x, long long x_bstride, long long x_n,
-                                                                    const float* __restrict__ mag, long long a_bstride,
-                                                                    const int* __restrict__ len_frames, long long len_mul, int P, int Q,
+                                                                    const float* __restrict__ mag, long long a_bstride, const Items it, int P, int Q,
                                                                     float* __restrict__ out) {
   __shared__ double2 s_tw[PT_M];  // exp(-2 pi i t / n), t < n/2
   __shared__ double2 s_z[SF_FPB][PT_M];
@@ -112,7 +110,7 @@ __global__ __launch_bounds__(64 * SF_FPB) void pitch_formant_kernel(const float*
   __shared__ float s_l[SF_FPB][PT_NB];
   const int wv = threadIdx.x >> 6, t = threadIdx.x & 63;
   const int b = blockIdx.y;
-  const long long len = len_frames ? len_frames[b] * len_mul : len_mul;
+  const long long len = it.len_in(b);
   const long long Fa = pt_frames_a(len);
   if (Fa == 0 || (long long)blockIdx.x * SF_FPB >= Fa + 2) return;  // uniform over the workgroup
   const long long f = (long long)blockIdx.x * SF_FPB + wv;
@@ -194,14 +192,13 @@ __device__ __forceinline__ int pt_tab_i(long long a, long long Fa) {
 // One workgroup per item (blockIdx.x), thread k = bin k.  phi: [B][p_bstride], row t at t * PT_NB.
 template <bool TAB>
 __global__ __launch_bounds__(64 * PT_WAVES) void pitch_phase_kernel(const float* __restrict__ mag, const unsigned* __restrict__ th,
-                                                                    long long a_bstride, const int* __restrict__ len_frames,
-                                                                    long long len_mul, int P, int Q, const long long* __restrict__ steps,
+                                                                    long long a_bstride, const Items it, int P, int Q, const long long* __restrict__ steps,
                                                                     long long s_bstride, unsigned* __restrict__ phi, long long p_bstride) {
   __shared__ float s_m[2][PT_NB + 4];  // m[k] at k + 2; -1 either side
   __shared__ unsigned s_adv[2][PT_NB], s_th[2][PT_NB];
   __shared__ unsigned long long s_pk[2][PT_WAVES];
   const int b = blockIdx.x, k = threadIdx.x, wv = k >> 6, lane = k & 63;
-  const long long len = len_frames ? len_frames[b] * len_mul : len_mul;
+  const long long len = it.len_in(b);
   const long long Fa = pt_frames_a(len);
   const long long* ab = TAB ? steps + (long long)b * s_bstride + 1 : nullptr;  // a_0 ..
   long long Fs;
@@ -296,15 +293,14 @@ __global__ __launch_bounds__(64 * PT_WAVES) void pitch_phase_kernel(const float*
 // Steps [0, F_s) of every item: wave w of workgroup blockIdx.x owns step blockIdx.x * SF_FPB + w.  fr: [B][fr_bstride], frame t at t * n.
 template <bool TAB>
 __global__ __launch_bounds__(64 * SF_FPB) void pitch_synth_kernel(const float* __restrict__ mag, long long a_bstride,
-                                                                  const unsigned* __restrict__ phi, long long p_bstride,
-                                                                  const int* __restrict__ len_frames, long long len_mul, int P, int Q,
+                                                                  const unsigned* __restrict__ phi, long long p_bstride, const Items it, int P, int Q,
                                                                   const long long* __restrict__ steps, long long s_bstride,
                                                                   const float* __restrict__ win, const float2* __restrict__ tw,
                                                                   float* __restrict__ fr, long long fr_bstride) {
   __shared__ float lds[SF_FPB][4][SF_PLANE];
   const int wv = threadIdx.x >> 6, t = threadIdx.x & 63;
   const int b = blockIdx.y;
-  const long long len = len_frames ? len_frames[b] * len_mul : len_mul;
+  const long long len = it.len_in(b);
   long long Fs;
   if constexpr (TAB) Fs = pt_tab_fs(steps + (long long)b * s_bstride, pt_frames_a(len));
   else Fs = pt_frames_s(len, P, Q);
@@ -346,14 +342,13 @@ __global__ __launch_bounds__(64 * SF_FPB) void pitch_synth_kernel(const float* _
 
 // u[b][j], j < n_count: the overlap-add of the item's F_s frames, exactly 0 at and beyond N_u = H (F_s - 1).
 template <bool TAB>
-__global__ __launch_bounds__(256) void pitch_ola_kernel(const float* __restrict__ fr, long long fr_bstride, const int* __restrict__ len_frames,
-                                                        long long len_mul, int P, int Q, const long long* __restrict__ steps,
-                                                        long long s_bstride, const float* __restrict__ inv_env,
+__global__ __launch_bounds__(256) void pitch_ola_kernel(const float* __restrict__ fr, long long fr_bstride, const Items it, int P, int Q,
+                                                        const long long* __restrict__ steps, long long s_bstride, const float* __restrict__ inv_env,
                                                         float* __restrict__ u, long long u_bstride, long long n_count) {
   const int b = blockIdx.y;
   const long long j = (long long)blockIdx.x * 256 + threadIdx.x;
   if (j >= n_count) return;
-  const long long len = len_frames ? len_frames[b] * len_mul : len_mul;
+  const long long len = it.len_in(b);
   long long Fs;
   if constexpr (TAB) Fs = pt_tab_fs(steps + (long long)b * s_bstride, pt_frames_a(len));
   else Fs = pt_frames_s(len, P, Q);
@@ -376,11 +371,10 @@ __global__ __launch_bounds__(256) void pitch_ola_kernel(const float* __restrict_
 }
 
 // nu[b] = N_u / H (the resampler's input length in units of H) and crop[b] = min(len, N_v); both 0 for an item below n/2 + 1
-__global__ void pitch_geom_kernel(const int* __restrict__ len_frames, long long len_mul, int B, int P, int Q, int* __restrict__ nu,
-                                  int* __restrict__ crop) {
+__global__ void pitch_geom_kernel(const Items it, int B, int P, int Q, int* __restrict__ nu, int* __restrict__ crop) {
   const int b = blockIdx.x * blockDim.x + threadIdx.x;
   if (b >= B) return;
-  const long long len = len_frames ? len_frames[b] * len_mul : len_mul;
+  const long long len = it.len_in(b);
   const long long Fs = pt_frames_s(len, P, Q);
   const long long Nu = Fs ? PT_H * (Fs - 1) : 0, Nv = (Nu * Q + P - 1) / P;
   nu[b] = (int)(Nu / PT_H);
@@ -388,11 +382,11 @@ __global__ void pitch_geom_kernel(const int* __restrict__ len_frames, long long 
 }
 
 // the items shorter than n/2 + 1 samples come back as they are (grid (2, B): 512 samples cover them)
-__global__ __launch_bounds__(256) void pitch_short_kernel(const float* __restrict__ x, long long x_bstride, const int* __restrict__ len_frames,
-                                                          long long len_mul, float* __restrict__ y, long long y_bstride, long long n_count) {
+__global__ __launch_bounds__(256) void pitch_short_kernel(const float* __restrict__ x, long long x_bstride, const Items it, float* __restrict__ y,
+                                                          long long y_bstride, long long n_count) {
   const int b = blockIdx.y;
   const long long j = (long long)blockIdx.x * 256 + threadIdx.x;
-  const long long len = len_frames ? len_frames[b] * len_mul : len_mul;
+  const long long len = it.len_in(b);
   if (len >= PT_M + 1 || j >= len || j >= n_count) return;
   y[(long long)b * y_bstride + j] = x[(long long)b * x_bstride + j];
 }
@@ -413,6 +407,7 @@ static int pitch_plan(float semitones, int* P, int* Q) {
 
 // The resampler tables of the ratios in use, per (device, P, Q).  A server may see any of 1501 ratios, so unlike the output-rate tables
 // (which captured graphs point into) these are evicted, least recently used first; a call in flight keeps its table alive.
+// (Not a DevTabs of op_door.hip.h: that one never evicts and hands out plain pointers.)
 #define PT_MAX_TABS 32
 static std::mutex g_pt_mu;
 static std::map<std::tuple<int, int, int>, std::pair<std::shared_ptr<ResampleTab>, uint64_t>> g_pt_tabs;
@@ -446,92 +441,130 @@ static size_t pitch_item_bytes(long long len, int P, int Q, bool formant) {
   return (size_t)(Fa + 2) * PT_NB * (formant ? 12 : 8) + (size_t)Fs * PT_NB * 4 + (size_t)Fs * PT_N * 4 + (size_t)(Fs - 1) * PT_H * 4 + 2 * sizeof(int) + 64;
 }
 
-// y[b][0 .. n_count) = the shifted item b, for B items on `stream`; x / len_frames / len_mul as in denoise_launch (device pointers),
-// h_len their lengths on the host.  Allocates its scratch and waits for the stream before it frees it: not capturable.  y is not x.
-// u_out (nullable): the stretch door -- u goes to u_out[b * u_bstride + j], j < u_bstride, and nothing is resampled.
-// formant: steps 3a-3d -- the synthesis reads the corrected magnitudes, the phase recursion the plain ones.
-static int pitch_run(int device, hipStream_t stream, const float* x, long long x_bstride, long long x_n, const int* len_frames, long long len_mul,
-                     const long long* h_len, int B, int P, int Q, bool formant, float* y, long long y_bstride, long long n_count, float* u_out,
-                     long long u_bstride) {
-  if (B <= 0) return VITS_OK;
+// ---- the phase-vocoder group runner (this stage and contour.hip.h) -------------------------------------------------------
+struct PvGroup { int b0, c; long long mx; };  // consecutive items whose scratch fits: the first, how many, the longest one's samples
+struct PvCarve {  // the scratch of a group, handed out front to back
+  char *base, *p;
+  template <typename T>
+  T* take(size_t n) { T* r = reinterpret_cast<T*>(p); p += sizeof(T) * n; return r; }
+  void align8() { p += (8 - (p - base) % 8) % 8; }
+};
+struct PvGeom {  // what a stage's front() settles for a group
+  Items it;                    // the group's items as the vocoder kernels see them
+  long long Fa = 0, Fs = 0;    // analysis frames of the longest item (0: no vocoder launches); the steps the strides and grids hold
+  int P = 1, Q = 1;            // the plain kernels' ratio
+  long long *steps = nullptr, s_bs = 0;  // TAB: the group's step table, rows at s_bs
+};
+
+// B items of h_len samples through the vocoder on `stream`, group by group: one scratch of head_bytes + the largest group's bytes
+// (item_bytes(len) of its longest item times its count, at most VITS_PITCH_MAX_SCRATCH), carved per group as front's own | mag | th |
+// analysis' own | phi | (align 8) | frames | u | finish's own, then analysis -> phase -> synth -> ola.  Allocates, and waits for the
+// stream before it frees: not capturable.  The stage supplies head(scr): its uploads in front of the groups; front(S, g, &v): its
+// scratch in front and the group's geometry (both hipError_t; front may wait for the stream); analysis(S, g, v, D, mag, th, a_bs): step 1,
+// returning the magnitudes the synthesis reads; finish(S, g, v, u, u_bs): what becomes of u [c][u_bs] (null: a group without frames).
+// u_out (nullable): the stretch doors -- u of item b goes to u_out[b * u_bstride + j], j < u_bstride (zeros for a frameless group).
+// `at`: what the refusal of an item that fits no group says behind "bytes of scratch".
+template <bool TAB, typename ItemBytes, typename Head, typename Front, typename Analysis, typename Finish>
+static int pv_run(const char* what, const char* at, int device, hipStream_t stream, const long long* h_len, int B, size_t head_bytes, float* u_out,
+                  long long u_bstride, ItemBytes&& item_bytes, Head&& head, Front&& front, Analysis&& analysis, Finish&& finish) {
   const StftTab* D = nullptr;
   TRY(stft_tab_get(device, PT_N, &D));
-  std::shared_ptr<ResampleTab> R;  // (held until the stream has been waited for)
-  if (!u_out) TRY(pitch_tab_get(device, P, Q, &R));
-  // groups of consecutive items whose scratch fits
-  std::vector<std::pair<int, int>> groups;  // (first item, count)
+  std::vector<PvGroup> groups;
   size_t need = 0;
   for (int b0 = 0; b0 < B;) {
     long long mx = 0;
     int c = 0;
     while (b0 + c < B && c < 65535) {
       const long long m2 = std::max(mx, h_len[b0 + c]);
-      if (pitch_item_bytes(m2, P, Q, formant) * (size_t)(c + 1) > (size_t)VITS_PITCH_MAX_SCRATCH) break;
+      if (item_bytes(m2) * (size_t)(c + 1) > (size_t)VITS_PITCH_MAX_SCRATCH) break;
       mx = m2;
       ++c;
     }
-    if (!c) return fail(VITS_ERR_UNSUPPORTED, "pitch: an item of %lld samples needs %zu bytes of scratch at %d/%d (limit %lld)", h_len[b0],
-                        pitch_item_bytes(h_len[b0], P, Q, formant), P, Q, (long long)VITS_PITCH_MAX_SCRATCH);
-    need = std::max(need, pitch_item_bytes(mx, P, Q, formant) * (size_t)c);
-    groups.emplace_back(b0, c);
+    if (!c) return fail(VITS_ERR_UNSUPPORTED, "%s: an item of %lld samples needs %zu bytes of scratch%s (limit %lld)", what, h_len[b0],
+                        item_bytes(h_len[b0]), at, (long long)VITS_PITCH_MAX_SCRATCH);
+    need = std::max(need, item_bytes(mx) * (size_t)c);
+    groups.push_back({b0, c, mx});
     b0 += c;
   }
   HIP_TRY(hipSetDevice(device));
   char* scr = nullptr;
-  if (hipMalloc((void**)&scr, need) != hipSuccess) return fail(VITS_ERR_NOMEM, "pitch: scratch alloc of %zu bytes failed", need);
-  for (const auto& g : groups) {
-    const int b0 = g.first, c = g.second;
-    long long mx = 0;
-    for (int b = 0; b < c; ++b) mx = std::max(mx, h_len[b0 + b]);
-    const float* xg = x + (long long)b0 * x_bstride;
-    const int* lg = len_frames ? len_frames + b0 : nullptr;
-    const long long Fa = pt_frames_a(mx), Fs = pt_frames_s(mx, P, Q);
-    if (Fa) {
-      const long long a_bs = (Fa + 2) * PT_NB, p_bs = Fs * PT_NB, f_bs = Fs * PT_N, u_bs = (Fs - 1) * PT_H;
-      char* p = scr;
-      float* d_mag = reinterpret_cast<float*>(p); p += sizeof(float) * (size_t)c * a_bs;
-      unsigned* d_th = reinterpret_cast<unsigned*>(p); p += sizeof(unsigned) * (size_t)c * a_bs;
-      float* d_magf = d_mag;  // what the synthesis reads
-      if (formant) { d_magf = reinterpret_cast<float*>(p); p += sizeof(float) * (size_t)c * a_bs; }
-      unsigned* d_phi = reinterpret_cast<unsigned*>(p); p += sizeof(unsigned) * (size_t)c * p_bs;
-      p += (8 - (p - scr) % 8) % 8;  // (the frames are written as float2)
-      float* d_fr = reinterpret_cast<float*>(p); p += sizeof(float) * (size_t)c * f_bs;
-      float* d_u = reinterpret_cast<float*>(p); p += sizeof(float) * (size_t)c * u_bs;
-      int* d_nu = reinterpret_cast<int*>(p); p += sizeof(int) * (size_t)c;
-      int* d_crop = reinterpret_cast<int*>(p);
-      hipLaunchKernelGGL(pitch_analysis_kernel, dim3((unsigned)((Fa + 2 + SF_FPB - 1) / SF_FPB), c), dim3(64 * SF_FPB), 0, stream, xg, x_bstride,
-                         x_n, lg, len_mul, D->d_win, D->d_tw, d_mag, d_th, a_bs);
-      if (formant)
-        hipLaunchKernelGGL(pitch_formant_kernel<false>, dim3((unsigned)((Fa + 2 + SF_FPB - 1) / SF_FPB), c), dim3(64 * SF_FPB), 0, stream, xg,
-                           x_bstride, x_n, d_mag, a_bs, lg, len_mul, P, Q, d_magf);
-      hipLaunchKernelGGL(pitch_phase_kernel<false>, dim3(c), dim3(64 * PT_WAVES), 0, stream, d_mag, d_th, a_bs, lg, len_mul, P, Q,
-                         (const long long*)nullptr, 0LL, d_phi, p_bs);
-      hipLaunchKernelGGL(pitch_synth_kernel<false>, dim3((unsigned)((Fs + SF_FPB - 1) / SF_FPB), c), dim3(64 * SF_FPB), 0, stream, d_magf, a_bs, d_phi,
-                         p_bs, lg, len_mul, P, Q, (const long long*)nullptr, 0LL, D->d_win, D->d_tw, d_fr, f_bs);
-      if (u_out) {
-        hipLaunchKernelGGL(pitch_ola_kernel<false>, dim3((unsigned)((u_bstride + 255) / 256), c), dim3(256), 0, stream, d_fr, f_bs, lg, len_mul, P, Q,
-                           (const long long*)nullptr, 0LL, D->d_env, u_out + (long long)b0 * u_bstride, u_bstride, u_bstride);
-      } else {
-        hipLaunchKernelGGL(pitch_ola_kernel<false>, dim3((unsigned)((u_bs + 255) / 256), c), dim3(256), 0, stream, d_fr, f_bs, lg, len_mul, P, Q,
-                           (const long long*)nullptr, 0LL, D->d_env, d_u, u_bs, u_bs);
-        hipLaunchKernelGGL(pitch_geom_kernel, dim3((unsigned)((c + 63) / 64)), dim3(64), 0, stream, lg, len_mul, c, P, Q, d_nu, d_crop);
-        resample_launch_crop(stream, *R, d_u, u_bs, u_bs, d_nu, PT_H, d_crop, c, y + (long long)b0 * y_bstride, y_bstride, n_count);
-      }
+  if (hipMalloc((void**)&scr, head_bytes + need) != hipSuccess) return fail(VITS_ERR_NOMEM, "%s: scratch alloc of %zu bytes failed", what, head_bytes + need);
+  hipError_t e = head(scr);
+  for (size_t gi = 0; gi < groups.size() && e == hipSuccess; ++gi) {
+    const PvGroup& g = groups[gi];
+    const int c = g.c;
+    PvCarve S{scr, scr + head_bytes};
+    PvGeom v;
+    if ((e = front(S, g, &v)) != hipSuccess) break;
+    float* u = nullptr;
+    long long u_bs = 0;
+    if (v.Fa) {
+      const long long a_bs = (v.Fa + 2) * PT_NB, p_bs = v.Fs * PT_NB, f_bs = v.Fs * PT_N;
+      float* mag = S.take<float>((size_t)c * a_bs);
+      unsigned* th = S.take<unsigned>((size_t)c * a_bs);
+      const float* magf = analysis(S, g, v, *D, mag, th, a_bs);
+      unsigned* phi = S.take<unsigned>((size_t)c * p_bs);
+      S.align8();  // (the frames are written as float2)
+      float* fr = S.take<float>((size_t)c * f_bs);
+      u_bs = u_out ? u_bstride : (v.Fs - 1) * PT_H;
+      u = u_out ? u_out + (long long)g.b0 * u_bstride : S.take<float>((size_t)c * u_bs);
+      hipLaunchKernelGGL(pitch_phase_kernel<TAB>, dim3(c), dim3(64 * PT_WAVES), 0, stream, mag, th, a_bs, v.it, v.P, v.Q, v.steps, v.s_bs, phi, p_bs);
+      hipLaunchKernelGGL(pitch_synth_kernel<TAB>, dim3((unsigned)((v.Fs + SF_FPB - 1) / SF_FPB), c), dim3(64 * SF_FPB), 0, stream, magf, a_bs, phi,
+                         p_bs, v.it, v.P, v.Q, v.steps, v.s_bs, D->d_win, D->d_tw, fr, f_bs);
+      hipLaunchKernelGGL(pitch_ola_kernel<TAB>, dim3((unsigned)((u_bs + 255) / 256), c), dim3(256), 0, stream, fr, f_bs, v.it, v.P, v.Q, v.steps,
+                         v.s_bs, D->d_env, u, u_bs, u_bs);
     } else if (u_out) {
-      hipMemsetAsync(u_out + (long long)b0 * u_bstride, 0, sizeof(float) * (size_t)c * u_bstride, stream);
-    } else {
-      for (int b = 0; b < c; ++b) hipMemsetAsync(y + (long long)(b0 + b) * y_bstride, 0, sizeof(float) * (size_t)n_count, stream);
+      hipMemsetAsync(u_out + (long long)g.b0 * u_bstride, 0, sizeof(float) * (size_t)c * u_bstride, stream);
     }
-    if (!u_out)
-      hipLaunchKernelGGL(pitch_short_kernel, dim3(2, c), dim3(256), 0, stream, xg, x_bstride, lg, len_mul, y + (long long)b0 * y_bstride, y_bstride,
-                         n_count);
+    finish(S, g, v, u, u_bs);
   }
-  hipError_t e = hipGetLastError();
+  if (e == hipSuccess) e = hipGetLastError();
   const hipError_t e2 = hipStreamSynchronize(stream);
   hipFree(scr);
   if (e == hipSuccess) e = e2;
-  if (e != hipSuccess) return fail(VITS_ERR_DEVICE, "pitch: %s", hipGetErrorString(e));
+  if (e != hipSuccess) return fail(VITS_ERR_DEVICE, "%s: %s", what, hipGetErrorString(e));
   return VITS_OK;
+}
+
+// y[b][0 .. n_count) = the shifted item b, for B items on `stream`; x / x_n / it as in denoise_launch (device pointers), h_len the
+// items' lengths on the host.  pv_run's: not capturable.  y is not x.  u_out (nullable): the stretch door -- nothing is resampled.
+// formant: steps 3a-3d -- the synthesis reads the corrected magnitudes, the phase recursion the plain ones.
+static int pitch_run(int device, hipStream_t stream, const float* x, long long x_bstride, long long x_n, const Items& it, const long long* h_len,
+                     int B, int P, int Q, bool formant, float* y, long long y_bstride, long long n_count, float* u_out, long long u_bstride) {
+  if (B <= 0) return VITS_OK;
+  std::shared_ptr<ResampleTab> R;  // (held until the stream has been waited for)
+  if (!u_out) TRY(pitch_tab_get(device, P, Q, &R));
+  char at[32];
+  snprintf(at, sizeof at, " at %d/%d", P, Q);
+  return pv_run<false>(
+      "pitch", at, device, stream, h_len, B, 0, u_out, u_bstride, [&](long long len) { return pitch_item_bytes(len, P, Q, formant); },
+      [](char*) { return hipSuccess; },
+      [&](PvCarve&, const PvGroup& g, PvGeom* v) {
+        *v = PvGeom{it.from(g.b0), pt_frames_a(g.mx), pt_frames_s(g.mx, P, Q), P, Q};
+        return hipSuccess;
+      },
+      [&](PvCarve& S, const PvGroup& g, const PvGeom& v, const StftTab& D, float* mag, unsigned* th, long long a_bs) -> const float* {
+        const float* xg = x + (long long)g.b0 * x_bstride;
+        const dim3 grid((unsigned)((v.Fa + 2 + SF_FPB - 1) / SF_FPB), g.c);
+        hipLaunchKernelGGL(pitch_analysis_kernel, grid, dim3(64 * SF_FPB), 0, stream, xg, x_bstride, x_n, v.it, D.d_win, D.d_tw, mag, th, a_bs);
+        if (!formant) return mag;
+        float* magf = S.take<float>((size_t)g.c * a_bs);
+        hipLaunchKernelGGL(pitch_formant_kernel<false>, grid, dim3(64 * SF_FPB), 0, stream, xg, x_bstride, x_n, mag, a_bs, v.it, P, Q, magf);
+        return magf;
+      },
+      [&](PvCarve& S, const PvGroup& g, const PvGeom& v, const float* u, long long u_bs) {
+        if (u_out) return;
+        float* yg = y + (long long)g.b0 * y_bstride;
+        if (u) {  // N_u / H and the crop per item, then u -> y through the P -> Q resampler
+          int* d_nu = S.take<int>(g.c);
+          int* d_crop = S.take<int>(g.c);
+          hipLaunchKernelGGL(pitch_geom_kernel, dim3((unsigned)((g.c + 63) / 64)), dim3(64), 0, stream, v.it, g.c, P, Q, d_nu, d_crop);
+          resample_launch_crop(stream, *R, u, u_bs, u_bs, Items{d_nu, PT_H}, d_crop, g.c, yg, y_bstride, n_count);
+        } else {
+          for (int b = 0; b < g.c; ++b) hipMemsetAsync(yg + (long long)b * y_bstride, 0, sizeof(float) * (size_t)n_count, stream);
+        }
+        hipLaunchKernelGGL(pitch_short_kernel, dim3(2, g.c), dim3(256), 0, stream, x + (long long)g.b0 * x_bstride, x_bstride, v.it, yg, y_bstride, n_count);
+      });
 }
 
 // what a shifting entry point of a vocoder needs checked before any work is queued
@@ -564,7 +597,7 @@ static int pitch_gain_run(int device, const float* dx, const int* dl, int B, lon
   if (!Fa) return VITS_OK;
   HIP_TRY(hipSetDevice(device));
   hipLaunchKernelGGL(pitch_formant_kernel<true>, dim3((unsigned)((Fa + 2 + SF_FPB - 1) / SF_FPB), B), dim3(64 * SF_FPB), 0, nullptr, dx, N, N,
-                     (const float*)nullptr, a_bs, dl, 1, P, Q, g);
+                     (const float*)nullptr, a_bs, Items{dl, 1}, P, Q, g);
   hipError_t e = hipGetLastError();
   const hipError_t e2 = hipStreamSynchronize(nullptr);
   if (e == hipSuccess) e = e2;
@@ -594,17 +627,16 @@ static int pitch_op(int device, const float* x, const int64_t* lengths, int32_t 
   }
   const long long Ny = stretch ? (long long)PT_H * (((N / PT_H + 2) * P + Q - 1) / Q - 1) : door == PT_DOOR_GAIN ? (N / PT_H + 3) * PT_NB : N;
   OpDoor d("pitch", device);
-  // every item's own samples only: what lies at and beyond lengths[b] never reaches the device
-  float* dx = d.out<float>((size_t)B * N, 0);
-  for (int b = 0; b < B && d.ok(); ++b)
-    if (lengths[b]) d.hip(hipMemcpy(dx + (size_t)b * N, x + (size_t)b * N, sizeof(float) * (size_t)lengths[b], hipMemcpyHostToDevice));
+  float* dx = d.up_items(x, lengths, B, N);
   int* dl = d.up(len32.data(), B);
   // (the gain door's kernel writes rows [0, F_a + 2) only: the others are zeros from here)
   float* dy = d.out<float>((size_t)B * Ny, door == PT_DOOR_GAIN ? 0 : 0xff);
-  if (d.ok())
-    TRY(door == PT_DOOR_GAIN ? pitch_gain_run(device, dx, dl, B, N, P, Q, dy)
-        : stretch            ? pitch_run(device, nullptr, dx, N, N, dl, 1, len64.data(), B, P, Q, formant, nullptr, 0, 0, dy, Ny)
-                             : pitch_run(device, nullptr, dx, N, N, dl, 1, len64.data(), B, P, Q, formant, dy, Ny, Ny, nullptr, 0));
+  const Items it{dl, 1};
+  if (d.ok()) {
+    if (door == PT_DOOR_GAIN) TRY(pitch_gain_run(device, dx, dl, B, N, P, Q, dy));
+    else if (stretch) TRY(pitch_run(device, nullptr, dx, N, N, it, len64.data(), B, P, Q, formant, nullptr, 0, 0, dy, Ny));
+    else TRY(pitch_run(device, nullptr, dx, N, N, it, len64.data(), B, P, Q, formant, dy, Ny, Ny, nullptr, 0));
+  }
   d.finish();
   d.down(y, dy, (size_t)B * Ny);
   return d.rc();

@@ -21,7 +21,7 @@ struct ResamplePlan {
   int L = 1, M = 1, taps = 1, half = 0;
   long long W = 0;  // Hw = W / L
   int span = 0;     // LDS floats one workgroup stages
-  long long n_out(long long len) const { return (len * L + M - 1) / M; }
+  long long n_out(long long len) const { return ::n_out(len, L, M); }
 };
 
 static int resample_plan(int rate_in, int rate_out, ResamplePlan* out) {
@@ -88,7 +88,7 @@ static void resample_fill(const ResamplePlan& P, float* table) {
 // ---- the kernel -----------------------------------------------------------------------------------------------------
 // One workgroup = VITS_RESAMPLE_TILE consecutive outputs [n0, n0 + TILE) of item blockIdx.y, one per thread.
 //   x        item b's input at x + b * x_bstride; x[j] is input sample x_off + j, and only 0 <= j < x_n is ever read
-//   len      valid input samples of item b: len_frames[b] * len_mul (len_frames null: len_mul itself); samples >= len count as 0
+//   len      valid input samples of item b: it.len_in(b) (ragged.hip.h); samples >= len count as 0
 //   tab      the device table [taps][L] described at the top
 //   y        item b's output at y + b * y_bstride; y[j] is output n_begin + j, written for 0 <= j < n_count
 //            (exactly 0 for outputs at and beyond ceil(len * L / M))
@@ -96,14 +96,13 @@ static void resample_fill(const ResamplePlan& P, float* table) {
 // CROP (the pitch stage, include/vits_pitch.h): item b's outputs at and beyond crop[b] are 0 as well; without it crop is not read.
 template <typename OUT, bool CROP = false>
 __global__ __launch_bounds__(VITS_RESAMPLE_TILE) void resample_kernel(const float* __restrict__ x, long long x_bstride, long long x_off,
-                                                                      long long x_n, const int* __restrict__ len_frames, long long len_mul,
-                                                                      const float* __restrict__ tab, int L, int M, int taps, int half,
-                                                                      long long W, OUT* __restrict__ y, long long y_bstride,
-                                                                      long long n_begin, long long n_count, float scale,
-                                                                      const SynthDev* dv, const int* __restrict__ crop) {
+                                                                      long long x_n, const Items it, const float* __restrict__ tab, int L, int M,
+                                                                      int taps, int half, long long W, OUT* __restrict__ y, long long y_bstride,
+                                                                      long long n_begin, long long n_count, float scale, const SynthDev* dv,
+                                                                      const int* __restrict__ crop) {
   __shared__ float xs[RS_SPAN_MAX];
   const int b = blockIdx.y, tid = threadIdx.x;
-  const long long len = len_frames ? len_frames[b] * len_mul : len_mul;
+  const long long len = it.len_in(b);
   const long long n0 = n_begin + (long long)blockIdx.x * VITS_RESAMPLE_TILE;
   const long long nm0 = n0 * M;  // 64-bit: n * M passes 2^31 within minutes of audio
   const long long q0 = nm0 / L;
@@ -122,7 +121,7 @@ __global__ __launch_bounds__(VITS_RESAMPLE_TILE) void resample_kernel(const floa
   if (j_out >= n_count) return;
   const long long n = n0 + tid;
   float acc = 0.f;
-  long long n_end = (len * L + M - 1) / M;
+  long long n_end = n_out(len, L, M);
   if constexpr (CROP) n_end = n_end < crop[b] ? n_end : crop[b];
   if (n < n_end) {
     const int v = p0 + tid * M;  // < L + 255 * M: 32-bit
@@ -147,9 +146,12 @@ __global__ __launch_bounds__(VITS_RESAMPLE_TILE) void resample_kernel(const floa
 
 // ---- device tables, cached per (device, rate_in, rate_out) ------------------------------------------------------------
 struct ResampleTab { ResamplePlan P; float* d = nullptr; };
-static std::mutex g_rs_mu;
-static std::map<std::tuple<int, int, int>, ResampleTab> g_rs_tabs;
+static DevTabs<std::tuple<int, int, int>, ResampleTab> g_rs_tabs;
 #define RS_MAX_TABS 64  // per process: captured graphs hold the pointers, so entries are never evicted
+// L / M of the rate T returns at (null: the native rate, 1 / 1), and the items of a call returned at it
+struct Rate { int L, M; };
+static Rate rate_of(const ResampleTab* T) { return T ? Rate{T->P.L, T->P.M} : Rate{1, 1}; }
+static Items items_at(const ResampleTab* T, const int* units, long long mul, long long cap) { return Items{units, mul, rate_of(T).L, rate_of(T).M, cap}; }
 
 // the device copy of T.P's table (hipMalloc + a synchronous copy)
 static int resample_upload(int device, ResampleTab& T) {
@@ -165,40 +167,34 @@ static int resample_upload(int device, ResampleTab& T) {
 
 // Uploads on first use (call it outside stream capture).
 static int resample_get(int device, int rate_in, int rate_out, const ResampleTab** out) {
-  std::lock_guard<std::mutex> g(g_rs_mu);
-  const auto key = std::make_tuple(device, rate_in, rate_out);
-  auto it = g_rs_tabs.find(key);
-  if (it != g_rs_tabs.end()) { *out = &it->second; return VITS_OK; }
-  ResampleTab T;
-  TRY(resample_plan(rate_in, rate_out, &T.P));
-  if (g_rs_tabs.size() >= RS_MAX_TABS) return fail(VITS_ERR_UNSUPPORTED, "resample: more than %d distinct rate pairs in one process", RS_MAX_TABS);
-  TRY(resample_upload(device, T));
-  *out = &g_rs_tabs.emplace(key, T).first->second;
-  return VITS_OK;
+  return g_rs_tabs.get(std::make_tuple(device, rate_in, rate_out), out, [&](ResampleTab& T) {
+    TRY(resample_plan(rate_in, rate_out, &T.P));
+    if (g_rs_tabs.size() >= RS_MAX_TABS) return fail(VITS_ERR_UNSUPPORTED, "resample: more than %d distinct rate pairs in one process", RS_MAX_TABS);
+    return resample_upload(device, T);
+  });
 }
 
 // Outputs [n_begin, n_begin + n_count) of B items on `stream` (capturable: no allocation, no synchronisation).
 template <typename OUT>
 static void resample_launch(hipStream_t stream, const ResampleTab& T, const float* x, long long x_bstride, long long x_off, long long x_n,
-                            const int* len_frames, long long len_mul, int B, OUT* y, long long y_bstride, long long n_begin, long long n_count,
-                            float scale, const SynthDev* dv) {
+                            const Items& it, int B, OUT* y, long long y_bstride, long long n_begin, long long n_count, float scale,
+                            const SynthDev* dv) {
   if (n_count <= 0 || B <= 0) return;
   const ResamplePlan& P = T.P;
   const unsigned gx = (unsigned)((n_count + VITS_RESAMPLE_TILE - 1) / VITS_RESAMPLE_TILE);
-  hipLaunchKernelGGL(resample_kernel<OUT>, dim3(gx, B), dim3(VITS_RESAMPLE_TILE), 0, stream, x, x_bstride, x_off, x_n, len_frames, len_mul,
-                     T.d, P.L, P.M, P.taps, P.half, P.W, y, y_bstride, n_begin, n_count, scale, dv, nullptr);
+  hipLaunchKernelGGL(resample_kernel<OUT>, dim3(gx, B), dim3(VITS_RESAMPLE_TILE), 0, stream, x, x_bstride, x_off, x_n, it, T.d, P.L, P.M, P.taps,
+                     P.half, P.W, y, y_bstride, n_begin, n_count, scale, dv, nullptr);
 }
 
-// The form of the pitch stage (include/vits_pitch.h): float outputs [0, n_count) of B items whose input lengths are len_units[b] *
-// len_mul and whose outputs at and beyond crop[b] are 0 (both device arrays).
-static void resample_launch_crop(hipStream_t stream, const ResampleTab& T, const float* x, long long x_bstride, long long x_n,
-                                 const int* len_units, long long len_mul, const int* crop, int B, float* y, long long y_bstride,
-                                 long long n_count) {
+// The form of the pitch stage (include/vits_pitch.h): float outputs [0, n_count) of B items whose input lengths are it.len_in(b) and
+// whose outputs at and beyond crop[b] are 0 (a device array).
+static void resample_launch_crop(hipStream_t stream, const ResampleTab& T, const float* x, long long x_bstride, long long x_n, const Items& it,
+                                 const int* crop, int B, float* y, long long y_bstride, long long n_count) {
   if (n_count <= 0 || B <= 0) return;
   const ResamplePlan& P = T.P;
   const unsigned gx = (unsigned)((n_count + VITS_RESAMPLE_TILE - 1) / VITS_RESAMPLE_TILE);
-  hipLaunchKernelGGL((resample_kernel<float, true>), dim3(gx, B), dim3(VITS_RESAMPLE_TILE), 0, stream, x, x_bstride, 0LL, x_n, len_units, len_mul,
-                     T.d, P.L, P.M, P.taps, P.half, P.W, y, y_bstride, 0LL, n_count, 1.f, (const SynthDev*)nullptr, crop);
+  hipLaunchKernelGGL((resample_kernel<float, true>), dim3(gx, B), dim3(VITS_RESAMPLE_TILE), 0, stream, x, x_bstride, 0LL, x_n, it, T.d, P.L, P.M,
+                     P.taps, P.half, P.W, y, y_bstride, 0LL, n_count, 1.f, (const SynthDev*)nullptr, crop);
 }
 
 // 0 / the native rate -> 0 (the entry point's own path); anything else must have a plan
@@ -251,7 +247,7 @@ int vits_op_resample(int device, const float* x, const int64_t* lengths, int32_t
   float* dx = d.up(x, (size_t)B * N);
   int* dl = d.up(len32.data(), B);
   float* dy = d.out<float>(B * Ny);
-  if (d.ok()) resample_launch<float>(nullptr, *T, dx, N, 0, N, dl, 1, B, dy, Ny, 0, Ny, 1.f, nullptr);
+  if (d.ok()) resample_launch<float>(nullptr, *T, dx, N, 0, N, Items{dl, 1}, B, dy, Ny, 0, Ny, 1.f, nullptr);
   d.finish();
   d.down(y, dy, B * Ny);
   return d.rc();

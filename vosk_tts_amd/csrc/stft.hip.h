@@ -215,40 +215,35 @@ struct StftTab {
   float2* d_tw = nullptr;    // [n]  exp(-2 pi i t / n)
   float* d_env = nullptr;    // [3][hop]  1 / sum w^2: head (frame -1 missing), interior, tail (frame F missing)
 };
-static std::mutex g_sf_mu;
-static std::map<std::pair<int, int>, StftTab> g_sf_tabs;  // never evicted: at most five frame lengths per device
+static DevTabs<std::pair<int, int>, StftTab> g_sf_tabs;  // at most five frame lengths per device
 
 // Uploads on first use (hipMalloc + a synchronous copy: call it outside stream capture).  n: a power of two in
 // [VITS_DENOISE_MIN_FILTER, VITS_DENOISE_MAX_FILTER] (denoise_filter_arg).
 static int stft_tab_get(int device, int n, const StftTab** out) {
-  std::lock_guard<std::mutex> g(g_sf_mu);
-  const auto key = std::make_pair(device, n);
-  auto it = g_sf_tabs.find(key);
-  if (it != g_sf_tabs.end()) { *out = &it->second; return VITS_OK; }
-  StftTab T;
-  T.n = n;
-  for (int m = n >> 1; m > 1; m >>= 1) ++T.log2m;
-  const int hop = n / 4;
-  std::vector<float> host((size_t)3 * n + 3 * hop);  // tw | win | env, as on the device
-  float *tw = host.data(), *win = tw + 2 * n, *env = win + n;
-  std::vector<double> w2(n);
-  for (int i = 0; i < n; ++i) {
-    const double s = sin(M_PI * (double)i / (double)n), a = 2.0 * M_PI * (double)i / (double)n;
-    win[i] = (float)(s * s);
-    w2[i] = (s * s) * (s * s);
-    tw[2 * i] = (float)cos(a);
-    tw[2 * i + 1] = (float)-sin(a);
-  }
-  for (int r = 0; r < hop; ++r) {
-    env[r] = (float)(1.0 / (w2[r] + w2[r + hop] + w2[r + 2 * hop]));
-    env[hop + r] = (float)(1.0 / (w2[r] + w2[r + hop] + w2[r + 2 * hop] + w2[r + 3 * hop]));
-    env[2 * hop + r] = (float)(1.0 / (w2[r + hop] + w2[r + 2 * hop] + w2[r + 3 * hop]));
-  }
-  float* d = nullptr;
-  TRY(dev_table_upload(device, "denoise", host.data(), host.size() * sizeof(float), (void**)&d));
-  T.d_tw = reinterpret_cast<float2*>(d);
-  T.d_win = d + 2 * n;
-  T.d_env = d + 3 * n;
-  *out = &g_sf_tabs.emplace(key, T).first->second;
-  return VITS_OK;
+  return g_sf_tabs.get(std::make_pair(device, n), out, [&](StftTab& T) {
+    T.n = n;
+    for (int m = n >> 1; m > 1; m >>= 1) ++T.log2m;
+    const int hop = n / 4;
+    std::vector<float> host((size_t)3 * n + 3 * hop);  // tw | win | env, as on the device
+    float *tw = host.data(), *win = tw + 2 * n, *env = win + n;
+    std::vector<double> w2(n);
+    for (int i = 0; i < n; ++i) {
+      const double s = sin(M_PI * (double)i / (double)n), a = 2.0 * M_PI * (double)i / (double)n;
+      win[i] = (float)(s * s);
+      w2[i] = (s * s) * (s * s);
+      tw[2 * i] = (float)cos(a);
+      tw[2 * i + 1] = (float)-sin(a);
+    }
+    for (int r = 0; r < hop; ++r) {
+      env[r] = (float)(1.0 / (w2[r] + w2[r + hop] + w2[r + 2 * hop]));
+      env[hop + r] = (float)(1.0 / (w2[r] + w2[r + hop] + w2[r + 2 * hop] + w2[r + 3 * hop]));
+      env[2 * hop + r] = (float)(1.0 / (w2[r + hop] + w2[r + 2 * hop] + w2[r + 3 * hop]));
+    }
+    float* d = nullptr;
+    TRY(dev_table_upload(device, "denoise", host.data(), host.size() * sizeof(float), (void**)&d));
+    T.d_tw = reinterpret_cast<float2*>(d);
+    T.d_win = d + 2 * n;
+    T.d_env = d + 3 * n;
+    return VITS_OK;
+  });
 }

@@ -910,7 +910,7 @@ static int stts_synth_fast(stts_model* m, const int64_t* ids, int32_t Tx, const 
         return fail(VITS_ERR_NOMEM, "denoise buffers of frame bucket %d", TB);
       }
     }
-    denoise_launch(st, *dn.T, Bk->d_audio, 0, 0, (long long)Bk->audio_elems, nullptr, S, 1, dn.bias, dn.strength, Bk->d_dn + Bk->audio_elems,
+    denoise_launch(st, *dn.T, Bk->d_audio, 0, 0, (long long)Bk->audio_elems, Items{nullptr, S}, 1, dn.bias, dn.strength, Bk->d_dn + Bk->audio_elems,
                    (long long)Bk->dn_scr_elems, Bk->d_dn, 0, 0, S);
     hipMemcpyAsync(Bk->out_h, Bk->d_dn, sizeof(float) * (size_t)S, hipMemcpyDeviceToHost, st);
   }
@@ -1034,7 +1034,7 @@ static int stts_synthesize_impl(stts_model* m, const int64_t* ids, int32_t Tx, c
         float* d_dn = call.dev<float>((size_t)S);
         float* d_scr = call.dev<float>(sc);
         if (!d_dn || !d_scr) { hipStreamSynchronize(s->stream); rc = fail(VITS_ERR_NOMEM, "alloc failed"); }
-        else denoise_launch(s->stream, *dn.T, d_audio, 0, 0, S, nullptr, S, 1, dn.bias, dn.strength, d_scr, (long long)sc, d_dn, 0, 0, S);
+        else denoise_launch(s->stream, *dn.T, d_audio, 0, 0, S, Items{nullptr, S}, 1, dn.bias, dn.strength, d_scr, (long long)sc, d_dn, 0, 0, S);
         d_src = d_dn;
       }
       if (rc == VITS_OK) hipMemcpyAsync(h_audio, d_src, sizeof(float) * (size_t)S, hipMemcpyDeviceToHost, s->stream);
@@ -1298,7 +1298,7 @@ static int stts_synthesize_batch_impl(stts_model* m, const int64_t* ids, const i
       float* d_dn = call.dev<float>((size_t)B * S);
       float* d_scr = call.dev<float>((size_t)B * sc);
       if (!d_dn || !d_scr) { hipStreamSynchronize(s->stream); rc = fail(VITS_ERR_NOMEM, "alloc failed"); }  // (the decoder is still queued on buffers of this call)
-      else denoise_launch(s->stream, *dn.T, d_audio, S, 0, S, d_len, v->hp.hop_length, B, dn.bias, dn.strength, d_scr, (long long)sc, d_dn, S, 0, S);
+      else denoise_launch(s->stream, *dn.T, d_audio, S, 0, S, Items{d_len, v->hp.hop_length}, B, dn.bias, dn.strength, d_scr, (long long)sc, d_dn, S, 0, S);
       d_src = d_dn;
     }
     if (rc == VITS_OK) hipMemcpyAsync(h_audio, d_src, sizeof(float) * (size_t)B * S, hipMemcpyDeviceToHost, s->stream);

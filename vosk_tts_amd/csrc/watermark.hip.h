@@ -79,19 +79,18 @@ __device__ __forceinline__ float wm_bin_gain(uint32_t mk, int q, int k, float gp
 }
 
 // The marked, windowed frames of every item: wave w of workgroup blockIdx.x owns frame f = blockIdx.x * SF_FPB + w.
-//   x      item b at x + b * x_bstride, samples [0, len), len = ld_len(..) (loudness.hip.h: the item as returned, at most N)
+//   x      item b at x + b * x_bstride, samples [0, len), len = it.len_out(b) (ragged.hip.h: the item as returned, at most it.cap)
 //   out    out[b * out_bstride + f * n + i]; an item shorter than n/2 + 1 has no frames (wm_ola_kernel passes it through)
 //   words  PAYLOAD: the coded word of item b at words[b]; not read otherwise
 template <bool PAYLOAD>
-__global__ __launch_bounds__(64 * SF_FPB) void wm_frames_kernel(const float* __restrict__ x, long long x_bstride, long long N,
-                                                                const int* __restrict__ len_frames, long long len_mul, int L, int Mr,
-                                                                const float* __restrict__ win, const float2* __restrict__ tw, uint32_t mk,
-                                                                float gp, float gm, float* __restrict__ out, long long out_bstride,
+__global__ __launch_bounds__(64 * SF_FPB) void wm_frames_kernel(const float* __restrict__ x, long long x_bstride, const Items it,
+                                                                const float* __restrict__ win, const float2* __restrict__ tw, uint32_t mk, float gp,
+                                                                float gm, float* __restrict__ out, long long out_bstride,
                                                                 const uint32_t* __restrict__ words) {
   __shared__ float lds[SF_FPB][4][SF_PLANE];
   const int wv = threadIdx.x >> 6, t = threadIdx.x & 63;
   const int b = blockIdx.y;
-  const long long len = ld_len(len_frames, len_mul, L, Mr, N, b);
+  const long long len = it.len_out(b);
   const long long F = len >= WM_M + 1 ? 1 + len / WM_H : 0;
   const long long f = (long long)blockIdx.x * SF_FPB + wv;
   if ((long long)blockIdx.x * SF_FPB >= F) return;  // the whole workgroup is beyond the item: uniform exit
@@ -121,13 +120,12 @@ __global__ __launch_bounds__(64 * SF_FPB) void wm_frames_kernel(const float* __r
 // beyond len; an item shorter than n/2 + 1 samples is x.  OUT = int16_t: pcm16_of.
 template <typename OUT>
 __global__ __launch_bounds__(256) void wm_ola_kernel(const float* __restrict__ fr, long long fr_bstride, const float* __restrict__ x,
-                                                     long long x_bstride, long long N, const int* __restrict__ len_frames, long long len_mul,
-                                                     int L, int Mr, const float* __restrict__ inv_env, OUT* __restrict__ y, long long y_bstride,
-                                                     long long n_count, float scale) {
+                                                     long long x_bstride, const Items it, const float* __restrict__ inv_env, OUT* __restrict__ y,
+                                                     long long y_bstride, long long n_count, float scale) {
   const int b = blockIdx.y;
   const long long j = (long long)blockIdx.x * 256 + threadIdx.x;
   if (j >= n_count) return;
-  const long long len = ld_len(len_frames, len_mul, L, Mr, N, b);
+  const long long len = it.len_out(b);
   float v = 0.f;
   if (j < len) {
     const long long F = 1 + len / WM_H;
@@ -375,28 +373,24 @@ static int wm_req(bool on, uint32_t key, float depth_db, WmReq* out, bool payloa
 // floats of scratch one item of N samples needs
 static size_t wm_scratch_elems(long long N) { return (size_t)(N / WM_H + 1) * WM_N; }
 
-// B items x [B, N] (item b: ld_len(len_frames, len_mul, L, Mr, N, b) samples) -> y [B, n_count columns] on `stream` (capturable: no
-// allocation, no synchronisation).  scratch holds B * scratch_bstride floats, scratch_bstride >= wm_scratch_elems(N).  d_words: the
+// B items x [B, N] (item b: it.len_out(b) samples) -> y [B, n_count columns] on `stream` (capturable: no
+// allocation, no synchronisation).  scratch holds B * scratch_bstride floats, scratch_bstride >= wm_scratch_elems(it.cap).  d_words: the
 // coded words [B] on the device where q.payload (an argument of the launch), not read otherwise.
 template <typename OUT>
-static void wm_launch(hipStream_t stream, const WmReq& q, const float* x, long long x_bstride, long long N, const int* len_frames,
-                      long long len_mul, int L, int Mr, int B, float* scratch, long long scratch_bstride, OUT* y, long long y_bstride,
-                      long long n_count, float scale, const uint32_t* d_words = nullptr) {
+static void wm_launch(hipStream_t stream, const WmReq& q, const float* x, long long x_bstride, const Items& it, int B, float* scratch,
+                      long long scratch_bstride, OUT* y, long long y_bstride, long long n_count, float scale, const uint32_t* d_words = nullptr) {
   if (n_count <= 0 || B <= 0) return;
   const StftTab& T = *q.T;
-  const long long Fmax = N >= WM_M + 1 ? 1 + N / WM_H : 0;
+  const long long Fmax = it.cap >= WM_M + 1 ? 1 + it.cap / WM_H : 0;
   const uint32_t mk = wm_mix(q.key);
   if (Fmax > 0) {
     const dim3 grid((unsigned)cdiv((int)Fmax, SF_FPB), B), block(64 * SF_FPB);
-    if (q.payload)
-      hipLaunchKernelGGL(wm_frames_kernel<true>, grid, block, 0, stream, x, x_bstride, N, len_frames, len_mul, L, Mr, T.d_win, T.d_tw, mk, q.gp, q.gm, scratch,
-                         scratch_bstride, d_words);
-    else
-      hipLaunchKernelGGL(wm_frames_kernel<false>, grid, block, 0, stream, x, x_bstride, N, len_frames, len_mul, L, Mr, T.d_win, T.d_tw, mk, q.gp, q.gm, scratch,
-                         scratch_bstride, (const uint32_t*)nullptr);
+    if (q.payload) hipLaunchKernelGGL(wm_frames_kernel<true>, grid, block, 0, stream, x, x_bstride, it, T.d_win, T.d_tw, mk, q.gp, q.gm, scratch,
+                                      scratch_bstride, d_words);
+    else hipLaunchKernelGGL(wm_frames_kernel<false>, grid, block, 0, stream, x, x_bstride, it, T.d_win, T.d_tw, mk, q.gp, q.gm, scratch,
+                            scratch_bstride, (const uint32_t*)nullptr);
   }
-  hipLaunchKernelGGL(wm_ola_kernel<OUT>, dim3((unsigned)((n_count + 255) / 256), B), dim3(256), 0, stream, scratch, scratch_bstride, x, x_bstride, N,
-                     len_frames, len_mul, L, Mr, T.d_env, y, y_bstride, n_count, scale);
+  hipLaunchKernelGGL(wm_ola_kernel<OUT>, dim3((unsigned)((n_count + 255) / 256), B), dim3(256), 0, stream, scratch, scratch_bstride, x, x_bstride, it, T.d_env, y, y_bstride, n_count, scale);
 }
 
 // ---- entry points ----------------------------------------------------------------------------------------------------------
@@ -414,7 +408,7 @@ static int wm_op(int device, const float* x, const int64_t* lengths, int32_t B, 
   uint32_t* dw = q.payload ? d.up(words, (size_t)B) : nullptr;
   float* ds = d.dev<float>((size_t)B * sc);
   float* dy = d.out<float>((size_t)B * N);
-  if (d.ok()) wm_launch<float>(nullptr, q, dx, N, N, dl, 1, 1, 1, B, ds, (long long)sc, dy, N, N, 1.f, dw);
+  if (d.ok()) wm_launch<float>(nullptr, q, dx, N, Items{dl, 1, 1, 1, N}, B, ds, (long long)sc, dy, N, N, 1.f, dw);
   d.finish();
   d.down(y, dy, (size_t)B * N);
   return d.rc();
