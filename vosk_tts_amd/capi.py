@@ -321,6 +321,13 @@ class SynthWatermarkPayloadOpts(SynthWatermarkOpts):
     _fields_ = WATERMARK_PAYLOAD_FIELDS
 
 
+# include/vits_watermark_scan.h
+WATERMARK_SCAN_MAX_SPAN = 8        # VITS_WATERMARK_SCAN_MAX_SPAN
+WATERMARK_SCAN_DEFAULT_SPAN = 4    # VITS_WATERMARK_SCAN_DEFAULT_SPAN
+WATERMARK_SCAN_PILOTS = 1          # VITS_WATERMARK_SCAN_PILOTS
+WATERMARK_PERIOD_SAMPLES = 16384   # VITS_WATERMARK_PERIOD_SAMPLES
+
+
 def payload_spec(payload):
     """watermark_payload= -> None, an int, or a tuple of ints (one per item of a batch); a value outside [0, 65535] is a ValueError
     naming it, as the library's VITS_ERR_ARG does: here before any device work"""
@@ -570,6 +577,7 @@ class VitsLib:
         self.has_intonation = False
         self.has_watermark = False
         self.has_watermark_payload = False
+        self.has_watermark_scan = False
         if self.is_device:
             c_i16p = ctypes.POINTER(ctypes.c_int16)
             f("synthesize_pcm16").argtypes = [ctypes.c_void_p, c_i64p, c_i64p, ctypes.c_int32, ctypes.c_int32, c_f32p, c_i64p,
@@ -701,6 +709,13 @@ class VitsLib:
                                                       c_u32p, c_f32p]
                 f("op_watermark_read").argtypes = [ctypes.c_int, c_f32p, c_i64p, ctypes.c_int32, ctypes.c_int64, ctypes.c_uint32, c_f64p, c_i32p,
                                                    c_i32p, c_u32p, c_i32p, c_f64p, c_f64p]
+            # include/vits_watermark_scan.h: windowed detector scores (the localiser's door)
+            self.has_watermark_scan = self.has("op_watermark_scan")
+            if self.has_watermark_scan:
+                f("watermark_scan_windows").argtypes = [ctypes.c_int64, ctypes.c_int32]
+                f("watermark_scan_windows").restype = ctypes.c_int64
+                f("op_watermark_scan").argtypes = [ctypes.c_int, c_f32p, c_i64p, ctypes.c_int32, ctypes.c_int64, ctypes.c_uint32, ctypes.c_int32,
+                                                   ctypes.c_uint32, ctypes.c_int64, ctypes.POINTER(ctypes.c_double), c_i32p, c_i32p]
             if self.has("debug_clock_probe"):
                 f("debug_clock_probe").argtypes = [ctypes.c_int, ctypes.c_int32, ctypes.POINTER(ctypes.c_double), ctypes.c_int32]
 
@@ -1172,6 +1187,42 @@ class VitsLib:
                                                  _p(off, c_i32p), _p(rows, c_i32p), payload.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32)),
                                                  _p(valid, c_i32p), _p(z_all, c_f64p), _p(bit_z, c_f64p)))
         return z, off, rows, payload, valid, z_all, bit_z
+
+    # ---- watermark localisation (include/vits_watermark_scan.h) ----------------------
+    def _need_watermark_scan(self):
+        if not self.has_watermark_scan:
+            raise VitsError(4, "this backend has no watermark scan (include/vits_watermark_scan.h)")
+
+    def watermark_scan_windows(self, n_samples, span=0):
+        """vits_watermark_scan_windows: the most windows of `span` periods any offset of an item of n_samples holds"""
+        self._need_watermark_scan()
+        n = self._fn("watermark_scan_windows")(int(n_samples), int(span))
+        if n < 0:
+            self.check(1)  # VITS_ERR_ARG, named by vits_last_error
+        return int(n)
+
+    def op_watermark_scan(self, x, lengths, key, span=0, pilots=False, device=0, w_cap=None):
+        """vits_op_watermark_scan: x float32 [B, N], lengths [B], span 1 .. 8 (0 = 4) -> (z_scan float64 [B, 128, w_cap], the score of
+        window w of `span` pattern periods at offset index o, exactly 0 beyond windows[b, o]; first_period int32 [B, 128], p0;
+        windows int32 [B, 128], W_o).  pilots: score the pilot positions only (audio marked with a payload).  w_cap: default what the
+        longest item needs, at least 1.  vosk_tts_amd.watermark_scan turns the three into segments."""
+        self._need_watermark_scan()
+        x = _f32(x)
+        if x.ndim != 2:
+            raise ValueError("x must be [B, N]")
+        B, N = x.shape
+        lengths = _i64(lengths).reshape(-1)
+        if lengths.shape != (B,):
+            raise ValueError("lengths must be [B]")
+        if w_cap is None:
+            w_cap = max([1] + [self.watermark_scan_windows(n, span) for n in lengths if 0 <= n <= N])
+        w_cap = int(w_cap)
+        z = np.empty((B, WATERMARK_OFFSETS, max(w_cap, 0)), np.float64)
+        p0, wins = np.empty((B, WATERMARK_OFFSETS), np.int32), np.empty((B, WATERMARK_OFFSETS), np.int32)
+        self.check(self._fn("op_watermark_scan")(device, _p(x, c_f32p), _p(lengths, c_i64p), B, N, int(key) & 0xFFFFFFFF, int(span),
+                                                 WATERMARK_SCAN_PILOTS if pilots else 0, w_cap, _p(z, ctypes.POINTER(ctypes.c_double)),
+                                                 _p(p0, c_i32p), _p(wins, c_i32p)))
+        return z, p0, wins
 
     # ---- prosody controls (include/vits_prosody.h) ------------------------------
     def _need_prosody(self):

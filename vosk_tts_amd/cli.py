@@ -68,6 +68,13 @@ _OPTIONS = (
                                  help="instead of synthesising: read the mark of --watermark KEY (default: the voice's inference.watermark_key) "
                                       "in this 16-bit mono WAV and print detected, z, the offset in samples, the payload (null unless valid) "
                                       "and the weakest coded bit's score")),
+    (("--locate-watermark",), dict(type=str, default=None, metavar="FILE",
+                                   help="instead of synthesising: find where the mark of --watermark KEY (default: the voice's "
+                                        "inference.watermark_key) sits in this 16-bit mono WAV and print one line per marked segment, in seconds")),
+    (("--watermark-span",), dict(type=int, default=4, metavar="N",
+                                 help="with --locate-watermark: pattern periods per scored window, 1 to 8 (default 4; a period is 16384 samples)")),
+    (("--read-payload",), dict(action="store_true",
+                               help="with --locate-watermark: the audio was marked with --watermark-payload; also read each segment's payload")),
     (("--ssml",), dict(action="store_true", help="the input is an SSML document: speak, p, s, sub, break, prosody, mark")),
     (("--document",), dict(action="store_true",
                            help="the input is a document: split into sentences and paragraphs (blank lines), synthesised as one batch and "
@@ -119,6 +126,20 @@ def read_watermark(synth, path, key):
     return 0
 
 
+def locate_watermark(synth, path, key, span=4, payload=False):
+    """--locate-watermark: Synth.locate_watermark for a 16-bit mono WAV, one JSON line per segment, in seconds of the file's own rate"""
+    import wave
+
+    with wave.open(path, "r") as f:
+        rate = f.getframerate()
+    for s in synth.locate_watermark(_wav_pcm(path, "--locate-watermark"), key, span=span, payload=payload):
+        line = {"start_s": round(s.start / rate, 3), "end_s": round(s.end / rate, 3), "z": round(s.z, 3), "offset_samples": s.offset_samples}
+        if payload:
+            line["payload"] = s.payload
+        print(json.dumps(line))
+    return 0
+
+
 def build_parser():
     ap = argparse.ArgumentParser(prog="vosk-tts-amd", description="Text to speech on the MI355X-native VITS2 engine")
     for flags, kw in _OPTIONS:
@@ -152,7 +173,8 @@ def run(opts):
     read = getattr(opts, "read_watermark", None)
     if getattr(opts, "watermark_payload", None) is not None and getattr(opts, "watermark", None) is None:
         raise SystemExit("--watermark-payload needs --watermark KEY")
-    if not opts.input and not detect and not read:
+    locate = getattr(opts, "locate_watermark", None)
+    if not opts.input and not detect and not read and not locate:
         logging.info("Please specify input text or file")
         return 1
     from .synth import Synth
@@ -163,6 +185,9 @@ def run(opts):
         return detect_watermark(synth, detect, getattr(opts, "watermark", None))
     if read:
         return read_watermark(synth, read, getattr(opts, "watermark", None))
+    if locate:
+        return locate_watermark(synth, locate, getattr(opts, "watermark", None), getattr(opts, "watermark_span", 4),
+                                bool(getattr(opts, "read_payload", False)))
     wm = {} if getattr(opts, "watermark", None) is None else {"watermark": opts.watermark}
     if getattr(opts, "watermark_payload", None) is not None:
         wm["watermark_payload"] = opts.watermark_payload

@@ -24,9 +24,21 @@
 //                            above, T's own plane and one more, 2 x 1536 doubles = 24 KiB -- then 24 threads sum their bit's positions in
 //                            ascending id (all 24 lanes read the same address: a broadcast), one thread packs the word and checks the CRC
 // The <false> forms are the kernels as they were.
+// The scan (include/vits_watermark_scan.h), two launches: wm_lb_kernel as it is, then
+//   wm_scan_kernel<PILOT>    one workgroup per (item, offset index, chunk of WM_SCAN_CHUNK consecutive windows), the ownership of
+//                            wm_score_kernel: thread id owns the six (q, j) at id + 256 i.  It walks the chunk's periods in order: T of the
+//                            period's 16 rows to LDS (the plane and the argument above), D of its six pairs into the newest slot of a
+//                            ring of the last 8 periods, the window's ascending sum over the last S slots, the two sums of the score
+//                            through the fixed LDS tree of wm_score_kernel.  The ring is registers, 8 x 6 doubles = 96 VGPRs: it is
+//                            shifted by one slot per period with every index a compile-time constant (42 register moves next to 6 LDS
+//                            rounds), because a slot index that rotates at run time would send the array to scratch, and an LDS ring
+//                            would cost 8 x 12 KiB per workgroup and an LDS read per term where the value is already in the thread
+//                            that owns it.  Chunks overlap by S - 1 periods (the first S - 1 periods of a chunk fill the ring and
+//                            score nothing), so 60 s of audio are 128 x 10 workgroups and not 128 serial ones; a window is the written
+//                            sum of its own S periods, so its bits do not depend on the chunking.  Gp is never stored.
 // Nothing waits between workgroups; there are no atomics.
 #pragma once
-#include "../../include/vits_watermark_payload.h"
+#include "../../include/vits_watermark_scan.h"
 
 #define WM_N VITS_WATERMARK_FRAME
 #define WM_M (WM_N / 2)
@@ -38,6 +50,8 @@
 #define WM_Q VITS_WATERMARK_ROWS
 #define WM_DH VITS_WATERMARK_DETECT_HOP
 #define WM_SCORE_THREADS 256
+#define WM_SCAN_SPAN VITS_WATERMARK_SCAN_MAX_SPAN
+#define WM_SCAN_CHUNK 8  // windows per workgroup of wm_scan_kernel
 static_assert(WM_N <= SF_N && (1 << WM_LOG2M) == WM_M, "the watermark runs on the frame transform of stft.hip.h");
 static_assert((WM_HI - WM_LO) == 4 * WM_G && (WM_Q * WM_G) % WM_SCORE_THREADS == 0, "96 groups of 4 bins; whole (q, j) per thread");
 
@@ -197,7 +211,7 @@ __global__ __launch_bounds__(64 * SF_FPB) void wm_lb_kernel(const float* __restr
 constexpr int WM_PER = WM_Q * WM_G / WM_SCORE_THREADS;  // (q, j) pairs per thread: 6, at the linear ids tid + i * WM_SCORE_THREADS
 // the complete rows [r0, r1] of offset index o of an item of F hop-128 frames, and where its pattern starts
 struct WmRows { int g0; long long pbase, r0, r1, rows; };
-__device__ __forceinline__ WmRows wm_rows_of(long long len, int o) {
+__host__ __device__ __forceinline__ WmRows wm_rows_of(long long len, int o) {
   WmRows R;
   const long long F = len >= WM_M + 1 ? 1 + len / WM_DH : 0;
   R.g0 = o & 1;
@@ -264,6 +278,86 @@ __global__ __launch_bounds__(WM_SCORE_THREADS) void wm_score_kernel(const float*
     const double d = red[1][0];
     z_all[(long long)b * VITS_WATERMARK_OFFSETS + o] = (R.rows > 0 && d > 0.0) ? red[0][0] / sqrt(d) : 0.0;
     rows_all[(long long)b * VITS_WATERMARK_OFFSETS + o] = (int)R.rows;
+  }
+}
+
+// include/vits_watermark_scan.h, S2 and S3: the first complete period of the rows R and the windows of span S they hold
+struct WmPeriods { long long p0, W; };
+__host__ __device__ __forceinline__ WmPeriods wm_periods_of(const WmRows& R, int S) {
+  WmPeriods P;
+  P.p0 = (R.r0 + WM_Q - 1) / WM_Q;                // (r0 >= 0, r1 >= -1: the divisions round as the definition's ceil and floor)
+  const long long p1 = (R.r1 + 1) / WM_Q - 1;
+  const long long n = p1 - P.p0 + 2 - S;
+  P.W = n > 0 ? n : 0;
+  return P;
+}
+
+// z_scan[(b * 128 + o) * w_cap + w] of the windows w in [blockIdx.y * WM_SCAN_CHUNK, +WM_SCAN_CHUNK) below W_o, of offset index
+// o = blockIdx.x of item b = blockIdx.z, from Lb; first_period and windows [b * 128 + o] by the workgroup of chunk 0.  S in [1, 8].
+// z_scan arrives zeroed: what lies at and beyond W_o is not written.  PILOT: the two sums over the pilot positions only.
+template <bool PILOT>
+__global__ __launch_bounds__(WM_SCORE_THREADS) void wm_scan_kernel(const float* __restrict__ Lb, long long lb_bstride, const int* __restrict__ lens,
+                                                                  uint32_t mk, int S, long long w_cap, double* __restrict__ z_scan,
+                                                                  int* __restrict__ first_period, int* __restrict__ windows) {
+  __shared__ double T[WM_Q * WM_G];
+  __shared__ double red[2][WM_SCORE_THREADS];
+  const int o = blockIdx.x, b = blockIdx.z, tid = threadIdx.x;
+  const WmRows R = wm_rows_of(lens[b], o);
+  const WmPeriods P = wm_periods_of(R, S);
+  const long long bo = (long long)b * VITS_WATERMARK_OFFSETS + o;
+  if (blockIdx.y == 0 && tid == 0) { first_period[bo] = (int)P.p0; windows[bo] = (int)P.W; }
+  const long long w0 = (long long)blockIdx.y * WM_SCAN_CHUNK;
+  const long long w1 = P.W < w0 + WM_SCAN_CHUNK ? P.W : w0 + WM_SCAN_CHUNK;  // this workgroup's windows: [w0, w1)
+  if (w1 <= w0) return;                                                       // uniform
+  const float* lb = Lb + (long long)b * lb_bstride;
+  double ring[WM_SCAN_SPAN][WM_PER];  // D of the thread's pairs in the last 8 periods, the newest in slot 7; static indices only
+#pragma unroll
+  for (int k = 0; k < WM_SCAN_SPAN; ++k)
+#pragma unroll
+    for (int i = 0; i < WM_PER; ++i) ring[k][i] = 0.0;
+  for (long long p = P.p0 + w0; p < P.p0 + w1 + S - 1; ++p) {  // every one a complete period: its 16 rows lie in [r0, r1]
+#pragma unroll
+    for (int i = 0; i < WM_PER; ++i) {
+      const int id = tid + i * WM_SCORE_THREADS, q = id / WM_G, j = id - q * WM_G;
+      const long long gf = R.g0 + 2 * (4 * (WM_Q * p + q) - R.pbase);  // the row's first frame; its four are 2 apart
+      const float* f = lb + gf * WM_G + j;
+      T[id] = (((double)f[0] + (double)f[2 * WM_G]) + (double)f[4 * WM_G] + (double)f[6 * WM_G]) * 0.25;
+    }
+    __syncthreads();
+#pragma unroll
+    for (int i = 0; i < WM_PER; ++i) {
+      const int id = tid + i * WM_SCORE_THREADS, j = id % WM_G;
+#pragma unroll
+      for (int k = 0; k + 1 < WM_SCAN_SPAN; ++k) ring[k][i] = ring[k + 1][i];
+      ring[WM_SCAN_SPAN - 1][i] = (j >= 1 && j <= WM_G - 2) ? T[id] - 0.5 * (T[id - 1] + T[id + 1]) : 0.0;
+    }
+    const long long w = p - (S - 1) - P.p0;  // the window this period completes
+    if (w >= w0) {                           // uniform
+      double num = 0.0, den = 0.0;
+#pragma unroll
+      for (int i = 0; i < WM_PER; ++i) {
+        const int id = tid + i * WM_SCORE_THREADS, q = id / WM_G, j = id - q * WM_G;
+        if (PILOT && !wm_pilot(q, j)) continue;
+        double G = 0.0;  // ((Gp[p0 + w] + Gp[p0 + w + 1]) + ...): slots 8 - S .. 7, ascending
+#pragma unroll
+        for (int k = 0; k < WM_SCAN_SPAN; ++k)
+          if (k >= WM_SCAN_SPAN - S) G = k == WM_SCAN_SPAN - S ? ring[k][i] : G + ring[k][i];
+        num += wm_chip(mk, q, j) ? G : -G;
+        den += G * G;
+      }
+      red[0][tid] = num;
+      red[1][tid] = den;
+      __syncthreads();
+      for (int s = WM_SCORE_THREADS / 2; s > 0; s >>= 1) {
+        if (tid < s) { red[0][tid] += red[0][tid + s]; red[1][tid] += red[1][tid + s]; }
+        __syncthreads();
+      }
+      if (tid == 0) {
+        const double d = red[1][0];
+        z_scan[bo * w_cap + w] = d > 0.0 ? red[0][0] / sqrt(d) : 0.0;
+      }
+    }
+    __syncthreads();  // T and red are free for the next period
   }
 }
 
@@ -482,4 +576,70 @@ int vits_op_watermark_read(int device, const float* x, const int64_t* lengths, i
                            int32_t* offset, int32_t* rows, uint32_t* payload, int32_t* valid, double* z_all, double* bit_z) {
   if (!payload || !valid) return fail(VITS_ERR_ARG, "watermark read: bad argument");
   return wm_detect_op("watermark read", device, x, lengths, B, N, key, z, offset, rows, z_all, payload, valid, bit_z);
+}
+
+// ---- the scan (include/vits_watermark_scan.h) ---------------------------------------------------------------------------------
+static int wm_span_arg(int32_t span, int* S) {
+  if (span < 0 || span > VITS_WATERMARK_SCAN_MAX_SPAN)
+    return fail(VITS_ERR_ARG, "watermark scan: span %d outside [1, %d] (0 = the default, %d)", (int)span, VITS_WATERMARK_SCAN_MAX_SPAN,
+                VITS_WATERMARK_SCAN_DEFAULT_SPAN);
+  *S = span ? span : VITS_WATERMARK_SCAN_DEFAULT_SPAN;
+  return VITS_OK;
+}
+// max_o W_o of an item of len samples
+static long long wm_scan_windows(long long len, int S) {
+  long long W = 0;
+  for (int o = 0; o < VITS_WATERMARK_OFFSETS; ++o) W = std::max(W, wm_periods_of(wm_rows_of(len, o), S).W);
+  return W;
+}
+
+int64_t vits_watermark_scan_windows(int64_t n_samples, int32_t span) {
+  int S = 0;
+  if (wm_span_arg(span, &S) != VITS_OK) return -1;
+  if (n_samples < 0) {
+    fail(VITS_ERR_ARG, "watermark scan: %lld samples", (long long)n_samples);
+    return -1;
+  }
+  return wm_scan_windows(n_samples, S);
+}
+
+int vits_op_watermark_scan(int device, const float* x, const int64_t* lengths, int32_t B, int64_t N, uint32_t key, int32_t span,
+                           uint32_t flags, int64_t w_cap, double* z_scan, int32_t* first_period, int32_t* windows) {
+  const char* what = "watermark scan";
+  int S = 0;
+  TRY(wm_span_arg(span, &S));
+  if (flags & ~VITS_WATERMARK_SCAN_PILOTS) return fail(VITS_ERR_ARG, "%s: unknown flags 0x%x", what, flags & ~VITS_WATERMARK_SCAN_PILOTS);
+  std::vector<int> len32;
+  TRY(op_items_check(what, x, lengths, B, N, &len32));
+  if (!z_scan || !first_period || !windows || w_cap < 0) return fail(VITS_ERR_ARG, "%s: bad argument", what);
+  long long need = 0;
+  for (int b = 0; b < B; ++b) need = std::max(need, wm_scan_windows(len32[b], S));
+  if (w_cap < need) return fail(VITS_ERR_ARG, "%s: w_cap %lld below the %lld windows of the longest item", what, (long long)w_cap, need);
+  const StftTab* T = nullptr;
+  TRY(stft_tab_get(device, WM_N, &T));
+  OpDoor d(what, device);
+  const long long Fmax = N >= WM_M + 1 ? 1 + N / WM_DH : 0;
+  const long long lbs = (Fmax ? Fmax : 1) * WM_G;
+  const size_t no = (size_t)B * VITS_WATERMARK_OFFSETS, nz = no * (size_t)w_cap;
+  float* dx = d.up(x, (size_t)B * N);
+  int* dl = d.up(len32.data(), B);
+  float* dlb = d.dev<float>((size_t)B * lbs);
+  double* dz = d.out<double>(nz ? nz : 1, 0);  // exactly 0 at and beyond W_o
+  int* dp0 = d.out<int>(no);
+  int* dw = d.out<int>(no);
+  if (d.ok()) {
+    const uint32_t mk = wm_mix(key);
+    if (Fmax > 0)
+      hipLaunchKernelGGL(wm_lb_kernel, dim3((unsigned)cdiv((int)Fmax, SF_FPB), B), dim3(64 * SF_FPB), 0, nullptr, dx, N, dl, T->d_win, T->d_tw, dlb, lbs);
+    const dim3 grid(VITS_WATERMARK_OFFSETS, (unsigned)std::max(1LL, (need + WM_SCAN_CHUNK - 1) / WM_SCAN_CHUNK), B);
+    if (flags & VITS_WATERMARK_SCAN_PILOTS)
+      hipLaunchKernelGGL(wm_scan_kernel<true>, grid, dim3(WM_SCORE_THREADS), 0, nullptr, dlb, lbs, dl, mk, S, (long long)w_cap, dz, dp0, dw);
+    else
+      hipLaunchKernelGGL(wm_scan_kernel<false>, grid, dim3(WM_SCORE_THREADS), 0, nullptr, dlb, lbs, dl, mk, S, (long long)w_cap, dz, dp0, dw);
+  }
+  d.finish();
+  if (nz) d.down(z_scan, dz, nz);
+  d.down(first_period, dp0, no);
+  d.down(windows, dw, no);
+  return d.rc();
 }

@@ -372,6 +372,37 @@ class Synth:
         z, off, _, payload, valid, _, bit_z = lib.op_watermark_read(x, [x.shape[1]], k, device=dev)
         return bool(z[0] >= WATERMARK_THRESHOLD), float(z[0]), int(off[0]), int(payload[0]) if valid[0] else None, bit_z[0]
 
+    def locate_watermark(self, audio, key=None, span=4, payload=False):
+        """[WatermarkSegment] (vosk_tts_amd/watermark_scan.py), sorted by start: where in a recording the mark of `key` (default: the
+        config key inference.watermark_key) sits, for audio in which marked speech stands between other speech or several marked
+        pieces are joined, where the whole-item score of detect_watermark dilutes.  The engine scores every window of `span` pattern
+        periods (0.74 s each at 22050 Hz; 1 to 8) at every offset (vits_op_watermark_scan, include/vits_watermark_scan.h); the windows
+        over the derived threshold t(Wmax) -- the detector's false-alarm bound of 1.9e-6 per item, spread over all windows -- are
+        grouped into segments with start, end (samples; each good to about a span), z and offset_samples.  payload=True: for audio
+        marked with a payload -- the scan scores the pilot positions only, each segment's crop goes through read_watermark, and the
+        segment carries payload (None unless that read is valid) and bit_z.  audio as for detect_watermark; audio shorter than span
+        periods has no window and no segment."""
+        from .watermark_scan import segments, span_arg
+
+        k = self._watermark_key(key)
+        S = span_arg(span)
+        a = np.asarray(audio)
+        x = a.astype(np.float32) / np.float32(32767.0) if a.dtype == np.int16 else a.astype(np.float32)
+        x = x.reshape(1, -1)
+        sess = self.model.onnx
+        lib = getattr(sess, "_lib", None)
+        if lib is None or not getattr(lib, "has_watermark_scan", False):
+            raise NotImplementedError("this session type has no watermark scan (include/vits_watermark_scan.h)")
+        if x.shape[1] == 0:
+            return []
+        dev = getattr(getattr(sess, "_vocoder", None) or getattr(sess, "_model", None), "device", 0)
+        z_scan, first, wins = lib.op_watermark_scan(x, [x.shape[1]], k, span=S, pilots=bool(payload), device=dev)
+        segs = segments(z_scan[0], first[0], wins[0], S, x.shape[1])
+        if payload:
+            for s in segs:
+                _, _, _, s.payload, s.bit_z = self.read_watermark(x[0, s.start:s.end], k)
+        return segs
+
     def measure_pitch(self, audio, rate=None):
         """(hz, median_hz) of one utterance: hz float32 [1 + n // 256], the F0 of every analysis frame of include/vits_intonation.h (hop
         256, 0 where unvoiced) as the engine's own tracker finds it (vits_op_f0_track, the track `pitch_range` scales), and the median of
